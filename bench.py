@@ -24,6 +24,12 @@ shadow rays per hit, L reflection rays per reflective hit) - the number to hold 
 
 At N = 1 rank 0 also renders a bounded band sample of the same frame with the CPU oracle (`cpu_baseline`) and the line reports
 the parity of the timed GPU frame against it (`parity`).  Rank 0 prints ONE JSON line.
+
+--dump-outputs DIR writes what the last timed step computed - the frame a caller of the timed path fetches, gathered over the
+ranks - as DIR/frame.npy (float64, res_v x res_h x 3).  A frame over 64 MB is written as a fixed sample of its pixels instead:
+DIR/frame_sample.npy (float64, n x 3) and DIR/frame_sample_index.npy (float64 flat pixel indices), drawn with a fixed seed.  Scene,
+jitter pattern and seed are fixed, so the same arguments give the same inputs on every run and two builds compare file for file.
+A DIR that bench.py creates holds a .gitignore of its own.
 """
 import argparse
 import contextlib
@@ -35,10 +41,13 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-HBM_PEAK_GBPS = 8000.0            # MI355X HBM3E peak, /opt/skills/guides/MI355X_MICROARCH.md
+HBM_PEAK_GBPS = 8000.0            # MI355X HBM3E peak (AMD Instinct MI355X specification)
 FP64_VECTOR_PEAK_TFLOPS = 78.6    # MI355X vector FP64; the path is FP64 VALU work, no MFMA
 SURVEY_BYTES_PER_RAY = 192        # RayRec 80 B + HitRec 16 B, each written once and read once
 PIXEL_BYTES = 24                  # one FP64 RGB store per pixel
+DUMP_MAX_BYTES = 64 << 20         # --dump-outputs: bytes written at most
+DUMP_SAMPLE_PIXELS = 1 << 20      # pixels of the fixed sample written when the whole frame would exceed DUMP_MAX_BYTES
+DUMP_SAMPLE_SEED = 0
 
 
 @contextlib.contextmanager
@@ -74,7 +83,13 @@ def main():
     ap.add_argument("--prewarm-ms", type=float, default=200.0, help="untimed frames queued for this long before the W warm-up steps of every workload (clock ramp); 0 = none")
     ap.add_argument("--no-boundary", action="store_true", help="skip the boundary legs (frames copied to the host): the counter passes of the profile scripts want a known number of frames")
     ap.add_argument("--blocking", action="store_true", help="render the timed frames one synchronous ft_render at a time instead of queuing them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the frame the last of them computed to DIR as .npy (float64; see the module docstring)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -183,12 +198,15 @@ def main():
                 k_launch[k] = v["launches"]
         barrier_sync()
         wall = time.perf_counter() - t0
+        frame = None
+        if args.dump_outputs and name == primary:                  # the last timed step's frame, still in HBM: fetched after the timed region
+            frame = ctx.fetch_frame(np.zeros((res_v, res_h, 3)))
         kernel_ms = sum(k_times.values())
         (wall_max, kernel_ms_max), (traced, ref_equiv, culled, listed) = reduce_max_sum(
             [wall, kernel_ms], [float(st["rays_traced"]), float(st["rays_reference_equivalent"]), float(st["rays_primary_culled"]), float(st["rays_primary"])])
         return {"name": name, "res": (res_h, res_v), "spp": spp, "scaling": scaling, "steps": steps, "warmup": warmup, "bands": bands, "jitter": jitter, "prewarm_frames": prewarm_frames,
                 "wall_max": wall_max, "kernel_ms_max": kernel_ms_max, "rays_traced_frame": traced, "rays_ref_equiv_frame": ref_equiv,
-                "rays_culled_frame": culled, "rays_listed_frame": listed, "st": st, "k_times": k_times, "k_launch": k_launch}
+                "rays_culled_frame": culled, "rays_listed_frame": listed, "st": st, "k_times": k_times, "k_launch": k_launch, "frame": frame}
 
     def summary(r):
         ms = r["wall_max"] / r["steps"] * 1e3
@@ -206,6 +224,11 @@ def main():
     P = results[primary]
     res_h, res_v = P["res"]
     spp = P["spp"]
+    dumped = None
+    if args.dump_outputs:
+        timed_frame = tiling.gather_frame(P["frame"], res_h, res_v, rank, world, group=host_group)
+        if rank == 0:
+            dumped = dump_outputs(args.dump_outputs, timed_frame)
 
     # The same frames with the frame pipeline switched off (every kernel alone on the device, one stream): what a launch of each kernel
     # takes when nothing runs beside it - the figure a serial rocprofv3 pass shows (profiles/*_serial_kernel_stats.csv).  Not the timed region.
@@ -367,6 +390,8 @@ def main():
                                "shadow_primary_rank0": int(st["rays_shadow_primary"]), "reflect_primary_rank0": int(st["rays_reflect_primary"])},
             "workloads": {k: summary(r) for k, r in results.items()},
         }
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"], out["parity"] = cpu_baseline(scene, res_h, res_v, spp, P["jitter"], args.cpu_baseline_seconds, full)
         print(json.dumps(out), flush=True)
@@ -374,6 +399,29 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     ctx.close()
+
+
+def dump_outputs(out_dir, frame):
+    """--dump-outputs: the frame of the last timed step as float64 .npy, whole if it fits in DUMP_MAX_BYTES, else a fixed sample of pixels."""
+    import numpy as np
+    if not os.path.isdir(out_dir):
+        os.makedirs(out_dir)
+        with open(os.path.join(out_dir, ".gitignore"), "w") as f:              # a directory of its own making stays out of git, wherever it is
+            f.write("# written by bench.py --dump-outputs\n*\n")
+    frame = np.ascontiguousarray(frame, dtype=np.float64)
+    if frame.nbytes <= DUMP_MAX_BYTES:
+        arrays = {"frame": frame}
+    else:
+        pixels = frame.reshape(-1, 3)
+        rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+        index = np.sort(rng.choice(pixels.shape[0], size=min(DUMP_SAMPLE_PIXELS, pixels.shape[0]), replace=False))
+        arrays = {"frame_sample": pixels[index], "frame_sample_index": index.astype(np.float64)}
+    for name in {"frame", "frame_sample", "frame_sample_index"} - set(arrays):   # an earlier run's other form must not pass for this run's
+        with contextlib.suppress(FileNotFoundError):
+            os.remove(os.path.join(out_dir, name + ".npy"))
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "files": {name + ".npy": list(a.shape) for name, a in arrays.items()}, "dtype": "float64"}
 
 
 def effective_cpus():

@@ -1,6 +1,6 @@
 // ft_capi.cpp — the C ABI of libfunctracer_hip.so (include/functracer_hip.h): context, scene
 // builder, HBM residency of the flattened scene and the per-frame wavefront pipeline driver.
-// Reference citations are relative to /root/reference/FuncTracer/.
+// Reference citations are relative to FuncTracer/ of the reference (antonburger/FuncTracer).
 #include <hip/hip_runtime.h>
 
 #include <chrono>

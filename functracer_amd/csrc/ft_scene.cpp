@@ -1,5 +1,5 @@
 // ft_scene.cpp — scene-graph flattening and host-side BSP build for the HIP path.
-// Reference citations are relative to /root/reference/FuncTracer/.
+// Reference citations are relative to FuncTracer/ of the reference (antonburger/FuncTracer).
 #include "ft_scene.h"
 
 #include <algorithm>

@@ -1,5 +1,5 @@
 // host_api.cpp — C ABI over the host-side scene model: parse, lower through a builder table,
-// jitter pattern, PNG output.  Reference citations are relative to /root/reference/FuncTracer/.
+// jitter pattern, PNG output.  Reference citations are relative to FuncTracer/ of the reference (antonburger/FuncTracer).
 #include "host_api.h"
 
 #include <cstdio>

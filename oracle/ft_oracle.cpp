@@ -1,6 +1,6 @@
 // ft_oracle.cpp — CPU restatement of FuncTracer's render loop.  TEST INFRASTRUCTURE ONLY
 // (see ft_oracle.h).  Every function cites the reference file:line it follows; citations are
-// relative to /root/reference/FuncTracer/.  The structure deliberately mirrors the reference:
+// relative to FuncTracer/ of the reference (antonburger/FuncTracer).  The structure deliberately mirrors the reference:
 // a Geometry is "ray -> all intersections along the infinite line" (Ray.fs:31), transforms are
 // applied per nesting level with 4x4 matrices (Transform.fs:80-87), CSG merges stable-sorted hit
 // lists (Csg.fs:74-94), closest = stable sort + skip negatives + head (Scene.fs:112-116) and

@@ -116,13 +116,17 @@ def test_two_rank_tiled_frame_on_the_hip_path(tmp_path, hip):
 
 @pytest.mark.gpu
 @pytest.mark.timeout(900)
-def test_bench_two_ranks_as_the_driver_launches_it():
+def test_bench_two_ranks_as_the_driver_launches_it(tmp_path, hip):
     """python -m torch.distributed.run --nproc-per-node 2 bench.py --gpus 2: one JSON line from rank 0, the timed workload is the
-    strong-scaled config 5 frame, and every workload's ray count is the single-context count (the bands partition the frame)."""
+    strong-scaled config 5 frame, and every workload's ray count is the single-context count (the bands partition the frame).
+    --dump-outputs: the sample of the timed frame, gathered over both ranks, is that of the single-context frame."""
     import json
     import subprocess
+
+    import functracer_amd as ft
+    dump = tmp_path / "dump"
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(H.ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--side-steps", "2"]
+           os.path.join(H.ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--side-steps", "2", "--dump-outputs", str(dump)]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=800, cwd=H.ROOT)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
@@ -130,6 +134,12 @@ def test_bench_two_ranks_as_the_driver_launches_it():
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and "3840x2160x64spp" in d["config"]["workload"] and d["value"] > 0
     assert set(d["workloads"]) == {"config5", "headline", "weak"}
+    index = np.load(dump / "frame_sample_index.npy").astype(np.int64)
+    scene = ft.parse_scene_file(H.scene_path("bunny"))
+    scene.lower(hip)
+    full, _ = hip.render(scene.camera, 3840, 2160, 64, ft.jitter_pattern(64))
+    assert np.array_equal(np.load(dump / "frame_sample.npy"), full.reshape(-1, 3)[index])
+    del full
     one = subprocess.run([sys.executable, os.path.join(H.ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--side-steps", "1", "--no-cpu-baseline"],
                          capture_output=True, text=True, timeout=800, cwd=H.ROOT)
     assert one.returncode == 0, one.stderr[-2000:]

@@ -10,7 +10,7 @@ tests/golden/known_answers.json under "hand_derived_round3":
   a2   blendPixels = mean of the samples in sample order, and CornerSampling's four-corner average              Image.fs:83-89, 112-116, 125-145
 
 Nothing here runs the oracle, the device path or the reference: every value is a closed form worked out from the cited lines of
-/root/reference/FuncTracer/*.fs and evaluated with plain Python floats (the seeded stream is re-implemented here from its written
+FuncTracer/*.fs of the reference and evaluated with plain Python floats (the seeded stream is re-implemented here from its written
 definition, DESIGN.md 2: a third, independent implementation).  tests/test_oracle_golden.py checks the oracle against them on the
 CPU, tests/test_gpu_parity.py the device (-m gpu).
 """

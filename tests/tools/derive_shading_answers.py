@@ -3,7 +3,7 @@
 tests/golden/known_answers.json under "hand_derived_shading" and "hand_derived_csg".
 
 Nothing here runs the oracle, the device path or the reference: every expected value is a closed form worked out on paper from
-the cited lines of /root/reference/FuncTracer/*.fs and evaluated below with plain Python floats.  The tests
+the cited lines of FuncTracer/*.fs of the reference and evaluated below with plain Python floats.  The tests
 (tests/test_oracle_golden.py on the CPU, tests/test_gpu_parity.py on the device) build each scene through the scene-builder API,
 shade the listed rays with getColourForRay (Shading.fs:131-139) and compare.
 

@@ -4,7 +4,7 @@ import json
 import os
 import sys
 
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import functracer_amd as ft
 
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

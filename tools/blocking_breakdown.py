@@ -1,6 +1,6 @@
 import os, sys, time
 import numpy as np
-R = os.environ.get("GRAFT_REPO_ROOT", "/root/repo"); sys.path.insert(0, R)
+R = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, R)
 import functracer_amd as ft
 ctx = ft.Context(0)
 for name, spp in (("bunny", 16), ("sample-det", 16), ("night-house-det", 16)):

@@ -1,6 +1,6 @@
 """Unclassified frames: one chunk (a simple, pipelined frame) against two.  python tools/chunk_ab.py   (GPU box)"""
 import os, sys, time
-R = os.environ.get("GRAFT_REPO_ROOT", "/root/repo"); sys.path.insert(0, R)
+R = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, R)
 import functracer_amd as ft
 ctx = ft.Context(0)
 for name, W, H, SPP in (("night-house-det", 1920, 1080, 16), ("night-house", 1920, 1080, 16), ("sample-det", 1920, 1080, 16), ("hollow-sphere", 1920, 1080, 16)):

@@ -1,8 +1,8 @@
 import ctypes as C, os, sys
 import numpy as np
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import functracer_amd as ft
-R = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ctx = ft.Context(0)
 p = ft.parse_scene_file(os.path.join(R, "scenes", "bunny.scene")); p.lower(ctx)
 jit = ft.jitter_pattern(16)

@@ -1,6 +1,6 @@
 """What one ft_render_enqueue costs the HOST (the first four calls from an idle context never wait for a slot): python tools/enqueue_host_cost.py"""
 import os, sys, time
-R = os.environ.get("GRAFT_REPO_ROOT", "/root/repo"); sys.path.insert(0, R)
+R = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, R)
 import functracer_amd as ft
 ctx = ft.Context(0)
 for name, spp in (("bunny", 16), ("hollow-sphere", 1), ("hollow-sphere", 16), ("sample-det", 16)):

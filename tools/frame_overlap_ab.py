@@ -1,9 +1,9 @@
 """A/B of the per-frame overheads on the headline (GPU box): queued frames, wall ms per frame for every setting of
 classify_ahead / zero_fill_skip / resolve_blocks.  python tools/frame_overlap_ab.py"""
 import os, sys, time
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import functracer_amd as ft
-ctx = ft.Context(0); p = ft.parse_scene_file(os.path.join(os.environ.get("GRAFT_REPO_ROOT", "/root/repo"), "scenes/bunny.scene")); p.lower(ctx); jit = ft.jitter_pattern(16)
+ctx = ft.Context(0); p = ft.parse_scene_file(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "scenes/bunny.scene")); p.lower(ctx); jit = ft.jitter_pattern(16)
 for ahead, skip, rb, aside, after in ((0, 0, 0, 0, 0), (1, 1, 0, 0, 1), (1, 1, 0, 1, 0), (1, 1, 0, 1, 1), (1, 1, 2, 1, 0), (0, 1, 0, 1, 0), (1, 0, 0, 1, 0)):
     ctx.set_option("classify_ahead", ahead); ctx.set_option("zero_fill_skip", skip); ctx.set_option("resolve_blocks", rb)
     ctx.set_option("resolve_aside", aside); ctx.set_option("classify_after_trace", after)

@@ -1,9 +1,9 @@
 """Diagnostic build (make item-counts): top-level items a wave's query evaluates, per kind of query.  GPU box:
 FT_HIP_LIB=build/libfunctracer_hip_counts.so python tools/item_counts.py"""
 import ctypes as C, os, sys
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import functracer_amd as ft
-R = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 lib = ft.hip_lib()
 ctx = ft.Context(0)
 buf = (C.c_ulonglong * 48)()

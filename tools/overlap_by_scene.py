@@ -1,7 +1,7 @@
 """Is the frame pipeline (classify_ahead / resolve_aside) worth it for a frame of this size?  Queued frames, wall ms per frame with each part
 on / off, per scene and size.  python tools/overlap_by_scene.py [out.json]   (GPU box)"""
 import json, os, sys, time
-R = os.environ.get("GRAFT_REPO_ROOT", os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, R)
 import functracer_amd as ft
 CASES = [("bunny", 1920, 1080, 16), ("bunny", 1920, 1080, 4), ("bunny", 3840, 2160, 64), ("bunny", 3840, 2160, 16), ("hollow-sphere", 1920, 1080, 1), ("hollow-sphere", 1920, 1080, 16),

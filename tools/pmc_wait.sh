@@ -3,7 +3,7 @@
 # usage: tools/pmc_wait.sh <scene> <spp> <tag>  -> gpurun_out/<tag>_wait.txt
 set -e
 scene=$1; spp=$2; tag=$3
-cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp
+cd "$(dirname "$0")/.."; export TMPDIR=/tmp
 B="python3 bench.py --scene $scene --spp $spp --res 1920 1080 --steps 5 --warmup 1 --no-cpu-baseline --side-steps 0 --prewarm-ms 0"
 rocprofv3 --kernel-trace --output-format csv --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_LDS -d gpurun_out/${tag}_wa -- $B > /dev/null 2>&1
 rocprofv3 --kernel-trace --output-format csv --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_DCACHE_REQ SQC_DCACHE_HITS SQC_DCACHE_MISSES SQ_IFETCH SQ_ACTIVE_INST_VMEM -d gpurun_out/${tag}_wb -- $B > /dev/null 2>&1 || echo "pass b failed"

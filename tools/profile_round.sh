@@ -3,7 +3,7 @@
 # (two PMC passes).  usage: tools/profile_round.sh <tag>   -> gpurun_out/<tag>_*  (copy what should be judged into profiles/)
 set -e
 tag=$1
-cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp
+cd "$(dirname "$0")/.."; export TMPDIR=/tmp
 B="python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --side-steps 0"
 P="$B --prewarm-ms 0 --no-boundary --no-alone"   # the counter passes: a known number of frames (3 + 20 + 1, all FP64), no clock pre-warm, Colour.Zero written every frame
 # the two traffic passes run with FT_OPTS=zero_fill_skip=0: k_resolve then writes every pixel every frame and its bytes are known exactly (the FETCH_SIZE calibration rests on them)

@@ -4,7 +4,7 @@
 # usage: tools/profile_scene.sh <tag> <scene> <spp>   -> gpurun_out/<tag>_<scene>x<spp>_*  (copy what should be judged into profiles/)
 set -e
 tag=$1; scene=$2; spp=$3
-cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp
+cd "$(dirname "$0")/.."; export TMPDIR=/tmp
 T=gpurun_out/${tag}_${scene}x${spp}
 B="python3 bench.py --scene $scene --spp $spp --res 1920 1080 --steps 20 --warmup 3 --no-cpu-baseline --side-steps 0"
 P="$B --prewarm-ms 0 --no-boundary --no-alone"   # the counter passes: a known number of frames (3 + 20 + 1, all FP64), no clock pre-warm, Colour.Zero written every frame

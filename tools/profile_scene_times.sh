@@ -3,7 +3,7 @@
 # usage: tools/profile_scene_times.sh <tag> <scene> <spp>
 set -e
 tag=$1; scene=$2; spp=$3
-cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp
+cd "$(dirname "$0")/.."; export TMPDIR=/tmp
 T=gpurun_out/${tag}_${scene}x${spp}
 B="python3 bench.py --scene $scene --spp $spp --res 1920 1080 --steps 20 --warmup 3 --no-cpu-baseline --side-steps 0"
 SERIAL=mains=1,classify_ahead=0,resolve_aside=0

@@ -1,7 +1,7 @@
 import os, sys
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import functracer_amd as ft
-R = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ctx = ft.Context(0)
 out = []
 for name, spp in (("hollow-sphere", 1), ("hollow-sphere", 16), ("night-house-det", 16), ("sample-det", 16)):

@@ -1,6 +1,6 @@
 """A rank's share of config 5 (3840x2160x64 over N ranks), queued frames: ms per frame for a few option settings.  python tools/rank_share_ab.py   (GPU box)"""
 import os, sys, time
-R = os.environ.get("GRAFT_REPO_ROOT", "/root/repo"); sys.path.insert(0, R)
+R = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, R)
 import functracer_amd as ft
 from functracer_amd import tiling
 ctx = ft.Context(0)

@@ -1,6 +1,6 @@
 """Headline frame period against the workgroup slots k_primary leaves free (option primary_reserve): python tools/reserve_sweep.py   (GPU box)"""
 import os, sys, time
-R = os.environ.get("GRAFT_REPO_ROOT", "/root/repo"); sys.path.insert(0, R)
+R = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, R)
 import functracer_amd as ft
 ctx = ft.Context(0)
 for name, W, H, SPP in (("bunny", 1920, 1080, 16), ("bunny", 1920, 1080, 4), ("bunny-bsp12", 1920, 1080, 16), ("moon", 1920, 1080, 16)):

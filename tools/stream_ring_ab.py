@@ -1,7 +1,7 @@
 """ft_render_enqueue_into, FP64 frames: ms per frame against the number of page-locked host buffers in the ring and the main streams.  python tools/stream_ring_ab.py"""
 import os, sys, time
 import numpy as np
-R = os.environ.get("GRAFT_REPO_ROOT", "/root/repo"); sys.path.insert(0, R)
+R = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, R)
 import functracer_amd as ft
 ctx = ft.Context(0)
 p = ft.parse_scene_file(os.path.join(R, "scenes/bunny.scene")); p.lower(ctx); jit = ft.jitter_pattern(16)

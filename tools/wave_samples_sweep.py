@@ -1,9 +1,9 @@
 """Kernel time of a 1080p frame against the number of samples a bounce-0 wavefront takes (option wave_samples)."""
 import os, sys
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import functracer_amd as ft
-R = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ctx = ft.Context(0)
 scenes = [("bunny", 16), ("bunny", 64), ("hollow-sphere", 16), ("night-house-det", 16), ("night-house", 16), ("bunny-bsp12", 16), ("sample-det", 16), ("moon", 16), ("repeat", 4)]
 for name, spp in scenes:

@@ -2,7 +2,7 @@
 python tools/window_hint_ab.py   (GPU box)"""
 import os, sys, time
 import numpy as np
-R = os.environ.get("GRAFT_REPO_ROOT", "/root/repo"); sys.path.insert(0, R)
+R = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, R)
 import functracer_amd as ft
 from functracer_amd import tiling
 ctx = ft.Context(0)

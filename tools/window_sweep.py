@@ -1,6 +1,6 @@
 """Frame time against the chunk window (option chunk_samples) on one frame: python tools/window_sweep.py [scene w h spp]   (GPU box)"""
 import os, sys, time
-R = os.environ.get("GRAFT_REPO_ROOT", "/root/repo"); sys.path.insert(0, R)
+R = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, R)
 import functracer_amd as ft
 name, W, H, SPP = (sys.argv[1], int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4])) if len(sys.argv) > 4 else ("bunny", 3840, 2160, 64)
 ctx = ft.Context(0)
