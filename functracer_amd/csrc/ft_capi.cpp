@@ -96,7 +96,7 @@ struct ft_context {
     bool level_hint = true;         // launch only as many k_bounce levels as the previous frame of the same signature had (+ 1); 0: always max_depth
 
     // scene in HBM
-    DeviceBuf d_leaves, d_m2w, d_materials, d_lights, d_program, d_meshes, d_nodes, d_bleaves, d_tris, d_culls, d_tri_orig, d_textures, d_tex_pixels, d_cull_items, d_cull_rows, d_item_pc, d_wave_counts, d_wide, d_mesh_wide, d_coarse;
+    DeviceBuf d_leaves, d_m2w, d_materials, d_lights, d_program, d_meshes, d_nodes, d_bleaves, d_tris, d_culls, d_tri_orig, d_textures, d_tex_pixels, d_cull_items, d_cull_rows, d_item_pc, d_wave_counts, d_wide, d_mesh_wide, d_coarse, d_ls_pairs, d_ls_nodes, d_ls_tris;
     // What k_classify writes and the frame's later kernels read exists once per frame slot, so that a queued frame's classification can
     // run (on `side`, behind an event) while the frame before it is still tracing: block_pos / pos_block and the frame's counters.
     DeviceBuf d_block_pos[kSlots], d_pos_block[kSlots], d_fc[kSlots];
@@ -344,7 +344,7 @@ void ft_destroy(ft_context* c) {
         for (hipStream_t m : c->more_mains) if (m) (void)hipStreamSynchronize(m);
         if (c->side) (void)hipStreamSynchronize(c->side);
         if (c->tail) (void)hipStreamSynchronize(c->tail);
-        DeviceBuf* bufs[] = {&c->d_leaves, &c->d_m2w, &c->d_materials, &c->d_lights, &c->d_program, &c->d_meshes, &c->d_nodes, &c->d_bleaves, &c->d_tris, &c->d_culls, &c->d_tri_orig, &c->d_textures, &c->d_tex_pixels, &c->d_cull_items, &c->d_cull_rows, &c->d_item_pc, &c->d_block_pos[0], &c->d_block_pos[1], &c->d_block_pos[2], &c->d_block_pos[3], &c->d_pos_block[0], &c->d_pos_block[1], &c->d_pos_block[2], &c->d_pos_block[3], &c->d_wave_counts, &c->d_wide, &c->d_mesh_wide, &c->d_coarse, &c->d_out_index,
+        DeviceBuf* bufs[] = {&c->d_leaves, &c->d_m2w, &c->d_materials, &c->d_lights, &c->d_program, &c->d_meshes, &c->d_nodes, &c->d_bleaves, &c->d_tris, &c->d_culls, &c->d_tri_orig, &c->d_textures, &c->d_tex_pixels, &c->d_cull_items, &c->d_cull_rows, &c->d_item_pc, &c->d_block_pos[0], &c->d_block_pos[1], &c->d_block_pos[2], &c->d_block_pos[3], &c->d_pos_block[0], &c->d_pos_block[1], &c->d_pos_block[2], &c->d_pos_block[3], &c->d_wave_counts, &c->d_wide, &c->d_mesh_wide, &c->d_coarse, &c->d_ls_pairs, &c->d_ls_nodes, &c->d_ls_tris, &c->d_out_index,
                              &c->d_rays[0], &c->d_rays[1], &c->d_rays[2], &c->d_rays[3], &c->d_rays[4], &c->d_rays[5], &c->d_acc[0], &c->d_acc[1], &c->d_acc[2], &c->d_out, &c->d_out8, &c->d_pixels, &c->d_jitter, &c->d_fc[0], &c->d_fc[1], &c->d_fc[2], &c->d_fc[3],
                              &c->d_dbg_in, &c->d_dbg_out};
         for (auto* b : bufs) release(*b);
@@ -392,6 +392,11 @@ int32_t ft_set_option(ft_context* c, const char* key, int64_t value) {
     if (!std::strcmp(key, "csg_auto_grow")) { c->csg_auto_grow = value != 0; return FT_OK; }
     if (!std::strcmp(key, "follow_below")) { if (value < -1) return FT_ERR_INVALID; c->follow_below = value; c->staged_hint = -1; for (ft_context* p : c->peers) { p->follow_below = value; p->staged_hint = -1; } return FT_OK; }
     if (!std::strcmp(key, "level_hint")) { c->level_hint = value != 0; for (ft_context* p : c->peers) p->level_hint = value != 0; return FT_OK; }
+    if (!std::strcmp(key, "light_space_shadows")) {   // 1 (default): directional shadow rays of coherent waves walk light-space trees; 0: the BVH
+        c->graph.light_space_shadows = value != 0; c->committed = false;
+        for (ft_context* p : c->peers) { p->graph.light_space_shadows = value != 0; p->committed = false; }
+        return FT_OK;
+    }
     if (!std::strcmp(key, "bvh_builder")) { if (value < 0 || value > 3) return FT_ERR_INVALID; c->bvh_builder = (int)value; c->committed = false; return FT_OK; }
     if (!std::strcmp(key, "mesh_unclipped_bvh")) { c->graph.mesh_unclipped_bvh = value != 0; c->committed = false; return FT_OK; }
     c->err = std::string("unknown option: ") + key;
@@ -572,6 +577,9 @@ static int32_t upload_scene(ft_context* c) {
     if ((rc = upload(c, c->d_mesh_wide, f.mesh_wide)) != FT_OK) return rc;
     if ((rc = upload(c, c->d_coarse, f.coarse_boxes)) != FT_OK) return rc;
     if ((rc = upload(c, c->d_tri_orig, f.tri_orig)) != FT_OK) return rc;
+    if ((rc = upload(c, c->d_ls_pairs, f.ls_pairs)) != FT_OK) return rc;
+    if ((rc = upload(c, c->d_ls_nodes, f.ls_nodes)) != FT_OK) return rc;
+    if ((rc = upload(c, c->d_ls_tris, f.ls_tris)) != FT_OK) return rc;
     for (int k = 0; k < ft_context::kSlots; ++k) { if ((rc = ensure(c, c->d_fc[k], sizeof(ftk::FrameCounters))) != FT_OK) return rc; c->fc_clean[k] = false; }
     c->zero_signature[0] = c->zero_signature[1] = 0;
     FT_HIP(c, hipStreamSynchronize(c->stream));
@@ -602,6 +610,7 @@ static int32_t upload_scene(ft_context* c) {
     S.coarse_boxes = c->d_coarse.as<float>();
     S.cull_items = c->d_cull_items.as<float>(); S.cull_rows = c->d_cull_rows.as<double>();
     S.wide = c->d_wide.as<double>(); S.mesh_wide = c->d_mesh_wide.as<int32_t>();
+    S.ls_pairs = c->d_ls_pairs.as<double>(); S.ls_nodes = c->d_ls_nodes.as<uint32_t>(); S.ls_tris = c->d_ls_tris.as<double>();
     S.item_pc = c->d_item_pc.as<uint32_t>();
     S.coherent_waves = c->coherent_waves ? 1 : 0;
     S.n_simd = c->n_cu * 4;
@@ -1470,6 +1479,19 @@ int32_t ft_debug_scene_info(ft_context* c, int64_t out[12]) {
     out[4] = (int64_t)f.bsp_leaves.size() - f.bvh_leaves; out[5] = (int64_t)(f.tris.size() / 9) - f.bvh_tris; out[6] = f.csg_capacity; out[7] = f.bsp_stack_capacity;   // BSP-only: excludes the device-side BVH
     int64_t bounded = 0; for (size_t k = 0; k + 1 < f.item_pc.size(); ++k) if (f.cull_items[8 * k + 3] < 1e30f) ++bounded;
     out[8] = (int64_t)f.item_pc.size() - 1; out[9] = bounded; out[10] = f.unbounded ? 1 : 0; out[11] = f.cull_bundle ? (int64_t)(f.cull_rows.size() / 3) : -1;
+    return FT_OK;
+}
+
+int32_t ft_debug_light_space(ft_context* c, int64_t sizes[4], double* pairs, uint32_t* nodes, double* tris, uint32_t* leaf_pairs) {
+    if (!c || !sizes) return FT_ERR_INVALID;
+    if (!c->committed) { c->err = "scene not committed"; return FT_ERR_STATE; }
+    const fth::FlatScene& f = c->flat;
+    sizes[0] = (int64_t)(f.ls_pairs.size() / ftd::kLsPairDoubles); sizes[1] = (int64_t)(f.ls_nodes.size() / ftd::kLsNodeWords);
+    sizes[2] = (int64_t)(f.ls_tris.size() / 9); sizes[3] = (int64_t)f.leaves.size();
+    if (pairs) std::memcpy(pairs, f.ls_pairs.data(), f.ls_pairs.size() * sizeof(double));
+    if (nodes) std::memcpy(nodes, f.ls_nodes.data(), f.ls_nodes.size() * sizeof(uint32_t));
+    if (tris) std::memcpy(tris, f.ls_tris.data(), f.ls_tris.size() * sizeof(double));
+    if (leaf_pairs) for (size_t k = 0; k < f.leaves.size(); ++k) leaf_pairs[k] = f.leaves[k].ls_pairs;
     return FT_OK;
 }
 

@@ -28,6 +28,9 @@ struct DevScene {
     const uint32_t* tri_orig;      // 1 per triangle
     const double* wide;            // 28 doubles per 4-wide BVH node (ft_flat.h)
     const int32_t* mesh_wide;      // per mesh: root of its 4-wide BVH or INT32_MIN
+    const double* ls_pairs;        // light-space shadow trees (ft_flat.h, kLsPairDoubles): pair records,
+    const uint32_t* ls_nodes;      //   their nodes
+    const double* ls_tris;         //   and the triangle records their leaves point at
     const uint8_t* tex_pixels;     // Rgb24 rows of the image textures (ftd::Texture::pixel_base indexes into it)
     const float* cull_items;       // 8 floats per top-level item (centre, radius, row mask; bare meshes: + first coarse box, count, leaf)
     const float* coarse_boxes;     // 6 floats per box: model-space boxes that cover a mesh (k_classify)

@@ -42,7 +42,8 @@ struct Leaf {
     uint32_t flags;
     uint32_t material;
     uint32_t mesh;         // index into meshes[] for LK_MESH
-    uint32_t pad[4];
+    uint32_t ls_pairs;     // first light-space shadow pair record of the leaf (one per light), ~0u = none (see kLsPairDoubles)
+    uint32_t pad[3];
 };
 
 struct Material {          // Ray.fs:4-10; 64 bytes
@@ -90,6 +91,24 @@ struct Mesh {
 //   [24], [25]     = int32 child[4]: >= 0 wide node, < 0 ~leaf index, INT32_MIN empty slot (whose box is all NaN: no ray passes it)
 //   [26]           = uint32 axes: split axis of the binary node | of its left child << 8 | of its right child << 16
 constexpr int kWideNodeDoubles = 28;
+// Light-space shadow trees (ft_scene.cpp, build_light_space; walked by mesh_shadow_packet).  The shadow rays of a directional light are
+// parallel: in a mesh leaf's model space they all travel along the same dm = w2m * -light.v.  For every (top-level-Leaf mesh leaf with a BVH,
+// directional light) pair the host builds an orthonormal frame (U, V, D), D = dm / |dm|, and a 4-wide tree whose boxes are (u, v)
+// rectangles plus the largest w, all relative to the mesh's bounds centre c.  A ray from o can only hit a triangle of a child whose
+// rectangle holds the (u, v) of o and whose w reaches past the w of o: five comparisons per child instead of a 3-D slab test.
+// Pair record, kLsPairDoubles doubles (per leaf, one per light, from Leaf::pad[0]; ~0u = the leaf has none):
+//   [0..2] U, [3..5] V, [6..8] D, [9..11] c, [12] k_rel, [13] s_abs: a lane's slack is k_rel * |o - c|_1 + s_abs (it covers the angle
+//   between the host's dm and the device's, and the rounding of the lane's projection); [14] int32 root (>= 0 node, INT32_MIN = none).
+// Node, kLsNodeWords 32-bit words: [5*c .. 5*c+4] float u_lo, u_hi, v_lo, v_hi, w_max of child c (rounded outward, inflated by the
+//   vertices' rounding); [20..23] int32 child[4]: >= 0 node, INT32_MIN empty slot (all-NaN box: no comparison passes it), otherwise a
+//   leaf ~(first << 3 | count) over count <= 7 triangle records ls_tris[first ..] - bitwise copies of the mesh's own records, so
+//   tri_hit_wave computes exactly what it computes on them.
+// Caps: kLsMaxPairs pairs per scene, kLsMaxTris triangles per pair, kLsMaxBytes of nodes + copied records per scene; beyond them, "none".
+constexpr int kLsPairDoubles = 16;
+constexpr int kLsNodeWords = 24;
+constexpr uint32_t kLsMaxPairs = 64;
+constexpr uint32_t kLsMaxTris = 1u << 20;
+constexpr uint64_t kLsMaxBytes = 256ull << 20;
 // The reference-shaped BSP of a `bspMesh depth` primitive (root >= 0) has a two-levels-at-a-time form as well, for the same walk:
 // 40 doubles = five BspNode slots of the node array per branch (ft_scene.cpp, widen_bsp): the boxes of the branch's two children,
 // those of its four grandchildren in the reference's visiting order (right-right, right-left, left-right, left-left), int32 child[4]

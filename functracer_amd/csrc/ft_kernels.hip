@@ -86,6 +86,9 @@ struct Scene {
     cup tri_orig;     // 1 per triangle
     cdp wide;         // 28 doubles per 4-wide BVH node
     cip mesh_wide;    // 1 per mesh
+    cdp ls_pairs;     // 16 doubles per light-space shadow pair (ft_flat.h, kLsPairDoubles)
+    cup ls_nodes;     // 24 words per light-space node
+    cdp ls_tris;      // 9 doubles per triangle record the light-space trees point at
     const uint8_t* tex_pixels;   // per-lane byte gathers: ordinary global loads
     const float* cull_items;     // lane k reads record k: ordinary global loads
     const float* coarse_boxes;   // lane k reads box k
@@ -102,6 +105,7 @@ template <class DS> FT_DEV Scene scene_view(const DS& g) {
     s.program = to_const_as(g.program); s.meshes = to_const_as(reinterpret_cast<const int32_t*>(g.meshes));
     s.nodes = to_const_as(reinterpret_cast<const double*>(g.nodes)); s.bsp_leaves = to_const_as(reinterpret_cast<const uint32_t*>(g.bsp_leaves));
     s.tris = to_const_as(g.tris); s.culls = to_const_as(g.culls); s.tri_orig = to_const_as(g.tri_orig); s.wide = to_const_as(g.wide); s.mesh_wide = to_const_as(g.mesh_wide);
+    s.ls_pairs = to_const_as(g.ls_pairs); s.ls_nodes = to_const_as(g.ls_nodes); s.ls_tris = to_const_as(g.ls_tris);
     s.tex_pixels = g.tex_pixels; s.cull_items = g.cull_items; s.coarse_boxes = g.coarse_boxes; s.cull_rows = to_const_as(g.cull_rows); s.item_pc = to_const_as(g.item_pc); s.n_items = g.n_items; s.n_cull_rows = g.n_cull_rows;
     s.n_leaves = g.n_leaves; s.n_lights = g.n_lights; s.csg_cap = g.csg_cap; s.stack_cap = g.stack_cap; s.csg_rows = g.csg_rows; s.lane_fold = g.lane_fold; s.n_simd = g.n_simd;
     return s;
@@ -683,6 +687,18 @@ FT_DEV bool mesh_bsp_packet(const Scene& S, int32_t root, int32_t wide_root, con
     return true;
 }
 
+#ifdef FT_ITEM_COUNTS
+// Diagnostic build only (tools/item_counts.py): the any-hit mesh walks of coherent waves, slots 16 + 28 .. 31 of the wave's words:
+// nodes visited, triangles tested, cycles spent in leaves, walks.
+__device__ unsigned long long g_clk[8192 * 48];
+#define FT_CLK_SLOT() (((blockIdx.x * (kBlock / 64) + threadIdx.x / 64) & 8191u) * 48u)
+#define FT_WALK_ADD(k, v) do { const unsigned long long v_ = (unsigned long long)(v); if (lane_id() == 0) atomicAdd(&g_clk[FT_CLK_SLOT() + 16 + 28 + (k)], v_); } while (0)
+#define FT_WALK_NOW() __builtin_amdgcn_s_memtime()
+#else
+#define FT_WALK_ADD(k, v) do { (void)(v); } while (0)
+#define FT_WALK_NOW() 0ull
+#endif
+
 // The same query for a COHERENT wavefront (primary rays of one 8x8 pixel block and their shadow rays):
 // the 64 rays walk the BVH together.  The node stack and the current node are wave-uniform (the stack lives
 // in the lanes of one VGPR: lane i holds entry i, popped with v_readlane), node and triangle data come through scalar loads,
@@ -708,12 +724,14 @@ FT_DEV void mesh_bvh_packet(const Scene& S, int32_t wide_root, const Ray& r, Que
     // The boxes of a node's four children live in the node (ft_flat.h): one scalar-load round trip decides four subtrees.
     const unsigned long long live0 = __ballot(alive);
     // majority direction per axis (bit a set: most live rays travel towards +a): which child is nearer
+    if (ANY) FT_WALK_ADD(3, 1);
     const uint32_t oct = (2 * __popcll(__ballot(alive && r.dx >= 0.0)) >= __popcll(live0) ? 1u : 0u) | (2 * __popcll(__ballot(alive && r.dy >= 0.0)) >= __popcll(live0) ? 2u : 0u) |
                          (2 * __popcll(__ballot(alive && r.dz >= 0.0)) >= __popcll(live0) ? 4u : 0u);
     for (;;) {
         cur = __builtin_amdgcn_readfirstlane(cur);
         sp = __builtin_amdgcn_readfirstlane(sp);                    // wave-uniform by construction; said here so that the stack arithmetic stays on the scalar unit
         if (cur >= 0) {
+            if (ANY) FT_WALK_ADD(0, 1);
             cdp nd = S.wide + (unsigned long long)kWideNodeDoubles * (uint32_t)cur;
             // children and axes are read up front, with the first boxes: fetched one by one behind each child's test, every
             // one of them was a scalar-load round trip of its own
@@ -774,6 +792,7 @@ FT_DEV void mesh_bvh_packet(const Scene& S, int32_t wide_root, const Ray& r, Que
 #pragma clang diagnostic pop
         } else {
             const uint32_t first = S.bsp_leaves[2 * (~cur)], count = S.bsp_leaves[2 * (~cur) + 1];
+            const unsigned long long clk_leaf = FT_WALK_NOW();
             for (uint32_t k = 0; k < count; ++k) {                 // wave-uniform: scalar loads
                 double t = 0.0;
                 const bool h = tri_hit_wave(S.tris + 9ull * (first + k), r, alive, t);
@@ -786,6 +805,7 @@ FT_DEV void mesh_bvh_packet(const Scene& S, int32_t wide_root, const Ray& r, Que
                     reach = nearer ? t : reach; best_tri = nearer ? orig : best_tri; found = found | nearer;
                 }
             }
+            if (ANY) { FT_WALK_ADD(1, count); FT_WALK_ADD(2, FT_WALK_NOW() - clk_leaf); }
             if (ANY) { if (!__any(alive)) break; }
         }
         if (sp == 0) break;
@@ -793,6 +813,72 @@ FT_DEV void mesh_bvh_packet(const Scene& S, int32_t wide_root, const Ray& r, Que
         cur = __builtin_amdgcn_readlane(stack_lanes, sp);
     }
     if (!ANY && found) q.hit(reach, leaf, best_tri, lit);
+}
+
+// Any-hit query of a directional light's shadow rays against a mesh, for a COHERENT wavefront, through the mesh's light-space tree
+// (ft_flat.h, kLsPairDoubles; built by build_light_space).  The rays are parallel, so in the light's frame a child can only hold a hit
+// if its (u, v) rectangle contains the origin's (u, v) and its largest w reaches past the origin's w: five comparisons per child
+// against the general slab test's six FMAs and ten min / max.  Each lane widens its own (u, v, w) by its slack and rounds the bounds
+// outward to float once; the stack, the pushes and the leaves are those of mesh_bvh_packet.  A lane is blocked iff some triangle record
+// gives tri_hit_wave a hit with t < max_dist; the records are bitwise copies of the mesh's, and every triangle a lane can hit lies in
+// every box on its path, so the result is the BVH walk's bit for bit, whatever order the tree is visited in.
+FT_DEV void mesh_shadow_packet(const Scene& S, cdp P, const Ray& r, Query<true>& q) {
+    bool alive = q.active && !q.blocked;
+    if (!__any(alive)) return;
+    float uL, uH, vL, vH, wL;
+    {
+        const double ox = r.ox - P[9], oy = r.oy - P[10], oz = r.oz - P[11];
+        const double u = ox * P[0] + oy * P[1] + oz * P[2], v = ox * P[3] + oy * P[4] + oz * P[5], w = ox * P[6] + oy * P[7] + oz * P[8];
+        const double s = P[12] * (fabs(ox) + fabs(oy) + fabs(oz)) + P[13];
+        // x -+ (s + 2.4e-7 (|x| + s)) rounds to a float on the far side of x -+ s (a float's rounding is at most 6e-8 of its magnitude)
+        const double su = s + 2.4e-7 * (fabs(u) + s), sv = s + 2.4e-7 * (fabs(v) + s), sw = s + 2.4e-7 * (fabs(w) + s);
+        const bool finite = fabs(u) + fabs(v) + fabs(w) + s < 1e300;        // a non-finite origin looks everywhere (it hits nothing there either)
+        const float inf = __builtin_inff();
+        uL = finite ? (float)(u - su) : -inf; uH = finite ? (float)(u + su) : inf;
+        vL = finite ? (float)(v - sv) : -inf; vH = finite ? (float)(v + sv) : inf;
+        wL = !alive ? inf : finite ? (float)(w - sw) : -inf;               // dead lanes: no box reaches +inf
+    }
+    const double bound = q.max_dist;
+    FT_WALK_ADD(3, 1);
+    int stack_lanes = 0, sp = 0;
+    int cur = reinterpret_cast<cip>(P + 14)[0];
+    for (;;) {
+        cur = __builtin_amdgcn_readfirstlane(cur);
+        sp = __builtin_amdgcn_readfirstlane(sp);
+        if (cur >= 0) {
+            FT_WALK_ADD(0, 1);
+            const FT_CONST float* nd = reinterpret_cast<const FT_CONST float*>(S.ls_nodes + (unsigned long long)kLsNodeWords * (uint32_t)cur);
+            const int32_t ch[4] = {reinterpret_cast<cip>(nd + 20)[0], reinterpret_cast<cip>(nd + 20)[1], reinterpret_cast<cip>(nd + 20)[2], reinterpret_cast<cip>(nd + 20)[3]};
+            unsigned long long m[4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {                           // bare comparisons, one ballot each (see mesh_bvh_packet)
+                const FT_CONST float* bx = nd + 5 * c;
+                m[c] = __builtin_amdgcn_ballot_w64(bx[0] <= uH) & __builtin_amdgcn_ballot_w64(bx[1] >= uL) & __builtin_amdgcn_ballot_w64(bx[2] <= vH) &
+                       __builtin_amdgcn_ballot_w64(bx[3] >= vL) & __builtin_amdgcn_ballot_w64(bx[4] >= wL);
+            }
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"
+#define FT_PUSH(c) asm("s_mov_b32 m0, %1\n\tv_writelane_b32 %0, %2, m0\n\ts_cmp_lg_u64 %3, 0\n\ts_addc_u32 %1, %1, 0" : "+v"(stack_lanes), "+s"(sp) : "s"(ch[c]), "s"(m[c]) : "m0", "scc")
+            FT_PUSH(3); FT_PUSH(2); FT_PUSH(1);
+#undef FT_PUSH
+#pragma clang diagnostic pop
+            if (m[0]) { cur = ch[0]; continue; }
+        } else {
+            const uint32_t first = (uint32_t)(~cur) >> 3, count = (uint32_t)(~cur) & 7u;
+            const unsigned long long clk_leaf = FT_WALK_NOW();
+            for (uint32_t k = 0; k < count; ++k) {                 // wave-uniform: scalar loads
+                double t = 0.0;
+                const bool h = tri_hit_wave(S.ls_tris + 9ull * (first + k), r, alive, t);
+                const bool b = h & (t < bound);
+                q.blocked = q.blocked | b; alive = alive & !b; wL = b ? __builtin_inff() : wL;
+            }
+            FT_WALK_ADD(1, count); FT_WALK_ADD(2, FT_WALK_NOW() - clk_leaf);
+            if (!__any(alive)) break;
+        }
+        if (sp == 0) break;
+        --sp;
+        cur = __builtin_amdgcn_readlane(stack_lanes, sp);
+    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1050,8 +1136,6 @@ FT_DEV ItemMask exact_cull(const Scene& S, const Ray& r, bool live) {
 #ifdef FT_ITEM_COUNTS
 // Diagnostic build only: shader-clock cycles waves spend in sections of the tracing kernels (s_memtime; summed over waves).
 // Every wave adds to 48 words of its own (no-return atomics on addresses nobody shares: shared words made the build eight times slower).
-__device__ unsigned long long g_clk[8192 * 48];
-#define FT_CLK_SLOT() (((blockIdx.x * (kBlock / 64) + threadIdx.x / 64) & 8191u) * 48u)
 #define FT_CLK_NOW() __builtin_amdgcn_s_memtime()
 #define FT_CLK_ADD(k, t0) do { const unsigned long long t1_ = __builtin_amdgcn_s_memtime(); if (lane_id() == 0) atomicAdd(&g_clk[FT_CLK_SLOT() + 16 + (k)], t1_ - (t0)); } while (0)
 #define FT_CLK_INC(k) do { if (lane_id() == 0) atomicAdd(&g_clk[FT_CLK_SLOT() + 16 + (k)], 1ull); } while (0)
@@ -1072,7 +1156,7 @@ __device__ unsigned long long g_clk[8192 * 48];
 // MESH = false compiles the triangle / BSP / BVH code out: scenes without meshes then run kernels with
 // markedly fewer registers.
 template <bool ANY, bool MESH>
-FT_DEV void trace(const Scene& S, const Ray& r, Query<ANY>& q, uint32_t* lds, bool& overflow, bool coherent = false, cdp to_light = nullptr) {
+FT_DEV void trace(const Scene& S, const Ray& r, Query<ANY>& q, uint32_t* lds, bool& overflow, bool coherent = false, cdp to_light = nullptr, int dir_light = -1) {
     HitList L;
     L.init(lds, S.csg_cap, S.csg_rows, S.lane_fold);
     int32_t* stack = reinterpret_cast<int32_t*>(lds + 4 * S.csg_rows * kBlock) + threadIdx.x;
@@ -1117,6 +1201,15 @@ FT_DEV void trace(const Scene& S, const Ray& r, Query<ANY>& q, uint32_t* lds, bo
                     if (bvh >= 0) {
                         Ray rm;
                         to_model(S.leaves + 16ull * arg, (H.flags & LF_XFORM) != 0, r, rm);
+                        if constexpr (ANY) {                            // a directional light's shadow rays: its light-space tree, if the leaf has one
+                            if (coherent && dir_light >= 0) {
+                                const uint32_t pairs = reinterpret_cast<cup>(S.leaves + 16ull * arg + 12)[4];   // Leaf::ls_pairs
+                                if (pairs != ~0u) {
+                                    cdp P = S.ls_pairs + (unsigned long long)kLsPairDoubles * (pairs + (uint32_t)dir_light);
+                                    if (reinterpret_cast<cip>(P + 14)[0] != INT32_MIN) { mesh_shadow_packet(S, P, rm, q); break; }
+                                }
+                            }
+                        }
                         if (coherent) mesh_bvh_packet<ANY>(S, S.mesh_wide[H.mesh], rm, q, arg, lit);
                         else mesh_bvh_query<ANY>(S, bvh, rm, q, arg, lit, stack);
                         break;
@@ -1550,7 +1643,7 @@ FT_DEV void light_visibility(const Scene& S, const Surface& sf, bool lit, unsign
                 sr = {sox, soy, soz, -lp[0], -lp[1], -lp[2]};
                 q.max_dist = 1.7976931348623157e308;           // System.Double.MaxValue
             }
-            if (__any(lit)) trace<true, MESH>(S, sr, q, lds, overflow, coherent, kind == LT_POINT ? lp : nullptr);
+            if (__any(lit)) trace<true, MESH>(S, sr, q, lds, overflow, coherent, kind == LT_POINT ? lp : nullptr, kind == LT_DIRECTIONAL ? l : -1);
             n_shadow_wave += (unsigned long long)__popcll(__ballot(lit));
             occluded = q.blocked ? 1ull : 0ull;
         }

@@ -441,7 +441,12 @@ int32_t SceneGraph::flatten(FlatScene& out, std::string& err) const {
     //  traces, costs every kernel variant 52 - 136 bytes of scratch per lane - k_primary<F,F,T,4> 56 -> 108, k_bounce<F,F,F> 0 -> 72 - whether
     //  or not a scene has a seventeenth light.  No scene of the reference has more than three.)
     if (out.lights.size() > 16) { err = "more than 16 lights are not supported on the device path"; return FT_ERR_UNSUPPORTED; }
+    if (light_space_shadows) build_light_space(out);
+    else for (auto& L : out.leaves) L.ls_pairs = ~0u;
     if (out.tris.empty()) { out.tris.assign(9, 0.0); out.tri_orig.assign(1, 0u); }   // keep device pointers non-null
+    if (out.ls_pairs.empty()) out.ls_pairs.assign(ftd::kLsPairDoubles, 0.0);
+    if (out.ls_nodes.empty()) out.ls_nodes.assign(ftd::kLsNodeWords, 0u);
+    if (out.ls_tris.empty()) out.ls_tris.assign(9, 0.0);
     if (out.culls.empty()) out.culls.push_back(ftd::CullRecord{});
     return FT_OK;
 }
@@ -817,6 +822,216 @@ int32_t build_bsp(const double* tris_abc, int64_t n_tris, int32_t depth, FlatSce
         out.mesh_coarse.push_back(first); out.mesh_coarse.push_back(count);
     }
     return FT_OK;
+}
+
+namespace {
+
+// ---- light-space shadow trees (ft_flat.h, kLsPairDoubles) ----------------------------------------
+// A 2-D surface-area build: the chance that a parallel ray passes a child is proportional to the area of its (u, v) rectangle, so
+// every cut is priced as area(left) x count(left) + area(right) x count(right), over 16 bins of the centroids along u and along v.
+struct LsBuilder {
+    FlatScene& out;
+    struct Item { double lo[2], hi[2], wmax, cu, cv; uint32_t rec; };   // projected triangle; rec = its record in out.tris
+    struct Rect { double lo[2], hi[2], wmax; };
+    struct BNode { Rect r; int32_t left, right; uint32_t first, count; };   // left < 0: a leaf over ls_tris[first, first + count)
+    std::vector<Item> items;
+    std::vector<BNode> bn;
+    double pad = 0.0;
+    static constexpr size_t kLeafTris = 4;
+    static constexpr int kBins = 16;
+
+    static Rect empty_rect() { const double inf = std::numeric_limits<double>::infinity(); return Rect{{inf, inf}, {-inf, -inf}, -inf}; }
+    static void grow(Rect& r, const Item& t) {
+        for (int a = 0; a < 2; ++a) { r.lo[a] = std::min(r.lo[a], t.lo[a]); r.hi[a] = std::max(r.hi[a], t.hi[a]); }
+        r.wmax = std::max(r.wmax, t.wmax);
+    }
+    static double area(const Rect& r) { return r.hi[0] < r.lo[0] ? 0.0 : (r.hi[0] - r.lo[0]) * (r.hi[1] - r.lo[1]); }
+
+    int32_t build(size_t lo, size_t hi, uint32_t level) {
+        Rect r = empty_rect(), cr = empty_rect();
+        for (size_t k = lo; k < hi; ++k) {
+            grow(r, items[k]);
+            const double c[2] = {items[k].cu, items[k].cv};
+            for (int a = 0; a < 2; ++a) { cr.lo[a] = std::min(cr.lo[a], c[a]); cr.hi[a] = std::max(cr.hi[a], c[a]); }
+        }
+        const int32_t node = (int32_t)bn.size();
+        bn.push_back(BNode{r, -1, -1, 0, 0});
+        if (hi - lo <= kLeafTris) {                                            // bitwise copies of the mesh's own records
+            bn[(size_t)node].first = (uint32_t)(out.ls_tris.size() / 9); bn[(size_t)node].count = (uint32_t)(hi - lo);
+            for (size_t k = lo; k < hi; ++k) out.ls_tris.insert(out.ls_tris.end(), &out.tris[9 * (size_t)items[k].rec], &out.tris[9 * (size_t)items[k].rec] + 9);
+            return node;
+        }
+        int axis = cr.hi[1] - cr.lo[1] > cr.hi[0] - cr.lo[0] ? 1 : 0;
+        size_t mid = (lo + hi) / 2;
+        bool binned = false;
+        if (level < 16) {                                                      // deeper: medians, so that the tree stays within the walk's stack
+            double best = std::numeric_limits<double>::infinity();
+            int best_axis = -1, best_cut = 0;
+            for (int a = 0; a < 2; ++a) {
+                const double ext = cr.hi[a] - cr.lo[a];
+                if (!(ext > 0.0)) continue;
+                Rect br[kBins]; size_t bc[kBins] = {};
+                for (auto& b : br) b = empty_rect();
+                for (size_t k = lo; k < hi; ++k) {
+                    const double c = a ? items[k].cv : items[k].cu;
+                    const int b = std::min(kBins - 1, (int)((c - cr.lo[a]) / ext * kBins));
+                    grow(br[b], items[k]); ++bc[b];
+                }
+                double right_area[kBins]; size_t right_n[kBins];
+                Rect acc = empty_rect(); size_t n = 0;
+                for (int b = kBins - 1; b > 0; --b) {
+                    for (int q = 0; q < 2; ++q) { acc.lo[q] = std::min(acc.lo[q], br[b].lo[q]); acc.hi[q] = std::max(acc.hi[q], br[b].hi[q]); }
+                    n += bc[b]; right_area[b] = area(acc); right_n[b] = n;
+                }
+                acc = empty_rect(); n = 0;
+                for (int b = 1; b < kBins; ++b) {                              // cut before bin b
+                    for (int q = 0; q < 2; ++q) { acc.lo[q] = std::min(acc.lo[q], br[b - 1].lo[q]); acc.hi[q] = std::max(acc.hi[q], br[b - 1].hi[q]); }
+                    n += bc[b - 1];
+                    if (n == 0 || right_n[b] == 0) continue;
+                    const double cost = area(acc) * (double)n + right_area[b] * (double)right_n[b];
+                    if (cost < best) { best = cost; best_axis = a; best_cut = b; }
+                }
+            }
+            if (best_axis >= 0) {
+                const int a = best_axis;
+                const double ext = cr.hi[a] - cr.lo[a];
+                auto left_of = [&](const Item& t) { const double c = a ? t.cv : t.cu; return std::min(kBins - 1, (int)((c - cr.lo[a]) / ext * kBins)) < best_cut; };
+                mid = (size_t)(std::partition(items.begin() + (long)lo, items.begin() + (long)hi, left_of) - items.begin());
+                binned = mid > lo && mid < hi;
+                axis = a;
+            }
+        }
+        if (!binned) {
+            mid = (lo + hi) / 2;
+            std::nth_element(items.begin() + (long)lo, items.begin() + (long)mid, items.begin() + (long)hi,
+                             [axis](const Item& x, const Item& y) { return axis ? x.cv < y.cv : x.cu < y.cu; });
+        }
+        const int32_t l = build(lo, mid, level + 1);
+        const int32_t rr = build(mid, hi, level + 1);
+        bn[(size_t)node].left = l; bn[(size_t)node].right = rr;
+        return node;
+    }
+
+    static float f_down(double x) { float f = (float)x; if ((double)f > x) f = std::nextafter(f, -std::numeric_limits<float>::infinity()); return f; }
+    static float f_up(double x) { float f = (float)x; if ((double)f < x) f = std::nextafter(f, std::numeric_limits<float>::infinity()); return f; }
+    int32_t child_ref(int32_t n) {
+        const BNode& b = bn[(size_t)n];
+        return b.left < 0 ? ~(int32_t)(b.first << 3 | b.count) : widen(n);
+    }
+    // Two levels of the binary tree per node, as BspBuilder::widen does: a half that is a leaf takes the first slot of its half.
+    int32_t widen(int32_t n) {
+        const size_t at = out.ls_nodes.size();
+        out.ls_nodes.resize(at + ftd::kLsNodeWords, 0u);
+        int32_t kids[4] = {-1, -1, -1, -1};
+        const int32_t halves[2] = {bn[(size_t)n].left, bn[(size_t)n].right};
+        for (int h = 0; h < 2; ++h) {
+            const BNode& c = bn[(size_t)halves[h]];
+            if (c.left < 0) { kids[2 * h] = halves[h]; continue; }
+            kids[2 * h] = c.left; kids[2 * h + 1] = c.right;
+        }
+        float box[20];
+        int32_t child[4] = {INT32_MIN, INT32_MIN, INT32_MIN, INT32_MIN};
+        for (int c = 0; c < 4; ++c) {
+            if (kids[c] < 0) { for (int k = 0; k < 5; ++k) box[5 * c + k] = std::numeric_limits<float>::quiet_NaN(); continue; }
+            const Rect& r = bn[(size_t)kids[c]].r;
+            box[5 * c + 0] = f_down(r.lo[0] - pad); box[5 * c + 1] = f_up(r.hi[0] + pad);
+            box[5 * c + 2] = f_down(r.lo[1] - pad); box[5 * c + 3] = f_up(r.hi[1] + pad);
+            box[5 * c + 4] = f_up(r.wmax + pad);
+            child[c] = child_ref(kids[c]);
+        }
+        std::memcpy(&out.ls_nodes[at], box, sizeof box);
+        std::memcpy(&out.ls_nodes[at + 20], child, sizeof child);
+        return (int32_t)(at / ftd::kLsNodeWords);
+    }
+};
+
+} // namespace
+
+void build_light_space(FlatScene& out) {
+    for (auto& L : out.leaves) L.ls_pairs = ~0u;
+    out.ls_pairs.clear(); out.ls_nodes.clear(); out.ls_tris.clear();
+    std::vector<uint32_t> dirs;
+    for (uint32_t l = 0; l < (uint32_t)out.lights.size(); ++l) if (out.lights[l].kind == ftd::LT_DIRECTIONAL) dirs.push_back(l);
+    if (dirs.empty()) return;
+    std::vector<bool> folded(out.leaves.size(), false);                        // only top-level leaves fold straight into a shadow query
+    for (uint32_t w : out.program) if ((w & 0xFFu) == ftd::OP_LEAF_FOLD && (w >> 8) < folded.size()) folded[w >> 8] = true;
+    uint32_t n_pairs = 0;
+    uint64_t bytes = 0;
+    for (uint32_t leaf = 0; leaf < (uint32_t)out.leaves.size(); ++leaf) {
+        ftd::Leaf& L = out.leaves[leaf];
+        if (L.kind != ftd::LK_MESH || !folded[leaf] || !(L.flags & ftd::LF_LIT) || L.mesh >= out.meshes.size()) continue;
+        const ftd::Mesh& m = out.meshes[L.mesh];
+        if (m.bvh_root < 0 || m.root >= 0) continue;                           // the coherent shadow walk replaced is the BVH of a top-level Leaf
+        const ftd::BspLeaf src = out.bsp_leaves[(size_t)~m.root];
+        if (src.n_tris < 8 || src.n_tris > ftd::kLsMaxTris) continue;
+        const uint32_t base = (uint32_t)(out.ls_pairs.size() / ftd::kLsPairDoubles);
+        bool any = false;
+        std::vector<double> recs((size_t)ftd::kLsPairDoubles * out.lights.size(), 0.0);
+        for (size_t l = 0; l < out.lights.size(); ++l) { const int32_t none = INT32_MIN; std::memcpy(&recs[ftd::kLsPairDoubles * l + 14], &none, 4); }
+        for (uint32_t l : dirs) {
+            if (n_pairs >= ftd::kLsMaxPairs) break;
+            const uint64_t need = (uint64_t)src.n_tris * 72 + (uint64_t)src.n_tris * ftd::kLsNodeWords * 4;   // records + at most n / 2 nodes, with room
+            if (bytes + need > ftd::kLsMaxBytes) continue;
+            // the model-space direction exactly as to_model computes it (ft_kernels.hip), d = -light.v (light_visibility)
+            const double d[3] = {-out.lights[l].v[0], -out.lights[l].v[1], -out.lights[l].v[2]};
+            const double* M = L.w2m;
+            double dm[3], dabs[3];
+            if (L.flags & ftd::LF_XFORM) {
+                for (int r = 0; r < 3; ++r) { dm[r] = M[4 * r] * d[0] + M[4 * r + 1] * d[1] + M[4 * r + 2] * d[2]; dabs[r] = std::fabs(M[4 * r] * d[0]) + std::fabs(M[4 * r + 1] * d[1]) + std::fabs(M[4 * r + 2] * d[2]); }
+            } else for (int r = 0; r < 3; ++r) { dm[r] = d[r]; dabs[r] = std::fabs(d[r]); }
+            const double len = std::sqrt(dm[0] * dm[0] + dm[1] * dm[1] + dm[2] * dm[2]);
+            const double lab = std::sqrt(dabs[0] * dabs[0] + dabs[1] * dabs[1] + dabs[2] * dabs[2]);
+            if (!(len > 1e-150) || !(len < 1e150) || !std::isfinite(lab)) continue; // zero or non-finite: such rays keep today's walk
+            // angle between this dm and the device's (fused or not, each component within a few ulp of |M||d|), plus the frame's own rounding
+            const double k_rel = 1e-6 + 64.0 * 1.1102230246251565e-16 * lab / len;
+            if (!(k_rel < 1e-3)) continue;                                     // ill-conditioned: boxes would be loose, keep today's walk
+            double D[3] = {dm[0] / len, dm[1] / len, dm[2] / len}, U[3], V[3];
+            int a = 0;                                                          // the axis least aligned with D: the frame stays orthonormal for any D
+            for (int q = 1; q < 3; ++q) if (std::fabs(D[q]) < std::fabs(D[a])) a = q;
+            const double e[3] = {a == 0 ? 1.0 : 0.0, a == 1 ? 1.0 : 0.0, a == 2 ? 1.0 : 0.0};
+            U[0] = D[1] * e[2] - D[2] * e[1]; U[1] = D[2] * e[0] - D[0] * e[2]; U[2] = D[0] * e[1] - D[1] * e[0];
+            const double lu = std::sqrt(U[0] * U[0] + U[1] * U[1] + U[2] * U[2]);
+            for (double& x : U) x /= lu;
+            V[0] = D[1] * U[2] - D[2] * U[1]; V[1] = D[2] * U[0] - D[0] * U[2]; V[2] = D[0] * U[1] - D[1] * U[0];
+            const double* mb = &out.mesh_bounds[6 * (size_t)L.mesh];
+            const double c[3] = {0.5 * (mb[0] + mb[3]), 0.5 * (mb[1] + mb[4]), 0.5 * (mb[2] + mb[5])};
+            LsBuilder B{out};
+            B.items.resize(src.n_tris);
+            double R = 0.0;
+            bool finite = true;
+            for (uint32_t k = 0; k < src.n_tris; ++k) {
+                const double* T = &out.tris[9 * (size_t)(src.first_tri + k)];
+                LsBuilder::Item& it = B.items[k];
+                it.rec = src.first_tri + k;
+                it.lo[0] = it.lo[1] = std::numeric_limits<double>::infinity(); it.hi[0] = it.hi[1] = it.wmax = -it.lo[0];
+                for (int v = 0; v < 3; ++v) {
+                    double p[3];
+                    for (int q = 0; q < 3; ++q) p[q] = (T[q] - c[q]) + (v == 1 ? T[3 + q] : v == 2 ? T[6 + q] : 0.0);
+                    const double pu = p[0] * U[0] + p[1] * U[1] + p[2] * U[2], pv = p[0] * V[0] + p[1] * V[1] + p[2] * V[2], pw = p[0] * D[0] + p[1] * D[1] + p[2] * D[2];
+                    it.lo[0] = std::min(it.lo[0], pu); it.hi[0] = std::max(it.hi[0], pu);
+                    it.lo[1] = std::min(it.lo[1], pv); it.hi[1] = std::max(it.hi[1], pv);
+                    it.wmax = std::max(it.wmax, pw);
+                    R = std::max(R, std::fabs(p[0]) + std::fabs(p[1]) + std::fabs(p[2]));
+                }
+                it.cu = 0.5 * (it.lo[0] + it.hi[0]); it.cv = 0.5 * (it.lo[1] + it.hi[1]);
+                finite = finite && std::fabs(it.lo[0]) + std::fabs(it.hi[0]) + std::fabs(it.lo[1]) + std::fabs(it.hi[1]) + std::fabs(it.wmax) < 1e30;
+            }
+            if (!finite) continue;
+            B.pad = 1e-7 * R + 1e-30;                                           // the vertices' projection rounding, with room
+            const size_t t0 = out.ls_tris.size(), n0 = out.ls_nodes.size();
+            const int32_t top = B.build(0, B.items.size(), 0);
+            const int32_t root = B.widen(top);
+            bytes += (uint64_t)(out.ls_tris.size() - t0) * 8 + (uint64_t)(out.ls_nodes.size() - n0) * 4;
+            double* rec = &recs[ftd::kLsPairDoubles * l];
+            for (int q = 0; q < 3; ++q) { rec[q] = U[q]; rec[3 + q] = V[q]; rec[6 + q] = D[q]; rec[9 + q] = c[q]; }
+            rec[12] = k_rel; rec[13] = (k_rel + 1e-6) * R + 1e-20;   // |p - o| <= |o - c|_1 + R for a hit p on the mesh
+            std::memcpy(&rec[14], &root, 4);
+            ++n_pairs; any = true;
+        }
+        if (!any) continue;
+        L.ls_pairs = base;
+        out.ls_pairs.insert(out.ls_pairs.end(), recs.begin(), recs.end());
+    }
 }
 
 int32_t slice_triangle(const double p0[3], const double n[3], const double tri[9], std::vector<double>& above, std::vector<double>& below, std::string& err) {

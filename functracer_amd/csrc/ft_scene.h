@@ -58,6 +58,10 @@ struct FlatScene {
     bool any_reflective = false;
     bool any_texture = false;
     bool mesh_under_csg = false;
+    // Light-space shadow trees (ft_flat.h, kLsPairDoubles): pair records, nodes and the triangle records they point at.
+    std::vector<double> ls_pairs;
+    std::vector<uint32_t> ls_nodes;
+    std::vector<double> ls_tris;
     // Meshes whose exact BVH is built on the device after the upload (ft_bvh.hip): the flattener only reserves their ranges.
     struct BvhJob { uint32_t mesh, first_global, n, node_base, leaf_base, tri_base, wide_base, coarse_first, coarse_count; };
     std::vector<BvhJob> bvh_jobs;
@@ -76,6 +80,8 @@ struct SceneGraph {
     // false = the host's recursive surface-area sweep (host-only contexts, and the fallback when a device build is refused).
     bool device_bvh = false;
     int64_t device_bvh_min_tris = 0;   // with device_bvh: meshes with fewer triangles than this get the host's SAH tree (better tree, slower build)
+    // Directional shadow rays of coherent waves walk a tree built in the light's frame (ft_flat.h, kLsPairDoubles); false = the BVH of every ray.
+    bool light_space_shadows = true;
 
     bool valid(int32_t id) const { return id >= 0 && id < (int32_t)nodes.size(); }
     // Returns FT_OK or a negative ft_status with err set.
@@ -85,6 +91,9 @@ struct SceneGraph {
 // BspMesh.compile (BspMesh.fs:51-65) on the host: appends nodes / leaves / clipped triangles to
 // the flat arrays and returns the root reference (>= 0 branch node, < 0 ~leaf) via mesh.
 int32_t build_bsp(const double* tris_abc, int64_t n_tris, int32_t depth, FlatScene& out, ftd::Mesh& mesh, std::string& err, bool device_bvh = false);
+
+// The light-space shadow trees of every (top-level-Leaf mesh leaf with a BVH, directional light) pair of a flattened scene (ft_flat.h).
+void build_light_space(FlatScene& out);
 
 // Triangle.slice (Triangle.fs:24-41) exposed for the known-answer tests of the product's own builder.
 int32_t slice_triangle(const double p0[3], const double n[3], const double tri[9],

@@ -27,6 +27,11 @@ for name, spp in (("bunny", 16), ("bunny-bsp12", 16), ("hollow-sphere", 16), ("h
     if clk[26]:
         nb = clk[26]
         print(f"   k_primary per batch ({nb} batches): total {clk[25] / nb:9.0f} cycles = ray generation {clk[22] / nb:8.0f} + closest trace {clk[23] / nb:8.0f} + shadow queries {clk[24] / nb:8.0f} + surface / shading / store / spawn {(clk[25] - clk[22] - clk[23] - clk[24]) / nb:8.0f}")
+    if clk[31]:
+        walks, qa = clk[31], v[8]
+        nb = clk[26] or 1
+        print(f"   coherent any-hit mesh walks {walks} ({walks / max(qa, 1):.2f} per shadow wave-query): nodes / walk {clk[28] / walks:7.2f}  triangles / walk {clk[29] / walks:7.2f}  "
+              f"leaf cycles / walk {clk[30] / walks:8.0f};  per k_primary batch: shadow {clk[24] / nb:8.0f} = leaves {clk[30] / nb:8.0f} + walk and the rest {(clk[24] - clk[30]) / nb:8.0f}")
     if clk[21]:
         nb = clk[21]
         print(f"   k_bounce per batch ({nb} batches): total {clk[20] / nb:9.0f} cycles = closest trace {clk[16] / nb:8.0f} + surface {(clk[17] - clk[16]) / nb:8.0f} + shadow queries {clk[18] / nb:8.0f} + shading / store / spawn {clk[19] / nb:8.0f}")
