@@ -14,6 +14,7 @@
 #include <limits>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/functracer_hip.h"
@@ -25,6 +26,7 @@
 struct DeviceBuf {
     void* p = nullptr; size_t bytes = 0;
     template <class T> T* as() const { return reinterpret_cast<T*>(p); }
+    void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
 };
 
 // Stage indices of ft_get_kernel_times.
@@ -62,6 +64,67 @@ struct DeviceWorker {
 };
 
 constexpr int64_t kDeviceBvhMinTris = 4096;   // "bvh_builder" = 2: smaller meshes get the host's swept SAH tree (a few ms at most), larger ones the device's binned one
+
+// The frame tunables of ft_set_option (kOptions, include/functracer_hip.h).  Every device of a context holds the same values; flags are 0 / 1.
+struct Options {
+    int64_t chunk_samples = 16ll << 20;   // measured: 8 Mi costs 10-25 % (more, smaller launches), 32 Mi slows the shading on many-light scenes
+    int64_t wave_samples = 0;       // bounce-0 wavefronts take up to this many samples of 64 / as many pixels when the sample count allows; 0: the default, 16
+    int64_t coherent_waves = 1;     // diagnostic: 0 routes every wavefront through the incoherent paths
+    int64_t timing = 1;             // HIP events: 0 around the frame only, 1 + around every tracing kernel (k_primary, the k_bounce levels), 2 around every stage
+    int64_t classify_pixels = 1;    // k_classify: pixel blocks that cannot see any item are finished before any ray is generated
+    int64_t follow_below = -1;      // a level of the reflection tree in which the previous frame had no more rays than this gets no launch of
+                                    // its own: the last level launched follows them in registers.  -1: two rays per SIMD (2048 on 256 CUs: 8 x n_cu).  Measured at 1080p
+                                    // (0 -> 10 000): hollow-sphere x1 0.881 -> 0.863 ms, sample-det x16 1.190 -> 1.164, sample-soft x4 0.905 -> 0.855; following
+                                    // levels of 50 000 rays and more loses (hollow-sphere x1 0.976): a lane then drags its wave through every level
+    int64_t level_hint = 1;         // launch only as many k_bounce levels as the previous frame of the same signature had (+ 1); 0: always max_depth
+    int64_t classify_ahead = 1;     // 0 keeps every kernel on the one stream
+    int64_t resolve_aside = 1;      // 0 keeps k_resolve on the main stream
+    int64_t zero_fill_skip = 1;     // 0 writes Colour.Zero into every finished block of every frame
+    int64_t mains = 2;              // 1 .. 3: main streams in use (measured: 2 is best - the headline 0.263 / 0.231 / 0.249 ms with 1 / 2 / 3, hollow-sphere x1 0.703 / 0.471 / 0.470)
+    int64_t bvh_builder = 2;        // who builds the exact BVH of top-level-Leaf meshes: 0 = the host (swept surface-area split: the best tree, 1.2 ms for 980
+                                    // triangles but 160 ms for 69.6 K), 1 = the device's linear BVH (ft_bvh.hip: ~1 ms, traces ~9 % slower), 3 = the device's
+                                    // binned surface-area tree over the Morton order, 2 = by size: the host's below kDeviceBvhMinTris triangles, 3's from there on
+    int64_t csg_auto_grow = 1;      // ft_render: double csg_mesh_capacity and render again when a hit list overflows (read on device 0)
+};
+
+// One buffer in HBM per array of the flattened scene; DevScene points into them (upload_scene).
+enum SceneArray { kLeaves, kM2w, kMaterials, kLights, kTextures, kTexPixels, kProgram, kMeshes, kNodes, kBspLeaves, kTris, kCulls, kCullItems,
+                  kCullRows, kItemPc, kWide, kMeshWide, kCoarse, kTriOrig, kLsPairs, kLsNodes, kLsTris, kSceneArrays };
+
+// HIP events of one frame on its main stream.  An event between two dependent kernels costs about 6 us of stream time, so by default
+// ("timing" = 1) only the kernels that trace rays (k_primary, the k_bounce levels) are bracketed; 2 brackets every stage, 0 only the frame.
+// The frame's first event is recorded in front of its first launch on the main stream, behind the waits for other streams' events: on a
+// queued frame it doubles as the start of k_primary's bracket (an event record costs ~5 us of stream time; a frame of 0.27 ms had four
+// between two k_primary launches, now two).
+struct Brackets {
+    std::vector<hipEvent_t> events; size_t used = 0;   // created as needed, reused by the slot's later frames
+    struct Span { hipEvent_t a, b; int kind; };
+    std::vector<Span> spans;
+    hipStream_t ms = nullptr;
+    int timing = 1;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;   // the frame's first and last event (ev1: where it is done)
+    hipEvent_t boundary = nullptr;
+    bool fresh = false;                        // `boundary` was recorded right before the next entry of the main stream
+    void begin(hipStream_t s, int t) { used = 0; spans.clear(); ms = s; timing = t; ev0 = ev1 = boundary = nullptr; fresh = false; }
+    hipEvent_t next() {
+        if (used == events.size()) { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) return nullptr; events.push_back(e); }
+        return events[used++];
+    }
+    hipEvent_t record(hipStream_t s) { hipEvent_t e = next(); if (e) (void)hipEventRecord(e, s); return e; }
+    void open() { if (ev0) return; ev0 = record(ms); boundary = ev0; fresh = true; }
+    template <class Fn> void timed(int kind, Fn&& fn) {
+        const bool bracket = timing >= 2 || (timing == 1 && (kind == kStageClosest || kind == kStageShade || kind == kStagePrimary));
+        open();
+        if (bracket && !fresh) boundary = record(ms);
+        fn();
+        if (!bracket) { fresh = false; return; }
+        hipEvent_t b = record(ms);
+        if (boundary && b) spans.push_back(Span{boundary, b, kind});
+        boundary = b; fresh = true;
+    }
+    void release() { for (hipEvent_t e : events) (void)hipEventDestroy(e); events.clear(); used = 0; }
+};
+
 struct ft_context {
     static constexpr int kMains = 3;   // main streams at most: consecutive simple frames trace on different ones (option "mains" says how many are in use)
     static constexpr int kAcc = kMains;   // copies of the sample colours: one per frame between its k_primary and its k_resolve
@@ -74,43 +137,23 @@ struct ft_context {
     hipStream_t stream = nullptr;
     hipStream_t more_mains[kMains - 1] = {};   // further main streams: consecutive simple queued frames trace on different ones, so that a frame's kernels are dispatched while its predecessors' drain
     std::string err;
+    Options opt;
 
     fth::SceneGraph graph;
     fth::FlatScene flat;
-    std::vector<float> cull_items_and_rows;   // what d_cull_items holds (the upload's source)
+    std::vector<float> cull_items_and_rows;   // what d_scene[kCullItems] holds (the upload's source)
     bool committed = false;
-    int bvh_builder = 2;            // who builds the exact BVH of top-level-Leaf meshes: 0 = the host (swept surface-area split: the best tree, 1.2 ms for 980
-                                    // triangles but 160 ms for 69.6 K), 1 = the device's linear BVH (ft_bvh.hip: ~1 ms, traces ~9 % slower), 3 = the device's
-                                    // binned surface-area tree over the Morton order, 2 = by size: the host's below kDeviceBvhMinTris triangles, 3's from there on
     double commit_ms[4] = {0, 0, 0, 0};   // last ft_scene_commit: flatten on the host, device BVH builds, uploads + the rest, BVH height (not a time)
 
-    int64_t chunk_samples = 16ll << 20;   // measured: 8 Mi costs 10-25 % (more, smaller launches), 32 Mi slows the shading on many-light scenes
-    int wave_samples_log2 = -1;     // bounce-0 wavefronts take 2^this samples of 64 / 2^this pixels when the sample count allows (option wave_samples); -1: the default, 16
-    bool coherent_waves = true;     // diagnostic: 0 routes every wavefront through the incoherent paths
-    int timing = 1;                 // HIP events: 0 around the frame only, 1 + around every tracing kernel (k_primary, the k_bounce levels), 2 around every stage
-    bool classify_pixels = true;    // k_classify: pixel blocks that cannot see any item are finished before any ray is generated
-    int64_t follow_below = -1;      // option "follow_below": a level of the reflection tree in which the previous frame had no more rays than this gets no launch of
-                                    // its own: the last level launched follows them in registers.  -1: two rays per SIMD (2048 on 256 CUs: 8 x n_cu).  Measured at 1080p
-                                    // (0 -> 10 000): hollow-sphere x1 0.881 -> 0.863 ms, sample-det x16 1.190 -> 1.164, sample-soft x4 0.905 -> 0.855; following
-                                    // levels of 50 000 rays and more loses (hollow-sphere x1 0.976): a lane then drags its wave through every level
-    bool level_hint = true;         // launch only as many k_bounce levels as the previous frame of the same signature had (+ 1); 0: always max_depth
-
-    // scene in HBM
-    DeviceBuf d_leaves, d_m2w, d_materials, d_lights, d_program, d_meshes, d_nodes, d_bleaves, d_tris, d_culls, d_tri_orig, d_textures, d_tex_pixels, d_cull_items, d_cull_rows, d_item_pc, d_wave_counts, d_wide, d_mesh_wide, d_coarse, d_ls_pairs, d_ls_nodes, d_ls_tris;
-    // What k_classify writes and the frame's later kernels read exists once per frame slot, so that a queued frame's classification can
-    // run (on `side`, behind an event) while the frame before it is still tracing: block_pos / pos_block and the frame's counters.
-    DeviceBuf d_block_pos[kSlots], d_pos_block[kSlots], d_fc[kSlots];
+    DeviceBuf d_scene[kSceneArrays];
     hipStream_t side = nullptr;     // the second stream: k_classify of frame N + 1 beside k_primary's tail / k_resolve of frame N (ft_render_enqueue)
-    bool classify_ahead = true;     // option "classify_ahead": 0 keeps every kernel on the one stream
-    bool classify_after_trace = false;   // option "classify_after_trace": the classification run ahead waits for the previous frame's tracing kernels
     // Kernel variants and resident workgroups per CU for the committed scene (they only change at commit): bit 0 FANCY, 1 SOFT, 2 MESH; the
     // primary's variant may carry bit 3 (the five-workgroup lean build).
     int variant = 0, variant_primary = 0, blocks_primary = 1, blocks_bounce = 1, blocks_resolve = 2;
-    int resolve_blocks_cap = 0;     // option "resolve_blocks": k_resolve workgroups per CU (0: every resident one)
     hipEvent_t classified = nullptr;  // behind the latest k_classify on either stream: the next one waits for it (they share the ticket words of d_wave_counts)
     ftk::DevScene dev_scene{};
     // frame buffers in HBM
-    DeviceBuf d_rays[2 * kMains], d_acc[kAcc], d_out, d_out8, d_pixels, d_jitter, d_dbg_in, d_dbg_out;
+    DeviceBuf d_rays[2 * kMains], d_acc[kAcc], d_out, d_out8, d_out_index, d_pixels, d_jitter, d_wave_counts, d_dbg_in, d_dbg_out;
     // The sample colours exist twice: a queued frame's k_resolve runs on a stream of its own (`tail`), behind an event, while the next
     // chunk's / frame's k_primary already fills the other copy - the small kernel hides in the big one's ramp instead of standing between
     // two of them.  acc_free[i]: behind the last k_resolve that read copy i (the next k_primary into that copy waits for it).
@@ -118,30 +161,32 @@ struct ft_context {
     hipStream_t tail = nullptr;
     hipEvent_t acc_free[kAcc] = {};
     bool acc_busy[kAcc] = {};
-    bool resolve_aside = true;      // option "resolve_aside": 0 keeps k_resolve on the main stream
-    bool fc_clean[kSlots] = {};   // d_fc[slot] is all zero: the slot's previous frame cleared it behind its report (no fill needed)
     // Colour.Zero in the blocks k_classify finished: what the last frame written into d_out / d_out8 classified (scene, camera, size, pixel
     // list, jitter extent).  A frame of the same signature finds those pixels zero already and does not write them again.
     uint64_t zero_signature[2] = {0, 0};
-    bool zero_fill_skip = true;     // option "zero_fill_skip"
     uint32_t classify_epoch = 0;    // tags the entries k_classify's waves publish in d_wave_counts (cleared only when it wraps or the buffer grows)
     int64_t ray_capacity = 0, acc_capacity = 0;
-    // Per-frame host state.  Two slots, so that one frame can be queued while the previous one still runs (ft_render_enqueue).
+    // Per-frame state.  One slot per frame in flight, so that frames can be queued while earlier ones still run (ft_render_enqueue).
     struct FrameSlot {
-        std::vector<hipEvent_t> events; size_t events_used = 0;
-        struct Span { hipEvent_t a, b; int kind; };
-        std::vector<Span> spans;
-        bool simple = false, alt = false;       // one chunk, k_resolve aside; alt: traced on main stream `main_ix` != 0
-        int main_ix = 0;
-        hipEvent_t ev0 = nullptr, ev1 = nullptr, done = nullptr;
-        hipEvent_t traced = nullptr;            // (one of `events`, not owned) behind the frame's last tracing kernel, in front of its k_resolve: where the NEXT frame's k_classify may start
+        // What k_classify writes and the frame's later kernels read exists once per slot, so that a queued frame's classification can
+        // run (on `side`, behind an event) while the frame before it is still tracing: block_pos / pos_block and the frame's counters.
+        DeviceBuf d_block_pos, d_pos_block, d_fc;
+        bool fc_clean = false;                  // d_fc is all zero: the slot's previous frame cleared it behind its report (no fill needed)
+        Brackets ev;
+        bool simple = false;                    // one chunk, k_resolve aside
+        int main_ix = 0;                        // the main stream it traces on
         ftk::FrameReport* h_report = nullptr;   // pinned: the frame's statistic stripes, k_classify's error word and the last chunk's rays per bounce,
         ftk::FrameReport* d_report = nullptr;   // written by the frame's last kernel through this device-side address of the same memory
-        int levels_launched = 0, last_bounce = 0;
         uint64_t signature = 0;                 // what the frame rendered (scene, size, samples, depth, threshold): keys the staged-launch hint
         bool pending = false;
-        uint64_t rays_primary = 0; int64_t n_pix_total = 0; int32_t spp = 0, n_launches = 0, n_chunks = 0, timing = 1, format = 0; bool classify = false;
+        uint64_t rays_primary = 0; int64_t n_pix_total = 0; int32_t spp = 0, n_launches = 0, n_chunks = 0, format = 0; bool classify = false;
         std::chrono::steady_clock::time_point wall0;
+        void release() {
+            d_block_pos.release(); d_pos_block.release(); d_fc.release();
+            if (h_report) (void)hipHostFree(h_report);
+            h_report = nullptr; d_report = nullptr;
+            ev.release();
+        }
     };
     FrameSlot slots[kSlots];
     int slot_turn = 0;
@@ -151,15 +196,8 @@ struct ft_context {
     // so the frame is complete however deep it goes.  -1: no history, launch max_depth levels.
     int staged_hint = -1;
     uint64_t staged_signature = 0;
-    int64_t active_hint = -1;        // active pixels of the last classified frame retired (and its signature): how wide the next frame's windows may be
-    uint64_t active_signature = 0;
-    int64_t window_cap = 64ll << 20; // option "window_cap": listed samples a hinted window may span
-    int64_t primary_reserve = 0;     // option "primary_reserve": workgroup slots a simple frame's k_primary leaves free
     int ray_sets = 0;                // main streams whose pair of ray buffers holds ray_capacity records
-    int mains = 2;                   // option "mains" (1 .. 3): main streams in use (measured: 2 is best - the headline 0.263 / 0.231 / 0.249 ms with 1 / 2 / 3, hollow-sphere x1 0.703 / 0.471 / 0.470); "two_mains" = 0 is mains = 1
-    bool window_hint = false;        // option "window_hint": 1 widens a classified frame's windows by what the last frame of its signature left inactive (see render_single)
     uint64_t commit_serial = 0;
-    bool csg_auto_grow = true;   // ft_render: double csg_mesh_capacity and render again when a hit list overflows
     bool accum_open = false;        // kernel times are being summed over pipelined frames (reset by the next enqueue after a wait)
     // pixel list of the last render, cached across calls with the same resolution and tiles
     std::vector<uint32_t> pixels;
@@ -167,7 +205,6 @@ struct ft_context {
     std::vector<ft_rect> pixel_rects;
     bool pixels_corner = false, pixels_tiled = false;   // the list holds corner-sampling pixels / is made of whole 8x8 tiles
     int last_format = 0;            // 0: the last frame is FP64 RGB in d_out, 1: RGBA8 in d_out8
-    DeviceBuf d_out_index;
     int64_t last_n_pix = 0;
     int32_t last_res_h = 0, last_res_v = 0;
     double k_ms[kStages] = {0, 0, 0, 0, 0};
@@ -199,7 +236,6 @@ template <class T> int32_t upload(ft_context* c, DeviceBuf& b, const std::vector
     if (!v.empty()) FT_HIP(c, hipMemcpyAsync(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, c->stream));
     return FT_OK;
 }
-void release(DeviceBuf& b) { if (b.p) (void)hipFree(b.p); b.p = nullptr; b.bytes = 0; }
 
 bool need_device(ft_context* c) {
     if (!c) return false;
@@ -219,16 +255,11 @@ ftk::RayBuf ray_view(const DeviceBuf& b, int64_t cap) {
 int32_t ensure_frame_buffers(ft_context* c, int64_t cap, bool reflective) {
     int32_t rc;
     if (cap > c->acc_capacity) { for (int k = 0; k < ft_context::kAcc; ++k) if ((rc = ensure(c, c->d_acc[k], (size_t)cap * 24)) != FT_OK) return rc; c->acc_capacity = cap; }
-    if (!reflective || (cap <= c->ray_capacity && c->ray_sets >= c->mains)) return FT_OK;
+    if (!reflective || (cap <= c->ray_capacity && c->ray_sets >= c->opt.mains)) return FT_OK;
     const int64_t want = std::max(cap, c->ray_capacity);
-    for (int i = 0; i < 2 * c->mains; ++i) if ((rc = ensure(c, c->d_rays[i], (size_t)want * (7 * 8 + 4))) != FT_OK) return rc;   // a ping-pong pair per main stream in use
-    c->ray_capacity = want; c->ray_sets = c->mains;
+    for (int i = 0; i < 2 * c->opt.mains; ++i) if ((rc = ensure(c, c->d_rays[i], (size_t)want * (7 * 8 + 4))) != FT_OK) return rc;   // a ping-pong pair per main stream in use
+    c->ray_capacity = want; c->ray_sets = (int)c->opt.mains;
     return FT_OK;
-}
-
-hipEvent_t next_event(ft_context::FrameSlot& f) {
-    if (f.events_used == f.events.size()) { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) return nullptr; f.events.push_back(e); }
-    return f.events[f.events_used++];
 }
 
 // ImagePlane.create (Image.fs:48-53, 67-81), evaluated once per frame on the host.
@@ -270,6 +301,12 @@ bool needs_fancy(const ftd::Material& m) {
     const bool whole = m.shineyness <= 64.0 && m.shineyness == std::floor(m.shineyness);
     return m.roughness != 0.0 || m.texture >= 0 || (m.shineyness > 0.0 && !whole) || m.shineyness != m.shineyness;
 }
+// The context's devices: itself, then its peers.
+std::vector<ft_context*> devices(ft_context* c) {
+    std::vector<ft_context*> devs{c};
+    devs.insert(devs.end(), c->peers.begin(), c->peers.end());
+    return devs;
+}
 size_t lds_bytes_for(const fth::FlatScene& f) {
     const int fold = std::max(1, lane_fold_for(f));
     return (4 * (((size_t)f.csg_capacity + (size_t)fold - 1) / (size_t)fold) + (size_t)f.stack_capacity) * ftk::kBlock * 4;
@@ -294,7 +331,7 @@ static int32_t create_single(int32_t device_id, int count, ft_context** out) {
         if (c->side) (void)hipStreamDestroy(c->side);
         (void)hipStreamDestroy(c->stream); delete c; return FT_ERR_HIP;
     }
-    for (hipStream_t& m : c->more_mains) if (hipStreamCreateWithFlags(&m, hipStreamNonBlocking) != hipSuccess) { m = nullptr; c->mains = 1; }   // (without them every frame takes the one main stream)
+    for (hipStream_t& m : c->more_mains) if (hipStreamCreateWithFlags(&m, hipStreamNonBlocking) != hipSuccess) { m = nullptr; c->opt.mains = 1; }   // (without them every frame takes the one main stream)
     c->n_cu = prop.multiProcessorCount;
     *out = c;
     return FT_OK;
@@ -344,11 +381,11 @@ void ft_destroy(ft_context* c) {
         for (hipStream_t m : c->more_mains) if (m) (void)hipStreamSynchronize(m);
         if (c->side) (void)hipStreamSynchronize(c->side);
         if (c->tail) (void)hipStreamSynchronize(c->tail);
-        DeviceBuf* bufs[] = {&c->d_leaves, &c->d_m2w, &c->d_materials, &c->d_lights, &c->d_program, &c->d_meshes, &c->d_nodes, &c->d_bleaves, &c->d_tris, &c->d_culls, &c->d_tri_orig, &c->d_textures, &c->d_tex_pixels, &c->d_cull_items, &c->d_cull_rows, &c->d_item_pc, &c->d_block_pos[0], &c->d_block_pos[1], &c->d_block_pos[2], &c->d_block_pos[3], &c->d_pos_block[0], &c->d_pos_block[1], &c->d_pos_block[2], &c->d_pos_block[3], &c->d_wave_counts, &c->d_wide, &c->d_mesh_wide, &c->d_coarse, &c->d_ls_pairs, &c->d_ls_nodes, &c->d_ls_tris, &c->d_out_index,
-                             &c->d_rays[0], &c->d_rays[1], &c->d_rays[2], &c->d_rays[3], &c->d_rays[4], &c->d_rays[5], &c->d_acc[0], &c->d_acc[1], &c->d_acc[2], &c->d_out, &c->d_out8, &c->d_pixels, &c->d_jitter, &c->d_fc[0], &c->d_fc[1], &c->d_fc[2], &c->d_fc[3],
-                             &c->d_dbg_in, &c->d_dbg_out};
-        for (auto* b : bufs) release(*b);
-        for (auto& f : c->slots) { f.traced = nullptr; if (f.h_report) { (void)hipHostFree(f.h_report); f.h_report = nullptr; f.d_report = nullptr; } for (auto e : f.events) (void)hipEventDestroy(e); f.events.clear(); }
+        for (DeviceBuf& b : c->d_scene) b.release();
+        for (DeviceBuf& b : c->d_rays) b.release();
+        for (DeviceBuf& b : c->d_acc) b.release();
+        for (DeviceBuf* b : {&c->d_out, &c->d_out8, &c->d_out_index, &c->d_pixels, &c->d_jitter, &c->d_wave_counts, &c->d_dbg_in, &c->d_dbg_out}) b->release();
+        for (auto& f : c->slots) f.release();
         if (c->classified) (void)hipEventDestroy(c->classified);
         for (hipEvent_t& e : c->acc_free) if (e) { (void)hipEventDestroy(e); e = nullptr; }
         if (c->side) (void)hipStreamDestroy(c->side);
@@ -361,44 +398,56 @@ void ft_destroy(ft_context* c) {
 
 const char* ft_last_error(const ft_context* c) { return c ? c->err.c_str() : "null context"; }
 
+// The keys of ft_set_option.  A flag takes any value as 0 / 1; any other value must lie in [lo, hi] (and be 0 or a power of two where
+// kPowerOfTwo says so).  It goes into an Options member of every device of the context, or into device 0's scene graph: the peers
+// receive the scene flattened on device 0.  kCommit / kLevelHint / kZeroFill: a change invalidates the committed scene, the staged
+// level hint, the zero-fill signatures.
+enum { kFlag = 1, kPowerOfTwo = 2, kCommit = 4, kLevelHint = 8, kZeroFill = 16 };
+struct OptionSpec {
+    const char* key;
+    int64_t lo, hi;
+    int64_t Options::* field;
+    void (*to_graph)(fth::SceneGraph&, int64_t);
+    int rules;
+};
+constexpr int64_t kNoLimit = std::numeric_limits<int64_t>::max();
+const OptionSpec kOptions[] = {
+    {"chunk_samples", 64, kNoLimit, &Options::chunk_samples, nullptr, 0},
+    {"wave_samples", 0, 16, &Options::wave_samples, nullptr, kPowerOfTwo},   // 1 .. 16 samples per wavefront (k_resolve's LDS tile holds 16)
+    {"coherent_waves", 0, 1, &Options::coherent_waves, nullptr, kFlag},
+    {"timing", 0, 2, &Options::timing, nullptr, 0},
+    {"classify_pixels", 0, 1, &Options::classify_pixels, nullptr, kFlag},
+    {"follow_below", -1, kNoLimit, &Options::follow_below, nullptr, kLevelHint},
+    {"level_hint", 0, 1, &Options::level_hint, nullptr, kFlag},
+    {"classify_ahead", 0, 1, &Options::classify_ahead, nullptr, kFlag},
+    {"resolve_aside", 0, 1, &Options::resolve_aside, nullptr, kFlag},
+    {"zero_fill_skip", 0, 1, &Options::zero_fill_skip, nullptr, kFlag | kZeroFill},
+    {"mains", 1, ft_context::kMains, &Options::mains, nullptr, 0},
+    {"bvh_builder", 0, 3, &Options::bvh_builder, nullptr, kCommit},
+    {"csg_auto_grow", 0, 1, &Options::csg_auto_grow, nullptr, kFlag},
+    {"csg_mesh_capacity", 1, 255, nullptr, [](fth::SceneGraph& g, int64_t v) { g.csg_mesh_capacity = (int32_t)v; }, kCommit},
+    // 1 (default): directional shadow rays of coherent waves walk light-space trees; 0: the BVH
+    {"light_space_shadows", 0, 1, nullptr, [](fth::SceneGraph& g, int64_t v) { g.light_space_shadows = v != 0; }, kFlag | kCommit},
+    {"mesh_unclipped_bvh", 0, 1, nullptr, [](fth::SceneGraph& g, int64_t v) { g.mesh_unclipped_bvh = v != 0; }, kFlag | kCommit},
+};
+
 int32_t ft_set_option(ft_context* c, const char* key, int64_t value) {
     if (!c || !key) return FT_ERR_INVALID;
-    if (!std::strcmp(key, "chunk_samples")) { if (value < 64) return FT_ERR_INVALID; c->chunk_samples = value; for (ft_context* p : c->peers) p->chunk_samples = value; return FT_OK; }
-    if (!std::strcmp(key, "csg_mesh_capacity")) { if (value < 1 || value > 255) return FT_ERR_INVALID; c->graph.csg_mesh_capacity = (int32_t)value; c->committed = false; return FT_OK; }
-    if (!std::strcmp(key, "coherent_waves")) { c->coherent_waves = value != 0; c->dev_scene.coherent_waves = value != 0 ? 1 : 0; for (ft_context* p : c->peers) { p->coherent_waves = value != 0; p->dev_scene.coherent_waves = c->dev_scene.coherent_waves; } return FT_OK; }
-    if (!std::strcmp(key, "wave_samples")) {
-        int l = 0; while ((1ll << l) < value) ++l;                 // 0: the default (16); 1, 2, 4, 8, 16: that many samples per wavefront (k_resolve's LDS tile holds 16)
-        if (value < 0 || value > 16 || (value > 0 && (1ll << l) != value)) return FT_ERR_INVALID;
-        if (value == 0) l = -1;
-        c->wave_samples_log2 = l; for (ft_context* p : c->peers) p->wave_samples_log2 = l; return FT_OK;
-    }
-    if (!std::strcmp(key, "timing")) { if (value < 0 || value > 2) return FT_ERR_INVALID; c->timing = (int)value; for (ft_context* p : c->peers) p->timing = (int)value; return FT_OK; }
-    if (!std::strcmp(key, "window_cap")) { if (value < 64 || value > (1ll << 30)) return FT_ERR_INVALID; c->window_cap = value; for (ft_context* p : c->peers) p->window_cap = value; return FT_OK; }
-    if (!std::strcmp(key, "primary_reserve")) { if (value < 0 || value > 4096) return FT_ERR_INVALID; c->primary_reserve = value; for (ft_context* p : c->peers) p->primary_reserve = value; return FT_OK; }
-    if (!std::strcmp(key, "two_mains") || !std::strcmp(key, "mains")) {
-        const int m = key[0] == 't' ? (value != 0 ? 2 : 1) : (int)value;
-        if (m < 1 || m > ft_context::kMains) return FT_ERR_INVALID;
-        auto set = [&](ft_context* p) { p->mains = p->more_mains[0] && p->more_mains[1] ? m : 1; };
-        set(c); for (ft_context* p : c->peers) set(p);
+    for (const OptionSpec& o : kOptions) {
+        if (std::strcmp(key, o.key)) continue;
+        if (o.rules & kFlag) value = value != 0;
+        else if (value < o.lo || value > o.hi || ((o.rules & kPowerOfTwo) && (value & (value - 1)))) return FT_ERR_INVALID;
+        if (o.to_graph) { o.to_graph(c->graph, value); c->committed = false; return FT_OK; }
+        for (ft_context* d : devices(c)) {
+            d->opt.*o.field = value;
+            for (hipStream_t m : d->more_mains) if (!m) d->opt.mains = 1;   // (without them every frame takes the one main stream)
+            d->dev_scene.coherent_waves = d->opt.coherent_waves ? 1 : 0;
+            if (o.rules & kCommit) d->committed = false;
+            if (o.rules & kLevelHint) d->staged_hint = -1;
+            if (o.rules & kZeroFill) d->zero_signature[0] = d->zero_signature[1] = 0;
+        }
         return FT_OK;
     }
-    if (!std::strcmp(key, "window_hint")) { c->window_hint = value != 0; for (ft_context* p : c->peers) p->window_hint = value != 0; return FT_OK; }
-    if (!std::strcmp(key, "resolve_aside")) { c->resolve_aside = value != 0; for (ft_context* p : c->peers) p->resolve_aside = value != 0; return FT_OK; }
-    if (!std::strcmp(key, "resolve_blocks")) { if (value < 0 || value > 8) return FT_ERR_INVALID; c->resolve_blocks_cap = (int)value; for (ft_context* p : c->peers) p->resolve_blocks_cap = (int)value; return FT_OK; }
-    if (!std::strcmp(key, "classify_after_trace")) { c->classify_after_trace = value != 0; for (ft_context* p : c->peers) p->classify_after_trace = value != 0; return FT_OK; }
-    if (!std::strcmp(key, "classify_ahead")) { c->classify_ahead = value != 0; for (ft_context* p : c->peers) p->classify_ahead = value != 0; return FT_OK; }
-    if (!std::strcmp(key, "zero_fill_skip")) { c->zero_fill_skip = value != 0; c->zero_signature[0] = c->zero_signature[1] = 0; for (ft_context* p : c->peers) { p->zero_fill_skip = value != 0; p->zero_signature[0] = p->zero_signature[1] = 0; } return FT_OK; }
-    if (!std::strcmp(key, "classify_pixels")) { c->classify_pixels = value != 0; for (ft_context* p : c->peers) p->classify_pixels = value != 0; return FT_OK; }
-    if (!std::strcmp(key, "csg_auto_grow")) { c->csg_auto_grow = value != 0; return FT_OK; }
-    if (!std::strcmp(key, "follow_below")) { if (value < -1) return FT_ERR_INVALID; c->follow_below = value; c->staged_hint = -1; for (ft_context* p : c->peers) { p->follow_below = value; p->staged_hint = -1; } return FT_OK; }
-    if (!std::strcmp(key, "level_hint")) { c->level_hint = value != 0; for (ft_context* p : c->peers) p->level_hint = value != 0; return FT_OK; }
-    if (!std::strcmp(key, "light_space_shadows")) {   // 1 (default): directional shadow rays of coherent waves walk light-space trees; 0: the BVH
-        c->graph.light_space_shadows = value != 0; c->committed = false;
-        for (ft_context* p : c->peers) { p->graph.light_space_shadows = value != 0; p->committed = false; }
-        return FT_OK;
-    }
-    if (!std::strcmp(key, "bvh_builder")) { if (value < 0 || value > 3) return FT_ERR_INVALID; c->bvh_builder = (int)value; c->committed = false; return FT_OK; }
-    if (!std::strcmp(key, "mesh_unclipped_bvh")) { c->graph.mesh_unclipped_bvh = value != 0; c->committed = false; return FT_OK; }
     c->err = std::string("unknown option: ") + key;
     return FT_ERR_INVALID;
 }
@@ -501,7 +550,7 @@ int32_t ft_scene_add_positional(ft_context* c, const double pos[3], const double
 
 static int32_t upload_scene(ft_context* c);
 static int32_t retire_pending(ft_context* c, ft_stats* stats);
-static bool any_pending(const ft_context* c, bool on_second_main = false) { for (const auto& f : c->slots) if (f.pending && (!on_second_main || f.alt)) return true; return false; }
+static bool any_pending(const ft_context* c, bool on_second_main = false) { for (const auto& f : c->slots) if (f.pending && (!on_second_main || f.main_ix != 0)) return true; return false; }
 
 int32_t ft_scene_commit(ft_context* c) {
     if (!c) return FT_ERR_INVALID;
@@ -512,8 +561,8 @@ int32_t ft_scene_commit(ft_context* c) {
     // reserves the ranges, upload_scene fills them.  A build the device refuses (a tree too deep for the traversal stacks) falls
     // back to the host's builder, once, for the whole scene.
     for (int attempt = 0; attempt < 2; ++attempt) {
-        c->graph.device_bvh = !c->host_only && c->bvh_builder >= 1 && attempt == 0;
-        c->graph.device_bvh_min_tris = c->bvh_builder == 2 ? kDeviceBvhMinTris : 0;   // 1: the device's linear BVH, 3: its surface-area tree, whatever the size
+        c->graph.device_bvh = !c->host_only && c->opt.bvh_builder >= 1 && attempt == 0;
+        c->graph.device_bvh_min_tris = c->opt.bvh_builder == 2 ? kDeviceBvhMinTris : 0;   // 1: the device's linear BVH, 3: its surface-area tree, whatever the size
         auto t0 = clock::now();
         int32_t rc = c->graph.flatten(c->flat, c->err);
         c->commit_ms[0] += ms_since(t0);
@@ -543,22 +592,20 @@ int32_t ft_get_commit_times(ft_context* c, double ms[4]) {
 static int32_t upload_scene(ft_context* c) {
     int32_t rc;
     FT_HIP(c, hipSetDevice(c->device));
-    // frames still queued trace the scene these uploads replace, and not all of them on the stream the uploads travel on (FrameSlot::alt)
+    // frames still queued trace the scene these uploads replace, and not all of them on the stream the uploads travel on (FrameSlot::main_ix)
     if (any_pending(c)) { if ((rc = retire_pending(c, nullptr)) != FT_OK) return rc; c->accum_open = false; }
     const fth::FlatScene& f = c->flat;
     if (lane_fold_for(f) == 0) { c->err = "scene needs more than 160 KiB of LDS per workgroup for CSG lists / BSP stacks even with 4 live lanes per wave"; return FT_ERR_UNSUPPORTED; }
-    if ((rc = upload(c, c->d_leaves, f.leaves)) != FT_OK) return rc;
-    if ((rc = upload(c, c->d_m2w, f.m2w)) != FT_OK) return rc;
-    if ((rc = upload(c, c->d_materials, f.materials)) != FT_OK) return rc;
-    if ((rc = upload(c, c->d_lights, f.lights)) != FT_OK) return rc;
-    if ((rc = upload(c, c->d_textures, f.textures)) != FT_OK) return rc;
-    if ((rc = upload(c, c->d_tex_pixels, f.tex_pixels)) != FT_OK) return rc;
-    if ((rc = upload(c, c->d_program, f.program)) != FT_OK) return rc;
-    if ((rc = upload(c, c->d_meshes, f.meshes)) != FT_OK) return rc;
-    if ((rc = upload(c, c->d_nodes, f.nodes)) != FT_OK) return rc;
-    if ((rc = upload(c, c->d_bleaves, f.bsp_leaves)) != FT_OK) return rc;
-    if ((rc = upload(c, c->d_tris, f.tris)) != FT_OK) return rc;
-    if ((rc = upload(c, c->d_culls, f.culls)) != FT_OK) return rc;
+    ftk::DevScene& S = c->dev_scene;
+    rc = FT_OK;
+    auto put = [&](SceneArray k, const auto& v, auto*& ptr) {   // array k into its buffer, and the device scene's pointer to it
+        if (rc == FT_OK) rc = upload(c, c->d_scene[k], v);
+        ptr = static_cast<std::remove_reference_t<decltype(ptr)>>(c->d_scene[k].p);
+    };
+    put(kLeaves, f.leaves, S.leaves); put(kM2w, f.m2w, S.m2w); put(kMaterials, f.materials, S.materials); put(kLights, f.lights, S.lights);
+    put(kTextures, f.textures, S.textures); put(kTexPixels, f.tex_pixels, S.tex_pixels); put(kProgram, f.program, S.program);
+    put(kMeshes, f.meshes, S.meshes); put(kNodes, f.nodes, S.nodes); put(kBspLeaves, f.bsp_leaves, S.bsp_leaves); put(kTris, f.tris, S.tris);
+    put(kCulls, f.culls, S.culls);
     {   // behind the items' float records: a float image of every parallel-sensitive direction (x, y, z, its length rounded up), which lane k of a
         // coherent wave tests against the bundle's cone before any ray is tested against it exactly (rows_nearly_parallel, ft_kernels.hip)
         std::vector<float>& v = c->cull_items_and_rows;
@@ -569,28 +616,24 @@ static int32_t upload_scene(ft_context* c) {
             float lf = (float)len; while ((double)lf < len) lf = std::nextafter(lf, std::numeric_limits<float>::infinity());
             v.push_back((float)f.cull_rows[k]); v.push_back((float)f.cull_rows[k + 1]); v.push_back((float)f.cull_rows[k + 2]); v.push_back(lf);
         }
-        if ((rc = upload(c, c->d_cull_items, v)) != FT_OK) return rc;
+        put(kCullItems, v, S.cull_items);
     }
-    if ((rc = upload(c, c->d_cull_rows, f.cull_rows)) != FT_OK) return rc;
-    if ((rc = upload(c, c->d_item_pc, f.item_pc)) != FT_OK) return rc;
-    if ((rc = upload(c, c->d_wide, f.wide)) != FT_OK) return rc;
-    if ((rc = upload(c, c->d_mesh_wide, f.mesh_wide)) != FT_OK) return rc;
-    if ((rc = upload(c, c->d_coarse, f.coarse_boxes)) != FT_OK) return rc;
-    if ((rc = upload(c, c->d_tri_orig, f.tri_orig)) != FT_OK) return rc;
-    if ((rc = upload(c, c->d_ls_pairs, f.ls_pairs)) != FT_OK) return rc;
-    if ((rc = upload(c, c->d_ls_nodes, f.ls_nodes)) != FT_OK) return rc;
-    if ((rc = upload(c, c->d_ls_tris, f.ls_tris)) != FT_OK) return rc;
-    for (int k = 0; k < ft_context::kSlots; ++k) { if ((rc = ensure(c, c->d_fc[k], sizeof(ftk::FrameCounters))) != FT_OK) return rc; c->fc_clean[k] = false; }
+    put(kCullRows, f.cull_rows, S.cull_rows); put(kItemPc, f.item_pc, S.item_pc); put(kWide, f.wide, S.wide); put(kMeshWide, f.mesh_wide, S.mesh_wide);
+    put(kCoarse, f.coarse_boxes, S.coarse_boxes); put(kTriOrig, f.tri_orig, S.tri_orig);
+    put(kLsPairs, f.ls_pairs, S.ls_pairs); put(kLsNodes, f.ls_nodes, S.ls_nodes); put(kLsTris, f.ls_tris, S.ls_tris);
+    if (rc != FT_OK) return rc;
+    for (auto& F : c->slots) { if ((rc = ensure(c, F.d_fc, sizeof(ftk::FrameCounters))) != FT_OK) return rc; F.fc_clean = false; }
     c->zero_signature[0] = c->zero_signature[1] = 0;
     FT_HIP(c, hipStreamSynchronize(c->stream));
     {   // the BVHs the flattener left to the device (ft_bvh.hip), straight into the ranges reserved in the arrays just uploaded
         const auto t0 = std::chrono::steady_clock::now();
         uint32_t tallest = 0;
         for (const fth::FlatScene::BvhJob& j : f.bvh_jobs) {
-            const ftk::LbvhTarget t{c->d_tris.as<double>(), j.first_global, j.n, c->d_nodes.as<ftd::BspNode>(), j.node_base, c->d_bleaves.as<ftd::BspLeaf>(), j.leaf_base,
-                                    c->d_tri_orig.as<uint32_t>(), j.tri_base, c->d_wide.as<double>(), j.wide_base, c->d_coarse.as<float>() + 6 * (size_t)j.coarse_first, j.coarse_count};
+            const DeviceBuf* B = c->d_scene;
+            const ftk::LbvhTarget t{B[kTris].as<double>(), j.first_global, j.n, B[kNodes].as<ftd::BspNode>(), j.node_base, B[kBspLeaves].as<ftd::BspLeaf>(), j.leaf_base,
+                                    B[kTriOrig].as<uint32_t>(), j.tri_base, B[kWide].as<double>(), j.wide_base, B[kCoarse].as<float>() + 6 * (size_t)j.coarse_first, j.coarse_count};
             uint32_t height = 0;
-            FT_HIP(c, ftk::build_lbvh(c->stream, t, &height, c->bvh_builder == 1 ? 0 : 1));
+            FT_HIP(c, ftk::build_lbvh(c->stream, t, &height, c->opt.bvh_builder == 1 ? 0 : 1));
             // height 0: a non-finite coordinate; > 40: deeper than the packet walk's 64-entry stack allows (3 entries per 4-wide level)
             if (height == 0 || height > 40) { c->err = "device BVH build refused (non-finite vertex or a tree deeper than 40 levels): the host builder takes over"; return FT_ERR_BUILD; }
             tallest = std::max(tallest, height);
@@ -602,17 +645,7 @@ static int32_t upload_scene(ft_context* c) {
             if (lane_fold_for(c->flat) == 0) { c->err = "scene needs more than 160 KiB of LDS per workgroup for CSG lists / BSP stacks even with 4 live lanes per wave"; return FT_ERR_UNSUPPORTED; }
         }
     }
-    ftk::DevScene& S = c->dev_scene;
-    S.leaves = c->d_leaves.as<double>(); S.m2w = c->d_m2w.as<double>();
-    S.materials = c->d_materials.as<ftd::Material>(); S.lights = c->d_lights.as<ftd::Light>(); S.textures = c->d_textures.as<ftd::Texture>();
-    S.program = c->d_program.as<uint32_t>(); S.meshes = c->d_meshes.as<ftd::Mesh>();
-    S.nodes = c->d_nodes.as<ftd::BspNode>(); S.bsp_leaves = c->d_bleaves.as<ftd::BspLeaf>(); S.tris = c->d_tris.as<double>(); S.culls = c->d_culls.as<double>(); S.tri_orig = c->d_tri_orig.as<uint32_t>(); S.tex_pixels = c->d_tex_pixels.as<uint8_t>();
-    S.coarse_boxes = c->d_coarse.as<float>();
-    S.cull_items = c->d_cull_items.as<float>(); S.cull_rows = c->d_cull_rows.as<double>();
-    S.wide = c->d_wide.as<double>(); S.mesh_wide = c->d_mesh_wide.as<int32_t>();
-    S.ls_pairs = c->d_ls_pairs.as<double>(); S.ls_nodes = c->d_ls_nodes.as<uint32_t>(); S.ls_tris = c->d_ls_tris.as<double>();
-    S.item_pc = c->d_item_pc.as<uint32_t>();
-    S.coherent_waves = c->coherent_waves ? 1 : 0;
+    S.coherent_waves = c->opt.coherent_waves ? 1 : 0;
     S.n_simd = c->n_cu * 4;
     S.n_items = (int32_t)f.item_pc.size() - 1; S.n_cull_rows = f.cull_bundle ? (int32_t)(f.cull_rows.size() / 3) : -1;
     S.n_leaves = (int32_t)f.leaves.size(); S.n_lights = (int32_t)f.lights.size();
@@ -630,7 +663,7 @@ static int32_t upload_scene(ft_context* c) {
     c->blocks_bounce = ftk::occupancy_blocks_bounce(lds, c->variant);
     c->blocks_resolve = ftk::occupancy_blocks_resolve();
     c->committed = true;
-    ++c->commit_serial; c->staged_hint = -1; c->active_hint = -1;
+    ++c->commit_serial; c->staged_hint = -1;
     return FT_OK;
 }
 
@@ -701,8 +734,7 @@ static void on_every_device(ft_context* c, const std::vector<bool>& take, const 
 static int32_t fetch_all(ft_context* c, void* out, int format) {
     if (!c || !out) return FT_ERR_INVALID;
     if (!need_device(c)) return FT_ERR_NO_DEVICE;
-    std::vector<ft_context*> devs{c};
-    devs.insert(devs.end(), c->peers.begin(), c->peers.end());
+    const std::vector<ft_context*> devs = devices(c);
     std::vector<ft_context*> with;
     for (ft_context* d : devs) if (d->last_n_pix > 0) with.push_back(d);
     if (with.empty()) { c->err = "no frame rendered yet"; return FT_ERR_STATE; }
@@ -728,16 +760,13 @@ struct RenderRequest {
 };
 static int32_t render_single(ft_context* c, const RenderRequest& q, void* out, ft_stats* stats, bool defer);
 static int32_t retire_frame(ft_context* c, ft_context::FrameSlot& f, ft_stats* stats);
-static int32_t retire_pending(ft_context* c, ft_stats* stats);
 static int32_t render_frame(ft_context* c, const RenderRequest& q, void* out, ft_stats* stats, bool defer);
 
 static int32_t with_growing_hit_lists(ft_context* c, const std::function<int32_t()>& run) {
     // Frames still queued by ft_render_enqueue are retired first, so that an overflow of one of THEM is reported as what it is
     // (queued frames are not rendered again) instead of being taken for this call's.
     if (!c->host_only) {
-        std::vector<ft_context*> devs{c};
-        devs.insert(devs.end(), c->peers.begin(), c->peers.end());
-        for (ft_context* d : devs) {
+        for (ft_context* d : devices(c)) {
             if (!any_pending(d)) continue;
             if (hipSetDevice(d->device) != hipSuccess) { c->err = "hipSetDevice failed"; return FT_ERR_NO_DEVICE; }
             const int32_t prc = retire_pending(d, nullptr);
@@ -746,7 +775,7 @@ static int32_t with_growing_hit_lists(ft_context* c, const std::function<int32_t
         }
     }
     int32_t rc = run();
-    while (rc == FT_ERR_OVERFLOW && c->csg_auto_grow && c->graph.csg_mesh_capacity < 255) {
+    while (rc == FT_ERR_OVERFLOW && c->opt.csg_auto_grow && c->graph.csg_mesh_capacity < 255) {
         const int32_t before = c->graph.csg_mesh_capacity;
         const std::string why = c->err;
         c->graph.csg_mesh_capacity = std::min(255, before * 2);
@@ -799,13 +828,20 @@ static std::vector<std::vector<ft_rect>> band_shares(const RenderRequest& q, siz
     return share;
 }
 
+static int32_t check_request(ft_context* c, const RenderRequest& q) {
+    if (!q.cam || q.res_h < 2 || q.res_v < 2 || q.spp < 0 || (q.spp > 0 && !q.jitter_xy) || q.max_depth < 0 || (q.tiles && q.n_tiles < 1)) { c->err = "bad ft_render argument"; return FT_ERR_INVALID; }
+    if (q.max_depth > ftk::kMaxBounce) { c->err = "max_depth above 16"; return FT_ERR_UNSUPPORTED; }
+    if ((int64_t)q.res_h * q.res_v > (int64_t)0x7FFFFFFF) { c->err = "resolution too large"; return FT_ERR_INVALID; }
+    return FT_OK;
+}
+
 static int32_t render_frame(ft_context* c, const RenderRequest& q, void* out, ft_stats* stats, bool defer) {
+    const int32_t rc = check_request(c, q);
+    if (rc != FT_OK) return rc;
     if (c->peers.empty() || c->host_only) return render_single(c, q, out, stats, defer);
-    if (!q.cam || q.res_h < 2 || q.res_v < 2 || (q.tiles && q.n_tiles < 1)) { c->err = "bad ft_render argument"; return FT_ERR_INVALID; }
     if (!c->committed) { c->err = "scene not committed (ft_scene_commit)"; return FT_ERR_STATE; }
     const auto wall0 = std::chrono::steady_clock::now();
-    std::vector<ft_context*> devs{c};
-    devs.insert(devs.end(), c->peers.begin(), c->peers.end());
+    const std::vector<ft_context*> devs = devices(c);
     const std::vector<std::vector<ft_rect>> share = band_shares(q, devs.size());
     std::vector<int32_t> rcs(devs.size(), FT_OK);
     std::vector<ft_stats> sts(devs.size());
@@ -827,62 +863,65 @@ static int32_t render_frame(ft_context* c, const RenderRequest& q, void* out, ft
     return FT_OK;
 }
 
-static int32_t render_single(ft_context* c, const RenderRequest& q, void* out, ft_stats* stats, bool defer) {
-    if (!c) return FT_ERR_INVALID;
-    const ft_camera* cam = q.cam;
-    const int32_t res_h = q.res_h, res_v = q.res_v, max_depth = q.max_depth, n_tiles = q.n_tiles;
-    const ft_rect* tiles = q.tiles;
-    const double* jitter_xy = q.jitter_xy;
-    const uint64_t seed = q.seed;
-    int32_t spp = q.spp;
-    if (!cam || res_h < 2 || res_v < 2 || spp < 0 || (spp > 0 && !jitter_xy) || max_depth < 0 || (tiles && n_tiles < 1)) { c->err = "bad ft_render argument"; return FT_ERR_INVALID; }
-    if (max_depth > ftk::kMaxBounce) { c->err = "max_depth above 16"; return FT_ERR_UNSUPPORTED; }
-    if ((int64_t)res_h * res_v > (int64_t)0x7FFFFFFF) { c->err = "resolution too large"; return FT_ERR_INVALID; }
-    if (!need_device(c)) return FT_ERR_NO_DEVICE;
-    if (!c->committed) { c->err = "scene not committed (ft_scene_commit)"; return FT_ERR_STATE; }
-    const bool corner = spp == 0;                                  // CornerSampling.strategy (Image.fs:125-150): one ray per pixel corner
-    if (corner) { spp = 1; }
-    const auto wall0 = std::chrono::steady_clock::now();
-    FT_HIP(c, hipSetDevice(c->device));
+// What a frame is, decided on the host from the request and the context's cached state before anything is queued (plan_pixels,
+// plan_chunks); queue_frame then puts it on the device.
+struct FramePlan {
+    struct Job { uint32_t id_base, n_ids, w, h, out_base, n_out; };   // a chunk: a window of the pixel list, or a corner grid
+    std::vector<ft_rect> rects;          // the tiles clipped to the frame
+    bool corner = false;                 // CornerSampling.strategy (Image.fs:125-150): one ray per pixel corner
+    bool same_list = false;              // the context's pixel list, and d_pixels, already are this frame's
+    std::vector<uint32_t> corner_ids;    // corner frames: the ids of the corner rays, what d_pixels must hold
+    std::vector<Job> jobs;
+    std::vector<double> jitter;          // what d_jitter must hold
+    int32_t spp = 0;
+    int64_t n_pix_total = 0;
+    bool classify = false;
+    bool simple = false;                 // a queued frame of one chunk: k_resolve aside, k_primary on the next main stream (queue_frame)
+    double jitter_extent = 1.0;
+    uint64_t signature = 0;              // scene, size, samples, depth, list, chunking: keys the level hint
+    uint64_t zsig = 0;                   // what decides which blocks k_classify finishes: keys the zero-fill skip
+    int64_t pix_per_chunk = 0, cap = 0;
+    int group_log2 = 0, last_bounce = 0;
+    ftk::Camera cam{};
+};
 
-    // Pixel list restricted to the tiles.  The reference enumerates pixels y-major, x (Image.fs:104); samples are
-    // independent, so the device is free to walk them in any order: rects whose sides are multiples of 8 are
-    // walked in 8x8 pixel blocks, which makes the 64 lanes of a wavefront a compact bundle of rays.
-    const bool whole = tiles == nullptr;
-    std::vector<ft_rect> rects;
-    if (whole) rects.push_back(ft_rect{0, 0, res_h, res_v});
-    else for (int k = 0; k < n_tiles; ++k) {
-        ft_rect r = tiles[k];
+// Pixel list restricted to the tiles.  The reference enumerates pixels y-major, x (Image.fs:104); samples are
+// independent, so the device is free to walk them in any order: rects whose sides are multiples of 8 are
+// walked in 8x8 pixel blocks, which makes the 64 lanes of a wavefront a compact bundle of rays.
+static void plan_pixels(ft_context* c, const RenderRequest& q, FramePlan& p) {
+    const int32_t res_h = q.res_h, res_v = q.res_v;
+    p.corner = q.spp == 0;
+    p.spp = p.corner ? 1 : q.spp;
+    if (!q.tiles) p.rects.push_back(ft_rect{0, 0, res_h, res_v});
+    else for (int k = 0; k < q.n_tiles; ++k) {
+        ft_rect r = q.tiles[k];
         if (r.x0 < 0) { r.w += r.x0; r.x0 = 0; }
         if (r.y0 < 0) { r.h += r.y0; r.y0 = 0; }
         if (r.x0 + r.w > res_h) r.w = res_h - r.x0;
         if (r.y0 + r.h > res_v) r.h = res_v - r.y0;
-        if (r.w > 0 && r.h > 0) rects.push_back(r);
+        if (r.w > 0 && r.h > 0) p.rects.push_back(r);
     }
-    const bool same_list = !corner && !c->pixels_corner && c->last_n_pix > 0 && c->last_res_h == res_h && c->last_res_v == res_v &&
-                           c->pixel_rects.size() == rects.size() && (rects.empty() || std::memcmp(c->pixel_rects.data(), rects.data(), rects.size() * sizeof(ft_rect)) == 0);
-    struct Job { uint32_t id_base, n_ids, w, h, out_base, n_out; };
-    std::vector<Job> jobs;
-    std::vector<uint32_t> corner_ids;
-    if (corner) {
+    const std::vector<ft_rect>& rects = p.rects;
+    p.same_list = !p.corner && !c->pixels_corner && c->last_n_pix > 0 && c->last_res_h == res_h && c->last_res_v == res_v &&
+                  c->pixel_rects.size() == rects.size() && (rects.empty() || std::memcmp(c->pixel_rects.data(), rects.data(), rects.size() * sizeof(ft_rect)) == 0);
+    std::vector<uint32_t>& px = c->pixels;
+    if (p.corner) {
         // Each rect (split by rows so that its corner grid fits one chunk) is a job of (w+1) x (h+1) corner rays.
-        std::vector<uint32_t>& px = c->pixels;
         px.clear();
         const uint32_t cs = (uint32_t)res_h + 1;
         for (const ft_rect& r : rects) {
-            int64_t max_rows = c->chunk_samples / (r.w + 1) - 1;
+            int64_t max_rows = c->opt.chunk_samples / (r.w + 1) - 1;
             if (max_rows < 1) max_rows = 1;
             for (int y0 = r.y0; y0 < r.y0 + r.h; y0 += (int)max_rows) {
                 const int h = (int)std::min<int64_t>(max_rows, r.y0 + r.h - y0);
-                Job j{(uint32_t)corner_ids.size(), (uint32_t)((r.w + 1) * (h + 1)), (uint32_t)r.w, (uint32_t)h, (uint32_t)px.size(), (uint32_t)(r.w * h)};
-                for (int y = y0; y <= y0 + h; ++y) for (int x = r.x0; x <= r.x0 + r.w; ++x) corner_ids.push_back((uint32_t)y * cs + (uint32_t)x);
+                FramePlan::Job j{(uint32_t)p.corner_ids.size(), (uint32_t)((r.w + 1) * (h + 1)), (uint32_t)r.w, (uint32_t)h, (uint32_t)px.size(), (uint32_t)(r.w * h)};
+                for (int y = y0; y <= y0 + h; ++y) for (int x = r.x0; x <= r.x0 + r.w; ++x) p.corner_ids.push_back((uint32_t)y * cs + (uint32_t)x);
                 for (int y = y0; y < y0 + h; ++y) for (int x = r.x0; x < r.x0 + r.w; ++x) px.push_back((uint32_t)(y * res_h + x));
-                jobs.push_back(j);
+                p.jobs.push_back(j);
             }
         }
         c->pixel_rects = rects; c->pixels_corner = true; c->pixels_tiled = false; c->last_n_pix = 0;
-    } else if (!same_list) {
-        std::vector<uint32_t>& px = c->pixels;
+    } else if (!p.same_list) {
         px.clear();
         bool tiled = true;
         for (const ft_rect& r : rects) {
@@ -901,101 +940,207 @@ static int32_t render_single(ft_context* c, const RenderRequest& q, void* out, f
         }
         c->pixel_rects = rects; c->pixels_corner = false; c->pixels_tiled = tiled; c->last_n_pix = 0;
     }
-    const std::vector<uint32_t>& pixels = c->pixels;
-    const int64_t n_pix_total = (int64_t)pixels.size();
-    if (stats) std::memset(stats, 0, sizeof *stats);
-    if (n_pix_total == 0) return FT_OK;
+    p.n_pix_total = (int64_t)px.size();
+}
 
-    int32_t rc;
+// Classification, signatures and chunking of a frame with a non-empty pixel list.
+static void plan_chunks(ft_context* c, const RenderRequest& q, bool defer, FramePlan& p) {
+    const int64_t n_pix_total = p.n_pix_total, spp = p.spp;
+    const int64_t chunk_samples = c->opt.chunk_samples;
     // k_classify bounds every sample of a pixel by a square of +-extent pixels around its centre.  The reference's offsets lie in the
     // unit disc (Jitter.fs:15-21) but the pattern is the caller's: the square follows the pattern, and a pattern with a non-finite
     // or absurd offset turns classification off instead of bounding nothing.
-    double jitter_extent = 1.0;
     bool jitter_bounded = true;
-    if (!corner) for (size_t k = 0; k < 2 * (size_t)spp; ++k) { const double v = jitter_xy[k]; if (!(std::fabs(v) <= 64.0)) jitter_bounded = false; else jitter_extent = std::max(jitter_extent, std::fabs(v)); }
+    if (!p.corner) for (size_t k = 0; k < 2 * (size_t)spp; ++k) { const double v = q.jitter_xy[k]; if (!(std::fabs(v) <= 64.0)) jitter_bounded = false; else p.jitter_extent = std::max(p.jitter_extent, std::fabs(v)); }
     // k_classify applies to pinhole cameras over pixel lists made of 8x8 tiles and scenes in which every top-level item is bounded (with
     // a ground plane in view an exact plane test does find the sky blocks - 20 % of night-house - but the denser first chunk makes the
     // shading slower than the blocks save).  A classified frame's chunks are windows of its ACTIVE pixel list, usually a fraction
     // of the frame: they are twice as wide (measured at 1080p x 16 in round 1: bunny 0.58 -> 0.55 ms, hollow-sphere 6.1 -> 5.8, sample
     // 1.64 -> 1.50; the unclassified night-house loses 14 % at that width and keeps the narrow one).
-    const bool classify = c->classify_pixels && jitter_bounded && !corner && c->pixels_tiled && !cam->has_focus && c->flat.cull_bundle && c->flat.item_pc.size() > 1 && !c->flat.unbounded;
-    uint64_t signature = c->commit_serial * 0x9E3779B97F4A7C15ull;
-    for (uint64_t v : {(uint64_t)res_h, (uint64_t)res_v, (uint64_t)spp, (uint64_t)max_depth, (uint64_t)n_pix_total, (uint64_t)c->chunk_samples, (uint64_t)(corner ? 1 : 0)})
-        signature = (signature ^ v) * 0x100000001B3ull;
+    p.classify = c->opt.classify_pixels && jitter_bounded && !p.corner && c->pixels_tiled && !q.cam->has_focus && c->flat.cull_bundle && c->flat.item_pc.size() > 1 && !c->flat.unbounded;
+    p.signature = c->commit_serial * 0x9E3779B97F4A7C15ull;
+    for (uint64_t v : {(uint64_t)q.res_h, (uint64_t)q.res_v, (uint64_t)spp, (uint64_t)q.max_depth, (uint64_t)n_pix_total, (uint64_t)chunk_samples, (uint64_t)(p.corner ? 1 : 0)})
+        p.signature = (p.signature ^ v) * 0x100000001B3ull;
     // (round 3: five times as wide, not twice - 80 Mi listed samples.  A frame of one window is a SIMPLE frame below: its k_resolve goes aside and its
     //  k_primary to the other main stream.  A rank's eighth of 3840x2160x64 - 66 M listed samples, 5 M of them active - was two windows, the
     //  second one empty: 0.458 -> 0.417 ms per frame as one; its half 1.69 -> 1.62, its quarter and the whole frame unchanged, tools/rank_share_ab.py)
     // An unclassified frame without soft lights is worth one chunk of twice the width for the same reason (night-house-det 1080p x 16: two
     // chunks 2.60 ms, one - a simple, pipelined frame - 2.46); with soft lights the narrow chunks still win (night-house: 3.62 against 3.75).
-    int64_t chunk_budget = classify ? 5 * c->chunk_samples : ((c->variant & 2) ? c->chunk_samples : 2 * c->chunk_samples);
     // The windows of a classified frame are cut from its LISTED pixels (the host does not know the active list's length when it queues
     // them), so a sparse frame is one window of work and a row of launches that find theirs empty (~20 us each: k_primary + k_resolve +
-    // the counter fill; 3840x2160x64 of the bunny: 16 windows, 14 empty).  Option "window_hint" = 1: when the last frame of this
-    // signature kept one pixel in `widen`, windows up to `widen` times as wide (at most "window_cap" listed samples) still hold no more
-    // ACTIVE samples than the measured optimum.  OFF by default - measured (tools/window_hint_ab.py, tools/window_sweep.py): the empty
-    // launches go (`other` 0.33 -> 0.23 ms on that frame) but k_primary over the SAME active samples runs 0 - 9 % slower behind wider
-    // colour planes, varying from one allocation of the planes to the next (the stride between the planes is not it: padding it changed
-    // nothing): a rank's quarter gains 4 %, a half loses 3 - 7 %, an eighth and the whole frame stay where they were.
-    if (classify && c->window_hint && c->active_hint >= 0 && c->active_signature == signature) {
-        const int64_t widen = std::max<int64_t>(1, std::min<int64_t>(16, n_pix_total / std::max<int64_t>(64, c->active_hint)));
-        chunk_budget = std::max(chunk_budget, std::min(c->window_cap, chunk_budget * widen));
-    }
-    int64_t pix_per_chunk = std::max<int64_t>(1, std::min<int64_t>(n_pix_total, chunk_budget / spp));
-    if (pix_per_chunk > 64) {
+    // the counter fill; 3840x2160x64 of the bunny: 16 windows, 14 empty).  Windows widened by the last frame's active count measured no
+    // net gain.
+    const int64_t chunk_budget = p.classify ? 5 * chunk_samples : ((c->variant & 2) ? chunk_samples : 2 * chunk_samples);
+    p.pix_per_chunk = std::max<int64_t>(1, std::min<int64_t>(n_pix_total, chunk_budget / spp));
+    if (p.pix_per_chunk > 64) {
         // equal chunks rather than full ones and a remainder: a short last chunk is all latency (measured on night-house at
         // 1080p x 16: 25 M + 8 M samples 5.35 ms, 2 x 16.6 M 4.83 ms); 8x8 blocks (= wavefronts) stay whole
-        const int64_t n_chunks = (n_pix_total + pix_per_chunk - 1) / pix_per_chunk;
+        const int64_t n_chunks = (n_pix_total + p.pix_per_chunk - 1) / p.pix_per_chunk;
         const int64_t even = ((n_pix_total + n_chunks - 1) / n_chunks + 63) / 64 * 64;
-        pix_per_chunk -= pix_per_chunk % 64;
-        if (even < pix_per_chunk) pix_per_chunk = even;
+        p.pix_per_chunk -= p.pix_per_chunk % 64;
+        if (even < p.pix_per_chunk) p.pix_per_chunk = even;
     }
-    int64_t cap = pix_per_chunk * spp;
-    if (corner) { cap = 1; for (auto& j : jobs) cap = std::max<int64_t>(cap, j.n_ids); }
-    else for (int64_t p0 = 0; p0 < n_pix_total; p0 += pix_per_chunk) {
-        const uint32_t n = (uint32_t)std::min<int64_t>(pix_per_chunk, n_pix_total - p0);
-        jobs.push_back(Job{(uint32_t)p0, n, 0, 0, (uint32_t)p0, n});
+    p.cap = p.pix_per_chunk * spp;
+    if (p.corner) { p.cap = 1; for (auto& j : p.jobs) p.cap = std::max<int64_t>(p.cap, j.n_ids); }
+    else for (int64_t p0 = 0; p0 < n_pix_total; p0 += p.pix_per_chunk) {
+        const uint32_t n = (uint32_t)std::min<int64_t>(p.pix_per_chunk, n_pix_total - p0);
+        p.jobs.push_back(FramePlan::Job{(uint32_t)p0, n, 0, 0, (uint32_t)p0, n});
     }
-    if (cap > 0x7FFFFFFFll) { c->err = "chunk too large"; return FT_ERR_INVALID; }
-    const int last_bounce = c->flat.any_reflective ? max_depth : 0;   // no reflective material ⇒ no reflection rays are ever spawned
-    if ((rc = ensure_frame_buffers(c, cap, last_bounce > 0)) != FT_OK) return rc;
-    const size_t frame_pixels = (size_t)res_h * (size_t)res_v;
-    {
-        DeviceBuf& ob = q.format == 1 ? c->d_out8 : c->d_out;
-        const void* before = ob.p;
-        if ((rc = ensure(c, ob, frame_pixels * (q.format == 1 ? 4 : 24))) != FT_OK) return rc;
-        if (ob.p != before) c->zero_signature[q.format] = 0;       // a new allocation holds nothing yet
-    }
-    std::vector<double> jit;
-    if (corner) jit = {-0.5, 0.5};                                 // Image.fs:131
-    else jit.assign(jitter_xy, jitter_xy + 2 * (size_t)spp);
-    // The uploads below travel on the first main stream: a frame still tracing on the second one (FrameSlot::alt), or one whose k_resolve is
+    p.last_bounce = c->flat.any_reflective ? q.max_depth : 0;   // no reflective material ⇒ no reflection rays are ever spawned
+    if (p.corner) p.jitter = {-0.5, 0.5};                        // Image.fs:131
+    else p.jitter.assign(q.jitter_xy, q.jitter_xy + 2 * (size_t)spp);
+    p.cam = make_camera(*q.cam, q.res_h, q.res_v);
+    // Samples per bounce-0 wavefront (slot_at, ft_kernels.hip): 2^group_log2 samples of 64 / 2^group_log2 pixels when the sample count
+    // has that power of two in it and the list is made of whole 8x8 blocks.  Narrow bundles pay most where a wave walks a BVH
+    // (measured at 1080p x 16, 1 -> 16 samples per wave: bunny through BSP leaves 1.46 -> 1.29 ms, night-house 4.63 -> 4.45).
+    const int64_t most = c->opt.wave_samples > 0 ? c->opt.wave_samples : 16;
+    if (!p.corner && c->pixels_tiled) while ((2ll << p.group_log2) <= most && !((spp >> p.group_log2) & 1)) ++p.group_log2;
+    p.zsig = p.signature;
+    auto mix = [&](const void* v, size_t n) { const unsigned char* b = static_cast<const unsigned char*>(v); for (size_t k = 0; k < n; ++k) p.zsig = (p.zsig ^ b[k]) * 0x100000001B3ull; };
+    mix(&p.cam, sizeof p.cam); mix(&p.jitter_extent, sizeof p.jitter_extent);
+    if (!p.rects.empty()) mix(p.rects.data(), p.rects.size() * sizeof(ft_rect));
+    p.zsig |= 1ull;                                              // never 0: 0 means "nothing known about the buffer"
+    // Queued frames of one chunk put k_resolve on its own stream (blocking frames have nothing to hide it in).  A frame cut into many
+    // windows (3840x2160x64: 16, most of them empty behind the classification) pays an event pair per window and gains nothing - the windows'
+    // small launches already overlap on one stream (measured: 3.46 -> 3.63 ms with it, profiles/r03_z_overlap_by_scene.json)
+    p.simple = defer && c->opt.resolve_aside && !p.corner && c->opt.timing < 2 && p.jobs.size() == 1;
+}
+
+// Frame buffers, the output frame and the pixel list / jitter pattern on the device.  `queued`: something this frame's k_classify
+// reads is still on its way on the first main stream.
+static int32_t upload_frame_inputs(ft_context* c, const RenderRequest& q, const FramePlan& p, bool& queued) {
+    int32_t rc;
+    if ((rc = ensure_frame_buffers(c, p.cap, p.last_bounce > 0)) != FT_OK) return rc;
+    DeviceBuf& ob = q.format == 1 ? c->d_out8 : c->d_out;
+    const void* before = ob.p;
+    if ((rc = ensure(c, ob, (size_t)q.res_h * (size_t)q.res_v * (q.format == 1 ? 4 : 24))) != FT_OK) return rc;
+    if (ob.p != before) c->zero_signature[q.format] = 0;          // a new allocation holds nothing yet
+    const bool new_jitter = p.jitter != c->jitter_on_device;      // frames usually reuse the pattern: skip the staged host-to-device copy
+    queued = p.corner || !p.same_list || new_jitter;
+    // The uploads below travel on the first main stream: a frame still tracing on the second one (FrameSlot::main_ix), or one whose k_resolve is
     // still to run on the tail stream (it reads the pixel list), reads what they replace.
-    if ((corner || !same_list || jit != c->jitter_on_device) && any_pending(c)) {
-        int32_t prc = retire_pending(c, nullptr); if (prc != FT_OK) return prc;
-    }
-    if (corner) {
-        if ((rc = upload(c, c->d_pixels, corner_ids)) != FT_OK) return rc;
-        if ((rc = upload(c, c->d_out_index, pixels)) != FT_OK) return rc;
-    } else if (!same_list) { if ((rc = upload(c, c->d_pixels, pixels)) != FT_OK) return rc; }
-    bool jitter_uploaded = false;
-    if (jit != c->jitter_on_device) {                              // frames usually reuse the pattern: skip the staged host-to-device copy
-        c->jitter_on_device = jit;                                 // (the copy source outlives this call)
+    if (queued && any_pending(c) && (rc = retire_pending(c, nullptr)) != FT_OK) return rc;
+    if (p.corner) {
+        if ((rc = upload(c, c->d_pixels, p.corner_ids)) != FT_OK) return rc;
+        if ((rc = upload(c, c->d_out_index, c->pixels)) != FT_OK) return rc;
+    } else if (!p.same_list && (rc = upload(c, c->d_pixels, c->pixels)) != FT_OK) return rc;
+    if (new_jitter) {
+        c->jitter_on_device = p.jitter;                            // (the copy source outlives this call)
         if ((rc = upload(c, c->d_jitter, c->jitter_on_device)) != FT_OK) return rc;
-        jitter_uploaded = true;
     }
+    return FT_OK;
+}
+
+// The whole frame is classified once; the chunks then take consecutive windows of the frame's ACTIVE pixel list, so a sparse
+// frame is one chunk of real work and launches that find their window empty return at once.
+static int32_t queue_classify(ft_context* c, const RenderRequest& q, const FramePlan& p, ft_context::FrameSlot& F, bool ahead) {
+    const ftk::Primary all{p.cam, c->d_pixels.as<uint32_t>(), c->d_jitter.as<double>(), 0u, (uint32_t)p.n_pix_total, p.spp, (uint32_t)q.res_h,
+                           (unsigned long long)q.seed, 1.0 / (double)p.n_pix_total, 1.0 / (double)q.res_h, nullptr, nullptr};
+    const ftk::ClassifyOut cls{F.d_block_pos.as<int32_t>(), F.d_pos_block.as<uint32_t>(), c->d_wave_counts.as<uint32_t>()};
+    auto* fc = F.d_fc.as<ftk::FrameCounters>();
+    const uint32_t epoch = ++c->classify_epoch;
+    // A queued frame's classification reads nothing the frames before it write (its slot's buffers were free once the slot's previous
+    // frame was retired): it goes to the side stream and the main stream waits for its event, so it runs beside the previous
+    // frame's k_primary tail and k_resolve instead of behind them.  A blocking frame, or one whose inputs are still being uploaded on
+    // the main stream, classifies in line.  (Started as soon as it is queued, it takes the first workgroup slots of the previous frame's
+    // k_primary: 226 -> 242 us, but holding it back for that frame's tracing only moved those 24 us.)
+    const hipStream_t cs = ahead ? c->side : F.ev.ms;
+    const ftk::Launch Lg{cs, c->n_cu * 8, 0, 0};
+    if (!c->classified) FT_HIP(c, hipEventCreateWithFlags(&c->classified, hipEventDisableTiming));
+    else FT_HIP(c, hipStreamWaitEvent(cs, c->classified, 0));  // one classification at a time, whichever streams they are on
+    if (ahead) {
+        ftk::launch_classify(Lg, c->dev_scene, all, cls, p.jitter_extent, epoch, fc);
+        FT_HIP(c, hipEventRecord(c->classified, c->side));
+        FT_HIP(c, hipStreamWaitEvent(F.ev.ms, c->classified, 0));
+    } else {
+        F.ev.timed(kStageOther, [&] { ftk::launch_classify(Lg, c->dev_scene, all, cls, p.jitter_extent, epoch, fc); });
+        FT_HIP(c, hipEventRecord(c->classified, F.ev.ms));
+    }
+    F.ev.fresh = false;
+    return FT_OK;
+}
+
+// The frame's chunks on its main stream: k_primary, the k_bounce levels and k_resolve of every window of the pixel list (or corner grid).
+static int32_t queue_chunks(ft_context* c, const RenderRequest& q, const FramePlan& p, ft_context::FrameSlot& F, int main_ix, int32_t& n_launches) {
+    Brackets& E = F.ev;
+    const hipStream_t ms = E.ms;
+    auto* fc = F.d_fc.as<ftk::FrameCounters>();
+    const size_t lds = lds_bytes_for(c->flat);
+    const ftk::Launch Lp{ms, c->n_cu * c->blocks_primary, lds, c->variant_primary};
+    const ftk::Launch Lb{ms, c->n_cu * c->blocks_bounce, lds, c->variant};
+    const ftk::Launch Lg{ms, c->n_cu * 8, 0, 0};
+    const ftk::Launch Lr{ms, c->n_cu * c->blocks_resolve, 0, 0};
+    const ftk::RayBuf rb[2] = {ray_view(c->d_rays[2 * main_ix], c->ray_capacity), ray_view(c->d_rays[2 * main_ix + 1], c->ray_capacity)};
+    const bool zeros_in_place = p.classify && c->opt.zero_fill_skip && c->zero_signature[q.format] == p.zsig;
+    c->zero_signature[q.format] = p.classify ? p.zsig : 0;
+    double* const out_rgb = q.format == 1 ? nullptr : c->d_out.as<double>();
+    uint8_t* const out_rgba = q.format == 1 ? c->d_out8.as<uint8_t>() : nullptr;
+    const uint32_t stride = (uint32_t)(p.corner ? q.res_h + 1 : q.res_h);
+    // Bounces >= 1: one k_bounce per level of the reflection tree, as many as the previous frame of this signature had (+ 1).
+    // With "timing" = 1 the whole region is one bracket (kind shade): a bracket per launch costs more than a small level does.
+    const bool hinted = c->opt.level_hint && c->staged_hint >= 0 && c->staged_signature == p.signature;
+    const int n_levels = hinted ? std::min(p.last_bounce, c->staged_hint + 1) : p.last_bounce;
+    for (const FramePlan::Job& job : p.jobs) {
+        const bool first = &job == &p.jobs.front(), last = &job == &p.jobs.back();   // the frame's last kernel hands the counters over (FrameReport)
+        const uint32_t n_pix = job.n_ids, n_samples = n_pix * (uint32_t)p.spp;
+        if (!first) E.timed(kStageOther, [&] { (void)hipMemsetAsync(&fc->cc, 0, sizeof(ftk::ChunkCounters), ms); });
+        ftk::Primary gen{p.cam, c->d_pixels.as<uint32_t>(), c->d_jitter.as<double>(), job.id_base, n_pix, p.spp, stride, (unsigned long long)q.seed,
+                         1.0 / (double)n_pix, 1.0 / (double)stride, nullptr, nullptr};
+        if (p.classify) { gen.counts = &fc->counts; gen.block_map = F.d_pos_block.as<uint32_t>(); }   // pix_base = job.id_base: the window's start in the active list
+        gen.group_log2 = (n_pix % 64u == 0u) ? p.group_log2 : 0;
+        const int at = c->acc_turn;
+        double* const acc = c->d_acc[at].as<double>();
+        if (c->acc_busy[at]) { FT_HIP(c, hipStreamWaitEvent(ms, c->acc_free[at], 0)); c->acc_busy[at] = false; E.fresh = false; }   // a k_resolve on `tail` may still be reading this copy
+        E.timed(kStagePrimary, [&] { ftk::launch_primary(Lp, c->dev_scene, gen, rb[1], acc, n_samples, q.max_depth, fc); });
+        auto bounce = [&](int b) { ftk::launch_bounce(Lb, c->dev_scene, gen, rb[b & 1], rb[(b + 1) & 1], acc, n_samples, b, q.max_depth, b == n_levels && n_levels < p.last_bounce, fc); };
+        if (E.timing >= 2) for (int b = 1; b <= n_levels; ++b) E.timed(kStageShade, [&] { bounce(b); });
+        else if (n_levels >= 1) E.timed(kStageShade, [&] { for (int b = 1; b <= n_levels; ++b) bounce(b); });
+        n_launches += 2 + n_levels;                                 // k_primary, the levels, k_resolve
+        if (!p.simple) for (int k = 0; k < ft_context::kAcc; ++k) if (c->acc_busy[k]) {   // a queued frame's k_resolve may still be writing the frame on `tail`: frames reach d_out in order
+            FT_HIP(c, hipStreamWaitEvent(ms, c->acc_free[k], 0)); c->acc_busy[k] = false; E.fresh = false;
+        }
+        if (p.corner) { E.timed(kStageResolve, [&] { ftk::launch_resolve_corner(Lg, acc, n_samples, job.w, job.h, c->d_out_index.as<uint32_t>() + job.out_base, out_rgb, out_rgba); }); continue; }
+        const ftk::ResolveArgs ra{acc, n_samples, p.classify ? &fc->counts : nullptr, job.id_base, n_pix, p.spp,
+                                  p.classify ? F.d_pos_block.as<uint32_t>() : nullptr, (p.classify && first && !zeros_in_place) ? F.d_block_pos.as<int32_t>() : nullptr,
+                                  (uint32_t)(p.n_pix_total / 64), c->d_pixels.as<uint32_t>(), out_rgb, out_rgba, (uint32_t)gen.group_log2, fc, last ? F.d_report : nullptr};
+        if (p.simple) {
+            // behind the frame's tracing kernels, on its own stream: the main stream goes straight on with the next frame.  Where the
+            // tracing ends: the event that closed its last bracket, if that is still the stream's last entry.
+            hipEvent_t traced = E.fresh ? E.boundary : nullptr;
+            if (!traced) { if (!(traced = E.next())) { c->err = "hipEventCreate failed"; return FT_ERR_HIP; } FT_HIP(c, hipEventRecord(traced, ms)); }
+            FT_HIP(c, hipStreamWaitEvent(c->tail, traced, 0));
+            ftk::Launch La = Lr; La.stream = c->tail;
+            ftk::launch_resolve(La, ra);
+            if (!c->acc_free[at]) FT_HIP(c, hipEventCreateWithFlags(&c->acc_free[at], hipEventDisableTiming));
+            FT_HIP(c, hipEventRecord(c->acc_free[at], c->tail));
+            c->acc_busy[at] = true;
+            c->acc_turn = (c->acc_turn + 1) % ft_context::kAcc;
+            E.fresh = false;
+        } else E.timed(kStageResolve, [&] { ftk::launch_resolve(Lr, ra); });
+        if (last) F.fc_clean = true;
+    }
+    if (!F.fc_clean) { ftk::launch_report(Lg, fc, F.d_report); F.fc_clean = true; }   // corner frames end in k_resolve_corner: the hand-over is a launch of its own
+    return FT_OK;
+}
+
+// Queue a planned frame: its inputs, its slot and main stream, the classification and the chunks.  A blocking frame is then retired
+// (and fetched into `out`); a queued one is retired by a later call.
+static int32_t queue_frame(ft_context* c, const RenderRequest& q, const FramePlan& p, void* out, ft_stats* stats, bool defer,
+                           std::chrono::steady_clock::time_point wall0) {
+    int32_t rc;
+    bool uploads_queued = false;
+    if ((rc = upload_frame_inputs(c, q, p, uploads_queued)) != FT_OK) return rc;
     // A blocking call retires whatever is in flight first; a deferred one only the frame whose slot (host state, counters, classification
     // buffers) it is about to reuse.
-    if (!defer) { int32_t prc = retire_pending(c, nullptr); if (prc != FT_OK) return prc; for (int k = 0; k < kStages; ++k) { c->k_ms[k] = 0; c->k_launches[k] = 0; } c->accum_open = false; }
+    if (!defer && (rc = retire_pending(c, nullptr)) != FT_OK) return rc;
     const int turn = c->slot_turn;
     ft_context::FrameSlot& F = c->slots[turn];
-    if (F.pending) { int32_t prc = retire_frame(c, F, nullptr); if (prc != FT_OK) return prc; }
-    if (defer && !c->accum_open) { for (int k = 0; k < kStages; ++k) { c->k_ms[k] = 0; c->k_launches[k] = 0; } c->accum_open = true; }
-    bool uploads_queued = !same_list || corner || jitter_uploaded; // something this frame's k_classify reads is still on its way on the main stream
-    ftk::ClassifyOut cls{};
-    if (classify) {
-        const size_t n_blocks = (size_t)n_pix_total / 64, n_waves = (n_blocks + 255) / 256;   // one word per k_classify workgroup
-        if ((rc = ensure(c, c->d_block_pos[turn], n_blocks * 4)) != FT_OK) return rc;
-        if ((rc = ensure(c, c->d_pos_block[turn], n_blocks * 4)) != FT_OK) return rc;
+    if (F.pending && (rc = retire_frame(c, F, nullptr)) != FT_OK) return rc;
+    if (!defer || !c->accum_open) { for (int k = 0; k < kStages; ++k) { c->k_ms[k] = 0; c->k_launches[k] = 0; } c->accum_open = defer; }   // queued frames sum their kernel times until a wait
+    if (p.classify) {
+        const size_t n_blocks = (size_t)p.n_pix_total / 64, n_waves = (n_blocks + 255) / 256;   // one word per k_classify workgroup
+        if ((rc = ensure(c, F.d_block_pos, n_blocks * 4)) != FT_OK) return rc;
+        if ((rc = ensure(c, F.d_pos_block, n_blocks * 4)) != FT_OK) return rc;
         if (c->d_wave_counts.bytes < n_waves * 4 || c->classify_epoch >= 0x3FFFFEu) {   // entries are tagged with the frame's epoch and never cleared in between
             if ((rc = ensure(c, c->d_wave_counts, std::max<size_t>(n_waves * 4, 4096) + 4096 * 4 + 2048 * 64)) != FT_OK) return rc;   // (+ room for the diagnostic build's stamps)
             FT_HIP(c, hipStreamSynchronize(c->side));              // (a classification of the other slot may still be publishing into the old words)
@@ -1003,235 +1148,79 @@ static int32_t render_single(ft_context* c, const RenderRequest& q, void* out, f
             c->classify_epoch = 0;
             uploads_queued = true;
         }
-        cls = ftk::ClassifyOut{c->d_block_pos[turn].as<int32_t>(), c->d_pos_block[turn].as<uint32_t>(), c->d_wave_counts.as<uint32_t>()};
     }
-    auto* fc = c->d_fc[turn].as<ftk::FrameCounters>();
     // Which main stream.  Two consecutive k_primary launches on ONE stream are an in-order pair: the second is dispatched when the first has
     // drained, and a persistent grid drains slowly (its last batches run on a machine that is mostly idle).  A simple frame - one chunk,
     // k_resolve aside - shares nothing with its predecessor that events do not already order (sample colours: acc_free; counters and
     // classification: per slot; the frame buffer: the tail stream; ray buffers: a pair per main stream), so every other one goes to the second main stream and its
     // workgroups take the CUs as the predecessor's leave them.
-    const ft_context::FrameSlot& prevF = c->slots[(turn + ft_context::kSlots - 1) % ft_context::kSlots];
-    const bool simple = defer && c->resolve_aside && !corner && c->timing < 2 && jobs.size() == 1;
-    if (!simple && any_pending(c, true)) { int32_t prc = retire_pending(c, nullptr); if (prc != FT_OK) return prc; }   // anything else keeps the one-stream order
-    const int main_ix = (simple && c->mains > 1 && !uploads_queued && prevF.pending && prevF.simple) ? (prevF.main_ix + 1) % c->mains : 0;   // the next stream after its predecessor's
-    const bool alt = main_ix != 0;
-    const hipStream_t ms = alt ? c->more_mains[main_ix - 1] : c->stream;
+    const ft_context::FrameSlot& prev = c->slots[(turn + ft_context::kSlots - 1) % ft_context::kSlots];
+    if (!p.simple && any_pending(c, true) && (rc = retire_pending(c, nullptr)) != FT_OK) return rc;   // anything else keeps the one-stream order
+    const int main_ix = (p.simple && c->opt.mains > 1 && !uploads_queued && prev.pending && prev.simple) ? (prev.main_ix + 1) % (int)c->opt.mains : 0;   // the next stream after its predecessor's
+    const hipStream_t ms = main_ix ? c->more_mains[main_ix - 1] : c->stream;
     // chunk counters, statistic stripes, list length, tickets: cleared by the slot's previous frame's last kernel, or by a fill when there was none
-    if (!c->fc_clean[turn]) { FT_HIP(c, hipMemsetAsync(fc, 0, sizeof(ftk::FrameCounters), ms)); uploads_queued = true; }
-    c->fc_clean[turn] = false;                                     // until this frame's own hand-over is queued
-
-    const ftk::Camera dcam = make_camera(*cam, res_h, res_v);
-    const size_t lds = lds_bytes_for(c->flat);
-    const int variant = c->variant;
-    // Samples per bounce-0 wavefront (slot_at, ft_kernels.hip): 2^group_log2 samples of 64 / 2^group_log2 pixels when the sample count
-    // has that power of two in it and the list is made of whole 8x8 blocks.  Narrow bundles pay most where a wave walks a BVH
-    // (measured at 1080p x 16, 1 -> 16 samples per wave: bunny through BSP leaves 1.46 -> 1.29 ms, night-house 4.63 -> 4.45).
-    int group_log2 = 0;
-    {
-        const int cap = c->wave_samples_log2 >= 0 ? c->wave_samples_log2 : 4;
-        while (group_log2 < cap && !((spp >> group_log2) & 1)) ++group_log2;
-        if (corner || !c->pixels_tiled) group_log2 = 0;
-    }
-    // Option "primary_reserve": workgroup slots a simple frame's k_primary leaves free for the k_resolve of the frame before and the k_classify
-    // of the frame after, which otherwise get their slots from its tail.  Measured (tools/reserve_sweep.py): the headline is best at 0
-    // (0.2505 ms; 64 free: 0.2545, 256: 0.2715), bunny-bsp12 too; moon x16 gains 3 % at 64.  Default 0.
-    const int reserve = simple && c->primary_reserve > 0 ? (int)c->primary_reserve : 0;
-    ftk::Launch Lp{ms, std::max(c->n_cu, c->n_cu * c->blocks_primary - reserve), lds, c->variant_primary};
-    ftk::Launch Lb{ms, c->n_cu * c->blocks_bounce, lds, variant};
-    ftk::Launch Lg{ms, c->n_cu * 8, 0, 0};
-    const int resolve_per_cu = c->resolve_blocks_cap > 0 ? std::min(c->resolve_blocks_cap, c->blocks_resolve) : c->blocks_resolve;
-    ftk::Launch Lr{ms, c->n_cu * resolve_per_cu, 0, 0};
-    ftk::RayBuf rb[2] = {ray_view(c->d_rays[2 * main_ix], c->ray_capacity), ray_view(c->d_rays[2 * main_ix + 1], c->ray_capacity)};
-
-    F.events_used = 0; F.spans.clear();
-    auto& spans = F.spans;
-    using Span = ft_context::FrameSlot::Span;
-    // HIP events between stages.  An event between two dependent kernels costs about 6 us of stream time, so by default ("timing"
-    // = 1) only the kernels that trace rays (k_primary, the k_bounce levels) are bracketed; 2 brackets every stage, 0 only the frame.
-    // The frame's first event is recorded in front of its first launch on the main stream, behind the waits for other streams' events: on a
-    // queued frame it doubles as the start of k_primary's bracket (an event record costs ~5 us of stream time; a frame of 0.27 ms had four
-    // between two k_primary launches, now two).
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    hipEvent_t boundary = nullptr;
-    bool boundary_fresh = false;                                   // `boundary` was recorded right before the next launch
-    auto open_frame = [&]() {
-        if (ev0) return;
-        ev0 = next_event(F);
-        if (ev0) (void)hipEventRecord(ev0, ms);
-        boundary = ev0; boundary_fresh = true;
-    };
-    const int timing = c->timing;
-    auto timed = [&](int kind, auto&& fn) {
-        const bool bracket = timing >= 2 || (timing == 1 && (kind == kStageClosest || kind == kStageShade || kind == kStagePrimary));
-        open_frame();
-        if (bracket && !boundary_fresh) { boundary = next_event(F); if (boundary) (void)hipEventRecord(boundary, ms); }
-        fn();
-        if (!bracket) { boundary_fresh = false; return; }
-        hipEvent_t b = next_event(F);
-        if (b) (void)hipEventRecord(b, ms);
-        if (boundary && b) spans.push_back(Span{boundary, b, kind});
-        boundary = b; boundary_fresh = true;
-    };
-    // What decides which blocks k_classify finishes: the scene, the camera, the frame's size and pixel list, the jitter pattern's extent.
-    uint64_t zsig = signature;
-    {
-        auto mix = [&](const void* p, size_t n) { const unsigned char* b = static_cast<const unsigned char*>(p); for (size_t k = 0; k < n; ++k) zsig = (zsig ^ b[k]) * 0x100000001B3ull; };
-        mix(&dcam, sizeof dcam); mix(&jitter_extent, sizeof jitter_extent);
-        if (!rects.empty()) mix(rects.data(), rects.size() * sizeof(ft_rect));
-        zsig |= 1ull;                                              // never 0: 0 means "nothing known about the buffer"
-    }
-    const bool zeros_in_place = classify && c->zero_fill_skip && c->zero_signature[q.format] == zsig;
-    c->zero_signature[q.format] = classify ? zsig : 0;
-    int n_chunks = 0, n_launches = 0, levels_launched = 0;
-    // The whole frame is classified once; the chunks then take consecutive windows of the frame's ACTIVE pixel list, so a sparse
-    // frame is one chunk of real work and launches that find their window empty return at once.
-    if (classify) {
-        const ftk::Primary all{dcam, c->d_pixels.as<uint32_t>(), c->d_jitter.as<double>(), 0u, (uint32_t)n_pix_total, spp, (uint32_t)res_h,
-                               (unsigned long long)seed, 1.0 / (double)n_pix_total, 1.0 / (double)res_h, nullptr, nullptr};
-        const uint32_t epoch = ++c->classify_epoch;
-        // A queued frame's classification reads nothing the frames before it write (its slot's buffers were free once the slot's previous
-        // frame was retired above): it goes to the side stream and the main stream waits for its event, so it runs beside the previous
-        // frame's k_primary tail and k_resolve instead of behind them.  A blocking frame, or one whose inputs are still being uploaded on
-        // the main stream, classifies in line.
-        const bool ahead = defer && c->classify_ahead && !uploads_queued;
-        hipStream_t cs = ahead ? c->side : ms;
-        if (!c->classified) FT_HIP(c, hipEventCreateWithFlags(&c->classified, hipEventDisableTiming));
-        else FT_HIP(c, hipStreamWaitEvent(cs, c->classified, 0));  // one classification at a time, whichever streams they are on
-        if (ahead) {
-            // beside the previous frame's k_resolve (a bandwidth-bound kernel that leaves registers free), not beside the head of its
-            // k_primary: started as soon as it was queued, the classification took the first workgroup slots of a grid that fills the chip
-            // (measured: k_primary 226 -> 242 us, the 24 us merely moved)
-            const ft_context::FrameSlot& prev = c->slots[(turn + ft_context::kSlots - 1) % ft_context::kSlots];
-            if (c->classify_after_trace && prev.pending && prev.traced) FT_HIP(c, hipStreamWaitEvent(c->side, prev.traced, 0));
-            const ftk::Launch Ls{c->side, Lg.grid, 0, 0};
-            ftk::launch_classify(Ls, c->dev_scene, all, cls, jitter_extent, epoch, fc);
-            FT_HIP(c, hipEventRecord(c->classified, c->side));
-            FT_HIP(c, hipStreamWaitEvent(ms, c->classified, 0));
-            boundary_fresh = false;
-        } else {
-            timed(kStageOther, [&] { ftk::launch_classify(Lg, c->dev_scene, all, cls, jitter_extent, epoch, fc); });
-            FT_HIP(c, hipEventRecord(c->classified, ms));
-            boundary_fresh = false;
-        }
-        ++n_launches;
-    }
+    if (!F.fc_clean) { FT_HIP(c, hipMemsetAsync(F.d_fc.p, 0, sizeof(ftk::FrameCounters), ms)); uploads_queued = true; }
+    F.fc_clean = false;                                            // until this frame's own hand-over is queued
+    F.ev.begin(ms, (int)c->opt.timing);
+    if (p.classify && (rc = queue_classify(c, q, p, F, defer && c->opt.classify_ahead && !uploads_queued)) != FT_OK) return rc;
     if (!F.h_report) {
         FT_HIP(c, hipHostMalloc(reinterpret_cast<void**>(&F.h_report), sizeof(ftk::FrameReport), hipHostMallocDefault));
         FT_HIP(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&F.d_report), F.h_report, 0));
     }
-    double* const out_rgb = q.format == 1 ? nullptr : c->d_out.as<double>();
-    uint8_t* const out_rgba = q.format == 1 ? c->d_out8.as<uint8_t>() : nullptr;
-    // queued frames: k_resolve on its own stream (blocking frames have nothing to hide it in).  Frames of one chunk only: a frame cut into many
-    // windows (3840x2160x64: 16, most of them empty behind the classification) pays an event pair per window and gains nothing - the windows'
-    // small launches already overlap on one stream (measured: 3.46 -> 3.63 ms with it, profiles/r03_z_overlap_by_scene.json)
-    const bool aside = defer && c->resolve_aside && !corner && timing < 2 && jobs.size() == 1;
-    for (const Job& job : jobs) {
-        const uint32_t n_pix = job.n_ids;
-        const uint32_t n_samples = n_pix * (uint32_t)spp;
-        if (n_chunks > 0) timed(kStageOther, [&] { (void)hipMemsetAsync(&fc->cc, 0, sizeof(ftk::ChunkCounters), ms); });
-        ++n_chunks;
-        ftk::Primary gen{dcam, c->d_pixels.as<uint32_t>(), c->d_jitter.as<double>(), job.id_base, n_pix, spp,
-                         (uint32_t)(corner ? res_h + 1 : res_h), (unsigned long long)seed,
-                         1.0 / (double)n_pix, 1.0 / (double)(corner ? res_h + 1 : res_h), nullptr, nullptr};
-        if (classify) { gen.counts = &fc->counts; gen.block_map = c->d_pos_block[turn].as<uint32_t>(); }   // pix_base = job.id_base: the window's start in the active list
-        gen.group_log2 = (n_pix % 64u == 0u) ? group_log2 : 0;
-        const int at = c->acc_turn;
-        double* const acc = c->d_acc[at].as<double>();
-        if (c->acc_busy[at]) { FT_HIP(c, hipStreamWaitEvent(ms, c->acc_free[at], 0)); c->acc_busy[at] = false; boundary_fresh = false; }   // a k_resolve on `tail` may still be reading this copy
-        timed(kStagePrimary, [&] { ftk::launch_primary(Lp, c->dev_scene, gen, rb[1], acc, n_samples, max_depth, fc); });
-        ++n_launches;
-        // Bounces >= 1: one k_bounce per level of the reflection tree, as many as the previous frame of this signature had (+ 1).
-        // With "timing" = 1 the whole region is one bracket (kind shade): a bracket per launch costs more than a small level does.
-        const bool hinted = c->level_hint && c->staged_hint >= 0 && c->staged_signature == signature;
-        const int n_levels = hinted ? std::min(last_bounce, c->staged_hint + 1) : last_bounce;
-        levels_launched = n_levels;
-        auto bounces = [&](auto&& stage) {
-            for (int b = 1; b <= n_levels; ++b) {
-                stage(kStageShade, [&] { ftk::launch_bounce(Lb, c->dev_scene, gen, rb[b & 1], rb[(b + 1) & 1], acc, n_samples, b, max_depth, b == n_levels && n_levels < last_bounce, fc); });
-                ++n_launches;
-            }
-        };
-        if (timing >= 2) bounces(timed);
-        else if (n_levels >= 1) timed(kStageShade, [&] { bounces([](int, auto&& fn) { fn(); }); });
-        if (&job == &jobs.back()) {                                // where the frame's tracing ends: the event that closed its last bracket, if that is still the stream's last entry
-            if (boundary_fresh && boundary) F.traced = boundary;
-            else { F.traced = next_event(F); if (!F.traced) { c->err = "hipEventCreate failed"; return FT_ERR_HIP; } FT_HIP(c, hipEventRecord(F.traced, ms)); }
-        }
-        if (!aside) for (int k = 0; k < ft_context::kAcc; ++k) if (c->acc_busy[k]) {   // a queued frame's k_resolve may still be writing the frame on `tail`: frames reach d_out in order
-            FT_HIP(c, hipStreamWaitEvent(ms, c->acc_free[k], 0)); c->acc_busy[k] = false; boundary_fresh = false;
-        }
-        if (corner) timed(kStageResolve, [&] { ftk::launch_resolve_corner(Lg, acc, n_samples, job.w, job.h, c->d_out_index.as<uint32_t>() + job.out_base, out_rgb, out_rgba); });
-        else {
-            const bool last_job = &job == &jobs.back();            // the frame's last kernel hands the counters over (FrameReport)
-            ftk::ResolveArgs ra{acc, n_samples, classify ? &fc->counts : nullptr, job.id_base, n_pix, spp,
-                                classify ? c->d_pos_block[turn].as<uint32_t>() : nullptr, (classify && n_chunks == 1 && !zeros_in_place) ? c->d_block_pos[turn].as<int32_t>() : nullptr,
-                                (uint32_t)(n_pix_total / 64), c->d_pixels.as<uint32_t>(), out_rgb, out_rgba, (uint32_t)gen.group_log2, fc, last_job ? F.d_report : nullptr};
-            if (aside) {
-                // behind the chunk's tracing kernels, on its own stream: the main stream goes straight on with the next chunk or frame
-                hipEvent_t et = last_job ? F.traced : next_event(F);
-                if (!et) { c->err = "hipEventCreate failed"; return FT_ERR_HIP; }
-                if (!last_job) FT_HIP(c, hipEventRecord(et, ms));
-                FT_HIP(c, hipStreamWaitEvent(c->tail, et, 0));
-                ftk::Launch La = Lr; La.stream = c->tail;
-                ftk::launch_resolve(La, ra);
-                if (!c->acc_free[at]) FT_HIP(c, hipEventCreateWithFlags(&c->acc_free[at], hipEventDisableTiming));
-                FT_HIP(c, hipEventRecord(c->acc_free[at], c->tail));
-                c->acc_busy[at] = true;
-                c->acc_turn = (c->acc_turn + 1) % ft_context::kAcc;
-                boundary_fresh = false;
-            } else timed(kStageResolve, [&] { ftk::launch_resolve(Lr, ra); });
-            if (last_job) c->fc_clean[turn] = true;
-        }
-        ++n_launches;
-    }
-    if (!c->fc_clean[turn]) { ftk::launch_report(Lg, fc, F.d_report); c->fc_clean[turn] = true; }   // corner frames end in k_resolve_corner: the hand-over is a launch of its own
-    c->last_n_pix = n_pix_total; c->last_res_h = res_h; c->last_res_v = res_v; c->last_format = q.format;
+    int32_t n_launches = p.classify ? 1 : 0;
+    if ((rc = queue_chunks(c, q, p, F, main_ix, n_launches)) != FT_OK) return rc;
+    c->last_n_pix = p.n_pix_total; c->last_res_h = q.res_h; c->last_res_v = q.res_v; c->last_format = q.format;
     if (defer && out) {                                            // ft_render_enqueue_into: the frame's way out is queued behind its last kernel
-        const hipStream_t cs = aside ? c->tail : ms;
-        int32_t crc = copy_frame_out(c, out, q.format, cs);
-        if (crc != FT_OK) return crc;
-        boundary_fresh = false;
+        if ((rc = copy_frame_out(c, out, q.format, p.simple ? c->tail : ms)) != FT_OK) return rc;
+        F.ev.fresh = false;
     }
-    open_frame();
-    if (aside) { ev1 = next_event(F); if (ev1) (void)hipEventRecord(ev1, c->tail); }                  // the frame ends where its last k_resolve (and copy) does
-    else if (boundary_fresh) ev1 = boundary;
-    else { ev1 = next_event(F); if (ev1) (void)hipEventRecord(ev1, ms); }
+    F.ev.open();
+    if (p.simple) F.ev.ev1 = F.ev.record(c->tail);                // the frame ends where its last k_resolve (and copy) does
+    else F.ev.ev1 = F.ev.fresh ? F.ev.boundary : F.ev.record(ms);
     FT_HIP(c, hipGetLastError());
-    F.signature = signature; F.levels_launched = levels_launched; F.last_bounce = last_bounce;
-    F.simple = simple; F.alt = alt; F.main_ix = main_ix;
-    F.done = ev1;                                                  // nothing follows the last kernel: its end is the frame's
-    F.ev0 = ev0; F.ev1 = ev1; F.pending = true; F.wall0 = wall0; F.timing = timing;
-    F.rays_primary = 0; for (auto& j : jobs) F.rays_primary += (uint64_t)j.n_ids * (uint64_t)spp;
-    F.n_pix_total = n_pix_total; F.spp = spp; F.n_launches = n_launches; F.n_chunks = n_chunks; F.classify = classify; F.format = q.format;
-    c->last_n_pix = n_pix_total; c->last_res_h = res_h; c->last_res_v = res_v; c->last_format = q.format;
+    F.signature = p.signature; F.simple = p.simple; F.main_ix = main_ix;
+    F.pending = true; F.wall0 = wall0;
+    F.rays_primary = 0; for (auto& j : p.jobs) F.rays_primary += (uint64_t)j.n_ids * (uint64_t)p.spp;
+    F.n_pix_total = p.n_pix_total; F.spp = p.spp; F.n_launches = n_launches; F.n_chunks = (int32_t)p.jobs.size(); F.classify = p.classify; F.format = q.format;
     c->slot_turn = (c->slot_turn + 1) % ft_context::kSlots;
     if (defer) return FT_OK;                                       // ft_render_enqueue: the frame is retired by a later call
-    int32_t rrc = retire_frame(c, F, stats);
-    if (rrc != FT_OK) return rrc;
-    if (out) { int32_t frc = fetch_single(c, out, q.format); if (frc != FT_OK) return frc; }   // out == NULL: the frame stays in HBM
+    if ((rc = retire_frame(c, F, stats)) != FT_OK) return rc;
+    if (out && (rc = fetch_single(c, out, q.format)) != FT_OK) return rc;   // out == NULL: the frame stays in HBM
     if (stats) stats->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
     return FT_OK;
+}
+
+static int32_t render_single(ft_context* c, const RenderRequest& q, void* out, ft_stats* stats, bool defer) {
+    if (!need_device(c)) return FT_ERR_NO_DEVICE;
+    if (!c->committed) { c->err = "scene not committed (ft_scene_commit)"; return FT_ERR_STATE; }
+    const auto wall0 = std::chrono::steady_clock::now();
+    FT_HIP(c, hipSetDevice(c->device));
+    FramePlan p;
+    plan_pixels(c, q, p);
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    if (p.n_pix_total == 0) return FT_OK;
+    plan_chunks(c, q, defer, p);
+    if (p.cap > 0x7FFFFFFFll) { c->err = "chunk too large"; return FT_ERR_INVALID; }
+    return queue_frame(c, q, p, out, stats, defer, wall0);
 }
 
 // Wait for a queued frame, add its stage times to the context's sums and fill its statistics.
 static int32_t retire_frame(ft_context* c, ft_context::FrameSlot& F, ft_stats* stats) {
     if (!F.pending) return FT_OK;
     F.pending = false;
-    if (F.done) FT_HIP(c, hipEventSynchronize(F.done)); else FT_HIP(c, hipStreamSynchronize(c->stream));
+    if (F.ev.ev1) FT_HIP(c, hipEventSynchronize(F.ev.ev1)); else FT_HIP(c, hipStreamSynchronize(c->stream));
     const ftk::RenderCounters hrc = F.h_report->total;              // the stripes, summed by the frame's last kernel
     const bool classify_failed = F.h_report->classify_error != 0;
     // How deep this frame's rays went in numbers worth a launch (more than "follow_below" rays; levels followed in registers count
     // theirs too): the next frame of the same signature launches that many levels + 1, and that last one follows what is left.
     int deepest = 0;
-    const int64_t few = c->follow_below >= 0 ? c->follow_below : 8ll * c->n_cu;   // -1: two rays per SIMD
+    const int64_t few = c->opt.follow_below >= 0 ? c->opt.follow_below : 8ll * c->n_cu;   // -1: two rays per SIMD
     while (deepest + 1 <= ftk::kMaxBounce && (int64_t)F.h_report->n_rays[deepest + 1] > few) ++deepest;
     c->staged_hint = deepest; c->staged_signature = F.signature;
-    if (F.classify && !classify_failed) { c->active_hint = (int64_t)F.h_report->n_pix_active; c->active_signature = F.signature; }
-    const int timing = F.timing; const int32_t spp = F.spp; const int64_t n_pix_total = F.n_pix_total; const bool classify = F.classify;
-    hipEvent_t ev0 = F.ev0, ev1 = F.ev1;
+    const int timing = F.ev.timing; const int32_t spp = F.spp; const int64_t n_pix_total = F.n_pix_total; const bool classify = F.classify;
+    hipEvent_t ev0 = F.ev.ev0, ev1 = F.ev.ev1;
     double bracketed = 0.0, traced = 0.0;
-    for (auto& s : F.spans) {
+    for (auto& s : F.ev.spans) {
         float ms = 0;
         if (hipEventElapsedTime(&ms, s.a, s.b) != hipSuccess) continue;
         c->k_ms[s.kind] += ms; c->k_launches[s.kind]++; bracketed += ms;
@@ -1317,10 +1306,8 @@ int32_t ft_render_wait(ft_context* c, ft_stats* stats) {
     if (!c) return FT_ERR_INVALID;
     if (c->host_only) return FT_ERR_NO_DEVICE;
     if (stats) std::memset(stats, 0, sizeof *stats);
-    std::vector<ft_context*> devs{c};
-    devs.insert(devs.end(), c->peers.begin(), c->peers.end());
     int32_t rc = FT_OK;
-    for (ft_context* d : devs) {
+    for (ft_context* d : devices(c)) {
         FT_HIP(c, hipSetDevice(d->device));
         ft_stats sd;
         std::memset(&sd, 0, sizeof sd);
@@ -1340,6 +1327,34 @@ int32_t ft_get_kernel_times(ft_context* c, double ms[5], int32_t launches[5]) {
 }
 
 // ------------------------------------------------------------------------------------------ debug / tests
+// The start of a ray query (ft_debug_closest / ft_debug_blocked): the checks, the device, the rays into d_dbg_in (origins, directions and,
+// when `max_dist` is given, the lengths), room for `out_bytes` per ray in d_dbg_out, and the overflow count cleared (in slot 0's counters).
+static int32_t debug_rays_in(ft_context* c, const double* origins, const double* dirs, const double* max_dist, int64_t n, size_t out_bytes) {
+    if (!need_device(c)) return FT_ERR_NO_DEVICE;
+    if (!c->committed) { c->err = "scene not committed"; return FT_ERR_STATE; }
+    if (n == 0) return FT_OK;
+    FT_HIP(c, hipSetDevice(c->device));
+    int32_t rc;
+    const size_t N = (size_t)n;
+    if ((rc = ensure(c, c->d_dbg_in, N * (max_dist ? 56 : 48))) != FT_OK) return rc;
+    if ((rc = ensure(c, c->d_dbg_out, N * out_bytes)) != FT_OK) return rc;
+    double* din = c->d_dbg_in.as<double>();
+    FT_HIP(c, hipMemcpyAsync(din, origins, N * 24, hipMemcpyHostToDevice, c->stream));
+    FT_HIP(c, hipMemcpyAsync(din + 3 * N, dirs, N * 24, hipMemcpyHostToDevice, c->stream));
+    if (max_dist) FT_HIP(c, hipMemcpyAsync(din + 6 * N, max_dist, N * 8, hipMemcpyHostToDevice, c->stream));
+    c->slots[0].fc_clean = false;
+    FT_HIP(c, hipMemsetAsync(c->slots[0].d_fc.p, 0, sizeof(unsigned long long), c->stream));   // the overflow count of this query
+    return FT_OK;
+}
+// ... and its end, behind the copies of the results: the overflow count read back, the stream synchronised.
+static int32_t debug_rays_done(ft_context* c) {
+    unsigned long long n_overflow = 0;
+    FT_HIP(c, hipMemcpyAsync(&n_overflow, c->slots[0].d_fc.p, sizeof n_overflow, hipMemcpyDeviceToHost, c->stream));
+    FT_HIP(c, hipStreamSynchronize(c->stream));
+    if (n_overflow) { c->err = "CSG hit list overflow"; return FT_ERR_OVERFLOW; }
+    return FT_OK;
+}
+
 static int32_t debug_closest(ft_context* c, const double* origins, const double* dirs, int64_t n, int32_t* hit, double* t, double* p, double* nrm, double* colour);
 int32_t ft_debug_closest(ft_context* c, const double* origins, const double* dirs, int64_t n, int32_t* hit, double* t, double* p, double* nrm, double* colour) {
     if (!c) return FT_ERR_INVALID;
@@ -1347,36 +1362,22 @@ int32_t ft_debug_closest(ft_context* c, const double* origins, const double* dir
 }
 static int32_t debug_closest(ft_context* c, const double* origins, const double* dirs, int64_t n, int32_t* hit, double* t, double* p, double* nrm, double* colour) {
     if (!c || !origins || !dirs || n < 0 || !hit || !t || !p || !nrm || !colour) return FT_ERR_INVALID;
-    if (!need_device(c)) return FT_ERR_NO_DEVICE;
-    if (!c->committed) { c->err = "scene not committed"; return FT_ERR_STATE; }
-    if (n == 0) return FT_OK;
-    FT_HIP(c, hipSetDevice(c->device));
-    int32_t rc;
+    int32_t rc = debug_rays_in(c, origins, dirs, nullptr, n, 4 + 8 + 72);
+    if (rc != FT_OK || n == 0) return rc;
     const size_t N = (size_t)n;
-    if ((rc = ensure(c, c->d_dbg_in, N * 48)) != FT_OK) return rc;
-    if ((rc = ensure(c, c->d_dbg_out, N * (4 + 8 + 72))) != FT_OK) return rc;
     double* din = c->d_dbg_in.as<double>();
-    FT_HIP(c, hipMemcpyAsync(din, origins, N * 24, hipMemcpyHostToDevice, c->stream));
-    FT_HIP(c, hipMemcpyAsync(din + 3 * N, dirs, N * 24, hipMemcpyHostToDevice, c->stream));
-    c->fc_clean[0] = false;
-    FT_HIP(c, hipMemsetAsync(c->d_fc[0].p, 0, sizeof(unsigned long long), c->stream));   // the overflow count of this query
     double* dt = c->d_dbg_out.as<double>();
     double* dp = dt + N; double* dn = dp + 3 * N; double* dc = dn + 3 * N;
     int32_t* dh = reinterpret_cast<int32_t*>(dc + 3 * N);
-    const size_t lds = lds_bytes_for(c->flat);
-    ftk::Launch L{c->stream, c->n_cu * 4, lds, 0};
-    ftk::launch_debug_closest(L, c->dev_scene, din, din + 3 * N, (uint32_t)n, dh, dt, dp, dn, dc, c->d_fc[0].as<unsigned long long>());
+    ftk::Launch L{c->stream, c->n_cu * 4, lds_bytes_for(c->flat), 0};
+    ftk::launch_debug_closest(L, c->dev_scene, din, din + 3 * N, (uint32_t)n, dh, dt, dp, dn, dc, c->slots[0].d_fc.as<unsigned long long>());
     FT_HIP(c, hipGetLastError());
     FT_HIP(c, hipMemcpyAsync(t, dt, N * 8, hipMemcpyDeviceToHost, c->stream));
     FT_HIP(c, hipMemcpyAsync(p, dp, N * 24, hipMemcpyDeviceToHost, c->stream));
     FT_HIP(c, hipMemcpyAsync(nrm, dn, N * 24, hipMemcpyDeviceToHost, c->stream));
     FT_HIP(c, hipMemcpyAsync(colour, dc, N * 24, hipMemcpyDeviceToHost, c->stream));
     FT_HIP(c, hipMemcpyAsync(hit, dh, N * 4, hipMemcpyDeviceToHost, c->stream));
-    unsigned long long n_overflow = 0;
-    FT_HIP(c, hipMemcpyAsync(&n_overflow, c->d_fc[0].p, sizeof n_overflow, hipMemcpyDeviceToHost, c->stream));
-    FT_HIP(c, hipStreamSynchronize(c->stream));
-    if (n_overflow) { c->err = "CSG hit list overflow"; return FT_ERR_OVERFLOW; }
-    return FT_OK;
+    return debug_rays_done(c);
 }
 
 static int32_t debug_blocked(ft_context* c, const double* origins, const double* dirs, const double* max_dist, int64_t n, int32_t* blocked);
@@ -1386,30 +1387,15 @@ int32_t ft_debug_blocked(ft_context* c, const double* origins, const double* dir
 }
 static int32_t debug_blocked(ft_context* c, const double* origins, const double* dirs, const double* max_dist, int64_t n, int32_t* blocked) {
     if (!c || !origins || !dirs || !max_dist || n < 0 || !blocked) return FT_ERR_INVALID;
-    if (!need_device(c)) return FT_ERR_NO_DEVICE;
-    if (!c->committed) { c->err = "scene not committed"; return FT_ERR_STATE; }
-    if (n == 0) return FT_OK;
-    FT_HIP(c, hipSetDevice(c->device));
-    int32_t rc;
+    int32_t rc = debug_rays_in(c, origins, dirs, max_dist, n, 4);
+    if (rc != FT_OK || n == 0) return rc;
     const size_t N = (size_t)n;
-    if ((rc = ensure(c, c->d_dbg_in, N * 56)) != FT_OK) return rc;
-    if ((rc = ensure(c, c->d_dbg_out, N * 4)) != FT_OK) return rc;
     double* din = c->d_dbg_in.as<double>();
-    FT_HIP(c, hipMemcpyAsync(din, origins, N * 24, hipMemcpyHostToDevice, c->stream));
-    FT_HIP(c, hipMemcpyAsync(din + 3 * N, dirs, N * 24, hipMemcpyHostToDevice, c->stream));
-    FT_HIP(c, hipMemcpyAsync(din + 6 * N, max_dist, N * 8, hipMemcpyHostToDevice, c->stream));
-    c->fc_clean[0] = false;
-    FT_HIP(c, hipMemsetAsync(c->d_fc[0].p, 0, sizeof(unsigned long long), c->stream));   // the overflow count of this query
-    const size_t lds = lds_bytes_for(c->flat);
-    ftk::Launch L{c->stream, c->n_cu * 4, lds, 0};
-    ftk::launch_debug_blocked(L, c->dev_scene, din, din + 3 * N, din + 6 * N, (uint32_t)n, c->d_dbg_out.as<int32_t>(), c->d_fc[0].as<unsigned long long>());
+    ftk::Launch L{c->stream, c->n_cu * 4, lds_bytes_for(c->flat), 0};
+    ftk::launch_debug_blocked(L, c->dev_scene, din, din + 3 * N, din + 6 * N, (uint32_t)n, c->d_dbg_out.as<int32_t>(), c->slots[0].d_fc.as<unsigned long long>());
     FT_HIP(c, hipGetLastError());
     FT_HIP(c, hipMemcpyAsync(blocked, c->d_dbg_out.p, N * 4, hipMemcpyDeviceToHost, c->stream));
-    unsigned long long n_overflow = 0;
-    FT_HIP(c, hipMemcpyAsync(&n_overflow, c->d_fc[0].p, sizeof n_overflow, hipMemcpyDeviceToHost, c->stream));
-    FT_HIP(c, hipStreamSynchronize(c->stream));
-    if (n_overflow) { c->err = "CSG hit list overflow"; return FT_ERR_OVERFLOW; }
-    return FT_OK;
+    return debug_rays_done(c);
 }
 
 // getColourForRay (Shading.fs:131-139) for explicit rays through the device path: the rays enter k_bounce as level 0 with weight 1
@@ -1437,8 +1423,8 @@ static int32_t debug_colour(ft_context* c, const double* origins, const double* 
         for (int k = 0; k < 3; ++k) { soa[(size_t)k * N + i] = origins[3 * i + k]; soa[(size_t)(3 + k) * N + i] = dirs[3 * i + k]; }
         soa[6 * N + i] = 1.0; slot[i] = (uint32_t)i;
     }
-    auto* fc = c->d_fc[0].as<ftk::FrameCounters>();
-    c->fc_clean[0] = false;
+    auto* fc = c->slots[0].d_fc.as<ftk::FrameCounters>();
+    c->slots[0].fc_clean = false;
     FT_HIP(c, hipMemsetAsync(fc, 0, sizeof(ftk::FrameCounters), c->stream));
     const ftk::RayBuf rb0 = ray_view(c->d_rays[0], c->ray_capacity), rb1 = ray_view(c->d_rays[1], c->ray_capacity);
     for (int k = 0; k < 7; ++k) FT_HIP(c, hipMemcpyAsync(c->d_rays[0].as<double>() + (size_t)k * cap, soa.data() + (size_t)k * N, N * 8, hipMemcpyHostToDevice, c->stream));

@@ -154,9 +154,9 @@ const char* ft_last_error(const ft_context* ctx);
  * top-level `bspMesh 0` leaf - same triangle records, same results bit for bit; 0: they walk the mesh's BVH like every other ray; a change re-commits),
  * "classify_ahead" / "resolve_aside" / "zero_fill_skip" (1 = default: what a stream of queued frames does that a single frame cannot - the next frame's k_classify on a second
  * stream, k_resolve on a third with the sample colours double-buffered, Colour.Zero not written again into blocks the last frame of the same signature left zero; 0 switches each off; k_resolve goes aside only in frames of one chunk), "mains" (2 = default, 1 .. 3: queued frames of one chunk take turns on that many main streams, so a frame's kernels are dispatched while its predecessor's drain
- * and two frames' reflection levels fill each other's idle stretches; "two_mains" = 0 / 1 is mains = 1 / 2), "primary_reserve" (0 = default: workgroup slots such a frame's k_primary leaves free for the small kernels queued beside it), "window_hint" (0 = default; 1: the chunks of a
- * classified frame are cut as wide as the last frame of the same scene, size and sample count left them room for, up to "window_cap" listed samples - fewer empty launches on sparse frames, measured no net gain), "wave_samples" (0 = default, 16: a bounce-0 wavefront takes up to that many jitter offsets of 64 / that many pixels of an
- * 8x8 block when the sample count has the power of two in it - a narrower bundle; 1, 2, 4, 8, 16; no pixel depends on it).  Scene-affecting options need a new ft_scene_commit. */
+ * and two frames' reflection levels fill each other's idle stretches), "wave_samples" (0 = default, 16: a bounce-0 wavefront takes up to that many jitter offsets of 64 / that many pixels of an
+ * 8x8 block when the sample count has the power of two in it - a narrower bundle; 1, 2, 4, 8, 16; no pixel depends on it).  Every option reaches every device of a context.  Scene-affecting
+ * options need a new ft_scene_commit.  Any other key is refused (FT_ERR_INVALID, "unknown option"). */
 int32_t ft_set_option(ft_context* ctx, const char* key, int64_t value);
 
 /* ---- scene graph builder (Scene.fs:8-53) ------------------------------------------------- */

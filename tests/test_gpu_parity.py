@@ -967,7 +967,7 @@ def test_three_frames_in_flight_on_two_main_streams(hip):
     cams = [ft.make_camera((0.0, 0.9, -7.0), (x, 0.7, 0.0), (0, 1, 0), H.deg(40.0)) for x in (0.6, -0.9, 0.0)]
     left = [(0, 0, 128, 192)]
     plan = [(0, jit, None, False), (1, jit, None, False), (2, jit, None, True), (0, jit, None, False), (1, jit2, None, False), (2, jit2, left, False), (0, jit, None, True)]
-    hip.set_option("two_mains", 0)
+    hip.set_option("mains", 1)
     want = []
     for cam, j, tiles, rgba8 in plan:
         if rgba8:
@@ -976,8 +976,8 @@ def test_three_frames_in_flight_on_two_main_streams(hip):
             full = np.full((h, w, 3), -5.0)
             hip.render(cams[cam], w, h, spp, j, tiles=tiles, out=full)
             want.append(full)
-    for two in (1, 0):
-        hip.set_option("two_mains", two)
+    for mains in (2, 1):
+        hip.set_option("mains", mains)
         with ft.PinnedArray((len(plan), h, w, 3)) as f64, ft.PinnedArray((len(plan), h, w, 4), dtype=np.uint8) as u8:
             f64[:] = -5.0
             for rep in range(2):                                    # the second round starts with three frames of the first still in flight
@@ -985,9 +985,9 @@ def test_three_frames_in_flight_on_two_main_streams(hip):
                     hip.render_enqueue(cams[cam], w, h, spp, j, tiles=tiles, rgba8=rgba8, out=u8[k] if rgba8 else f64[k])
             st = hip.wait()
             for k, (cam, j, tiles, rgba8) in enumerate(plan):
-                assert np.array_equal(u8[k] if rgba8 else f64[k], want[k]), (two, k)
+                assert np.array_equal(u8[k] if rgba8 else f64[k], want[k]), (mains, k)
             assert st["rays_primary"] == w * h * spp
-    hip.set_option("two_mains", 1)
+    hip.set_option("mains", 2)
 
 
 def test_zero_fill_skip_and_classification_ahead_change_no_pixel(hip):

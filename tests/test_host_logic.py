@@ -165,18 +165,25 @@ def test_jitter_pattern_rule():                               # Jitter.fs:15-24:
 
 
 def test_pipeline_options_are_validated():
-    """ft_set_option: the frame-pipeline tunables of round 3 (include/functracer_hip.h) accept their documented range and refuse anything else."""
+    """ft_set_option: every tunable (include/functracer_hip.h) accepts its documented range and refuses anything else; a flag takes any
+    value.  The options of finished experiments are gone and fail like any unknown key."""
     ctx = ft.Context(host_only=True)
-    for key, good, bad in (("mains", (1, 2, 3), (0, 4, -1)), ("two_mains", (0, 1), ()), ("primary_reserve", (0, 64, 4096), (-1, 4097)),
-                           ("window_cap", (64, 80 << 20), (0, 63)), ("window_hint", (0, 1), ()), ("classify_ahead", (0, 1), ()),
-                           ("resolve_aside", (0, 1), ()), ("zero_fill_skip", (0, 1), ())):
+    flag = ((0, 1, 2, -1), ())
+    for key, (good, bad) in (("chunk_samples", ((64, 16 << 20), (63, 0, -1))), ("csg_mesh_capacity", ((1, 32, 255), (0, 256, -1))),
+                             ("csg_auto_grow", flag), ("coherent_waves", flag), ("wave_samples", ((0, 1, 2, 4, 8, 16), (-1, 3, 5, 32))),
+                             ("timing", ((0, 1, 2), (-1, 3))), ("mains", ((1, 2, 3), (0, 4, -1))), ("resolve_aside", flag),
+                             ("classify_ahead", flag), ("zero_fill_skip", flag), ("classify_pixels", flag), ("level_hint", flag),
+                             ("follow_below", ((-1, 0, 10000), (-2,))), ("bvh_builder", ((0, 1, 2, 3), (-1, 4))),
+                             ("light_space_shadows", flag), ("mesh_unclipped_bvh", flag)):
         for v in good:
             ctx.set_option(key, v)
         for v in bad:
             with pytest.raises(ft.FtError):
                 ctx.set_option(key, v)
-    with pytest.raises(ft.FtError):
-        ctx.set_option("no_such_option", 1)
+    for key in ("no_such_option", "window_hint", "window_cap", "primary_reserve", "classify_after_trace", "resolve_blocks", "two_mains"):
+        with pytest.raises(ft.FtError) as e:
+            ctx.set_option(key, 1)
+        assert e.value.status == -1 and "unknown option" in str(e.value), key
     ctx.close()
 
 

@@ -9,8 +9,8 @@ W, H, SPP = 3840, 2160, 64
 jit = ft.jitter_pattern(SPP)
 for world in (8, 4, 2):
     tiles = tiling.bands_for_rank(W, H, 0, world)
-    for label, opts in (("default", {}), ("one window", {"chunk_samples": 40 << 20}), ("one window, one main", {"chunk_samples": 40 << 20, "two_mains": 0}), ("default, one main", {"two_mains": 0})):
-        for k, v in {"chunk_samples": 16 << 20, "two_mains": 1, **opts}.items(): ctx.set_option(k, v)
+    for label, opts in (("default", {}), ("one window", {"chunk_samples": 40 << 20}), ("one window, one main", {"chunk_samples": 40 << 20, "mains": 1}), ("default, one main", {"mains": 1})):
+        for k, v in {"chunk_samples": 16 << 20, "mains": 2, **opts}.items(): ctx.set_option(k, v)
         best = 1e9
         for rep in range(3):
             n = 48
