@@ -60,6 +60,9 @@ def hip_lib():
         lib.ft_render_enqueue_into.argtypes = [C.c_void_p, C.POINTER(_capi.ft_camera), C.c_int32, C.c_int32, C.c_int32, _capi.c_double_p, C.c_int32, C.c_uint64, C.POINTER(_capi.ft_rect), C.c_int32, C.c_int32, C.c_void_p]
         lib.ft_get_kernel_times.argtypes = [C.c_void_p, _capi.c_double_p, _capi.c_int32_p]
         lib.ft_quantise_rgba8.argtypes = [_capi.c_double_p, C.c_int64, C.POINTER(C.c_uint8)]
+        for name, res, args in _capi.PROGRESSIVE_SIGNATURES:
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = res, args
         _hip = lib
     return _hip
 
@@ -302,6 +305,60 @@ class Context(SceneBuilder):
         self._check(self._lib.ft_get_kernel_times(self._ctx, _capi.dptr(ms), n.ctypes.data_as(_capi.c_int32_p)))
         names = ["other", "closest", "shade", "resolve", "primary"]   # "other": the fill, k_classify (and k_resolve unless "timing" = 2); "shade": k_bounce, all levels; "closest": unused
         return {k: {"ms": float(ms[i]), "launches": int(n[i])} for i, k in enumerate(names)}
+
+    # progressive accumulation (ft_progressive_*, include/functracer_hip.h) ---------------------------
+    def progressive_begin(self, camera, res_h, res_v, max_depth=MAX_DEPTH, tiles=None, tolerance=0.0, min_samples=2):
+        """Start accumulating one fixed request pass by pass (replaces any earlier accumulation).  tolerance > 0: adaptive - an 8x8 block
+        stops receiving samples once it has min_samples and the standard error of every pixel's mean is within tolerance."""
+        rects, n_rects = _capi.make_rects(tiles)
+        self._check(self._lib.ft_progressive_begin(self._ctx, C.byref(camera), res_h, res_v, max_depth, rects, n_rects, float(tolerance), int(min_samples)))
+        self._progressive = (res_h, res_v, tolerance > 0)
+
+    def progressive_pass(self, spp, jitter, seed=DEFAULT_SEED, rgba8=False, out=None, fetch=True):
+        """spp new samples (jitter: spp x 2) for every block not yet retired.  Returns (running mean frame - rgb[res_v, res_h, 3] float64, or
+        rgba[res_v, res_h, 4] uint8 with rgba8 - and this pass's stats dict); with fetch=False the frame stays in HBM (returns (None, stats))."""
+        res_h, res_v, _ = self._progressive_shape()
+        jitter = _capi.as_f64(jitter, (int(spp), 2)) if spp > 0 else np.zeros((1, 2))
+        if fetch and out is None:
+            out = np.zeros((res_v, res_h, 4), dtype=np.uint8) if rgba8 else np.zeros((res_v, res_h, 3))
+        st = _capi.ft_stats()
+        self._check(self._lib.ft_progressive_pass(self._ctx, int(spp), _capi.dptr(jitter), int(seed), 1 if rgba8 else 0,
+                                                  out.ctypes.data_as(C.c_void_p) if fetch else None, C.byref(st)))
+        return (out if fetch else None), st.as_dict()
+
+    def progressive_fetch(self):
+        """(mean[res_v, res_h, 3], stderr[res_v, res_h, 3] or None for a plain accumulation, samples[res_v, res_h] uint32) of the tile
+        pixels; other pixels stay 0."""
+        res_h, res_v, adaptive = self._progressive_shape()
+        mean, samples = np.zeros((res_v, res_h, 3)), np.zeros((res_v, res_h), dtype=np.uint32)
+        se = np.zeros((res_v, res_h, 3)) if adaptive else None
+        self._check(self._lib.ft_progressive_fetch(self._ctx, _capi.dptr(mean), _capi.dptr(se) if adaptive else None,
+                                                   samples.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return mean, se, samples
+
+    def progressive_status(self):
+        out = (C.c_int64 * 6)()
+        self._check(self._lib.ft_progressive_status(self._ctx, out))
+        keys = ["passes", "min_samples", "max_samples", "blocks", "blocks_retired", "samples_traced"]
+        return dict(zip(keys, list(out)))
+
+    def progressive_end(self):
+        self._check(self._lib.ft_progressive_end(self._ctx))
+        self._progressive = None
+
+    def progressive(self, camera, res_h, res_v, pieces, seeds, tolerance=0.0, min_samples=2, max_depth=MAX_DEPTH, tiles=None, rgba8=False):
+        """Begin, then one pass per piece of a jitter pattern (pieces: arrays of n x 2 offsets; seeds: one per pass), yielding
+        (frame, stats) after each; the accumulation stays open afterwards for progressive_fetch / progressive_status."""
+        self.progressive_begin(camera, res_h, res_v, max_depth=max_depth, tiles=tiles, tolerance=tolerance, min_samples=min_samples)
+        for piece, seed in zip(pieces, seeds):
+            piece = _capi.as_f64(piece).reshape(-1, 2)
+            yield self.progressive_pass(piece.shape[0], piece, seed=seed, rgba8=rgba8)
+
+    def _progressive_shape(self):
+        shape = getattr(self, "_progressive", None)
+        if shape is None:                                           # the frame's size is unknown: nothing to size the output by
+            raise FtError(-5, "no progressive accumulation (progressive_begin)")
+        return shape
 
     def closest(self, origins, dirs):
         """Scene.intersectScene (Scene.fs:118) for explicit rays, through the device path."""

@@ -88,6 +88,17 @@ BUILDER_SIGNATURES = [
 ]
 
 
+# ft_progressive_* (include/functracer_hip.h): progressive accumulation over one fixed request.
+PROGRESSIVE_SIGNATURES = [
+    ("ft_progressive_begin", C.c_int32, [C.c_void_p, C.POINTER(ft_camera), C.c_int32, C.c_int32, C.c_int32, C.POINTER(ft_rect), C.c_int32,
+                                         C.c_double, C.c_int32]),
+    ("ft_progressive_pass", C.c_int32, [C.c_void_p, C.c_int32, c_double_p, C.c_uint64, C.c_int32, C.c_void_p, C.POINTER(ft_stats)]),
+    ("ft_progressive_fetch", C.c_int32, [C.c_void_p, c_double_p, c_double_p, C.POINTER(C.c_uint32)]),
+    ("ft_progressive_status", C.c_int32, [C.c_void_p, C.POINTER(C.c_int64)]),
+    ("ft_progressive_end", C.c_int32, [C.c_void_p]),
+]
+
+
 class fth_builder(C.Structure):
     _fields_ = [(name, C.CFUNCTYPE(res, *args)) for name, res, args in BUILDER_SIGNATURES]
 

@@ -209,6 +209,22 @@ struct ft_context {
     int32_t last_res_h = 0, last_res_v = 0;
     double k_ms[kStages] = {0, 0, 0, 0, 0};
     int32_t k_launches[kStages] = {0, 0, 0, 0, 0};
+    int64_t last_active_pix = 0;    // pixels in the active list of the last frame retired (all listed ones when it was not classified)
+    // A progressive accumulation (ft_progressive_begin .. _end).  Every device holds the request with its share of the frame (its 8-row
+    // bands on a multi-device context) and the running state of that share by position in its pixel list; device 0 also the pass count.
+    // The state is double-buffered: a pass reads side `cur` and writes side cur ^ 1, and cur flips only once every device's pass has
+    // completed without a hit-list overflow, so the pass that runs again after the lists grew starts from the same sums.
+    struct Progressive {
+        bool open = false;
+        ft_camera cam{};
+        int32_t res_h = 0, res_v = 0, max_depth = 0, min_samples = 0;
+        double tolerance = 0.0;
+        std::vector<ft_rect> tiles;  // this device's rects, as the passes request them (clipped by plan_pixels)
+        int64_t n_pix = 0, n_blocks = 0, passes = 0, samples = 0, traced = 0;   // samples: the most any pixel can have; traced: the last pass's
+        DeviceBuf d_sum[2], d_sq[2], d_blk[2];
+        int cur = 0;
+        void release() { for (int k = 0; k < 2; ++k) { d_sum[k].release(); d_sq[k].release(); d_blk[k].release(); } *this = Progressive(); }
+    } prog;
 };
 
 namespace {
@@ -386,6 +402,7 @@ void ft_destroy(ft_context* c) {
         for (DeviceBuf& b : c->d_acc) b.release();
         for (DeviceBuf* b : {&c->d_out, &c->d_out8, &c->d_out_index, &c->d_pixels, &c->d_jitter, &c->d_wave_counts, &c->d_dbg_in, &c->d_dbg_out}) b->release();
         for (auto& f : c->slots) f.release();
+        c->prog.release();
         if (c->classified) (void)hipEventDestroy(c->classified);
         for (hipEvent_t& e : c->acc_free) if (e) { (void)hipEventDestroy(e); e = nullptr; }
         if (c->side) (void)hipStreamDestroy(c->side);
@@ -512,8 +529,15 @@ ft_node ft_sg_texture_image(ft_context* c, const uint8_t* rgb24, int32_t width, 
     return add_node(c, std::move(n));
 }
 
+// Ends the progressive accumulation of a context, on every device (its buffers are freed).
+static void progressive_close(ft_context* c) {
+    if (!c->prog.open) return;
+    for (ft_context* d : devices(c)) { if (!d->host_only) (void)hipSetDevice(d->device); d->prog.release(); }
+}
+
 int32_t ft_scene_clear(ft_context* c) {
     if (!c) return FT_ERR_INVALID;
+    progressive_close(c);
     c->graph.nodes.clear(); c->graph.lights.clear(); c->graph.root = -1; c->committed = false;
     return FT_OK;
 }
@@ -551,9 +575,16 @@ int32_t ft_scene_add_positional(ft_context* c, const double pos[3], const double
 static int32_t upload_scene(ft_context* c);
 static int32_t retire_pending(ft_context* c, ft_stats* stats);
 static bool any_pending(const ft_context* c, bool on_second_main = false) { for (const auto& f : c->slots) if (f.pending && (!on_second_main || f.main_ix != 0)) return true; return false; }
+static int32_t commit_scene(ft_context* c);
 
+// A caller's commit ends the progressive accumulation; the re-commit of with_growing_hit_lists (commit_scene) does not.
 int32_t ft_scene_commit(ft_context* c) {
     if (!c) return FT_ERR_INVALID;
+    progressive_close(c);
+    return commit_scene(c);
+}
+
+static int32_t commit_scene(ft_context* c) {
     using clock = std::chrono::steady_clock;
     auto ms_since = [](clock::time_point t0) { return std::chrono::duration<double, std::milli>(clock::now() - t0).count(); };
     for (double& v : c->commit_ms) v = 0.0;
@@ -757,6 +788,7 @@ void ft_host_free(void* p) { if (p) (void)hipHostFree(p); }
 struct RenderRequest {
     const ft_camera* cam; int32_t res_h, res_v, spp; const double* jitter_xy; int32_t max_depth; uint64_t seed;
     const ft_rect* tiles; int32_t n_tiles; int format;               // 0: FP64 RGB frame, 1: RGBA8 frame
+    bool progressive = false;                                        // a pass of the context's progressive accumulation (ft_progressive_pass)
 };
 static int32_t render_single(ft_context* c, const RenderRequest& q, void* out, ft_stats* stats, bool defer);
 static int32_t retire_frame(ft_context* c, ft_context::FrameSlot& f, ft_stats* stats);
@@ -779,9 +811,9 @@ static int32_t with_growing_hit_lists(ft_context* c, const std::function<int32_t
         const int32_t before = c->graph.csg_mesh_capacity;
         const std::string why = c->err;
         c->graph.csg_mesh_capacity = std::min(255, before * 2);
-        if (ft_scene_commit(c) != FT_OK) {                          // the longer lists do not fit: back to the scene as it was
+        if (commit_scene(c) != FT_OK) {                            // the longer lists do not fit: back to the scene as it was
             c->graph.csg_mesh_capacity = before;
-            if (ft_scene_commit(c) == FT_OK) c->err = why;
+            if (commit_scene(c) == FT_OK) c->err = why;
             return FT_ERR_OVERFLOW;
         }
         rc = run();
@@ -877,6 +909,8 @@ struct FramePlan {
     int64_t n_pix_total = 0;
     bool classify = false;
     bool simple = false;                 // a queued frame of one chunk: k_resolve aside, k_primary on the next main stream (queue_frame)
+    bool progressive = false;            // a progressive pass: k_resolve_progressive over the accumulation's running sums
+    bool mask_only = false;              // ... classified only by the retired blocks (adaptive passes of frames the host does not classify)
     double jitter_extent = 1.0;
     uint64_t signature = 0;              // scene, size, samples, depth, list, chunking: keys the level hint
     uint64_t zsig = 0;                   // what decides which blocks k_classify finishes: keys the zero-fill skip
@@ -888,19 +922,46 @@ struct FramePlan {
 // Pixel list restricted to the tiles.  The reference enumerates pixels y-major, x (Image.fs:104); samples are
 // independent, so the device is free to walk them in any order: rects whose sides are multiples of 8 are
 // walked in 8x8 pixel blocks, which makes the 64 lanes of a wavefront a compact bundle of rays.
-static void plan_pixels(ft_context* c, const RenderRequest& q, FramePlan& p) {
-    const int32_t res_h = q.res_h, res_v = q.res_v;
-    p.corner = q.spp == 0;
-    p.spp = p.corner ? 1 : q.spp;
-    if (!q.tiles) p.rects.push_back(ft_rect{0, 0, res_h, res_v});
+static std::vector<ft_rect> clip_rects(const RenderRequest& q) {
+    std::vector<ft_rect> rects;
+    if (!q.tiles) rects.push_back(ft_rect{0, 0, q.res_h, q.res_v});
     else for (int k = 0; k < q.n_tiles; ++k) {
         ft_rect r = q.tiles[k];
         if (r.x0 < 0) { r.w += r.x0; r.x0 = 0; }
         if (r.y0 < 0) { r.h += r.y0; r.y0 = 0; }
-        if (r.x0 + r.w > res_h) r.w = res_h - r.x0;
-        if (r.y0 + r.h > res_v) r.h = res_v - r.y0;
-        if (r.w > 0 && r.h > 0) p.rects.push_back(r);
+        if (r.x0 + r.w > q.res_h) r.w = q.res_h - r.x0;
+        if (r.y0 + r.h > q.res_v) r.h = q.res_v - r.y0;
+        if (r.w > 0 && r.h > 0) rects.push_back(r);
     }
+    return rects;
+}
+// The pixel list of (non-corner) rects; returns whether it is made of whole 8x8 tiles.
+static bool list_pixels(const std::vector<ft_rect>& rects, int32_t res_h, std::vector<uint32_t>& px) {
+    px.clear();
+    bool tiled = true;
+    for (const ft_rect& r : rects) {
+        if (r.w % 8 == 0 && r.h % 8 == 0) {
+            // inside a block the pixels run in Z order (first its top-left corner, last its bottom-right one, as k_classify expects):
+            // the 4 or 16 consecutive pixels a wavefront takes under grouped numbering are a 2x2 or 4x4 square, not a strip
+            for (int ty = 0; ty < r.h; ty += 8) for (int tx = 0; tx < r.w; tx += 8)
+                for (int k = 0; k < 64; ++k) {
+                    const int ix = (k & 1) | ((k >> 1) & 2) | ((k >> 2) & 4), iy = ((k >> 1) & 1) | ((k >> 2) & 2) | ((k >> 3) & 4);
+                    px.push_back((uint32_t)((r.y0 + ty + iy) * res_h + r.x0 + tx + ix));
+                }
+        } else {
+            tiled = false;
+            for (int y = r.y0; y < r.y0 + r.h; ++y) for (int x = r.x0; x < r.x0 + r.w; ++x) px.push_back((uint32_t)(y * res_h + x));
+        }
+    }
+    return tiled;
+}
+
+static void plan_pixels(ft_context* c, const RenderRequest& q, FramePlan& p) {
+    const int32_t res_h = q.res_h, res_v = q.res_v;
+    p.corner = q.spp == 0;
+    p.spp = p.corner ? 1 : q.spp;
+    p.progressive = q.progressive;
+    p.rects = clip_rects(q);
     const std::vector<ft_rect>& rects = p.rects;
     p.same_list = !p.corner && !c->pixels_corner && c->last_n_pix > 0 && c->last_res_h == res_h && c->last_res_v == res_v &&
                   c->pixel_rects.size() == rects.size() && (rects.empty() || std::memcmp(c->pixel_rects.data(), rects.data(), rects.size() * sizeof(ft_rect)) == 0);
@@ -922,22 +983,7 @@ static void plan_pixels(ft_context* c, const RenderRequest& q, FramePlan& p) {
         }
         c->pixel_rects = rects; c->pixels_corner = true; c->pixels_tiled = false; c->last_n_pix = 0;
     } else if (!p.same_list) {
-        px.clear();
-        bool tiled = true;
-        for (const ft_rect& r : rects) {
-            if (r.w % 8 == 0 && r.h % 8 == 0) {
-                // inside a block the pixels run in Z order (first its top-left corner, last its bottom-right one, as k_classify expects):
-                // the 4 or 16 consecutive pixels a wavefront takes under grouped numbering are a 2x2 or 4x4 square, not a strip
-                for (int ty = 0; ty < r.h; ty += 8) for (int tx = 0; tx < r.w; tx += 8)
-                    for (int k = 0; k < 64; ++k) {
-                        const int ix = (k & 1) | ((k >> 1) & 2) | ((k >> 2) & 4), iy = ((k >> 1) & 1) | ((k >> 2) & 2) | ((k >> 3) & 4);
-                        px.push_back((uint32_t)((r.y0 + ty + iy) * res_h + r.x0 + tx + ix));
-                    }
-            } else {
-                tiled = false;
-                for (int y = r.y0; y < r.y0 + r.h; ++y) for (int x = r.x0; x < r.x0 + r.w; ++x) px.push_back((uint32_t)(y * res_h + x));
-            }
-        }
+        const bool tiled = list_pixels(rects, res_h, px);
         c->pixel_rects = rects; c->pixels_corner = false; c->pixels_tiled = tiled; c->last_n_pix = 0;
     }
     p.n_pix_total = (int64_t)px.size();
@@ -971,6 +1017,9 @@ static void plan_chunks(ft_context* c, const RenderRequest& q, bool defer, Frame
     // the counter fill; 3840x2160x64 of the bunny: 16 windows, 14 empty).  Windows widened by the last frame's active count measured no
     // net gain.
     const int64_t chunk_budget = p.classify ? 5 * chunk_samples : ((c->variant & 2) ? chunk_samples : 2 * chunk_samples);
+    // An adaptive progressive pass always runs k_classify: on a frame the host does not classify (unbounded items, a focus camera, the
+    // option off, an unbounded pattern) only to leave the retired blocks out of the active list.  Its windows stay as wide as unclassified ones.
+    if (p.progressive && c->prog.tolerance > 0.0 && !p.classify) p.classify = p.mask_only = true;
     p.pix_per_chunk = std::max<int64_t>(1, std::min<int64_t>(n_pix_total, chunk_budget / spp));
     if (p.pix_per_chunk > 64) {
         // equal chunks rather than full ones and a remainder: a short last chunk is all latency (measured on night-house at
@@ -1037,6 +1086,7 @@ static int32_t queue_classify(ft_context* c, const RenderRequest& q, const Frame
     const ftk::Primary all{p.cam, c->d_pixels.as<uint32_t>(), c->d_jitter.as<double>(), 0u, (uint32_t)p.n_pix_total, p.spp, (uint32_t)q.res_h,
                            (unsigned long long)q.seed, 1.0 / (double)p.n_pix_total, 1.0 / (double)q.res_h, nullptr, nullptr};
     const ftk::ClassifyOut cls{F.d_block_pos.as<int32_t>(), F.d_pos_block.as<uint32_t>(), c->d_wave_counts.as<uint32_t>()};
+    const uint32_t* retired = p.progressive ? c->prog.d_blk[c->prog.cur].as<uint32_t>() : nullptr;   // a progressive pass leaves its retired blocks out
     auto* fc = F.d_fc.as<ftk::FrameCounters>();
     const uint32_t epoch = ++c->classify_epoch;
     // A queued frame's classification reads nothing the frames before it write (its slot's buffers were free once the slot's previous
@@ -1049,11 +1099,11 @@ static int32_t queue_classify(ft_context* c, const RenderRequest& q, const Frame
     if (!c->classified) FT_HIP(c, hipEventCreateWithFlags(&c->classified, hipEventDisableTiming));
     else FT_HIP(c, hipStreamWaitEvent(cs, c->classified, 0));  // one classification at a time, whichever streams they are on
     if (ahead) {
-        ftk::launch_classify(Lg, c->dev_scene, all, cls, p.jitter_extent, epoch, fc);
+        ftk::launch_classify(Lg, c->dev_scene, all, cls, p.jitter_extent, epoch, fc, retired, p.mask_only);
         FT_HIP(c, hipEventRecord(c->classified, c->side));
         FT_HIP(c, hipStreamWaitEvent(F.ev.ms, c->classified, 0));
     } else {
-        F.ev.timed(kStageOther, [&] { ftk::launch_classify(Lg, c->dev_scene, all, cls, p.jitter_extent, epoch, fc); });
+        F.ev.timed(kStageOther, [&] { ftk::launch_classify(Lg, c->dev_scene, all, cls, p.jitter_extent, epoch, fc, retired, p.mask_only); });
         FT_HIP(c, hipEventRecord(c->classified, F.ev.ms));
     }
     F.ev.fresh = false;
@@ -1071,8 +1121,8 @@ static int32_t queue_chunks(ft_context* c, const RenderRequest& q, const FramePl
     const ftk::Launch Lg{ms, c->n_cu * 8, 0, 0};
     const ftk::Launch Lr{ms, c->n_cu * c->blocks_resolve, 0, 0};
     const ftk::RayBuf rb[2] = {ray_view(c->d_rays[2 * main_ix], c->ray_capacity), ray_view(c->d_rays[2 * main_ix + 1], c->ray_capacity)};
-    const bool zeros_in_place = p.classify && c->opt.zero_fill_skip && c->zero_signature[q.format] == p.zsig;
-    c->zero_signature[q.format] = p.classify ? p.zsig : 0;
+    const bool zeros_in_place = p.classify && !p.progressive && c->opt.zero_fill_skip && c->zero_signature[q.format] == p.zsig;
+    c->zero_signature[q.format] = p.classify && !p.progressive ? p.zsig : 0;   // (a progressive pass writes means into the finished blocks)
     double* const out_rgb = q.format == 1 ? nullptr : c->d_out.as<double>();
     uint8_t* const out_rgba = q.format == 1 ? c->d_out8.as<uint8_t>() : nullptr;
     const uint32_t stride = (uint32_t)(p.corner ? q.res_h + 1 : q.res_h);
@@ -1103,7 +1153,15 @@ static int32_t queue_chunks(ft_context* c, const RenderRequest& q, const FramePl
         const ftk::ResolveArgs ra{acc, n_samples, p.classify ? &fc->counts : nullptr, job.id_base, n_pix, p.spp,
                                   p.classify ? F.d_pos_block.as<uint32_t>() : nullptr, (p.classify && first && !zeros_in_place) ? F.d_block_pos.as<int32_t>() : nullptr,
                                   (uint32_t)(p.n_pix_total / 64), c->d_pixels.as<uint32_t>(), out_rgb, out_rgba, (uint32_t)gen.group_log2, fc, last ? F.d_report : nullptr};
-        if (p.simple) {
+        if (p.progressive) {
+            ft_context::Progressive& P = c->prog;
+            const int in = P.cur, out = P.cur ^ 1;
+            const ftk::ProgressiveArgs pa{P.d_sum[in].as<double>(), P.d_sum[out].as<double>(), P.d_sq[in].as<double>(), P.d_sq[out].as<double>(),
+                                          P.d_blk[in].as<uint32_t>(), P.d_blk[out].as<uint32_t>(), (uint32_t)P.n_pix, (uint32_t)P.min_samples, P.tolerance};
+            ftk::ResolveArgs rp = ra;
+            rp.block_pos = p.classify && first ? F.d_block_pos.as<int32_t>() : nullptr;   // every block the pass does not trace, every pass
+            E.timed(kStageResolve, [&] { ftk::launch_resolve_progressive(Lr, rp, pa); });
+        } else if (p.simple) {
             // behind the frame's tracing kernels, on its own stream: the main stream goes straight on with the next frame.  Where the
             // tracing ends: the event that closed its last bracket, if that is still the stream's last entry.
             hipEvent_t traced = E.fresh ? E.boundary : nullptr;
@@ -1199,8 +1257,10 @@ static int32_t render_single(ft_context* c, const RenderRequest& q, void* out, f
     plan_pixels(c, q, p);
     if (stats) std::memset(stats, 0, sizeof *stats);
     if (p.n_pix_total == 0) return FT_OK;
+    if (q.progressive && p.n_pix_total != c->prog.n_pix) { c->err = "progressive pass: the pixel list differs from the accumulation's"; return FT_ERR_STATE; }
     plan_chunks(c, q, defer, p);
     if (p.cap > 0x7FFFFFFFll) { c->err = "chunk too large"; return FT_ERR_INVALID; }
+    if (p.classify && p.progressive && p.jobs.size() > 1 && p.pix_per_chunk % 64) { c->err = "progressive pass: too many samples per pass for whole-block windows"; return FT_ERR_UNSUPPORTED; }
     return queue_frame(c, q, p, out, stats, defer, wall0);
 }
 
@@ -1218,6 +1278,7 @@ static int32_t retire_frame(ft_context* c, ft_context::FrameSlot& F, ft_stats* s
     while (deepest + 1 <= ftk::kMaxBounce && (int64_t)F.h_report->n_rays[deepest + 1] > few) ++deepest;
     c->staged_hint = deepest; c->staged_signature = F.signature;
     const int timing = F.ev.timing; const int32_t spp = F.spp; const int64_t n_pix_total = F.n_pix_total; const bool classify = F.classify;
+    c->last_active_pix = classify ? (int64_t)F.h_report->n_pix_active : n_pix_total;
     hipEvent_t ev0 = F.ev.ev0, ev1 = F.ev.ev1;
     double bracketed = 0.0, traced = 0.0;
     for (auto& s : F.ev.spans) {
@@ -1317,6 +1378,159 @@ int32_t ft_render_wait(ft_context* c, ft_stats* stats) {
         if (stats) { const double wall = std::max(stats->wall_ms, sd.wall_ms); add_stats(stats, sd); stats->wall_ms = wall; }
     }
     return rc;
+}
+
+// ------------------------------------------------------------------------------------------ progressive accumulation
+// A progressive render is a run of blocking frames over one fixed request whose k_resolve goes on from each pixel's running sum
+// (k_resolve_progressive): the sum of a pixel's samples in pass order, then sample order, is the sum one ft_render over the concatenated
+// pattern forms, so the mean S / n is that frame bit for bit.  See functracer_hip.h.
+static const double kNoJitter[2] = {0.0, 0.0};
+static RenderRequest progressive_request(const ft_context::Progressive& P) {
+    return RenderRequest{&P.cam, P.res_h, P.res_v, 1, kNoJitter, P.max_depth, 0, P.tiles.data(), (int32_t)P.tiles.size(), 0, true};
+}
+
+int32_t ft_progressive_begin(ft_context* c, const ft_camera* cam, int32_t res_h, int32_t res_v, int32_t max_depth, const ft_rect* tiles, int32_t n_tiles,
+                             double tolerance, int32_t min_samples) {
+    if (!c) return FT_ERR_INVALID;
+    if (!need_device(c)) return FT_ERR_NO_DEVICE;
+    const RenderRequest q{cam, res_h, res_v, 1, kNoJitter, max_depth, 0, tiles, n_tiles, 0};
+    int32_t rc = check_request(c, q);
+    if (rc != FT_OK) return rc;
+    if (tolerance != tolerance) { c->err = "progressive tolerance is NaN"; return FT_ERR_INVALID; }
+    const bool adaptive = tolerance > 0.0;
+    if (adaptive && min_samples < 2) { c->err = "an adaptive progressive render needs min_samples >= 2 (a standard error needs two samples)"; return FT_ERR_INVALID; }
+    if (adaptive) for (const ft_rect& r : clip_rects(q))
+        if (r.w % 8 || r.h % 8) { c->err = "adaptive progressive rendering retires 8x8 blocks: every clipped tile needs sides that are multiples of 8"; return FT_ERR_UNSUPPORTED; }
+    if (!c->committed) { c->err = "scene not committed (ft_scene_commit)"; return FT_ERR_STATE; }
+    progressive_close(c);                                           // a second begin replaces the first
+    const std::vector<ft_context*> devs = devices(c);
+    const std::vector<std::vector<ft_rect>> share = devs.size() > 1 ? band_shares(q, devs.size()) : std::vector<std::vector<ft_rect>>{clip_rects(q)};
+    for (size_t d = 0; d < devs.size(); ++d) {
+        ft_context* D = devs[d];
+        ft_context::Progressive& P = D->prog;
+        P.open = true;
+        P.cam = *cam; P.res_h = res_h; P.res_v = res_v; P.max_depth = max_depth; P.tolerance = adaptive ? tolerance : 0.0; P.min_samples = adaptive ? min_samples : 0;
+        P.tiles = share[d];
+        P.n_pix = 0;
+        if (!P.tiles.empty()) for (const ft_rect& r : clip_rects(progressive_request(P))) P.n_pix += (int64_t)r.w * r.h;
+        P.n_blocks = (P.n_pix + 63) / 64;
+        if (P.n_pix == 0) continue;
+        const size_t plane_bytes = (size_t)P.n_pix * 24;
+        rc = hipSetDevice(D->device) == hipSuccess ? FT_OK : FT_ERR_HIP;
+        for (int k = 0; k < 2 && rc == FT_OK; ++k)
+            if ((rc = ensure(D, P.d_sum[k], plane_bytes)) != FT_OK || (adaptive && (rc = ensure(D, P.d_sq[k], plane_bytes)) != FT_OK) ||
+                (rc = ensure(D, P.d_blk[k], (size_t)P.n_blocks * 4)) != FT_OK) break;
+        if (rc == FT_OK && (hipMemsetAsync(P.d_sum[0].p, 0, plane_bytes, D->stream) != hipSuccess || (adaptive && hipMemsetAsync(P.d_sq[0].p, 0, plane_bytes, D->stream) != hipSuccess) ||
+                            hipMemsetAsync(P.d_blk[0].p, 0, (size_t)P.n_blocks * 4, D->stream) != hipSuccess || hipStreamSynchronize(D->stream) != hipSuccess)) {
+            D->err = "progressive accumulation: clearing the running sums failed"; rc = FT_ERR_HIP;
+        }
+        if (rc != FT_OK) { if (D != c) c->err = D->err; progressive_close(c); return rc; }
+    }
+    return FT_OK;
+}
+
+int32_t ft_progressive_pass(ft_context* c, int32_t spp, const double* jitter_xy, uint64_t seed, int32_t rgba8, void* out, ft_stats* stats) {
+    if (!c) return FT_ERR_INVALID;
+    if (!need_device(c)) return FT_ERR_NO_DEVICE;
+    if (!c->prog.open) { c->err = "no progressive accumulation (ft_progressive_begin; a caller's ft_scene_commit or ft_scene_clear ends it)"; return FT_ERR_STATE; }
+    if (spp == 0) { c->err = "a progressive pass needs spp >= 1: corner sampling's blend is not a per-pixel average"; return FT_ERR_UNSUPPORTED; }
+    if (spp < 0 || !jitter_xy) { c->err = "bad ft_progressive_pass argument"; return FT_ERR_INVALID; }
+    if (c->prog.samples + spp > 0x7FFFFFFFll) { c->err = "more than 2^31 - 1 samples per pixel"; return FT_ERR_INVALID; }
+    const auto wall0 = std::chrono::steady_clock::now();
+    const std::vector<ft_context*> devs = devices(c);
+    std::vector<ft_stats> sts(devs.size());
+    // One host thread per device, as render_frame: every device traces its share and copies its bands of the means into `out`.  A hit-list
+    // overflow anywhere re-commits and runs the pass again on every device, from the same side of the running sums.
+    const int32_t rc = with_growing_hit_lists(c, [&] {
+        std::vector<int32_t> rcs(devs.size(), FT_OK);
+        on_every_device(c, std::vector<bool>(devs.size(), true), [&](size_t d) {
+            ft_context* D = devs[d];
+            std::memset(&sts[d], 0, sizeof(ft_stats));
+            if (D->prog.n_pix == 0) { D->last_n_pix = 0; return; }
+            RenderRequest q = progressive_request(D->prog);
+            q.spp = spp; q.jitter_xy = jitter_xy; q.seed = seed; q.format = rgba8 ? 1 : 0;
+            rcs[d] = render_single(D, q, out, &sts[d], false);
+        });
+        for (size_t d = 0; d < devs.size(); ++d) if (rcs[d] != FT_OK) { if (d) c->err = devs[d]->err; return rcs[d]; }
+        return (int32_t)FT_OK;
+    });
+    if (rc != FT_OK) return rc;
+    c->prog.passes += 1; c->prog.samples += spp; c->prog.traced = 0;
+    for (ft_context* D : devs) if (D->prog.n_pix > 0) { D->prog.cur ^= 1; c->prog.traced += D->last_active_pix * spp; }
+    if (stats) {
+        std::memset(stats, 0, sizeof *stats);
+        for (auto& s : sts) add_stats(stats, s);
+        stats->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+    }
+    return FT_OK;
+}
+
+// fn(device, its list's pixel ids, running sums, sums of squares (adaptive only, when `squares`), block words) for every device with pixels.
+static int32_t progressive_read(ft_context* c, bool squares, const std::function<void(const ft_context::Progressive&, const std::vector<uint32_t>&,
+                                const std::vector<double>&, const std::vector<double>&, const std::vector<uint32_t>&)>& fn) {
+    for (ft_context* D : devices(c)) {
+        const ft_context::Progressive& P = D->prog;
+        if (P.n_pix == 0) continue;
+        const size_t n = (size_t)P.n_pix;
+        std::vector<double> sum(3 * n), sq(squares ? 3 * n : 0);
+        std::vector<uint32_t> blk((size_t)P.n_blocks), px;
+        FT_HIP(c, hipSetDevice(D->device));
+        FT_HIP(c, hipStreamSynchronize(D->stream));
+        FT_HIP(c, hipMemcpy(sum.data(), P.d_sum[P.cur].p, 3 * n * 8, hipMemcpyDeviceToHost));
+        if (squares) FT_HIP(c, hipMemcpy(sq.data(), P.d_sq[P.cur].p, 3 * n * 8, hipMemcpyDeviceToHost));
+        FT_HIP(c, hipMemcpy(blk.data(), P.d_blk[P.cur].p, blk.size() * 4, hipMemcpyDeviceToHost));
+        list_pixels(clip_rects(progressive_request(P)), P.res_h, px);
+        fn(P, px, sum, sq, blk);
+    }
+    return FT_OK;
+}
+
+int32_t ft_progressive_fetch(ft_context* c, double* mean_rgb, double* stderr_rgb, uint32_t* samples) {
+    if (!c) return FT_ERR_INVALID;
+    if (!need_device(c)) return FT_ERR_NO_DEVICE;
+    if (!c->prog.open) { c->err = "no progressive accumulation (ft_progressive_begin)"; return FT_ERR_STATE; }
+    if (stderr_rgb && !(c->prog.tolerance > 0.0)) { c->err = "standard errors are kept by adaptive accumulations only (tolerance > 0)"; return FT_ERR_STATE; }
+    return progressive_read(c, stderr_rgb != nullptr, [&](const ft_context::Progressive& P, const std::vector<uint32_t>& px, const std::vector<double>& sum,
+                                                         const std::vector<double>& sq, const std::vector<uint32_t>& blk) {
+        const size_t n = (size_t)P.n_pix;
+        for (size_t i = 0; i < n; ++i) {
+            const uint32_t cnt = blk[i >> 6] & ~ftk::kRetired;
+            const double dn = (double)cnt;
+            const size_t o = px[i];
+            for (int ch = 0; ch < 3; ++ch) {
+                const double S = sum[(size_t)ch * n + i];
+                if (mean_rgb) mean_rgb[3 * o + ch] = cnt ? S / dn : 0.0;
+                if (stderr_rgb) {                                   // as k_resolve_progressive judges it
+                    double se = 0.0;
+                    if (cnt >= 2) { const double m = S / dn, v0 = sq[(size_t)ch * n + i] / dn - m * m, v = (v0 < 0.0 ? 0.0 : v0) * dn / (dn - 1.0); se = std::sqrt(v / dn); }
+                    stderr_rgb[3 * o + ch] = se;
+                }
+            }
+            if (samples) samples[o] = cnt;
+        }
+    });
+}
+
+int32_t ft_progressive_status(ft_context* c, int64_t out[6]) {
+    if (!c || !out) return FT_ERR_INVALID;
+    if (!need_device(c)) return FT_ERR_NO_DEVICE;
+    if (!c->prog.open) { c->err = "no progressive accumulation (ft_progressive_begin)"; return FT_ERR_STATE; }
+    int64_t lo = std::numeric_limits<int64_t>::max(), hi = 0, blocks = 0, retired = 0;
+    const int32_t rc = progressive_read(c, false, [&](const ft_context::Progressive& P, const std::vector<uint32_t>&, const std::vector<double>&,
+                                                      const std::vector<double>&, const std::vector<uint32_t>& blk) {
+        for (uint32_t w : blk) { const int64_t cnt = w & ~ftk::kRetired; lo = std::min(lo, cnt); hi = std::max(hi, cnt); retired += (w & ftk::kRetired) ? 1 : 0; }
+        blocks += P.n_blocks;
+    });
+    if (rc != FT_OK) return rc;
+    out[0] = c->prog.passes; out[1] = blocks ? lo : 0; out[2] = hi; out[3] = blocks; out[4] = retired; out[5] = c->prog.traced;
+    return FT_OK;
+}
+
+int32_t ft_progressive_end(ft_context* c) {
+    if (!c) return FT_ERR_INVALID;
+    if (!need_device(c)) return FT_ERR_NO_DEVICE;
+    progressive_close(c);
+    return FT_OK;
 }
 
 int32_t ft_get_kernel_times(ft_context* c, double ms[5], int32_t launches[5]) {

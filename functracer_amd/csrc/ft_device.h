@@ -142,8 +142,12 @@ int occupancy_blocks_bounce(size_t lds_bytes, int variant);
 // top-level item (bare meshes also against their coarse boxes).  Blocks nothing can be hit from get block_pos = -1 (k_resolve writes
 // their pixels as Colour.Zero; none of their rays is ever generated); the others are appended, in block order, to the frame's active
 // pixel list (pos_block: the block of the pixel list behind each block of the active list), whose length lands in fc->counts.  `epoch` tags this frame's entries of wave_counts.
+// Progressive passes (ft_progressive_pass) also hand over their blocks' words (ProgressiveArgs::blk_in): a retired block is neither listed nor
+// finished but gets block_pos = kBlockRetired; with `mask_only` the cone and box tests are skipped and every block that has not retired is listed.
 struct ClassifyOut { int32_t* block_pos; uint32_t* pos_block; uint32_t* wave_counts; };
-void launch_classify(const Launch& L, const DevScene& S, const Primary& gen_list, const ClassifyOut& out, double jitter_extent, uint32_t epoch, FrameCounters* fc);
+constexpr int32_t kBlockRetired = -2;
+void launch_classify(const Launch& L, const DevScene& S, const Primary& gen_list, const ClassifyOut& out, double jitter_extent, uint32_t epoch, FrameCounters* fc,
+                     const uint32_t* retired = nullptr, bool mask_only = false);
 // The frame's pixels: mean over the spp samples of each pixel of the chunk's window, in sample order (Image.fs:112-116), written as
 // FP64 RGB (out_rgb) and / or as Image.write's RGBA8 bytes (out_rgba, Image.fs:36); with `zero_culled` also Colour.Zero for every
 // pixel of the blocks k_classify finished.  Pixel p of the list goes to out index pixel_ids[p] (whole frame) or p (tiles, packed).
@@ -159,6 +163,21 @@ struct ResolveArgs {
 };
 void launch_resolve(const Launch& L, const ResolveArgs& a);   // L.grid: at most this many workgroups (occupancy_blocks_resolve() per CU: one resident round)
 int occupancy_blocks_resolve();
+// The running state of a progressive accumulation, by POSITION in the frame's pixel list (fixed for the accumulation): per pixel the sums of
+// its samples so far (3 planes of n_list doubles) and, adaptive only, of their squares; per 64-entry block of the list one word: samples so
+// far (bits 0-30) and kRetired.  A pass reads the `in` side and writes every entry of the `out` side (the host swaps them after a pass
+// that did not overflow).
+struct ProgressiveArgs {
+    const double* sum_in; double* sum_out;
+    const double* sq_in; double* sq_out;       // null: plain accumulation, nothing retires
+    const uint32_t* blk_in; uint32_t* blk_out;
+    uint32_t n_list, min_samples;
+    double tolerance;                          // a block retires when its largest standard error of the mean is <= this
+};
+constexpr uint32_t kRetired = 0x80000000u;
+// k_resolve of a progressive pass: each pixel's sum goes on from its running sum (same additions in the same order as one k_resolve
+// over the concatenated pattern), mean = S / n out, S / Q / n back, retirement per block; finished blocks add spp zero samples.
+void launch_resolve_progressive(const Launch& L, const ResolveArgs& a, const ProgressiveArgs& pa);
 void launch_report(const Launch& L, FrameCounters* fc, FrameReport* report);   // the same hand-over as a launch of its own (frames that end in another kernel)
 // CornerSampling.blendPixels (Image.fs:134-144) for a w x h rect whose (w+1) x (h+1) corner colours are in acc (one sample each).
 void launch_resolve_corner(const Launch& L, const double* acc, uint32_t acc_stride, uint32_t w, uint32_t h, const uint32_t* out_index, double* out_rgb, uint8_t* out_rgba);

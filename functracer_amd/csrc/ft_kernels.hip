@@ -9,6 +9,7 @@
 //               wavefront buffer in HBM, the ones that terminate are dropped by wave-ballot / prefix-sum compaction when the next
 //               level is spawned, so every lane of a level is live
 //   k_resolve   per-pixel mean (Image.fs:112-116), Colour.Zero for the blocks k_classify finished, FP64 and / or RGBA8 (Image.fs:36)
+//   k_resolve_progressive  the same for a progressive pass: sums go on from the running sums of earlier passes; blocks retire (ft_progressive_*)
 // All tracing kernels are persistent grids whose waves pull 64-ray batches from 64 interleaved cursors.
 //
 // Execution model notes (wave64, CDNA4):
@@ -2010,12 +2011,15 @@ __global__ __launch_bounds__(kBlock, FANCY ? 2 : (!SOFT && !MESH ? FT_BOUNCE_LEA
 // pixel id is copied: a wave copying the ids of 64 kept blocks one after the other took 35 us) without a second kernel: workgroups take their 256-block segment in
 // ticket order, publish how many blocks they keep, and add up the counts of the tickets before theirs (all of them already running, so
 // the wait is bounded by the slowest classification; it is also bounded by a poll limit that fails the frame rather than hang).
-// The host only runs this for pinhole cameras, pixel lists made of 8x8 tiles and scenes made of bounded items.
+// The host only runs this for pinhole cameras, pixel lists made of 8x8 tiles and scenes made of bounded items - except for adaptive
+// progressive passes, which run it on any 8x8-tiled list, in mask-only mode where the host would not classify (ClassifyArgs::mask_only).
 struct ClassifyArgs {
     DevScene S; Primary gen;                                        // gen.pixel_ids / n_pix: the frame's full pixel list (8x8 tiles)
     ClassifyOut out; FrameCounters* fc;
     double jitter_extent;                                           // max(1, largest |offset| of the caller's jitter pattern), in pixels
     uint32_t epoch;                                                 // tags this frame's entries of out.wave_counts (never cleared)
+    const uint32_t* retired;                                        // progressive passes: the blocks' words (kRetired); null otherwise
+    uint32_t mask_only;                                             // 1: no cone / box tests, every block that has not retired is listed
 };
 constexpr uint32_t kClassifyPollLimit = 1u << 22;
 
@@ -2083,7 +2087,7 @@ __global__ __launch_bounds__(kClassifyBlock) void k_classify(ClassifyArgs) {
     const float cox = (float)g->cam.o[0], coy = (float)g->cam.o[1], coz = (float)g->cam.o[2];
     const float origin_mag = fabsf(cox) + fabsf(coy) + fabsf(coz);
     const Cone B{ax, ay, az, cox, coy, coz, cos_t, sqrtf(fmaxf(0.0f, 1.0f - cos_t * cos_t)) + 1e-5f, 1e-5f * (1.0f + origin_mag), par_rows, __builtin_inff()};
-    bool keep = !bounded;
+    bool keep = !bounded || K->mask_only != 0u;                     // (mask-only: the item loop below ends at once)
     for (int item = 0; item < S.n_items; ++item) {                  // wave-uniform: the item record comes through scalar loads
         if (!__any(!keep)) break;
         const FT_CONST float* I = to_const_as(S.cull_items) + 8u * (uint32_t)item;
@@ -2158,7 +2162,8 @@ __global__ __launch_bounds__(kClassifyBlock) void k_classify(ClassifyArgs) {
         }
         keep = keep || reach;
     }
-    keep = keep && valid;
+    const bool gone = K->retired && (K->retired[lb] & kRetired) != 0u;   // a progressive render's retired block: no rays, no Colour.Zero
+    keep = keep && valid && !gone;
     FT_STAMP(3);
     // ---- compaction in block order
     const FT_CONST ClassifyOut& out = K->out;
@@ -2200,7 +2205,7 @@ __global__ __launch_bounds__(kClassifyBlock) void k_classify(ClassifyArgs) {
     FT_STAMP(4);
     const uint32_t before = sh_before + before_wave;                // kept blocks before this wave's first
     const uint32_t pos = before + lanes_below(km);
-    if (valid) out.block_pos[blk] = keep ? (int32_t)pos : -1;
+    if (valid) out.block_pos[blk] = keep ? (int32_t)pos : (gone ? kBlockRetired : -1);
     if (keep) out.pos_block[pos] = blk;                             // the active list as a block map: pixel ids stay where they are
     if (threadIdx.x == 0 && (ticket + 1u) * kClassifyBlock >= n_blocks && ticket * kClassifyBlock < n_blocks)
         K->fc->counts.n_pix = 64u * (sh_before + n_keep_wg);        // the last segment publishes the length of the list
@@ -2283,15 +2288,17 @@ __global__ __launch_bounds__(kBlock) void k_report(FrameCounters* fc, FrameRepor
 // colour planes whole (3 G coalesced loads in flight per lane), passes them through LDS plane by plane, and every lane then sums its own
 // pixel's samples in sample order: each colour is fetched once, in full lines (reading them pixel by pixel touches four times as many
 // lines per instruction).  The tile is the wave's own: the LDS keeps one wave's accesses in order, so a compiler barrier is all that
-// stands between the stores and the loads of other lanes' words.
-template <int GL, class Emit>
-FT_DEV void resolve_grouped(const ResolveArgs& a, uint32_t n_pix, double* T, Emit&& emit) {
+// stands between the stores and the loads of other lanes' words.  start(q, sum, sq) gives a pixel's sums before its first sample (Zero, or a
+// progressive pass's running sums); SQ also sums the squares (adaptive progressive passes).
+template <int GL, bool SQ, class Start, class Emit>
+FT_DEV void resolve_grouped(const ResolveArgs& a, uint32_t n_pix, double* T, Start&& start, Emit&& emit) {
     constexpr uint32_t G = 1u << GL, pw = 6u - GL, ppw = 1u << pw, row = 64u + ppw;   // rows padded so that the 64 / G-lane groups fall on different banks
     const uint32_t nb = n_pix >> 6, wave = threadIdx.x >> 6, lane = threadIdx.x & 63u, waves_total = gridDim.x * (kBlock / 64);
     const uint32_t mine = (lane >> pw) * row + (lane & (ppw - 1u));
     auto wave_sync = [] { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); };
     for (uint32_t blk = blockIdx.x * (kBlock / 64) + wave; blk < nb; blk += waves_total) {
-        double sum[3] = {0.0, 0.0, 0.0};
+        double sum[3], sq[3];
+        start((blk << 6) + lane, sum, sq);
         for (uint32_t s0 = 0; s0 < (uint32_t)a.spp; s0 += G) {
             double v[3][G];
 #pragma unroll
@@ -2304,11 +2311,11 @@ FT_DEV void resolve_grouped(const ResolveArgs& a, uint32_t n_pix, double* T, Emi
                 for (uint32_t k = 0; k < G; ++k) T[k * row + lane] = v[p][k];
                 wave_sync();
 #pragma unroll
-                for (uint32_t ds = 0; ds < G; ++ds) sum[p] += T[mine + (ds << pw)];
+                for (uint32_t ds = 0; ds < G; ++ds) { const double x = T[mine + (ds << pw)]; sum[p] += x; if (SQ) sq[p] += x * x; }
                 wave_sync();
             }
         }
-        emit((blk << 6) + lane, sum[0], sum[1], sum[2]);
+        emit((blk << 6) + lane, sum, sq);
     }
 }
 
@@ -2318,27 +2325,28 @@ __global__ __launch_bounds__(kBlock) void k_resolve(ResolveArgs a) {
     if (a.counts) { const uint32_t n_active = a.counts->n_pix; n_pix = n_active > a.first ? (n_active - a.first < a.n_pix_host ? n_active - a.first : a.n_pix_host) : 0u; }
     const double spp = (double)a.spp;
     const uint32_t group_log2 = (n_pix & 63u) ? 0u : a.group_log2;    // as pix_count decides it
-    auto emit = [&](uint32_t q, double r, double g, double b) {
+    auto emit = [&](uint32_t q, const double (&s)[3], const double (&)[3]) {
         const uint32_t al = a.first + q;                            // position in the active list -> position in the original pixel list
         const uint32_t p = a.pos_block ? a.pos_block[al >> 6] * 64u + (al & 63u) : al;
-        write_pixel(a.out_rgb, a.out_rgba, a.pixel_ids ? (size_t)a.pixel_ids[p] : (size_t)p, r / spp, g / spp, b / spp);
+        write_pixel(a.out_rgb, a.out_rgba, a.pixel_ids ? (size_t)a.pixel_ids[p] : (size_t)p, s[0] / spp, s[1] / spp, s[2] / spp);
     };
+    auto from_zero = [](uint32_t, double (&s)[3], double (&)[3]) { s[0] = s[1] = s[2] = 0.0; };
     if (group_log2 == 0u) {
         for (uint32_t q = blockIdx.x * kBlock + threadIdx.x; q < n_pix; q += gridDim.x * kBlock) {
-            double r = 0.0, g = 0.0, b = 0.0;
-            for (int s = 0; s < a.spp; ++s) {
-                const size_t i = (size_t)s * n_pix + q;
-                r += a.acc[i]; g += a.acc[(size_t)a.acc_stride + i]; b += a.acc[2 * (size_t)a.acc_stride + i];
+            double s[3] = {0.0, 0.0, 0.0}, none[3];
+            for (int k = 0; k < a.spp; ++k) {
+                const size_t i = (size_t)k * n_pix + q;
+                s[0] += a.acc[i]; s[1] += a.acc[(size_t)a.acc_stride + i]; s[2] += a.acc[2 * (size_t)a.acc_stride + i];
             }
-            emit(q, r, g, b);
+            emit(q, s, none);
         }
     } else {
         double* T = tile + (threadIdx.x >> 6) * (8 * 136);
         switch (group_log2) {
-            case 1: resolve_grouped<1>(a, n_pix, T, emit); break;
-            case 2: resolve_grouped<2>(a, n_pix, T, emit); break;
-            case 3: resolve_grouped<3>(a, n_pix, T, emit); break;
-            default: resolve_grouped<4>(a, n_pix, T, emit); break;
+            case 1: resolve_grouped<1, false>(a, n_pix, T, from_zero, emit); break;
+            case 2: resolve_grouped<2, false>(a, n_pix, T, from_zero, emit); break;
+            case 3: resolve_grouped<3, false>(a, n_pix, T, from_zero, emit); break;
+            default: resolve_grouped<4, false>(a, n_pix, T, from_zero, emit); break;
         }
     }
     __syncthreads();                                                // the tile serves the hand-over next
@@ -2348,6 +2356,82 @@ __global__ __launch_bounds__(kBlock) void k_resolve(ResolveArgs a) {
             if (a.block_pos[blk] >= 0) continue;
             const uint32_t p = blk * 64u + lane;
             write_pixel(a.out_rgb, a.out_rgba, a.pixel_ids ? (size_t)a.pixel_ids[p] : (size_t)p, 0.0, 0.0, 0.0);
+        }
+    }
+    if (a.report) hand_over_frame(a.fc, a.report, reinterpret_cast<unsigned long long*>(tile));
+}
+
+// Pixel p of a progressive accumulation's list after a pass: its sums back into the `out` side, its mean S / n into the frame, and - by the
+// lane of the block's first pixel - its block's word.  An adaptive pass retires a block that has at least min_samples samples and whose
+// largest standard error of the mean over its 64 pixels and 3 channels, sqrt(max(0, Q/n - (S/n)^2) * n / (n - 1) / n), is within the
+// tolerance; a NaN never is.  The wave holds exactly the block (all 64 lanes active), so the ballot is the block's reduction.
+FT_DEV void progressive_out(const ResolveArgs& a, const ProgressiveArgs& pa, uint32_t p, const double (&s)[3], const double (&sq)[3], uint32_t word) {
+    const size_t L = pa.n_list;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { pa.sum_out[(size_t)c * L + p] = s[c]; if (pa.sq_out) pa.sq_out[(size_t)c * L + p] = sq[c]; }
+    const double dn = (double)(word & ~kRetired);
+    write_pixel(a.out_rgb, a.out_rgba, a.pixel_ids ? (size_t)a.pixel_ids[p] : (size_t)p, s[0] / dn, s[1] / dn, s[2] / dn);
+    if (pa.sq_out && !(word & kRetired)) {                          // block-uniform
+        bool within = (word & ~kRetired) >= pa.min_samples;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const double m = s[c] / dn, v0 = sq[c] / dn - m * m, v = (v0 < 0.0 ? 0.0 : v0) * dn / (dn - 1.0);
+            within = within && sqrt(v / dn) <= pa.tolerance;
+        }
+        if (__ballot(!within) == 0ull) word |= kRetired;
+    }
+    if ((p & 63u) == 0u) pa.blk_out[p >> 6] = word;
+}
+
+// k_resolve of a progressive pass: as k_resolve, but every pixel's sum (and sum of squares) starts from its running sum instead of Zero,
+// and the pixels leave as S / n with n the samples of all passes so far.  With block_pos the launch also hands over the blocks the pass
+// did not trace: a finished block (k_classify: nothing in reach) gains spp zero samples - S unchanged, n + spp, exactly what tracing them
+// gives - and a retired block is copied through.  The sums are indexed by position in the frame's pixel list, so a wave reads one
+// contiguous 512-byte run per plane.
+template <bool SQ>
+__global__ __launch_bounds__(kBlock) void k_resolve_progressive(ResolveArgs a, ProgressiveArgs pa) {
+    __shared__ double tile[(kBlock / 64) * 8 * 136];
+    uint32_t n_pix = a.n_pix_host;
+    if (a.counts) { const uint32_t n_active = a.counts->n_pix; n_pix = n_active > a.first ? (n_active - a.first < a.n_pix_host ? n_active - a.first : a.n_pix_host) : 0u; }
+    const uint32_t group_log2 = (n_pix & 63u) ? 0u : a.group_log2;
+    const size_t L = pa.n_list;
+    auto at = [&](uint32_t q) { const uint32_t al = a.first + q; return a.pos_block ? a.pos_block[al >> 6] * 64u + (al & 63u) : al; };
+    auto load = [&](uint32_t p, double (&s)[3], double (&sq)[3]) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { s[c] = pa.sum_in[(size_t)c * L + p]; sq[c] = SQ ? pa.sq_in[(size_t)c * L + p] : 0.0; }
+    };
+    auto start = [&](uint32_t q, double (&s)[3], double (&sq)[3]) { load(at(q), s, sq); };
+    auto emit = [&](uint32_t q, const double (&s)[3], const double (&sq)[3]) { const uint32_t p = at(q); progressive_out(a, pa, p, s, sq, pa.blk_in[p >> 6] + (uint32_t)a.spp); };
+    if (group_log2 == 0u) {
+        for (uint32_t q = blockIdx.x * kBlock + threadIdx.x; q < n_pix; q += gridDim.x * kBlock) {
+            double s[3], sq[3];
+            start(q, s, sq);
+            for (int k = 0; k < a.spp; ++k) {
+                const size_t i = (size_t)k * n_pix + q;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) { const double x = a.acc[(size_t)c * a.acc_stride + i]; s[c] += x; if (SQ) sq[c] += x * x; }
+            }
+            emit(q, s, sq);
+        }
+    } else {
+        double* T = tile + (threadIdx.x >> 6) * (8 * 136);
+        switch (group_log2) {
+            case 1: resolve_grouped<1, SQ>(a, n_pix, T, start, emit); break;
+            case 2: resolve_grouped<2, SQ>(a, n_pix, T, start, emit); break;
+            case 3: resolve_grouped<3, SQ>(a, n_pix, T, start, emit); break;
+            default: resolve_grouped<4, SQ>(a, n_pix, T, start, emit); break;
+        }
+    }
+    __syncthreads();                                                // the tile serves the hand-over next
+    if (a.block_pos) {                                              // one wave per block the pass did not trace
+        const uint32_t lane = threadIdx.x & 63u;
+        for (uint32_t blk = blockIdx.x * (kBlock / 64) + threadIdx.x / 64; blk < a.n_blocks_total; blk += gridDim.x * (kBlock / 64)) {
+            const int32_t bp = a.block_pos[blk];
+            if (bp >= 0) continue;
+            const uint32_t p = blk * 64u + lane, word = pa.blk_in[blk];
+            double s[3], sq[3];
+            load(p, s, sq);
+            progressive_out(a, pa, p, s, sq, bp == kBlockRetired ? word : word + (uint32_t)a.spp);
         }
     }
     if (a.report) hand_over_frame(a.fc, a.report, reinterpret_cast<unsigned long long*>(tile));
@@ -2448,8 +2532,9 @@ void launch_primary(const Launch& L, const DevScene& S, const Primary& gen, RayB
     const PrimaryArgs a{S, gen, next, acc, fc, acc_stride, max_depth};
     hipLaunchKernelGGL(primary_variant(L.variant), dim3(L.grid), dim3(kBlock), L.lds_bytes, L.stream, a);
 }
-void launch_classify(const Launch& L, const DevScene& S, const Primary& gen_list, const ClassifyOut& out, double jitter_extent, uint32_t epoch, FrameCounters* fc) {
-    const ClassifyArgs a{S, gen_list, out, fc, jitter_extent, epoch};
+void launch_classify(const Launch& L, const DevScene& S, const Primary& gen_list, const ClassifyOut& out, double jitter_extent, uint32_t epoch, FrameCounters* fc,
+                     const uint32_t* retired, bool mask_only) {
+    const ClassifyArgs a{S, gen_list, out, fc, jitter_extent, epoch, retired, mask_only ? 1u : 0u};
     const uint32_t n_blocks = gen_list.n_pix / 64u;
     hipLaunchKernelGGL(k_classify, dim3((n_blocks + kClassifyBlock - 1u) / kClassifyBlock), dim3(kClassifyBlock), 0, L.stream, a);
 }
@@ -2462,6 +2547,11 @@ void launch_resolve(const Launch& L, const ResolveArgs& a) {
     // L.grid: one resident round of workgroups (occupancy_blocks_resolve x CUs; the grouped path holds 3 x 16 colours per lane: fewer waves fit
     // than the tracing kernels' grids assume), so that the hand-over at the end waits for one generation of workgroups, not for several
     hipLaunchKernelGGL(k_resolve, dim3(blocks_for(work, L.grid)), dim3(kBlock), 0, L.stream, a);
+}
+void launch_resolve_progressive(const Launch& L, const ResolveArgs& a, const ProgressiveArgs& pa) {
+    const uint32_t work = a.block_pos ? (a.n_blocks_total * 64u > a.n_pix_host ? a.n_blocks_total * 64u : a.n_pix_host) : a.n_pix_host;
+    if (pa.sq_in) hipLaunchKernelGGL(k_resolve_progressive<true>, dim3(blocks_for(work, L.grid)), dim3(kBlock), 0, L.stream, a, pa);
+    else hipLaunchKernelGGL(k_resolve_progressive<false>, dim3(blocks_for(work, L.grid)), dim3(kBlock), 0, L.stream, a, pa);
 }
 #ifdef FT_ITEM_COUNTS
 extern "C" int ft_debug_item_counts(unsigned long long out[48], int reset) {      // [0..15] item counters, [16..47] section clocks, summed over the waves' slots

@@ -246,6 +246,46 @@ int32_t ft_render_enqueue_rgba8(ft_context* ctx, const ft_camera* cam, int32_t r
                                 int32_t max_depth, uint64_t seed, const ft_rect* tiles, int32_t n_tiles);
 int32_t ft_render_wait(ft_context* ctx, ft_stats* stats);
 
+/* ---- progressive accumulation ------------------------------------------------------------- */
+/* A frame refined pass by pass without tracing any sample twice: each pass adds samples to the running per-pixel sums of one fixed
+ * request, and pixels whose 8x8 block has settled stop receiving samples.
+ *  - Exactness: pixel p holds S, the sum of its samples per channel in the order they were traced (pass order, then sample order within a
+ *    pass); a pass's resolve continues that sum from S, and the mean is S / n.  A frame built from passes over pieces of a jitter pattern is
+ *    therefore bit-identical to one ft_render over the whole pattern (Image.fs:112-116: Array.average is a sequential sum, then one
+ *    division).  A block that k_classify finishes in a pass adds spp zero samples: S unchanged, n += spp, what tracing them gives.
+ *  - Seeded streams: soft-light and depth-of-field streams of a pass are keyed as in an ft_render of that pass (sample = pixel_id * spp + s,
+ *    with the pass's spp and seed): a pass's samples are those of ft_render(cam, spp, jitter_xy, seed).  Give each pass its own seed.
+ *  - Retirement (tolerance > 0): after each pass, per pixel and channel var = max(0, Q/n - (S/n)^2) * n / (n - 1) and se = sqrt(var / n),
+ *    with Q the running sum of squares.  A 64-pixel block (an 8x8 tile of the list) retires when n >= min_samples and the largest se of
+ *    its 64 pixels and 3 channels is <= tolerance.  Retirement is final: a retired block is never traced again and its S, Q, n stay.
+ *  - Lifetime: one accumulation per context; a caller's ft_scene_commit or ft_scene_clear ends it (the next pass returns FT_ERR_STATE, as a
+ *    pass without a begin does).  The re-commit by which a blocking call grows the CSG hit lists does not: the pass that overflowed leaves no
+ *    trace and runs again.  ft_render calls between passes are allowed and change nothing accumulated.  A pass retires queued frames first,
+ *    overwrites the frame buffer (ft_fetch_frame / ft_fetch_frame_rgba8 return the means) and forgets which blocks the last ft_render
+ *    left as Colour.Zero.
+ *  - Multi-device contexts: each device accumulates, retires and copies out the 8-row bands ft_render gives it; fetch and status combine them.
+ *  - Host-only contexts: FT_ERR_NO_DEVICE from every ft_progressive_* call.
+ * Device memory: 48 bytes per tile pixel (S, two copies), 96 with tolerance > 0 (Q too), and 8 bytes per 64-pixel block. */
+/* Start a progressive accumulation (a second begin replaces the first).  Fixes the camera, frame size, recursion limit and tiles (as
+ * ft_render's) for every later pass.  tolerance <= 0: plain accumulation, nothing retires.  tolerance > 0: adaptive; min_samples >= 2 is
+ * required (else FT_ERR_INVALID) and every clipped tile must have sides that are multiples of 8 (else FT_ERR_UNSUPPORTED). */
+int32_t ft_progressive_begin(ft_context* ctx, const ft_camera* cam, int32_t res_h, int32_t res_v, int32_t max_depth,
+                             const ft_rect* tiles, int32_t n_tiles, double tolerance, int32_t min_samples);
+/* One blocking pass: spp >= 1 new samples (jitter_xy = spp x 2, seed as ft_render's) for every block not yet retired; spp == 0 (corner
+ * sampling, whose blend is not a per-pixel average) is FT_ERR_UNSUPPORTED.  Writes the running mean of every tile pixel (retired blocks
+ * included) into out, laid out as ft_render's out_rgb, or as ft_render_rgba8's bytes if rgba8 != 0.  out may be NULL: the mean then stays
+ * in the frame buffer for ft_fetch_frame / ft_fetch_frame_rgba8.  stats: as ft_render's, for this pass. */
+int32_t ft_progressive_pass(ft_context* ctx, int32_t spp, const double* jitter_xy, uint64_t seed, int32_t rgba8, void* out, ft_stats* stats);
+/* The accumulated state of the tile pixels; any pointer may be NULL: mean (res_v x res_h x 3; 0 before the first pass), standard error of
+ * the mean per channel (same shape; 0 where fewer than 2 samples; adaptive accumulations only, else FT_ERR_STATE), samples per pixel
+ * (res_v x res_h). */
+int32_t ft_progressive_fetch(ft_context* ctx, double* mean_rgb, double* stderr_rgb, uint32_t* samples);
+/* out = passes, min and max samples per pixel, 64-pixel blocks in the accumulation, blocks retired, samples traced in the last pass
+ * (the listed samples of the blocks its active list held). */
+int32_t ft_progressive_status(ft_context* ctx, int64_t out[6]);
+/* End the accumulation and free its buffers (FT_OK when there is none). */
+int32_t ft_progressive_end(ft_context* ctx);
+
 /* Closest hit of single rays through the device path (Scene.intersectScene, Scene.fs:118, after
  * Shading.slightOffset is NOT applied): for tests.  Outputs per ray: t, p[3], n[3], material index
  * resolved colour[3]; hit[i] = 0 when the ray misses. */
