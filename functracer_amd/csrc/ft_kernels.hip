@@ -149,9 +149,6 @@ FT_DEV uint32_t lane_id() { return __lane_id(); }
 // pair: held across the batch loop in VGPRs such values - reciprocals of the launch's counts, the number of lights as a double -
 // were what the register allocator spilled to scratch first.
 FT_DEV double uniform_f64(double v) {
-#ifdef FT_AB_NO_UNIFORM
-    return v;
-#endif
     const unsigned long long b = (unsigned long long)__double_as_longlong(v);
     const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)b), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(b >> 32));
     return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
@@ -333,6 +330,45 @@ FT_DEV bool aabb_hit(cdp nd, const Ray& r, double ivx, double ivy, double ivz, d
     return (tmin < __builtin_inf()) && (tmax > -__builtin_inf());
 }
 
+// The node stack of a per-lane walk: this lane's entry i at stack[i * kBlock] in LDS (consecutive lanes, consecutive banks).
+struct LaneStack {
+    int32_t* stack; int sp;
+    FT_DEV void push(int child) { stack[sp * kBlock] = child; ++sp; }
+    FT_DEV int pop() { if (sp > 0) { --sp; return stack[sp * kBlock]; } return kDone; }
+};
+
+// The node stack of a wave-uniform walk: entry i in lane i of one VGPR, popped with v_readlane.
+struct WaveStack {
+    int lanes = 0, sp = 0;
+    // a push is one v_writelane at the top slot (free when nothing is entered: the write is then simply not kept) and a scalar add;
+    // the lane select goes through m0 (one scalar operand per vector instruction), which the compiler reserves and nothing else here uses
+    // (naming it as clobbered keeps the operands out of it; the compiler remarks that the register is reserved)
+    FT_DEV void push(int child, unsigned long long mask) {
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"
+        asm("s_mov_b32 m0, %1\n\tv_writelane_b32 %0, %2, m0\n\ts_cmp_lg_u64 %3, 0\n\ts_addc_u32 %1, %1, 0" : "+v"(lanes), "+s"(sp) : "s"(child), "s"(mask) : "m0", "scc");
+#pragma clang diagnostic pop
+    }
+    FT_DEV bool pop(int& cur) {
+        if (sp == 0) return false;
+        --sp;
+        cur = __builtin_amdgcn_readlane(lanes, sp);
+        return true;
+    }
+};
+
+// An any-hit leaf of a wave-uniform walk: triangles first .. first + count - 1 of `tris` in list order, wave-uniform (scalar loads).
+// A lane with a hit nearer than `bound` is blocked and leaves `alive`; the caller then takes that lane's own bound out of play.
+template <bool ANY>
+FT_DEV void any_hit_leaf(cdp tris, uint32_t first, uint32_t count, const Ray& r, double bound, Query<ANY>& q, bool& alive) {
+    for (uint32_t k = 0; k < count; ++k) {
+        double t = 0.0;
+        const bool h = tri_hit_wave(tris + 9ull * (first + k), r, alive, t);
+        const bool b = h & (t < bound);
+        q.blocked = q.blocked | b; alive = alive & !b;
+    }
+}
+
 template <class Emit>
 FT_DEV void mesh_hits(const Scene& S, uint32_t mesh_idx, const Ray& r, bool active, int32_t* stack, Emit&& emit) {
     const int32_t root = S.meshes[4 * mesh_idx];
@@ -349,14 +385,13 @@ FT_DEV void mesh_hits(const Scene& S, uint32_t mesh_idx, const Ray& r, bool acti
     // RIGHT child come before those of the LEFT child.  Per-lane DFS with the pending left children on an
     // LDS stack.
     const double ivx = 1.0 / r.dx, ivy = 1.0 / r.dy, ivz = 1.0 / r.dz;
-    int sp = 0;
+    LaneStack st{stack, 0};
     int cur = active ? root : kDone;
     while (__any(cur != kDone)) {
         while (cur >= 0) {                                         // descend through branches
             cdp nd = S.nodes + 8ull * (uint32_t)cur;
-            if (aabb_hit(nd, r, ivx, ivy, ivz)) { cip ch = reinterpret_cast<cip>(nd + 6); stack[sp * kBlock] = ch[0]; ++sp; cur = ch[1]; }
-            else if (sp > 0) { --sp; cur = stack[sp * kBlock]; }
-            else cur = kDone;
+            if (aabb_hit(nd, r, ivx, ivy, ivz)) { cip ch = reinterpret_cast<cip>(nd + 6); st.push(ch[0]); cur = ch[1]; }
+            else cur = st.pop();
         }
         if (cur != kDone) {                                        // a leaf: every triangle, in list order
             const uint32_t first = S.bsp_leaves[2 * (~cur)], count = S.bsp_leaves[2 * (~cur) + 1];
@@ -364,7 +399,7 @@ FT_DEV void mesh_hits(const Scene& S, uint32_t mesh_idx, const Ray& r, bool acti
                 double t;
                 if (tri_hit(S.tris + 9ull * (first + k), r, t)) emit(t, 0u, first + k);
             }
-            if (sp > 0) { --sp; cur = stack[sp * kBlock]; } else cur = kDone;
+            cur = st.pop();
         }
     }
 }
@@ -497,7 +532,7 @@ FT_DEV void mesh_bvh_query(const Scene& S, int32_t bvh_root, const Ray& r, Query
     double bound = ANY ? q.max_dist : q.best_t;                    // a hit at t >= bound cannot change the query's result
     uint32_t best_tri = 0xFFFFFFFFu;
     bool found = false;
-    int sp = 0;
+    LaneStack st{stack, 0};
     int cur = (q.active && !(ANY && q.blocked)) ? bvh_root : kDone;
     while (__any(cur != kDone)) {
         while (cur >= 0) {
@@ -513,22 +548,21 @@ FT_DEV void mesh_bvh_query(const Scene& S, int32_t bvh_root, const Ray& r, Query
                 const uint32_t axis = reinterpret_cast<cup>(nd + 7)[0];
                 const double da = axis == 0 ? r.dx : axis == 1 ? r.dy : r.dz;
                 const int near = da >= 0.0 ? ch[0] : ch[1], far = da >= 0.0 ? ch[1] : ch[0];
-                stack[sp * kBlock] = far; ++sp; cur = near;        // near child first: the bound shrinks sooner
-            } else if (sp > 0) { --sp; cur = stack[sp * kBlock]; }
-            else cur = kDone;
+                st.push(far); cur = near;                          // near child first: the bound shrinks sooner
+            } else cur = st.pop();
         }
         if (cur != kDone) {
             const uint32_t first = S.bsp_leaves[2 * (~cur)], count = S.bsp_leaves[2 * (~cur) + 1];
             for (uint32_t k = 0; k < count; ++k) {
                 double t;
                 if (!tri_hit(S.tris + 9ull * (first + k), r, t)) continue;
-                if (ANY) { if (t < bound) { q.blocked = true; sp = 0; break; } }
+                if (ANY) { if (t < bound) { q.blocked = true; st.sp = 0; break; } }
                 else {
                     const uint32_t orig = S.tri_orig[first + k];
                     if (t < bound || (found && t == bound && orig < best_tri)) { bound = t; best_tri = orig; found = true; }
                 }
             }
-            if (sp > 0) { --sp; cur = stack[sp * kBlock]; } else cur = kDone;
+            cur = st.pop();
         }
     }
     if (!ANY && found) q.hit(bound, leaf, best_tri, lit);
@@ -539,66 +573,76 @@ FT_DEV void mesh_bvh_query(const Scene& S, int32_t bvh_root, const Ray& r, Query
 // stable sort; a node is entered iff the reference's own box test passes AND the box can still hold a usable
 // hit (its entry distance is not beyond the current bound, with a margin far above the rounding of either side, and it does not
 // lie wholly behind the ray's origin: a triangle hit needs t > 1e-7, Triangle.fs:62, and the sign of a computed distance is exact).
-// PACKET = the wave walks the tree together (uniform stack in the lanes of a VGPR, scalar loads).
-template <bool ANY, bool PACKET>
+// Each lane walks on its own, with its pending left children on an LDS stack.
+template <bool ANY>
 FT_DEV void mesh_bsp_query(const Scene& S, int32_t root, const Ray& r, Query<ANY>& q, uint32_t leaf, bool lit, int32_t* stack) {
+    const bool alive = q.active && !(ANY && q.blocked);
+    if (!__any(alive)) return;
+    const double ivx = 1.0 / r.dx, ivy = 1.0 / r.dy, ivz = 1.0 / r.dz;
+    double bound = ANY ? q.max_dist : q.best_t;
+    uint32_t best_tri = 0u;
+    bool found = false;
+    LaneStack st{stack, 0};
+    int cur = alive ? root : kDone;
+    while (__any(cur != kDone)) {
+        while (cur >= 0) {
+            cdp nd = S.nodes + 8ull * (uint32_t)cur;
+            double entry = 0.0, exit = 0.0;
+            if (aabb_hit(nd, r, ivx, ivy, ivz, &entry, &exit) && !(entry > bound * (1.0 + 1e-12) + 1e-12) && !(exit < 0.0)) {
+                cip ch = reinterpret_cast<cip>(nd + 6); st.push(ch[0]); cur = ch[1];
+            } else cur = st.pop();
+        }
+        if (cur != kDone) {
+            const uint32_t first = S.bsp_leaves[2 * (~cur)], count = S.bsp_leaves[2 * (~cur) + 1];
+            for (uint32_t k = 0; k < count; ++k) {
+                double t;
+                if (!tri_hit(S.tris + 9ull * (first + k), r, t)) continue;
+                if (ANY) { if (t < bound) { q.blocked = true; st.sp = 0; break; } }
+                else if (t < bound) { bound = t; best_tri = first + k; found = true; }
+            }
+            cur = st.pop();
+        }
+    }
+    if (!ANY && found) q.hit(bound, leaf, best_tri, lit);
+}
+
+// The same walk for a coherent wave that mesh_bsp_packet turned away: the wave walks the tree one node at a time together (a
+// WaveStack, scalar loads), entering a node if any live lane's test passes.
+template <bool ANY>
+FT_DEV void mesh_bsp_narrow(const Scene& S, int32_t root, const Ray& r, Query<ANY>& q, uint32_t leaf, bool lit) {
     bool alive = q.active && !(ANY && q.blocked);
     if (!__any(alive)) return;
     const double ivx = 1.0 / r.dx, ivy = 1.0 / r.dy, ivz = 1.0 / r.dz;
     double bound = ANY ? q.max_dist : q.best_t;
     uint32_t best_tri = 0u;
     bool found = false;
-    int sp = 0, stack_lanes = 0;
-    int cur = PACKET ? root : (alive ? root : kDone);
+    WaveStack st;
+    int cur = root;
     for (;;) {
-        if (PACKET) {
-            cur = __builtin_amdgcn_readfirstlane(cur);
-            if (cur >= 0) {
-                cdp nd = S.nodes + 8ull * (uint32_t)cur;
-                double entry = 0.0, exit = 0.0;
-                const bool enter = alive && aabb_hit(nd, r, ivx, ivy, ivz, &entry, &exit) && !(entry > bound * (1.0 + 1e-12) + 1e-12) && !(exit < 0.0);
-                if (__any(enter)) {
-                    cip ch = reinterpret_cast<cip>(nd + 6);
-                    const int left = ch[0];
-                    stack_lanes = ((int)lane_id() == sp) ? left : stack_lanes;
-                    ++sp; cur = ch[1];
-                    continue;
-                }
-            } else {
-                const uint32_t first = S.bsp_leaves[2 * (~cur)], count = S.bsp_leaves[2 * (~cur) + 1];
-                for (uint32_t k = 0; k < count; ++k) {
-                    double t;
-                    if (alive && tri_hit(S.tris + 9ull * (first + k), r, t)) {
-                        if (ANY) { if (t < bound) { q.blocked = true; alive = false; } }
-                        else if (t < bound) { bound = t; best_tri = first + k; found = true; }
-                    }
-                }
-                if (ANY) { if (!__any(alive)) break; }
+        cur = __builtin_amdgcn_readfirstlane(cur);
+        if (cur >= 0) {
+            cdp nd = S.nodes + 8ull * (uint32_t)cur;
+            double entry = 0.0, exit = 0.0;
+            const bool enter = alive && aabb_hit(nd, r, ivx, ivy, ivz, &entry, &exit) && !(entry > bound * (1.0 + 1e-12) + 1e-12) && !(exit < 0.0);
+            if (__any(enter)) {
+                cip ch = reinterpret_cast<cip>(nd + 6);
+                const int left = ch[0];
+                st.lanes = ((int)lane_id() == st.sp) ? left : st.lanes;
+                ++st.sp; cur = ch[1];
+                continue;
             }
-            if (sp == 0) break;
-            --sp;
-            cur = __builtin_amdgcn_readlane(stack_lanes, sp);
         } else {
-            if (!__any(cur != kDone)) break;
-            while (cur >= 0) {
-                cdp nd = S.nodes + 8ull * (uint32_t)cur;
-                double entry = 0.0, exit = 0.0;
-                if (aabb_hit(nd, r, ivx, ivy, ivz, &entry, &exit) && !(entry > bound * (1.0 + 1e-12) + 1e-12) && !(exit < 0.0)) {
-                    cip ch = reinterpret_cast<cip>(nd + 6); stack[sp * kBlock] = ch[0]; ++sp; cur = ch[1];
-                } else if (sp > 0) { --sp; cur = stack[sp * kBlock]; }
-                else cur = kDone;
-            }
-            if (cur != kDone) {
-                const uint32_t first = S.bsp_leaves[2 * (~cur)], count = S.bsp_leaves[2 * (~cur) + 1];
-                for (uint32_t k = 0; k < count; ++k) {
-                    double t;
-                    if (!tri_hit(S.tris + 9ull * (first + k), r, t)) continue;
-                    if (ANY) { if (t < bound) { q.blocked = true; sp = 0; break; } }
+            const uint32_t first = S.bsp_leaves[2 * (~cur)], count = S.bsp_leaves[2 * (~cur) + 1];
+            for (uint32_t k = 0; k < count; ++k) {
+                double t;
+                if (alive && tri_hit(S.tris + 9ull * (first + k), r, t)) {
+                    if (ANY) { if (t < bound) { q.blocked = true; alive = false; } }
                     else if (t < bound) { bound = t; best_tri = first + k; found = true; }
                 }
-                if (sp > 0) { --sp; cur = stack[sp * kBlock]; } else cur = kDone;
             }
+            if (ANY) { if (!__any(alive)) break; }
         }
+        if (!st.pop(cur)) break;
     }
     if (!ANY && found) q.hit(bound, leaf, best_tri, lit);
 }
@@ -614,7 +658,7 @@ FT_DEV void mesh_bsp_query(const Scene& S, int32_t root, const Ray& r, Query<ANY
 // triangles, which can only reject a leaf none of whose triangles the ray can hit.  Williams' test decides on NaN (0 * inf: a zero
 // direction component, origin on a slab plane) by falling through its comparisons; with every direction component of every live lane
 // comfortably non-zero no NaN or infinity can arise and the test is max(entries) <= min(exits), which is what runs here - a wave with
-// such a lane returns false and takes the one-node-at-a-time walk above.  Children are visited in the reference's order, so "strictly
+// such a lane returns false and takes the one-node-at-a-time walk above (mesh_bsp_narrow).  Children are visited in the reference's order, so "strictly
 // smaller t wins" still reproduces the stable sort; the pushes are static (LL, LR, RL; RR is taken directly).
 template <bool ANY>
 FT_DEV bool mesh_bsp_packet(const Scene& S, int32_t root, int32_t wide_root, const Ray& r, Query<ANY>& q, uint32_t leaf, bool lit) {
@@ -629,61 +673,60 @@ FT_DEV bool mesh_bsp_packet(const Scene& S, int32_t root, int32_t wide_root, con
     auto reach_of = [](double b) { const double m = b * (1.0 + 1e-12) + 1e-12; return m != m ? __builtin_inf() : m; };   // how far a box may begin and still matter
     double reach = alive ? reach_of(bound) : -__builtin_inf();
     // entry / exit distances of a box by the reference's arithmetic
-#define FT_SLAB(bx, tmin, tmax) \
-    double tmin, tmax; { double t0 = ((bx)[0] - ox) * ivx, t1 = ((bx)[3] - ox) * ivx; tmin = fmin(t0, t1); tmax = fmax(t0, t1); \
-      t0 = ((bx)[1] - oy) * ivy; t1 = ((bx)[4] - oy) * ivy; tmin = fmax(tmin, fmin(t0, t1)); tmax = fmin(tmax, fmax(t0, t1)); \
-      t0 = ((bx)[2] - oz) * ivz; t1 = ((bx)[5] - oz) * ivz; tmin = fmax(tmin, fmin(t0, t1)); tmax = fmin(tmax, fmax(t0, t1)); }
-#define FT_ENTERED(tmin, tmax) (__builtin_amdgcn_ballot_w64(tmax >= fmax(tmin, 0.0)) & __builtin_amdgcn_ballot_w64(tmin <= reach))
+    auto slab = [&](cdp bx, double& tmin, double& tmax) {
+        double t0 = (bx[0] - ox) * ivx, t1 = (bx[3] - ox) * ivx; tmin = fmin(t0, t1); tmax = fmax(t0, t1);
+        t0 = (bx[1] - oy) * ivy; t1 = (bx[4] - oy) * ivy; tmin = fmax(tmin, fmin(t0, t1)); tmax = fmin(tmax, fmax(t0, t1));
+        t0 = (bx[2] - oz) * ivz; t1 = (bx[5] - oz) * ivz; tmin = fmax(tmin, fmin(t0, t1)); tmax = fmin(tmax, fmax(t0, t1));
+    };
+    auto entered = [&](cdp bx) {                                   // the lanes that enter the box: one ballot per bare comparison (see mesh_bvh_packet)
+        double tmin, tmax;
+        slab(bx, tmin, tmax);
+        return __builtin_amdgcn_ballot_w64(tmax >= fmax(tmin, 0.0)) & __builtin_amdgcn_ballot_w64(tmin <= reach);
+    };
     {   // the root's own box (its parent's record would have held it)
-        cdp nd = S.nodes + 8ull * (uint32_t)root;
-        FT_SLAB(nd, tmin, tmax);
+        double tmin, tmax;
+        slab(S.nodes + 8ull * (uint32_t)root, tmin, tmax);
         const bool in = (tmax >= fmax(tmin, 0.0)) & (tmin <= reach);
         alive = alive & in; reach = in ? reach : -__builtin_inf();
         if (!__any(alive)) return true;
     }
     uint32_t best_tri = 0u;
     bool found = false;
-    int stack_lanes = 0, sp = 0, cur = wide_root;
+    WaveStack st;
+    int cur = wide_root;
     for (;;) {
         cur = __builtin_amdgcn_readfirstlane(cur);
-        sp = __builtin_amdgcn_readfirstlane(sp);
+        st.sp = __builtin_amdgcn_readfirstlane(st.sp);
         if (cur >= 0) {
             cdp nd = S.nodes + 8ull * (uint32_t)cur;
             const int32_t ch[4] = {reinterpret_cast<cip>(nd + 36)[0], reinterpret_cast<cip>(nd + 36)[1], reinterpret_cast<cip>(nd + 36)[2], reinterpret_cast<cip>(nd + 36)[3]};
             unsigned long long half[2], m[4];
 #pragma unroll
-            for (int h = 0; h < 2; ++h) { FT_SLAB(nd + 6 * h, tmin, tmax); half[h] = FT_ENTERED(tmin, tmax); }
+            for (int h = 0; h < 2; ++h) half[h] = entered(nd + 6 * h);
 #pragma unroll
-            for (int c = 0; c < 4; ++c) { FT_SLAB(nd + 12 + 6 * c, tmin, tmax); m[c] = FT_ENTERED(tmin, tmax) & half[c >> 1]; }
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-#define FT_PUSH(c) asm("s_mov_b32 m0, %1\n\tv_writelane_b32 %0, %2, m0\n\ts_cmp_lg_u64 %3, 0\n\ts_addc_u32 %1, %1, 0" : "+v"(stack_lanes), "+s"(sp) : "s"(ch[c]), "s"(m[c]) : "m0", "scc")
-            FT_PUSH(3); FT_PUSH(2); FT_PUSH(1);
-#undef FT_PUSH
-#pragma clang diagnostic pop
+            for (int c = 0; c < 4; ++c) m[c] = entered(nd + 12 + 6 * c) & half[c >> 1];
+            st.push(ch[3], m[3]); st.push(ch[2], m[2]); st.push(ch[1], m[1]);
             if (m[0]) { cur = ch[0]; continue; }
         } else {
             const uint32_t first = S.bsp_leaves[2 * (~cur)], count = S.bsp_leaves[2 * (~cur) + 1];
-            for (uint32_t k = 0; k < count; ++k) {                 // list order; wave-uniform: scalar loads
-                double t = 0.0;
-                const bool h = tri_hit_wave(S.tris + 9ull * (first + k), r, alive, t);
-                if (ANY) {
-                    const bool b = h & (t < bound);
-                    q.blocked = q.blocked | b; alive = alive & !b; reach = b ? -__builtin_inf() : reach;
-                } else if (__any(h)) {
-                    const bool nearer = h & (t < bound);
-                    bound = nearer ? t : bound; best_tri = nearer ? first + k : best_tri; found = found | nearer;
-                    reach = nearer ? reach_of(t) : reach;
+            if (ANY) {
+                any_hit_leaf(S.tris, first, count, r, bound, q, alive);
+                reach = alive ? reach : -__builtin_inf();
+                if (!__any(alive)) break;
+            } else {
+                for (uint32_t k = 0; k < count; ++k) {             // list order; wave-uniform: scalar loads
+                    double t = 0.0;
+                    const bool h = tri_hit_wave(S.tris + 9ull * (first + k), r, alive, t);
+                    if (__any(h)) {
+                        const bool nearer = h & (t < bound);
+                        bound = nearer ? t : bound; best_tri = nearer ? first + k : best_tri; found = found | nearer;
+                        reach = nearer ? reach_of(t) : reach;
+                    }
                 }
             }
-            if (ANY) { if (!__any(alive)) break; }
         }
-        if (sp == 0) break;
-        --sp;
-        cur = __builtin_amdgcn_readlane(stack_lanes, sp);
+        if (!st.pop(cur)) break;
     }
-#undef FT_SLAB
-#undef FT_ENTERED
     if (!ANY && found) q.hit(bound, leaf, best_tri, lit);
     return true;
 }
@@ -719,8 +762,7 @@ FT_DEV void mesh_bvh_packet(const Scene& S, int32_t wide_root, const Ray& r, Que
     double reach = alive ? bound : -__builtin_inf();               // how far a box may lie and still matter to this lane: nowhere for a dead one
     uint32_t best_tri = 0xFFFFFFFFu;
     bool found = false;
-    int stack_lanes = 0;                                           // lane i holds stack entry i (at most 3 per level of the wide tree)
-    int sp = 0;
+    WaveStack st;                                                  // at most 3 entries per level of the wide tree
     int cur = wide_root;
     // The boxes of a node's four children live in the node (ft_flat.h): one scalar-load round trip decides four subtrees.
     const unsigned long long live0 = __ballot(alive);
@@ -730,7 +772,7 @@ FT_DEV void mesh_bvh_packet(const Scene& S, int32_t wide_root, const Ray& r, Que
                          (2 * __popcll(__ballot(alive && r.dz >= 0.0)) >= __popcll(live0) ? 4u : 0u);
     for (;;) {
         cur = __builtin_amdgcn_readfirstlane(cur);
-        sp = __builtin_amdgcn_readfirstlane(sp);                    // wave-uniform by construction; said here so that the stack arithmetic stays on the scalar unit
+        st.sp = __builtin_amdgcn_readfirstlane(st.sp);              // wave-uniform by construction; said here so that the stack arithmetic stays on the scalar unit
         if (cur >= 0) {
             if (ANY) FT_WALK_ADD(0, 1);
             cdp nd = S.wide + (unsigned long long)kWideNodeDoubles * (uint32_t)cur;
@@ -762,7 +804,7 @@ FT_DEV void mesh_bvh_packet(const Scene& S, int32_t wide_root, const Ray& r, Que
                 asm("s_cmp_lg_u64 %1, 0\n\ts_addc_u32 %0, %0, 0\n\ts_cmp_lg_u64 %2, 0\n\ts_addc_u32 %0, %0, 0\n\ts_cmp_lg_u64 %3, 0\n\ts_addc_u32 %0, %0, 0\n\ts_cmp_lg_u64 %4, 0\n\ts_addc_u32 %0, %0, 0"
                     : "+s"(n_in) : "s"(m[0]), "s"(m[1]), "s"(m[2]), "s"(m[3]) : "scc");
                 if (n_in == 1u) { cur = m[0] ? ch[0] : m[1] ? ch[1] : m[2] ? ch[2] : ch[3]; continue; }
-                if (n_in == 0u) { if (sp == 0) break; --sp; cur = __builtin_amdgcn_readlane(stack_lanes, sp); continue; }
+                if (n_in == 0u) { if (!st.pop(cur)) break; continue; }
             }
             // Visiting order, nearest first by the majority directions: halves by the node's axis, slots within a half by the child's.
             // The entered children go on the stack far to near and the common pop below takes the nearest; one of eight fixed
@@ -770,12 +812,7 @@ FT_DEV void mesh_bvh_packet(const Scene& S, int32_t wide_root, const Ray& r, Que
             // cost ~250 scalar instructions per node - eight-byte select chains - against ~80 vector ones: the scalar pipe, one
             // per CU, was the busier half of this kernel).
             const uint32_t order = (((oct >> (axes & 3u)) & 1u) << 2) | (((oct >> ((axes >> 8) & 3u)) & 1u) << 1) | ((oct >> ((axes >> 16) & 3u)) & 1u);
-            // a push is one v_writelane at the top slot (free when nothing is entered: the write is then simply not kept) and a scalar add;
-            // the lane select goes through m0 (one scalar operand per vector instruction), which the compiler reserves and nothing else here uses
-            // (naming it as clobbered keeps the operands out of it; the compiler remarks that the register is reserved)
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-#define FT_PUSH(c) asm("s_mov_b32 m0, %1\n\tv_writelane_b32 %0, %2, m0\n\ts_cmp_lg_u64 %3, 0\n\ts_addc_u32 %1, %1, 0" : "+v"(stack_lanes), "+s"(sp) : "s"(ch[c]), "s"(m[c]) : "m0", "scc")
+#define FT_PUSH(c) st.push(ch[c], m[c])
             // the nearest child is not pushed and popped again: when it is entered the walk goes straight on with it
 #define FT_NEXT(c) if (m[c]) { cur = ch[c]; continue; }
             switch (order) {                                        // bit 2: left half first; bit 1: slot 0 before 1; bit 0: slot 2 before 3
@@ -790,28 +827,27 @@ FT_DEV void mesh_bvh_packet(const Scene& S, int32_t wide_root, const Ray& r, Que
             }
 #undef FT_NEXT
 #undef FT_PUSH
-#pragma clang diagnostic pop
         } else {
             const uint32_t first = S.bsp_leaves[2 * (~cur)], count = S.bsp_leaves[2 * (~cur) + 1];
-            const unsigned long long clk_leaf = FT_WALK_NOW();
-            for (uint32_t k = 0; k < count; ++k) {                 // wave-uniform: scalar loads
-                double t = 0.0;
-                const bool h = tri_hit_wave(S.tris + 9ull * (first + k), r, alive, t);
-                if (ANY) {
-                    const bool b = h & (t < bound);
-                    q.blocked = q.blocked | b; alive = alive & !b; reach = b ? -__builtin_inf() : reach;
-                } else if (__any(h)) {                              // a live lane's reach IS its nearest distance so far
-                    const uint32_t orig = S.tri_orig[first + k];
-                    const bool nearer = h & ((t < reach) | (found & (t == reach) & (orig < best_tri)));
-                    reach = nearer ? t : reach; best_tri = nearer ? orig : best_tri; found = found | nearer;
+            if (ANY) {
+                const unsigned long long clk_leaf = FT_WALK_NOW();
+                any_hit_leaf(S.tris, first, count, r, bound, q, alive);
+                reach = alive ? reach : -__builtin_inf();
+                FT_WALK_ADD(1, count); FT_WALK_ADD(2, FT_WALK_NOW() - clk_leaf);
+                if (!__any(alive)) break;
+            } else {
+                for (uint32_t k = 0; k < count; ++k) {             // wave-uniform: scalar loads
+                    double t = 0.0;
+                    const bool h = tri_hit_wave(S.tris + 9ull * (first + k), r, alive, t);
+                    if (__any(h)) {                                 // a live lane's reach IS its nearest distance so far
+                        const uint32_t orig = S.tri_orig[first + k];
+                        const bool nearer = h & ((t < reach) | (found & (t == reach) & (orig < best_tri)));
+                        reach = nearer ? t : reach; best_tri = nearer ? orig : best_tri; found = found | nearer;
+                    }
                 }
             }
-            if (ANY) { FT_WALK_ADD(1, count); FT_WALK_ADD(2, FT_WALK_NOW() - clk_leaf); }
-            if (ANY) { if (!__any(alive)) break; }
         }
-        if (sp == 0) break;
-        --sp;
-        cur = __builtin_amdgcn_readlane(stack_lanes, sp);
+        if (!st.pop(cur)) break;
     }
     if (!ANY && found) q.hit(reach, leaf, best_tri, lit);
 }
@@ -841,11 +877,11 @@ FT_DEV void mesh_shadow_packet(const Scene& S, cdp P, const Ray& r, Query<true>&
     }
     const double bound = q.max_dist;
     FT_WALK_ADD(3, 1);
-    int stack_lanes = 0, sp = 0;
+    WaveStack st;
     int cur = reinterpret_cast<cip>(P + 14)[0];
     for (;;) {
         cur = __builtin_amdgcn_readfirstlane(cur);
-        sp = __builtin_amdgcn_readfirstlane(sp);
+        st.sp = __builtin_amdgcn_readfirstlane(st.sp);
         if (cur >= 0) {
             FT_WALK_ADD(0, 1);
             const FT_CONST float* nd = reinterpret_cast<const FT_CONST float*>(S.ls_nodes + (unsigned long long)kLsNodeWords * (uint32_t)cur);
@@ -857,28 +893,17 @@ FT_DEV void mesh_shadow_packet(const Scene& S, cdp P, const Ray& r, Query<true>&
                 m[c] = __builtin_amdgcn_ballot_w64(bx[0] <= uH) & __builtin_amdgcn_ballot_w64(bx[1] >= uL) & __builtin_amdgcn_ballot_w64(bx[2] <= vH) &
                        __builtin_amdgcn_ballot_w64(bx[3] >= vL) & __builtin_amdgcn_ballot_w64(bx[4] >= wL);
             }
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-#define FT_PUSH(c) asm("s_mov_b32 m0, %1\n\tv_writelane_b32 %0, %2, m0\n\ts_cmp_lg_u64 %3, 0\n\ts_addc_u32 %1, %1, 0" : "+v"(stack_lanes), "+s"(sp) : "s"(ch[c]), "s"(m[c]) : "m0", "scc")
-            FT_PUSH(3); FT_PUSH(2); FT_PUSH(1);
-#undef FT_PUSH
-#pragma clang diagnostic pop
+            st.push(ch[3], m[3]); st.push(ch[2], m[2]); st.push(ch[1], m[1]);
             if (m[0]) { cur = ch[0]; continue; }
         } else {
             const uint32_t first = (uint32_t)(~cur) >> 3, count = (uint32_t)(~cur) & 7u;
             const unsigned long long clk_leaf = FT_WALK_NOW();
-            for (uint32_t k = 0; k < count; ++k) {                 // wave-uniform: scalar loads
-                double t = 0.0;
-                const bool h = tri_hit_wave(S.ls_tris + 9ull * (first + k), r, alive, t);
-                const bool b = h & (t < bound);
-                q.blocked = q.blocked | b; alive = alive & !b; wL = b ? __builtin_inff() : wL;
-            }
+            any_hit_leaf(S.ls_tris, first, count, r, bound, q, alive);
+            wL = alive ? wL : __builtin_inff();
             FT_WALK_ADD(1, count); FT_WALK_ADD(2, FT_WALK_NOW() - clk_leaf);
             if (!__any(alive)) break;
         }
-        if (sp == 0) break;
-        --sp;
-        cur = __builtin_amdgcn_readlane(stack_lanes, sp);
+        if (!st.pop(cur)) break;
     }
 }
 
@@ -1221,8 +1246,8 @@ FT_DEV void trace(const Scene& S, const Ray& r, Query<ANY>& q, uint32_t* lds, bo
                         to_model(S.leaves + 16ull * arg, (H.flags & LF_XFORM) != 0, r, rm);
                         if (coherent) {
                             const int32_t wide_root = S.mesh_wide[H.mesh];     // the tree two levels at a time (none: deeper than the packet's stack)
-                            if (wide_root == INT32_MIN || !mesh_bsp_packet<ANY>(S, bsp_root, wide_root, rm, q, arg, lit)) mesh_bsp_query<ANY, true>(S, bsp_root, rm, q, arg, lit, stack);
-                        } else mesh_bsp_query<ANY, false>(S, bsp_root, rm, q, arg, lit, stack);
+                            if (wide_root == INT32_MIN || !mesh_bsp_packet<ANY>(S, bsp_root, wide_root, rm, q, arg, lit)) mesh_bsp_narrow<ANY>(S, bsp_root, rm, q, arg, lit);
+                        } else mesh_bsp_query<ANY>(S, bsp_root, rm, q, arg, lit, stack);
                         break;
                     }
                 }
@@ -1455,11 +1480,7 @@ FT_DEV void textured_colour(const Scene& S, const MaterialV& mat, double u, doub
 struct BatchCursor {
     uint32_t* ctr; uint32_t cls;
     FT_DEV BatchCursor(uint32_t* counters) {
-#ifdef FT_AB_NO_UNIFORM_WAVE
-        const uint32_t wave = blockIdx.x * (kBlock / 64) + threadIdx.x / 64;
-#else
         const uint32_t wave = blockIdx.x * (kBlock / 64) + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / 64));   // uniform: the cursor's address stays scalar
-#endif
         cls = wave % (uint32_t)kWorkGroups;
         ctr = counters + 16u * cls;
     }
@@ -1702,12 +1723,7 @@ FT_DEV void shade_lights(const Scene& S, const Surface& sf, const MaterialV& mat
                 // Math.Pow proper only exists in the FANCY variants (the host routes every scene with such an exponent there): inlined into the
                 // lean kernels its seventeen polynomial constants were hoisted out of the batch loop and spilled - 136 bytes of scratch per lane,
                 // stored by every wave of every launch before its first batch
-#ifdef FT_AB_POW_ALL
-                constexpr bool kPow = true;
-#else
-                constexpr bool kPow = FANCY;
-#endif
-                if (kPow) { if (__any(wants && !small_int)) { const double pw = pow(base, mat.shineyness); if (wants && !small_int) si = pw; } }
+                if (FANCY) { if (__any(wants && !small_int)) { const double pw = pow(base, mat.shineyness); if (wants && !small_int) si = pw; } }
             }
             if (!(mat.shineyness <= 0.0 || si <= 0.0)) { fr = lcr * si; fg = lcg * si; fb = lcb * si; }
         }
@@ -1750,12 +1766,7 @@ struct PrimaryArgs {
 // A fifth wave pays on the leanest variant only (no meshes, no soft lights; measured: night-house-det 3.60 -> 3.30 ms, the others even
 // or worse), and only where the scene's LDS lets five workgroups live on a CU: hollow-sphere's hit lists allow four, and the
 // five-workgroup build - fewer registers, more scratch - costs it 3 %.  So the lean variant exists twice and the host picks.
-#ifndef FT_PRIMARY_BLOCKS
-#define FT_PRIMARY_BLOCKS 4
-#endif
-#ifndef FT_LEAN_BLOCKS
-#define FT_LEAN_BLOCKS 5
-#endif
+constexpr int kPrimaryBlocks = 4, kLeanBlocks = 5;
 template <bool FANCY, bool SOFT, bool MESH, int BLOCKS>
 __global__ __launch_bounds__(kBlock, BLOCKS) void k_primary(PrimaryArgs) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
@@ -1876,14 +1887,8 @@ struct BounceArgs {
     uint32_t acc_stride; int32_t bounce, max_depth;
     int32_t follow;                                                // the last level launched: rays it spawns are followed to their end in registers, not queued
 };
-#ifndef FT_BOUNCE_BLOCKS
-#define FT_BOUNCE_BLOCKS 4
-#endif
 template <bool FANCY, bool SOFT, bool MESH>
-#ifndef FT_BOUNCE_LEAN
-#define FT_BOUNCE_LEAN FT_BOUNCE_BLOCKS
-#endif
-__global__ __launch_bounds__(kBlock, FANCY ? 2 : (!SOFT && !MESH ? FT_BOUNCE_LEAN : FT_BOUNCE_BLOCKS)) void k_bounce(BounceArgs) {
+__global__ __launch_bounds__(kBlock, FANCY ? 2 : 4) void k_bounce(BounceArgs) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const FT_CONST BounceArgs* K = kernel_args<BounceArgs>();
     const int bounce = K->bounce;
@@ -2225,10 +2230,6 @@ FT_DEV void write_pixel(double* out_rgb, uint8_t* out_rgba, size_t o, double r, 
     if (out_rgba) reinterpret_cast<uint32_t*>(out_rgba)[o] = to_byte(r) | (to_byte(g) << 8) | (to_byte(b) << 16) | 0xFF000000u;   // R, G, B, A = 255 in memory order
 }
 
-// k_resolve: every pixel of the chunk's window of the active list gets the mean of its samples, summed from Zero in sample order and
-// divided once (JitteredSampling.blendPixels, Image.fs:112-116: Array.average = sum, then DivideByInt, CommonTypes.fs:43-48); with
-// block_pos the launch also writes Colour.Zero for the pixels of every block k_classify finished.  Each pixel of the frame is
-// written once, as FP64 RGB and / or as RGBA8 bytes.
 // The end of a frame: the last workgroup to get here copies what the host wants of the counters into the pinned report and clears
 // the counters for the next frame.  Every other workgroup has finished with them (the ticket is taken after a workgroup's last
 // access) and the kernels that wrote them ended before this one began.
@@ -2319,46 +2320,60 @@ FT_DEV void resolve_grouped(const ResolveArgs& a, uint32_t n_pix, double* T, Sta
     }
 }
 
-__global__ __launch_bounds__(kBlock) void k_resolve(ResolveArgs a) {
+// The body of k_resolve and k_resolve_progressive.  start(q, sum, sq) and emit(q, sum, sq) as in resolve_grouped, q the pixel's place in
+// the chunk's window; untraced(p, bp) for pixel p of every block k_classify took out of the frame (block_pos[blk] = bp < 0).
+template <bool SQ, class Start, class Emit, class Untraced>
+FT_DEV void resolve_body(const ResolveArgs& a, Start&& start, Emit&& emit, Untraced&& untraced) {
     __shared__ double tile[(kBlock / 64) * 8 * 136];                // per wave 8 x 136 doubles >= G rows of 64 + 64 / G for G = 2 .. 16 (and 8 KB for the hand-over)
     uint32_t n_pix = a.n_pix_host;                                  // all pixels of the chunk, or its window of the frame's active list (k_classify)
     if (a.counts) { const uint32_t n_active = a.counts->n_pix; n_pix = n_active > a.first ? (n_active - a.first < a.n_pix_host ? n_active - a.first : a.n_pix_host) : 0u; }
-    const double spp = (double)a.spp;
     const uint32_t group_log2 = (n_pix & 63u) ? 0u : a.group_log2;    // as pix_count decides it
+    if (group_log2 == 0u) {
+        for (uint32_t q = blockIdx.x * kBlock + threadIdx.x; q < n_pix; q += gridDim.x * kBlock) {
+            double s[3], sq[3];
+            start(q, s, sq);
+            for (int k = 0; k < a.spp; ++k) {
+                const size_t i = (size_t)k * n_pix + q;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) { const double x = a.acc[(size_t)c * a.acc_stride + i]; s[c] += x; if (SQ) sq[c] += x * x; }
+            }
+            emit(q, s, sq);
+        }
+    } else {
+        double* T = tile + (threadIdx.x >> 6) * (8 * 136);
+        switch (group_log2) {
+            case 1: resolve_grouped<1, SQ>(a, n_pix, T, start, emit); break;
+            case 2: resolve_grouped<2, SQ>(a, n_pix, T, start, emit); break;
+            case 3: resolve_grouped<3, SQ>(a, n_pix, T, start, emit); break;
+            default: resolve_grouped<4, SQ>(a, n_pix, T, start, emit); break;
+        }
+    }
+    __syncthreads();                                                // the tile serves the hand-over next
+    if (a.block_pos) {                                              // one wave per untraced block
+        const uint32_t lane = threadIdx.x & 63u;
+        for (uint32_t blk = blockIdx.x * (kBlock / 64) + threadIdx.x / 64; blk < a.n_blocks_total; blk += gridDim.x * (kBlock / 64)) {
+            const int32_t bp = a.block_pos[blk];
+            if (bp >= 0) continue;
+            untraced(blk * 64u + lane, bp);
+        }
+    }
+    if (a.report) hand_over_frame(a.fc, a.report, reinterpret_cast<unsigned long long*>(tile));
+}
+
+// k_resolve: every pixel of the chunk's window of the active list gets the mean of its samples, summed from Zero in sample order and
+// divided once (JitteredSampling.blendPixels, Image.fs:112-116: Array.average = sum, then DivideByInt, CommonTypes.fs:43-48); with
+// block_pos the launch also writes Colour.Zero for the pixels of every block k_classify finished.  Each pixel of the frame is
+// written once, as FP64 RGB and / or as RGBA8 bytes.
+__global__ __launch_bounds__(kBlock) void k_resolve(ResolveArgs a) {
+    const double spp = (double)a.spp;
+    auto from_zero = [](uint32_t, double (&s)[3], double (&)[3]) { s[0] = s[1] = s[2] = 0.0; };
     auto emit = [&](uint32_t q, const double (&s)[3], const double (&)[3]) {
         const uint32_t al = a.first + q;                            // position in the active list -> position in the original pixel list
         const uint32_t p = a.pos_block ? a.pos_block[al >> 6] * 64u + (al & 63u) : al;
         write_pixel(a.out_rgb, a.out_rgba, a.pixel_ids ? (size_t)a.pixel_ids[p] : (size_t)p, s[0] / spp, s[1] / spp, s[2] / spp);
     };
-    auto from_zero = [](uint32_t, double (&s)[3], double (&)[3]) { s[0] = s[1] = s[2] = 0.0; };
-    if (group_log2 == 0u) {
-        for (uint32_t q = blockIdx.x * kBlock + threadIdx.x; q < n_pix; q += gridDim.x * kBlock) {
-            double s[3] = {0.0, 0.0, 0.0}, none[3];
-            for (int k = 0; k < a.spp; ++k) {
-                const size_t i = (size_t)k * n_pix + q;
-                s[0] += a.acc[i]; s[1] += a.acc[(size_t)a.acc_stride + i]; s[2] += a.acc[2 * (size_t)a.acc_stride + i];
-            }
-            emit(q, s, none);
-        }
-    } else {
-        double* T = tile + (threadIdx.x >> 6) * (8 * 136);
-        switch (group_log2) {
-            case 1: resolve_grouped<1, false>(a, n_pix, T, from_zero, emit); break;
-            case 2: resolve_grouped<2, false>(a, n_pix, T, from_zero, emit); break;
-            case 3: resolve_grouped<3, false>(a, n_pix, T, from_zero, emit); break;
-            default: resolve_grouped<4, false>(a, n_pix, T, from_zero, emit); break;
-        }
-    }
-    __syncthreads();                                                // the tile serves the hand-over next
-    if (a.block_pos) {                                              // one wave per finished block: Colour.Zero for its 64 pixels
-        const uint32_t lane = threadIdx.x & 63u;
-        for (uint32_t blk = blockIdx.x * (kBlock / 64) + threadIdx.x / 64; blk < a.n_blocks_total; blk += gridDim.x * (kBlock / 64)) {
-            if (a.block_pos[blk] >= 0) continue;
-            const uint32_t p = blk * 64u + lane;
-            write_pixel(a.out_rgb, a.out_rgba, a.pixel_ids ? (size_t)a.pixel_ids[p] : (size_t)p, 0.0, 0.0, 0.0);
-        }
-    }
-    if (a.report) hand_over_frame(a.fc, a.report, reinterpret_cast<unsigned long long*>(tile));
+    auto finished = [&](uint32_t p, int32_t) { write_pixel(a.out_rgb, a.out_rgba, a.pixel_ids ? (size_t)a.pixel_ids[p] : (size_t)p, 0.0, 0.0, 0.0); };   // Colour.Zero
+    resolve_body<false>(a, from_zero, emit, finished);
 }
 
 // Pixel p of a progressive accumulation's list after a pass: its sums back into the `out` side, its mean S / n into the frame, and - by the
@@ -2390,10 +2405,6 @@ FT_DEV void progressive_out(const ResolveArgs& a, const ProgressiveArgs& pa, uin
 // contiguous 512-byte run per plane.
 template <bool SQ>
 __global__ __launch_bounds__(kBlock) void k_resolve_progressive(ResolveArgs a, ProgressiveArgs pa) {
-    __shared__ double tile[(kBlock / 64) * 8 * 136];
-    uint32_t n_pix = a.n_pix_host;
-    if (a.counts) { const uint32_t n_active = a.counts->n_pix; n_pix = n_active > a.first ? (n_active - a.first < a.n_pix_host ? n_active - a.first : a.n_pix_host) : 0u; }
-    const uint32_t group_log2 = (n_pix & 63u) ? 0u : a.group_log2;
     const size_t L = pa.n_list;
     auto at = [&](uint32_t q) { const uint32_t al = a.first + q; return a.pos_block ? a.pos_block[al >> 6] * 64u + (al & 63u) : al; };
     auto load = [&](uint32_t p, double (&s)[3], double (&sq)[3]) {
@@ -2402,39 +2413,13 @@ __global__ __launch_bounds__(kBlock) void k_resolve_progressive(ResolveArgs a, P
     };
     auto start = [&](uint32_t q, double (&s)[3], double (&sq)[3]) { load(at(q), s, sq); };
     auto emit = [&](uint32_t q, const double (&s)[3], const double (&sq)[3]) { const uint32_t p = at(q); progressive_out(a, pa, p, s, sq, pa.blk_in[p >> 6] + (uint32_t)a.spp); };
-    if (group_log2 == 0u) {
-        for (uint32_t q = blockIdx.x * kBlock + threadIdx.x; q < n_pix; q += gridDim.x * kBlock) {
-            double s[3], sq[3];
-            start(q, s, sq);
-            for (int k = 0; k < a.spp; ++k) {
-                const size_t i = (size_t)k * n_pix + q;
-#pragma unroll
-                for (int c = 0; c < 3; ++c) { const double x = a.acc[(size_t)c * a.acc_stride + i]; s[c] += x; if (SQ) sq[c] += x * x; }
-            }
-            emit(q, s, sq);
-        }
-    } else {
-        double* T = tile + (threadIdx.x >> 6) * (8 * 136);
-        switch (group_log2) {
-            case 1: resolve_grouped<1, SQ>(a, n_pix, T, start, emit); break;
-            case 2: resolve_grouped<2, SQ>(a, n_pix, T, start, emit); break;
-            case 3: resolve_grouped<3, SQ>(a, n_pix, T, start, emit); break;
-            default: resolve_grouped<4, SQ>(a, n_pix, T, start, emit); break;
-        }
-    }
-    __syncthreads();                                                // the tile serves the hand-over next
-    if (a.block_pos) {                                              // one wave per block the pass did not trace
-        const uint32_t lane = threadIdx.x & 63u;
-        for (uint32_t blk = blockIdx.x * (kBlock / 64) + threadIdx.x / 64; blk < a.n_blocks_total; blk += gridDim.x * (kBlock / 64)) {
-            const int32_t bp = a.block_pos[blk];
-            if (bp >= 0) continue;
-            const uint32_t p = blk * 64u + lane, word = pa.blk_in[blk];
-            double s[3], sq[3];
-            load(p, s, sq);
-            progressive_out(a, pa, p, s, sq, bp == kBlockRetired ? word : word + (uint32_t)a.spp);
-        }
-    }
-    if (a.report) hand_over_frame(a.fc, a.report, reinterpret_cast<unsigned long long*>(tile));
+    auto untraced = [&](uint32_t p, int32_t bp) {
+        const uint32_t word = pa.blk_in[p >> 6];
+        double s[3], sq[3];
+        load(p, s, sq);
+        progressive_out(a, pa, p, s, sq, bp == kBlockRetired ? word : word + (uint32_t)a.spp);
+    };
+    resolve_body<SQ>(a, start, emit, untraced);
 }
 
 __global__ __launch_bounds__(kBlock) void k_resolve_corner(const double* __restrict__ acc, uint32_t acc_stride, uint32_t w, uint32_t h,
@@ -2499,14 +2484,14 @@ __global__ __launch_bounds__(kBlock) void k_debug_blocked(DevScene Sg, const dou
 typedef void (*PrimaryKernel)(PrimaryArgs);
 static PrimaryKernel primary_variant(int v) {                      // bit 0 FANCY, bit 1 SOFT, bit 2 MESH, bit 3: the lean variant built for five workgroups per CU
     switch (v & 15) {
-        case 0: return k_primary<false, false, false, FT_PRIMARY_BLOCKS>;
-        case 8: return k_primary<false, false, false, FT_LEAN_BLOCKS>;
+        case 0: return k_primary<false, false, false, kPrimaryBlocks>;
+        case 8: return k_primary<false, false, false, kLeanBlocks>;
         case 1: case 9: return k_primary<true, false, false, 2>;
-        case 2: case 10: return k_primary<false, true, false, FT_PRIMARY_BLOCKS>;
+        case 2: case 10: return k_primary<false, true, false, kPrimaryBlocks>;
         case 3: case 11: return k_primary<true, true, false, 2>;
-        case 4: case 12: return k_primary<false, false, true, FT_PRIMARY_BLOCKS>;
+        case 4: case 12: return k_primary<false, false, true, kPrimaryBlocks>;
         case 5: case 13: return k_primary<true, false, true, 2>;
-        case 6: case 14: return k_primary<false, true, true, FT_PRIMARY_BLOCKS>;
+        case 6: case 14: return k_primary<false, true, true, kPrimaryBlocks>;
         default: return k_primary<true, true, true, 2>;
     }
 }
@@ -2542,16 +2527,19 @@ void launch_bounce(const Launch& L, const DevScene& S, const Primary& gen, RayBu
     const BounceArgs a{S, gen, rays, next, acc, fc, acc_stride, bounce, max_depth, follow ? 1 : 0};
     hipLaunchKernelGGL(bounce_variant(L.variant), dim3(L.grid), dim3(kBlock), L.lds_bytes, L.stream, a);
 }
-void launch_resolve(const Launch& L, const ResolveArgs& a) {
+// Workgroups of a resolve launch: L.grid is one resident round of workgroups (occupancy_blocks_resolve x CUs; the grouped path holds 3 x 16
+// colours per lane: fewer waves fit than the tracing kernels' grids assume), so that the hand-over at the end waits for one generation of
+// workgroups, not for several
+static int resolve_blocks(const Launch& L, const ResolveArgs& a) {
     const uint32_t work = a.block_pos ? (a.n_blocks_total * 64u > a.n_pix_host ? a.n_blocks_total * 64u : a.n_pix_host) : a.n_pix_host;
-    // L.grid: one resident round of workgroups (occupancy_blocks_resolve x CUs; the grouped path holds 3 x 16 colours per lane: fewer waves fit
-    // than the tracing kernels' grids assume), so that the hand-over at the end waits for one generation of workgroups, not for several
-    hipLaunchKernelGGL(k_resolve, dim3(blocks_for(work, L.grid)), dim3(kBlock), 0, L.stream, a);
+    return blocks_for(work, L.grid);
+}
+void launch_resolve(const Launch& L, const ResolveArgs& a) {
+    hipLaunchKernelGGL(k_resolve, dim3(resolve_blocks(L, a)), dim3(kBlock), 0, L.stream, a);
 }
 void launch_resolve_progressive(const Launch& L, const ResolveArgs& a, const ProgressiveArgs& pa) {
-    const uint32_t work = a.block_pos ? (a.n_blocks_total * 64u > a.n_pix_host ? a.n_blocks_total * 64u : a.n_pix_host) : a.n_pix_host;
-    if (pa.sq_in) hipLaunchKernelGGL(k_resolve_progressive<true>, dim3(blocks_for(work, L.grid)), dim3(kBlock), 0, L.stream, a, pa);
-    else hipLaunchKernelGGL(k_resolve_progressive<false>, dim3(blocks_for(work, L.grid)), dim3(kBlock), 0, L.stream, a, pa);
+    if (pa.sq_in) hipLaunchKernelGGL(k_resolve_progressive<true>, dim3(resolve_blocks(L, a)), dim3(kBlock), 0, L.stream, a, pa);
+    else hipLaunchKernelGGL(k_resolve_progressive<false>, dim3(resolve_blocks(L, a)), dim3(kBlock), 0, L.stream, a, pa);
 }
 #ifdef FT_ITEM_COUNTS
 extern "C" int ft_debug_item_counts(unsigned long long out[48], int reset) {      // [0..15] item counters, [16..47] section clocks, summed over the waves' slots
@@ -2584,7 +2572,7 @@ static int clamp_blocks(int n) { return n < 1 ? 1 : (n > 8 ? 8 : n); }
 int occupancy_blocks_primary(size_t lds_bytes, int* variant) {
     int n = 0;
     if ((*variant & 7) == 0) {
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, primary_variant(8), kBlock, lds_bytes) == hipSuccess && n >= FT_LEAN_BLOCKS) { *variant |= 8; return clamp_blocks(n); }
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, primary_variant(8), kBlock, lds_bytes) == hipSuccess && n >= kLeanBlocks) { *variant |= 8; return clamp_blocks(n); }
     }
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, primary_variant(*variant), kBlock, lds_bytes) != hipSuccess) n = 1;
     return clamp_blocks(n);
