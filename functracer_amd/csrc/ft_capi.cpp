@@ -312,10 +312,9 @@ int lane_fold_for(const fth::FlatScene& f) {
     return 0;
 }
 // Materials only the FANCY kernel variants shade: Oren-Nayar, textures, and a specular exponent that is not a small whole number
-// (the lean variants raise to whole powers up to 64 by square-and-multiply and do not carry Math.Pow, ft_kernels.hip shade_lights).
+// (ftd::small_whole_exponent: the lean variants do not carry Math.Pow).
 bool needs_fancy(const ftd::Material& m) {
-    const bool whole = m.shineyness <= 64.0 && m.shineyness == std::floor(m.shineyness);
-    return m.roughness != 0.0 || m.texture >= 0 || (m.shineyness > 0.0 && !whole) || m.shineyness != m.shineyness;
+    return m.roughness != 0.0 || m.texture >= 0 || (m.shineyness > 0.0 && !ftd::small_whole_exponent(m.shineyness)) || m.shineyness != m.shineyness;
 }
 // The context's devices: itself, then its peers.
 std::vector<ft_context*> devices(ft_context* c) {

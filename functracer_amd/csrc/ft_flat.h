@@ -68,6 +68,10 @@ struct Texture {             // Scene.Texture (Scene.fs:47-53) flattened; 384 by
     double ops[kMaxUvOps][3];// uv functions outermost first: {0, sx, sy} scale | {1, cos a, sin a} rotate
 };
 
+// A specular exponent the lean kernel variants raise by square-and-multiply (ft_kernels.hip shade_lights): a whole number up to 64.
+// Any other positive exponent needs Math.Pow, which only the FANCY variants carry (ft_capi.cpp needs_fancy).
+constexpr bool small_whole_exponent(double s) { return s <= 64.0 && s == __builtin_floor(s); }
+
 enum LightKind : uint32_t { LT_DIRECTIONAL = 0, LT_SOFT = 1, LT_POINT = 2 };
 struct Light {             // Light.fs:7-14; 96 bytes
     double v[3];           // normalised direction | position

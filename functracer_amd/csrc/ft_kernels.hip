@@ -119,6 +119,10 @@ FT_DEV MaterialV material_at(const Scene& S, uint32_t i) {
     v.apply_lighting = reinterpret_cast<cup>(m + 6)[0]; v.texture = reinterpret_cast<cip>(m + 6)[1]; v.hue_rot = reinterpret_cast<cup>(m + 7)[0];
     return v;
 }
+FT_DEV bool material_lit(const Scene& S, uint32_t i) { return reinterpret_cast<cup>(S.materials + 8ull * i + 6)[0] != 0; }   // per-lane: one word, not the record
+FT_DEV int32_t material_texture(const Scene& S, uint32_t i) { return reinterpret_cast<cip>(S.materials + 8ull * i + 6)[1]; }
+FT_DEV uint32_t light_kind(const Scene& S, uint32_t l) { return reinterpret_cast<cup>(S.lights + 12ull * l + 10)[0]; }   // wave-uniform l: scalar loads
+FT_DEV int32_t light_samples(const Scene& S, uint32_t l) { return reinterpret_cast<cip>(S.lights + 12ull * l + 10)[1]; }
 
 struct Ray { double ox, oy, oz, dx, dy, dz; };
 struct V3 { double x, y, z; };
@@ -239,6 +243,8 @@ struct Query {
     double best_t; uint32_t id0, id1;
     double max_dist; bool blocked;
     bool active;
+    FT_DEV static Query closest(bool active) { Query q; q.active = active; q.best_t = __builtin_inf(); q.id0 = ID_MISS; q.id1 = 0; q.max_dist = 0.0; q.blocked = false; return q; }
+    FT_DEV static Query any(bool active, double max_dist) { Query q; q.active = active; q.blocked = false; q.best_t = 0; q.id0 = 0; q.id1 = 0; q.max_dist = max_dist; return q; }
     FT_DEV void hit(double t, uint32_t i0, uint32_t i1, bool lit) {
         if (!active) return;
         if (ANY) { if (t >= 0.0 && t < max_dist && lit) blocked = true; }
@@ -1388,7 +1394,7 @@ FT_DEV Surface surface_at(const Scene& S, const Ray& rw, double t, uint32_t id0,
     to_model(M, xform, rw, r);
     V3 p, n;
     double tu = 0.0, tv = 0.0;                                     // newIntersection: uv = (0,0) (Ray.fs:29)
-    const bool textured = TEXTURED && reinterpret_cast<cip>(S.materials + 8ull * H.material + 6)[1] >= 0;
+    const bool textured = TEXTURED && material_texture(S, H.material) >= 0;
     switch (H.kind) {
         case LK_SPHERE:
             p = {r.ox + t * r.dx, r.oy + t * r.dy, r.oz + t * r.dz}; n = normalise(p);
@@ -1634,18 +1640,17 @@ FT_DEV void light_visibility(const Scene& S, const Surface& sf, bool lit, unsign
     vis_lo = 0ull; vis_hi = 0ull;
     for (int l = 0; l < n_lights; ++l) {                       // wave-uniform; getLightsOnPoint (Shading.fs:109-117)
         cdp lp = S.lights + 12ull * (uint32_t)l;               // scalar loads
-        const uint32_t kind = reinterpret_cast<cup>(lp + 10)[0];
+        const uint32_t kind = light_kind(S, (uint32_t)l);
         const double sox = sf.p.x + 0.0001 * sf.n.x, soy = sf.p.y + 0.0001 * sf.n.y, soz = sf.p.z + 0.0001 * sf.n.z;
         unsigned long long occluded = 0ull;
         bool overflow = false;
         if (SOFT && kind == LT_SOFT) {                         // softShadowLightIntensity (Shading.fs:24-31)
-            const int samples = reinterpret_cast<cip>(lp + 10)[1];
+            const int samples = light_samples(S, (uint32_t)l);
             const JitterFrame frame(V3{-lp[0], -lp[1], -lp[2]}, lp[11]);   // (moved into scalar registers - make_uniform - the nine doubles cost MORE scratch: 176 -> 248 B in k_bounce<F,T,T>)
             Rng rng = make_rng(seed_of(), sample, (uint32_t)bounce, (uint32_t)l, 1u);
             for (int k = 0; k < samples; ++k) {                // wave-uniform count; each lane draws its own direction
                 const V3 dj = frame.jittered(rng);
-                Query<true> qs;
-                qs.active = lit; qs.blocked = false; qs.best_t = 0; qs.id0 = 0; qs.id1 = 0; qs.max_dist = 1.7976931348623157e308;
+                Query<true> qs = Query<true>::any(lit, 1.7976931348623157e308);
                 bool ovf = false;
                 if (__any(lit)) trace<true, MESH>(S, Ray{sox, soy, soz, dj.x, dj.y, dj.z}, qs, lds, ovf, false);
                 if (qs.blocked) ++occluded;
@@ -1653,8 +1658,7 @@ FT_DEV void light_visibility(const Scene& S, const Surface& sf, bool lit, unsign
                 n_shadow_wave += (unsigned long long)__popcll(__ballot(lit));
             }
         } else {
-            Query<true> q;
-            q.active = lit; q.blocked = false; q.best_t = 0; q.id0 = 0; q.id1 = 0;
+            Query<true> q = Query<true>::any(lit, 0.0);
             Ray sr;
             if (kind == LT_POINT) {                            // shadowLightIntensity (Shading.fs:33-42)
                 const double ddx = lp[0] - sox, ddy = lp[1] - soy, ddz = lp[2] - soz;
@@ -1685,7 +1689,7 @@ FT_DEV void shade_lights(const Scene& S, const Surface& sf, const MaterialV& mat
         if (active && !lit) { cr += mat.colour[0]; cg += mat.colour[1]; cb += mat.colour[2]; }   // shadeIfRequired (Shading.fs:100-104)
         if (!lit) continue;
         cdp lp = S.lights + 12ull * (uint32_t)l;
-        const uint32_t kind = reinterpret_cast<cup>(lp + 10)[0];
+        const uint32_t kind = light_kind(S, (uint32_t)l);
         const double occluded = (double)((l < 8 ? vis_lo >> (8 * l) : vis_hi >> (8 * (l - 8))) & 0xFFull);
         double intensity; V3 ld;
         if (kind == LT_POINT) {                                // Light.attenuate (Light.fs:16-17), lightDirection (Shading.fs:44-48)
@@ -1695,7 +1699,7 @@ FT_DEV void shade_lights(const Scene& S, const Surface& sf, const MaterialV& mat
             intensity = occluded != 0.0 ? 0.0 : 1.0 / (lp[3] + dist * (lp[4] + dist * lp[5]));
             ld = normalise(V3{sf.p.x - lp[0], sf.p.y - lp[1], sf.p.z - lp[2]});
         } else {
-            if (SOFT && kind == LT_SOFT) { const double samples = (double)reinterpret_cast<cip>(lp + 10)[1]; intensity = (samples - occluded) / samples; }
+            if (SOFT && kind == LT_SOFT) { const double samples = (double)light_samples(S, (uint32_t)l); intensity = (samples - occluded) / samples; }
             else intensity = occluded != 0.0 ? 0.0 : 1.0;
             ld = {lp[0], lp[1], lp[2]};
         }
@@ -1707,13 +1711,13 @@ FT_DEV void shade_lights(const Scene& S, const Surface& sf, const MaterialV& mat
             const V3 rl = normalise(V3{ld.x - k2 * nn.x, ld.y - k2 * nn.y, ld.z - k2 * nn.z});         // Vector.reflect (CommonTypes.fs:72)
             const V3 vd = normalise(V3{r.dx, r.dy, r.dz});
             // intensity = (view . -reflected) ** shineyness.  With shineyness <= 0 the shader is black whatever the power is, so
-            // the power is only evaluated when some lane needs it; integral exponents up to 64 (the usual case) go through
+            // the power is only evaluated when some lane needs it; integral exponents up to 64 (the usual case, ft_flat.h) go through
             // square-and-multiply, everything else through pow.
             const bool wants = active && mat.shineyness > 0.0;
             double si = 0.0;
             if (__any(wants)) {                                   // each lane takes its own route: a ray's result must not depend on its wave
                 const double base = dot3(vd.x, vd.y, vd.z, -rl.x, -rl.y, -rl.z);
-                const bool small_int = mat.shineyness <= 64.0 && mat.shineyness == floor(mat.shineyness);
+                const bool small_int = small_whole_exponent(mat.shineyness);
                 if (__any(wants && small_int)) {
                     const uint32_t e = (wants && small_int) ? (uint32_t)mat.shineyness : 0u;
                     double b = base, pw = 1.0;
@@ -1802,8 +1806,7 @@ __global__ __launch_bounds__(kBlock, BLOCKS) void k_primary(PrimaryArgs) {
                 ro = {r.ox + 0.0001 * r.dx, r.oy + 0.0001 * r.dy, r.oz + 0.0001 * r.dz, r.dx, r.dy, r.dz};   // slightOffset (Shading.fs:129)
             }
         }
-        Query<false> q;
-        q.active = active; q.best_t = __builtin_inf(); q.id0 = ID_MISS; q.id1 = 0; q.max_dist = 0.0; q.blocked = false;
+        Query<false> q = Query<false>::closest(active);
         bool overflow;
         const unsigned long long clk_a = FT_CLK_NOW();
         FT_CLK_ADD(22, clk_batch);
@@ -1820,7 +1823,7 @@ __global__ __launch_bounds__(kBlock, BLOCKS) void k_primary(PrimaryArgs) {
             unsigned long long sample = 0ull;
             if (hit) {
                 sf = surface_at<FANCY>(S, ro, q.best_t, q.id0, q.id1);
-                lit = reinterpret_cast<cup>(S.materials + 8ull * sf.material + 6)[0] != 0;
+                lit = material_lit(S, sf.material);
                 if (SOFT) sample = (unsigned long long)pid * (unsigned long long)fresh(K)->gen.spp + at_of(bi).s;
             }
             unsigned long long vis_lo, vis_hi;
@@ -1925,8 +1928,7 @@ __global__ __launch_bounds__(kBlock, FANCY ? 2 : 4) void k_bounce(BounceArgs) {
             //  variants by -20 .. +20 bytes either way: the spills come from inside the item evaluation, not from what lives around it.)
             // ---- closest hit; the geometry sees the offset ray (Shading.fs:135), the shaders the original one (Shading.fs:137)
             const Ray ro{r.ox + 0.0001 * r.dx, r.oy + 0.0001 * r.dy, r.oz + 0.0001 * r.dz, r.dx, r.dy, r.dz};   // slightOffset (Shading.fs:129)
-            Query<false> q;
-            q.active = alive; q.best_t = __builtin_inf(); q.id0 = ID_MISS; q.id1 = 0; q.max_dist = 0.0; q.blocked = false;
+            Query<false> q = Query<false>::closest(alive);
             bool overflow;
             const unsigned long long clk_a = FT_CLK_NOW();
             trace<false, MESH>(S, ro, q, lds, overflow, false);
@@ -1941,7 +1943,7 @@ __global__ __launch_bounds__(kBlock, FANCY ? 2 : 4) void k_bounce(BounceArgs) {
             unsigned long long sample = 0ull;
             if (hit) {
                 sf = surface_at<FANCY>(S, ro, q.best_t, q.id0, q.id1);
-                lit = reinterpret_cast<cup>(S.materials + 8ull * sf.material + 6)[0] != 0;
+                lit = material_lit(S, sf.material);
                 if (SOFT) sample = sample_id(&fresh(K)->gen, px, slot);
             }
             unsigned long long vis_lo, vis_hi;
@@ -2441,8 +2443,7 @@ __global__ __launch_bounds__(kBlock) void k_debug_closest(DevScene Sg, const dou
     const uint32_t B = 64u / (uint32_t)S.lane_fold, n_batches = (n + B - 1) / B;
     for (uint32_t b = blockIdx.x * (kBlock / 64) + threadIdx.x / 64; b < n_batches; b += gridDim.x * (kBlock / 64)) {
         const uint32_t i = b * B + lane_id();
-        Query<false> q;
-        q.active = i < n && lane_id() < B; q.best_t = __builtin_inf(); q.id0 = ID_MISS; q.id1 = 0; q.max_dist = 0; q.blocked = false;
+        Query<false> q = Query<false>::closest(i < n && lane_id() < B);
         Ray r{0, 0, 0, 0, 0, 0};
         if (q.active) r = {o[3 * i], o[3 * i + 1], o[3 * i + 2], d[3 * i], d[3 * i + 1], d[3 * i + 2]};
         bool overflow;
@@ -2469,8 +2470,7 @@ __global__ __launch_bounds__(kBlock) void k_debug_blocked(DevScene Sg, const dou
     const uint32_t B = 64u / (uint32_t)S.lane_fold, n_batches = (n + B - 1) / B;
     for (uint32_t b = blockIdx.x * (kBlock / 64) + threadIdx.x / 64; b < n_batches; b += gridDim.x * (kBlock / 64)) {
         const uint32_t i = b * B + lane_id();
-        Query<true> q;
-        q.active = i < n && lane_id() < B; q.blocked = false; q.best_t = 0; q.id0 = 0; q.id1 = 0; q.max_dist = 0;
+        Query<true> q = Query<true>::any(i < n && lane_id() < B, 0.0);
         Ray r{0, 0, 0, 0, 0, 0};
         if (q.active) { r = {o[3 * i], o[3 * i + 1], o[3 * i + 2], d[3 * i], d[3 * i + 1], d[3 * i + 2]}; q.max_dist = max_dist[i]; }
         bool overflow;

@@ -335,6 +335,29 @@ def test_textures_and_oren_nayar(hip):
     assert worst < 1e-6
 
 
+def test_specular_exponents_beyond_square_and_multiply(hip):
+    """The lean kernel variants raise whole exponents up to 64 by square-and-multiply and carry no Math.Pow (ft_flat.h,
+    small_whole_exponent).  Exponents 65 (whole, but beyond that) and 2.5 are the only materials here that need a FANCY variant: a
+    lean kernel would shade their highlights black.  Which variant runs is not visible from Python, so this checks the frames only:
+    64 alone and 64, 65 and 2.5 together, against the oracle."""
+    cam = ft.make_camera((0, 1.5, -7), (0, 0, 0), (0, 1, 0), H.deg(50.0))
+    jit = ft.jitter_pattern(2)
+    for exponents in ((64.0,), (64.0, 65.0, 2.5)):
+        orc = O.Oracle()
+        for b in (orc, hip):
+            b.clear()
+            objs = [b.material(b.translate((2.2 * k - 1.1 * (len(exponents) - 1), 0, 0), b.primitive(ft.SPHERE)), colour=(0.8, 0.5, 0.3),
+                               reflectance=0.3, shineyness=e) for k, e in enumerate(exponents)]
+            objs.append(b.material(b.translate((0, -1, 0), b.primitive(ft.PLANE)), colour=(0.4, 0.6, 0.4), reflectance=0.2, shineyness=64.0))
+            b.set_objects(b.group(objs))
+            b.add_directional((0.3, -1, 0.8), (0.9, 0.9, 0.9))
+            b.add_positional((-1, 3, -4), (1, 0.05, 0.01), (0.8, 0.8, 1.0))
+            b.commit()
+        want, _ = orc.render(cam, 160, 120, 2, jit)
+        got, _ = hip.render(cam, 160, 120, 2, jit)
+        H.assert_frames_match(got, want, what=f"specular exponents {exponents}")
+
+
 def test_thirteen_nested_texture_functions(hip):
     """Scene.TextureFunction nests without bound in the reference (Scene.fs:47-53, 68-75); the flat texture record holds thirteen uv
     functions (five until round 3).  A plane and a sphere under the full thirteen - scales and rotations alternating - against the oracle."""
