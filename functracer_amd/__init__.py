@@ -59,6 +59,8 @@ def hip_lib():
         lib.ft_render_wait.argtypes = [C.c_void_p, C.POINTER(_capi.ft_stats)]
         lib.ft_render_enqueue_into.argtypes = [C.c_void_p, C.POINTER(_capi.ft_camera), C.c_int32, C.c_int32, C.c_int32, _capi.c_double_p, C.c_int32, C.c_uint64, C.POINTER(_capi.ft_rect), C.c_int32, C.c_int32, C.c_void_p]
         lib.ft_get_kernel_times.argtypes = [C.c_void_p, _capi.c_double_p, _capi.c_int32_p]
+        lib.ft_render_aov.argtypes = [C.c_void_p, C.POINTER(_capi.ft_camera), C.c_int32, C.c_int32, C.c_int32, _capi.c_double_p, C.c_int32,
+                                      C.c_uint64, C.POINTER(_capi.ft_rect), C.c_int32, C.POINTER(_capi.ft_aov), C.POINTER(_capi.ft_stats)]
         lib.ft_quantise_rgba8.argtypes = [_capi.c_double_p, C.c_int64, C.POINTER(C.c_uint8)]
         for name, res, args in _capi.PROGRESSIVE_SIGNATURES:
             fn = getattr(lib, name)
@@ -359,6 +361,48 @@ class Context(SceneBuilder):
         if shape is None:                                           # the frame's size is unknown: nothing to size the output by
             raise FtError(-5, "no progressive accumulation (progressive_begin)")
         return shape
+
+    def render_aov(self, camera, res_h, res_v, spp, jitter, sample=0, seed=DEFAULT_SEED, tiles=None, channels=None, out=None):
+        """Per-pixel surface buffers (ft_render_aov): the hit of sample `sample`'s geometry ray of the frame
+        render(camera, res_h, res_v, spp, jitter, seed=seed, tiles=tiles) would trace, per tile pixel.  Returns a dict of the requested
+        planes ('t', 'p', 'n', 'colour', 'material', 'leaf', 'node', 'triangle'; None = all), each [res_v, res_h] or [res_v, res_h, 3],
+        plus 'stats'.  Planes are created holding the miss values; `out` may hand over planes of its own (pixels outside the tiles keep
+        what they hold)."""
+        want = [c[0] for c in _capi.AOV_CHANNELS] if channels is None else list(channels)
+        unknown = set(want) - {c[0] for c in _capi.AOV_CHANNELS}
+        if unknown:
+            raise ValueError(f"unknown AOV channels {sorted(unknown)}")
+        jitter = np.zeros((1, 2)) if spp == 0 else _capi.as_f64(jitter, (spp, 2))
+        planes, aov = {}, _capi.ft_aov()
+        for name, dtype, width, miss in _capi.AOV_CHANNELS:
+            if name not in want:
+                continue
+            shape = (res_v, res_h) if width == 1 else (res_v, res_h, width)
+            a = out[name] if out is not None and name in out else np.full(shape, miss, dtype=dtype)
+            if a.shape != shape or a.dtype != dtype or not a.flags.c_contiguous:
+                raise ValueError(f"AOV plane {name}: need a C-contiguous {np.dtype(dtype).name} array of shape {shape}")
+            planes[name] = a
+            setattr(aov, name, a.ctypes.data_as(_capi.c_double_p if dtype == np.float64 else _capi.c_int32_p))
+        rects, n_rects = _capi.make_rects(tiles)
+        st = _capi.ft_stats()
+        self._check(self._lib.ft_render_aov(self._ctx, C.byref(camera), res_h, res_v, spp, _capi.dptr(jitter), int(sample), int(seed),
+                                            rects, n_rects, C.byref(aov), C.byref(st)))
+        planes["stats"] = st.as_dict()
+        return planes
+
+    def pick(self, camera, res_h, res_v, x, y, spp=1, jitter=None, sample=0, seed=DEFAULT_SEED):
+        """What is at pixel (x, y) (row 0 = top): the record of render_aov for that one pixel (a 1x1 tile) as a dict of plain
+        values, or None when the ray misses everything.  The device counterpart of printIntersectionAt (Program.fs:33-49)."""
+        jitter = np.zeros((1, 2)) if jitter is None else jitter
+        out = {name: np.full((res_v, res_h) if w == 1 else (res_v, res_h, w), miss, dtype=dt) for name, dt, w, miss in _capi.AOV_CHANNELS}
+        self.render_aov(camera, res_h, res_v, spp, jitter, sample=sample, seed=seed, tiles=[(x, y, 1, 1)], out=out)
+        if out["leaf"][y, x] < 0:
+            return None
+        rec = {}
+        for name, dt, w, _ in _capi.AOV_CHANNELS:
+            v = out[name][y, x]
+            rec[name] = tuple(float(c) for c in v) if w == 3 else (float(v) if dt == np.float64 else int(v))
+        return rec
 
     def closest(self, origins, dirs):
         """Scene.intersectScene (Scene.fs:118) for explicit rays, through the device path."""

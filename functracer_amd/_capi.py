@@ -63,6 +63,16 @@ class ft_stats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class ft_aov(C.Structure):
+    _fields_ = [("t", c_double_p), ("p", c_double_p), ("n", c_double_p), ("colour", c_double_p), ("material", c_double_p),
+                ("leaf", c_int32_p), ("node", c_int32_p), ("triangle", c_int32_p)]
+
+
+# ft_render_aov channels: (name, dtype, components per pixel, value of a pixel whose ray misses everything)
+AOV_CHANNELS = [("t", np.float64, 1, np.inf), ("p", np.float64, 3, 0.0), ("n", np.float64, 3, 0.0), ("colour", np.float64, 3, 0.0),
+                ("material", np.float64, 3, 0.0), ("leaf", np.int32, 1, -1), ("node", np.int32, 1, -1), ("triangle", np.int32, 1, -1)]
+
+
 class fth_options(C.Structure):
     _fields_ = [("camera", ft_camera), ("res_h", C.c_int32), ("res_v", C.c_int32), ("samples", C.c_int32), ("corner", C.c_int32)]
 

@@ -184,6 +184,7 @@ struct EmitArgs {
     BspNode* nodes; uint32_t node_base;        // n - 1 records
     BspLeaf* leaves; uint32_t leaf_base;       // (n - 1) + n records: internal node i as a leaf -> leaf_base + i; sorted triangle k alone -> leaf_base + n - 1 + k
     double* tris_out; uint32_t* tri_orig; uint32_t tri_base;   // n sorted triangle records
+    uint32_t* tri_src;                         // their input faces, copied from the leaf records (ft_flat.h)
     double* wide; uint32_t wide_base;          // n - 1 records of kWideNodeDoubles
 };
 __device__ __forceinline__ double pad_of(const BuildState* st) { return 1e-7 * unordered(st->extent) + 1e-300; }   // as the host builder: pruning can never drop a real hit
@@ -211,6 +212,7 @@ __global__ __launch_bounds__(256) void k_bvh_emit(EmitArgs a) {
         double* O = a.tris_out + 9ull * (a.tri_base + i);
         for (int k = 0; k < 9; ++k) O[k] = T[k];
         a.tri_orig[a.tri_base + i] = a.first_global + src;
+        a.tri_src[a.tri_base + i] = a.tri_src[a.first_global + src];    // (the leaf's records lie outside the range written here)
         a.leaves[a.leaf_base + (a.n - 1u) + i] = i < a.counts[1] ? BspLeaf{a.tri_base + a.leaf_first[i], a.leaf_count[i]} : BspLeaf{0u, 0u};   // build leaf i
     }
     if (i >= a.counts[0]) return;
@@ -544,7 +546,7 @@ hipError_t build_lbvh(hipStream_t stream, const LbvhTarget& t, uint32_t* height,
             hipLaunchKernelGGL(k_sah_leaf_boxes, grid, block, 0, stream, ss, vals, tb, lf, lc, lb, counts, st);
         }
         const EmitArgs ea{t.tris, t.first_global, n, vals, left, right, rf, rl, sb, lb, nb, st, lf, lc, counts,
-                          t.nodes, t.node_base, t.leaves, t.leaf_base, t.tris, t.tri_orig, t.tri_base, t.wide, t.wide_base};
+                          t.nodes, t.node_base, t.leaves, t.leaf_base, t.tris, t.tri_orig, t.tri_base, t.tri_src, t.wide, t.wide_base};
         hipLaunchKernelGGL(k_bvh_emit, grid, block, 0, stream, ea);
         if (t.coarse_count) hipLaunchKernelGGL(k_bvh_coarse, dim3(1), dim3(64), 0, stream, ea, t.coarse, t.coarse_count);
         BVH_HIP(hipGetLastError());

@@ -89,7 +89,9 @@ struct Options {
 
 // One buffer in HBM per array of the flattened scene; DevScene points into them (upload_scene).
 enum SceneArray { kLeaves, kM2w, kMaterials, kLights, kTextures, kTexPixels, kProgram, kMeshes, kNodes, kBspLeaves, kTris, kCulls, kCullItems,
-                  kCullRows, kItemPc, kWide, kMeshWide, kCoarse, kTriOrig, kLsPairs, kLsNodes, kLsTris, kSceneArrays };
+                  kCullRows, kItemPc, kWide, kMeshWide, kCoarse, kTriOrig, kLsPairs, kLsNodes, kLsTris,
+                  kTriSrc, kRunNodes,   // read by k_aov only (ft_render_aov): not part of DevScene
+                  kSceneArrays };
 
 // HIP events of one frame on its main stream.  An event between two dependent kernels costs about 6 us of stream time, so by default
 // ("timing" = 1) only the kernels that trace rays (k_primary, the k_bounce levels) are bracketed; 2 brackets every stage, 0 only the frame.
@@ -149,11 +151,14 @@ struct ft_context {
     hipStream_t side = nullptr;     // the second stream: k_classify of frame N + 1 beside k_primary's tail / k_resolve of frame N (ft_render_enqueue)
     // Kernel variants and resident workgroups per CU for the committed scene (they only change at commit): bit 0 FANCY, 1 SOFT, 2 MESH; the
     // primary's variant may carry bit 3 (the five-workgroup lean build).
-    int variant = 0, variant_primary = 0, blocks_primary = 1, blocks_bounce = 1, blocks_resolve = 2;
+    int variant = 0, variant_primary = 0, blocks_primary = 1, blocks_bounce = 1, blocks_resolve = 2, blocks_aov = 1;
     hipEvent_t classified = nullptr;  // behind the latest k_classify on either stream: the next one waits for it (they share the ticket words of d_wave_counts)
     ftk::DevScene dev_scene{};
     // frame buffers in HBM
     DeviceBuf d_rays[2 * kMains], d_acc[kAcc], d_out, d_out8, d_out_index, d_pixels, d_jitter, d_wave_counts, d_dbg_in, d_dbg_out;
+    // ft_render_aov's own pixel list, jitter pattern, planes and counters: nothing a frame or a progressive pass keeps is touched
+    DeviceBuf d_aov_pixels, d_aov_jitter, d_aov_out, d_aov_ctr;
+    hipEvent_t aov_ev[2] = {};      // around each k_aov launch (kernel_ms)
     // The sample colours exist twice: a queued frame's k_resolve runs on a stream of its own (`tail`), behind an event, while the next
     // chunk's / frame's k_primary already fills the other copy - the small kernel hides in the big one's ramp instead of standing between
     // two of them.  acc_free[i]: behind the last k_resolve that read copy i (the next k_primary into that copy waits for it).
@@ -399,11 +404,12 @@ void ft_destroy(ft_context* c) {
         for (DeviceBuf& b : c->d_scene) b.release();
         for (DeviceBuf& b : c->d_rays) b.release();
         for (DeviceBuf& b : c->d_acc) b.release();
-        for (DeviceBuf* b : {&c->d_out, &c->d_out8, &c->d_out_index, &c->d_pixels, &c->d_jitter, &c->d_wave_counts, &c->d_dbg_in, &c->d_dbg_out}) b->release();
+        for (DeviceBuf* b : {&c->d_out, &c->d_out8, &c->d_out_index, &c->d_pixels, &c->d_jitter, &c->d_wave_counts, &c->d_dbg_in, &c->d_dbg_out, &c->d_aov_pixels, &c->d_aov_jitter, &c->d_aov_out, &c->d_aov_ctr}) b->release();
         for (auto& f : c->slots) f.release();
         c->prog.release();
         if (c->classified) (void)hipEventDestroy(c->classified);
         for (hipEvent_t& e : c->acc_free) if (e) { (void)hipEventDestroy(e); e = nullptr; }
+        for (hipEvent_t& e : c->aov_ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
         if (c->side) (void)hipStreamDestroy(c->side);
         if (c->tail) (void)hipStreamDestroy(c->tail);
         for (hipStream_t m : c->more_mains) if (m) (void)hipStreamDestroy(m);
@@ -651,6 +657,8 @@ static int32_t upload_scene(ft_context* c) {
     put(kCullRows, f.cull_rows, S.cull_rows); put(kItemPc, f.item_pc, S.item_pc); put(kWide, f.wide, S.wide); put(kMeshWide, f.mesh_wide, S.mesh_wide);
     put(kCoarse, f.coarse_boxes, S.coarse_boxes); put(kTriOrig, f.tri_orig, S.tri_orig);
     put(kLsPairs, f.ls_pairs, S.ls_pairs); put(kLsNodes, f.ls_nodes, S.ls_nodes); put(kLsTris, f.ls_tris, S.ls_tris);
+    if (rc == FT_OK) rc = upload(c, c->d_scene[kTriSrc], f.tri_src);
+    if (rc == FT_OK) rc = upload(c, c->d_scene[kRunNodes], f.run_nodes);
     if (rc != FT_OK) return rc;
     for (auto& F : c->slots) { if ((rc = ensure(c, F.d_fc, sizeof(ftk::FrameCounters))) != FT_OK) return rc; F.fc_clean = false; }
     c->zero_signature[0] = c->zero_signature[1] = 0;
@@ -661,7 +669,8 @@ static int32_t upload_scene(ft_context* c) {
         for (const fth::FlatScene::BvhJob& j : f.bvh_jobs) {
             const DeviceBuf* B = c->d_scene;
             const ftk::LbvhTarget t{B[kTris].as<double>(), j.first_global, j.n, B[kNodes].as<ftd::BspNode>(), j.node_base, B[kBspLeaves].as<ftd::BspLeaf>(), j.leaf_base,
-                                    B[kTriOrig].as<uint32_t>(), j.tri_base, B[kWide].as<double>(), j.wide_base, B[kCoarse].as<float>() + 6 * (size_t)j.coarse_first, j.coarse_count};
+                                    B[kTriOrig].as<uint32_t>(), j.tri_base, B[kWide].as<double>(), j.wide_base, B[kCoarse].as<float>() + 6 * (size_t)j.coarse_first, j.coarse_count,
+                                    B[kTriSrc].as<uint32_t>()};
             uint32_t height = 0;
             FT_HIP(c, ftk::build_lbvh(c->stream, t, &height, c->opt.bvh_builder == 1 ? 0 : 1));
             // height 0: a non-finite coordinate; > 40: deeper than the packet walk's 64-entry stack allows (3 entries per 4-wide level)
@@ -692,6 +701,7 @@ static int32_t upload_scene(ft_context* c) {
     c->blocks_primary = ftk::occupancy_blocks_primary(lds, &c->variant_primary);
     c->blocks_bounce = ftk::occupancy_blocks_bounce(lds, c->variant);
     c->blocks_resolve = ftk::occupancy_blocks_resolve();
+    c->blocks_aov = ftk::occupancy_blocks_aov(lds, c->variant);
     c->committed = true;
     ++c->commit_serial; c->staged_hint = -1;
     return FT_OK;
@@ -1537,6 +1547,143 @@ int32_t ft_get_kernel_times(ft_context* c, double ms[5], int32_t launches[5]) {
     for (int k = 0; k < kStages; ++k) { ms[k] = c->k_ms[k]; launches[k] = c->k_launches[k]; }
     for (ft_context* p : c->peers) for (int k = 0; k < kStages; ++k) { ms[k] = std::max(ms[k], p->k_ms[k]); launches[k] = std::max(launches[k], p->k_launches[k]); }   // the slowest device's
     return FT_OK;
+}
+
+// ------------------------------------------------------------------------------------------ per-pixel surface buffers
+// ft_render_aov: the hit of one sample's geometry ray per tile pixel (functracer_hip.h).  The call keeps to buffers of its own - pixel
+// list, jitter pattern, planes, counters - so the frame buffer, the cached pixel list, the zero-fill and level-hint history and a
+// progressive accumulation stay as they were.  The list is ft_render's (8x8 blocks in Z order where the rects allow), cut into windows
+// of "chunk_samples" entries; per window one k_aov writes the requested planes by list position and the host scatters them into the
+// caller's frame-shaped planes.
+namespace {
+struct AovPlanes { int64_t off[8]; int width[8]; size_t bytes_per_entry; };   // t, p, n, colour, material, leaf, node, triangle
+AovPlanes aov_planes(const ft_aov& o, int64_t per) {
+    AovPlanes a{};
+    const void* want[8] = {o.t, o.p, o.n, o.colour, o.material, o.leaf, o.node, o.triangle};
+    const int width[8] = {1, 3, 3, 3, 3, 1, 1, 1};
+    int64_t at = 0;                                                 // bytes; doubles first, then the 32-bit planes
+    for (int k = 0; k < 8; ++k) {
+        a.off[k] = -1; a.width[k] = width[k];
+        if (!want[k]) continue;
+        a.off[k] = at;
+        at += per * width[k] * (k < 5 ? 8 : 4);
+        a.bytes_per_entry += (size_t)width[k] * (k < 5 ? 8 : 4);
+    }
+    return a;
+}
+} // namespace
+
+static int32_t aov_single(ft_context* c, const RenderRequest& q, int32_t sample, const ft_aov& o, ft_stats* stats) {
+    if (!need_device(c)) return FT_ERR_NO_DEVICE;
+    if (!c->committed) { c->err = "scene not committed (ft_scene_commit)"; return FT_ERR_STATE; }
+    const auto wall0 = std::chrono::steady_clock::now();
+    FT_HIP(c, hipSetDevice(c->device));
+    int32_t rc;
+    if (any_pending(c) && (rc = retire_pending(c, nullptr)) != FT_OK) return rc;
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    std::vector<uint32_t> px;
+    (void)list_pixels(clip_rects(q), q.res_h, px);
+    const int64_t n_pix = (int64_t)px.size();
+    if (n_pix == 0) return FT_OK;
+    int64_t per = std::max<int64_t>(1, std::min<int64_t>(n_pix, c->opt.chunk_samples));
+    if (per > 64) per -= per % 64;                                  // windows of whole 8x8 blocks
+    const AovPlanes pl = aov_planes(o, per);
+    if ((rc = upload(c, c->d_aov_pixels, px)) != FT_OK) return rc;
+    if ((rc = upload(c, c->d_aov_jitter, std::vector<double>(q.jitter_xy, q.jitter_xy + 2 * (size_t)q.spp))) != FT_OK) return rc;
+    if ((rc = ensure(c, c->d_aov_out, (size_t)per * pl.bytes_per_entry)) != FT_OK) return rc;
+    if ((rc = ensure(c, c->d_aov_ctr, 2 * sizeof(unsigned long long))) != FT_OK) return rc;
+    FT_HIP(c, hipMemsetAsync(c->d_aov_ctr.p, 0, 2 * sizeof(unsigned long long), c->stream));
+    const ftk::Camera cam = make_camera(*q.cam, q.res_h, q.res_v);
+    const size_t lds = lds_bytes_for(c->flat);
+    const ftk::Launch L{c->stream, c->n_cu * c->blocks_aov, lds, c->variant};
+    const ftk::AovSource src{c->d_scene[kTriSrc].as<uint32_t>(), c->d_scene[kRunNodes].as<int32_t>()};
+    char* const dev = c->d_aov_out.as<char>();
+    std::vector<char> host((size_t)per * pl.bytes_per_entry);
+    hipEvent_t* const ev = c->aov_ev;
+    for (int k = 0; k < 2; ++k) if (!ev[k]) FT_HIP(c, hipEventCreate(&ev[k]));
+    double kernel_ms = 0.0;
+    int32_t n_launches = 0;
+    void* const dst[8] = {o.t, o.p, o.n, o.colour, o.material, o.leaf, o.node, o.triangle};
+    for (int64_t p0 = 0; p0 < n_pix; p0 += per) {
+        const uint32_t n = (uint32_t)std::min<int64_t>(per, n_pix - p0);
+        ftk::Primary gen{cam, c->d_aov_pixels.as<uint32_t>(), c->d_aov_jitter.as<double>(), (uint32_t)p0, n, q.spp, (uint32_t)q.res_h, (unsigned long long)q.seed,
+                         1.0 / (double)n, 1.0 / (double)q.res_h, nullptr, nullptr};
+        gen.group_log2 = 0;
+        auto plane = [&](int k) -> void* { return pl.off[k] < 0 ? nullptr : dev + pl.off[k]; };
+        const ftk::AovOut out{static_cast<double*>(plane(0)), static_cast<double*>(plane(1)), static_cast<double*>(plane(2)), static_cast<double*>(plane(3)),
+                              static_cast<double*>(plane(4)), static_cast<int32_t*>(plane(5)), static_cast<int32_t*>(plane(6)), static_cast<int32_t*>(plane(7)), n};
+        FT_HIP(c, hipEventRecord(ev[0], c->stream));
+        ftk::launch_aov(L, c->dev_scene, gen, (uint32_t)sample, src, out, c->d_aov_ctr.as<unsigned long long>());
+        FT_HIP(c, hipGetLastError());
+        FT_HIP(c, hipEventRecord(ev[1], c->stream));
+        ++n_launches;
+        for (int k = 0; k < 8; ++k) if (pl.off[k] >= 0) {          // a channel's planes lie back to back: n entries apart within the window
+            const size_t esz = k < 5 ? 8 : 4;
+            FT_HIP(c, hipMemcpyAsync(host.data() + pl.off[k], dev + pl.off[k], (size_t)n * pl.width[k] * esz, hipMemcpyDeviceToHost, c->stream));
+        }
+        FT_HIP(c, hipStreamSynchronize(c->stream));
+        float ms = 0.0f;
+        if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) kernel_ms += ms;
+        for (int k = 0; k < 8; ++k) if (pl.off[k] >= 0) {          // into the caller's planes: frame layout, row 0 = top, w components per pixel
+            const int w = pl.width[k];
+            const char* src_k = host.data() + pl.off[k];
+            if (k < 5) {
+                const double* s = reinterpret_cast<const double*>(src_k);
+                double* d = static_cast<double*>(dst[k]);
+                for (uint32_t i = 0; i < n; ++i) { const size_t id = px[(size_t)p0 + i]; for (int a = 0; a < w; ++a) d[id * w + a] = s[(size_t)a * n + i]; }
+            } else {
+                const int32_t* s = reinterpret_cast<const int32_t*>(src_k);
+                int32_t* d = static_cast<int32_t*>(dst[k]);
+                for (uint32_t i = 0; i < n; ++i) d[px[(size_t)p0 + i]] = s[i];
+            }
+        }
+    }
+    unsigned long long ctr[2] = {0, 0};
+    FT_HIP(c, hipMemcpy(ctr, c->d_aov_ctr.p, sizeof ctr, hipMemcpyDeviceToHost));
+    if (ctr[1]) { c->err = "CSG hit list overflow"; return FT_ERR_OVERFLOW; }
+    if (stats) {
+        stats->rays_primary = (uint64_t)n_pix; stats->hits_primary = ctr[0];
+        stats->kernel_ms = kernel_ms; stats->n_launches = n_launches;
+        stats->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+    }
+    return FT_OK;
+}
+
+static int32_t aov_frame(ft_context* c, const RenderRequest& q, int32_t sample, const ft_aov& o, ft_stats* stats) {
+    if (c->peers.empty()) return aov_single(c, q, sample, o, stats);
+    if (!c->committed) { c->err = "scene not committed (ft_scene_commit)"; return FT_ERR_STATE; }
+    const auto wall0 = std::chrono::steady_clock::now();
+    const std::vector<ft_context*> devs = devices(c);
+    const std::vector<std::vector<ft_rect>> share = band_shares(q, devs.size());   // ft_render's 8-row bands: each device writes its rows
+    std::vector<int32_t> rcs(devs.size(), FT_OK);
+    std::vector<ft_stats> sts(devs.size());
+    on_every_device(c, std::vector<bool>(devs.size(), true), [&](size_t d) {
+        std::memset(&sts[d], 0, sizeof(ft_stats));
+        if (share[d].empty()) return;
+        RenderRequest qd = q;
+        qd.tiles = share[d].data(); qd.n_tiles = (int32_t)share[d].size();
+        rcs[d] = aov_single(devs[d], qd, sample, o, &sts[d]);
+    });
+    for (size_t d = 0; d < devs.size(); ++d) if (rcs[d] != FT_OK) { if (d) c->err = devs[d]->err; return rcs[d]; }
+    if (stats) {
+        std::memset(stats, 0, sizeof *stats);
+        for (auto& s : sts) add_stats(stats, s);
+        stats->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+    }
+    return FT_OK;
+}
+
+int32_t ft_render_aov(ft_context* c, const ft_camera* cam, int32_t res_h, int32_t res_v, int32_t spp, const double* jitter_xy,
+                      int32_t sample, uint64_t seed, const ft_rect* tiles, int32_t n_tiles, const ft_aov* out, ft_stats* stats) {
+    if (!c) return FT_ERR_INVALID;
+    const RenderRequest q{cam, res_h, res_v, spp, jitter_xy, 0, seed, tiles, n_tiles, 0};
+    int32_t rc = check_request(c, q);
+    if (rc != FT_OK) return rc;
+    if (spp == 0) { c->err = "ft_render_aov: corner sampling (spp == 0) has no per-sample geometry ray"; return FT_ERR_UNSUPPORTED; }
+    if (sample < 0 || sample >= spp) { c->err = "ft_render_aov: sample outside [0, spp)"; return FT_ERR_INVALID; }
+    if (!out || !(out->t || out->p || out->n || out->colour || out->material || out->leaf || out->node || out->triangle)) { c->err = "ft_render_aov: no channel requested"; return FT_ERR_INVALID; }
+    if (!need_device(c)) return FT_ERR_NO_DEVICE;
+    return with_growing_hit_lists(c, [&] { return aov_frame(c, q, sample, *out, stats); });
 }
 
 // ------------------------------------------------------------------------------------------ debug / tests

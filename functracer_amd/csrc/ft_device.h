@@ -192,8 +192,23 @@ struct LbvhTarget {
     uint32_t* tri_orig; uint32_t tri_base;
     double* wide; uint32_t wide_base;
     float* coarse; uint32_t coarse_count;
+    uint32_t* tri_src;                 // per triangle record: its input face (ft_flat.h); the sorted copies take their leaf record's
 };
 hipError_t build_lbvh(hipStream_t stream, const LbvhTarget& t, uint32_t* height, int kind = 1);   // kind 0: linear BVH, 1: binned surface-area tree over the Morton order
+
+// Per-pixel surface buffers (ft_render_aov): for every entry of the chunk's pixel list (gen: pix_base, n_pix; one sample plane) the
+// closest hit of the geometry ray of sample `sample` - primary_ray_from exactly as k_primary calls it, then slightOffset - and what
+// the shaders would see there.  Planes are struct-of-arrays by list position: out.<x>[i] for entry pix_base + i, the 3-vectors as
+// three planes of `stride` entries (x, y, z).  A null plane is not written.  counters[0] += hits, counters[1] += rays whose hit
+// list overflowed.
+struct AovOut {
+    double *t, *p, *n, *colour, *material;
+    int32_t *leaf, *node, *triangle;
+    uint32_t stride;
+};
+struct AovSource { const uint32_t* tri_src; const int32_t* run_nodes; };   // the tables only k_aov reads (ft_flat.h)
+void launch_aov(const Launch& L, const DevScene& S, const Primary& gen, uint32_t sample, const AovSource& src, const AovOut& out, unsigned long long* counters);
+int occupancy_blocks_aov(size_t lds_bytes, int variant);
 
 // Debug: closest hit / blocked for arbitrary rays (no slightOffset).
 void launch_debug_closest(const Launch& L, const DevScene& S, const double* o, const double* d, uint32_t n,

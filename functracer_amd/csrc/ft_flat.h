@@ -43,7 +43,10 @@ struct Leaf {
     uint32_t material;
     uint32_t mesh;         // index into meshes[] for LK_MESH
     uint32_t ls_pairs;     // first light-space shadow pair record of the leaf (one per light), ~0u = none (see kLsPairDoubles)
-    uint32_t pad[3];
+    uint32_t pad[3];       // read by k_aov only: [0] the builder node (ft_sg_primitive / _triangle / _bsp_mesh) the leaf was made from, or
+                           // ~0u for a run of bare triangles merged into one mesh; [1] runs: 1 + offset of their nodes in run_nodes (one per
+                           // triangle, in list order), else 0
+
 };
 
 struct Material {          // Ray.fs:4-10; 64 bytes
@@ -126,6 +129,8 @@ struct BspNode {           // 64 bytes; BspMesh.fs:12-19 (also used for BVH node
 struct BspLeaf { uint32_t first_tri, n_tris; };
 // Triangles: 9 doubles each = v0, edge1 = v1 - v0, edge2 = v2 - v0 (Triangle.fs:45-46 evaluated once on the host).
 // tri_orig[k] = index of the same triangle in the mesh's reference-order list (identity except inside BVH leaves).
+// tri_src[k] = index of the input face (the `tris` handed to ft_sg_bsp_mesh) the record is, or was cut from by the BSP build; read by
+// k_aov only.  Every builder gives the same value for the same record: BVH copies take it from the leaf record they copy.
 //
 // The BVH is an acceleration structure the reference does not have.  A top-level Leaf is "every triangle,
 // in list order" (BspMesh.fs:53, 95-97); closest-hit / any-hit over that list only depend on the set of hits

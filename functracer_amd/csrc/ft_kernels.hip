@@ -2479,7 +2479,92 @@ __global__ __launch_bounds__(kBlock) void k_debug_blocked(DevScene Sg, const dou
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// k_aov: per-pixel surface buffers (ft_render_aov).  A wave takes 64 consecutive entries of the chunk's pixel list - one 8x8 block of a
+// tiled list, as k_primary's batches of a one-sample plane are (plain slot numbering: slot = list entry) - and generates the geometry
+// ray of sample `sample` with k_primary's own primary_ray_from (jitter offset `sample`, depth-of-field stream pixel_id * spp + sample)
+// and slightOffset.  The closest hit is the coherent packet walk k_primary uses; a hit then goes through surface_at / material_at and,
+// in the FANCY variants, the texture lookup: no shadow rays, no shaders, no spawn.  Every requested plane is stored by list position,
+// 512 contiguous bytes per wave and plane.
+struct AovArgs {
+    DevScene S; Primary gen; AovSource src; AovOut out;
+    unsigned long long* counters;
+    uint32_t sample;
+};
+template <bool FANCY, bool MESH>
+__global__ __launch_bounds__(kBlock, FANCY ? 2 : 4) void k_aov(AovArgs) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    const FT_CONST AovArgs* K = kernel_args<AovArgs>();
+    const Scene S = scene_view(K->S);
+    const uint32_t n = K->gen.n_pix;
+    const uint32_t B = 64u / (uint32_t)S.lane_fold, n_batches = (n + B - 1) / B;   // folded lanes lend their LDS columns to the live ones (HitList)
+    const bool coherent = K->S.coherent_waves != 0;
+    unsigned long long n_hit_wave = 0, n_ovf_wave = 0;
+    const uint32_t wave = blockIdx.x * (kBlock / 64) + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / 64));
+    for (uint32_t b = wave; b < n_batches; b += gridDim.x * (kBlock / 64)) {
+        const uint32_t i = b * B + lane_id();
+        const bool active = lane_id() < B && i < n;
+        Ray ro{0, 0, 0, 0, 0, 0};
+        if (active) {
+            const FT_CONST AovArgs* Kb = fresh(K);
+            const Ray r = primary_ray_from(&Kb->gen, Kb->sample, list_pixel(&Kb->gen, Kb->gen.pix_base + i));
+            ro = {r.ox + 0.0001 * r.dx, r.oy + 0.0001 * r.dy, r.oz + 0.0001 * r.dz, r.dx, r.dy, r.dz};   // slightOffset (Shading.fs:129)
+        }
+        Query<false> q = Query<false>::closest(active);
+        bool overflow;
+        trace<false, MESH>(S, ro, q, lds, overflow, coherent);
+        n_ovf_wave += (unsigned long long)__popcll(__ballot(overflow && active));
+        const bool hit = active && q.id0 != ID_MISS;
+        n_hit_wave += (unsigned long long)__popcll(__ballot(hit));
+        Surface sf{{0, 0, 0}, {0, 0, 0}, 0, 0.0, 0.0};
+        double col[3] = {0.0, 0.0, 0.0}, mt[3] = {0.0, 0.0, 0.0};
+        int32_t leaf = -1, node = -1, tri = -1;
+        if (hit) {
+            sf = surface_at<FANCY>(S, ro, q.best_t, q.id0, q.id1);
+            MaterialV mat = material_at(S, sf.material);
+            if (FANCY) { if (mat.texture >= 0) textured_colour(S, mat, sf.u, sf.v, mat.colour); }
+            col[0] = mat.colour[0]; col[1] = mat.colour[1]; col[2] = mat.colour[2];
+            mt[0] = mat.reflectance; mt[1] = mat.shineyness; mt[2] = mat.roughness;
+            const uint32_t l = q.id0 & ID_LEAF_MASK;
+            cup W = reinterpret_cast<cup>(S.leaves + 16ull * l);            // ftd::Leaf as words: kind at 24, pad[0] / pad[1] at 29 / 30
+            const FT_CONST AovArgs* Kc = fresh(K);
+            const uint32_t run = W[30];
+            leaf = (int32_t)l; node = (int32_t)W[29];
+            if (MESH && W[24] == LK_MESH) {
+                const uint32_t face = Kc->src.tri_src[q.id1];
+                if (run) { node = Kc->src.run_nodes[run - 1u + face]; tri = 0; }   // a run of bare triangles: each is its own ft_sg_triangle
+                else tri = (int32_t)face;
+            }
+        }
+        if (active) {
+            const FT_CONST AovArgs* Ko = fresh(K);
+            const size_t st = Ko->out.stride;
+            if (double* o = Ko->out.t) o[i] = hit ? q.best_t : __builtin_inf();
+            if (double* o = Ko->out.p) { o[i] = sf.p.x; o[st + i] = sf.p.y; o[2 * st + i] = sf.p.z; }
+            if (double* o = Ko->out.n) { o[i] = sf.n.x; o[st + i] = sf.n.y; o[2 * st + i] = sf.n.z; }
+            if (double* o = Ko->out.colour) { o[i] = col[0]; o[st + i] = col[1]; o[2 * st + i] = col[2]; }
+            if (double* o = Ko->out.material) { o[i] = mt[0]; o[st + i] = mt[1]; o[2 * st + i] = mt[2]; }
+            if (int32_t* o = Ko->out.leaf) o[i] = leaf;
+            if (int32_t* o = Ko->out.node) o[i] = node;
+            if (int32_t* o = Ko->out.triangle) o[i] = tri;
+        }
+    }
+    unsigned long long* ctr = fresh(K)->counters;
+    wave_add(&ctr[0], n_hit_wave);
+    wave_add(&ctr[1], n_ovf_wave);
+}
+
 } // namespace
+
+typedef void (*AovKernel)(AovArgs);
+static AovKernel aov_variant(int v) {                              // bit 0 FANCY, bit 2 MESH (Launch::variant); soft lights play no part
+    switch (v & 5) {
+        case 0: return k_aov<false, false>;
+        case 1: return k_aov<true, false>;
+        case 4: return k_aov<false, true>;
+        default: return k_aov<true, true>;
+    }
+}
 
 typedef void (*PrimaryKernel)(PrimaryArgs);
 static PrimaryKernel primary_variant(int v) {                      // bit 0 FANCY, bit 1 SOFT, bit 2 MESH, bit 3: the lean variant built for five workgroups per CU
@@ -2563,6 +2648,12 @@ void launch_debug_blocked(const Launch& L, const DevScene& S, const double* o, c
     hipLaunchKernelGGL(k_debug_blocked, dim3(blocks_for(n, L.grid)), dim3(kBlock), L.lds_bytes, L.stream, S, o, d, max_dist, n, blocked, overflow);
 }
 
+void launch_aov(const Launch& L, const DevScene& S, const Primary& gen, uint32_t sample, const AovSource& src, const AovOut& out, unsigned long long* counters) {
+    const AovArgs a{S, gen, src, out, counters, sample};
+    const uint32_t waves = (gen.n_pix + 63u) / 64u * (uint32_t)S.lane_fold;   // batches of 64 / lane_fold entries
+    hipLaunchKernelGGL(aov_variant(L.variant), dim3(blocks_for(waves * 64u, L.grid)), dim3(kBlock), L.lds_bytes, L.stream, a);
+}
+
 } // namespace ftk
 
 // Resident workgroups per CU for the persistent grids (register- and LDS-limited).
@@ -2580,6 +2671,11 @@ int occupancy_blocks_primary(size_t lds_bytes, int* variant) {
 int occupancy_blocks_resolve() {
     int n = 0;
     return (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_resolve, kBlock, 0) == hipSuccess && n > 0) ? clamp_blocks(n) : 2;
+}
+int occupancy_blocks_aov(size_t lds_bytes, int variant) {
+    int n = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, aov_variant(variant), kBlock, lds_bytes) != hipSuccess) n = 1;
+    return clamp_blocks(n);
 }
 int occupancy_blocks_bounce(size_t lds_bytes, int variant) {
     int n = 0;

@@ -158,8 +158,12 @@ struct Flattener {
         return (uint32_t)out.materials.size() - 1;
     }
 
-    void emit_leaf(uint32_t kind, uint32_t mesh, const WalkCtx& c, bool flip, bool in_csg, int max_hits) {
+    // `node`: the builder node the leaf stands for (Leaf::pad[0]); `run`: the builder nodes of a run of bare triangles, one per
+    // triangle of the leaf's mesh, or null (Leaf::pad[1], ft_flat.h).
+    void emit_leaf(uint32_t kind, uint32_t mesh, const WalkCtx& c, bool flip, bool in_csg, int max_hits, int32_t node, const std::vector<int32_t>* run = nullptr) {
         ftd::Leaf L{};
+        L.pad[0] = (uint32_t)node;
+        if (run) { L.pad[1] = (uint32_t)out.run_nodes.size() + 1u; out.run_nodes.insert(out.run_nodes.end(), run->begin(), run->end()); }
         for (int r = 0; r < 3; ++r) for (int k = 0; k < 4; ++k) L.w2m[4 * r + k] = c.w2m.a[4 * r + k];
         L.kind = kind; L.mesh = mesh;
         L.material = resolve_material(c);
@@ -324,14 +328,14 @@ struct Flattener {
                 static const uint32_t kind_of[8] = {ftd::LK_CIRCLE, ftd::LK_SQUARE, ftd::LK_CUBE, ftd::LK_SPHERE, ftd::LK_PLANE, ftd::LK_CONE, ftd::LK_SOLIDCYL, ftd::LK_CYLINDER};
                 static const int max_hits[8] = {1, 1, 6, 2, 1, 2, 4, 2};
                 ItemMark im = begin_item(in_csg);
-                emit_leaf(kind_of[n.prim], 0, c, false, in_csg, max_hits[n.prim]);
+                emit_leaf(kind_of[n.prim], 0, c, false, in_csg, max_hits[n.prim], id);
                 end_item(im);
                 break;
             }
             case GraphNode::TriangleP: {
                 uint32_t mesh = mesh_for(-1, n.tri, 1, 0);
                 ItemMark im = begin_item(in_csg);
-                if (status == FT_OK) emit_leaf(ftd::LK_MESH, mesh, c, false, in_csg, 1);
+                if (status == FT_OK) emit_leaf(ftd::LK_MESH, mesh, c, false, in_csg, 1, id);
                 end_item(im);
                 break;
             }
@@ -340,7 +344,7 @@ struct Flattener {
                 ItemMark im = begin_item(in_csg);
                 if (status == FT_OK) {
                     if (in_csg) out.mesh_under_csg = true;
-                    emit_leaf(ftd::LK_MESH, mesh, c, false, in_csg, g.csg_mesh_capacity);
+                    emit_leaf(ftd::LK_MESH, mesh, c, false, in_csg, g.csg_mesh_capacity, id);
                 }
                 end_item(im);
                 break;
@@ -369,12 +373,13 @@ struct Flattener {
                     const GraphNode& ch = g.nodes[n.children[i]];
                     if (ch.kind == GraphNode::TriangleP) {
                         std::vector<double> run;
+                        std::vector<int32_t> run_ids;
                         while (i < n.children.size() && g.nodes[n.children[i]].kind == GraphNode::TriangleP) {
-                            const double* t = g.nodes[n.children[i]].tri; run.insert(run.end(), t, t + 9); ++i;
+                            const double* t = g.nodes[n.children[i]].tri; run.insert(run.end(), t, t + 9); run_ids.push_back(n.children[i]); ++i;
                         }
                         uint32_t mesh = mesh_for(-1, run.data(), (int64_t)(run.size() / 9), 0);
                         ItemMark im = begin_item(in_csg);
-                        if (status == FT_OK) emit_leaf(ftd::LK_MESH, mesh, c, false, in_csg, (int)std::min<size_t>(run.size() / 9, (size_t)g.csg_mesh_capacity));
+                        if (status == FT_OK) emit_leaf(ftd::LK_MESH, mesh, c, false, in_csg, (int)std::min<size_t>(run.size() / 9, (size_t)g.csg_mesh_capacity), -1, &run_ids);
                         end_item(im);
                     } else {
                         walk(n.children[i], c, in_csg); ++i;
@@ -443,11 +448,12 @@ int32_t SceneGraph::flatten(FlatScene& out, std::string& err) const {
     if (out.lights.size() > 16) { err = "more than 16 lights are not supported on the device path"; return FT_ERR_UNSUPPORTED; }
     if (light_space_shadows) build_light_space(out);
     else for (auto& L : out.leaves) L.ls_pairs = ~0u;
-    if (out.tris.empty()) { out.tris.assign(9, 0.0); out.tri_orig.assign(1, 0u); }   // keep device pointers non-null
+    if (out.tris.empty()) { out.tris.assign(9, 0.0); out.tri_orig.assign(1, 0u); out.tri_src.assign(1, 0u); }   // keep device pointers non-null
     if (out.ls_pairs.empty()) out.ls_pairs.assign(ftd::kLsPairDoubles, 0.0);
     if (out.ls_nodes.empty()) out.ls_nodes.assign(ftd::kLsNodeWords, 0u);
     if (out.ls_tris.empty()) out.ls_tris.assign(9, 0.0);
     if (out.culls.empty()) out.culls.push_back(ftd::CullRecord{});
+    if (out.run_nodes.empty()) out.run_nodes.assign(1, -1);
     return FT_OK;
 }
 
@@ -455,7 +461,7 @@ int32_t SceneGraph::flatten(FlatScene& out, std::string& err) const {
 namespace {
 
 struct P3 { double x, y, z; };
-struct Tri3 { P3 a, b, c; };
+struct Tri3 { P3 a, b, c; uint32_t src; };   // src: index of the input face the triangle is (a piece of)
 struct SplitPlane { P3 p0, n; };
 
 inline double dot3(P3 a, P3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
@@ -479,12 +485,12 @@ bool edge_cut(const SplitPlane& pl, P3 from, P3 to, P3& out) {
 
 // Triangle.slice' (Triangle.fs:13-22): `lone` is alone on its side; outputs one piece on the lone side
 // and two on the other, winding preserved.
-bool cut_lone(const SplitPlane& pl, P3 lone, P3 q, P3 r, std::vector<Tri3>& lone_side, std::vector<Tri3>& pair_side) {
+bool cut_lone(const SplitPlane& pl, P3 lone, P3 q, P3 r, uint32_t src, std::vector<Tri3>& lone_side, std::vector<Tri3>& pair_side) {
     P3 lq, lr, ql, rl;
     if (!edge_cut(pl, lone, q, lq) || !edge_cut(pl, lone, r, lr) || !edge_cut(pl, q, lone, ql) || !edge_cut(pl, r, lone, rl)) return false;
-    lone_side.push_back({lone, lq, lr});
-    pair_side.push_back({ql, q, r});
-    pair_side.push_back({r, rl, ql});
+    lone_side.push_back({lone, lq, lr, src});                                   // every piece keeps the input face it was cut from
+    pair_side.push_back({ql, q, r, src});
+    pair_side.push_back({r, rl, ql, src});
     return true;
 }
 
@@ -492,9 +498,9 @@ bool cut_lone(const SplitPlane& pl, P3 lone, P3 q, P3 r, std::vector<Tri3>& lone
 bool split_triangle(const SplitPlane& pl, const Tri3& t, std::vector<Tri3>& above, std::vector<Tri3>& below) {
     const bool ua = above_plane(pl, t.a), ub = above_plane(pl, t.b), uc = above_plane(pl, t.c);
     if (ua == ub && ub == uc) { (ua ? above : below).push_back(t); return true; }
-    if (ua == ub) return cut_lone(pl, t.c, t.a, t.b, uc ? above : below, uc ? below : above);   // c is alone
-    if (ua == uc) return cut_lone(pl, t.b, t.c, t.a, ub ? above : below, ub ? below : above);   // b is alone
-    return cut_lone(pl, t.a, t.b, t.c, ua ? above : below, ua ? below : above);                 // a is alone
+    if (ua == ub) return cut_lone(pl, t.c, t.a, t.b, t.src, uc ? above : below, uc ? below : above);   // c is alone
+    if (ua == uc) return cut_lone(pl, t.b, t.c, t.a, t.src, ub ? above : below, ub ? below : above);   // b is alone
+    return cut_lone(pl, t.a, t.b, t.c, t.src, ua ? above : below, ua ? below : above);                 // a is alone
 }
 
 struct BspBuilder {
@@ -508,6 +514,7 @@ struct BspBuilder {
         for (auto& t : ts) {                                                    // v0, edge1, edge2 (Triangle.fs:45-46)
             const double rec[9] = {t.a.x, t.a.y, t.a.z, t.b.x - t.a.x, t.b.y - t.a.y, t.b.z - t.a.z, t.c.x - t.a.x, t.c.y - t.a.y, t.c.z - t.a.z};
             out.tri_orig.push_back((uint32_t)(out.tris.size() / 9));
+            out.tri_src.push_back(t.src);
             out.tris.insert(out.tris.end(), rec, rec + 9);
         }
         out.bsp_leaves.push_back(L);
@@ -527,6 +534,7 @@ struct BspBuilder {
                 const Tri3& t = ts[idx[k]];
                 const double rec[9] = {t.a.x, t.a.y, t.a.z, t.b.x - t.a.x, t.b.y - t.a.y, t.b.z - t.a.z, t.c.x - t.a.x, t.c.y - t.a.y, t.c.z - t.a.z};
                 out.tri_orig.push_back(first_global + idx[k]);
+                out.tri_src.push_back(t.src);
                 out.tris.insert(out.tris.end(), rec, rec + 9);
             }
             out.bsp_leaves.push_back(L);
@@ -732,7 +740,7 @@ int32_t build_bsp(const double* tris_abc, int64_t n_tris, int32_t depth, FlatSce
     std::vector<Tri3> ts((size_t)n_tris);
     for (int64_t i = 0; i < n_tris; ++i) {
         const double* v = tris_abc + 9 * i;
-        ts[(size_t)i] = {{v[0], v[1], v[2]}, {v[3], v[4], v[5]}, {v[6], v[7], v[8]}};
+        ts[(size_t)i] = {{v[0], v[1], v[2]}, {v[3], v[4], v[5]}, {v[6], v[7], v[8]}, (uint32_t)i};
     }
     BspBuilder b{out, err};
     int32_t root = (n_tris == 0) ? b.make_leaf(ts) : b.compile(depth, ts, 0);   // an empty mesh is an empty group
@@ -750,6 +758,7 @@ int32_t build_bsp(const double* tris_abc, int64_t n_tris, int32_t depth, FlatSce
         out.bsp_leaves.resize(out.bsp_leaves.size() + (2 * (size_t)n - 1), ftd::BspLeaf{0, 0});
         out.tris.resize(out.tris.size() + 9 * (size_t)n, 0.0);
         out.tri_orig.resize(out.tri_orig.size() + n, 0u);
+        out.tri_src.resize(out.tri_src.size() + n, 0u);                        // k_bvh_emit copies them from the leaf's records
         out.wide.resize(out.wide.size() + (size_t)ftd::kWideNodeDoubles * (n - 1), 0.0);
         for (uint32_t k = 0; k < job.coarse_count; ++k) { const float all[6] = {-3e38f, -3e38f, -3e38f, 3e38f, 3e38f, 3e38f}; out.coarse_boxes.insert(out.coarse_boxes.end(), all, all + 6); }   // until the build: everything
         out.bvh_jobs.push_back(job);
@@ -1036,7 +1045,7 @@ void build_light_space(FlatScene& out) {
 
 int32_t slice_triangle(const double p0[3], const double n[3], const double tri[9], std::vector<double>& above, std::vector<double>& below, std::string& err) {
     SplitPlane pl{{p0[0], p0[1], p0[2]}, {n[0], n[1], n[2]}};
-    Tri3 t{{tri[0], tri[1], tri[2]}, {tri[3], tri[4], tri[5]}, {tri[6], tri[7], tri[8]}};
+    Tri3 t{{tri[0], tri[1], tri[2]}, {tri[3], tri[4], tri[5]}, {tri[6], tri[7], tri[8]}, 0u};
     std::vector<Tri3> a, b;
     if (!split_triangle(pl, t, a, b)) { err = "edge parallel to plane"; return FT_ERR_BUILD; }
     auto dump = [](const std::vector<Tri3>& v, std::vector<double>& o) {

@@ -40,6 +40,8 @@ struct FlatScene {
     std::vector<ftd::BspLeaf> bsp_leaves;
     std::vector<double> tris;         // 9 per triangle: v0, e1, e2
     std::vector<uint32_t> tri_orig;   // 1 per triangle (see ft_flat.h)
+    std::vector<uint32_t> tri_src;    // 1 per triangle: the index of its face in the list the mesh was built from (ft_flat.h)
+    std::vector<int32_t> run_nodes;   // the builder nodes of runs of bare triangles, one per triangle (Leaf::pad[1], ft_flat.h)
     std::vector<double> wide;         // 28 doubles per 4-wide BVH node (ft_flat.h), walked by coherent wavefronts
     std::vector<int32_t> mesh_wide;   // per mesh: root of its 4-wide BVH, or INT32_MIN
     std::vector<float> coarse_boxes;  // 6 floats per box (lo, hi; model space, rounded outward): <= 64 boxes per mesh that cover all its triangles

@@ -1,6 +1,9 @@
 // Program.cpp — command-line driver with the flow of Program.fs:51-100: parse the scene,
 // create the image plane + rays + shade + blend (one ft_render call on the GPU), write the PNG.
 //   functracer <scene-file> [output.png]        (2 args: file output; otherwise PNG to stdout)
+//   functracer <scene-file> --intersection-at X Y
+//                                               what is at pixel (X, Y), row 0 = top, on stderr; no image (the device counterpart of
+//                                               printIntersectionAt, Program.fs:33-49: ft_render_aov of a 1x1 tile, jitter offset (0, 0))
 // Phase timings go to stderr like the reference's eprintfn calls (Program.fs:53-67).  Unlike the
 // reference nothing but the PNG is ever written to stdout (its printfn calls at Program.fs:96-97
 // corrupt the PNG stream the GUI reads).
@@ -33,8 +36,30 @@ static const fth_builder kHipBuilder = {
     [](void* c) { return ft_scene_commit((ft_context*)c); },
 };
 
+// The hit record of one pixel (ft_render_aov over a 1x1 tile), printed as `key = value` lines; doubles round-trip (%.17g).
+static int print_intersection_at(ft_context* ctx, const fth_options& opt, int32_t x, int32_t y, uint64_t seed) {
+    if (x < 0 || y < 0 || x >= opt.res_h || y >= opt.res_v) { std::fprintf(stderr, "pixel (%d, %d) outside the %dx%d image\n", x, y, opt.res_h, opt.res_v); return 1; }
+    const size_t n = (size_t)opt.res_h * opt.res_v, at = (size_t)y * opt.res_h + x;
+    std::vector<double> t(n), p(3 * n), nr(3 * n), col(3 * n), mat(3 * n);
+    std::vector<int32_t> leaf(n, -1), node(n, -1), tri(n, -1);
+    const ft_aov aov{t.data(), p.data(), nr.data(), col.data(), mat.data(), leaf.data(), node.data(), tri.data()};
+    const double jitter[2] = {0.0, 0.0};
+    const ft_rect px{x, y, 1, 1};
+    const int32_t rc = ft_render_aov(ctx, &opt.camera, opt.res_h, opt.res_v, 1, jitter, 0, seed, &px, 1, &aov, nullptr);
+    if (rc != FT_OK) { std::fprintf(stderr, "ft_render_aov failed (%d): %s\n", rc, ft_last_error(ctx)); return 1; }
+    std::fprintf(stderr, "intersection at (%d, %d):\n", x, y);
+    if (leaf[at] < 0) { std::fprintf(stderr, "None\n"); return 0; }
+    auto v3 = [&](const char* k, const std::vector<double>& v) { std::fprintf(stderr, "%s = %.17g %.17g %.17g\n", k, v[3 * at], v[3 * at + 1], v[3 * at + 2]); };
+    std::fprintf(stderr, "t = %.17g\n", t[at]);
+    v3("p", p); v3("n", nr); v3("colour", col); v3("material", mat);
+    std::fprintf(stderr, "leaf = %d\nnode = %d\ntriangle = %d\n", leaf[at], node[at], tri[at]);
+    return 0;
+}
+
 int main(int argc, char** argv) {
-    if (argc < 2) { std::fprintf(stderr, "usage: functracer <scene-file> [output.png]\n"); return 2; }
+    if (argc < 2) { std::fprintf(stderr, "usage: functracer <scene-file> [output.png | --intersection-at X Y]\n"); return 2; }
+    const bool pick = argc >= 3 && std::strcmp(argv[2], "--intersection-at") == 0;
+    if (pick && argc != 5) { std::fprintf(stderr, "usage: functracer <scene-file> --intersection-at X Y\n"); return 2; }
     const auto t0 = std::chrono::steady_clock::now();
     auto ms = [&] { return (long)std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t0).count(); };
     std::fprintf(stderr, "Using input file: %s\n", argv[1]);
@@ -44,7 +69,7 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "Parsed input %lims\n", ms());
     fth_options opt;
     fth_scene_options(scene, &opt);
-    if (opt.corner) { std::fprintf(stderr, "samples corner (Image.fs:125-150) is not on the device path yet\n"); return 1; }
+    if (opt.corner && !pick) { std::fprintf(stderr, "samples corner (Image.fs:125-150) is not on the device path yet\n"); return 1; }
 
     int32_t dev = 0;
     if (const char* e = std::getenv("FT_DEVICE")) dev = std::atoi(e);
@@ -57,6 +82,12 @@ int main(int argc, char** argv) {
 
     uint64_t seed = 20260104ull;
     if (const char* e = std::getenv("FT_SEED")) seed = std::strtoull(e, nullptr, 10);
+    if (pick) {
+        const int prc = print_intersection_at(ctx, opt, std::atoi(argv[3]), std::atoi(argv[4]), seed);
+        ft_destroy(ctx);
+        fth_scene_free(scene);
+        return prc;
+    }
     std::vector<double> jitter(2 * (size_t)opt.samples);
     fth_jitter_pattern(seed, opt.samples, jitter.data());
     std::vector<double> rgb((size_t)opt.res_h * opt.res_v * 3);

@@ -286,6 +286,37 @@ int32_t ft_progressive_status(ft_context* ctx, int64_t out[6]);
 /* End the accumulation and free its buffers (FT_OK when there is none). */
 int32_t ft_progressive_end(ft_context* ctx);
 
+/* ---- per-pixel surface buffers (AOVs) ---------------------------------------------------------- */
+/* ft_render_aov reports, for every tile pixel, the hit of the geometry ray of sample `sample` that
+ * ft_render(cam, res_h, res_v, spp, jitter_xy, max_depth, seed, tiles) would trace for that pixel: rayThroughPixel with jitter offset
+ * `sample` (Image.fs:83-89), depth of field with the stream key pixel_id * spp + sample exactly as a frame's sample, then slightOffset
+ * (Shading.fs:129-136).  The buffers therefore describe the surface that sample of the frame shades, bit for bit.  printIntersectionAt
+ * (Program.fs:33-49) intersects the un-offset ray instead: the two disagree only for surfaces closer than 1e-4 * |d| to the eye.
+ * Planes are row-major res_v x res_h, row 0 = top (as ft_render's out_rgb); 3-vectors are 3 doubles per pixel.  Only tile pixels are
+ * written.  Per pixel (hit | miss):
+ *   t         RayIntersection.t along the offset ray                                                   | +inf
+ *   p         the hit point the shaders use                                                            | 0
+ *   n         the normal the shaders see (after transforms and flipNormals)                            | 0
+ *   colour    the material colour after texture and hueShift (what ft_debug_closest reports)           | 0
+ *   material  reflectance, shineyness, roughness                                                       | 0
+ *   leaf      index of the placed primitive in the committed scene (a flattened leaf)                  | -1
+ *   node      the ft_node of the ft_sg_primitive / ft_sg_triangle / ft_sg_bsp_mesh call that made the leaf (a node placed twice
+ *             gives two leaves and one node); under CSG the operand whose surface was hit               | -1
+ *   triangle  meshes: index into the tris handed to ft_sg_bsp_mesh (a piece clipped by the BSP build reports the face it was cut
+ *             from); ft_sg_triangle: 0; other primitives: -1                                            | -1
+ * Device memory: up to 116 bytes per pixel of a window of "chunk_samples" pixels, plus the pixel list. */
+typedef struct ft_aov {            /* any pointer may be NULL: that channel is neither computed into HBM nor copied */
+    double* t; double* p; double* n; double* colour; double* material;
+    int32_t* leaf; int32_t* node; int32_t* triangle;
+} ft_aov;
+/* Blocking; retires queued frames first.  spp == 0 (corner sampling) is FT_ERR_UNSUPPORTED; sample outside [0, spp) or no channel
+ * requested FT_ERR_INVALID; a host-only context FT_ERR_NO_DEVICE.  Hit lists that overflow grow and the call runs again (csg_auto_grow).
+ * Multi-device contexts split the frame into ft_render's 8-row bands.  stats: rays_primary, hits_primary, kernel_ms, wall_ms and
+ * n_launches; the other fields are 0.  The frame buffer (ft_fetch_frame*), the next ft_render's history and a progressive accumulation
+ * are left as they were. */
+int32_t ft_render_aov(ft_context* ctx, const ft_camera* cam, int32_t res_h, int32_t res_v, int32_t spp, const double* jitter_xy,
+                      int32_t sample, uint64_t seed, const ft_rect* tiles, int32_t n_tiles, const ft_aov* out, ft_stats* stats);
+
 /* Closest hit of single rays through the device path (Scene.intersectScene, Scene.fs:118, after
  * Shading.slightOffset is NOT applied): for tests.  Outputs per ray: t, p[3], n[3], material index
  * resolved colour[3]; hit[i] = 0 when the ray misses. */
