@@ -448,8 +448,10 @@ const OptionSpec kOptions[] = {
     {"bvh_builder", 0, 3, &Options::bvh_builder, nullptr, kCommit},
     {"csg_auto_grow", 0, 1, &Options::csg_auto_grow, nullptr, kFlag},
     {"csg_mesh_capacity", 1, 255, nullptr, [](fth::SceneGraph& g, int64_t v) { g.csg_mesh_capacity = (int32_t)v; }, kCommit},
-    // 1 (default): directional shadow rays of coherent waves walk light-space trees; 0: the BVH
-    {"light_space_shadows", 0, 1, nullptr, [](fth::SceneGraph& g, int64_t v) { g.light_space_shadows = v != 0; }, kFlag | kCommit},
+    // directional shadow rays of coherent waves: 0 the BVH; 1 light-space trees; 2 (default) light-space grids, the trees for wide waves.
+    // It was a flag before the grids: it still takes any value, and any other than 0 / 1 means 2.
+    {"light_space_shadows", std::numeric_limits<int64_t>::min(), kNoLimit, nullptr,
+     [](fth::SceneGraph& g, int64_t v) { g.light_space_shadows = v == 0 || v == 1 ? (int32_t)v : 2; }, kCommit},
     {"mesh_unclipped_bvh", 0, 1, nullptr, [](fth::SceneGraph& g, int64_t v) { g.mesh_unclipped_bvh = v != 0; }, kFlag | kCommit},
 };
 

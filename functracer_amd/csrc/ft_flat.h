@@ -105,17 +105,31 @@ constexpr int kWideNodeDoubles = 28;
 // rectangle holds the (u, v) of o and whose w reaches past the w of o: five comparisons per child instead of a 3-D slab test.
 // Pair record, kLsPairDoubles doubles (per leaf, one per light, from Leaf::pad[0]; ~0u = the leaf has none):
 //   [0..2] U, [3..5] V, [6..8] D, [9..11] c, [12] k_rel, [13] s_abs: a lane's slack is k_rel * |o - c|_1 + s_abs (it covers the angle
-//   between the host's dm and the device's, and the rounding of the lane's projection); [14] int32 root (>= 0 node, INT32_MIN = none).
+//   between the host's dm and the device's, and the rounding of the lane's projection); [14] int32 root (>= 0 node, INT32_MIN = none);
+//   the grid (below) in the words after it: [14] high word uint32 `cells`, [15] low word float `s`, high word uint32 n_u | n_v << 16
+//   (0 = the pair has no grid).
 // Node, kLsNodeWords 32-bit words: [5*c .. 5*c+4] float u_lo, u_hi, v_lo, v_hi, w_max of child c (rounded outward, inflated by the
 //   vertices' rounding); [20..23] int32 child[4]: >= 0 node, INT32_MIN empty slot (all-NaN box: no comparison passes it), otherwise a
 //   leaf ~(first << 3 | count) over count <= 7 triangle records ls_tris[first ..] - bitwise copies of the mesh's own records, so
 //   tri_hit_wave computes exactly what it computes on them.
+// Grid (option light_space_shadows = 2; walked by mesh_shadow_grid): n_u x n_v square cells of side 1 / s centred on c.  The cell of a
+//   float coordinate x is clamp(floor(fmaf(x, s, 0.5f * n)), 0, n - 1) - the same float operations on the host and the device, and
+//   monotone in x, so a rectangle that overlaps a triangle's rectangle covers a cell that lists it.  Cell (i, j) is 4 words at
+//   ls_nodes[cells + 4 * (j * n_u + i)]: {first, box, count, 0}.  Its entries are the triangles whose rectangle (the tree's rounding and
+//   inflation, per triangle) overlaps the cell, sorted by w_max descending: entry k is the record ls_tris[first + k] (a bitwise copy
+//   again) and the five floats u_lo, u_hi, v_lo, v_hi, w_max at ls_nodes[box + 5 k].  Grid words follow the pair's nodes, padded to a
+//   whole node.
 // Caps: kLsMaxPairs pairs per scene, kLsMaxTris triangles per pair, kLsMaxBytes of nodes + copied records per scene; beyond them, "none".
+// A grid holds at most kLsGridEntriesPerTri entries per triangle and no cell more than kLsGridMaxCell entries (else the pair keeps the tree
+// alone); a wave whose rectangle covers more than kLsGridWaveCells cells walks the tree.
 constexpr int kLsPairDoubles = 16;
 constexpr int kLsNodeWords = 24;
 constexpr uint32_t kLsMaxPairs = 64;
 constexpr uint32_t kLsMaxTris = 1u << 20;
 constexpr uint64_t kLsMaxBytes = 256ull << 20;
+constexpr uint32_t kLsGridEntriesPerTri = 16;
+constexpr uint32_t kLsGridMaxCell = 256;
+constexpr uint32_t kLsGridWaveCells = 4;
 // The reference-shaped BSP of a `bspMesh depth` primitive (root >= 0) has a two-levels-at-a-time form as well, for the same walk:
 // 40 doubles = five BspNode slots of the node array per branch (ft_scene.cpp, widen_bsp): the boxes of the branch's two children,
 // those of its four grandchildren in the reference's visiting order (right-right, right-left, left-right, left-left), int32 child[4]

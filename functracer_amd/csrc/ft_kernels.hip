@@ -858,70 +858,7 @@ FT_DEV void mesh_bvh_packet(const Scene& S, int32_t wide_root, const Ray& r, Que
     if (!ANY && found) q.hit(reach, leaf, best_tri, lit);
 }
 
-// Any-hit query of a directional light's shadow rays against a mesh, for a COHERENT wavefront, through the mesh's light-space tree
-// (ft_flat.h, kLsPairDoubles; built by build_light_space).  The rays are parallel, so in the light's frame a child can only hold a hit
-// if its (u, v) rectangle contains the origin's (u, v) and its largest w reaches past the origin's w: five comparisons per child
-// against the general slab test's six FMAs and ten min / max.  Each lane widens its own (u, v, w) by its slack and rounds the bounds
-// outward to float once; the stack, the pushes and the leaves are those of mesh_bvh_packet.  A lane is blocked iff some triangle record
-// gives tri_hit_wave a hit with t < max_dist; the records are bitwise copies of the mesh's, and every triangle a lane can hit lies in
-// every box on its path, so the result is the BVH walk's bit for bit, whatever order the tree is visited in.
-FT_DEV void mesh_shadow_packet(const Scene& S, cdp P, const Ray& r, Query<true>& q) {
-    bool alive = q.active && !q.blocked;
-    if (!__any(alive)) return;
-    float uL, uH, vL, vH, wL;
-    {
-        const double ox = r.ox - P[9], oy = r.oy - P[10], oz = r.oz - P[11];
-        const double u = ox * P[0] + oy * P[1] + oz * P[2], v = ox * P[3] + oy * P[4] + oz * P[5], w = ox * P[6] + oy * P[7] + oz * P[8];
-        const double s = P[12] * (fabs(ox) + fabs(oy) + fabs(oz)) + P[13];
-        // x -+ (s + 2.4e-7 (|x| + s)) rounds to a float on the far side of x -+ s (a float's rounding is at most 6e-8 of its magnitude)
-        const double su = s + 2.4e-7 * (fabs(u) + s), sv = s + 2.4e-7 * (fabs(v) + s), sw = s + 2.4e-7 * (fabs(w) + s);
-        const bool finite = fabs(u) + fabs(v) + fabs(w) + s < 1e300;        // a non-finite origin looks everywhere (it hits nothing there either)
-        const float inf = __builtin_inff();
-        uL = finite ? (float)(u - su) : -inf; uH = finite ? (float)(u + su) : inf;
-        vL = finite ? (float)(v - sv) : -inf; vH = finite ? (float)(v + sv) : inf;
-        wL = !alive ? inf : finite ? (float)(w - sw) : -inf;               // dead lanes: no box reaches +inf
-    }
-    const double bound = q.max_dist;
-    FT_WALK_ADD(3, 1);
-    WaveStack st;
-    int cur = reinterpret_cast<cip>(P + 14)[0];
-    for (;;) {
-        cur = __builtin_amdgcn_readfirstlane(cur);
-        st.sp = __builtin_amdgcn_readfirstlane(st.sp);
-        if (cur >= 0) {
-            FT_WALK_ADD(0, 1);
-            const FT_CONST float* nd = reinterpret_cast<const FT_CONST float*>(S.ls_nodes + (unsigned long long)kLsNodeWords * (uint32_t)cur);
-            const int32_t ch[4] = {reinterpret_cast<cip>(nd + 20)[0], reinterpret_cast<cip>(nd + 20)[1], reinterpret_cast<cip>(nd + 20)[2], reinterpret_cast<cip>(nd + 20)[3]};
-            unsigned long long m[4];
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {                           // bare comparisons, one ballot each (see mesh_bvh_packet)
-                const FT_CONST float* bx = nd + 5 * c;
-                m[c] = __builtin_amdgcn_ballot_w64(bx[0] <= uH) & __builtin_amdgcn_ballot_w64(bx[1] >= uL) & __builtin_amdgcn_ballot_w64(bx[2] <= vH) &
-                       __builtin_amdgcn_ballot_w64(bx[3] >= vL) & __builtin_amdgcn_ballot_w64(bx[4] >= wL);
-            }
-            st.push(ch[3], m[3]); st.push(ch[2], m[2]); st.push(ch[1], m[1]);
-            if (m[0]) { cur = ch[0]; continue; }
-        } else {
-            const uint32_t first = (uint32_t)(~cur) >> 3, count = (uint32_t)(~cur) & 7u;
-            const unsigned long long clk_leaf = FT_WALK_NOW();
-            any_hit_leaf(S.ls_tris, first, count, r, bound, q, alive);
-            wL = alive ? wL : __builtin_inff();
-            FT_WALK_ADD(1, count); FT_WALK_ADD(2, FT_WALK_NOW() - clk_leaf);
-            if (!__any(alive)) break;
-        }
-        if (!st.pop(cur)) break;
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// Wave-level pre-test of the item culls.  OP_CULL tests one item against the 64 rays of the wave, 64 lanes x ~40
-// FP64 instructions per item; scenes with tens of items spend most of a coherent batch there.  Here the roles are
-// swapped once per query: the rays of the wave are bounded by a cone (apex = origin of the first live lane, padded by
-// the largest origin distance; axis = that lane's direction; half-angle = largest deviation) and lane k tests ITEM k's
-// bounding sphere against that cone, so up to 64 items cost one pass of ~25 FP32 instructions.  Conservative by
-// construction: a sphere is dropped only when it lies wholly beyond the tangent plane of the cone nearest to it, all
-// float roundings are covered by explicit slack, and items with a parallel-sensitive face direction (Plane.fs:13-16)
-// that some ray of the wave is nearly parallel to are always kept.  Survivors still run the exact per-ray test of OP_CULL.
+// Wave reductions (DPP within rows of 16, then the four rows).
 FT_DEV float row16_reduce_min(float v) {
     v = fminf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, false)));    // quad_perm [1,0,3,2]
     v = fminf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, false)));    // quad_perm [2,3,0,1]
@@ -935,6 +872,143 @@ FT_DEV float wave_min(float v) {                                    // all 64 la
     const float c = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32)), d = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 48));
     return fminf(fminf(a, b), fminf(c, d));
 }
+FT_DEV float wave_max(float v) { return -wave_min(-v); }
+
+// Any-hit query of a directional light's shadow rays against a mesh, for a COHERENT wavefront, through the mesh's light-space tree
+// (ft_flat.h, kLsPairDoubles; built by build_light_space).  The rays are parallel, so in the light's frame a child can only hold a hit
+// if its (u, v) rectangle contains the origin's (u, v) and its largest w reaches past the origin's w: five comparisons per child
+// against the general slab test's six FMAs and ten min / max.  Each lane widens its own (u, v, w) by its slack and rounds the bounds
+// outward to float once; the stack, the pushes and the leaves are those of mesh_bvh_packet.  A lane is blocked iff some triangle record
+// gives tri_hit_wave a hit with t < max_dist; the records are bitwise copies of the mesh's, and every triangle a lane can hit lies in
+// every box on its path, so the result is the BVH walk's bit for bit, whatever order the tree is visited in.
+
+// A lane's origin in a pair's frame (u, v, w relative to c), widened by its slack and rounded outward to float.
+struct LsLane { float uL, uH, vL, vH, wL; };
+FT_DEV LsLane ls_project(cdp P, const Ray& r, bool alive) {
+    LsLane b;
+    const double ox = r.ox - P[9], oy = r.oy - P[10], oz = r.oz - P[11];
+    const double u = ox * P[0] + oy * P[1] + oz * P[2], v = ox * P[3] + oy * P[4] + oz * P[5], w = ox * P[6] + oy * P[7] + oz * P[8];
+    const double s = P[12] * (fabs(ox) + fabs(oy) + fabs(oz)) + P[13];
+    // x -+ (s + 2.4e-7 (|x| + s)) rounds to a float on the far side of x -+ s (a float's rounding is at most 6e-8 of its magnitude)
+    const double su = s + 2.4e-7 * (fabs(u) + s), sv = s + 2.4e-7 * (fabs(v) + s), sw = s + 2.4e-7 * (fabs(w) + s);
+    const bool finite = fabs(u) + fabs(v) + fabs(w) + s < 1e300;        // a non-finite origin looks everywhere (it hits nothing there either)
+    const float inf = __builtin_inff();
+    b.uL = finite ? (float)(u - su) : -inf; b.uH = finite ? (float)(u + su) : inf;
+    b.vL = finite ? (float)(v - sv) : -inf; b.vH = finite ? (float)(v + sv) : inf;
+    b.wL = !alive ? inf : finite ? (float)(w - sw) : -inf;             // dead lanes: no box reaches +inf
+    return b;
+}
+
+FT_DEV void ls_tree_walk(const Scene& S, int cur, LsLane& b, const Ray& r, Query<true>& q, bool& alive) {
+    const double bound = q.max_dist;
+    WaveStack st;
+    for (;;) {
+        cur = __builtin_amdgcn_readfirstlane(cur);
+        st.sp = __builtin_amdgcn_readfirstlane(st.sp);
+        if (cur >= 0) {
+            FT_WALK_ADD(0, 1);
+            const FT_CONST float* nd = reinterpret_cast<const FT_CONST float*>(S.ls_nodes + (unsigned long long)kLsNodeWords * (uint32_t)cur);
+            const int32_t ch[4] = {reinterpret_cast<cip>(nd + 20)[0], reinterpret_cast<cip>(nd + 20)[1], reinterpret_cast<cip>(nd + 20)[2], reinterpret_cast<cip>(nd + 20)[3]};
+            unsigned long long m[4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {                           // bare comparisons, one ballot each (see mesh_bvh_packet)
+                const FT_CONST float* bx = nd + 5 * c;
+                m[c] = __builtin_amdgcn_ballot_w64(bx[0] <= b.uH) & __builtin_amdgcn_ballot_w64(bx[1] >= b.uL) & __builtin_amdgcn_ballot_w64(bx[2] <= b.vH) &
+                       __builtin_amdgcn_ballot_w64(bx[3] >= b.vL) & __builtin_amdgcn_ballot_w64(bx[4] >= b.wL);
+            }
+            st.push(ch[3], m[3]); st.push(ch[2], m[2]); st.push(ch[1], m[1]);
+            if (m[0]) { cur = ch[0]; continue; }
+        } else {
+            const uint32_t first = (uint32_t)(~cur) >> 3, count = (uint32_t)(~cur) & 7u;
+            const unsigned long long clk_leaf = FT_WALK_NOW();
+            any_hit_leaf(S.ls_tris, first, count, r, bound, q, alive);
+            b.wL = alive ? b.wL : __builtin_inff();
+            FT_WALK_ADD(1, count); FT_WALK_ADD(2, FT_WALK_NOW() - clk_leaf);
+            if (!__any(alive)) break;
+        }
+        if (!st.pop(cur)) break;
+    }
+}
+
+FT_DEV void mesh_shadow_packet(const Scene& S, cdp P, const Ray& r, Query<true>& q) {
+    bool alive = q.active && !q.blocked;
+    if (!__any(alive)) return;
+    LsLane b = ls_project(P, r, alive);
+    FT_WALK_ADD(3, 1);
+    ls_tree_walk(S, reinterpret_cast<cip>(P + 14)[0], b, r, q, alive);
+}
+
+// The same query through the pair's grid (ft_flat.h; option light_space_shadows = 2).  The tree's chain of about six dependent node
+// fetches becomes two: the cell's word, then its entries, contiguous, whose addresses are all known at once.  The wave's live lanes
+// span one rectangle (usually one cell: a batch is a few adjacent pixels' hit points), the cells it covers are visited in wave-uniform
+// order.  A cell's entries are fetched with one vector load (lane e: entry e's box) and tested against the wave's rectangle and its
+// smallest w; each survivor is tested like a tree child, against every lane, before tri_hit_wave.  They come by w_max, largest first:
+// the triangles nearest the light go first.  A cell lists every triangle whose rectangle overlaps it and the wave's cells overlap every
+// lane's rectangle (the cell function is monotone), so the result is the tree's and the BVH's bit for bit.
+// A wave that covers more than kLsGridWaveCells cells (incoherent, or a non-finite origin) walks the tree instead.
+FT_DEV uint32_t ls_cell(float x, float s, uint32_t n) {
+    const float f = __builtin_floorf(__builtin_fmaf(x, s, 0.5f * (float)n));
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)fminf(fmaxf(f, 0.0f), (float)(n - 1)));
+}
+FT_DEV void mesh_shadow_grid(const Scene& S, cdp P, const Ray& r, Query<true>& q) {
+    bool alive = q.active && !q.blocked;
+    if (!__any(alive)) return;
+    LsLane b = ls_project(P, r, alive);
+    FT_WALK_ADD(3, 1);
+    const uint32_t cells = reinterpret_cast<cup>(P + 14)[1], dims = reinterpret_cast<cup>(P + 15)[1];
+    const float s = __uint_as_float(reinterpret_cast<cup>(P + 15)[0]);
+    const uint32_t nu = dims & 0xFFFFu, nv = dims >> 16;
+    const float inf = __builtin_inff();
+    const float u_min = wave_min(alive ? b.uL : inf), u_max = wave_max(alive ? b.uH : -inf);
+    const float v_min = wave_min(alive ? b.vL : inf), v_max = wave_max(alive ? b.vH : -inf);
+    const uint32_t i0 = ls_cell(u_min, s, nu), i1 = ls_cell(u_max, s, nu), j0 = ls_cell(v_min, s, nv), j1 = ls_cell(v_max, s, nv);
+    if ((i1 - i0 + 1) * (j1 - j0 + 1) > kLsGridWaveCells) { ls_tree_walk(S, reinterpret_cast<cip>(P + 14)[0], b, r, q, alive); return; }
+    const double bound = q.max_dist;
+    for (uint32_t j = j0; j <= j1; ++j) {
+        for (uint32_t i = i0; i <= i1; ++i) {
+            FT_WALK_ADD(0, 1);
+            cup C = S.ls_nodes + cells + 4u * (j * nu + i);
+            const uint32_t first = C[0], count = C[2];
+            const FT_CONST float* bx = reinterpret_cast<const FT_CONST float*>(S.ls_nodes + C[1]);
+            const float w_min = wave_min(b.wL);                     // dead lanes hold +inf
+            const unsigned long long clk_leaf = FT_WALK_NOW();
+            uint32_t tested = 0;
+            // Lane e holds entry base + e's box, all requested at once, and tests it against the wave's rectangle; the survivors are
+            // then tested against every lane, in entry order, from the boxes in registers.
+            for (uint32_t base = 0; base < count; base += 64) {
+                const uint32_t e = base + lane_id();
+                const FT_CONST float* eb = bx + 5u * min(e, count - 1u);
+                const float eu0 = eb[0], eu1 = eb[1], ev0 = eb[2], ev1 = eb[3], ew = eb[4];
+                unsigned long long m = __ballot((e < count) & (eu0 <= u_max) & (eu1 >= u_min) & (ev0 <= v_max) & (ev1 >= v_min) & (ew >= w_min));
+                while (m) {
+                    const int k = (int)__builtin_ctzll(m);
+                    m &= m - 1ull;
+                    const float bu0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(eu0), k)), bu1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(eu1), k));
+                    const float bv0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ev0), k)), bv1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ev1), k));
+                    const float bw = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ew), k));
+                    if (!__any((bu0 <= b.uH) & (bu1 >= b.uL) & (bv0 <= b.vH) & (bv1 >= b.vL) & (bw >= b.wL))) continue;
+                    any_hit_leaf(S.ls_tris, first + base + (uint32_t)k, 1, r, bound, q, alive);
+                    b.wL = alive ? b.wL : inf;
+                    ++tested;
+                    if (!__any(alive)) break;
+                }
+                if (!__any(alive)) break;
+            }
+            FT_WALK_ADD(1, tested); FT_WALK_ADD(2, FT_WALK_NOW() - clk_leaf);
+            if (!__any(alive)) return;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Wave-level pre-test of the item culls.  OP_CULL tests one item against the 64 rays of the wave, 64 lanes x ~40
+// FP64 instructions per item; scenes with tens of items spend most of a coherent batch there.  Here the roles are
+// swapped once per query: the rays of the wave are bounded by a cone (apex = origin of the first live lane, padded by
+// the largest origin distance; axis = that lane's direction; half-angle = largest deviation) and lane k tests ITEM k's
+// bounding sphere against that cone, so up to 64 items cost one pass of ~25 FP32 instructions.  Conservative by
+// construction: a sphere is dropped only when it lies wholly beyond the tangent plane of the cone nearest to it, all
+// float roundings are covered by explicit slack, and items with a parallel-sensitive face direction (Plane.fs:13-16)
+// that some ray of the wave is nearly parallel to are always kept.  Survivors still run the exact per-ray test of OP_CULL.
 constexpr int kSparseLanes = 8;                                     // at most this many live rays: exact_cull tests lane = item
 struct ItemMask { unsigned long long lo, hi; bool valid; };   // bit k: top-level item k may be hit by some ray of the wave (items >= 128: not covered)
 // A bundle of rays bounded by a cone: apex c (origins within rho of it), unit axis a, half-angle given by cos_t (rounded down) /
@@ -1005,7 +1079,6 @@ FT_DEV uint32_t rows_nearly_parallel(const Scene& S, const Ray& r, bool live, fl
     }
     return par_rows;
 }
-FT_DEV float wave_max(float v) { return -wave_min(-v); }
 // Shadow rays towards a point light (Shading.fs:38-42: d = normalise (position - point), maxDistance = |position - point|): every ray
 // of the wave passes through the light, so the bundle is a cone whose APEX is the light - no origin spread to pad it with - and a
 // usable hit (0 <= t < maxDistance, Scene.fs:121) lies between the light and the ray's origin: no further from the apex than the
@@ -1238,7 +1311,11 @@ FT_DEV void trace(const Scene& S, const Ray& r, Query<ANY>& q, uint32_t* lds, bo
                                 const uint32_t pairs = reinterpret_cast<cup>(S.leaves + 16ull * arg + 12)[4];   // Leaf::ls_pairs
                                 if (pairs != ~0u) {
                                     cdp P = S.ls_pairs + (unsigned long long)kLsPairDoubles * (pairs + (uint32_t)dir_light);
-                                    if (reinterpret_cast<cip>(P + 14)[0] != INT32_MIN) { mesh_shadow_packet(S, P, rm, q); break; }
+                                    if (reinterpret_cast<cip>(P + 14)[0] != INT32_MIN) {
+                                        if (reinterpret_cast<cup>(P + 15)[1] != 0u) mesh_shadow_grid(S, P, rm, q);
+                                        else mesh_shadow_packet(S, P, rm, q);
+                                        break;
+                                    }
                                 }
                             }
                         }

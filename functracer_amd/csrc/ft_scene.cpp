@@ -446,7 +446,7 @@ int32_t SceneGraph::flatten(FlatScene& out, std::string& err) const {
     //  traces, costs every kernel variant 52 - 136 bytes of scratch per lane - k_primary<F,F,T,4> 56 -> 108, k_bounce<F,F,F> 0 -> 72 - whether
     //  or not a scene has a seventeenth light.  No scene of the reference has more than three.)
     if (out.lights.size() > 16) { err = "more than 16 lights are not supported on the device path"; return FT_ERR_UNSUPPORTED; }
-    if (light_space_shadows) build_light_space(out);
+    if (light_space_shadows) build_light_space(out, light_space_shadows == 2);
     else for (auto& L : out.leaves) L.ls_pairs = ~0u;
     if (out.tris.empty()) { out.tris.assign(9, 0.0); out.tri_orig.assign(1, 0u); out.tri_src.assign(1, 0u); }   // keep device pointers non-null
     if (out.ls_pairs.empty()) out.ls_pairs.assign(ftd::kLsPairDoubles, 0.0);
@@ -954,9 +954,83 @@ struct LsBuilder {
     }
 };
 
+// The cell of a float coordinate along an axis of n cells (ft_flat.h, grid): the device computes the same float operations.
+uint32_t ls_cell(float x, float s, uint32_t n) {
+    const float f = std::floor(std::fma(x, s, 0.5f * (float)n));
+    return (uint32_t)std::fmin(std::fmax(f, 0.0f), (float)(n - 1));
+}
+
+// The grid of a pair whose tree B has just built (ft_flat.h, grid).  Square cells, about as many as there are triangles: a closed mesh
+// covers the occupied part of its projection about twice, and each triangle then overlaps about four cells, so an occupied cell lists
+// 4 - 8 entries.  Coarser while the entries exceed kLsGridEntriesPerTri per triangle; none when the fullest cell exceeds kLsGridMaxCell
+// or the bytes the cap leaves.  Returns false with nothing appended, or appends the cell table and entry boxes to ls_nodes, the
+// entries' records to ls_tris, and sets the pair words.
+bool build_grid(FlatScene& out, const LsBuilder& B, uint64_t& bytes, double* rec) {
+    struct Entry { float box[5]; uint32_t rec; };
+    const size_t n = B.items.size();
+    std::vector<Entry> es(n);
+    double Ru = 0.0, Rv = 0.0;
+    for (size_t k = 0; k < n; ++k) {
+        const LsBuilder::Item& t = B.items[k];
+        Entry& e = es[k];
+        e.box[0] = LsBuilder::f_down(t.lo[0] - B.pad); e.box[1] = LsBuilder::f_up(t.hi[0] + B.pad);
+        e.box[2] = LsBuilder::f_down(t.lo[1] - B.pad); e.box[3] = LsBuilder::f_up(t.hi[1] + B.pad);
+        e.box[4] = LsBuilder::f_up(t.wmax + B.pad);
+        e.rec = t.rec;
+        Ru = std::max({Ru, std::fabs((double)e.box[0]), std::fabs((double)e.box[1])});
+        Rv = std::max({Rv, std::fabs((double)e.box[2]), std::fabs((double)e.box[3])});
+    }
+    const double side = 2.0 * std::max(Ru, Rv);
+    if (!(side > 0.0)) return false;
+    const double h = std::max(std::sqrt(4.0 * Ru * Rv / (double)n), side / 1024.0);
+    float s = (float)(1.0 / h);
+    uint32_t nu = 0, nv = 0;
+    size_t entries = 0;
+    for (int attempt = 0;; ++attempt) {
+        if (attempt == 8 || !(s > 0.0f)) return false;
+        nu = (uint32_t)std::min(1024.0, std::max(1.0, std::ceil(2.0 * Ru * (double)s)));
+        nv = (uint32_t)std::min(1024.0, std::max(1.0, std::ceil(2.0 * Rv * (double)s)));
+        entries = 0;
+        for (const Entry& e : es)
+            entries += (size_t)(ls_cell(e.box[1], s, nu) - ls_cell(e.box[0], s, nu) + 1) * (ls_cell(e.box[3], s, nv) - ls_cell(e.box[2], s, nv) + 1);
+        if ((uint64_t)nu * nv <= 2 * (uint64_t)n && entries <= (size_t)ftd::kLsGridEntriesPerTri * n) break;
+        s *= 0.75f;
+    }
+    if ((uint64_t)nu * nv < 2) return false;
+    std::vector<std::vector<uint32_t>> cell((size_t)nu * nv);
+    for (uint32_t k = 0; k < (uint32_t)n; ++k) {
+        const Entry& e = es[k];
+        for (uint32_t j = ls_cell(e.box[2], s, nv); j <= ls_cell(e.box[3], s, nv); ++j)
+            for (uint32_t i = ls_cell(e.box[0], s, nu); i <= ls_cell(e.box[1], s, nu); ++i) cell[(size_t)j * nu + i].push_back(k);
+    }
+    for (const auto& c : cell) if (c.size() > ftd::kLsGridMaxCell) return false;
+    const uint64_t need = (uint64_t)cell.size() * 16 + (uint64_t)entries * (72 + 20) + ftd::kLsNodeWords * 4;
+    if (bytes + need > ftd::kLsMaxBytes) return false;
+    const size_t at = out.ls_nodes.size();
+    size_t box = at + 4 * cell.size();
+    out.ls_nodes.resize(box + 5 * entries, 0u);
+    for (size_t c = 0; c < cell.size(); ++c) {
+        auto& list = cell[c];
+        std::stable_sort(list.begin(), list.end(), [&](uint32_t x, uint32_t y) { return es[x].box[4] > es[y].box[4]; });
+        const uint32_t word[4] = {(uint32_t)(out.ls_tris.size() / 9), (uint32_t)box, (uint32_t)list.size(), 0u};
+        std::memcpy(&out.ls_nodes[at + 4 * c], word, sizeof word);
+        for (uint32_t k : list) {
+            std::memcpy(&out.ls_nodes[box], es[k].box, sizeof es[k].box);
+            box += 5;
+            out.ls_tris.insert(out.ls_tris.end(), &out.tris[9 * (size_t)es[k].rec], &out.tris[9 * (size_t)es[k].rec] + 9);
+        }
+    }
+    out.ls_nodes.resize((out.ls_nodes.size() + ftd::kLsNodeWords - 1) / ftd::kLsNodeWords * ftd::kLsNodeWords, 0u);
+    bytes += (uint64_t)(out.ls_nodes.size() - at) * 4 + (uint64_t)entries * 72;
+    uint32_t words[3] = {(uint32_t)at, 0u, nu | nv << 16};
+    std::memcpy(&words[1], &s, 4);
+    std::memcpy(reinterpret_cast<char*>(&rec[14]) + 4, words, sizeof words);
+    return true;
+}
+
 } // namespace
 
-void build_light_space(FlatScene& out) {
+void build_light_space(FlatScene& out, bool grids) {
     for (auto& L : out.leaves) L.ls_pairs = ~0u;
     out.ls_pairs.clear(); out.ls_nodes.clear(); out.ls_tris.clear();
     std::vector<uint32_t> dirs;
@@ -1035,6 +1109,7 @@ void build_light_space(FlatScene& out) {
             for (int q = 0; q < 3; ++q) { rec[q] = U[q]; rec[3 + q] = V[q]; rec[6 + q] = D[q]; rec[9 + q] = c[q]; }
             rec[12] = k_rel; rec[13] = (k_rel + 1e-6) * R + 1e-20;   // |p - o| <= |o - c|_1 + R for a hit p on the mesh
             std::memcpy(&rec[14], &root, 4);
+            if (grids) build_grid(out, B, bytes, rec);
             ++n_pairs; any = true;
         }
         if (!any) continue;

@@ -82,8 +82,9 @@ struct SceneGraph {
     // false = the host's recursive surface-area sweep (host-only contexts, and the fallback when a device build is refused).
     bool device_bvh = false;
     int64_t device_bvh_min_tris = 0;   // with device_bvh: meshes with fewer triangles than this get the host's SAH tree (better tree, slower build)
-    // Directional shadow rays of coherent waves walk a tree built in the light's frame (ft_flat.h, kLsPairDoubles); false = the BVH of every ray.
-    bool light_space_shadows = true;
+    // Directional shadow rays of coherent waves: 2 = a grid in the light's frame, with the tree below as the fallback of wide waves; 1 = a
+    // tree built in the light's frame (ft_flat.h, kLsPairDoubles); 0 = the BVH of every ray.
+    int32_t light_space_shadows = 2;
 
     bool valid(int32_t id) const { return id >= 0 && id < (int32_t)nodes.size(); }
     // Returns FT_OK or a negative ft_status with err set.
@@ -94,8 +95,9 @@ struct SceneGraph {
 // the flat arrays and returns the root reference (>= 0 branch node, < 0 ~leaf) via mesh.
 int32_t build_bsp(const double* tris_abc, int64_t n_tris, int32_t depth, FlatScene& out, ftd::Mesh& mesh, std::string& err, bool device_bvh = false);
 
-// The light-space shadow trees of every (top-level-Leaf mesh leaf with a BVH, directional light) pair of a flattened scene (ft_flat.h).
-void build_light_space(FlatScene& out);
+// The light-space shadow trees of every (top-level-Leaf mesh leaf with a BVH, directional light) pair of a flattened scene (ft_flat.h),
+// and with `grids` each pair's grid as well.
+void build_light_space(FlatScene& out, bool grids);
 
 // Triangle.slice (Triangle.fs:24-41) exposed for the known-answer tests of the product's own builder.
 int32_t slice_triangle(const double p0[3], const double n[3], const double tri[9],

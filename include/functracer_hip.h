@@ -150,8 +150,10 @@ const char* ft_last_error(const ft_context* ctx);
  * differ from the reference-shaped clipped BSP in the last bits), "bvh_builder" (who builds the exact BVH of top-level-Leaf meshes at commit - 0: the host, a swept
  * surface-area split (the best tree, a slow build: 160 ms for 70 K triangles); 1: the device, a linear BVH (1 ms, traces ~9 % slower); 3: the device, a binned surface-area tree
  * over the Morton order (5.5 ms, traces like the host's or better); 2 = default: the host below 4096 triangles, the device's surface-area tree from there on),
- * "light_space_shadows" (1 = default: the shadow rays of a directional light in a coherent wave walk a tree built at commit in the light's frame for each
- * top-level `bspMesh 0` leaf - same triangle records, same results bit for bit; 0: they walk the mesh's BVH like every other ray; a change re-commits),
+ * "light_space_shadows" (2 = default: the shadow rays of a directional light in a coherent wave look up a uniform grid built at commit in the light's frame
+ * for each top-level `bspMesh 0` leaf, and walk the tree of option 1 where a wave spans more than a few cells; 1: they walk a tree built in the light's
+ * frame; 0: they walk the mesh's BVH like every other ray.  Same triangle records, same results bit for bit; a value other than 0 / 1 means 2; a change
+ * re-commits),
  * "classify_ahead" / "resolve_aside" / "zero_fill_skip" (1 = default: what a stream of queued frames does that a single frame cannot - the next frame's k_classify on a second
  * stream, k_resolve on a third with the sample colours double-buffered, Colour.Zero not written again into blocks the last frame of the same signature left zero; 0 switches each off; k_resolve goes aside only in frames of one chunk), "mains" (2 = default, 1 .. 3: queued frames of one chunk take turns on that many main streams, so a frame's kernels are dispatched while its predecessor's drain
  * and two frames' reflection levels fill each other's idle stretches), "wave_samples" (0 = default, 16: a bounce-0 wavefront takes up to that many jitter offsets of 64 / that many pixels of an
@@ -340,7 +342,7 @@ int32_t ft_create_host_only(ft_context** out);
 int32_t ft_debug_scene_info(ft_context* ctx, int64_t out[12]);
 int32_t ft_debug_slice(const double p0[3], const double n[3], const double tri[9],
                        double above[18], int32_t* n_above, double below[18], int32_t* n_below);
-/* The light-space shadow trees of the committed scene (option "light_space_shadows"; layout in ft_flat.h, kLsPairDoubles):
+/* The light-space shadow trees and grids of the committed scene (option "light_space_shadows"; layout in ft_flat.h, kLsPairDoubles):
  * sizes = pair records, nodes, triangle records, leaves; each non-null array receives 16 doubles per record, 24 words per node,
  * 9 doubles per triangle and, per leaf, the index of its first pair record (0xFFFFFFFF = none).  Host-only contexts too. */
 int32_t ft_debug_light_space(ft_context* ctx, int64_t sizes[4], double* pairs, uint32_t* nodes, double* tris, uint32_t* leaf_pairs);
