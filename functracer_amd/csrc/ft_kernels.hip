@@ -1195,6 +1195,10 @@ FT_DEV ItemMask exact_cull(const Scene& S, const Ray& r, bool live) {
     const float dd = dx * dx + dy * dy + dz * dz;
     const bool tame = live && dd > 1e-30f && dd < 1e30f && fabsf(ox) < 1e15f && fabsf(oy) < 1e15f && fabsf(oz) < 1e15f;   // else: no float verdicts for this lane
     { const float inv = __builtin_amdgcn_rsqf(dd); dx *= inv; dy *= inv; dz *= inv; }   // a unit direction (to a few ulps: the 1e-4 slack below covers it) drops |d|^2 out of every comparison
+    // The float origin is off by up to 2^-24 |o| per component: the test below is then about a centre moved by that much, which a
+    // radius grown by as much covers (the host grew the record's radius by its own centre's rounding).  Relative slack cannot do it:
+    // 1e5 from the origin the rounding is ~4e-3, whatever the distances compared.  (x 1.0005: the 1.001 slack on r^2.)
+    const float o_round = 1.0005f * 1.2e-7f * (fabsf(ox) + fabsf(oy) + fabsf(oz));
     uint32_t par_lane = 0;                                         // face directions this lane's ray is nearly parallel to (Plane.fs:13-16)
     const bool rows_known = S.n_cull_rows >= 0;                    // (more than 32 distinct directions in the scene: the table does not exist)
     for (int k = 0; k < S.n_cull_rows; ++k) {
@@ -1204,11 +1208,11 @@ FT_DEV ItemMask exact_cull(const Scene& S, const Ray& r, bool live) {
     // The float records sit in the lanes (lane j: items j and 64 + j, one vector load each before the loop) and are handed round by
     // v_readlane: fetched one by one through scalar loads, every item of the loop began with a memory round trip of its own - the
     // fixed ~17 us a batch of incoherent rays cost whatever it held was mostly this loop, twice (closest, then shadow).
-    struct ItemRec { float x, y, z, r2, rows; };                  // r2: the bounding sphere's radius squared, inflated (+inf: unbounded - no comparison below holds)
+    struct ItemRec { float x, y, z, r, rows; };                   // r: the bounding sphere's radius x 1.0005 (+inf: unbounded - no comparison below holds)
     auto load_rec = [&](int item) {
         const float* I = S.cull_items + 8 * ((item < n ? item : 0) + (int)opaque_zero());
         const float rad = I[3];
-        return ItemRec{I[0], I[1], I[2], rad < 1e30f ? rad * rad * 1.001f : __builtin_inff(), I[4]};
+        return ItemRec{I[0], I[1], I[2], rad < 1e30f ? rad * 1.0005f : __builtin_inff(), I[4]};
     };
     const ItemRec lo = load_rec((int)lane_id());
     ItemRec hi{0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
@@ -1218,11 +1222,13 @@ FT_DEV ItemMask exact_cull(const Scene& S, const Ray& r, bool live) {
         const int src = k & 63;
         const bool first = k < 64;                                  // wave-uniform
         const float I[5] = {lane_of(first ? lo.x : hi.x, src), lane_of(first ? lo.y : hi.y, src), lane_of(first ? lo.z : hi.z, src),
-                            lane_of(first ? lo.r2 : hi.r2, src), lane_of(first ? lo.rows : hi.rows, src)};
+                            lane_of(first ? lo.r : hi.r, src), lane_of(first ? lo.rows : hi.rows, src)};
         const float cx = ox - I[0], cy = oy - I[1], cz = oz - I[2];
         const uint32_t rows = __float_as_uint(I[4]);
         const float b = cx * dx + cy * dy + cz * dz, cc = cx * cx + cy * cy + cz * cz, b2 = b * b;
-        const float margin = cc * 0.9999f - I[3];                   // |c|^2 less the slack for every rounding above, less the inflated radius^2
+        const float reach = I[3] + o_round;                         // radius + the origin's rounding (the centre's is in the radius)
+        // |c|^2 less the relative slack for the roundings of this arithmetic, less the radius^2 grown by the absolute rounding of the operands
+        const float margin = cc * 0.9999f - reach * reach;
         const bool line_misses = margin > b2;                       // the line passes the bounding sphere by a margin: |c|^2 - (c.u)^2 > r^2 + slack
         const bool leaves = margin > 0.0f && b > 0.0f && b2 > 1e-6f * cc;   // outside it and moving away: every hit has t < 0
         const bool certainly_missed = tame && rows_known && (line_misses || leaves) && (rows & par_lane) == 0u;

@@ -279,9 +279,15 @@ struct Flattener {
                 if (k == out.cull_rows.size() / 3) { if (k >= 32) { out.cull_bundle = false; break; } out.cull_rows.insert(out.cull_rows.end(), v.begin(), v.end()); }
                 mask |= 1u << k;
             }
-            float rf = (float)r; while ((double)rf < r) rf = std::nextafter(rf, std::numeric_limits<float>::infinity());
+            // The float centre is off by up to half an ulp of each coordinate - 4e-3 at 1e5 from the origin, whatever the item's size -
+            // and the radius grows by exactly that much, so that the float sphere still holds the item.
+            const float fc[3] = {(float)R.centre[0], (float)R.centre[1], (float)R.centre[2]};
+            double moved = 0.0;
+            for (int a = 0; a < 3; ++a) moved += ((double)fc[a] - R.centre[a]) * ((double)fc[a] - R.centre[a]);
+            const double rr = r + std::sqrt(moved) * (1.0 + 1e-9);
+            float rf = (float)rr; while ((double)rf < rr) rf = std::nextafter(rf, std::numeric_limits<float>::infinity());
             float bits; std::memcpy(&bits, &mask, 4);
-            float rec[8] = {(float)R.centre[0], (float)R.centre[1], (float)R.centre[2], rf, bits, 0.f, 0.f, 0.f};
+            float rec[8] = {fc[0], fc[1], fc[2], rf, bits, 0.f, 0.f, 0.f};
             if (out.leaves.size() == m.leaf_at + 1 && out.leaves[m.leaf_at].kind == ftd::LK_MESH) {   // a bare mesh: [5] first coarse box, [6] count, [7] its leaf
                 const uint32_t mesh = out.leaves[m.leaf_at].mesh, w[3] = {out.mesh_coarse[2 * mesh], out.mesh_coarse[2 * mesh + 1], (uint32_t)m.leaf_at};
                 std::memcpy(&rec[5], w, sizeof w);

@@ -24,6 +24,7 @@ class SceneRecipe:
         self.rng = np.random.default_rng(seed)
         self.calls = []          # (method, args, kwargs) with node references as ("n", index)
         root = self._group(depth=0, top=True)
+        self.root = root[1]                                       # the top-level group's call: its children are the scene's items
         self.calls.append(("set_objects", (root,), {}))
         r = self.rng
         for _ in range(int(r.integers(1, 4))):
@@ -96,9 +97,13 @@ class SceneRecipe:
             kids.append(self._material(self._emit("translate", (0.0, -3.0, 0.0), self._emit("primitive", ft.PLANE))))
         return self._emit("group", kids)
 
-    def build(self, b):
+    def build(self, b, offset=None, scale=1.0):
+        """Replay the calls on builder `b`.  offset / scale: the whole scene mapped by x -> scale * x + offset, applied to each
+        top-level item's own transform (the item table stays the same) and to the positional lights; the caller maps the camera."""
         b.clear()
         made = {}
+        moved = offset is not None or scale != 1.0
+        off = np.zeros(3) if offset is None else np.asarray(offset, dtype=np.float64)
 
         def ref(x):
             if isinstance(x, tuple) and len(x) == 2 and x[0] == "n":
@@ -108,7 +113,12 @@ class SceneRecipe:
             return x
 
         for k, (method, args, kwargs) in enumerate(self.calls):
-            made[k] = getattr(b, method)(*[ref(a) for a in args], **kwargs)
+            args = [ref(a) for a in args]
+            if moved and k == self.root:
+                args = [[b.transform([("scale", float(scale)), ("translate", tuple(off))], kid) for kid in args[0]]]
+            elif moved and method == "add_positional":
+                args = [tuple(float(scale) * np.asarray(args[0], dtype=np.float64) + off)] + args[1:]
+            made[k] = getattr(b, method)(*args, **kwargs)
         b.commit()
 
 
