@@ -61,6 +61,7 @@ def hip_lib():
         lib.ft_get_kernel_times.argtypes = [C.c_void_p, _capi.c_double_p, _capi.c_int32_p]
         lib.ft_render_aov.argtypes = [C.c_void_p, C.POINTER(_capi.ft_camera), C.c_int32, C.c_int32, C.c_int32, _capi.c_double_p, C.c_int32,
                                       C.c_uint64, C.POINTER(_capi.ft_rect), C.c_int32, C.POINTER(_capi.ft_aov), C.POINTER(_capi.ft_stats)]
+        lib.ft_denoise.argtypes = _capi.DENOISE_SIGNATURE
         lib.ft_quantise_rgba8.argtypes = [_capi.c_double_p, C.c_int64, C.POINTER(C.c_uint8)]
         for name, res, args in _capi.PROGRESSIVE_SIGNATURES:
             fn = getattr(lib, name)
@@ -389,6 +390,30 @@ class Context(SceneBuilder):
                                             rects, n_rects, C.byref(aov), C.byref(st)))
         planes["stats"] = st.as_dict()
         return planes
+
+    def denoise(self, camera, res_h, res_v, spp, jitter, sample=0, seed=DEFAULT_SEED, tiles=None, rgba8=False, out=None, **params):
+        """ft_denoise: the FP64 frame in HBM (the last render / progressive_pass of res_h x res_v) filtered on the device by an
+        edge-avoiding a-trous filter guided by render_aov's n, p and colour of the same (camera, spp, jitter, sample, seed, tiles).
+        params: iterations, sigma_colour, sigma_normal, sigma_position, demodulate, albedo_floor, use_variance, variance_floor
+        (_capi.DENOISE_DEFAULTS).  Returns (rgb[res_v, res_h, 3] float64 or rgba[res_v, res_h, 4] uint8, stats dict); pixels outside
+        the tiles keep what `out` held (0 in a fresh array).  The frame in HBM stays as it was."""
+        unknown = set(params) - set(_capi.DENOISE_DEFAULTS)
+        if unknown:
+            raise ValueError(f"unknown denoise parameters {sorted(unknown)}")
+        p = _capi.ft_denoise_params()
+        for k, v in {**_capi.DENOISE_DEFAULTS, **params}.items():
+            setattr(p, k, int(v) if k in ("iterations", "demodulate", "use_variance") else float(v))
+        jitter = np.zeros((1, 2)) if spp == 0 else _capi.as_f64(jitter, (spp, 2))
+        shape, dtype = ((res_v, res_h, 4), np.uint8) if rgba8 else ((res_v, res_h, 3), np.float64)
+        if out is None:
+            out = np.zeros(shape, dtype=dtype)
+        if out.shape != shape or out.dtype != dtype or not out.flags.c_contiguous:
+            raise ValueError(f"denoise: need a C-contiguous {np.dtype(dtype).name} array of shape {shape}")
+        rects, n_rects = _capi.make_rects(tiles)
+        st = _capi.ft_stats()
+        self._check(self._lib.ft_denoise(self._ctx, C.byref(camera), res_h, res_v, spp, _capi.dptr(jitter), int(sample), int(seed), rects, n_rects,
+                                         C.byref(p), 1 if rgba8 else 0, out.ctypes.data_as(C.c_void_p), C.byref(st)))
+        return out, st.as_dict()
 
     def pick(self, camera, res_h, res_v, x, y, spp=1, jitter=None, sample=0, seed=DEFAULT_SEED):
         """What is at pixel (x, y) (row 0 = top): the record of render_aov for that one pixel (a 1x1 tile) as a dict of plain

@@ -68,6 +68,22 @@ class ft_aov(C.Structure):
                 ("leaf", c_int32_p), ("node", c_int32_p), ("triangle", c_int32_p)]
 
 
+class ft_denoise_params(C.Structure):
+    """ft_denoise's parameters (include/functracer_hip.h): a-trous iterations 0 .. 6, the three edge-stopping sigmas (0 = term off),
+    demodulation by the material colour and the variance-guided colour term."""
+    _fields_ = [("iterations", C.c_int32), ("demodulate", C.c_int32), ("use_variance", C.c_int32), ("_pad", C.c_int32),
+                ("sigma_colour", C.c_double), ("sigma_normal", C.c_double), ("sigma_position", C.c_double),
+                ("albedo_floor", C.c_double), ("variance_floor", C.c_double)]
+
+
+# Context.denoise's defaults (also the CLI's, functracer_amd/host/Program.cpp)
+DENOISE_DEFAULTS = dict(iterations=5, sigma_colour=0.6, sigma_normal=0.3, sigma_position=0.0, demodulate=1, albedo_floor=1e-3,
+                        use_variance=0, variance_floor=1e-4)
+
+DENOISE_SIGNATURE = [C.c_void_p, C.POINTER(ft_camera), C.c_int32, C.c_int32, C.c_int32, c_double_p, C.c_int32, C.c_uint64, C.POINTER(ft_rect),
+                     C.c_int32, C.POINTER(ft_denoise_params), C.c_int32, C.c_void_p, C.POINTER(ft_stats)]
+
+
 # ft_render_aov channels: (name, dtype, components per pixel, value of a pixel whose ray misses everything)
 AOV_CHANNELS = [("t", np.float64, 1, np.inf), ("p", np.float64, 3, 0.0), ("n", np.float64, 3, 0.0), ("colour", np.float64, 3, 0.0),
                 ("material", np.float64, 3, 0.0), ("leaf", np.int32, 1, -1), ("node", np.int32, 1, -1), ("triangle", np.int32, 1, -1)]

@@ -159,6 +159,10 @@ struct ft_context {
     // ft_render_aov's own pixel list, jitter pattern, planes and counters: nothing a frame or a progressive pass keeps is touched
     DeviceBuf d_aov_pixels, d_aov_jitter, d_aov_out, d_aov_ctr;
     hipEvent_t aov_ev[2] = {};      // around each k_aov launch (kernel_ms)
+    // ft_denoise's own buffers, frame-sized, allocated by the first call: the guide records, the two colour buffers the iterations
+    // alternate between (the last one's FP64 result lands in one of them) and the RGBA8 result
+    DeviceBuf d_dn_guides, d_dn_u[2], d_dn_out8;
+    hipEvent_t dn_ev[2] = {};       // around the scatter kernels and iterations of a call (kernel_ms)
     // The sample colours exist twice: a queued frame's k_resolve runs on a stream of its own (`tail`), behind an event, while the next
     // chunk's / frame's k_primary already fills the other copy - the small kernel hides in the big one's ramp instead of standing between
     // two of them.  acc_free[i]: behind the last k_resolve that read copy i (the next k_primary into that copy waits for it).
@@ -404,12 +408,13 @@ void ft_destroy(ft_context* c) {
         for (DeviceBuf& b : c->d_scene) b.release();
         for (DeviceBuf& b : c->d_rays) b.release();
         for (DeviceBuf& b : c->d_acc) b.release();
-        for (DeviceBuf* b : {&c->d_out, &c->d_out8, &c->d_out_index, &c->d_pixels, &c->d_jitter, &c->d_wave_counts, &c->d_dbg_in, &c->d_dbg_out, &c->d_aov_pixels, &c->d_aov_jitter, &c->d_aov_out, &c->d_aov_ctr}) b->release();
+        for (DeviceBuf* b : {&c->d_out, &c->d_out8, &c->d_out_index, &c->d_pixels, &c->d_jitter, &c->d_wave_counts, &c->d_dbg_in, &c->d_dbg_out, &c->d_aov_pixels, &c->d_aov_jitter, &c->d_aov_out, &c->d_aov_ctr, &c->d_dn_guides, &c->d_dn_u[0], &c->d_dn_u[1], &c->d_dn_out8}) b->release();
         for (auto& f : c->slots) f.release();
         c->prog.release();
         if (c->classified) (void)hipEventDestroy(c->classified);
         for (hipEvent_t& e : c->acc_free) if (e) { (void)hipEventDestroy(e); e = nullptr; }
         for (hipEvent_t& e : c->aov_ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
+        for (hipEvent_t& e : c->dn_ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
         if (c->side) (void)hipStreamDestroy(c->side);
         if (c->tail) (void)hipStreamDestroy(c->tail);
         for (hipStream_t m : c->more_mains) if (m) (void)hipStreamDestroy(m);
@@ -725,20 +730,25 @@ static int32_t fetch_single(ft_context* c, void* out, int format) {
 }
 // The rects of the context's pixel list out of d_out / d_out8 into the caller's frame: blocking copies, or (async != null) queued on that
 // stream behind the frame's k_resolve - the caller's memory should then be page-locked (ft_host_alloc), or the runtime stages the copy.
+static int32_t copy_rects_out(ft_context* c, void* out, const void* frame, size_t px, int32_t res_h, const std::vector<ft_rect>& rects, hipStream_t async);
 static int32_t copy_frame_out(ft_context* c, void* out, int format, hipStream_t async) {
+    return copy_rects_out(c, out, format == 1 ? c->d_out8.p : c->d_out.p, format == 1 ? 4 : 24, c->last_res_h, c->pixel_rects, async);
+}
+// `rects` of a frame-layout buffer in HBM (px bytes per pixel, res_h pixels per row) into the caller's frame of the same layout.
+static int32_t copy_rects_out(ft_context* c, void* out, const void* frame, size_t px, int32_t res_h, const std::vector<ft_rect>& rects, hipStream_t async) {
     auto copy1 = [&](void* d, const void* s_, size_t n) { return async ? hipMemcpyAsync(d, s_, n, hipMemcpyDeviceToHost, async) : hipMemcpy(d, s_, n, hipMemcpyDeviceToHost); };
     auto copy2 = [&](void* d, size_t dp, const void* s_, size_t sp, size_t w, size_t h) { return async ? hipMemcpy2DAsync(d, dp, s_, sp, w, h, hipMemcpyDeviceToHost, async) : hipMemcpy2D(d, dp, s_, sp, w, h, hipMemcpyDeviceToHost); };
-    const size_t px = format == 1 ? 4 : 24, pitch = (size_t)c->last_res_h * px;
-    const char* src = static_cast<const char*>(format == 1 ? c->d_out8.p : c->d_out.p);
+    const size_t pitch = (size_t)res_h * px;
+    const char* src = static_cast<const char*>(frame);
     char* dst = static_cast<char*>(out);
     // A device of a multi-device context holds every N-th 8-row band of the frame: whole rows, equally high, equally spaced.  Those go
     // out as ONE two-dimensional copy whose "rows" are the bands (band = 8 x pitch contiguous bytes, 8 N x pitch apart on both sides) -
     // 34 blocking copies of 737 KB per device at 4K otherwise.  A shorter last band follows on its own.
     size_t k0 = 0;
     {
-        const auto& R = c->pixel_rects;
+        const auto& R = rects;
         size_t run = 0;
-        if (R.size() >= 3 && R[0].x0 == 0 && R[0].w == c->last_res_h) {
+        if (R.size() >= 3 && R[0].x0 == 0 && R[0].w == res_h) {
             const int step = R[1].y0 - R[0].y0;
             run = 1;
             while (run < R.size() && R[run].x0 == 0 && R[run].w == R[0].w && R[run].h == R[0].h && R[run].y0 == R[0].y0 + (int)run * step) ++run;
@@ -749,12 +759,12 @@ static int32_t copy_frame_out(ft_context* c, void* out, int format, hipStream_t 
             }
         }
     }
-    for (size_t k = k0; k < c->pixel_rects.size();) {
-        const ft_rect r = c->pixel_rects[k];
-        if (r.x0 == 0 && r.w == c->last_res_h) {                    // whole rows; vertically adjacent rects go out as one copy
+    for (size_t k = k0; k < rects.size();) {
+        const ft_rect r = rects[k];
+        if (r.x0 == 0 && r.w == res_h) {                    // whole rows; vertically adjacent rects go out as one copy
             int rows = r.h;
             size_t k2 = k + 1;
-            while (k2 < c->pixel_rects.size() && c->pixel_rects[k2].x0 == 0 && c->pixel_rects[k2].w == r.w && c->pixel_rects[k2].y0 == r.y0 + rows) { rows += c->pixel_rects[k2].h; ++k2; }
+            while (k2 < rects.size() && rects[k2].x0 == 0 && rects[k2].w == r.w && rects[k2].y0 == r.y0 + rows) { rows += rects[k2].h; ++k2; }
             FT_HIP(c, copy1(dst + (size_t)r.y0 * pitch, src + (size_t)r.y0 * pitch, (size_t)rows * pitch));
             k = k2;
         } else {
@@ -1559,9 +1569,8 @@ int32_t ft_get_kernel_times(ft_context* c, double ms[5], int32_t launches[5]) {
 // caller's frame-shaped planes.
 namespace {
 struct AovPlanes { int64_t off[8]; int width[8]; size_t bytes_per_entry; };   // t, p, n, colour, material, leaf, node, triangle
-AovPlanes aov_planes(const ft_aov& o, int64_t per) {
+AovPlanes aov_planes(const bool (&want)[8], int64_t per) {
     AovPlanes a{};
-    const void* want[8] = {o.t, o.p, o.n, o.colour, o.material, o.leaf, o.node, o.triangle};
     const int width[8] = {1, 3, 3, 3, 3, 1, 1, 1};
     int64_t at = 0;                                                 // bytes; doubles first, then the 32-bit planes
     for (int k = 0; k < 8; ++k) {
@@ -1573,23 +1582,23 @@ AovPlanes aov_planes(const ft_aov& o, int64_t per) {
     }
     return a;
 }
+struct AovRun { int64_t n_pix = 0; unsigned long long hits = 0; double kernel_ms = 0.0; int32_t n_launches = 0; };
 } // namespace
 
-static int32_t aov_single(ft_context* c, const RenderRequest& q, int32_t sample, const ft_aov& o, ft_stats* stats) {
-    if (!need_device(c)) return FT_ERR_NO_DEVICE;
-    if (!c->committed) { c->err = "scene not committed (ft_scene_commit)"; return FT_ERR_STATE; }
-    const auto wall0 = std::chrono::steady_clock::now();
-    FT_HIP(c, hipSetDevice(c->device));
+// The device half of an AOV pass, shared by ft_render_aov and ft_denoise: the pixel list `px` and the pattern go up, and per window of
+// "chunk_samples" entries one k_aov writes the wanted planes into d_aov_out by position in the window.  consume(p0, n, planes, dev) then
+// sees the window [p0, p0 + n) with its planes still in HBM, behind the kernel on the context's stream - it copies them out, or queues a
+// kernel that reads them.  The stream is drained after every window (the next one overwrites the planes' buffer and the event pair).
+static int32_t aov_windows(ft_context* c, const RenderRequest& q, int32_t sample, const bool (&want)[8], const std::vector<uint32_t>& px, AovRun& run,
+                           const std::function<int32_t(int64_t, uint32_t, const AovPlanes&, char*)>& consume) {
     int32_t rc;
-    if (any_pending(c) && (rc = retire_pending(c, nullptr)) != FT_OK) return rc;
-    if (stats) std::memset(stats, 0, sizeof *stats);
-    std::vector<uint32_t> px;
-    (void)list_pixels(clip_rects(q), q.res_h, px);
     const int64_t n_pix = (int64_t)px.size();
+    run = AovRun{};
+    run.n_pix = n_pix;
     if (n_pix == 0) return FT_OK;
     int64_t per = std::max<int64_t>(1, std::min<int64_t>(n_pix, c->opt.chunk_samples));
     if (per > 64) per -= per % 64;                                  // windows of whole 8x8 blocks
-    const AovPlanes pl = aov_planes(o, per);
+    const AovPlanes pl = aov_planes(want, per);
     if ((rc = upload(c, c->d_aov_pixels, px)) != FT_OK) return rc;
     if ((rc = upload(c, c->d_aov_jitter, std::vector<double>(q.jitter_xy, q.jitter_xy + 2 * (size_t)q.spp))) != FT_OK) return rc;
     if ((rc = ensure(c, c->d_aov_out, (size_t)per * pl.bytes_per_entry)) != FT_OK) return rc;
@@ -1600,12 +1609,8 @@ static int32_t aov_single(ft_context* c, const RenderRequest& q, int32_t sample,
     const ftk::Launch L{c->stream, c->n_cu * c->blocks_aov, lds, c->variant};
     const ftk::AovSource src{c->d_scene[kTriSrc].as<uint32_t>(), c->d_scene[kRunNodes].as<int32_t>()};
     char* const dev = c->d_aov_out.as<char>();
-    std::vector<char> host((size_t)per * pl.bytes_per_entry);
     hipEvent_t* const ev = c->aov_ev;
     for (int k = 0; k < 2; ++k) if (!ev[k]) FT_HIP(c, hipEventCreate(&ev[k]));
-    double kernel_ms = 0.0;
-    int32_t n_launches = 0;
-    void* const dst[8] = {o.t, o.p, o.n, o.colour, o.material, o.leaf, o.node, o.triangle};
     for (int64_t p0 = 0; p0 < n_pix; p0 += per) {
         const uint32_t n = (uint32_t)std::min<int64_t>(per, n_pix - p0);
         ftk::Primary gen{cam, c->d_aov_pixels.as<uint32_t>(), c->d_aov_jitter.as<double>(), (uint32_t)p0, n, q.spp, (uint32_t)q.res_h, (unsigned long long)q.seed,
@@ -1618,14 +1623,44 @@ static int32_t aov_single(ft_context* c, const RenderRequest& q, int32_t sample,
         ftk::launch_aov(L, c->dev_scene, gen, (uint32_t)sample, src, out, c->d_aov_ctr.as<unsigned long long>());
         FT_HIP(c, hipGetLastError());
         FT_HIP(c, hipEventRecord(ev[1], c->stream));
-        ++n_launches;
+        ++run.n_launches;
+        if ((rc = consume(p0, n, pl, dev)) != FT_OK) return rc;
+        FT_HIP(c, hipStreamSynchronize(c->stream));
+        float ms = 0.0f;
+        if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) run.kernel_ms += ms;
+    }
+    unsigned long long ctr[2] = {0, 0};
+    FT_HIP(c, hipMemcpy(ctr, c->d_aov_ctr.p, sizeof ctr, hipMemcpyDeviceToHost));
+    if (ctr[1]) { c->err = "CSG hit list overflow"; return FT_ERR_OVERFLOW; }
+    run.hits = ctr[0];
+    return FT_OK;
+}
+
+static int32_t aov_single(ft_context* c, const RenderRequest& q, int32_t sample, const ft_aov& o, ft_stats* stats) {
+    if (!need_device(c)) return FT_ERR_NO_DEVICE;
+    if (!c->committed) { c->err = "scene not committed (ft_scene_commit)"; return FT_ERR_STATE; }
+    const auto wall0 = std::chrono::steady_clock::now();
+    FT_HIP(c, hipSetDevice(c->device));
+    int32_t rc;
+    if (any_pending(c) && (rc = retire_pending(c, nullptr)) != FT_OK) return rc;
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    std::vector<uint32_t> px;
+    (void)list_pixels(clip_rects(q), q.res_h, px);
+    if (px.empty()) return FT_OK;
+    void* const dst[8] = {o.t, o.p, o.n, o.colour, o.material, o.leaf, o.node, o.triangle};
+    bool want[8];
+    for (int k = 0; k < 8; ++k) want[k] = dst[k] != nullptr;
+    std::vector<char> host;
+    AovRun run;
+    rc = aov_windows(c, q, sample, want, px, run, [&](int64_t p0, uint32_t n, const AovPlanes& pl, char* dev) -> int32_t {
+        size_t need = 0;                                            // the planes keep the offsets of a full window
+        for (int k = 0; k < 8; ++k) if (pl.off[k] >= 0) need = std::max(need, (size_t)pl.off[k] + (size_t)n * pl.width[k] * (k < 5 ? 8 : 4));
+        if (host.size() < need) host.resize(need);
         for (int k = 0; k < 8; ++k) if (pl.off[k] >= 0) {          // a channel's planes lie back to back: n entries apart within the window
             const size_t esz = k < 5 ? 8 : 4;
             FT_HIP(c, hipMemcpyAsync(host.data() + pl.off[k], dev + pl.off[k], (size_t)n * pl.width[k] * esz, hipMemcpyDeviceToHost, c->stream));
         }
         FT_HIP(c, hipStreamSynchronize(c->stream));
-        float ms = 0.0f;
-        if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) kernel_ms += ms;
         for (int k = 0; k < 8; ++k) if (pl.off[k] >= 0) {          // into the caller's planes: frame layout, row 0 = top, w components per pixel
             const int w = pl.width[k];
             const char* src_k = host.data() + pl.off[k];
@@ -1639,13 +1674,12 @@ static int32_t aov_single(ft_context* c, const RenderRequest& q, int32_t sample,
                 for (uint32_t i = 0; i < n; ++i) d[px[(size_t)p0 + i]] = s[i];
             }
         }
-    }
-    unsigned long long ctr[2] = {0, 0};
-    FT_HIP(c, hipMemcpy(ctr, c->d_aov_ctr.p, sizeof ctr, hipMemcpyDeviceToHost));
-    if (ctr[1]) { c->err = "CSG hit list overflow"; return FT_ERR_OVERFLOW; }
+        return FT_OK;
+    });
+    if (rc != FT_OK) return rc;
     if (stats) {
-        stats->rays_primary = (uint64_t)n_pix; stats->hits_primary = ctr[0];
-        stats->kernel_ms = kernel_ms; stats->n_launches = n_launches;
+        stats->rays_primary = (uint64_t)run.n_pix; stats->hits_primary = run.hits;
+        stats->kernel_ms = run.kernel_ms; stats->n_launches = run.n_launches;
         stats->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
     }
     return FT_OK;
@@ -1686,6 +1720,139 @@ int32_t ft_render_aov(ft_context* c, const ft_camera* cam, int32_t res_h, int32_
     if (!out || !(out->t || out->p || out->n || out->colour || out->material || out->leaf || out->node || out->triangle)) { c->err = "ft_render_aov: no channel requested"; return FT_ERR_INVALID; }
     if (!need_device(c)) return FT_ERR_NO_DEVICE;
     return with_growing_hit_lists(c, [&] { return aov_frame(c, q, sample, *out, stats); });
+}
+
+// ------------------------------------------------------------------------------------------ denoising the frame in HBM
+// ft_denoise (functracer_hip.h).  The guide pass is ft_render_aov's (aov_windows: n, p, colour, leaf), but its windows
+// never leave the device: k_denoise_scatter turns each into frame-layout guide records and u_0 = c / d.  Then one k_denoise per
+// iteration alternates between two colour buffers; the last one multiplies d back.  Only buffers of the call's own are written: d_out is
+// read, the cached pixel list, signatures, level hint and a progressive accumulation are not touched.
+static int32_t denoise_single(ft_context* c, const RenderRequest& q, int32_t sample, const ft_denoise_params& P, bool rgba8, void* out, ft_stats* stats) {
+    const auto wall0 = std::chrono::steady_clock::now();
+    FT_HIP(c, hipSetDevice(c->device));
+    int32_t rc;
+    if (any_pending(c) && (rc = retire_pending(c, nullptr)) != FT_OK) return rc;
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    if (c->last_n_pix <= 0 || c->last_format != 0 || c->last_res_h != q.res_h || c->last_res_v != q.res_v) {
+        c->err = c->last_n_pix <= 0 ? "ft_denoise: no frame rendered yet" : c->last_format != 0 ? "ft_denoise: the frame in HBM is RGBA8 (ft_render_rgba8); the filter needs the FP64 frame"
+                                                                                                   : "ft_denoise: the frame in HBM has another size";
+        return FT_ERR_STATE;
+    }
+    const std::vector<ft_rect> rects = clip_rects(q);
+    const ft_context::Progressive& G = c->prog;
+    if (P.use_variance) {
+        const bool live = G.open && G.tolerance > 0.0 && G.passes > 0 && G.res_h == q.res_h && G.res_v == q.res_v;
+        const std::vector<ft_rect> mine = live ? clip_rects(progressive_request(G)) : std::vector<ft_rect>();
+        if (!live || mine.size() != rects.size() || (!rects.empty() && std::memcmp(mine.data(), rects.data(), rects.size() * sizeof(ft_rect)) != 0)) {
+            c->err = "ft_denoise: use_variance needs a live adaptive progressive accumulation (tolerance > 0, at least one pass) of the same size and tiles";
+            return FT_ERR_STATE;
+        }
+    }
+    std::vector<uint32_t> px;
+    (void)list_pixels(rects, q.res_h, px);
+    if (px.empty()) return FT_OK;
+    if (!c->committed) { c->err = "scene not committed (ft_scene_commit)"; return FT_ERR_STATE; }
+    FT_HIP(c, hipStreamSynchronize(c->stream));                     // the frame may have been written on another stream (fetch_single)
+    for (hipStream_t m : c->more_mains) if (m) FT_HIP(c, hipStreamSynchronize(m));
+    FT_HIP(c, hipStreamSynchronize(c->tail));
+    const size_t n_px = (size_t)q.res_h * (size_t)q.res_v;
+    const double* frame = c->d_out.as<double>();
+    const void* result = frame;                                     // zero iterations: the frame itself
+    double kernel_ms = 0.0;
+    int32_t n_launches = 0;
+    AovRun run;
+    hipEvent_t* const ev = c->dn_ev;
+    for (int k = 0; k < 2; ++k) if (!ev[k]) FT_HIP(c, hipEventCreate(&ev[k]));
+    auto elapsed = [&]() -> int32_t {
+        FT_HIP(c, hipStreamSynchronize(c->stream));
+        float ms = 0.0f;
+        if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) kernel_ms += ms;
+        return FT_OK;
+    };
+    if (rgba8 && (rc = ensure(c, c->d_dn_out8, n_px * 4)) != FT_OK) return rc;
+    if (P.iterations > 0) {
+        if ((rc = ensure(c, c->d_dn_guides, n_px * ftk::kDenoiseGuideBytes)) != FT_OK) return rc;
+        for (int k = 0; k < 2; ++k) if ((rc = ensure(c, c->d_dn_u[k], n_px * 24)) != FT_OK) return rc;
+        ftk::DenoiseGuides g{};
+        double* plane = c->d_dn_guides.as<double>();
+        for (int k = 0; k < 3; ++k) { g.n[k] = plane + (size_t)k * n_px; g.p[k] = plane + (size_t)(3 + k) * n_px; g.d[k] = plane + (size_t)(6 + k) * n_px; }
+        g.v = plane + 9 * n_px;
+        g.cls = reinterpret_cast<uint8_t*>(plane + 10 * n_px);
+        FT_HIP(c, hipMemsetAsync(g.cls, ftk::kDenoiseOutside, n_px, c->stream));
+        const bool want[8] = {false, true, true, true, false, true, false, false};   // p, n, colour, leaf
+        rc = aov_windows(c, q, sample, want, px, run, [&](int64_t p0, uint32_t n, const AovPlanes& pl, char* dev) -> int32_t {
+            ftk::DenoiseScatterArgs a{};
+            a.pixel_ids = c->d_aov_pixels.as<uint32_t>(); a.first = (uint32_t)p0; a.n = n;
+            a.p_plane = reinterpret_cast<const double*>(dev + pl.off[1]); a.n_plane = reinterpret_cast<const double*>(dev + pl.off[2]);
+            a.colour = reinterpret_cast<const double*>(dev + pl.off[3]); a.leaf = reinterpret_cast<const int32_t*>(dev + pl.off[5]); a.stride = n;
+            a.frame = frame; a.u0 = c->d_dn_u[0].as<double>(); a.g = g;
+            a.demodulate = P.demodulate ? 1 : 0; a.albedo_floor = P.albedo_floor;
+            if (P.use_variance) {
+                a.sum = G.d_sum[G.cur].as<double>(); a.sq = G.d_sq[G.cur].as<double>(); a.blk = G.d_blk[G.cur].as<uint32_t>();
+                a.n_list = (uint32_t)G.n_pix; a.variance_floor = P.variance_floor;
+            }
+            FT_HIP(c, hipEventRecord(ev[0], c->stream));
+            ftk::launch_denoise_scatter(c->stream, a);
+            FT_HIP(c, hipGetLastError());
+            FT_HIP(c, hipEventRecord(ev[1], c->stream));
+            ++n_launches;
+            return elapsed();
+        });
+        if (rc != FT_OK) return rc;
+        auto inv_sq = [](double sigma) { return sigma > 0.0 ? 1.0 / (sigma * sigma) : 0.0; };
+        FT_HIP(c, hipEventRecord(ev[0], c->stream));
+        for (int i = 0; i < P.iterations; ++i) {
+            const bool last = i + 1 == P.iterations;
+            ftk::DenoiseArgs a{};
+            a.u_in = c->d_dn_u[i & 1].as<double>(); a.u_out = c->d_dn_u[(i + 1) & 1].as<double>();
+            a.out8 = last && rgba8 ? c->d_dn_out8.as<uint8_t>() : nullptr;
+            a.g = g; a.res_h = q.res_h; a.res_v = q.res_v; a.step = 1 << i;
+            a.inv_sn2 = inv_sq(P.sigma_normal); a.inv_sp2 = inv_sq(P.sigma_position); a.inv_sc2 = inv_sq(P.sigma_colour * std::ldexp(1.0, -i));
+            ftk::launch_denoise(c->stream, a, last);
+            ++n_launches;
+            if (last) result = rgba8 ? (const void*)a.out8 : (const void*)a.u_out;
+        }
+        FT_HIP(c, hipGetLastError());
+        FT_HIP(c, hipEventRecord(ev[1], c->stream));
+        if ((rc = elapsed()) != FT_OK) return rc;
+    } else if (rgba8) {
+        FT_HIP(c, hipEventRecord(ev[0], c->stream));
+        ftk::launch_denoise_quantise(c->stream, frame, c->d_dn_out8.as<uint8_t>(), (uint32_t)n_px);
+        FT_HIP(c, hipGetLastError());
+        FT_HIP(c, hipEventRecord(ev[1], c->stream));
+        ++n_launches;
+        if ((rc = elapsed()) != FT_OK) return rc;
+        result = c->d_dn_out8.p;
+    }
+    if ((rc = copy_rects_out(c, out, result, rgba8 ? 4 : 24, q.res_h, rects, nullptr)) != FT_OK) return rc;
+    if (stats) {
+        stats->rays_primary = (uint64_t)run.n_pix; stats->hits_primary = run.hits;
+        stats->kernel_ms = run.kernel_ms + kernel_ms; stats->n_launches = run.n_launches + n_launches;
+        stats->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+    }
+    return FT_OK;
+}
+
+int32_t ft_denoise(ft_context* c, const ft_camera* cam, int32_t res_h, int32_t res_v, int32_t spp, const double* jitter_xy, int32_t sample, uint64_t seed,
+                   const ft_rect* tiles, int32_t n_tiles, const ft_denoise_params* params, int32_t rgba8, void* out, ft_stats* stats) {
+    if (!c) return FT_ERR_INVALID;
+    const RenderRequest q{cam, res_h, res_v, spp, jitter_xy, 0, seed, tiles, n_tiles, 0};
+    int32_t rc = check_request(c, q);
+    if (rc != FT_OK) return rc;
+    if (spp == 0) { c->err = "ft_denoise: corner sampling (spp == 0) has no per-sample geometry ray to take the guides from"; return FT_ERR_UNSUPPORTED; }
+    if (sample < 0 || sample >= spp) { c->err = "ft_denoise: sample outside [0, spp)"; return FT_ERR_INVALID; }
+    if (!params || !out) { c->err = "ft_denoise: null params or out"; return FT_ERR_INVALID; }
+    const ft_denoise_params& P = *params;
+    if (P.iterations < 0 || P.iterations > 6) { c->err = "ft_denoise: iterations outside 0 .. 6"; return FT_ERR_INVALID; }
+    if (!(P.sigma_colour >= 0.0) || !(P.sigma_normal >= 0.0) || !(P.sigma_position >= 0.0)) { c->err = "ft_denoise: a sigma is negative or NaN (0 switches a term off)"; return FT_ERR_INVALID; }
+    if (P.demodulate && !(P.albedo_floor > 0.0)) { c->err = "ft_denoise: demodulate needs albedo_floor > 0"; return FT_ERR_INVALID; }
+    if (P.use_variance && !(P.variance_floor > 0.0)) { c->err = "ft_denoise: use_variance needs variance_floor > 0"; return FT_ERR_INVALID; }
+    if (!need_device(c)) return FT_ERR_NO_DEVICE;
+    if (!c->peers.empty()) {
+        c->err = "ft_denoise: a context over several devices keeps the frame in 8-row bands on different devices and a tap crosses bands; gathering them is not supported";
+        return FT_ERR_UNSUPPORTED;
+    }
+    return with_growing_hit_lists(c, [&] { return denoise_single(c, q, sample, P, rgba8 != 0, out, stats); });
 }
 
 // ------------------------------------------------------------------------------------------ debug / tests

@@ -210,6 +210,36 @@ struct AovSource { const uint32_t* tri_src; const int32_t* run_nodes; };   // th
 void launch_aov(const Launch& L, const DevScene& S, const Primary& gen, uint32_t sample, const AovSource& src, const AovOut& out, unsigned long long* counters);
 int occupancy_blocks_aov(size_t lds_bytes, int variant);
 
+// ft_denoise (ft_denoise.hip; the filter is defined in functracer_hip.h and DESIGN.md 11).  The guide record of a pixel, in FRAME
+// layout (index y * res_h + x), one plane per component: what a tap reads of its neighbour (n, p, class: 49 bytes) and what only the
+// pixel itself needs (the demodulation divisor d, the variance factor V: 32 bytes).
+enum : uint8_t { kDenoiseMiss = 0, kDenoiseHit = 1, kDenoiseOutside = 2 };   // outside the request's tiles: no tap matches it
+struct DenoiseGuides { double* n[3]; double* p[3]; double* d[3]; double* v; uint8_t* cls; };
+constexpr size_t kDenoiseGuideBytes = 10 * 8 + 1;
+// k_denoise_scatter: a window of k_aov's planes (n, p, colour as three planes of `stride` entries, leaf; by position in the window)
+// into the guide records of the pixels pixel_ids[first .. first + n), and u0 = frame / d.  sum != null: V from the running sums of an
+// adaptive progressive accumulation over the same list (ProgressiveArgs' layout, n_list entries); else V = 1.
+struct DenoiseScatterArgs {
+    const uint32_t* pixel_ids; uint32_t first, n;
+    const double *n_plane, *p_plane, *colour; const int32_t* leaf; uint32_t stride;
+    const double* frame; double* u0;
+    DenoiseGuides g;
+    int32_t demodulate; double albedo_floor;
+    const double *sum, *sq; const uint32_t* blk; uint32_t n_list; double variance_floor;
+};
+void launch_denoise_scatter(hipStream_t stream, const DenoiseScatterArgs& a);
+// k_denoise: one a-trous iteration with taps `step` pixels apart over the whole frame, u_in -> u_out (res_v x res_h x 3 doubles each).
+// inv_s*2 = 1 / sigma^2 (the colour one already scaled by 4^i), 0: that term is off.  `last`: the result is multiplied by d and goes
+// to out8 as RGBA8 bytes when that is non-null, else to u_out.
+struct DenoiseArgs {
+    const double* u_in; double* u_out; uint8_t* out8;
+    DenoiseGuides g;
+    int32_t res_h, res_v, step;
+    double inv_sn2, inv_sp2, inv_sc2;
+};
+void launch_denoise(hipStream_t stream, const DenoiseArgs& a, bool last);
+void launch_denoise_quantise(hipStream_t stream, const double* rgb, uint8_t* out8, uint32_t n_px);   // ft_quantise_rgba8 on the device
+
 // Debug: closest hit / blocked for arbitrary rays (no slightOffset).
 void launch_debug_closest(const Launch& L, const DevScene& S, const double* o, const double* d, uint32_t n,
                           int32_t* hit, double* t, double* p, double* nrm, double* colour, unsigned long long* overflow);

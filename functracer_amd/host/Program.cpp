@@ -1,6 +1,10 @@
 // Program.cpp — command-line driver with the flow of Program.fs:51-100: parse the scene,
 // create the image plane + rays + shade + blend (one ft_render call on the GPU), write the PNG.
 //   functracer <scene-file> [output.png]        (2 args: file output; otherwise PNG to stdout)
+//   functracer <scene-file> <output.png> --denoise N
+//                                               the frame filtered on the device before it is written: ft_denoise with N a-trous
+//                                               iterations (0 .. 6) guided by the surfaces of sample 0, demodulated by the material colour;
+//                                               sigma_colour 0.6, sigma_normal 0.3, sigma_position 0 (off), albedo_floor 1e-3, no variance
 //   functracer <scene-file> --intersection-at X Y
 //                                               what is at pixel (X, Y), row 0 = top, on stderr; no image (the device counterpart of
 //                                               printIntersectionAt, Program.fs:33-49: ft_render_aov of a 1x1 tile, jitter offset (0, 0))
@@ -60,6 +64,8 @@ int main(int argc, char** argv) {
     if (argc < 2) { std::fprintf(stderr, "usage: functracer <scene-file> [output.png | --intersection-at X Y]\n"); return 2; }
     const bool pick = argc >= 3 && std::strcmp(argv[2], "--intersection-at") == 0;
     if (pick && argc != 5) { std::fprintf(stderr, "usage: functracer <scene-file> --intersection-at X Y\n"); return 2; }
+    const bool denoise = argc >= 4 && std::strcmp(argv[3], "--denoise") == 0;
+    if (denoise && argc != 5) { std::fprintf(stderr, "usage: functracer <scene-file> <output.png> --denoise N\n"); return 2; }
     const auto t0 = std::chrono::steady_clock::now();
     auto ms = [&] { return (long)std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t0).count(); };
     std::fprintf(stderr, "Using input file: %s\n", argv[1]);
@@ -97,7 +103,13 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "Shaded scene %lims (%.3f ms on the GPU, %.1f Mrays/s, %llu rays)\n", ms(), st.kernel_ms,
                  (double)st.rays_traced / (st.kernel_ms * 1e3), (unsigned long long)st.rays_traced);
     std::vector<uint8_t> rgba((size_t)opt.res_h * opt.res_v * 4);
-    ft_quantise_rgba8(rgb.data(), (int64_t)opt.res_h * opt.res_v, rgba.data());
+    if (denoise) {                                                 // the frame is still in HBM: filter it there, bytes out
+        const ft_denoise_params dp{std::atoi(argv[4]), 1, 0, 0, 0.6, 0.3, 0.0, 1e-3, 1e-4};
+        ft_stats ds;
+        rc = ft_denoise(ctx, &opt.camera, opt.res_h, opt.res_v, opt.samples, jitter.data(), 0, seed, nullptr, 0, &dp, 1, rgba.data(), &ds);
+        if (rc != FT_OK) { std::fprintf(stderr, "ft_denoise failed (%d): %s\n", rc, ft_last_error(ctx)); return 1; }
+        std::fprintf(stderr, "Denoised %lims (%d iterations, %.3f ms on the GPU)\n", ms(), dp.iterations, ds.kernel_ms);
+    } else ft_quantise_rgba8(rgb.data(), (int64_t)opt.res_h * opt.res_v, rgba.data());
     std::fprintf(stderr, "Writing output %lims\n", ms());
     const char* out = argc >= 3 ? argv[2] : "/dev/stdout";
     if (argc >= 3) std::fprintf(stderr, "Using output file: %s\n", argv[2]); else std::fprintf(stderr, "Using standard output\n");

@@ -319,6 +319,43 @@ typedef struct ft_aov {            /* any pointer may be NULL: that channel is n
 int32_t ft_render_aov(ft_context* ctx, const ft_camera* cam, int32_t res_h, int32_t res_v, int32_t spp, const double* jitter_xy,
                       int32_t sample, uint64_t seed, const ft_rect* tiles, int32_t n_tiles, const ft_aov* out, ft_stats* stats);
 
+/* ---- denoising the frame in HBM ---------------------------------------------------------------- */
+/* ft_denoise filters the FP64 frame that is in HBM (what ft_fetch_frame would return) on the device with an edge-avoiding a-trous
+ * wavelet filter (Dammertz et al. 2010), FP64, guided by the surface buffers ft_render_aov defines for the same
+ * (cam, res, spp, jitter_xy, sample, seed, tiles).  Per frame pixel x: c(x) the frame; n(x), p(x), a(x) the normal, point and
+ * `colour` plane of sample `sample`'s geometry ray; k(x) its class, hit (leaf >= 0) or miss; T the tile pixels of the request (the
+ * clipped rects, the whole frame when tiles == NULL); se(x) the per-channel standard error of the mean of a live ADAPTIVE progressive
+ * accumulation, as ft_progressive_fetch defines it (use_variance only).
+ *   d(x) = per channel max(a(x), albedo_floor) for a hit pixel when `demodulate`, else 1;  u_0 = c / d.
+ *   V(x) = variance_floor + (1/3) * sum_ch (se_ch(x) / d_ch(x))^2 when `use_variance`, else 1.
+ *   for i = 0 .. iterations-1, s = 2^i, h = [1/16, 1/4, 3/8, 1/4, 1/16], taps q = x + s * (dx, dy), dy = -2 .. 2 outer, dx = -2 .. 2 inner
+ *   (the summation order); a tap takes part only if q is in T and k(q) == k(x):
+ *     E = |n(x)-n(q)|^2 / sigma_normal^2 + |p(x)-p(q)|^2 / sigma_position^2 + |u_i(x)-u_i(q)|^2 / ((sigma_colour * 2^-i)^2 * V(x))
+ *     (a term whose sigma is 0 is left out; for miss pixels n and p are 0, so only the colour term acts),
+ *     w = h[dx+2] * h[dy+2] * exp(-E),   u_{i+1}(x) = (sum w * u_i(q)) / (sum w).   The centre tap has E = 0: the denominator is never 0.
+ *   Non-finite data never spreads: a tap whose E is NaN or whose u_i(q) has a non-finite channel is skipped, and a pixel whose own
+ *   u_i(x) has a non-finite channel is copied through unchanged (the reference's specular term can produce NaN, Shading.fs:85-87).
+ *   Result: u_N(x) * d(x) for every x in T; pixels outside T are not written; iterations == 0 returns c bit for bit.
+ * The variance is NOT filtered from iteration to iteration (SVGF does; out of scope).  The guides are those of ONE sample: a
+ * depth-of-field frame gets sample `sample`'s surfaces and is softened accordingly.
+ * Blocking; retires queued frames first.  `out` is laid out as ft_render's out_rgb, or as ft_render_rgba8's bytes when rgba8 != 0
+ * (quantised on the device: the bytes of ft_quantise_rgba8 of the FP64 result); whole rows leave as one copy, as ft_fetch_frame's do
+ * (one DMA when out came from ft_host_alloc).
+ * Errors, checked before anything runs: spp == 0 FT_ERR_UNSUPPORTED; sample outside [0, spp), null params / out, iterations outside
+ * 0 .. 6, a negative (or NaN) sigma, a floor <= 0 where it is used FT_ERR_INVALID; then a host-only context FT_ERR_NO_DEVICE; a context
+ * over several devices FT_ERR_UNSUPPORTED (the frame lives in bands on different devices and a tap crosses bands); no FP64 frame of
+ * res_h x res_v in HBM (nothing rendered, an RGBA8 frame, another size) FT_ERR_STATE; use_variance without a live adaptive accumulation
+ * of the same size and tiles FT_ERR_STATE.  Hit lists that overflow in the guide pass grow and the call runs again (csg_auto_grow).
+ * The frame buffer, the next ft_render's history and a progressive accumulation are left as they were.
+ * stats: rays_primary / hits_primary of the guide pass (0 when iterations == 0: there is none), kernel_ms, wall_ms, n_launches; the
+ * rest 0.  Device memory, allocated on first use and kept: 81 bytes per frame pixel of guides, two colour buffers of 24, 4 of RGBA8
+ * when asked for, beside ft_render_aov's window (76 bytes per pixel of it: n, p, colour, leaf). */
+typedef struct ft_denoise_params { int32_t iterations, demodulate, use_variance, _pad;
+    double sigma_colour, sigma_normal, sigma_position, albedo_floor, variance_floor; } ft_denoise_params;
+int32_t ft_denoise(ft_context* ctx, const ft_camera* cam, int32_t res_h, int32_t res_v, int32_t spp,
+                   const double* jitter_xy, int32_t sample, uint64_t seed, const ft_rect* tiles, int32_t n_tiles,
+                   const ft_denoise_params* params, int32_t rgba8, void* out, ft_stats* stats);
+
 /* Closest hit of single rays through the device path (Scene.intersectScene, Scene.fs:118, after
  * Shading.slightOffset is NOT applied): for tests.  Outputs per ray: t, p[3], n[3], material index
  * resolved colour[3]; hit[i] = 0 when the ray misses. */
