@@ -63,7 +63,7 @@ def hip_lib():
                                       C.c_uint64, C.POINTER(_capi.ft_rect), C.c_int32, C.POINTER(_capi.ft_aov), C.POINTER(_capi.ft_stats)]
         lib.ft_denoise.argtypes = _capi.DENOISE_SIGNATURE
         lib.ft_quantise_rgba8.argtypes = [_capi.c_double_p, C.c_int64, C.POINTER(C.c_uint8)]
-        for name, res, args in _capi.PROGRESSIVE_SIGNATURES:
+        for name, res, args in _capi.PROGRESSIVE_SIGNATURES + _capi.TEMPORAL_SIGNATURES:
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _hip = lib
@@ -414,6 +414,59 @@ class Context(SceneBuilder):
         self._check(self._lib.ft_denoise(self._ctx, C.byref(camera), res_h, res_v, spp, _capi.dptr(jitter), int(sample), int(seed), rects, n_rects,
                                          C.byref(p), 1 if rgba8 else 0, out.ctypes.data_as(C.c_void_p), C.byref(st)))
         return out, st.as_dict()
+
+    # reprojected frame accumulation for a moving camera (ft_temporal_*, include/functracer_hip.h) -----
+    def temporal_begin(self, res_h, res_v, tiles=None):
+        """Start accumulating the frames of a camera path (replaces any earlier accumulation); fixes the frame size and the tiles."""
+        rects, n_rects = _capi.make_rects(tiles)
+        self._check(self._lib.ft_temporal_begin(self._ctx, int(res_h), int(res_v), rects, n_rects))
+        self._temporal = (int(res_h), int(res_v))
+
+    def temporal_accumulate(self, camera, spp, jitter, sample=0, seed=DEFAULT_SEED, rgba8=False, out=None, fetch=True, **params):
+        """ft_temporal_accumulate: the FP64 frame in HBM (the last render of the begin's size, from `camera`) blended with the history
+        of the surfaces render_aov reports for (camera, spp, jitter, sample, seed), looked up where they lay in the previous call's
+        image.  params: max_history, to_frame, min_normal_dot, position_tolerance_px (_capi.TEMPORAL_DEFAULTS).  Returns (the
+        accumulated rgb[res_v, res_h, 3] float64 or rgba[res_v, res_h, 4] uint8, stats dict); pixels outside the tiles keep what
+        `out` held (0 in a fresh array); with fetch=False nothing is copied out (returns (None, stats))."""
+        unknown = set(params) - set(_capi.TEMPORAL_DEFAULTS)
+        if unknown:
+            raise ValueError(f"unknown temporal parameters {sorted(unknown)}")
+        res_h, res_v = self._temporal_shape()
+        p = _capi.ft_temporal_params()
+        for k, v in {**_capi.TEMPORAL_DEFAULTS, **params}.items():
+            setattr(p, k, int(v) if k in ("max_history", "to_frame") else float(v))
+        jitter = np.zeros((1, 2)) if spp <= 0 else _capi.as_f64(jitter, (spp, 2))
+        shape, dtype = ((res_v, res_h, 4), np.uint8) if rgba8 else ((res_v, res_h, 3), np.float64)
+        if fetch and out is None:
+            out = np.zeros(shape, dtype=dtype)
+        if fetch and (out.shape != shape or out.dtype != dtype or not out.flags.c_contiguous):
+            raise ValueError(f"temporal_accumulate: need a C-contiguous {np.dtype(dtype).name} array of shape {shape}")
+        st = _capi.ft_stats()
+        self._check(self._lib.ft_temporal_accumulate(self._ctx, C.byref(camera), int(spp), _capi.dptr(jitter), int(sample), int(seed), C.byref(p),
+                                                     1 if rgba8 else 0, out.ctypes.data_as(C.c_void_p) if fetch else None, C.byref(st)))
+        return (out if fetch else None), st.as_dict()
+
+    def temporal_fetch(self):
+        """(mean[res_v, res_h, 3], stderr[res_v, res_h, 3], history length[res_v, res_h] float64) of the tile pixels; other pixels stay 0."""
+        res_h, res_v = self._temporal_shape()
+        mean, se, length = np.zeros((res_v, res_h, 3)), np.zeros((res_v, res_h, 3)), np.zeros((res_v, res_h))
+        self._check(self._lib.ft_temporal_fetch(self._ctx, _capi.dptr(mean), _capi.dptr(se), _capi.dptr(length)))
+        return mean, se, length
+
+    def temporal_status(self):
+        out = (C.c_int64 * 4)()
+        self._check(self._lib.ft_temporal_status(self._ctx, out))
+        return dict(zip(["calls", "pixels", "with_history", "at_max_history"], list(out)))
+
+    def temporal_end(self):
+        self._check(self._lib.ft_temporal_end(self._ctx))
+        self._temporal = None
+
+    def _temporal_shape(self):
+        shape = getattr(self, "_temporal", None)
+        if shape is None:                                           # the frame's size is unknown: nothing to size the output by
+            raise FtError(-5, "no temporal accumulation (temporal_begin)")
+        return shape
 
     def pick(self, camera, res_h, res_v, x, y, spp=1, jitter=None, sample=0, seed=DEFAULT_SEED):
         """What is at pixel (x, y) (row 0 = top): the record of render_aov for that one pixel (a 1x1 tile) as a dict of plain

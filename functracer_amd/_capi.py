@@ -84,6 +84,26 @@ DENOISE_SIGNATURE = [C.c_void_p, C.POINTER(ft_camera), C.c_int32, C.c_int32, C.c
                      C.c_int32, C.POINTER(ft_denoise_params), C.c_int32, C.c_void_p, C.POINTER(ft_stats)]
 
 
+class ft_temporal_params(C.Structure):
+    """ft_temporal_accumulate's parameters (include/functracer_hip.h): the history length at which the running mean turns into an
+    exponential average, whether the means replace the frame in HBM, and the two surface tests of a history tap."""
+    _fields_ = [("max_history", C.c_int32), ("to_frame", C.c_int32), ("min_normal_dot", C.c_double), ("position_tolerance_px", C.c_double)]
+
+
+# Context.temporal_accumulate's defaults
+TEMPORAL_DEFAULTS = dict(max_history=32, to_frame=0, min_normal_dot=0.9, position_tolerance_px=4.0)
+
+# ft_temporal_* (include/functracer_hip.h): frames along a camera path accumulated by reprojection.
+TEMPORAL_SIGNATURES = [
+    ("ft_temporal_begin", C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(ft_rect), C.c_int32]),
+    ("ft_temporal_accumulate", C.c_int32, [C.c_void_p, C.POINTER(ft_camera), C.c_int32, c_double_p, C.c_int32, C.c_uint64,
+                                           C.POINTER(ft_temporal_params), C.c_int32, C.c_void_p, C.POINTER(ft_stats)]),
+    ("ft_temporal_fetch", C.c_int32, [C.c_void_p, c_double_p, c_double_p, c_double_p]),
+    ("ft_temporal_status", C.c_int32, [C.c_void_p, C.POINTER(C.c_int64)]),
+    ("ft_temporal_end", C.c_int32, [C.c_void_p]),
+]
+
+
 # ft_render_aov channels: (name, dtype, components per pixel, value of a pixel whose ray misses everything)
 AOV_CHANNELS = [("t", np.float64, 1, np.inf), ("p", np.float64, 3, 0.0), ("n", np.float64, 3, 0.0), ("colour", np.float64, 3, 0.0),
                 ("material", np.float64, 3, 0.0), ("leaf", np.int32, 1, -1), ("node", np.int32, 1, -1), ("triangle", np.int32, 1, -1)]

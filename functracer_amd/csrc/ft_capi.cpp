@@ -234,7 +234,23 @@ struct ft_context {
         int cur = 0;
         void release() { for (int k = 0; k < 2; ++k) { d_sum[k].release(); d_sq[k].release(); d_blk[k].release(); } *this = Progressive(); }
     } prog;
+    // A temporal accumulation (ft_temporal_begin .. _end; single-device contexts only): the two history sets in frame layout
+    // (ftk::TemporalSet, kTemporalSetBytes per frame pixel), the previous call's image plane, the call's result buffers and its two counts.
+    // A call reads set `prev` and writes the other one; prev flips only once the call has succeeded, so a call that runs again after the
+    // hit lists grew, or that failed, finds the history as it was.
+    struct Temporal {
+        bool open = false;
+        int32_t res_h = 0, res_v = 0;
+        std::vector<ft_rect> rects;     // the tiles clipped to the frame
+        int64_t n_pix = 0, calls = 0, with_history = 0, at_max = 0;
+        ftk::Camera cam{};              // the previous call's (calls > 0)
+        DeviceBuf d_set[2], d_rgb, d_rgba8, d_ctr;
+        int prev = 0;
+        void release() { for (DeviceBuf* b : {&d_set[0], &d_set[1], &d_rgb, &d_rgba8, &d_ctr}) b->release(); *this = Temporal(); }
+    } temporal;
+    hipEvent_t tp_ev[2] = {};       // around each k_temporal launch (kernel_ms)
 };
+static_assert(ftk::kTemporalMinWeight == FT_TEMPORAL_MIN_WEIGHT, "the header states the constant k_temporal uses");
 
 namespace {
 
@@ -411,6 +427,8 @@ void ft_destroy(ft_context* c) {
         for (DeviceBuf* b : {&c->d_out, &c->d_out8, &c->d_out_index, &c->d_pixels, &c->d_jitter, &c->d_wave_counts, &c->d_dbg_in, &c->d_dbg_out, &c->d_aov_pixels, &c->d_aov_jitter, &c->d_aov_out, &c->d_aov_ctr, &c->d_dn_guides, &c->d_dn_u[0], &c->d_dn_u[1], &c->d_dn_out8}) b->release();
         for (auto& f : c->slots) f.release();
         c->prog.release();
+        c->temporal.release();
+        for (hipEvent_t& e : c->tp_ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
         if (c->classified) (void)hipEventDestroy(c->classified);
         for (hipEvent_t& e : c->acc_free) if (e) { (void)hipEventDestroy(e); e = nullptr; }
         for (hipEvent_t& e : c->aov_ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
@@ -547,9 +565,17 @@ static void progressive_close(ft_context* c) {
     for (ft_context* d : devices(c)) { if (!d->host_only) (void)hipSetDevice(d->device); d->prog.release(); }
 }
 
+// Ends the temporal accumulation of a context (its buffers are freed): leaf ids are only comparable within one commit.
+static void temporal_close(ft_context* c) {
+    if (!c->temporal.open) return;
+    (void)hipSetDevice(c->device);
+    c->temporal.release();
+}
+
 int32_t ft_scene_clear(ft_context* c) {
     if (!c) return FT_ERR_INVALID;
     progressive_close(c);
+    temporal_close(c);
     c->graph.nodes.clear(); c->graph.lights.clear(); c->graph.root = -1; c->committed = false;
     return FT_OK;
 }
@@ -589,10 +615,11 @@ static int32_t retire_pending(ft_context* c, ft_stats* stats);
 static bool any_pending(const ft_context* c, bool on_second_main = false) { for (const auto& f : c->slots) if (f.pending && (!on_second_main || f.main_ix != 0)) return true; return false; }
 static int32_t commit_scene(ft_context* c);
 
-// A caller's commit ends the progressive accumulation; the re-commit of with_growing_hit_lists (commit_scene) does not.
+// A caller's commit ends the progressive and the temporal accumulation; the re-commit of with_growing_hit_lists (commit_scene) does not.
 int32_t ft_scene_commit(ft_context* c) {
     if (!c) return FT_ERR_INVALID;
     progressive_close(c);
+    temporal_close(c);
     return commit_scene(c);
 }
 
@@ -1853,6 +1880,189 @@ int32_t ft_denoise(ft_context* c, const ft_camera* cam, int32_t res_h, int32_t r
         return FT_ERR_UNSUPPORTED;
     }
     return with_growing_hit_lists(c, [&] { return denoise_single(c, q, sample, P, rgba8 != 0, out, stats); });
+}
+
+// ------------------------------------------------------------------------------------------ reprojected frame accumulation
+// ft_temporal_* (functracer_hip.h).  The guide pass is ft_render_aov's again (aov_windows: p, n, leaf), its windows stay
+// on the device, and one k_temporal per window blends the frame's colours with the previous history set and writes the other one.
+static ftk::TemporalSet temporal_set(const DeviceBuf& b, size_t n_px) {
+    ftk::TemporalSet s{};
+    double* plane = b.as<double>();                                 // M, Q and N first: ft_temporal_fetch reads them as one run
+    for (int k = 0; k < 3; ++k) { s.m[k] = plane + (size_t)k * n_px; s.q[k] = plane + (size_t)(3 + k) * n_px; s.p[k] = plane + (size_t)(7 + k) * n_px; s.n[k] = plane + (size_t)(10 + k) * n_px; }
+    s.len = plane + 6 * n_px;
+    s.leaf = reinterpret_cast<int32_t*>(plane + 13 * n_px);
+    return s;
+}
+
+int32_t ft_temporal_begin(ft_context* c, int32_t res_h, int32_t res_v, const ft_rect* tiles, int32_t n_tiles) {
+    if (!c) return FT_ERR_INVALID;
+    if (res_h < 2 || res_v < 2 || (tiles && n_tiles < 1) || (int64_t)res_h * res_v > (int64_t)0x7FFFFFFF) { c->err = "bad ft_temporal_begin argument"; return FT_ERR_INVALID; }
+    if (!need_device(c)) return FT_ERR_NO_DEVICE;
+    if (!c->peers.empty()) {
+        c->err = "ft_temporal_begin: a context over several devices keeps the frame in 8-row bands on different devices and a tap crosses bands; gathering them is not supported";
+        return FT_ERR_UNSUPPORTED;
+    }
+    temporal_close(c);                                              // a second begin replaces the first
+    ft_context::Temporal& T = c->temporal;
+    const int32_t rc = [&]() -> int32_t {
+        FT_HIP(c, hipSetDevice(c->device));
+        const size_t set_bytes = (size_t)res_h * (size_t)res_v * ftk::kTemporalSetBytes;
+        int32_t r;
+        for (DeviceBuf& b : T.d_set) {                              // N = 0 everywhere: no tap finds history (the rest is cleared with it)
+            if ((r = ensure(c, b, set_bytes)) != FT_OK) return r;
+            FT_HIP(c, hipMemsetAsync(b.p, 0, set_bytes, c->stream));
+        }
+        if ((r = ensure(c, T.d_ctr, 2 * sizeof(unsigned long long))) != FT_OK) return r;
+        FT_HIP(c, hipStreamSynchronize(c->stream));
+        return FT_OK;
+    }();
+    if (rc != FT_OK) { T.release(); return rc; }
+    T.open = true; T.res_h = res_h; T.res_v = res_v;
+    T.rects = clip_rects(RenderRequest{nullptr, res_h, res_v, 1, kNoJitter, 0, 0, tiles, n_tiles, 0});
+    for (const ft_rect& r : T.rects) T.n_pix += (int64_t)r.w * r.h;
+    return FT_OK;
+}
+
+static int32_t temporal_single(ft_context* c, const RenderRequest& q, int32_t sample, const ft_temporal_params& P, bool rgba8, void* out, ft_stats* stats) {
+    const auto wall0 = std::chrono::steady_clock::now();
+    FT_HIP(c, hipSetDevice(c->device));
+    int32_t rc;
+    if (any_pending(c) && (rc = retire_pending(c, nullptr)) != FT_OK) return rc;
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    ft_context::Temporal& T = c->temporal;
+    if (c->last_n_pix <= 0 || c->last_format != 0 || c->last_res_h != T.res_h || c->last_res_v != T.res_v) {
+        c->err = c->last_n_pix <= 0 ? "ft_temporal_accumulate: no frame rendered yet" : c->last_format != 0 ? "ft_temporal_accumulate: the frame in HBM is RGBA8 (ft_render_rgba8); the accumulation needs the FP64 frame"
+                                                                                                               : "ft_temporal_accumulate: the frame in HBM has another size than ft_temporal_begin fixed";
+        return FT_ERR_STATE;
+    }
+    std::vector<uint32_t> px;
+    (void)list_pixels(T.rects, T.res_h, px);
+    if (!c->committed) { c->err = "scene not committed (ft_scene_commit)"; return FT_ERR_STATE; }
+    FT_HIP(c, hipStreamSynchronize(c->stream));                     // the frame may have been written on another stream (fetch_single)
+    for (hipStream_t m : c->more_mains) if (m) FT_HIP(c, hipStreamSynchronize(m));
+    FT_HIP(c, hipStreamSynchronize(c->tail));
+    const size_t n_px = (size_t)T.res_h * (size_t)T.res_v;
+    const bool want_rgb = P.to_frame || (out && !rgba8), want_rgba8 = out && rgba8;
+    if (want_rgb && (rc = ensure(c, T.d_rgb, n_px * 24)) != FT_OK) return rc;
+    if (want_rgba8 && (rc = ensure(c, T.d_rgba8, n_px * 4)) != FT_OK) return rc;
+    FT_HIP(c, hipMemsetAsync(T.d_ctr.p, 0, 2 * sizeof(unsigned long long), c->stream));
+    const ftk::Camera cam = make_camera(*q.cam, T.res_h, T.res_v);
+    double kernel_ms = 0.0;
+    int32_t n_launches = 0;
+    AovRun run;
+    hipEvent_t* const ev = c->tp_ev;
+    for (int k = 0; k < 2; ++k) if (!ev[k]) FT_HIP(c, hipEventCreate(&ev[k]));
+    const bool want[8] = {false, true, true, false, false, true, false, false};   // p, n, leaf
+    rc = aov_windows(c, q, sample, want, px, run, [&](int64_t p0, uint32_t n, const AovPlanes& pl, char* dev) -> int32_t {
+        ftk::TemporalArgs a{};
+        a.pixel_ids = c->d_aov_pixels.as<uint32_t>(); a.first = (uint32_t)p0; a.n = n;
+        a.p_plane = reinterpret_cast<const double*>(dev + pl.off[1]); a.n_plane = reinterpret_cast<const double*>(dev + pl.off[2]);
+        a.leaf = reinterpret_cast<const int32_t*>(dev + pl.off[5]); a.stride = n;
+        a.frame = c->d_out.as<double>();
+        a.prev = temporal_set(T.d_set[T.prev], n_px); a.cur = temporal_set(T.d_set[T.prev ^ 1], n_px);
+        for (int k = 0; k < 3; ++k) { a.o[k] = T.cam.o[k]; a.i[k] = T.cam.i[k]; a.j[k] = T.cam.j[k]; a.k[k] = T.cam.k[k]; }
+        a.tlx = T.cam.tlx; a.tly = T.cam.tly; a.pw = T.cam.pw; a.ph = T.cam.ph;
+        a.res_h = T.res_h; a.res_v = T.res_v; a.has_prev = T.calls > 0 ? 1 : 0;
+        a.max_history = (double)P.max_history; a.min_normal_dot = P.min_normal_dot;
+        a.tol_scale = P.position_tolerance_px * std::max(T.cam.pw, T.cam.ph);
+        a.out_rgb = want_rgb ? T.d_rgb.as<double>() : nullptr; a.out8 = want_rgba8 ? T.d_rgba8.as<uint8_t>() : nullptr;
+        a.counters = T.d_ctr.as<unsigned long long>();
+        FT_HIP(c, hipEventRecord(ev[0], c->stream));
+        ftk::launch_temporal(c->stream, a);
+        FT_HIP(c, hipGetLastError());
+        FT_HIP(c, hipEventRecord(ev[1], c->stream));
+        ++n_launches;
+        FT_HIP(c, hipStreamSynchronize(c->stream));
+        float ms = 0.0f;
+        if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) kernel_ms += ms;
+        return FT_OK;
+    });
+    if (rc != FT_OK) return rc;                                     // nothing was flipped: the history is as it was
+    unsigned long long ctr[2] = {0, 0};
+    if (!px.empty()) FT_HIP(c, hipMemcpy(ctr, T.d_ctr.p, sizeof ctr, hipMemcpyDeviceToHost));
+    if (out && (rc = copy_rects_out(c, out, rgba8 ? T.d_rgba8.p : T.d_rgb.p, rgba8 ? 4 : 24, T.res_h, T.rects, nullptr)) != FT_OK) return rc;
+    if (P.to_frame && !px.empty()) {                                // the means replace the tile pixels of the frame, once the call can no longer fail
+        const size_t pitch = (size_t)T.res_h * 24;
+        for (const ft_rect& r : T.rects) {
+            const size_t off = (size_t)r.y0 * pitch + (size_t)r.x0 * 24;
+            FT_HIP(c, hipMemcpy2DAsync(c->d_out.as<char>() + off, pitch, T.d_rgb.as<char>() + off, pitch, (size_t)r.w * 24, (size_t)r.h, hipMemcpyDeviceToDevice, c->stream));
+        }
+        FT_HIP(c, hipStreamSynchronize(c->stream));
+        c->zero_signature[0] = 0;                                   // (as a progressive pass: the blocks the last ft_render left as Colour.Zero hold means now)
+    }
+    T.prev ^= 1; T.cam = cam; T.calls += 1;
+    T.with_history = (int64_t)ctr[0]; T.at_max = (int64_t)ctr[1];
+    if (stats) {
+        stats->rays_primary = (uint64_t)run.n_pix; stats->hits_primary = run.hits;
+        stats->kernel_ms = run.kernel_ms + kernel_ms; stats->trace_kernel_ms = run.kernel_ms; stats->n_launches = run.n_launches + n_launches;
+        stats->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+    }
+    return FT_OK;
+}
+
+int32_t ft_temporal_accumulate(ft_context* c, const ft_camera* cam, int32_t spp, const double* jitter_xy, int32_t sample, uint64_t seed,
+                               const ft_temporal_params* params, int32_t rgba8, void* out, ft_stats* stats) {
+    if (!c) return FT_ERR_INVALID;
+    if (spp == 0) { c->err = "ft_temporal_accumulate: corner sampling (spp == 0) has no per-sample geometry ray to take the surfaces from"; return FT_ERR_UNSUPPORTED; }
+    if (spp < 0 || !jitter_xy) { c->err = "bad ft_temporal_accumulate argument"; return FT_ERR_INVALID; }
+    if (sample < 0 || sample >= spp) { c->err = "ft_temporal_accumulate: sample outside [0, spp)"; return FT_ERR_INVALID; }
+    if (!cam || !params) { c->err = "ft_temporal_accumulate: null cam or params"; return FT_ERR_INVALID; }
+    const ft_temporal_params& P = *params;
+    if (P.max_history < 1) { c->err = "ft_temporal_accumulate: max_history below 1"; return FT_ERR_INVALID; }
+    if (!(P.min_normal_dot >= -1.0 && P.min_normal_dot <= 1.0)) { c->err = "ft_temporal_accumulate: min_normal_dot is NaN or outside [-1, 1]"; return FT_ERR_INVALID; }
+    if (!(P.position_tolerance_px > 0.0)) { c->err = "ft_temporal_accumulate: position_tolerance_px is not > 0"; return FT_ERR_INVALID; }
+    if (!need_device(c)) return FT_ERR_NO_DEVICE;
+    if (!c->peers.empty()) {
+        c->err = "ft_temporal_accumulate: a context over several devices keeps the frame in 8-row bands on different devices and a tap crosses bands; gathering them is not supported";
+        return FT_ERR_UNSUPPORTED;
+    }
+    if (!c->temporal.open) { c->err = "no temporal accumulation (ft_temporal_begin; a caller's ft_scene_commit or ft_scene_clear ends it)"; return FT_ERR_STATE; }
+    const RenderRequest q{cam, c->temporal.res_h, c->temporal.res_v, spp, jitter_xy, 0, seed, nullptr, 0, 0};   // (the pixel list is made from the begin's rects)
+    return with_growing_hit_lists(c, [&] { return temporal_single(c, q, sample, P, rgba8 != 0, out, stats); });
+}
+
+int32_t ft_temporal_fetch(ft_context* c, double* mean_rgb, double* stderr_rgb, double* length) {
+    if (!c) return FT_ERR_INVALID;
+    if (!need_device(c)) return FT_ERR_NO_DEVICE;
+    const ft_context::Temporal& T = c->temporal;
+    if (!T.open) { c->err = "no temporal accumulation (ft_temporal_begin)"; return FT_ERR_STATE; }
+    const size_t n_px = (size_t)T.res_h * (size_t)T.res_v;
+    std::vector<double> h(7 * n_px);                                // M, Q, N of the set the last call wrote
+    FT_HIP(c, hipSetDevice(c->device));
+    FT_HIP(c, hipStreamSynchronize(c->stream));
+    FT_HIP(c, hipMemcpy(h.data(), T.d_set[T.prev].p, h.size() * 8, hipMemcpyDeviceToHost));
+    for (const ft_rect& r : T.rects)
+        for (int y = r.y0; y < r.y0 + r.h; ++y) for (int x = r.x0; x < r.x0 + r.w; ++x) {
+            const size_t id = (size_t)y * (size_t)T.res_h + (size_t)x;
+            const double N = h[6 * n_px + id];
+            for (int ch = 0; ch < 3; ++ch) {
+                const double M = h[(size_t)ch * n_px + id];
+                if (mean_rgb) mean_rgb[3 * id + ch] = M;
+                if (stderr_rgb) {
+                    double se = 0.0;
+                    if (N >= 2.0) { const double mm = M * M, v = h[(size_t)(3 + ch) * n_px + id] - mm; se = std::sqrt((v > 0.0 ? v : 0.0) / N); }
+                    stderr_rgb[3 * id + ch] = se;
+                }
+            }
+            if (length) length[id] = N;
+        }
+    return FT_OK;
+}
+
+int32_t ft_temporal_status(ft_context* c, int64_t out[4]) {
+    if (!c || !out) return FT_ERR_INVALID;
+    if (!need_device(c)) return FT_ERR_NO_DEVICE;
+    const ft_context::Temporal& T = c->temporal;
+    if (!T.open) { c->err = "no temporal accumulation (ft_temporal_begin)"; return FT_ERR_STATE; }
+    out[0] = T.calls; out[1] = T.n_pix; out[2] = T.with_history; out[3] = T.at_max;
+    return FT_OK;
+}
+
+int32_t ft_temporal_end(ft_context* c) {
+    if (!c) return FT_ERR_INVALID;
+    if (!need_device(c)) return FT_ERR_NO_DEVICE;
+    temporal_close(c);
+    return FT_OK;
 }
 
 // ------------------------------------------------------------------------------------------ debug / tests

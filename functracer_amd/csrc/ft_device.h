@@ -240,6 +240,30 @@ struct DenoiseArgs {
 void launch_denoise(hipStream_t stream, const DenoiseArgs& a, bool last);
 void launch_denoise_quantise(hipStream_t stream, const double* rgb, uint8_t* out8, uint32_t n_px);   // ft_quantise_rgba8 on the device
 
+// ft_temporal_* (ft_temporal.hip; the accumulation is defined in functracer_hip.h and DESIGN.md 12).  A history set in FRAME layout
+// (index y * res_h + x), one plane per component as DenoiseGuides: what decides whether a tap takes part first (leaf, N: 12 bytes,
+// then n, p: 48), then what it contributes (M, Q: 48).
+struct TemporalSet { double* m[3]; double* q[3]; double* len; double* p[3]; double* n[3]; int32_t* leaf; };
+constexpr size_t kTemporalSetBytes = 13 * 8 + 4;
+constexpr double kTemporalMinWeight = 1.0 / 16.0;   // FT_TEMPORAL_MIN_WEIGHT (functracer_hip.h; ft_capi.cpp asserts that they agree)
+// k_temporal: one lane per entry of a window of the pixel list.  k_aov's planes of the window (p, n as three planes of `stride`
+// entries, leaf; by position) and the frame's colour at the pixel are blended with what `prev` holds where the pixel's point projects
+// to through the previous call's image plane (o, i, j, k, tlx, tly, pw, ph); the pixel's record goes into `cur`, its mean into
+// out_rgb (frame layout, 3 doubles per pixel) and out8 (RGBA8) where those are non-null.  has_prev == 0: the first call after begin.
+// tol_scale = position_tolerance_px * max(pw, ph).  counters[0] += pixels with valid history, counters[1] += pixels at max_history.
+struct TemporalArgs {
+    const uint32_t* pixel_ids; uint32_t first, n;
+    const double *p_plane, *n_plane; const int32_t* leaf; uint32_t stride;
+    const double* frame;
+    TemporalSet prev, cur;
+    double o[3], i[3], j[3], k[3], tlx, tly, pw, ph;
+    int32_t res_h, res_v, has_prev;
+    double max_history, min_normal_dot, tol_scale;
+    double* out_rgb; uint8_t* out8;
+    unsigned long long* counters;
+};
+void launch_temporal(hipStream_t stream, const TemporalArgs& a);
+
 // Debug: closest hit / blocked for arbitrary rays (no slightOffset).
 void launch_debug_closest(const Launch& L, const DevScene& S, const double* o, const double* d, uint32_t n,
                           int32_t* hit, double* t, double* p, double* nrm, double* colour, unsigned long long* overflow);

@@ -1,0 +1,113 @@
+// ft_temporal.hip — the kernel of ft_temporal_accumulate (include/functracer_hip.h): the FP64 frame in HBM blended with
+// the history of the surface point each pixel shows, fetched where that point lay in the previous call's image.  A translation unit of
+// its own, as ft_denoise.hip: nothing here is inlined into, or shares registers or LDS with, the tracing kernels of ft_kernels.hip.
+//
+// One lane per entry of a window of the pixel list, queued behind the window's k_aov.  The list runs in 8x8 blocks (Z order inside a
+// block), so a wavefront holds one block: what it reads by pixel id and what it writes are 8 runs of 64 bytes per plane (192 of the
+// interleaved colours), and its 4 x 64 taps fall into a region of about 9x9 pixels of the previous set, 8-byte planes again: the four
+// taps of a lane and those of its neighbours are the same cache lines, served by the L2; the kernel stages nothing.  A tap is tested
+// in the order of what it costs: leaf and N (12 bytes), n (24), p (24), and only one that takes part reads M and Q (48).
+#include <hip/hip_runtime.h>
+
+#include "ft_device.h"
+
+namespace ftk {
+namespace {
+
+__device__ __forceinline__ bool finite3(double a, double b, double c) { return isfinite(a) && isfinite(b) && isfinite(c); }
+
+// Image.write's toByte (Image.fs:36, Math.fs:12-16), as ft_quantise_rgba8: clamp to [0, 1] (a NaN passes the clamp), * 255, truncate.
+__device__ __forceinline__ uint32_t to_byte(double x) {
+    if (x > 1.0) x = 1.0; else if (x < 0.0) x = 0.0;
+    x = x * 255.0;
+    return (x != x) ? 0u : (uint32_t)x;
+}
+
+__global__ __launch_bounds__(kBlock) void k_temporal(TemporalArgs a) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= a.n) return;
+    const size_t id = a.pixel_ids[a.first + i];                     // y * res_h + x
+    const size_t S = a.stride;
+    const int32_t leaf = a.leaf[i];
+    const bool hit = leaf >= 0;
+    const double c0 = a.frame[3 * id], c1 = a.frame[3 * id + 1], c2 = a.frame[3 * id + 2];
+    double p0 = 0.0, p1 = 0.0, p2 = 0.0, n0 = 0.0, n1 = 0.0, n2 = 0.0;
+    if (hit) {
+        p0 = a.p_plane[i]; p1 = a.p_plane[S + i]; p2 = a.p_plane[2 * S + i];
+        n0 = a.n_plane[i]; n1 = a.n_plane[S + i]; n2 = a.n_plane[2 * S + i];
+    }
+    double W = 0.0, m0 = 0.0, m1 = 0.0, m2 = 0.0, q0 = 0.0, q1 = 0.0, q2 = 0.0, len = 0.0;
+    if (hit && a.has_prev) {
+        const double v0 = p0 - a.o[0], v1 = p1 - a.o[1], v2 = p2 - a.o[2];
+        const double zc = v0 * a.k[0] + v1 * a.k[1] + v2 * a.k[2];
+        if (zc > 0.0) {                                             // the inverse of rayThroughPixel (Image.fs:83-89) at jitter 0
+            const double fx = ((v0 * a.i[0] + v1 * a.i[1] + v2 * a.i[2]) / zc - a.tlx) / a.pw;
+            const double fy = (a.tly - (v0 * a.j[0] + v1 * a.j[1] + v2 * a.j[2]) / zc) / a.ph;
+            // outside [-1, res): none of the four taps lies in the frame (a NaN fails every comparison)
+            if (fx >= -1.0 && fx < (double)a.res_h && fy >= -1.0 && fy < (double)a.res_v) {
+                const double fx0 = floor(fx), fy0 = floor(fy);
+                const int x0 = (int)fx0, y0 = (int)fy0;
+                const double wx = fx - fx0, wy = fy - fy0;
+                const double tol = a.tol_scale * zc;
+                const double tol2 = tol * tol;
+#pragma unroll
+                for (int dy = 0; dy < 2; ++dy) {
+                    const int qy = y0 + dy;
+                    if (qy < 0 || qy >= a.res_v) continue;
+#pragma unroll
+                    for (int dx = 0; dx < 2; ++dx) {
+                        const int qx = x0 + dx;
+                        if (qx < 0 || qx >= a.res_h) continue;
+                        const size_t q = (size_t)qy * (size_t)a.res_h + (size_t)qx;
+                        const double lq = a.prev.len[q];
+                        if (!(lq >= 1.0) || a.prev.leaf[q] != leaf) continue;
+                        if (!(n0 * a.prev.n[0][q] + n1 * a.prev.n[1][q] + n2 * a.prev.n[2][q] >= a.min_normal_dot)) continue;
+                        const double e0 = p0 - a.prev.p[0][q], e1 = p1 - a.prev.p[1][q], e2 = p2 - a.prev.p[2][q];
+                        if (!(e0 * e0 + e1 * e1 + e2 * e2 <= tol2)) continue;
+                        const double hm0 = a.prev.m[0][q], hm1 = a.prev.m[1][q], hm2 = a.prev.m[2][q];
+                        const double hq0 = a.prev.q[0][q], hq1 = a.prev.q[1][q], hq2 = a.prev.q[2][q];
+                        if (!finite3(hm0, hm1, hm2) || !finite3(hq0, hq1, hq2)) continue;
+                        const double b = (dx ? wx : 1.0 - wx) * (dy ? wy : 1.0 - wy);
+                        W += b; len += b * lq;
+                        m0 += b * hm0; m1 += b * hm1; m2 += b * hm2;
+                        q0 += b * hq0; q1 += b * hq1; q2 += b * hq2;
+                    }
+                }
+            }
+        }
+    }
+    const double s0 = c0 * c0, s1 = c1 * c1, s2 = c2 * c2;          // statements of their own: not fused into the differences below
+    const bool finite = finite3(c0, c1, c2);
+    const bool history = finite && W >= kTemporalMinWeight;
+    double N = finite ? 1.0 : 0.0, M0 = c0, M1 = c1, M2 = c2, Q0 = s0, Q1 = s1, Q2 = s2;
+    if (history) {
+        m0 /= W; m1 /= W; m2 /= W; q0 /= W; q1 /= W; q2 /= W;
+        N = len / W + 1.0;
+        if (N > a.max_history) N = a.max_history;
+        M0 = m0 + (c0 - m0) / N; M1 = m1 + (c1 - m1) / N; M2 = m2 + (c2 - m2) / N;
+        Q0 = q0 + (s0 - q0) / N; Q1 = q1 + (s1 - q1) / N; Q2 = q2 + (s2 - q2) / N;
+    }
+    a.cur.m[0][id] = M0; a.cur.m[1][id] = M1; a.cur.m[2][id] = M2;
+    a.cur.q[0][id] = Q0; a.cur.q[1][id] = Q1; a.cur.q[2][id] = Q2;
+    a.cur.len[id] = N;
+    a.cur.p[0][id] = p0; a.cur.p[1][id] = p1; a.cur.p[2][id] = p2;
+    a.cur.n[0][id] = n0; a.cur.n[1][id] = n1; a.cur.n[2][id] = n2;
+    a.cur.leaf[id] = leaf;
+    if (a.out_rgb) { a.out_rgb[3 * id] = M0; a.out_rgb[3 * id + 1] = M1; a.out_rgb[3 * id + 2] = M2; }
+    if (a.out8) reinterpret_cast<uint32_t*>(a.out8)[id] = to_byte(M0) | (to_byte(M1) << 8) | (to_byte(M2) << 16) | 0xFF000000u;
+    // the call's two counts: one atomic per wavefront and count (the lanes past the window's end left above; lane 0 never does alone)
+    const unsigned long long with_history = __ballot(history), at_max = __ballot(finite && N == a.max_history);
+    if ((threadIdx.x & 63u) == 0u) {
+        if (with_history) atomicAdd(&a.counters[0], (unsigned long long)__popcll(with_history));
+        if (at_max) atomicAdd(&a.counters[1], (unsigned long long)__popcll(at_max));
+    }
+}
+
+} // namespace
+
+void launch_temporal(hipStream_t stream, const TemporalArgs& a) {
+    if (a.n == 0) return;
+    hipLaunchKernelGGL(k_temporal, dim3((a.n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, a);
+}
+
+} // namespace ftk

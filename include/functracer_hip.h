@@ -356,6 +356,64 @@ int32_t ft_denoise(ft_context* ctx, const ft_camera* cam, int32_t res_h, int32_t
                    const double* jitter_xy, int32_t sample, uint64_t seed, const ft_rect* tiles, int32_t n_tiles,
                    const ft_denoise_params* params, int32_t rgba8, void* out, ft_stats* stats);
 
+/* ---- reprojected frame accumulation for a moving camera ---------------------------------------- */
+/* ft_temporal_* accumulates the FP64 frames a host renders along a camera path: each pixel's surface point is projected into the
+ * previous call's image, what was accumulated there is fetched, checked for being the same surface and blended with the new frame.
+ * The scene is static (leaf ids and points are compared in world space).  State lives in the context, on a single device: two history
+ * sets in frame layout (row 0 = top), "previous" and "current", flipped after every call; per frame pixel a set holds the mean M (3
+ * doubles), the mean of squares Q (3), the history length N (1), p and n (3 each) and leaf (int32): 108 bytes; and the previous call's
+ * image plane cam' (ImagePlane.create of its ft_camera, Image.fs:48-81: o' i' j' k', the top-left pixel centre tlx' tly', the pixel
+ * size pw' ph').  ft_temporal_begin sets N = 0 everywhere in both sets.
+ * ft_temporal_accumulate takes c(x), the FP64 frame in HBM (what ft_fetch_frame would return); p(x), n(x), leaf(x) as ft_render_aov
+ * defines them for the call's (cam, res, spp, jitter_xy, sample, seed, tiles); T, the tile pixels fixed at begin.  For every x in T:
+ *  1. Projection, for a hit pixel (leaf(x) >= 0) with a previous call behind it: v = p(x) - o', zc = v.k'; if zc > 0:
+ *     fx = ((v.i')/zc - tlx') / pw', fy = (tly' - (v.j')/zc) / ph' (the inverse of rayThroughPixel, Image.fs:83-89, at jitter 0: pixel
+ *     centres sit at integer coordinates); x0 = floor(fx), y0 = floor(fy), wx = fx - x0, wy = fy - y0.
+ *  2. Taps q = (x0+dx, y0+dy), dy = 0, 1 outer, dx = 0, 1 inner (the summation order), b_q = (dx ? wx : 1-wx) * (dy ? wy : 1-wy).  A tap
+ *     is valid iff q is in the frame, N'(q) >= 1, leaf'(q) == leaf(x), n(x).n'(q) >= min_normal_dot,
+ *     |p(x)-p'(q)|^2 <= (position_tolerance_px * max(pw', ph') * zc)^2, and M'(q), Q'(q) are finite in every channel.
+ *  3. W = sum of b_q over the valid taps; the history is valid iff W >= FT_TEMPORAL_MIN_WEIGHT (which also makes the result continuous
+ *     where fx crosses an integer).  Then M_h = (sum b_q M'(q)) / W, Q_h and N_h likewise; N(x) = min(N_h + 1, max_history);
+ *     M(x) = M_h + (c(x) - M_h) / N(x); Q(x) = Q_h + (c(x)^2 - Q_h) / N(x) per channel.
+ *  4. No history (a miss pixel, the first call after begin, zc <= 0, W below the constant): N(x) = 1, M(x) = c(x) bit for bit,
+ *     Q(x) = c(x)^2.
+ *  5. Non-finite data never spreads: a pixel whose c(x) has a non-finite channel stores N(x) = 0, M(x) = c(x) (and Q(x) = c(x)^2), so
+ *     no later tap uses it; clause 2 already rejects non-finite history.
+ *  6. M, Q, N, p(x), n(x), leaf(x) go into the current set (p = n = 0 for a miss); pixels outside T are never written and keep N = 0.
+ *     The sets are then flipped and cam' = cam.
+ *  7. M(x) for x in T goes to `out`, laid out as ft_render's out_rgb, or as ft_render_rgba8's bytes when rgba8 != 0 (quantised on the
+ *     device with ft_quantise_rgba8's arithmetic); out may be NULL.  With to_frame != 0, M also replaces the tile pixels of the FP64
+ *     frame in HBM, so ft_fetch_frame and ft_denoise see the accumulated frame (and which blocks the last ft_render left as Colour.Zero
+ *     is forgotten, as after a progressive pass: a later ft_render is bit-identical all the same).
+ * With a static camera this is the running mean of the frames up to max_history, an exponential average after that.
+ * Lifetime: one accumulation per context (a second begin replaces the first); a caller's ft_scene_commit or ft_scene_clear ends it,
+ * because leaf ids are only comparable within one commit; the re-commit by which a blocking call grows the CSG hit lists does not.
+ * Errors of ft_temporal_accumulate, checked before anything runs, in this order: spp == 0 FT_ERR_UNSUPPORTED; then FT_ERR_INVALID
+ * for spp < 0 or a null jitter_xy, sample outside [0, spp), null cam or params, max_history < 1, min_normal_dot NaN or outside
+ * [-1, 1], position_tolerance_px not > 0; then a host-only context FT_ERR_NO_DEVICE; a context over several devices
+ * FT_ERR_UNSUPPORTED (taps cross the bands the frame lives in, as ft_denoise's); then FT_ERR_STATE for no begin, an accumulation
+ * ended by a commit, or no FP64 frame of the begin's size in HBM.  ft_temporal_begin: FT_ERR_INVALID for a size below 2 x 2 or
+ * tiles != NULL with n_tiles < 1, then FT_ERR_NO_DEVICE and FT_ERR_UNSUPPORTED as above.
+ * The call blocks and retires queued frames first.  Hit lists that overflow grow and the call runs again (csg_auto_grow); a call that
+ * failed leaves the history as it was.  stats: rays_primary, hits_primary, kernel_ms, wall_ms, n_launches, and trace_kernel_ms = the
+ * share of kernel_ms that is the guide pass (k_aov); the rest 0.  The cached pixel list, the level hint, a progressive accumulation
+ * and (without to_frame) the frame buffer stay untouched.
+ * Device memory: 216 bytes per frame pixel (the two sets), 24 for the FP64 result and 4 for RGBA8 when asked for, beside
+ * ft_render_aov's window (52 bytes per pixel of it: p, n, leaf). */
+#define FT_TEMPORAL_MIN_WEIGHT 0.0625   /* 1/16 */
+typedef struct ft_temporal_params { int32_t max_history, to_frame; double min_normal_dot, position_tolerance_px; } ft_temporal_params;
+int32_t ft_temporal_begin(ft_context* ctx, int32_t res_h, int32_t res_v, const ft_rect* tiles, int32_t n_tiles);
+int32_t ft_temporal_accumulate(ft_context* ctx, const ft_camera* cam, int32_t spp, const double* jitter_xy, int32_t sample, uint64_t seed,
+                               const ft_temporal_params* params, int32_t rgba8, void* out, ft_stats* stats);
+/* The accumulated state of the tile pixels (frame-shaped planes; other pixels are not written); any pointer may be NULL: the mean M
+ * (res_v x res_h x 3), the standard error of the mean per channel, sqrt(max(0, Q - M*M) / max(N, 1)) with the product unfused and 0
+ * where N < 2 (same shape), and the history length N (res_v x res_h).  FT_ERR_STATE without an accumulation. */
+int32_t ft_temporal_fetch(ft_context* ctx, double* mean_rgb, double* stderr_rgb, double* length);
+/* out = calls since begin, tile pixels, pixels with valid history in the last call, pixels whose N is max_history after it. */
+int32_t ft_temporal_status(ft_context* ctx, int64_t out[4]);
+/* End the accumulation and free its buffers (FT_OK when there is none). */
+int32_t ft_temporal_end(ft_context* ctx);
+
 /* Closest hit of single rays through the device path (Scene.intersectScene, Scene.fs:118, after
  * Shading.slightOffset is NOT applied): for tests.  Outputs per ray: t, p[3], n[3], material index
  * resolved colour[3]; hit[i] = 0 when the ray misses. */
