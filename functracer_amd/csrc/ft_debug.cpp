@@ -1,0 +1,180 @@
+// ft_debug.cpp — ft_debug_*: explicit ray queries through the device paths and views of the committed scene, for the tests.
+#include "ft_context.h"
+using namespace ftc;
+
+extern "C" {
+
+// ------------------------------------------------------------------------------------------ debug / tests
+// The start of a ray query (ft_debug_closest / ft_debug_blocked): the checks, the device, the rays into d_dbg_in (origins, directions and,
+// when `max_dist` is given, the lengths), room for `out_bytes` per ray in d_dbg_out, and the overflow count cleared (in slot 0's counters).
+static int32_t debug_rays_in(ft_context* c, const double* origins, const double* dirs, const double* max_dist, int64_t n, size_t out_bytes) {
+    if (!need_device(c)) return FT_ERR_NO_DEVICE;
+    if (!c->committed) { c->err = "scene not committed"; return FT_ERR_STATE; }
+    if (n == 0) return FT_OK;
+    FT_HIP(c, hipSetDevice(c->device));
+    int32_t rc;
+    const size_t N = (size_t)n;
+    if ((rc = ensure(c, c->d_dbg_in, N * (max_dist ? 56 : 48))) != FT_OK) return rc;
+    if ((rc = ensure(c, c->d_dbg_out, N * out_bytes)) != FT_OK) return rc;
+    double* din = c->d_dbg_in.as<double>();
+    FT_HIP(c, hipMemcpyAsync(din, origins, N * 24, hipMemcpyHostToDevice, c->stream));
+    FT_HIP(c, hipMemcpyAsync(din + 3 * N, dirs, N * 24, hipMemcpyHostToDevice, c->stream));
+    if (max_dist) FT_HIP(c, hipMemcpyAsync(din + 6 * N, max_dist, N * 8, hipMemcpyHostToDevice, c->stream));
+    c->slots[0].fc_clean = false;
+    FT_HIP(c, hipMemsetAsync(c->slots[0].d_fc.p, 0, sizeof(unsigned long long), c->stream));   // the overflow count of this query
+    return FT_OK;
+}
+// ... and its end, behind the copies of the results: the overflow count read back, the stream synchronised.
+static int32_t debug_rays_done(ft_context* c) {
+    unsigned long long n_overflow = 0;
+    FT_HIP(c, hipMemcpyAsync(&n_overflow, c->slots[0].d_fc.p, sizeof n_overflow, hipMemcpyDeviceToHost, c->stream));
+    FT_HIP(c, hipStreamSynchronize(c->stream));
+    if (n_overflow) { c->err = "CSG hit list overflow"; return FT_ERR_OVERFLOW; }
+    return FT_OK;
+}
+
+static int32_t debug_closest(ft_context* c, const double* origins, const double* dirs, int64_t n, int32_t* hit, double* t, double* p, double* nrm, double* colour) {
+    if (!c || !origins || !dirs || n < 0 || !hit || !t || !p || !nrm || !colour) return FT_ERR_INVALID;
+    int32_t rc = debug_rays_in(c, origins, dirs, nullptr, n, 4 + 8 + 72);
+    if (rc != FT_OK || n == 0) return rc;
+    const size_t N = (size_t)n;
+    double* din = c->d_dbg_in.as<double>();
+    double* dt = c->d_dbg_out.as<double>();
+    double* dp = dt + N; double* dn = dp + 3 * N; double* dc = dn + 3 * N;
+    int32_t* dh = reinterpret_cast<int32_t*>(dc + 3 * N);
+    ftk::Launch L{c->stream, c->n_cu * 4, lds_bytes_for(c->flat), 0};
+    ftk::launch_debug_closest(L, c->dev_scene, din, din + 3 * N, (uint32_t)n, dh, dt, dp, dn, dc, c->slots[0].d_fc.as<unsigned long long>());
+    FT_HIP(c, hipGetLastError());
+    FT_HIP(c, hipMemcpyAsync(t, dt, N * 8, hipMemcpyDeviceToHost, c->stream));
+    FT_HIP(c, hipMemcpyAsync(p, dp, N * 24, hipMemcpyDeviceToHost, c->stream));
+    FT_HIP(c, hipMemcpyAsync(nrm, dn, N * 24, hipMemcpyDeviceToHost, c->stream));
+    FT_HIP(c, hipMemcpyAsync(colour, dc, N * 24, hipMemcpyDeviceToHost, c->stream));
+    FT_HIP(c, hipMemcpyAsync(hit, dh, N * 4, hipMemcpyDeviceToHost, c->stream));
+    return debug_rays_done(c);
+}
+int32_t ft_debug_closest(ft_context* c, const double* origins, const double* dirs, int64_t n, int32_t* hit, double* t, double* p, double* nrm, double* colour) {
+    if (!c) return FT_ERR_INVALID;
+    return with_growing_hit_lists(c, [&] { return debug_closest(c, origins, dirs, n, hit, t, p, nrm, colour); });
+}
+
+static int32_t debug_blocked(ft_context* c, const double* origins, const double* dirs, const double* max_dist, int64_t n, int32_t* blocked) {
+    if (!c || !origins || !dirs || !max_dist || n < 0 || !blocked) return FT_ERR_INVALID;
+    int32_t rc = debug_rays_in(c, origins, dirs, max_dist, n, 4);
+    if (rc != FT_OK || n == 0) return rc;
+    const size_t N = (size_t)n;
+    double* din = c->d_dbg_in.as<double>();
+    ftk::Launch L{c->stream, c->n_cu * 4, lds_bytes_for(c->flat), 0};
+    ftk::launch_debug_blocked(L, c->dev_scene, din, din + 3 * N, din + 6 * N, (uint32_t)n, c->d_dbg_out.as<int32_t>(), c->slots[0].d_fc.as<unsigned long long>());
+    FT_HIP(c, hipGetLastError());
+    FT_HIP(c, hipMemcpyAsync(blocked, c->d_dbg_out.p, N * 4, hipMemcpyDeviceToHost, c->stream));
+    return debug_rays_done(c);
+}
+int32_t ft_debug_blocked(ft_context* c, const double* origins, const double* dirs, const double* max_dist, int64_t n, int32_t* blocked) {
+    if (!c) return FT_ERR_INVALID;
+    return with_growing_hit_lists(c, [&] { return debug_blocked(c, origins, dirs, max_dist, n, blocked); });
+}
+
+// getColourForRay (Shading.fs:131-139) for explicit rays through the device path: the rays enter k_bounce as level 0 with weight 1
+// and are followed to their end, so closest hit, shadow queries, shaders and up to max_depth reflection bounces run exactly as they
+// do for a frame's samples.  Streams of soft lights are keyed with seed 0 and sample = ray index.
+static int32_t debug_colour(ft_context* c, const double* origins, const double* dirs, int64_t n, int32_t max_depth, double* rgb) {
+    if (!c || !origins || !dirs || n < 0 || !rgb || max_depth < 0) return FT_ERR_INVALID;
+    if (max_depth > ftk::kMaxBounce) { c->err = "max_depth above 16"; return FT_ERR_UNSUPPORTED; }
+    if (n >= (1ll << 30)) return FT_ERR_INVALID;
+    if (!need_device(c)) return FT_ERR_NO_DEVICE;
+    if (!c->committed) { c->err = "scene not committed"; return FT_ERR_STATE; }
+    if (n == 0) return FT_OK;
+    FT_HIP(c, hipSetDevice(c->device));
+    int32_t rc;
+    if ((rc = ensure_frame_buffers(c, n, true)) != FT_OK) return rc;
+    const size_t N = (size_t)n, cap = (size_t)c->ray_capacity;
+    std::vector<double> soa(7 * N);
+    std::vector<uint32_t> slot(N);
+    for (size_t i = 0; i < N; ++i) {
+        for (int k = 0; k < 3; ++k) { soa[(size_t)k * N + i] = origins[3 * i + k]; soa[(size_t)(3 + k) * N + i] = dirs[3 * i + k]; }
+        soa[6 * N + i] = 1.0; slot[i] = (uint32_t)i;
+    }
+    auto* fc = c->slots[0].d_fc.as<ftk::FrameCounters>();
+    c->slots[0].fc_clean = false;
+    FT_HIP(c, hipMemsetAsync(fc, 0, sizeof(ftk::FrameCounters), c->stream));
+    const ftk::RayBuf rb0 = ray_view(c->d_rays[0], c->ray_capacity), rb1 = ray_view(c->d_rays[1], c->ray_capacity);
+    for (int k = 0; k < 7; ++k) FT_HIP(c, hipMemcpyAsync(c->d_rays[0].as<double>() + (size_t)k * cap, soa.data() + (size_t)k * N, N * 8, hipMemcpyHostToDevice, c->stream));
+    FT_HIP(c, hipMemcpyAsync(rb0.slot, slot.data(), N * 4, hipMemcpyHostToDevice, c->stream));
+    const uint32_t n_rays = (uint32_t)n;
+    FT_HIP(c, hipMemcpyAsync(&fc->cc.n_rays[0], &n_rays, 4, hipMemcpyHostToDevice, c->stream));
+    FT_HIP(c, hipMemsetAsync(c->d_acc[0].p, 0, 3 * N * 8, c->stream));
+    const size_t lds = lds_bytes_for(c->flat);
+    ftk::Launch Lt{c->stream, c->n_cu * c->blocks_bounce, lds, c->variant};
+    ftk::Primary gen{};
+    gen.pixel_ids = nullptr; gen.pix_base = 0; gen.n_pix = n_rays; gen.spp = 1; gen.inv_n_pix = 1.0 / (double)n_rays; gen.seed = 0ull; gen.counts = nullptr; gen.block_map = nullptr;
+    ftk::launch_bounce(Lt, c->dev_scene, gen, rb0, rb1, c->d_acc[0].as<double>(), n_rays, 0, max_depth, true, fc);   // level 0, followed to the end
+    FT_HIP(c, hipGetLastError());
+    std::vector<double> planes(3 * N);
+    FT_HIP(c, hipMemcpyAsync(planes.data(), c->d_acc[0].p, 3 * N * 8, hipMemcpyDeviceToHost, c->stream));
+    struct { ftk::RenderCounters stats[ftk::kStatStripes]; } tail;
+    FT_HIP(c, hipMemcpyAsync(&tail, &fc->stats[0], sizeof tail, hipMemcpyDeviceToHost, c->stream));
+    FT_HIP(c, hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < N; ++i) { rgb[3 * i] = planes[i]; rgb[3 * i + 1] = planes[N + i]; rgb[3 * i + 2] = planes[2 * N + i]; }
+    unsigned long long ovf = 0;
+    for (int k = 0; k < ftk::kStatStripes; ++k) ovf += tail.stats[k].csg_overflow;
+    if (ovf) { c->err = "CSG hit list overflow"; return FT_ERR_OVERFLOW; }
+    return FT_OK;
+}
+int32_t ft_debug_colour(ft_context* c, const double* origins, const double* dirs, int64_t n, int32_t max_depth, double* rgb) {
+    if (!c) return FT_ERR_INVALID;
+    return with_growing_hit_lists(c, [&] { return debug_colour(c, origins, dirs, n, max_depth, rgb); });
+}
+
+/* Diagnostic builds (-DFT_STAMPS): the s_memrealtime stamps k_classify's workgroups left behind (8 per workgroup). */
+int32_t ft_debug_classify_stamps(ft_context* c, unsigned long long* out, int32_t n_groups) {
+    if (!c || !out || n_groups < 1 || n_groups > 2048 || !c->d_wave_counts.p) return FT_ERR_INVALID;
+    if (hipSetDevice(c->device) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return FT_ERR_HIP;
+    return hipMemcpy(out, c->d_wave_counts.as<uint32_t>() + 4096, (size_t)n_groups * 64, hipMemcpyDeviceToHost) == hipSuccess ? FT_OK : FT_ERR_HIP;
+}
+
+int32_t ft_debug_scene_info(ft_context* c, int64_t out[12]) {
+    if (!c || !out) return FT_ERR_INVALID;
+    if (!c->committed) { c->err = "scene not committed"; return FT_ERR_STATE; }
+    const fth::FlatScene& f = c->flat;
+    out[0] = (int64_t)f.leaves.size(); out[1] = (int64_t)f.program.size(); out[2] = (int64_t)f.meshes.size(); out[3] = (int64_t)f.nodes.size() - f.bvh_nodes;
+    out[4] = (int64_t)f.bsp_leaves.size() - f.bvh_leaves; out[5] = (int64_t)(f.tris.size() / 9) - f.bvh_tris; out[6] = f.csg_capacity; out[7] = f.bsp_stack_capacity;   // BSP-only: excludes the device-side BVH
+    int64_t bounded = 0; for (size_t k = 0; k + 1 < f.item_pc.size(); ++k) if (f.cull_items[8 * k + 3] < 1e30f) ++bounded;
+    out[8] = (int64_t)f.item_pc.size() - 1; out[9] = bounded; out[10] = f.unbounded ? 1 : 0; out[11] = f.cull_bundle ? (int64_t)(f.cull_rows.size() / 3) : -1;
+    return FT_OK;
+}
+
+int32_t ft_debug_light_space(ft_context* c, int64_t sizes[4], double* pairs, uint32_t* nodes, double* tris, uint32_t* leaf_pairs) {
+    if (!c || !sizes) return FT_ERR_INVALID;
+    if (!c->committed) { c->err = "scene not committed"; return FT_ERR_STATE; }
+    const fth::FlatScene& f = c->flat;
+    sizes[0] = (int64_t)(f.ls_pairs.size() / ftd::kLsPairDoubles); sizes[1] = (int64_t)(f.ls_nodes.size() / ftd::kLsNodeWords);
+    sizes[2] = (int64_t)(f.ls_tris.size() / 9); sizes[3] = (int64_t)f.leaves.size();
+    if (pairs) std::memcpy(pairs, f.ls_pairs.data(), f.ls_pairs.size() * sizeof(double));
+    if (nodes) std::memcpy(nodes, f.ls_nodes.data(), f.ls_nodes.size() * sizeof(uint32_t));
+    if (tris) std::memcpy(tris, f.ls_tris.data(), f.ls_tris.size() * sizeof(double));
+    if (leaf_pairs) for (size_t k = 0; k < f.leaves.size(); ++k) leaf_pairs[k] = f.leaves[k].ls_pairs;
+    return FT_OK;
+}
+
+int32_t ft_debug_slice(const double p0[3], const double n[3], const double tri[9], double above[18], int32_t* n_above, double below[18], int32_t* n_below) {
+    if (!p0 || !n || !tri || !above || !below || !n_above || !n_below) return FT_ERR_INVALID;
+    std::vector<double> a, b; std::string err;
+    int32_t rc = fth::slice_triangle(p0, n, tri, a, b, err);
+    if (rc != FT_OK) return rc;
+    *n_above = (int32_t)(a.size() / 9); *n_below = (int32_t)(b.size() / 9);
+    if (!a.empty()) std::memcpy(above, a.data(), a.size() * 8);
+    if (!b.empty()) std::memcpy(below, b.data(), b.size() * 8);
+    return FT_OK;
+}
+
+int32_t ft_debug_devices(ft_context* c, int32_t* ordinals, int32_t capacity) {   // the device ordinals behind a context, in order; returns how many
+    if (!c || capacity < 0 || (capacity > 0 && !ordinals)) return FT_ERR_INVALID;
+    if (c->host_only) return 0;
+    int32_t n = 0;
+    if (n < capacity) ordinals[n] = c->device;
+    ++n;
+    for (ft_context* p : c->peers) { if (n < capacity) ordinals[n] = p->device; ++n; }
+    return n;
+}
+
+} // extern "C"

@@ -1,5 +1,5 @@
 // ft_device.h — device-side buffer descriptors and the host-callable launch interface of
-// ft_kernels.hip.  Included by the C-ABI layer (ft_capi.cpp); contains no HIP device code.
+// ft_kernels.hip.  Included by the C-ABI layer (ft_context.h); contains no HIP device code.
 #ifndef FT_DEVICE_H
 #define FT_DEVICE_H
 #include <hip/hip_runtime_api.h>
@@ -245,7 +245,7 @@ void launch_denoise_quantise(hipStream_t stream, const double* rgb, uint8_t* out
 // then n, p: 48), then what it contributes (M, Q: 48).
 struct TemporalSet { double* m[3]; double* q[3]; double* len; double* p[3]; double* n[3]; int32_t* leaf; };
 constexpr size_t kTemporalSetBytes = 13 * 8 + 4;
-constexpr double kTemporalMinWeight = 1.0 / 16.0;   // FT_TEMPORAL_MIN_WEIGHT (functracer_hip.h; ft_capi.cpp asserts that they agree)
+constexpr double kTemporalMinWeight = 1.0 / 16.0;   // FT_TEMPORAL_MIN_WEIGHT (functracer_hip.h; ft_context.h asserts that they agree)
 // k_temporal: one lane per entry of a window of the pixel list.  k_aov's planes of the window (p, n as three planes of `stride`
 // entries, leaf; by position) and the frame's colour at the pixel are blended with what `prev` holds where the pixel's point projects
 // to through the previous call's image plane (o, i, j, k, tlx, tly, pw, ph); the pixel's record goes into `cur`, its mean into

@@ -1,0 +1,445 @@
+// ft_passes.cpp — the passes over the surface buffers: ft_render_aov, and ft_denoise and ft_temporal_* which take their guides from it.
+#include "ft_context.h"
+
+namespace ftc {
+
+// Ends the temporal accumulation of a context (its buffers are freed): leaf ids are only comparable within one commit.
+void temporal_close(ft_context* c) {
+    if (!c->temporal.open) return;
+    (void)hipSetDevice(c->device);
+    c->temporal.release();
+}
+
+} // namespace ftc
+using namespace ftc;
+
+extern "C" {
+
+// ------------------------------------------------------------------------------------------ per-pixel surface buffers
+// ft_render_aov: the hit of one sample's geometry ray per tile pixel (functracer_hip.h).  The call keeps to buffers of its own - pixel
+// list, jitter pattern, planes, counters - so the frame buffer, the cached pixel list, the zero-fill and level-hint history and a
+// progressive accumulation stay as they were.  The list is ft_render's (8x8 blocks in Z order where the rects allow), cut into windows
+// of "chunk_samples" entries; per window one k_aov writes the requested planes by list position and the host scatters them into the
+// caller's frame-shaped planes.
+namespace {
+struct AovPlanes { int64_t off[8]; int width[8], esz[8]; size_t bytes_per_entry; };   // t, p, n, colour, material, leaf, node, triangle; esz: bytes of an element
+AovPlanes aov_planes(const bool (&want)[8], int64_t per) {
+    AovPlanes a{};
+    const int width[8] = {1, 3, 3, 3, 3, 1, 1, 1};
+    int64_t at = 0;                                                 // bytes; doubles first, then the 32-bit planes
+    for (int k = 0; k < 8; ++k) {
+        a.off[k] = -1; a.width[k] = width[k]; a.esz[k] = k < 5 ? 8 : 4;
+        if (!want[k]) continue;
+        a.off[k] = at;
+        at += per * width[k] * a.esz[k];
+        a.bytes_per_entry += (size_t)width[k] * a.esz[k];
+    }
+    return a;
+}
+struct AovRun { int64_t n_pix = 0; unsigned long long hits = 0; double kernel_ms = 0.0; int32_t n_launches = 0; };
+} // namespace
+
+// The device half of an AOV pass, shared by ft_render_aov and ft_denoise: the pixel list `px` and the pattern go up, and per window of
+// "chunk_samples" entries one k_aov writes the wanted planes into d_aov_out by position in the window.  consume(p0, n, planes, dev) then
+// sees the window [p0, p0 + n) with its planes still in HBM, behind the kernel on the context's stream - it copies them out, or queues a
+// kernel that reads them.  The stream is drained after every window (the next one overwrites the planes' buffer and the event pair).
+static int32_t aov_windows(ft_context* c, const RenderRequest& q, int32_t sample, const bool (&want)[8], const std::vector<uint32_t>& px, AovRun& run,
+                           const std::function<int32_t(int64_t, uint32_t, const AovPlanes&, char*)>& consume) {
+    int32_t rc;
+    const int64_t n_pix = (int64_t)px.size();
+    run = AovRun{};
+    run.n_pix = n_pix;
+    if (n_pix == 0) return FT_OK;
+    int64_t per = std::max<int64_t>(1, std::min<int64_t>(n_pix, c->opt.chunk_samples));
+    if (per > 64) per -= per % 64;                                  // windows of whole 8x8 blocks
+    const AovPlanes pl = aov_planes(want, per);
+    if ((rc = upload(c, c->aov.d_pixels, px)) != FT_OK) return rc;
+    if ((rc = upload(c, c->aov.d_jitter, std::vector<double>(q.jitter_xy, q.jitter_xy + 2 * (size_t)q.spp))) != FT_OK) return rc;
+    if ((rc = ensure(c, c->aov.d_out, (size_t)per * pl.bytes_per_entry)) != FT_OK) return rc;
+    if ((rc = ensure(c, c->aov.d_ctr, 2 * sizeof(unsigned long long))) != FT_OK) return rc;
+    FT_HIP(c, hipMemsetAsync(c->aov.d_ctr.p, 0, 2 * sizeof(unsigned long long), c->stream));
+    const ftk::Camera cam = make_camera(*q.cam, q.res_h, q.res_v);
+    const size_t lds = lds_bytes_for(c->flat);
+    const ftk::Launch L{c->stream, c->n_cu * c->blocks_aov, lds, c->variant};
+    const ftk::AovSource src{c->d_scene[kTriSrc].as<uint32_t>(), c->d_scene[kRunNodes].as<int32_t>()};
+    char* const dev = c->aov.d_out.as<char>();
+    for (int64_t p0 = 0; p0 < n_pix; p0 += per) {
+        const uint32_t n = (uint32_t)std::min<int64_t>(per, n_pix - p0);
+        ftk::Primary gen{cam, c->aov.d_pixels.as<uint32_t>(), c->aov.d_jitter.as<double>(), (uint32_t)p0, n, q.spp, (uint32_t)q.res_h, (unsigned long long)q.seed,
+                         1.0 / (double)n, 1.0 / (double)q.res_h, nullptr, nullptr};
+        gen.group_log2 = 0;
+        auto plane = [&](int k) -> void* { return pl.off[k] < 0 ? nullptr : dev + pl.off[k]; };
+        const ftk::AovOut out{static_cast<double*>(plane(0)), static_cast<double*>(plane(1)), static_cast<double*>(plane(2)), static_cast<double*>(plane(3)),
+                              static_cast<double*>(plane(4)), static_cast<int32_t*>(plane(5)), static_cast<int32_t*>(plane(6)), static_cast<int32_t*>(plane(7)), n};
+        rc = c->aov.timer.run(c, run.kernel_ms, [&] { ftk::launch_aov(L, c->dev_scene, gen, (uint32_t)sample, src, out, c->aov.d_ctr.as<unsigned long long>()); },
+                              [&] { ++run.n_launches; return consume(p0, n, pl, dev); });
+        if (rc != FT_OK) return rc;
+    }
+    unsigned long long ctr[2] = {0, 0};
+    FT_HIP(c, hipMemcpy(ctr, c->aov.d_ctr.p, sizeof ctr, hipMemcpyDeviceToHost));
+    if (ctr[1]) { c->err = "CSG hit list overflow"; return FT_ERR_OVERFLOW; }
+    run.hits = ctr[0];
+    return FT_OK;
+}
+
+// This device is about to run a guide pass: the frames still queued on it are retired first, and the caller's stats start from zero.
+static int32_t begin_pass(ft_context* c, ft_stats* stats) {
+    FT_HIP(c, hipSetDevice(c->device));
+    int32_t rc;
+    if (any_pending(c) && (rc = retire_pending(c, nullptr)) != FT_OK) return rc;
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    return FT_OK;
+}
+// ... and has run it: the k_aov launches of `run` and the `own_launches` kernels of the pass itself, own_ms on the device, behind them.
+static void end_pass(ft_stats* stats, const AovRun& run, double own_ms, int32_t own_launches, std::chrono::steady_clock::time_point wall0) {
+    if (!stats) return;
+    stats->rays_primary = (uint64_t)run.n_pix; stats->hits_primary = run.hits;
+    stats->kernel_ms = run.kernel_ms + own_ms; stats->n_launches = run.n_launches + own_launches;
+    stats->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+}
+// What `api` reads must be the FP64 frame of this size in HBM; `reader` and `size_tail` word the refusal.
+static int32_t need_fp64_frame(ft_context* c, const std::string& api, int32_t res_h, int32_t res_v, const char* reader, const char* size_tail) {
+    if (c->last_n_pix > 0 && c->last_format == 0 && c->last_res_h == res_h && c->last_res_v == res_v) return FT_OK;
+    c->err = api + (c->last_n_pix <= 0 ? ": no frame rendered yet" : c->last_format != 0 ? std::string(": the frame in HBM is RGBA8 (ft_render_rgba8); the ") + reader + " needs the FP64 frame"
+                                                                                       : std::string(": the frame in HBM has another size") + size_tail);
+    return FT_ERR_STATE;
+}
+// The passes that read the whole frame in HBM refuse a context over several devices.
+static int32_t need_one_device(ft_context* c, const std::string& api) {
+    if (c->peers.empty()) return FT_OK;
+    c->err = api + ": a context over several devices keeps the frame in 8-row bands on different devices and a tap crosses bands; gathering them is not supported";
+    return FT_ERR_UNSUPPORTED;
+}
+// The sample a guide pass takes its geometry ray from; `corner_tail` ends the sentence about corner sampling.  (Behind check_request
+// the second test cannot fail: ft_temporal_accumulate, which has no request to check, relies on it.)
+static int32_t check_guide_sample(ft_context* c, const std::string& api, int32_t spp, const double* jitter_xy, int32_t sample, const char* corner_tail) {
+    if (spp == 0) { c->err = api + ": corner sampling (spp == 0) has no per-sample geometry ray" + corner_tail; return FT_ERR_UNSUPPORTED; }
+    if (spp < 0 || !jitter_xy) { c->err = "bad " + api + " argument"; return FT_ERR_INVALID; }
+    if (sample < 0 || sample >= spp) { c->err = api + ": sample outside [0, spp)"; return FT_ERR_INVALID; }
+    return FT_OK;
+}
+
+static int32_t aov_single(ft_context* c, const RenderRequest& q, int32_t sample, const ft_aov& o, ft_stats* stats) {
+    if (!need_device(c)) return FT_ERR_NO_DEVICE;
+    if (!need_committed(c)) return FT_ERR_STATE;
+    const auto wall0 = std::chrono::steady_clock::now();
+    int32_t rc;
+    if ((rc = begin_pass(c, stats)) != FT_OK) return rc;
+    std::vector<uint32_t> px;
+    (void)list_pixels(clip_rects(q), q.res_h, px);
+    if (px.empty()) return FT_OK;
+    void* const dst[8] = {o.t, o.p, o.n, o.colour, o.material, o.leaf, o.node, o.triangle};
+    bool want[8];
+    for (int k = 0; k < 8; ++k) want[k] = dst[k] != nullptr;
+    std::vector<char> host;
+    AovRun run;
+    rc = aov_windows(c, q, sample, want, px, run, [&](int64_t p0, uint32_t n, const AovPlanes& pl, char* dev) -> int32_t {
+        size_t need = 0;                                            // the planes keep the offsets of a full window
+        for (int k = 0; k < 8; ++k) if (pl.off[k] >= 0) need = std::max(need, (size_t)pl.off[k] + (size_t)n * pl.width[k] * pl.esz[k]);
+        if (host.size() < need) host.resize(need);
+        for (int k = 0; k < 8; ++k) if (pl.off[k] >= 0) {          // a channel's planes lie back to back: n entries apart within the window
+            FT_HIP(c, hipMemcpyAsync(host.data() + pl.off[k], dev + pl.off[k], (size_t)n * pl.width[k] * pl.esz[k], hipMemcpyDeviceToHost, c->stream));
+        }
+        FT_HIP(c, hipStreamSynchronize(c->stream));
+        for (int k = 0; k < 8; ++k) if (pl.off[k] >= 0) {          // into the caller's planes: frame layout, row 0 = top, w components per pixel
+            const int w = pl.width[k];
+            const char* src_k = host.data() + pl.off[k];
+            if (pl.esz[k] == 8) {
+                const double* s = reinterpret_cast<const double*>(src_k);
+                double* d = static_cast<double*>(dst[k]);
+                for (uint32_t i = 0; i < n; ++i) { const size_t id = px[(size_t)p0 + i]; for (int a = 0; a < w; ++a) d[id * w + a] = s[(size_t)a * n + i]; }
+            } else {
+                const int32_t* s = reinterpret_cast<const int32_t*>(src_k);
+                int32_t* d = static_cast<int32_t*>(dst[k]);
+                for (uint32_t i = 0; i < n; ++i) d[px[(size_t)p0 + i]] = s[i];
+            }
+        }
+        return FT_OK;
+    });
+    if (rc != FT_OK) return rc;
+    end_pass(stats, run, 0.0, 0, wall0);
+    return FT_OK;
+}
+
+static int32_t aov_frame(ft_context* c, const RenderRequest& q, int32_t sample, const ft_aov& o, ft_stats* stats) {
+    if (c->peers.empty()) return aov_single(c, q, sample, o, stats);
+    if (!need_committed(c)) return FT_ERR_STATE;
+    const auto wall0 = std::chrono::steady_clock::now();
+    const std::vector<std::vector<ft_rect>> share = band_shares(q, 1 + c->peers.size());   // ft_render's 8-row bands: each device writes its rows
+    return on_every_device(c, stats, wall0, [&](size_t d, ft_context* D, ft_stats* sd) -> int32_t {
+        if (share[d].empty()) return FT_OK;
+        RenderRequest qd = q;
+        qd.tiles = share[d].data(); qd.n_tiles = (int32_t)share[d].size();
+        return aov_single(D, qd, sample, o, sd);
+    });
+}
+
+int32_t ft_render_aov(ft_context* c, const ft_camera* cam, int32_t res_h, int32_t res_v, int32_t spp, const double* jitter_xy,
+                      int32_t sample, uint64_t seed, const ft_rect* tiles, int32_t n_tiles, const ft_aov* out, ft_stats* stats) {
+    if (!c) return FT_ERR_INVALID;
+    const RenderRequest q{cam, res_h, res_v, spp, jitter_xy, 0, seed, tiles, n_tiles, 0};
+    int32_t rc = check_request(c, q);
+    if (rc != FT_OK) return rc;
+    if ((rc = check_guide_sample(c, "ft_render_aov", spp, jitter_xy, sample, "")) != FT_OK) return rc;
+    if (!out || !(out->t || out->p || out->n || out->colour || out->material || out->leaf || out->node || out->triangle)) { c->err = "ft_render_aov: no channel requested"; return FT_ERR_INVALID; }
+    if (!need_device(c)) return FT_ERR_NO_DEVICE;
+    return with_growing_hit_lists(c, [&] { return aov_frame(c, q, sample, *out, stats); });
+}
+
+// ------------------------------------------------------------------------------------------ denoising the frame in HBM
+// ft_denoise (functracer_hip.h).  The guide pass is ft_render_aov's (aov_windows: n, p, colour, leaf), but its windows
+// never leave the device: k_denoise_scatter turns each into frame-layout guide records and u_0 = c / d.  Then one k_denoise per
+// iteration alternates between two colour buffers; the last one multiplies d back.  Only buffers of the call's own are written: d_out is
+// read, the cached pixel list, signatures, level hint and a progressive accumulation are not touched.
+static int32_t denoise_single(ft_context* c, const RenderRequest& q, int32_t sample, const ft_denoise_params& P, bool rgba8, void* out, ft_stats* stats) {
+    const auto wall0 = std::chrono::steady_clock::now();
+    int32_t rc;
+    if ((rc = begin_pass(c, stats)) != FT_OK) return rc;
+    if ((rc = need_fp64_frame(c, "ft_denoise", q.res_h, q.res_v, "filter", "")) != FT_OK) return rc;
+    const std::vector<ft_rect> rects = clip_rects(q);
+    const ft_context::Progressive& G = c->prog;
+    if (P.use_variance) {
+        const bool live = G.open && G.tolerance > 0.0 && G.passes > 0 && G.res_h == q.res_h && G.res_v == q.res_v;
+        const std::vector<ft_rect> mine = live ? clip_rects(progressive_request(G)) : std::vector<ft_rect>();
+        if (!live || mine.size() != rects.size() || (!rects.empty() && std::memcmp(mine.data(), rects.data(), rects.size() * sizeof(ft_rect)) != 0)) {
+            c->err = "ft_denoise: use_variance needs a live adaptive progressive accumulation (tolerance > 0, at least one pass) of the same size and tiles";
+            return FT_ERR_STATE;
+        }
+    }
+    std::vector<uint32_t> px;
+    (void)list_pixels(rects, q.res_h, px);
+    if (px.empty()) return FT_OK;
+    if (!need_committed(c)) return FT_ERR_STATE;
+    if ((rc = drain_frame_streams(c)) != FT_OK) return rc;          // the frame may have been written on another stream (fetch_single)
+    const size_t n_px = (size_t)q.res_h * (size_t)q.res_v;
+    const double* frame = c->d_out.as<double>();
+    const void* result = frame;                                     // zero iterations: the frame itself
+    double kernel_ms = 0.0;
+    int32_t n_launches = 0;
+    AovRun run;
+    TimedLaunch& timer = c->denoise.timer;
+    if (rgba8 && (rc = ensure(c, c->denoise.d_out8, n_px * 4)) != FT_OK) return rc;
+    if (P.iterations > 0) {
+        if ((rc = ensure(c, c->denoise.d_guides, n_px * ftk::kDenoiseGuideBytes)) != FT_OK) return rc;
+        for (int k = 0; k < 2; ++k) if ((rc = ensure(c, c->denoise.d_u[k], n_px * 24)) != FT_OK) return rc;
+        ftk::DenoiseGuides g{};
+        double* plane = c->denoise.d_guides.as<double>();
+        for (int k = 0; k < 3; ++k) { g.n[k] = plane + (size_t)k * n_px; g.p[k] = plane + (size_t)(3 + k) * n_px; g.d[k] = plane + (size_t)(6 + k) * n_px; }
+        g.v = plane + 9 * n_px;
+        g.cls = reinterpret_cast<uint8_t*>(plane + 10 * n_px);
+        FT_HIP(c, hipMemsetAsync(g.cls, ftk::kDenoiseOutside, n_px, c->stream));
+        const bool want[8] = {false, true, true, true, false, true, false, false};   // p, n, colour, leaf
+        rc = aov_windows(c, q, sample, want, px, run, [&](int64_t p0, uint32_t n, const AovPlanes& pl, char* dev) -> int32_t {
+            ftk::DenoiseScatterArgs a{};
+            a.pixel_ids = c->aov.d_pixels.as<uint32_t>(); a.first = (uint32_t)p0; a.n = n;
+            a.p_plane = reinterpret_cast<const double*>(dev + pl.off[1]); a.n_plane = reinterpret_cast<const double*>(dev + pl.off[2]);
+            a.colour = reinterpret_cast<const double*>(dev + pl.off[3]); a.leaf = reinterpret_cast<const int32_t*>(dev + pl.off[5]); a.stride = n;
+            a.frame = frame; a.u0 = c->denoise.d_u[0].as<double>(); a.g = g;
+            a.demodulate = P.demodulate ? 1 : 0; a.albedo_floor = P.albedo_floor;
+            if (P.use_variance) {
+                a.sum = G.d_sum[G.cur].as<double>(); a.sq = G.d_sq[G.cur].as<double>(); a.blk = G.d_blk[G.cur].as<uint32_t>();
+                a.n_list = (uint32_t)G.n_pix; a.variance_floor = P.variance_floor;
+            }
+            ++n_launches;
+            return timer.run(c, kernel_ms, [&] { ftk::launch_denoise_scatter(c->stream, a); });
+        });
+        if (rc != FT_OK) return rc;
+        auto inv_sq = [](double sigma) { return sigma > 0.0 ? 1.0 / (sigma * sigma) : 0.0; };
+        rc = timer.run(c, kernel_ms, [&] { for (int i = 0; i < P.iterations; ++i) {   // one bracket around all iterations
+            const bool last = i + 1 == P.iterations;
+            ftk::DenoiseArgs a{};
+            a.u_in = c->denoise.d_u[i & 1].as<double>(); a.u_out = c->denoise.d_u[(i + 1) & 1].as<double>();
+            a.out8 = last && rgba8 ? c->denoise.d_out8.as<uint8_t>() : nullptr;
+            a.g = g; a.res_h = q.res_h; a.res_v = q.res_v; a.step = 1 << i;
+            a.inv_sn2 = inv_sq(P.sigma_normal); a.inv_sp2 = inv_sq(P.sigma_position); a.inv_sc2 = inv_sq(P.sigma_colour * std::ldexp(1.0, -i));
+            ftk::launch_denoise(c->stream, a, last);
+            ++n_launches;
+            if (last) result = rgba8 ? (const void*)a.out8 : (const void*)a.u_out;
+        } });
+        if (rc != FT_OK) return rc;
+    } else if (rgba8) {
+        ++n_launches;
+        if ((rc = timer.run(c, kernel_ms, [&] { ftk::launch_denoise_quantise(c->stream, frame, c->denoise.d_out8.as<uint8_t>(), (uint32_t)n_px); })) != FT_OK) return rc;
+        result = c->denoise.d_out8.p;
+    }
+    if ((rc = copy_rects_out(c, out, result, rgba8 ? 4 : 24, q.res_h, rects, nullptr)) != FT_OK) return rc;
+    end_pass(stats, run, kernel_ms, n_launches, wall0);
+    return FT_OK;
+}
+
+int32_t ft_denoise(ft_context* c, const ft_camera* cam, int32_t res_h, int32_t res_v, int32_t spp, const double* jitter_xy, int32_t sample, uint64_t seed,
+                   const ft_rect* tiles, int32_t n_tiles, const ft_denoise_params* params, int32_t rgba8, void* out, ft_stats* stats) {
+    if (!c) return FT_ERR_INVALID;
+    const RenderRequest q{cam, res_h, res_v, spp, jitter_xy, 0, seed, tiles, n_tiles, 0};
+    int32_t rc = check_request(c, q);
+    if (rc != FT_OK) return rc;
+    if ((rc = check_guide_sample(c, "ft_denoise", spp, jitter_xy, sample, " to take the guides from")) != FT_OK) return rc;
+    if (!params || !out) { c->err = "ft_denoise: null params or out"; return FT_ERR_INVALID; }
+    const ft_denoise_params& P = *params;
+    if (P.iterations < 0 || P.iterations > 6) { c->err = "ft_denoise: iterations outside 0 .. 6"; return FT_ERR_INVALID; }
+    if (!(P.sigma_colour >= 0.0) || !(P.sigma_normal >= 0.0) || !(P.sigma_position >= 0.0)) { c->err = "ft_denoise: a sigma is negative or NaN (0 switches a term off)"; return FT_ERR_INVALID; }
+    if (P.demodulate && !(P.albedo_floor > 0.0)) { c->err = "ft_denoise: demodulate needs albedo_floor > 0"; return FT_ERR_INVALID; }
+    if (P.use_variance && !(P.variance_floor > 0.0)) { c->err = "ft_denoise: use_variance needs variance_floor > 0"; return FT_ERR_INVALID; }
+    if (!need_device(c)) return FT_ERR_NO_DEVICE;
+    if ((rc = need_one_device(c, "ft_denoise")) != FT_OK) return rc;
+    return with_growing_hit_lists(c, [&] { return denoise_single(c, q, sample, P, rgba8 != 0, out, stats); });
+}
+
+// ------------------------------------------------------------------------------------------ reprojected frame accumulation
+// ft_temporal_* (functracer_hip.h).  The guide pass is ft_render_aov's again (aov_windows: p, n, leaf), its windows stay
+// on the device, and one k_temporal per window blends the frame's colours with the previous history set and writes the other one.
+static ftk::TemporalSet temporal_set(const DeviceBuf& b, size_t n_px) {
+    ftk::TemporalSet s{};
+    double* plane = b.as<double>();                                 // M, Q and N first: ft_temporal_fetch reads them as one run
+    for (int k = 0; k < 3; ++k) { s.m[k] = plane + (size_t)k * n_px; s.q[k] = plane + (size_t)(3 + k) * n_px; s.p[k] = plane + (size_t)(7 + k) * n_px; s.n[k] = plane + (size_t)(10 + k) * n_px; }
+    s.len = plane + 6 * n_px;
+    s.leaf = reinterpret_cast<int32_t*>(plane + 13 * n_px);
+    return s;
+}
+
+int32_t ft_temporal_begin(ft_context* c, int32_t res_h, int32_t res_v, const ft_rect* tiles, int32_t n_tiles) {
+    if (!c) return FT_ERR_INVALID;
+    if (res_h < 2 || res_v < 2 || (tiles && n_tiles < 1) || (int64_t)res_h * res_v > (int64_t)0x7FFFFFFF) { c->err = "bad ft_temporal_begin argument"; return FT_ERR_INVALID; }
+    if (!need_device(c)) return FT_ERR_NO_DEVICE;
+    int32_t rc;
+    if ((rc = need_one_device(c, "ft_temporal_begin")) != FT_OK) return rc;
+    temporal_close(c);                                              // a second begin replaces the first
+    ft_context::Temporal& T = c->temporal;
+    rc = [&]() -> int32_t {
+        FT_HIP(c, hipSetDevice(c->device));
+        const size_t set_bytes = (size_t)res_h * (size_t)res_v * ftk::kTemporalSetBytes;
+        int32_t r;
+        for (DeviceBuf& b : T.d_set) {                              // N = 0 everywhere: no tap finds history (the rest is cleared with it)
+            if ((r = ensure(c, b, set_bytes)) != FT_OK) return r;
+            FT_HIP(c, hipMemsetAsync(b.p, 0, set_bytes, c->stream));
+        }
+        if ((r = ensure(c, T.d_ctr, 2 * sizeof(unsigned long long))) != FT_OK) return r;
+        FT_HIP(c, hipStreamSynchronize(c->stream));
+        return FT_OK;
+    }();
+    if (rc != FT_OK) { T.release(); return rc; }
+    T.open = true; T.res_h = res_h; T.res_v = res_v;
+    T.rects = clip_rects(RenderRequest{nullptr, res_h, res_v, 1, kNoJitter, 0, 0, tiles, n_tiles, 0});
+    for (const ft_rect& r : T.rects) T.n_pix += (int64_t)r.w * r.h;
+    return FT_OK;
+}
+
+static int32_t temporal_single(ft_context* c, const RenderRequest& q, int32_t sample, const ft_temporal_params& P, bool rgba8, void* out, ft_stats* stats) {
+    const auto wall0 = std::chrono::steady_clock::now();
+    int32_t rc;
+    if ((rc = begin_pass(c, stats)) != FT_OK) return rc;
+    ft_context::Temporal& T = c->temporal;
+    if ((rc = need_fp64_frame(c, "ft_temporal_accumulate", T.res_h, T.res_v, "accumulation", " than ft_temporal_begin fixed")) != FT_OK) return rc;
+    std::vector<uint32_t> px;
+    (void)list_pixels(T.rects, T.res_h, px);
+    if (!need_committed(c)) return FT_ERR_STATE;
+    if ((rc = drain_frame_streams(c)) != FT_OK) return rc;          // the frame may have been written on another stream (fetch_single)
+    const size_t n_px = (size_t)T.res_h * (size_t)T.res_v;
+    const bool want_rgb = P.to_frame || (out && !rgba8), want_rgba8 = out && rgba8;
+    if (want_rgb && (rc = ensure(c, T.d_rgb, n_px * 24)) != FT_OK) return rc;
+    if (want_rgba8 && (rc = ensure(c, T.d_rgba8, n_px * 4)) != FT_OK) return rc;
+    FT_HIP(c, hipMemsetAsync(T.d_ctr.p, 0, 2 * sizeof(unsigned long long), c->stream));
+    const ftk::Camera cam = make_camera(*q.cam, T.res_h, T.res_v);
+    double kernel_ms = 0.0;
+    int32_t n_launches = 0;
+    AovRun run;
+    const bool want[8] = {false, true, true, false, false, true, false, false};   // p, n, leaf
+    rc = aov_windows(c, q, sample, want, px, run, [&](int64_t p0, uint32_t n, const AovPlanes& pl, char* dev) -> int32_t {
+        ftk::TemporalArgs a{};
+        a.pixel_ids = c->aov.d_pixels.as<uint32_t>(); a.first = (uint32_t)p0; a.n = n;
+        a.p_plane = reinterpret_cast<const double*>(dev + pl.off[1]); a.n_plane = reinterpret_cast<const double*>(dev + pl.off[2]);
+        a.leaf = reinterpret_cast<const int32_t*>(dev + pl.off[5]); a.stride = n;
+        a.frame = c->d_out.as<double>();
+        a.prev = temporal_set(T.d_set[T.prev], n_px); a.cur = temporal_set(T.d_set[T.prev ^ 1], n_px);
+        for (int k = 0; k < 3; ++k) { a.o[k] = T.cam.o[k]; a.i[k] = T.cam.i[k]; a.j[k] = T.cam.j[k]; a.k[k] = T.cam.k[k]; }
+        a.tlx = T.cam.tlx; a.tly = T.cam.tly; a.pw = T.cam.pw; a.ph = T.cam.ph;
+        a.res_h = T.res_h; a.res_v = T.res_v; a.has_prev = T.calls > 0 ? 1 : 0;
+        a.max_history = (double)P.max_history; a.min_normal_dot = P.min_normal_dot;
+        a.tol_scale = P.position_tolerance_px * std::max(T.cam.pw, T.cam.ph);
+        a.out_rgb = want_rgb ? T.d_rgb.as<double>() : nullptr; a.out8 = want_rgba8 ? T.d_rgba8.as<uint8_t>() : nullptr;
+        a.counters = T.d_ctr.as<unsigned long long>();
+        ++n_launches;
+        return T.timer.run(c, kernel_ms, [&] { ftk::launch_temporal(c->stream, a); });
+    });
+    if (rc != FT_OK) return rc;                                     // nothing was flipped: the history is as it was
+    unsigned long long ctr[2] = {0, 0};
+    if (!px.empty()) FT_HIP(c, hipMemcpy(ctr, T.d_ctr.p, sizeof ctr, hipMemcpyDeviceToHost));
+    if (out && (rc = copy_rects_out(c, out, rgba8 ? T.d_rgba8.p : T.d_rgb.p, rgba8 ? 4 : 24, T.res_h, T.rects, nullptr)) != FT_OK) return rc;
+    if (P.to_frame && !px.empty()) {                                // the means replace the tile pixels of the frame, once the call can no longer fail
+        const size_t pitch = (size_t)T.res_h * 24;
+        for (const ft_rect& r : T.rects) {
+            const size_t off = (size_t)r.y0 * pitch + (size_t)r.x0 * 24;
+            FT_HIP(c, hipMemcpy2DAsync(c->d_out.as<char>() + off, pitch, T.d_rgb.as<char>() + off, pitch, (size_t)r.w * 24, (size_t)r.h, hipMemcpyDeviceToDevice, c->stream));
+        }
+        FT_HIP(c, hipStreamSynchronize(c->stream));
+        c->zero_signature[0] = 0;                                   // (as a progressive pass: the blocks the last ft_render left as Colour.Zero hold means now)
+    }
+    T.prev ^= 1; T.cam = cam; T.calls += 1;
+    T.with_history = (int64_t)ctr[0]; T.at_max = (int64_t)ctr[1];
+    end_pass(stats, run, kernel_ms, n_launches, wall0);
+    if (stats) stats->trace_kernel_ms = run.kernel_ms;
+    return FT_OK;
+}
+
+int32_t ft_temporal_accumulate(ft_context* c, const ft_camera* cam, int32_t spp, const double* jitter_xy, int32_t sample, uint64_t seed,
+                               const ft_temporal_params* params, int32_t rgba8, void* out, ft_stats* stats) {
+    if (!c) return FT_ERR_INVALID;
+    int32_t rc;
+    if ((rc = check_guide_sample(c, "ft_temporal_accumulate", spp, jitter_xy, sample, " to take the surfaces from")) != FT_OK) return rc;
+    if (!cam || !params) { c->err = "ft_temporal_accumulate: null cam or params"; return FT_ERR_INVALID; }
+    const ft_temporal_params& P = *params;
+    if (P.max_history < 1) { c->err = "ft_temporal_accumulate: max_history below 1"; return FT_ERR_INVALID; }
+    if (!(P.min_normal_dot >= -1.0 && P.min_normal_dot <= 1.0)) { c->err = "ft_temporal_accumulate: min_normal_dot is NaN or outside [-1, 1]"; return FT_ERR_INVALID; }
+    if (!(P.position_tolerance_px > 0.0)) { c->err = "ft_temporal_accumulate: position_tolerance_px is not > 0"; return FT_ERR_INVALID; }
+    if (!need_device(c)) return FT_ERR_NO_DEVICE;
+    if ((rc = need_one_device(c, "ft_temporal_accumulate")) != FT_OK) return rc;
+    if (!c->temporal.open) { c->err = "no temporal accumulation (ft_temporal_begin; a caller's ft_scene_commit or ft_scene_clear ends it)"; return FT_ERR_STATE; }
+    const RenderRequest q{cam, c->temporal.res_h, c->temporal.res_v, spp, jitter_xy, 0, seed, nullptr, 0, 0};   // (the pixel list is made from the begin's rects)
+    return with_growing_hit_lists(c, [&] { return temporal_single(c, q, sample, P, rgba8 != 0, out, stats); });
+}
+
+int32_t ft_temporal_fetch(ft_context* c, double* mean_rgb, double* stderr_rgb, double* length) {
+    if (!c) return FT_ERR_INVALID;
+    if (!need_device(c)) return FT_ERR_NO_DEVICE;
+    const ft_context::Temporal& T = c->temporal;
+    if (!T.open) { c->err = "no temporal accumulation (ft_temporal_begin)"; return FT_ERR_STATE; }
+    const size_t n_px = (size_t)T.res_h * (size_t)T.res_v;
+    std::vector<double> h(7 * n_px);                                // M, Q, N of the set the last call wrote
+    FT_HIP(c, hipSetDevice(c->device));
+    FT_HIP(c, hipStreamSynchronize(c->stream));
+    FT_HIP(c, hipMemcpy(h.data(), T.d_set[T.prev].p, h.size() * 8, hipMemcpyDeviceToHost));
+    for (const ft_rect& r : T.rects)
+        for (int y = r.y0; y < r.y0 + r.h; ++y) for (int x = r.x0; x < r.x0 + r.w; ++x) {
+            const size_t id = (size_t)y * (size_t)T.res_h + (size_t)x;
+            const double N = h[6 * n_px + id];
+            for (int ch = 0; ch < 3; ++ch) {
+                const double M = h[(size_t)ch * n_px + id];
+                if (mean_rgb) mean_rgb[3 * id + ch] = M;
+                if (stderr_rgb) {
+                    double se = 0.0;
+                    if (N >= 2.0) { const double mm = M * M, v = h[(size_t)(3 + ch) * n_px + id] - mm; se = std::sqrt((v > 0.0 ? v : 0.0) / N); }
+                    stderr_rgb[3 * id + ch] = se;
+                }
+            }
+            if (length) length[id] = N;
+        }
+    return FT_OK;
+}
+
+int32_t ft_temporal_status(ft_context* c, int64_t out[4]) {
+    if (!c || !out) return FT_ERR_INVALID;
+    if (!need_device(c)) return FT_ERR_NO_DEVICE;
+    const ft_context::Temporal& T = c->temporal;
+    if (!T.open) { c->err = "no temporal accumulation (ft_temporal_begin)"; return FT_ERR_STATE; }
+    out[0] = T.calls; out[1] = T.n_pix; out[2] = T.with_history; out[3] = T.at_max;
+    return FT_OK;
+}
+
+int32_t ft_temporal_end(ft_context* c) {
+    if (!c) return FT_ERR_INVALID;
+    if (!need_device(c)) return FT_ERR_NO_DEVICE;
+    temporal_close(c);
+    return FT_OK;
+}
+
+} // extern "C"

@@ -5,12 +5,14 @@
 #   tools/sanitize_host.sh        -> prints the sanitizer findings (none expected) and the pytest summary
 set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd); cd "$ROOT"
-make -s -C functracer_amd/csrc ft_kernels.o ft_bvh.o
+CSRC=functracer_amd/csrc
+DEVICE_OBJS=$(make -s -C $CSRC print-DEVICE_OBJS); CAPI_OBJS=$(make -s -C $CSRC print-CAPI_OBJS)   # the Makefile's lists
+make -s -C $CSRC $DEVICE_OBJS
 mkdir -p build/asan
 SAN="-fsanitize=address,undefined -fno-omit-frame-pointer -g -O1 -std=c++17 -fPIC -ffp-contract=off"
-g++ $SAN -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -c functracer_amd/csrc/ft_capi.cpp -o build/asan/ft_capi.o
-g++ $SAN -c functracer_amd/csrc/ft_scene.cpp -o build/asan/ft_scene.o
-g++ $SAN -shared -o build/asan/libfunctracer_hip.so build/asan/ft_capi.o build/asan/ft_scene.o functracer_amd/csrc/ft_kernels.o functracer_amd/csrc/ft_bvh.o -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib
+for o in $CAPI_OBJS; do g++ $SAN -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -c $CSRC/${o%.o}.cpp -o build/asan/$o; done
+g++ $SAN -c $CSRC/ft_scene.cpp -o build/asan/ft_scene.o
+g++ $SAN -shared -o build/asan/libfunctracer_hip.so $(for o in $CAPI_OBJS ft_scene.o; do echo build/asan/$o; done) $(for o in $DEVICE_OBJS; do echo $CSRC/$o; done) -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib
 (cd functracer_amd/host && g++ $SAN -shared -o "$ROOT/build/asan/libfunctracer_host.so" SceneParser.cpp ImageLoader.cpp host_api.cpp -lz)
 export FT_HIP_LIB=$ROOT/build/asan/libfunctracer_hip.so FT_HOST_LIB=$ROOT/build/asan/libfunctracer_host.so
 export LD_PRELOAD="$(g++ -print-file-name=libasan.so) $(g++ -print-file-name=libubsan.so)"
