@@ -62,6 +62,7 @@ def hip_lib():
         lib.ft_render_aov.argtypes = [C.c_void_p, C.POINTER(_capi.ft_camera), C.c_int32, C.c_int32, C.c_int32, _capi.c_double_p, C.c_int32,
                                       C.c_uint64, C.POINTER(_capi.ft_rect), C.c_int32, C.POINTER(_capi.ft_aov), C.POINTER(_capi.ft_stats)]
         lib.ft_denoise.argtypes = _capi.DENOISE_SIGNATURE
+        lib.ft_temporal_filter.restype, lib.ft_temporal_filter.argtypes = C.c_int32, _capi.TEMPORAL_FILTER_SIGNATURE
         lib.ft_quantise_rgba8.argtypes = [_capi.c_double_p, C.c_int64, C.POINTER(C.c_uint8)]
         for name, res, args in _capi.PROGRESSIVE_SIGNATURES + _capi.TEMPORAL_SIGNATURES:
             fn = getattr(lib, name)
@@ -445,6 +446,40 @@ class Context(SceneBuilder):
         self._check(self._lib.ft_temporal_accumulate(self._ctx, C.byref(camera), int(spp), _capi.dptr(jitter), int(sample), int(seed), C.byref(p),
                                                      1 if rgba8 else 0, out.ctypes.data_as(C.c_void_p) if fetch else None, C.byref(st)))
         return (out if fetch else None), st.as_dict()
+
+    def temporal_filter(self, camera=None, spp=1, jitter=None, sample=0, seed=DEFAULT_SEED, rgba8=False, out=None, variance=False, **params):
+        """ft_temporal_filter: the history the last temporal_accumulate wrote, filtered on the device by an edge-avoiding a-trous filter
+        whose colour term is scaled by a per-pixel variance (the history's standard error; a 7x7 spatial estimate where the history is
+        shorter than min_history) that is filtered from iteration to iteration.  With demodulate, (camera, spp, jitter, sample, seed) are
+        those of that temporal_accumulate; without, they are not read.  params: iterations, demodulate, min_history, to_frame,
+        sigma_colour, sigma_normal, sigma_position, albedo_floor, variance_floor (_capi.TEMPORAL_FILTER_DEFAULTS).  variance: False, True
+        (a fresh plane) or a float64 array [res_v, res_h] to fill; out=False copies no colour out.  Returns (rgb[res_v, res_h, 3] float64
+        or rgba[res_v, res_h, 4] uint8 or None, variance[res_v, res_h] or None, stats dict); pixels outside the tiles keep what the
+        arrays held (0 in fresh ones)."""
+        unknown = set(params) - set(_capi.TEMPORAL_FILTER_DEFAULTS)
+        if unknown:
+            raise ValueError(f"unknown temporal filter parameters {sorted(unknown)}")
+        res_h, res_v = self._temporal_shape()
+        p = _capi.ft_temporal_filter_params()
+        for k, v in {**_capi.TEMPORAL_FILTER_DEFAULTS, **params}.items():
+            setattr(p, k, int(v) if k in ("iterations", "demodulate", "min_history", "to_frame") else float(v))
+        if jitter is not None:
+            jitter = np.zeros((1, 2)) if spp <= 0 else _capi.as_f64(jitter, (spp, 2))
+        shape, dtype = ((res_v, res_h, 4), np.uint8) if rgba8 else ((res_v, res_h, 3), np.float64)
+        if out is None:
+            out = np.zeros(shape, dtype=dtype)
+        elif out is False:
+            out = None
+        if out is not None and (out.shape != shape or out.dtype != dtype or not out.flags.c_contiguous):
+            raise ValueError(f"temporal_filter: need a C-contiguous {np.dtype(dtype).name} array of shape {shape}")
+        var = np.zeros((res_v, res_h)) if variance is True else None if variance is False or variance is None else variance
+        if var is not None and (var.shape != (res_v, res_h) or var.dtype != np.float64 or not var.flags.c_contiguous):
+            raise ValueError(f"temporal_filter: the variance needs a C-contiguous float64 array of shape {(res_v, res_h)}")
+        st = _capi.ft_stats()
+        self._check(self._lib.ft_temporal_filter(self._ctx, C.byref(camera) if camera is not None else None, int(spp),
+                                                 _capi.dptr(jitter) if jitter is not None else None, int(sample), int(seed), C.byref(p), 1 if rgba8 else 0,
+                                                 out.ctypes.data_as(C.c_void_p) if out is not None else None, _capi.dptr(var) if var is not None else None, C.byref(st)))
+        return out, var, st.as_dict()
 
     def temporal_fetch(self):
         """(mean[res_v, res_h, 3], stderr[res_v, res_h, 3], history length[res_v, res_h] float64) of the tile pixels; other pixels stay 0."""

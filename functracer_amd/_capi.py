@@ -104,6 +104,23 @@ TEMPORAL_SIGNATURES = [
 ]
 
 
+class ft_temporal_filter_params(C.Structure):
+    """ft_temporal_filter's parameters (include/functracer_hip.h): a-trous iterations 0 .. 6, demodulation by the material colour, the
+    history length below which the spatial variance estimate steps in, whether the result replaces the frame in HBM, the three
+    edge-stopping sigmas (0 = term off) and the two floors."""
+    _fields_ = [("iterations", C.c_int32), ("demodulate", C.c_int32), ("min_history", C.c_int32), ("to_frame", C.c_int32),
+                ("sigma_colour", C.c_double), ("sigma_normal", C.c_double), ("sigma_position", C.c_double),
+                ("albedo_floor", C.c_double), ("variance_floor", C.c_double)]
+
+
+# Context.temporal_filter's defaults
+TEMPORAL_FILTER_DEFAULTS = dict(iterations=4, demodulate=1, min_history=4, to_frame=0, sigma_colour=2.0, sigma_normal=0.3, sigma_position=0.0,
+                                albedo_floor=1e-3, variance_floor=1e-6)
+
+TEMPORAL_FILTER_SIGNATURE = [C.c_void_p, C.POINTER(ft_camera), C.c_int32, c_double_p, C.c_int32, C.c_uint64, C.POINTER(ft_temporal_filter_params),
+                             C.c_int32, C.c_void_p, c_double_p, C.POINTER(ft_stats)]
+
+
 # ft_render_aov channels: (name, dtype, components per pixel, value of a pixel whose ray misses everything)
 AOV_CHANNELS = [("t", np.float64, 1, np.inf), ("p", np.float64, 3, 0.0), ("n", np.float64, 3, 0.0), ("colour", np.float64, 3, 0.0),
                 ("material", np.float64, 3, 0.0), ("leaf", np.int32, 1, -1), ("node", np.int32, 1, -1), ("triangle", np.int32, 1, -1)]

@@ -262,7 +262,14 @@ struct ft_context {
         DeviceBuf d_set[2], d_rgb, d_rgba8, d_ctr;
         TimedLaunch timer;              // around each k_temporal launch (kernel_ms)
         int prev = 0;
-        void release() { for (DeviceBuf* b : {&d_set[0], &d_set[1], &d_rgb, &d_rgba8, &d_ctr}) b->release(); timer.release(); *this = Temporal(); }
+        // ft_temporal_filter's planes, frame-sized, allocated by the first filter call of the accumulation: the divisor d,
+        // the class, the two colour buffers and the two variance planes the iterations alternate between, and the RGBA8 result
+        DeviceBuf d_fd, d_fcls, d_fu[2], d_fv[2], d_f8;
+        TimedLaunch ftimer;             // around the kernels of a filter call (kernel_ms)
+        void release() {
+            for (DeviceBuf* b : {&d_set[0], &d_set[1], &d_rgb, &d_rgba8, &d_ctr, &d_fd, &d_fcls, &d_fu[0], &d_fu[1], &d_fv[0], &d_fv[1], &d_f8}) b->release();
+            timer.release(); ftimer.release(); *this = Temporal();
+        }
     } temporal;
 };
 static_assert(ftk::kTemporalMinWeight == FT_TEMPORAL_MIN_WEIGHT, "the header states the constant k_temporal uses");

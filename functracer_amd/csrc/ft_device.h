@@ -264,6 +264,42 @@ struct TemporalArgs {
 };
 void launch_temporal(hipStream_t stream, const TemporalArgs& a);
 
+// ft_temporal_filter (ft_temporal_filter.hip; the filter is defined in functracer_hip.h and DESIGN.md 13): a variance-guided a-trous
+// filter that reads a history set in place.  Its own planes, in FRAME layout: the demodulation divisor d (one plane per channel; null
+// without `demodulate`: d = 1), the class (DenoiseGuides' values), and two colour buffers (3 doubles per pixel) and two variance planes
+// the iterations alternate between.  Before k_tfilter_prepare the class plane holds kDenoiseOutside outside the tiles and anything
+// else inside; prepare makes that hit or miss.
+struct TFilterPlanes { const double* d[3]; uint8_t* cls; };
+// The demodulate scatter: a window of k_aov's planes (colour as three planes of `stride` entries, leaf; by position in the window)
+// into d of the pixels pixel_ids[first .. first + n): max(colour, albedo_floor) where the set's leaf is a hit and the guide's leaf is
+// the same one, else 1.
+struct TFilterScatterArgs {
+    const uint32_t* pixel_ids; uint32_t first, n;
+    const double* colour; const int32_t* leaf; uint32_t stride;
+    const int32_t* set_leaf; double* d[3]; double albedo_floor;
+};
+void launch_tfilter_scatter(hipStream_t stream, const TFilterScatterArgs& a);
+// k_tfilter_prepare: one lane per pixel of the rect (x0, y0, w, h), clipped to the frame.  Writes the class, u0 = M / d (M itself with
+// `raw`: the call has no iterations and returns M bit for bit; then also out8 where non-null) and v0, the temporal variance or, where
+// N < min_history, the larger of it and the 7x7 spatial estimate.  inv_s*2 = 1 / sigma^2, 0: that term is off.
+struct TFilterPrepareArgs {
+    TemporalSet set; TFilterPlanes g;
+    double* u0; double* v0; uint8_t* out8;
+    int32_t res_h, res_v, x0, y0, w, h, raw;
+    double min_history, inv_sn2, inv_sp2;
+};
+void launch_tfilter_prepare(hipStream_t stream, const TFilterPrepareArgs& a);
+// k_tfilter: one a-trous iteration with taps `step` pixels apart over the whole frame, the 3x3 prefilter of the variance fused in:
+// (u_in, v_in) -> (u_out, v_out).  n, p are read from the set's planes.  `last`: the colour is multiplied by d and goes to u_out
+// and, as RGBA8 bytes, to out8, each where non-null.  At steps 1 and 2 tile and halo are staged in the LDS.
+struct TFilterArgs {
+    const double* u_in; const double* v_in; double* u_out; double* v_out; uint8_t* out8;
+    TemporalSet set; TFilterPlanes g;
+    int32_t res_h, res_v, step;
+    double inv_sn2, inv_sp2, inv_sc2, variance_floor;
+};
+void launch_tfilter(hipStream_t stream, const TFilterArgs& a, bool last);
+
 // Debug: closest hit / blocked for arbitrary rays (no slightOffset).
 void launch_debug_closest(const Launch& L, const DevScene& S, const double* o, const double* d, uint32_t n,
                           int32_t* hit, double* t, double* p, double* nrm, double* colour, unsigned long long* overflow);

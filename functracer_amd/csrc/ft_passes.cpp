@@ -1,4 +1,5 @@
-// ft_passes.cpp — the passes over the surface buffers: ft_render_aov, and ft_denoise and ft_temporal_* which take their guides from it.
+// ft_passes.cpp — the passes over the surface buffers: ft_render_aov, and ft_denoise, ft_temporal_* and ft_temporal_filter which take
+// their guides from it.
 #include "ft_context.h"
 
 namespace ftc {
@@ -396,6 +397,122 @@ int32_t ft_temporal_accumulate(ft_context* c, const ft_camera* cam, int32_t spp,
     if (!c->temporal.open) { c->err = "no temporal accumulation (ft_temporal_begin; a caller's ft_scene_commit or ft_scene_clear ends it)"; return FT_ERR_STATE; }
     const RenderRequest q{cam, c->temporal.res_h, c->temporal.res_v, spp, jitter_xy, 0, seed, nullptr, 0, 0};   // (the pixel list is made from the begin's rects)
     return with_growing_hit_lists(c, [&] { return temporal_single(c, q, sample, P, rgba8 != 0, out, stats); });
+}
+
+// ft_temporal_filter (functracer_hip.h): the set the last accumulate wrote, filtered in place.  Only the filter's own
+// planes are written until the call can no longer fail; the sets, cam', the counts, the cached pixel list and the level hint are not
+// touched.  Without `demodulate` there is no guide pass, no pixel list and no upload: the class plane is filled per rect and the
+// kernels run over rects and the frame.
+static int32_t temporal_filter_single(ft_context* c, const RenderRequest& q, int32_t sample, const ft_temporal_filter_params& P, bool rgba8, void* out,
+                                      double* out_variance, ft_stats* stats) {
+    const auto wall0 = std::chrono::steady_clock::now();
+    int32_t rc;
+    if ((rc = begin_pass(c, stats)) != FT_OK) return rc;
+    ft_context::Temporal& T = c->temporal;
+    if (P.to_frame && (rc = need_fp64_frame(c, "ft_temporal_filter", T.res_h, T.res_v, "filter's to_frame", " than ft_temporal_begin fixed")) != FT_OK) return rc;
+    AovRun run;
+    if (T.n_pix == 0) { end_pass(stats, run, 0.0, 0, wall0); return FT_OK; }
+    if (P.demodulate && !need_committed(c)) return FT_ERR_STATE;
+    if ((rc = drain_frame_streams(c)) != FT_OK) return rc;          // the frame may have been written on another stream (fetch_single)
+    const size_t n_px = (size_t)T.res_h * (size_t)T.res_v;
+    const bool want8 = out && rgba8, want_rgb = P.to_frame || (out && !rgba8);
+    if (P.demodulate && (rc = ensure(c, T.d_fd, n_px * 24)) != FT_OK) return rc;
+    if ((rc = ensure(c, T.d_fcls, n_px)) != FT_OK) return rc;
+    for (int k = 0; k < 2; ++k) {
+        if ((rc = ensure(c, T.d_fu[k], n_px * 24)) != FT_OK) return rc;
+        if ((rc = ensure(c, T.d_fv[k], n_px * 8)) != FT_OK) return rc;
+    }
+    if (want8 && (rc = ensure(c, T.d_f8, n_px * 4)) != FT_OK) return rc;
+    const ftk::TemporalSet set = temporal_set(T.d_set[T.prev], n_px);
+    ftk::TFilterPlanes g{};
+    double* dw[3] = {nullptr, nullptr, nullptr};
+    if (P.demodulate) for (int k = 0; k < 3; ++k) g.d[k] = dw[k] = T.d_fd.as<double>() + (size_t)k * n_px;
+    g.cls = T.d_fcls.as<uint8_t>();
+    FT_HIP(c, hipMemsetAsync(g.cls, ftk::kDenoiseOutside, n_px, c->stream));   // outside everywhere, then "in the tiles" per rect: k_tfilter_prepare makes that hit or miss
+    for (const ft_rect& r : T.rects)
+        FT_HIP(c, hipMemset2DAsync(g.cls + (size_t)r.y0 * (size_t)T.res_h + (size_t)r.x0, (size_t)T.res_h, ftk::kDenoiseMiss, (size_t)r.w, (size_t)r.h, c->stream));
+    double kernel_ms = 0.0;
+    int32_t n_launches = 0;
+    TimedLaunch& timer = T.ftimer;
+    if (P.demodulate) {
+        std::vector<uint32_t> px;
+        (void)list_pixels(T.rects, T.res_h, px);
+        const bool want[8] = {false, false, false, true, false, true, false, false};   // colour, leaf
+        rc = aov_windows(c, q, sample, want, px, run, [&](int64_t p0, uint32_t n, const AovPlanes& pl, char* dev) -> int32_t {
+            ftk::TFilterScatterArgs a{};
+            a.pixel_ids = c->aov.d_pixels.as<uint32_t>(); a.first = (uint32_t)p0; a.n = n;
+            a.colour = reinterpret_cast<const double*>(dev + pl.off[3]); a.leaf = reinterpret_cast<const int32_t*>(dev + pl.off[5]); a.stride = n;
+            a.set_leaf = set.leaf; a.albedo_floor = P.albedo_floor;
+            for (int k = 0; k < 3; ++k) a.d[k] = dw[k];
+            ++n_launches;
+            return timer.run(c, kernel_ms, [&] { ftk::launch_tfilter_scatter(c->stream, a); });
+        });
+        if (rc != FT_OK) return rc;
+    }
+    auto inv_sq = [](double sigma) { return sigma > 0.0 ? 1.0 / (sigma * sigma) : 0.0; };
+    const void* result = T.d_fu[0].p;                               // no iterations: prepare's M
+    const double* variance = T.d_fv[0].as<double>();
+    rc = timer.run(c, kernel_ms, [&] {                              // one bracket around prepare and all iterations
+        for (const ft_rect& r : T.rects) {
+            ftk::TFilterPrepareArgs a{};
+            a.set = set; a.g = g; a.u0 = T.d_fu[0].as<double>(); a.v0 = T.d_fv[0].as<double>();
+            a.raw = P.iterations == 0 ? 1 : 0; a.out8 = a.raw && want8 ? T.d_f8.as<uint8_t>() : nullptr;
+            a.res_h = T.res_h; a.res_v = T.res_v; a.x0 = r.x0; a.y0 = r.y0; a.w = r.w; a.h = r.h;
+            a.min_history = (double)P.min_history; a.inv_sn2 = inv_sq(P.sigma_normal); a.inv_sp2 = inv_sq(P.sigma_position);
+            ftk::launch_tfilter_prepare(c->stream, a);
+            ++n_launches;
+        }
+        for (int i = 0; i < P.iterations; ++i) {
+            const bool last = i + 1 == P.iterations;
+            ftk::TFilterArgs a{};
+            a.u_in = T.d_fu[i & 1].as<double>(); a.v_in = T.d_fv[i & 1].as<double>();
+            a.u_out = !last || want_rgb ? T.d_fu[(i + 1) & 1].as<double>() : nullptr; a.v_out = T.d_fv[(i + 1) & 1].as<double>();
+            a.out8 = last && want8 ? T.d_f8.as<uint8_t>() : nullptr;
+            a.set = set; a.g = g; a.res_h = T.res_h; a.res_v = T.res_v; a.step = 1 << i;
+            a.inv_sn2 = inv_sq(P.sigma_normal); a.inv_sp2 = inv_sq(P.sigma_position); a.inv_sc2 = inv_sq(P.sigma_colour); a.variance_floor = P.variance_floor;
+            ftk::launch_tfilter(c->stream, a, last);
+            ++n_launches;
+            if (last) { result = a.u_out; variance = a.v_out; }
+        }
+    });
+    if (rc != FT_OK) return rc;
+    if (out && (rc = copy_rects_out(c, out, rgba8 ? T.d_f8.p : result, rgba8 ? 4 : 24, T.res_h, T.rects, nullptr)) != FT_OK) return rc;
+    if (out_variance && (rc = copy_rects_out(c, out_variance, variance, 8, T.res_h, T.rects, nullptr)) != FT_OK) return rc;
+    if (P.to_frame) {                                               // the result replaces the tile pixels of the frame, once the call can no longer fail
+        const size_t pitch = (size_t)T.res_h * 24;
+        for (const ft_rect& r : T.rects) {
+            const size_t off = (size_t)r.y0 * pitch + (size_t)r.x0 * 24;
+            FT_HIP(c, hipMemcpy2DAsync(c->d_out.as<char>() + off, pitch, static_cast<const char*>(result) + off, pitch, (size_t)r.w * 24, (size_t)r.h, hipMemcpyDeviceToDevice, c->stream));
+        }
+        FT_HIP(c, hipStreamSynchronize(c->stream));
+        c->zero_signature[0] = 0;                                   // (as ft_temporal_accumulate's to_frame)
+    }
+    end_pass(stats, run, kernel_ms, n_launches, wall0);
+    if (stats) stats->trace_kernel_ms = run.kernel_ms;
+    return FT_OK;
+}
+
+int32_t ft_temporal_filter(ft_context* c, const ft_camera* cam, int32_t spp, const double* jitter_xy, int32_t sample, uint64_t seed,
+                           const ft_temporal_filter_params* params, int32_t rgba8, void* out, double* out_variance, ft_stats* stats) {
+    if (!c) return FT_ERR_INVALID;
+    if (!params || (!out && !out_variance)) { c->err = "ft_temporal_filter: null params, or neither out nor out_variance"; return FT_ERR_INVALID; }
+    const ft_temporal_filter_params& P = *params;
+    if (P.iterations < 0 || P.iterations > 6) { c->err = "ft_temporal_filter: iterations outside 0 .. 6"; return FT_ERR_INVALID; }
+    if (!(P.sigma_colour >= 0.0) || !(P.sigma_normal >= 0.0) || !(P.sigma_position >= 0.0)) { c->err = "ft_temporal_filter: a sigma is negative or NaN (0 switches a term off)"; return FT_ERR_INVALID; }
+    if (P.min_history < 1) { c->err = "ft_temporal_filter: min_history below 1"; return FT_ERR_INVALID; }
+    if (!(P.variance_floor > 0.0)) { c->err = "ft_temporal_filter: variance_floor is not > 0"; return FT_ERR_INVALID; }
+    if (P.demodulate && !(P.albedo_floor > 0.0)) { c->err = "ft_temporal_filter: demodulate needs albedo_floor > 0"; return FT_ERR_INVALID; }
+    int32_t rc;
+    if (P.demodulate) {
+        if ((rc = check_guide_sample(c, "ft_temporal_filter", spp, jitter_xy, sample, " to take the material colour from")) != FT_OK) return rc;
+        if (!cam) { c->err = "ft_temporal_filter: demodulate needs the camera of the accumulate call"; return FT_ERR_INVALID; }
+    }
+    if (!need_device(c)) return FT_ERR_NO_DEVICE;
+    if ((rc = need_one_device(c, "ft_temporal_filter")) != FT_OK) return rc;
+    if (!c->temporal.open) { c->err = "no temporal accumulation (ft_temporal_begin; a caller's ft_scene_commit or ft_scene_clear ends it)"; return FT_ERR_STATE; }
+    if (c->temporal.calls == 0) { c->err = "ft_temporal_filter: no ft_temporal_accumulate since ft_temporal_begin"; return FT_ERR_STATE; }
+    const RenderRequest q{cam, c->temporal.res_h, c->temporal.res_v, spp, jitter_xy, 0, seed, nullptr, 0, 0};   // (read with demodulate only)
+    return with_growing_hit_lists(c, [&] { return temporal_filter_single(c, q, sample, P, rgba8 != 0, out, out_variance, stats); });
 }
 
 int32_t ft_temporal_fetch(ft_context* c, double* mean_rgb, double* stderr_rgb, double* length) {

@@ -414,6 +414,56 @@ int32_t ft_temporal_status(ft_context* ctx, int64_t out[4]);
 /* End the accumulation and free its buffers (FT_OK when there is none). */
 int32_t ft_temporal_end(ft_context* ctx);
 
+/* ---- variance-guided filter of the temporal history -------------------------------------------- */
+/* ft_temporal_filter filters, on the device, the history set the last ft_temporal_accumulate wrote (the "previous" set after the flip)
+ * with an edge-avoiding a-trous filter whose colour term is scaled by a per-pixel variance that is filtered from iteration to iteration
+ * (Schied et al. 2017), FP64.  The set is read in place.  Per frame pixel x: M(x), N(x), p(x), n(x), leaf(x) of the set; se_ch(x) the
+ * per-channel standard error exactly as ft_temporal_fetch defines it (sqrt(max(0, Q - M*M) / max(N, 1)), the product unfused, 0 where
+ * N < 2); T the tile pixels fixed at ft_temporal_begin; k(x) the class: hit (leaf >= 0) or miss for x in T, "outside" otherwise, which
+ * matches no tap.  max(a, b) below is a > b ? a : b.
+ *  1. d(x).  With `demodulate` one guide pass (ft_render_aov's colour a and leaf for cam, the begin's size, spp, jitter_xy, sample, seed:
+ *     the arguments of the accumulate call this follows) gives, for a hit pixel whose guide leaf equals the set's leaf, d(x) = per channel
+ *     max(a(x), albedo_floor); otherwise, and without `demodulate`, d(x) = 1.  Without `demodulate` cam, spp, jitter_xy, sample and seed
+ *     are not read (they may be null / 0), no guide pass runs and no pixel list is uploaded.
+ *  2. u_0 = M / d;  vt(x) = (1/3) * sum_ch (se_ch(x) / d_ch(x))^2.
+ *  3. Where N(x) < min_history (N compared as the double that is stored), a spatial estimate: taps q = x + (dx, dy), dy = -3 .. 3 outer,
+ *     dx = -3 .. 3 inner, taking part iff q is in the frame, k(q) == k(x) and u_0(q) is finite;
+ *     g = exp(-(|n(x)-n(q)|^2 / sigma_normal^2 + |p(x)-p(q)|^2 / sigma_position^2)) (a term whose sigma is 0 is left out; a miss pixel has
+ *     no geometric term); m1_ch = sum g * u_0(q)_ch / sum g, m2_ch = sum g * (u_0(q)_ch * u_0(q)_ch) / sum g,
+ *     vs = (1/3) * sum_ch max(m2_ch - m1_ch * m1_ch, 0) with the product unfused; v_0(x) = max(vs, vt(x)).  Elsewhere v_0(x) = vt(x).
+ *  4. For i = 0 .. iterations-1, s = 2^i, h = [1/16, 1/4, 3/8, 1/4, 1/16]:
+ *     gv_i(x) = the 3x3 average of v_i with the weights [1/4, 1/2, 1/4] x [1/4, 1/2, 1/4] over the taps at distance 1 (not s) that are
+ *     in the frame, have class k(x) and a finite v_i, renormalised by the weights that took part;
+ *     taps q = x + s * (dx, dy), dy = -2 .. 2 outer, dx = -2 .. 2 inner (the summation order), taking part iff q is in the frame,
+ *     k(q) == k(x), u_i(q) and v_i(q) are finite and E is not NaN, with
+ *     E = |n(x)-n(q)|^2 / sigma_normal^2 + |p(x)-p(q)|^2 / sigma_position^2 + |u_i(x)-u_i(q)|^2 / (sigma_colour^2 * (gv_i(x) + variance_floor))
+ *     (a term whose sigma is 0 is left out; a miss pixel has no geometric term; there is no 2^-i on sigma_colour: the variance shrinks
+ *     by itself), w = h[dx+2] * h[dy+2] * exp(-E),
+ *     u_{i+1}(x) = (sum w * u_i(q)) / (sum w),   v_{i+1}(x) = (sum w * w * v_i(q)) / (sum w)^2.
+ *     A pixel whose own u_i(x) or v_i(x) is not finite is copied through, u and v: an N = 0 pixel of ft_temporal_accumulate's clause 5
+ *     stays where it is and spreads nothing.
+ *  5. u_N(x) * d(x) for x in T goes to `out`, laid out as ft_render's out_rgb, or as ft_render_rgba8's bytes when rgba8 != 0 (quantised
+ *     on the device with ft_quantise_rgba8's arithmetic); v_N(x) goes to out_variance (res_v x res_h doubles); either may be NULL, not
+ *     both.  Pixels outside T are not written.  iterations == 0 returns M bit for bit, and v_0.  With to_frame != 0 the FP64 result also
+ *     replaces the tile pixels of the FP64 frame in HBM once the call can no longer fail (and which blocks the last ft_render left as
+ *     Colour.Zero is forgotten, exactly as ft_temporal_accumulate's to_frame does).
+ * The history sets, cam', the counts of ft_temporal_status, the level hint, the cached pixel list, a progressive accumulation and
+ * (without to_frame) the frame buffer are left untouched: an accumulate after a filter call gives bit for bit what it gives without
+ * one.  The filtered colour is NOT fed back into the history (SVGF does; it would change what ft_temporal_* means).
+ * Errors, checked before anything runs, in this order: null params, or out and out_variance both null, FT_ERR_INVALID; iterations
+ * outside 0 .. 6, a negative or NaN sigma, min_history < 1, variance_floor not > 0, demodulate with albedo_floor not > 0 FT_ERR_INVALID;
+ * with demodulate, spp == 0 FT_ERR_UNSUPPORTED, then null cam or jitter_xy, spp < 0, sample outside [0, spp) FT_ERR_INVALID; a host-only
+ * context FT_ERR_NO_DEVICE; a context over several devices FT_ERR_UNSUPPORTED; no begin, an accumulation ended by a commit, or no
+ * accumulate call since begin FT_ERR_STATE; to_frame without an FP64 frame of the begin's size in HBM FT_ERR_STATE.
+ * The call blocks and retires queued frames first.  Hit lists that overflow in the guide pass grow and the call runs again
+ * (csg_auto_grow).  stats: as ft_temporal_accumulate's; trace_kernel_ms is the guide pass's share of kernel_ms, 0 without demodulate.
+ * Device memory, allocated by the first filter call of an accumulation and freed with it (ft_temporal_end, a commit, the context), per
+ * frame pixel: d 24 (with demodulate), class 1, two colour buffers of 24, two variance planes of 8, and 4 of RGBA8 when asked for. */
+typedef struct ft_temporal_filter_params { int32_t iterations, demodulate, min_history, to_frame;
+    double sigma_colour, sigma_normal, sigma_position, albedo_floor, variance_floor; } ft_temporal_filter_params;   /* 56 bytes */
+int32_t ft_temporal_filter(ft_context* ctx, const ft_camera* cam, int32_t spp, const double* jitter_xy, int32_t sample, uint64_t seed,
+                           const ft_temporal_filter_params* params, int32_t rgba8, void* out, double* out_variance, ft_stats* stats);
+
 /* Closest hit of single rays through the device path (Scene.intersectScene, Scene.fs:118, after
  * Shading.slightOffset is NOT applied): for tests.  Outputs per ray: t, p[3], n[3], material index
  * resolved colour[3]; hit[i] = 0 when the ray misses. */
