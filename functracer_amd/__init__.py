@@ -64,7 +64,7 @@ def hip_lib():
         lib.ft_denoise.argtypes = _capi.DENOISE_SIGNATURE
         lib.ft_temporal_filter.restype, lib.ft_temporal_filter.argtypes = C.c_int32, _capi.TEMPORAL_FILTER_SIGNATURE
         lib.ft_quantise_rgba8.argtypes = [_capi.c_double_p, C.c_int64, C.POINTER(C.c_uint8)]
-        for name, res, args in _capi.PROGRESSIVE_SIGNATURES + _capi.TEMPORAL_SIGNATURES:
+        for name, res, args in _capi.PROGRESSIVE_SIGNATURES + _capi.TEMPORAL_SIGNATURES + _capi.MOTION_SIGNATURES:
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _hip = lib
@@ -502,6 +502,25 @@ class Context(SceneBuilder):
         if shape is None:                                           # the frame's size is unknown: nothing to size the output by
             raise FtError(-5, "no temporal accumulation (temporal_begin)")
         return shape
+
+    # moving rigid objects under a temporal accumulation (include/functracer_hip.h) ---------------------
+    def set_transform(self, node, ops):
+        """ft_sg_set_transform: replace the transform list of the node `transform(ops, child)` returned (ops as there); the child stays."""
+        self._check(self._lib.ft_sg_set_transform(self._ctx, int(node), _capi.transform_array(ops) if len(ops) else None, len(ops)))
+
+    def commit_moved(self):
+        """ft_scene_commit_moved: commit a graph whose transforms alone changed since the last commit.  A temporal accumulation stays open
+        and its history follows the moved leaves; a progressive accumulation ends."""
+        self._check(self._lib.ft_scene_commit_moved(self._ctx))
+        self._progressive = None
+
+    def leaf_matrices(self):
+        """ft_debug_leaf_matrices: (m2w[leaves, 3, 4], w2m[leaves, 3, 4]) of the scene the context holds."""
+        n = C.c_int64()
+        self._check(self._lib.ft_debug_leaf_matrices(self._ctx, C.byref(n), None, None))
+        m2w, w2m = np.zeros((n.value, 3, 4)), np.zeros((n.value, 3, 4))
+        self._check(self._lib.ft_debug_leaf_matrices(self._ctx, C.byref(n), _capi.dptr(m2w), _capi.dptr(w2m)))
+        return m2w, w2m
 
     def pick(self, camera, res_h, res_v, x, y, spp=1, jitter=None, sample=0, seed=DEFAULT_SEED):
         """What is at pixel (x, y) (row 0 = top): the record of render_aov for that one pixel (a 1x1 tile) as a dict of plain

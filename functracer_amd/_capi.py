@@ -104,6 +104,14 @@ TEMPORAL_SIGNATURES = [
 ]
 
 
+# Moving rigid objects under a temporal accumulation (include/functracer_hip.h): not part of the generic builder, which also drives the oracle.
+MOTION_SIGNATURES = [
+    ("ft_sg_set_transform", C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(ft_transform), C.c_int32]),
+    ("ft_scene_commit_moved", C.c_int32, [C.c_void_p]),
+    ("ft_debug_leaf_matrices", C.c_int32, [C.c_void_p, C.POINTER(C.c_int64), c_double_p, c_double_p]),
+]
+
+
 class ft_temporal_filter_params(C.Structure):
     """ft_temporal_filter's parameters (include/functracer_hip.h): a-trous iterations 0 .. 6, demodulation by the material colour, the
     history length below which the spatial variance estimate steps in, whether the result replaces the frame in HBM, the three
@@ -198,6 +206,20 @@ def bind_builder(lib, prefix):
     return table
 
 
+def transform_array(ops):
+    """ft_transform[len(ops)] of ('translate', v) | ('scale', v) | ('rotate', axis, angle_rad) entries."""
+    arr = (ft_transform * len(ops))()
+    for i, op in enumerate(ops):
+        kind = {"translate": TRANSLATE, "scale": SCALE, "rotate": ROTATE}[op[0]]
+        arr[i].kind = kind
+        v = op[1]
+        if kind == SCALE and np.isscalar(v):
+            v = (v, v, v)
+        arr[i].v = (C.c_double * 3)(*[float(x) for x in v])
+        arr[i].angle = float(op[2]) if kind == ROTATE else 0.0
+    return arr
+
+
 class SceneBuilder:
     """Mirror of the Scene.fs constructors over a C context (`lib`, `prefix`, `ctx` pointer)."""
 
@@ -235,16 +257,7 @@ class SceneBuilder:
     # Scene.SceneFunction --------------------------------------------------------------
     def transform(self, ops, child):
         """ops: list of ('translate', v) | ('scale', v) | ('rotate', axis, angle_rad); >1 entries = Composed."""
-        arr = (ft_transform * len(ops))()
-        for i, op in enumerate(ops):
-            kind = {"translate": TRANSLATE, "scale": SCALE, "rotate": ROTATE}[op[0]]
-            arr[i].kind = kind
-            v = op[1]
-            if kind == SCALE and np.isscalar(v):
-                v = (v, v, v)
-            arr[i].v = (C.c_double * 3)(*[float(x) for x in v])
-            arr[i].angle = float(op[2]) if kind == ROTATE else 0.0
-        return self._check(self._f("sg_transform")(self._ctx, arr, len(ops), child))
+        return self._check(self._f("sg_transform")(self._ctx, transform_array(ops), len(ops), child))
 
     def translate(self, v, child):
         return self.transform([("translate", v)], child)

@@ -218,7 +218,7 @@ int32_t ft_set_option(ft_context* c, const char* key, int64_t value) {
 }
 
 // ------------------------------------------------------------------------------------------ builder
-static ft_node add_node(ft_context* c, fth::GraphNode&& n) { c->graph.nodes.push_back(std::move(n)); c->committed = false; return (ft_node)c->graph.nodes.size() - 1; }
+static ft_node add_node(ft_context* c, fth::GraphNode&& n) { c->graph.nodes.push_back(std::move(n)); c->committed = false; c->restructured = true; return (ft_node)c->graph.nodes.size() - 1; }
 
 ft_node ft_sg_primitive(ft_context* c, int32_t kind) {
     if (!c || kind < 0 || kind > FT_PRIM_CYLINDER) return FT_ERR_INVALID;
@@ -238,6 +238,17 @@ ft_node ft_sg_transform(ft_context* c, const ft_transform* ts, int32_t n_ts, ft_
     for (int i = 0; i < n_ts; ++i) { if (ts[i].kind < FT_TRANSLATE || ts[i].kind > FT_ROTATE) return FT_ERR_INVALID; n.xf.push_back(ts[i]); }
     n.children = {child};
     return add_node(c, std::move(n));
+}
+// The transform list of an existing Transform node replaced; the child stays.  Not a structural change: the graph flattens to the same
+// leaves in the same order, which is what ft_scene_commit_moved needs.
+int32_t ft_sg_set_transform(ft_context* c, ft_node node, const ft_transform* ts, int32_t n_ts) {
+    if (!c) return FT_ERR_INVALID;
+    if (!c->graph.valid(node) || c->graph.nodes[node].kind != fth::GraphNode::Transform) { c->err = "ft_sg_set_transform: not a transform node"; return FT_ERR_INVALID; }
+    if (!ts || n_ts < 1) { c->err = "ft_sg_set_transform: no transforms"; return FT_ERR_INVALID; }
+    for (int i = 0; i < n_ts; ++i) if (ts[i].kind < FT_TRANSLATE || ts[i].kind > FT_ROTATE) { c->err = "ft_sg_set_transform: bad transform kind"; return FT_ERR_INVALID; }
+    c->graph.nodes[node].xf.assign(ts, ts + n_ts);
+    c->committed = false;
+    return FT_OK;
 }
 ft_node ft_sg_material(ft_context* c, const ft_material* m, ft_node child) {
     if (!c || !c->graph.valid(child) || !m) return FT_ERR_INVALID;
@@ -281,33 +292,33 @@ int32_t ft_scene_clear(ft_context* c) {
     if (!c) return FT_ERR_INVALID;
     progressive_close(c);
     temporal_close(c);
-    c->graph.nodes.clear(); c->graph.lights.clear(); c->graph.root = -1; c->committed = false;
+    c->graph.nodes.clear(); c->graph.lights.clear(); c->graph.root = -1; c->committed = false; c->restructured = true;
     return FT_OK;
 }
 int32_t ft_scene_set_objects(ft_context* c, ft_node root) {
     if (!c || !c->graph.valid(root)) return FT_ERR_INVALID;
-    c->graph.root = root; c->committed = false;
+    c->graph.root = root; c->committed = false; c->restructured = true;
     return FT_OK;
 }
 int32_t ft_scene_add_directional(ft_context* c, const double dir[3], const double colour[3]) {      // Light.directional (Light.fs:19-20)
     if (!c || !dir || !colour) return FT_ERR_INVALID;
     ftd::Light l{}; l.kind = ftd::LT_DIRECTIONAL;
     std::memcpy(l.v, dir, sizeof l.v); norm3(l.v); std::memcpy(l.colour, colour, sizeof l.colour);
-    c->graph.lights.push_back(l); c->committed = false;
+    c->graph.lights.push_back(l); c->committed = false; c->restructured = true;
     return FT_OK;
 }
 int32_t ft_scene_add_soft_directional(ft_context* c, const double dir[3], int32_t samples, double scatter_rad, const double colour[3]) {  // Light.fs:22-23
     if (!c || !dir || !colour || samples < 1) return FT_ERR_INVALID;
     ftd::Light l{}; l.kind = ftd::LT_SOFT; l.samples = samples; l.scatter = scatter_rad;
     std::memcpy(l.v, dir, sizeof l.v); norm3(l.v); std::memcpy(l.colour, colour, sizeof l.colour);
-    c->graph.lights.push_back(l); c->committed = false;            // rejected at commit until the seeded stream lands
+    c->graph.lights.push_back(l); c->committed = false; c->restructured = true;            // rejected at commit until the seeded stream lands
     return FT_OK;
 }
 int32_t ft_scene_add_positional(ft_context* c, const double pos[3], const double falloff[3], const double colour[3]) {  // Light.fs:25-26
     if (!c || !pos || !falloff || !colour) return FT_ERR_INVALID;
     ftd::Light l{}; l.kind = ftd::LT_POINT;
     std::memcpy(l.v, pos, sizeof l.v); std::memcpy(l.falloff, falloff, sizeof l.falloff); std::memcpy(l.colour, colour, sizeof l.colour);
-    c->graph.lights.push_back(l); c->committed = false;
+    c->graph.lights.push_back(l); c->committed = false; c->restructured = true;
     return FT_OK;
 }
 
@@ -407,6 +418,8 @@ int32_t commit_scene(ft_context* c) {
     using clock = std::chrono::steady_clock;
     auto ms_since = [](clock::time_point t0) { return std::chrono::duration<double, std::milli>(clock::now() - t0).count(); };
     for (double& v : c->commit_ms) v = 0.0;
+    c->holds_commit = false;                                        // `flat` is being replaced
+    const auto done = [c](int32_t rc) { if (rc == FT_OK) { c->holds_commit = true; c->restructured = false; } return rc; };
     // A device context builds the exact BVH of top-level-Leaf meshes on the device ("bvh_builder" = 1; 2, the default: from 4096 triangles on): the flattener
     // reserves the ranges, upload_scene fills them.  A build the device refuses (a tree too deep for the traversal stacks) falls
     // back to the host's builder, once, for the whole scene.
@@ -417,7 +430,7 @@ int32_t commit_scene(ft_context* c) {
         int32_t rc = c->graph.flatten(c->flat, c->err);
         c->commit_ms[0] += ms_since(t0);
         if (rc != FT_OK) return rc;
-        if (c->host_only) { c->committed = true; return FT_OK; }
+        if (c->host_only) { c->committed = true; return done(FT_OK); }
         t0 = clock::now();
         rc = upload_scene(c);
         for (ft_context* p : c->peers) {                            // replicate the flattened scene on every other device
@@ -428,7 +441,7 @@ int32_t commit_scene(ft_context* c) {
         }
         c->commit_ms[2] += ms_since(t0) - c->commit_ms[1];
         if (rc == FT_ERR_BUILD && c->graph.device_bvh) continue;    // refused by the device builder: the host builds it
-        return rc;
+        return done(rc);
     }
     return FT_ERR_BUILD;
 }
@@ -443,6 +456,19 @@ int32_t ft_scene_commit(ft_context* c) {
     progressive_close(c);
     temporal_close(c);
     return commit_scene(c);
+}
+
+// The commit of a graph whose transforms alone changed (ft_sg_set_transform): ft_scene_commit's, but the temporal accumulation stays
+// open - the leaves are the same in the same order, and the next ft_temporal_accumulate takes each moved leaf's surfaces back to the
+// pose its history was written in (ft_passes.cpp).  A progressive accumulation's sums belong to the old scene: it ends.
+int32_t ft_scene_commit_moved(ft_context* c) {
+    if (!c) return FT_ERR_INVALID;
+    if (!c->holds_commit) { c->err = "ft_scene_commit_moved: no committed scene to move (ft_scene_commit)"; return FT_ERR_STATE; }
+    if (c->restructured) { c->err = "ft_scene_commit_moved: the graph, the root or the lights changed since the commit (ft_scene_commit)"; return FT_ERR_STATE; }
+    progressive_close(c);
+    const int32_t rc = commit_scene(c);
+    if (rc == FT_OK) ++c->pose_serial;
+    return rc;
 }
 
 int32_t ft_get_commit_times(ft_context* c, double ms[4]) {

@@ -154,6 +154,10 @@ struct ft_context {
     fth::FlatScene flat;
     std::vector<float> cull_items_and_rows;   // what d_scene[kCullItems] holds (the upload's source)
     bool committed = false;
+    // What ft_scene_commit_moved asks for: `flat` is a successful commit's, and no builder call since has added a node, changed the root
+    // or the lights, or cleared the graph (ft_sg_set_transform and ft_set_option have not) - the same leaves in the same order.
+    bool holds_commit = false, restructured = false;
+    uint64_t pose_serial = 0;       // advanced by ft_scene_commit_moved only (commit_serial also by the hit lists' re-commit, which moves nothing)
     double commit_ms[4] = {0, 0, 0, 0};   // last ft_scene_commit: flatten on the host, device BVH builds, uploads + the rest, BVH height (not a time)
 
     DeviceBuf d_scene[kSceneArrays];
@@ -262,12 +266,17 @@ struct ft_context {
         DeviceBuf d_set[2], d_rgb, d_rgba8, d_ctr;
         TimedLaunch timer;              // around each k_temporal launch (kernel_ms)
         int prev = 0;
+        // The pose the history was written in: the context's pose_serial at the last successful accumulate and every
+        // leaf's m2w and w2m then (12 doubles each); d_motion: the call's records for k_temporal<true> (ftk::kTemporalMotionDoubles per leaf)
+        uint64_t pose = 0;
+        std::vector<double> h_m2w, h_w2m;
+        DeviceBuf d_motion;
         // ft_temporal_filter's planes, frame-sized, allocated by the first filter call of the accumulation: the divisor d,
         // the class, the two colour buffers and the two variance planes the iterations alternate between, and the RGBA8 result
         DeviceBuf d_fd, d_fcls, d_fu[2], d_fv[2], d_f8;
         TimedLaunch ftimer;             // around the kernels of a filter call (kernel_ms)
         void release() {
-            for (DeviceBuf* b : {&d_set[0], &d_set[1], &d_rgb, &d_rgba8, &d_ctr, &d_fd, &d_fcls, &d_fu[0], &d_fu[1], &d_fv[0], &d_fv[1], &d_f8}) b->release();
+            for (DeviceBuf* b : {&d_set[0], &d_set[1], &d_rgb, &d_rgba8, &d_ctr, &d_motion, &d_fd, &d_fcls, &d_fu[0], &d_fu[1], &d_fv[0], &d_fv[1], &d_f8}) b->release();
             timer.release(); ftimer.release(); *this = Temporal();
         }
     } temporal;

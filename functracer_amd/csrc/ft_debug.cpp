@@ -143,6 +143,18 @@ int32_t ft_debug_scene_info(ft_context* c, int64_t out[12]) {
     return FT_OK;
 }
 
+// The per-leaf matrices of the scene the context holds (the last successful commit's, also while the graph is being edited): 12
+// doubles each, rows of the 3x4 model->world and world->model matrices.
+int32_t ft_debug_leaf_matrices(ft_context* c, int64_t* n_leaves, double* m2w, double* w2m) {
+    if (!c || !n_leaves) return FT_ERR_INVALID;
+    if (!c->holds_commit) { c->err = "scene not committed"; return FT_ERR_STATE; }
+    const fth::FlatScene& f = c->flat;
+    *n_leaves = (int64_t)f.leaves.size();
+    if (m2w) std::memcpy(m2w, f.m2w.data(), f.leaves.size() * 12 * sizeof(double));
+    if (w2m) for (size_t k = 0; k < f.leaves.size(); ++k) std::memcpy(w2m + 12 * k, f.leaves[k].w2m, sizeof f.leaves[k].w2m);
+    return FT_OK;
+}
+
 int32_t ft_debug_light_space(ft_context* c, int64_t sizes[4], double* pairs, uint32_t* nodes, double* tris, uint32_t* leaf_pairs) {
     if (!c || !sizes) return FT_ERR_INVALID;
     if (!c->committed) { c->err = "scene not committed"; return FT_ERR_STATE; }

@@ -251,6 +251,12 @@ constexpr double kTemporalMinWeight = 1.0 / 16.0;   // FT_TEMPORAL_MIN_WEIGHT (f
 // to through the previous call's image plane (o, i, j, k, tlx, tly, pw, ph); the pixel's record goes into `cur`, its mean into
 // out_rgb (frame layout, 3 doubles per pixel) and out8 (RGBA8) where those are non-null.  has_prev == 0: the first call after begin.
 // tol_scale = position_tolerance_px * max(pw, ph).  counters[0] += pixels with valid history, counters[1] += pixels at max_history.
+// motion: null (the scene has the pose the history was written in), or one record of kTemporalMotionDoubles per leaf of the scene
+// (n_leaves of them) that takes a hit pixel's point and normal back to that pose before they are projected and compared:
+//   [0..11] D, rows of the 3x4 map from a current world point of the leaf to where that point was; [12..20] A, rows of the 3x3
+//   inverse of D's linear part (a normal goes back through its transpose); [21] 1.0 if the leaf moved, 0.0: p and n are used as they
+//   are; [22], [23] unused.
+constexpr int kTemporalMotionDoubles = 24;
 struct TemporalArgs {
     const uint32_t* pixel_ids; uint32_t first, n;
     const double *p_plane, *n_plane; const int32_t* leaf; uint32_t stride;
@@ -261,6 +267,7 @@ struct TemporalArgs {
     double max_history, min_normal_dot, tol_scale;
     double* out_rgb; uint8_t* out8;
     unsigned long long* counters;
+    const double* motion; uint32_t n_leaves;
 };
 void launch_temporal(hipStream_t stream, const TemporalArgs& a);
 

@@ -4,7 +4,8 @@
 
 namespace ftc {
 
-// Ends the temporal accumulation of a context (its buffers are freed): leaf ids are only comparable within one commit.
+// Ends the temporal accumulation of a context (its buffers are freed): leaf ids are only comparable within one commit and the
+// ft_scene_commit_moved calls that follow it.
 void temporal_close(ft_context* c) {
     if (!c->temporal.open) return;
     (void)hipSetDevice(c->device);
@@ -298,6 +299,31 @@ static ftk::TemporalSet temporal_set(const DeviceBuf& b, size_t n_px) {
     return s;
 }
 
+// The records of k_temporal<true> (ftk::kTemporalMotionDoubles per leaf, ft_device.h) for a scene whose leaves stand at (m2w, w2m) now
+// and whose history was written when they stood at (H, Wh).  Per leaf: D = H o w2m, a 3x4 affine product that takes a current world
+// point of the leaf to where it was; A = m2w_lin * Wh_lin, the inverse of D's linear part; moved: any of the 12 m2w doubles differs.
+static std::vector<double> temporal_motion(const fth::FlatScene& f, const std::vector<double>& H, const std::vector<double>& Wh) {
+    const size_t n = f.leaves.size();
+    std::vector<double> rec(n * ftk::kTemporalMotionDoubles, 0.0);
+    for (size_t l = 0; l < n; ++l) {
+        const double* M = &f.m2w[12 * l];
+        const double* Wc = f.leaves[l].w2m;
+        const double* Hl = &H[12 * l];
+        const double* Wl = &Wh[12 * l];
+        double* r = &rec[l * ftk::kTemporalMotionDoubles];
+        for (int i = 0; i < 3; ++i) {
+            for (int j = 0; j < 4; ++j) {
+                double d = Hl[4 * i] * Wc[j] + Hl[4 * i + 1] * Wc[4 + j] + Hl[4 * i + 2] * Wc[8 + j];
+                if (j == 3) d += Hl[4 * i + 3];
+                r[4 * i + j] = d;
+            }
+            for (int j = 0; j < 3; ++j) r[12 + 3 * i + j] = M[4 * i] * Wl[j] + M[4 * i + 1] * Wl[4 + j] + M[4 * i + 2] * Wl[8 + j];
+        }
+        r[21] = std::memcmp(M, Hl, 12 * sizeof(double)) != 0 ? 1.0 : 0.0;   // bitwise: any double differs (a NaN matrix counts as moved)
+    }
+    return rec;
+}
+
 int32_t ft_temporal_begin(ft_context* c, int32_t res_h, int32_t res_v, const ft_rect* tiles, int32_t n_tiles) {
     if (!c) return FT_ERR_INVALID;
     if (res_h < 2 || res_v < 2 || (tiles && n_tiles < 1) || (int64_t)res_h * res_v > (int64_t)0x7FFFFFFF) { c->err = "bad ft_temporal_begin argument"; return FT_ERR_INVALID; }
@@ -341,6 +367,15 @@ static int32_t temporal_single(ft_context* c, const RenderRequest& q, int32_t sa
     if (want_rgba8 && (rc = ensure(c, T.d_rgba8, n_px * 4)) != FT_OK) return rc;
     FT_HIP(c, hipMemsetAsync(T.d_ctr.p, 0, 2 * sizeof(unsigned long long), c->stream));
     const ftk::Camera cam = make_camera(*q.cam, T.res_h, T.res_v);
+    // The scene was committed in another pose since the history was written (ft_scene_commit_moved, perhaps several times: H is the
+    // pose of the last accumulate, so they compose): every leaf's way back to that pose goes up and k_temporal<true> runs.
+    const size_t n_leaves = c->flat.leaves.size();
+    const bool moving = T.calls > 0 && T.pose != c->pose_serial;
+    if (moving) {
+        if (T.h_m2w.size() != 12 * n_leaves || T.h_w2m.size() != 12 * n_leaves) { c->err = "ft_temporal_accumulate: the scene has other leaves than the history"; return FT_ERR_STATE; }
+        if ((rc = upload(c, T.d_motion, temporal_motion(c->flat, T.h_m2w, T.h_w2m))) != FT_OK) return rc;
+        FT_HIP(c, hipStreamSynchronize(c->stream));                 // (the records are a temporary)
+    }
     double kernel_ms = 0.0;
     int32_t n_launches = 0;
     AovRun run;
@@ -359,6 +394,7 @@ static int32_t temporal_single(ft_context* c, const RenderRequest& q, int32_t sa
         a.tol_scale = P.position_tolerance_px * std::max(T.cam.pw, T.cam.ph);
         a.out_rgb = want_rgb ? T.d_rgb.as<double>() : nullptr; a.out8 = want_rgba8 ? T.d_rgba8.as<uint8_t>() : nullptr;
         a.counters = T.d_ctr.as<unsigned long long>();
+        a.motion = moving ? T.d_motion.as<double>() : nullptr; a.n_leaves = (uint32_t)n_leaves;
         ++n_launches;
         return T.timer.run(c, kernel_ms, [&] { ftk::launch_temporal(c->stream, a); });
     });
@@ -374,6 +410,12 @@ static int32_t temporal_single(ft_context* c, const RenderRequest& q, int32_t sa
         }
         FT_HIP(c, hipStreamSynchronize(c->stream));
         c->zero_signature[0] = 0;                                   // (as a progressive pass: the blocks the last ft_render left as Colour.Zero hold means now)
+    }
+    if (T.calls == 0 || moving) {                                   // the pose the set just written belongs to
+        T.h_m2w = c->flat.m2w;
+        T.h_w2m.resize(12 * n_leaves);
+        for (size_t l = 0; l < n_leaves; ++l) std::memcpy(&T.h_w2m[12 * l], c->flat.leaves[l].w2m, 12 * sizeof(double));
+        T.pose = c->pose_serial;
     }
     T.prev ^= 1; T.cam = cam; T.calls += 1;
     T.with_history = (int64_t)ctr[0]; T.at_max = (int64_t)ctr[1];
@@ -511,6 +553,10 @@ int32_t ft_temporal_filter(ft_context* c, const ft_camera* cam, int32_t spp, con
     if ((rc = need_one_device(c, "ft_temporal_filter")) != FT_OK) return rc;
     if (!c->temporal.open) { c->err = "no temporal accumulation (ft_temporal_begin; a caller's ft_scene_commit or ft_scene_clear ends it)"; return FT_ERR_STATE; }
     if (c->temporal.calls == 0) { c->err = "ft_temporal_filter: no ft_temporal_accumulate since ft_temporal_begin"; return FT_ERR_STATE; }
+    if (P.demodulate && c->temporal.pose != c->pose_serial) {
+        c->err = "ft_temporal_filter: demodulate after ft_scene_commit_moved needs an ft_temporal_accumulate first (the guide pass would show another pose than the set)";
+        return FT_ERR_STATE;
+    }
     const RenderRequest q{cam, c->temporal.res_h, c->temporal.res_v, spp, jitter_xy, 0, seed, nullptr, 0, 0};   // (read with demodulate only)
     return with_growing_hit_lists(c, [&] { return temporal_filter_single(c, q, sample, P, rgba8 != 0, out, out_variance, stats); });
 }

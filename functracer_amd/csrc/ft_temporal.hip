@@ -7,6 +7,11 @@
 // interleaved colours), and its 4 x 64 taps fall into a region of about 9x9 pixels of the previous set, 8-byte planes again: the four
 // taps of a lane and those of its neighbours are the same cache lines, served by the L2; the kernel stages nothing.  A tap is tested
 // in the order of what it costs: leaf and N (12 bytes), n (24), p (24), and only one that takes part reads M and Q (48).
+//
+// k_temporal<true> runs when the scene's pose differs from the one the history was written in (ft_scene_commit_moved): a hit
+// lane whose leaf moved takes its point and normal back to that pose through the leaf's motion record (kTemporalMotionDoubles) before
+// the projection and the tap tests; every other lane, and k_temporal<false>, runs the statements below on p and n themselves.  The
+// lanes of a wavefront mostly share a leaf, so the record's 176 bytes are one or two cache lines read by every lane at the same address.
 #include <hip/hip_runtime.h>
 
 #include "ft_device.h"
@@ -23,7 +28,7 @@ __device__ __forceinline__ uint32_t to_byte(double x) {
     return (x != x) ? 0u : (uint32_t)x;
 }
 
-__global__ __launch_bounds__(kBlock) void k_temporal(TemporalArgs a) {
+template <bool MOVING> __global__ __launch_bounds__(kBlock) void k_temporal(TemporalArgs a) {
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= a.n) return;
     const size_t id = a.pixel_ids[a.first + i];                     // y * res_h + x
@@ -36,9 +41,24 @@ __global__ __launch_bounds__(kBlock) void k_temporal(TemporalArgs a) {
         p0 = a.p_plane[i]; p1 = a.p_plane[S + i]; p2 = a.p_plane[2 * S + i];
         n0 = a.n_plane[i]; n1 = a.n_plane[S + i]; n2 = a.n_plane[2 * S + i];
     }
+    // the point and the normal the history is asked about: p and n, or where they were in the pose the history was written in
+    double r0 = p0, r1 = p1, r2 = p2, u0 = n0, u1 = n1, u2 = n2;
+    if (MOVING && hit && a.has_prev && (uint32_t)leaf < a.n_leaves) {
+        const double* rec = a.motion + (size_t)leaf * kTemporalMotionDoubles;
+        if (rec[21] != 0.0) {
+            r0 = rec[0] * p0 + rec[1] * p1 + rec[2] * p2 + rec[3];      // D (p, 1), rows left to right
+            r1 = rec[4] * p0 + rec[5] * p1 + rec[6] * p2 + rec[7];
+            r2 = rec[8] * p0 + rec[9] * p1 + rec[10] * p2 + rec[11];
+            const double t0 = rec[12] * n0 + rec[15] * n1 + rec[18] * n2;   // A^T n
+            const double t1 = rec[13] * n0 + rec[16] * n1 + rec[19] * n2;
+            const double t2 = rec[14] * n0 + rec[17] * n1 + rec[20] * n2;
+            const double s = 1.0 / sqrt(t0 * t0 + t1 * t1 + t2 * t2);       // (a non-finite result fails every tap's normal test)
+            u0 = t0 * s; u1 = t1 * s; u2 = t2 * s;
+        }
+    }
     double W = 0.0, m0 = 0.0, m1 = 0.0, m2 = 0.0, q0 = 0.0, q1 = 0.0, q2 = 0.0, len = 0.0;
     if (hit && a.has_prev) {
-        const double v0 = p0 - a.o[0], v1 = p1 - a.o[1], v2 = p2 - a.o[2];
+        const double v0 = r0 - a.o[0], v1 = r1 - a.o[1], v2 = r2 - a.o[2];
         const double zc = v0 * a.k[0] + v1 * a.k[1] + v2 * a.k[2];
         if (zc > 0.0) {                                             // the inverse of rayThroughPixel (Image.fs:83-89) at jitter 0
             const double fx = ((v0 * a.i[0] + v1 * a.i[1] + v2 * a.i[2]) / zc - a.tlx) / a.pw;
@@ -61,8 +81,8 @@ __global__ __launch_bounds__(kBlock) void k_temporal(TemporalArgs a) {
                         const size_t q = (size_t)qy * (size_t)a.res_h + (size_t)qx;
                         const double lq = a.prev.len[q];
                         if (!(lq >= 1.0) || a.prev.leaf[q] != leaf) continue;
-                        if (!(n0 * a.prev.n[0][q] + n1 * a.prev.n[1][q] + n2 * a.prev.n[2][q] >= a.min_normal_dot)) continue;
-                        const double e0 = p0 - a.prev.p[0][q], e1 = p1 - a.prev.p[1][q], e2 = p2 - a.prev.p[2][q];
+                        if (!(u0 * a.prev.n[0][q] + u1 * a.prev.n[1][q] + u2 * a.prev.n[2][q] >= a.min_normal_dot)) continue;
+                        const double e0 = r0 - a.prev.p[0][q], e1 = r1 - a.prev.p[1][q], e2 = r2 - a.prev.p[2][q];
                         if (!(e0 * e0 + e1 * e1 + e2 * e2 <= tol2)) continue;
                         const double hm0 = a.prev.m[0][q], hm1 = a.prev.m[1][q], hm2 = a.prev.m[2][q];
                         const double hq0 = a.prev.q[0][q], hq1 = a.prev.q[1][q], hq2 = a.prev.q[2][q];
@@ -107,7 +127,8 @@ __global__ __launch_bounds__(kBlock) void k_temporal(TemporalArgs a) {
 
 void launch_temporal(hipStream_t stream, const TemporalArgs& a) {
     if (a.n == 0) return;
-    hipLaunchKernelGGL(k_temporal, dim3((a.n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, a);
+    if (a.motion) hipLaunchKernelGGL(k_temporal<true>, dim3((a.n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, a);
+    else hipLaunchKernelGGL(k_temporal<false>, dim3((a.n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, a);
 }
 
 } // namespace ftk

@@ -167,6 +167,9 @@ ft_node ft_sg_triangle(ft_context* ctx, const double v[9]);                   /*
 /* BspMesh.bspMesh false depth triangles (BspMesh.fs:88-97); tris = n x 9 doubles (a,b,c). */
 ft_node ft_sg_bsp_mesh(ft_context* ctx, int32_t depth, const double* tris, int64_t n_tris); /* Scene.fs:9 */
 ft_node ft_sg_transform(ft_context* ctx, const ft_transform* ts, int32_t n, ft_node child); /* Scene.fs:42 */
+/* Replaces the transform list of an existing ft_sg_transform node (the child stays; n may differ from the old count): see
+ * "moving rigid objects" below. */
+int32_t ft_sg_set_transform(ft_context* ctx, ft_node node, const ft_transform* ts, int32_t n);
 ft_node ft_sg_material(ft_context* ctx, const ft_material* m, ft_node child);  /* Scene.fs:43     */
 ft_node ft_sg_hue_shift(ft_context* ctx, double angle, ft_node child);         /* Scene.fs:45     */
 ft_node ft_sg_ignore_light(ft_context* ctx, ft_node child);                    /* Scene.fs:46     */
@@ -359,7 +362,8 @@ int32_t ft_denoise(ft_context* ctx, const ft_camera* cam, int32_t res_h, int32_t
 /* ---- reprojected frame accumulation for a moving camera ---------------------------------------- */
 /* ft_temporal_* accumulates the FP64 frames a host renders along a camera path: each pixel's surface point is projected into the
  * previous call's image, what was accumulated there is fetched, checked for being the same surface and blended with the new frame.
- * The scene is static (leaf ids and points are compared in world space).  State lives in the context, on a single device: two history
+ * The scene is static (leaf ids and points are compared in world space) unless it is moved with ft_scene_commit_moved ("moving rigid
+ * objects" below).  State lives in the context, on a single device: two history
  * sets in frame layout (row 0 = top), "previous" and "current", flipped after every call; per frame pixel a set holds the mean M (3
  * doubles), the mean of squares Q (3), the history length N (1), p and n (3 each) and leaf (int32): 108 bytes; and the previous call's
  * image plane cam' (ImagePlane.create of its ft_camera, Image.fs:48-81: o' i' j' k', the top-left pixel centre tlx' tly', the pixel
@@ -463,6 +467,49 @@ typedef struct ft_temporal_filter_params { int32_t iterations, demodulate, min_h
     double sigma_colour, sigma_normal, sigma_position, albedo_floor, variance_floor; } ft_temporal_filter_params;   /* 56 bytes */
 int32_t ft_temporal_filter(ft_context* ctx, const ft_camera* cam, int32_t spp, const double* jitter_xy, int32_t sample, uint64_t seed,
                            const ft_temporal_filter_params* params, int32_t rgba8, void* out, double* out_variance, ft_stats* stats);
+
+/* ---- moving rigid objects under a temporal accumulation --------------------------------------- */
+/* ft_sg_set_transform + ft_scene_commit_moved move objects of a committed scene without ending ft_temporal_*: the history then follows
+ * each moved leaf instead of being looked up where the leaf's surface is now.
+ * ft_sg_set_transform(node, ts, n) replaces the transform list of an ft_sg_transform node.  FT_ERR_INVALID, with nothing changed, for a
+ * null context, an invalid handle, a node that is not a transform node, null ts, n < 1 or a kind that is no ft_transform_kind.  Like
+ * every builder call it leaves the scene uncommitted; unlike the others it is not a structural change.
+ * ft_scene_commit_moved commits the graph exactly as ft_scene_commit does (the flatten, the BVH builds, the uploads, every device of the
+ * context, ft_get_commit_times), so a later ft_render is bit-identical to one from a fresh context built with the new transforms.  It
+ * differs in three ways:
+ *  - It returns FT_ERR_STATE, and does nothing, unless the context holds a successful commit and no structural change was made since:
+ *    structural are the ft_sg_* calls that add a node, ft_scene_set_objects, ft_scene_add_* and ft_scene_clear; ft_sg_set_transform and
+ *    ft_set_option are not.  The graph therefore flattens to the same leaves in the same order (one m2w / w2m pair per leaf, composed
+ *    over the transform nodes above it).
+ *  - It ends a progressive accumulation (its sums belong to the old scene) but NOT the temporal accumulation.
+ *  - It advances the context's pose counter.  (The re-commit by which a blocking call grows the CSG hit lists does not.)
+ * A successful ft_temporal_accumulate remembers the pose its set was written in: the pose counter and, per leaf l, H_l = m2w(l) and
+ * Wh_l = w2m(l) (3x4, rows).  An accumulate that finds the pose counter unchanged runs as defined above.  Otherwise, with m2w_cur and
+ * w2m_cur the matrices of the live commit, per leaf:
+ *   moved_l = any of the 12 doubles of m2w_cur(l) differs from H_l (bitwise);
+ *   D_l = H_l o w2m_cur(l), the 3x4 affine product: D[i][j] = H[i][0] W[0][j] + H[i][1] W[1][j] + H[i][2] W[2][j], + H[i][3] for j = 3,
+ *         summed left to right, unfused.  It maps a current world point of the leaf to where that point was;
+ *   A_l = m2w_cur(l)_lin . Wh_l_lin, the 3x3 product summed the same way: the inverse of D_l's linear part.
+ * and for a hit pixel x with leaf l = leaf(x) and moved_l:
+ *   pr = D_l (p(x), 1): pr_i = D[i][0] p_0 + D[i][1] p_1 + D[i][2] p_2 + D[i][3], left to right;
+ *   nr = A_l^T n(x): t_j = A[0][j] n_0 + A[1][j] n_1 + A[2][j] n_2, nr = t * (1 / sqrt(t.t)).
+ * Clauses 1 to 3 of ft_temporal_accumulate then use pr and nr wherever they use p(x) and n(x): v = pr - o' (and with it zc, fx, fy and
+ * the tolerance), nr.n'(q) >= min_normal_dot, |pr - p'(q)|^2 <= tol^2.  A non-finite nr fails every tap by those comparisons.  Clause 6
+ * still stores the CURRENT p(x), n(x), leaf(x), and the pose of the live commit becomes the set's.  Miss pixels and pixels whose leaf has
+ * moved_l = 0 take the path defined above with p and n untouched: static surfaces beside a moving object get the bits they would get
+ * without it.  Several ft_scene_commit_moved calls between two accumulates compose by construction: H is the pose at the last
+ * accumulate, not at the last commit.
+ * What follows a leaf is its history, not its shading: light that changes on a moving surface (it turns towards a light, a shadow
+ * sweeps over it) is averaged as noise is, max_history bounding how long it lingers.  Lights do not move; meshes do not deform.
+ * ft_temporal_filter with `demodulate` returns FT_ERR_STATE between an ft_scene_commit_moved and the next ft_temporal_accumulate (its
+ * guide pass would show another pose than the set); without `demodulate` it runs as before.
+ * A host that never calls these functions gets bit-identical results from everything else.
+ * Device memory: 192 bytes per leaf while a moved pose is being accumulated. */
+int32_t ft_scene_commit_moved(ft_context* ctx);
+/* The per-leaf matrices of the scene the context holds (the last successful commit's; they stay readable while the graph is being
+ * edited), for tests: *n_leaves, and into each non-null array 12 doubles per leaf, the rows of the 3x4 model->world (m2w) and
+ * world->model (w2m) matrix.  Host-only contexts too.  FT_ERR_STATE without a successful commit. */
+int32_t ft_debug_leaf_matrices(ft_context* ctx, int64_t* n_leaves, double* m2w, double* w2m);
 
 /* Closest hit of single rays through the device path (Scene.intersectScene, Scene.fs:118, after
  * Shading.slightOffset is NOT applied): for tests.  Outputs per ray: t, p[3], n[3], material index

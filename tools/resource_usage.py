@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Registers, scratch and occupancy of every kernel of ft_kernels.hip as the compiler reports them (no GPU needed):
+"""Registers, scratch and occupancy of every kernel of ft_kernels.hip and ft_temporal.hip as the compiler reports them (no GPU needed):
 python tools/resource_usage.py > profiles/<tag>_resource_usage.json"""
 import json
 import os
