@@ -54,6 +54,7 @@ def hip_lib():
         lib.ft_get_commit_times.argtypes = [C.c_void_p, _capi.c_double_p]
         lib.ft_debug_scene_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
         lib.ft_debug_devices.argtypes = [C.c_void_p, _capi.c_int32_p, C.c_int32]
+        lib.ft_debug_mesh_trees.restype, lib.ft_debug_mesh_trees.argtypes = C.c_int32, _capi.MESH_TREES_SIGNATURE
         lib.ft_debug_slice.argtypes = [_capi.c_double_p] * 4 + [_capi.c_int32_p, _capi.c_double_p, _capi.c_int32_p]
         lib.ft_render_enqueue.argtypes = [C.c_void_p, C.POINTER(_capi.ft_camera), C.c_int32, C.c_int32, C.c_int32, _capi.c_double_p, C.c_int32, C.c_uint64, C.POINTER(_capi.ft_rect), C.c_int32]
         lib.ft_render_wait.argtypes = [C.c_void_p, C.POINTER(_capi.ft_stats)]
@@ -575,6 +576,25 @@ class Context(SceneBuilder):
         ms = np.zeros(4)
         self._check(self._lib.ft_get_commit_times(self._ctx, _capi.dptr(ms)))
         return {"flatten_ms": float(ms[0]), "device_bvh_ms": float(ms[1]), "upload_ms": float(ms[2]), "device_bvh_height": int(ms[3])}
+
+    def mesh_trees(self):
+        """ft_debug_mesh_trees: the mesh trees of the committed scene as the kernels walk them, read back from device memory (from the
+        flattened scene in a host-only context).  A dict of `nodes` (records of _capi.BSP_NODE_DTYPE), `bsp_leaves` [n, 2] (first_tri,
+        n_tris), `tris` [n, 9], `tri_orig`, `tri_src`, `wide` [n, 28] float64, `coarse_boxes` [n, 6] float32, `meshes` [n, 6] int32 (root,
+        bvh_root, n_source_tris, wide root, first coarse box, coarse box count), `jobs` (a list of dicts, _capi.BVH_JOB_FIELDS),
+        `stack_capacity` and `from_device`."""
+        sizes = (C.c_int64 * 12)()
+        self._check(self._lib.ft_debug_mesh_trees(self._ctx, sizes, *([None] * 9)))
+        n = list(sizes)
+        out = {"nodes": np.zeros(n[0], dtype=_capi.BSP_NODE_DTYPE), "bsp_leaves": np.zeros((n[1], 2), dtype=np.uint32), "tris": np.zeros((n[2], 9)),
+               "tri_orig": np.zeros(n[3], dtype=np.uint32), "tri_src": np.zeros(n[4], dtype=np.uint32), "wide": np.zeros((n[5], 28)),
+               "coarse_boxes": np.zeros((n[6], 6), dtype=np.float32), "meshes": np.zeros((n[7], 6), dtype=np.int32)}
+        jobs = np.zeros((n[8], 9), dtype=np.uint32)
+        order = ["nodes", "bsp_leaves", "tris", "tri_orig", "tri_src", "wide", "coarse_boxes", "meshes"]
+        self._check(self._lib.ft_debug_mesh_trees(self._ctx, sizes, *[out[k].ctypes.data for k in order], jobs.ctypes.data))
+        out["jobs"] = [dict(zip(_capi.BVH_JOB_FIELDS, (int(v) for v in row))) for row in jobs]
+        out["stack_capacity"], out["from_device"] = int(sizes[9]), bool(sizes[10])
+        return out
 
     def scene_info(self):
         out = (C.c_int64 * 12)()

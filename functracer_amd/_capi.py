@@ -112,6 +112,12 @@ MOTION_SIGNATURES = [
 ]
 
 
+# ft_debug_mesh_trees (include/functracer_hip.h): the mesh trees as they lie in HBM, for the tests' structure checker.
+MESH_TREES_SIGNATURE = [C.c_void_p, C.POINTER(C.c_int64)] + [C.c_void_p] * 9
+BSP_NODE_DTYPE = np.dtype([("bmin", np.float64, 3), ("bmax", np.float64, 3), ("left", np.int32), ("right", np.int32), ("axis", np.uint32), ("pad", np.uint32)])
+BVH_JOB_FIELDS = ["mesh", "first_global", "n", "node_base", "leaf_base", "tri_base", "wide_base", "coarse_first", "coarse_count"]
+
+
 class ft_temporal_filter_params(C.Structure):
     """ft_temporal_filter's parameters (include/functracer_hip.h): a-trous iterations 0 .. 6, demodulation by the material colour, the
     history length below which the spatial variance estimate steps in, whether the result replaces the frame in HBM, the three

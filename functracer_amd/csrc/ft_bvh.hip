@@ -296,12 +296,12 @@ __global__ __launch_bounds__(256) void k_bvh_single_leaves(const double* __restr
 // hands its own box to both halves.  The tree only decides which boxes a ray looks into: no pixel depends on it (ft_flat.h).
 constexpr int kBins = 16;
 constexpr uint32_t kBinWords = 7;                                    // ordered lo xyz, hi xyz, count
-struct SahState { uint32_t n_internal, n_leaves, level_begin, level_end, level, pad[3]; };
+struct SahState { uint32_t n_internal, n_leaves, level_begin, level_end, level, leaf_base, pad[2]; };   // leaf_base: build leaves made before this level
 
 __global__ void k_sah_begin(SahState* s, uint32_t n, uint32_t* range_first, uint32_t* range_last, double* node_boxes, const BuildState* st, int32_t* node_of, uint32_t* seg_first) {
     const uint32_t p = blockIdx.x * 256u + threadIdx.x;
     if (p == 0u) {
-        s->n_internal = 1u; s->n_leaves = 0u; s->level_begin = 0u; s->level_end = 1u; s->level = 0u;
+        s->n_internal = 1u; s->n_leaves = 0u; s->level_begin = 0u; s->level_end = 1u; s->level = 0u; s->leaf_base = 0u;
         range_first[0] = 0u; range_last[0] = n - 1u;
         for (int a = 0; a < 3; ++a) { node_boxes[a] = unordered(st->lo[a]); node_boxes[3 + a] = unordered(st->hi[a]); }
     }
@@ -338,7 +338,9 @@ __global__ __launch_bounds__(256) void k_sah_bin(const SahState* s, uint32_t n, 
 }
 // One WAVE per open node (a thread per node spent the upper rounds of the tree reading 336 words one after the other): lane l < 48
 // holds bin l % 16 of axis l / 16, prefix and suffix unions run over the 16 lanes of an axis, lane b prices plane b of its axis, the
-// cheapest of the 45 wins; lane 0 makes the two children (an internal node or a build leaf each) and their boxes.
+// cheapest of the 45 wins; lane 0 records the plane, the boxes of the two children (child_boxes: 12 doubles per open node) and how many
+// of them are internal nodes (kids).  The children are numbered afterwards, in the order of the level's open nodes (k_sah_assign): an
+// atomic counter here would hand out the numbers in the order the waves happen to run, another tree in HBM from commit to commit.
 struct BinBox { double lo[3], hi[3]; uint32_t cnt; };
 __device__ __forceinline__ BinBox shfl_box(const BinBox& b, int src) {
     BinBox r;
@@ -348,10 +350,11 @@ __device__ __forceinline__ BinBox shfl_box(const BinBox& b, int src) {
 }
 __device__ __forceinline__ void unite(BinBox& a, const BinBox& b) { for (int k = 0; k < 3; ++k) { a.lo[k] = fmin(a.lo[k], b.lo[k]); a.hi[k] = fmax(a.hi[k], b.hi[k]); } a.cnt += b.cnt; }
 __device__ __forceinline__ double half_area(const BinBox& b) { const double dx = b.hi[0] - b.lo[0], dy = b.hi[1] - b.lo[1], dz = b.hi[2] - b.lo[2]; return dx * dy + dy * dz + dz * dx; }
-__global__ __launch_bounds__(256) void k_sah_split(SahState* s, const unsigned long long* __restrict__ bins, uint32_t* range_first, uint32_t* range_last, int32_t* left, int32_t* right,
-                                                   uint32_t* split_bit, uint32_t* plane, uint32_t* n_left, double* node_boxes, uint32_t* leaf_first, uint32_t* leaf_count) {
-    const uint32_t o = s->level_begin + blockIdx.x * 4u + threadIdx.x / 64u, lane = threadIdx.x & 63u;
-    if (o >= s->level_end) return;                                  // (whole waves leave together)
+__global__ __launch_bounds__(256) void k_sah_split(const SahState* s, const unsigned long long* __restrict__ bins, const uint32_t* __restrict__ range_first, const uint32_t* __restrict__ range_last,
+                                                   uint32_t* split_bit, uint32_t* plane, uint32_t* n_left, const double* __restrict__ node_boxes, uint32_t* __restrict__ kids,
+                                                   double* __restrict__ child_boxes) {
+    const uint32_t rel = blockIdx.x * 4u + threadIdx.x / 64u, o = s->level_begin + rel, lane = threadIdx.x & 63u;
+    if (o >= s->level_end) { if (lane == 0u) kids[rel] = 0u; return; }   // (whole waves leave together; the scan runs over the launch's slots)
     const double inf = __builtin_inf();
     const uint32_t bin = lane % kBins;
     BinBox mine{{inf, inf, inf}, {-inf, -inf, -inf}, 0u};
@@ -383,22 +386,37 @@ __global__ __launch_bounds__(256) void k_sah_split(SahState* s, const unsigned l
     }
     if (lane != 0u) return;
     split_bit[o] = best_axis == 3u ? 0u : best_axis; plane[o] = best_axis << 8 | best_plane; n_left[o] = best_left;
+    kids[rel] = (best_left > kLeafTris ? 1u : 0u) + (size - best_left > kLeafTris ? 1u : 0u);
+    double* cb = child_boxes + 12ull * rel;
+    for (int k = 0; k < 3; ++k) { cb[k] = lb.lo[k]; cb[3 + k] = lb.hi[k]; cb[6 + k] = rb.lo[k]; cb[9 + k] = rb.hi[k]; }
+}
+// The children of the level's open nodes, numbered in the order of the nodes (left before right): `before` is the exclusive scan of kids,
+// so open node t's internal children start at level_end + before[t] and its build leaves at leaf_base + 2 t - before[t].
+__global__ __launch_bounds__(256) void k_sah_assign(SahState* s, uint32_t slots, const uint32_t* __restrict__ before, const double* __restrict__ child_boxes,
+                                                    const uint32_t* __restrict__ n_left, uint32_t* range_first, uint32_t* range_last, int32_t* left, int32_t* right, double* node_boxes,
+                                                    uint32_t* leaf_first, uint32_t* leaf_count) {
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= slots) return;
+    const uint32_t o = s->level_begin + t, level_end = s->level_end;
+    if (o >= level_end) return;
+    const uint32_t first = range_first[o], size = range_last[o] - first + 1u, best_left = n_left[o];
     const uint32_t sizes[2] = {best_left, size - best_left}, firsts[2] = {first, first + best_left};
+    uint32_t next_node = level_end + before[t], next_leaf = s->leaf_base + 2u * t - before[t];
     int32_t refs[2];
     for (int c = 0; c < 2; ++c) {
         if (sizes[c] > kLeafTris) {
-            const uint32_t id = atomicAdd(&s->n_internal, 1u);
+            const uint32_t id = next_node++;
             range_first[id] = firsts[c]; range_last[id] = firsts[c] + sizes[c] - 1u;
-            const BinBox& bx = c == 0 ? lb : rb;
-            for (int k = 0; k < 3; ++k) { node_boxes[6ull * id + k] = bx.lo[k]; node_boxes[6ull * id + 3 + k] = bx.hi[k]; }
+            for (int k = 0; k < 6; ++k) node_boxes[6ull * id + k] = child_boxes[12ull * t + 6 * c + k];
             refs[c] = (int32_t)id;
         } else {
-            const uint32_t j = atomicAdd(&s->n_leaves, 1u);
+            const uint32_t j = next_leaf++;
             leaf_first[j] = firsts[c]; leaf_count[j] = sizes[c];
             refs[c] = ~(int32_t)j;
         }
     }
     left[o] = refs[0]; right[o] = refs[1];
+    if (o == level_end - 1u) { s->n_internal = next_node; s->n_leaves = next_leaf; }   // (nobody reads these two before k_sah_next_level)
 }
 // Sort key of every position: (start of its segment, side of its node's plane).  Positions outside the open nodes keep their place.
 __global__ __launch_bounds__(256) void k_sah_keys(const SahState* s, uint32_t n, const uint32_t* __restrict__ vals, const int32_t* __restrict__ node_of, const uint32_t* __restrict__ seg_first,
@@ -444,7 +462,7 @@ __global__ __launch_bounds__(256) void k_sah_descend(const SahState* s, uint32_t
     node_of[p] = child >= 0 ? child : -1;
     seg_first[p] = range_first[o] + (second ? n_left[o] : 0u);
 }
-__global__ void k_sah_next_level(SahState* s) { s->level_begin = s->level_end; s->level_end = s->n_internal; s->level += 1u; }
+__global__ void k_sah_next_level(SahState* s) { s->level_begin = s->level_end; s->level_end = s->n_internal; s->leaf_base = s->n_leaves; s->level += 1u; }
 __global__ __launch_bounds__(256) void k_sah_leaf_boxes(const SahState* s, const uint32_t* __restrict__ vals, const double* __restrict__ tri_boxes, const uint32_t* __restrict__ leaf_first,
                                                          const uint32_t* __restrict__ leaf_count, double* __restrict__ leaf_boxes, uint32_t* __restrict__ counts, BuildState* st) {
     const uint32_t j = blockIdx.x * 256u + threadIdx.x;
@@ -479,7 +497,8 @@ hipError_t build_lbvh(hipStream_t stream, const LbvhTarget& t, uint32_t* height,
     const size_t o_state = take(sizeof(BuildState)), o_tb = take(n8 * 48), o_nb = take(n8 * 48), o_k0 = take(n8 * 4), o_k1 = take(n8 * 4), o_v0 = take(n8 * 4), o_v1 = take(n8 * 4),
                  o_l = take(n8 * 4), o_r = take(n8 * 4), o_f = take(n8 * 4), o_la = take(n8 * 4), o_pn = take(n8 * 4), o_pl = take(n8 * 4), o_sb = take(n8 * 4), o_ar = take(n8 * 4), o_h = take(n8 * 4),
                  o_lf = take(n8 * 4), o_lc = take(n8 * 4), o_lb = take(n8 * 48), o_cnt = take(16),
-                 o_sah = take(sizeof(SahState)), o_bins = take(sah ? open_max * 3 * kBins * kBinWords * 8 : 8);
+                 o_sah = take(sizeof(SahState)), o_bins = take(sah ? open_max * 3 * kBins * kBinWords * 8 : 8),
+                 o_kids = take(sah ? (open_max + 8) * 4 : 8), o_before = take(sah ? (open_max + 8) * 4 : 8), o_cb = take(sah ? (open_max + 8) * 96 : 8);
     {
         BVH_HIP(hipMalloc(reinterpret_cast<void**>(&scratch), off));
         BuildState* st = reinterpret_cast<BuildState*>(scratch + o_state);
@@ -494,6 +513,8 @@ hipError_t build_lbvh(hipStream_t stream, const LbvhTarget& t, uint32_t* height,
         uint32_t* counts = reinterpret_cast<uint32_t*>(scratch + o_cnt);
         SahState* ss = reinterpret_cast<SahState*>(scratch + o_sah);
         unsigned long long* bins = reinterpret_cast<unsigned long long*>(scratch + o_bins);
+        uint32_t* kids = reinterpret_cast<uint32_t*>(scratch + o_kids); uint32_t* before = reinterpret_cast<uint32_t*>(scratch + o_before);
+        double* child_boxes = reinterpret_cast<double*>(scratch + o_cb);
         const dim3 grid((n + 255u) / 256u), block(256);
         hipLaunchKernelGGL(k_bvh_init, dim3(1), dim3(1), 0, stream, st);
         hipLaunchKernelGGL(k_bvh_prepare, grid, block, 0, stream, t.tris, t.first_global, n, tb, st);
@@ -534,7 +555,10 @@ hipError_t build_lbvh(hipStream_t stream, const LbvhTarget& t, uint32_t* height,
                 const uint32_t words_blocks = (uint32_t)std::min<unsigned long long>(((unsigned long long)open * 3u * kBins * kBinWords + 255u) / 256u, 4096ull);
                 hipLaunchKernelGGL(k_sah_clear_bins, dim3(words_blocks), block, 0, stream, ss, bins);
                 hipLaunchKernelGGL(k_sah_bin, grid, block, 0, stream, ss, n, vin, node_of, tb, nb, bins);
-                hipLaunchKernelGGL(k_sah_split, dim3((open + 3u) / 4u), block, 0, stream, ss, bins, rf, rl, left, right, sb, plane, n_left, nb, lf, lc);
+                const uint32_t slots = (open + 3u) / 4u * 4u;       // one wave of k_sah_split each; those past the level's end count no children
+                hipLaunchKernelGGL(k_sah_split, dim3(slots / 4u), block, 0, stream, ss, bins, rf, rl, sb, plane, n_left, nb, kids, child_boxes);
+                BVH_HIP(rocprim::exclusive_scan(sort_tmp, sort_bytes, kids, before, 0u, slots, rocprim::plus<uint32_t>(), stream));
+                hipLaunchKernelGGL(k_sah_assign, dim3((slots + 255u) / 256u), block, 0, stream, ss, slots, before, child_boxes, n_left, rf, rl, left, right, nb, lf, lc);
                 hipLaunchKernelGGL(k_sah_keys, grid, block, 0, stream, ss, n, vin, node_of, seg_first, tb, nb, plane, n_left, rf, kin);
                 BVH_HIP(rocprim::exclusive_scan(sort_tmp, sort_bytes, kin, kout, 0u, n, rocprim::plus<uint32_t>(), stream));
                 hipLaunchKernelGGL(k_sah_scatter, grid, block, 0, stream, ss, n, vin, vout, node_of, seg_first, kin, kout, n_left, plane);

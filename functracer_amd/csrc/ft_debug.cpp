@@ -168,6 +168,47 @@ int32_t ft_debug_light_space(ft_context* c, int64_t sizes[4], double* pairs, uin
     return FT_OK;
 }
 
+// The mesh trees as they lie in HBM after the last commit (device contexts: copied back from device memory, so what ft_bvh.hip built
+// into the ranges the flattener reserved is seen; host-only contexts: the flattened arrays), and the host-side tables needed to walk them.
+int32_t ft_debug_mesh_trees(ft_context* c, int64_t sizes[12], void* nodes, uint32_t* bsp_leaves, double* tris, uint32_t* tri_orig, uint32_t* tri_src, double* wide,
+                            float* coarse_boxes, int32_t* meshes, uint32_t* jobs) {
+    if (!c || !sizes) return FT_ERR_INVALID;
+    if (!c->committed) { c->err = "scene not committed"; return FT_ERR_STATE; }
+    const fth::FlatScene& f = c->flat;
+    sizes[0] = (int64_t)f.nodes.size(); sizes[1] = (int64_t)f.bsp_leaves.size(); sizes[2] = (int64_t)(f.tris.size() / 9); sizes[3] = (int64_t)f.tri_orig.size();
+    sizes[4] = (int64_t)f.tri_src.size(); sizes[5] = (int64_t)(f.wide.size() / ftd::kWideNodeDoubles); sizes[6] = (int64_t)(f.coarse_boxes.size() / 6);
+    sizes[7] = (int64_t)f.meshes.size(); sizes[8] = (int64_t)f.bvh_jobs.size(); sizes[9] = c->host_only ? f.stack_capacity : c->dev_scene.stack_cap;
+    sizes[10] = c->host_only ? 0 : 1; sizes[11] = 0;
+    if (!c->host_only) {
+        FT_HIP(c, hipSetDevice(c->device));
+        const int32_t rc = drain_frame_streams(c);
+        if (rc != FT_OK) return rc;
+    }
+    auto get = [&](void* dst, SceneArray k, const void* host, size_t bytes) -> int32_t {
+        if (!dst || bytes == 0) return FT_OK;
+        if (c->host_only) { std::memcpy(dst, host, bytes); return FT_OK; }
+        if (c->d_scene[k].bytes < bytes) { c->err = "ft_debug_mesh_trees: a scene array in device memory is smaller than the flattened one"; return FT_ERR_STATE; }
+        FT_HIP(c, hipMemcpy(dst, c->d_scene[k].p, bytes, hipMemcpyDeviceToHost));
+        return FT_OK;
+    };
+    int32_t rc;
+    if ((rc = get(nodes, kNodes, f.nodes.data(), f.nodes.size() * sizeof(ftd::BspNode))) != FT_OK) return rc;
+    if ((rc = get(bsp_leaves, kBspLeaves, f.bsp_leaves.data(), f.bsp_leaves.size() * sizeof(ftd::BspLeaf))) != FT_OK) return rc;
+    if ((rc = get(tris, kTris, f.tris.data(), f.tris.size() * sizeof(double))) != FT_OK) return rc;
+    if ((rc = get(tri_orig, kTriOrig, f.tri_orig.data(), f.tri_orig.size() * sizeof(uint32_t))) != FT_OK) return rc;
+    if ((rc = get(tri_src, kTriSrc, f.tri_src.data(), f.tri_src.size() * sizeof(uint32_t))) != FT_OK) return rc;
+    if ((rc = get(wide, kWide, f.wide.data(), f.wide.size() * sizeof(double))) != FT_OK) return rc;
+    if ((rc = get(coarse_boxes, kCoarse, f.coarse_boxes.data(), f.coarse_boxes.size() * sizeof(float))) != FT_OK) return rc;
+    if (meshes) for (size_t m = 0; m < f.meshes.size(); ++m) {
+        int32_t* r = meshes + 6 * m;
+        r[0] = f.meshes[m].root; r[1] = f.meshes[m].bvh_root; r[2] = (int32_t)f.meshes[m].n_source_tris; r[3] = f.mesh_wide[m];
+        r[4] = (int32_t)f.mesh_coarse[2 * m]; r[5] = (int32_t)f.mesh_coarse[2 * m + 1];
+    }
+    static_assert(sizeof(fth::FlatScene::BvhJob) == 9 * sizeof(uint32_t), "a job goes out as nine words");
+    if (jobs && !f.bvh_jobs.empty()) std::memcpy(jobs, f.bvh_jobs.data(), f.bvh_jobs.size() * sizeof(fth::FlatScene::BvhJob));
+    return FT_OK;
+}
+
 int32_t ft_debug_slice(const double p0[3], const double n[3], const double tri[9], double above[18], int32_t* n_above, double below[18], int32_t* n_below) {
     if (!p0 || !n || !tri || !above || !below || !n_above || !n_below) return FT_ERR_INVALID;
     std::vector<double> a, b; std::string err;

@@ -538,6 +538,15 @@ int32_t ft_debug_slice(const double p0[3], const double n[3], const double tri[9
  * sizes = pair records, nodes, triangle records, leaves; each non-null array receives 16 doubles per record, 24 words per node,
  * 9 doubles per triangle and, per leaf, the index of its first pair record (0xFFFFFFFF = none).  Host-only contexts too. */
 int32_t ft_debug_light_space(ft_context* ctx, int64_t sizes[4], double* pairs, uint32_t* nodes, double* tris, uint32_t* leaf_pairs);
+/* The mesh trees of the committed scene as the kernels walk them (layouts in ft_flat.h), for tests.  A device context copies the arrays
+ * back from device memory, so the trees ft_bvh.hip built after the upload are seen; a host-only context hands out the flattened arrays.
+ * sizes = BspNode records, BspLeaf records, triangle records, tri_orig entries, tri_src entries, 4-wide nodes, coarse boxes, meshes,
+ * device build jobs, the per-lane tree stack capacity, 1 if the arrays came from device memory, 0.  Each non-null array receives
+ * 64 bytes per node, 2 words per leaf, 9 doubles per triangle, a word per tri_orig / tri_src entry, 28 doubles per wide node, 6 floats
+ * per coarse box, 6 words per mesh (root, bvh_root, n_source_tris, root of the 4-wide tree or INT32_MIN, first coarse box, coarse
+ * box count) and 9 words per job (mesh, first_global, n, node_base, leaf_base, tri_base, wide_base, coarse_first, coarse_count). */
+int32_t ft_debug_mesh_trees(ft_context* ctx, int64_t sizes[12], void* nodes, uint32_t* bsp_leaves, double* tris, uint32_t* tri_orig, uint32_t* tri_src,
+                            double* wide, float* coarse_boxes, int32_t* meshes, uint32_t* jobs);
 /* HIP-event time per stage over the last ft_render: index 4 primary (bounce 0 fused: generate + closest + shade), 2 the later
  * bounces (one k_bounce per level; one bracket around them all, or with "timing" = 2 one per level), 3 resolve and 0 the rest (the
  * fill, classification) with "timing" = 2; otherwise 0 = everything that is not bracketed and 3 = 0.  Index 1 is unused. */
