@@ -596,6 +596,23 @@ class Context(SceneBuilder):
         out["stack_capacity"], out["from_device"] = int(sizes[9]), bool(sizes[10])
         return out
 
+    def block_lists(self):
+        """ft_debug_block_lists: the per-block triangle candidate lists of the last classified frame (option "primary_block_lists"), read
+        back from device memory.  A dict of `leaf` (the mesh leaf the lists are for; -1: that frame carried none, the arrays are then
+        empty), `heads` (one word per active block: _capi.LIST_NONE = the block walks the tree, else first entry << 7 | count),
+        `pos_block` (the block of the frame's pixel list behind each active block), `entries` (records of _capi.LIST_ENTRY_DTYPE: the
+        triangle's record and list index and its rectangle on the image plane, in the (jx, jy) of the primary rays), `plane` (tlx, tly,
+        pw, ph: pixel (x, y) under jitter offset (ox, oy) looks through jx = tlx + (x + ox) pw, jy = tly - (y - oy) ph) and `capacity`."""
+        sizes = (C.c_int64 * 4)()
+        plane = np.zeros(4)
+        fn = self._lib.ft_debug_block_lists
+        fn.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        self._check(fn(self._ctx, sizes, None, None, None, None))
+        heads, pos_block = np.zeros(sizes[0], dtype=np.uint32), np.zeros(sizes[0], dtype=np.uint32)
+        entries = np.zeros(sizes[1], dtype=_capi.LIST_ENTRY_DTYPE)
+        self._check(fn(self._ctx, sizes, plane.ctypes.data, heads.ctypes.data, pos_block.ctypes.data, entries.ctypes.data))
+        return {"leaf": int(sizes[2]), "heads": heads, "pos_block": pos_block, "entries": entries, "plane": plane, "capacity": int(sizes[3])}
+
     def scene_info(self):
         out = (C.c_int64 * 12)()
         self._check(self._lib.ft_debug_scene_info(self._ctx, out))

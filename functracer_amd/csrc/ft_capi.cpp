@@ -188,6 +188,7 @@ const OptionSpec kOptions[] = {
     {"mains", 1, ft_context::kMains, &Options::mains, nullptr, 0},
     {"bvh_builder", 0, 3, &Options::bvh_builder, nullptr, kCommit},
     {"csg_auto_grow", 0, 1, &Options::csg_auto_grow, nullptr, kFlag},
+    {"primary_block_lists", 0, 1, &Options::primary_block_lists, nullptr, kFlag},
     {"csg_mesh_capacity", 1, 255, nullptr, [](fth::SceneGraph& g, int64_t v) { g.csg_mesh_capacity = (int32_t)v; }, kCommit},
     // directional shadow rays of coherent waves: 0 the BVH; 1 light-space trees; 2 (default) light-space grids, the trees for wide waves.
     // It was a flag before the grids: it still takes any value, and any other than 0 / 1 means 2.

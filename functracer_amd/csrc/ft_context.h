@@ -94,6 +94,7 @@ struct Options {
                                     // triangles but 160 ms for 69.6 K), 1 = the device's linear BVH (ft_bvh.hip: ~1 ms, traces ~9 % slower), 3 = the device's
                                     // binned surface-area tree over the Morton order, 2 = by size: the host's below kDeviceBvhMinTris triangles, 3's from there on
     int64_t csg_auto_grow = 1;      // ft_render: double csg_mesh_capacity and render again when a hit list overflows (read on device 0)
+    int64_t primary_block_lists = 1;   // k_block_lists: the primaries of a classified frame over ONE bare mesh test their block's candidate list; 0: the tree walk everywhere
 };
 
 // One buffer in HBM per array of the flattened scene; DevScene points into them (upload_scene).
@@ -199,6 +200,9 @@ struct ft_context {
         // What k_classify writes and the frame's later kernels read exists once per slot, so that a queued frame's classification can
         // run (on `side`, behind an event) while the frame before it is still tracing: block_pos / pos_block and the frame's counters.
         DeviceBuf d_block_pos, d_pos_block, d_fc;
+        DeviceBuf d_list_heads, d_list_pool;    // k_block_lists: a header per active block, the entries (ftk::BlockLists)
+        int32_t list_leaf = -1;                 // the mesh leaf this slot's frame carries lists for; -1: none
+        ftk::Camera list_cam{};                 // that frame's image plane (ft_debug_block_lists)
         bool fc_clean = false;                  // d_fc is all zero: the slot's previous frame cleared it behind its report (no fill needed)
         Brackets ev;
         bool simple = false;                    // one chunk, k_resolve aside
@@ -210,7 +214,7 @@ struct ft_context {
         uint64_t rays_primary = 0; int64_t n_pix_total = 0; int32_t spp = 0, n_launches = 0, n_chunks = 0, format = 0; bool classify = false;
         std::chrono::steady_clock::time_point wall0;
         void release() {
-            d_block_pos.release(); d_pos_block.release(); d_fc.release();
+            d_block_pos.release(); d_pos_block.release(); d_fc.release(); d_list_heads.release(); d_list_pool.release();
             if (h_report) (void)hipHostFree(h_report);
             h_report = nullptr; d_report = nullptr;
             ev.release();
@@ -218,6 +222,7 @@ struct ft_context {
     };
     FrameSlot slots[kSlots];
     int slot_turn = 0;
+    int last_classified_slot = -1;   // the slot of the last classified frame queued (ft_debug_block_lists)
     // Levels of the reflection tree worth launching: the host cannot know how deep the rays of a frame go without waiting, and a
     // k_bounce launch that finds no rays still costs a few microseconds.  It launches as many levels as the previous frame of the
     // same signature had rays in, plus one; the last one launched follows whatever it still spawns to the end inside the kernel,

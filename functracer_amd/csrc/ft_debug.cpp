@@ -209,6 +209,34 @@ int32_t ft_debug_mesh_trees(ft_context* c, int64_t sizes[12], void* nodes, uint3
     return FT_OK;
 }
 
+// The candidate lists of the last classified frame queued, as k_block_lists left them in its slot (the frame's counters are gone by
+// then: the active block count comes from its report, the entries in use from the headers).
+int32_t ft_debug_block_lists(ft_context* c, int64_t sizes[4], double plane[4], uint32_t* heads, uint32_t* pos_block, uint32_t* entries) {
+    if (!c || !sizes) return FT_ERR_INVALID;
+    if (c->host_only) return FT_ERR_NO_DEVICE;
+    sizes[0] = sizes[1] = sizes[3] = 0; sizes[2] = -1;
+    if (c->last_classified_slot < 0) return FT_OK;
+    FT_HIP(c, hipSetDevice(c->device));
+    int32_t rc = retire_pending(c, nullptr);
+    if (rc != FT_OK) return rc;
+    if ((rc = drain_frame_streams(c)) != FT_OK) return rc;
+    const ft_context::FrameSlot& F = c->slots[c->last_classified_slot];
+    if (F.list_leaf < 0 || !F.h_report) return FT_OK;
+    const size_t n_active = std::min<size_t>(F.h_report->n_pix_active / 64u, F.d_list_heads.bytes / 4);
+    std::vector<uint32_t> h(n_active);
+    if (n_active) FT_HIP(c, hipMemcpy(h.data(), F.d_list_heads.p, n_active * 4, hipMemcpyDeviceToHost));
+    size_t used = 0;
+    for (uint32_t v : h) if (v != ftk::kListNone) used = std::max<size_t>(used, (size_t)(v >> 7) + (v & 127u));
+    const size_t cap = F.d_list_pool.bytes / (ftk::kListEntryWords * 4);
+    if (used > cap) { c->err = "ft_debug_block_lists: a header points past the pool"; return FT_ERR_STATE; }
+    sizes[0] = (int64_t)n_active; sizes[1] = (int64_t)used; sizes[2] = F.list_leaf; sizes[3] = (int64_t)cap;
+    if (plane) { plane[0] = F.list_cam.tlx; plane[1] = F.list_cam.tly; plane[2] = F.list_cam.pw; plane[3] = F.list_cam.ph; }
+    if (heads && n_active) std::memcpy(heads, h.data(), n_active * 4);
+    if (pos_block && n_active) FT_HIP(c, hipMemcpy(pos_block, F.d_pos_block.p, n_active * 4, hipMemcpyDeviceToHost));
+    if (entries && used) FT_HIP(c, hipMemcpy(entries, F.d_list_pool.p, used * ftk::kListEntryWords * 4, hipMemcpyDeviceToHost));
+    return FT_OK;
+}
+
 int32_t ft_debug_slice(const double p0[3], const double n[3], const double tri[9], double above[18], int32_t* n_above, double below[18], int32_t* n_below) {
     if (!p0 || !n || !tri || !above || !below || !n_above || !n_below) return FT_ERR_INVALID;
     std::vector<double> a, b; std::string err;

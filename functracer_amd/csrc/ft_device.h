@@ -83,7 +83,7 @@ struct FrameCounters {
     uint32_t classify_ticket;      // k_classify: waves take their 64-block segment in ticket order, so a wave's predecessors are always running
     uint32_t classify_error;       // set when a bounded wait ran out (never observed; the host then fails the frame instead of hanging)
     uint32_t report_ticket;        // k_resolve / k_report: ticket stripes that are complete (the workgroup that completes the last one writes the frame's report)
-    uint32_t pad[1];
+    uint32_t list_cursor;          // k_block_lists: entries of the slot's list pool handed out so far
     uint32_t report_stripe[64];    // workgroups of stripe blockIdx % 64 that have finished (8000 tickets on one word took 80 us)
 };
 // What the host reads of a frame's counters, in pinned host memory.  The last workgroup of the frame's last k_resolve writes it and
@@ -127,6 +127,9 @@ struct Primary {
                                    // chunk works on the window [pix_base, pix_base + n_pix) of it
     const uint32_t* block_map;     // with counts: block b of the active list is block block_map[b] of pixel_ids; null: pixel_ids is the list itself
     int32_t group_log2;            // samples are numbered in groups of 2^this per 64-pixel block (slot_at, ft_kernels.hip); 0: sample plane by sample plane
+    // The frame's per-block triangle candidate lists (k_block_lists), or null: one header per block of the ACTIVE list and the pool
+    // their entries lie in; list_leaf is the bare mesh leaf they are for.
+    const uint32_t* list_heads; const uint32_t* list_pool; int32_t list_leaf;
 };
 // Bounce 0 fused (k_primary): generate the primary rays of the chunk, closest hit, shadow queries, shaders, reflection spawn, and
 // one colour per sample stored into acc (Colour.Zero for a miss).
@@ -148,6 +151,15 @@ struct ClassifyOut { int32_t* block_pos; uint32_t* pos_block; uint32_t* wave_cou
 constexpr int32_t kBlockRetired = -2;
 void launch_classify(const Launch& L, const DevScene& S, const Primary& gen_list, const ClassifyOut& out, double jitter_extent, uint32_t epoch, FrameCounters* fc,
                      const uint32_t* retired = nullptr, bool mask_only = false);
+// Per-block triangle candidate lists for the primaries of a classified frame (k_block_lists, queued behind its k_classify): one wave
+// per active block walks the 4-wide tree of the bare mesh leaf `leaf` with the block's pyramid and keeps the triangles whose rectangle on
+// the image plane overlaps the block's.  heads[b], for block b of the active list: kListNone (more than kListCap triangles, the pool
+// is full, or the pyramid is degenerate: the block's rays walk the tree) or first entry << 7 | count.  An entry is kListEntryWords
+// words: the triangle's record in DevScene::tris, its list index (tri_orig), and the rectangle x0, x1, y0, y1 as floats, rounded outward,
+// in the (jx, jy) coordinates of the primary rays.  fc->list_cursor hands out the pool.
+constexpr uint32_t kListNone = 0xFFFFFFFFu, kListCap = 64, kListEntryWords = 6;
+struct BlockLists { uint32_t* heads; uint32_t* pool; uint32_t pool_entries; int32_t leaf; };
+void launch_block_lists(const Launch& L, const DevScene& S, const Primary& gen_list, const uint32_t* pos_block, const BlockLists& out, double jitter_extent, FrameCounters* fc);
 // The frame's pixels: mean over the spp samples of each pixel of the chunk's window, in sample order (Image.fs:112-116), written as
 // FP64 RGB (out_rgb) and / or as Image.write's RGBA8 bytes (out_rgba, Image.fs:36); with `zero_culled` also Colour.Zero for every
 // pixel of the blocks k_classify finished.  Pixel p of the list goes to out index pixel_ids[p] (whole frame) or p (tiles, packed).

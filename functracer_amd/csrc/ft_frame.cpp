@@ -141,6 +141,7 @@ struct FramePlan {
     uint64_t zsig = 0;                   // what decides which blocks k_classify finishes: keys the zero-fill skip
     int64_t pix_per_chunk = 0, cap = 0;
     int group_log2 = 0, last_bounce = 0;
+    int32_t list_leaf = -1;              // >= 0: the frame carries per-block candidate lists for this bare mesh leaf (k_block_lists)
     ftk::Camera cam{};
 };
 
@@ -269,6 +270,19 @@ static void plan_chunks(ft_context* c, const RenderRequest& q, bool defer, Frame
     // (measured at 1080p x 16, 1 -> 16 samples per wave: bunny through BSP leaves 1.46 -> 1.29 ms, night-house 4.63 -> 4.45).
     const int64_t most = c->opt.wave_samples > 0 ? c->opt.wave_samples : 16;
     if (!p.corner && c->pixels_tiled) while ((2ll << p.group_log2) <= most && !((spp >> p.group_log2) & 1)) ++p.group_log2;
+    // Candidate lists: classified frames in grouped numbering over a scene with exactly ONE bare mesh leaf that has a 4-wide BVH.  Scenes
+    // with several such leaves and progressive passes keep the tree walk.
+    if (c->opt.primary_block_lists && p.classify && !p.mask_only && !p.progressive && p.group_log2 > 0 && (c->variant & 4)) {
+        int32_t leaf = -1, n_bare = 0;
+        for (size_t k = 0; k + 1 < c->flat.item_pc.size(); ++k) {
+            uint32_t w[3]; std::memcpy(w, &c->flat.cull_items[8 * k + 5], sizeof w);   // first coarse box, count, leaf
+            if (w[1] != 0u) { ++n_bare; leaf = (int32_t)w[2]; }
+        }
+        if (n_bare == 1) {
+            const uint32_t mesh = c->flat.leaves[leaf].mesh;
+            if (c->flat.meshes[mesh].bvh_root != INT32_MIN && c->flat.mesh_wide[mesh] != INT32_MIN) p.list_leaf = leaf;
+        }
+    }
     p.zsig = p.signature;
     auto mix = [&](const void* v, size_t n) { const unsigned char* b = static_cast<const unsigned char*>(v); for (size_t k = 0; k < n; ++k) p.zsig = (p.zsig ^ b[k]) * 0x100000001B3ull; };
     mix(&p.cam, sizeof p.cam); mix(&p.jitter_extent, sizeof p.jitter_extent);
@@ -323,12 +337,16 @@ static int32_t queue_classify(ft_context* c, const RenderRequest& q, const Frame
     const ftk::Launch Lg{cs, c->n_cu * 8, 0, 0};
     if (!c->classified) FT_HIP(c, hipEventCreateWithFlags(&c->classified, hipEventDisableTiming));
     else FT_HIP(c, hipStreamWaitEvent(cs, c->classified, 0));  // one classification at a time, whichever streams they are on
+    // the block lists right behind the classification, on its stream and inside its event: they ride beside the predecessors' tracing too
+    const ftk::BlockLists lists{F.d_list_heads.as<uint32_t>(), F.d_list_pool.as<uint32_t>(), (uint32_t)(F.d_list_pool.bytes / (ftk::kListEntryWords * 4)), p.list_leaf};
+    auto queue_lists = [&] { if (p.list_leaf >= 0) ftk::launch_block_lists(Lg, c->dev_scene, all, cls.pos_block, lists, p.jitter_extent, fc); };
     if (ahead) {
         ftk::launch_classify(Lg, c->dev_scene, all, cls, p.jitter_extent, epoch, fc, retired, p.mask_only);
+        queue_lists();
         FT_HIP(c, hipEventRecord(c->classified, c->side));
         FT_HIP(c, hipStreamWaitEvent(F.ev.ms, c->classified, 0));
     } else {
-        F.ev.timed(kStageOther, [&] { ftk::launch_classify(Lg, c->dev_scene, all, cls, p.jitter_extent, epoch, fc, retired, p.mask_only); });
+        F.ev.timed(kStageOther, [&] { ftk::launch_classify(Lg, c->dev_scene, all, cls, p.jitter_extent, epoch, fc, retired, p.mask_only); queue_lists(); });
         FT_HIP(c, hipEventRecord(c->classified, F.ev.ms));
     }
     F.ev.fresh = false;
@@ -362,6 +380,7 @@ static int32_t queue_chunks(ft_context* c, const RenderRequest& q, const FramePl
         ftk::Primary gen{p.cam, c->d_pixels.as<uint32_t>(), c->d_jitter.as<double>(), job.id_base, n_pix, p.spp, stride, (unsigned long long)q.seed,
                          1.0 / (double)n_pix, 1.0 / (double)stride, nullptr, nullptr};
         if (p.classify) { gen.counts = &fc->counts; gen.block_map = F.d_pos_block.as<uint32_t>(); }   // pix_base = job.id_base: the window's start in the active list
+        if (p.list_leaf >= 0) { gen.list_heads = F.d_list_heads.as<uint32_t>(); gen.list_pool = F.d_list_pool.as<uint32_t>(); gen.list_leaf = p.list_leaf; }
         gen.group_log2 = (n_pix % 64u == 0u) ? p.group_log2 : 0;
         const int at = c->acc_turn;
         double* const acc = c->d_acc[at].as<double>();
@@ -424,6 +443,14 @@ static int32_t queue_frame(ft_context* c, const RenderRequest& q, const FramePla
         const size_t n_blocks = (size_t)p.n_pix_total / 64, n_waves = (n_blocks + 255) / 256;   // one word per k_classify workgroup
         if ((rc = ensure(c, F.d_block_pos, n_blocks * 4)) != FT_OK) return rc;
         if ((rc = ensure(c, F.d_pos_block, n_blocks * 4)) != FT_OK) return rc;
+        if (p.list_leaf >= 0) {
+            // a header per block; the pool is sized from the block count, 16 entries a block (a list holds 64 at most, the bunny's blocks
+            // average under ten): blocks that find it full walk the tree
+            if ((rc = ensure(c, F.d_list_heads, n_blocks * 4)) != FT_OK) return rc;
+            if ((rc = ensure(c, F.d_list_pool, (16 * n_blocks + 4096) * ftk::kListEntryWords * 4)) != FT_OK) return rc;
+        }
+        F.list_leaf = p.list_leaf; F.list_cam = p.cam;
+        c->last_classified_slot = turn;
         if (c->d_wave_counts.bytes < n_waves * 4 || c->classify_epoch >= 0x3FFFFEu) {   // entries are tagged with the frame's epoch and never cleared in between
             if ((rc = ensure(c, c->d_wave_counts, std::max<size_t>(n_waves * 4, 4096) + 4096 * 4 + 2048 * 64)) != FT_OK) return rc;   // (+ room for the diagnostic build's stamps)
             FT_HIP(c, hipStreamSynchronize(c->side));              // (a classification of the other slot may still be publishing into the old words)
@@ -431,6 +458,9 @@ static int32_t queue_frame(ft_context* c, const RenderRequest& q, const FramePla
             c->classify_epoch = 0;
             uploads_queued = true;
         }
+    } else {
+        F.list_leaf = -1;                                          // the slot's lists, if any, were its previous frame's
+        if (c->last_classified_slot == turn) c->last_classified_slot = -1;
     }
     // Which main stream.  Two consecutive k_primary launches on ONE stream are an in-order pair: the second is dispatched when the first has
     // drained, and a persistent grid drains slowly (its last batches run on a machine that is mostly idle).  A simple frame - one chunk,
@@ -450,7 +480,7 @@ static int32_t queue_frame(ft_context* c, const RenderRequest& q, const FramePla
         FT_HIP(c, hipHostMalloc(reinterpret_cast<void**>(&F.h_report), sizeof(ftk::FrameReport), hipHostMallocDefault));
         FT_HIP(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&F.d_report), F.h_report, 0));
     }
-    int32_t n_launches = p.classify ? 1 : 0;
+    int32_t n_launches = p.classify ? 1 : 0;                       // k_classify; k_block_lists rides behind it and is not counted (functracer_hip.h)
     if ((rc = queue_chunks(c, q, p, F, main_ix, n_launches)) != FT_OK) return rc;
     c->last_n_pix = p.n_pix_total; c->last_res_h = q.res_h; c->last_res_v = q.res_v; c->last_format = q.format;
     if (defer && out) {                                            // ft_render_enqueue_into: the frame's way out is queued behind its last kernel

@@ -1000,6 +1000,49 @@ FT_DEV void mesh_shadow_grid(const Scene& S, cdp P, const Ray& r, Query<true>& q
     }
 }
 
+#ifdef FT_ITEM_COUNTS
+// Diagnostic build only: the list path of the closest queries, slots 16 + 2, 3, 7 of the wave's words (unused halves of the closest
+// kinds' clock pairs): entries offered, entries past the rectangle test (every one of them is a triangle tested), queries.
+#define FT_LIST_ADD(k, v) do { const unsigned long long v_ = (unsigned long long)(v); if (lane_id() == 0) atomicAdd(&g_clk[FT_CLK_SLOT() + 16 + (k)], v_); } while (0)
+#else
+#define FT_LIST_ADD(k, v) do { (void)(v); } while (0)
+#endif
+
+// The closest query of a COHERENT wave of primaries against a bare mesh through its block's candidate list (k_block_lists; ft_device.h)
+// instead of the tree: the header came through a scalar load a batch ahead, lane e fetches entry e (all addresses known at once, as in
+// mesh_shadow_grid), one ballot keeps the entries whose rectangle overlaps the wave's own rectangle on the image plane, and the survivors
+// go through tri_hit_wave in list order under the leaf loop's rule of mesh_bvh_packet: nearer, or as near with the lower list index.
+// That rule makes the result independent of the order and the route by which triangles are offered, and a list holds every triangle a
+// ray of the block can hit, so the hit is the walk's bit for bit.
+struct ListQuery { const uint32_t* pool; uint32_t head; uint32_t leaf; float x0, x1, y0, y1; };   // head = kListNone: the tree walk; x0 .. y1: the wave's rectangle, rounded outward
+FT_DEV void mesh_list_closest(const Scene& S, const ListQuery& Lq, const Ray& r, Query<false>& q, uint32_t leaf, bool lit) {
+    const bool alive = q.active;
+    const uint32_t count = Lq.head & 127u, first = Lq.head >> 7;
+    FT_LIST_ADD(7, 1); FT_LIST_ADD(2, count);
+    if (count == 0u || !__any(alive)) return;
+    const uint32_t* E = Lq.pool + (size_t)kListEntryWords * (first + min(lane_id(), count - 1u));
+    const uint32_t tri_v = E[0], orig_v = E[1];
+    const float ex0 = __uint_as_float(E[2]), ex1 = __uint_as_float(E[3]), ey0 = __uint_as_float(E[4]), ey1 = __uint_as_float(E[5]);
+    unsigned long long m = __ballot((lane_id() < count) & (ex0 <= Lq.x1) & (ex1 >= Lq.x0) & (ey0 <= Lq.y1) & (ey1 >= Lq.y0));
+    FT_LIST_ADD(3, __popcll(m));
+    double reach = alive ? q.best_t : -__builtin_inf();
+    uint32_t best_tri = 0xFFFFFFFFu;
+    bool found = false;
+    while (m) {
+        const int k = (int)__builtin_ctzll(m);
+        m &= m - 1ull;
+        const uint32_t tri = (uint32_t)__builtin_amdgcn_readlane((int)tri_v, k);
+        double t = 0.0;
+        const bool h = tri_hit_wave(S.tris + 9ull * tri, r, alive, t);
+        if (__any(h)) {
+            const uint32_t orig = (uint32_t)__builtin_amdgcn_readlane((int)orig_v, k);
+            const bool nearer = h & ((t < reach) | (found & (t == reach) & (orig < best_tri)));
+            reach = nearer ? t : reach; best_tri = nearer ? orig : best_tri; found = found | nearer;
+        }
+    }
+    if (found) q.hit(reach, leaf, best_tri, lit);
+}
+
 // ---------------------------------------------------------------------------------------------
 // Wave-level pre-test of the item culls.  OP_CULL tests one item against the 64 rays of the wave, 64 lanes x ~40
 // FP64 instructions per item; scenes with tens of items spend most of a coherent batch there.  Here the roles are
@@ -1267,7 +1310,8 @@ FT_DEV ItemMask exact_cull(const Scene& S, const Ray& r, bool live) {
 // MESH = false compiles the triangle / BSP / BVH code out: scenes without meshes then run kernels with
 // markedly fewer registers.
 template <bool ANY, bool MESH>
-FT_DEV void trace(const Scene& S, const Ray& r, Query<ANY>& q, uint32_t* lds, bool& overflow, bool coherent = false, cdp to_light = nullptr, int dir_light = -1) {
+FT_DEV void trace(const Scene& S, const Ray& r, Query<ANY>& q, uint32_t* lds, bool& overflow, bool coherent = false, cdp to_light = nullptr, int dir_light = -1,
+                  const ListQuery* lists = nullptr) {
     HitList L;
     L.init(lds, S.csg_cap, S.csg_rows, S.lane_fold);
     int32_t* stack = reinterpret_cast<int32_t*>(lds + 4 * S.csg_rows * kBlock) + threadIdx.x;
@@ -1324,6 +1368,9 @@ FT_DEV void trace(const Scene& S, const Ray& r, Query<ANY>& q, uint32_t* lds, bo
                                     }
                                 }
                             }
+                        }
+                        if constexpr (!ANY) {                           // k_primary's closest query of a block that carries a candidate list
+                            if (coherent && lists && lists->head != kListNone && arg == lists->leaf) { mesh_list_closest(S, *lists, rm, q, arg, lit); break; }
                         }
                         if (coherent) mesh_bvh_packet<ANY>(S, S.mesh_wide[H.mesh], rm, q, arg, lit);
                         else mesh_bvh_query<ANY>(S, bvh, rm, q, arg, lit, stack);
@@ -1691,11 +1738,12 @@ FT_DEV unsigned long long sample_id(PrimaryArg g, const Pix& px, uint32_t slot) 
 
 // Primary rays are never stored: k_primary generates them from the sample's place (ImagePlane.rayThroughPixel, Image.fs:83-89).
 FT_DEV uint32_t primary_pixel(PrimaryArg g, const SlotAt& at) { return list_pixel(g, g->pix_base + at.pl); }   // the one memory access a primary ray needs
-FT_DEV Ray primary_ray_from(PrimaryArg g, uint32_t s, uint32_t pid) {
+FT_DEV Ray primary_ray_from(PrimaryArg g, uint32_t s, uint32_t pid, double* jxy = nullptr) {   // jxy: the ray's point (jx, jy) on the image plane
     const uint32_t py = div_by(pid, g->inv_stride), px = pid - py * g->stride;
     const double centre_x = g->cam.tlx + (double)px * g->cam.pw, centre_y = g->cam.tly - (double)py * g->cam.ph;
     const double ox = g->jitter[2 * s], oy = g->jitter[2 * s + 1];
     const double jx = centre_x + ox * g->cam.pw, jy = centre_y + oy * g->cam.ph;
+    if (jxy) { jxy[0] = jx; jxy[1] = jy; }
     Ray r{g->cam.o[0], g->cam.o[1], g->cam.o[2],
           (g->cam.k[0] + jx * g->cam.i[0]) + jy * g->cam.j[0], (g->cam.k[1] + jx * g->cam.i[1]) + jy * g->cam.j[1], (g->cam.k[2] + jx * g->cam.i[2]) + jy * g->cam.j[2]};
     if (g->cam.has_focus) {                                         // ImagePlane.depthOfFieldJitter (Image.fs:91-94, Ray.fs:15-18)
@@ -1874,9 +1922,19 @@ __global__ __launch_bounds__(kBlock, BLOCKS) void k_primary(PrimaryArgs) {
     uint32_t bi = cursor.grab(), bi_next = cursor.grab();
     uint32_t pid_next = 0;
     if (bi < n_batches && bi * B + lane_id() < n && lane_id() < B) pid_next = primary_pixel(&K->gen, at_of(bi));
+    // The block's candidate list (k_block_lists) in place of the mesh's tree: grouped numbering only (a batch is then part of ONE block of
+    // the frame's active list, block (pix_base + pl) / 64), coherent waves only.  The header is requested a batch ahead, like the pixel id.
+    const bool use_lists = MESH && coherent && px.group_log2 != 0u && K->gen.list_heads != nullptr;
+    auto head_of = [&](const FT_CONST PrimaryArgs* Kx, uint32_t batch) -> uint32_t {
+        const uint32_t blk = (uint32_t)__builtin_amdgcn_readfirstlane((int)((Kx->gen.pix_base + slot_at(px, batch, 0u).pl) >> 6));
+        return to_const_as(Kx->gen.list_heads)[blk];
+    };
+    uint32_t head_next = kListNone;
+    if (use_lists && bi < n_batches) head_next = head_of(K, bi);
     for (; bi < n_batches; bi = bi_next, bi_next = cursor.grab()) {
         const uint32_t i = bi * B + lane_id();
         const uint32_t pid = pid_next;
+        ListQuery lq{nullptr, head_next, 0u, 0.f, 0.f, 0.f, 0.f};
         const bool active = i < n && lane_id() < B;
         const unsigned long long clk_batch = FT_CLK_NOW();          // (diagnostic build: sections of a batch, slots 22 .. 27)
         // ---- closest hit; the geometry sees the offset ray (Shading.fs:135), the shaders the original one (Shading.fs:137)
@@ -1884,16 +1942,25 @@ __global__ __launch_bounds__(kBlock, BLOCKS) void k_primary(PrimaryArgs) {
         {
             const FT_CONST PrimaryArgs* Kb = fresh(K);              // camera, pixel list: loaded here, dead before the trace
             if (bi_next < n_batches && bi_next * B + lane_id() < n && lane_id() < B) pid_next = primary_pixel(&Kb->gen, at_of(bi_next));
+            if (use_lists && bi_next < n_batches) head_next = head_of(Kb, bi_next);
+            double jxy[2] = {0.0, 0.0};
             if (active) {
-                const Ray r = primary_ray_from(&Kb->gen, at_of(bi).s, pid);
+                const Ray r = primary_ray_from(&Kb->gen, at_of(bi).s, pid, jxy);
                 ro = {r.ox + 0.0001 * r.dx, r.oy + 0.0001 * r.dy, r.oz + 0.0001 * r.dz, r.dx, r.dy, r.dz};   // slightOffset (Shading.fs:129)
+            }
+            if (MESH && lq.head != kListNone) {                      // (wave-uniform) the wave's rectangle on the image plane, rounded outward to float
+                const float inf = __builtin_inff();
+                const float fx = (float)jxy[0], fy = (float)jxy[1], sx = 2.4e-7f * fabsf(fx) + 1e-37f, sy = 2.4e-7f * fabsf(fy) + 1e-37f;
+                lq.x0 = wave_min(active ? fx - sx : inf); lq.x1 = wave_max(active ? fx + sx : -inf);
+                lq.y0 = wave_min(active ? fy - sy : inf); lq.y1 = wave_max(active ? fy + sy : -inf);
+                lq.pool = Kb->gen.list_pool; lq.leaf = (uint32_t)Kb->gen.list_leaf;
             }
         }
         Query<false> q = Query<false>::closest(active);
         bool overflow;
         const unsigned long long clk_a = FT_CLK_NOW();
         FT_CLK_ADD(22, clk_batch);
-        trace<false, MESH>(S, ro, q, lds, overflow, coherent);
+        trace<false, MESH>(S, ro, q, lds, overflow, coherent, nullptr, -1, MESH ? &lq : nullptr);
         FT_CLK_ADD(23, clk_a);
         n_ovf_wave += (unsigned long long)__popcll(__ballot(overflow && active));
         const bool hit = active && q.id0 != ID_MISS;
@@ -2103,6 +2170,51 @@ __global__ __launch_bounds__(kBlock, FANCY ? 2 : 4) void k_bounce(BounceArgs) {
 // the wait is bounded by the slowest classification; it is also bounded by a poll limit that fails the frame rather than hang).
 // The host only runs this for pinhole cameras, pixel lists made of 8x8 tiles and scenes made of bounded items - except for adaptive
 // progressive passes, which run it on any 8x8-tiled list, in mask-only mode where the host would not classify (ClassifyArgs::mask_only).
+// What k_classify and k_block_lists share: a block's rectangle on the image plane, in the (jx, jy) of primary_ray_from, widened by the
+// jitter extent; the directions through its centre and its four corners; and the pyramid through the corner rays in a mesh leaf's
+// model space - four side planes through the apex, inward normals as floats.  A box is out of reach of every ray of the block if its
+// corner furthest along one side's inward normal still lies behind that side (beyond_side; the slack covers the float arithmetic);
+// a side whose orientation could not be told (`sided` bit clear) cuts nothing off.
+struct BlockRect { double jxa, jxb, jya, jyb; };
+FT_DEV BlockRect block_rect(PrimaryArg g, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, double jitter_extent) {
+    const double ext = jitter_extent * 1.000001;
+    return {g->cam.tlx + ((double)x0 - ext) * g->cam.pw, g->cam.tlx + ((double)x1 + ext) * g->cam.pw,
+            g->cam.tly - ((double)y1 + ext) * g->cam.ph, g->cam.tly - ((double)y0 - ext) * g->cam.ph};
+}
+FT_DEV void block_corner_dirs(PrimaryArg g, const BlockRect& R, double (&d)[5][3]) {
+    const double jxa = R.jxa, jxb = R.jxb, jya = R.jya, jyb = R.jyb;
+#pragma unroll
+    for (int c = 0; c < 5; ++c) {
+        const double jx = c == 0 ? 0.5 * (jxa + jxb) : ((c == 1 || c == 4) ? jxa : jxb), jy = c == 0 ? 0.5 * (jya + jyb) : (c <= 2 ? jya : jyb);
+        d[c][0] = (g->cam.k[0] + jx * g->cam.i[0]) + jy * g->cam.j[0]; d[c][1] = (g->cam.k[1] + jx * g->cam.i[1]) + jy * g->cam.j[1];
+        d[c][2] = (g->cam.k[2] + jx * g->cam.i[2]) + jy * g->cam.j[2];
+    }
+}
+struct Pyramid { float pn[4][3]; uint32_t sided; double ox, oy, oz; };   // ox, oy, oz: the apex (the camera in model space)
+FT_DEV Pyramid block_pyramid(cdp Mw, bool xform, PrimaryArg g, const double (&d)[5][3]) {
+    Pyramid P;
+    Ray corner[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) to_model(Mw, xform, Ray{g->cam.o[0], g->cam.o[1], g->cam.o[2], d[c + 1][0], d[c + 1][1], d[c + 1][2]}, corner[c]);
+    P.sided = 0;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {                           // side plane through corner rays c and c+1, oriented by the opposite corner
+        const Ray& a = corner[c]; const Ray& bq = corner[(c + 1) & 3]; const Ray& opp = corner[(c + 2) & 3];
+        float nx = (float)(a.dy * bq.dz - a.dz * bq.dy), ny = (float)(a.dz * bq.dx - a.dx * bq.dz), nz = (float)(a.dx * bq.dy - a.dy * bq.dx);
+        const float side = nx * (float)opp.dx + ny * (float)opp.dy + nz * (float)opp.dz;
+        if (side < 0.0f) { nx = -nx; ny = -ny; nz = -nz; }
+        P.pn[c][0] = nx; P.pn[c][1] = ny; P.pn[c][2] = nz; if (side != 0.0f) P.sided |= 1u << c;
+    }
+    P.ox = corner[0].ox; P.oy = corner[0].oy; P.oz = corner[0].oz;
+    return P;
+}
+// (qx, qy, qz): a box's corner furthest along the inward normal (nx, ny, nz) of a side, relative to the apex
+FT_DEV bool beyond_side(float nx, float ny, float nz, bool sided, float qx, float qy, float qz) {
+    const float dd = nx * qx + ny * qy + nz * qz;
+    const float slack = 1e-4f * (fabsf(nx * qx) + fabsf(ny * qy) + fabsf(nz * qz));
+    return dd < -slack && sided;
+}
+
 struct ClassifyArgs {
     DevScene S; Primary gen;                                        // gen.pixel_ids / n_pix: the frame's full pixel list (8x8 tiles)
     ClassifyOut out; FrameCounters* fc;
@@ -2141,16 +2253,8 @@ __global__ __launch_bounds__(kClassifyBlock) void k_classify(ClassifyArgs) {
     const uint32_t y0 = div_by(pid0, g->inv_stride), x0 = pid0 - y0 * g->stride, y1 = div_by(pid1, g->inv_stride), x1 = pid1 - y1 * g->stride;
     if (__builtin_amdgcn_readfirstlane((int)(x0 + y0 + x1 + y1)) == -12345) return;   // (keeps the loads ahead of the stamp in the diagnostic build; never true)
     FT_STAMP(2);
-    const double ext = K->jitter_extent * 1.000001;
-    const double jxa = g->cam.tlx + ((double)x0 - ext) * g->cam.pw, jxb = g->cam.tlx + ((double)x1 + ext) * g->cam.pw;
-    const double jya = g->cam.tly - ((double)y1 + ext) * g->cam.ph, jyb = g->cam.tly - ((double)y0 - ext) * g->cam.ph;
     double d[5][3];                                                 // centre, then the corners in order around the block
-#pragma unroll
-    for (int c = 0; c < 5; ++c) {
-        const double jx = c == 0 ? 0.5 * (jxa + jxb) : ((c == 1 || c == 4) ? jxa : jxb), jy = c == 0 ? 0.5 * (jya + jyb) : (c <= 2 ? jya : jyb);
-        d[c][0] = (g->cam.k[0] + jx * g->cam.i[0]) + jy * g->cam.j[0]; d[c][1] = (g->cam.k[1] + jx * g->cam.i[1]) + jy * g->cam.j[1];
-        d[c][2] = (g->cam.k[2] + jx * g->cam.i[2]) + jy * g->cam.j[2];
-    }
+    block_corner_dirs(g, block_rect(g, x0, y0, x1, y1, K->jitter_extent), d);
     float ax = 0.f, ay = 0.f, az = 0.f, cos_dev = 1.0f;
     bool finite = true;
 #pragma unroll
@@ -2189,19 +2293,8 @@ __global__ __launch_bounds__(kClassifyBlock) void k_classify(ClassifyArgs) {
             const uint32_t first_box = __float_as_uint(I[5]), leaf = __float_as_uint(I[7]);
             const LeafHead Hm = leaf_head(S, leaf);
             cdp Mw = S.leaves + 16ull * leaf;
-            Ray corner[4];
-#pragma unroll
-            for (int c = 0; c < 4; ++c) to_model(Mw, (Hm.flags & LF_XFORM) != 0, Ray{g->cam.o[0], g->cam.o[1], g->cam.o[2], d[c + 1][0], d[c + 1][1], d[c + 1][2]}, corner[c]);
-            float pn[4][3]; uint32_t sided = 0;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {                           // side plane through corner rays c and c+1, oriented by the opposite corner
-                const Ray& a = corner[c]; const Ray& bq = corner[(c + 1) & 3]; const Ray& opp = corner[(c + 2) & 3];
-                float nx = (float)(a.dy * bq.dz - a.dz * bq.dy), ny = (float)(a.dz * bq.dx - a.dx * bq.dz), nz = (float)(a.dx * bq.dy - a.dy * bq.dx);
-                const float side = nx * (float)opp.dx + ny * (float)opp.dy + nz * (float)opp.dz;
-                if (side < 0.0f) { nx = -nx; ny = -ny; nz = -nz; }
-                pn[c][0] = nx; pn[c][1] = ny; pn[c][2] = nz; if (side != 0.0f) sided |= 1u << c;
-            }
-            const float ox = (float)corner[0].ox, oy = (float)corner[0].oy, oz = (float)corner[0].oz;   // the camera in model space: the same for every block
+            const Pyramid Py = block_pyramid(Mw, (Hm.flags & LF_XFORM) != 0, g, d);
+            const float ox = (float)Py.ox, oy = (float)Py.oy, oz = (float)Py.oz;   // the camera in model space: the same for every block
             // The boxes sit in the lanes (lane k: box k of the current 64) and are broadcast one at a time; every lane tests ITS block.
             // Groups of eight neighbouring boxes (siblings in the tree they were cut from) are tried first as one box: a block whose
             // pyramid misses the union of a group skips its eight members, and the walk ends as soon as every block has found a box
@@ -2210,12 +2303,10 @@ __global__ __launch_bounds__(kClassifyBlock) void k_classify(ClassifyArgs) {
                 bool in = true;
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
-                    const float nx = pn[c][0], ny = pn[c][1], nz = pn[c][2];
+                    const float nx = Py.pn[c][0], ny = Py.pn[c][1], nz = Py.pn[c][2];
                     // the box corner furthest along the inward normal
                     const float qx = (nx > 0.0f ? q[3] : q[0]) - ox, qy = (ny > 0.0f ? q[4] : q[1]) - oy, qz = (nz > 0.0f ? q[5] : q[2]) - oz;
-                    const float dd = nx * qx + ny * qy + nz * qz;
-                    const float slack = 1e-4f * (fabsf(nx * qx) + fabsf(ny * qy) + fabsf(nz * qz));
-                    if (dd < -slack && ((sided >> c) & 1u)) in = false;     // wholly outside this side of the pyramid
+                    if (beyond_side(nx, ny, nz, ((Py.sided >> c) & 1u) != 0u, qx, qy, qz)) in = false;     // wholly outside this side of the pyramid
                 }
                 return in;
             };
@@ -2302,6 +2393,143 @@ __global__ __launch_bounds__(kClassifyBlock) void k_classify(ClassifyArgs) {
     const unsigned long long n_valid = (unsigned long long)__popcll(__ballot(valid));
     wave_add(&K->fc->stats[(ticket * (kClassifyBlock / 64) + wave) % (uint32_t)kStatStripes].pixels_culled, 64ull * (n_valid - (unsigned long long)n_keep));
     FT_STAMP(5);
+}
+
+// ---------------------------------------------------------------------------------------------
+// k_block_lists: per-block triangle candidate lists for the primaries of a classified frame (ft_device.h, BlockLists; read by
+// mesh_list_closest).  The 16 batches of a block (64 at 64 samples) would each walk the top of the mesh's tree from the root; here ONE
+// wave per active block walks it once, with the block's pyramid, and keeps what it finds.
+//   Nodes: the walk of mesh_bvh_packet (wave-uniform, WaveStack) with k_classify's test in place of the slab test: lane 4 c + s tests
+//   child c against side s, so a node costs one test; a child is entered unless one side cuts it off.
+//   Leaves: lane k projects triangle k onto the image plane.  In the leaf's model space a primary ray's direction is affine in its
+//   point (jx, jy) of the plane, d = Km + jx Im + jy Jm, so with R = [Km Im Jm]^-1 (once per wave) a vertex p maps to
+//   (a, b, c) = R (p - o), jx = b / a, jy = c / a, and a > 0 in front of the camera.  A hit point is a convex combination of the
+//   vertices, so it projects into the bounding rectangle of the three - unless a vertex has a <= 0 (the triangle reaches the camera
+//   plane): then the rectangle is unbounded.  Every quantity carries an error bound (kProjEps times the magnitudes that went in: a
+//   thousand times the rounding of the few products, so that it also covers what to_model and the ray's own arithmetic add), the
+//   rectangle grows by 1e-3 of its size (tri_hit's range tests decide in rounded arithmetic: a ray that passes a hair outside an edge may
+//   still count as a hit) and is rounded outward to float.  A triangle is kept if its rectangle overlaps the block's.
+// A block whose list would pass kListCap entries, or for which the pool has no room left, or whose pyramid is degenerate, gets
+// kListNone: its rays walk the tree as before.
+struct BlockListArgs {
+    DevScene S; Primary gen;                                        // gen.pixel_ids: the frame's full pixel list (8x8 tiles)
+    const uint32_t* pos_block; BlockLists out; FrameCounters* fc;
+    double jitter_extent;
+};
+constexpr double kProjEps = 1e-12;
+FT_DEV float round_down(double x) { return (float)(x - (2.4e-7 * fabs(x) + 1e-37)); }   // a float's rounding is at most 6e-8 of its magnitude
+FT_DEV float round_up(double x) { return (float)(x + (2.4e-7 * fabs(x) + 1e-37)); }
+__global__ __launch_bounds__(kBlock) void k_block_lists(BlockListArgs) {
+    __shared__ uint32_t sh_entries[kBlock / 64][kListCap * kListEntryWords];
+    const FT_CONST BlockListArgs* K = kernel_args<BlockListArgs>();
+    const Scene S = scene_view(K->S);
+    const PrimaryArg g = &K->gen;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / 64u));
+    uint32_t* mine = sh_entries[wave];
+    const uint32_t n_active = to_const_as(&K->fc->counts)->n_pix / 64u;
+    const uint32_t leaf = (uint32_t)K->out.leaf;
+    const LeafHead Hm = leaf_head(S, leaf);
+    cdp Mw = S.leaves + 16ull * leaf;
+    const bool xform = (Hm.flags & LF_XFORM) != 0;
+    const int32_t root = S.mesh_wide[Hm.mesh];
+    // R = [Km Im Jm]^-1 by cofactors; om: the camera in model space
+    Ray mk, mi, mj;
+    to_model(Mw, xform, Ray{g->cam.o[0], g->cam.o[1], g->cam.o[2], g->cam.k[0], g->cam.k[1], g->cam.k[2]}, mk);
+    to_model(Mw, xform, Ray{g->cam.o[0], g->cam.o[1], g->cam.o[2], g->cam.i[0], g->cam.i[1], g->cam.i[2]}, mi);
+    to_model(Mw, xform, Ray{g->cam.o[0], g->cam.o[1], g->cam.o[2], g->cam.j[0], g->cam.j[1], g->cam.j[2]}, mj);
+    const double c0x = mi.dy * mj.dz - mi.dz * mj.dy, c0y = mi.dz * mj.dx - mi.dx * mj.dz, c0z = mi.dx * mj.dy - mi.dy * mj.dx;   // Im x Jm
+    const double c1x = mj.dy * mk.dz - mj.dz * mk.dy, c1y = mj.dz * mk.dx - mj.dx * mk.dz, c1z = mj.dx * mk.dy - mj.dy * mk.dx;   // Jm x Km
+    const double c2x = mk.dy * mi.dz - mk.dz * mi.dy, c2y = mk.dz * mi.dx - mk.dx * mi.dz, c2z = mk.dx * mi.dy - mk.dy * mi.dx;   // Km x Im
+    const double det = mk.dx * c0x + mk.dy * c0y + mk.dz * c0z, inv_det = 1.0 / det;
+    const double r0x = c0x * inv_det, r0y = c0y * inv_det, r0z = c0z * inv_det, r1x = c1x * inv_det, r1y = c1y * inv_det, r1z = c1z * inv_det,
+                 r2x = c2x * inv_det, r2y = c2y * inv_det, r2z = c2z * inv_det;
+    const double omx = mk.ox, omy = mk.oy, omz = mk.oz;
+    const bool usable = root != INT32_MIN && fabs(det) > 1e-300 &&
+                        fabs(r0x) + fabs(r0y) + fabs(r0z) + fabs(r1x) + fabs(r1y) + fabs(r1z) + fabs(r2x) + fabs(r2y) + fabs(r2z) + fabs(omx) + fabs(omy) + fabs(omz) < 1e300;
+    const uint32_t side = lane_id() & 3u, child = (lane_id() >> 2) & 3u;
+    for (uint32_t pos = blockIdx.x * (kBlock / 64u) + wave; pos < n_active; pos += gridDim.x * (kBlock / 64u)) {   // wave-uniform
+        const uint32_t blk = to_const_as(K->pos_block)[pos];
+        const uint32_t pid0 = to_const_as(g->pixel_ids)[(size_t)blk * 64u], pid1 = to_const_as(g->pixel_ids)[(size_t)blk * 64u + 63u];
+        const uint32_t y0 = div_by(pid0, g->inv_stride), x0 = pid0 - y0 * g->stride, y1 = div_by(pid1, g->inv_stride), x1 = pid1 - y1 * g->stride;
+        const BlockRect R = block_rect(g, x0, y0, x1, y1, K->jitter_extent);
+        double d[5][3];
+        block_corner_dirs(g, R, d);
+        const Pyramid Py = block_pyramid(Mw, xform, g, d);
+        const float bx0 = round_down(R.jxa), bx1 = round_up(R.jxb), by0 = round_down(R.jya), by1 = round_up(R.jyb);
+        // this lane's side of the pyramid
+        const float nx = side == 0u ? Py.pn[0][0] : side == 1u ? Py.pn[1][0] : side == 2u ? Py.pn[2][0] : Py.pn[3][0];
+        const float ny = side == 0u ? Py.pn[0][1] : side == 1u ? Py.pn[1][1] : side == 2u ? Py.pn[2][1] : Py.pn[3][1];
+        const float nz = side == 0u ? Py.pn[0][2] : side == 1u ? Py.pn[1][2] : side == 2u ? Py.pn[2][2] : Py.pn[3][2];
+        const bool sided = ((Py.sided >> side) & 1u) != 0u;
+        bool whole = usable && Py.sided == 0xFu && bx0 <= bx1 && by0 <= by1;   // (a NaN anywhere in the rectangle fails the comparisons)
+        uint32_t n = 0;
+        WaveStack st;
+        int cur = root;
+        while (whole) {
+            cur = __builtin_amdgcn_readfirstlane(cur);
+            st.sp = __builtin_amdgcn_readfirstlane(st.sp);
+            if (cur >= 0) {
+                cdp nd = S.wide + (unsigned long long)kWideNodeDoubles * (uint32_t)cur;
+                const int32_t ch[4] = {reinterpret_cast<cip>(nd + 24)[0], reinterpret_cast<cip>(nd + 24)[1], reinterpret_cast<cip>(nd + 24)[2], reinterpret_cast<cip>(nd + 24)[3]};
+                cdp bx = nd + 6u * child;
+                // the box corner furthest along the inward normal, relative to the apex (the difference in FP64: no cancellation in float)
+                const float qx = (float)((nx > 0.0f ? bx[3] : bx[0]) - Py.ox), qy = (float)((ny > 0.0f ? bx[4] : bx[1]) - Py.oy), qz = (float)((nz > 0.0f ? bx[5] : bx[2]) - Py.oz);
+                const uint32_t cut = (uint32_t)(__ballot(lane_id() < 16u && beyond_side(nx, ny, nz, sided, qx, qy, qz)) & 0xFFFFull);
+#pragma unroll
+                for (int c = 3; c >= 0; --c) st.push(ch[c], __builtin_amdgcn_ballot_w64(ch[c] != INT32_MIN && ((cut >> (4 * c)) & 0xFu) == 0u));   // (a ballot: the mask in scalar registers) an empty slot's box is all NaN
+            } else {
+                const uint32_t first = S.bsp_leaves[2 * (~cur)], count = S.bsp_leaves[2 * (~cur) + 1];
+                for (uint32_t base = 0; base < count && whole; base += 64u) {
+                    const uint32_t k = base + lane_id(), tri = first + (k < count ? k : count - 1u);
+                    cdp T = S.tris + 9ull * tri;
+                    const double vx[3] = {T[0], T[0] + T[3], T[0] + T[6]}, vy[3] = {T[1], T[1] + T[4], T[1] + T[7]}, vz[3] = {T[2], T[2] + T[5], T[2] + T[8]};
+                    double xl = __builtin_inf(), xh = -__builtin_inf(), yl = __builtin_inf(), yh = -__builtin_inf();
+                    bool bounded = true;
+#pragma unroll
+                    for (int v = 0; v < 3; ++v) {
+                        const double px = vx[v] - omx, py = vy[v] - omy, pz = vz[v] - omz;
+                        const double mx = fabs(vx[v]) + fabs(omx), my = fabs(vy[v]) + fabs(omy), mz = fabs(vz[v]) + fabs(omz);
+                        const double a = r0x * px + r0y * py + r0z * pz, b = r1x * px + r1y * py + r1z * pz, c = r2x * px + r2y * py + r2z * pz;
+                        const double ea = kProjEps * (fabs(r0x) * mx + fabs(r0y) * my + fabs(r0z) * mz), eb = kProjEps * (fabs(r1x) * mx + fabs(r1y) * my + fabs(r1z) * mz),
+                                     ec = kProjEps * (fabs(r2x) * mx + fabs(r2y) * my + fabs(r2z) * mz);
+                        const double am = a - ea;                   // the least a can be
+                        const double jx = b / a, jy = c / a, ex = (eb + fabs(jx) * ea) / am, ey = (ec + fabs(jy) * ea) / am;
+                        bounded = bounded && am > 0.0 && fabs(jx) + fabs(jy) + ex + ey < 1e300;
+                        xl = fmin(xl, jx - ex); xh = fmax(xh, jx + ex); yl = fmin(yl, jy - ey); yh = fmax(yh, jy + ey);
+                    }
+                    const double grow = 1e-3 * ((xh - xl) + (yh - yl));
+                    const float inf = __builtin_inff();
+                    const float tx0 = bounded ? round_down(xl - grow) : -inf, tx1 = bounded ? round_up(xh + grow) : inf;
+                    const float ty0 = bounded ? round_down(yl - grow) : -inf, ty1 = bounded ? round_up(yh + grow) : inf;
+                    const bool keep = k < count && tx0 <= bx1 && tx1 >= bx0 && ty0 <= by1 && ty1 >= by0;
+                    const unsigned long long km = __ballot(keep);
+                    const uint32_t n_keep = (uint32_t)__popcll(km);
+                    if (n + n_keep > kListCap) { whole = false; break; }
+                    if (keep) {
+                        uint32_t* e = mine + kListEntryWords * (n + lanes_below(km));
+                        e[0] = tri; e[1] = S.tri_orig[tri]; e[2] = __float_as_uint(tx0); e[3] = __float_as_uint(tx1); e[4] = __float_as_uint(ty0); e[5] = __float_as_uint(ty1);
+                    }
+                    n += n_keep;
+                }
+            }
+            if (!st.pop(cur)) break;
+        }
+        // room in the pool, then the entries out of the LDS (one wave: its LDS accesses complete in order)
+        uint32_t head = kListNone;
+        if (whole) {
+            uint32_t at = 0;
+            if (lane_id() == 0 && n) at = atomicAdd(&K->fc->list_cursor, n);
+            at = (uint32_t)__builtin_amdgcn_readfirstlane((int)at);
+            if (at <= K->out.pool_entries && n <= K->out.pool_entries - at && at + n < (1u << 25)) {
+                __builtin_amdgcn_wave_barrier();
+                uint32_t* dst = K->out.pool + (size_t)kListEntryWords * at;
+                for (uint32_t w = lane_id(); w < kListEntryWords * n; w += 64u) dst[w] = mine[w];
+                head = (at << 7) | n;
+            }
+        }
+        if (lane_id() == 0) K->out.heads[pos] = head;
+        __builtin_amdgcn_wave_barrier();                            // the next block's entries go into the same LDS words
+    }
 }
 
 // Image.write's toByte (Image.fs:36; Math.clamp, Math.fs:12-16): clamp to [0, 1] (NaN passes the clamp), * 255, truncate.
@@ -2690,6 +2918,11 @@ void launch_classify(const Launch& L, const DevScene& S, const Primary& gen_list
     const ClassifyArgs a{S, gen_list, out, fc, jitter_extent, epoch, retired, mask_only ? 1u : 0u};
     const uint32_t n_blocks = gen_list.n_pix / 64u;
     hipLaunchKernelGGL(k_classify, dim3((n_blocks + kClassifyBlock - 1u) / kClassifyBlock), dim3(kClassifyBlock), 0, L.stream, a);
+}
+void launch_block_lists(const Launch& L, const DevScene& S, const Primary& gen_list, const uint32_t* pos_block, const BlockLists& out, double jitter_extent, FrameCounters* fc) {
+    const BlockListArgs a{S, gen_list, pos_block, out, fc, jitter_extent};
+    const uint32_t n_blocks = gen_list.n_pix / 64u, need = (n_blocks + kBlock / 64u - 1u) / (kBlock / 64u);   // a wave per block, grid-strided over the active ones
+    hipLaunchKernelGGL(k_block_lists, dim3(need < (uint32_t)L.grid ? (need ? need : 1u) : (uint32_t)L.grid), dim3(kBlock), 0, L.stream, a);
 }
 void launch_bounce(const Launch& L, const DevScene& S, const Primary& gen, RayBuf rays, RayBuf next, double* acc, uint32_t acc_stride, int bounce, int max_depth, bool follow, FrameCounters* fc) {
     const BounceArgs a{S, gen, rays, next, acc, fc, acc_stride, bounce, max_depth, follow ? 1 : 0};

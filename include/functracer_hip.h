@@ -118,7 +118,7 @@ typedef struct ft_stats {
     double   wall_ms;        /* host wall time of the call incl. copies                        */
     double   trace_kernel_ms;/* HIP-event time of the closest-hit + shade/shadow kernels only  */
     uint64_t algorithmic_bytes; /* bytes the pipeline has to move for this frame by construction (roofline) */
-    int32_t  n_launches;
+    int32_t  n_launches;     /* kernels launched for the call; k_block_lists, which rides behind k_classify, is not counted */
     int32_t  n_chunks;
     uint64_t hits_total;     /* hits shaded over all bounces                                   */
     uint64_t algorithmic_bytes_closest; /* unused since ABI 2 (always 0)                       */
@@ -154,6 +154,10 @@ const char* ft_last_error(const ft_context* ctx);
  * for each top-level `bspMesh 0` leaf, and walk the tree of option 1 where a wave spans more than a few cells; 1: they walk a tree built in the light's
  * frame; 0: they walk the mesh's BVH like every other ray.  Same triangle records, same results bit for bit; a value other than 0 / 1 means 2; a change
  * re-commits),
+ * "primary_block_lists" (1 = default: in a classified frame over a scene with exactly one top-level `bspMesh 0` leaf, one wave per active 8x8 block walks the
+ * mesh's tree once with the block's pyramid and keeps the triangles whose rectangle on the image plane overlaps the block's; the block's primary rays then test
+ * that short list instead of walking the tree, each from the root.  Blocks with more than 64 candidates, progressive passes and scenes with several such leaves
+ * keep the walk; 0: the walk everywhere.  Same triangle records, the closest hit does not depend on the order they are offered in: same frames bit for bit),
  * "classify_ahead" / "resolve_aside" / "zero_fill_skip" (1 = default: what a stream of queued frames does that a single frame cannot - the next frame's k_classify on a second
  * stream, k_resolve on a third with the sample colours double-buffered, Colour.Zero not written again into blocks the last frame of the same signature left zero; 0 switches each off; k_resolve goes aside only in frames of one chunk), "mains" (2 = default, 1 .. 3: queued frames of one chunk take turns on that many main streams, so a frame's kernels are dispatched while its predecessor's drain
  * and two frames' reflection levels fill each other's idle stretches), "wave_samples" (0 = default, 16: a bounce-0 wavefront takes up to that many jitter offsets of 64 / that many pixels of an
@@ -547,6 +551,13 @@ int32_t ft_debug_light_space(ft_context* ctx, int64_t sizes[4], double* pairs, u
  * box count) and 9 words per job (mesh, first_global, n, node_base, leaf_base, tri_base, wide_base, coarse_first, coarse_count). */
 int32_t ft_debug_mesh_trees(ft_context* ctx, int64_t sizes[12], void* nodes, uint32_t* bsp_leaves, double* tris, uint32_t* tri_orig, uint32_t* tri_src,
                             double* wide, float* coarse_boxes, int32_t* meshes, uint32_t* jobs);
+/* The per-block triangle candidate lists of the last classified frame queued (option "primary_block_lists"), read back from device memory once
+ * everything queued has run, for tests.  sizes = active blocks, entries in use, the mesh leaf the lists are for (-1: that frame carried none; the
+ * other sizes are then 0), the pool's capacity in entries.  Each non-null array receives: plane = tlx, tly, pw, ph of the frame's image plane
+ * (pixel (x, y) under jitter offset (ox, oy) looks through jx = tlx + (x + ox) pw, jy = tly - (y - oy) ph); heads = one word per active block,
+ * 0xFFFFFFFF (the block walks the tree) or first entry << 7 | count; pos_block = the block of the frame's pixel list behind each active block;
+ * entries = 6 words each: the triangle's record, its list index (tri_orig), and its rectangle x0, x1, y0, y1 in (jx, jy) as floats. */
+int32_t ft_debug_block_lists(ft_context* ctx, int64_t sizes[4], double plane[4], uint32_t* heads, uint32_t* pos_block, uint32_t* entries);
 /* HIP-event time per stage over the last ft_render: index 4 primary (bounce 0 fused: generate + closest + shade), 2 the later
  * bounces (one k_bounce per level; one bracket around them all, or with "timing" = 2 one per level), 3 resolve and 0 the rest (the
  * fill, classification) with "timing" = 2; otherwise 0 = everything that is not bracketed and 3 = 0.  Index 1 is unused. */
