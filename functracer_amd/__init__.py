@@ -65,7 +65,7 @@ def hip_lib():
         lib.ft_denoise.argtypes = _capi.DENOISE_SIGNATURE
         lib.ft_temporal_filter.restype, lib.ft_temporal_filter.argtypes = C.c_int32, _capi.TEMPORAL_FILTER_SIGNATURE
         lib.ft_quantise_rgba8.argtypes = [_capi.c_double_p, C.c_int64, C.POINTER(C.c_uint8)]
-        for name, res, args in _capi.PROGRESSIVE_SIGNATURES + _capi.TEMPORAL_SIGNATURES + _capi.MOTION_SIGNATURES:
+        for name, res, args in _capi.PROGRESSIVE_SIGNATURES + _capi.TEMPORAL_SIGNATURES + _capi.MOTION_SIGNATURES + _capi.DEFORM_SIGNATURES:
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _hip = lib
@@ -513,6 +513,18 @@ class Context(SceneBuilder):
         """ft_scene_commit_moved: commit a graph whose transforms alone changed since the last commit.  A temporal accumulation stays open
         and its history follows the moved leaves; a progressive accumulation ends."""
         self._check(self._lib.ft_scene_commit_moved(self._ctx))
+        self._progressive = None
+
+    # deforming meshes: a refit instead of a rebuild (include/functracer_hip.h) ------------------------
+    def set_mesh_triangles(self, node, tris):
+        """ft_sg_set_mesh_triangles: replace the vertices of the node `bsp_mesh(depth, tris)` returned (tris as there, the same count)."""
+        t = _capi.as_f64(tris).reshape(-1, 9)
+        self._check(self._lib.ft_sg_set_mesh_triangles(self._ctx, int(node), _capi.dptr(t), t.shape[0]))
+
+    def commit_deformed(self):
+        """ft_scene_commit_deformed: commit a graph whose mesh vertices alone changed since the last commit by refitting the trees on the
+        device.  A temporal accumulation stays open; a progressive accumulation ends."""
+        self._check(self._lib.ft_scene_commit_deformed(self._ctx))
         self._progressive = None
 
     def leaf_matrices(self):

@@ -112,6 +112,13 @@ MOTION_SIGNATURES = [
 ]
 
 
+# Deforming meshes (include/functracer_hip.h): new vertices for an existing bspMesh node, committed by a refit of its tree on the device.
+DEFORM_SIGNATURES = [
+    ("ft_sg_set_mesh_triangles", C.c_int32, [C.c_void_p, C.c_int32, c_double_p, C.c_int64]),
+    ("ft_scene_commit_deformed", C.c_int32, [C.c_void_p]),
+]
+
+
 # ft_debug_mesh_trees (include/functracer_hip.h): the mesh trees as they lie in HBM, for the tests' structure checker.
 MESH_TREES_SIGNATURE = [C.c_void_p, C.POINTER(C.c_int64)] + [C.c_void_p] * 9
 BSP_NODE_DTYPE = np.dtype([("bmin", np.float64, 3), ("bmax", np.float64, 3), ("left", np.int32), ("right", np.int32), ("axis", np.uint32), ("pad", np.uint32)])

@@ -148,7 +148,7 @@ void ft_destroy(ft_context* c) {
         for (DeviceBuf& b : c->d_acc) b.release();
         for (DeviceBuf* b : {&c->d_out, &c->d_out8, &c->d_out_index, &c->d_pixels, &c->d_jitter, &c->d_wave_counts, &c->d_dbg_in, &c->d_dbg_out}) b->release();
         for (auto& f : c->slots) f.release();
-        c->prog.release(); c->aov.release(); c->denoise.release(); c->temporal.release();   // what the features own
+        c->prog.release(); c->aov.release(); c->denoise.release(); c->temporal.release(); c->refit.release();   // what the features own
         if (c->classified) (void)hipEventDestroy(c->classified);
         for (hipEvent_t& e : c->acc_free) if (e) { (void)hipEventDestroy(e); e = nullptr; }
         if (c->side) (void)hipStreamDestroy(c->side);
@@ -203,12 +203,12 @@ int32_t ft_set_option(ft_context* c, const char* key, int64_t value) {
         if (std::strcmp(key, o.key)) continue;
         if (o.rules & kFlag) value = value != 0;
         else if (value < o.lo || value > o.hi || ((o.rules & kPowerOfTwo) && (value & (value - 1)))) return FT_ERR_INVALID;
-        if (o.to_graph) { o.to_graph(c->graph, value); c->committed = false; return FT_OK; }
+        if (o.to_graph) { o.to_graph(c->graph, value); c->committed = false; c->options_pending = true; return FT_OK; }
         for (ft_context* d : devices(c)) {
             d->opt.*o.field = value;
             for (hipStream_t m : d->more_mains) if (!m) d->opt.mains = 1;   // (without them every frame takes the one main stream)
             d->dev_scene.coherent_waves = d->opt.coherent_waves ? 1 : 0;
-            if (o.rules & kCommit) d->committed = false;
+            if (o.rules & kCommit) { d->committed = false; c->options_pending = true; }
             if (o.rules & kLevelHint) d->staged_hint = -1;
             if (o.rules & kZeroFill) d->zero_signature[0] = d->zero_signature[1] = 0;
         }
@@ -248,6 +248,19 @@ int32_t ft_sg_set_transform(ft_context* c, ft_node node, const ft_transform* ts,
     if (!ts || n_ts < 1) { c->err = "ft_sg_set_transform: no transforms"; return FT_ERR_INVALID; }
     for (int i = 0; i < n_ts; ++i) if (ts[i].kind < FT_TRANSLATE || ts[i].kind > FT_ROTATE) { c->err = "ft_sg_set_transform: bad transform kind"; return FT_ERR_INVALID; }
     c->graph.nodes[node].xf.assign(ts, ts + n_ts);
+    c->committed = false; c->moved_pending = true;
+    return FT_OK;
+}
+// The vertices of an existing mesh node replaced; the count stays.  Not a structural change either: the graph flattens to the same leaves
+// over the same meshes, which is what ft_scene_commit_deformed needs.
+int32_t ft_sg_set_mesh_triangles(ft_context* c, ft_node node, const double* tris, int64_t n_tris) {
+    if (!c) return FT_ERR_INVALID;
+    if (!c->graph.valid(node) || c->graph.nodes[node].kind != fth::GraphNode::Mesh) { c->err = "ft_sg_set_mesh_triangles: not a bspMesh node"; return FT_ERR_INVALID; }
+    if (!tris) { c->err = "ft_sg_set_mesh_triangles: no triangles"; return FT_ERR_INVALID; }
+    fth::GraphNode& n = c->graph.nodes[node];
+    if (n_tris < 0 || (uint64_t)n_tris != n.tris.size() / 9) { c->err = "ft_sg_set_mesh_triangles: the triangle count differs from the node's"; return FT_ERR_INVALID; }
+    n.tris.assign(tris, tris + 9 * n_tris);
+    n.deformed = true;
     c->committed = false;
     return FT_OK;
 }
@@ -333,6 +346,19 @@ static int32_t lds_fits(ft_context* c) {
     return FT_ERR_UNSUPPORTED;
 }
 
+// What d_scene[kCullItems] holds: the items' float records and, behind them, a float image of every parallel-sensitive direction (x, y, z,
+// its length rounded up), which lane k of a coherent wave tests against the bundle's cone before any ray is tested against it exactly
+// (rows_nearly_parallel, ft_kernels.hip).
+static void cull_items_image(const fth::FlatScene& f, std::vector<float>& v) {
+    v = f.cull_items;
+    v.resize(8 * (f.item_pc.size() - 1), 0.0f);
+    for (size_t k = 0; k + 2 < f.cull_rows.size(); k += 3) {
+        const double len = std::sqrt(f.cull_rows[k] * f.cull_rows[k] + f.cull_rows[k + 1] * f.cull_rows[k + 1] + f.cull_rows[k + 2] * f.cull_rows[k + 2]);
+        float lf = (float)len; while ((double)lf < len) lf = std::nextafter(lf, std::numeric_limits<float>::infinity());
+        v.push_back((float)f.cull_rows[k]); v.push_back((float)f.cull_rows[k + 1]); v.push_back((float)f.cull_rows[k + 2]); v.push_back(lf);
+    }
+}
+
 static int32_t upload_scene(ft_context* c) {
     int32_t rc;
     FT_HIP(c, hipSetDevice(c->device));
@@ -340,6 +366,7 @@ static int32_t upload_scene(ft_context* c) {
     if (any_pending(c)) { if ((rc = retire_pending(c, nullptr)) != FT_OK) return rc; c->accum_open = false; }
     const fth::FlatScene& f = c->flat;
     if ((rc = lds_fits(c)) != FT_OK) return rc;
+    c->refit.ready = false;                                         // the trees these uploads bring are not the ones its tables describe
     ftk::DevScene& S = c->dev_scene;
     rc = FT_OK;
     auto put = [&](SceneArray k, const auto& v, auto*& ptr) {   // array k into its buffer, and the device scene's pointer to it
@@ -350,18 +377,8 @@ static int32_t upload_scene(ft_context* c) {
     put(kTextures, f.textures, S.textures); put(kTexPixels, f.tex_pixels, S.tex_pixels); put(kProgram, f.program, S.program);
     put(kMeshes, f.meshes, S.meshes); put(kNodes, f.nodes, S.nodes); put(kBspLeaves, f.bsp_leaves, S.bsp_leaves); put(kTris, f.tris, S.tris);
     put(kCulls, f.culls, S.culls);
-    {   // behind the items' float records: a float image of every parallel-sensitive direction (x, y, z, its length rounded up), which lane k of a
-        // coherent wave tests against the bundle's cone before any ray is tested against it exactly (rows_nearly_parallel, ft_kernels.hip)
-        std::vector<float>& v = c->cull_items_and_rows;
-        v = f.cull_items;
-        v.resize(8 * (f.item_pc.size() - 1), 0.0f);
-        for (size_t k = 0; k + 2 < f.cull_rows.size(); k += 3) {
-            const double len = std::sqrt(f.cull_rows[k] * f.cull_rows[k] + f.cull_rows[k + 1] * f.cull_rows[k + 1] + f.cull_rows[k + 2] * f.cull_rows[k + 2]);
-            float lf = (float)len; while ((double)lf < len) lf = std::nextafter(lf, std::numeric_limits<float>::infinity());
-            v.push_back((float)f.cull_rows[k]); v.push_back((float)f.cull_rows[k + 1]); v.push_back((float)f.cull_rows[k + 2]); v.push_back(lf);
-        }
-        put(kCullItems, v, S.cull_items);
-    }
+    cull_items_image(f, c->cull_items_and_rows);
+    put(kCullItems, c->cull_items_and_rows, S.cull_items);
     put(kCullRows, f.cull_rows, S.cull_rows); put(kItemPc, f.item_pc, S.item_pc); put(kWide, f.wide, S.wide); put(kMeshWide, f.mesh_wide, S.mesh_wide);
     put(kCoarse, f.coarse_boxes, S.coarse_boxes); put(kTriOrig, f.tri_orig, S.tri_orig);
     put(kLsPairs, f.ls_pairs, S.ls_pairs); put(kLsNodes, f.ls_nodes, S.ls_nodes); put(kLsTris, f.ls_tris, S.ls_tris);
@@ -420,7 +437,10 @@ int32_t commit_scene(ft_context* c) {
     auto ms_since = [](clock::time_point t0) { return std::chrono::duration<double, std::milli>(clock::now() - t0).count(); };
     for (double& v : c->commit_ms) v = 0.0;
     c->holds_commit = false;                                        // `flat` is being replaced
-    const auto done = [c](int32_t rc) { if (rc == FT_OK) { c->holds_commit = true; c->restructured = false; } return rc; };
+    const auto done = [c](int32_t rc) {
+        if (rc == FT_OK) { c->holds_commit = true; c->restructured = false; c->moved_pending = false; c->options_pending = false; for (fth::GraphNode& n : c->graph.nodes) n.deformed = false; }
+        return rc;
+    };
     // A device context builds the exact BVH of top-level-Leaf meshes on the device ("bvh_builder" = 1; 2, the default: from 4096 triangles on): the flattener
     // reserves the ranges, upload_scene fills them.  A build the device refuses (a tree too deep for the traversal stacks) falls
     // back to the host's builder, once, for the whole scene.
@@ -447,6 +467,84 @@ int32_t commit_scene(ft_context* c) {
     return FT_ERR_BUILD;
 }
 
+// ------------------------------------------------------------------------------------------ refit (ft_scene_commit_deformed)
+// One edited mesh of the held scene: its index, its builder node and what one pass over the new vertices gave.
+struct DeformedMesh { uint32_t mesh; int32_t node; fth::MeshScan scan; };
+
+static ftk::RefitMesh refit_ranges(const fth::FlatScene& f, uint32_t mesh, double pad) {
+    const ftd::Mesh& M = f.meshes[mesh];
+    const fth::FlatScene::MeshRange& r = f.mesh_ranges[mesh];
+    ftk::RefitMesh m{};
+    m.first_global = f.bsp_leaves[(size_t)~M.root].first_tri; m.n = f.bsp_leaves[(size_t)~M.root].n_tris;
+    m.node_first = r.node_first; m.node_count = r.node_count; m.leaf_first = r.leaf_first; m.leaf_count = r.leaf_count;
+    m.tri_first = r.tri_first; m.tri_count = r.tri_count; m.wide_first = r.wide_first; m.wide_count = r.wide_count;
+    m.bvh_root = M.bvh_root;
+    for (const fth::FlatScene::BvhJob& j : f.bvh_jobs) if (j.mesh == mesh) m.device_built = 1u;
+    m.coarse_first = f.mesh_coarse[2 * mesh]; m.coarse_count = f.mesh_coarse[2 * mesh + 1];
+    m.pad = pad;
+    return m;
+}
+
+// The refit of `edits` on one device of the context: `f` is the held scene with the new cull records and leaves already in it, `g` the
+// graph with the new vertices.  ms[0] += uploads and the rest, ms[1] += the kernels.
+static int32_t refit_device(ft_context* c, const fth::FlatScene& f, const fth::SceneGraph& g, const std::vector<DeformedMesh>& edits, double ms[2]) {
+    using clock = std::chrono::steady_clock;
+    auto since = [](clock::time_point t0) { return std::chrono::duration<double, std::milli>(clock::now() - t0).count(); };
+    int32_t rc;
+    FT_HIP(c, hipSetDevice(c->device));
+    const auto t0 = clock::now();
+    // frames still queued trace the scene this refit rewrites (as upload_scene)
+    if (any_pending(c)) { if ((rc = retire_pending(c, nullptr)) != FT_OK) return rc; c->accum_open = false; }
+    if ((rc = drain_frame_streams(c)) != FT_OK) return rc;
+    if (c->side) FT_HIP(c, hipStreamSynchronize(c->side));
+    ft_context::Refit& R = c->refit;
+    DeviceBuf* B = c->d_scene;
+    const bool first = !R.ready;
+    if (first) {
+        if ((rc = ensure(c, R.d_parent_node, f.nodes.size() * 4)) != FT_OK || (rc = ensure(c, R.d_arrived, f.nodes.size() * 4)) != FT_OK ||
+            (rc = ensure(c, R.d_parent_leaf, f.bsp_leaves.size() * 4)) != FT_OK || (rc = ensure(c, R.d_leaf_boxes, f.bsp_leaves.size() * 48)) != FT_OK ||
+            (rc = upload(c, R.d_wide_node, f.wide_node)) != FT_OK) return rc;
+        FT_HIP(c, hipMemsetAsync(R.d_parent_node.p, 0xFF, R.d_parent_node.bytes, c->stream));
+        FT_HIP(c, hipMemsetAsync(R.d_parent_leaf.p, 0xFF, R.d_parent_leaf.bytes, c->stream));
+    }
+    const ftk::RefitArrays A{B[kTris].as<double>(), B[kNodes].as<ftd::BspNode>(), B[kBspLeaves].as<ftd::BspLeaf>(), B[kTriOrig].as<uint32_t>(), B[kWide].as<double>(),
+                             B[kCoarse].as<float>(), R.d_wide_node.as<int32_t>(), R.d_parent_node.as<int32_t>(), R.d_parent_leaf.as<int32_t>(), R.d_arrived.as<uint32_t>(),
+                             R.d_leaf_boxes.as<double>()};
+    size_t n_verts = 0;
+    for (const DeformedMesh& e : edits) n_verts += g.nodes[(size_t)e.node].tris.size();
+    if ((rc = ensure(c, R.d_verts, n_verts * 8)) != FT_OK) return rc;
+    size_t at = 0;
+    for (const DeformedMesh& e : edits) {
+        const std::vector<double>& v = g.nodes[(size_t)e.node].tris;
+        if (!v.empty()) FT_HIP(c, hipMemcpyAsync(R.d_verts.as<double>() + at, v.data(), v.size() * 8, hipMemcpyHostToDevice, c->stream));
+        at += v.size();
+    }
+    if ((rc = upload(c, B[kLeaves], f.leaves)) != FT_OK || (rc = upload(c, B[kCulls], f.culls)) != FT_OK) return rc;
+    cull_items_image(f, c->cull_items_and_rows);
+    if ((rc = upload(c, B[kCullItems], c->cull_items_and_rows)) != FT_OK) return rc;
+    FT_HIP(c, hipStreamSynchronize(c->stream));
+    ms[0] += since(t0);
+    const auto t1 = clock::now();
+    if (first) {
+        for (uint32_t k = 0; k < (uint32_t)f.meshes.size(); ++k) if (f.meshes[k].root < 0 && f.meshes[k].bvh_root != INT32_MIN) ftk::refit_parents(c->stream, A, refit_ranges(f, k, 0.0));
+        R.ready = true;
+    }
+    at = 0;
+    for (const DeformedMesh& e : edits) {
+        const ftk::RefitMesh m = refit_ranges(f, e.mesh, 1e-7 * e.scan.extent + 1e-300);
+        if (m.node_count) FT_HIP(c, hipMemsetAsync(R.d_arrived.as<uint32_t>() + m.node_first, 0, (size_t)m.node_count * 4, c->stream));
+        ftk::refit_mesh(c->stream, A, m, R.d_verts.as<double>() + at);
+        at += 9 * (size_t)m.n;
+    }
+    FT_HIP(c, hipGetLastError());
+    FT_HIP(c, hipStreamSynchronize(c->stream));
+    ms[1] += since(t1);
+    c->zero_signature[0] = c->zero_signature[1] = 0;                // the blocks k_classify finishes are another scene's
+    c->committed = true;
+    ++c->commit_serial; c->staged_hint = -1;
+    return FT_OK;
+}
+
 } // namespace ftc
 
 extern "C" {
@@ -470,6 +568,61 @@ int32_t ft_scene_commit_moved(ft_context* c) {
     const int32_t rc = commit_scene(c);
     if (rc == FT_OK) ++c->pose_serial;
     return rc;
+}
+
+// The commit of a graph whose mesh vertices alone changed (ft_sg_set_mesh_triangles): the trees keep their topology and are refit on the
+// device (ft_refit.hip); the temporal accumulation stays open and the pose counter stays, a progressive accumulation ends.
+int32_t ft_scene_commit_deformed(ft_context* c) {
+    if (!c) return FT_ERR_INVALID;
+    if (!c->holds_commit) { c->err = "ft_scene_commit_deformed: no committed scene to deform (ft_scene_commit)"; return FT_ERR_STATE; }
+    if (c->restructured) { c->err = "ft_scene_commit_deformed: the graph, the root or the lights changed since the commit (ft_scene_commit)"; return FT_ERR_STATE; }
+    if (c->moved_pending) { c->err = "ft_scene_commit_deformed: an ft_sg_set_transform is pending (ft_scene_commit_moved first)"; return FT_ERR_STATE; }
+    if (c->options_pending) { c->err = "ft_scene_commit_deformed: a commit-time option changed since the commit (ft_scene_commit)"; return FT_ERR_STATE; }
+    using clock = std::chrono::steady_clock;
+    const auto t0 = clock::now();
+    fth::FlatScene& f = c->flat;
+    // Host: one pass over every edited mesh - bounds, extent, finiteness - before anything is changed or uploaded.
+    std::vector<DeformedMesh> edits;
+    for (uint32_t m = 0; m < (uint32_t)f.meshes.size(); ++m) {
+        const int32_t id = f.mesh_node[m];
+        if (id < 0 || !c->graph.valid(id) || !c->graph.nodes[(size_t)id].deformed) continue;
+        const fth::GraphNode& n = c->graph.nodes[(size_t)id];
+        const bool refuse_depth = n.depth > 0 && !c->graph.mesh_unclipped_bvh;
+        const fth::MeshScan scan = refuse_depth ? fth::MeshScan{} : fth::scan_mesh(n.tris.data(), (int64_t)(n.tris.size() / 9));
+        if (refuse_depth || !scan.finite || f.meshes[m].root >= 0) {
+            c->err = refuse_depth || f.meshes[m].root >= 0 ? "ft_scene_commit_deformed: an edited mesh has depth above 0 - its clipped BSP depends on the positions (ft_scene_commit)"
+                                                            : "ft_scene_commit_deformed: an edited mesh holds a non-finite coordinate (ft_scene_commit)";
+            c->committed = true;                                     // the old commit stays in HBM and stays renderable
+            return FT_ERR_UNSUPPORTED;
+        }
+        edits.push_back(DeformedMesh{m, id, scan});
+    }
+    if (c->host_only) {                                             // the same rules; the commit itself is the full one
+        progressive_close(c);
+        return commit_scene(c);
+    }
+    std::vector<double> bounds = f.mesh_bounds;
+    for (const DeformedMesh& e : edits) for (int k = 0; k < 6; ++k) bounds[6 * (size_t)e.mesh + k] = e.scan.bounds[k];
+    int32_t rc = c->graph.reflatten_deformed(f, bounds, c->err);   // the cull records, by the flattener's own walk
+    if (rc != FT_OK) { if (rc == FT_ERR_UNSUPPORTED) c->committed = true; return rc; }
+    // The light-space structures are built from the vertices and are not refit: the directional shadow rays of an edited mesh walk its
+    // BVH (the same bits, include/functracer_hip.h "light_space_shadows") until the next full commit brings them back.
+    std::vector<bool> edited(f.meshes.size(), false);
+    for (const DeformedMesh& e : edits) edited[e.mesh] = true;
+    for (ftd::Leaf& L : f.leaves) if (L.kind == ftd::LK_MESH && L.mesh < edited.size() && edited[L.mesh]) L.ls_pairs = ~0u;
+    progressive_close(c);
+    const double tallest = c->commit_ms[3];
+    for (double& v : c->commit_ms) v = 0.0;
+    c->commit_ms[3] = tallest;
+    c->commit_ms[0] = std::chrono::duration<double, std::milli>(clock::now() - t0).count();
+    double ms[2] = {0.0, 0.0};
+    for (ft_context* d : devices(c)) {                              // every device refits its own copy
+        if ((rc = refit_device(d, f, c->graph, edits, ms)) != FT_OK) { if (d != c) c->err = d->err; break; }
+    }
+    c->commit_ms[1] = ms[1]; c->commit_ms[2] = ms[0];
+    if (rc != FT_OK) { for (ft_context* d : devices(c)) d->committed = false; c->holds_commit = false; return rc; }   // HBM holds neither scene whole: ft_scene_commit
+    for (fth::GraphNode& n : c->graph.nodes) n.deformed = false;
+    return FT_OK;
 }
 
 int32_t ft_get_commit_times(ft_context* c, double ms[4]) {

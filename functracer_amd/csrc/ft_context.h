@@ -158,6 +158,9 @@ struct ft_context {
     // What ft_scene_commit_moved asks for: `flat` is a successful commit's, and no builder call since has added a node, changed the root
     // or the lights, or cleared the graph (ft_sg_set_transform and ft_set_option have not) - the same leaves in the same order.
     bool holds_commit = false, restructured = false;
+    // What ft_scene_commit_deformed asks for on top of that: no ft_sg_set_transform and no commit-time option waiting for a full commit
+    // (both cleared by every successful full commit).
+    bool moved_pending = false, options_pending = false;
     uint64_t pose_serial = 0;       // advanced by ft_scene_commit_moved only (commit_serial also by the hit lists' re-commit, which moves nothing)
     double commit_ms[4] = {0, 0, 0, 0};   // last ft_scene_commit: flatten on the host, device BVH builds, uploads + the rest, BVH height (not a time)
 
@@ -221,6 +224,13 @@ struct ft_context {
         }
     };
     FrameSlot slots[kSlots];
+    // ft_scene_commit_deformed's own tables in HBM (ftk::RefitArrays), made by the first refit after a full commit and kept until the next
+    // one (`ready`); d_verts: the new vertices of the meshes being refit.
+    struct Refit {
+        DeviceBuf d_verts, d_parent_node, d_parent_leaf, d_arrived, d_leaf_boxes, d_wide_node;
+        bool ready = false;
+        void release() { for (DeviceBuf* b : {&d_verts, &d_parent_node, &d_parent_leaf, &d_arrived, &d_leaf_boxes, &d_wide_node}) b->release(); ready = false; }
+    } refit;
     int slot_turn = 0;
     int last_classified_slot = -1;   // the slot of the last classified frame queued (ft_debug_block_lists)
     // Levels of the reflection tree worth launching: the host cannot know how deep the rays of a frame go without waiting, and a

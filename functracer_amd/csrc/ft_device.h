@@ -208,6 +208,29 @@ struct LbvhTarget {
 };
 hipError_t build_lbvh(hipStream_t stream, const LbvhTarget& t, uint32_t* height, int kind = 1);   // kind 0: linear BVH, 1: binned surface-area tree over the Morton order
 
+// Refit of a mesh whose vertices changed (ft_refit.hip, ft_scene_commit_deformed): the topology every builder left in the scene's arrays
+// stays, the triangle records and every box over them are written again.  RefitArrays: the scene's arrays in HBM and the refit's own
+// tables, all indexed as the scene's - parent_node / arrived per BspNode, parent_leaf / leaf_boxes (6 doubles) per BspLeaf, wide_node per
+// 4-wide node (the binary node it is two levels of).  RefitMesh: one mesh's ranges (fth::FlatScene::MeshRange); device_built: the ranges
+// are a device job's, where binary node i also exists as BspLeaf leaf_first + i and only those of more than four triangles are nodes of
+// the tree; pad: the builders' inflation for the new vertices, 1e-7 * extent + 1e-300.
+struct RefitArrays {
+    double* tris; ftd::BspNode* nodes; const ftd::BspLeaf* leaves; const uint32_t* tri_orig; double* wide; float* coarse;
+    const int32_t* wide_node; int32_t* parent_node; int32_t* parent_leaf; uint32_t* arrived; double* leaf_boxes;
+};
+struct RefitMesh {
+    uint32_t first_global, n;
+    uint32_t node_first, node_count, leaf_first, leaf_count, tri_first, tri_count, wide_first, wide_count;
+    int32_t bvh_root;                  // INT32_MIN: the mesh has no BVH - its records alone are written
+    uint32_t device_built;
+    uint32_t coarse_first, coarse_count;
+    double pad;
+};
+// The parent of every node and leaf of the mesh's tree, once per full commit (the tables must hold -1 in the mesh's ranges before).
+void refit_parents(hipStream_t stream, const RefitArrays& A, const RefitMesh& m);
+// verts: the mesh's new vertices in HBM, n x 9 doubles (a, b, c).  Records and sorted copies, boxes leaves to root, 4-wide slots, coarse boxes.
+void refit_mesh(hipStream_t stream, const RefitArrays& A, const RefitMesh& m, const double* verts);
+
 // Per-pixel surface buffers (ft_render_aov): for every entry of the chunk's pixel list (gen: pix_base, n_pix; one sample plane) the
 // closest hit of the geometry ray of sample `sample` - primary_ray_from exactly as k_primary calls it, then slightOffset - and what
 // the shaders would see there.  Planes are struct-of-arrays by list position: out.<x>[i] for entry pix_base + i, the 3-vectors as

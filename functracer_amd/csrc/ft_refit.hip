@@ -1,0 +1,186 @@
+// ft_refit.hip — the BVH of a top-level-Leaf mesh refit ON THE DEVICE after its vertices changed (ft_scene_commit_deformed).
+// The tree any builder left in the scene's arrays - the host's swept surface-area split (ft_scene.cpp, BspBuilder::bvh_build) or one of
+// ft_bvh.hip's - keeps its topology: left / right / axis, the leaf ranges, tri_orig, tri_src, the 4-wide children, the coarse frontier.
+// What depends on the positions is written again, so that the tree still (a) holds every triangle once, (b) bounds them with inflated
+// boxes and (c) breaks ties by list index: the three properties that make it give the linear scan's hits bit for bit (ft_flat.h).
+//
+// Stages (all on the context's stream; n = triangles of the mesh):
+//   k_refit_parents  once per full commit: the parent of every node and leaf of the tree, read off the emitted left / right
+//   k_refit_records  per list-order triangle v0, e1 = v1 - v0, e2 = v2 - v0 (the flattener's subtraction); per sorted copy the same
+//                    arithmetic on its tri_orig's vertices, hence a bitwise copy of that record
+//   k_refit_fit      per leaf its box from (v0, v0 + e1, v0 + e2) - what the hit test reads, as k_bvh_prepare - inflated; then leaves to
+//                    root as k_bvh_fit: the second child to arrive unites the boxes.  Inflating commutes with min / max (x - pad is
+//                    monotone in x), so a node's stored box is the exact bound of its triangles, inflated: what every builder stores
+//   k_refit_wide     per 4-wide node the inflated boxes of what its slots point to; empty slots stay all-NaN
+//   k_refit_coarse   one thread: the level of the tree with at most 64 nodes (the rule both builders use), as float boxes rounded outward
+#include <hip/hip_runtime.h>
+
+#include <math.h>
+#include <stdint.h>
+
+#include "ft_device.h"
+
+using namespace ftd;
+
+namespace ftk {
+namespace {
+
+constexpr uint32_t kLeafTris = 4;                                   // as the builders
+
+__device__ __forceinline__ bool node_in(const RefitMesh& m, int32_t r) { return r >= 0 && (uint32_t)r >= m.node_first && (uint32_t)r - m.node_first < m.node_count; }
+__device__ __forceinline__ bool leaf_in(const RefitMesh& m, int32_t r) { return r < 0 && r != INT32_MIN && (uint32_t)~r >= m.leaf_first && (uint32_t)~r - m.leaf_first < m.leaf_count; }
+// Node r of the mesh's range is a node of its tree.  A device job wrote a record for every node of its build, and lets those of at most
+// four triangles stand as leaves (ft_bvh.hip, scene_ref): build node i is also BspLeaf leaf_first + i, which holds its triangle count
+// (0 where the surface-area builder made fewer nodes than the range has room for).
+__device__ __forceinline__ bool real_node(const RefitArrays& A, const RefitMesh& m, uint32_t r) {
+    return !m.device_built || A.leaves[m.leaf_first + (r - m.node_first)].n_tris > kLeafTris;
+}
+
+__global__ __launch_bounds__(256) void k_refit_parents(RefitArrays A, RefitMesh m) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= m.node_count) return;
+    const uint32_t r = m.node_first + i;
+    if (!real_node(A, m, r)) return;
+    const int32_t ch[2] = {A.nodes[r].left, A.nodes[r].right};
+    for (int c = 0; c < 2; ++c) {
+        if (node_in(m, ch[c])) A.parent_node[ch[c]] = (int32_t)r;
+        else if (leaf_in(m, ch[c])) A.parent_leaf[~ch[c]] = (int32_t)r;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_refit_records(RefitArrays A, RefitMesh m, const double* __restrict__ verts) {
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= m.n + m.tri_count) return;
+    uint32_t dst = m.first_global + t, src = t;
+    if (t >= m.n) {                                                 // a sorted copy: its list-order triangle's vertices
+        dst = m.tri_first + (t - m.n);
+        src = A.tri_orig[dst] - m.first_global;
+        if (src >= m.n) return;
+    }
+    const double* V = verts + 9ull * src;
+    double* O = A.tris + 9ull * dst;
+    for (int a = 0; a < 3; ++a) { O[a] = V[a]; O[3 + a] = V[3 + a] - V[a]; O[6 + a] = V[6 + a] - V[a]; }
+}
+
+// The inflated box of leaf `l` (an index into the scene's BspLeaf array), or false when it is no leaf of the tree's size.
+__device__ __forceinline__ bool leaf_box(const RefitArrays& A, const RefitMesh& m, uint32_t l, double box[6]) {
+    const BspLeaf L = A.leaves[l];
+    if (L.n_tris == 0u || L.n_tris > kLeafTris || L.first_tri < m.tri_first || L.first_tri - m.tri_first + L.n_tris > m.tri_count) return false;
+    for (int a = 0; a < 3; ++a) { box[a] = __builtin_inf(); box[3 + a] = -__builtin_inf(); }
+    for (uint32_t k = 0; k < L.n_tris; ++k) {
+        const double* T = A.tris + 9ull * (L.first_tri + k);
+        for (int a = 0; a < 3; ++a) {
+            const double v0 = T[a], v1 = T[a] + T[3 + a], v2 = T[a] + T[6 + a];
+            box[a] = fmin(box[a], fmin(v0, fmin(v1, v2))); box[3 + a] = fmax(box[3 + a], fmax(v0, fmax(v1, v2)));
+        }
+    }
+    for (int a = 0; a < 3; ++a) { box[a] = box[a] - m.pad; box[3 + a] = box[3 + a] + m.pad; }
+    return true;
+}
+
+__global__ __launch_bounds__(256) void k_refit_fit(RefitArrays A, RefitMesh m) {
+    const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+    if (j >= m.leaf_count) return;
+    const uint32_t l = m.leaf_first + j;
+    double box[6];
+    if (!leaf_box(A, m, l, box)) return;
+    for (int k = 0; k < 6; ++k) A.leaf_boxes[6ull * l + k] = box[k];
+    if (m.device_built && j < m.node_count) {                       // a build node standing as a leaf: its BspNode record holds the same box
+        BspNode* nd = A.nodes + (m.node_first + j);
+        for (int a = 0; a < 3; ++a) { nd->bmin[a] = box[a]; nd->bmax[a] = box[3 + a]; }
+    }
+    int32_t node = A.parent_leaf[l];
+    while (node_in(m, node)) {
+        __threadfence();                                            // this thread's box of the child below is visible before the counter moves
+        if (atomicAdd(&A.arrived[node], 1u) == 0u) return;          // the sibling subtree is not done yet: its thread carries on from here
+        __threadfence();
+        double lo[3], hi[3];
+        const int32_t ch[2] = {A.nodes[node].left, A.nodes[node].right};
+        for (int c = 0; c < 2; ++c) {
+            if (!(node_in(m, ch[c]) || leaf_in(m, ch[c]))) return;
+            const volatile double* b = ch[c] >= 0 ? A.nodes[ch[c]].bmin : A.leaf_boxes + 6ull * (uint32_t)~ch[c];   // (bmin, bmax: six doubles in a row)
+            for (int a = 0; a < 3; ++a) { const double lw = b[a], up = b[3 + a]; lo[a] = c == 0 ? lw : fmin(lo[a], lw); hi[a] = c == 0 ? up : fmax(hi[a], up); }
+        }
+        for (int a = 0; a < 3; ++a) { A.nodes[node].bmin[a] = lo[a]; A.nodes[node].bmax[a] = hi[a]; }
+        node = A.parent_node[node];
+    }
+}
+
+// The inflated box of what a reference of the tree points to: a node's record, a leaf's entry of leaf_boxes.
+__device__ __forceinline__ bool ref_box(const RefitArrays& A, const RefitMesh& m, int32_t ref, double* out) {
+    const double* b;
+    if (node_in(m, ref)) b = A.nodes[ref].bmin;
+    else if (leaf_in(m, ref)) b = A.leaf_boxes + 6ull * (uint32_t)~ref;
+    else return false;
+    for (int k = 0; k < 6; ++k) out[k] = b[k];
+    return true;
+}
+
+__global__ __launch_bounds__(256) void k_refit_wide(RefitArrays A, RefitMesh m) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= m.wide_count) return;
+    const uint32_t w = m.wide_first + i;
+    const int32_t b = A.wide_node[w];
+    if (!node_in(m, b) || !real_node(A, m, (uint32_t)b)) return;
+    double* W = A.wide + (unsigned long long)kWideNodeDoubles * w;
+    const int32_t halves[2] = {A.nodes[b].left, A.nodes[b].right};
+    for (int h = 0; h < 2; ++h) {                                   // the slots as widen / k_bvh_emit fill them: a leaf takes one slot of its half
+        const int32_t c = halves[h];
+        if (c < 0) { ref_box(A, m, c, W + 6 * (2 * h)); continue; }
+        if (!node_in(m, c)) continue;
+        const int32_t gk[2] = {A.nodes[c].left, A.nodes[c].right};
+        for (int k = 0; k < 2; ++k) ref_box(A, m, gk[k], W + 6 * (2 * h + k));
+    }
+}
+
+__device__ __forceinline__ float round_down(double v) { float f = (float)v; if ((double)f > v) f = __uint_as_float(f > 0.0f ? __float_as_uint(f) - 1u : (f < 0.0f ? __float_as_uint(f) + 1u : 0x80000001u)); return f; }
+__device__ __forceinline__ float round_up(double v) { return -round_down(-v); }
+// The frontier both builders take (build_bsp, k_bvh_coarse): levels of the tree as long as the next one has at most 64 entries; the
+// same `count` boxes, the last one repeated where the frontier is shorter; k_bvh_coarse's outward rounding, here of the inflated boxes.
+__global__ void k_refit_coarse(RefitArrays A, RefitMesh m) {
+    __shared__ int32_t frontier[2][64];
+    if (threadIdx.x != 0 || m.coarse_count == 0u || !(node_in(m, m.bvh_root) || leaf_in(m, m.bvh_root))) return;
+    int cur = 0; uint32_t nf = 1;
+    frontier[0][0] = m.bvh_root;
+    for (;;) {
+        uint32_t nn = 0; bool any_inner = false, fits = true;
+        for (uint32_t k = 0; k < nf; ++k) {
+            const int32_t c = frontier[cur][k];
+            const bool inner = node_in(m, c);
+            if (nn + (inner ? 2u : 1u) > 64u) { fits = false; break; }
+            if (!inner) { frontier[cur ^ 1][nn++] = c; continue; }
+            any_inner = true;
+            frontier[cur ^ 1][nn++] = A.nodes[c].left; frontier[cur ^ 1][nn++] = A.nodes[c].right;
+        }
+        if (!any_inner || !fits) break;
+        cur ^= 1; nf = nn;
+    }
+    for (uint32_t k = 0; k < m.coarse_count; ++k) {
+        double b[6];
+        if (!ref_box(A, m, frontier[cur][k < nf ? k : nf - 1u], b)) continue;
+        float* out = A.coarse + 6ull * (m.coarse_first + k);
+        for (int x = 0; x < 3; ++x) {
+            const double lo = b[x], hi = b[3 + x];
+            const double pad = 1e-5 * (fabs(lo) + fabs(hi) + (hi - lo)) + 1e-30;
+            out[x] = round_down(lo - pad); out[3 + x] = round_up(hi + pad);
+        }
+    }
+}
+
+} // namespace
+
+void refit_parents(hipStream_t stream, const RefitArrays& A, const RefitMesh& m) {
+    if (m.node_count == 0u) return;
+    hipLaunchKernelGGL(k_refit_parents, dim3((m.node_count + 255u) / 256u), dim3(256), 0, stream, A, m);
+}
+
+void refit_mesh(hipStream_t stream, const RefitArrays& A, const RefitMesh& m, const double* verts) {
+    if (m.n == 0u) return;
+    hipLaunchKernelGGL(k_refit_records, dim3((m.n + m.tri_count + 255u) / 256u), dim3(256), 0, stream, A, m, verts);
+    if (m.bvh_root == INT32_MIN || m.leaf_count == 0u) return;
+    hipLaunchKernelGGL(k_refit_fit, dim3((m.leaf_count + 255u) / 256u), dim3(256), 0, stream, A, m);
+    if (m.wide_count) hipLaunchKernelGGL(k_refit_wide, dim3((m.wide_count + 255u) / 256u), dim3(256), 0, stream, A, m);
+    if (m.coarse_count) hipLaunchKernelGGL(k_refit_coarse, dim3(1), dim3(64), 0, stream, A, m);
+}
+
+} // namespace ftk

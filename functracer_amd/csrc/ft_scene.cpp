@@ -102,6 +102,8 @@ struct Flattener {
     int cur_list = 0, max_list = 0;                  // static bound on the per-lane hit-list length
     std::vector<bool> leaf_bounds;                   // per leaf: its box is part of its item's bounds (WalkCtx::bounds)
     std::map<const GraphNode*, size_t> image_base;   // image texture node -> offset of its pixels in out.tex_pixels
+    const FlatScene* held = nullptr;                 // reflatten_deformed: the meshes are this scene's, in the same order, and are not built
+    const std::vector<double>* held_bounds = nullptr;
 
     Flattener(const SceneGraph& g_, FlatScene& o, std::string& e) : g(g_), out(o), err(e) {}
 
@@ -178,17 +180,34 @@ struct Flattener {
 
     uint32_t mesh_for(int32_t node_id, const double* tris, int64_t n, int32_t depth) {
         if (node_id >= 0) { auto it = mesh_of_node.find(node_id); if (it != mesh_of_node.end()) return it->second; }
+        if (held) {
+            const size_t at = out.meshes.size();
+            if (at >= held->meshes.size() || held->mesh_node[at] != node_id || held->meshes[at].n_source_tris != (uint32_t)n) { status = FT_ERR_UNSUPPORTED; err = "the graph no longer flattens to the held meshes"; return 0; }
+            out.meshes.push_back(held->meshes[at]);
+            out.mesh_bounds.insert(out.mesh_bounds.end(), held_bounds->begin() + 6 * (long)at, held_bounds->begin() + 6 * (long)at + 6);
+            if (node_id >= 0) mesh_of_node[node_id] = (uint32_t)at;
+            return (uint32_t)at;
+        }
         ftd::Mesh m{};
+        const size_t n0 = out.nodes.size(), l0 = out.bsp_leaves.size(), t0 = out.tris.size() / 9, w0 = out.wide.size() / ftd::kWideNodeDoubles;
         int32_t rc = build_bsp(tris, n, depth, out, m, err, g.device_bvh && n >= g.device_bvh_min_tris);
         if (rc != FT_OK) { status = rc; return 0; }
         out.meshes.push_back(m);
         {
-            const double inf = std::numeric_limits<double>::infinity();
-            double b[6] = {inf, inf, inf, -inf, -inf, -inf};
-            for (int64_t i = 0; i < 3 * n; ++i) for (int a = 0; a < 3; ++a) { double v = tris[3 * i + a]; if (v < b[a]) b[a] = v; if (v > b[3 + a]) b[3 + a] = v; }
-            out.mesh_bounds.insert(out.mesh_bounds.end(), b, b + 6);
+            const MeshScan s = scan_mesh(tris, n);
+            out.mesh_bounds.insert(out.mesh_bounds.end(), s.bounds, s.bounds + 6);
         }
         uint32_t idx = (uint32_t)out.meshes.size() - 1;
+        out.mesh_node.push_back(node_id);
+        {   // where its BVH went (FlatScene::MeshRange): a top-level Leaf's records come first, then the tree's
+            FlatScene::MeshRange r{};
+            if (m.root < 0 && m.bvh_root != INT32_MIN) {
+                const uint32_t own_tris = out.bsp_leaves[(size_t)~m.root].n_tris;
+                r = FlatScene::MeshRange{(uint32_t)n0, (uint32_t)(out.nodes.size() - n0), (uint32_t)l0 + 1u, (uint32_t)(out.bsp_leaves.size() - l0) - 1u,
+                                         (uint32_t)t0 + own_tris, (uint32_t)(out.tris.size() / 9 - t0) - own_tris, (uint32_t)w0, (uint32_t)(out.wide.size() / ftd::kWideNodeDoubles - w0)};
+            }
+            out.mesh_ranges.push_back(r);
+        }
         if (node_id >= 0) mesh_of_node[node_id] = idx;
         if ((int32_t)m.max_depth + 1 > out.stack_capacity && m.root >= 0) out.stack_capacity = (int32_t)m.max_depth + 1;
         if ((int32_t)m.max_depth + 1 > out.bsp_stack_capacity && m.root >= 0) out.bsp_stack_capacity = (int32_t)m.max_depth + 1;
@@ -429,6 +448,43 @@ struct Flattener {
 
 } // namespace
 
+MeshScan scan_mesh(const double* tris, int64_t n) {
+    const double inf = std::numeric_limits<double>::infinity();
+    MeshScan s{{inf, inf, inf, -inf, -inf, -inf}, 0.0, true};
+    for (int64_t i = 0; i < n; ++i) {
+        const double* T = tris + 9 * i;
+        for (int k = 0; k < 3; ++k) for (int a = 0; a < 3; ++a) { const double v = T[3 * k + a]; if (v < s.bounds[a]) s.bounds[a] = v; if (v > s.bounds[3 + a]) s.bounds[3 + a] = v; }
+        for (int a = 0; a < 3; ++a) {                               // as the hit test sees them (k_bvh_prepare): v0, v0 + e1, v0 + e2
+            const double v0 = T[a], v1 = T[a] + (T[3 + a] - T[a]), v2 = T[a] + (T[6 + a] - T[a]);
+            const double f[3] = {std::fabs(v0), std::fabs(v1), std::fabs(v2)};
+            for (double x : f) { if (!(x < 1e300)) s.finite = false; if (x > s.extent) s.extent = x; }
+            if (!(std::fabs(T[3 + a]) < 1e300) || !(std::fabs(T[6 + a]) < 1e300)) s.finite = false;   // (the host builder tests the vertices as given)
+        }
+    }
+    return s;
+}
+
+int32_t SceneGraph::reflatten_deformed(FlatScene& held, const std::vector<double>& bounds, std::string& err) const {
+    if (!valid(root) || bounds.size() != 6 * held.meshes.size() || held.mesh_node.size() != held.meshes.size()) { err = "no held scene to deform"; return FT_ERR_STATE; }
+    FlatScene out;
+    out.mesh_coarse = held.mesh_coarse;                             // end_item reads a bare mesh's coarse range
+    Flattener f(*this, out, err);
+    f.held = &held; f.held_bounds = &bounds;
+    WalkCtx c;
+    f.walk(root, c, false);
+    if (f.status != FT_OK) return f.status;
+    out.item_pc.push_back((uint32_t)out.program.size());
+    out.program.push_back(ftd::make_op(ftd::OP_END, 0));
+    if (out.culls.empty()) out.culls.push_back(ftd::CullRecord{});
+    // Everything but the bounds must be what it was: the same leaves, the same program over the same items, the same face directions.
+    const bool same = out.meshes.size() == held.meshes.size() && out.leaves.size() == held.leaves.size() && out.program == held.program && out.item_pc == held.item_pc &&
+                      out.culls.size() == held.culls.size() && out.cull_items.size() == held.cull_items.size() && out.cull_rows == held.cull_rows &&
+                      out.cull_bundle == held.cull_bundle && out.unbounded == held.unbounded;
+    if (!same) { err = "the deformed bounds change which items have bounds: ft_scene_commit rebuilds the scene"; return FT_ERR_UNSUPPORTED; }
+    held.mesh_bounds.swap(out.mesh_bounds); held.culls.swap(out.culls); held.cull_items.swap(out.cull_items);
+    return FT_OK;
+}
+
 int32_t SceneGraph::flatten(FlatScene& out, std::string& err) const {
     out = FlatScene();
     if (!valid(root)) { err = "scene has no objects (ft_scene_set_objects)"; return FT_ERR_STATE; }
@@ -617,6 +673,7 @@ struct BspBuilder {
     int32_t widen(int32_t n) {
         const size_t at = out.wide.size();
         out.wide.resize(at + ftd::kWideNodeDoubles, 0.0);
+        out.wide_node.push_back(n);
         int32_t child[4] = {INT32_MIN, INT32_MIN, INT32_MIN, INT32_MIN};
         Box box[4] = {};
         uint32_t axes = out.nodes[(size_t)n].axis;
@@ -766,6 +823,7 @@ int32_t build_bsp(const double* tris_abc, int64_t n_tris, int32_t depth, FlatSce
         out.tri_orig.resize(out.tri_orig.size() + n, 0u);
         out.tri_src.resize(out.tri_src.size() + n, 0u);                        // k_bvh_emit copies them from the leaf's records
         out.wide.resize(out.wide.size() + (size_t)ftd::kWideNodeDoubles * (n - 1), 0.0);
+        for (uint32_t k = 0; k + 1 < n; ++k) out.wide_node.push_back((int32_t)(job.node_base + k));   // k_bvh_emit: wide node i is binary node i
         for (uint32_t k = 0; k < job.coarse_count; ++k) { const float all[6] = {-3e38f, -3e38f, -3e38f, 3e38f, 3e38f, 3e38f}; out.coarse_boxes.insert(out.coarse_boxes.end(), all, all + 6); }   // until the build: everything
         out.bvh_jobs.push_back(job);
         out.bvh_nodes += n - 1; out.bvh_leaves += 2 * (int64_t)n - 1; out.bvh_tris += n;

@@ -17,6 +17,7 @@ struct GraphNode {
     double tri[9] = {0};              // TriangleP
     int32_t depth = 0;                // Mesh: BspMesh.bspMesh depth
     std::vector<double> tris;         // Mesh: n x 9 (a,b,c)
+    bool deformed = false;            // Mesh: the vertices were replaced (ft_sg_set_mesh_triangles) since the last successful commit
     std::vector<ft_transform> xf;     // Transform: one basic transform or a Composed list
     ft_material mat{};                // MaterialF
     int32_t op = 0;                   // Csg
@@ -67,7 +68,20 @@ struct FlatScene {
     // Meshes whose exact BVH is built on the device after the upload (ft_bvh.hip): the flattener only reserves their ranges.
     struct BvhJob { uint32_t mesh, first_global, n, node_base, leaf_base, tri_base, wide_base, coarse_first, coarse_count; };
     std::vector<BvhJob> bvh_jobs;
+    // What a refit (ft_scene_commit_deformed, ft_refit.hip) needs to find a mesh again: per mesh the builder node it was made from (-1: a
+    // bare triangle or a run of them) and the ranges its BVH occupies in nodes / bsp_leaves / tris (the sorted copies) / wide - all counts
+    // 0 for a mesh without one; per 4-wide node the binary node it is two levels of (device-built ranges: node_base + its offset).
+    struct MeshRange { uint32_t node_first, node_count, leaf_first, leaf_count, tri_first, tri_count, wide_first, wide_count; };
+    std::vector<int32_t> mesh_node;
+    std::vector<MeshRange> mesh_ranges;
+    std::vector<int32_t> wide_node;
 };
+
+// One pass over the vertices of a mesh (n x 9 doubles): the bounds as the flattener keeps them (mesh_bounds), the largest |coordinate| of
+// the vertices as the hit test sees them (v0, v0 + e1, v0 + e2: what the BVH builders inflate their boxes by) and whether every
+// coordinate passes the builders' own test, |v| < 1e300.
+struct MeshScan { double bounds[6]; double extent; bool finite; };
+MeshScan scan_mesh(const double* tris_abc, int64_t n_tris);
 
 struct SceneGraph {
     std::vector<GraphNode> nodes;
@@ -89,6 +103,11 @@ struct SceneGraph {
     bool valid(int32_t id) const { return id >= 0 && id < (int32_t)nodes.size(); }
     // Returns FT_OK or a negative ft_status with err set.
     int32_t flatten(FlatScene& out, std::string& err) const;
+    // The cull records of a graph that differs from the one `held` was flattened from in mesh vertices only (ft_scene_commit_deformed):
+    // the flattener's walk again, with held's meshes taken as they are and `bounds` (6 per mesh of held) as their bounds.  On FT_OK
+    // held.mesh_bounds, culls and cull_items are the fresh flatten's; FT_ERR_UNSUPPORTED, with held untouched, when the new bounds change
+    // anything else (an item that gains or loses its bounds).
+    int32_t reflatten_deformed(FlatScene& held, const std::vector<double>& bounds, std::string& err) const;
 };
 
 // BspMesh.compile (BspMesh.fs:51-65) on the host: appends nodes / leaves / clipped triangles to

@@ -504,12 +504,55 @@ int32_t ft_temporal_filter(ft_context* ctx, const ft_camera* cam, int32_t spp, c
  * without it.  Several ft_scene_commit_moved calls between two accumulates compose by construction: H is the pose at the last
  * accumulate, not at the last commit.
  * What follows a leaf is its history, not its shading: light that changes on a moving surface (it turns towards a light, a shadow
- * sweeps over it) is averaged as noise is, max_history bounding how long it lingers.  Lights do not move; meshes do not deform.
+ * sweeps over it) is averaged as noise is, max_history bounding how long it lingers.  Lights do not move; meshes deform through
+ * ft_scene_commit_deformed (below), which moves no history.
  * ft_temporal_filter with `demodulate` returns FT_ERR_STATE between an ft_scene_commit_moved and the next ft_temporal_accumulate (its
  * guide pass would show another pose than the set); without `demodulate` it runs as before.
  * A host that never calls these functions gets bit-identical results from everything else.
  * Device memory: 192 bytes per leaf while a moved pose is being accumulated. */
 int32_t ft_scene_commit_moved(ft_context* ctx);
+/* ---- deforming meshes: a refit instead of a rebuild -------------------------------------------- */
+/* ft_sg_set_mesh_triangles + ft_scene_commit_deformed change the vertices of `bspMesh 0` meshes of a committed scene without rebuilding
+ * a tree and without ending ft_temporal_*.
+ * ft_sg_set_mesh_triangles(node, tris, n_tris) replaces the vertices of an existing ft_sg_bsp_mesh node; tris = n x 9 doubles as there,
+ * copied.  FT_ERR_INVALID, with nothing changed, for a null context, an invalid handle, a node that is not a bspMesh node, null tris or
+ * an n_tris that differs from the node's triangle count.  Like ft_sg_set_transform it leaves the scene uncommitted and is not a structural
+ * change; a later plain ft_scene_commit gives what a fresh graph with the new vertices gives.
+ * ft_scene_commit_deformed commits a graph in which only mesh vertices changed since the last successful commit:
+ *  - FT_ERR_STATE, and nothing done, unless the context holds a successful commit and no structural change was made since (the rule of
+ *    ft_scene_commit_moved), or while an ft_sg_set_transform is pending (ft_scene_commit_moved first, then deform) or an ft_set_option
+ *    that needs a new ft_scene_commit.
+ *  - FT_ERR_UNSUPPORTED when an edited mesh has depth above 0 (its clipped BSP depends on the positions), holds a non-finite coordinate
+ *    (|v| < 1e300 fails, the builders' own test) or moves so far that a top-level item gains or loses its bounds.  This is decided on the
+ *    host before anything is uploaded: the old commit stays in HBM and is renderable again; ft_scene_commit handles these cases.
+ *  - On success every later call - ft_render, ft_render_enqueue, ft_progressive_*, ft_render_aov, ft_denoise, the ft_debug_* ray queries -
+ *    gives what it gives on a fresh context whose graph was built with the new vertices and committed with ft_scene_commit, bit for bit.
+ *  - It ends a progressive accumulation, retires queued frames first (as every commit does), leaves the temporal accumulation OPEN and
+ *    does not advance the pose counter: a deformed leaf gets no special treatment, clause 2's leaf, normal and position tests decide pixel
+ *    by pixel whether the history still fits.  On a multi-device context every device refits its own copy.  A host-only context checks
+ *    the same rules and then runs the full host commit.
+ *  - ft_get_commit_times: [0] host work, [1] the refit kernels, [2] uploads, [3] unchanged.  The first refit after a full commit also
+ *    derives the trees' parent links on the device, inside [1].
+ * What is kept: the topology of every tree as the last full commit built it, whichever builder did ("bvh_builder" 0, 1, 3) - children,
+ * split axes, leaf ranges, tri_orig, tri_src, the 4-wide children, the coarse frontier; meshes that were not edited are not touched.
+ * What is written again, per edited mesh: the triangle records (v0, e1 = v1 - v0, e2 = v2 - v0) and their sorted copies, the boxes of
+ * the binary nodes (the exact bounds of the vertices as the hit test sees them, inflated by 1e-7 * extent + 1e-300, extent = the largest
+ * |coordinate| of the new mesh), the 4-wide slot boxes, the coarse boxes; on the host the mesh bounds and the cull records of the items
+ * that hold the mesh.  A tree that holds every triangle once, bounds them with inflated boxes and breaks ties by list index gives the
+ * linear scan's hits whatever its shape, hence the bit-identity above.
+ * "light_space_shadows" 1 / 2: the light-space trees and grids are built on the host from the vertices and are NOT refit.  Every leaf of
+ * an edited mesh loses its pair records (ft_debug_light_space: 0xFFFFFFFF), so its directional shadow rays walk the refit BVH as option 0
+ * does - the same bits - until the next full ft_scene_commit brings the structures back.
+ * Tree quality: the refit tree is the OLD vertices' tree around the new ones, so its boxes overlap more the further the mesh moves from
+ * the pose it was built in, and the walk slows down while the results stay exact.  A host should interleave a full ft_scene_commit when
+ * its deformation has accumulated that far; tools/refit_rate.py measures the k_primary ratio of a refit tree to a fresh one under an
+ * accumulating twist (the ratio has not been measured yet).
+ * A host that never calls these functions gets bit-identical results from everything else.
+ * Device memory: 8 bytes per BspNode, 52 per BspLeaf and 4 per 4-wide node of the scene from the first refit on, plus the vertices of
+ * the meshes being refit. */
+int32_t ft_sg_set_mesh_triangles(ft_context* ctx, ft_node node, const double* tris, int64_t n_tris);
+int32_t ft_scene_commit_deformed(ft_context* ctx);
+
 /* The per-leaf matrices of the scene the context holds (the last successful commit's; they stay readable while the graph is being
  * edited), for tests: *n_leaves, and into each non-null array 12 doubles per leaf, the rows of the 3x4 model->world (m2w) and
  * world->model (w2m) matrix.  Host-only contexts too.  FT_ERR_STATE without a successful commit. */
