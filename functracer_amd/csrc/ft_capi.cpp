@@ -189,6 +189,7 @@ const OptionSpec kOptions[] = {
     {"bvh_builder", 0, 3, &Options::bvh_builder, nullptr, kCommit},
     {"csg_auto_grow", 0, 1, &Options::csg_auto_grow, nullptr, kFlag},
     {"primary_block_lists", 0, 1, &Options::primary_block_lists, nullptr, kFlag},
+    {"uniform_surface", 0, 1, &Options::uniform_surface, nullptr, kFlag},
     {"csg_mesh_capacity", 1, 255, nullptr, [](fth::SceneGraph& g, int64_t v) { g.csg_mesh_capacity = (int32_t)v; }, kCommit},
     // directional shadow rays of coherent waves: 0 the BVH; 1 light-space trees; 2 (default) light-space grids, the trees for wide waves.
     // It was a flag before the grids: it still takes any value, and any other than 0 / 1 means 2.
@@ -208,6 +209,7 @@ int32_t ft_set_option(ft_context* c, const char* key, int64_t value) {
             d->opt.*o.field = value;
             for (hipStream_t m : d->more_mains) if (!m) d->opt.mains = 1;   // (without them every frame takes the one main stream)
             d->dev_scene.coherent_waves = d->opt.coherent_waves ? 1 : 0;
+            d->dev_scene.uniform_surface = d->opt.uniform_surface ? 1 : 0;
             if (o.rules & kCommit) { d->committed = false; c->options_pending = true; }
             if (o.rules & kLevelHint) d->staged_hint = -1;
             if (o.rules & kZeroFill) d->zero_signature[0] = d->zero_signature[1] = 0;
@@ -410,6 +412,7 @@ static int32_t upload_scene(ft_context* c) {
         }
     }
     S.coherent_waves = c->opt.coherent_waves ? 1 : 0;
+    S.uniform_surface = c->opt.uniform_surface ? 1 : 0;
     S.n_simd = c->n_cu * 4;
     S.n_items = (int32_t)f.item_pc.size() - 1; S.n_cull_rows = f.cull_bundle ? (int32_t)(f.cull_rows.size() / 3) : -1;
     S.n_leaves = (int32_t)f.leaves.size(); S.n_lights = (int32_t)f.lights.size();

@@ -95,6 +95,7 @@ struct Options {
                                     // binned surface-area tree over the Morton order, 2 = by size: the host's below kDeviceBvhMinTris triangles, 3's from there on
     int64_t csg_auto_grow = 1;      // ft_render: double csg_mesh_capacity and render again when a hit list overflows (read on device 0)
     int64_t primary_block_lists = 1;   // k_block_lists: the primaries of a classified frame over ONE bare mesh test their block's candidate list; 0: the tree walk everywhere
+    int64_t uniform_surface = 1;    // k_primary: one-leaf batches take leaf and material through scalar loads, dead shader work and empty-list batches are skipped; 0: per lane, everything (A/B)
 };
 
 // One buffer in HBM per array of the flattened scene; DevScene points into them (upload_scene).

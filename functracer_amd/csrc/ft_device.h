@@ -42,6 +42,8 @@ struct DevScene {
     int32_t csg_rows, lane_fold;   // LDS rows per hit-list column and lanes folded together (see HitList): csg_cap <= csg_rows * lane_fold
     int32_t n_simd;                // SIMDs of the device (CUs x 4): how far few rays are spread (batch_lanes_for)
     int32_t coherent_waves;        // 1 (default): bounce-0 wavefronts use the bundle paths (cone cull, packet traversal); 0: every wave is treated as incoherent (diagnostic)   // sum over lights of the shadow rays the reference casts per hit
+    int32_t uniform_surface;       // 1 (default): a k_primary batch whose hit lanes share one leaf reads that leaf and its material through scalar loads, the shaders
+                                   // skip what no lane of the wave can use, a batch with an empty candidate list stores Colour.Zero unseen; 0: per lane, everything (A/B)
 };
 
 // Ray wavefront buffer, struct-of-arrays so a wave's 64 records are 512 contiguous bytes per field: 7 doubles + the sample slot =

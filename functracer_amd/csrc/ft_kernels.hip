@@ -1514,9 +1514,12 @@ FT_DEV void cylinder_side(const Ray& r, double t, V3& p, V3& n) {   // Cylinder.
     n = (dot3(nn.x, nn.y, nn.z, r.dx, r.dy, r.dz) < 0.0) ? nn : V3{-nn.x, -nn.y, -nn.z};
 }
 
-template <bool TEXTURED>
-FT_DEV Surface surface_at(const Scene& S, const Ray& rw, double t, uint32_t id0, uint32_t id1) {
-    const uint32_t leaf = id0 & ID_LEAF_MASK, sub = (id0 >> ID_SUB_SHIFT) & ID_SUB_MASK;
+// ONE_LEAF: the caller found every hit lane of the wave on one leaf and hands its index over in a scalar register (wave_leaf).  The head,
+// M, W and the material word then come through scalar loads and the switch is a scalar branch; the expressions are the same, operand
+// for operand.  What is a lane's own - t, id1, sub, the triangle's edges, ID_FLIP - stays per lane.
+template <bool TEXTURED, bool ONE_LEAF = false>
+FT_DEV Surface surface_at(const Scene& S, const Ray& rw, double t, uint32_t id0, uint32_t id1, uint32_t wave_leaf = 0u) {
+    const uint32_t leaf = ONE_LEAF ? wave_leaf : id0 & ID_LEAF_MASK, sub = (id0 >> ID_SUB_SHIFT) & ID_SUB_MASK;
     const LeafHead H = leaf_head(S, leaf);
     cdp M = S.leaves + 16ull * leaf;
     const bool xform = (H.flags & LF_XFORM) != 0;
@@ -1811,9 +1814,9 @@ FT_DEV void light_visibility(const Scene& S, const Surface& sf, bool lit, unsign
 
 // The shaders of Shading.fs:50-107 over all lights for one hit: sum of specular + diffuse fragments (the reflection shader
 // travels with the path weight).
-template <bool FANCY, bool SOFT>
+template <bool FANCY, bool SOFT, bool VOTED = false>
 FT_DEV void shade_lights(const Scene& S, const Surface& sf, const MaterialV& mat, const Ray& r, bool active, bool lit,
-                         unsigned long long vis_lo, unsigned long long vis_hi, double& cr, double& cg, double& cb) {
+                         unsigned long long vis_lo, unsigned long long vis_hi, double& cr, double& cg, double& cb, bool voted = false) {
     const int n_lights = S.n_lights;
     cr = 0.0; cg = 0.0; cb = 0.0;                                  // sum over fragments (Seq.sumBy shader, Shading.fs:139)
     for (int l = 0; l < n_lights; ++l) {
@@ -1837,16 +1840,23 @@ FT_DEV void shade_lights(const Scene& S, const Surface& sf, const MaterialV& mat
         const double lcr = intensity * lp[6], lcg = intensity * lp[7], lcb = intensity * lp[8];   // scaleColour (Image.fs:25-26)
         double fr = 0.0, fg = 0.0, fb = 0.0;
         {                                                      // specularShader (Shading.fs:78-87)
-            const V3 nn = normalise(sf.n);
-            const double k2 = 2.0 * dot3(ld.x, ld.y, ld.z, nn.x, nn.y, nn.z);
-            const V3 rl = normalise(V3{ld.x - k2 * nn.x, ld.y - k2 * nn.y, ld.z - k2 * nn.z});         // Vector.reflect (CommonTypes.fs:72)
-            const V3 vd = normalise(V3{r.dx, r.dy, r.dz});
+            // The reflected light vector and the view vector feed nothing but the power's base.  Their three normalisations branch, so the
+            // compiler leaves them where they are written: with VOTED and `voted` (k_primary, option "uniform_surface") that is under the vote.
+            V3 rl{0, 0, 0}, vd{0, 0, 0};
+            auto reflected_and_view = [&]() {
+                const V3 nn = normalise(sf.n);
+                const double k2 = 2.0 * dot3(ld.x, ld.y, ld.z, nn.x, nn.y, nn.z);
+                rl = normalise(V3{ld.x - k2 * nn.x, ld.y - k2 * nn.y, ld.z - k2 * nn.z});                  // Vector.reflect (CommonTypes.fs:72)
+                vd = normalise(V3{r.dx, r.dy, r.dz});
+            };
+            if (!VOTED || !voted) reflected_and_view();
             // intensity = (view . -reflected) ** shineyness.  With shineyness <= 0 the shader is black whatever the power is, so
             // the power is only evaluated when some lane needs it; integral exponents up to 64 (the usual case, ft_flat.h) go through
             // square-and-multiply, everything else through pow.
             const bool wants = active && mat.shineyness > 0.0;
             double si = 0.0;
             if (__any(wants)) {                                   // each lane takes its own route: a ray's result must not depend on its wave
+                if (VOTED && voted) reflected_and_view();
                 const double base = dot3(vd.x, vd.y, vd.z, -rl.x, -rl.y, -rl.z);
                 const bool small_int = small_whole_exponent(mat.shineyness);
                 if (__any(wants && small_int)) {
@@ -1917,6 +1927,9 @@ __global__ __launch_bounds__(kBlock, BLOCKS) void k_primary(PrimaryArgs) {
     const uint32_t B = px.group_log2 ? 64u : batch_lanes_for(n, S.lane_fold, S.n_simd);
     const uint32_t n_batches = (n + B - 1) / B;
     const bool coherent = K->S.coherent_waves != 0;
+    // The one-leaf surface path and the one-material vote behind it (below) are compiled into the lean mesh variant <F,F,T> only.  The FANCY,
+    // SOFT and mesh-free variants take of option "uniform_surface" the view-ray vote and, where not FANCY, the voted normalisations of shade_lights.
+    constexpr bool kOneLeaf = MESH && !FANCY && !SOFT;
     auto at_of = [&](uint32_t batch) -> SlotAt { return px.group_log2 ? slot_at(px, batch, lane_id()) : slot_at(px, batch * B + lane_id()); };
     BatchCursor cursor(&cc->work_trace[0][0]);
     uint32_t bi = cursor.grab(), bi_next = cursor.grab();
@@ -1939,16 +1952,22 @@ __global__ __launch_bounds__(kBlock, BLOCKS) void k_primary(PrimaryArgs) {
         const unsigned long long clk_batch = FT_CLK_NOW();          // (diagnostic build: sections of a batch, slots 22 .. 27)
         // ---- closest hit; the geometry sees the offset ray (Shading.fs:135), the shaders the original one (Shading.fs:137)
         Ray ro{0, 0, 0, 0, 0, 0};
+        bool empty = false;                                         // (wave-uniform) nothing to trace: see below
         {
             const FT_CONST PrimaryArgs* Kb = fresh(K);              // camera, pixel list: loaded here, dead before the trace
             if (bi_next < n_batches && bi_next * B + lane_id() < n && lane_id() < B) pid_next = primary_pixel(&Kb->gen, at_of(bi_next));
             if (use_lists && bi_next < n_batches) head_next = head_of(Kb, bi_next);
+            // A list with no entry under a mesh that is the scene's only item: no ray of the batch can hit anything, whatever its jitter (the
+            // list covers the block's rectangle under every offset; frames of a focus camera are never classified and carry no lists, the test on
+            // has_focus only says so here).  No ray is generated
+            // and none traced: the query stays a miss, the batch stores Colour.Zero below and adds nothing to any counter, as its trace would have.
+            empty = use_lists && lq.head != kListNone && (lq.head & 127u) == 0u && Kb->S.uniform_surface != 0 && Kb->S.n_items == 1 && Kb->gen.cam.has_focus == 0;
             double jxy[2] = {0.0, 0.0};
-            if (active) {
+            if (active && !empty) {
                 const Ray r = primary_ray_from(&Kb->gen, at_of(bi).s, pid, jxy);
                 ro = {r.ox + 0.0001 * r.dx, r.oy + 0.0001 * r.dy, r.oz + 0.0001 * r.dz, r.dx, r.dy, r.dz};   // slightOffset (Shading.fs:129)
             }
-            if (MESH && lq.head != kListNone) {                      // (wave-uniform) the wave's rectangle on the image plane, rounded outward to float
+            if (MESH && lq.head != kListNone && !empty) {            // (wave-uniform) the wave's rectangle on the image plane, rounded outward to float
                 const float inf = __builtin_inff();
                 const float fx = (float)jxy[0], fy = (float)jxy[1], sx = 2.4e-7f * fabsf(fx) + 1e-37f, sy = 2.4e-7f * fabsf(fy) + 1e-37f;
                 lq.x0 = wave_min(active ? fx - sx : inf); lq.x1 = wave_max(active ? fx + sx : -inf);
@@ -1957,10 +1976,11 @@ __global__ __launch_bounds__(kBlock, BLOCKS) void k_primary(PrimaryArgs) {
             }
         }
         Query<false> q = Query<false>::closest(active);
-        bool overflow;
+        bool overflow = false;
         const unsigned long long clk_a = FT_CLK_NOW();
         FT_CLK_ADD(22, clk_batch);
-        trace<false, MESH>(S, ro, q, lds, overflow, coherent, nullptr, -1, MESH ? &lq : nullptr);
+        if (!empty) trace<false, MESH>(S, ro, q, lds, overflow, coherent, nullptr, -1, MESH ? &lq : nullptr);
+        else FT_LIST_ADD(6, 1);
         FT_CLK_ADD(23, clk_a);
         n_ovf_wave += (unsigned long long)__popcll(__ballot(overflow && active));
         const bool hit = active && q.id0 != ID_MISS;
@@ -1971,37 +1991,66 @@ __global__ __launch_bounds__(kBlock, BLOCKS) void k_primary(PrimaryArgs) {
             Surface sf{{0, 0, 0}, {0, 1, 0}, 0, 0.0, 0.0};
             bool lit = false;
             unsigned long long sample = 0ull;
+            // One leaf under every hit lane (the headline: every batch that hits anything): that leaf's index in a scalar register, and with
+            // it the head, the matrices and the material as scalar loads instead of 64 lanes' copies of them.  Any other wave: per lane.
+            // (Compiled into the lean mesh variant only: the second copy of the surface code costs the FANCY variants - atan2, asin - up to
+            // 64 B/lane of scratch and the soft-light one a hundred more spill instructions, and the mesh-free scenes' waves mostly straddle leaves.)
+            const unsigned long long clk_s = FT_CLK_NOW();
+            bool one_leaf = false;
+            uint32_t wave_leaf = 0u;
+            if (kOneLeaf && coherent && fresh(K)->S.uniform_surface != 0) {      // (option "uniform_surface")
+                wave_leaf = (uint32_t)__builtin_amdgcn_readlane((int)(q.id0 & ID_LEAF_MASK), (int)__builtin_ctzll(hit_mask));
+                one_leaf = __ballot(hit && (q.id0 & ID_LEAF_MASK) != wave_leaf) == 0ull;
+                if (one_leaf) FT_CLK_INC(27);
+            }
             if (hit) {
-                sf = surface_at<FANCY>(S, ro, q.best_t, q.id0, q.id1);
-                lit = material_lit(S, sf.material);
+                if (kOneLeaf && one_leaf) {
+                    sf = surface_at<FANCY, true>(S, ro, q.best_t, q.id0, q.id1, wave_leaf);
+                    lit = material_lit(S, leaf_head(S, wave_leaf).material);
+                } else {
+                    sf = surface_at<FANCY>(S, ro, q.best_t, q.id0, q.id1);
+                    lit = material_lit(S, sf.material);
+                }
                 if (SOFT) sample = (unsigned long long)pid * (unsigned long long)fresh(K)->gen.spp + at_of(bi).s;
             }
             unsigned long long vis_lo, vis_hi;
             const unsigned long long clk_b = FT_CLK_NOW();
+            FT_CLK_ADD(10, clk_s);                                  // (diagnostic build: the surface part of the last section, slot 10; one-leaf batches, slot 27)
             light_visibility<SOFT, MESH>(S, sf, lit, sample, [&]() { return fresh(K)->gen.seed; }, 0, coherent, lds, vis_lo, vis_hi, n_shadow_wave, n_ovf_wave);
             FT_CLK_ADD(24, clk_b);
-            MaterialV mat = material_at(S, sf.material);
+            // (the option and the vote again, on the material index this time, rather than two more values kept across the shadow traces)
+            const bool uniform = coherent && fresh(K)->S.uniform_surface != 0;
+            const uint32_t wave_mat = (uint32_t)__builtin_amdgcn_readlane((int)sf.material, (int)__builtin_ctzll(hit_mask));
+            MaterialV mat;
+            if (kOneLeaf && uniform && __ballot(hit && sf.material != wave_mat) == 0ull) mat = material_at(S, wave_mat);
+            else mat = material_at(S, sf.material);
             if (FANCY) { if (hit && mat.texture >= 0) textured_colour(S, mat, sf.u, sf.v, mat.colour); }
             // the view ray is generated again here rather than kept in registers across the shadow traces (same arithmetic, same value; keeping only
             // its point on the image plane - two doubles - across them was measured too: scratch 48 -> 72 B/lane, the headline even, the CSG scenes 2.5 % slower)
+            // - and only when a lane of the wave reads it: the specular power's base, Oren-Nayar, a reflection ray.  A lane that reads it makes
+            // the vote true itself, so no lane's ray depends on its neighbours.
             const FT_CONST PrimaryArgs* K2 = fresh(K);
-            const Ray rv = hit ? primary_ray_from(&K2->gen, at_of(bi).s, pid) : Ray{0, 0, 0, 0, 0, 0};
-            shade_lights<FANCY, SOFT>(S, sf, mat, rv, hit, lit, vis_lo, vis_hi, cr, cg, cb);
-            // reflectionShader (Shading.fs:89-98), see k_bounce: one ray of weight L * reflectance stands for the L identical sub-traces
             const bool spawn = lit && mat.reflectance > 0.0 && 0 < K2->max_depth;
+            const bool reads_view = spawn || (lit && (mat.shineyness > 0.0 || (FANCY && mat.roughness != 0.0)));
+            Ray rv{0, 0, 0, 0, 0, 0};
+            if (!uniform || __any(reads_view)) { if (hit) rv = primary_ray_from(&K2->gen, at_of(bi).s, pid); }
+            shade_lights<FANCY, SOFT, !FANCY>(S, sf, mat, rv, hit, lit, vis_lo, vis_hi, cr, cg, cb, uniform);
+            // reflectionShader (Shading.fs:89-98), see k_bounce: one ray of weight L * reflectance stands for the L identical sub-traces
             const unsigned long long m = __ballot(spawn);
             const uint32_t cnt = (uint32_t)__popcll(m);
-            uint32_t dst = 0;
-            if (lane_id() == 0 && cnt) dst = atomicAdd(&K2->fc->cc.n_rays[1], cnt);
-            dst = __builtin_amdgcn_readfirstlane(dst);
-            if (spawn) {
+            if (cnt) {                                              // (a scalar branch: a wave that spawns nothing skips the slot arithmetic with the stores)
+                uint32_t dst = 0;
+                if (lane_id() == 0) dst = atomicAdd(&K2->fc->cc.n_rays[1], cnt);
+                dst = __builtin_amdgcn_readfirstlane(dst);
                 const uint32_t o = dst + lanes_below(m);
-                const FT_CONST RayBuf& next = K2->next;
-                const double k2 = 2.0 * dot3(rv.dx, rv.dy, rv.dz, sf.n.x, sf.n.y, sf.n.z);
-                next.ox[o] = sf.p.x; next.oy[o] = sf.p.y; next.oz[o] = sf.p.z;
-                next.dx[o] = rv.dx - k2 * sf.n.x; next.dy[o] = rv.dy - k2 * sf.n.y; next.dz[o] = rv.dz - k2 * sf.n.z;
-                next.w[o] = 1.0 * (mat.reflectance * uniform_f64((double)n_lights));
-                next.slot[o] = i;
+                if (spawn) {
+                    const FT_CONST RayBuf& next = K2->next;
+                    const double k2 = 2.0 * dot3(rv.dx, rv.dy, rv.dz, sf.n.x, sf.n.y, sf.n.z);
+                    next.ox[o] = sf.p.x; next.oy[o] = sf.p.y; next.oz[o] = sf.p.z;
+                    next.dx[o] = rv.dx - k2 * sf.n.x; next.dy[o] = rv.dy - k2 * sf.n.y; next.dz[o] = rv.dz - k2 * sf.n.z;
+                    next.w[o] = 1.0 * (mat.reflectance * uniform_f64((double)n_lights));
+                    next.slot[o] = i;
+                }
             }
             n_refl_wave += cnt;
             n_hit_wave += (unsigned long long)__popcll(hit_mask);

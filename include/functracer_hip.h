@@ -158,6 +158,10 @@ const char* ft_last_error(const ft_context* ctx);
  * mesh's tree once with the block's pyramid and keeps the triangles whose rectangle on the image plane overlaps the block's; the block's primary rays then test
  * that short list instead of walking the tree, each from the root.  Blocks with more than 64 candidates, progressive passes and scenes with several such leaves
  * keep the walk; 0: the walk everywhere.  Same triangle records, the closest hit does not depend on the order they are offered in: same frames bit for bit),
+ * "uniform_surface" (1 = default: a bounce-0 wavefront whose hit lanes all lie on one leaf reads that leaf's record, matrices and material once, through scalar
+ * loads, instead of once per lane (scenes with meshes and without textures, rough materials or soft lights: the kernel the headline runs); the shaders leave out what no lane of the wavefront reads (the specular term's three normalisations, the regenerated view ray);
+ * and, with "primary_block_lists", a wavefront whose block has an empty candidate list stores Colour.Zero without generating its rays when the mesh is the scene's
+ * only item and the camera has no focus.  0: everything per lane, nothing left out.  Same expressions either way: same frames and counters bit for bit),
  * "classify_ahead" / "resolve_aside" / "zero_fill_skip" (1 = default: what a stream of queued frames does that a single frame cannot - the next frame's k_classify on a second
  * stream, k_resolve on a third with the sample colours double-buffered, Colour.Zero not written again into blocks the last frame of the same signature left zero; 0 switches each off; k_resolve goes aside only in frames of one chunk), "mains" (2 = default, 1 .. 3: queued frames of one chunk take turns on that many main streams, so a frame's kernels are dispatched while its predecessor's drain
  * and two frames' reflection levels fill each other's idle stretches), "wave_samples" (0 = default, 16: a bounce-0 wavefront takes up to that many jitter offsets of 64 / that many pixels of an

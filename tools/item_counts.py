@@ -27,6 +27,11 @@ for name, spp in (("bunny", 16), ("bunny-bsp12", 16), ("hollow-sphere", 16), ("h
     if clk[26]:
         nb = clk[26]
         print(f"   k_primary per batch ({nb} batches): total {clk[25] / nb:9.0f} cycles = ray generation {clk[22] / nb:8.0f} + closest trace {clk[23] / nb:8.0f} + shadow queries {clk[24] / nb:8.0f} + surface / shading / store / spawn {(clk[25] - clk[22] - clk[23] - clk[24]) / nb:8.0f}")
+    if clk[10]:                                            # the last section split: the surface of the hits (slot 10; slot 27: batches on the one-leaf path)
+        nb = clk[26]
+        print(f"   surface / shading / store / spawn = surface {clk[10] / nb:8.0f} + shading / store / spawn {(clk[25] - clk[22] - clk[23] - clk[24] - clk[10]) / nb:8.0f};  one-leaf batches {clk[27]} of {nb}")
+    if clk[6]:                                             # option uniform_surface: batches of an empty list that stored Colour.Zero without a ray (slot 6)
+        print(f"   k_primary batches finished on an empty candidate list: {clk[6]} of {clk[26]}")
     if clk[7]:                                             # the candidate lists of the closest queries (k_block_lists): slots 2, 3, 7
         lq = clk[7]
         print(f"   closest queries through a block's list {lq} ({lq / max(v[0], 1):.2f} per coherent closest wave-query): entries offered / query {clk[2] / lq:6.2f}  "
