@@ -609,8 +609,8 @@ class Context(SceneBuilder):
         return out
 
     def block_lists(self):
-        """ft_debug_block_lists: the per-block triangle candidate lists of the last classified frame (option "primary_block_lists"), read
-        back from device memory.  A dict of `leaf` (the mesh leaf the lists are for; -1: that frame carried none, the arrays are then
+        """ft_debug_block_lists: the per-block triangle candidate lists of the last frame queued (option "primary_block_lists"), read
+        back from device memory.  A dict of `leaf` (the mesh leaf the lists are for; -1: that frame was not classified or carried none, the arrays are then
         empty), `heads` (one word per active block: _capi.LIST_NONE = the block walks the tree, else first entry << 7 | count),
         `pos_block` (the block of the frame's pixel list behind each active block), `entries` (records of _capi.LIST_ENTRY_DTYPE: the
         triangle's record and list index and its rectangle on the image plane, in the (jx, jy) of the primary rays), `plane` (tlx, tly,

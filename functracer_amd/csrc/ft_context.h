@@ -233,7 +233,7 @@ struct ft_context {
         void release() { for (DeviceBuf* b : {&d_verts, &d_parent_node, &d_parent_leaf, &d_arrived, &d_leaf_boxes, &d_wide_node}) b->release(); ready = false; }
     } refit;
     int slot_turn = 0;
-    int last_classified_slot = -1;   // the slot of the last classified frame queued (ft_debug_block_lists)
+    int last_classified_slot = -1;   // the slot of the last frame queued if that frame was classified, else -1 (ft_debug_block_lists)
     // Levels of the reflection tree worth launching: the host cannot know how deep the rays of a frame go without waiting, and a
     // k_bounce launch that finds no rays still costs a few microseconds.  It launches as many levels as the previous frame of the
     // same signature had rays in, plus one; the last one launched follows whatever it still spawns to the end inside the kernel,

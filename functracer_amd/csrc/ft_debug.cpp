@@ -209,7 +209,7 @@ int32_t ft_debug_mesh_trees(ft_context* c, int64_t sizes[12], void* nodes, uint3
     return FT_OK;
 }
 
-// The candidate lists of the last classified frame queued, as k_block_lists left them in its slot (the frame's counters are gone by
+// The candidate lists of the last frame queued if it was classified (none otherwise), as k_block_lists left them in its slot (the frame's counters are gone by
 // then: the active block count comes from its report, the entries in use from the headers).
 int32_t ft_debug_block_lists(ft_context* c, int64_t sizes[4], double plane[4], uint32_t* heads, uint32_t* pos_block, uint32_t* entries) {
     if (!c || !sizes) return FT_ERR_INVALID;

@@ -460,7 +460,7 @@ static int32_t queue_frame(ft_context* c, const RenderRequest& q, const FramePla
         }
     } else {
         F.list_leaf = -1;                                          // the slot's lists, if any, were its previous frame's
-        if (c->last_classified_slot == turn) c->last_classified_slot = -1;
+        c->last_classified_slot = -1;                              // (ft_debug_block_lists describes the LAST frame queued: not an older frame's lists, still in another slot)
     }
     // Which main stream.  Two consecutive k_primary launches on ONE stream are an in-order pair: the second is dispatched when the first has
     // drained, and a persistent grid drains slowly (its last batches run on a machine that is mostly idle).  A simple frame - one chunk,

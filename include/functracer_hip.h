@@ -598,8 +598,8 @@ int32_t ft_debug_light_space(ft_context* ctx, int64_t sizes[4], double* pairs, u
  * box count) and 9 words per job (mesh, first_global, n, node_base, leaf_base, tri_base, wide_base, coarse_first, coarse_count). */
 int32_t ft_debug_mesh_trees(ft_context* ctx, int64_t sizes[12], void* nodes, uint32_t* bsp_leaves, double* tris, uint32_t* tri_orig, uint32_t* tri_src,
                             double* wide, float* coarse_boxes, int32_t* meshes, uint32_t* jobs);
-/* The per-block triangle candidate lists of the last classified frame queued (option "primary_block_lists"), read back from device memory once
- * everything queued has run, for tests.  sizes = active blocks, entries in use, the mesh leaf the lists are for (-1: that frame carried none; the
+/* The per-block triangle candidate lists of the last frame queued (option "primary_block_lists"), read back from device memory once
+ * everything queued has run, for tests.  sizes = active blocks, entries in use, the mesh leaf the lists are for (-1: that frame was not classified or carried none; the
  * other sizes are then 0), the pool's capacity in entries.  Each non-null array receives: plane = tlx, tly, pw, ph of the frame's image plane
  * (pixel (x, y) under jitter offset (ox, oy) looks through jx = tlx + (x + ox) pw, jy = tly - (y - oy) ph); heads = one word per active block,
  * 0xFFFFFFFF (the block walks the tree) or first entry << 7 | count; pos_block = the block of the frame's pixel list behind each active block;
