@@ -527,6 +527,16 @@ class Context(SceneBuilder):
         self._check(self._lib.ft_scene_commit_deformed(self._ctx))
         self._progressive = None
 
+    def tree_quality(self, node):
+        """ft_scene_tree_quality: the measured surface-area cost of the tree of the `bsp_mesh(0, tris)` node as it lies in device memory.
+        A dict of `cost` (now), `cost_built` (when the tree was last built), `ratio` (cost / cost_built; 1.0 when cost_built is 0),
+        `rebuildable` (the tree was built on the device: "refit_rebuild_percent" can rebuild it in place) and `rebuilds` (in place, since the
+        last full commit)."""
+        out = np.zeros(4)
+        self._check(self._lib.ft_scene_tree_quality(self._ctx, int(node), _capi.dptr(out)))
+        cost, built = float(out[0]), float(out[1])
+        return {"cost": cost, "cost_built": built, "ratio": cost / built if built > 0.0 else 1.0, "rebuildable": int(out[2]), "rebuilds": int(out[3])}
+
     def leaf_matrices(self):
         """ft_debug_leaf_matrices: (m2w[leaves, 3, 4], w2m[leaves, 3, 4]) of the scene the context holds."""
         n = C.c_int64()

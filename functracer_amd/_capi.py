@@ -116,6 +116,7 @@ MOTION_SIGNATURES = [
 DEFORM_SIGNATURES = [
     ("ft_sg_set_mesh_triangles", C.c_int32, [C.c_void_p, C.c_int32, c_double_p, C.c_int64]),
     ("ft_scene_commit_deformed", C.c_int32, [C.c_void_p]),
+    ("ft_scene_tree_quality", C.c_int32, [C.c_void_p, C.c_int32, c_double_p]),
 ]
 
 

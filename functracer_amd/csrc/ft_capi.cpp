@@ -3,6 +3,7 @@
 // the features over it ft_progressive.cpp and ft_passes.cpp, the test entry points ft_debug.cpp.
 // Reference citations are relative to FuncTracer/ of the reference (antonburger/FuncTracer).
 #include "ft_context.h"
+#include "ft_refit_cost.h"
 
 namespace ftc {
 
@@ -164,8 +165,8 @@ const char* ft_last_error(const ft_context* c) { return c ? c->err.c_str() : "nu
 // The keys of ft_set_option.  A flag takes any value as 0 / 1; any other value must lie in [lo, hi] (and be 0 or a power of two where
 // kPowerOfTwo says so).  It goes into an Options member of every device of the context, or into device 0's scene graph: the peers
 // receive the scene flattened on device 0.  kCommit / kLevelHint / kZeroFill: a change invalidates the committed scene, the staged
-// level hint, the zero-fill signatures.
-enum { kFlag = 1, kPowerOfTwo = 2, kCommit = 4, kLevelHint = 8, kZeroFill = 16 };
+// level hint, the zero-fill signatures.  kOrZero: 0 is valid beside [lo, hi].
+enum { kFlag = 1, kPowerOfTwo = 2, kCommit = 4, kLevelHint = 8, kZeroFill = 16, kOrZero = 32 };
 struct OptionSpec {
     const char* key;
     int64_t lo, hi;
@@ -190,6 +191,8 @@ const OptionSpec kOptions[] = {
     {"csg_auto_grow", 0, 1, &Options::csg_auto_grow, nullptr, kFlag},
     {"primary_block_lists", 0, 1, &Options::primary_block_lists, nullptr, kFlag},
     {"uniform_surface", 0, 1, &Options::uniform_surface, nullptr, kFlag},
+    // read by ft_scene_commit_deformed alone: no commit depends on it, so it leaves the committed scene as it is
+    {"refit_rebuild_percent", 100, 1000000, &Options::refit_rebuild_percent, nullptr, kOrZero},
     {"csg_mesh_capacity", 1, 255, nullptr, [](fth::SceneGraph& g, int64_t v) { g.csg_mesh_capacity = (int32_t)v; }, kCommit},
     // directional shadow rays of coherent waves: 0 the BVH; 1 light-space trees; 2 (default) light-space grids, the trees for wide waves.
     // It was a flag before the grids: it still takes any value, and any other than 0 / 1 means 2.
@@ -203,7 +206,7 @@ int32_t ft_set_option(ft_context* c, const char* key, int64_t value) {
     for (const OptionSpec& o : kOptions) {
         if (std::strcmp(key, o.key)) continue;
         if (o.rules & kFlag) value = value != 0;
-        else if (value < o.lo || value > o.hi || ((o.rules & kPowerOfTwo) && (value & (value - 1)))) return FT_ERR_INVALID;
+        else if (!((o.rules & kOrZero) && value == 0) && (value < o.lo || value > o.hi || ((o.rules & kPowerOfTwo) && (value & (value - 1))))) return FT_ERR_INVALID;
         if (o.to_graph) { o.to_graph(c->graph, value); c->committed = false; c->options_pending = true; return FT_OK; }
         for (ft_context* d : devices(c)) {
             d->opt.*o.field = value;
@@ -361,6 +364,46 @@ static void cull_items_image(const fth::FlatScene& f, std::vector<float>& v) {
     }
 }
 
+// The ranges of a device job in the context's scene arrays, as ft_bvh.hip takes them.
+static ftk::LbvhTarget lbvh_target(ft_context* c, const fth::FlatScene::BvhJob& j) {
+    const DeviceBuf* B = c->d_scene;
+    return ftk::LbvhTarget{B[kTris].as<double>(), j.first_global, j.n, B[kNodes].as<ftd::BspNode>(), j.node_base, B[kBspLeaves].as<ftd::BspLeaf>(), j.leaf_base,
+                           B[kTriOrig].as<uint32_t>(), j.tri_base, B[kWide].as<double>(), j.wide_base, B[kCoarse].as<float>() + 6 * (size_t)j.coarse_first, j.coarse_count,
+                           B[kTriSrc].as<uint32_t>()};
+}
+
+// Room in the per-lane node stacks of the incoherent walk (LDS) for a device-built tree of `height` node levels.
+static int32_t fit_stacks(ft_context* c, uint32_t height) {
+    if ((int32_t)height + 1 > c->flat.stack_capacity) c->flat.stack_capacity = (int32_t)height + 1;
+    return lds_fits(c);
+}
+
+// What the launches read of the scene `flat` describes and the arrays in HBM hold: the device scene's counts and capacities, the kernel
+// variants and the resident workgroups per CU.  At the end of every upload, and again when a rebuild in place made a taller tree.
+static void derive_launch_shape(ft_context* c) {
+    const fth::FlatScene& f = c->flat;
+    ftk::DevScene& S = c->dev_scene;
+    S.coherent_waves = c->opt.coherent_waves ? 1 : 0;
+    S.uniform_surface = c->opt.uniform_surface ? 1 : 0;
+    S.n_simd = c->n_cu * 4;
+    S.n_items = (int32_t)f.item_pc.size() - 1; S.n_cull_rows = f.cull_bundle ? (int32_t)(f.cull_rows.size() / 3) : -1;
+    S.n_leaves = (int32_t)f.leaves.size(); S.n_lights = (int32_t)f.lights.size();
+    S.csg_cap = f.csg_capacity; S.stack_cap = f.stack_capacity;
+    S.lane_fold = lane_fold_for(f); S.csg_rows = (f.csg_capacity + S.lane_fold - 1) / S.lane_fold;
+    S.shadow_rays_per_hit = 0;
+    for (auto& l : f.lights) S.shadow_rays_per_hit += (l.kind == ftd::LT_SOFT) ? l.samples : 1;   // Shading.fs:24-42
+    c->variant = 0;
+    for (auto& m : f.materials) if (needs_fancy(m)) c->variant |= 1;                               // FANCY
+    for (auto& l : f.lights) if (l.kind == ftd::LT_SOFT) c->variant |= 2;                          // SOFT
+    if (!f.meshes.empty()) c->variant |= 4;                                                        // MESH
+    const size_t lds = lds_bytes_for(c->flat);
+    c->variant_primary = c->variant;
+    c->blocks_primary = ftk::occupancy_blocks_primary(lds, &c->variant_primary);
+    c->blocks_bounce = ftk::occupancy_blocks_bounce(lds, c->variant);
+    c->blocks_resolve = ftk::occupancy_blocks_resolve();
+    c->blocks_aov = ftk::occupancy_blocks_aov(lds, c->variant);
+}
+
 static int32_t upload_scene(ft_context* c) {
     int32_t rc;
     FT_HIP(c, hipSetDevice(c->device));
@@ -394,12 +437,8 @@ static int32_t upload_scene(ft_context* c) {
         const auto t0 = std::chrono::steady_clock::now();
         uint32_t tallest = 0;
         for (const fth::FlatScene::BvhJob& j : f.bvh_jobs) {
-            const DeviceBuf* B = c->d_scene;
-            const ftk::LbvhTarget t{B[kTris].as<double>(), j.first_global, j.n, B[kNodes].as<ftd::BspNode>(), j.node_base, B[kBspLeaves].as<ftd::BspLeaf>(), j.leaf_base,
-                                    B[kTriOrig].as<uint32_t>(), j.tri_base, B[kWide].as<double>(), j.wide_base, B[kCoarse].as<float>() + 6 * (size_t)j.coarse_first, j.coarse_count,
-                                    B[kTriSrc].as<uint32_t>()};
             uint32_t height = 0;
-            FT_HIP(c, ftk::build_lbvh(c->stream, t, &height, c->opt.bvh_builder == 1 ? 0 : 1));
+            FT_HIP(c, ftk::build_lbvh(c->stream, lbvh_target(c, j), &height, c->opt.bvh_builder == 1 ? 0 : 1));
             // height 0: a non-finite coordinate; > 40: deeper than the packet walk's 64-entry stack allows (3 entries per 4-wide level)
             if (height == 0 || height > 40) { c->err = "device BVH build refused (non-finite vertex or a tree deeper than 40 levels): the host builder takes over"; return FT_ERR_BUILD; }
             tallest = std::max(tallest, height);
@@ -407,29 +446,10 @@ static int32_t upload_scene(ft_context* c) {
         if (!f.bvh_jobs.empty()) {
             c->commit_ms[1] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
             c->commit_ms[3] = tallest;
-            if ((int32_t)tallest + 1 > c->flat.stack_capacity) c->flat.stack_capacity = (int32_t)tallest + 1;   // per-lane node stacks of the incoherent walk (LDS)
-            if ((rc = lds_fits(c)) != FT_OK) return rc;
+            if ((rc = fit_stacks(c, tallest)) != FT_OK) return rc;
         }
     }
-    S.coherent_waves = c->opt.coherent_waves ? 1 : 0;
-    S.uniform_surface = c->opt.uniform_surface ? 1 : 0;
-    S.n_simd = c->n_cu * 4;
-    S.n_items = (int32_t)f.item_pc.size() - 1; S.n_cull_rows = f.cull_bundle ? (int32_t)(f.cull_rows.size() / 3) : -1;
-    S.n_leaves = (int32_t)f.leaves.size(); S.n_lights = (int32_t)f.lights.size();
-    S.csg_cap = f.csg_capacity; S.stack_cap = f.stack_capacity;
-    S.lane_fold = lane_fold_for(f); S.csg_rows = (f.csg_capacity + S.lane_fold - 1) / S.lane_fold;
-    S.shadow_rays_per_hit = 0;
-    for (auto& l : f.lights) S.shadow_rays_per_hit += (l.kind == ftd::LT_SOFT) ? l.samples : 1;   // Shading.fs:24-42
-    c->variant = 0;
-    for (auto& m : f.materials) if (needs_fancy(m)) c->variant |= 1;                               // FANCY
-    for (auto& l : f.lights) if (l.kind == ftd::LT_SOFT) c->variant |= 2;                          // SOFT
-    if (!f.meshes.empty()) c->variant |= 4;                                                        // MESH
-    const size_t lds = lds_bytes_for(c->flat);
-    c->variant_primary = c->variant;
-    c->blocks_primary = ftk::occupancy_blocks_primary(lds, &c->variant_primary);
-    c->blocks_bounce = ftk::occupancy_blocks_bounce(lds, c->variant);
-    c->blocks_resolve = ftk::occupancy_blocks_resolve();
-    c->blocks_aov = ftk::occupancy_blocks_aov(lds, c->variant);
+    derive_launch_shape(c);
     c->committed = true;
     ++c->commit_serial; c->staged_hint = -1;
     return FT_OK;
@@ -440,6 +460,7 @@ int32_t commit_scene(ft_context* c) {
     auto ms_since = [](clock::time_point t0) { return std::chrono::duration<double, std::milli>(clock::now() - t0).count(); };
     for (double& v : c->commit_ms) v = 0.0;
     c->holds_commit = false;                                        // `flat` is being replaced
+    c->tree_quality.clear();                                        // and with it every tree the costs and rebuild counts were of
     const auto done = [c](int32_t rc) {
         if (rc == FT_OK) { c->holds_commit = true; c->restructured = false; c->moved_pending = false; c->options_pending = false; for (fth::GraphNode& n : c->graph.nodes) n.deformed = false; }
         return rc;
@@ -474,23 +495,78 @@ int32_t commit_scene(ft_context* c) {
 // One edited mesh of the held scene: its index, its builder node and what one pass over the new vertices gave.
 struct DeformedMesh { uint32_t mesh; int32_t node; fth::MeshScan scan; };
 
-static ftk::RefitMesh refit_ranges(const fth::FlatScene& f, uint32_t mesh, double pad) {
-    const ftd::Mesh& M = f.meshes[mesh];
-    const fth::FlatScene::MeshRange& r = f.mesh_ranges[mesh];
-    ftk::RefitMesh m{};
-    m.first_global = f.bsp_leaves[(size_t)~M.root].first_tri; m.n = f.bsp_leaves[(size_t)~M.root].n_tris;
-    m.node_first = r.node_first; m.node_count = r.node_count; m.leaf_first = r.leaf_first; m.leaf_count = r.leaf_count;
-    m.tri_first = r.tri_first; m.tri_count = r.tri_count; m.wide_first = r.wide_first; m.wide_count = r.wide_count;
-    m.bvh_root = M.bvh_root;
-    for (const fth::FlatScene::BvhJob& j : f.bvh_jobs) if (j.mesh == mesh) m.device_built = 1u;
-    m.coarse_first = f.mesh_coarse[2 * mesh]; m.coarse_count = f.mesh_coarse[2 * mesh + 1];
-    m.pad = pad;
-    return m;
+using ftk::refit::refit_ranges;                                    // one mesh's ranges as the refit kernels take them (ft_refit_cost.h)
+
+static bool refittable(const fth::FlatScene& f, uint32_t mesh) { return f.meshes[mesh].root < 0 && f.meshes[mesh].bvh_root != INT32_MIN; }
+static const fth::FlatScene::BvhJob* job_of(const fth::FlatScene& f, uint32_t mesh) {
+    for (const fth::FlatScene::BvhJob& j : f.bvh_jobs) if (j.mesh == mesh) return &j;
+    return nullptr;
+}
+// The scene's arrays in HBM and, once a refit has made them, the refit's own tables.
+static ftk::RefitArrays refit_arrays(ft_context* c) {
+    DeviceBuf* B = c->d_scene;
+    ft_context::Refit& R = c->refit;
+    return ftk::RefitArrays{B[kTris].as<double>(), B[kNodes].as<ftd::BspNode>(), B[kBspLeaves].as<ftd::BspLeaf>(), B[kTriOrig].as<uint32_t>(), B[kWide].as<double>(),
+                            B[kCoarse].as<float>(), R.d_wide_node.as<int32_t>(), R.d_parent_node.as<int32_t>(), R.d_parent_leaf.as<int32_t>(), R.d_arrived.as<uint32_t>(),
+                            R.d_leaf_boxes.as<double>()};
 }
 
+// The cost of mesh `mesh`'s tree as it lies in this device's HBM (ftk::refit_cost); blocks until it is there.  Nothing else may be
+// writing the scene's arrays: the caller has retired the queued frames.
+static int32_t measure_cost(ft_context* c, const fth::FlatScene& f, uint32_t mesh, double* cost) {
+    const ftk::RefitMesh m = refit_ranges(f, mesh, 0.0);
+    const uint32_t blocks = ftk::refit_cost_blocks(m);
+    int32_t rc;
+    if ((rc = ensure(c, c->refit.d_cost, ((size_t)blocks + 1) * 8)) != FT_OK) return rc;
+    double* d = c->refit.d_cost.as<double>();
+    ftk::refit_cost(c->stream, refit_arrays(c), m, d, d + blocks);
+    FT_HIP(c, hipGetLastError());
+    FT_HIP(c, hipMemcpyAsync(cost, d + blocks, 8, hipMemcpyDeviceToHost, c->stream));
+    FT_HIP(c, hipStreamSynchronize(c->stream));
+    return FT_OK;
+}
+// cost_built of every refittable mesh that has none yet (the context's first device; before a refit rewrites anything).
+static int32_t record_built_costs(ft_context* c, const fth::FlatScene& f) {
+    c->tree_quality.resize(f.meshes.size());
+    for (uint32_t k = 0; k < (uint32_t)f.meshes.size(); ++k) {
+        ft_context::TreeQuality& q = c->tree_quality[k];
+        if (q.known || !refittable(f, k)) continue;
+        const int32_t rc = measure_cost(c, f, k, &q.cost_built);
+        if (rc != FT_OK) return rc;
+        q.known = true;
+    }
+    return FT_OK;
+}
+
+// The tree of a device job built again in place from the list-order records the refit has just written.  The job's node,
+// leaf and 4-wide ranges first go back to what the flattener reserved (build_bsp, all zero bytes): k_bvh_emit leaves the slots past the
+// new node count alone and real_node() reads the leaf twin of every slot, so a twin the old tree left there would pass for a node of
+// the new one.  Then the builder, as upload_scene runs it, and the refit's parent tables of the mesh's ranges.
+static int32_t rebuild_in_place(ft_context* c, const fth::FlatScene& f, const fth::FlatScene::BvhJob& j, uint32_t* height) {
+    DeviceBuf* B = c->d_scene;
+    ft_context::Refit& R = c->refit;
+    const fth::FlatScene::JobSpans sp = fth::FlatScene::reserved_spans(j);
+    FT_HIP(c, hipMemsetAsync(B[kNodes].as<ftd::BspNode>() + sp.node_first, 0, sp.node_count * sizeof(ftd::BspNode), c->stream));
+    FT_HIP(c, hipMemsetAsync(B[kBspLeaves].as<ftd::BspLeaf>() + sp.leaf_first, 0, sp.leaf_count * sizeof(ftd::BspLeaf), c->stream));
+    FT_HIP(c, hipMemsetAsync(B[kWide].as<double>() + ftd::kWideNodeDoubles * sp.wide_first, 0, sp.wide_count * ftd::kWideNodeDoubles * 8, c->stream));
+    FT_HIP(c, ftk::build_lbvh(c->stream, lbvh_target(c, j), height, c->opt.bvh_builder == 1 ? 0 : 1));
+    if (*height == 0 || *height > 40) { c->err = "ft_scene_commit_deformed: the rebuild in place was refused (a tree deeper than 40 levels): ft_scene_commit"; return FT_ERR_BUILD; }
+    FT_HIP(c, hipMemsetAsync(R.d_parent_node.as<int32_t>() + sp.node_first, 0xFF, sp.node_count * 4, c->stream));
+    FT_HIP(c, hipMemsetAsync(R.d_parent_leaf.as<int32_t>() + sp.leaf_first, 0xFF, sp.leaf_count * 4, c->stream));
+    ftk::refit_parents(c->stream, refit_arrays(c), refit_ranges(f, j.mesh, 0.0));
+    FT_HIP(c, hipGetLastError());
+    FT_HIP(c, hipStreamSynchronize(c->stream));
+    return FT_OK;
+}
+
+// What the context's first device decides for the others ("refit_rebuild_percent"): per edit whether its tree is rebuilt in place, and the
+// tallest tree the rebuilds made.
+struct RebuildPlan { std::vector<uint8_t> rebuild; uint32_t tallest = 0; };
+
 // The refit of `edits` on one device of the context: `f` is the held scene with the new cull records and leaves already in it, `g` the
-// graph with the new vertices.  ms[0] += uploads and the rest, ms[1] += the kernels.
-static int32_t refit_device(ft_context* c, const fth::FlatScene& f, const fth::SceneGraph& g, const std::vector<DeformedMesh>& edits, double ms[2]) {
+// graph with the new vertices.  ms[0] += uploads and the rest, ms[1] += the kernels.  lead: the context's first device, which measures
+// the costs and fills `plan`; the others carry the plan out.
+static int32_t refit_device(ft_context* c, const fth::FlatScene& f, const fth::SceneGraph& g, const std::vector<DeformedMesh>& edits, double ms[2], bool lead, RebuildPlan& plan) {
     using clock = std::chrono::steady_clock;
     auto since = [](clock::time_point t0) { return std::chrono::duration<double, std::milli>(clock::now() - t0).count(); };
     int32_t rc;
@@ -510,9 +586,7 @@ static int32_t refit_device(ft_context* c, const fth::FlatScene& f, const fth::S
         FT_HIP(c, hipMemsetAsync(R.d_parent_node.p, 0xFF, R.d_parent_node.bytes, c->stream));
         FT_HIP(c, hipMemsetAsync(R.d_parent_leaf.p, 0xFF, R.d_parent_leaf.bytes, c->stream));
     }
-    const ftk::RefitArrays A{B[kTris].as<double>(), B[kNodes].as<ftd::BspNode>(), B[kBspLeaves].as<ftd::BspLeaf>(), B[kTriOrig].as<uint32_t>(), B[kWide].as<double>(),
-                             B[kCoarse].as<float>(), R.d_wide_node.as<int32_t>(), R.d_parent_node.as<int32_t>(), R.d_parent_leaf.as<int32_t>(), R.d_arrived.as<uint32_t>(),
-                             R.d_leaf_boxes.as<double>()};
+    const ftk::RefitArrays A = refit_arrays(c);
     size_t n_verts = 0;
     for (const DeformedMesh& e : edits) n_verts += g.nodes[(size_t)e.node].tris.size();
     if ((rc = ensure(c, R.d_verts, n_verts * 8)) != FT_OK) return rc;
@@ -528,8 +602,9 @@ static int32_t refit_device(ft_context* c, const fth::FlatScene& f, const fth::S
     FT_HIP(c, hipStreamSynchronize(c->stream));
     ms[0] += since(t0);
     const auto t1 = clock::now();
+    if (lead && (rc = record_built_costs(c, f)) != FT_OK) return rc;   // of the trees as they were built: nothing has been rewritten yet
     if (first) {
-        for (uint32_t k = 0; k < (uint32_t)f.meshes.size(); ++k) if (f.meshes[k].root < 0 && f.meshes[k].bvh_root != INT32_MIN) ftk::refit_parents(c->stream, A, refit_ranges(f, k, 0.0));
+        for (uint32_t k = 0; k < (uint32_t)f.meshes.size(); ++k) if (refittable(f, k)) ftk::refit_parents(c->stream, A, refit_ranges(f, k, 0.0));
         R.ready = true;
     }
     at = 0;
@@ -541,6 +616,28 @@ static int32_t refit_device(ft_context* c, const fth::FlatScene& f, const fth::S
     }
     FT_HIP(c, hipGetLastError());
     FT_HIP(c, hipStreamSynchronize(c->stream));
+    // "refit_rebuild_percent": a device-built tree whose cost has grown past the host's threshold is built again in place
+    const int64_t percent = c->opt.refit_rebuild_percent;
+    if (lead) plan.rebuild.assign(edits.size(), 0);
+    for (size_t k = 0; percent > 0 && k < edits.size(); ++k) {
+        const uint32_t mesh = edits[k].mesh;
+        const fth::FlatScene::BvhJob* j = job_of(f, mesh);
+        if (!j || !refittable(f, mesh)) continue;                   // host-built trees are measured (ft_scene_tree_quality) and never rebuilt
+        if (lead) {
+            double now = 0.0;
+            if ((rc = measure_cost(c, f, mesh, &now)) != FT_OK) return rc;
+            plan.rebuild[k] = now * 100.0 > (double)percent * c->tree_quality[mesh].cost_built ? 1 : 0;
+        }
+        if (!plan.rebuild[k]) continue;
+        uint32_t height = 0;
+        if ((rc = rebuild_in_place(c, f, *j, &height)) != FT_OK) return rc;
+        plan.tallest = std::max(plan.tallest, height);
+        if (lead) {
+            ft_context::TreeQuality& q = c->tree_quality[mesh];
+            if ((rc = measure_cost(c, f, mesh, &q.cost_built)) != FT_OK) return rc;
+            ++q.rebuilds;
+        }
+    }
     ms[1] += since(t1);
     c->zero_signature[0] = c->zero_signature[1] = 0;                // the blocks k_classify finishes are another scene's
     c->committed = true;
@@ -619,12 +716,48 @@ int32_t ft_scene_commit_deformed(ft_context* c) {
     c->commit_ms[3] = tallest;
     c->commit_ms[0] = std::chrono::duration<double, std::milli>(clock::now() - t0).count();
     double ms[2] = {0.0, 0.0};
+    RebuildPlan plan;
     for (ft_context* d : devices(c)) {                              // every device refits its own copy
-        if ((rc = refit_device(d, f, c->graph, edits, ms)) != FT_OK) { if (d != c) c->err = d->err; break; }
+        if ((rc = refit_device(d, f, c->graph, edits, ms, d == c, plan)) != FT_OK) { if (d != c) c->err = d->err; break; }
+    }
+    if (rc == FT_OK && plan.tallest > 0) {                          // rebuilt trees: the height figure, and room in the stacks for a taller one
+        c->commit_ms[3] = std::max(c->commit_ms[3], (double)plan.tallest);
+        for (ft_context* d : devices(c)) {
+            if ((int32_t)plan.tallest + 1 <= d->flat.stack_capacity) continue;
+            if ((rc = fit_stacks(d, plan.tallest)) != FT_OK) { if (d != c) c->err = d->err; break; }
+            derive_launch_shape(d);
+        }
     }
     c->commit_ms[1] = ms[1]; c->commit_ms[2] = ms[0];
     if (rc != FT_OK) { for (ft_context* d : devices(c)) d->committed = false; c->holds_commit = false; return rc; }   // HBM holds neither scene whole: ft_scene_commit
     for (fth::GraphNode& n : c->graph.nodes) n.deformed = false;
+    return FT_OK;
+}
+
+// The measured quality of one mesh's tree: what a host sets "refit_rebuild_percent" by.
+int32_t ft_scene_tree_quality(ft_context* c, ft_node mesh_node, double out[4]) {
+    if (!c || !out) return FT_ERR_INVALID;
+    if (!c->graph.valid(mesh_node) || c->graph.nodes[mesh_node].kind != fth::GraphNode::Mesh) { c->err = "ft_scene_tree_quality: not a bspMesh node"; return FT_ERR_INVALID; }
+    if (!c->holds_commit) { c->err = "ft_scene_tree_quality: no committed scene (ft_scene_commit)"; return FT_ERR_STATE; }
+    const fth::FlatScene& f = c->flat;
+    uint32_t mesh = 0;
+    while (mesh < (uint32_t)f.meshes.size() && f.mesh_node[mesh] != mesh_node) ++mesh;   // a node under several transforms is one mesh
+    if (mesh == (uint32_t)f.meshes.size()) { c->err = "ft_scene_tree_quality: the node is not part of the committed scene (ft_scene_commit)"; return FT_ERR_STATE; }
+    if ((c->graph.nodes[mesh_node].depth > 0 && !c->graph.mesh_unclipped_bvh) || !refittable(f, mesh)) {
+        c->err = "ft_scene_tree_quality: the mesh has no BVH (depth above 0, or fewer than 8 triangles)"; return FT_ERR_UNSUPPORTED;
+    }
+    if (!need_device(c)) return FT_ERR_NO_DEVICE;
+    int32_t rc;
+    FT_HIP(c, hipSetDevice(c->device));
+    if (any_pending(c)) { if ((rc = retire_pending(c, nullptr)) != FT_OK) return rc; c->accum_open = false; }
+    if ((rc = drain_frame_streams(c)) != FT_OK) return rc;
+    if (c->side) FT_HIP(c, hipStreamSynchronize(c->side));
+    c->tree_quality.resize(f.meshes.size());
+    ft_context::TreeQuality& q = c->tree_quality[mesh];
+    double now = 0.0;
+    if ((rc = measure_cost(c, f, mesh, &now)) != FT_OK) return rc;
+    if (!q.known) { q.cost_built = now; q.known = true; }           // no refit since the build, or it would have been recorded then
+    out[0] = now; out[1] = q.cost_built; out[2] = job_of(f, mesh) ? 1.0 : 0.0; out[3] = (double)q.rebuilds;
     return FT_OK;
 }
 

@@ -95,6 +95,7 @@ struct Options {
                                     // binned surface-area tree over the Morton order, 2 = by size: the host's below kDeviceBvhMinTris triangles, 3's from there on
     int64_t csg_auto_grow = 1;      // ft_render: double csg_mesh_capacity and render again when a hit list overflows (read on device 0)
     int64_t primary_block_lists = 1;   // k_block_lists: the primaries of a classified frame over ONE bare mesh test their block's candidate list; 0: the tree walk everywhere
+    int64_t refit_rebuild_percent = 0;   // ft_scene_commit_deformed rebuilds a device-built tree in place once cost now x 100 > this x cost as built; 0: never (not a commit-time option)
     int64_t uniform_surface = 1;    // k_primary: one-leaf batches take leaf and material through scalar loads, dead shader work and empty-list batches are skipped; 0: per lane, everything (A/B)
 };
 
@@ -229,9 +230,15 @@ struct ft_context {
     // one (`ready`); d_verts: the new vertices of the meshes being refit.
     struct Refit {
         DeviceBuf d_verts, d_parent_node, d_parent_leaf, d_arrived, d_leaf_boxes, d_wide_node;
+        DeviceBuf d_cost;           // k_refit_cost's partials and, behind them, its result
         bool ready = false;
-        void release() { for (DeviceBuf* b : {&d_verts, &d_parent_node, &d_parent_leaf, &d_arrived, &d_leaf_boxes, &d_wide_node}) b->release(); ready = false; }
+        void release() { for (DeviceBuf* b : {&d_verts, &d_parent_node, &d_parent_leaf, &d_arrived, &d_leaf_boxes, &d_wide_node, &d_cost}) b->release(); ready = false; }
     } refit;
+    // ft_scene_tree_quality, per mesh of `flat`, kept on the context's first device: the cost of the tree when it was last
+    // built - measured the first time it is needed after a full commit, and again by every rebuild in place - and the rebuilds in place since
+    // that commit.  Emptied by every full commit.
+    struct TreeQuality { double cost_built = 0.0; bool known = false; uint32_t rebuilds = 0; };
+    std::vector<TreeQuality> tree_quality;
     int slot_turn = 0;
     int last_classified_slot = -1;   // the slot of the last frame queued if that frame was classified, else -1 (ft_debug_block_lists)
     // Levels of the reflection tree worth launching: the host cannot know how deep the rays of a frame go without waiting, and a

@@ -232,6 +232,13 @@ struct RefitMesh {
 void refit_parents(hipStream_t stream, const RefitArrays& A, const RefitMesh& m);
 // verts: the mesh's new vertices in HBM, n x 9 doubles (a, b, c).  Records and sorted copies, boxes leaves to root, 4-wide slots, coarse boxes.
 void refit_mesh(hipStream_t stream, const RefitArrays& A, const RefitMesh& m, const double* verts);
+// The surface-area cost of the mesh's binary tree as it lies in HBM (k_refit_cost), with A(box) = dx dy + dy dz + dz dx:
+//   ( sum over the real inner nodes of A(stored box) + sum over the leaves of n_tris x A(exact bound of the leaf's sorted records) ) / A(root's stored box),
+// 0 when the root's area is 0 or not finite.  Reads A.tris, A.nodes and A.leaves only (the refit's own tables may be null).  partials:
+// refit_cost_blocks(m) doubles of scratch in HBM; *cost (in HBM) receives the result.  The sum has a fixed shape - lane shuffles, the four
+// waves of a block through LDS, the blocks' partials in index order - so that one tree gives the same bits on every device and run.
+inline uint32_t refit_cost_blocks(const RefitMesh& m) { return (m.node_count + 255u) / 256u; }
+void refit_cost(hipStream_t stream, const RefitArrays& A, const RefitMesh& m, double* partials, double* cost);
 
 // Per-pixel surface buffers (ft_render_aov): for every entry of the chunk's pixel list (gen: pix_base, n_pix; one sample plane) the
 // closest hit of the geometry ray of sample `sample` - primary_ray_from exactly as k_primary calls it, then slightOffset - and what

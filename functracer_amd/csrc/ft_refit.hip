@@ -13,28 +13,22 @@
 //                    monotone in x), so a node's stored box is the exact bound of its triangles, inflated: what every builder stores
 //   k_refit_wide     per 4-wide node the inflated boxes of what its slots point to; empty slots stay all-NaN
 //   k_refit_coarse   one thread: the level of the tree with at most 64 nodes (the rule both builders use), as float boxes rounded outward
+// Beside them k_refit_cost / k_refit_cost_sum measure the surface-area cost of a tree as it lies in HBM (ft_scene_tree_quality, the
+// "refit_rebuild_percent" decision): one thread per node slot, a sum of fixed shape, no floating-point atomics.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
 #include <stdint.h>
 
 #include "ft_device.h"
+#include "ft_refit_cost.h"
 
 using namespace ftd;
 
 namespace ftk {
 namespace {
 
-constexpr uint32_t kLeafTris = 4;                                   // as the builders
-
-__device__ __forceinline__ bool node_in(const RefitMesh& m, int32_t r) { return r >= 0 && (uint32_t)r >= m.node_first && (uint32_t)r - m.node_first < m.node_count; }
-__device__ __forceinline__ bool leaf_in(const RefitMesh& m, int32_t r) { return r < 0 && r != INT32_MIN && (uint32_t)~r >= m.leaf_first && (uint32_t)~r - m.leaf_first < m.leaf_count; }
-// Node r of the mesh's range is a node of its tree.  A device job wrote a record for every node of its build, and lets those of at most
-// four triangles stand as leaves (ft_bvh.hip, scene_ref): build node i is also BspLeaf leaf_first + i, which holds its triangle count
-// (0 where the surface-area builder made fewer nodes than the range has room for).
-__device__ __forceinline__ bool real_node(const RefitArrays& A, const RefitMesh& m, uint32_t r) {
-    return !m.device_built || A.leaves[m.leaf_first + (r - m.node_first)].n_tris > kLeafTris;
-}
+using namespace refit;                                             // node_in, leaf_in, real_node, leaf_bound, the cost arithmetic (ft_refit_cost.h)
 
 __global__ __launch_bounds__(256) void k_refit_parents(RefitArrays A, RefitMesh m) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
@@ -64,16 +58,7 @@ __global__ __launch_bounds__(256) void k_refit_records(RefitArrays A, RefitMesh 
 
 // The inflated box of leaf `l` (an index into the scene's BspLeaf array), or false when it is no leaf of the tree's size.
 __device__ __forceinline__ bool leaf_box(const RefitArrays& A, const RefitMesh& m, uint32_t l, double box[6]) {
-    const BspLeaf L = A.leaves[l];
-    if (L.n_tris == 0u || L.n_tris > kLeafTris || L.first_tri < m.tri_first || L.first_tri - m.tri_first + L.n_tris > m.tri_count) return false;
-    for (int a = 0; a < 3; ++a) { box[a] = __builtin_inf(); box[3 + a] = -__builtin_inf(); }
-    for (uint32_t k = 0; k < L.n_tris; ++k) {
-        const double* T = A.tris + 9ull * (L.first_tri + k);
-        for (int a = 0; a < 3; ++a) {
-            const double v0 = T[a], v1 = T[a] + T[3 + a], v2 = T[a] + T[6 + a];
-            box[a] = fmin(box[a], fmin(v0, fmin(v1, v2))); box[3 + a] = fmax(box[3 + a], fmax(v0, fmax(v1, v2)));
-        }
-    }
+    if (!leaf_bound(A, m, l, box)) return false;
     for (int a = 0; a < 3; ++a) { box[a] = box[a] - m.pad; box[3 + a] = box[3 + a] + m.pad; }
     return true;
 }
@@ -167,7 +152,31 @@ __global__ void k_refit_coarse(RefitArrays A, RefitMesh m) {
     }
 }
 
+// One thread per node slot of the mesh's range (cost_term, ft_refit_cost.h).  The block's sum has a fixed shape: xor shuffles within the
+// wave64, the four waves in order through LDS, one partial per block.
+__global__ __launch_bounds__(256) void k_refit_cost(RefitArrays A, RefitMesh m, double* __restrict__ partials) {
+    __shared__ double wave_sum[4];
+    double term = cost_term(A, m, blockIdx.x * 256u + threadIdx.x);
+    for (int off = 32; off > 0; off >>= 1) term += __shfl_xor(term, off);
+    if ((threadIdx.x & 63u) == 0u) wave_sum[threadIdx.x >> 6] = term;
+    __syncthreads();
+    if (threadIdx.x == 0u) partials[blockIdx.x] = ((wave_sum[0] + wave_sum[1]) + wave_sum[2]) + wave_sum[3];
+}
+// One thread: the partials in index order, over the area of the root's stored box.
+__global__ void k_refit_cost_sum(RefitArrays A, RefitMesh m, const double* __restrict__ partials, uint32_t n_partials, double* __restrict__ cost) {
+    if (blockIdx.x != 0u || threadIdx.x != 0u) return;
+    double sum = 0.0;
+    for (uint32_t k = 0; k < n_partials; ++k) sum += partials[k];
+    *cost = cost_of_sum(A, m, sum);
+}
+
 } // namespace
+
+void refit_cost(hipStream_t stream, const RefitArrays& A, const RefitMesh& m, double* partials, double* cost) {
+    const uint32_t blocks = refit_cost_blocks(m);
+    if (blocks) hipLaunchKernelGGL(k_refit_cost, dim3(blocks), dim3(256), 0, stream, A, m, partials);
+    hipLaunchKernelGGL(k_refit_cost_sum, dim3(1), dim3(64), 0, stream, A, m, partials, blocks, cost);
+}
 
 void refit_parents(hipStream_t stream, const RefitArrays& A, const RefitMesh& m) {
     if (m.node_count == 0u) return;

@@ -68,6 +68,10 @@ struct FlatScene {
     // Meshes whose exact BVH is built on the device after the upload (ft_bvh.hip): the flattener only reserves their ranges.
     struct BvhJob { uint32_t mesh, first_global, n, node_base, leaf_base, tri_base, wide_base, coarse_first, coarse_count; };
     std::vector<BvhJob> bvh_jobs;
+    // What build_bsp reserved for a job as zero bytes and the device builder may leave partly untouched: [first, first + count) records of
+    // nodes, bsp_leaves and 4-wide nodes.  A rebuild in place (ft_scene_commit_deformed) puts them back to zero bytes first.
+    struct JobSpans { size_t node_first, node_count, leaf_first, leaf_count, wide_first, wide_count; };
+    static JobSpans reserved_spans(const BvhJob& j) { return JobSpans{j.node_base, (size_t)j.n - 1, j.leaf_base, 2 * (size_t)j.n - 1, j.wide_base, (size_t)j.n - 1}; }
     // What a refit (ft_scene_commit_deformed, ft_refit.hip) needs to find a mesh again: per mesh the builder node it was made from (-1: a
     // bare triangle or a run of them) and the ranges its BVH occupies in nodes / bsp_leaves / tris (the sorted copies) / wide - all counts
     // 0 for a mesh without one; per 4-wide node the binary node it is two levels of (device-built ranges: node_base + its offset).

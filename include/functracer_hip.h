@@ -165,7 +165,10 @@ const char* ft_last_error(const ft_context* ctx);
  * "classify_ahead" / "resolve_aside" / "zero_fill_skip" (1 = default: what a stream of queued frames does that a single frame cannot - the next frame's k_classify on a second
  * stream, k_resolve on a third with the sample colours double-buffered, Colour.Zero not written again into blocks the last frame of the same signature left zero; 0 switches each off; k_resolve goes aside only in frames of one chunk), "mains" (2 = default, 1 .. 3: queued frames of one chunk take turns on that many main streams, so a frame's kernels are dispatched while its predecessor's drain
  * and two frames' reflection levels fill each other's idle stretches), "wave_samples" (0 = default, 16: a bounce-0 wavefront takes up to that many jitter offsets of 64 / that many pixels of an
- * 8x8 block when the sample count has the power of two in it - a narrower bundle; 1, 2, 4, 8, 16; no pixel depends on it).  Every option reaches every device of a context.  Scene-affecting
+ * 8x8 block when the sample count has the power of two in it - a narrower bundle; 1, 2, 4, 8, 16; no pixel depends on it),
+ * "refit_rebuild_percent" (0 = default: never; 100 .. 1000000: ft_scene_commit_deformed builds the tree of an edited, device-built mesh again in place once
+ * its measured cost x 100 exceeds this x its cost as built - "deforming meshes" below; any other value is refused.  It is read by ft_scene_commit_deformed
+ * alone and needs no new ft_scene_commit).  Every option reaches every device of a context.  Scene-affecting
  * options need a new ft_scene_commit.  Any other key is refused (FT_ERR_INVALID, "unknown option"). */
 int32_t ft_set_option(ft_context* ctx, const char* key, int64_t value);
 
@@ -548,14 +551,37 @@ int32_t ft_scene_commit_moved(ft_context* ctx);
  * an edited mesh loses its pair records (ft_debug_light_space: 0xFFFFFFFF), so its directional shadow rays walk the refit BVH as option 0
  * does - the same bits - until the next full ft_scene_commit brings the structures back.
  * Tree quality: the refit tree is the OLD vertices' tree around the new ones, so its boxes overlap more the further the mesh moves from
- * the pose it was built in, and the walk slows down while the results stay exact.  A host should interleave a full ft_scene_commit when
- * its deformation has accumulated that far; tools/refit_rate.py measures the k_primary ratio of a refit tree to a fresh one under an
- * accumulating twist (the ratio has not been measured yet).
+ * the pose it was built in, and the walk slows down while the results stay exact.  The library measures how far that has gone:
+ * ft_scene_tree_quality(mesh_node, out) gives the surface-area cost of the mesh's binary tree as it lies in device memory,
+ *    cost = ( sum over the inner nodes of A(stored box) + sum over the leaves of n_tris x A(exact bound of the leaf's triangles) ) / A(root's stored box),
+ *    A(lo, hi) = dx dy + dy dz + dz dx; 0 when the root's area is 0 or not finite,
+ * summed on the device in a fixed order (the same tree gives the same bits on every device and in every run):
+ *    out[0] the cost now; out[1] the cost as built - measured when the tree was last built, by a full commit or by a rebuild in place
+ *    (recorded by the first ft_scene_commit_deformed after a full commit before it rewrites anything, or by an earlier query);
+ *    out[2] 1 if the tree was built on the device and can be rebuilt in place, else 0; out[3] rebuilds in place since the last full commit.
+ *    FT_ERR_INVALID for a null context or out, an invalid handle or a node that is not a bspMesh node; FT_ERR_STATE without a held commit
+ *    (or for a node that is not part of it); FT_ERR_UNSUPPORTED for a mesh without a BVH (depth above 0, or fewer than 8 triangles);
+ *    FT_ERR_NO_DEVICE on a host-only context, in this order.  A node placed under several transforms has one tree and one answer.  The call
+ *    blocks and retires queued frames first; a multi-device context answers from its first device.
+ * out[0] / out[1] is the ratio a host judges by; which ratio is tolerable is the host's choice (DESIGN.md 16.1 lists the ratios of the
+ * test catalogue: a jitter of 1 % stays below 1.25, a permutation of the triangles reaches 5 - 900).  The remedy needs no full commit:
+ * with "refit_rebuild_percent" = P > 0, ft_scene_commit_deformed measures every edited, device-built mesh after its refit and, where
+ * cost now x 100 > P x cost as built, runs the device builder again for that one mesh into the ranges its tree already occupies, from
+ * the records the refit has just written.  Mesh and leaf indices, the tree's root, the 4-wide root and the coarse range do not move,
+ * the temporal accumulation stays open, the pose counter stays, other meshes are not touched, and the results are still those of a fresh
+ * context, bit for bit (the argument above holds for any tree).  The rebuilt tree's cost becomes the cost as built.  The decision is taken
+ * on the first device of a multi-device context and carried out on all of them.  A rebuild the builder refuses (a tree deeper than 40
+ * levels) fails the call with FT_ERR_BUILD, the context then holds no commit, and ft_scene_commit recovers.  ft_get_commit_times: [1]
+ * includes the cost kernels and the rebuilds, [3] becomes the larger of its old value and the rebuilt trees' heights.  Trees built by the
+ * host ("bvh_builder" 0; meshes below 4096 triangles under the default 2) are measured and never rebuilt in place: a host that wants
+ * rebuilds for small meshes sets "bvh_builder" to 1 or 3.  tools/refit_rate.py measures the k_primary ratio of a refit tree to a fresh
+ * one beside the cost ratio, and what a commit that rebuilds costs.
  * A host that never calls these functions gets bit-identical results from everything else.
  * Device memory: 8 bytes per BspNode, 52 per BspLeaf and 4 per 4-wide node of the scene from the first refit on, plus the vertices of
  * the meshes being refit. */
 int32_t ft_sg_set_mesh_triangles(ft_context* ctx, ft_node node, const double* tris, int64_t n_tris);
 int32_t ft_scene_commit_deformed(ft_context* ctx);
+int32_t ft_scene_tree_quality(ft_context* ctx, ft_node mesh_node, double out[4]);
 
 /* The per-leaf matrices of the scene the context holds (the last successful commit's; they stay readable while the graph is being
  * edited), for tests: *n_leaves, and into each non-null array 12 doubles per leaf, the rows of the 3x4 model->world (m2w) and

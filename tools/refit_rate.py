@@ -2,10 +2,13 @@
 """What ft_scene_commit_deformed costs and what the refit tree is worth, on the full-size stand-in mesh (bunny_synth_full.ply, 69.6 K
 faces) as `bspMesh 0` under "bvh_builder" 0 and 3.
 Commit cost: ft_get_commit_times of an ft_scene_commit_deformed against an ft_scene_commit of the same edited graph in the same process
-(the parent's path), `rounds` of each, alternating; medians with min and max.
+(the parent's path), `rounds` of each, alternating; medians with min and max.  Where the tree can be rebuilt in place (builder 3), also
+`rounds` of an ft_scene_commit_deformed that rebuilds ("refit_rebuild_percent" = 200 and, each round, another permutation of the
+triangles - the worst case for a tree that keeps its topology), with how many of them did rebuild.
 Tree quality: k_primary time of a 1920x1080, 1-spp frame after 1, 4 and 16 accumulated steps of a twist about the vertical axis (0.05 rad
 per step between the mesh's bottom and top), traced on the refit tree (one refit per step, each of the previous refit's tree) and on a
-freshly built tree of the same vertices; medians of `frames` frames.
+freshly built tree of the same vertices; medians of `frames` frames.  Beside each k_primary ratio stands the cost ratio
+ft_scene_tree_quality measures for the refit tree (cost now / cost as built), which is what a host sets "refit_rebuild_percent" by.
 Prints one JSON line; run on the GPU box."""
 import json, os, statistics, sys
 import numpy as np
@@ -76,11 +79,26 @@ def main():
                     cost[how][k].append(t[k])
                 cost[how]["total_ms"].append(sum(t[k] for k in keys))
         res = {"commit_cost_ms": {how: {k: stats(v) for k, v in c.items()} for how, c in cost.items()}, "first_refit_ms": first, "tree_quality": {}}
+        if ctx.tree_quality(m)["rebuildable"]:                       # a commit that rebuilds in place
+            build(ctx, tris)
+            ctx.set_option("refit_rebuild_percent", 200)
+            c, rebuilt = {k: [] for k in keys + ("total_ms",)}, 0
+            for r in range(rounds):
+                before = ctx.tree_quality(m)["rebuilds"]
+                ctx.set_mesh_triangles(m, tris[np.random.default_rng(r).permutation(tris.shape[0])])
+                ctx.commit_deformed()
+                t = ctx.commit_times()
+                rebuilt += ctx.tree_quality(m)["rebuilds"] - before
+                for k in keys:
+                    c[k].append(t[k])
+                c["total_ms"].append(sum(t[k] for k in keys))
+            res["commit_cost_ms"]["commit_deformed_rebuild"] = dict({k: stats(v) for k, v in c.items()}, rebuilt=rebuilt)
+            ctx.set_option("refit_rebuild_percent", 0)
         # tree quality: refit step by step from the rest pose, against a fresh build of the same vertices
         build(ctx, tris)
         fresh = ft.Context(0)
         fresh.set_option("bvh_builder", builder)
-        res["tree_quality"]["0"] = {"fresh_k_primary_ms": primary_ms(ctx, cam, frames)}
+        res["tree_quality"]["0"] = {"fresh_k_primary_ms": primary_ms(ctx, cam, frames), "cost": round(ctx.tree_quality(m)["cost"], 4)}
         for step in range(1, 17):
             ctx.set_mesh_triangles(m, twisted(tris, step))
             ctx.commit_deformed()
@@ -89,7 +107,8 @@ def main():
                 build(fresh, twisted(tris, step))
                 b = primary_ms(fresh, cam, frames)
                 same = bool(np.array_equal(ctx.render(cam, 480, 270, 1, np.zeros((1, 2)))[0], fresh.render(cam, 480, 270, 1, np.zeros((1, 2)))[0]))
-                res["tree_quality"][str(step)] = {"refit_k_primary_ms": a, "fresh_k_primary_ms": b, "ratio": round(a["median"] / b["median"], 3), "frames_identical": same}
+                res["tree_quality"][str(step)] = {"refit_k_primary_ms": a, "fresh_k_primary_ms": b, "ratio": round(a["median"] / b["median"], 3),
+                                                  "cost_ratio": round(ctx.tree_quality(m)["ratio"], 3), "frames_identical": same}
         out["builders"][str(builder)] = res
         ctx.close(), fresh.close()
     print(json.dumps(out))
