@@ -345,9 +345,10 @@ int32_t ft_scene_add_positional(ft_context* c, const double pos[3], const double
 
 namespace ftc {
 
+static const char* const kLdsRefusal = "scene needs more than 160 KiB of LDS per workgroup for CSG lists / BSP stacks even with 4 live lanes per wave";
 static int32_t lds_fits(ft_context* c) {
     if (lane_fold_for(c->flat) != 0) return FT_OK;
-    c->err = "scene needs more than 160 KiB of LDS per workgroup for CSG lists / BSP stacks even with 4 live lanes per wave";
+    c->err = kLdsRefusal;
     return FT_ERR_UNSUPPORTED;
 }
 
@@ -459,8 +460,7 @@ int32_t commit_scene(ft_context* c) {
     using clock = std::chrono::steady_clock;
     auto ms_since = [](clock::time_point t0) { return std::chrono::duration<double, std::milli>(clock::now() - t0).count(); };
     for (double& v : c->commit_ms) v = 0.0;
-    c->holds_commit = false;                                        // `flat` is being replaced
-    c->tree_quality.clear();                                        // and with it every tree the costs and rebuild counts were of
+    const bool held = c->holds_commit;
     const auto done = [c](int32_t rc) {
         if (rc == FT_OK) { c->holds_commit = true; c->restructured = false; c->moved_pending = false; c->options_pending = false; for (fth::GraphNode& n : c->graph.nodes) n.deformed = false; }
         return rc;
@@ -472,9 +472,20 @@ int32_t commit_scene(ft_context* c) {
         c->graph.device_bvh = !c->host_only && c->opt.bvh_builder >= 1 && attempt == 0;
         c->graph.device_bvh_min_tris = c->opt.bvh_builder == 2 ? kDeviceBvhMinTris : 0;   // 1: the device's linear BVH, 3: its surface-area tree, whatever the size
         auto t0 = clock::now();
-        int32_t rc = c->graph.flatten(c->flat, c->err);
+        fth::FlatScene fresh;
+        int32_t rc = c->graph.flatten(fresh, c->err);
+        if (rc == FT_OK && !c->host_only && lane_fold_for(fresh) == 0) { rc = FT_ERR_UNSUPPORTED; c->err = kLdsRefusal; }
         c->commit_ms[0] += ms_since(t0);
-        if (rc != FT_OK) return rc;
+        if (rc != FT_OK) {
+            // Refused by the flattener (a limit of the device path; a graph without objects) before anything was replaced:
+            // `flat` and the arrays in HBM are still the previous commit's, whole, and stay renderable - as after a refused
+            // ft_scene_commit_deformed.
+            if (attempt == 0 && held) for (ft_context* d : devices(c)) d->committed = true;
+            return rc;
+        }
+        c->holds_commit = false;                                    // `flat` is being replaced
+        c->tree_quality.clear();                                    // and with it every tree the costs and rebuild counts were of
+        c->flat = std::move(fresh);
         if (c->host_only) { c->committed = true; return done(FT_OK); }
         t0 = clock::now();
         rc = upload_scene(c);

@@ -206,7 +206,10 @@ int32_t ft_scene_add_soft_directional(ft_context* ctx, const double dir[3], int3
 int32_t ft_scene_add_positional(ft_context* ctx, const double pos[3], const double falloff[3],
                                 const double colour[3]);
 /* Flatten the graph, build BSP trees (BspMesh.compile, BspMesh.fs:51-65) and upload to HBM.  The exact BVH that stands in for the
- * linear scan of a `bspMesh 0` (BspMesh.fs:95-97) is built by the host below 4096 triangles and on the device from there on ("bvh_builder" = 2, default). */
+ * linear scan of a `bspMesh 0` (BspMesh.fs:95-97) is built by the host below 4096 triangles and on the device from there on ("bvh_builder" = 2, default).
+ * A graph beyond a limit of the device path (CSG nesting, hits per ray in a CSG subtree, lights, soft-light samples, uv
+ * functions, LDS) is FT_ERR_UNSUPPORTED with a message that names the limit.  A commit the flattener refuses - for a limit, or for a
+ * graph without objects (FT_ERR_STATE) - replaces nothing: the scene committed before it, if any, stays in HBM and stays renderable. */
 int32_t ft_scene_commit(ft_context* ctx);
 /* Wall time of the last ft_scene_commit in ms: [0] flatten on the host (includes the host's BVH builds with "bvh_builder" = 0),
  * [1] BVH builds on the device, [2] uploads and the rest; [3] is not a time: the height of the tallest device-built tree. */
