@@ -1380,10 +1380,15 @@ FT_DEV void trace(const Scene& S, const Ray& r, Query<ANY>& q, uint32_t* lds, bo
                     if (bsp_root >= 0) {
                         Ray rm;
                         to_model(S.leaves + 16ull * arg, (H.flags & LF_XFORM) != 0, r, rm);
+                        bool per_lane = !coherent;
                         if (coherent) {
                             const int32_t wide_root = S.mesh_wide[H.mesh];     // the tree two levels at a time (none: deeper than the packet's stack)
-                            if (wide_root == INT32_MIN || !mesh_bsp_packet<ANY>(S, bsp_root, wide_root, rm, q, arg, lit)) mesh_bsp_narrow<ANY>(S, bsp_root, rm, q, arg, lit);
-                        } else mesh_bsp_query<ANY>(S, bsp_root, rm, q, arg, lit, stack);
+                            // mesh_bsp_narrow keeps one pending left child per level in a WaveStack: a tree taller than its 64 lanes takes
+                            // the per-lane walk, whose LDS stack holds Mesh::max_depth + 1 entries whatever the height
+                            if (wide_root == INT32_MIN && (uint32_t)S.meshes[4 * H.mesh + 2] > 64u) per_lane = true;
+                            else if (wide_root == INT32_MIN || !mesh_bsp_packet<ANY>(S, bsp_root, wide_root, rm, q, arg, lit)) mesh_bsp_narrow<ANY>(S, bsp_root, rm, q, arg, lit);
+                        }
+                        if (per_lane) mesh_bsp_query<ANY>(S, bsp_root, rm, q, arg, lit, stack);
                         break;
                     }
                 }
