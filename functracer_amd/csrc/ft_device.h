@@ -254,18 +254,22 @@ struct AovSource { const uint32_t* tri_src; const int32_t* run_nodes; };   // th
 void launch_aov(const Launch& L, const DevScene& S, const Primary& gen, uint32_t sample, const AovSource& src, const AovOut& out, unsigned long long* counters);
 int occupancy_blocks_aov(size_t lds_bytes, int variant);
 
+// A window of k_aov's planes by position, as the passes below read it: entry i of the window is the pixel pixel_ids[first + i]
+// (y * res_h + x), 0 <= i < n; p, n and colour are three planes of `stride` entries each (x, y, z), leaf one.  A pass fills in the
+// planes it asked k_aov for; the others stay null.
+struct GuideWindow { const uint32_t* pixel_ids; uint32_t first, n; const double *p_plane, *n_plane, *colour; const int32_t* leaf; uint32_t stride; };
+
 // ft_denoise (ft_denoise.hip; the filter is defined in functracer_hip.h and DESIGN.md 11).  The guide record of a pixel, in FRAME
 // layout (index y * res_h + x), one plane per component: what a tap reads of its neighbour (n, p, class: 49 bytes) and what only the
 // pixel itself needs (the demodulation divisor d, the variance factor V: 32 bytes).
 enum : uint8_t { kDenoiseMiss = 0, kDenoiseHit = 1, kDenoiseOutside = 2 };   // outside the request's tiles: no tap matches it
 struct DenoiseGuides { double* n[3]; double* p[3]; double* d[3]; double* v; uint8_t* cls; };
 constexpr size_t kDenoiseGuideBytes = 10 * 8 + 1;
-// k_denoise_scatter: a window of k_aov's planes (n, p, colour as three planes of `stride` entries, leaf; by position in the window)
-// into the guide records of the pixels pixel_ids[first .. first + n), and u0 = frame / d.  sum != null: V from the running sums of an
-// adaptive progressive accumulation over the same list (ProgressiveArgs' layout, n_list entries); else V = 1.
+// k_denoise_scatter: a window of k_aov's planes (n, p, colour, leaf) into the guide records of its pixels, and u0 = frame / d.
+// sum != null: V from the running sums of an adaptive progressive accumulation over the same list (ProgressiveArgs' layout, n_list
+// entries); else V = 1.
 struct DenoiseScatterArgs {
-    const uint32_t* pixel_ids; uint32_t first, n;
-    const double *n_plane, *p_plane, *colour; const int32_t* leaf; uint32_t stride;
+    GuideWindow win;
     const double* frame; double* u0;
     DenoiseGuides g;
     int32_t demodulate; double albedo_floor;
@@ -290,10 +294,10 @@ void launch_denoise_quantise(hipStream_t stream, const double* rgb, uint8_t* out
 struct TemporalSet { double* m[3]; double* q[3]; double* len; double* p[3]; double* n[3]; int32_t* leaf; };
 constexpr size_t kTemporalSetBytes = 13 * 8 + 4;
 constexpr double kTemporalMinWeight = 1.0 / 16.0;   // FT_TEMPORAL_MIN_WEIGHT (functracer_hip.h; ft_context.h asserts that they agree)
-// k_temporal: one lane per entry of a window of the pixel list.  k_aov's planes of the window (p, n as three planes of `stride`
-// entries, leaf; by position) and the frame's colour at the pixel are blended with what `prev` holds where the pixel's point projects
-// to through the previous call's image plane (o, i, j, k, tlx, tly, pw, ph); the pixel's record goes into `cur`, its mean into
-// out_rgb (frame layout, 3 doubles per pixel) and out8 (RGBA8) where those are non-null.  has_prev == 0: the first call after begin.
+// k_temporal: one lane per entry of a window of the pixel list.  k_aov's planes of the window (p, n, leaf) and the frame's colour
+// at the pixel are blended with what `prev` holds where the pixel's point projects to through the previous call's image plane (o, i,
+// j, k, tlx, tly, pw, ph); the pixel's record goes into `cur`, its mean into out_rgb (frame layout, 3 doubles per pixel) and out8
+// (RGBA8) where those are non-null.  has_prev == 0: the first call after begin.
 // tol_scale = position_tolerance_px * max(pw, ph).  counters[0] += pixels with valid history, counters[1] += pixels at max_history.
 // motion: null (the scene has the pose the history was written in), or one record of kTemporalMotionDoubles per leaf of the scene
 // (n_leaves of them) that takes a hit pixel's point and normal back to that pose before they are projected and compared:
@@ -302,8 +306,7 @@ constexpr double kTemporalMinWeight = 1.0 / 16.0;   // FT_TEMPORAL_MIN_WEIGHT (f
 //   are; [22], [23] unused.
 constexpr int kTemporalMotionDoubles = 24;
 struct TemporalArgs {
-    const uint32_t* pixel_ids; uint32_t first, n;
-    const double *p_plane, *n_plane; const int32_t* leaf; uint32_t stride;
+    GuideWindow win;
     const double* frame;
     TemporalSet prev, cur;
     double o[3], i[3], j[3], k[3], tlx, tly, pw, ph;
@@ -321,12 +324,10 @@ void launch_temporal(hipStream_t stream, const TemporalArgs& a);
 // the iterations alternate between.  Before k_tfilter_prepare the class plane holds kDenoiseOutside outside the tiles and anything
 // else inside; prepare makes that hit or miss.
 struct TFilterPlanes { const double* d[3]; uint8_t* cls; };
-// The demodulate scatter: a window of k_aov's planes (colour as three planes of `stride` entries, leaf; by position in the window)
-// into d of the pixels pixel_ids[first .. first + n): max(colour, albedo_floor) where the set's leaf is a hit and the guide's leaf is
-// the same one, else 1.
+// The demodulate scatter: a window of k_aov's planes (colour, leaf) into d of its pixels: max(colour, albedo_floor) where the set's
+// leaf is a hit and the guide's leaf is the same one, else 1.
 struct TFilterScatterArgs {
-    const uint32_t* pixel_ids; uint32_t first, n;
-    const double* colour; const int32_t* leaf; uint32_t stride;
+    GuideWindow win;
     const int32_t* set_leaf; double* d[3]; double albedo_floor;
 };
 void launch_tfilter_scatter(hipStream_t stream, const TFilterScatterArgs& a);

@@ -27,6 +27,7 @@
 #include <stdint.h>
 
 #include "ft_device.h"
+#include "ft_filter.h"
 
 using namespace ftd;
 
@@ -2586,15 +2587,10 @@ __global__ __launch_bounds__(kBlock) void k_block_lists(BlockListArgs) {
     }
 }
 
-// Image.write's toByte (Image.fs:36; Math.clamp, Math.fs:12-16): clamp to [0, 1] (NaN passes the clamp), * 255, truncate.
-FT_DEV uint32_t to_byte(double x) {
-    if (x > 1.0) x = 1.0; else if (x < 0.0) x = 0.0;
-    x = x * 255.0;
-    return (x != x) ? 0u : (uint32_t)(uint8_t)x;
-}
+// The bytes are Image.write's toByte (store_rgba8, ft_filter.h).
 FT_DEV void write_pixel(double* out_rgb, uint8_t* out_rgba, size_t o, double r, double g, double b) {
     if (out_rgb) { out_rgb[3 * o] = r; out_rgb[3 * o + 1] = g; out_rgb[3 * o + 2] = b; }
-    if (out_rgba) reinterpret_cast<uint32_t*>(out_rgba)[o] = to_byte(r) | (to_byte(g) << 8) | (to_byte(b) << 16) | 0xFF000000u;   // R, G, B, A = 255 in memory order
+    if (out_rgba) store_rgba8(out_rgba, o, r, g, b);
 }
 
 // The end of a frame: the last workgroup to get here copies what the host wants of the counters into the pinned report and clears

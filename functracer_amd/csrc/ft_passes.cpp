@@ -25,6 +25,7 @@ extern "C" {
 // caller's frame-shaped planes.
 namespace {
 struct AovPlanes { int64_t off[8]; int width[8], esz[8]; size_t bytes_per_entry; };   // t, p, n, colour, material, leaf, node, triangle; esz: bytes of an element
+void* aov_plane(const AovPlanes& pl, char* dev, int k) { return pl.off[k] < 0 ? nullptr : dev + pl.off[k]; }   // plane k of the window at `dev`; null: not wanted
 AovPlanes aov_planes(const bool (&want)[8], int64_t per) {
     AovPlanes a{};
     const int width[8] = {1, 3, 3, 3, 3, 1, 1, 1};
@@ -40,6 +41,27 @@ AovPlanes aov_planes(const bool (&want)[8], int64_t per) {
 }
 struct AovRun { int64_t n_pix = 0; unsigned long long hits = 0; double kernel_ms = 0.0; int32_t n_launches = 0; };
 } // namespace
+
+// What the passes below share.  The parameters of the a-trous filters: the iteration count and the sigmas, then (the passes check their
+// own in between) the albedo floor.
+static int32_t check_filter_params(ft_context* c, const std::string& api, int32_t iterations, double sigma_colour, double sigma_normal, double sigma_position) {
+    if (iterations < 0 || iterations > 6) { c->err = api + ": iterations outside 0 .. 6"; return FT_ERR_INVALID; }
+    if (!(sigma_colour >= 0.0) || !(sigma_normal >= 0.0) || !(sigma_position >= 0.0)) { c->err = api + ": a sigma is negative or NaN (0 switches a term off)"; return FT_ERR_INVALID; }
+    return FT_OK;
+}
+static int32_t check_albedo_floor(ft_context* c, const std::string& api, int32_t demodulate, double albedo_floor) {
+    if (demodulate && !(albedo_floor > 0.0)) { c->err = api + ": demodulate needs albedo_floor > 0"; return FT_ERR_INVALID; }
+    return FT_OK;
+}
+static double inv_sq(double sigma) { return sigma > 0.0 ? 1.0 / (sigma * sigma) : 0.0; }   // 1 / sigma^2 as the kernels take it; 0 switches the term off
+// The window [p0, p0 + n) of aov_windows as a kernel reads it: the planes the pass asked k_aov for, the others null.
+static ftk::GuideWindow guide_window(ft_context* c, int64_t p0, uint32_t n, const AovPlanes& pl, char* dev) {
+    return ftk::GuideWindow{c->aov.d_pixels.as<uint32_t>(), (uint32_t)p0, n, static_cast<const double*>(aov_plane(pl, dev, 1)), static_cast<const double*>(aov_plane(pl, dev, 2)),
+                            static_cast<const double*>(aov_plane(pl, dev, 3)), static_cast<const int32_t*>(aov_plane(pl, dev, 5)), n};
+}
+static int32_t read_counters(ft_context* c, const DeviceBuf& buf, unsigned long long (&ctr)[2]) {   // the two counts a pass's kernels kept in `buf`
+    FT_HIP(c, hipMemcpy(ctr, buf.p, sizeof ctr, hipMemcpyDeviceToHost)); return FT_OK;
+}
 
 // The device half of an AOV pass, shared by ft_render_aov and ft_denoise: the pixel list `px` and the pattern go up, and per window of
 // "chunk_samples" entries one k_aov writes the wanted planes into d_aov_out by position in the window.  consume(p0, n, planes, dev) then
@@ -70,15 +92,14 @@ static int32_t aov_windows(ft_context* c, const RenderRequest& q, int32_t sample
         ftk::Primary gen{cam, c->aov.d_pixels.as<uint32_t>(), c->aov.d_jitter.as<double>(), (uint32_t)p0, n, q.spp, (uint32_t)q.res_h, (unsigned long long)q.seed,
                          1.0 / (double)n, 1.0 / (double)q.res_h, nullptr, nullptr};
         gen.group_log2 = 0;
-        auto plane = [&](int k) -> void* { return pl.off[k] < 0 ? nullptr : dev + pl.off[k]; };
-        const ftk::AovOut out{static_cast<double*>(plane(0)), static_cast<double*>(plane(1)), static_cast<double*>(plane(2)), static_cast<double*>(plane(3)),
-                              static_cast<double*>(plane(4)), static_cast<int32_t*>(plane(5)), static_cast<int32_t*>(plane(6)), static_cast<int32_t*>(plane(7)), n};
+        const ftk::AovOut out{static_cast<double*>(aov_plane(pl, dev, 0)), static_cast<double*>(aov_plane(pl, dev, 1)), static_cast<double*>(aov_plane(pl, dev, 2)), static_cast<double*>(aov_plane(pl, dev, 3)),
+                              static_cast<double*>(aov_plane(pl, dev, 4)), static_cast<int32_t*>(aov_plane(pl, dev, 5)), static_cast<int32_t*>(aov_plane(pl, dev, 6)), static_cast<int32_t*>(aov_plane(pl, dev, 7)), n};
         rc = c->aov.timer.run(c, run.kernel_ms, [&] { ftk::launch_aov(L, c->dev_scene, gen, (uint32_t)sample, src, out, c->aov.d_ctr.as<unsigned long long>()); },
                               [&] { ++run.n_launches; return consume(p0, n, pl, dev); });
         if (rc != FT_OK) return rc;
     }
     unsigned long long ctr[2] = {0, 0};
-    FT_HIP(c, hipMemcpy(ctr, c->aov.d_ctr.p, sizeof ctr, hipMemcpyDeviceToHost));
+    if ((rc = read_counters(c, c->aov.d_ctr, ctr)) != FT_OK) return rc;
     if (ctr[1]) { c->err = "CSG hit list overflow"; return FT_ERR_OVERFLOW; }
     run.hits = ctr[0];
     return FT_OK;
@@ -233,9 +254,7 @@ static int32_t denoise_single(ft_context* c, const RenderRequest& q, int32_t sam
         const bool want[8] = {false, true, true, true, false, true, false, false};   // p, n, colour, leaf
         rc = aov_windows(c, q, sample, want, px, run, [&](int64_t p0, uint32_t n, const AovPlanes& pl, char* dev) -> int32_t {
             ftk::DenoiseScatterArgs a{};
-            a.pixel_ids = c->aov.d_pixels.as<uint32_t>(); a.first = (uint32_t)p0; a.n = n;
-            a.p_plane = reinterpret_cast<const double*>(dev + pl.off[1]); a.n_plane = reinterpret_cast<const double*>(dev + pl.off[2]);
-            a.colour = reinterpret_cast<const double*>(dev + pl.off[3]); a.leaf = reinterpret_cast<const int32_t*>(dev + pl.off[5]); a.stride = n;
+            a.win = guide_window(c, p0, n, pl, dev);
             a.frame = frame; a.u0 = c->denoise.d_u[0].as<double>(); a.g = g;
             a.demodulate = P.demodulate ? 1 : 0; a.albedo_floor = P.albedo_floor;
             if (P.use_variance) {
@@ -246,7 +265,6 @@ static int32_t denoise_single(ft_context* c, const RenderRequest& q, int32_t sam
             return timer.run(c, kernel_ms, [&] { ftk::launch_denoise_scatter(c->stream, a); });
         });
         if (rc != FT_OK) return rc;
-        auto inv_sq = [](double sigma) { return sigma > 0.0 ? 1.0 / (sigma * sigma) : 0.0; };
         rc = timer.run(c, kernel_ms, [&] { for (int i = 0; i < P.iterations; ++i) {   // one bracket around all iterations
             const bool last = i + 1 == P.iterations;
             ftk::DenoiseArgs a{};
@@ -278,9 +296,8 @@ int32_t ft_denoise(ft_context* c, const ft_camera* cam, int32_t res_h, int32_t r
     if ((rc = check_guide_sample(c, "ft_denoise", spp, jitter_xy, sample, " to take the guides from")) != FT_OK) return rc;
     if (!params || !out) { c->err = "ft_denoise: null params or out"; return FT_ERR_INVALID; }
     const ft_denoise_params& P = *params;
-    if (P.iterations < 0 || P.iterations > 6) { c->err = "ft_denoise: iterations outside 0 .. 6"; return FT_ERR_INVALID; }
-    if (!(P.sigma_colour >= 0.0) || !(P.sigma_normal >= 0.0) || !(P.sigma_position >= 0.0)) { c->err = "ft_denoise: a sigma is negative or NaN (0 switches a term off)"; return FT_ERR_INVALID; }
-    if (P.demodulate && !(P.albedo_floor > 0.0)) { c->err = "ft_denoise: demodulate needs albedo_floor > 0"; return FT_ERR_INVALID; }
+    if ((rc = check_filter_params(c, "ft_denoise", P.iterations, P.sigma_colour, P.sigma_normal, P.sigma_position)) != FT_OK) return rc;
+    if ((rc = check_albedo_floor(c, "ft_denoise", P.demodulate, P.albedo_floor)) != FT_OK) return rc;
     if (P.use_variance && !(P.variance_floor > 0.0)) { c->err = "ft_denoise: use_variance needs variance_floor > 0"; return FT_ERR_INVALID; }
     if (!need_device(c)) return FT_ERR_NO_DEVICE;
     if ((rc = need_one_device(c, "ft_denoise")) != FT_OK) return rc;
@@ -298,6 +315,21 @@ static ftk::TemporalSet temporal_set(const DeviceBuf& b, size_t n_px) {
     s.leaf = reinterpret_cast<int32_t*>(plane + 13 * n_px);
     return s;
 }
+// `to_frame`: the tile pixels of the frame in HBM become those of `rgb` (frame layout, 3 doubles per pixel).
+static int32_t temporal_to_frame(ft_context* c, const void* rgb) {
+    const ft_context::Temporal& T = c->temporal;
+    const size_t pitch = (size_t)T.res_h * 24;
+    for (const ft_rect& r : T.rects) {
+        const size_t off = (size_t)r.y0 * pitch + (size_t)r.x0 * 24;
+        FT_HIP(c, hipMemcpy2DAsync(c->d_out.as<char>() + off, pitch, static_cast<const char*>(rgb) + off, pitch, (size_t)r.w * 24, (size_t)r.h, hipMemcpyDeviceToDevice, c->stream));
+    }
+    FT_HIP(c, hipStreamSynchronize(c->stream));
+    c->zero_signature[0] = 0;                                       // (as a progressive pass: the blocks the last ft_render left as Colour.Zero hold means now)
+    return FT_OK;
+}
+// The refusals of the calls that need an open accumulation.
+static const char kNoTemporal[] = "no temporal accumulation (ft_temporal_begin)";
+static const char kNoTemporalEnded[] = "no temporal accumulation (ft_temporal_begin; a caller's ft_scene_commit or ft_scene_clear ends it)";
 
 // The records of k_temporal<true> (ftk::kTemporalMotionDoubles per leaf, ft_device.h) for a scene whose leaves stand at (m2w, w2m) now
 // and whose history was written when they stood at (H, Wh).  Per leaf: D = H o w2m, a 3x4 affine product that takes a current world
@@ -382,9 +414,7 @@ static int32_t temporal_single(ft_context* c, const RenderRequest& q, int32_t sa
     const bool want[8] = {false, true, true, false, false, true, false, false};   // p, n, leaf
     rc = aov_windows(c, q, sample, want, px, run, [&](int64_t p0, uint32_t n, const AovPlanes& pl, char* dev) -> int32_t {
         ftk::TemporalArgs a{};
-        a.pixel_ids = c->aov.d_pixels.as<uint32_t>(); a.first = (uint32_t)p0; a.n = n;
-        a.p_plane = reinterpret_cast<const double*>(dev + pl.off[1]); a.n_plane = reinterpret_cast<const double*>(dev + pl.off[2]);
-        a.leaf = reinterpret_cast<const int32_t*>(dev + pl.off[5]); a.stride = n;
+        a.win = guide_window(c, p0, n, pl, dev);
         a.frame = c->d_out.as<double>();
         a.prev = temporal_set(T.d_set[T.prev], n_px); a.cur = temporal_set(T.d_set[T.prev ^ 1], n_px);
         for (int k = 0; k < 3; ++k) { a.o[k] = T.cam.o[k]; a.i[k] = T.cam.i[k]; a.j[k] = T.cam.j[k]; a.k[k] = T.cam.k[k]; }
@@ -400,17 +430,9 @@ static int32_t temporal_single(ft_context* c, const RenderRequest& q, int32_t sa
     });
     if (rc != FT_OK) return rc;                                     // nothing was flipped: the history is as it was
     unsigned long long ctr[2] = {0, 0};
-    if (!px.empty()) FT_HIP(c, hipMemcpy(ctr, T.d_ctr.p, sizeof ctr, hipMemcpyDeviceToHost));
+    if (!px.empty() && (rc = read_counters(c, T.d_ctr, ctr)) != FT_OK) return rc;
     if (out && (rc = copy_rects_out(c, out, rgba8 ? T.d_rgba8.p : T.d_rgb.p, rgba8 ? 4 : 24, T.res_h, T.rects, nullptr)) != FT_OK) return rc;
-    if (P.to_frame && !px.empty()) {                                // the means replace the tile pixels of the frame, once the call can no longer fail
-        const size_t pitch = (size_t)T.res_h * 24;
-        for (const ft_rect& r : T.rects) {
-            const size_t off = (size_t)r.y0 * pitch + (size_t)r.x0 * 24;
-            FT_HIP(c, hipMemcpy2DAsync(c->d_out.as<char>() + off, pitch, T.d_rgb.as<char>() + off, pitch, (size_t)r.w * 24, (size_t)r.h, hipMemcpyDeviceToDevice, c->stream));
-        }
-        FT_HIP(c, hipStreamSynchronize(c->stream));
-        c->zero_signature[0] = 0;                                   // (as a progressive pass: the blocks the last ft_render left as Colour.Zero hold means now)
-    }
+    if (P.to_frame && !px.empty() && (rc = temporal_to_frame(c, T.d_rgb.p)) != FT_OK) return rc;   // the means replace the tile pixels of the frame, once the call can no longer fail
     if (T.calls == 0 || moving) {                                   // the pose the set just written belongs to
         T.h_m2w = c->flat.m2w;
         T.h_w2m.resize(12 * n_leaves);
@@ -436,7 +458,7 @@ int32_t ft_temporal_accumulate(ft_context* c, const ft_camera* cam, int32_t spp,
     if (!(P.position_tolerance_px > 0.0)) { c->err = "ft_temporal_accumulate: position_tolerance_px is not > 0"; return FT_ERR_INVALID; }
     if (!need_device(c)) return FT_ERR_NO_DEVICE;
     if ((rc = need_one_device(c, "ft_temporal_accumulate")) != FT_OK) return rc;
-    if (!c->temporal.open) { c->err = "no temporal accumulation (ft_temporal_begin; a caller's ft_scene_commit or ft_scene_clear ends it)"; return FT_ERR_STATE; }
+    if (!c->temporal.open) { c->err = kNoTemporalEnded; return FT_ERR_STATE; }
     const RenderRequest q{cam, c->temporal.res_h, c->temporal.res_v, spp, jitter_xy, 0, seed, nullptr, 0, 0};   // (the pixel list is made from the begin's rects)
     return with_growing_hit_lists(c, [&] { return temporal_single(c, q, sample, P, rgba8 != 0, out, stats); });
 }
@@ -482,8 +504,7 @@ static int32_t temporal_filter_single(ft_context* c, const RenderRequest& q, int
         const bool want[8] = {false, false, false, true, false, true, false, false};   // colour, leaf
         rc = aov_windows(c, q, sample, want, px, run, [&](int64_t p0, uint32_t n, const AovPlanes& pl, char* dev) -> int32_t {
             ftk::TFilterScatterArgs a{};
-            a.pixel_ids = c->aov.d_pixels.as<uint32_t>(); a.first = (uint32_t)p0; a.n = n;
-            a.colour = reinterpret_cast<const double*>(dev + pl.off[3]); a.leaf = reinterpret_cast<const int32_t*>(dev + pl.off[5]); a.stride = n;
+            a.win = guide_window(c, p0, n, pl, dev);
             a.set_leaf = set.leaf; a.albedo_floor = P.albedo_floor;
             for (int k = 0; k < 3; ++k) a.d[k] = dw[k];
             ++n_launches;
@@ -491,7 +512,6 @@ static int32_t temporal_filter_single(ft_context* c, const RenderRequest& q, int
         });
         if (rc != FT_OK) return rc;
     }
-    auto inv_sq = [](double sigma) { return sigma > 0.0 ? 1.0 / (sigma * sigma) : 0.0; };
     const void* result = T.d_fu[0].p;                               // no iterations: prepare's M
     const double* variance = T.d_fv[0].as<double>();
     rc = timer.run(c, kernel_ms, [&] {                              // one bracket around prepare and all iterations
@@ -520,15 +540,7 @@ static int32_t temporal_filter_single(ft_context* c, const RenderRequest& q, int
     if (rc != FT_OK) return rc;
     if (out && (rc = copy_rects_out(c, out, rgba8 ? T.d_f8.p : result, rgba8 ? 4 : 24, T.res_h, T.rects, nullptr)) != FT_OK) return rc;
     if (out_variance && (rc = copy_rects_out(c, out_variance, variance, 8, T.res_h, T.rects, nullptr)) != FT_OK) return rc;
-    if (P.to_frame) {                                               // the result replaces the tile pixels of the frame, once the call can no longer fail
-        const size_t pitch = (size_t)T.res_h * 24;
-        for (const ft_rect& r : T.rects) {
-            const size_t off = (size_t)r.y0 * pitch + (size_t)r.x0 * 24;
-            FT_HIP(c, hipMemcpy2DAsync(c->d_out.as<char>() + off, pitch, static_cast<const char*>(result) + off, pitch, (size_t)r.w * 24, (size_t)r.h, hipMemcpyDeviceToDevice, c->stream));
-        }
-        FT_HIP(c, hipStreamSynchronize(c->stream));
-        c->zero_signature[0] = 0;                                   // (as ft_temporal_accumulate's to_frame)
-    }
+    if (P.to_frame && (rc = temporal_to_frame(c, result)) != FT_OK) return rc;   // the result replaces them, once the call can no longer fail
     end_pass(stats, run, kernel_ms, n_launches, wall0);
     if (stats) stats->trace_kernel_ms = run.kernel_ms;
     return FT_OK;
@@ -539,19 +551,18 @@ int32_t ft_temporal_filter(ft_context* c, const ft_camera* cam, int32_t spp, con
     if (!c) return FT_ERR_INVALID;
     if (!params || (!out && !out_variance)) { c->err = "ft_temporal_filter: null params, or neither out nor out_variance"; return FT_ERR_INVALID; }
     const ft_temporal_filter_params& P = *params;
-    if (P.iterations < 0 || P.iterations > 6) { c->err = "ft_temporal_filter: iterations outside 0 .. 6"; return FT_ERR_INVALID; }
-    if (!(P.sigma_colour >= 0.0) || !(P.sigma_normal >= 0.0) || !(P.sigma_position >= 0.0)) { c->err = "ft_temporal_filter: a sigma is negative or NaN (0 switches a term off)"; return FT_ERR_INVALID; }
+    int32_t rc;
+    if ((rc = check_filter_params(c, "ft_temporal_filter", P.iterations, P.sigma_colour, P.sigma_normal, P.sigma_position)) != FT_OK) return rc;
     if (P.min_history < 1) { c->err = "ft_temporal_filter: min_history below 1"; return FT_ERR_INVALID; }
     if (!(P.variance_floor > 0.0)) { c->err = "ft_temporal_filter: variance_floor is not > 0"; return FT_ERR_INVALID; }
-    if (P.demodulate && !(P.albedo_floor > 0.0)) { c->err = "ft_temporal_filter: demodulate needs albedo_floor > 0"; return FT_ERR_INVALID; }
-    int32_t rc;
+    if ((rc = check_albedo_floor(c, "ft_temporal_filter", P.demodulate, P.albedo_floor)) != FT_OK) return rc;
     if (P.demodulate) {
         if ((rc = check_guide_sample(c, "ft_temporal_filter", spp, jitter_xy, sample, " to take the material colour from")) != FT_OK) return rc;
         if (!cam) { c->err = "ft_temporal_filter: demodulate needs the camera of the accumulate call"; return FT_ERR_INVALID; }
     }
     if (!need_device(c)) return FT_ERR_NO_DEVICE;
     if ((rc = need_one_device(c, "ft_temporal_filter")) != FT_OK) return rc;
-    if (!c->temporal.open) { c->err = "no temporal accumulation (ft_temporal_begin; a caller's ft_scene_commit or ft_scene_clear ends it)"; return FT_ERR_STATE; }
+    if (!c->temporal.open) { c->err = kNoTemporalEnded; return FT_ERR_STATE; }
     if (c->temporal.calls == 0) { c->err = "ft_temporal_filter: no ft_temporal_accumulate since ft_temporal_begin"; return FT_ERR_STATE; }
     if (P.demodulate && c->temporal.pose != c->pose_serial) {
         c->err = "ft_temporal_filter: demodulate after ft_scene_commit_moved needs an ft_temporal_accumulate first (the guide pass would show another pose than the set)";
@@ -565,7 +576,7 @@ int32_t ft_temporal_fetch(ft_context* c, double* mean_rgb, double* stderr_rgb, d
     if (!c) return FT_ERR_INVALID;
     if (!need_device(c)) return FT_ERR_NO_DEVICE;
     const ft_context::Temporal& T = c->temporal;
-    if (!T.open) { c->err = "no temporal accumulation (ft_temporal_begin)"; return FT_ERR_STATE; }
+    if (!T.open) { c->err = kNoTemporal; return FT_ERR_STATE; }
     const size_t n_px = (size_t)T.res_h * (size_t)T.res_v;
     std::vector<double> h(7 * n_px);                                // M, Q, N of the set the last call wrote
     FT_HIP(c, hipSetDevice(c->device));
@@ -593,7 +604,7 @@ int32_t ft_temporal_status(ft_context* c, int64_t out[4]) {
     if (!c || !out) return FT_ERR_INVALID;
     if (!need_device(c)) return FT_ERR_NO_DEVICE;
     const ft_context::Temporal& T = c->temporal;
-    if (!T.open) { c->err = "no temporal accumulation (ft_temporal_begin)"; return FT_ERR_STATE; }
+    if (!T.open) { c->err = kNoTemporal; return FT_ERR_STATE; }
     out[0] = T.calls; out[1] = T.n_pix; out[2] = T.with_history; out[3] = T.at_max;
     return FT_OK;
 }

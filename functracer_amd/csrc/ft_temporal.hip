@@ -15,31 +15,23 @@
 #include <hip/hip_runtime.h>
 
 #include "ft_device.h"
+#include "ft_filter.h"
 
 namespace ftk {
 namespace {
 
-__device__ __forceinline__ bool finite3(double a, double b, double c) { return isfinite(a) && isfinite(b) && isfinite(c); }
-
-// Image.write's toByte (Image.fs:36, Math.fs:12-16), as ft_quantise_rgba8: clamp to [0, 1] (a NaN passes the clamp), * 255, truncate.
-__device__ __forceinline__ uint32_t to_byte(double x) {
-    if (x > 1.0) x = 1.0; else if (x < 0.0) x = 0.0;
-    x = x * 255.0;
-    return (x != x) ? 0u : (uint32_t)x;
-}
-
 template <bool MOVING> __global__ __launch_bounds__(kBlock) void k_temporal(TemporalArgs a) {
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= a.n) return;
-    const size_t id = a.pixel_ids[a.first + i];                     // y * res_h + x
-    const size_t S = a.stride;
-    const int32_t leaf = a.leaf[i];
+    if (i >= a.win.n) return;
+    const size_t id = a.win.pixel_ids[a.win.first + i];             // y * res_h + x
+    const size_t S = a.win.stride;
+    const int32_t leaf = a.win.leaf[i];
     const bool hit = leaf >= 0;
     const double c0 = a.frame[3 * id], c1 = a.frame[3 * id + 1], c2 = a.frame[3 * id + 2];
     double p0 = 0.0, p1 = 0.0, p2 = 0.0, n0 = 0.0, n1 = 0.0, n2 = 0.0;
     if (hit) {
-        p0 = a.p_plane[i]; p1 = a.p_plane[S + i]; p2 = a.p_plane[2 * S + i];
-        n0 = a.n_plane[i]; n1 = a.n_plane[S + i]; n2 = a.n_plane[2 * S + i];
+        p0 = a.win.p_plane[i]; p1 = a.win.p_plane[S + i]; p2 = a.win.p_plane[2 * S + i];
+        n0 = a.win.n_plane[i]; n1 = a.win.n_plane[S + i]; n2 = a.win.n_plane[2 * S + i];
     }
     // the point and the normal the history is asked about: p and n, or where they were in the pose the history was written in
     double r0 = p0, r1 = p1, r2 = p2, u0 = n0, u1 = n1, u2 = n2;
@@ -114,7 +106,7 @@ template <bool MOVING> __global__ __launch_bounds__(kBlock) void k_temporal(Temp
     a.cur.n[0][id] = n0; a.cur.n[1][id] = n1; a.cur.n[2][id] = n2;
     a.cur.leaf[id] = leaf;
     if (a.out_rgb) { a.out_rgb[3 * id] = M0; a.out_rgb[3 * id + 1] = M1; a.out_rgb[3 * id + 2] = M2; }
-    if (a.out8) reinterpret_cast<uint32_t*>(a.out8)[id] = to_byte(M0) | (to_byte(M1) << 8) | (to_byte(M2) << 16) | 0xFF000000u;
+    if (a.out8) store_rgba8(a.out8, id, M0, M1, M2);
     // the call's two counts: one atomic per wavefront and count (the lanes past the window's end left above; lane 0 never does alone)
     const unsigned long long with_history = __ballot(history), at_max = __ballot(finite && N == a.max_history);
     if ((threadIdx.x & 63u) == 0u) {
@@ -126,9 +118,9 @@ template <bool MOVING> __global__ __launch_bounds__(kBlock) void k_temporal(Temp
 } // namespace
 
 void launch_temporal(hipStream_t stream, const TemporalArgs& a) {
-    if (a.n == 0) return;
-    if (a.motion) hipLaunchKernelGGL(k_temporal<true>, dim3((a.n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, a);
-    else hipLaunchKernelGGL(k_temporal<false>, dim3((a.n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, a);
+    if (a.win.n == 0) return;
+    if (a.motion) hipLaunchKernelGGL(k_temporal<true>, dim3((a.win.n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, a);
+    else hipLaunchKernelGGL(k_temporal<false>, dim3((a.win.n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, a);
 }
 
 } // namespace ftk
