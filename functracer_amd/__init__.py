@@ -249,6 +249,9 @@ class Context(SceneBuilder):
             pass
 
     def set_option(self, key, value):
+        """ft_set_option: an integer tunable by name (include/functracer_hip.h lists them).  Among them "temporal_follow_deformed" (0 / 1,
+        no new commit needed): commit_deformed keeps the records of the meshes it refits as the open temporal accumulation last saw them and
+        the next temporal_accumulate follows their triangles."""
         self._check(self._lib.ft_set_option(self._ctx, key.encode(), int(value)))
 
     def render(self, camera, res_h, res_v, spp, jitter, max_depth=MAX_DEPTH, seed=DEFAULT_SEED, tiles=None, out=None, fetch=True):
@@ -429,7 +432,8 @@ class Context(SceneBuilder):
         of the surfaces render_aov reports for (camera, spp, jitter, sample, seed), looked up where they lay in the previous call's
         image.  params: max_history, to_frame, min_normal_dot, position_tolerance_px (_capi.TEMPORAL_DEFAULTS).  Returns (the
         accumulated rgb[res_v, res_h, 3] float64 or rgba[res_v, res_h, 4] uint8, stats dict); pixels outside the tiles keep what
-        `out` held (0 in a fresh array); with fetch=False nothing is copied out (returns (None, stats))."""
+        `out` held (0 in a fresh array); with fetch=False nothing is copied out (returns (None, stats)).  After a commit_moved the history
+        follows the moved leaves; after a commit_deformed under set_option("temporal_follow_deformed", 1) it follows the triangles."""
         unknown = set(params) - set(_capi.TEMPORAL_DEFAULTS)
         if unknown:
             raise ValueError(f"unknown temporal parameters {sorted(unknown)}")
@@ -523,7 +527,8 @@ class Context(SceneBuilder):
 
     def commit_deformed(self):
         """ft_scene_commit_deformed: commit a graph whose mesh vertices alone changed since the last commit by refitting the trees on the
-        device.  A temporal accumulation stays open; a progressive accumulation ends."""
+        device.  A temporal accumulation stays open; a progressive accumulation ends.  Under set_option("temporal_follow_deformed", 1) the
+        edited meshes' records are kept as the accumulation last saw them (72 bytes per triangle, until the next temporal_accumulate)."""
         self._check(self._lib.ft_scene_commit_deformed(self._ctx))
         self._progressive = None
 

@@ -191,6 +191,8 @@ const OptionSpec kOptions[] = {
     {"csg_auto_grow", 0, 1, &Options::csg_auto_grow, nullptr, kFlag},
     {"primary_block_lists", 0, 1, &Options::primary_block_lists, nullptr, kFlag},
     {"uniform_surface", 0, 1, &Options::uniform_surface, nullptr, kFlag},
+    // read by ft_scene_commit_deformed and ft_temporal_accumulate: no commit depends on it either
+    {"temporal_follow_deformed", 0, 1, &Options::temporal_follow_deformed, nullptr, kFlag},
     // read by ft_scene_commit_deformed alone: no commit depends on it, so it leaves the committed scene as it is
     {"refit_rebuild_percent", 100, 1000000, &Options::refit_rebuild_percent, nullptr, kOrZero},
     {"csg_mesh_capacity", 1, 255, nullptr, [](fth::SceneGraph& g, int64_t v) { g.csg_mesh_capacity = (int32_t)v; }, kCommit},
@@ -213,6 +215,7 @@ int32_t ft_set_option(ft_context* c, const char* key, int64_t value) {
             for (hipStream_t m : d->more_mains) if (!m) d->opt.mains = 1;   // (without them every frame takes the one main stream)
             d->dev_scene.coherent_waves = d->opt.coherent_waves ? 1 : 0;
             d->dev_scene.uniform_surface = d->opt.uniform_surface ? 1 : 0;
+            if (!d->opt.temporal_follow_deformed) temporal_drop_snapshots(d);   // (nothing to do unless the option has just gone back to 0)
             if (o.rules & kCommit) { d->committed = false; c->options_pending = true; }
             if (o.rules & kLevelHint) d->staged_hint = -1;
             if (o.rules & kZeroFill) d->zero_signature[0] = d->zero_signature[1] = 0;
@@ -570,6 +573,41 @@ static int32_t rebuild_in_place(ft_context* c, const fth::FlatScene& f, const ft
     return FT_OK;
 }
 
+// The list-order records of every mesh of `edits` that holds no snapshot yet, copied device to device behind what the accumulation
+// already keeps (ft_context::Temporal::d_snap), on the context's stream: ahead of the refit kernels that overwrite them.
+static int32_t snapshot_records(ft_context* c, const fth::FlatScene& f, const std::vector<DeformedMesh>& edits) {
+    ft_context::Temporal& T = c->temporal;
+    std::vector<ft_context::Temporal::Snapshot> fresh;
+    size_t need = T.snap_used;
+    for (const DeformedMesh& e : edits) {
+        bool held = false;
+        for (const ft_context::Temporal::Snapshot& s : T.snaps) held = held || s.mesh == e.mesh;
+        const ftk::RefitMesh m = refit_ranges(f, e.mesh, 0.0);
+        if (held || m.n == 0 || (size_t)m.first_global + m.n > f.tris.size() / 9) continue;
+        fresh.push_back({e.mesh, (uint32_t)need, m.n});
+        need += m.n;
+    }
+    if (fresh.empty()) return FT_OK;
+    if (need > 0xFFFFFFFFull) { c->err = "ft_scene_commit_deformed: more than 2^32 triangles to snapshot"; return FT_ERR_INVALID; }
+    int32_t rc;
+    if (T.d_snap.bytes < need * 72) {                               // grows by a buffer of the new size that takes over what is kept
+        DeviceBuf grown;
+        if ((rc = ensure(c, grown, need * 72)) != FT_OK) return rc;
+        if (T.snap_used) FT_HIP(c, hipMemcpyAsync(grown.p, T.d_snap.p, T.snap_used * 72, hipMemcpyDeviceToDevice, c->stream));
+        FT_HIP(c, hipStreamSynchronize(c->stream));
+        T.d_snap.release();
+        T.d_snap = grown;
+    }
+    const double* tris = c->d_scene[kTris].as<double>();
+    for (const ft_context::Temporal::Snapshot& s : fresh) {
+        const ftk::RefitMesh m = refit_ranges(f, s.mesh, 0.0);
+        FT_HIP(c, hipMemcpyAsync(T.d_snap.as<double>() + 9 * (size_t)s.first, tris + 9 * (size_t)m.first_global, (size_t)s.n * 72, hipMemcpyDeviceToDevice, c->stream));
+        T.snaps.push_back(s);
+    }
+    T.snap_used = need;
+    return FT_OK;
+}
+
 // What the context's first device decides for the others ("refit_rebuild_percent"): per edit whether its tree is rebuilt in place, and the
 // tallest tree the rebuilds made.
 struct RebuildPlan { std::vector<uint8_t> rebuild; uint32_t tallest = 0; };
@@ -607,6 +645,9 @@ static int32_t refit_device(ft_context* c, const fth::FlatScene& f, const fth::S
         if (!v.empty()) FT_HIP(c, hipMemcpyAsync(R.d_verts.as<double>() + at, v.data(), v.size() * 8, hipMemcpyHostToDevice, c->stream));
         at += v.size();
     }
+    // "temporal_follow_deformed": what the open accumulation's history saw of each edited mesh, before the first refit since the last
+    // accumulate overwrites it (later ones keep it, so several deformations between two accumulates compose)
+    if (c->opt.temporal_follow_deformed && c->temporal.open && c->temporal.calls > 0 && (rc = snapshot_records(c, f, edits)) != FT_OK) return rc;
     if ((rc = upload(c, B[kLeaves], f.leaves)) != FT_OK || (rc = upload(c, B[kCulls], f.culls)) != FT_OK) return rc;
     cull_items_image(f, c->cull_items_and_rows);
     if ((rc = upload(c, B[kCullItems], c->cull_items_and_rows)) != FT_OK) return rc;

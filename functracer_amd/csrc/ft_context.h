@@ -96,6 +96,7 @@ struct Options {
     int64_t csg_auto_grow = 1;      // ft_render: double csg_mesh_capacity and render again when a hit list overflows (read on device 0)
     int64_t primary_block_lists = 1;   // k_block_lists: the primaries of a classified frame over ONE bare mesh test their block's candidate list; 0: the tree walk everywhere
     int64_t refit_rebuild_percent = 0;   // ft_scene_commit_deformed rebuilds a device-built tree in place once cost now x 100 > this x cost as built; 0: never (not a commit-time option)
+    int64_t temporal_follow_deformed = 0;   // ft_scene_commit_deformed keeps a mesh's records as the history saw them and ft_temporal_accumulate follows them
     int64_t uniform_surface = 1;    // k_primary: one-leaf batches take leaf and material through scalar loads, dead shader work and empty-list batches are skipped; 0: per lane, everything (A/B)
 };
 
@@ -294,12 +295,20 @@ struct ft_context {
         uint64_t pose = 0;
         std::vector<double> h_m2w, h_w2m;
         DeviceBuf d_motion;
+        // "temporal_follow_deformed" (DESIGN.md 16.2): the list-order records (9 doubles per triangle) of every mesh refit since the last
+        // accumulate, as they lay in HBM before its first refit - `n` records of mesh `mesh` at record `first` of d_snap (snap_used of them
+        // in all); d_deform: the call's records for k_temporal<MOVING, true> (ftk::TemporalDeformLeaf per leaf).  Dropped by every
+        // successful accumulate, with the accumulation, and when the option goes back to 0 (ftc::temporal_drop_snapshots).
+        struct Snapshot { uint32_t mesh, first, n; };
+        std::vector<Snapshot> snaps;
+        size_t snap_used = 0;
+        DeviceBuf d_snap, d_deform;
         // ft_temporal_filter's planes, frame-sized, allocated by the first filter call of the accumulation: the divisor d,
         // the class, the two colour buffers and the two variance planes the iterations alternate between, and the RGBA8 result
         DeviceBuf d_fd, d_fcls, d_fu[2], d_fv[2], d_f8;
         TimedLaunch ftimer;             // around the kernels of a filter call (kernel_ms)
         void release() {
-            for (DeviceBuf* b : {&d_set[0], &d_set[1], &d_rgb, &d_rgba8, &d_ctr, &d_motion, &d_fd, &d_fcls, &d_fu[0], &d_fu[1], &d_fv[0], &d_fv[1], &d_f8}) b->release();
+            for (DeviceBuf* b : {&d_set[0], &d_set[1], &d_rgb, &d_rgba8, &d_ctr, &d_motion, &d_snap, &d_deform, &d_fd, &d_fcls, &d_fu[0], &d_fu[1], &d_fv[0], &d_fv[1], &d_f8}) b->release();
             timer.release(); ftimer.release(); *this = Temporal();
         }
     } temporal;
@@ -382,5 +391,6 @@ int32_t with_growing_hit_lists(ft_context* c, const std::function<int32_t()>& ru
 RenderRequest progressive_request(const ft_context::Progressive& P);
 void progressive_close(ft_context* c);
 void temporal_close(ft_context* c);
+void temporal_drop_snapshots(ft_context* c);
 
 } // namespace ftc

@@ -255,9 +255,10 @@ void launch_aov(const Launch& L, const DevScene& S, const Primary& gen, uint32_t
 int occupancy_blocks_aov(size_t lds_bytes, int variant);
 
 // A window of k_aov's planes by position, as the passes below read it: entry i of the window is the pixel pixel_ids[first + i]
-// (y * res_h + x), 0 <= i < n; p, n and colour are three planes of `stride` entries each (x, y, z), leaf one.  A pass fills in the
-// planes it asked k_aov for; the others stay null.
-struct GuideWindow { const uint32_t* pixel_ids; uint32_t first, n; const double *p_plane, *n_plane, *colour; const int32_t* leaf; uint32_t stride; };
+// (y * res_h + x), 0 <= i < n; p, n and colour are three planes of `stride` entries each (x, y, z), leaf and triangle one.  A pass fills
+// in the planes it asked k_aov for; the others stay null.  (triangle comes first: behind stride it shifts the kernel arguments of the
+// kernels that do not read it, and k_temporal<false> and k_temporal<true> then schedule to 4 more bytes of code - DESIGN.md 16.2.)
+struct GuideWindow { const int32_t* triangle; const uint32_t* pixel_ids; uint32_t first, n; const double *p_plane, *n_plane, *colour; const int32_t* leaf; uint32_t stride; };
 
 // ft_denoise (ft_denoise.hip; the filter is defined in functracer_hip.h and DESIGN.md 11).  The guide record of a pixel, in FRAME
 // layout (index y * res_h + x), one plane per component: what a tap reads of its neighbour (n, p, class: 49 bytes) and what only the
@@ -305,6 +306,12 @@ constexpr double kTemporalMinWeight = 1.0 / 16.0;   // FT_TEMPORAL_MIN_WEIGHT (f
 //   inverse of D's linear part (a normal goes back through its transpose); [21] 1.0 if the leaf moved, 0.0: p and n are used as they
 //   are; [22], [23] unused.
 constexpr int kTemporalMotionDoubles = 24;
+// deform: null, or one record per leaf of the scene for k_temporal<MOVING, true> ("temporal_follow_deformed"): a hit pixel
+// on a leaf whose mesh was snapshotted before a refit (n > 0) and whose triangle (the window's triangle plane) changed goes back to
+// where its material point was - its barycentric coordinates in the live record tris[first_live + triangle], the same coordinates in
+// snap[snap_first + triangle] (9 doubles each: v0, e1, e2), then H.  W: the live w2m of the leaf; H, Wh: its m2w and the linear part of
+// its w2m in the pose the history was written in (rows).  Such a pixel does not take the motion record's way: this one ends in that pose.
+struct TemporalDeformLeaf { double W[12], H[12], Wh[9]; uint32_t first_live, snap_first, n, pad; };
 struct TemporalArgs {
     GuideWindow win;
     const double* frame;
@@ -315,6 +322,7 @@ struct TemporalArgs {
     double* out_rgb; uint8_t* out8;
     unsigned long long* counters;
     const double* motion; uint32_t n_leaves;
+    const TemporalDeformLeaf* deform; const double *tris, *snap;
 };
 void launch_temporal(hipStream_t stream, const TemporalArgs& a);
 

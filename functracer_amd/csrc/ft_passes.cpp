@@ -12,6 +12,16 @@ void temporal_close(ft_context* c) {
     c->temporal.release();
 }
 
+// The snapshots of "temporal_follow_deformed" and their device memory let go: the history has caught up with the meshes (a successful
+// accumulate), or nothing will follow them (the option back at 0).
+void temporal_drop_snapshots(ft_context* c) {
+    ft_context::Temporal& T = c->temporal;
+    if (T.snaps.empty() && !T.d_snap.p && !T.d_deform.p) return;
+    (void)hipSetDevice(c->device);
+    T.snaps.clear(); T.snap_used = 0;
+    T.d_snap.release(); T.d_deform.release();
+}
+
 } // namespace ftc
 using namespace ftc;
 
@@ -56,8 +66,8 @@ static int32_t check_albedo_floor(ft_context* c, const std::string& api, int32_t
 static double inv_sq(double sigma) { return sigma > 0.0 ? 1.0 / (sigma * sigma) : 0.0; }   // 1 / sigma^2 as the kernels take it; 0 switches the term off
 // The window [p0, p0 + n) of aov_windows as a kernel reads it: the planes the pass asked k_aov for, the others null.
 static ftk::GuideWindow guide_window(ft_context* c, int64_t p0, uint32_t n, const AovPlanes& pl, char* dev) {
-    return ftk::GuideWindow{c->aov.d_pixels.as<uint32_t>(), (uint32_t)p0, n, static_cast<const double*>(aov_plane(pl, dev, 1)), static_cast<const double*>(aov_plane(pl, dev, 2)),
-                            static_cast<const double*>(aov_plane(pl, dev, 3)), static_cast<const int32_t*>(aov_plane(pl, dev, 5)), n};
+    return ftk::GuideWindow{static_cast<const int32_t*>(aov_plane(pl, dev, 7)), c->aov.d_pixels.as<uint32_t>(), (uint32_t)p0, n, static_cast<const double*>(aov_plane(pl, dev, 1)),
+                            static_cast<const double*>(aov_plane(pl, dev, 2)), static_cast<const double*>(aov_plane(pl, dev, 3)), static_cast<const int32_t*>(aov_plane(pl, dev, 5)), n};
 }
 static int32_t read_counters(ft_context* c, const DeviceBuf& buf, unsigned long long (&ctr)[2]) {   // the two counts a pass's kernels kept in `buf`
     FT_HIP(c, hipMemcpy(ctr, buf.p, sizeof ctr, hipMemcpyDeviceToHost)); return FT_OK;
@@ -356,6 +366,27 @@ static std::vector<double> temporal_motion(const fth::FlatScene& f, const std::v
     return rec;
 }
 
+// The records of k_temporal<MOVING, true> (ftk::TemporalDeformLeaf per leaf, ft_device.h): every mesh leaf whose mesh holds a snapshot gets
+// its live w2m, the m2w and the linear part of the w2m the history was written under, and where its live and its kept records start;
+// every other leaf n = 0.  A snapshot whose mesh no longer has the range it was taken from is left out (n = 0).
+static std::vector<ftk::TemporalDeformLeaf> temporal_deform(const fth::FlatScene& f, const ft_context::Temporal& T) {
+    std::vector<ftk::TemporalDeformLeaf> rec(f.leaves.size(), ftk::TemporalDeformLeaf{});
+    for (size_t l = 0; l < f.leaves.size(); ++l) {
+        const ftd::Leaf& L = f.leaves[l];
+        if (L.kind != ftd::LK_MESH || L.mesh >= f.meshes.size() || f.meshes[L.mesh].root >= 0 || (size_t)~f.meshes[L.mesh].root >= f.bsp_leaves.size()) continue;
+        const ftd::BspLeaf& list = f.bsp_leaves[(size_t)~f.meshes[L.mesh].root];
+        for (const ft_context::Temporal::Snapshot& s : T.snaps) {
+            if (s.mesh != L.mesh || s.n != list.n_tris || (size_t)list.first_tri + s.n > f.tris.size() / 9 || (size_t)s.first + s.n > T.snap_used) continue;
+            ftk::TemporalDeformLeaf& r = rec[l];
+            std::memcpy(r.W, L.w2m, sizeof r.W);
+            std::memcpy(r.H, &T.h_m2w[12 * l], sizeof r.H);
+            for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) r.Wh[3 * i + j] = T.h_w2m[12 * l + 4 * i + j];
+            r.first_live = list.first_tri; r.snap_first = s.first; r.n = s.n;
+        }
+    }
+    return rec;
+}
+
 int32_t ft_temporal_begin(ft_context* c, int32_t res_h, int32_t res_v, const ft_rect* tiles, int32_t n_tiles) {
     if (!c) return FT_ERR_INVALID;
     if (res_h < 2 || res_v < 2 || (tiles && n_tiles < 1) || (int64_t)res_h * res_v > (int64_t)0x7FFFFFFF) { c->err = "bad ft_temporal_begin argument"; return FT_ERR_INVALID; }
@@ -403,15 +434,19 @@ static int32_t temporal_single(ft_context* c, const RenderRequest& q, int32_t sa
     // pose of the last accumulate, so they compose): every leaf's way back to that pose goes up and k_temporal<true> runs.
     const size_t n_leaves = c->flat.leaves.size();
     const bool moving = T.calls > 0 && T.pose != c->pose_serial;
-    if (moving) {
+    // "temporal_follow_deformed": meshes were refit since the history was written and their records of then are kept: k_temporal<true, true>
+    // runs, with the triangle plane in its windows
+    const bool following = c->opt.temporal_follow_deformed && T.calls > 0 && !T.snaps.empty();
+    if (moving || following) {
         if (T.h_m2w.size() != 12 * n_leaves || T.h_w2m.size() != 12 * n_leaves) { c->err = "ft_temporal_accumulate: the scene has other leaves than the history"; return FT_ERR_STATE; }
-        if ((rc = upload(c, T.d_motion, temporal_motion(c->flat, T.h_m2w, T.h_w2m))) != FT_OK) return rc;
+        if (moving && (rc = upload(c, T.d_motion, temporal_motion(c->flat, T.h_m2w, T.h_w2m))) != FT_OK) return rc;
+        if (following && (rc = upload(c, T.d_deform, temporal_deform(c->flat, T))) != FT_OK) return rc;
         FT_HIP(c, hipStreamSynchronize(c->stream));                 // (the records are a temporary)
     }
     double kernel_ms = 0.0;
     int32_t n_launches = 0;
     AovRun run;
-    const bool want[8] = {false, true, true, false, false, true, false, false};   // p, n, leaf
+    const bool want[8] = {false, true, true, false, false, true, false, following};   // p, n, leaf; the triangle only in a call that follows
     rc = aov_windows(c, q, sample, want, px, run, [&](int64_t p0, uint32_t n, const AovPlanes& pl, char* dev) -> int32_t {
         ftk::TemporalArgs a{};
         a.win = guide_window(c, p0, n, pl, dev);
@@ -425,6 +460,7 @@ static int32_t temporal_single(ft_context* c, const RenderRequest& q, int32_t sa
         a.out_rgb = want_rgb ? T.d_rgb.as<double>() : nullptr; a.out8 = want_rgba8 ? T.d_rgba8.as<uint8_t>() : nullptr;
         a.counters = T.d_ctr.as<unsigned long long>();
         a.motion = moving ? T.d_motion.as<double>() : nullptr; a.n_leaves = (uint32_t)n_leaves;
+        if (following) { a.deform = T.d_deform.as<ftk::TemporalDeformLeaf>(); a.tris = c->d_scene[kTris].as<double>(); a.snap = T.d_snap.as<double>(); }
         ++n_launches;
         return T.timer.run(c, kernel_ms, [&] { ftk::launch_temporal(c->stream, a); });
     });
@@ -439,6 +475,7 @@ static int32_t temporal_single(ft_context* c, const RenderRequest& q, int32_t sa
         for (size_t l = 0; l < n_leaves; ++l) std::memcpy(&T.h_w2m[12 * l], c->flat.leaves[l].w2m, 12 * sizeof(double));
         T.pose = c->pose_serial;
     }
+    temporal_drop_snapshots(c);                                     // the set just written saw the meshes as they are
     T.prev ^= 1; T.cam = cam; T.calls += 1;
     T.with_history = (int64_t)ctr[0]; T.at_max = (int64_t)ctr[1];
     end_pass(stats, run, kernel_ms, n_launches, wall0);

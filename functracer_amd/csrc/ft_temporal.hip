@@ -12,6 +12,13 @@
 // lane whose leaf moved takes its point and normal back to that pose through the leaf's motion record (kTemporalMotionDoubles) before
 // the projection and the tap tests; every other lane, and k_temporal<false>, runs the statements below on p and n themselves.  The
 // lanes of a wavefront mostly share a leaf, so the record's 176 bytes are one or two cache lines read by every lane at the same address.
+//
+// k_temporal<MOVING, true> runs when "temporal_follow_deformed" is set and a mesh was snapshotted before its refit (ft_scene_commit_deformed,
+// DESIGN.md 16.2): a hit lane whose triangle changed solves for its barycentric coordinates in the live record and takes the same
+// coordinates in the snapshot's record back through H.  It reads its leaf's TemporalDeformLeaf (280 bytes at one address for the lanes
+// that share the leaf) and two records of 72 bytes; the lanes of an 8x8 block lie on a few neighbouring triangles, so those are a
+// few cache lines per wavefront, read once each: staging them in LDS would add a barrier and save no fetch.  The leaf index and the
+// triangle index come from planes and are range-checked before they address anything.
 #include <hip/hip_runtime.h>
 
 #include "ft_device.h"
@@ -20,7 +27,7 @@
 namespace ftk {
 namespace {
 
-template <bool MOVING> __global__ __launch_bounds__(kBlock) void k_temporal(TemporalArgs a) {
+template <bool MOVING, bool DEFORMING = false> __global__ __launch_bounds__(kBlock) void k_temporal(TemporalArgs a) {
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= a.win.n) return;
     const size_t id = a.win.pixel_ids[a.win.first + i];             // y * res_h + x
@@ -35,7 +42,50 @@ template <bool MOVING> __global__ __launch_bounds__(kBlock) void k_temporal(Temp
     }
     // the point and the normal the history is asked about: p and n, or where they were in the pose the history was written in
     double r0 = p0, r1 = p1, r2 = p2, u0 = n0, u1 = n1, u2 = n2;
-    if (MOVING && hit && a.has_prev && (uint32_t)leaf < a.n_leaves) {
+    bool followed = false;                                          // through the snapshot: the way back already ends in the history's pose
+    if (DEFORMING && hit && a.has_prev && (uint32_t)leaf < a.n_leaves) {
+        const TemporalDeformLeaf* L = a.deform + (size_t)leaf;
+        const uint32_t tau = (uint32_t)a.win.triangle[i], n_m = L->n;   // n_m = 0: the leaf's mesh holds no snapshot
+        if (tau < n_m) {
+            const double* live = a.tris + 9ull * ((size_t)L->first_live + tau);
+            const double* old = a.snap + 9ull * ((size_t)L->snap_first + tau);
+            double T[9], O[9];
+            bool same = true;
+#pragma unroll
+            for (int k = 0; k < 9; ++k) { T[k] = live[k]; O[k] = old[k]; same = same && __double_as_longlong(T[k]) == __double_as_longlong(O[k]); }
+            if (!same) {
+                const double* Wm = L->W;
+                const double q0 = Wm[0] * p0 + Wm[1] * p1 + Wm[2] * p2 + Wm[3];     // the hit point in model space
+                const double q1 = Wm[4] * p0 + Wm[5] * p1 + Wm[6] * p2 + Wm[7];
+                const double q2 = Wm[8] * p0 + Wm[9] * p1 + Wm[10] * p2 + Wm[11];
+                const double d0 = q0 - T[0], d1 = q1 - T[1], d2 = q2 - T[2];
+                const double d11 = T[3] * T[3] + T[4] * T[4] + T[5] * T[5], d12 = T[3] * T[6] + T[4] * T[7] + T[5] * T[8];
+                const double d22 = T[6] * T[6] + T[7] * T[7] + T[8] * T[8];
+                const double h1 = d0 * T[3] + d1 * T[4] + d2 * T[5], h2 = d0 * T[6] + d1 * T[7] + d2 * T[8];
+                const double det = d11 * d22 - d12 * d12;
+                if (det > 0.0) {                                    // (a collapsed triangle, or a NaN, keeps the existing path)
+                    const double beta = (d22 * h1 - d12 * h2) / det, gamma = (d11 * h2 - d12 * h1) / det;
+                    if (isfinite(beta) && isfinite(gamma)) {
+                        followed = true;
+                        const double w0 = O[0] + beta * O[3] + gamma * O[6], w1 = O[1] + beta * O[4] + gamma * O[7], w2 = O[2] + beta * O[5] + gamma * O[8];
+                        const double* Hm = L->H;
+                        r0 = Hm[0] * w0 + Hm[1] * w1 + Hm[2] * w2 + Hm[3];
+                        r1 = Hm[4] * w0 + Hm[5] * w1 + Hm[6] * w2 + Hm[7];
+                        r2 = Hm[8] * w0 + Hm[9] * w1 + Hm[10] * w2 + Hm[11];
+                        const double g0 = T[4] * T[8] - T[5] * T[7], g1 = T[5] * T[6] - T[3] * T[8], g2 = T[3] * T[7] - T[4] * T[6];       // e1 x e2
+                        const double f0 = O[4] * O[8] - O[5] * O[7], f1 = O[5] * O[6] - O[3] * O[8], f2 = O[3] * O[7] - O[4] * O[6];
+                        const double c0n = Wm[0] * g0 + Wm[4] * g1 + Wm[8] * g2, c1n = Wm[1] * g0 + Wm[5] * g1 + Wm[9] * g2, c2n = Wm[2] * g0 + Wm[6] * g1 + Wm[10] * g2;
+                        const double side = (n0 * c0n + n1 * c1n + n2 * c2n < 0.0) ? -1.0 : 1.0;   // the side of the triangle the shaders' normal is on
+                        const double* Wh = L->Wh;
+                        const double t0 = Wh[0] * f0 + Wh[3] * f1 + Wh[6] * f2, t1 = Wh[1] * f0 + Wh[4] * f1 + Wh[7] * f2, t2 = Wh[2] * f0 + Wh[5] * f1 + Wh[8] * f2;
+                        const double s = 1.0 / sqrt(t0 * t0 + t1 * t1 + t2 * t2);   // (a non-finite result fails every tap's normal test)
+                        u0 = side * t0 * s; u1 = side * t1 * s; u2 = side * t2 * s;
+                    }
+                }
+            }
+        }
+    }
+    if (MOVING && !(DEFORMING && (followed || !a.motion)) && hit && a.has_prev && (uint32_t)leaf < a.n_leaves) {
         const double* rec = a.motion + (size_t)leaf * kTemporalMotionDoubles;
         if (rec[21] != 0.0) {
             r0 = rec[0] * p0 + rec[1] * p1 + rec[2] * p2 + rec[3];      // D (p, 1), rows left to right
@@ -119,8 +169,10 @@ template <bool MOVING> __global__ __launch_bounds__(kBlock) void k_temporal(Temp
 
 void launch_temporal(hipStream_t stream, const TemporalArgs& a) {
     if (a.win.n == 0) return;
-    if (a.motion) hipLaunchKernelGGL(k_temporal<true>, dim3((a.win.n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, a);
-    else hipLaunchKernelGGL(k_temporal<false>, dim3((a.win.n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, a);
+    const dim3 grid((a.win.n + kBlock - 1) / kBlock), block(kBlock);
+    if (a.deform) hipLaunchKernelGGL((k_temporal<true, true>), grid, block, 0, stream, a);   // (a null motion table: no leaf moved)
+    else if (a.motion) hipLaunchKernelGGL(k_temporal<true>, grid, block, 0, stream, a);
+    else hipLaunchKernelGGL(k_temporal<false>, grid, block, 0, stream, a);
 }
 
 } // namespace ftk

@@ -168,7 +168,11 @@ const char* ft_last_error(const ft_context* ctx);
  * 8x8 block when the sample count has the power of two in it - a narrower bundle; 1, 2, 4, 8, 16; no pixel depends on it),
  * "refit_rebuild_percent" (0 = default: never; 100 .. 1000000: ft_scene_commit_deformed builds the tree of an edited, device-built mesh again in place once
  * its measured cost x 100 exceeds this x its cost as built - "deforming meshes" below; any other value is refused.  It is read by ft_scene_commit_deformed
- * alone and needs no new ft_scene_commit).  Every option reaches every device of a context.  Scene-affecting
+ * alone and needs no new ft_scene_commit),
+ * "temporal_follow_deformed" (0 = default; any other value means 1: ft_scene_commit_deformed keeps the triangle records of the meshes it refits as the open
+ * temporal accumulation last saw them, and the next ft_temporal_accumulate takes every pixel on a changed triangle back to where that point of the triangle was -
+ * "history on deforming meshes" below.  It needs no new ft_scene_commit; a host-only or multi-device context accepts it without effect, because the accumulation
+ * lives on a single device; with 0 every call launches the kernels and gives the bits it gave before the option existed).  Every option reaches every device of a context.  Scene-affecting
  * options need a new ft_scene_commit.  Any other key is refused (FT_ERR_INVALID, "unknown option"). */
 int32_t ft_set_option(ft_context* ctx, const char* key, int64_t value);
 
@@ -515,7 +519,7 @@ int32_t ft_temporal_filter(ft_context* ctx, const ft_camera* cam, int32_t spp, c
  * accumulate, not at the last commit.
  * What follows a leaf is its history, not its shading: light that changes on a moving surface (it turns towards a light, a shadow
  * sweeps over it) is averaged as noise is, max_history bounding how long it lingers.  Lights do not move; meshes deform through
- * ft_scene_commit_deformed (below), which moves no history.
+ * ft_scene_commit_deformed (below), whose history follows the triangles with "temporal_follow_deformed" ("history on deforming meshes").
  * ft_temporal_filter with `demodulate` returns FT_ERR_STATE between an ft_scene_commit_moved and the next ft_temporal_accumulate (its
  * guide pass would show another pose than the set); without `demodulate` it runs as before.
  * A host that never calls these functions gets bit-identical results from everything else.
@@ -538,8 +542,8 @@ int32_t ft_scene_commit_moved(ft_context* ctx);
  *  - On success every later call - ft_render, ft_render_enqueue, ft_progressive_*, ft_render_aov, ft_denoise, the ft_debug_* ray queries -
  *    gives what it gives on a fresh context whose graph was built with the new vertices and committed with ft_scene_commit, bit for bit.
  *  - It ends a progressive accumulation, retires queued frames first (as every commit does), leaves the temporal accumulation OPEN and
- *    does not advance the pose counter: a deformed leaf gets no special treatment, clause 2's leaf, normal and position tests decide pixel
- *    by pixel whether the history still fits.  On a multi-device context every device refits its own copy.  A host-only context checks
+ *    does not advance the pose counter: by default a deformed leaf gets no special treatment, clause 2's leaf, normal and position tests
+ *    decide pixel by pixel whether the history still fits ("temporal_follow_deformed" = 1: "history on deforming meshes" below).  On a multi-device context every device refits its own copy.  A host-only context checks
  *    the same rules and then runs the full host commit.
  *  - ft_get_commit_times: [0] host work, [1] the refit kernels, [2] uploads, [3] unchanged.  The first refit after a full commit also
  *    derives the trees' parent links on the device, inside [1].
@@ -585,6 +589,36 @@ int32_t ft_scene_commit_moved(ft_context* ctx);
 int32_t ft_sg_set_mesh_triangles(ft_context* ctx, ft_node node, const double* tris, int64_t n_tris);
 int32_t ft_scene_commit_deformed(ft_context* ctx);
 int32_t ft_scene_tree_quality(ft_context* ctx, ft_node mesh_node, double out[4]);
+/* ---- history on deforming meshes ("temporal_follow_deformed") ----------------------------------- */
+/* Without the option the history of a deformed mesh survives only where its surface stayed within clause 2's position tolerance.  With
+ * ft_set_option("temporal_follow_deformed", 1) the history follows the triangles, as it follows moved leaves:
+ * The snapshot.  A successful ft_scene_commit_deformed on the device path copies, before it refits a mesh, the mesh's list-order triangle
+ * records (v0, e1, e2: 72 bytes per triangle) as they lie in device memory into a buffer of the temporal accumulation - if the option is
+ * 1, an accumulation is open with at least one successful ft_temporal_accumulate behind it, and the mesh holds no snapshot yet.  Only the
+ * first commit after an accumulate snapshots a mesh: several deformations between two accumulates compose by construction, as H is the
+ * pose at the last accumulate.  Meshes that were not edited get none; a commit refused on the host takes none; the rebuild in place
+ * ("refit_rebuild_percent") does not touch list-order records.  The copy is part of ft_get_commit_times [2].  Snapshots are dropped at
+ * the end of every successful ft_temporal_accumulate, by ft_temporal_begin and ft_temporal_end, by whatever ends the accumulation (a
+ * full commit, ft_scene_clear, the context) and when the option is set to 0; a failed accumulate keeps them.
+ * The take-back, in an ft_temporal_accumulate with the option 1, a call behind it and at least one snapshot.  A hit pixel x takes it when
+ * its leaf l = leaf(x) is a mesh leaf whose mesh m holds a snapshot and tau = triangle(x) (ft_render_aov's plane) satisfies 0 <= tau < n_m,
+ * compared unsigned.  With (a, e1, e2) the live record of triangle tau of m, (a', e1', e2') the snapshot's, W = w2m_cur(l), H = H_l and
+ * Wh = Wh_l ("moving rigid objects": the live matrices unless an ft_scene_commit_moved intervened), every sum left to right as written:
+ *   if the 18 doubles of the two records are bitwise equal, the pixel takes the path it takes without the option (p and n, or D_l);
+ *   q_i = W[i][0] p_0 + W[i][1] p_1 + W[i][2] p_2 + W[i][3];  r = q - a;
+ *   d11 = e1.e1, d12 = e1.e2, d22 = e2.e2, r1 = r.e1, r2 = r.e2, det = d11 * d22 - d12 * d12;  if !(det > 0), that path too;
+ *   beta = (d22 * r1 - d12 * r2) / det, gamma = (d11 * r2 - d12 * r1) / det;  if either is not finite, that path too;
+ *   q'_i = a'_i + beta e1'_i + gamma e2'_i;  pr_i = H[i][0] q'_0 + H[i][1] q'_1 + H[i][2] q'_2 + H[i][3];
+ *   g = e1 x e2, g' = e1' x e2';  c_j = W[0][j] g_0 + W[1][j] g_1 + W[2][j] g_2;  s = (n(x).c < 0) ? -1 : 1 (the side of the triangle
+ *   the shaders' normal is on);  t_j = Wh[0][j] g'_0 + Wh[1][j] g'_1 + Wh[2][j] g'_2;  nr = s * t * (1 / sqrt(t.t)).
+ * Clauses 1 to 3 then use pr and nr wherever they use p(x) and n(x), exactly as for a moved leaf; a non-finite nr fails every tap; clause
+ * 2's leaf test is unchanged; clause 6 stores the current p, n, leaf.  For such pixels this replaces the D_l route - it already ends in the
+ * history's pose - so a mesh that is both moved and deformed between two accumulates is followed through both.  A triangle that did not
+ * change, a pixel on another leaf and a miss pixel get the bits they get without the option.
+ * As for moving objects, what follows a triangle is its history, not its shading: light that changes on a bending surface is averaged as
+ * noise is.  ft_temporal_filter with `demodulate` between a deform and the next accumulate behaves as it does without the option.
+ * Device memory: 72 bytes per triangle of each snapshotted mesh until the next accumulate, 280 bytes per leaf and 4 more bytes per pixel
+ * of ft_render_aov's window (the triangle plane) in a call that follows. */
 
 /* The per-leaf matrices of the scene the context holds (the last successful commit's; they stay readable while the graph is being
  * edited), for tests: *n_leaves, and into each non-null array 12 doubles per leaf, the rows of the 3x4 model->world (m2w) and
