@@ -54,6 +54,7 @@ def hip_lib():
         lib.ft_get_commit_times.argtypes = [C.c_void_p, _capi.c_double_p]
         lib.ft_debug_scene_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
         lib.ft_debug_devices.argtypes = [C.c_void_p, _capi.c_int32_p, C.c_int32]
+        lib.ft_debug_classify_reuse.restype, lib.ft_debug_classify_reuse.argtypes = C.c_int32, [C.c_void_p, C.POINTER(C.c_int64)]
         lib.ft_debug_mesh_trees.restype, lib.ft_debug_mesh_trees.argtypes = C.c_int32, _capi.MESH_TREES_SIGNATURE
         lib.ft_debug_slice.argtypes = [_capi.c_double_p] * 4 + [_capi.c_int32_p, _capi.c_double_p, _capi.c_int32_p]
         lib.ft_render_enqueue.argtypes = [C.c_void_p, C.POINTER(_capi.ft_camera), C.c_int32, C.c_int32, C.c_int32, _capi.c_double_p, C.c_int32, C.c_uint64, C.POINTER(_capi.ft_rect), C.c_int32]
@@ -639,6 +640,14 @@ class Context(SceneBuilder):
         entries = np.zeros(sizes[1], dtype=_capi.LIST_ENTRY_DTYPE)
         self._check(fn(self._ctx, sizes, plane.ctypes.data, heads.ctypes.data, pos_block.ctypes.data, entries.ctypes.data))
         return {"leaf": int(sizes[2]), "heads": heads, "pos_block": pos_block, "entries": entries, "plane": plane, "capacity": int(sizes[3])}
+
+    def classify_reuse(self):
+        """ft_debug_classify_reuse: what the frames queued since the context was created did with their classifications (option
+        "classify_reuse"), summed over its devices - a dict of `classified` (k_classify launched), `reused` (a slot's kept classification
+        read as it was), `windows_launched` and `windows_skipped` (windows past the end of a kept active list)."""
+        out = (C.c_int64 * 4)()
+        self._check(self._lib.ft_debug_classify_reuse(self._ctx, out))
+        return dict(zip(_capi.CLASSIFY_REUSE_FIELDS, (int(v) for v in out)))
 
     def scene_info(self):
         out = (C.c_int64 * 12)()

@@ -148,6 +148,8 @@ AOV_CHANNELS = [("t", np.float64, 1, np.inf), ("p", np.float64, 3, 0.0), ("n", n
                 ("material", np.float64, 3, 0.0), ("leaf", np.int32, 1, -1), ("node", np.int32, 1, -1), ("triangle", np.int32, 1, -1)]
 
 
+# ft_debug_classify_reuse: its four counts, in order
+CLASSIFY_REUSE_FIELDS = ("classified", "reused", "windows_launched", "windows_skipped")
 # ft_debug_block_lists: an entry of a block's candidate list (ft_device.h, kListEntryWords) and the header of a block that has none
 LIST_ENTRY_DTYPE = np.dtype([("tri", np.uint32), ("orig", np.uint32), ("x0", np.float32), ("x1", np.float32), ("y0", np.float32), ("y1", np.float32)])
 LIST_NONE = 0xFFFFFFFF

@@ -165,8 +165,8 @@ const char* ft_last_error(const ft_context* c) { return c ? c->err.c_str() : "nu
 // The keys of ft_set_option.  A flag takes any value as 0 / 1; any other value must lie in [lo, hi] (and be 0 or a power of two where
 // kPowerOfTwo says so).  It goes into an Options member of every device of the context, or into device 0's scene graph: the peers
 // receive the scene flattened on device 0.  kCommit / kLevelHint / kZeroFill: a change invalidates the committed scene, the staged
-// level hint, the zero-fill signatures.  kOrZero: 0 is valid beside [lo, hi].
-enum { kFlag = 1, kPowerOfTwo = 2, kCommit = 4, kLevelHint = 8, kZeroFill = 16, kOrZero = 32 };
+// level hint, the zero-fill signatures.  kOrZero: 0 is valid beside [lo, hi].  kClassified: setting it drops what the frame slots keep of their last classification.
+enum { kFlag = 1, kPowerOfTwo = 2, kCommit = 4, kLevelHint = 8, kZeroFill = 16, kOrZero = 32, kClassified = 64 };
 struct OptionSpec {
     const char* key;
     int64_t lo, hi;
@@ -180,16 +180,17 @@ const OptionSpec kOptions[] = {
     {"wave_samples", 0, 16, &Options::wave_samples, nullptr, kPowerOfTwo},   // 1 .. 16 samples per wavefront (k_resolve's LDS tile holds 16)
     {"coherent_waves", 0, 1, &Options::coherent_waves, nullptr, kFlag},
     {"timing", 0, 2, &Options::timing, nullptr, 0},
-    {"classify_pixels", 0, 1, &Options::classify_pixels, nullptr, kFlag},
+    {"classify_pixels", 0, 1, &Options::classify_pixels, nullptr, kFlag | kClassified},
     {"follow_below", -1, kNoLimit, &Options::follow_below, nullptr, kLevelHint},
     {"level_hint", 0, 1, &Options::level_hint, nullptr, kFlag},
     {"classify_ahead", 0, 1, &Options::classify_ahead, nullptr, kFlag},
     {"resolve_aside", 0, 1, &Options::resolve_aside, nullptr, kFlag},
     {"zero_fill_skip", 0, 1, &Options::zero_fill_skip, nullptr, kFlag | kZeroFill},
+    {"classify_reuse", 0, 1, &Options::classify_reuse, nullptr, kFlag | kClassified},
     {"mains", 1, ft_context::kMains, &Options::mains, nullptr, 0},
     {"bvh_builder", 0, 3, &Options::bvh_builder, nullptr, kCommit},
     {"csg_auto_grow", 0, 1, &Options::csg_auto_grow, nullptr, kFlag},
-    {"primary_block_lists", 0, 1, &Options::primary_block_lists, nullptr, kFlag},
+    {"primary_block_lists", 0, 1, &Options::primary_block_lists, nullptr, kFlag | kClassified},
     {"uniform_surface", 0, 1, &Options::uniform_surface, nullptr, kFlag},
     // read by ft_scene_commit_deformed and ft_temporal_accumulate: no commit depends on it either
     {"temporal_follow_deformed", 0, 1, &Options::temporal_follow_deformed, nullptr, kFlag},
@@ -219,6 +220,7 @@ int32_t ft_set_option(ft_context* c, const char* key, int64_t value) {
             if (o.rules & kCommit) { d->committed = false; c->options_pending = true; }
             if (o.rules & kLevelHint) d->staged_hint = -1;
             if (o.rules & kZeroFill) d->zero_signature[0] = d->zero_signature[1] = 0;
+            if (o.rules & kClassified) for (auto& F : d->slots) { F.kept.valid = false; F.keeps = false; }   // (a frame still queued goes on reading its slot's buffers)
         }
         return FT_OK;
     }
@@ -434,7 +436,7 @@ static int32_t upload_scene(ft_context* c) {
     if (rc == FT_OK) rc = upload(c, c->d_scene[kTriSrc], f.tri_src);
     if (rc == FT_OK) rc = upload(c, c->d_scene[kRunNodes], f.run_nodes);
     if (rc != FT_OK) return rc;
-    for (auto& F : c->slots) { if ((rc = ensure(c, F.d_fc, sizeof(ftk::FrameCounters))) != FT_OK) return rc; F.fc_clean = false; }
+    for (auto& F : c->slots) { if ((rc = ensure(c, F.d_fc, sizeof(ftk::SlotCounters))) != FT_OK) return rc; F.fc_clean = false; }
     c->zero_signature[0] = c->zero_signature[1] = 0;
     FT_HIP(c, hipStreamSynchronize(c->stream));
     {   // the BVHs the flattener left to the device (ft_bvh.hip), straight into the ranges reserved in the arrays just uploaded

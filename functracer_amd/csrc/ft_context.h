@@ -89,6 +89,7 @@ struct Options {
     int64_t classify_ahead = 1;     // 0 keeps every kernel on the one stream
     int64_t resolve_aside = 1;      // 0 keeps k_resolve on the main stream
     int64_t zero_fill_skip = 1;     // 0 writes Colour.Zero into every finished block of every frame
+    int64_t classify_reuse = 1;     // 0 classifies every classified frame again, whatever its slot still holds (A/B)
     int64_t mains = 2;              // 1 .. 3: main streams in use (measured: 2 is best - the headline 0.263 / 0.231 / 0.249 ms with 1 / 2 / 3, hollow-sphere x1 0.703 / 0.471 / 0.470)
     int64_t bvh_builder = 2;        // who builds the exact BVH of top-level-Leaf meshes: 0 = the host (swept surface-area split: the best tree, 1.2 ms for 980
                                     // triangles but 160 ms for 69.6 K), 1 = the device's linear BVH (ft_bvh.hip: ~1 ms, traces ~9 % slower), 3 = the device's
@@ -138,6 +139,21 @@ struct Brackets {
         boundary = b; fresh = true;
     }
     void release() { for (hipEvent_t e : events) (void)hipEventDestroy(e); events.clear(); used = 0; }
+};
+
+// What decides every word k_classify and k_block_lists write for a frame (neither reads the sample count, the offsets themselves or the
+// wave grouping): the fields are compared, not hashed.
+struct ClassifyKey {
+    uint64_t commit_serial = 0;
+    int32_t res_h = 0, res_v = 0, list_leaf = -1;
+    double jitter_extent = 0.0;
+    ftk::Camera cam{};
+    std::vector<ft_rect> rects;      // the tiles clipped to the frame: they and res_h decide the pixel list
+    bool operator==(const ClassifyKey& o) const {
+        return commit_serial == o.commit_serial && res_h == o.res_h && res_v == o.res_v && list_leaf == o.list_leaf &&
+               std::memcmp(&jitter_extent, &o.jitter_extent, sizeof jitter_extent) == 0 && std::memcmp(&cam, &o.cam, sizeof cam) == 0 &&
+               rects.size() == o.rects.size() && (rects.empty() || std::memcmp(rects.data(), o.rects.data(), rects.size() * sizeof(ft_rect)) == 0);
+    }
 };
 
 struct ft_context {
@@ -209,7 +225,13 @@ struct ft_context {
         DeviceBuf d_list_heads, d_list_pool;    // k_block_lists: a header per active block, the entries (ftk::BlockLists)
         int32_t list_leaf = -1;                 // the mesh leaf this slot's frame carries lists for; -1: none
         ftk::Camera list_cam{};                 // that frame's image plane (ft_debug_block_lists)
-        bool fc_clean = false;                  // d_fc is all zero: the slot's previous frame cleared it behind its report (no fill needed)
+        // "classify_reuse": what d_block_pos, d_pos_block, the lists and SlotCounters::kept hold.  `valid` from the retirement, without
+        // error, of the frame that classified into them until anything makes that untrue; a frame of the same key then launches neither
+        // k_classify nor k_block_lists.  n_active, culled: what that frame's report said (the active list's length; ft_stats'
+        // rays_primary_culled is made from the other, which a frame that reuses the buffers does not count again).
+        struct Classified { bool valid = false; ClassifyKey key; int64_t n_active = 0; uint64_t culled = 0; } kept;
+        bool keeps = false, reuses = false;     // the pending frame fills `kept` when it retires / reads the buffers as they are
+        bool fc_clean = false;                  // d_fc's FrameCounters are all zero: the slot's previous frame cleared it behind its report (no fill needed)
         Brackets ev;
         bool simple = false;                    // one chunk, k_resolve aside
         int main_ix = 0;                        // the main stream it traces on
@@ -217,7 +239,7 @@ struct ft_context {
         ftk::FrameReport* d_report = nullptr;   // written by the frame's last kernel through this device-side address of the same memory
         uint64_t signature = 0;                 // what the frame rendered (scene, size, samples, depth, threshold): keys the staged-launch hint
         bool pending = false;
-        uint64_t rays_primary = 0; int64_t n_pix_total = 0; int32_t spp = 0, n_launches = 0, n_chunks = 0, format = 0; bool classify = false;
+        uint64_t rays_primary = 0; int64_t n_pix_total = 0; int32_t spp = 0, n_launches = 0, n_chunks = 0, format = 0; bool classify = false;   // (n_launches, n_chunks: as planned from the request, FramePlan::n_planned)
         std::chrono::steady_clock::time_point wall0;
         void release() {
             d_block_pos.release(); d_pos_block.release(); d_fc.release(); d_list_heads.release(); d_list_pool.release();
@@ -241,6 +263,7 @@ struct ft_context {
     struct TreeQuality { double cost_built = 0.0; bool known = false; uint32_t rebuilds = 0; };
     std::vector<TreeQuality> tree_quality;
     int slot_turn = 0;
+    int64_t reuse_counts[4] = {0, 0, 0, 0};   // since ft_create: classifications launched / reused, windows launched / skipped (ft_debug_classify_reuse)
     int last_classified_slot = -1;   // the slot of the last frame queued if that frame was classified, else -1 (ft_debug_block_lists)
     // Levels of the reflection tree worth launching: the host cannot know how deep the rays of a frame go without waiting, and a
     // k_bounce launch that finds no rays still costs a few microseconds.  It launches as many levels as the previous frame of the

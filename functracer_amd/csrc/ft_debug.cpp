@@ -237,6 +237,15 @@ int32_t ft_debug_block_lists(ft_context* c, int64_t sizes[4], double plane[4], u
     return FT_OK;
 }
 
+// What the frame driver did with the classifications and windows of the frames queued since ft_create, summed over the context's devices.
+int32_t ft_debug_classify_reuse(ft_context* c, int64_t out[4]) {
+    if (!c || !out) return FT_ERR_INVALID;
+    if (c->host_only) return FT_ERR_NO_DEVICE;
+    for (int k = 0; k < 4; ++k) out[k] = 0;
+    for (const ft_context* d : devices(c)) for (int k = 0; k < 4; ++k) out[k] += d->reuse_counts[k];
+    return FT_OK;
+}
+
 int32_t ft_debug_slice(const double p0[3], const double n[3], const double tri[9], double above[18], int32_t* n_above, double below[18], int32_t* n_below) {
     if (!p0 || !n || !tri || !above || !below || !n_above || !n_below) return FT_ERR_INVALID;
     std::vector<double> a, b; std::string err;

@@ -77,24 +77,27 @@ struct RenderCounters {
 };
 constexpr int kStatStripes = 64;
 // Everything a frame's kernels count in, in one allocation so that ONE fill clears it: the chunk counters (cleared again before
-// every further chunk), the statistic stripes, the length of the active pixel list and k_classify's ticket / error words.
+// every further chunk), the statistic stripes and k_classify's ticket / error words.
 struct FrameCounters {
     ChunkCounters cc;
     RenderCounters stats[kStatStripes];
-    PixCount counts;
     uint32_t classify_ticket;      // k_classify: waves take their 64-block segment in ticket order, so a wave's predecessors are always running
     uint32_t classify_error;       // set when a bounded wait ran out (never observed; the host then fails the frame instead of hanging)
     uint32_t report_ticket;        // k_resolve / k_report: ticket stripes that are complete (the workgroup that completes the last one writes the frame's report)
     uint32_t list_cursor;          // k_block_lists: entries of the slot's list pool handed out so far
     uint32_t report_stripe[64];    // workgroups of stripe blockIdx % 64 that have finished (8000 tickets on one word took 80 us)
 };
+// A frame slot's counters as they lie in HBM.  `kept`, the length of the active pixel list in the slot's classification buffers, is
+// outside what the hand-over and the host's fills clear: only k_classify writes it, so that a later frame of the same view can read the
+// buffers and their length as they are ("classify_reuse").
+struct SlotCounters { FrameCounters fc; PixCount kept; };
 // What the host reads of a frame's counters, in pinned host memory.  The last workgroup of the frame's last k_resolve writes it and
 // then clears the FrameCounters for the next frame: a steady stream of frames needs no fill and no device-to-host copy in between
 // (three dispatches less per frame, ~20 us of a 0.4 ms frame with the gaps around them).
 struct FrameReport {               // 256 bytes: one wavefront writes it with one store instruction (word by word over PCIe a report of
     RenderCounters total;          // all 64 stripes took 200 us); the stripes summed in stripe order
     uint32_t n_rays[kMaxBounce + 2];   // the last chunk's rays per bounce
-    uint32_t n_pix_active;         // PixCount::n_pix
+    uint32_t n_pix_active;         // the length of the frame's active list (SlotCounters::kept); 0 for a frame that was not classified
     uint32_t classify_error;
     uint32_t pad[12];
 };
@@ -146,10 +149,10 @@ int occupancy_blocks_bounce(size_t lds_bytes, int variant);
 // ray bundle - all samples of its pixels - is bounded by a cone through its outermost jittered corners and tested against every
 // top-level item (bare meshes also against their coarse boxes).  Blocks nothing can be hit from get block_pos = -1 (k_resolve writes
 // their pixels as Colour.Zero; none of their rays is ever generated); the others are appended, in block order, to the frame's active
-// pixel list (pos_block: the block of the pixel list behind each block of the active list), whose length lands in fc->counts.  `epoch` tags this frame's entries of wave_counts.
+// pixel list (pos_block: the block of the pixel list behind each block of the active list), whose length lands in out.kept.  `epoch` tags this frame's entries of wave_counts.
 // Progressive passes (ft_progressive_pass) also hand over their blocks' words (ProgressiveArgs::blk_in): a retired block is neither listed nor
 // finished but gets block_pos = kBlockRetired; with `mask_only` the cone and box tests are skipped and every block that has not retired is listed.
-struct ClassifyOut { int32_t* block_pos; uint32_t* pos_block; uint32_t* wave_counts; };
+struct ClassifyOut { int32_t* block_pos; uint32_t* pos_block; uint32_t* wave_counts; PixCount* kept; };
 constexpr int32_t kBlockRetired = -2;
 void launch_classify(const Launch& L, const DevScene& S, const Primary& gen_list, const ClassifyOut& out, double jitter_extent, uint32_t epoch, FrameCounters* fc,
                      const uint32_t* retired = nullptr, bool mask_only = false);
@@ -158,10 +161,10 @@ void launch_classify(const Launch& L, const DevScene& S, const Primary& gen_list
 // the image plane overlaps the block's.  heads[b], for block b of the active list: kListNone (more than kListCap triangles, the pool
 // is full, or the pyramid is degenerate: the block's rays walk the tree) or first entry << 7 | count.  An entry is kListEntryWords
 // words: the triangle's record in DevScene::tris, its list index (tri_orig), and the rectangle x0, x1, y0, y1 as floats, rounded outward,
-// in the (jx, jy) coordinates of the primary rays.  fc->list_cursor hands out the pool.
+// in the (jx, jy) coordinates of the primary rays.  fc->list_cursor hands out the pool; `counts`: the length of the active list (ClassifyOut::kept).
 constexpr uint32_t kListNone = 0xFFFFFFFFu, kListCap = 64, kListEntryWords = 6;
 struct BlockLists { uint32_t* heads; uint32_t* pool; uint32_t pool_entries; int32_t leaf; };
-void launch_block_lists(const Launch& L, const DevScene& S, const Primary& gen_list, const uint32_t* pos_block, const BlockLists& out, double jitter_extent, FrameCounters* fc);
+void launch_block_lists(const Launch& L, const DevScene& S, const Primary& gen_list, const uint32_t* pos_block, const BlockLists& out, double jitter_extent, FrameCounters* fc, const PixCount* counts);
 // The frame's pixels: mean over the spp samples of each pixel of the chunk's window, in sample order (Image.fs:112-116), written as
 // FP64 RGB (out_rgb) and / or as Image.write's RGBA8 bytes (out_rgba, Image.fs:36); with `zero_culled` also Colour.Zero for every
 // pixel of the blocks k_classify finished.  Pixel p of the list goes to out index pixel_ids[p] (whole frame) or p (tiles, packed).
@@ -192,7 +195,7 @@ constexpr uint32_t kRetired = 0x80000000u;
 // k_resolve of a progressive pass: each pixel's sum goes on from its running sum (same additions in the same order as one k_resolve
 // over the concatenated pattern), mean = S / n out, S / Q / n back, retirement per block; finished blocks add spp zero samples.
 void launch_resolve_progressive(const Launch& L, const ResolveArgs& a, const ProgressiveArgs& pa);
-void launch_report(const Launch& L, FrameCounters* fc, FrameReport* report);   // the same hand-over as a launch of its own (frames that end in another kernel)
+void launch_report(const Launch& L, FrameCounters* fc, FrameReport* report);   // the same hand-over as a launch of its own (frames that end in another kernel: none of them is classified)
 // CornerSampling.blendPixels (Image.fs:134-144) for a w x h rect whose (w+1) x (h+1) corner colours are in acc (one sample each).
 void launch_resolve_corner(const Launch& L, const double* acc, uint32_t acc_stride, uint32_t w, uint32_t h, const uint32_t* out_index, double* out_rgb, uint8_t* out_rgba);
 // Device-side BVH build (ft_bvh.hip): a linear BVH over triangles [first_global, first_global + n) of `tris`, written into the ranges

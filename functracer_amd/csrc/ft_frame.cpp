@@ -48,9 +48,20 @@ int32_t check_request(ft_context* c, const RenderRequest& q) {
 static int32_t retire_frame(ft_context* c, ft_context::FrameSlot& F, ft_stats* stats) {
     if (!F.pending) return FT_OK;
     F.pending = false;
+    // "classify_reuse": a frame that classified leaves its slot's buffers described by `kept` once it has ended without error; one that
+    // read them as they were leaves them so.  Any error drops the record.
+    const bool keeps = F.keeps, reuses = F.reuses;
+    const bool held = F.kept.valid;                                 // (a change of option may have dropped the record under a queued frame)
+    F.keeps = F.reuses = false;
+    F.kept.valid = false;
     if (F.ev.ev1) FT_HIP(c, hipEventSynchronize(F.ev.ev1)); else FT_HIP(c, hipStreamSynchronize(c->stream));
-    const ftk::RenderCounters hrc = F.h_report->total;              // the stripes, summed by the frame's last kernel
+    ftk::RenderCounters hrc = F.h_report->total;                    // the stripes, summed by the frame's last kernel
     const bool classify_failed = F.h_report->classify_error != 0;
+    if (reuses) hrc.pixels_culled = F.kept.culled;                  // counted by the frame that classified; this one's stripes hold 0
+    if ((keeps || (reuses && held)) && !classify_failed && !hrc.csg_overflow) {
+        F.kept.valid = true;
+        if (keeps) { F.kept.n_active = (int64_t)F.h_report->n_pix_active; F.kept.culled = hrc.pixels_culled; }
+    }
     // How deep this frame's rays went in numbers worth a launch (more than "follow_below" rays; levels followed in registers count
     // theirs too): the next frame of the same signature launches that many levels + 1, and that last one follows what is left.
     int deepest = 0;
@@ -143,6 +154,12 @@ struct FramePlan {
     int group_log2 = 0, last_bounce = 0;
     int32_t list_leaf = -1;              // >= 0: the frame carries per-block candidate lists for this bare mesh leaf (k_block_lists)
     ftk::Camera cam{};
+    // "classify_reuse": the key of what this frame's classification writes (keepable: a plain classified frame; a progressive pass's
+    // depends on its retired blocks), whether the frame's slot already holds exactly that, and the windows a frame that classifies is
+    // cut into - what ft_stats reports whichever way the frame runs.
+    bool keepable = false, reuse = false;
+    ClassifyKey key;
+    int32_t n_planned = 0;
 };
 
 // Pixel list restricted to the tiles.  The reference enumerates pixels y-major, x (Image.fs:104); samples are
@@ -241,7 +258,7 @@ static void plan_chunks(ft_context* c, const RenderRequest& q, bool defer, Frame
     // The windows of a classified frame are cut from its LISTED pixels (the host does not know the active list's length when it queues
     // them), so a sparse frame is one window of work and a row of launches that find theirs empty (~20 us each: k_primary + k_resolve +
     // the counter fill; 3840x2160x64 of the bunny: 16 windows, 14 empty).  Windows widened by the last frame's active count measured no
-    // net gain.
+    // net gain.  A frame that finds its classification in its slot ("classify_reuse", below) does know the length.
     const int64_t chunk_budget = p.classify ? 5 * chunk_samples : ((c->variant & 2) ? chunk_samples : 2 * chunk_samples);
     // An adaptive progressive pass always runs k_classify: on a frame the host does not classify (unbounded items, a focus camera, the
     // option off, an unbounded pattern) only to leave the retired blocks out of the active list.  Its windows stay as wide as unclassified ones.
@@ -291,6 +308,31 @@ static void plan_chunks(ft_context* c, const RenderRequest& q, bool defer, Frame
     // Queued frames of one chunk put k_resolve on its own stream (blocking frames have nothing to hide it in).  A frame cut into many
     // windows (3840x2160x64: 16, most of them empty behind the classification) pays an event pair per window and gains nothing - the windows'
     // small launches already overlap on one stream (measured: 3.46 -> 3.63 ms with it, profiles/r03_z_overlap_by_scene.json)
+    p.n_planned = (int32_t)p.jobs.size();
+    // The slot this frame takes (its previous frame has been retired: render_single) may still hold this very classification.
+    const ft_context::FrameSlot& F = c->slots[c->slot_turn];
+    p.keepable = p.classify && !p.progressive && !p.mask_only;
+    if (p.keepable) {
+        p.key.commit_serial = c->commit_serial; p.key.res_h = q.res_h; p.key.res_v = q.res_v; p.key.list_leaf = p.list_leaf;
+        p.key.jitter_extent = p.jitter_extent; p.key.cam = p.cam; p.key.rects = p.rects;
+        p.reuse = c->opt.classify_reuse && !F.pending && F.kept.valid && F.kept.key == p.key;
+    }
+    // Such a frame knows its active list's length before anything is queued: its windows are cut from that list by the rule above, no
+    // wider than the frame's own (p.cap and the buffers stay what a frame that classifies needs), and those past its end are not launched.
+    // A frame without an active pixel still launches one: its k_resolve writes the finished blocks and hands the counters over.
+    if (p.reuse) {
+        const int64_t n_active = std::max<int64_t>(F.kept.n_active, std::min<int64_t>(64, n_pix_total));
+        int64_t per = p.pix_per_chunk;
+        if (per > 64) {
+            const int64_t n_chunks = (n_active + per - 1) / per;
+            per = std::min(per, ((n_active + n_chunks - 1) / n_chunks + 63) / 64 * 64);
+        }
+        p.jobs.clear();
+        for (int64_t p0 = 0; p0 < n_active; p0 += per) {
+            const uint32_t n = (uint32_t)std::min<int64_t>(per, n_active - p0);
+            p.jobs.push_back(FramePlan::Job{(uint32_t)p0, n, 0, 0, (uint32_t)p0, n});
+        }
+    }
     p.simple = defer && c->opt.resolve_aside && !p.corner && c->opt.timing < 2 && p.jobs.size() == 1;
 }
 
@@ -324,7 +366,8 @@ static int32_t upload_frame_inputs(ft_context* c, const RenderRequest& q, const 
 static int32_t queue_classify(ft_context* c, const RenderRequest& q, const FramePlan& p, ft_context::FrameSlot& F, bool ahead) {
     const ftk::Primary all{p.cam, c->d_pixels.as<uint32_t>(), c->d_jitter.as<double>(), 0u, (uint32_t)p.n_pix_total, p.spp, (uint32_t)q.res_h,
                            (unsigned long long)q.seed, 1.0 / (double)p.n_pix_total, 1.0 / (double)q.res_h, nullptr, nullptr};
-    const ftk::ClassifyOut cls{F.d_block_pos.as<int32_t>(), F.d_pos_block.as<uint32_t>(), c->d_wave_counts.as<uint32_t>()};
+    ftk::PixCount* const kept = &F.d_fc.as<ftk::SlotCounters>()->kept;
+    const ftk::ClassifyOut cls{F.d_block_pos.as<int32_t>(), F.d_pos_block.as<uint32_t>(), c->d_wave_counts.as<uint32_t>(), kept};
     const uint32_t* retired = p.progressive ? c->prog.d_blk[c->prog.cur].as<uint32_t>() : nullptr;   // a progressive pass leaves its retired blocks out
     auto* fc = F.d_fc.as<ftk::FrameCounters>();
     const uint32_t epoch = ++c->classify_epoch;
@@ -339,7 +382,7 @@ static int32_t queue_classify(ft_context* c, const RenderRequest& q, const Frame
     else FT_HIP(c, hipStreamWaitEvent(cs, c->classified, 0));  // one classification at a time, whichever streams they are on
     // the block lists right behind the classification, on its stream and inside its event: they ride beside the predecessors' tracing too
     const ftk::BlockLists lists{F.d_list_heads.as<uint32_t>(), F.d_list_pool.as<uint32_t>(), (uint32_t)(F.d_list_pool.bytes / (ftk::kListEntryWords * 4)), p.list_leaf};
-    auto queue_lists = [&] { if (p.list_leaf >= 0) ftk::launch_block_lists(Lg, c->dev_scene, all, cls.pos_block, lists, p.jitter_extent, fc); };
+    auto queue_lists = [&] { if (p.list_leaf >= 0) ftk::launch_block_lists(Lg, c->dev_scene, all, cls.pos_block, lists, p.jitter_extent, fc, kept); };
     if (ahead) {
         ftk::launch_classify(Lg, c->dev_scene, all, cls, p.jitter_extent, epoch, fc, retired, p.mask_only);
         queue_lists();
@@ -358,6 +401,7 @@ static int32_t queue_chunks(ft_context* c, const RenderRequest& q, const FramePl
     Brackets& E = F.ev;
     const hipStream_t ms = E.ms;
     auto* fc = F.d_fc.as<ftk::FrameCounters>();
+    const ftk::PixCount* const kept = &F.d_fc.as<ftk::SlotCounters>()->kept;   // the active list's length: this frame's k_classify wrote it, or the one this frame reuses
     const size_t lds = lds_bytes_for(c->flat);
     const ftk::Launch Lp{ms, c->n_cu * c->blocks_primary, lds, c->variant_primary};
     const ftk::Launch Lb{ms, c->n_cu * c->blocks_bounce, lds, c->variant};
@@ -379,7 +423,7 @@ static int32_t queue_chunks(ft_context* c, const RenderRequest& q, const FramePl
         if (!first) E.timed(kStageOther, [&] { (void)hipMemsetAsync(&fc->cc, 0, sizeof(ftk::ChunkCounters), ms); });
         ftk::Primary gen{p.cam, c->d_pixels.as<uint32_t>(), c->d_jitter.as<double>(), job.id_base, n_pix, p.spp, stride, (unsigned long long)q.seed,
                          1.0 / (double)n_pix, 1.0 / (double)stride, nullptr, nullptr};
-        if (p.classify) { gen.counts = &fc->counts; gen.block_map = F.d_pos_block.as<uint32_t>(); }   // pix_base = job.id_base: the window's start in the active list
+        if (p.classify) { gen.counts = kept; gen.block_map = F.d_pos_block.as<uint32_t>(); }   // pix_base = job.id_base: the window's start in the active list
         if (p.list_leaf >= 0) { gen.list_heads = F.d_list_heads.as<uint32_t>(); gen.list_pool = F.d_list_pool.as<uint32_t>(); gen.list_leaf = p.list_leaf; }
         gen.group_log2 = (n_pix % 64u == 0u) ? p.group_log2 : 0;
         const int at = c->acc_turn;
@@ -394,7 +438,7 @@ static int32_t queue_chunks(ft_context* c, const RenderRequest& q, const FramePl
             FT_HIP(c, hipStreamWaitEvent(ms, c->acc_free[k], 0)); c->acc_busy[k] = false; E.fresh = false;
         }
         if (p.corner) { E.timed(kStageResolve, [&] { ftk::launch_resolve_corner(Lg, acc, n_samples, job.w, job.h, c->d_out_index.as<uint32_t>() + job.out_base, out_rgb, out_rgba); }); continue; }
-        const ftk::ResolveArgs ra{acc, n_samples, p.classify ? &fc->counts : nullptr, job.id_base, n_pix, p.spp,
+        const ftk::ResolveArgs ra{acc, n_samples, p.classify ? kept : nullptr, job.id_base, n_pix, p.spp,
                                   p.classify ? F.d_pos_block.as<uint32_t>() : nullptr, (p.classify && first && !zeros_in_place) ? F.d_block_pos.as<int32_t>() : nullptr,
                                   (uint32_t)(p.n_pix_total / 64), c->d_pixels.as<uint32_t>(), out_rgb, out_rgba, (uint32_t)gen.group_log2, fc, last ? F.d_report : nullptr};
         if (p.progressive) {
@@ -422,6 +466,7 @@ static int32_t queue_chunks(ft_context* c, const RenderRequest& q, const FramePl
         if (last) F.fc_clean = true;
     }
     if (!F.fc_clean) { ftk::launch_report(Lg, fc, F.d_report); F.fc_clean = true; }   // corner frames end in k_resolve_corner: the hand-over is a launch of its own
+    n_launches += (p.n_planned - (int32_t)p.jobs.size()) * (2 + n_levels);   // ft_stats counts the windows not launched as well
     return FT_OK;
 }
 
@@ -436,10 +481,19 @@ static int32_t queue_frame(ft_context* c, const RenderRequest& q, const FramePla
     // buffers) it is about to reuse.
     if (!defer && (rc = retire_pending(c, nullptr)) != FT_OK) return rc;
     const int turn = c->slot_turn;
-    ft_context::FrameSlot& F = c->slots[turn];
-    if (F.pending && (rc = retire_frame(c, F, nullptr)) != FT_OK) return rc;
+    ft_context::FrameSlot& F = c->slots[turn];                     // (its previous frame was retired before this one was planned)
     if (!defer || !c->accum_open) { for (int k = 0; k < kStages; ++k) { c->k_ms[k] = 0; c->k_launches[k] = 0; } c->accum_open = defer; }   // queued frames sum their kernel times until a wait
-    if (p.classify) {
+    // What the slot keeps of its last classification stays true only through a frame that reads it as it is; a frame that classifies makes it
+    // unknown until it retires, any other frame is not followed (it leaves the buffers alone but last_classified_slot moves on).
+    F.keeps = p.keepable && !p.reuse; F.reuses = p.reuse;
+    if (!p.reuse) F.kept.valid = false;
+    if (F.keeps) F.kept.key = p.key;
+    c->reuse_counts[p.reuse ? 1 : 0] += p.classify ? 1 : 0;
+    c->reuse_counts[2] += (int64_t)p.jobs.size(); c->reuse_counts[3] += p.n_planned - (int64_t)p.jobs.size();
+    if (p.reuse) {                                                 // the buffers are large enough: they hold this frame's classification
+        F.list_leaf = p.list_leaf; F.list_cam = p.cam;
+        c->last_classified_slot = turn;
+    } else if (p.classify) {
         const size_t n_blocks = (size_t)p.n_pix_total / 64, n_waves = (n_blocks + 255) / 256;   // one word per k_classify workgroup
         if ((rc = ensure(c, F.d_block_pos, n_blocks * 4)) != FT_OK) return rc;
         if ((rc = ensure(c, F.d_pos_block, n_blocks * 4)) != FT_OK) return rc;
@@ -475,7 +529,7 @@ static int32_t queue_frame(ft_context* c, const RenderRequest& q, const FramePla
     if (!F.fc_clean) { FT_HIP(c, hipMemsetAsync(F.d_fc.p, 0, sizeof(ftk::FrameCounters), ms)); uploads_queued = true; }
     F.fc_clean = false;                                            // until this frame's own hand-over is queued
     F.ev.begin(ms, (int)c->opt.timing);
-    if (p.classify && (rc = queue_classify(c, q, p, F, defer && c->opt.classify_ahead && !uploads_queued)) != FT_OK) return rc;
+    if (p.classify && !p.reuse && (rc = queue_classify(c, q, p, F, defer && c->opt.classify_ahead && !uploads_queued)) != FT_OK) return rc;
     if (!F.h_report) {
         FT_HIP(c, hipHostMalloc(reinterpret_cast<void**>(&F.h_report), sizeof(ftk::FrameReport), hipHostMallocDefault));
         FT_HIP(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&F.d_report), F.h_report, 0));
@@ -493,8 +547,10 @@ static int32_t queue_frame(ft_context* c, const RenderRequest& q, const FramePla
     FT_HIP(c, hipGetLastError());
     F.signature = p.signature; F.simple = p.simple; F.main_ix = main_ix;
     F.pending = true; F.wall0 = wall0;
-    F.rays_primary = 0; for (auto& j : p.jobs) F.rays_primary += (uint64_t)j.n_ids * (uint64_t)p.spp;
-    F.n_pix_total = p.n_pix_total; F.spp = p.spp; F.n_launches = n_launches; F.n_chunks = (int32_t)p.jobs.size(); F.classify = p.classify; F.format = q.format;
+    F.rays_primary = 0;
+    if (p.corner) for (auto& j : p.jobs) F.rays_primary += (uint64_t)j.n_ids * (uint64_t)p.spp;
+    else F.rays_primary = (uint64_t)p.n_pix_total * (uint64_t)p.spp;   // the windows of a pixel list cover it, launched or not
+    F.n_pix_total = p.n_pix_total; F.spp = p.spp; F.n_launches = n_launches; F.n_chunks = p.n_planned; F.classify = p.classify; F.format = q.format;
     c->slot_turn = (c->slot_turn + 1) % ft_context::kSlots;
     if (defer) return FT_OK;                                       // ft_render_enqueue: the frame is retired by a later call
     if ((rc = retire_frame(c, F, stats)) != FT_OK) return rc;
@@ -513,6 +569,8 @@ int32_t render_single(ft_context* c, const RenderRequest& q, void* out, ft_stats
     if (stats) std::memset(stats, 0, sizeof *stats);
     if (p.n_pix_total == 0) return FT_OK;
     if (q.progressive && p.n_pix_total != c->prog.n_pix) { c->err = "progressive pass: the pixel list differs from the accumulation's"; return FT_ERR_STATE; }
+    // The slot the frame takes is free before it is planned: the plan looks at what the slot's last classification left in it.
+    if (c->slots[c->slot_turn].pending) { const int32_t rc = retire_frame(c, c->slots[c->slot_turn], nullptr); if (rc != FT_OK) return rc; }
     plan_chunks(c, q, defer, p);
     if (p.cap > 0x7FFFFFFFll) { c->err = "chunk too large"; return FT_ERR_INVALID; }
     if (p.classify && p.progressive && p.jobs.size() > 1 && p.pix_per_chunk % 64) { c->err = "progressive pass: too many samples per pass for whole-block windows"; return FT_ERR_UNSUPPORTED; }

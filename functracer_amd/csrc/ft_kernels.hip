@@ -2444,7 +2444,7 @@ __global__ __launch_bounds__(kClassifyBlock) void k_classify(ClassifyArgs) {
     if (valid) out.block_pos[blk] = keep ? (int32_t)pos : (gone ? kBlockRetired : -1);
     if (keep) out.pos_block[pos] = blk;                             // the active list as a block map: pixel ids stay where they are
     if (threadIdx.x == 0 && (ticket + 1u) * kClassifyBlock >= n_blocks && ticket * kClassifyBlock < n_blocks)
-        K->fc->counts.n_pix = 64u * (sh_before + n_keep_wg);        // the last segment publishes the length of the list
+        out.kept->n_pix = 64u * (sh_before + n_keep_wg);            // the last segment publishes the length of the list
     const unsigned long long n_valid = (unsigned long long)__popcll(__ballot(valid));
     wave_add(&K->fc->stats[(ticket * (kClassifyBlock / 64) + wave) % (uint32_t)kStatStripes].pixels_culled, 64ull * (n_valid - (unsigned long long)n_keep));
     FT_STAMP(5);
@@ -2470,6 +2470,7 @@ struct BlockListArgs {
     DevScene S; Primary gen;                                        // gen.pixel_ids: the frame's full pixel list (8x8 tiles)
     const uint32_t* pos_block; BlockLists out; FrameCounters* fc;
     double jitter_extent;
+    const PixCount* counts;                                         // the length of the active list (ClassifyOut::kept)
 };
 constexpr double kProjEps = 1e-12;
 FT_DEV float round_down(double x) { return (float)(x - (2.4e-7 * fabs(x) + 1e-37)); }   // a float's rounding is at most 6e-8 of its magnitude
@@ -2481,7 +2482,7 @@ __global__ __launch_bounds__(kBlock) void k_block_lists(BlockListArgs) {
     const PrimaryArg g = &K->gen;
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / 64u));
     uint32_t* mine = sh_entries[wave];
-    const uint32_t n_active = to_const_as(&K->fc->counts)->n_pix / 64u;
+    const uint32_t n_active = to_const_as(K->counts)->n_pix / 64u;
     const uint32_t leaf = (uint32_t)K->out.leaf;
     const LeafHead Hm = leaf_head(S, leaf);
     cdp Mw = S.leaves + 16ull * leaf;
@@ -2596,7 +2597,8 @@ FT_DEV void write_pixel(double* out_rgb, uint8_t* out_rgba, size_t o, double r, 
 // The end of a frame: the last workgroup to get here copies what the host wants of the counters into the pinned report and clears
 // the counters for the next frame.  Every other workgroup has finished with them (the ticket is taken after a workgroup's last
 // access) and the kernels that wrote them ended before this one began.
-FT_DEV void hand_over_frame(FrameCounters* fc, FrameReport* report, unsigned long long* cells) {   // cells: 8 KB of LDS
+// counts: the length of a classified frame's active list (it lies outside the counters and stays), or null.
+FT_DEV void hand_over_frame(FrameCounters* fc, const PixCount* counts, FrameReport* report, unsigned long long* cells) {   // cells: 8 KB of LDS
     __shared__ uint32_t last;
     const uint32_t t = threadIdx.x;
     __syncthreads();
@@ -2628,7 +2630,7 @@ FT_DEV void hand_over_frame(FrameCounters* fc, FrameReport* report, unsigned lon
     }
     uint32_t word = 0u;
     if (t >= 64 && t < 64 + kMaxBounce + 2) word = fc->cc.n_rays[t - 64];
-    else if (t == 128) word = fc->counts.n_pix;
+    else if (t == 128) word = counts ? counts->n_pix : 0u;
     else if (t == 129) word = fc->classify_error;
     __syncthreads();
     uint32_t* words = reinterpret_cast<uint32_t*>(rep);
@@ -2644,7 +2646,7 @@ FT_DEV void hand_over_frame(FrameCounters* fc, FrameReport* report, unsigned lon
 }
 __global__ __launch_bounds__(kBlock) void k_report(FrameCounters* fc, FrameReport* report) {
     __shared__ unsigned long long cells[kStatStripes * 16];
-    hand_over_frame(fc, report, cells);
+    hand_over_frame(fc, nullptr, report, cells);
 }
 
 // k_resolve under grouped numbering (slot_at): the G samples of a pixel under consecutive offsets lie 64 / G doubles apart in ONE
@@ -2720,7 +2722,7 @@ FT_DEV void resolve_body(const ResolveArgs& a, Start&& start, Emit&& emit, Untra
             untraced(blk * 64u + lane, bp);
         }
     }
-    if (a.report) hand_over_frame(a.fc, a.report, reinterpret_cast<unsigned long long*>(tile));
+    if (a.report) hand_over_frame(a.fc, a.counts, a.report, reinterpret_cast<unsigned long long*>(tile));
 }
 
 // k_resolve: every pixel of the chunk's window of the active list gets the mean of its samples, summed from Zero in sample order and
@@ -2969,8 +2971,8 @@ void launch_classify(const Launch& L, const DevScene& S, const Primary& gen_list
     const uint32_t n_blocks = gen_list.n_pix / 64u;
     hipLaunchKernelGGL(k_classify, dim3((n_blocks + kClassifyBlock - 1u) / kClassifyBlock), dim3(kClassifyBlock), 0, L.stream, a);
 }
-void launch_block_lists(const Launch& L, const DevScene& S, const Primary& gen_list, const uint32_t* pos_block, const BlockLists& out, double jitter_extent, FrameCounters* fc) {
-    const BlockListArgs a{S, gen_list, pos_block, out, fc, jitter_extent};
+void launch_block_lists(const Launch& L, const DevScene& S, const Primary& gen_list, const uint32_t* pos_block, const BlockLists& out, double jitter_extent, FrameCounters* fc, const PixCount* counts) {
+    const BlockListArgs a{S, gen_list, pos_block, out, fc, jitter_extent, counts};
     const uint32_t n_blocks = gen_list.n_pix / 64u, need = (n_blocks + kBlock / 64u - 1u) / (kBlock / 64u);   // a wave per block, grid-strided over the active ones
     hipLaunchKernelGGL(k_block_lists, dim3(need < (uint32_t)L.grid ? (need ? need : 1u) : (uint32_t)L.grid), dim3(kBlock), 0, L.stream, a);
 }

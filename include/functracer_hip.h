@@ -118,8 +118,10 @@ typedef struct ft_stats {
     double   wall_ms;        /* host wall time of the call incl. copies                        */
     double   trace_kernel_ms;/* HIP-event time of the closest-hit + shade/shadow kernels only  */
     uint64_t algorithmic_bytes; /* bytes the pipeline has to move for this frame by construction (roofline) */
-    int32_t  n_launches;     /* kernels launched for the call; k_block_lists, which rides behind k_classify, is not counted */
-    int32_t  n_chunks;
+    int32_t  n_launches;     /* kernels of the call as it is planned from the request: k_classify (one, also when "classify_reuse" finds it done), then per
+                              * window k_primary, the k_bounce levels the level hint asks for and k_resolve - also for windows "classify_reuse" does not launch.
+                              * k_block_lists, which rides behind k_classify, is not counted.  ft_debug_classify_reuse tells what really ran */
+    int32_t  n_chunks;       /* windows of the pixel list the call is cut into, planned the same way (launched or not) */
     uint64_t hits_total;     /* hits shaded over all bounces                                   */
     uint64_t algorithmic_bytes_closest; /* unused since ABI 2 (always 0)                       */
     uint64_t algorithmic_bytes_shade;   /* the k_bounce share (bounces >= 1)                   */
@@ -162,6 +164,11 @@ const char* ft_last_error(const ft_context* ctx);
  * loads, instead of once per lane (scenes with meshes and without textures, rough materials or soft lights: the kernel the headline runs); the shaders leave out what no lane of the wavefront reads (the specular term's three normalisations, the regenerated view ray);
  * and, with "primary_block_lists", a wavefront whose block has an empty candidate list stores Colour.Zero without generating its rays when the mesh is the scene's
  * only item and the camera has no focus.  0: everything per lane, nothing left out.  Same expressions either way: same frames and counters bit for bit),
+ * "classify_reuse" (1 = default: a classified frame whose scene commit, frame size, tiles, camera, jitter extent (not the offsets) and candidate-list leaf equal, field
+ * for field, those of the frame that last classified into the same one of the four frame slots launches neither k_classify nor k_block_lists: it reads that frame's
+ * block maps, lists and active count as they are, and launches only the windows of its pixel list that hold active pixels - a held view, whatever its pattern, seed, samples
+ * or max_depth, from the fifth frame on.  Every commit, a frame of another key, a progressive pass, a corner-sampled or unclassified frame in the slot, an error, and setting
+ * this option, "classify_pixels" or "primary_block_lists" drop what a slot keeps.  0: every frame classifies.  Same frames and ft_stats (times aside) bit for bit),
  * "classify_ahead" / "resolve_aside" / "zero_fill_skip" (1 = default: what a stream of queued frames does that a single frame cannot - the next frame's k_classify on a second
  * stream, k_resolve on a third with the sample colours double-buffered, Colour.Zero not written again into blocks the last frame of the same signature left zero; 0 switches each off; k_resolve goes aside only in frames of one chunk), "mains" (2 = default, 1 .. 3: queued frames of one chunk take turns on that many main streams, so a frame's kernels are dispatched while its predecessor's drain
  * and two frames' reflection levels fill each other's idle stretches), "wave_samples" (0 = default, 16: a bounce-0 wavefront takes up to that many jitter offsets of 64 / that many pixels of an
@@ -668,6 +675,9 @@ int32_t ft_debug_mesh_trees(ft_context* ctx, int64_t sizes[12], void* nodes, uin
  * 0xFFFFFFFF (the block walks the tree) or first entry << 7 | count; pos_block = the block of the frame's pixel list behind each active block;
  * entries = 6 words each: the triangle's record, its list index (tri_orig), and its rectangle x0, x1, y0, y1 in (jx, jy) as floats. */
 int32_t ft_debug_block_lists(ft_context* ctx, int64_t sizes[4], double plane[4], uint32_t* heads, uint32_t* pos_block, uint32_t* entries);
+/* "classify_reuse" at work, for tests: counts since ft_create, summed over the context's devices - classifications launched, classifications reused, windows
+ * launched, windows not launched because the kept active list ends before them.  FT_ERR_NO_DEVICE on a host-only context. */
+int32_t ft_debug_classify_reuse(ft_context* ctx, int64_t out[4]);
 /* HIP-event time per stage over the last ft_render: index 4 primary (bounce 0 fused: generate + closest + shade), 2 the later
  * bounces (one k_bounce per level; one bracket around them all, or with "timing" = 2 one per level), 3 resolve and 0 the rest (the
  * fill, classification) with "timing" = 2; otherwise 0 = everything that is not bracketed and 3 = 0.  Index 1 is unused. */
