@@ -499,6 +499,31 @@ class Context(SceneBuilder):
         self._check(self._lib.ft_temporal_status(self._ctx, out))
         return dict(zip(["calls", "pixels", "with_history", "at_max_history"], list(out)))
 
+    def temporal_set_clamp(self, params=(), off=False, **kw):
+        """ft_temporal_set_clamp: the neighbourhood clamp of the history for every later temporal_accumulate of the open accumulation -
+        the fetched mean is moved into mu +- (gamma * sd + floor) of the current frame's (2 radius + 1)^2 neighbourhood and a pixel it
+        moved keeps at most clamped_history of its length.  Keywords: radius, clamped_history, gamma, floor
+        (_capi.TEMPORAL_CLAMP_DEFAULTS).  temporal_set_clamp(None) or off=True switches it off, as temporal_begin does."""
+        if params is None or off:
+            if kw:
+                raise ValueError("temporal_set_clamp: parameters given together with off")
+            self._check(self._lib.ft_temporal_set_clamp(self._ctx, None))
+            return
+        kw = {**dict(params), **kw}
+        unknown = set(kw) - set(_capi.TEMPORAL_CLAMP_DEFAULTS)
+        if unknown:
+            raise ValueError(f"unknown temporal clamp parameters {sorted(unknown)}")
+        p = _capi.ft_temporal_clamp_params()
+        for k, v in {**_capi.TEMPORAL_CLAMP_DEFAULTS, **kw}.items():
+            setattr(p, k, int(v) if k in ("radius", "clamped_history") else float(v))
+        self._check(self._lib.ft_temporal_set_clamp(self._ctx, C.byref(p)))
+
+    def temporal_clamp_status(self):
+        """ft_temporal_clamp_status: {"radius": the radius in force (0 = off), "clamped": pixels the clamp moved in the last accumulate}."""
+        out = (C.c_int64 * 2)()
+        self._check(self._lib.ft_temporal_clamp_status(self._ctx, out))
+        return dict(zip(["radius", "clamped"], list(out)))
+
     def temporal_end(self):
         self._check(self._lib.ft_temporal_end(self._ctx))
         self._temporal = None

@@ -104,6 +104,21 @@ TEMPORAL_SIGNATURES = [
 ]
 
 
+class ft_temporal_clamp_params(C.Structure):
+    """ft_temporal_set_clamp's parameters (include/functracer_hip.h, clause 3a): the radius of the neighbourhood (1 .. 3), the history
+    length a clamped pixel keeps at most, and the box mu +- (gamma * sd + floor)."""
+    _fields_ = [("radius", C.c_int32), ("clamped_history", C.c_int32), ("gamma", C.c_double), ("floor", C.c_double)]
+
+
+# Context.temporal_set_clamp's defaults
+TEMPORAL_CLAMP_DEFAULTS = dict(radius=1, clamped_history=1, gamma=1.0, floor=1e-4)
+
+TEMPORAL_SIGNATURES += [
+    ("ft_temporal_set_clamp", C.c_int32, [C.c_void_p, C.POINTER(ft_temporal_clamp_params)]),
+    ("ft_temporal_clamp_status", C.c_int32, [C.c_void_p, C.POINTER(C.c_int64)]),
+]
+
+
 # Moving rigid objects under a temporal accumulation (include/functracer_hip.h): not part of the generic builder, which also drives the oracle.
 MOTION_SIGNATURES = [
     ("ft_sg_set_transform", C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(ft_transform), C.c_int32]),

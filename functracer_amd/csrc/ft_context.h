@@ -330,8 +330,15 @@ struct ft_context {
         // the class, the two colour buffers and the two variance planes the iterations alternate between, and the RGBA8 result
         DeviceBuf d_fd, d_fcls, d_fu[2], d_fv[2], d_f8;
         TimedLaunch ftimer;             // around the kernels of a filter call (kernel_ms)
+        // ft_temporal_set_clamp: clamp.radius 0 = off.  d_box: the six lo / hi planes k_temporal_box writes before the
+        // first window of an accumulate; d_mask: a byte per frame pixel, 1 in T, filled once (mask_built); both allocated by the first
+        // accumulate with the clamp on.  clamped: the pixels the clamp moved in the last accumulate.
+        ft_temporal_clamp_params clamp{};
+        int64_t clamped = 0;
+        DeviceBuf d_box, d_mask;
+        bool mask_built = false;
         void release() {
-            for (DeviceBuf* b : {&d_set[0], &d_set[1], &d_rgb, &d_rgba8, &d_ctr, &d_motion, &d_snap, &d_deform, &d_fd, &d_fcls, &d_fu[0], &d_fu[1], &d_fv[0], &d_fv[1], &d_f8}) b->release();
+            for (DeviceBuf* b : {&d_set[0], &d_set[1], &d_rgb, &d_rgba8, &d_ctr, &d_motion, &d_snap, &d_deform, &d_fd, &d_fcls, &d_fu[0], &d_fu[1], &d_fv[0], &d_fv[1], &d_f8, &d_box, &d_mask}) b->release();
             timer.release(); ftimer.release(); *this = Temporal();
         }
     } temporal;

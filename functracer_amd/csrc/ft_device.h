@@ -302,7 +302,8 @@ constexpr double kTemporalMinWeight = 1.0 / 16.0;   // FT_TEMPORAL_MIN_WEIGHT (f
 // at the pixel are blended with what `prev` holds where the pixel's point projects to through the previous call's image plane (o, i,
 // j, k, tlx, tly, pw, ph); the pixel's record goes into `cur`, its mean into out_rgb (frame layout, 3 doubles per pixel) and out8
 // (RGBA8) where those are non-null.  has_prev == 0: the first call after begin.
-// tol_scale = position_tolerance_px * max(pw, ph).  counters[0] += pixels with valid history, counters[1] += pixels at max_history.
+// tol_scale = position_tolerance_px * max(pw, ph).  counters[0] += pixels with valid history, counters[1] += pixels at max_history
+// (three words: [2] is the clamp's, below).
 // motion: null (the scene has the pose the history was written in), or one record of kTemporalMotionDoubles per leaf of the scene
 // (n_leaves of them) that takes a hit pixel's point and normal back to that pose before they are projected and compared:
 //   [0..11] D, rows of the 3x4 map from a current world point of the leaf to where that point was; [12..20] A, rows of the 3x3
@@ -315,6 +316,11 @@ constexpr int kTemporalMotionDoubles = 24;
 // snap[snap_first + triangle] (9 doubles each: v0, e1, e2), then H.  W: the live w2m of the leaf; H, Wh: its m2w and the linear part of
 // its w2m in the pose the history was written in (rows).  Such a pixel does not take the motion record's way: this one ends in that pose.
 struct TemporalDeformLeaf { double W[12], H[12], Wh[9]; uint32_t first_live, snap_first, n, pad; };
+// The colour boxes of the neighbourhood clamp (clause 3a of ft_temporal_accumulate): per channel the planes lo and hi in FRAME layout,
+// written by k_temporal_box from the frame and read by k_temporal by pixel id.  counters[2] += pixels the clamp moved.
+struct TemporalBox { double* lo[3]; double* hi[3]; };
+constexpr size_t kTemporalBoxBytes = 6 * 8;
+constexpr int kTemporalClampMaxRadius = 3;
 struct TemporalArgs {
     GuideWindow win;
     const double* frame;
@@ -326,8 +332,20 @@ struct TemporalArgs {
     unsigned long long* counters;
     const double* motion; uint32_t n_leaves;
     const TemporalDeformLeaf* deform; const double *tris, *snap;
+    // the neighbourhood clamp (ft_temporal_set_clamp), read by k_temporal<.., .., true> alone: box.lo[0] null = off and
+    // k_temporal<.., .., false> runs.  Behind everything else, so the arguments the unclamped kernels read lie where they lay.
+    TemporalBox box; double clamped_history;
 };
 void launch_temporal(hipStream_t stream, const TemporalArgs& a);
+// k_temporal_box: one lane per pixel of the rect (x0, y0, w, h), clipped to the frame; a workgroup stages its 64 x 4 pixels and a halo
+// of `radius` (1 .. 3) of the frame's colours in the LDS and writes box.lo and box.hi of clause 3a.  mask: one byte per frame pixel,
+// non-zero for the pixels in T.
+struct TemporalBoxArgs {
+    const double* frame; const uint8_t* mask; TemporalBox box;
+    int32_t res_h, res_v, x0, y0, w, h, radius;
+    double gamma, floor;
+};
+void launch_temporal_box(hipStream_t stream, const TemporalBoxArgs& a);
 
 // ft_temporal_filter (ft_temporal_filter.hip; the filter is defined in functracer_hip.h and DESIGN.md 13): a variance-guided a-trous
 // filter that reads a history set in place.  Its own planes, in FRAME layout: the demodulation divisor d (one plane per channel; null

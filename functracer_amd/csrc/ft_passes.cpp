@@ -69,8 +69,8 @@ static ftk::GuideWindow guide_window(ft_context* c, int64_t p0, uint32_t n, cons
     return ftk::GuideWindow{static_cast<const int32_t*>(aov_plane(pl, dev, 7)), c->aov.d_pixels.as<uint32_t>(), (uint32_t)p0, n, static_cast<const double*>(aov_plane(pl, dev, 1)),
                             static_cast<const double*>(aov_plane(pl, dev, 2)), static_cast<const double*>(aov_plane(pl, dev, 3)), static_cast<const int32_t*>(aov_plane(pl, dev, 5)), n};
 }
-static int32_t read_counters(ft_context* c, const DeviceBuf& buf, unsigned long long (&ctr)[2]) {   // the two counts a pass's kernels kept in `buf`
-    FT_HIP(c, hipMemcpy(ctr, buf.p, sizeof ctr, hipMemcpyDeviceToHost)); return FT_OK;
+static int32_t read_counters(ft_context* c, const DeviceBuf& buf, unsigned long long* ctr, size_t n = 2) {   // the n counts a pass's kernels kept in `buf`
+    FT_HIP(c, hipMemcpy(ctr, buf.p, n * sizeof *ctr, hipMemcpyDeviceToHost)); return FT_OK;
 }
 
 // The device half of an AOV pass, shared by ft_render_aov and ft_denoise: the pixel list `px` and the pattern go up, and per window of
@@ -403,7 +403,7 @@ int32_t ft_temporal_begin(ft_context* c, int32_t res_h, int32_t res_v, const ft_
             if ((r = ensure(c, b, set_bytes)) != FT_OK) return r;
             FT_HIP(c, hipMemsetAsync(b.p, 0, set_bytes, c->stream));
         }
-        if ((r = ensure(c, T.d_ctr, 2 * sizeof(unsigned long long))) != FT_OK) return r;
+        if ((r = ensure(c, T.d_ctr, 3 * sizeof(unsigned long long))) != FT_OK) return r;
         FT_HIP(c, hipStreamSynchronize(c->stream));
         return FT_OK;
     }();
@@ -428,7 +428,7 @@ static int32_t temporal_single(ft_context* c, const RenderRequest& q, int32_t sa
     const bool want_rgb = P.to_frame || (out && !rgba8), want_rgba8 = out && rgba8;
     if (want_rgb && (rc = ensure(c, T.d_rgb, n_px * 24)) != FT_OK) return rc;
     if (want_rgba8 && (rc = ensure(c, T.d_rgba8, n_px * 4)) != FT_OK) return rc;
-    FT_HIP(c, hipMemsetAsync(T.d_ctr.p, 0, 2 * sizeof(unsigned long long), c->stream));
+    FT_HIP(c, hipMemsetAsync(T.d_ctr.p, 0, 3 * sizeof(unsigned long long), c->stream));
     const ftk::Camera cam = make_camera(*q.cam, T.res_h, T.res_v);
     // The scene was committed in another pose since the history was written (ft_scene_commit_moved, perhaps several times: H is the
     // pose of the last accumulate, so they compose): every leaf's way back to that pose goes up and k_temporal<true> runs.
@@ -445,6 +445,25 @@ static int32_t temporal_single(ft_context* c, const RenderRequest& q, int32_t sa
     }
     double kernel_ms = 0.0;
     int32_t n_launches = 0;
+    // The clamp is on (ft_temporal_set_clamp): the boxes of the frame's neighbourhoods, one k_temporal_box per rect in front of the first
+    // window.  They depend on the frame alone, so a call that runs again for longer hit lists writes the same boxes again.
+    ftk::TemporalBox box{};
+    if (T.clamp.radius > 0 && !px.empty()) {
+        if ((rc = ensure(c, T.d_box, n_px * ftk::kTemporalBoxBytes)) != FT_OK || (rc = ensure(c, T.d_mask, n_px)) != FT_OK) return rc;
+        uint8_t* const mask = T.d_mask.as<uint8_t>();
+        if (!T.mask_built) {                                        // the rects are the begin's: once per accumulation (as ft_temporal_filter fills its class plane)
+            FT_HIP(c, hipMemsetAsync(mask, 0, n_px, c->stream));
+            for (const ft_rect& r : T.rects)
+                FT_HIP(c, hipMemset2DAsync(mask + (size_t)r.y0 * (size_t)T.res_h + (size_t)r.x0, (size_t)T.res_h, 1, (size_t)r.w, (size_t)r.h, c->stream));
+            T.mask_built = true;
+        }
+        for (int k = 0; k < 3; ++k) { box.lo[k] = T.d_box.as<double>() + (size_t)k * n_px; box.hi[k] = T.d_box.as<double>() + (size_t)(3 + k) * n_px; }
+        rc = T.timer.run(c, kernel_ms, [&] { for (const ft_rect& r : T.rects) {
+            ftk::launch_temporal_box(c->stream, ftk::TemporalBoxArgs{c->d_out.as<double>(), mask, box, T.res_h, T.res_v, r.x0, r.y0, r.w, r.h, T.clamp.radius, T.clamp.gamma, T.clamp.floor});
+            ++n_launches;
+        } });
+        if (rc != FT_OK) return rc;
+    }
     AovRun run;
     const bool want[8] = {false, true, true, false, false, true, false, following};   // p, n, leaf; the triangle only in a call that follows
     rc = aov_windows(c, q, sample, want, px, run, [&](int64_t p0, uint32_t n, const AovPlanes& pl, char* dev) -> int32_t {
@@ -461,12 +480,13 @@ static int32_t temporal_single(ft_context* c, const RenderRequest& q, int32_t sa
         a.counters = T.d_ctr.as<unsigned long long>();
         a.motion = moving ? T.d_motion.as<double>() : nullptr; a.n_leaves = (uint32_t)n_leaves;
         if (following) { a.deform = T.d_deform.as<ftk::TemporalDeformLeaf>(); a.tris = c->d_scene[kTris].as<double>(); a.snap = T.d_snap.as<double>(); }
+        a.box = box; a.clamped_history = (double)T.clamp.clamped_history;
         ++n_launches;
         return T.timer.run(c, kernel_ms, [&] { ftk::launch_temporal(c->stream, a); });
     });
     if (rc != FT_OK) return rc;                                     // nothing was flipped: the history is as it was
-    unsigned long long ctr[2] = {0, 0};
-    if (!px.empty() && (rc = read_counters(c, T.d_ctr, ctr)) != FT_OK) return rc;
+    unsigned long long ctr[3] = {0, 0, 0};
+    if (!px.empty() && (rc = read_counters(c, T.d_ctr, ctr, 3)) != FT_OK) return rc;
     if (out && (rc = copy_rects_out(c, out, rgba8 ? T.d_rgba8.p : T.d_rgb.p, rgba8 ? 4 : 24, T.res_h, T.rects, nullptr)) != FT_OK) return rc;
     if (P.to_frame && !px.empty() && (rc = temporal_to_frame(c, T.d_rgb.p)) != FT_OK) return rc;   // the means replace the tile pixels of the frame, once the call can no longer fail
     if (T.calls == 0 || moving) {                                   // the pose the set just written belongs to
@@ -477,7 +497,7 @@ static int32_t temporal_single(ft_context* c, const RenderRequest& q, int32_t sa
     }
     temporal_drop_snapshots(c);                                     // the set just written saw the meshes as they are
     T.prev ^= 1; T.cam = cam; T.calls += 1;
-    T.with_history = (int64_t)ctr[0]; T.at_max = (int64_t)ctr[1];
+    T.with_history = (int64_t)ctr[0]; T.at_max = (int64_t)ctr[1]; T.clamped = (int64_t)ctr[2];
     end_pass(stats, run, kernel_ms, n_launches, wall0);
     if (stats) stats->trace_kernel_ms = run.kernel_ms;
     return FT_OK;
@@ -643,6 +663,33 @@ int32_t ft_temporal_status(ft_context* c, int64_t out[4]) {
     const ft_context::Temporal& T = c->temporal;
     if (!T.open) { c->err = kNoTemporal; return FT_ERR_STATE; }
     out[0] = T.calls; out[1] = T.n_pix; out[2] = T.with_history; out[3] = T.at_max;
+    return FT_OK;
+}
+
+int32_t ft_temporal_set_clamp(ft_context* c, const ft_temporal_clamp_params* params) {
+    if (!c) return FT_ERR_INVALID;
+    if (params) {
+        const ft_temporal_clamp_params& P = *params;
+        if (P.radius < 1 || P.radius > ftk::kTemporalClampMaxRadius) { c->err = "ft_temporal_set_clamp: radius outside 1 .. 3"; return FT_ERR_INVALID; }
+        if (P.clamped_history < 0) { c->err = "ft_temporal_set_clamp: clamped_history below 0"; return FT_ERR_INVALID; }
+        if (!(P.gamma >= 0.0) || !std::isfinite(P.gamma)) { c->err = "ft_temporal_set_clamp: gamma is negative or not finite"; return FT_ERR_INVALID; }
+        if (!(P.floor >= 0.0) || !std::isfinite(P.floor)) { c->err = "ft_temporal_set_clamp: floor is negative or not finite"; return FT_ERR_INVALID; }
+    }
+    if (!need_device(c)) return FT_ERR_NO_DEVICE;
+    int32_t rc;
+    if ((rc = need_one_device(c, "ft_temporal_set_clamp")) != FT_OK) return rc;
+    ft_context::Temporal& T = c->temporal;
+    if (!T.open) { c->err = kNoTemporalEnded; return FT_ERR_STATE; }
+    T.clamp = params ? *params : ft_temporal_clamp_params{};       // (radius 0: off; what is accumulated stays as it is)
+    return FT_OK;
+}
+
+int32_t ft_temporal_clamp_status(ft_context* c, int64_t out[2]) {
+    if (!c || !out) return FT_ERR_INVALID;
+    if (!need_device(c)) return FT_ERR_NO_DEVICE;
+    const ft_context::Temporal& T = c->temporal;
+    if (!T.open) { c->err = kNoTemporal; return FT_ERR_STATE; }
+    out[0] = T.clamp.radius; out[1] = T.clamped;
     return FT_OK;
 }
 

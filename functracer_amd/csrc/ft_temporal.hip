@@ -19,6 +19,12 @@
 // that share the leaf) and two records of 72 bytes; the lanes of an 8x8 block lie on a few neighbouring triangles, so those are a
 // few cache lines per wavefront, read once each: staging them in LDS would add a barrier and save no fetch.  The leaf index and the
 // triangle index come from planes and are range-checked before they address anything.
+//
+// k_temporal<.., .., true> runs while ft_temporal_set_clamp is on: behind the division by W a lane reads the six
+// doubles of its pixel's colour box by pixel id - 8 runs of 64 bytes per plane, as everything else it reads by pixel id - and moves the
+// fetched mean into it.  The boxes come from k_temporal_box, once per call and clipped rect before the first window: 64 x 4 pixels per
+// workgroup, the frame's colours and a halo staged in the LDS (at most 70 x 10 pixels x 25 bytes).  The instantiations without CLAMP
+// are, instruction for instruction, what they were before the clamp existed (the new arguments lie behind the old ones).
 #include <hip/hip_runtime.h>
 
 #include "ft_device.h"
@@ -27,7 +33,16 @@
 namespace ftk {
 namespace {
 
-template <bool MOVING, bool DEFORMING = false> __global__ __launch_bounds__(kBlock) void k_temporal(TemporalArgs a) {
+// Clause 3a's two per-channel steps.  The products are statements of their own, as the definition has them.
+__device__ __forceinline__ double clamp_to(double m, double lo, double hi) { return m < lo ? lo : (m > hi ? hi : m); }
+__device__ __forceinline__ double moved_square(double q, double m, double k) {
+    const double mm = m * m;
+    const double vh = q - mm;
+    const double kk = k * k;
+    return kk + (vh > 0.0 ? vh : 0.0);
+}
+
+template <bool MOVING, bool DEFORMING = false, bool CLAMP = false> __global__ __launch_bounds__(kBlock) void k_temporal(TemporalArgs a) {
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= a.win.n) return;
     const size_t id = a.win.pixel_ids[a.win.first + i];             // y * res_h + x
@@ -142,9 +157,21 @@ template <bool MOVING, bool DEFORMING = false> __global__ __launch_bounds__(kBlo
     const bool finite = finite3(c0, c1, c2);
     const bool history = finite && W >= kTemporalMinWeight;
     double N = finite ? 1.0 : 0.0, M0 = c0, M1 = c1, M2 = c2, Q0 = s0, Q1 = s1, Q2 = s2;
+    bool clamped = false;
     if (history) {
         m0 /= W; m1 /= W; m2 /= W; q0 /= W; q1 /= W; q2 /= W;
-        N = len / W + 1.0;
+        double nh = len / W;
+        if (CLAMP) {                                                // clause 3a: the fetched mean into the box of the frame's neighbourhood
+            const double k0 = clamp_to(m0, a.box.lo[0][id], a.box.hi[0][id]), k1 = clamp_to(m1, a.box.lo[1][id], a.box.hi[1][id]);
+            const double k2 = clamp_to(m2, a.box.lo[2][id], a.box.hi[2][id]);
+            clamped = k0 != m0 || k1 != m1 || k2 != m2;
+            if (clamped) {                                          // the history keeps its variance around the moved mean, and is shortened
+                q0 = moved_square(q0, m0, k0); q1 = moved_square(q1, m1, k1); q2 = moved_square(q2, m2, k2);
+                m0 = k0; m1 = k1; m2 = k2;
+                if (nh > a.clamped_history) nh = a.clamped_history;
+            }
+        }
+        N = nh + 1.0;
         if (N > a.max_history) N = a.max_history;
         M0 = m0 + (c0 - m0) / N; M1 = m1 + (c1 - m1) / N; M2 = m2 + (c2 - m2) / N;
         Q0 = q0 + (s0 - q0) / N; Q1 = q1 + (s1 - q1) / N; Q2 = q2 + (s2 - q2) / N;
@@ -157,11 +184,67 @@ template <bool MOVING, bool DEFORMING = false> __global__ __launch_bounds__(kBlo
     a.cur.leaf[id] = leaf;
     if (a.out_rgb) { a.out_rgb[3 * id] = M0; a.out_rgb[3 * id + 1] = M1; a.out_rgb[3 * id + 2] = M2; }
     if (a.out8) store_rgba8(a.out8, id, M0, M1, M2);
-    // the call's two counts: one atomic per wavefront and count (the lanes past the window's end left above; lane 0 never does alone)
+    // the call's counts: one atomic per wavefront and count (the lanes past the window's end left above; lane 0 never does alone)
     const unsigned long long with_history = __ballot(history), at_max = __ballot(finite && N == a.max_history);
+    const unsigned long long moved = CLAMP ? __ballot(clamped) : 0ull;
     if ((threadIdx.x & 63u) == 0u) {
         if (with_history) atomicAdd(&a.counters[0], (unsigned long long)__popcll(with_history));
         if (at_max) atomicAdd(&a.counters[1], (unsigned long long)__popcll(at_max));
+        if (CLAMP && moved) atomicAdd(&a.counters[2], (unsigned long long)__popcll(moved));
+    }
+}
+
+// The box of a pixel's neighbourhood in the frame (clause 3a).  One lane per pixel of a clipped rect, a workgroup per 64 x 4 pixels of
+// it, as k_tfilter_prepare; the tile and its halo of R pixels are staged in the LDS - the colours interleaved as the frame holds them,
+// and a byte per staged pixel: it takes part iff it lies in the frame, is in T (the mask) and is finite.  A lane then sums its
+// (2R + 1)^2 taps from the LDS in the defined order.  Products are statements of their own: nothing here is fused.
+template <int R> __global__ __launch_bounds__(kBlock) void k_temporal_box(TemporalBoxArgs a) {
+    constexpr int TW = 64 + 2 * R, NT = TW * (4 + 2 * R);
+    __shared__ double Lc[3 * NT];
+    __shared__ uint8_t Lk[NT];
+    const int tx0 = a.x0 + (int)(blockIdx.x * 64u), ty0 = a.y0 + (int)(blockIdx.y * 4u);
+    for (int t = (int)(threadIdx.y * 64u + threadIdx.x); t < NT; t += kBlock) {
+        const int ty = t / TW, tx = t - ty * TW;
+        const int gx = tx0 - R + tx, gy = ty0 - R + ty;
+        uint8_t k = 0;
+        if (gx >= 0 && gx < a.res_h && gy >= 0 && gy < a.res_v) {
+            const size_t q = (size_t)gy * (size_t)a.res_h + (size_t)gx;
+            if (a.mask[q]) {
+                const double c0 = a.frame[3 * q], c1 = a.frame[3 * q + 1], c2 = a.frame[3 * q + 2];
+                if (finite3(c0, c1, c2)) { k = 1; Lc[3 * t] = c0; Lc[3 * t + 1] = c1; Lc[3 * t + 2] = c2; }
+            }
+        }
+        Lk[t] = k;
+    }
+    __syncthreads();
+    const int lx = (int)(blockIdx.x * 64u + threadIdx.x), ly = (int)(blockIdx.y * 4u + threadIdx.y);
+    if (lx >= a.w || ly >= a.h) return;
+    const size_t id = (size_t)(a.y0 + ly) * (size_t)a.res_h + (size_t)(a.x0 + lx);
+    double n = 0.0, s1[3] = {0.0, 0.0, 0.0}, s2[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+    for (int dy = 0; dy <= 2 * R; ++dy) {
+#pragma unroll
+        for (int dx = 0; dx <= 2 * R; ++dx) {
+            const int t = ((int)threadIdx.y + dy) * TW + (int)threadIdx.x + dx;
+            if (!Lk[t]) continue;
+            n += 1.0;
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) {
+                const double c = Lc[3 * t + ch];
+                const double cc = c * c;
+                s1[ch] += c; s2[ch] += cc;
+            }
+        }
+    }
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {                                // (a pixel that is not finite itself may have no tap: NaN, and clause 3a never reads it)
+        const double mu = s1[ch] / n, m2 = s2[ch] / n;
+        const double mm = mu * mu;
+        const double v = m2 - mm;
+        const double sd = sqrt(v > 0.0 ? v : 0.0);
+        const double gs = a.gamma * sd;
+        const double h = gs + a.floor;
+        a.box.lo[ch][id] = mu - h; a.box.hi[ch][id] = mu + h;
     }
 }
 
@@ -170,9 +253,23 @@ template <bool MOVING, bool DEFORMING = false> __global__ __launch_bounds__(kBlo
 void launch_temporal(hipStream_t stream, const TemporalArgs& a) {
     if (a.win.n == 0) return;
     const dim3 grid((a.win.n + kBlock - 1) / kBlock), block(kBlock);
+    if (a.box.lo[0]) {                                              // the clamp is on: the same three, reading the boxes
+        if (a.deform) hipLaunchKernelGGL((k_temporal<true, true, true>), grid, block, 0, stream, a);
+        else if (a.motion) hipLaunchKernelGGL((k_temporal<true, false, true>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((k_temporal<false, false, true>), grid, block, 0, stream, a);
+        return;
+    }
     if (a.deform) hipLaunchKernelGGL((k_temporal<true, true>), grid, block, 0, stream, a);   // (a null motion table: no leaf moved)
     else if (a.motion) hipLaunchKernelGGL(k_temporal<true>, grid, block, 0, stream, a);
     else hipLaunchKernelGGL(k_temporal<false>, grid, block, 0, stream, a);
+}
+
+void launch_temporal_box(hipStream_t stream, const TemporalBoxArgs& a) {
+    if (a.w <= 0 || a.h <= 0) return;
+    const dim3 grid = tile_grid(a.w, a.h), block = tile_block();
+    if (a.radius == 1) hipLaunchKernelGGL(k_temporal_box<1>, grid, block, 0, stream, a);
+    else if (a.radius == 2) hipLaunchKernelGGL(k_temporal_box<2>, grid, block, 0, stream, a);
+    else hipLaunchKernelGGL(k_temporal_box<kTemporalClampMaxRadius>, grid, block, 0, stream, a);
 }
 
 } // namespace ftk

@@ -404,6 +404,18 @@ int32_t ft_denoise(ft_context* ctx, const ft_camera* cam, int32_t res_h, int32_t
  *  3. W = sum of b_q over the valid taps; the history is valid iff W >= FT_TEMPORAL_MIN_WEIGHT (which also makes the result continuous
  *     where fx crosses an integer).  Then M_h = (sum b_q M'(q)) / W, Q_h and N_h likewise; N(x) = min(N_h + 1, max_history);
  *     M(x) = M_h + (c(x) - M_h) / N(x); Q(x) = Q_h + (c(x)^2 - Q_h) / N(x) per channel.
+ *  3a. The neighbourhood clamp, only while ft_temporal_set_clamp (below) has it on, with its radius r, gamma, floor and clamped_history;
+ *     for a pixel whose history is valid by clause 3 (so c(x) is finite).  No product here is fused with a sum.
+ *     Taps q = x + (dx, dy), dy = -r .. r outer, dx = -r .. r inner (the summation order); a tap takes part iff q lies in the frame, q is
+ *     in T (the frame outside the tiles is not this render's) and c(q) is finite in every channel.  k = the number of taps that took
+ *     part; k >= 1, as x itself does.  Per channel: s1 = sum c(q); s2 = sum (c(q) * c(q)); mu = s1 / k; v = s2 / k - mu * mu;
+ *     sd = sqrt(v > 0 ? v : 0); h = gamma * sd + floor; lo = mu - h, hi = mu + h.
+ *     M_c = M_h < lo ? lo : (M_h > hi ? hi : M_h) per channel; clamped(x) = M_c != M_h in any channel.
+ *     Where clamped(x): per channel Vh = Q_h - M_h * M_h and Q_c = M_c * M_c + (Vh > 0 ? Vh : 0) - the history keeps its variance around
+ *     the moved mean - and N_h = min(N_h, clamped_history).  Elsewhere Q_c = Q_h and N_h stays.
+ *     Clause 3 then continues with M_c, Q_c and that N_h: N(x) = min(N_h + 1, max_history), M(x) = M_c + (c(x) - M_c) / N(x), Q likewise;
+ *     clamped_history = 0 therefore restarts a clamped pixel at M = c.  Pixels without valid history take clause 4 or 5 as before; a
+ *     miss pixel has no history, so the clamp never touches it.
  *  4. No history (a miss pixel, the first call after begin, zc <= 0, W below the constant): N(x) = 1, M(x) = c(x) bit for bit,
  *     Q(x) = c(x)^2.
  *  5. Non-finite data never spreads: a pixel whose c(x) has a non-finite channel stores N(x) = 0, M(x) = c(x) (and Q(x) = c(x)^2), so
@@ -440,6 +452,37 @@ int32_t ft_temporal_accumulate(ft_context* ctx, const ft_camera* cam, int32_t sp
 int32_t ft_temporal_fetch(ft_context* ctx, double* mean_rgb, double* stderr_rgb, double* length);
 /* out = calls since begin, tile pixels, pixels with valid history in the last call, pixels whose N is max_history after it. */
 int32_t ft_temporal_status(ft_context* ctx, int64_t out[4]);
+/* The neighbourhood clamp of the history (clause 3a above; variance clipping, Salvi 2016): the fetched history mean is moved into the
+ * box mu +- (gamma * sd + floor) of the CURRENT frame's (2r+1)^2 neighbourhood before it is blended, and the history is shortened to
+ * clamped_history where that moved it.  Without it the history follows surfaces but not their shading: a shadow or a reflection that
+ * left a surface whose history is valid lingers for up to max_history calls.  Off after ft_temporal_begin: every kernel launched and
+ * every bit produced is then what it is without these functions.
+ * ft_temporal_set_clamp may be called any time between ft_temporal_begin and the end of the accumulation; every later
+ * ft_temporal_accumulate reads it, nothing already accumulated changes.  params == NULL switches it off.  A second begin replaces the
+ * first, clamp included; whatever ends the accumulation drops it.
+ *  - floor absorbs rounding where the neighbourhood is flat: there sd = 0, and a history that differs from mu in the last bit would
+ *    otherwise count as clamped (and lose its length).
+ *  - gamma >= sqrt((2r+1)^2 - 1) can never clamp a history that equals the current frame: no sample of k values lies further than
+ *    sqrt(k - 1) standard deviations from their mean (Samuelson's inequality), and the bound is met by one bright tap among equal ones.
+ *    That is 2.83 for r = 1, 4.90 for r = 2, 6.93 for r = 3.  gamma near 1 is the aggressive setting for noise-free frames; noisy
+ *    1-spp frames want a larger radius and a larger gamma, or the clamp takes the noise of the neighbourhood for a change of light.
+ *  - It composes with ft_scene_commit_moved, ft_scene_commit_deformed and "temporal_follow_deformed": those only change which history
+ *    is fetched.  ft_temporal_filter is unaffected.  With to_frame the frame is overwritten after the boxes were taken: they see the
+ *    rendered colours.
+ * Errors, in this order: a null context FT_ERR_INVALID; with non-null params FT_ERR_INVALID for radius outside 1 .. 3,
+ * clamped_history < 0, gamma NaN, infinite or negative, floor NaN, infinite or negative; a host-only context FT_ERR_NO_DEVICE; a
+ * context over several devices FT_ERR_UNSUPPORTED; no open accumulation FT_ERR_STATE.
+ * ft_temporal_clamp_status: out = the radius in force (0 = off), the pixels with clamped(x) in the last accumulate (0 after a call
+ * that ran with the clamp off; a failed accumulate leaves the previous value, as it leaves the other counts).  The with_history and
+ * at_max counts of ft_temporal_status keep their meaning.  FT_ERR_INVALID for a null context or out, then FT_ERR_NO_DEVICE, then
+ * FT_ERR_STATE without an accumulation.
+ * stats of an accumulate with the clamp on: the box pass (one kernel per clipped rect, before the first window) counts towards
+ * kernel_ms and n_launches, not towards trace_kernel_ms.
+ * Device memory, allocated by the first accumulate with the clamp on and freed with the accumulation: 48 bytes per frame pixel for the
+ * boxes (lo and hi, three channels) and 1 for the in-T mask.  The accumulation's counters are three words. */
+typedef struct ft_temporal_clamp_params { int32_t radius, clamped_history; double gamma, floor; } ft_temporal_clamp_params;  /* 24 bytes */
+int32_t ft_temporal_set_clamp(ft_context* ctx, const ft_temporal_clamp_params* params);   /* params == NULL: off */
+int32_t ft_temporal_clamp_status(ft_context* ctx, int64_t out[2]);   /* radius in force (0 = off), pixels clamped in the last accumulate */
 /* End the accumulation and free its buffers (FT_OK when there is none). */
 int32_t ft_temporal_end(ft_context* ctx);
 
@@ -525,7 +568,9 @@ int32_t ft_temporal_filter(ft_context* ctx, const ft_camera* cam, int32_t spp, c
  * without it.  Several ft_scene_commit_moved calls between two accumulates compose by construction: H is the pose at the last
  * accumulate, not at the last commit.
  * What follows a leaf is its history, not its shading: light that changes on a moving surface (it turns towards a light, a shadow
- * sweeps over it) is averaged as noise is, max_history bounding how long it lingers.  Lights do not move; meshes deform through
+ * sweeps over it) is averaged as noise is, max_history bounding how long it lingers - unless the neighbourhood clamp is on
+ * (ft_temporal_set_clamp, clause 3a of ft_temporal_accumulate), which pulls such history to the colours the current frame shows
+ * around the pixel and shortens it.  Lights do not move; meshes deform through
  * ft_scene_commit_deformed (below), whose history follows the triangles with "temporal_follow_deformed" ("history on deforming meshes").
  * ft_temporal_filter with `demodulate` returns FT_ERR_STATE between an ft_scene_commit_moved and the next ft_temporal_accumulate (its
  * guide pass would show another pose than the set); without `demodulate` it runs as before.
@@ -623,7 +668,7 @@ int32_t ft_scene_tree_quality(ft_context* ctx, ft_node mesh_node, double out[4])
  * history's pose - so a mesh that is both moved and deformed between two accumulates is followed through both.  A triangle that did not
  * change, a pixel on another leaf and a miss pixel get the bits they get without the option.
  * As for moving objects, what follows a triangle is its history, not its shading: light that changes on a bending surface is averaged as
- * noise is.  ft_temporal_filter with `demodulate` between a deform and the next accumulate behaves as it does without the option.
+ * noise is (ft_temporal_set_clamp is the remedy here too).  ft_temporal_filter with `demodulate` between a deform and the next accumulate behaves as it does without the option.
  * Device memory: 72 bytes per triangle of each snapshotted mesh until the next accumulate, 280 bytes per leaf and 4 more bytes per pixel
  * of ft_render_aov's window (the triangle plane) in a call that follows. */
 
