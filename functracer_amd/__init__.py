@@ -66,7 +66,7 @@ def hip_lib():
         lib.ft_denoise.argtypes = _capi.DENOISE_SIGNATURE
         lib.ft_temporal_filter.restype, lib.ft_temporal_filter.argtypes = C.c_int32, _capi.TEMPORAL_FILTER_SIGNATURE
         lib.ft_quantise_rgba8.argtypes = [_capi.c_double_p, C.c_int64, C.POINTER(C.c_uint8)]
-        for name, res, args in _capi.PROGRESSIVE_SIGNATURES + _capi.TEMPORAL_SIGNATURES + _capi.MOTION_SIGNATURES + _capi.DEFORM_SIGNATURES:
+        for name, res, args in _capi.PROGRESSIVE_SIGNATURES + _capi.TEMPORAL_SIGNATURES + _capi.TEMPORAL_QUEUE_SIGNATURES + _capi.MOTION_SIGNATURES + _capi.DEFORM_SIGNATURES:
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _hip = lib
@@ -486,6 +486,42 @@ class Context(SceneBuilder):
                                                  _capi.dptr(jitter) if jitter is not None else None, int(sample), int(seed), C.byref(p), 1 if rgba8 else 0,
                                                  out.ctypes.data_as(C.c_void_p) if out is not None else None, _capi.dptr(var) if var is not None else None, C.byref(st)))
         return out, var, st.as_dict()
+
+    def temporal_enqueue(self, camera, spp, jitter, sample=0, seed=DEFAULT_SEED, rgba8=False, out=None, filter=None, **params):
+        """ft_temporal_enqueue: temporal_accumulate and, with `filter` (a dict of temporal_filter's parameters; {} for the defaults), the
+        temporal_filter of its result, queued behind the last frame queued or rendered; returns at once.  out: a C-contiguous array of
+        the result's shape (rgb[res_v, res_h, 3] float64 or rgba[res_v, res_h, 4] uint8) that outlives the call, best a PinnedArray's,
+        one per call in flight; it is the host's again after temporal_wait(), or once _capi.TEMPORAL_QUEUE_DEPTH more calls were queued.
+        None (without a filter only): nothing leaves the device.  params: temporal_accumulate's; to_frame is refused, here and in `filter`."""
+        unknown = set(params) - set(_capi.TEMPORAL_DEFAULTS)
+        if unknown:
+            raise ValueError(f"unknown temporal parameters {sorted(unknown)}")
+        res_h, res_v = self._temporal_shape()
+        p = _capi.ft_temporal_params()
+        for k, v in {**_capi.TEMPORAL_DEFAULTS, **params}.items():
+            setattr(p, k, int(v) if k in ("max_history", "to_frame") else float(v))
+        fp = None
+        if filter is not None:
+            unknown = set(filter) - set(_capi.TEMPORAL_FILTER_DEFAULTS)
+            if unknown:
+                raise ValueError(f"unknown temporal filter parameters {sorted(unknown)}")
+            fp = _capi.ft_temporal_filter_params()
+            for k, v in {**_capi.TEMPORAL_FILTER_DEFAULTS, **filter}.items():
+                setattr(fp, k, int(v) if k in ("iterations", "demodulate", "min_history", "to_frame") else float(v))
+        jitter = np.zeros((1, 2)) if spp <= 0 else _capi.as_f64(jitter, (spp, 2))
+        shape, dtype = ((res_v, res_h, 4), np.uint8) if rgba8 else ((res_v, res_h, 3), np.float64)
+        if out is not None and (out.shape != shape or out.dtype != dtype or not out.flags.c_contiguous):
+            raise ValueError(f"temporal_enqueue: need a C-contiguous {np.dtype(dtype).name} array of shape {shape}")
+        self._check(self._lib.ft_temporal_enqueue(self._ctx, C.byref(camera), int(spp), _capi.dptr(jitter), int(sample), int(seed), C.byref(p),
+                                                  C.byref(fp) if fp is not None else None, 1 if rgba8 else 0,
+                                                  out.ctypes.data_as(C.c_void_p) if out is not None else None))
+
+    def temporal_wait(self):
+        """ft_temporal_wait: blocks until every queued temporal call has finished, raises the first error among them and returns the
+        stats dict of the last one (all zero with nothing queued)."""
+        st = _capi.ft_stats()
+        self._check(self._lib.ft_temporal_wait(self._ctx, C.byref(st)))
+        return st.as_dict()
 
     def temporal_fetch(self):
         """(mean[res_v, res_h, 3], stderr[res_v, res_h, 3], history length[res_v, res_h] float64) of the tile pixels; other pixels stay 0."""

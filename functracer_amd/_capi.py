@@ -157,6 +157,14 @@ TEMPORAL_FILTER_DEFAULTS = dict(iterations=4, demodulate=1, min_history=4, to_fr
 TEMPORAL_FILTER_SIGNATURE = [C.c_void_p, C.POINTER(ft_camera), C.c_int32, c_double_p, C.c_int32, C.c_uint64, C.POINTER(ft_temporal_filter_params),
                              C.c_int32, C.c_void_p, c_double_p, C.POINTER(ft_stats)]
 
+# ft_temporal_enqueue / ft_temporal_wait (include/functracer_hip.h): the accumulate and its filter as one queued call.
+TEMPORAL_QUEUE_DEPTH = 4
+TEMPORAL_QUEUE_SIGNATURES = [
+    ("ft_temporal_enqueue", C.c_int32, [C.c_void_p, C.POINTER(ft_camera), C.c_int32, c_double_p, C.c_int32, C.c_uint64, C.POINTER(ft_temporal_params),
+                                        C.POINTER(ft_temporal_filter_params), C.c_int32, C.c_void_p]),
+    ("ft_temporal_wait", C.c_int32, [C.c_void_p, C.POINTER(ft_stats)]),
+]
+
 
 # ft_render_aov channels: (name, dtype, components per pixel, value of a pixel whose ray misses everything)
 AOV_CHANNELS = [("t", np.float64, 1, np.inf), ("p", np.float64, 3, 0.0), ("n", np.float64, 3, 0.0), ("colour", np.float64, 3, 0.0),

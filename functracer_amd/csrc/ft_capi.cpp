@@ -413,8 +413,9 @@ static void derive_launch_shape(ft_context* c) {
 static int32_t upload_scene(ft_context* c) {
     int32_t rc;
     FT_HIP(c, hipSetDevice(c->device));
-    // frames still queued trace the scene these uploads replace, and not all of them on the stream the uploads travel on (FrameSlot::main_ix)
-    if (any_pending(c)) { if ((rc = retire_pending(c, nullptr)) != FT_OK) return rc; c->accum_open = false; }
+    // frames still queued trace the scene these uploads replace, and not all of them on the stream the uploads travel on (FrameSlot::main_ix);
+    // queued temporal calls read the frames, and their guide passes the scene
+    if (any_queued(c)) { if ((rc = retire_queued(c)) != FT_OK) return rc; c->accum_open = false; }
     const fth::FlatScene& f = c->flat;
     if ((rc = lds_fits(c)) != FT_OK) return rc;
     c->refit.ready = false;                                         // the trees these uploads bring are not the ones its tables describe
@@ -624,7 +625,7 @@ static int32_t refit_device(ft_context* c, const fth::FlatScene& f, const fth::S
     FT_HIP(c, hipSetDevice(c->device));
     const auto t0 = clock::now();
     // frames still queued trace the scene this refit rewrites (as upload_scene)
-    if (any_pending(c)) { if ((rc = retire_pending(c, nullptr)) != FT_OK) return rc; c->accum_open = false; }
+    if (any_queued(c)) { if ((rc = retire_queued(c)) != FT_OK) return rc; c->accum_open = false; }
     if ((rc = drain_frame_streams(c)) != FT_OK) return rc;
     if (c->side) FT_HIP(c, hipStreamSynchronize(c->side));
     ft_context::Refit& R = c->refit;
@@ -803,7 +804,7 @@ int32_t ft_scene_tree_quality(ft_context* c, ft_node mesh_node, double out[4]) {
     if (!need_device(c)) return FT_ERR_NO_DEVICE;
     int32_t rc;
     FT_HIP(c, hipSetDevice(c->device));
-    if (any_pending(c)) { if ((rc = retire_pending(c, nullptr)) != FT_OK) return rc; c->accum_open = false; }
+    if (any_queued(c)) { if ((rc = retire_queued(c)) != FT_OK) return rc; c->accum_open = false; }
     if ((rc = drain_frame_streams(c)) != FT_OK) return rc;
     if (c->side) FT_HIP(c, hipStreamSynchronize(c->side));
     c->tree_quality.resize(f.meshes.size());

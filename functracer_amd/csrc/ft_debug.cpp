@@ -217,7 +217,7 @@ int32_t ft_debug_block_lists(ft_context* c, int64_t sizes[4], double plane[4], u
     sizes[0] = sizes[1] = sizes[3] = 0; sizes[2] = -1;
     if (c->last_classified_slot < 0) return FT_OK;
     FT_HIP(c, hipSetDevice(c->device));
-    int32_t rc = retire_pending(c, nullptr);
+    int32_t rc = retire_queued(c);
     if (rc != FT_OK) return rc;
     if ((rc = drain_frame_streams(c)) != FT_OK) return rc;
     const ft_context::FrameSlot& F = c->slots[c->last_classified_slot];

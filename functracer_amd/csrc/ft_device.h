@@ -346,6 +346,13 @@ struct TemporalBoxArgs {
     double gamma, floor;
 };
 void launch_temporal_box(hipStream_t stream, const TemporalBoxArgs& a);
+// k_temporal_report: the hand-over at the end of a queued temporal call (ft_temporal_enqueue), the frame driver's launch_report for the
+// temporal counts.  One wavefront, the call's last kernel on its stream: it copies k_temporal's three counts and the guide pass's two
+// (hits, rays whose hit list overflowed) into `report` - the device-side address of a pinned record the host reads once the call's last
+// event has passed - and clears both sets of counters for the next call.
+struct TemporalReport { unsigned long long with_history, at_max, clamped, hits, overflow, pad[3]; };   // 64 bytes
+static_assert(sizeof(TemporalReport) == 64, "k_temporal_report writes the record as eight 8-byte cells");
+void launch_temporal_report(hipStream_t stream, unsigned long long* temporal_counters, unsigned long long* guide_counters, TemporalReport* report);
 
 // ft_temporal_filter (ft_temporal_filter.hip; the filter is defined in functracer_hip.h and DESIGN.md 13): a variance-guided a-trous
 // filter that reads a history set in place.  Its own planes, in FRAME layout: the demodulation divisor d (one plane per channel; null

@@ -525,6 +525,13 @@ static int32_t queue_frame(ft_context* c, const RenderRequest& q, const FramePla
     if (!p.simple && any_pending(c, true) && (rc = retire_pending(c, nullptr)) != FT_OK) return rc;   // anything else keeps the one-stream order
     const int main_ix = (p.simple && c->opt.mains > 1 && !uploads_queued && prev.pending && prev.simple) ? (prev.main_ix + 1) % (int)c->opt.mains : 0;   // the next stream after its predecessor's
     const hipStream_t ms = main_ix ? c->more_mains[main_ix - 1] : c->stream;
+    // A queued temporal call (ft_temporal_enqueue) may still be reading the FP64 frame this one overwrites: the stream this frame's
+    // k_resolve / k_resolve_corner (and, inside k_resolve, the fill of the finished blocks) runs on waits for the event behind that
+    // call's last reader.  The tracing kernels do not wait.  Taken only by the first FP64 frame queued after such a call.
+    if (c->temporal.fork_owed && q.format == 0) {
+        FT_HIP(c, hipStreamWaitEvent(p.simple ? c->tail : ms, c->temporal.fork, 0));
+        c->temporal.fork_owed = false;
+    }
     // chunk counters, statistic stripes, list length, tickets: cleared by the slot's previous frame's last kernel, or by a fill when there was none
     if (!F.fc_clean) { FT_HIP(c, hipMemsetAsync(F.d_fc.p, 0, sizeof(ftk::FrameCounters), ms)); uploads_queued = true; }
     F.fc_clean = false;                                            // until this frame's own hand-over is queued
@@ -624,13 +631,13 @@ static int32_t render_frame(ft_context* c, const RenderRequest& q, void* out, ft
 }
 
 int32_t with_growing_hit_lists(ft_context* c, const std::function<int32_t()>& run) {
-    // Frames still queued by ft_render_enqueue are retired first, so that an overflow of one of THEM is reported as what it is
-    // (queued frames are not rendered again) instead of being taken for this call's.
+    // Frames still queued by ft_render_enqueue, and the temporal calls queued behind them (ft_temporal_enqueue), are retired first, so that
+    // an overflow of one of THEM is reported as what it is (neither is run again) instead of being taken for this call's.
     if (!c->host_only) {
         for (ft_context* d : devices(c)) {
-            if (!any_pending(d)) continue;
+            if (!any_queued(d)) continue;
             if (hipSetDevice(d->device) != hipSuccess) { c->err = "hipSetDevice failed"; return FT_ERR_NO_DEVICE; }
-            const int32_t prc = retire_pending(d, nullptr);
+            const int32_t prc = retire_queued(d);
             d->accum_open = false;
             if (prc != FT_OK) { if (d != c) c->err = d->err; return prc; }
         }

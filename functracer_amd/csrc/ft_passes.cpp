@@ -9,7 +9,8 @@ namespace ftc {
 void temporal_close(ft_context* c) {
     if (!c->temporal.open) return;
     (void)hipSetDevice(c->device);
-    c->temporal.release();
+    (void)retire_temporal(c, nullptr);                              // queued calls still use the buffers (an overflow among them has closed it already)
+    if (c->temporal.open) c->temporal.release();
 }
 
 // The snapshots of "temporal_follow_deformed" and their device memory let go: the history has caught up with the meshes (a successful
@@ -65,8 +66,8 @@ static int32_t check_albedo_floor(ft_context* c, const std::string& api, int32_t
 }
 static double inv_sq(double sigma) { return sigma > 0.0 ? 1.0 / (sigma * sigma) : 0.0; }   // 1 / sigma^2 as the kernels take it; 0 switches the term off
 // The window [p0, p0 + n) of aov_windows as a kernel reads it: the planes the pass asked k_aov for, the others null.
-static ftk::GuideWindow guide_window(ft_context* c, int64_t p0, uint32_t n, const AovPlanes& pl, char* dev) {
-    return ftk::GuideWindow{static_cast<const int32_t*>(aov_plane(pl, dev, 7)), c->aov.d_pixels.as<uint32_t>(), (uint32_t)p0, n, static_cast<const double*>(aov_plane(pl, dev, 1)),
+static ftk::GuideWindow guide_window(const uint32_t* pixel_ids, int64_t p0, uint32_t n, const AovPlanes& pl, char* dev) {
+    return ftk::GuideWindow{static_cast<const int32_t*>(aov_plane(pl, dev, 7)), pixel_ids, (uint32_t)p0, n, static_cast<const double*>(aov_plane(pl, dev, 1)),
                             static_cast<const double*>(aov_plane(pl, dev, 2)), static_cast<const double*>(aov_plane(pl, dev, 3)), static_cast<const int32_t*>(aov_plane(pl, dev, 5)), n};
 }
 static int32_t read_counters(ft_context* c, const DeviceBuf& buf, unsigned long long* ctr, size_t n = 2) {   // the n counts a pass's kernels kept in `buf`
@@ -77,6 +78,23 @@ static int32_t read_counters(ft_context* c, const DeviceBuf& buf, unsigned long 
 // "chunk_samples" entries one k_aov writes the wanted planes into d_aov_out by position in the window.  consume(p0, n, planes, dev) then
 // sees the window [p0, p0 + n) with its planes still in HBM, behind the kernel on the context's stream - it copies them out, or queues a
 // kernel that reads them.  The stream is drained after every window (the next one overwrites the planes' buffer and the event pair).
+// The windows of a guide pass over n_pix list entries: `per` entries each, whole 8x8 blocks.
+static int64_t guide_window_size(const ft_context* c, int64_t n_pix) {
+    int64_t per = std::max<int64_t>(1, std::min<int64_t>(n_pix, c->opt.chunk_samples));
+    if (per > 64) per -= per % 64;
+    return per;
+}
+// One k_aov over the window [p0, p0 + n) of the list `pixels` (on the device, as `jitter`), its planes into `dev` by position in the window.
+static void launch_guide_window(ft_context* c, const RenderRequest& q, int32_t sample, const ftk::Camera& cam, const uint32_t* pixels, const double* jitter,
+                                int64_t p0, uint32_t n, const AovPlanes& pl, char* dev) {
+    const ftk::Launch L{c->stream, c->n_cu * c->blocks_aov, lds_bytes_for(c->flat), c->variant};
+    const ftk::AovSource src{c->d_scene[kTriSrc].as<uint32_t>(), c->d_scene[kRunNodes].as<int32_t>()};
+    ftk::Primary gen{cam, pixels, jitter, (uint32_t)p0, n, q.spp, (uint32_t)q.res_h, (unsigned long long)q.seed, 1.0 / (double)n, 1.0 / (double)q.res_h, nullptr, nullptr};
+    gen.group_log2 = 0;
+    const ftk::AovOut out{static_cast<double*>(aov_plane(pl, dev, 0)), static_cast<double*>(aov_plane(pl, dev, 1)), static_cast<double*>(aov_plane(pl, dev, 2)), static_cast<double*>(aov_plane(pl, dev, 3)),
+                          static_cast<double*>(aov_plane(pl, dev, 4)), static_cast<int32_t*>(aov_plane(pl, dev, 5)), static_cast<int32_t*>(aov_plane(pl, dev, 6)), static_cast<int32_t*>(aov_plane(pl, dev, 7)), n};
+    ftk::launch_aov(L, c->dev_scene, gen, (uint32_t)sample, src, out, c->aov.d_ctr.as<unsigned long long>());
+}
 static int32_t aov_windows(ft_context* c, const RenderRequest& q, int32_t sample, const bool (&want)[8], const std::vector<uint32_t>& px, AovRun& run,
                            const std::function<int32_t(int64_t, uint32_t, const AovPlanes&, char*)>& consume) {
     int32_t rc;
@@ -84,27 +102,19 @@ static int32_t aov_windows(ft_context* c, const RenderRequest& q, int32_t sample
     run = AovRun{};
     run.n_pix = n_pix;
     if (n_pix == 0) return FT_OK;
-    int64_t per = std::max<int64_t>(1, std::min<int64_t>(n_pix, c->opt.chunk_samples));
-    if (per > 64) per -= per % 64;                                  // windows of whole 8x8 blocks
+    const int64_t per = guide_window_size(c, n_pix);
     const AovPlanes pl = aov_planes(want, per);
     if ((rc = upload(c, c->aov.d_pixels, px)) != FT_OK) return rc;
     if ((rc = upload(c, c->aov.d_jitter, std::vector<double>(q.jitter_xy, q.jitter_xy + 2 * (size_t)q.spp))) != FT_OK) return rc;
     if ((rc = ensure(c, c->aov.d_out, (size_t)per * pl.bytes_per_entry)) != FT_OK) return rc;
     if ((rc = ensure(c, c->aov.d_ctr, 2 * sizeof(unsigned long long))) != FT_OK) return rc;
     FT_HIP(c, hipMemsetAsync(c->aov.d_ctr.p, 0, 2 * sizeof(unsigned long long), c->stream));
+    c->aov.ctr_clean = false;
     const ftk::Camera cam = make_camera(*q.cam, q.res_h, q.res_v);
-    const size_t lds = lds_bytes_for(c->flat);
-    const ftk::Launch L{c->stream, c->n_cu * c->blocks_aov, lds, c->variant};
-    const ftk::AovSource src{c->d_scene[kTriSrc].as<uint32_t>(), c->d_scene[kRunNodes].as<int32_t>()};
     char* const dev = c->aov.d_out.as<char>();
     for (int64_t p0 = 0; p0 < n_pix; p0 += per) {
         const uint32_t n = (uint32_t)std::min<int64_t>(per, n_pix - p0);
-        ftk::Primary gen{cam, c->aov.d_pixels.as<uint32_t>(), c->aov.d_jitter.as<double>(), (uint32_t)p0, n, q.spp, (uint32_t)q.res_h, (unsigned long long)q.seed,
-                         1.0 / (double)n, 1.0 / (double)q.res_h, nullptr, nullptr};
-        gen.group_log2 = 0;
-        const ftk::AovOut out{static_cast<double*>(aov_plane(pl, dev, 0)), static_cast<double*>(aov_plane(pl, dev, 1)), static_cast<double*>(aov_plane(pl, dev, 2)), static_cast<double*>(aov_plane(pl, dev, 3)),
-                              static_cast<double*>(aov_plane(pl, dev, 4)), static_cast<int32_t*>(aov_plane(pl, dev, 5)), static_cast<int32_t*>(aov_plane(pl, dev, 6)), static_cast<int32_t*>(aov_plane(pl, dev, 7)), n};
-        rc = c->aov.timer.run(c, run.kernel_ms, [&] { ftk::launch_aov(L, c->dev_scene, gen, (uint32_t)sample, src, out, c->aov.d_ctr.as<unsigned long long>()); },
+        rc = c->aov.timer.run(c, run.kernel_ms, [&] { launch_guide_window(c, q, sample, cam, c->aov.d_pixels.as<uint32_t>(), c->aov.d_jitter.as<double>(), p0, n, pl, dev); },
                               [&] { ++run.n_launches; return consume(p0, n, pl, dev); });
         if (rc != FT_OK) return rc;
     }
@@ -115,11 +125,11 @@ static int32_t aov_windows(ft_context* c, const RenderRequest& q, int32_t sample
     return FT_OK;
 }
 
-// This device is about to run a guide pass: the frames still queued on it are retired first, and the caller's stats start from zero.
+// This device is about to run a guide pass: the frames and temporal calls still queued on it are retired first, and the caller's stats start from zero.
 static int32_t begin_pass(ft_context* c, ft_stats* stats) {
     FT_HIP(c, hipSetDevice(c->device));
     int32_t rc;
-    if (any_pending(c) && (rc = retire_pending(c, nullptr)) != FT_OK) return rc;
+    if (any_queued(c) && (rc = retire_queued(c)) != FT_OK) return rc;
     if (stats) std::memset(stats, 0, sizeof *stats);
     return FT_OK;
 }
@@ -264,7 +274,7 @@ static int32_t denoise_single(ft_context* c, const RenderRequest& q, int32_t sam
         const bool want[8] = {false, true, true, true, false, true, false, false};   // p, n, colour, leaf
         rc = aov_windows(c, q, sample, want, px, run, [&](int64_t p0, uint32_t n, const AovPlanes& pl, char* dev) -> int32_t {
             ftk::DenoiseScatterArgs a{};
-            a.win = guide_window(c, p0, n, pl, dev);
+            a.win = guide_window(c->aov.d_pixels.as<uint32_t>(), p0, n, pl, dev);
             a.frame = frame; a.u0 = c->denoise.d_u[0].as<double>(); a.g = g;
             a.demodulate = P.demodulate ? 1 : 0; a.albedo_floor = P.albedo_floor;
             if (P.use_variance) {
@@ -393,6 +403,7 @@ int32_t ft_temporal_begin(ft_context* c, int32_t res_h, int32_t res_v, const ft_
     if (!need_device(c)) return FT_ERR_NO_DEVICE;
     int32_t rc;
     if ((rc = need_one_device(c, "ft_temporal_begin")) != FT_OK) return rc;
+    if ((rc = retire_temporal(c, nullptr)) != FT_OK) return rc;     // an error among the queued calls of the accumulation this one replaces
     temporal_close(c);                                              // a second begin replaces the first
     ft_context::Temporal& T = c->temporal;
     rc = [&]() -> int32_t {
@@ -414,6 +425,70 @@ int32_t ft_temporal_begin(ft_context* c, int32_t res_h, int32_t res_v, const ft_
     return FT_OK;
 }
 
+// The steps ft_temporal_accumulate and ft_temporal_enqueue share; what differs between them is what stands between the launches.
+// The clamp's planes: allocated by the first call with the clamp on, the mask filled once per accumulation (the rects are the begin's,
+// as ft_temporal_filter fills its class plane); `box` then points into them.
+static int32_t temporal_box_planes(ft_context* c, ftk::TemporalBox& box) {
+    ft_context::Temporal& T = c->temporal;
+    const size_t n_px = (size_t)T.res_h * (size_t)T.res_v;
+    int32_t rc;
+    if ((rc = ensure(c, T.d_box, n_px * ftk::kTemporalBoxBytes)) != FT_OK || (rc = ensure(c, T.d_mask, n_px)) != FT_OK) return rc;
+    uint8_t* const mask = T.d_mask.as<uint8_t>();
+    if (!T.mask_built) {
+        FT_HIP(c, hipMemsetAsync(mask, 0, n_px, c->stream));
+        for (const ft_rect& r : T.rects)
+            FT_HIP(c, hipMemset2DAsync(mask + (size_t)r.y0 * (size_t)T.res_h + (size_t)r.x0, (size_t)T.res_h, 1, (size_t)r.w, (size_t)r.h, c->stream));
+        T.mask_built = true;
+    }
+    for (int k = 0; k < 3; ++k) { box.lo[k] = T.d_box.as<double>() + (size_t)k * n_px; box.hi[k] = T.d_box.as<double>() + (size_t)(3 + k) * n_px; }
+    return FT_OK;
+}
+// One k_temporal_box per rect: the boxes of the frame's neighbourhoods.
+static void launch_temporal_boxes(ft_context* c, const ftk::TemporalBox& box, int32_t& n_launches) {
+    const ft_context::Temporal& T = c->temporal;
+    for (const ft_rect& r : T.rects) {
+        ftk::launch_temporal_box(c->stream, ftk::TemporalBoxArgs{c->d_out.as<double>(), T.d_mask.as<uint8_t>(), box, T.res_h, T.res_v, r.x0, r.y0, r.w, r.h, T.clamp.radius, T.clamp.gamma, T.clamp.floor});
+        ++n_launches;
+    }
+}
+// The records a window's k_temporal reads beside the sets: null where the call does not move / follow.
+struct TemporalRecords { const double* motion = nullptr; const ftk::TemporalDeformLeaf* deform = nullptr; const double* snap = nullptr; };
+// k_temporal's arguments for the window `win`, from the accumulation as it stands before the call's flip.
+static ftk::TemporalArgs temporal_args(ft_context* c, const ftk::GuideWindow& win, const ft_temporal_params& P, bool want_rgb, bool want_rgba8, const TemporalRecords& rec,
+                                       const ftk::TemporalBox& box) {
+    const ft_context::Temporal& T = c->temporal;
+    const size_t n_px = (size_t)T.res_h * (size_t)T.res_v;
+    ftk::TemporalArgs a{};
+    a.win = win;
+    a.frame = c->d_out.as<double>();
+    a.prev = temporal_set(T.d_set[T.prev], n_px); a.cur = temporal_set(T.d_set[T.prev ^ 1], n_px);
+    for (int k = 0; k < 3; ++k) { a.o[k] = T.cam.o[k]; a.i[k] = T.cam.i[k]; a.j[k] = T.cam.j[k]; a.k[k] = T.cam.k[k]; }
+    a.tlx = T.cam.tlx; a.tly = T.cam.tly; a.pw = T.cam.pw; a.ph = T.cam.ph;
+    a.res_h = T.res_h; a.res_v = T.res_v; a.has_prev = T.calls > 0 ? 1 : 0;
+    a.max_history = (double)P.max_history; a.min_normal_dot = P.min_normal_dot;
+    a.tol_scale = P.position_tolerance_px * std::max(T.cam.pw, T.cam.ph);
+    a.out_rgb = want_rgb ? T.d_rgb.as<double>() : nullptr; a.out8 = want_rgba8 ? T.d_rgba8.as<uint8_t>() : nullptr;
+    a.counters = T.d_ctr.as<unsigned long long>();
+    a.motion = rec.motion; a.n_leaves = (uint32_t)c->flat.leaves.size();
+    if (rec.deform) { a.deform = rec.deform; a.tris = c->d_scene[kTris].as<double>(); a.snap = rec.snap; }
+    a.box = box; a.clamped_history = (double)T.clamp.clamped_history;
+    return a;
+}
+// The host's half of a successful accumulate, blocking or queued: the pose the set just written belongs to, the snapshots it has caught
+// up with, the flip, cam' and the call count.
+static void temporal_advance(ft_context* c, const ftk::Camera& cam, bool moving) {
+    ft_context::Temporal& T = c->temporal;
+    const size_t n_leaves = c->flat.leaves.size();
+    if (T.calls == 0 || moving) {
+        T.h_m2w = c->flat.m2w;
+        T.h_w2m.resize(12 * n_leaves);
+        for (size_t l = 0; l < n_leaves; ++l) std::memcpy(&T.h_w2m[12 * l], c->flat.leaves[l].w2m, 12 * sizeof(double));
+        T.pose = c->pose_serial;
+    }
+    temporal_drop_snapshots(c);                                     // the set just written saw the meshes as they are
+    T.prev ^= 1; T.cam = cam; T.calls += 1;
+}
+
 static int32_t temporal_single(ft_context* c, const RenderRequest& q, int32_t sample, const ft_temporal_params& P, bool rgba8, void* out, ft_stats* stats) {
     const auto wall0 = std::chrono::steady_clock::now();
     int32_t rc;
@@ -429,6 +504,7 @@ static int32_t temporal_single(ft_context* c, const RenderRequest& q, int32_t sa
     if (want_rgb && (rc = ensure(c, T.d_rgb, n_px * 24)) != FT_OK) return rc;
     if (want_rgba8 && (rc = ensure(c, T.d_rgba8, n_px * 4)) != FT_OK) return rc;
     FT_HIP(c, hipMemsetAsync(T.d_ctr.p, 0, 3 * sizeof(unsigned long long), c->stream));
+    T.ctr_clean = false;
     const ftk::Camera cam = make_camera(*q.cam, T.res_h, T.res_v);
     // The scene was committed in another pose since the history was written (ft_scene_commit_moved, perhaps several times: H is the
     // pose of the last accumulate, so they compose): every leaf's way back to that pose goes up and k_temporal<true> runs.
@@ -449,38 +525,16 @@ static int32_t temporal_single(ft_context* c, const RenderRequest& q, int32_t sa
     // window.  They depend on the frame alone, so a call that runs again for longer hit lists writes the same boxes again.
     ftk::TemporalBox box{};
     if (T.clamp.radius > 0 && !px.empty()) {
-        if ((rc = ensure(c, T.d_box, n_px * ftk::kTemporalBoxBytes)) != FT_OK || (rc = ensure(c, T.d_mask, n_px)) != FT_OK) return rc;
-        uint8_t* const mask = T.d_mask.as<uint8_t>();
-        if (!T.mask_built) {                                        // the rects are the begin's: once per accumulation (as ft_temporal_filter fills its class plane)
-            FT_HIP(c, hipMemsetAsync(mask, 0, n_px, c->stream));
-            for (const ft_rect& r : T.rects)
-                FT_HIP(c, hipMemset2DAsync(mask + (size_t)r.y0 * (size_t)T.res_h + (size_t)r.x0, (size_t)T.res_h, 1, (size_t)r.w, (size_t)r.h, c->stream));
-            T.mask_built = true;
-        }
-        for (int k = 0; k < 3; ++k) { box.lo[k] = T.d_box.as<double>() + (size_t)k * n_px; box.hi[k] = T.d_box.as<double>() + (size_t)(3 + k) * n_px; }
-        rc = T.timer.run(c, kernel_ms, [&] { for (const ft_rect& r : T.rects) {
-            ftk::launch_temporal_box(c->stream, ftk::TemporalBoxArgs{c->d_out.as<double>(), mask, box, T.res_h, T.res_v, r.x0, r.y0, r.w, r.h, T.clamp.radius, T.clamp.gamma, T.clamp.floor});
-            ++n_launches;
-        } });
-        if (rc != FT_OK) return rc;
+        if ((rc = temporal_box_planes(c, box)) != FT_OK) return rc;
+        if ((rc = T.timer.run(c, kernel_ms, [&] { launch_temporal_boxes(c, box, n_launches); })) != FT_OK) return rc;
     }
     AovRun run;
     const bool want[8] = {false, true, true, false, false, true, false, following};   // p, n, leaf; the triangle only in a call that follows
+    TemporalRecords rec;
+    if (moving) rec.motion = T.d_motion.as<double>();
+    if (following) { rec.deform = T.d_deform.as<ftk::TemporalDeformLeaf>(); rec.snap = T.d_snap.as<double>(); }
     rc = aov_windows(c, q, sample, want, px, run, [&](int64_t p0, uint32_t n, const AovPlanes& pl, char* dev) -> int32_t {
-        ftk::TemporalArgs a{};
-        a.win = guide_window(c, p0, n, pl, dev);
-        a.frame = c->d_out.as<double>();
-        a.prev = temporal_set(T.d_set[T.prev], n_px); a.cur = temporal_set(T.d_set[T.prev ^ 1], n_px);
-        for (int k = 0; k < 3; ++k) { a.o[k] = T.cam.o[k]; a.i[k] = T.cam.i[k]; a.j[k] = T.cam.j[k]; a.k[k] = T.cam.k[k]; }
-        a.tlx = T.cam.tlx; a.tly = T.cam.tly; a.pw = T.cam.pw; a.ph = T.cam.ph;
-        a.res_h = T.res_h; a.res_v = T.res_v; a.has_prev = T.calls > 0 ? 1 : 0;
-        a.max_history = (double)P.max_history; a.min_normal_dot = P.min_normal_dot;
-        a.tol_scale = P.position_tolerance_px * std::max(T.cam.pw, T.cam.ph);
-        a.out_rgb = want_rgb ? T.d_rgb.as<double>() : nullptr; a.out8 = want_rgba8 ? T.d_rgba8.as<uint8_t>() : nullptr;
-        a.counters = T.d_ctr.as<unsigned long long>();
-        a.motion = moving ? T.d_motion.as<double>() : nullptr; a.n_leaves = (uint32_t)n_leaves;
-        if (following) { a.deform = T.d_deform.as<ftk::TemporalDeformLeaf>(); a.tris = c->d_scene[kTris].as<double>(); a.snap = T.d_snap.as<double>(); }
-        a.box = box; a.clamped_history = (double)T.clamp.clamped_history;
+        const ftk::TemporalArgs a = temporal_args(c, guide_window(c->aov.d_pixels.as<uint32_t>(), p0, n, pl, dev), P, want_rgb, want_rgba8, rec, box);
         ++n_launches;
         return T.timer.run(c, kernel_ms, [&] { ftk::launch_temporal(c->stream, a); });
     });
@@ -489,17 +543,22 @@ static int32_t temporal_single(ft_context* c, const RenderRequest& q, int32_t sa
     if (!px.empty() && (rc = read_counters(c, T.d_ctr, ctr, 3)) != FT_OK) return rc;
     if (out && (rc = copy_rects_out(c, out, rgba8 ? T.d_rgba8.p : T.d_rgb.p, rgba8 ? 4 : 24, T.res_h, T.rects, nullptr)) != FT_OK) return rc;
     if (P.to_frame && !px.empty() && (rc = temporal_to_frame(c, T.d_rgb.p)) != FT_OK) return rc;   // the means replace the tile pixels of the frame, once the call can no longer fail
-    if (T.calls == 0 || moving) {                                   // the pose the set just written belongs to
-        T.h_m2w = c->flat.m2w;
-        T.h_w2m.resize(12 * n_leaves);
-        for (size_t l = 0; l < n_leaves; ++l) std::memcpy(&T.h_w2m[12 * l], c->flat.leaves[l].w2m, 12 * sizeof(double));
-        T.pose = c->pose_serial;
-    }
-    temporal_drop_snapshots(c);                                     // the set just written saw the meshes as they are
-    T.prev ^= 1; T.cam = cam; T.calls += 1;
+    temporal_advance(c, cam, moving);
     T.with_history = (int64_t)ctr[0]; T.at_max = (int64_t)ctr[1]; T.clamped = (int64_t)ctr[2];
     end_pass(stats, run, kernel_ms, n_launches, wall0);
     if (stats) stats->trace_kernel_ms = run.kernel_ms;
+    return FT_OK;
+}
+
+// The argument checks of ft_temporal_accumulate, which ft_temporal_enqueue makes in the same order under its own name.
+static int32_t check_accumulate_args(ft_context* c, const std::string& api, const ft_camera* cam, int32_t spp, const double* jitter_xy, int32_t sample, const ft_temporal_params* params) {
+    int32_t rc;
+    if ((rc = check_guide_sample(c, api, spp, jitter_xy, sample, " to take the surfaces from")) != FT_OK) return rc;
+    if (!cam || !params) { c->err = api + ": null cam or params"; return FT_ERR_INVALID; }
+    const ft_temporal_params& P = *params;
+    if (P.max_history < 1) { c->err = api + ": max_history below 1"; return FT_ERR_INVALID; }
+    if (!(P.min_normal_dot >= -1.0 && P.min_normal_dot <= 1.0)) { c->err = api + ": min_normal_dot is NaN or outside [-1, 1]"; return FT_ERR_INVALID; }
+    if (!(P.position_tolerance_px > 0.0)) { c->err = api + ": position_tolerance_px is not > 0"; return FT_ERR_INVALID; }
     return FT_OK;
 }
 
@@ -507,12 +566,8 @@ int32_t ft_temporal_accumulate(ft_context* c, const ft_camera* cam, int32_t spp,
                                const ft_temporal_params* params, int32_t rgba8, void* out, ft_stats* stats) {
     if (!c) return FT_ERR_INVALID;
     int32_t rc;
-    if ((rc = check_guide_sample(c, "ft_temporal_accumulate", spp, jitter_xy, sample, " to take the surfaces from")) != FT_OK) return rc;
-    if (!cam || !params) { c->err = "ft_temporal_accumulate: null cam or params"; return FT_ERR_INVALID; }
+    if ((rc = check_accumulate_args(c, "ft_temporal_accumulate", cam, spp, jitter_xy, sample, params)) != FT_OK) return rc;
     const ft_temporal_params& P = *params;
-    if (P.max_history < 1) { c->err = "ft_temporal_accumulate: max_history below 1"; return FT_ERR_INVALID; }
-    if (!(P.min_normal_dot >= -1.0 && P.min_normal_dot <= 1.0)) { c->err = "ft_temporal_accumulate: min_normal_dot is NaN or outside [-1, 1]"; return FT_ERR_INVALID; }
-    if (!(P.position_tolerance_px > 0.0)) { c->err = "ft_temporal_accumulate: position_tolerance_px is not > 0"; return FT_ERR_INVALID; }
     if (!need_device(c)) return FT_ERR_NO_DEVICE;
     if ((rc = need_one_device(c, "ft_temporal_accumulate")) != FT_OK) return rc;
     if (!c->temporal.open) { c->err = kNoTemporalEnded; return FT_ERR_STATE; }
@@ -524,6 +579,53 @@ int32_t ft_temporal_accumulate(ft_context* c, const ft_camera* cam, int32_t spp,
 // planes are written until the call can no longer fail; the sets, cam', the counts, the cached pixel list and the level hint are not
 // touched.  Without `demodulate` there is no guide pass, no pixel list and no upload: the class plane is filled per rect and the
 // kernels run over rects and the frame.
+// The steps ft_temporal_filter and ft_temporal_enqueue share.  The filter's planes: allocated by the first filter of the accumulation; the
+// class plane is filled here - outside everywhere, then "in the tiles" per rect: k_tfilter_prepare makes that hit or miss.
+static int32_t tfilter_planes(ft_context* c, bool demodulate, bool want8, ftk::TFilterPlanes& g) {
+    ft_context::Temporal& T = c->temporal;
+    const size_t n_px = (size_t)T.res_h * (size_t)T.res_v;
+    int32_t rc;
+    if (demodulate && (rc = ensure(c, T.d_fd, n_px * 24)) != FT_OK) return rc;
+    if ((rc = ensure(c, T.d_fcls, n_px)) != FT_OK) return rc;
+    for (int k = 0; k < 2; ++k) {
+        if ((rc = ensure(c, T.d_fu[k], n_px * 24)) != FT_OK) return rc;
+        if ((rc = ensure(c, T.d_fv[k], n_px * 8)) != FT_OK) return rc;
+    }
+    if (want8 && (rc = ensure(c, T.d_f8, n_px * 4)) != FT_OK) return rc;
+    if (demodulate) for (int k = 0; k < 3; ++k) g.d[k] = T.d_fd.as<double>() + (size_t)k * n_px;
+    g.cls = T.d_fcls.as<uint8_t>();
+    FT_HIP(c, hipMemsetAsync(g.cls, ftk::kDenoiseOutside, n_px, c->stream));
+    for (const ft_rect& r : T.rects)
+        FT_HIP(c, hipMemset2DAsync(g.cls + (size_t)r.y0 * (size_t)T.res_h + (size_t)r.x0, (size_t)T.res_h, ftk::kDenoiseMiss, (size_t)r.w, (size_t)r.h, c->stream));
+    return FT_OK;
+}
+// k_tfilter_prepare per rect and the iterations; result / variance: where the last one left them (prepare's planes without iterations).
+static void launch_tfilter_passes(ft_context* c, const ft_temporal_filter_params& P, const ftk::TemporalSet& set, const ftk::TFilterPlanes& g, bool want8, bool want_rgb,
+                                  int32_t& n_launches, const void*& result, const double*& variance) {
+    const ft_context::Temporal& T = c->temporal;
+    for (const ft_rect& r : T.rects) {
+        ftk::TFilterPrepareArgs a{};
+        a.set = set; a.g = g; a.u0 = T.d_fu[0].as<double>(); a.v0 = T.d_fv[0].as<double>();
+        a.raw = P.iterations == 0 ? 1 : 0; a.out8 = a.raw && want8 ? T.d_f8.as<uint8_t>() : nullptr;
+        a.res_h = T.res_h; a.res_v = T.res_v; a.x0 = r.x0; a.y0 = r.y0; a.w = r.w; a.h = r.h;
+        a.min_history = (double)P.min_history; a.inv_sn2 = inv_sq(P.sigma_normal); a.inv_sp2 = inv_sq(P.sigma_position);
+        ftk::launch_tfilter_prepare(c->stream, a);
+        ++n_launches;
+    }
+    for (int i = 0; i < P.iterations; ++i) {
+        const bool last = i + 1 == P.iterations;
+        ftk::TFilterArgs a{};
+        a.u_in = T.d_fu[i & 1].as<double>(); a.v_in = T.d_fv[i & 1].as<double>();
+        a.u_out = !last || want_rgb ? T.d_fu[(i + 1) & 1].as<double>() : nullptr; a.v_out = T.d_fv[(i + 1) & 1].as<double>();
+        a.out8 = last && want8 ? T.d_f8.as<uint8_t>() : nullptr;
+        a.set = set; a.g = g; a.res_h = T.res_h; a.res_v = T.res_v; a.step = 1 << i;
+        a.inv_sn2 = inv_sq(P.sigma_normal); a.inv_sp2 = inv_sq(P.sigma_position); a.inv_sc2 = inv_sq(P.sigma_colour); a.variance_floor = P.variance_floor;
+        ftk::launch_tfilter(c->stream, a, last);
+        ++n_launches;
+        if (last) { result = a.u_out; variance = a.v_out; }
+    }
+}
+
 static int32_t temporal_filter_single(ft_context* c, const RenderRequest& q, int32_t sample, const ft_temporal_filter_params& P, bool rgba8, void* out,
                                       double* out_variance, ft_stats* stats) {
     const auto wall0 = std::chrono::steady_clock::now();
@@ -537,21 +639,9 @@ static int32_t temporal_filter_single(ft_context* c, const RenderRequest& q, int
     if ((rc = drain_frame_streams(c)) != FT_OK) return rc;          // the frame may have been written on another stream (fetch_single)
     const size_t n_px = (size_t)T.res_h * (size_t)T.res_v;
     const bool want8 = out && rgba8, want_rgb = P.to_frame || (out && !rgba8);
-    if (P.demodulate && (rc = ensure(c, T.d_fd, n_px * 24)) != FT_OK) return rc;
-    if ((rc = ensure(c, T.d_fcls, n_px)) != FT_OK) return rc;
-    for (int k = 0; k < 2; ++k) {
-        if ((rc = ensure(c, T.d_fu[k], n_px * 24)) != FT_OK) return rc;
-        if ((rc = ensure(c, T.d_fv[k], n_px * 8)) != FT_OK) return rc;
-    }
-    if (want8 && (rc = ensure(c, T.d_f8, n_px * 4)) != FT_OK) return rc;
     const ftk::TemporalSet set = temporal_set(T.d_set[T.prev], n_px);
     ftk::TFilterPlanes g{};
-    double* dw[3] = {nullptr, nullptr, nullptr};
-    if (P.demodulate) for (int k = 0; k < 3; ++k) g.d[k] = dw[k] = T.d_fd.as<double>() + (size_t)k * n_px;
-    g.cls = T.d_fcls.as<uint8_t>();
-    FT_HIP(c, hipMemsetAsync(g.cls, ftk::kDenoiseOutside, n_px, c->stream));   // outside everywhere, then "in the tiles" per rect: k_tfilter_prepare makes that hit or miss
-    for (const ft_rect& r : T.rects)
-        FT_HIP(c, hipMemset2DAsync(g.cls + (size_t)r.y0 * (size_t)T.res_h + (size_t)r.x0, (size_t)T.res_h, ftk::kDenoiseMiss, (size_t)r.w, (size_t)r.h, c->stream));
+    if ((rc = tfilter_planes(c, P.demodulate != 0, want8, g)) != FT_OK) return rc;
     double kernel_ms = 0.0;
     int32_t n_launches = 0;
     TimedLaunch& timer = T.ftimer;
@@ -561,9 +651,9 @@ static int32_t temporal_filter_single(ft_context* c, const RenderRequest& q, int
         const bool want[8] = {false, false, false, true, false, true, false, false};   // colour, leaf
         rc = aov_windows(c, q, sample, want, px, run, [&](int64_t p0, uint32_t n, const AovPlanes& pl, char* dev) -> int32_t {
             ftk::TFilterScatterArgs a{};
-            a.win = guide_window(c, p0, n, pl, dev);
+            a.win = guide_window(c->aov.d_pixels.as<uint32_t>(), p0, n, pl, dev);
             a.set_leaf = set.leaf; a.albedo_floor = P.albedo_floor;
-            for (int k = 0; k < 3; ++k) a.d[k] = dw[k];
+            for (int k = 0; k < 3; ++k) a.d[k] = T.d_fd.as<double>() + (size_t)k * n_px;
             ++n_launches;
             return timer.run(c, kernel_ms, [&] { ftk::launch_tfilter_scatter(c->stream, a); });
         });
@@ -571,35 +661,27 @@ static int32_t temporal_filter_single(ft_context* c, const RenderRequest& q, int
     }
     const void* result = T.d_fu[0].p;                               // no iterations: prepare's M
     const double* variance = T.d_fv[0].as<double>();
-    rc = timer.run(c, kernel_ms, [&] {                              // one bracket around prepare and all iterations
-        for (const ft_rect& r : T.rects) {
-            ftk::TFilterPrepareArgs a{};
-            a.set = set; a.g = g; a.u0 = T.d_fu[0].as<double>(); a.v0 = T.d_fv[0].as<double>();
-            a.raw = P.iterations == 0 ? 1 : 0; a.out8 = a.raw && want8 ? T.d_f8.as<uint8_t>() : nullptr;
-            a.res_h = T.res_h; a.res_v = T.res_v; a.x0 = r.x0; a.y0 = r.y0; a.w = r.w; a.h = r.h;
-            a.min_history = (double)P.min_history; a.inv_sn2 = inv_sq(P.sigma_normal); a.inv_sp2 = inv_sq(P.sigma_position);
-            ftk::launch_tfilter_prepare(c->stream, a);
-            ++n_launches;
-        }
-        for (int i = 0; i < P.iterations; ++i) {
-            const bool last = i + 1 == P.iterations;
-            ftk::TFilterArgs a{};
-            a.u_in = T.d_fu[i & 1].as<double>(); a.v_in = T.d_fv[i & 1].as<double>();
-            a.u_out = !last || want_rgb ? T.d_fu[(i + 1) & 1].as<double>() : nullptr; a.v_out = T.d_fv[(i + 1) & 1].as<double>();
-            a.out8 = last && want8 ? T.d_f8.as<uint8_t>() : nullptr;
-            a.set = set; a.g = g; a.res_h = T.res_h; a.res_v = T.res_v; a.step = 1 << i;
-            a.inv_sn2 = inv_sq(P.sigma_normal); a.inv_sp2 = inv_sq(P.sigma_position); a.inv_sc2 = inv_sq(P.sigma_colour); a.variance_floor = P.variance_floor;
-            ftk::launch_tfilter(c->stream, a, last);
-            ++n_launches;
-            if (last) { result = a.u_out; variance = a.v_out; }
-        }
-    });
-    if (rc != FT_OK) return rc;
+    // one bracket around prepare and all iterations
+    if ((rc = timer.run(c, kernel_ms, [&] { launch_tfilter_passes(c, P, set, g, want8, want_rgb, n_launches, result, variance); })) != FT_OK) return rc;
     if (out && (rc = copy_rects_out(c, out, rgba8 ? T.d_f8.p : result, rgba8 ? 4 : 24, T.res_h, T.rects, nullptr)) != FT_OK) return rc;
     if (out_variance && (rc = copy_rects_out(c, out_variance, variance, 8, T.res_h, T.rects, nullptr)) != FT_OK) return rc;
     if (P.to_frame && (rc = temporal_to_frame(c, result)) != FT_OK) return rc;   // the result replaces them, once the call can no longer fail
     end_pass(stats, run, kernel_ms, n_launches, wall0);
     if (stats) stats->trace_kernel_ms = run.kernel_ms;
+    return FT_OK;
+}
+
+// The argument checks of ft_temporal_filter behind its null tests, which ft_temporal_enqueue makes in the same order under its own name.
+static int32_t check_tfilter_args(ft_context* c, const std::string& api, const ft_camera* cam, int32_t spp, const double* jitter_xy, int32_t sample, const ft_temporal_filter_params& P) {
+    int32_t rc;
+    if ((rc = check_filter_params(c, api, P.iterations, P.sigma_colour, P.sigma_normal, P.sigma_position)) != FT_OK) return rc;
+    if (P.min_history < 1) { c->err = api + ": min_history below 1"; return FT_ERR_INVALID; }
+    if (!(P.variance_floor > 0.0)) { c->err = api + ": variance_floor is not > 0"; return FT_ERR_INVALID; }
+    if ((rc = check_albedo_floor(c, api, P.demodulate, P.albedo_floor)) != FT_OK) return rc;
+    if (P.demodulate) {
+        if ((rc = check_guide_sample(c, api, spp, jitter_xy, sample, " to take the material colour from")) != FT_OK) return rc;
+        if (!cam) { c->err = api + ": demodulate needs the camera of the accumulate call"; return FT_ERR_INVALID; }
+    }
     return FT_OK;
 }
 
@@ -609,14 +691,7 @@ int32_t ft_temporal_filter(ft_context* c, const ft_camera* cam, int32_t spp, con
     if (!params || (!out && !out_variance)) { c->err = "ft_temporal_filter: null params, or neither out nor out_variance"; return FT_ERR_INVALID; }
     const ft_temporal_filter_params& P = *params;
     int32_t rc;
-    if ((rc = check_filter_params(c, "ft_temporal_filter", P.iterations, P.sigma_colour, P.sigma_normal, P.sigma_position)) != FT_OK) return rc;
-    if (P.min_history < 1) { c->err = "ft_temporal_filter: min_history below 1"; return FT_ERR_INVALID; }
-    if (!(P.variance_floor > 0.0)) { c->err = "ft_temporal_filter: variance_floor is not > 0"; return FT_ERR_INVALID; }
-    if ((rc = check_albedo_floor(c, "ft_temporal_filter", P.demodulate, P.albedo_floor)) != FT_OK) return rc;
-    if (P.demodulate) {
-        if ((rc = check_guide_sample(c, "ft_temporal_filter", spp, jitter_xy, sample, " to take the material colour from")) != FT_OK) return rc;
-        if (!cam) { c->err = "ft_temporal_filter: demodulate needs the camera of the accumulate call"; return FT_ERR_INVALID; }
-    }
+    if ((rc = check_tfilter_args(c, "ft_temporal_filter", cam, spp, jitter_xy, sample, P)) != FT_OK) return rc;
     if (!need_device(c)) return FT_ERR_NO_DEVICE;
     if ((rc = need_one_device(c, "ft_temporal_filter")) != FT_OK) return rc;
     if (!c->temporal.open) { c->err = kNoTemporalEnded; return FT_ERR_STATE; }
@@ -629,9 +704,233 @@ int32_t ft_temporal_filter(ft_context* c, const ft_camera* cam, int32_t spp, con
     return with_growing_hit_lists(c, [&] { return temporal_filter_single(c, q, sample, P, rgba8 != 0, out, out_variance, stats); });
 }
 
+// ------------------------------------------------------------------------------------------ queued temporal calls
+// ft_temporal_enqueue / ft_temporal_wait (functracer_hip.h).  The call is the blocking pair's kernels, launched as they
+// are, in the pair's order on the context's first main stream with nothing between them but stream order: no host wait between windows,
+// one event pair around the lot, and k_temporal_report as the last kernel, which hands the counts to the slot's pinned record.  What the
+// blocking calls do on the host once the device has finished - the flip, cam', the pose, the snapshot drop - happens when the call is
+// queued; the counts arrive when it retires.  DESIGN.md 12.2 lists every buffer the call shares with a frame or another call and what
+// orders the two.
+} // extern "C"
+
+// A buffer that queued calls may still be using is not freed under them: everything they queue is on the context's first main stream.
+static int32_t ensure_quiet(ft_context* c, DeviceBuf& b, size_t bytes) {
+    if (b.p && b.bytes < std::max<size_t>(bytes, 16) && c->temporal.q_pending > 0) FT_HIP(c, hipStreamSynchronize(c->stream));
+    return ensure(c, b, bytes);
+}
+template <class T> static int32_t upload_quiet(ft_context* c, DeviceBuf& b, const std::vector<T>& v) {
+    const int32_t rc = ensure_quiet(c, b, v.size() * sizeof(T));
+    return rc != FT_OK ? rc : upload(c, b, v);
+}
+
+// Waits for the call in slot S and takes its counts; `stats`, when given, receives the call's.
+static int32_t retire_temporal_slot(ft_context* c, ft_context::Temporal::QueueSlot& S, ft_stats* stats) {
+    ft_context::Temporal& T = c->temporal;
+    FT_HIP(c, hipEventSynchronize(S.ev[1]));
+    const ftk::TemporalReport r = *S.h_report;
+    S.d_snap.release();                                             // the snapshots the call followed
+    T.with_history = (int64_t)r.with_history; T.at_max = (int64_t)r.at_max; T.clamped = (int64_t)r.clamped;
+    if (stats) {
+        std::memset(stats, 0, sizeof *stats);
+        stats->rays_primary = (uint64_t)S.n_pix; stats->hits_primary = r.hits;
+        stats->n_launches = S.n_launches;
+        float ms = 0.0f;
+        if (hipEventElapsedTime(&ms, S.ev[0], S.ev[1]) == hipSuccess) stats->kernel_ms = ms;
+        stats->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - S.wall0).count();
+    }
+    if (r.overflow) {
+        c->err = "ft_temporal_enqueue: CSG hit list overflow in the guide pass of a queued call; the accumulation is ended (one blocking ft_render or "
+                 "ft_temporal_accumulate grows the lists, which stay: then ft_temporal_begin again)";
+        return FT_ERR_OVERFLOW;
+    }
+    return FT_OK;
+}
+
+namespace ftc {
+int32_t retire_temporal(ft_context* c, ft_stats* stats) {
+    ft_context::Temporal& T = c->temporal;
+    if (T.q_pending == 0) return FT_OK;
+    FT_HIP(c, hipSetDevice(c->device));
+    int32_t rc = FT_OK;
+    std::string why;
+    while (T.q_pending > 0) {                                       // oldest first; the statistics asked for are the newest call's
+        ft_context::Temporal::QueueSlot& S = T.queue[(T.q_turn + ft_context::Temporal::kQueue - T.q_pending) % ft_context::Temporal::kQueue];
+        const int32_t r = retire_temporal_slot(c, S, T.q_pending == 1 ? stats : nullptr);
+        --T.q_pending;
+        if (r != FT_OK && rc == FT_OK) { rc = r; why = c->err; }
+    }
+    T.fork_owed = false;                                            // the event behind the last reader of the frame has passed
+    if (rc == FT_ERR_OVERFLOW) T.release();                         // later calls read a history written from overflowed rays: as ft_temporal_end
+    if (rc != FT_OK) c->err = why;
+    return rc;
+}
+} // namespace ftc
+
+static int32_t temporal_enqueue_single(ft_context* c, const RenderRequest& q, int32_t sample, const ft_temporal_params& P, const ft_temporal_filter_params* F, bool rgba8, void* host_out) {
+    using Temporal = ft_context::Temporal;
+    const auto wall0 = std::chrono::steady_clock::now();
+    int32_t rc;
+    FT_HIP(c, hipSetDevice(c->device));
+    Temporal& T = c->temporal;
+    if ((rc = need_fp64_frame(c, "ft_temporal_enqueue", T.res_h, T.res_v, "accumulation", " than ft_temporal_begin fixed")) != FT_OK) return rc;
+    if (!need_committed(c)) return FT_ERR_STATE;
+    const size_t n_leaves = c->flat.leaves.size();
+    const bool moving = T.calls > 0 && T.pose != c->pose_serial;
+    const bool following = c->opt.temporal_follow_deformed && T.calls > 0 && !T.snaps.empty();
+    if ((moving || following) && (T.h_m2w.size() != 12 * n_leaves || T.h_w2m.size() != 12 * n_leaves)) { c->err = "ft_temporal_enqueue: the scene has other leaves than the history"; return FT_ERR_STATE; }
+    // The slot: call k + FT_TEMPORAL_QUEUE_DEPTH waits for call k here, on the host.  An error of that call is this call's answer (and
+    // ends the wait for the others: their host buffers are the host's again).
+    if (T.q_pending == Temporal::kQueue) {
+        rc = retire_temporal_slot(c, T.queue[T.q_turn], nullptr);
+        --T.q_pending;
+        if (rc != FT_OK) {
+            const std::string why = c->err;
+            (void)retire_temporal(c, nullptr);
+            if (rc == FT_ERR_OVERFLOW && T.open) T.release();
+            c->err = why;
+            return rc;
+        }
+    }
+    Temporal::QueueSlot& S = T.queue[T.q_turn];
+    if (!S.h_report) {
+        FT_HIP(c, hipHostMalloc(reinterpret_cast<void**>(&S.h_report), sizeof(ftk::TemporalReport), hipHostMallocDefault));
+        FT_HIP(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&S.d_report), S.h_report, 0));
+    }
+    for (hipEvent_t& e : S.ev) if (!e) FT_HIP(c, hipEventCreate(&e));
+    if (!T.fork) FT_HIP(c, hipEventCreateWithFlags(&T.fork, hipEventDisableTiming));
+    const size_t n_px = (size_t)T.res_h * (size_t)T.res_v;
+    const int64_t n_pix = T.n_pix;
+    const bool filtering = F && n_pix > 0;                           // (the blocking filter returns at once over no pixels)
+    const bool want_rgb = !F && host_out && !rgba8, want_rgba8 = !F && host_out && rgba8;   // the accumulate's own results: only when they leave
+    if (want_rgb && (rc = ensure_quiet(c, T.d_rgb, n_px * 24)) != FT_OK) return rc;
+    if (want_rgba8 && (rc = ensure_quiet(c, T.d_rgba8, n_px * 4)) != FT_OK) return rc;
+    // Everything below is queued on the one stream, in the blocking pair's order.  First what the accumulation keeps for its queued calls.
+    if (n_pix > 0 && T.q_pixels.empty()) {
+        (void)list_pixels(T.rects, T.res_h, T.q_pixels);
+        if ((rc = upload_quiet(c, T.d_qpixels, T.q_pixels)) != FT_OK) return rc;
+    }
+    {
+        std::vector<double> jitter(q.jitter_xy, q.jitter_xy + 2 * (size_t)q.spp);
+        if (jitter != T.q_jitter || !T.d_qjitter.p) {
+            S.jitter = jitter;                                      // (the copy's source lives as long as the call)
+            if ((rc = upload_quiet(c, T.d_qjitter, S.jitter)) != FT_OK) return rc;
+            T.q_jitter.swap(jitter);
+        }
+    }
+    if ((rc = ensure_quiet(c, c->aov.d_ctr, 2 * sizeof(unsigned long long))) != FT_OK) return rc;
+    if (!T.ctr_clean) FT_HIP(c, hipMemsetAsync(T.d_ctr.p, 0, 3 * sizeof(unsigned long long), c->stream));
+    if (!c->aov.ctr_clean) FT_HIP(c, hipMemsetAsync(c->aov.d_ctr.p, 0, 2 * sizeof(unsigned long long), c->stream));
+    TemporalRecords rec;
+    if (moving) {
+        S.motion = temporal_motion(c->flat, T.h_m2w, T.h_w2m);
+        if ((rc = upload_quiet(c, S.d_motion, S.motion)) != FT_OK) return rc;
+        rec.motion = S.d_motion.as<double>();
+    }
+    if (following) {
+        S.deform = temporal_deform(c->flat, T);
+        if ((rc = upload_quiet(c, S.d_deform, S.deform)) != FT_OK) return rc;
+        rec.deform = S.d_deform.as<ftk::TemporalDeformLeaf>(); rec.snap = T.d_snap.as<double>();
+    }
+    const int64_t per = guide_window_size(c, n_pix);
+    const bool want[8] = {false, true, true, filtering && F->demodulate, false, true, false, following};   // p, n, leaf; the colour for the filter's d; the triangle in a call that follows
+    const AovPlanes pl = aov_planes(want, per);
+    if (n_pix > 0 && (rc = ensure_quiet(c, c->aov.d_out, (size_t)per * pl.bytes_per_entry)) != FT_OK) return rc;
+    ftk::TemporalBox box{};
+    const bool clamping = T.clamp.radius > 0 && n_pix > 0;
+    if (clamping && (rc = temporal_box_planes(c, box)) != FT_OK) return rc;
+    ftk::TFilterPlanes g{};
+    // Join: the frame this call reads may still be on its way on the frame driver's other streams - k_resolve on `tail`, the tracing of
+    // simple frames on the further mains (the first main is this call's own stream).  Waits on the device only.
+    if (n_pix > 0 && any_pending(c)) {
+        bool on[ft_context::kMains] = {};
+        for (const ft_context::FrameSlot& f : c->slots) if (f.pending) { on[0] = on[0] || f.simple; if (f.main_ix > 0) on[f.main_ix] = true; }
+        for (int k = 0; k < ft_context::kMains; ++k) {
+            if (!on[k]) continue;
+            if (!T.join[k]) FT_HIP(c, hipEventCreateWithFlags(&T.join[k], hipEventDisableTiming));
+            FT_HIP(c, hipEventRecord(T.join[k], k == 0 ? c->tail : c->more_mains[k - 1]));
+            FT_HIP(c, hipStreamWaitEvent(c->stream, T.join[k], 0));
+        }
+    }
+    FT_HIP(c, hipEventRecord(S.ev[0], c->stream));
+    int32_t n_launches = 0;
+    if (clamping) launch_temporal_boxes(c, box, n_launches);
+    const ftk::TemporalSet written = temporal_set(T.d_set[T.prev ^ 1], n_px);   // the set this call writes: the filter's input
+    if (filtering) {
+        const bool want8 = rgba8;
+        if ((rc = tfilter_planes(c, F->demodulate != 0, want8, g)) != FT_OK) return rc;
+    }
+    const ftk::Camera cam = make_camera(*q.cam, T.res_h, T.res_v);
+    char* const dev = c->aov.d_out.as<char>();
+    for (int64_t p0 = 0; p0 < n_pix; p0 += per) {
+        const uint32_t n = (uint32_t)std::min<int64_t>(per, n_pix - p0);
+        launch_guide_window(c, q, sample, cam, T.d_qpixels.as<uint32_t>(), T.d_qjitter.as<double>(), p0, n, pl, dev);
+        const ftk::GuideWindow win = guide_window(T.d_qpixels.as<uint32_t>(), p0, n, pl, dev);
+        ftk::launch_temporal(c->stream, temporal_args(c, win, P, want_rgb, want_rgba8, rec, box));
+        n_launches += 2;
+        // Fork: behind the last kernel that reads the frame.  The next frame's writers of d_out wait for this event (queue_frame).
+        if (p0 + per >= n_pix) { FT_HIP(c, hipEventRecord(T.fork, c->stream)); T.fork_owed = true; }
+        if (filtering && F->demodulate) {                            // the filter's d from this window's colours: there is no second guide pass
+            ftk::TFilterScatterArgs a{};
+            a.win = win; a.set_leaf = written.leaf; a.albedo_floor = F->albedo_floor;
+            for (int k = 0; k < 3; ++k) a.d[k] = T.d_fd.as<double>() + (size_t)k * n_px;
+            ftk::launch_tfilter_scatter(c->stream, a);
+            ++n_launches;
+        }
+    }
+    if (!F && host_out && (rc = copy_rects_out(c, host_out, rgba8 ? T.d_rgba8.p : T.d_rgb.p, rgba8 ? 4 : 24, T.res_h, T.rects, c->stream)) != FT_OK) return rc;
+    if (filtering) {
+        const void* result = T.d_fu[0].p;
+        const double* variance = T.d_fv[0].as<double>();
+        launch_tfilter_passes(c, *F, written, g, rgba8, !rgba8, n_launches, result, variance);
+        if ((rc = copy_rects_out(c, host_out, rgba8 ? T.d_f8.p : result, rgba8 ? 4 : 24, T.res_h, T.rects, c->stream)) != FT_OK) return rc;
+    }
+    ftk::launch_temporal_report(c->stream, T.d_ctr.as<unsigned long long>(), c->aov.d_ctr.as<unsigned long long>(), S.d_report);
+    T.ctr_clean = c->aov.ctr_clean = true;
+    FT_HIP(c, hipEventRecord(S.ev[1], c->stream));
+    FT_HIP(c, hipGetLastError());
+    // The host's half, now: the snapshots this call follows stay alive in its slot, everything else as the blocking call leaves it.
+    S.d_snap.release();
+    if (following) { S.d_snap = T.d_snap; T.d_snap = DeviceBuf{}; }
+    temporal_advance(c, cam, moving);
+    S.n_pix = n_pix; S.n_launches = n_launches; S.wall0 = wall0;
+    T.q_turn = (T.q_turn + 1) % Temporal::kQueue; ++T.q_pending;
+    return FT_OK;
+}
+
+extern "C" {
+
+int32_t ft_temporal_enqueue(ft_context* c, const ft_camera* cam, int32_t spp, const double* jitter_xy, int32_t sample, uint64_t seed,
+                            const ft_temporal_params* params, const ft_temporal_filter_params* filter, int32_t rgba8, void* host_out) {
+    if (!c) return FT_ERR_INVALID;
+    static const std::string api = "ft_temporal_enqueue";
+    int32_t rc;
+    if ((rc = check_accumulate_args(c, api, cam, spp, jitter_xy, sample, params)) != FT_OK) return rc;
+    if (filter) {
+        if (!host_out) { c->err = api + ": a filter needs host_out (the filtered frame has nowhere else to go)"; return FT_ERR_INVALID; }
+        if ((rc = check_tfilter_args(c, api, cam, spp, jitter_xy, sample, *filter)) != FT_OK) return rc;
+    }
+    if (params->to_frame) { c->err = api + ": to_frame is not offered in the queued call (it would write the frame a queued frame may be writing): use the blocking ft_temporal_accumulate"; return FT_ERR_INVALID; }
+    if (filter && filter->to_frame) { c->err = api + ": the filter's to_frame is not offered in the queued call: use the blocking ft_temporal_filter"; return FT_ERR_INVALID; }
+    if (!need_device(c)) return FT_ERR_NO_DEVICE;
+    if ((rc = need_one_device(c, api)) != FT_OK) return rc;
+    if (!c->temporal.open) { c->err = kNoTemporalEnded; return FT_ERR_STATE; }
+    const RenderRequest q{cam, c->temporal.res_h, c->temporal.res_v, spp, jitter_xy, 0, seed, nullptr, 0, 0};
+    return temporal_enqueue_single(c, q, sample, *params, filter, rgba8 != 0, host_out);
+}
+
+int32_t ft_temporal_wait(ft_context* c, ft_stats* stats) {
+    if (!c) return FT_ERR_INVALID;
+    if (!need_device(c)) return FT_ERR_NO_DEVICE;
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    return retire_temporal(c, stats);
+}
+
+// The calls below answer from the host's copy of the accumulation's state: queued calls are retired first.
 int32_t ft_temporal_fetch(ft_context* c, double* mean_rgb, double* stderr_rgb, double* length) {
     if (!c) return FT_ERR_INVALID;
     if (!need_device(c)) return FT_ERR_NO_DEVICE;
+    int32_t qrc;
+    if ((qrc = retire_temporal(c, nullptr)) != FT_OK) return qrc;
     const ft_context::Temporal& T = c->temporal;
     if (!T.open) { c->err = kNoTemporal; return FT_ERR_STATE; }
     const size_t n_px = (size_t)T.res_h * (size_t)T.res_v;
@@ -660,6 +959,8 @@ int32_t ft_temporal_fetch(ft_context* c, double* mean_rgb, double* stderr_rgb, d
 int32_t ft_temporal_status(ft_context* c, int64_t out[4]) {
     if (!c || !out) return FT_ERR_INVALID;
     if (!need_device(c)) return FT_ERR_NO_DEVICE;
+    int32_t qrc;
+    if ((qrc = retire_temporal(c, nullptr)) != FT_OK) return qrc;
     const ft_context::Temporal& T = c->temporal;
     if (!T.open) { c->err = kNoTemporal; return FT_ERR_STATE; }
     out[0] = T.calls; out[1] = T.n_pix; out[2] = T.with_history; out[3] = T.at_max;
@@ -687,6 +988,8 @@ int32_t ft_temporal_set_clamp(ft_context* c, const ft_temporal_clamp_params* par
 int32_t ft_temporal_clamp_status(ft_context* c, int64_t out[2]) {
     if (!c || !out) return FT_ERR_INVALID;
     if (!need_device(c)) return FT_ERR_NO_DEVICE;
+    int32_t qrc;
+    if ((qrc = retire_temporal(c, nullptr)) != FT_OK) return qrc;
     const ft_context::Temporal& T = c->temporal;
     if (!T.open) { c->err = kNoTemporal; return FT_ERR_STATE; }
     out[0] = T.clamp.radius; out[1] = T.clamped;
@@ -696,8 +999,9 @@ int32_t ft_temporal_clamp_status(ft_context* c, int64_t out[2]) {
 int32_t ft_temporal_end(ft_context* c) {
     if (!c) return FT_ERR_INVALID;
     if (!need_device(c)) return FT_ERR_NO_DEVICE;
+    const int32_t qrc = retire_temporal(c, nullptr);                // an error among the queued calls is reported; the accumulation ends either way
     temporal_close(c);
-    return FT_OK;
+    return qrc;
 }
 
 } // extern "C"

@@ -248,7 +248,24 @@ template <int R> __global__ __launch_bounds__(kBlock) void k_temporal_box(Tempor
     }
 }
 
+// The end of a queued call.  What it hands over was written by kernels that ended before this one began (their atomics were performed
+// at the L2), so the loads need no fence; the record lies in pinned host memory and the stores are plain vector stores: they are
+// visible to the host when the kernel has ended, and the host reads the record only behind an event recorded after this launch (the
+// frame driver's hand_over_frame relies on the same).  The loads return before the cells are cleared: each lane clears what it read.
+__global__ __launch_bounds__(64) void k_temporal_report(unsigned long long* temporal_counters, unsigned long long* guide_counters, TemporalReport* report) {
+    const uint32_t t = threadIdx.x;
+    if (t >= 8) return;
+    unsigned long long* const cell = t < 3 ? temporal_counters + t : (t < 5 ? guide_counters + (t - 3) : nullptr);
+    const unsigned long long v = cell ? *cell : 0ull;
+    reinterpret_cast<unsigned long long*>(report)[t] = v;
+    if (cell) *cell = 0ull;
+}
+
 } // namespace
+
+void launch_temporal_report(hipStream_t stream, unsigned long long* temporal_counters, unsigned long long* guide_counters, TemporalReport* report) {
+    hipLaunchKernelGGL(k_temporal_report, dim3(1), dim3(64), 0, stream, temporal_counters, guide_counters, report);
+}
 
 void launch_temporal(hipStream_t stream, const TemporalArgs& a) {
     if (a.win.n == 0) return;

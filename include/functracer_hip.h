@@ -536,6 +536,48 @@ typedef struct ft_temporal_filter_params { int32_t iterations, demodulate, min_h
 int32_t ft_temporal_filter(ft_context* ctx, const ft_camera* cam, int32_t spp, const double* jitter_xy, int32_t sample, uint64_t seed,
                            const ft_temporal_filter_params* params, int32_t rgba8, void* out, double* out_variance, ft_stats* stats);
 
+/* ---- queued temporal calls ------------------------------------------------------------------- */
+/* ft_temporal_enqueue queues one ft_temporal_accumulate and, with filter != NULL, the ft_temporal_filter of its result, and returns;
+ * ft_temporal_wait retires what is queued.  A host that renders with ft_render_enqueue keeps its pipeline: neither call waits on the
+ * host for the other.
+ * Meaning: a queued call produces, bit for bit, what the blocking pair
+ *     ft_temporal_accumulate(cam, spp, jitter_xy, sample, seed, params, rgba8, filter ? NULL : host_out, ..), then, with a filter,
+ *     ft_temporal_filter(cam, spp, jitter_xy, sample, seed, filter, rgba8, host_out, NULL, ..)
+ * produces on a device that has finished everything queued before it: the two history sets and cam', the pose and the snapshots that
+ * are dropped, the counts of ft_temporal_status and ft_temporal_clamp_status, the bytes in host_out.  c(x) is the FP64 frame of the last
+ * frame queued or rendered before the call, a frame of ft_render_enqueue that has not finished included: the call is ordered behind
+ * that frame on the device, and a later ft_render_enqueue* is ordered so that it does not overwrite the frame before the call has read it.
+ *  - ft_temporal_set_clamp applies to the calls queued after it.  ft_scene_commit_moved / ft_scene_commit_deformed and
+ *    "temporal_follow_deformed" work as with the blocking call; a commit retires queued temporal calls first, as it retires queued frames.
+ *  - With filter->demodulate the one guide pass of the call also delivers the material colour the filter's d is made from: there is
+ *    no second k_aov (same arguments, same bits).
+ *  - host_out (laid out as ft_temporal_accumulate's out; the tile pixels are written) should come from ft_host_alloc, one buffer per call
+ *    in flight.  A buffer is the host's again when ft_temporal_wait has returned or when call k + FT_TEMPORAL_QUEUE_DEPTH has been
+ *    queued: that call waits for call k on the host, nothing else does.  host_out may be NULL only when filter is NULL.
+ *  - Not offered: params->to_frame != 0 and filter->to_frame != 0 (FT_ERR_INVALID; the blocking calls do that) - the queued call never
+ *    writes the frame - and the filter's variance plane (a blocking ft_temporal_filter after the wait delivers it).
+ * Errors of ft_temporal_enqueue, checked before anything is queued and leaving everything as it was, in this order:
+ * ft_temporal_accumulate's argument errors; with a filter, FT_ERR_INVALID for a null host_out, then ft_temporal_filter's argument
+ * errors; FT_ERR_INVALID for params->to_frame, then for filter->to_frame; a host-only context FT_ERR_NO_DEVICE; a context over several
+ * devices FT_ERR_UNSUPPORTED; FT_ERR_STATE for no open accumulation, or no FP64 frame of the begin's size as the host knows it when the
+ * call is made.
+ * A hit list that overflows in the guide pass of a queued call cannot be repaired behind the host's back: FT_ERR_OVERFLOW is returned by
+ * whichever call retires the temporal call (ft_render_enqueue has the same rule), the lists do not grow, and the accumulation is ended as
+ * by ft_temporal_end - later queued calls have read a history written from overflowed rays.  The remedy: one blocking ft_render or
+ * ft_temporal_accumulate first, whose grown lists stay, then ft_temporal_begin again.
+ * ft_temporal_wait blocks until every queued temporal call has finished, returns the first error among them, and gives the stats of the
+ * last one: rays_primary, hits_primary, n_launches (the hand-over kernel behind the call is not counted), wall_ms from the enqueue to
+ * its retirement, kernel_ms from one event pair around the call's device work; trace_kernel_ms is 0 (the guide pass is not bracketed
+ * apart) and so is the rest.  FT_OK with nothing queued.
+ * Queued temporal calls are retired first by every call that retires queued frames first, and by ft_temporal_fetch, _status,
+ * _clamp_status, _begin and _end, the blocking ft_temporal_accumulate and ft_temporal_filter, ft_render_aov, ft_denoise, every commit,
+ * ft_scene_clear and ft_destroy.  ft_render_enqueue* and ft_render_wait do not. */
+#define FT_TEMPORAL_QUEUE_DEPTH 4
+int32_t ft_temporal_enqueue(ft_context* ctx, const ft_camera* cam, int32_t spp, const double* jitter_xy, int32_t sample, uint64_t seed,
+                            const ft_temporal_params* params, const ft_temporal_filter_params* filter /* NULL: no filter */,
+                            int32_t rgba8, void* host_out);
+int32_t ft_temporal_wait(ft_context* ctx, ft_stats* stats);
+
 /* ---- moving rigid objects under a temporal accumulation --------------------------------------- */
 /* ft_sg_set_transform + ft_scene_commit_moved move objects of a committed scene without ending ft_temporal_*: the history then follows
  * each moved leaf instead of being looked up where the leaf's surface is now.
