@@ -55,6 +55,8 @@ def hip_lib():
         lib.ft_debug_scene_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
         lib.ft_debug_devices.argtypes = [C.c_void_p, _capi.c_int32_p, C.c_int32]
         lib.ft_debug_classify_reuse.restype, lib.ft_debug_classify_reuse.argtypes = C.c_int32, [C.c_void_p, C.POINTER(C.c_int64)]
+        if hasattr(lib, "ft_debug_primary_kernels"):              # (FT_HIP_LIB may name an older build: A/B runs against the parent commit's library)
+            lib.ft_debug_primary_kernels.restype, lib.ft_debug_primary_kernels.argtypes = C.c_int32, [C.c_void_p, C.POINTER(C.c_int64)]
         lib.ft_debug_mesh_trees.restype, lib.ft_debug_mesh_trees.argtypes = C.c_int32, _capi.MESH_TREES_SIGNATURE
         lib.ft_debug_slice.argtypes = [_capi.c_double_p] * 4 + [_capi.c_int32_p, _capi.c_double_p, _capi.c_int32_p]
         lib.ft_render_enqueue.argtypes = [C.c_void_p, C.POINTER(_capi.ft_camera), C.c_int32, C.c_int32, C.c_int32, _capi.c_double_p, C.c_int32, C.c_uint64, C.POINTER(_capi.ft_rect), C.c_int32]
@@ -709,6 +711,13 @@ class Context(SceneBuilder):
         out = (C.c_int64 * 4)()
         self._check(self._lib.ft_debug_classify_reuse(self._ctx, out))
         return dict(zip(_capi.CLASSIFY_REUSE_FIELDS, (int(v) for v in out)))
+
+    def primary_kernels(self):
+        """ft_debug_primary_kernels: the bounce-0 launches since the context was created, summed over its devices - a dict of `k_primary`
+        and `k_primary_mesh` (option "primary_mesh_kernel")."""
+        out = (C.c_int64 * 2)()
+        self._check(self._lib.ft_debug_primary_kernels(self._ctx, out))
+        return {"k_primary": int(out[0]), "k_primary_mesh": int(out[1])}
 
     def scene_info(self):
         out = (C.c_int64 * 12)()

@@ -192,6 +192,7 @@ const OptionSpec kOptions[] = {
     {"csg_auto_grow", 0, 1, &Options::csg_auto_grow, nullptr, kFlag},
     {"primary_block_lists", 0, 1, &Options::primary_block_lists, nullptr, kFlag | kClassified},
     {"uniform_surface", 0, 1, &Options::uniform_surface, nullptr, kFlag},
+    {"primary_mesh_kernel", 0, 1, &Options::primary_mesh_kernel, nullptr, kFlag},   // (no classification depends on it: the slots keep theirs)
     // read by ft_scene_commit_deformed and ft_temporal_accumulate: no commit depends on it either
     {"temporal_follow_deformed", 0, 1, &Options::temporal_follow_deformed, nullptr, kFlag},
     // read by ft_scene_commit_deformed alone: no commit depends on it, so it leaves the committed scene as it is
@@ -384,6 +385,20 @@ static int32_t fit_stacks(ft_context* c, uint32_t height) {
     return lds_fits(c);
 }
 
+// The scene k_primary_mesh is written for (ft_kernels.hip): one top-level item whose program is a single OP_LEAF_FOLD of leaf 0, a lit LK_MESH
+// leaf with a BVH (`bspMesh 0`), under directional lights only; no material that needs a FANCY variant or reflects.  `variant`: the scene's.
+static bool mesh_kernel_scene(const fth::FlatScene& f, int variant) {
+    if (variant != 4 || f.item_pc.size() != 2 || f.leaves.size() != 1 || f.any_reflective) return false;
+    size_t pc = f.item_pc[0] & 0x7FFFFFFFu;
+    if (pc < f.program.size() && (f.program[pc] & 0xFFu) == ftd::OP_CULL) pc += 2;   // the item's own cull: it only ever skips a query that finds nothing
+    if (pc + 1 >= f.program.size() || f.program[pc] != (uint32_t)ftd::OP_LEAF_FOLD || (f.program[pc + 1] & 0xFFu) != ftd::OP_END) return false;   // (leaf 0: arg = 0)
+    const ftd::Leaf& L = f.leaves[0];
+    if (L.kind != ftd::LK_MESH || !(L.flags & ftd::LF_LIT) || L.mesh >= f.meshes.size() || f.meshes[L.mesh].bvh_root < 0) return false;
+    for (auto& l : f.lights) if (l.kind != ftd::LT_DIRECTIONAL) return false;
+    for (auto& m : f.materials) if (m.reflectance > 0.0) return false;
+    return true;
+}
+
 // What the launches read of the scene `flat` describes and the arrays in HBM hold: the device scene's counts and capacities, the kernel
 // variants and the resident workgroups per CU.  At the end of every upload, and again when a rebuild in place made a taller tree.
 static void derive_launch_shape(ft_context* c) {
@@ -408,6 +423,8 @@ static void derive_launch_shape(ft_context* c) {
     c->blocks_bounce = ftk::occupancy_blocks_bounce(lds, c->variant);
     c->blocks_resolve = ftk::occupancy_blocks_resolve();
     c->blocks_aov = ftk::occupancy_blocks_aov(lds, c->variant);
+    c->mesh_kernel_scene = mesh_kernel_scene(f, c->variant);
+    c->blocks_primary_mesh = ftk::occupancy_blocks_primary_mesh();
 }
 
 static int32_t upload_scene(ft_context* c) {

@@ -98,6 +98,7 @@ struct Options {
     int64_t primary_block_lists = 1;   // k_block_lists: the primaries of a classified frame over ONE bare mesh test their block's candidate list; 0: the tree walk everywhere
     int64_t refit_rebuild_percent = 0;   // ft_scene_commit_deformed rebuilds a device-built tree in place once cost now x 100 > this x cost as built; 0: never (not a commit-time option)
     int64_t temporal_follow_deformed = 0;   // ft_scene_commit_deformed keeps a mesh's records as the history saw them and ft_temporal_accumulate follows them
+    int64_t primary_mesh_kernel = 1;   // k_primary_mesh for the frames that qualify (ft_context::mesh_kernel_scene, queue_chunks); 0: k_primary everywhere (A/B)
     int64_t uniform_surface = 1;    // k_primary: one-leaf batches take leaf and material through scalar loads, dead shader work and empty-list batches are skipped; 0: per lane, everything (A/B)
 };
 
@@ -188,6 +189,8 @@ struct ft_context {
     // Kernel variants and resident workgroups per CU for the committed scene (they only change at commit): bit 0 FANCY, 1 SOFT, 2 MESH; the
     // primary's variant may carry bit 3 (the five-workgroup lean build).
     int variant = 0, variant_primary = 0, blocks_primary = 1, blocks_bounce = 1, blocks_resolve = 2, blocks_aov = 1;
+    bool mesh_kernel_scene = false; // the committed scene is what k_primary_mesh is written for (derive_launch_shape); the frame's share of the rule: queue_chunks
+    int blocks_primary_mesh = 1;
     hipEvent_t classified = nullptr;  // behind the latest k_classify on either stream: the next one waits for it (they share the ticket words of d_wave_counts)
     ftk::DevScene dev_scene{};
     // frame buffers in HBM
@@ -265,6 +268,7 @@ struct ft_context {
     std::vector<TreeQuality> tree_quality;
     int slot_turn = 0;
     int64_t reuse_counts[4] = {0, 0, 0, 0};   // since ft_create: classifications launched / reused, windows launched / skipped (ft_debug_classify_reuse)
+    int64_t primary_launches[2] = {0, 0};     // since ft_create: bounce-0 launches of k_primary / of k_primary_mesh (ft_debug_primary_kernels)
     int last_classified_slot = -1;   // the slot of the last frame queued if that frame was classified, else -1 (ft_debug_block_lists)
     // Levels of the reflection tree worth launching: the host cannot know how deep the rays of a frame go without waiting, and a
     // k_bounce launch that finds no rays still costs a few microseconds.  It launches as many levels as the previous frame of the

@@ -246,6 +246,15 @@ int32_t ft_debug_classify_reuse(ft_context* c, int64_t out[4]) {
     return FT_OK;
 }
 
+// Which kernel the bounce-0 launches of the frames queued since ft_create went to: k_primary, k_primary_mesh.
+int32_t ft_debug_primary_kernels(ft_context* c, int64_t out[2]) {
+    if (!c || !out) return FT_ERR_INVALID;
+    if (c->host_only) return FT_ERR_NO_DEVICE;
+    out[0] = out[1] = 0;
+    for (const ft_context* d : devices(c)) for (int k = 0; k < 2; ++k) out[k] += d->primary_launches[k];
+    return FT_OK;
+}
+
 int32_t ft_debug_slice(const double p0[3], const double n[3], const double tri[9], double above[18], int32_t* n_above, double below[18], int32_t* n_below) {
     if (!p0 || !n || !tri || !above || !below || !n_above || !n_below) return FT_ERR_INVALID;
     std::vector<double> a, b; std::string err;

@@ -140,6 +140,10 @@ struct Primary {
 // one colour per sample stored into acc (Colour.Zero for a miss).
 void launch_primary(const Launch& L, const DevScene& S, const Primary& gen, RayBuf next, double* acc, uint32_t acc_stride, int max_depth, FrameCounters* fc);
 int occupancy_blocks_primary(size_t lds_bytes, int* variant);   // may add bit 3 to *variant: the lean kernel built for five workgroups per CU
+// Launch::variant bit 4, for launch_primary alone: k_primary_mesh, the kernel of a scene that is one bare mesh under directional lights
+// (ft_kernels.hip; the caller has checked scene and frame, sets lds_bytes = 0 and sizes the grid by occupancy_blocks_primary_mesh).
+constexpr int kVariantMeshKernel = 16;
+int occupancy_blocks_primary_mesh();
 // One level of the reflection tree (bounce k >= 1) fused (k_bounce): closest hit, shadow queries, shaders and accumulation for every
 // ray of rays (n = fc->cc.n_rays[bounce]); the level's reflection rays are compacted into `next`, or, with `follow`, followed to their
 // end inside the launch (the last level the host launches).  A launch that finds no rays returns at once.

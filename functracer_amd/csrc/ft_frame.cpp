@@ -429,7 +429,14 @@ static int32_t queue_chunks(ft_context* c, const RenderRequest& q, const FramePl
         const int at = c->acc_turn;
         double* const acc = c->d_acc[at].as<double>();
         if (c->acc_busy[at]) { FT_HIP(c, hipStreamWaitEvent(ms, c->acc_free[at], 0)); c->acc_busy[at] = false; E.fresh = false; }   // a k_resolve on `tail` may still be reading this copy
-        E.timed(kStagePrimary, [&] { ftk::launch_primary(Lp, c->dev_scene, gen, rb[1], acc, n_samples, q.max_depth, fc); });
+        // k_primary_mesh (option "primary_mesh_kernel") for the scene it is written for, in a plain frame of whole wavefronts: grouped numbering,
+        // coherent waves, the one-leaf path on, no focus.  Anything else - progressive passes, corner sampling among it - takes k_primary.
+        const bool mesh_kernel = c->opt.primary_mesh_kernel && c->mesh_kernel_scene && c->opt.coherent_waves && c->opt.uniform_surface && !p.progressive && !p.corner &&
+                                 gen.group_log2 > 0 && !p.cam.has_focus;
+        ftk::Launch Lj = Lp;
+        if (mesh_kernel) { Lj.grid = c->n_cu * c->blocks_primary_mesh; Lj.lds_bytes = 0; Lj.variant |= ftk::kVariantMeshKernel; }
+        ++c->primary_launches[mesh_kernel ? 1 : 0];
+        E.timed(kStagePrimary, [&] { ftk::launch_primary(Lj, c->dev_scene, gen, rb[1], acc, n_samples, q.max_depth, fc); });
         auto bounce = [&](int b) { ftk::launch_bounce(Lb, c->dev_scene, gen, rb[b & 1], rb[(b + 1) & 1], acc, n_samples, b, q.max_depth, b == n_levels && n_levels < p.last_bounce, fc); };
         if (E.timing >= 2) for (int b = 1; b <= n_levels; ++b) E.timed(kStageShade, [&] { bounce(b); });
         else if (n_levels >= 1) E.timed(kStageShade, [&] { for (int b = 1; b <= n_levels; ++b) bounce(b); });

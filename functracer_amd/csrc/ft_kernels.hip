@@ -5,6 +5,7 @@
 // per chunk of samples of the active list:
 //   k_primary   bounce 0, fused: primary rays generated in registers (Image.fs:83-89, 100-110), closest hit (Scene.fs:112-118 over
 //               the flattened Scene.intersect, Scene.fs:67-104), shadow rays + Phong + reflection spawn (Shading.fs:24-139)
+//   k_primary_mesh  k_primary for a scene that is one bare mesh with a BVH under directional lights: the same steps without the rest
 //   k_bounce    one launch per level of the reflection tree (bounce k >= 1), fused the same way: the rays live in a ping-pong
 //               wavefront buffer in HBM, the ones that terminate are dropped by wave-ballot / prefix-sum compaction when the next
 //               level is spawned, so every lane of a level is live
@@ -2081,6 +2082,162 @@ __global__ __launch_bounds__(kBlock, BLOCKS) void k_primary(PrimaryArgs) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// k_primary_mesh: bounce 0 of a scene that is ONE lit bare mesh leaf with a BVH (leaf 0, the scene's only item) under directional lights,
+// no FANCY or reflective material, no focus camera, coherent waves, grouped numbering (the host checks all of it: mesh_kernel_scene in
+// ft_capi.cpp, queue_chunks).  The same batches, the same device functions and so the same values as k_primary<F,F,T> computes for such a
+// frame - what is left out is everything that frame never runs: the program loop and the item culls (with one item the mask is item 0;
+// the culls only ever skip work that finds no hit), the hit lists and LDS stacks, every other primitive, the CSG code, pow, the spawn.
+// The scene's pointers are read from the kernarg segment where a section needs them (fresh(): scalar loads that hit the scalar cache)
+// instead of living in scalar registers across the batch.  It is written against a register budget: BLOCKS workgroups per CU.
+#ifdef FT_ITEM_COUNTS
+#define FT_MESH_COUNT(kind, k, v) do { const unsigned long long v_ = (unsigned long long)(v); if (lane_id() == 0) atomicAdd(&g_clk[FT_CLK_SLOT() + 4 * (kind) + (k)], v_); } while (0)
+#else
+#define FT_MESH_COUNT(kind, k, v) do { } while (0)
+#endif
+template <int BLOCKS>
+__global__ __launch_bounds__(kBlock, BLOCKS) void k_primary_mesh(PrimaryArgs) {
+    const FT_CONST PrimaryArgs* K = kernel_args<PrimaryArgs>();
+    constexpr uint32_t kLeaf = 0u;                                  // the scene's one leaf
+    Pix px = pix_count(&K->gen);
+    // The reciprocal of the block count, read by every slot_at, into a scalar register pair for good: the compiler knows the quotient of
+    // uniform values for uniform, drops uniform_f64's readfirstlane and holds it in a vector pair across the kernel.  Behind a lane term
+    // it cannot see through (lane x an opaque zero) the readfirstlane stays.
+    {
+        const unsigned long long b = (unsigned long long)__double_as_longlong(px.inv_blocks);
+        const uint32_t veil = lane_id() * opaque_zero();
+        const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)((uint32_t)b + veil)), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)((uint32_t)(b >> 32) + veil));
+        px.inv_blocks = __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+    }
+    const uint32_t n = px.n * (uint32_t)K->gen.spp;
+    const uint32_t n_batches = (n + 63u) / 64u;                     // grouped numbering: whole wavefronts
+    unsigned long long n_shadow_wave = 0, n_hit_wave = 0;
+    BatchCursor cursor(&K->fc->cc.work_trace[0][0]);
+    uint32_t bi = cursor.grab(), bi_next = cursor.grab();
+    uint32_t pid_next = 0;
+    if (bi < n_batches && bi * 64u + lane_id() < n) pid_next = primary_pixel(&K->gen, slot_at(px, bi, lane_id()));
+    const bool use_lists = px.group_log2 != 0u && K->gen.list_heads != nullptr;
+    auto head_of = [&](const FT_CONST PrimaryArgs* Kx, uint32_t batch) -> uint32_t {
+        const uint32_t blk = (uint32_t)__builtin_amdgcn_readfirstlane((int)((Kx->gen.pix_base + slot_at(px, batch, 0u).pl) >> 6));
+        return to_const_as(Kx->gen.list_heads)[blk];
+    };
+    uint32_t head_next = kListNone;
+    if (use_lists && bi < n_batches) head_next = head_of(K, bi);
+    for (; bi < n_batches; bi = bi_next, bi_next = cursor.grab()) {
+        const uint32_t i = bi * 64u + lane_id();
+        const uint32_t pid = pid_next;
+        ListQuery lq{nullptr, head_next, kLeaf, 0.f, 0.f, 0.f, 0.f};
+        const bool active = i < n;
+        const unsigned long long clk_batch = FT_CLK_NOW();
+        // ---- the ray, offset for the geometry (Shading.fs:129, 135); an empty list ends the batch here (k_primary: `empty`)
+        Ray ro{0, 0, 0, 0, 0, 0};
+        bool empty = false;
+        {
+            const FT_CONST PrimaryArgs* Kb = fresh(K);
+            if (bi_next < n_batches && bi_next * 64u + lane_id() < n) pid_next = primary_pixel(&Kb->gen, slot_at(px, bi_next, lane_id()));
+            if (use_lists && bi_next < n_batches) head_next = head_of(Kb, bi_next);
+            empty = use_lists && lq.head != kListNone && (lq.head & 127u) == 0u;
+            double jxy[2] = {0.0, 0.0};
+            if (active && !empty) {
+                const Ray r = primary_ray_from(&Kb->gen, slot_at(px, bi, lane_id()).s, pid, jxy);
+                ro = {r.ox + 0.0001 * r.dx, r.oy + 0.0001 * r.dy, r.oz + 0.0001 * r.dz, r.dx, r.dy, r.dz};
+            }
+            if (lq.head != kListNone && !empty) {
+                const float inf = __builtin_inff();
+                const float fx = (float)jxy[0], fy = (float)jxy[1], sx = 2.4e-7f * fabsf(fx) + 1e-37f, sy = 2.4e-7f * fabsf(fy) + 1e-37f;
+                lq.x0 = wave_min(active ? fx - sx : inf); lq.x1 = wave_max(active ? fx + sx : -inf);
+                lq.y0 = wave_min(active ? fy - sy : inf); lq.y1 = wave_max(active ? fy + sy : -inf);
+                lq.pool = Kb->gen.list_pool;
+            }
+        }
+        // ---- closest hit: the block's candidate list, or the packet walk (no list for the block, or no lists in the frame)
+        Query<false> q = Query<false>::closest(active);
+        const unsigned long long clk_a = FT_CLK_NOW();
+        FT_CLK_ADD(22, clk_batch);
+        if (!empty) {
+            const Scene S = scene_view(fresh(K)->S);
+            const LeafHead H = leaf_head(S, kLeaf);
+            Ray rm;
+            to_model(S.leaves + 16ull * kLeaf, (H.flags & LF_XFORM) != 0, ro, rm);
+            FT_MESH_COUNT(0, 0, 1); FT_MESH_COUNT(0, 1, 1); FT_MESH_COUNT(0, 2, __popcll(__ballot(active))); FT_MESH_COUNT(0, 3, 1);
+            if (lq.head != kListNone) mesh_list_closest(S, lq, rm, q, kLeaf, (H.flags & LF_LIT) != 0);
+            else mesh_bvh_packet<false>(S, S.mesh_wide[H.mesh], rm, q, kLeaf, (H.flags & LF_LIT) != 0);
+            FT_CLK_ADD(1, clk_a);
+        } else FT_LIST_ADD(6, 1);
+        FT_CLK_ADD(23, clk_a);
+        const bool hit = active && q.id0 != ID_MISS;
+        const unsigned long long hit_mask = __ballot(hit);
+        double cr = 0.0, cg = 0.0, cb = 0.0;                        // a sample whose primary ray hits nothing is Colour.Zero
+        if (hit_mask) {
+            // ---- the surface: the one-leaf path of k_primary
+            Surface sf{{0, 0, 0}, {0, 1, 0}, 0, 0.0, 0.0};
+            bool lit = false;
+            const unsigned long long clk_s = FT_CLK_NOW();
+            FT_CLK_INC(27);
+            if (hit) {
+                const Scene S = scene_view(fresh(K)->S);
+                sf = surface_at<false, true>(S, ro, q.best_t, q.id0, q.id1, kLeaf);
+                lit = material_lit(S, leaf_head(S, kLeaf).material);
+            }
+            // ---- one shadow query per light (light_visibility, directional lights), straight from the leaf's pair records
+            unsigned long long vis_lo = 0ull, vis_hi = 0ull;
+            const unsigned long long clk_b = FT_CLK_NOW();
+            FT_CLK_ADD(10, clk_s);
+            {
+                const Scene S = scene_view(fresh(K)->S);
+                const int n_lights = S.n_lights;
+                for (int l = 0; l < n_lights; ++l) {
+                    cdp lp = S.lights + 12ull * (uint32_t)l;
+                    const double sox = sf.p.x + 0.0001 * sf.n.x, soy = sf.p.y + 0.0001 * sf.n.y, soz = sf.p.z + 0.0001 * sf.n.z;
+                    Query<true> qs = Query<true>::any(lit, 1.7976931348623157e308);   // System.Double.MaxValue
+                    if (__any(lit)) {
+                        const unsigned long long clk_q = FT_CLK_NOW();
+                        FT_MESH_COUNT(2, 0, 1); FT_MESH_COUNT(2, 1, 1); FT_MESH_COUNT(2, 2, __popcll(__ballot(lit))); FT_MESH_COUNT(2, 3, 1);
+                        const LeafHead H = leaf_head(S, kLeaf);     // (the leaf is lit: a lit lane took the flag from its material)
+                        const Ray sr{sox, soy, soz, -lp[0], -lp[1], -lp[2]};
+                        Ray rm;
+                        to_model(S.leaves + 16ull * kLeaf, (H.flags & LF_XFORM) != 0, sr, rm);
+                        const uint32_t pairs = reinterpret_cast<cup>(S.leaves + 16ull * kLeaf + 12)[4];   // Leaf::ls_pairs
+                        cdp P = S.ls_pairs + (unsigned long long)kLsPairDoubles * (pairs + (uint32_t)l);
+                        if (pairs != ~0u && reinterpret_cast<cip>(P + 14)[0] != INT32_MIN) {
+                            if (reinterpret_cast<cup>(P + 15)[1] != 0u) mesh_shadow_grid(S, P, rm, qs);
+                            else mesh_shadow_packet(S, P, rm, qs);
+                        } else mesh_bvh_packet<true>(S, S.mesh_wide[H.mesh], rm, qs, kLeaf, true);
+                        FT_CLK_ADD(9, clk_q);
+                    }
+                    n_shadow_wave += (unsigned long long)__popcll(__ballot(lit));
+                    const unsigned long long occluded = qs.blocked ? 1ull : 0ull;
+                    if (l < 8) vis_lo |= occluded << (8 * l); else vis_hi |= occluded << (8 * (l - 8));
+                }
+            }
+            FT_CLK_ADD(24, clk_b);
+            // ---- the shaders; the view ray is generated again, and only when a lane reads it (k_primary)
+            {
+                const Scene S = scene_view(fresh(K)->S);
+                const MaterialV mat = material_at(S, leaf_head(S, kLeaf).material);
+                const FT_CONST PrimaryArgs* K2 = fresh(K);
+                const bool reads_view = lit && mat.shineyness > 0.0;
+                Ray rv{0, 0, 0, 0, 0, 0};
+                if (__any(reads_view)) { if (hit) rv = primary_ray_from(&K2->gen, slot_at(px, bi, lane_id()).s, pid); }
+                shade_lights<false, false, true>(S, sf, mat, rv, hit, lit, vis_lo, vis_hi, cr, cg, cb, true);
+            }
+            n_hit_wave += (unsigned long long)__popcll(hit_mask);
+        }
+        if (active) {
+            const FT_CONST PrimaryArgs* Ka = fresh(K);
+            double* acc = Ka->acc; const uint32_t acc_stride = Ka->acc_stride;
+            acc[i] = 1.0 * cr; acc[(size_t)acc_stride + i] = 1.0 * cg; acc[2 * (size_t)acc_stride + i] = 1.0 * cb;
+        }
+        FT_CLK_ADD(25, clk_batch); FT_CLK_INC(26);
+    }
+    RenderCounters* mine = my_stats(fresh(K)->fc);
+    wave_add(&mine->rays_shadow, n_shadow_wave);
+    wave_add(&mine->rays_shadow_primary, n_shadow_wave);
+    wave_add(&mine->hits_total, n_hit_wave);
+    wave_add(&mine->hits_primary, n_hit_wave);
+    wave_add(&mine->ref_equiv, uniform_f64((double)fresh(K)->S.shadow_rays_per_hit * (double)n_hit_wave));
+}
+
+// ---------------------------------------------------------------------------------------------
 // k_bounce: one level of the reflection tree (bounce k >= 1) as one kernel - the same fusion as k_primary, for rays that come out
 // of the wavefront buffer instead of the camera: closest hit, shadow queries, shaders, accumulation into the sample's colour and
 // the spawn of the level's reflection rays, compacted by wave ballot + prefix sum into the other half of the ping-pong buffer, so
@@ -2944,6 +3101,13 @@ static PrimaryKernel primary_variant(int v) {                      // bit 0 FANC
     }
 }
 
+// k_primary_mesh is built for FT_MESH_BLOCKS workgroups per CU: the fastest of 4, 5 and 6 on the headline (the others are
+// a build with -DFT_MESH_BLOCKS=n away, `make resource-usage MESH_BLOCKS=n` reports their registers).
+#ifndef FT_MESH_BLOCKS
+#define FT_MESH_BLOCKS 5
+#endif
+static PrimaryKernel mesh_kernel() { return k_primary_mesh<FT_MESH_BLOCKS>; }
+
 typedef void (*BounceKernel)(BounceArgs);
 static BounceKernel bounce_variant(int v) {
     switch (v & 7) {
@@ -2963,7 +3127,7 @@ static int blocks_for(uint32_t n, int grid) { uint32_t need = (n + kBlock - 1) /
 
 void launch_primary(const Launch& L, const DevScene& S, const Primary& gen, RayBuf next, double* acc, uint32_t acc_stride, int max_depth, FrameCounters* fc) {
     const PrimaryArgs a{S, gen, next, acc, fc, acc_stride, max_depth};
-    hipLaunchKernelGGL(primary_variant(L.variant), dim3(L.grid), dim3(kBlock), L.lds_bytes, L.stream, a);
+    hipLaunchKernelGGL((L.variant & kVariantMeshKernel) ? mesh_kernel() : primary_variant(L.variant), dim3(L.grid), dim3(kBlock), L.lds_bytes, L.stream, a);
 }
 void launch_classify(const Launch& L, const DevScene& S, const Primary& gen_list, const ClassifyOut& out, double jitter_extent, uint32_t epoch, FrameCounters* fc,
                      const uint32_t* retired, bool mask_only) {
@@ -3034,6 +3198,11 @@ int occupancy_blocks_primary(size_t lds_bytes, int* variant) {
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, primary_variant(8), kBlock, lds_bytes) == hipSuccess && n >= kLeanBlocks) { *variant |= 8; return clamp_blocks(n); }
     }
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, primary_variant(*variant), kBlock, lds_bytes) != hipSuccess) n = 1;
+    return clamp_blocks(n);
+}
+int occupancy_blocks_primary_mesh() {                                // (no LDS: registers alone decide)
+    int n = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, mesh_kernel(), kBlock, 0) != hipSuccess) n = 1;
     return clamp_blocks(n);
 }
 int occupancy_blocks_resolve() {

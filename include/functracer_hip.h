@@ -164,6 +164,11 @@ const char* ft_last_error(const ft_context* ctx);
  * loads, instead of once per lane (scenes with meshes and without textures, rough materials or soft lights: the kernel the headline runs); the shaders leave out what no lane of the wavefront reads (the specular term's three normalisations, the regenerated view ray);
  * and, with "primary_block_lists", a wavefront whose block has an empty candidate list stores Colour.Zero without generating its rays when the mesh is the scene's
  * only item and the camera has no focus.  0: everything per lane, nothing left out.  Same expressions either way: same frames and counters bit for bit),
+ * "primary_mesh_kernel" (1 = default: bounce 0 of a scene that is one lit top-level `bspMesh 0` leaf and nothing else, under directional lights only, with no
+ * rough, textured or reflective material and no specular exponent that needs Math.Pow, runs k_primary_mesh - the same steps and expressions as k_primary's for such
+ * a scene, without the code such a scene never reaches, in fewer registers and with more waves in flight - when the camera has no focus and the frame is a plain
+ * (not progressive, not corner-sampled) one in grouped numbering with "coherent_waves" and "uniform_surface" on; 0: k_primary everywhere.  Same frames and
+ * ft_stats (times aside) bit for bit; no re-commit, and what the frame slots keep of their classifications stays),
  * "classify_reuse" (1 = default: a classified frame whose scene commit, frame size, tiles, camera, jitter extent (not the offsets) and candidate-list leaf equal, field
  * for field, those of the frame that last classified into the same one of the four frame slots launches neither k_classify nor k_block_lists: it reads that frame's
  * block maps, lists and active count as they are, and launches only the windows of its pixel list that hold active pixels - a held view, whatever its pattern, seed, samples
@@ -765,6 +770,9 @@ int32_t ft_debug_block_lists(ft_context* ctx, int64_t sizes[4], double plane[4],
 /* "classify_reuse" at work, for tests: counts since ft_create, summed over the context's devices - classifications launched, classifications reused, windows
  * launched, windows not launched because the kept active list ends before them.  FT_ERR_NO_DEVICE on a host-only context. */
 int32_t ft_debug_classify_reuse(ft_context* ctx, int64_t out[4]);
+/* "primary_mesh_kernel" at work, for tests: bounce-0 launches since ft_create, summed over the context's devices - out[0] of k_primary, out[1] of
+ * k_primary_mesh.  FT_ERR_NO_DEVICE on a host-only context. */
+int32_t ft_debug_primary_kernels(ft_context* ctx, int64_t out[2]);
 /* HIP-event time per stage over the last ft_render: index 4 primary (bounce 0 fused: generate + closest + shade), 2 the later
  * bounces (one k_bounce per level; one bracket around them all, or with "timing" = 2 one per level), 3 resolve and 0 the rest (the
  * fill, classification) with "timing" = 2; otherwise 0 = everything that is not bracketed and 3 = 0.  Index 1 is unused. */

@@ -60,6 +60,9 @@ def main():
         out[k] = {"launches": len(f), "fetch_raw_bytes_per_launch": sum(f) / max(1, len(f)), "fetch_corrected_bytes_per_launch": read_scale * sum(f) / max(1, len(f)),
                   "write_bytes_per_launch": sum(w) / max(1, len(w))}
         out[k]["traffic_bytes_per_launch"] = out[k]["fetch_corrected_bytes_per_launch"] + out[k]["write_bytes_per_launch"]
+    # bench.py reads the bounce-0 kernel of the headline under "k_primary": where every bounce-0 launch went to k_primary_mesh, that is the kernel
+    if "k_primary_mesh" in out and "k_primary" not in out:
+        out["k_primary"] = dict(out["k_primary_mesh"], kernel="k_primary_mesh")
     print(json.dumps(out, indent=1))
 
 

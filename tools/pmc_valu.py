@@ -56,6 +56,9 @@ def main():
             "fp64_arith_share_of_valu": round((f64 + fma) / max(1.0, valu), 4),
             "fp64_tflops_upper": round((f64 + 2.0 * fma) * 64.0 / seconds / 1e12, 3),
         }
+    # bench.py reads the bounce-0 kernel of the headline under "k_primary": where every bounce-0 launch went to k_primary_mesh, that is the kernel
+    if "k_primary_mesh" in out and "k_primary" not in out:
+        out["k_primary"] = dict(out["k_primary_mesh"], kernel="k_primary_mesh")
     print(json.dumps(out, indent=1))
 
 
