@@ -23,6 +23,19 @@
 //   * coherent wavefronts (one 8x8 pixel block) walk mesh trees as a packet with a wave-uniform stack, and bound their
 //     rays by a cone that is tested against the bounding spheres of all top-level items at once (one lane per item);
 //   * launch arguments are read from the kernarg segment where they are used (scalar loads), not held in SGPRs.
+//
+// Translation units.  The library is linked from three units that compile side by side: ft_k_<unit>.hip sets FT_UNIT and includes this
+// file.  The device functions and kernel templates are every unit's; what a unit instantiates, the plain kernels and the launchers are its
+// own.  The MESH kernels and the frame's kernels share a unit because a device function is internal to its unit: where all calls in a
+// unit pass it the same constant (`coherent` of trace, `jxy` of primary_ray_from) the compiler propagates it before inlining, and only
+// beside k_primary<*, *, true, *> do k_bounce<*, *, true>, k_aov and k_debug_blocked come out the machine code they are in one unit
+// (tools/kernel_isa_equal.py).  Compiled as it stands this file is all three - the diagnostic builds need that: g_clk is one array.
+#define FT_UNIT_MESH_FRAME 1     // the MESH = true kernels, k_primary_mesh; k_classify, k_block_lists, k_report, k_resolve*, k_aov, k_debug_*
+#define FT_UNIT_PRIMARY 2        // k_primary<*, *, false, *>; launch_primary and the occupancy functions of all k_primary
+#define FT_UNIT_BOUNCE 4         // k_bounce<*, *, false>; launch_bounce and the occupancy function of all k_bounce
+#ifndef FT_UNIT
+#define FT_UNIT 7
+#endif
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -160,6 +173,42 @@ FT_DEV double uniform_f64(double v) {
     return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
 }
 FT_DEV uint32_t lanes_below(unsigned long long mask) { return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u)); }
+
+// The macros of the two diagnostic builds; the shipped build compiles every one of them to nothing.
+// -DFT_ITEM_COUNTS (make item-counts, tools/item_counts.py): every wave adds to kClkWords words of its own in g_clk (no-return atomics on
+// addresses nobody shares: shared words made the build eight times slower); ft_debug_item_counts sums them over the waves.  The layout,
+// which the readers know by number:
+//   [4 * kind + k]       FT_COUNT, FT_MESH_COUNT: top-level items a wave's query evaluates; kind = ANY * 2 + incoherent (FT_COUNT: of its
+//                        surroundings); k = 0 queries, 1 items evaluated, 2 live lanes, 3 items the mask offered (before each item's own OP_CULL)
+//   [kClkSection + k]    FT_CLK_ADD, FT_CLK_INC: shader-clock cycles (s_memtime) waves spend in section k of the tracing kernels, or a count
+//                        FT_LIST_ADD: the list path of the closest queries, in unused halves of the closest kinds' clock pairs: k = 2 entries
+//                        offered, 3 entries past the rectangle test (every one of them is a triangle tested), 6 empty lists, 7 queries
+//   [kClkWalk + k]       FT_WALK_ADD: the any-hit mesh walks of coherent waves: nodes visited, triangles tested, cycles spent in leaves, walks
+// -DFT_STAMPS: s_memrealtime (100 MHz) at the phases of every workgroup of k_classify, into the words behind wave_counts[4096].
+constexpr uint32_t kClkWaves = 8192, kClkWords = 48, kClkSection = 16, kClkWalk = kClkSection + 28;
+#ifdef FT_ITEM_COUNTS
+__device__ unsigned long long g_clk[kClkWaves * kClkWords];
+#define FT_CLK_SLOT() (((blockIdx.x * (kBlock / 64) + threadIdx.x / 64) & (kClkWaves - 1u)) * kClkWords)
+#define FT_LANE0_ADD(base, k, v) if (lane_id() == 0) atomicAdd(&g_clk[FT_CLK_SLOT() + (base) + (k)], (v))   // (inside the two below only)
+#define FT_SLOT_ADD(base, k, v) do { const unsigned long long v_ = (unsigned long long)(v); FT_LANE0_ADD(base, k, v_); } while (0)   // v: the whole wave's (ballots)
+#define FT_CLK_NOW() __builtin_amdgcn_s_memtime()
+#define FT_CLK_ADD(k, t0) do { const unsigned long long t1_ = FT_CLK_NOW(); FT_LANE0_ADD(kClkSection, k, t1_ - (t0)); } while (0)
+#else
+#define FT_SLOT_ADD(base, k, v) do { (void)sizeof((base) + (k) + (v)); } while (0)   // (names what its arguments name, evaluates nothing)
+#define FT_CLK_NOW() 0ull
+#define FT_CLK_ADD(k, t0) FT_SLOT_ADD(kClkSection, k, t0)
+#endif
+#define FT_COUNT(k, v) FT_SLOT_ADD(4 * ((ANY ? 2 : 0) + (coherent ? 0 : 1)), k, v)
+#define FT_MESH_COUNT(kind, k, v) FT_SLOT_ADD(4 * (kind), k, v)
+#define FT_CLK_INC(k) FT_SLOT_ADD(kClkSection, k, 1ull)
+#define FT_LIST_ADD(k, v) FT_SLOT_ADD(kClkSection, k, v)
+#define FT_WALK_ADD(k, v) FT_SLOT_ADD(kClkWalk, k, v)
+#define FT_WALK_NOW() FT_CLK_NOW()
+#ifdef FT_STAMPS
+#define FT_STAMP(k) do { if (threadIdx.x == 0) reinterpret_cast<unsigned long long*>(K->out.wave_counts + 4096)[blockIdx.x * 8 + (k)] = __builtin_amdgcn_s_memrealtime(); } while (0)
+#else
+#define FT_STAMP(k) do { } while (0)
+#endif
 
 // ---------------------------------------------------------------------------------------------
 // Per-lane hit list in LDS (only used under CSG nodes).  Entry e, word w of this lane lives at
@@ -739,18 +788,6 @@ FT_DEV bool mesh_bsp_packet(const Scene& S, int32_t root, int32_t wide_root, con
     return true;
 }
 
-#ifdef FT_ITEM_COUNTS
-// Diagnostic build only (tools/item_counts.py): the any-hit mesh walks of coherent waves, slots 16 + 28 .. 31 of the wave's words:
-// nodes visited, triangles tested, cycles spent in leaves, walks.
-__device__ unsigned long long g_clk[8192 * 48];
-#define FT_CLK_SLOT() (((blockIdx.x * (kBlock / 64) + threadIdx.x / 64) & 8191u) * 48u)
-#define FT_WALK_ADD(k, v) do { const unsigned long long v_ = (unsigned long long)(v); if (lane_id() == 0) atomicAdd(&g_clk[FT_CLK_SLOT() + 16 + 28 + (k)], v_); } while (0)
-#define FT_WALK_NOW() __builtin_amdgcn_s_memtime()
-#else
-#define FT_WALK_ADD(k, v) do { (void)(v); } while (0)
-#define FT_WALK_NOW() 0ull
-#endif
-
 // The same query for a COHERENT wavefront (primary rays of one 8x8 pixel block and their shadow rays):
 // the 64 rays walk the BVH together.  The node stack and the current node are wave-uniform (the stack lives
 // in the lanes of one VGPR: lane i holds entry i, popped with v_readlane), node and triangle data come through scalar loads,
@@ -1001,14 +1038,6 @@ FT_DEV void mesh_shadow_grid(const Scene& S, cdp P, const Ray& r, Query<true>& q
         }
     }
 }
-
-#ifdef FT_ITEM_COUNTS
-// Diagnostic build only: the list path of the closest queries, slots 16 + 2, 3, 7 of the wave's words (unused halves of the closest
-// kinds' clock pairs): entries offered, entries past the rectangle test (every one of them is a triangle tested), queries.
-#define FT_LIST_ADD(k, v) do { const unsigned long long v_ = (unsigned long long)(v); if (lane_id() == 0) atomicAdd(&g_clk[FT_CLK_SLOT() + 16 + (k)], v_); } while (0)
-#else
-#define FT_LIST_ADD(k, v) do { (void)(v); } while (0)
-#endif
 
 // The closest query of a COHERENT wave of primaries against a bare mesh through its block's candidate list (k_block_lists; ft_device.h)
 // instead of the tree: the header came through a scalar load a batch ahead, lane e fetches entry e (all addresses known at once, as in
@@ -1289,24 +1318,6 @@ FT_DEV ItemMask exact_cull(const Scene& S, const Ray& r, bool live) {
     return M;
 }
 
-#ifdef FT_ITEM_COUNTS
-// Diagnostic build only: shader-clock cycles waves spend in sections of the tracing kernels (s_memtime; summed over waves).
-// Every wave adds to 48 words of its own (no-return atomics on addresses nobody shares: shared words made the build eight times slower).
-#define FT_CLK_NOW() __builtin_amdgcn_s_memtime()
-#define FT_CLK_ADD(k, t0) do { const unsigned long long t1_ = __builtin_amdgcn_s_memtime(); if (lane_id() == 0) atomicAdd(&g_clk[FT_CLK_SLOT() + 16 + (k)], t1_ - (t0)); } while (0)
-#define FT_CLK_INC(k) do { if (lane_id() == 0) atomicAdd(&g_clk[FT_CLK_SLOT() + 16 + (k)], 1ull); } while (0)
-#else
-#define FT_CLK_NOW() 0ull
-#define FT_CLK_ADD(k, t0) do { (void)(t0); } while (0)
-#define FT_CLK_INC(k) do { } while (0)
-#endif
-#ifdef FT_ITEM_COUNTS
-// Diagnostic build only (tools/item_counts.py): how many top-level items a wave's query evaluates.  [4 * kind + k], kind = ANY * 2 + incoherent:
-// k = 0 queries, 1 items evaluated, 2 live lanes, 3 items the mask offered (before each item's own OP_CULL).
-#define FT_COUNT(k, v) do { const unsigned long long v_ = (unsigned long long)(v); if (lane_id() == 0) atomicAdd(&g_clk[FT_CLK_SLOT() + 4 * ((ANY ? 2 : 0) + (coherent ? 0 : 1)) + (k)], v_); } while (0)
-#else
-#define FT_COUNT(k, v) do { } while (0)
-#endif
 // ---------------------------------------------------------------------------------------------
 // The scene program interpreter: Scene.intersect (Scene.fs:67-104) + closest / lightIsBocked.
 // MESH = false compiles the triangle / BSP / BVH code out: scenes without meshes then run kernels with
@@ -1919,6 +1930,23 @@ struct PrimaryArgs {
 // or worse), and only where the scene's LDS lets five workgroups live on a CU: hollow-sphere's hit lists allow four, and the
 // five-workgroup build - fewer registers, more scratch - costs it 3 %.  So the lean variant exists twice and the host picks.
 constexpr int kPrimaryBlocks = 4, kLeanBlocks = 5;
+// What k_primary and k_primary_mesh share word for word.  The head of the candidate list of the block a grouped batch is part of:
+FT_DEV uint32_t list_head_of(const FT_CONST PrimaryArgs* Kx, const Pix& px, uint32_t batch) {
+    const uint32_t blk = (uint32_t)__builtin_amdgcn_readfirstlane((int)((Kx->gen.pix_base + slot_at(px, batch, 0u).pl) >> 6));
+    return to_const_as(Kx->gen.list_heads)[blk];
+}
+// slightOffset (Shading.fs:129) of primary ray r, and (wave-uniform) the wave's rectangle on the image plane, rounded outward to float
+FT_DEV Ray offset_ray(const Ray& r) { return {r.ox + 0.0001 * r.dx, r.oy + 0.0001 * r.dy, r.oz + 0.0001 * r.dz, r.dx, r.dy, r.dz}; }
+FT_DEV void wave_rect(ListQuery& lq, const double (&jxy)[2], bool active) {
+    const float inf = __builtin_inff();
+    const float fx = (float)jxy[0], fy = (float)jxy[1], sx = 2.4e-7f * fabsf(fx) + 1e-37f, sy = 2.4e-7f * fabsf(fy) + 1e-37f;
+    lq.x0 = wave_min(active ? fx - sx : inf); lq.x1 = wave_max(active ? fx + sx : -inf);
+    lq.y0 = wave_min(active ? fy - sy : inf); lq.y1 = wave_max(active ? fy + sy : -inf);
+}
+FT_DEV void store_first(const FT_CONST PrimaryArgs* Ka, uint32_t i, double cr, double cg, double cb) {   // the sample's first contribution: a plain store (path weight 1)
+    double* acc = Ka->acc; const uint32_t acc_stride = Ka->acc_stride;
+    acc[i] = 1.0 * cr; acc[(size_t)acc_stride + i] = 1.0 * cg; acc[2 * (size_t)acc_stride + i] = 1.0 * cb;
+}
 template <bool FANCY, bool SOFT, bool MESH, int BLOCKS>
 __global__ __launch_bounds__(kBlock, BLOCKS) void k_primary(PrimaryArgs) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
@@ -1945,12 +1973,8 @@ __global__ __launch_bounds__(kBlock, BLOCKS) void k_primary(PrimaryArgs) {
     // The block's candidate list (k_block_lists) in place of the mesh's tree: grouped numbering only (a batch is then part of ONE block of
     // the frame's active list, block (pix_base + pl) / 64), coherent waves only.  The header is requested a batch ahead, like the pixel id.
     const bool use_lists = MESH && coherent && px.group_log2 != 0u && K->gen.list_heads != nullptr;
-    auto head_of = [&](const FT_CONST PrimaryArgs* Kx, uint32_t batch) -> uint32_t {
-        const uint32_t blk = (uint32_t)__builtin_amdgcn_readfirstlane((int)((Kx->gen.pix_base + slot_at(px, batch, 0u).pl) >> 6));
-        return to_const_as(Kx->gen.list_heads)[blk];
-    };
     uint32_t head_next = kListNone;
-    if (use_lists && bi < n_batches) head_next = head_of(K, bi);
+    if (use_lists && bi < n_batches) head_next = list_head_of(K, px, bi);
     for (; bi < n_batches; bi = bi_next, bi_next = cursor.grab()) {
         const uint32_t i = bi * B + lane_id();
         const uint32_t pid = pid_next;
@@ -1963,22 +1987,16 @@ __global__ __launch_bounds__(kBlock, BLOCKS) void k_primary(PrimaryArgs) {
         {
             const FT_CONST PrimaryArgs* Kb = fresh(K);              // camera, pixel list: loaded here, dead before the trace
             if (bi_next < n_batches && bi_next * B + lane_id() < n && lane_id() < B) pid_next = primary_pixel(&Kb->gen, at_of(bi_next));
-            if (use_lists && bi_next < n_batches) head_next = head_of(Kb, bi_next);
+            if (use_lists && bi_next < n_batches) head_next = list_head_of(Kb, px, bi_next);
             // A list with no entry under a mesh that is the scene's only item: no ray of the batch can hit anything, whatever its jitter (the
             // list covers the block's rectangle under every offset; frames of a focus camera are never classified and carry no lists, the test on
             // has_focus only says so here).  No ray is generated
             // and none traced: the query stays a miss, the batch stores Colour.Zero below and adds nothing to any counter, as its trace would have.
             empty = use_lists && lq.head != kListNone && (lq.head & 127u) == 0u && Kb->S.uniform_surface != 0 && Kb->S.n_items == 1 && Kb->gen.cam.has_focus == 0;
             double jxy[2] = {0.0, 0.0};
-            if (active && !empty) {
-                const Ray r = primary_ray_from(&Kb->gen, at_of(bi).s, pid, jxy);
-                ro = {r.ox + 0.0001 * r.dx, r.oy + 0.0001 * r.dy, r.oz + 0.0001 * r.dz, r.dx, r.dy, r.dz};   // slightOffset (Shading.fs:129)
-            }
-            if (MESH && lq.head != kListNone && !empty) {            // (wave-uniform) the wave's rectangle on the image plane, rounded outward to float
-                const float inf = __builtin_inff();
-                const float fx = (float)jxy[0], fy = (float)jxy[1], sx = 2.4e-7f * fabsf(fx) + 1e-37f, sy = 2.4e-7f * fabsf(fy) + 1e-37f;
-                lq.x0 = wave_min(active ? fx - sx : inf); lq.x1 = wave_max(active ? fx + sx : -inf);
-                lq.y0 = wave_min(active ? fy - sy : inf); lq.y1 = wave_max(active ? fy + sy : -inf);
+            if (active && !empty) ro = offset_ray(primary_ray_from(&Kb->gen, at_of(bi).s, pid, jxy));
+            if (MESH && lq.head != kListNone && !empty) {
+                wave_rect(lq, jxy, active);
                 lq.pool = Kb->gen.list_pool; lq.leaf = (uint32_t)Kb->gen.list_leaf;
             }
         }
@@ -2062,11 +2080,7 @@ __global__ __launch_bounds__(kBlock, BLOCKS) void k_primary(PrimaryArgs) {
             n_refl_wave += cnt;
             n_hit_wave += (unsigned long long)__popcll(hit_mask);
         }
-        if (active) {                                               // the sample's first contribution: a plain store (path weight 1)
-            const FT_CONST PrimaryArgs* Ka = fresh(K);
-            double* acc = Ka->acc; const uint32_t acc_stride = Ka->acc_stride;
-            acc[i] = 1.0 * cr; acc[(size_t)acc_stride + i] = 1.0 * cg; acc[2 * (size_t)acc_stride + i] = 1.0 * cb;
-        }
+        if (active) store_first(fresh(K), i, cr, cg, cb);
         FT_CLK_ADD(25, clk_batch); FT_CLK_INC(26);
     }
     RenderCounters* mine = my_stats(fresh(K)->fc);
@@ -2089,11 +2103,6 @@ __global__ __launch_bounds__(kBlock, BLOCKS) void k_primary(PrimaryArgs) {
 // the culls only ever skip work that finds no hit), the hit lists and LDS stacks, every other primitive, the CSG code, pow, the spawn.
 // The scene's pointers are read from the kernarg segment where a section needs them (fresh(): scalar loads that hit the scalar cache)
 // instead of living in scalar registers across the batch.  It is written against a register budget: BLOCKS workgroups per CU.
-#ifdef FT_ITEM_COUNTS
-#define FT_MESH_COUNT(kind, k, v) do { const unsigned long long v_ = (unsigned long long)(v); if (lane_id() == 0) atomicAdd(&g_clk[FT_CLK_SLOT() + 4 * (kind) + (k)], v_); } while (0)
-#else
-#define FT_MESH_COUNT(kind, k, v) do { } while (0)
-#endif
 template <int BLOCKS>
 __global__ __launch_bounds__(kBlock, BLOCKS) void k_primary_mesh(PrimaryArgs) {
     const FT_CONST PrimaryArgs* K = kernel_args<PrimaryArgs>();
@@ -2116,12 +2125,8 @@ __global__ __launch_bounds__(kBlock, BLOCKS) void k_primary_mesh(PrimaryArgs) {
     uint32_t pid_next = 0;
     if (bi < n_batches && bi * 64u + lane_id() < n) pid_next = primary_pixel(&K->gen, slot_at(px, bi, lane_id()));
     const bool use_lists = px.group_log2 != 0u && K->gen.list_heads != nullptr;
-    auto head_of = [&](const FT_CONST PrimaryArgs* Kx, uint32_t batch) -> uint32_t {
-        const uint32_t blk = (uint32_t)__builtin_amdgcn_readfirstlane((int)((Kx->gen.pix_base + slot_at(px, batch, 0u).pl) >> 6));
-        return to_const_as(Kx->gen.list_heads)[blk];
-    };
     uint32_t head_next = kListNone;
-    if (use_lists && bi < n_batches) head_next = head_of(K, bi);
+    if (use_lists && bi < n_batches) head_next = list_head_of(K, px, bi);
     for (; bi < n_batches; bi = bi_next, bi_next = cursor.grab()) {
         const uint32_t i = bi * 64u + lane_id();
         const uint32_t pid = pid_next;
@@ -2134,18 +2139,12 @@ __global__ __launch_bounds__(kBlock, BLOCKS) void k_primary_mesh(PrimaryArgs) {
         {
             const FT_CONST PrimaryArgs* Kb = fresh(K);
             if (bi_next < n_batches && bi_next * 64u + lane_id() < n) pid_next = primary_pixel(&Kb->gen, slot_at(px, bi_next, lane_id()));
-            if (use_lists && bi_next < n_batches) head_next = head_of(Kb, bi_next);
+            if (use_lists && bi_next < n_batches) head_next = list_head_of(Kb, px, bi_next);
             empty = use_lists && lq.head != kListNone && (lq.head & 127u) == 0u;
             double jxy[2] = {0.0, 0.0};
-            if (active && !empty) {
-                const Ray r = primary_ray_from(&Kb->gen, slot_at(px, bi, lane_id()).s, pid, jxy);
-                ro = {r.ox + 0.0001 * r.dx, r.oy + 0.0001 * r.dy, r.oz + 0.0001 * r.dz, r.dx, r.dy, r.dz};
-            }
+            if (active && !empty) ro = offset_ray(primary_ray_from(&Kb->gen, slot_at(px, bi, lane_id()).s, pid, jxy));
             if (lq.head != kListNone && !empty) {
-                const float inf = __builtin_inff();
-                const float fx = (float)jxy[0], fy = (float)jxy[1], sx = 2.4e-7f * fabsf(fx) + 1e-37f, sy = 2.4e-7f * fabsf(fy) + 1e-37f;
-                lq.x0 = wave_min(active ? fx - sx : inf); lq.x1 = wave_max(active ? fx + sx : -inf);
-                lq.y0 = wave_min(active ? fy - sy : inf); lq.y1 = wave_max(active ? fy + sy : -inf);
+                wave_rect(lq, jxy, active);
                 lq.pool = Kb->gen.list_pool;
             }
         }
@@ -2222,11 +2221,7 @@ __global__ __launch_bounds__(kBlock, BLOCKS) void k_primary_mesh(PrimaryArgs) {
             }
             n_hit_wave += (unsigned long long)__popcll(hit_mask);
         }
-        if (active) {
-            const FT_CONST PrimaryArgs* Ka = fresh(K);
-            double* acc = Ka->acc; const uint32_t acc_stride = Ka->acc_stride;
-            acc[i] = 1.0 * cr; acc[(size_t)acc_stride + i] = 1.0 * cg; acc[2 * (size_t)acc_stride + i] = 1.0 * cb;
-        }
+        if (active) store_first(fresh(K), i, cr, cg, cb);
         FT_CLK_ADD(25, clk_batch); FT_CLK_INC(26);
     }
     RenderCounters* mine = my_stats(fresh(K)->fc);
@@ -2367,6 +2362,7 @@ __global__ __launch_bounds__(kBlock, FANCY ? 2 : 4) void k_bounce(BounceArgs) {
 }
 
 // ---------------------------------------------------------------------------------------------
+#if FT_UNIT & FT_UNIT_MESH_FRAME                                    // (from here to the end of the device code)
 // k_classify: which 64-pixel blocks of the frame can see anything at all, and the list of those that can.  One LANE per block (an
 // 8x8 tile of the pixel list), one workgroup per 256 consecutive blocks.  The rays of a block - ALL samples of its pixels: the caller's
 // jitter offsets lie within +-extent pixels (the reference's in the unit disc, Jitter.fs:15-21) - have directions k + jx i + jy j
@@ -2444,12 +2440,6 @@ __global__ __launch_bounds__(kClassifyBlock) void k_classify(ClassifyArgs) {
     const Scene S = scene_view(K->S);
     const PrimaryArg g = &K->gen;
     const uint32_t n_blocks = g->n_pix / 64u;
-#ifdef FT_STAMPS
-    // diagnostic build only: s_memrealtime (100 MHz) at the phases of every workgroup, into the words behind wave_counts[4096]
-#define FT_STAMP(k) do { if (threadIdx.x == 0) reinterpret_cast<unsigned long long*>(K->out.wave_counts + 4096)[blockIdx.x * 8 + (k)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define FT_STAMP(k) do { } while (0)
-#endif
     FT_STAMP(0);
     if (threadIdx.x == 0) sh_ticket = atomicAdd(&K->fc->classify_ticket, 1u);
     __syncthreads();
@@ -3073,9 +3063,79 @@ __global__ __launch_bounds__(kBlock, FANCY ? 2 : 4) void k_aov(AovArgs) {
     wave_add(&ctr[0], n_hit_wave);
     wave_add(&ctr[1], n_ovf_wave);
 }
+#endif
 
+// The variants of k_primary and k_bounce by the bits of Launch::variant: bit 0 FANCY, bit 1 SOFT, bit 2 MESH, bit 3 (k_primary only): the
+// lean variant (none of the three) built for five workgroups per CU.  A unit instantiates the kernels of one value of bit 2.
+typedef void (*PrimaryKernel)(PrimaryArgs);
+template <bool MESH>
+PrimaryKernel primary_family(int v) {
+    switch (v & 11) {
+        case 0: return k_primary<false, false, MESH, kPrimaryBlocks>;
+        case 8: return k_primary<false, false, MESH, MESH ? kPrimaryBlocks : kLeanBlocks>;
+        case 1: case 9: return k_primary<true, false, MESH, 2>;
+        case 2: case 10: return k_primary<false, true, MESH, kPrimaryBlocks>;
+        default: return k_primary<true, true, MESH, 2>;
+    }
+}
+typedef void (*BounceKernel)(BounceArgs);
+template <bool MESH>
+BounceKernel bounce_family(int v) {
+    switch (v & 3) {
+        case 0: return k_bounce<false, false, MESH>;
+        case 1: return k_bounce<true, false, MESH>;
+        case 2: return k_bounce<false, true, MESH>;
+        default: return k_bounce<true, true, MESH>;
+    }
+}
 } // namespace
 
+// The MESH kernels reach the launchers' units as untyped host pointers: the argument structures are types of each unit's own.
+__attribute__((visibility("hidden"))) const void* primary_mesh_kernels(int v);   // v = kVariantMeshKernel: k_primary_mesh
+__attribute__((visibility("hidden"))) const void* bounce_mesh_kernels(int v);
+static inline int clamp_blocks(int n) { return n < 1 ? 1 : (n > 8 ? 8 : n); }
+template <class Kernel> static int occupancy_blocks(Kernel kernel, size_t lds_bytes) {   // resident workgroups per CU of a persistent grid (register- and LDS-limited)
+    int n = 0;
+    return clamp_blocks(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, kBlock, lds_bytes) == hipSuccess ? n : 1);
+}
+
+// ============================================================================================ launchers
+#if FT_UNIT & FT_UNIT_PRIMARY
+static PrimaryKernel from_mesh_unit(int v) { return reinterpret_cast<PrimaryKernel>(const_cast<void*>(primary_mesh_kernels(v))); }
+static PrimaryKernel primary_variant(int v) { return (v & 4) ? from_mesh_unit(v & 15) : primary_family<false>(v); }
+static PrimaryKernel mesh_kernel() { return from_mesh_unit(kVariantMeshKernel); }
+void launch_primary(const Launch& L, const DevScene& S, const Primary& gen, RayBuf next, double* acc, uint32_t acc_stride, int max_depth, FrameCounters* fc) {
+    const PrimaryArgs a{S, gen, next, acc, fc, acc_stride, max_depth};
+    hipLaunchKernelGGL((L.variant & kVariantMeshKernel) ? mesh_kernel() : primary_variant(L.variant), dim3(L.grid), dim3(kBlock), L.lds_bytes, L.stream, a);
+}
+// Resident workgroups per CU of k_primary for this scene; *variant gains bit 3 when the five-workgroup build of the lean variant fits.
+int occupancy_blocks_primary(size_t lds_bytes, int* variant) {
+    int n = 0;
+    if ((*variant & 7) == 0) {
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, primary_variant(8), kBlock, lds_bytes) == hipSuccess && n >= kLeanBlocks) { *variant |= 8; return clamp_blocks(n); }
+    }
+    return occupancy_blocks(primary_variant(*variant), lds_bytes);
+}
+int occupancy_blocks_primary_mesh() { return occupancy_blocks(mesh_kernel(), 0); }   // (no LDS: registers alone decide)
+#endif
+#if FT_UNIT & FT_UNIT_BOUNCE
+static BounceKernel bounce_variant(int v) { return (v & 4) ? reinterpret_cast<BounceKernel>(const_cast<void*>(bounce_mesh_kernels(v))) : bounce_family<false>(v); }
+void launch_bounce(const Launch& L, const DevScene& S, const Primary& gen, RayBuf rays, RayBuf next, double* acc, uint32_t acc_stride, int bounce, int max_depth, bool follow, FrameCounters* fc) {
+    const BounceArgs a{S, gen, rays, next, acc, fc, acc_stride, bounce, max_depth, follow ? 1 : 0};
+    hipLaunchKernelGGL(bounce_variant(L.variant), dim3(L.grid), dim3(kBlock), L.lds_bytes, L.stream, a);
+}
+int occupancy_blocks_bounce(size_t lds_bytes, int variant) { return occupancy_blocks(bounce_variant(variant), lds_bytes); }
+#endif
+#if FT_UNIT & FT_UNIT_MESH_FRAME
+// k_primary_mesh is built for FT_MESH_BLOCKS workgroups per CU: the fastest of 4, 5 and 6 on the headline (DESIGN.md 5; the others are
+// a build with -DFT_MESH_BLOCKS=n away, `make resource-usage MESH_BLOCKS=n` reports their registers).
+#ifndef FT_MESH_BLOCKS
+#define FT_MESH_BLOCKS 5
+#endif
+const void* primary_mesh_kernels(int v) {
+    return (v & kVariantMeshKernel) ? reinterpret_cast<const void*>(&k_primary_mesh<FT_MESH_BLOCKS>) : reinterpret_cast<const void*>(primary_family<true>(v));
+}
+const void* bounce_mesh_kernels(int v) { return reinterpret_cast<const void*>(bounce_family<true>(v)); }
 typedef void (*AovKernel)(AovArgs);
 static AovKernel aov_variant(int v) {                              // bit 0 FANCY, bit 2 MESH (Launch::variant); soft lights play no part
     switch (v & 5) {
@@ -3085,50 +3145,8 @@ static AovKernel aov_variant(int v) {                              // bit 0 FANC
         default: return k_aov<true, true>;
     }
 }
-
-typedef void (*PrimaryKernel)(PrimaryArgs);
-static PrimaryKernel primary_variant(int v) {                      // bit 0 FANCY, bit 1 SOFT, bit 2 MESH, bit 3: the lean variant built for five workgroups per CU
-    switch (v & 15) {
-        case 0: return k_primary<false, false, false, kPrimaryBlocks>;
-        case 8: return k_primary<false, false, false, kLeanBlocks>;
-        case 1: case 9: return k_primary<true, false, false, 2>;
-        case 2: case 10: return k_primary<false, true, false, kPrimaryBlocks>;
-        case 3: case 11: return k_primary<true, true, false, 2>;
-        case 4: case 12: return k_primary<false, false, true, kPrimaryBlocks>;
-        case 5: case 13: return k_primary<true, false, true, 2>;
-        case 6: case 14: return k_primary<false, true, true, kPrimaryBlocks>;
-        default: return k_primary<true, true, true, 2>;
-    }
-}
-
-// k_primary_mesh is built for FT_MESH_BLOCKS workgroups per CU: the fastest of 4, 5 and 6 on the headline (DESIGN.md 5; the others are
-// a build with -DFT_MESH_BLOCKS=n away, `make resource-usage MESH_BLOCKS=n` reports their registers).
-#ifndef FT_MESH_BLOCKS
-#define FT_MESH_BLOCKS 5
-#endif
-static PrimaryKernel mesh_kernel() { return k_primary_mesh<FT_MESH_BLOCKS>; }
-
-typedef void (*BounceKernel)(BounceArgs);
-static BounceKernel bounce_variant(int v) {
-    switch (v & 7) {
-        case 0: return k_bounce<false, false, false>;
-        case 1: return k_bounce<true, false, false>;
-        case 2: return k_bounce<false, true, false>;
-        case 3: return k_bounce<true, true, false>;
-        case 4: return k_bounce<false, false, true>;
-        case 5: return k_bounce<true, false, true>;
-        case 6: return k_bounce<false, true, true>;
-        default: return k_bounce<true, true, true>;
-    }
-}
-
-// ============================================================================================ launchers
 static int blocks_for(uint32_t n, int grid) { uint32_t need = (n + kBlock - 1) / kBlock; if (need < 1) need = 1; return (int)(need < (uint32_t)grid ? need : (uint32_t)grid); }
 
-void launch_primary(const Launch& L, const DevScene& S, const Primary& gen, RayBuf next, double* acc, uint32_t acc_stride, int max_depth, FrameCounters* fc) {
-    const PrimaryArgs a{S, gen, next, acc, fc, acc_stride, max_depth};
-    hipLaunchKernelGGL((L.variant & kVariantMeshKernel) ? mesh_kernel() : primary_variant(L.variant), dim3(L.grid), dim3(kBlock), L.lds_bytes, L.stream, a);
-}
 void launch_classify(const Launch& L, const DevScene& S, const Primary& gen_list, const ClassifyOut& out, double jitter_extent, uint32_t epoch, FrameCounters* fc,
                      const uint32_t* retired, bool mask_only) {
     const ClassifyArgs a{S, gen_list, out, fc, jitter_extent, epoch, retired, mask_only ? 1u : 0u};
@@ -3139,10 +3157,6 @@ void launch_block_lists(const Launch& L, const DevScene& S, const Primary& gen_l
     const BlockListArgs a{S, gen_list, pos_block, out, fc, jitter_extent, counts};
     const uint32_t n_blocks = gen_list.n_pix / 64u, need = (n_blocks + kBlock / 64u - 1u) / (kBlock / 64u);   // a wave per block, grid-strided over the active ones
     hipLaunchKernelGGL(k_block_lists, dim3(need < (uint32_t)L.grid ? (need ? need : 1u) : (uint32_t)L.grid), dim3(kBlock), 0, L.stream, a);
-}
-void launch_bounce(const Launch& L, const DevScene& S, const Primary& gen, RayBuf rays, RayBuf next, double* acc, uint32_t acc_stride, int bounce, int max_depth, bool follow, FrameCounters* fc) {
-    const BounceArgs a{S, gen, rays, next, acc, fc, acc_stride, bounce, max_depth, follow ? 1 : 0};
-    hipLaunchKernelGGL(bounce_variant(L.variant), dim3(L.grid), dim3(kBlock), L.lds_bytes, L.stream, a);
 }
 // Workgroups of a resolve launch: L.grid is one resident round of workgroups (occupancy_blocks_resolve x CUs; the grouped path holds 3 x 16
 // colours per lane: fewer waves fit than the tracing kernels' grids assume), so that the hand-over at the end waits for one generation of
@@ -3159,11 +3173,11 @@ void launch_resolve_progressive(const Launch& L, const ResolveArgs& a, const Pro
     else hipLaunchKernelGGL(k_resolve_progressive<false>, dim3(resolve_blocks(L, a)), dim3(kBlock), 0, L.stream, a, pa);
 }
 #ifdef FT_ITEM_COUNTS
-extern "C" int ft_debug_item_counts(unsigned long long out[48], int reset) {      // [0..15] item counters, [16..47] section clocks, summed over the waves' slots
-    static unsigned long long host[8192 * 48];
+extern "C" int ft_debug_item_counts(unsigned long long out[48], int reset) {      // the waves' words (FT_ITEM_COUNTS, above), summed over the waves
+    static unsigned long long host[kClkWaves * kClkWords];
     if (hipDeviceSynchronize() != hipSuccess || hipMemcpyFromSymbol(host, HIP_SYMBOL(g_clk), sizeof host) != hipSuccess) return -1;
-    for (int k = 0; k < 48; ++k) { out[k] = 0; for (int w = 0; w < 8192; ++w) out[k] += host[w * 48 + k]; }
-    if (reset) { static const unsigned long long z[8192 * 48] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(g_clk), z, sizeof z) != hipSuccess) return -1; }
+    for (uint32_t k = 0; k < kClkWords; ++k) { out[k] = 0; for (uint32_t w = 0; w < kClkWaves; ++w) out[k] += host[w * kClkWords + k]; }
+    if (reset) { static const unsigned long long z[kClkWaves * kClkWords] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(g_clk), z, sizeof z) != hipSuccess) return -1; }
     return 0;
 }
 #endif
@@ -3185,38 +3199,11 @@ void launch_aov(const Launch& L, const DevScene& S, const Primary& gen, uint32_t
     const uint32_t waves = (gen.n_pix + 63u) / 64u * (uint32_t)S.lane_fold;   // batches of 64 / lane_fold entries
     hipLaunchKernelGGL(aov_variant(L.variant), dim3(blocks_for(waves * 64u, L.grid)), dim3(kBlock), L.lds_bytes, L.stream, a);
 }
-
-} // namespace ftk
-
-// Resident workgroups per CU for the persistent grids (register- and LDS-limited).
-namespace ftk {
-static int clamp_blocks(int n) { return n < 1 ? 1 : (n > 8 ? 8 : n); }
-// Resident workgroups per CU of k_primary for this scene; *variant gains bit 3 when the five-workgroup build of the lean variant fits.
-int occupancy_blocks_primary(size_t lds_bytes, int* variant) {
-    int n = 0;
-    if ((*variant & 7) == 0) {
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, primary_variant(8), kBlock, lds_bytes) == hipSuccess && n >= kLeanBlocks) { *variant |= 8; return clamp_blocks(n); }
-    }
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, primary_variant(*variant), kBlock, lds_bytes) != hipSuccess) n = 1;
-    return clamp_blocks(n);
-}
-int occupancy_blocks_primary_mesh() {                                // (no LDS: registers alone decide)
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, mesh_kernel(), kBlock, 0) != hipSuccess) n = 1;
-    return clamp_blocks(n);
-}
 int occupancy_blocks_resolve() {
     int n = 0;
     return (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_resolve, kBlock, 0) == hipSuccess && n > 0) ? clamp_blocks(n) : 2;
 }
-int occupancy_blocks_aov(size_t lds_bytes, int variant) {
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, aov_variant(variant), kBlock, lds_bytes) != hipSuccess) n = 1;
-    return clamp_blocks(n);
-}
-int occupancy_blocks_bounce(size_t lds_bytes, int variant) {
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, bounce_variant(variant), kBlock, lds_bytes) != hipSuccess) n = 1;
-    return clamp_blocks(n);
-}
+int occupancy_blocks_aov(size_t lds_bytes, int variant) { return occupancy_blocks(aov_variant(variant), lds_bytes); }
+#endif
+
 } // namespace ftk

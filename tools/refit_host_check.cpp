@@ -4,8 +4,8 @@
 // Build and run from the repository root (the device objects are linked as they are: make -C functracer_amd/csrc first):
 //   C=functracer_amd/csrc; S="-fsanitize=address,undefined -fno-omit-frame-pointer -g -O1 -std=c++17 -ffp-contract=off"
 //   g++ $S -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include tools/refit_host_check.cpp $C/ft_capi.cpp $C/ft_frame.cpp $C/ft_progressive.cpp \
-//       $C/ft_passes.cpp $C/ft_debug.cpp $C/ft_scene.cpp $C/ft_kernels.o $C/ft_bvh.o $C/ft_refit.o $C/ft_denoise.o $C/ft_temporal.o \
-//       $C/ft_temporal_filter.o -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib -o build/refit_host_check && build/refit_host_check
+//       $C/ft_passes.cpp $C/ft_debug.cpp $C/ft_scene.cpp $(for o in $(make -s -C $C print-DEVICE_OBJS); do echo $C/$o; done) \
+//       -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib -o build/refit_host_check && build/refit_host_check
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>

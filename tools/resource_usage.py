@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Registers, scratch and occupancy of every kernel of ft_kernels.hip and ft_temporal.hip as the compiler reports them (no GPU needed):
+"""Registers, scratch and occupancy of every kernel of ft_kernels.hip (compiled as it stands: one unit) and ft_temporal.hip as the compiler reports them (no GPU
+needed; RU_UNITS="ft_k_mesh_frame ft_k_primary ft_k_bounce" in the environment: of the units the library is linked from):
 python tools/resource_usage.py > profiles/<tag>_resource_usage.json
 python tools/resource_usage.py 4 5 6 > ...   the same with k_primary_mesh built for each of these workgroup counts (make MESH_BLOCKS=n), merged"""
 import json
