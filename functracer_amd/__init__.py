@@ -68,7 +68,7 @@ def hip_lib():
         lib.ft_denoise.argtypes = _capi.DENOISE_SIGNATURE
         lib.ft_temporal_filter.restype, lib.ft_temporal_filter.argtypes = C.c_int32, _capi.TEMPORAL_FILTER_SIGNATURE
         lib.ft_quantise_rgba8.argtypes = [_capi.c_double_p, C.c_int64, C.POINTER(C.c_uint8)]
-        for name, res, args in _capi.PROGRESSIVE_SIGNATURES + _capi.TEMPORAL_SIGNATURES + _capi.TEMPORAL_QUEUE_SIGNATURES + _capi.MOTION_SIGNATURES + _capi.DEFORM_SIGNATURES:
+        for name, res, args in _capi.PROGRESSIVE_SIGNATURES + _capi.TEMPORAL_SIGNATURES + _capi.TEMPORAL_QUEUE_SIGNATURES + _capi.MOTION_SIGNATURES + _capi.DEFORM_SIGNATURES + _capi.LIGHT_SIGNATURES:
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _hip = lib
@@ -594,6 +594,26 @@ class Context(SceneBuilder):
         device.  A temporal accumulation stays open; a progressive accumulation ends.  Under set_option("temporal_follow_deformed", 1) the
         edited meshes' records are kept as the accumulation last saw them (72 bytes per triangle, until the next temporal_accumulate)."""
         self._check(self._lib.ft_scene_commit_deformed(self._ctx))
+        self._progressive = None
+
+    # moving lights (include/functracer_hip.h) ---------------------------------------------------------
+    def set_directional(self, light, direction, colour):
+        """ft_scene_set_directional: new direction and colour for light `light` (the index in add_* order), a directional light."""
+        self._check(self._lib.ft_scene_set_directional(self._ctx, int(light), _capi.vec3(direction), _capi.vec3(colour)))
+
+    def set_soft_directional(self, light, direction, scatter_rad, colour):
+        """ft_scene_set_soft_directional: new direction, scatter angle and colour for a soft directional light; its sample count stays."""
+        self._check(self._lib.ft_scene_set_soft_directional(self._ctx, int(light), _capi.vec3(direction), float(scatter_rad), _capi.vec3(colour)))
+
+    def set_positional(self, light, position, falloff, colour):
+        """ft_scene_set_positional: new position, falloff and colour for a point light."""
+        self._check(self._lib.ft_scene_set_positional(self._ctx, int(light), _capi.vec3(position), _capi.vec3(falloff), _capi.vec3(colour)))
+
+    def commit_lights(self):
+        """ft_scene_commit_lights: commit a graph whose light values alone changed since the last commit: the lights are uploaded again and
+        the light-space shadow trees of the directions that changed are refit on the device.  A temporal accumulation stays open; a
+        progressive accumulation ends."""
+        self._check(self._lib.ft_scene_commit_lights(self._ctx))
         self._progressive = None
 
     def tree_quality(self, node):

@@ -135,6 +135,15 @@ DEFORM_SIGNATURES = [
 ]
 
 
+# Moving lights (include/functracer_hip.h): new values for an existing light, committed without a flatten or a BVH build.
+LIGHT_SIGNATURES = [
+    ("ft_scene_set_directional", C.c_int32, [C.c_void_p, C.c_int32, c_double_p, c_double_p]),
+    ("ft_scene_set_soft_directional", C.c_int32, [C.c_void_p, C.c_int32, c_double_p, C.c_double, c_double_p]),
+    ("ft_scene_set_positional", C.c_int32, [C.c_void_p, C.c_int32, c_double_p, c_double_p, c_double_p]),
+    ("ft_scene_commit_lights", C.c_int32, [C.c_void_p]),
+]
+
+
 # ft_debug_mesh_trees (include/functracer_hip.h): the mesh trees as they lie in HBM, for the tests' structure checker.
 MESH_TREES_SIGNATURE = [C.c_void_p, C.POINTER(C.c_int64)] + [C.c_void_p] * 9
 BSP_NODE_DTYPE = np.dtype([("bmin", np.float64, 3), ("bmax", np.float64, 3), ("left", np.int32), ("right", np.int32), ("axis", np.uint32), ("pad", np.uint32)])

@@ -149,7 +149,7 @@ void ft_destroy(ft_context* c) {
         for (DeviceBuf& b : c->d_acc) b.release();
         for (DeviceBuf* b : {&c->d_out, &c->d_out8, &c->d_out_index, &c->d_pixels, &c->d_jitter, &c->d_wave_counts, &c->d_dbg_in, &c->d_dbg_out}) b->release();
         for (auto& f : c->slots) f.release();
-        c->prog.release(); c->aov.release(); c->denoise.release(); c->temporal.release(); c->refit.release();   // what the features own
+        c->prog.release(); c->aov.release(); c->denoise.release(); c->temporal.release(); c->refit.release(); c->lightspace.release();   // what the features own
         if (c->classified) (void)hipEventDestroy(c->classified);
         for (hipEvent_t& e : c->acc_free) if (e) { (void)hipEventDestroy(e); e = nullptr; }
         if (c->side) (void)hipStreamDestroy(c->side);
@@ -346,6 +346,36 @@ int32_t ft_scene_add_positional(ft_context* c, const double pos[3], const double
     c->graph.lights.push_back(l); c->committed = false; c->restructured = true;
     return FT_OK;
 }
+// The values of an existing light replaced, with the arithmetic of the ft_scene_add_* of its kind; the kind and a soft light's sample count
+// stay (they fix the kernel variant, shadow_rays_per_hit and the byte packing).  Not a structural change: what ft_scene_commit_lights needs.
+static ftd::Light* light_to_set(ft_context* c, int32_t light, uint32_t kind, const char* who) {
+    if (light < 0 || (size_t)light >= c->graph.lights.size()) { c->err = std::string(who) + ": no such light"; return nullptr; }
+    if (c->graph.lights[(size_t)light].kind != kind) { c->err = std::string(who) + ": the light is of another kind (ft_scene_clear / ft_scene_add_* change kinds)"; return nullptr; }
+    c->committed = false; c->lights_pending = true;
+    return &c->graph.lights[(size_t)light];
+}
+int32_t ft_scene_set_directional(ft_context* c, int32_t light, const double dir[3], const double colour[3]) {
+    if (!c || !dir || !colour) return FT_ERR_INVALID;
+    ftd::Light* l = light_to_set(c, light, ftd::LT_DIRECTIONAL, "ft_scene_set_directional");
+    if (!l) return FT_ERR_INVALID;
+    std::memcpy(l->v, dir, sizeof l->v); norm3(l->v); std::memcpy(l->colour, colour, sizeof l->colour);
+    return FT_OK;
+}
+int32_t ft_scene_set_soft_directional(ft_context* c, int32_t light, const double dir[3], double scatter_rad, const double colour[3]) {
+    if (!c || !dir || !colour) return FT_ERR_INVALID;
+    ftd::Light* l = light_to_set(c, light, ftd::LT_SOFT, "ft_scene_set_soft_directional");
+    if (!l) return FT_ERR_INVALID;
+    l->scatter = scatter_rad;
+    std::memcpy(l->v, dir, sizeof l->v); norm3(l->v); std::memcpy(l->colour, colour, sizeof l->colour);
+    return FT_OK;
+}
+int32_t ft_scene_set_positional(ft_context* c, int32_t light, const double pos[3], const double falloff[3], const double colour[3]) {
+    if (!c || !pos || !falloff || !colour) return FT_ERR_INVALID;
+    ftd::Light* l = light_to_set(c, light, ftd::LT_POINT, "ft_scene_set_positional");
+    if (!l) return FT_ERR_INVALID;
+    std::memcpy(l->v, pos, sizeof l->v); std::memcpy(l->falloff, falloff, sizeof l->falloff); std::memcpy(l->colour, colour, sizeof l->colour);
+    return FT_OK;
+}
 
 } // extern "C"
 
@@ -436,6 +466,7 @@ static int32_t upload_scene(ft_context* c) {
     const fth::FlatScene& f = c->flat;
     if ((rc = lds_fits(c)) != FT_OK) return rc;
     c->refit.ready = false;                                         // the trees these uploads bring are not the ones its tables describe
+    c->lightspace.reset();                                          // nor the light-space trees ft_scene_commit_lights' tables describe
     ftk::DevScene& S = c->dev_scene;
     rc = FT_OK;
     auto put = [&](SceneArray k, const auto& v, auto*& ptr) {   // array k into its buffer, and the device scene's pointer to it
@@ -485,7 +516,7 @@ int32_t commit_scene(ft_context* c) {
     for (double& v : c->commit_ms) v = 0.0;
     const bool held = c->holds_commit;
     const auto done = [c](int32_t rc) {
-        if (rc == FT_OK) { c->holds_commit = true; c->restructured = false; c->moved_pending = false; c->options_pending = false; for (fth::GraphNode& n : c->graph.nodes) n.deformed = false; }
+        if (rc == FT_OK) { c->holds_commit = true; c->restructured = false; c->moved_pending = false; c->options_pending = false; c->lights_pending = false; for (fth::GraphNode& n : c->graph.nodes) n.deformed = false; }
         return rc;
     };
     // A device context builds the exact BVH of top-level-Leaf meshes on the device ("bvh_builder" = 1; 2, the default: from 4096 triangles on): the flattener
@@ -717,6 +748,249 @@ static int32_t refit_device(ft_context* c, const fth::FlatScene& f, const fth::S
     return FT_OK;
 }
 
+// ------------------------------------------------------------------------------------------ moving lights (ft_scene_commit_lights)
+// What the first ft_scene_commit_lights after a full commit reads off `f` as that commit left it (ft_context::LightSpace): the pairs that
+// have a tree, what of their records does not depend on the direction, and each tree's 4-wide nodes by level, deepest first.
+static void derive_light_space_tables(const fth::FlatScene& f, ft_context::LightSpace& T) {
+    T.pairs.clear(); T.order.clear();
+    T.base_node_words = f.ls_nodes.size(); T.base_tri_doubles = f.ls_tris.size();
+    const size_t n_nodes = f.ls_nodes.size() / ftd::kLsNodeWords, n_recs = f.ls_pairs.size() / ftd::kLsPairDoubles;
+    std::vector<uint8_t> seen(n_nodes, 0);
+    for (uint32_t leaf = 0; leaf < (uint32_t)f.leaves.size(); ++leaf) {
+        const ftd::Leaf& L = f.leaves[leaf];
+        if (L.ls_pairs == ~0u || L.kind != ftd::LK_MESH || L.mesh >= f.meshes.size() || f.meshes[L.mesh].root >= 0) continue;
+        const size_t bl = (size_t)~f.meshes[L.mesh].root;
+        if (bl >= f.bsp_leaves.size()) continue;
+        const ftd::BspLeaf src = f.bsp_leaves[bl];
+        if ((size_t)src.first_tri + src.n_tris > f.tris.size() / 9) continue;
+        const double* mb = &f.mesh_bounds[6 * (size_t)L.mesh];
+        const double c[3] = {0.5 * (mb[0] + mb[3]), 0.5 * (mb[1] + mb[4]), 0.5 * (mb[2] + mb[5])};
+        double R = 0.0;                                             // as build_light_space sums it: it does not depend on the frame
+        for (uint32_t k = 0; k < src.n_tris; ++k) {
+            const double* Tr = &f.tris[9 * (size_t)(src.first_tri + k)];
+            for (int v = 0; v < 3; ++v) {
+                double p[3];
+                for (int q = 0; q < 3; ++q) p[q] = (Tr[q] - c[q]) + (v == 1 ? Tr[3 + q] : v == 2 ? Tr[6 + q] : 0.0);
+                R = std::max(R, std::fabs(p[0]) + std::fabs(p[1]) + std::fabs(p[2]));
+            }
+        }
+        for (uint32_t l = 0; l < (uint32_t)f.lights.size(); ++l) {
+            const size_t rec = (size_t)L.ls_pairs + l;
+            if (f.lights[l].kind != ftd::LT_DIRECTIONAL || rec >= n_recs) continue;
+            int32_t root;
+            std::memcpy(&root, &f.ls_pairs[ftd::kLsPairDoubles * rec + 14], 4);
+            if (root < 0 || (size_t)root >= n_nodes || seen[(size_t)root]) continue;   // none at the commit: none until the next one
+            ft_context::LightSpace::Pair P{};
+            P.rec = (uint32_t)rec; P.leaf = leaf; P.light = l; P.root = root; P.R = R; P.first_tri = src.first_tri; P.n_tris = src.n_tris;
+            for (int q = 0; q < 3; ++q) { P.c[q] = c[q]; P.v0[q] = f.lights[l].v[q]; }
+            std::memcpy(P.rec0, &f.ls_pairs[ftd::kLsPairDoubles * rec], sizeof P.rec0);
+            // breadth first: `level` holds one level of the tree; the levels are then laid out deepest first
+            std::vector<std::vector<uint32_t>> by_level;
+            std::vector<uint32_t> level{(uint32_t)root};
+            seen[(size_t)root] = 1;
+            while (!level.empty()) {
+                std::vector<uint32_t> next;
+                for (uint32_t n : level) for (int k = 0; k < 4; ++k) {
+                    const int32_t ch = (int32_t)f.ls_nodes[(size_t)ftd::kLsNodeWords * n + 20 + k];
+                    if (ch < 0 || (size_t)ch >= n_nodes || seen[(size_t)ch]) continue;   // a leaf, an empty slot (or no tree at all)
+                    seen[(size_t)ch] = 1;
+                    next.push_back((uint32_t)ch);
+                }
+                by_level.push_back(std::move(level));
+                level = std::move(next);
+            }
+            for (size_t d = by_level.size(); d-- > 0;) {
+                P.levels.push_back({(uint32_t)T.order.size(), (uint32_t)by_level[d].size()});
+                T.order.insert(T.order.end(), by_level[d].begin(), by_level[d].end());
+            }
+            T.pairs.push_back(std::move(P));
+        }
+    }
+    T.ready = true;
+}
+
+// One pair's share of an ft_scene_commit_lights: its frame; whether its tree is refit (its direction changed in this call); whether its
+// grid is built again behind the arrays of the full commit (every pair whose direction is not that commit's, in every call that
+// turns any light: the region is laid out anew each time, so it never grows), and what the context's first device decided for that grid.
+struct LightJob {
+    const ft_context::LightSpace::Pair* pair; ftk::LsFrame frame; bool refit, regrid;
+    bool grid = false; float s = 0.0f; uint32_t nu = 0, nv = 0, entries = 0, at = 0, tri_at = 0;
+    size_t slot = 0;                                                // of the device's per-pair scratch (ft_context::LightSpace::d_ebox, d_counts)
+};
+
+// build_grid's decisions for one pair (ft_scene.cpp), its host loops run as passes on the device: readback 1 Ru and Rv, readback 2 the
+// entries under each candidate of the attempt loop, readback 3 the fullest cell.  `bytes`: what the arrays hold so far, against the cap.
+// The pair's entry boxes and cell counts stay in its scratch slot for the pass that writes the grid.
+static int32_t plan_grid(ft_context* c, LightJob& j, uint64_t& bytes) {
+    ft_context::LightSpace& L = c->lightspace;
+    DeviceBuf& ebox = L.d_ebox[j.slot];
+    DeviceBuf& counts = L.d_counts[j.slot];
+    const uint32_t n = j.pair->n_tris;
+    int32_t rc;
+    if ((rc = ensure(c, ebox, (size_t)n * 20)) != FT_OK) return rc;
+    const double* tris = c->d_scene[kTris].as<double>() + 9 * (size_t)j.pair->first_tri;
+    uint32_t* small = L.d_small.as<uint32_t>();                     // [0] Ru, [1] Rv, [2] the fullest cell, [4 ..] eight 64-bit sums
+    unsigned long long* sums = reinterpret_cast<unsigned long long*>(small + 4);
+    FT_HIP(c, hipMemsetAsync(small, 0, 128, c->stream));
+    ftk::ls_grid_entries(c->stream, tris, n, j.frame, ebox.as<float>(), small);
+    float ruv[2];
+    FT_HIP(c, hipMemcpyAsync(ruv, small, 8, hipMemcpyDeviceToHost, c->stream));
+    FT_HIP(c, hipStreamSynchronize(c->stream));
+    // build_grid's own arithmetic from here on
+    const double Ru = (double)ruv[0], Rv = (double)ruv[1];
+    const double side = 2.0 * std::max(Ru, Rv);
+    if (!(side > 0.0)) return FT_OK;
+    const double h = std::max(std::sqrt(4.0 * Ru * Rv / (double)n), side / 1024.0);
+    float s = (float)(1.0 / h);
+    ftk::LsGridCandidates C{};
+    for (int attempt = 0; attempt < 8 && s > 0.0f; ++attempt, s *= 0.75f) {
+        C.s[C.n] = s;
+        C.nu[C.n] = (uint32_t)std::min(1024.0, std::max(1.0, std::ceil(2.0 * Ru * (double)s)));
+        C.nv[C.n] = (uint32_t)std::min(1024.0, std::max(1.0, std::ceil(2.0 * Rv * (double)s)));
+        ++C.n;
+    }
+    if (C.n == 0) return FT_OK;
+    ftk::ls_grid_count(c->stream, ebox.as<float>(), n, C, sums);
+    unsigned long long got[8];
+    FT_HIP(c, hipMemcpyAsync(got, sums, sizeof got, hipMemcpyDeviceToHost, c->stream));
+    FT_HIP(c, hipStreamSynchronize(c->stream));
+    int a = 0;
+    while (a < C.n && !((uint64_t)C.nu[a] * C.nv[a] <= 2 * (uint64_t)n && got[a] <= (uint64_t)ftd::kLsGridEntriesPerTri * n)) ++a;
+    if (a == C.n || (uint64_t)C.nu[a] * C.nv[a] < 2) return FT_OK;
+    const uint32_t cells = C.nu[a] * C.nv[a];
+    if ((rc = ensure(c, counts, (size_t)cells * 4)) != FT_OK) return rc;
+    FT_HIP(c, hipMemsetAsync(counts.p, 0, (size_t)cells * 4, c->stream));
+    ftk::ls_grid_cell_counts(c->stream, ebox.as<float>(), n, C.s[a], C.nu[a], C.nv[a], counts.as<uint32_t>(), small + 2);
+    uint32_t fullest = 0;
+    FT_HIP(c, hipMemcpyAsync(&fullest, small + 2, 4, hipMemcpyDeviceToHost, c->stream));
+    FT_HIP(c, hipStreamSynchronize(c->stream));
+    if (fullest > ftd::kLsGridMaxCell) return FT_OK;
+    const uint64_t need = (uint64_t)cells * 16 + got[a] * (72 + 20) + ftd::kLsNodeWords * 4;
+    if (bytes + need > ftd::kLsMaxBytes) return FT_OK;
+    bytes += need;
+    j.grid = true; j.s = C.s[a]; j.nu = C.nu[a]; j.nv = C.nv[a]; j.entries = (uint32_t)got[a];
+    return FT_OK;
+}
+
+// The new lights on one device of the context: `f` is the held scene with the new lights and pair records already in it (the grid words of
+// the jobs' records excepted: the first device, `lead`, decides them here and writes them into f; the others carry them out).  The trees
+// of the jobs that ask for it are written again in their new frames, the grids laid out anew behind the full commit's arrays
+// (ft_lightspace.hip; `relay`: some light turned and the scene has grids).  ms[0] += uploads and the rest, ms[1] += the kernels.
+static int32_t relight_device(ft_context* c, fth::FlatScene& f, const ft_context::LightSpace& T, std::vector<LightJob>& jobs, bool relay, bool lead, double ms[2]) {
+    using clock = std::chrono::steady_clock;
+    auto since = [](clock::time_point t0) { return std::chrono::duration<double, std::milli>(clock::now() - t0).count(); };
+    int32_t rc;
+    FT_HIP(c, hipSetDevice(c->device));
+    const auto t0 = clock::now();
+    // frames still queued trace the scene these uploads rewrite (as upload_scene): they show the old lights
+    if (any_queued(c)) { if ((rc = retire_queued(c)) != FT_OK) return rc; c->accum_open = false; }
+    if ((rc = drain_frame_streams(c)) != FT_OK) return rc;
+    if (c->side) FT_HIP(c, hipStreamSynchronize(c->side));
+    DeviceBuf* B = c->d_scene;
+    ft_context::LightSpace& L = c->lightspace;
+    if (L.node_words == 0) { L.node_words = T.base_node_words; L.tri_doubles = T.base_tri_doubles; }   // the first call since the upload
+    if (!jobs.empty() && !L.order_uploaded) {
+        if ((rc = upload(c, L.d_order, T.order)) != FT_OK) return rc;
+        L.order_uploaded = true;
+    }
+    if ((rc = upload(c, B[kLights], f.lights)) != FT_OK) return rc;
+    FT_HIP(c, hipStreamSynchronize(c->stream));
+    ms[0] += since(t0);
+    const auto t1 = clock::now();
+    if (B[kLsNodes].bytes < L.node_words * 4 || B[kLsTris].bytes < L.tri_doubles * 8 || L.node_words < T.base_node_words || L.tri_doubles < T.base_tri_doubles ||
+        B[kTris].bytes < f.tris.size() * 8) { c->err = "ft_scene_commit_lights: a scene array in device memory is smaller than the flattened one"; return FT_ERR_STATE; }
+    const uint32_t n_nodes = (uint32_t)(T.base_node_words / ftd::kLsNodeWords), n_tris = (uint32_t)(T.base_tri_doubles / 9);   // the trees lie in the full commit's part
+    size_t slots = 0;
+    bool regrid = relay;                                            // a light turned: the region behind the full commit's arrays is laid out anew, be it to nothing
+    for (const LightJob& j : jobs) {
+        if (j.regrid) slots = std::max(slots, j.slot + 1);
+        if (!j.refit) continue;
+        for (const auto& lv : j.pair->levels)                       // deepest level first: a node's children are done before it
+            ftk::ls_refit_level(c->stream, B[kLsNodes].as<uint32_t>(), n_nodes, B[kLsTris].as<double>(), n_tris, L.d_order.as<uint32_t>() + lv.first, lv.second, j.frame);
+        L.rewritten = true;
+    }
+    FT_HIP(c, hipGetLastError());
+    size_t words = T.base_node_words, doubles = T.base_tri_doubles;   // the arrays' sizes: the full commit's part, the grids behind it
+    if (regrid) {
+        if (L.d_ebox.size() < slots) { L.d_ebox.resize(slots); L.d_counts.resize(slots); }
+        if ((rc = ensure(c, L.d_small, 128)) != FT_OK) return rc;
+        if (lead) {                                                 // the decisions that need a readback, and with them the layout
+            uint64_t bytes = (uint64_t)T.base_node_words * 4 + (uint64_t)T.base_tri_doubles * 8;
+            size_t at = T.base_node_words, recs = T.base_tri_doubles / 9;
+            for (LightJob& j : jobs) {
+                if (!j.regrid) continue;
+                if ((rc = plan_grid(c, j, bytes)) != FT_OK) return rc;
+                if (!j.grid) continue;
+                j.at = (uint32_t)at; j.tri_at = (uint32_t)recs;
+                const size_t own = 4 * (size_t)j.nu * j.nv + 5 * (size_t)j.entries;
+                at += (own + ftd::kLsNodeWords - 1) / ftd::kLsNodeWords * ftd::kLsNodeWords;   // padded to a whole node, as build_grid pads
+                recs += j.entries;
+                uint32_t w[3] = {j.at, 0u, j.nu | j.nv << 16};
+                std::memcpy(&w[1], &j.s, 4);
+                std::memcpy(reinterpret_cast<char*>(&f.ls_pairs[(size_t)ftd::kLsPairDoubles * j.pair->rec + 14]) + 4, w, sizeof w);
+            }
+        }
+        for (const LightJob& j : jobs) {
+            if (!j.grid) continue;
+            const size_t own = 4 * (size_t)j.nu * j.nv + 5 * (size_t)j.entries;
+            words = std::max(words, (size_t)j.at + (own + ftd::kLsNodeWords - 1) / ftd::kLsNodeWords * ftd::kLsNodeWords);
+            doubles = std::max(doubles, 9 * ((size_t)j.tri_at + j.entries));
+        }
+        if (words == T.base_node_words && doubles == T.base_tri_doubles && words == L.node_words && doubles == L.tri_doubles) regrid = false;   // no grid before, none now
+    }
+    if (regrid) {
+        // Fresh arrays of exactly that size: the full commit's part as it lies in HBM now (the refit trees in it), the grids behind it.
+        DeviceBuf nodes, tris;
+        if ((rc = ensure(c, nodes, words * 4)) != FT_OK || (rc = ensure(c, tris, doubles * 8)) != FT_OK) { nodes.release(); tris.release(); return rc; }
+        const auto fail = [&](int32_t code) { nodes.release(); tris.release(); return code; };
+        if (hipMemcpyAsync(nodes.p, B[kLsNodes].p, T.base_node_words * 4, hipMemcpyDeviceToDevice, c->stream) != hipSuccess ||
+            hipMemcpyAsync(tris.p, B[kLsTris].p, T.base_tri_doubles * 8, hipMemcpyDeviceToDevice, c->stream) != hipSuccess ||
+            (words > T.base_node_words && hipMemsetAsync(nodes.as<uint32_t>() + T.base_node_words, 0, (words - T.base_node_words) * 4, c->stream) != hipSuccess) ||
+            (doubles > T.base_tri_doubles && hipMemsetAsync(tris.as<double>() + T.base_tri_doubles, 0, (doubles - T.base_tri_doubles) * 8, c->stream) != hipSuccess)) {
+            c->err = "ft_scene_commit_lights: copying the light-space arrays failed"; return fail(FT_ERR_HIP);
+        }
+        for (const LightJob& j : jobs) {
+            if (!j.grid) continue;
+            const uint32_t n = j.pair->n_tris, cells = j.nu * j.nv;
+            const double* mesh = B[kTris].as<double>() + 9 * (size_t)j.pair->first_tri;
+            size_t scan_bytes = 0;
+            if (ftk::ls_grid_scan(c->stream, nullptr, nullptr, cells, nullptr, &scan_bytes) != hipSuccess) { c->err = "ft_scene_commit_lights: sizing the scan failed"; return fail(FT_ERR_HIP); }
+            DeviceBuf& ebox = L.d_ebox[j.slot];
+            DeviceBuf& counts = L.d_counts[j.slot];
+            if ((rc = ensure(c, ebox, (size_t)n * 20)) != FT_OK || (rc = ensure(c, counts, (size_t)cells * 4)) != FT_OK || (rc = ensure(c, L.d_first, (size_t)cells * 4)) != FT_OK ||
+                (rc = ensure(c, L.d_cursor, (size_t)cells * 4)) != FT_OK || (rc = ensure(c, L.d_idx, (size_t)j.entries * 4)) != FT_OK || (rc = ensure(c, L.d_scan, scan_bytes)) != FT_OK) return fail(rc);
+            if (hipMemsetAsync(L.d_cursor.p, 0, (size_t)cells * 4, c->stream) != hipSuccess) { c->err = "ft_scene_commit_lights: hipMemsetAsync failed"; return fail(FT_ERR_HIP); }
+            if (!lead) {                                            // (the first device's slot holds both since plan_grid)
+                if (hipMemsetAsync(counts.p, 0, (size_t)cells * 4, c->stream) != hipSuccess) { c->err = "ft_scene_commit_lights: hipMemsetAsync failed"; return fail(FT_ERR_HIP); }
+                ftk::ls_grid_entries(c->stream, mesh, n, j.frame, ebox.as<float>(), nullptr);
+                ftk::ls_grid_cell_counts(c->stream, ebox.as<float>(), n, j.s, j.nu, j.nv, counts.as<uint32_t>(), nullptr);
+            }
+            if (ftk::ls_grid_scan(c->stream, counts.as<uint32_t>(), L.d_first.as<uint32_t>(), cells, L.d_scan.p, &scan_bytes) != hipSuccess) { c->err = "ft_scene_commit_lights: the scan failed"; return fail(FT_ERR_HIP); }
+            ftk::ls_grid_emit(c->stream, ebox.as<float>(), mesh, n, j.s, j.nu, j.nv, counts.as<uint32_t>(), L.d_first.as<uint32_t>(), L.d_cursor.as<uint32_t>(), L.d_idx.as<uint32_t>(),
+                              j.entries, nodes.as<uint32_t>(), j.at, tris.as<double>(), j.tri_at);
+        }
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) { c->err = "ft_scene_commit_lights: the grid kernels failed"; return fail(FT_ERR_HIP); }
+        // nothing reads the old arrays any more: the streams were drained above
+        B[kLsNodes].release(); B[kLsTris].release();
+        B[kLsNodes] = nodes; B[kLsTris] = tris;
+        ftk::DevScene& S = c->dev_scene;
+        S.ls_nodes = static_cast<std::remove_reference_t<decltype(S.ls_nodes)>>(nodes.p);
+        S.ls_tris = static_cast<std::remove_reference_t<decltype(S.ls_tris)>>(tris.p);
+        L.node_words = words; L.tri_doubles = doubles;
+        L.rewritten = true;
+    }
+    FT_HIP(c, hipStreamSynchronize(c->stream));
+    ms[1] += since(t1);
+    const auto t2 = clock::now();
+    if ((rc = upload(c, B[kLsPairs], f.ls_pairs)) != FT_OK) return rc;
+    FT_HIP(c, hipStreamSynchronize(c->stream));
+    ms[0] += since(t2);
+    c->zero_signature[0] = c->zero_signature[1] = 0;                // (as every commit)
+    c->committed = true;
+    ++c->commit_serial; c->staged_hint = -1;
+    return FT_OK;
+}
+
 } // namespace ftc
 
 extern "C" {
@@ -750,6 +1024,7 @@ int32_t ft_scene_commit_deformed(ft_context* c) {
     if (c->restructured) { c->err = "ft_scene_commit_deformed: the graph, the root or the lights changed since the commit (ft_scene_commit)"; return FT_ERR_STATE; }
     if (c->moved_pending) { c->err = "ft_scene_commit_deformed: an ft_sg_set_transform is pending (ft_scene_commit_moved first)"; return FT_ERR_STATE; }
     if (c->options_pending) { c->err = "ft_scene_commit_deformed: a commit-time option changed since the commit (ft_scene_commit)"; return FT_ERR_STATE; }
+    if (c->lights_pending) { c->err = "ft_scene_commit_deformed: a light setter is pending (ft_scene_commit_lights first)"; return FT_ERR_STATE; }
     using clock = std::chrono::steady_clock;
     const auto t0 = clock::now();
     fth::FlatScene& f = c->flat;
@@ -803,6 +1078,80 @@ int32_t ft_scene_commit_deformed(ft_context* c) {
     c->commit_ms[1] = ms[1]; c->commit_ms[2] = ms[0];
     if (rc != FT_OK) { for (ft_context* d : devices(c)) d->committed = false; c->holds_commit = false; return rc; }   // HBM holds neither scene whole: ft_scene_commit
     for (fth::GraphNode& n : c->graph.nodes) n.deformed = false;
+    return FT_OK;
+}
+
+// The commit of a graph whose lights alone changed (ft_scene_set_directional / _soft_directional / _positional): no flatten and no BVH
+// work.  The lights are uploaded again; every light-space pair whose direction changed gets its record derived again on the host, as
+// build_light_space derives it, its tree refit and its grid built again on the device (ft_lightspace.hip).  The temporal accumulation
+// stays open and the pose counter stays; a progressive accumulation ends.
+int32_t ft_scene_commit_lights(ft_context* c) {
+    if (!c) return FT_ERR_INVALID;
+    if (!c->holds_commit) { c->err = "ft_scene_commit_lights: no committed scene to relight (ft_scene_commit)"; return FT_ERR_STATE; }
+    if (c->restructured) { c->err = "ft_scene_commit_lights: the graph, the root or the number or kinds of the lights changed since the commit (ft_scene_commit)"; return FT_ERR_STATE; }
+    if (c->moved_pending) { c->err = "ft_scene_commit_lights: an ft_sg_set_transform is pending (ft_scene_commit_moved first)"; return FT_ERR_STATE; }
+    for (const fth::GraphNode& n : c->graph.nodes) if (n.deformed) { c->err = "ft_scene_commit_lights: an ft_sg_set_mesh_triangles is pending (ft_scene_commit_deformed first)"; return FT_ERR_STATE; }
+    if (c->options_pending) { c->err = "ft_scene_commit_lights: a commit-time option changed since the commit (ft_scene_commit)"; return FT_ERR_STATE; }
+    if (c->host_only) {                                             // the same rules; the commit itself is the full one
+        progressive_close(c);
+        return commit_scene(c);
+    }
+    using clock = std::chrono::steady_clock;
+    const auto t0 = clock::now();
+    fth::FlatScene& f = c->flat;
+    if (c->graph.lights.size() != f.lights.size()) { c->err = "ft_scene_commit_lights: the number of lights changed since the commit (ft_scene_commit)"; return FT_ERR_STATE; }
+    ft_context::LightSpace& T = c->lightspace;
+    if (!T.ready) derive_light_space_tables(f, T);                  // off the records as the full commit left them
+    std::vector<ftd::Light> lights = c->graph.lights;
+    for (ftd::Light& l : lights) if (l.kind == ftd::LT_SOFT) l.tan_half_scatter = std::tan(l.scatter / 2.0);   // (as the flattener)
+    const auto same_dir = [](const double a[3], const double b[3]) { return std::memcmp(a, b, 3 * sizeof(double)) == 0; };
+    // Only a direction that changes touches a pair: colours and the other kinds of light are the upload alone.
+    bool turned = false;
+    for (const ft_context::LightSpace::Pair& P : T.pairs) turned = turned || (f.leaves[P.leaf].ls_pairs != ~0u && !same_dir(lights[P.light].v, f.lights[P.light].v));
+    const bool grids = c->graph.light_space_shadows == 2;
+    std::vector<LightJob> jobs;
+    size_t n_regrid = 0;
+    for (const ft_context::LightSpace::Pair& P : T.pairs) {
+        if (!turned || f.leaves[P.leaf].ls_pairs == ~0u) continue;  // (stripped by ft_scene_commit_deformed: stays stripped)
+        const bool refit = !same_dir(lights[P.light].v, f.lights[P.light].v);
+        double* rec = &f.ls_pairs[(size_t)ftd::kLsPairDoubles * P.rec];
+        LightJob j{&P, {}, refit, false};
+        if (same_dir(lights[P.light].v, P.v0)) {
+            // the full commit's direction (again): its record, and with it its grid, which still lies where that commit put it
+            std::memcpy(rec, P.rec0, sizeof P.rec0);
+            if (!refit) continue;
+            for (int q = 0; q < 3; ++q) { j.frame.U[q] = rec[q]; j.frame.V[q] = rec[3 + q]; j.frame.D[q] = rec[6 + q]; j.frame.c[q] = rec[9 + q]; }
+        } else {
+            for (int k = 0; k < ftd::kLsPairDoubles; ++k) rec[k] = 0.0;
+            fth::LsPairFrame fr;
+            // (every projected coordinate is at most R in size: the builder's finiteness test, five of them below 1e30, holds with R < 2e29)
+            const bool usable = fth::ls_pair_frame(f.leaves[P.leaf], lights[P.light], fr) && P.R < 2e29;
+            const int32_t root = usable ? P.root : INT32_MIN;       // none: the tree's nodes and records stay where they are for the direction's return
+            std::memcpy(&rec[14], &root, 4);
+            if (!usable) continue;
+            for (int q = 0; q < 3; ++q) { rec[q] = j.frame.U[q] = fr.U[q]; rec[3 + q] = j.frame.V[q] = fr.V[q]; rec[6 + q] = j.frame.D[q] = fr.D[q]; rec[9 + q] = j.frame.c[q] = P.c[q]; }
+            rec[12] = fr.k_rel; rec[13] = (fr.k_rel + 1e-6) * P.R + 1e-20;
+            j.regrid = grids;
+        }
+        j.frame.pad = 1e-7 * P.R + 1e-30;
+        if (j.regrid) j.slot = n_regrid++;
+        jobs.push_back(j);
+    }
+    f.lights = lights;
+    progressive_close(c);
+    const double tallest = c->commit_ms[3];
+    for (double& v : c->commit_ms) v = 0.0;
+    c->commit_ms[3] = tallest;
+    c->commit_ms[0] = std::chrono::duration<double, std::milli>(clock::now() - t0).count();
+    double ms[2] = {0.0, 0.0};
+    int32_t rc = FT_OK;
+    for (ft_context* d : devices(c)) {                              // every device rewrites its own copy; the first decides the grids
+        if ((rc = relight_device(d, f, T, jobs, turned && grids, d == c, ms)) != FT_OK) { if (d != c) c->err = d->err; break; }
+    }
+    for (ft_context* p : c->peers) { p->flat.lights = f.lights; p->flat.ls_pairs = f.ls_pairs; }
+    c->commit_ms[1] = ms[1]; c->commit_ms[2] = ms[0];
+    if (rc != FT_OK) { for (ft_context* d : devices(c)) d->committed = false; c->holds_commit = false; return rc; }   // HBM holds neither scene whole: ft_scene_commit
+    c->lights_pending = false;
     return FT_OK;
 }
 

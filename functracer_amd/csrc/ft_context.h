@@ -181,7 +181,8 @@ struct ft_context {
     // What ft_scene_commit_deformed asks for on top of that: no ft_sg_set_transform and no commit-time option waiting for a full commit
     // (both cleared by every successful full commit).
     bool moved_pending = false, options_pending = false;
-    uint64_t pose_serial = 0;       // advanced by ft_scene_commit_moved only (commit_serial also by the hit lists' re-commit, which moves nothing)
+    bool lights_pending = false;    // an ft_scene_set_* light setter since the last successful commit (ft_scene_commit_deformed waits for ft_scene_commit_lights)
+    uint64_t pose_serial = 0;      // advanced by ft_scene_commit_moved only (commit_serial also by the hit lists' re-commit, which moves nothing)
     double commit_ms[4] = {0, 0, 0, 0};   // last ft_scene_commit: flatten on the host, device BVH builds, uploads + the rest, BVH height (not a time)
 
     DeviceBuf d_scene[kSceneArrays];
@@ -261,6 +262,35 @@ struct ft_context {
         bool ready = false;
         void release() { for (DeviceBuf* b : {&d_verts, &d_parent_node, &d_parent_leaf, &d_arrived, &d_leaf_boxes, &d_wide_node, &d_cost}) b->release(); ready = false; }
     } refit;
+    // ft_scene_commit_lights.  On the context's first device, derived from `flat` by the first call after a full commit
+    // (`ready`) and kept until the next one: per (leaf, directional light) pair that had a tree then its record as that commit wrote it
+    // (rec0) and the light's direction then (v0), the tree's root, what of the record does not depend on the direction (centre, R; the
+    // leaf's w2m through `leaf`), the mesh's list-order records (first_tri, n_tris) and the tree's 4-wide nodes by level, deepest level
+    // first (levels: offset and count into `order`); base_*: the sizes of ls_nodes and ls_tris as that commit laid them out - the grids
+    // built since lie behind them.  On every device: `order` in HBM (d_order, uploaded by the device's first refit), the sizes of its
+    // ls_nodes and ls_tris now, whether they have been rewritten since the upload (ft_debug_light_space then answers from HBM) and the
+    // grid builder's scratch, kept from call to call.
+    struct LightSpace {
+        struct Pair {
+            uint32_t rec, leaf, light; int32_t root; double c[3], R; uint32_t first_tri, n_tris; double v0[3], rec0[ftd::kLsPairDoubles];
+            std::vector<std::pair<uint32_t, uint32_t>> levels;
+        };
+        std::vector<Pair> pairs;
+        std::vector<uint32_t> order;
+        size_t base_node_words = 0, base_tri_doubles = 0;
+        bool ready = false;
+        DeviceBuf d_order, d_first, d_cursor, d_idx, d_small, d_scan;
+        std::vector<DeviceBuf> d_ebox, d_counts;   // per pair whose grid a call builds: its entry boxes and cell counts, from the pass that decides the grid to the one that writes it
+        size_t node_words = 0, tri_doubles = 0;
+        bool order_uploaded = false, rewritten = false;
+        void reset() { pairs.clear(); order.clear(); ready = order_uploaded = rewritten = false; node_words = tri_doubles = base_node_words = base_tri_doubles = 0; }
+        void release() {
+            for (DeviceBuf* b : {&d_order, &d_first, &d_cursor, &d_idx, &d_small, &d_scan}) b->release();
+            for (DeviceBuf& b : d_ebox) b.release();
+            for (DeviceBuf& b : d_counts) b.release();
+            d_ebox.clear(); d_counts.clear(); reset();
+        }
+    } lightspace;
     // ft_scene_tree_quality, per mesh of `flat`, kept on the context's first device: the cost of the tree when it was last
     // built - measured the first time it is needed after a full commit, and again by every rebuild in place - and the rebuilds in place since
     // that commit.  Emptied by every full commit.

@@ -161,9 +161,26 @@ int32_t ft_debug_light_space(ft_context* c, int64_t sizes[4], double* pairs, uin
     const fth::FlatScene& f = c->flat;
     sizes[0] = (int64_t)(f.ls_pairs.size() / ftd::kLsPairDoubles); sizes[1] = (int64_t)(f.ls_nodes.size() / ftd::kLsNodeWords);
     sizes[2] = (int64_t)(f.ls_tris.size() / 9); sizes[3] = (int64_t)f.leaves.size();
-    if (pairs) std::memcpy(pairs, f.ls_pairs.data(), f.ls_pairs.size() * sizeof(double));
-    if (nodes) std::memcpy(nodes, f.ls_nodes.data(), f.ls_nodes.size() * sizeof(uint32_t));
-    if (tris) std::memcpy(tris, f.ls_tris.data(), f.ls_tris.size() * sizeof(double));
+    if (!c->host_only && c->lightspace.rewritten) {
+        // an ft_scene_commit_lights has rewritten trees and grids in HBM since the full commit: the arrays as they lie there, at the
+        // sizes they have there (as ft_debug_mesh_trees)
+        const ft_context::LightSpace& L = c->lightspace;
+        sizes[1] = (int64_t)(L.node_words / ftd::kLsNodeWords); sizes[2] = (int64_t)(L.tri_doubles / 9);
+        FT_HIP(c, hipSetDevice(c->device));
+        const int32_t rc = drain_frame_streams(c);
+        if (rc != FT_OK) return rc;
+        const DeviceBuf* B = c->d_scene;
+        if (B[kLsPairs].bytes < f.ls_pairs.size() * 8 || B[kLsNodes].bytes < L.node_words * 4 || B[kLsTris].bytes < L.tri_doubles * 8) {
+            c->err = "ft_debug_light_space: a light-space array in device memory is smaller than recorded"; return FT_ERR_STATE;
+        }
+        if (pairs) FT_HIP(c, hipMemcpy(pairs, B[kLsPairs].p, f.ls_pairs.size() * sizeof(double), hipMemcpyDeviceToHost));
+        if (nodes) FT_HIP(c, hipMemcpy(nodes, B[kLsNodes].p, L.node_words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        if (tris) FT_HIP(c, hipMemcpy(tris, B[kLsTris].p, L.tri_doubles * sizeof(double), hipMemcpyDeviceToHost));
+    } else {
+        if (pairs) std::memcpy(pairs, f.ls_pairs.data(), f.ls_pairs.size() * sizeof(double));
+        if (nodes) std::memcpy(nodes, f.ls_nodes.data(), f.ls_nodes.size() * sizeof(uint32_t));
+        if (tris) std::memcpy(tris, f.ls_tris.data(), f.ls_tris.size() * sizeof(double));
+    }
     if (leaf_pairs) for (size_t k = 0; k < f.leaves.size(); ++k) leaf_pairs[k] = f.leaves[k].ls_pairs;
     return FT_OK;
 }

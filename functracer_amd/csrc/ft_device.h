@@ -247,6 +247,28 @@ void refit_mesh(hipStream_t stream, const RefitArrays& A, const RefitMesh& m, co
 inline uint32_t refit_cost_blocks(const RefitMesh& m) { return (m.node_count + 255u) / 256u; }
 void refit_cost(hipStream_t stream, const RefitArrays& A, const RefitMesh& m, double* partials, double* cost);
 
+// Refit of a light-space shadow tree whose light turned (ft_lightspace.hip, ft_scene_commit_lights).  LsFrame: the pair's new frame and
+// centre as its record holds them (ft_flat.h, kLsPairDoubles) and the builder's inflation, 1e-7 * R + 1e-30.  One call per level of the
+// tree, deepest first: order[0 .. count) are that level's 4-wide nodes (indices into ls_nodes), whose child boxes are written again -
+// leaf children from their records in ls_tris, node children from the boxes the call before wrote.
+struct LsFrame { double U[3], V[3], D[3], c[3], pad; };
+void ls_refit_level(hipStream_t stream, uint32_t* ls_nodes, uint32_t n_nodes, const double* ls_tris, uint32_t n_tris, const uint32_t* order, uint32_t count, const LsFrame& F);
+// The grid of such a pair built again (ft_scene.cpp, build_grid, its host loops as passes; tris: the mesh's n list-order records in HBM):
+//   ls_grid_entries     ebox[5 k ..] = triangle k's entry box; ruv (zeroed by the caller, or null): the bits of Ru and Rv
+//   ls_grid_count       sums[a] (zeroed by the caller) += the cells every entry covers under candidate a of build_grid's attempt loop
+//   ls_grid_cell_counts counts[cell] (zeroed) = entries of the cell under the chosen candidate; *max_count (zeroed, or null) = the fullest cell's
+//   ls_grid_scan        first = exclusive scan of counts (tmp = null: *tmp_bytes receives the scratch size needed)
+//   ls_grid_emit        the grid itself: cell words at ls_nodes[at ..], entry boxes behind them, the entries' records at ls_tris[9 tri_at ..];
+//                       cursor: n_u x n_v zeroed words, idx: n_entries words of scratch.  Entries of a cell sorted by (w_max descending, list
+//                       index ascending), so two builds of the same input are byte-identical whatever order the atomics arrive in.
+struct LsGridCandidates { int n; float s[8]; uint32_t nu[8], nv[8]; };
+void ls_grid_entries(hipStream_t stream, const double* tris, uint32_t n, const LsFrame& F, float* ebox, uint32_t* ruv);
+void ls_grid_count(hipStream_t stream, const float* ebox, uint32_t n, const LsGridCandidates& C, unsigned long long* sums);
+void ls_grid_cell_counts(hipStream_t stream, const float* ebox, uint32_t n, float s, uint32_t nu, uint32_t nv, uint32_t* counts, uint32_t* max_count);
+hipError_t ls_grid_scan(hipStream_t stream, const uint32_t* counts, uint32_t* first, uint32_t n_cells, void* tmp, size_t* tmp_bytes);
+void ls_grid_emit(hipStream_t stream, const float* ebox, const double* tris, uint32_t n, float s, uint32_t nu, uint32_t nv, const uint32_t* counts, const uint32_t* first,
+                  uint32_t* cursor, uint32_t* idx, uint32_t n_entries, uint32_t* ls_nodes, uint32_t at, double* ls_tris, uint32_t tri_at);
+
 // Per-pixel surface buffers (ft_render_aov): for every entry of the chunk's pixel list (gen: pix_base, n_pix; one sample plane) the
 // closest hit of the geometry ray of sample `sample` - primary_ray_from exactly as k_primary calls it, then slightOffset - and what
 // the shaders would see there.  Planes are struct-of-arrays by list position: out.<x>[i] for entry pix_base + i, the 3-vectors as

@@ -1094,6 +1094,35 @@ bool build_grid(FlatScene& out, const LsBuilder& B, uint64_t& bytes, double* rec
 
 } // namespace
 
+// The frame of a (mesh leaf, directional light) pair (ft_flat.h, kLsPairDoubles) and its k_rel; false where the direction is zero, not
+// finite or ill-conditioned in the leaf's model space: such a pair has no tree.
+bool ls_pair_frame(const ftd::Leaf& L, const ftd::Light& light, LsPairFrame& out) {
+    // the model-space direction exactly as to_model computes it (ft_kernels.hip), d = -light.v (light_visibility)
+    const double d[3] = {-light.v[0], -light.v[1], -light.v[2]};
+    const double* M = L.w2m;
+    double dm[3], dabs[3];
+    if (L.flags & ftd::LF_XFORM) {
+        for (int r = 0; r < 3; ++r) { dm[r] = M[4 * r] * d[0] + M[4 * r + 1] * d[1] + M[4 * r + 2] * d[2]; dabs[r] = std::fabs(M[4 * r] * d[0]) + std::fabs(M[4 * r + 1] * d[1]) + std::fabs(M[4 * r + 2] * d[2]); }
+    } else for (int r = 0; r < 3; ++r) { dm[r] = d[r]; dabs[r] = std::fabs(d[r]); }
+    const double len = std::sqrt(dm[0] * dm[0] + dm[1] * dm[1] + dm[2] * dm[2]);
+    const double lab = std::sqrt(dabs[0] * dabs[0] + dabs[1] * dabs[1] + dabs[2] * dabs[2]);
+    if (!(len > 1e-150) || !(len < 1e150) || !std::isfinite(lab)) return false; // zero or non-finite: such rays keep today's walk
+    // angle between this dm and the device's (fused or not, each component within a few ulp of |M||d|), plus the frame's own rounding
+    const double k_rel = 1e-6 + 64.0 * 1.1102230246251565e-16 * lab / len;
+    if (!(k_rel < 1e-3)) return false;                                     // ill-conditioned: boxes would be loose, keep today's walk
+    double* U = out.U; double* V = out.V; double* D = out.D;
+    for (int q = 0; q < 3; ++q) D[q] = dm[q] / len;
+    int a = 0;                                                          // the axis least aligned with D: the frame stays orthonormal for any D
+    for (int q = 1; q < 3; ++q) if (std::fabs(D[q]) < std::fabs(D[a])) a = q;
+    const double e[3] = {a == 0 ? 1.0 : 0.0, a == 1 ? 1.0 : 0.0, a == 2 ? 1.0 : 0.0};
+    U[0] = D[1] * e[2] - D[2] * e[1]; U[1] = D[2] * e[0] - D[0] * e[2]; U[2] = D[0] * e[1] - D[1] * e[0];
+    const double lu = std::sqrt(U[0] * U[0] + U[1] * U[1] + U[2] * U[2]);
+    for (int q = 0; q < 3; ++q) U[q] /= lu;
+    V[0] = D[1] * U[2] - D[2] * U[1]; V[1] = D[2] * U[0] - D[0] * U[2]; V[2] = D[0] * U[1] - D[1] * U[0];
+    out.k_rel = k_rel;
+    return true;
+}
+
 void build_light_space(FlatScene& out, bool grids) {
     for (auto& L : out.leaves) L.ls_pairs = ~0u;
     out.ls_pairs.clear(); out.ls_nodes.clear(); out.ls_tris.clear();
@@ -1119,27 +1148,9 @@ void build_light_space(FlatScene& out, bool grids) {
             if (n_pairs >= ftd::kLsMaxPairs) break;
             const uint64_t need = (uint64_t)src.n_tris * 72 + (uint64_t)src.n_tris * ftd::kLsNodeWords * 4;   // records + at most n / 2 nodes, with room
             if (bytes + need > ftd::kLsMaxBytes) continue;
-            // the model-space direction exactly as to_model computes it (ft_kernels.hip), d = -light.v (light_visibility)
-            const double d[3] = {-out.lights[l].v[0], -out.lights[l].v[1], -out.lights[l].v[2]};
-            const double* M = L.w2m;
-            double dm[3], dabs[3];
-            if (L.flags & ftd::LF_XFORM) {
-                for (int r = 0; r < 3; ++r) { dm[r] = M[4 * r] * d[0] + M[4 * r + 1] * d[1] + M[4 * r + 2] * d[2]; dabs[r] = std::fabs(M[4 * r] * d[0]) + std::fabs(M[4 * r + 1] * d[1]) + std::fabs(M[4 * r + 2] * d[2]); }
-            } else for (int r = 0; r < 3; ++r) { dm[r] = d[r]; dabs[r] = std::fabs(d[r]); }
-            const double len = std::sqrt(dm[0] * dm[0] + dm[1] * dm[1] + dm[2] * dm[2]);
-            const double lab = std::sqrt(dabs[0] * dabs[0] + dabs[1] * dabs[1] + dabs[2] * dabs[2]);
-            if (!(len > 1e-150) || !(len < 1e150) || !std::isfinite(lab)) continue; // zero or non-finite: such rays keep today's walk
-            // angle between this dm and the device's (fused or not, each component within a few ulp of |M||d|), plus the frame's own rounding
-            const double k_rel = 1e-6 + 64.0 * 1.1102230246251565e-16 * lab / len;
-            if (!(k_rel < 1e-3)) continue;                                     // ill-conditioned: boxes would be loose, keep today's walk
-            double D[3] = {dm[0] / len, dm[1] / len, dm[2] / len}, U[3], V[3];
-            int a = 0;                                                          // the axis least aligned with D: the frame stays orthonormal for any D
-            for (int q = 1; q < 3; ++q) if (std::fabs(D[q]) < std::fabs(D[a])) a = q;
-            const double e[3] = {a == 0 ? 1.0 : 0.0, a == 1 ? 1.0 : 0.0, a == 2 ? 1.0 : 0.0};
-            U[0] = D[1] * e[2] - D[2] * e[1]; U[1] = D[2] * e[0] - D[0] * e[2]; U[2] = D[0] * e[1] - D[1] * e[0];
-            const double lu = std::sqrt(U[0] * U[0] + U[1] * U[1] + U[2] * U[2]);
-            for (double& x : U) x /= lu;
-            V[0] = D[1] * U[2] - D[2] * U[1]; V[1] = D[2] * U[0] - D[0] * U[2]; V[2] = D[0] * U[1] - D[1] * U[0];
+            LsPairFrame frame;
+            if (!ls_pair_frame(L, out.lights[l], frame)) continue;   // zero, non-finite or ill-conditioned: such rays keep today's walk
+            const double *U = frame.U, *V = frame.V, *D = frame.D, k_rel = frame.k_rel;
             const double* mb = &out.mesh_bounds[6 * (size_t)L.mesh];
             const double c[3] = {0.5 * (mb[0] + mb[3]), 0.5 * (mb[1] + mb[4]), 0.5 * (mb[2] + mb[5])};
             LsBuilder B{out};

@@ -121,6 +121,9 @@ int32_t build_bsp(const double* tris_abc, int64_t n_tris, int32_t depth, FlatSce
 // The light-space shadow trees of every (top-level-Leaf mesh leaf with a BVH, directional light) pair of a flattened scene (ft_flat.h),
 // and with `grids` each pair's grid as well.
 void build_light_space(FlatScene& out, bool grids);
+// What build_light_space derives from a leaf's w2m and a light's direction alone, for ft_scene_commit_lights to derive again.
+struct LsPairFrame { double U[3], V[3], D[3], k_rel; };
+bool ls_pair_frame(const ftd::Leaf& L, const ftd::Light& light, LsPairFrame& out);
 
 // Triangle.slice (Triangle.fs:24-41) exposed for the known-answer tests of the product's own builder.
 int32_t slice_triangle(const double p0[3], const double n[3], const double tri[9],

@@ -617,7 +617,7 @@ int32_t ft_temporal_wait(ft_context* ctx, ft_stats* stats);
  * What follows a leaf is its history, not its shading: light that changes on a moving surface (it turns towards a light, a shadow
  * sweeps over it) is averaged as noise is, max_history bounding how long it lingers - unless the neighbourhood clamp is on
  * (ft_temporal_set_clamp, clause 3a of ft_temporal_accumulate), which pulls such history to the colours the current frame shows
- * around the pixel and shortens it.  Lights do not move; meshes deform through
+ * around the pixel and shortens it.  Lights move through ft_scene_commit_lights ("moving lights" below); meshes deform through
  * ft_scene_commit_deformed (below), whose history follows the triangles with "temporal_follow_deformed" ("history on deforming meshes").
  * ft_temporal_filter with `demodulate` returns FT_ERR_STATE between an ft_scene_commit_moved and the next ft_temporal_accumulate (its
  * guide pass would show another pose than the set); without `demodulate` it runs as before.
@@ -688,6 +688,66 @@ int32_t ft_scene_commit_moved(ft_context* ctx);
 int32_t ft_sg_set_mesh_triangles(ft_context* ctx, ft_node node, const double* tris, int64_t n_tris);
 int32_t ft_scene_commit_deformed(ft_context* ctx);
 int32_t ft_scene_tree_quality(ft_context* ctx, ft_node mesh_node, double out[4]);
+/* ---- moving lights ----------------------------------------------------------------------------- */
+/* ft_scene_set_directional / _soft_directional / _positional + ft_scene_commit_lights change the lights of a committed scene without a
+ * flatten, without a BVH build and without ending ft_temporal_*.
+ * The setters replace the values of the light with index `light` (the order of the ft_scene_add_* calls) with the arithmetic of the
+ * ft_scene_add_* of its kind: directions are normalised as there, everything else is copied.  FT_ERR_INVALID, with nothing changed, for
+ * a null context or pointer, an index out of range or a light of another kind.  The kind of a light and a soft light's sample count
+ * cannot be set: they decide the kernel variant, the shadow rays per hit and the byte packing, and changing them stays a structural
+ * change (ft_scene_clear / ft_scene_add_*).  Like ft_sg_set_transform a setter leaves the scene uncommitted and is not a structural
+ * change; a later plain ft_scene_commit or ft_scene_commit_moved gives what a fresh graph with the new lights gives.
+ * ft_scene_commit_lights commits a graph in which only light values changed since the last successful commit:
+ *  - FT_ERR_STATE, and nothing done, unless the context holds a successful commit and no structural change was made since (the rule of
+ *    ft_scene_commit_moved), or while an ft_sg_set_transform is pending (ft_scene_commit_moved first), an ft_sg_set_mesh_triangles is
+ *    pending (ft_scene_commit_deformed first) or an ft_set_option that needs a new ft_scene_commit.  ft_scene_commit_deformed in turn
+ *    returns FT_ERR_STATE while a light setter is pending (ft_scene_commit_lights first).
+ *  - On success every later call - ft_render*, the queued forms, ft_progressive_*, ft_render_aov, ft_denoise, ft_temporal_*, the
+ *    ft_debug_* ray queries - gives what it gives on a fresh context whose graph was built with the new lights and committed with
+ *    ft_scene_commit, bit for bit, frames and counters.
+ *  - It ends a progressive accumulation, retires queued frames first (a frame queued before the call shows the old lights), leaves the
+ *    temporal accumulation OPEN and does not advance the pose counter.  On a multi-device context every device rewrites its own copy.
+ *    A host-only context checks the same rules and then runs the full host commit.
+ *  - ft_get_commit_times: [0] host work, [1] the refit and grid kernels with their readbacks, [2] uploads, [3] unchanged.  On a multi-device
+ *    context the first device takes the decisions that need a readback (a grid's resolution, "no grid"); all devices carry them out.
+ * "light_space_shadows" 1 / 2: for every (mesh leaf, directional light) pair that had a tree at the last full commit and whose direction
+ * changed, the pair record (frame, slack) is derived again on the host with the full commit's arithmetic (one rule is stricter: where the
+ * full commit tests that the projected bounds are finite, this call requires the mesh's extent about its centre, R, below 2e29, which
+ * implies it; a pair with R from 2e29 on gets no tree here and its rays walk the BVH - the same bits), and on the device
+ * (ft_lightspace.hip) the tree is refit - its topology and leaf records stay, every box is projected again into the new frame in FP64 and
+ * rounded outward - and, with option 2, the grid is built again by the full commit's rules (the same entry boxes, attempt loop, cell
+ * function, caps and order within a cell; two builds of the same input are byte-identical).  Any structure that holds every triangle in
+ * conservative boxes gives the BVH walk's bits, hence the bit-identity above.  Only a direction that changes touches a pair: colours and the
+ * other kinds of light are an upload alone.  A direction that is zero, not finite or ill-conditioned in the leaf's model space gets root
+ * INT32_MIN and no grid (its rays walk the BVH) until a later call gives it a usable direction again; a pair that had no tree at the last
+ * full commit, and the pairs ft_scene_commit_deformed stripped, stay without one until the next full commit; a light back at the direction
+ * of the last full commit gets that commit's record and grid back.  The grids built since the full commit lie behind that commit's
+ * arrays in freshly sized arrays that every call which turns a light lays out anew, so repeated calls do not grow memory; the bytes the
+ * cap (256 MiB) counts include the full commit's arrays whole.  Once a call has rewritten anything ft_debug_light_space answers from device
+ * memory.
+ * Cost: a call in which no direction changes is two uploads.  A call that turns ANY light refits the trees of the pairs that turned and
+ * builds the grid of EVERY pair whose direction is not the last full commit's, the ones that did not turn in this call included: the
+ * region behind the commit's arrays is laid out anew as a whole, so that no grid is moved.  With several directional lights or mesh
+ * leaves the cost therefore grows with the pairs that have turned since the full commit, not with the ones that turn now; the figures
+ * below are for one light over one mesh.
+ * Tree quality: the refit tree is the OLD direction's tree in the new frame - its leaves hold triangles that were neighbours in the old
+ * projection - so its rectangles overlap more the further the light has turned from the direction of the last full commit, and the waves
+ * the grid hands to the tree (those that cover more than four cells) slow down while the results stay exact.  Measured on a 69.6 K-face
+ * mesh at 1920 x 1080 x 16: k_primary after a turn of 1 degree costs what a full commit's costs, 10 degrees 1.41 x (1.10 x
+ * option 0), 45 degrees 6.7 x, 90 degrees 15 x, 180 degrees 1.46 x.  From about 10 degrees of accumulated turn on, a host that
+ * renders many frames under the new direction should pay for a full ft_scene_commit (75 - 85 ms there, against 2 ms for this call), which
+ * builds a fresh tree; the library does not decide this by itself.
+ * What follows a surface is its history, not its shading: light that moves over a surface is averaged by ft_temporal_accumulate as noise
+ * is, max_history bounding how long it lingers - unless the neighbourhood clamp is on (ft_temporal_set_clamp), which pulls such history
+ * to the colours the current frame shows around the pixel and shortens it.
+ * A host that never calls these functions gets bit-identical results from everything else.
+ * Device memory: 4 bytes per 4-wide node of the trees that can be refit, the grids built since the full commit, and while a call runs
+ * 20 bytes per triangle and 4 per cell of every pair whose grid is built (kept from call to call) and 8 per cell and 4 per entry of the
+ * largest grid. */
+int32_t ft_scene_set_directional(ft_context* ctx, int32_t light, const double dir[3], const double colour[3]);
+int32_t ft_scene_set_soft_directional(ft_context* ctx, int32_t light, const double dir[3], double scatter_rad, const double colour[3]);
+int32_t ft_scene_set_positional(ft_context* ctx, int32_t light, const double pos[3], const double falloff[3], const double colour[3]);
+int32_t ft_scene_commit_lights(ft_context* ctx);
 /* ---- history on deforming meshes ("temporal_follow_deformed") ----------------------------------- */
 /* Without the option the history of a deformed mesh survives only where its surface stayed within clause 2's position tolerance.  With
  * ft_set_option("temporal_follow_deformed", 1) the history follows the triangles, as it follows moved leaves:
