@@ -724,6 +724,19 @@ class Context(SceneBuilder):
         self._check(fn(self._ctx, sizes, plane.ctypes.data, heads.ctypes.data, pos_block.ctypes.data, entries.ctypes.data))
         return {"leaf": int(sizes[2]), "heads": heads, "pos_block": pos_block, "entries": entries, "plane": plane, "capacity": int(sizes[3])}
 
+    def edge_records(self):
+        """ft_debug_edge_records: the edge records of option "edge_cull" as they lie in device memory - a dict of `grid` (n x 3 x 3 floats,
+        one record per triangle record ft_debug_light_space hands out, under the same index; empty where the scene carries none) and `lists`
+        (one per entry of block_lists()["entries"]).  A record is three lines (a, b, c), a x + b y + c <= 0 inside; zeros: no edges."""
+        sizes = (C.c_int64 * 2)()
+        fn = self._lib.ft_debug_edge_records
+        fn.restype, fn.argtypes = C.c_int32, [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p]
+        self._check(fn(self._ctx, sizes, None, None))
+        grid = np.zeros((sizes[0],) + _capi.EDGE_RECORD_SHAPE, dtype=np.float32)
+        lists = np.zeros((sizes[1],) + _capi.EDGE_RECORD_SHAPE, dtype=np.float32)
+        self._check(fn(self._ctx, sizes, grid.ctypes.data, lists.ctypes.data))
+        return {"grid": grid[:sizes[0]], "lists": lists[:sizes[1]]}
+
     def classify_reuse(self):
         """ft_debug_classify_reuse: what the frames queued since the context was created did with their classifications (option
         "classify_reuse"), summed over its devices - a dict of `classified` (k_classify launched), `reused` (a slot's kept classification

@@ -185,6 +185,8 @@ CLASSIFY_REUSE_FIELDS = ("classified", "reused", "windows_launched", "windows_sk
 # ft_debug_block_lists: an entry of a block's candidate list (ft_device.h, kListEntryWords) and the header of a block that has none
 LIST_ENTRY_DTYPE = np.dtype([("tri", np.uint32), ("orig", np.uint32), ("x0", np.float32), ("x1", np.float32), ("y0", np.float32), ("y1", np.float32)])
 LIST_NONE = 0xFFFFFFFF
+# ft_debug_edge_records: a record is three lines (a, b, c) as floats (ft_device.h, kEdgeFloats)
+EDGE_RECORD_SHAPE = (3, 3)
 
 
 class fth_options(C.Structure):

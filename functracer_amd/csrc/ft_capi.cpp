@@ -192,6 +192,7 @@ const OptionSpec kOptions[] = {
     {"csg_auto_grow", 0, 1, &Options::csg_auto_grow, nullptr, kFlag},
     {"primary_block_lists", 0, 1, &Options::primary_block_lists, nullptr, kFlag | kClassified},
     {"uniform_surface", 0, 1, &Options::uniform_surface, nullptr, kFlag},
+    {"edge_cull", 0, 1, &Options::edge_cull, nullptr, kFlag},       // (read per frame; the records are written whatever it says: nothing kept depends on it)
     {"primary_mesh_kernel", 0, 1, &Options::primary_mesh_kernel, nullptr, kFlag},   // (no classification depends on it: the slots keep theirs)
     // read by ft_scene_commit_deformed and ft_temporal_accumulate: no commit depends on it either
     {"temporal_follow_deformed", 0, 1, &Options::temporal_follow_deformed, nullptr, kFlag},
@@ -217,6 +218,7 @@ int32_t ft_set_option(ft_context* c, const char* key, int64_t value) {
             for (hipStream_t m : d->more_mains) if (!m) d->opt.mains = 1;   // (without them every frame takes the one main stream)
             d->dev_scene.coherent_waves = d->opt.coherent_waves ? 1 : 0;
             d->dev_scene.uniform_surface = d->opt.uniform_surface ? 1 : 0;
+            d->dev_scene.ls_edges = d->opt.edge_cull ? d->lightspace.d_edges.as<float>() : nullptr;
             if (!d->opt.temporal_follow_deformed) temporal_drop_snapshots(d);   // (nothing to do unless the option has just gone back to 0)
             if (o.rules & kCommit) { d->committed = false; c->options_pending = true; }
             if (o.rules & kLevelHint) d->staged_hint = -1;
@@ -457,6 +459,41 @@ static void derive_launch_shape(ft_context* c) {
     c->blocks_primary_mesh = ftk::occupancy_blocks_primary_mesh();
 }
 
+// The edge records of every shadow grid of the scene as it lies in HBM (option "edge_cull"; ft_edges.h, k_ls_edges), after an upload or a
+// rebuild of the light-space arrays: pairs = the pair records as just uploaded (their grid words name the cell tables), node_words and
+// tri_doubles the sizes of ls_nodes and ls_tris there.  Zeros - the record that cuts nothing off - under every record no grid entry
+// points at.  No grid, or more records than kLsEdgeMaxBytes holds: no array, and the shadow queries go by the rectangles alone.
+static int32_t build_ls_edges(ft_context* c, const std::vector<double>& pairs, size_t node_words, size_t tri_doubles) {
+    ft_context::LightSpace& L = c->lightspace;
+    ftk::DevScene& S = c->dev_scene;
+    S.ls_edges = nullptr;
+    const size_t n_recs = tri_doubles / 9, bytes = n_recs * ftk::kEdgeFloats * sizeof(float);
+    bool grids = false;
+    for (size_t r = 0; r + 1 <= pairs.size() / ftd::kLsPairDoubles; ++r) {
+        uint32_t w[2];
+        std::memcpy(w, &pairs[ftd::kLsPairDoubles * r + 15], sizeof w);
+        grids = grids || w[1] != 0u;
+    }
+    if (!grids || n_recs == 0 || bytes > ftd::kLsEdgeMaxBytes || node_words > 0xFFFFFFFFull || n_recs > 0xFFFFFFFFull) { L.d_edges.release(); return FT_OK; }
+    int32_t rc;
+    if ((rc = ensure(c, L.d_edges, bytes)) != FT_OK) return rc;
+    FT_HIP(c, hipMemsetAsync(L.d_edges.p, 0, bytes, c->stream));
+    const DeviceBuf* B = c->d_scene;
+    for (size_t r = 0; r + 1 <= pairs.size() / ftd::kLsPairDoubles; ++r) {
+        uint32_t w[2];
+        std::memcpy(w, &pairs[ftd::kLsPairDoubles * r + 15], sizeof w);
+        int32_t root;
+        std::memcpy(&root, &pairs[ftd::kLsPairDoubles * r + 14], 4);
+        if (w[1] == 0u || root == INT32_MIN) continue;
+        ftk::ls_edge_records(c->stream, B[kLsPairs].as<double>() + ftd::kLsPairDoubles * r, B[kLsNodes].as<uint32_t>(), (uint32_t)node_words, B[kLsTris].as<double>(),
+                             (uint32_t)n_recs, (w[1] & 0xFFFFu) * (w[1] >> 16), L.d_edges.as<float>());
+    }
+    FT_HIP(c, hipGetLastError());
+    FT_HIP(c, hipStreamSynchronize(c->stream));
+    S.ls_edges = c->opt.edge_cull ? L.d_edges.as<float>() : nullptr;
+    return FT_OK;
+}
+
 static int32_t upload_scene(ft_context* c) {
     int32_t rc;
     FT_HIP(c, hipSetDevice(c->device));
@@ -504,6 +541,7 @@ static int32_t upload_scene(ft_context* c) {
             if ((rc = fit_stacks(c, tallest)) != FT_OK) return rc;
         }
     }
+    if ((rc = build_ls_edges(c, f.ls_pairs, f.ls_nodes.size(), f.ls_tris.size())) != FT_OK) return rc;
     derive_launch_shape(c);
     c->committed = true;
     ++c->commit_serial; c->staged_hint = -1;
@@ -985,6 +1023,10 @@ static int32_t relight_device(ft_context* c, fth::FlatScene& f, const ft_context
     if ((rc = upload(c, B[kLsPairs], f.ls_pairs)) != FT_OK) return rc;
     FT_HIP(c, hipStreamSynchronize(c->stream));
     ms[0] += since(t2);
+    // the edge records of the grids as they lie now: the rebuilt ones, and the full commit's under the frames the refit gave their pairs
+    const auto t3 = clock::now();
+    if (!jobs.empty() && (rc = build_ls_edges(c, f.ls_pairs, L.node_words, L.tri_doubles)) != FT_OK) return rc;   // (no job: no pair record and no array changed)
+    ms[1] += since(t3);
     c->zero_signature[0] = c->zero_signature[1] = 0;                // (as every commit)
     c->committed = true;
     ++c->commit_serial; c->staged_hint = -1;

@@ -99,6 +99,7 @@ struct Options {
     int64_t refit_rebuild_percent = 0;   // ft_scene_commit_deformed rebuilds a device-built tree in place once cost now x 100 > this x cost as built; 0: never (not a commit-time option)
     int64_t temporal_follow_deformed = 0;   // ft_scene_commit_deformed keeps a mesh's records as the history saw them and ft_temporal_accumulate follows them
     int64_t primary_mesh_kernel = 1;   // k_primary_mesh for the frames that qualify (ft_context::mesh_kernel_scene, queue_chunks); 0: k_primary everywhere (A/B)
+    int64_t edge_cull = 1;          // candidate-list and shadow-grid entries are also tested against their triangle's projected edges (ft_edges.h); 0: the rectangles alone (A/B)
     int64_t uniform_surface = 1;    // k_primary: one-leaf batches take leaf and material through scalar loads, dead shader work and empty-list batches are skipped; 0: per lane, everything (A/B)
 };
 
@@ -228,6 +229,7 @@ struct ft_context {
         // run (on `side`, behind an event) while the frame before it is still tracing: block_pos / pos_block and the frame's counters.
         DeviceBuf d_block_pos, d_pos_block, d_fc;
         DeviceBuf d_list_heads, d_list_pool;    // k_block_lists: a header per active block, the entries (ftk::BlockLists)
+        DeviceBuf d_list_edges;                 // the entries' edge records, kEdgeFloats floats under the same index: as large in entries, kept and reused as the pool
         int32_t list_leaf = -1;                 // the mesh leaf this slot's frame carries lists for; -1: none
         ftk::Camera list_cam{};                 // that frame's image plane (ft_debug_block_lists)
         // "classify_reuse": what d_block_pos, d_pos_block, the lists and SlotCounters::kept hold.  `valid` from the retirement, without
@@ -247,7 +249,7 @@ struct ft_context {
         uint64_t rays_primary = 0; int64_t n_pix_total = 0; int32_t spp = 0, n_launches = 0, n_chunks = 0, format = 0; bool classify = false;   // (n_launches, n_chunks: as planned from the request, FramePlan::n_planned)
         std::chrono::steady_clock::time_point wall0;
         void release() {
-            d_block_pos.release(); d_pos_block.release(); d_fc.release(); d_list_heads.release(); d_list_pool.release();
+            d_block_pos.release(); d_pos_block.release(); d_fc.release(); d_list_heads.release(); d_list_pool.release(); d_list_edges.release();
             if (h_report) (void)hipHostFree(h_report);
             h_report = nullptr; d_report = nullptr;
             ev.release();
@@ -280,12 +282,16 @@ struct ft_context {
         size_t base_node_words = 0, base_tri_doubles = 0;
         bool ready = false;
         DeviceBuf d_order, d_first, d_cursor, d_idx, d_small, d_scan;
+        // Option "edge_cull": the edge records of the grids' entries (ft_edges.h), one per record of ls_tris as it lies in HBM now, written
+        // by k_ls_edges after every upload of the light-space arrays and at the end of every ft_scene_commit_lights; empty where the scene
+        // has no grid or the records would pass kLsEdgeMaxBytes (the shadow queries then go by the rectangles alone).
+        DeviceBuf d_edges;
         std::vector<DeviceBuf> d_ebox, d_counts;   // per pair whose grid a call builds: its entry boxes and cell counts, from the pass that decides the grid to the one that writes it
         size_t node_words = 0, tri_doubles = 0;
         bool order_uploaded = false, rewritten = false;
         void reset() { pairs.clear(); order.clear(); ready = order_uploaded = rewritten = false; node_words = tri_doubles = base_node_words = base_tri_doubles = 0; }
         void release() {
-            for (DeviceBuf* b : {&d_order, &d_first, &d_cursor, &d_idx, &d_small, &d_scan}) b->release();
+            for (DeviceBuf* b : {&d_order, &d_first, &d_cursor, &d_idx, &d_small, &d_scan, &d_edges}) b->release();
             for (DeviceBuf& b : d_ebox) b.release();
             for (DeviceBuf& b : d_counts) b.release();
             d_ebox.clear(); d_counts.clear(); reset();

@@ -254,6 +254,36 @@ int32_t ft_debug_block_lists(ft_context* c, int64_t sizes[4], double plane[4], u
     return FT_OK;
 }
 
+// The edge records (ft_edges.h) beside the arrays ft_debug_light_space and ft_debug_block_lists hand out, under the same indices.
+int32_t ft_debug_edge_records(ft_context* c, int64_t sizes[2], float* grid_edges, float* list_edges) {
+    if (!c || !sizes) return FT_ERR_INVALID;
+    if (c->host_only) return FT_ERR_NO_DEVICE;
+    sizes[0] = sizes[1] = 0;
+    FT_HIP(c, hipSetDevice(c->device));
+    int32_t rc = retire_queued(c);
+    if (rc != FT_OK) return rc;
+    if ((rc = drain_frame_streams(c)) != FT_OK) return rc;
+    const size_t rec_bytes = ftk::kEdgeFloats * sizeof(float);
+    if (c->committed && c->lightspace.d_edges.p) {
+        const size_t n_recs = (c->lightspace.rewritten ? c->lightspace.tri_doubles : c->flat.ls_tris.size()) / 9;
+        if (c->lightspace.d_edges.bytes < n_recs * rec_bytes) { c->err = "ft_debug_edge_records: the edge array in device memory is smaller than recorded"; return FT_ERR_STATE; }
+        sizes[0] = (int64_t)n_recs;
+        if (grid_edges && n_recs) FT_HIP(c, hipMemcpy(grid_edges, c->lightspace.d_edges.p, n_recs * rec_bytes, hipMemcpyDeviceToHost));
+    }
+    if (c->last_classified_slot < 0) return FT_OK;
+    const ft_context::FrameSlot& F = c->slots[c->last_classified_slot];
+    if (F.list_leaf < 0 || !F.h_report) return FT_OK;
+    const size_t n_active = std::min<size_t>(F.h_report->n_pix_active / 64u, F.d_list_heads.bytes / 4);
+    std::vector<uint32_t> h(n_active);
+    if (n_active) FT_HIP(c, hipMemcpy(h.data(), F.d_list_heads.p, n_active * 4, hipMemcpyDeviceToHost));
+    size_t used = 0;
+    for (uint32_t v : h) if (v != ftk::kListNone) used = std::max<size_t>(used, (size_t)(v >> 7) + (v & 127u));
+    if (used * rec_bytes > F.d_list_edges.bytes) { c->err = "ft_debug_edge_records: a header points past the edge pool"; return FT_ERR_STATE; }
+    sizes[1] = (int64_t)used;
+    if (list_edges && used) FT_HIP(c, hipMemcpy(list_edges, F.d_list_edges.p, used * rec_bytes, hipMemcpyDeviceToHost));
+    return FT_OK;
+}
+
 // What the frame driver did with the classifications and windows of the frames queued since ft_create, summed over the context's devices.
 int32_t ft_debug_classify_reuse(ft_context* c, int64_t out[4]) {
     if (!c || !out) return FT_ERR_INVALID;

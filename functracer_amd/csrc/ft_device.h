@@ -36,6 +36,8 @@ struct DevScene {
     const float* coarse_boxes;     // 6 floats per box: model-space boxes that cover a mesh (k_classify)
     const uint32_t* item_pc;       // n_items + 1 program counters: where each top-level item starts (last: the OP_END word)
     const double* cull_rows;       // 3 per distinct parallel-sensitive direction
+    const float* ls_edges;         // option "edge_cull": kEdgeFloats floats per record of ls_tris, the edge records of the shadow grids' entries (ft_edges.h,
+                                   // k_ls_edges; zeros for every other record), or null: the option is 0, or the scene has no grid
     int32_t n_leaves, n_lights, csg_cap, stack_cap;
     int32_t shadow_rays_per_hit;   // sum over lights of the shadow rays the reference casts per hit
     int32_t n_items, n_cull_rows;  // n_cull_rows < 0: pre-test disabled
@@ -135,6 +137,7 @@ struct Primary {
     // The frame's per-block triangle candidate lists (k_block_lists), or null: one header per block of the ACTIVE list and the pool
     // their entries lie in; list_leaf is the bare mesh leaf they are for.
     const uint32_t* list_heads; const uint32_t* list_pool; int32_t list_leaf;
+    const float* list_edges;       // option "edge_cull": kEdgeFloats floats per entry of list_pool (BlockLists::edges), or null
 };
 // Bounce 0 fused (k_primary): generate the primary rays of the chunk, closest hit, shadow queries, shaders, reflection spawn, and
 // one colour per sample stored into acc (Colour.Zero for a miss).
@@ -166,8 +169,9 @@ void launch_classify(const Launch& L, const DevScene& S, const Primary& gen_list
 // is full, or the pyramid is degenerate: the block's rays walk the tree) or first entry << 7 | count.  An entry is kListEntryWords
 // words: the triangle's record in DevScene::tris, its list index (tri_orig), and the rectangle x0, x1, y0, y1 as floats, rounded outward,
 // in the (jx, jy) coordinates of the primary rays.  fc->list_cursor hands out the pool; `counts`: the length of the active list (ClassifyOut::kept).
-constexpr uint32_t kListNone = 0xFFFFFFFFu, kListCap = 64, kListEntryWords = 6;
-struct BlockLists { uint32_t* heads; uint32_t* pool; uint32_t pool_entries; int32_t leaf; };
+// edges: a second pool under the same entry index, kEdgeFloats floats per entry, the entry's edge record (ft_edges.h), or null.
+constexpr uint32_t kListNone = 0xFFFFFFFFu, kListCap = 64, kListEntryWords = 6, kEdgeFloats = 9;
+struct BlockLists { uint32_t* heads; uint32_t* pool; uint32_t pool_entries; int32_t leaf; float* edges; };
 void launch_block_lists(const Launch& L, const DevScene& S, const Primary& gen_list, const uint32_t* pos_block, const BlockLists& out, double jitter_extent, FrameCounters* fc, const PixCount* counts);
 // The frame's pixels: mean over the spp samples of each pixel of the chunk's window, in sample order (Image.fs:112-116), written as
 // FP64 RGB (out_rgb) and / or as Image.write's RGBA8 bytes (out_rgba, Image.fs:36); with `zero_culled` also Colour.Zero for every
@@ -268,6 +272,11 @@ void ls_grid_cell_counts(hipStream_t stream, const float* ebox, uint32_t n, floa
 hipError_t ls_grid_scan(hipStream_t stream, const uint32_t* counts, uint32_t* first, uint32_t n_cells, void* tmp, size_t* tmp_bytes);
 void ls_grid_emit(hipStream_t stream, const float* ebox, const double* tris, uint32_t n, float s, uint32_t nu, uint32_t nv, const uint32_t* counts, const uint32_t* first,
                   uint32_t* cursor, uint32_t* idx, uint32_t n_entries, uint32_t* ls_nodes, uint32_t at, double* ls_tris, uint32_t tri_at);
+// The edge records of one pair's grid (k_ls_edges; option "edge_cull"): `pair`, the pair's record in HBM, names the frame and the cell
+// table; one wave per cell, one lane per entry, edges[kEdgeFloats * r ..] for the entry's record r of ls_tris.  node_words, n_recs: the
+// sizes of ls_nodes and of ls_tris (and so of edges): nothing beyond them is read or written.  No host twin: it runs after every upload
+// or rebuild of the arrays, on every device.
+void ls_edge_records(hipStream_t stream, const double* pair, const uint32_t* ls_nodes, uint32_t node_words, const double* ls_tris, uint32_t n_recs, uint32_t n_cells, float* edges);
 
 // Per-pixel surface buffers (ft_render_aov): for every entry of the chunk's pixel list (gen: pix_base, n_pix; one sample plane) the
 // closest hit of the geometry ray of sample `sample` - primary_ray_from exactly as k_primary calls it, then slightOffset - and what

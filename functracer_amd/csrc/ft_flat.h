@@ -127,6 +127,7 @@ constexpr int kLsNodeWords = 24;
 constexpr uint32_t kLsMaxPairs = 64;
 constexpr uint32_t kLsMaxTris = 1u << 20;
 constexpr uint64_t kLsMaxBytes = 256ull << 20;
+constexpr uint64_t kLsEdgeMaxBytes = 128ull << 20;   // of edge records (ft_edges.h: 36 bytes per 72-byte record of ls_tris, so kLsMaxBytes implies it); beyond it, none
 constexpr uint32_t kLsGridEntriesPerTri = 16;
 constexpr uint32_t kLsGridMaxCell = 256;
 constexpr uint32_t kLsGridWaveCells = 4;

@@ -381,7 +381,8 @@ static int32_t queue_classify(ft_context* c, const RenderRequest& q, const Frame
     if (!c->classified) FT_HIP(c, hipEventCreateWithFlags(&c->classified, hipEventDisableTiming));
     else FT_HIP(c, hipStreamWaitEvent(cs, c->classified, 0));  // one classification at a time, whichever streams they are on
     // the block lists right behind the classification, on its stream and inside its event: they ride beside the predecessors' tracing too
-    const ftk::BlockLists lists{F.d_list_heads.as<uint32_t>(), F.d_list_pool.as<uint32_t>(), (uint32_t)(F.d_list_pool.bytes / (ftk::kListEntryWords * 4)), p.list_leaf};
+    const ftk::BlockLists lists{F.d_list_heads.as<uint32_t>(), F.d_list_pool.as<uint32_t>(), (uint32_t)(F.d_list_pool.bytes / (ftk::kListEntryWords * 4)), p.list_leaf,
+                                F.d_list_edges.bytes / (ftk::kEdgeFloats * 4) >= F.d_list_pool.bytes / (ftk::kListEntryWords * 4) ? F.d_list_edges.as<float>() : nullptr};   // (written whatever "edge_cull" says: a later frame may reuse the lists with it on)
     auto queue_lists = [&] { if (p.list_leaf >= 0) ftk::launch_block_lists(Lg, c->dev_scene, all, cls.pos_block, lists, p.jitter_extent, fc, kept); };
     if (ahead) {
         ftk::launch_classify(Lg, c->dev_scene, all, cls, p.jitter_extent, epoch, fc, retired, p.mask_only);
@@ -424,7 +425,9 @@ static int32_t queue_chunks(ft_context* c, const RenderRequest& q, const FramePl
         ftk::Primary gen{p.cam, c->d_pixels.as<uint32_t>(), c->d_jitter.as<double>(), job.id_base, n_pix, p.spp, stride, (unsigned long long)q.seed,
                          1.0 / (double)n_pix, 1.0 / (double)stride, nullptr, nullptr};
         if (p.classify) { gen.counts = kept; gen.block_map = F.d_pos_block.as<uint32_t>(); }   // pix_base = job.id_base: the window's start in the active list
-        if (p.list_leaf >= 0) { gen.list_heads = F.d_list_heads.as<uint32_t>(); gen.list_pool = F.d_list_pool.as<uint32_t>(); gen.list_leaf = p.list_leaf; }
+        if (p.list_leaf >= 0) { gen.list_heads = F.d_list_heads.as<uint32_t>(); gen.list_pool = F.d_list_pool.as<uint32_t>(); gen.list_leaf = p.list_leaf;
+                                 // (the edge pool is sized with the entry pool and written by the k_block_lists that wrote that one)
+                                 gen.list_edges = c->opt.edge_cull && F.d_list_edges.bytes / (ftk::kEdgeFloats * 4) >= F.d_list_pool.bytes / (ftk::kListEntryWords * 4) ? F.d_list_edges.as<float>() : nullptr; }
         gen.group_log2 = (n_pix % 64u == 0u) ? p.group_log2 : 0;
         const int at = c->acc_turn;
         double* const acc = c->d_acc[at].as<double>();
@@ -509,6 +512,7 @@ static int32_t queue_frame(ft_context* c, const RenderRequest& q, const FramePla
             // average under ten): blocks that find it full walk the tree
             if ((rc = ensure(c, F.d_list_heads, n_blocks * 4)) != FT_OK) return rc;
             if ((rc = ensure(c, F.d_list_pool, (16 * n_blocks + 4096) * ftk::kListEntryWords * 4)) != FT_OK) return rc;
+            if ((rc = ensure(c, F.d_list_edges, F.d_list_pool.bytes / (ftk::kListEntryWords * 4) * ftk::kEdgeFloats * 4)) != FT_OK) return rc;
         }
         F.list_leaf = p.list_leaf; F.list_cam = p.cam;
         c->last_classified_slot = turn;

@@ -41,6 +41,7 @@
 #include <stdint.h>
 
 #include "ft_device.h"
+#include "ft_edges.h"
 #include "ft_filter.h"
 
 using namespace ftd;
@@ -105,6 +106,7 @@ struct Scene {
     cdp ls_pairs;     // 16 doubles per light-space shadow pair (ft_flat.h, kLsPairDoubles)
     cup ls_nodes;     // 24 words per light-space node
     cdp ls_tris;      // 9 doubles per triangle record the light-space trees point at
+    const float* ls_edges;       // lane e reads entry e's edge record (ft_edges.h), or null
     const uint8_t* tex_pixels;   // per-lane byte gathers: ordinary global loads
     const float* cull_items;     // lane k reads record k: ordinary global loads
     const float* coarse_boxes;   // lane k reads box k
@@ -121,7 +123,7 @@ template <class DS> FT_DEV Scene scene_view(const DS& g) {
     s.program = to_const_as(g.program); s.meshes = to_const_as(reinterpret_cast<const int32_t*>(g.meshes));
     s.nodes = to_const_as(reinterpret_cast<const double*>(g.nodes)); s.bsp_leaves = to_const_as(reinterpret_cast<const uint32_t*>(g.bsp_leaves));
     s.tris = to_const_as(g.tris); s.culls = to_const_as(g.culls); s.tri_orig = to_const_as(g.tri_orig); s.wide = to_const_as(g.wide); s.mesh_wide = to_const_as(g.mesh_wide);
-    s.ls_pairs = to_const_as(g.ls_pairs); s.ls_nodes = to_const_as(g.ls_nodes); s.ls_tris = to_const_as(g.ls_tris);
+    s.ls_pairs = to_const_as(g.ls_pairs); s.ls_nodes = to_const_as(g.ls_nodes); s.ls_tris = to_const_as(g.ls_tris); s.ls_edges = g.ls_edges;
     s.tex_pixels = g.tex_pixels; s.cull_items = g.cull_items; s.coarse_boxes = g.coarse_boxes; s.cull_rows = to_const_as(g.cull_rows); s.item_pc = to_const_as(g.item_pc); s.n_items = g.n_items; s.n_cull_rows = g.n_cull_rows;
     s.n_leaves = g.n_leaves; s.n_lights = g.n_lights; s.csg_cap = g.csg_cap; s.stack_cap = g.stack_cap; s.csg_rows = g.csg_rows; s.lane_fold = g.lane_fold; s.n_simd = g.n_simd;
     return s;
@@ -182,7 +184,8 @@ FT_DEV uint32_t lanes_below(unsigned long long mask) { return __builtin_amdgcn_m
 //                        surroundings); k = 0 queries, 1 items evaluated, 2 live lanes, 3 items the mask offered (before each item's own OP_CULL)
 //   [kClkSection + k]    FT_CLK_ADD, FT_CLK_INC: shader-clock cycles (s_memtime) waves spend in section k of the tracing kernels, or a count
 //                        FT_LIST_ADD: the list path of the closest queries, in unused halves of the closest kinds' clock pairs: k = 2 entries
-//                        offered, 3 entries past the rectangle test (every one of them is a triangle tested), 6 empty lists, 7 queries
+//                        offered, 3 entries past the wave's tests (every one of them is a triangle tested), 6 empty lists, 7 queries, 11 entries
+//                        the rectangle test keeps (3: what the edge test keeps of those); the shadow grids' entries likewise: 14 and 15
 //   [kClkWalk + k]       FT_WALK_ADD: the any-hit mesh walks of coherent waves: nodes visited, triangles tested, cycles spent in leaves, walks
 // -DFT_STAMPS: s_memrealtime (100 MHz) at the phases of every workgroup of k_classify, into the words behind wave_counts[4096].
 constexpr uint32_t kClkWaves = 8192, kClkWords = 48, kClkSection = 16, kClkWalk = kClkSection + 28;
@@ -1018,7 +1021,12 @@ FT_DEV void mesh_shadow_grid(const Scene& S, cdp P, const Ray& r, Query<true>& q
                 const uint32_t e = base + lane_id();
                 const FT_CONST float* eb = bx + 5u * min(e, count - 1u);
                 const float eu0 = eb[0], eu1 = eb[1], ev0 = eb[2], ev1 = eb[3], ew = eb[4];
-                unsigned long long m = __ballot((e < count) & (eu0 <= u_max) & (eu1 >= u_min) & (ev0 <= v_max) & (ev1 >= v_min) & (ew >= w_min));
+                const bool in_rect = (e < count) & (eu0 <= u_max) & (eu1 >= u_min) & (ev0 <= v_max) & (ev1 >= v_min) & (ew >= w_min);
+                // option "edge_cull": the wave's rectangle wholly outside one edge of the entry's triangle (ft_edges.h) - no lane can hit it
+                bool outside = false;
+                if (S.ls_edges) outside = edges_outside(S.ls_edges + (size_t)kEdgeFloats * (first + min(e, count - 1u)), u_min, u_max, v_min, v_max);
+                unsigned long long m = __ballot(in_rect && !outside);
+                FT_LIST_ADD(14, __popcll(__ballot(in_rect))); FT_LIST_ADD(15, __popcll(m));
                 while (m) {
                     const int k = (int)__builtin_ctzll(m);
                     m &= m - 1ull;
@@ -1045,7 +1053,7 @@ FT_DEV void mesh_shadow_grid(const Scene& S, cdp P, const Ray& r, Query<true>& q
 // go through tri_hit_wave in list order under the leaf loop's rule of mesh_bvh_packet: nearer, or as near with the lower list index.
 // That rule makes the result independent of the order and the route by which triangles are offered, and a list holds every triangle a
 // ray of the block can hit, so the hit is the walk's bit for bit.
-struct ListQuery { const uint32_t* pool; uint32_t head; uint32_t leaf; float x0, x1, y0, y1; };   // head = kListNone: the tree walk; x0 .. y1: the wave's rectangle, rounded outward
+struct ListQuery { const uint32_t* pool; uint32_t head; uint32_t leaf; float x0, x1, y0, y1; const float* edges; };   // head = kListNone: the tree walk; x0 .. y1: the wave's rectangle, rounded outward; edges: the entries' edge records or null
 FT_DEV void mesh_list_closest(const Scene& S, const ListQuery& Lq, const Ray& r, Query<false>& q, uint32_t leaf, bool lit) {
     const bool alive = q.active;
     const uint32_t count = Lq.head & 127u, first = Lq.head >> 7;
@@ -1054,8 +1062,12 @@ FT_DEV void mesh_list_closest(const Scene& S, const ListQuery& Lq, const Ray& r,
     const uint32_t* E = Lq.pool + (size_t)kListEntryWords * (first + min(lane_id(), count - 1u));
     const uint32_t tri_v = E[0], orig_v = E[1];
     const float ex0 = __uint_as_float(E[2]), ex1 = __uint_as_float(E[3]), ey0 = __uint_as_float(E[4]), ey1 = __uint_as_float(E[5]);
-    unsigned long long m = __ballot((lane_id() < count) & (ex0 <= Lq.x1) & (ex1 >= Lq.x0) & (ey0 <= Lq.y1) & (ey1 >= Lq.y0));
-    FT_LIST_ADD(3, __popcll(m));
+    const bool in_rect = (lane_id() < count) & (ex0 <= Lq.x1) & (ex1 >= Lq.x0) & (ey0 <= Lq.y1) & (ey1 >= Lq.y0);
+    // option "edge_cull": the wave's rectangle wholly outside one edge of the entry's triangle (ft_edges.h) - no lane can hit it
+    bool outside = false;
+    if (Lq.edges) outside = edges_outside(Lq.edges + (size_t)kEdgeFloats * (first + min(lane_id(), count - 1u)), Lq.x0, Lq.x1, Lq.y0, Lq.y1);
+    unsigned long long m = __ballot(in_rect && !outside);
+    FT_LIST_ADD(11, __popcll(__ballot(in_rect))); FT_LIST_ADD(3, __popcll(m));
     double reach = alive ? q.best_t : -__builtin_inf();
     uint32_t best_tri = 0xFFFFFFFFu;
     bool found = false;
@@ -1997,7 +2009,7 @@ __global__ __launch_bounds__(kBlock, BLOCKS) void k_primary(PrimaryArgs) {
             if (active && !empty) ro = offset_ray(primary_ray_from(&Kb->gen, at_of(bi).s, pid, jxy));
             if (MESH && lq.head != kListNone && !empty) {
                 wave_rect(lq, jxy, active);
-                lq.pool = Kb->gen.list_pool; lq.leaf = (uint32_t)Kb->gen.list_leaf;
+                lq.pool = Kb->gen.list_pool; lq.leaf = (uint32_t)Kb->gen.list_leaf; lq.edges = Kb->gen.list_edges;
             }
         }
         Query<false> q = Query<false>::closest(active);
@@ -2145,7 +2157,7 @@ __global__ __launch_bounds__(kBlock, BLOCKS) void k_primary_mesh(PrimaryArgs) {
             if (active && !empty) ro = offset_ray(primary_ray_from(&Kb->gen, slot_at(px, bi, lane_id()).s, pid, jxy));
             if (lq.head != kListNone && !empty) {
                 wave_rect(lq, jxy, active);
-                lq.pool = Kb->gen.list_pool;
+                lq.pool = Kb->gen.list_pool; lq.edges = Kb->gen.list_edges;
             }
         }
         // ---- closest hit: the block's candidate list, or the packet walk (no list for the block, or no lists in the frame)
@@ -2624,11 +2636,13 @@ FT_DEV float round_down(double x) { return (float)(x - (2.4e-7 * fabs(x) + 1e-37
 FT_DEV float round_up(double x) { return (float)(x + (2.4e-7 * fabs(x) + 1e-37)); }
 __global__ __launch_bounds__(kBlock) void k_block_lists(BlockListArgs) {
     __shared__ uint32_t sh_entries[kBlock / 64][kListCap * kListEntryWords];
+    __shared__ float sh_edges[kBlock / 64][kListCap * kEdgeFloats];   // the entries' edge records (ft_edges.h), under the same index
     const FT_CONST BlockListArgs* K = kernel_args<BlockListArgs>();
     const Scene S = scene_view(K->S);
     const PrimaryArg g = &K->gen;
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / 64u));
     uint32_t* mine = sh_entries[wave];
+    float* mine_edges = sh_edges[wave];
     const uint32_t n_active = to_const_as(K->counts)->n_pix / 64u;
     const uint32_t leaf = (uint32_t)K->out.leaf;
     const LeafHead Hm = leaf_head(S, leaf);
@@ -2688,6 +2702,7 @@ __global__ __launch_bounds__(kBlock) void k_block_lists(BlockListArgs) {
                     const double vx[3] = {T[0], T[0] + T[3], T[0] + T[6]}, vy[3] = {T[1], T[1] + T[4], T[1] + T[7]}, vz[3] = {T[2], T[2] + T[5], T[2] + T[8]};
                     double xl = __builtin_inf(), xh = -__builtin_inf(), yl = __builtin_inf(), yh = -__builtin_inf();
                     bool bounded = true;
+                    double pjx[3], pjy[3], e_max = 0.0;             // the projected vertices and the largest of their error bounds (the edge record)
 #pragma unroll
                     for (int v = 0; v < 3; ++v) {
                         const double px = vx[v] - omx, py = vy[v] - omy, pz = vz[v] - omz;
@@ -2699,6 +2714,7 @@ __global__ __launch_bounds__(kBlock) void k_block_lists(BlockListArgs) {
                         const double jx = b / a, jy = c / a, ex = (eb + fabs(jx) * ea) / am, ey = (ec + fabs(jy) * ea) / am;
                         bounded = bounded && am > 0.0 && fabs(jx) + fabs(jy) + ex + ey < 1e300;
                         xl = fmin(xl, jx - ex); xh = fmax(xh, jx + ex); yl = fmin(yl, jy - ey); yh = fmax(yh, jy + ey);
+                        pjx[v] = jx; pjy[v] = jy; e_max = fmax(e_max, fmax(ex, ey));
                     }
                     const double grow = 1e-3 * ((xh - xl) + (yh - yl));
                     const float inf = __builtin_inff();
@@ -2711,6 +2727,14 @@ __global__ __launch_bounds__(kBlock) void k_block_lists(BlockListArgs) {
                     if (keep) {
                         uint32_t* e = mine + kListEntryWords * (n + lanes_below(km));
                         e[0] = tri; e[1] = S.tri_orig[tri]; e[2] = __float_as_uint(tx0); e[3] = __float_as_uint(tx1); e[4] = __float_as_uint(ty0); e[5] = __float_as_uint(ty1);
+                        if (K->out.edges) {
+                            // the rectangle lies e_max + grow (and its outward rounding, which the record's own float slack covers) outside the
+                            // projected vertices; e_max + grow is a NaN where the rectangle is not bounded, and the record then the sentinel anyway
+                            float rec[kEdgeFloats];
+                            edge_record(pjx, pjy, e_max + grow, bounded, rec);
+                            float* er = mine_edges + kEdgeFloats * (n + lanes_below(km));
+                            for (uint32_t q = 0; q < kEdgeFloats; ++q) er[q] = rec[q];
+                        }
                     }
                     n += n_keep;
                 }
@@ -2727,6 +2751,10 @@ __global__ __launch_bounds__(kBlock) void k_block_lists(BlockListArgs) {
                 __builtin_amdgcn_wave_barrier();
                 uint32_t* dst = K->out.pool + (size_t)kListEntryWords * at;
                 for (uint32_t w = lane_id(); w < kListEntryWords * n; w += 64u) dst[w] = mine[w];
+                if (K->out.edges) {
+                    float* de = K->out.edges + (size_t)kEdgeFloats * at;
+                    for (uint32_t w = lane_id(); w < kEdgeFloats * n; w += 64u) de[w] = mine_edges[w];
+                }
                 head = (at << 7) | n;
             }
         }

@@ -16,6 +16,7 @@
 #include <stdint.h>
 
 #include "ft_device.h"
+#include "ft_edges.h"
 
 using namespace ftd;
 
@@ -164,7 +165,50 @@ __global__ __launch_bounds__(256) void k_ls_emit(const float* __restrict__ ebox,
     }
 }
 
+// ---- the edge records of a pair's grid (ft_edges.h; option "edge_cull") --------------------------------------------------------------
+// One wave per cell, one lane per entry: the entry's record in ls_tris projected as grow_by_tri projects it, and the record of its three
+// edges in (u, v).  E, the inflation the entry's rectangle carries: how far the five-float box the builder wrote beside the entry lies
+// outside the projected vertices - the builder's pad and its outward rounding, read off the box itself, so it is the grid's own whoever
+// built it (build_grid on the host, k_ls_emit here).  Every index is checked against the arrays' sizes: a cell table that says otherwise
+// writes nothing.
+__global__ __launch_bounds__(256) void k_ls_edges(const double* __restrict__ pair, const uint32_t* __restrict__ nodes, uint32_t node_words,
+                                                  const double* __restrict__ tris, uint32_t n_recs, uint32_t n_cells, float* __restrict__ edges) {
+    const uint32_t cell = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    if (cell >= n_cells) return;
+    const uint32_t cells = reinterpret_cast<const uint32_t*>(pair + 14)[1];
+    if ((uint64_t)cells + 4ull * cell + 4ull > node_words) return;
+    const uint32_t* W = nodes + cells + 4ull * cell;
+    const uint32_t first = W[0], box = W[1];
+    uint32_t cnt = W[2];
+    if (cnt > kLsGridMaxCell) cnt = kLsGridMaxCell;
+    if ((uint64_t)first + cnt > n_recs || (uint64_t)box + 5ull * cnt > node_words) return;
+    LsFrame F;
+    for (int q = 0; q < 3; ++q) { F.U[q] = pair[q]; F.V[q] = pair[3 + q]; F.D[q] = pair[6 + q]; F.c[q] = pair[9 + q]; }
+    F.pad = 0.0;
+    for (uint32_t e = lane; e < cnt; e += 64u) {
+        const double* T = tris + 9ull * (first + e);
+        double x[3], y[3];
+        for (int v = 0; v < 3; ++v) {
+            double p[3];
+            for (int q = 0; q < 3; ++q) p[q] = __dadd_rn(__dsub_rn(T[q], F.c[q]), v == 1 ? T[3 + q] : v == 2 ? T[6 + q] : 0.0);
+            x[v] = dot_lr(p, F.U); y[v] = dot_lr(p, F.V);
+        }
+        const float* B = reinterpret_cast<const float*>(nodes + box + 5ull * e);
+        const double xl = fmin(x[0], fmin(x[1], x[2])), xh = fmax(x[0], fmax(x[1], x[2])), yl = fmin(y[0], fmin(y[1], y[2])), yh = fmax(y[0], fmax(y[1], y[2]));
+        const double E = fmax(fmax(xl - (double)B[0], (double)B[1] - xh), fmax(yl - (double)B[2], (double)B[3] - yh));
+        const bool bounded = fabs((double)B[0]) + fabs((double)B[1]) + fabs((double)B[2]) + fabs((double)B[3]) < 3e38;
+        float rec[kEdgeFloats];
+        edge_record(x, y, E, bounded, rec);
+        for (uint32_t q = 0; q < kEdgeFloats; ++q) edges[(size_t)kEdgeFloats * (first + e) + q] = rec[q];
+    }
+}
+
 } // namespace
+
+void ls_edge_records(hipStream_t stream, const double* pair, const uint32_t* ls_nodes, uint32_t node_words, const double* ls_tris, uint32_t n_recs, uint32_t n_cells, float* edges) {
+    if (n_cells == 0u) return;
+    hipLaunchKernelGGL(k_ls_edges, dim3((n_cells + 3u) / 4u), dim3(256), 0, stream, pair, ls_nodes, node_words, ls_tris, n_recs, n_cells, edges);
+}
 
 void ls_grid_entries(hipStream_t stream, const double* tris, uint32_t n, const LsFrame& F, float* ebox, uint32_t* ruv) {
     hipLaunchKernelGGL(k_ls_entries, dim3((n + 255u) / 256u), dim3(256), 0, stream, tris, n, F, ebox, ruv);

@@ -169,6 +169,10 @@ const char* ft_last_error(const ft_context* ctx);
  * a scene, without the code such a scene never reaches, in fewer registers and with more waves in flight - when the camera has no focus and the frame is a plain
  * (not progressive, not corner-sampled) one in grouped numbering with "coherent_waves" and "uniform_surface" on; 0: k_primary everywhere.  Same frames and
  * ft_stats (times aside) bit for bit; no re-commit, and what the frame slots keep of their classifications stays),
+ * "edge_cull" (1 = default: beside its rectangle every entry of a block's candidate list and of a directional light's shadow grid carries the three edges of its
+ * projected triangle, and a wavefront whose own rectangle lies wholly outside one of them skips the triangle without fetching it; slivers, triangles that reach the
+ * camera plane and scenes past the record cap carry none.  Only triangles no ray of the wavefront can hit are skipped: same frames and ft_stats (times aside) bit
+ * for bit.  0: the rectangles alone.  Read per frame; no re-commit, and what the frame slots keep of their classifications stays),
  * "classify_reuse" (1 = default: a classified frame whose scene commit, frame size, tiles, camera, jitter extent (not the offsets) and candidate-list leaf equal, field
  * for field, those of the frame that last classified into the same one of the four frame slots launches neither k_classify nor k_block_lists: it reads that frame's
  * block maps, lists and active count as they are, and launches only the windows of its pixel list that hold active pixels - a held view, whatever its pattern, seed, samples
@@ -827,6 +831,12 @@ int32_t ft_debug_mesh_trees(ft_context* ctx, int64_t sizes[12], void* nodes, uin
  * 0xFFFFFFFF (the block walks the tree) or first entry << 7 | count; pos_block = the block of the frame's pixel list behind each active block;
  * entries = 6 words each: the triangle's record, its list index (tri_orig), and its rectangle x0, x1, y0, y1 in (jx, jy) as floats. */
 int32_t ft_debug_block_lists(ft_context* ctx, int64_t sizes[4], double plane[4], uint32_t* heads, uint32_t* pos_block, uint32_t* entries);
+/* The edge records of option "edge_cull" as they lie in device memory (written whatever the option says), for tests.  sizes[0] = records of the committed
+ * scene's shadow grids: one per triangle record ft_debug_light_space hands out, under the same index, or 0 where the scene carries none; sizes[1] = records of
+ * the candidate lists ft_debug_block_lists describes: one per entry in use, under the same index.  Each non-null array receives 9 floats per record: three lines
+ * (a, b, c) with a x + b y + c <= 0 at every point of the entry's plane - (u, v) of the pair's frame, (jx, jy) of the image plane - from which a ray can hit the
+ * triangle; nine zeros: no edges, the entry is never skipped (also under every record that is not a grid entry).  FT_ERR_NO_DEVICE on a host-only context. */
+int32_t ft_debug_edge_records(ft_context* ctx, int64_t sizes[2], float* grid_edges, float* list_edges);
 /* "classify_reuse" at work, for tests: counts since ft_create, summed over the context's devices - classifications launched, classifications reused, windows
  * launched, windows not launched because the kept active list ends before them.  FT_ERR_NO_DEVICE on a host-only context. */
 int32_t ft_debug_classify_reuse(ft_context* ctx, int64_t out[4]);

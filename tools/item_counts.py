@@ -35,7 +35,11 @@ for name, spp in (("bunny", 16), ("bunny-bsp12", 16), ("hollow-sphere", 16), ("h
     if clk[7]:                                             # the candidate lists of the closest queries (k_block_lists): slots 2, 3, 7
         lq = clk[7]
         print(f"   closest queries through a block's list {lq} ({lq / max(v[0], 1):.2f} per coherent closest wave-query): entries offered / query {clk[2] / lq:6.2f}  "
-              f"past the rectangle test = triangles tested {clk[3] / lq:6.2f}")
+              f"past the wave's tests = triangles tested {clk[3] / lq:6.2f}")
+        if clk[11]:                                        # option edge_cull (slot 11; a library from before it leaves the slot at 0)
+            print(f"      entries kept by the rectangles / query {clk[11] / lq:6.2f}  kept by the edges {clk[3] / lq:6.2f}")
+    if clk[14] and clk[31]:                                # the shadow grids' entries: slots 14 (rectangles) and 15 (edges)
+        print(f"   shadow-grid entries per walk: kept by the rectangles {clk[14] / clk[31]:6.2f}  kept by the edges {clk[15] / clk[31]:6.2f}")
     if clk[31]:
         walks, qa = clk[31], v[8]
         nb = clk[26] or 1
