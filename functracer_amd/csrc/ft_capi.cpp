@@ -198,6 +198,8 @@ const OptionSpec kOptions[] = {
     {"temporal_follow_deformed", 0, 1, &Options::temporal_follow_deformed, nullptr, kFlag},
     // read by ft_scene_commit_deformed alone: no commit depends on it, so it leaves the committed scene as it is
     {"refit_rebuild_percent", 100, 1000000, &Options::refit_rebuild_percent, nullptr, kOrZero},
+    // read by ft_scene_commit_deformed alone, as the one above (any value other than 0 means 1)
+    {"deform_light_space", 0, 1, &Options::deform_light_space, nullptr, kFlag},
     {"csg_mesh_capacity", 1, 255, nullptr, [](fth::SceneGraph& g, int64_t v) { g.csg_mesh_capacity = (int32_t)v; }, kCommit},
     // directional shadow rays of coherent waves: 0 the BVH; 1 light-space trees; 2 (default) light-space grids, the trees for wide waves.
     // It was a flag before the grids: it still takes any value, and any other than 0 / 1 means 2.
@@ -790,7 +792,7 @@ static int32_t refit_device(ft_context* c, const fth::FlatScene& f, const fth::S
 // What the first ft_scene_commit_lights after a full commit reads off `f` as that commit left it (ft_context::LightSpace): the pairs that
 // have a tree, what of their records does not depend on the direction, and each tree's 4-wide nodes by level, deepest first.
 static void derive_light_space_tables(const fth::FlatScene& f, ft_context::LightSpace& T) {
-    T.pairs.clear(); T.order.clear();
+    T.pairs.clear(); T.order.clear(); T.src.clear();
     T.base_node_words = f.ls_nodes.size(); T.base_tri_doubles = f.ls_tris.size();
     const size_t n_nodes = f.ls_nodes.size() / ftd::kLsNodeWords, n_recs = f.ls_pairs.size() / ftd::kLsPairDoubles;
     std::vector<uint8_t> seen(n_nodes, 0);
@@ -803,15 +805,7 @@ static void derive_light_space_tables(const fth::FlatScene& f, ft_context::Light
         if ((size_t)src.first_tri + src.n_tris > f.tris.size() / 9) continue;
         const double* mb = &f.mesh_bounds[6 * (size_t)L.mesh];
         const double c[3] = {0.5 * (mb[0] + mb[3]), 0.5 * (mb[1] + mb[4]), 0.5 * (mb[2] + mb[5])};
-        double R = 0.0;                                             // as build_light_space sums it: it does not depend on the frame
-        for (uint32_t k = 0; k < src.n_tris; ++k) {
-            const double* Tr = &f.tris[9 * (size_t)(src.first_tri + k)];
-            for (int v = 0; v < 3; ++v) {
-                double p[3];
-                for (int q = 0; q < 3; ++q) p[q] = (Tr[q] - c[q]) + (v == 1 ? Tr[3 + q] : v == 2 ? Tr[6 + q] : 0.0);
-                R = std::max(R, std::fabs(p[0]) + std::fabs(p[1]) + std::fabs(p[2]));
-            }
-        }
+        const double R = fth::ls_pair_extent(&f.tris[9 * (size_t)src.first_tri], src.n_tris, false, c);   // as build_light_space sums it: it does not depend on the frame
         for (uint32_t l = 0; l < (uint32_t)f.lights.size(); ++l) {
             const size_t rec = (size_t)L.ls_pairs + l;
             if (f.lights[l].kind != ftd::LT_DIRECTIONAL || rec >= n_recs) continue;
@@ -820,6 +814,7 @@ static void derive_light_space_tables(const fth::FlatScene& f, ft_context::Light
             if (root < 0 || (size_t)root >= n_nodes || seen[(size_t)root]) continue;   // none at the commit: none until the next one
             ft_context::LightSpace::Pair P{};
             P.rec = (uint32_t)rec; P.leaf = leaf; P.light = l; P.root = root; P.R = R; P.first_tri = src.first_tri; P.n_tris = src.n_tris;
+            P.mesh = L.mesh; P.ls_first = ~0u; P.src_at = (uint32_t)T.src.size(); P.deformed = false;
             for (int q = 0; q < 3; ++q) { P.c[q] = c[q]; P.v0[q] = f.lights[l].v[q]; }
             std::memcpy(P.rec0, &f.ls_pairs[ftd::kLsPairDoubles * rec], sizeof P.rec0);
             // breadth first: `level` holds one level of the tree; the levels are then laid out deepest first
@@ -830,6 +825,7 @@ static void derive_light_space_tables(const fth::FlatScene& f, ft_context::Light
                 std::vector<uint32_t> next;
                 for (uint32_t n : level) for (int k = 0; k < 4; ++k) {
                     const int32_t ch = (int32_t)f.ls_nodes[(size_t)ftd::kLsNodeWords * n + 20 + k];
+                    if (ch < 0 && ch != INT32_MIN) P.ls_first = std::min(P.ls_first, (uint32_t)~ch >> 3);   // the builder appended the tree's leaves in one run
                     if (ch < 0 || (size_t)ch >= n_nodes || seen[(size_t)ch]) continue;   // a leaf, an empty slot (or no tree at all)
                     seen[(size_t)ch] = 1;
                     next.push_back((uint32_t)ch);
@@ -841,6 +837,11 @@ static void derive_light_space_tables(const fth::FlatScene& f, ft_context::Light
                 P.levels.push_back({(uint32_t)T.order.size(), (uint32_t)by_level[d].size()});
                 T.order.insert(T.order.end(), by_level[d].begin(), by_level[d].end());
             }
+            // the triangles the tree's leaf records copy; a run that does not lie in ls_src leaves the pair without them, and a deformed
+            // commit then strips its leaf as it did before "deform_light_space"
+            if ((size_t)P.ls_first + P.n_tris <= f.ls_src.size() && (size_t)P.ls_first + P.n_tris <= f.ls_tris.size() / 9)
+                T.src.insert(T.src.end(), f.ls_src.begin() + P.ls_first, f.ls_src.begin() + P.ls_first + P.n_tris);
+            else P.ls_first = ~0u;
             T.pairs.push_back(std::move(P));
         }
     }
@@ -850,11 +851,39 @@ static void derive_light_space_tables(const fth::FlatScene& f, ft_context::Light
 // One pair's share of an ft_scene_commit_lights: its frame; whether its tree is refit (its direction changed in this call); whether its
 // grid is built again behind the arrays of the full commit (every pair whose direction is not that commit's, in every call that
 // turns any light: the region is laid out anew each time, so it never grows), and what the context's first device decided for that grid.
+// gather: its mesh was refit in this call (ft_scene_commit_deformed, "deform_light_space"), so the tree's leaf records are copied again
+// from the mesh's list-order records before anything reads them - also where the record is unusable and nothing else is done, so that the
+// tree is current whenever a later call refits its boxes.
 struct LightJob {
     const ft_context::LightSpace::Pair* pair; ftk::LsFrame frame; bool refit, regrid;
+    bool gather = false;
     bool grid = false; float s = 0.0f; uint32_t nu = 0, nv = 0, entries = 0, at = 0, tri_at = 0;
     size_t slot = 0;                                                // of the device's per-pair scratch (ft_context::LightSpace::d_ebox, d_counts)
 };
+
+// The record of a pair that is not the full commit's any more - its light points elsewhere, or its mesh has been deformed - derived again
+// from the pair's current centre and R as build_light_space derives it, and the pair's job: its tree refit (`refit`: the direction or the
+// vertices changed in this call), its grid built again behind the full commit's arrays (`grids`: the scene has them).  No usable frame,
+// or R from 2e29 on: root INT32_MIN and no grid - its rays walk the BVH, and the tree's nodes and records stay where they are.
+static void moved_pair_job(fth::FlatScene& f, const ft_context::LightSpace::Pair& P, const ftd::Light& light, bool refit, bool gather, bool grids, std::vector<LightJob>& jobs, size_t& n_regrid) {
+    double* rec = &f.ls_pairs[(size_t)ftd::kLsPairDoubles * P.rec];
+    LightJob j{&P, {}, false, false};
+    j.gather = gather;
+    for (int k = 0; k < ftd::kLsPairDoubles; ++k) rec[k] = 0.0;
+    fth::LsPairFrame fr;
+    // (every projected coordinate is at most R in size: the builder's finiteness test, five of them below 1e30, holds with R < 2e29)
+    const bool usable = fth::ls_pair_frame(f.leaves[P.leaf], light, fr) && P.R < 2e29;
+    const int32_t root = usable ? P.root : INT32_MIN;               // none: the tree's nodes and records stay where they are for the direction's return
+    std::memcpy(&rec[14], &root, 4);
+    if (usable) {
+        for (int q = 0; q < 3; ++q) { rec[q] = j.frame.U[q] = fr.U[q]; rec[3 + q] = j.frame.V[q] = fr.V[q]; rec[6 + q] = j.frame.D[q] = fr.D[q]; rec[9 + q] = j.frame.c[q] = P.c[q]; }
+        rec[12] = fr.k_rel; rec[13] = (fr.k_rel + 1e-6) * P.R + 1e-20;
+        j.frame.pad = 1e-7 * P.R + 1e-30;
+        j.refit = refit; j.regrid = grids;
+        if (j.regrid) j.slot = n_regrid++;
+    }
+    if (usable || gather) jobs.push_back(j);
+}
 
 // build_grid's decisions for one pair (ft_scene.cpp), its host loops run as passes on the device: readback 1 Ru and Rv, readback 2 the
 // entries under each candidate of the attempt loop, readback 3 the fullest cell.  `bytes`: what the arrays hold so far, against the cap.
@@ -910,20 +939,18 @@ static int32_t plan_grid(ft_context* c, LightJob& j, uint64_t& bytes) {
     return FT_OK;
 }
 
-// The new lights on one device of the context: `f` is the held scene with the new lights and pair records already in it (the grid words of
-// the jobs' records excepted: the first device, `lead`, decides them here and writes them into f; the others carry them out).  The trees
-// of the jobs that ask for it are written again in their new frames, the grids laid out anew behind the full commit's arrays
-// (ft_lightspace.hip; `relay`: some light turned and the scene has grids).  ms[0] += uploads and the rest, ms[1] += the kernels.
-static int32_t relight_device(ft_context* c, fth::FlatScene& f, const ft_context::LightSpace& T, std::vector<LightJob>& jobs, bool relay, bool lead, double ms[2]) {
+// The light-space structures of one device of the context brought up to the pair records in `f` (the grid words of the jobs' records
+// excepted: the first device, `lead`, decides them here and writes them into f; the others carry them out), for ft_scene_commit_lights
+// and ft_scene_commit_deformed alike (`who` names the caller in an error).  Nothing else may be reading or writing the scene's arrays:
+// the caller has retired the queued frames and drained the streams.  On the stream, in order: the leaf records of the jobs that gather,
+// the trees of the jobs that refit written again in their frames, the grids laid out anew behind the full commit's arrays
+// (ft_lightspace.hip; `relay`: the scene has grids and what one of them must hold changed), the pair records, the edge records.
+// ms[0] += uploads and the rest, ms[1] += the kernels and their readbacks.
+static int32_t rebuild_light_space(ft_context* c, fth::FlatScene& f, const ft_context::LightSpace& T, std::vector<LightJob>& jobs, bool relay, bool lead, double ms[2], const char* who) {
     using clock = std::chrono::steady_clock;
     auto since = [](clock::time_point t0) { return std::chrono::duration<double, std::milli>(clock::now() - t0).count(); };
     int32_t rc;
-    FT_HIP(c, hipSetDevice(c->device));
     const auto t0 = clock::now();
-    // frames still queued trace the scene these uploads rewrite (as upload_scene): they show the old lights
-    if (any_queued(c)) { if ((rc = retire_queued(c)) != FT_OK) return rc; c->accum_open = false; }
-    if ((rc = drain_frame_streams(c)) != FT_OK) return rc;
-    if (c->side) FT_HIP(c, hipStreamSynchronize(c->side));
     DeviceBuf* B = c->d_scene;
     ft_context::LightSpace& L = c->lightspace;
     if (L.node_words == 0) { L.node_words = T.base_node_words; L.tri_doubles = T.base_tri_doubles; }   // the first call since the upload
@@ -931,17 +958,27 @@ static int32_t relight_device(ft_context* c, fth::FlatScene& f, const ft_context
         if ((rc = upload(c, L.d_order, T.order)) != FT_OK) return rc;
         L.order_uploaded = true;
     }
-    if ((rc = upload(c, B[kLights], f.lights)) != FT_OK) return rc;
+    bool gathers = false;
+    for (const LightJob& j : jobs) gathers = gathers || j.gather;
+    if (gathers && !L.src_uploaded) {
+        if ((rc = upload(c, L.d_src, T.src)) != FT_OK) return rc;
+        L.src_uploaded = true;
+    }
     FT_HIP(c, hipStreamSynchronize(c->stream));
     ms[0] += since(t0);
     const auto t1 = clock::now();
     if (B[kLsNodes].bytes < L.node_words * 4 || B[kLsTris].bytes < L.tri_doubles * 8 || L.node_words < T.base_node_words || L.tri_doubles < T.base_tri_doubles ||
-        B[kTris].bytes < f.tris.size() * 8) { c->err = "ft_scene_commit_lights: a scene array in device memory is smaller than the flattened one"; return FT_ERR_STATE; }
+        B[kTris].bytes < f.tris.size() * 8) { c->err = std::string(who) + ": a scene array in device memory is smaller than the flattened one"; return FT_ERR_STATE; }
     const uint32_t n_nodes = (uint32_t)(T.base_node_words / ftd::kLsNodeWords), n_tris = (uint32_t)(T.base_tri_doubles / 9);   // the trees lie in the full commit's part
     size_t slots = 0;
     bool regrid = relay;                                            // a light turned: the region behind the full commit's arrays is laid out anew, be it to nothing
-    for (const LightJob& j : jobs) {
+    for (const LightJob& j : jobs) {                                // (a pair's tree lies apart from every other's: one pass over the jobs keeps each tree's order)
         if (j.regrid) slots = std::max(slots, j.slot + 1);
+        if (j.gather && j.pair->src_at + (size_t)j.pair->n_tris <= T.src.size()) {
+            ftk::ls_gather(c->stream, B[kTris].as<double>(), (uint32_t)(f.tris.size() / 9), j.pair->first_tri, j.pair->n_tris, L.d_src.as<uint32_t>() + j.pair->src_at, j.pair->n_tris,
+                           B[kLsTris].as<double>(), n_tris, j.pair->ls_first);
+            L.rewritten = true;
+        }
         if (!j.refit) continue;
         for (const auto& lv : j.pair->levels)                       // deepest level first: a node's children are done before it
             ftk::ls_refit_level(c->stream, B[kLsNodes].as<uint32_t>(), n_nodes, B[kLsTris].as<double>(), n_tris, L.d_order.as<uint32_t>() + lv.first, lv.second, j.frame);
@@ -985,29 +1022,29 @@ static int32_t relight_device(ft_context* c, fth::FlatScene& f, const ft_context
             hipMemcpyAsync(tris.p, B[kLsTris].p, T.base_tri_doubles * 8, hipMemcpyDeviceToDevice, c->stream) != hipSuccess ||
             (words > T.base_node_words && hipMemsetAsync(nodes.as<uint32_t>() + T.base_node_words, 0, (words - T.base_node_words) * 4, c->stream) != hipSuccess) ||
             (doubles > T.base_tri_doubles && hipMemsetAsync(tris.as<double>() + T.base_tri_doubles, 0, (doubles - T.base_tri_doubles) * 8, c->stream) != hipSuccess)) {
-            c->err = "ft_scene_commit_lights: copying the light-space arrays failed"; return fail(FT_ERR_HIP);
+            c->err = std::string(who) + ": copying the light-space arrays failed"; return fail(FT_ERR_HIP);
         }
         for (const LightJob& j : jobs) {
             if (!j.grid) continue;
             const uint32_t n = j.pair->n_tris, cells = j.nu * j.nv;
             const double* mesh = B[kTris].as<double>() + 9 * (size_t)j.pair->first_tri;
             size_t scan_bytes = 0;
-            if (ftk::ls_grid_scan(c->stream, nullptr, nullptr, cells, nullptr, &scan_bytes) != hipSuccess) { c->err = "ft_scene_commit_lights: sizing the scan failed"; return fail(FT_ERR_HIP); }
+            if (ftk::ls_grid_scan(c->stream, nullptr, nullptr, cells, nullptr, &scan_bytes) != hipSuccess) { c->err = std::string(who) + ": sizing the scan failed"; return fail(FT_ERR_HIP); }
             DeviceBuf& ebox = L.d_ebox[j.slot];
             DeviceBuf& counts = L.d_counts[j.slot];
             if ((rc = ensure(c, ebox, (size_t)n * 20)) != FT_OK || (rc = ensure(c, counts, (size_t)cells * 4)) != FT_OK || (rc = ensure(c, L.d_first, (size_t)cells * 4)) != FT_OK ||
                 (rc = ensure(c, L.d_cursor, (size_t)cells * 4)) != FT_OK || (rc = ensure(c, L.d_idx, (size_t)j.entries * 4)) != FT_OK || (rc = ensure(c, L.d_scan, scan_bytes)) != FT_OK) return fail(rc);
-            if (hipMemsetAsync(L.d_cursor.p, 0, (size_t)cells * 4, c->stream) != hipSuccess) { c->err = "ft_scene_commit_lights: hipMemsetAsync failed"; return fail(FT_ERR_HIP); }
+            if (hipMemsetAsync(L.d_cursor.p, 0, (size_t)cells * 4, c->stream) != hipSuccess) { c->err = std::string(who) + ": hipMemsetAsync failed"; return fail(FT_ERR_HIP); }
             if (!lead) {                                            // (the first device's slot holds both since plan_grid)
-                if (hipMemsetAsync(counts.p, 0, (size_t)cells * 4, c->stream) != hipSuccess) { c->err = "ft_scene_commit_lights: hipMemsetAsync failed"; return fail(FT_ERR_HIP); }
+                if (hipMemsetAsync(counts.p, 0, (size_t)cells * 4, c->stream) != hipSuccess) { c->err = std::string(who) + ": hipMemsetAsync failed"; return fail(FT_ERR_HIP); }
                 ftk::ls_grid_entries(c->stream, mesh, n, j.frame, ebox.as<float>(), nullptr);
                 ftk::ls_grid_cell_counts(c->stream, ebox.as<float>(), n, j.s, j.nu, j.nv, counts.as<uint32_t>(), nullptr);
             }
-            if (ftk::ls_grid_scan(c->stream, counts.as<uint32_t>(), L.d_first.as<uint32_t>(), cells, L.d_scan.p, &scan_bytes) != hipSuccess) { c->err = "ft_scene_commit_lights: the scan failed"; return fail(FT_ERR_HIP); }
+            if (ftk::ls_grid_scan(c->stream, counts.as<uint32_t>(), L.d_first.as<uint32_t>(), cells, L.d_scan.p, &scan_bytes) != hipSuccess) { c->err = std::string(who) + ": the scan failed"; return fail(FT_ERR_HIP); }
             ftk::ls_grid_emit(c->stream, ebox.as<float>(), mesh, n, j.s, j.nu, j.nv, counts.as<uint32_t>(), L.d_first.as<uint32_t>(), L.d_cursor.as<uint32_t>(), L.d_idx.as<uint32_t>(),
                               j.entries, nodes.as<uint32_t>(), j.at, tris.as<double>(), j.tri_at);
         }
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) { c->err = "ft_scene_commit_lights: the grid kernels failed"; return fail(FT_ERR_HIP); }
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) { c->err = std::string(who) + ": the grid kernels failed"; return fail(FT_ERR_HIP); }
         // nothing reads the old arrays any more: the streams were drained above
         B[kLsNodes].release(); B[kLsTris].release();
         B[kLsNodes] = nodes; B[kLsTris] = tris;
@@ -1027,6 +1064,23 @@ static int32_t relight_device(ft_context* c, fth::FlatScene& f, const ft_context
     const auto t3 = clock::now();
     if (!jobs.empty() && (rc = build_ls_edges(c, f.ls_pairs, L.node_words, L.tri_doubles)) != FT_OK) return rc;   // (no job: no pair record and no array changed)
     ms[1] += since(t3);
+    return FT_OK;
+}
+
+// The new lights on one device of the context: `f` is the held scene with the new lights and pair records already in it.  The lights are
+// uploaded, then the light-space structures follow (rebuild_light_space; `relay`: some light turned and the scene has grids).
+static int32_t relight_device(ft_context* c, fth::FlatScene& f, const ft_context::LightSpace& T, std::vector<LightJob>& jobs, bool relay, bool lead, double ms[2]) {
+    using clock = std::chrono::steady_clock;
+    int32_t rc;
+    FT_HIP(c, hipSetDevice(c->device));
+    const auto t0 = clock::now();
+    // frames still queued trace the scene these uploads rewrite (as upload_scene): they show the old lights
+    if (any_queued(c)) { if ((rc = retire_queued(c)) != FT_OK) return rc; c->accum_open = false; }
+    if ((rc = drain_frame_streams(c)) != FT_OK) return rc;
+    if (c->side) FT_HIP(c, hipStreamSynchronize(c->side));
+    if ((rc = upload(c, c->d_scene[kLights], f.lights)) != FT_OK) return rc;
+    ms[0] += std::chrono::duration<double, std::milli>(clock::now() - t0).count();
+    if ((rc = rebuild_light_space(c, f, T, jobs, relay, lead, ms, "ft_scene_commit_lights")) != FT_OK) return rc;
     c->zero_signature[0] = c->zero_signature[1] = 0;                // (as every commit)
     c->committed = true;
     ++c->commit_serial; c->staged_hint = -1;
@@ -1090,15 +1144,47 @@ int32_t ft_scene_commit_deformed(ft_context* c) {
         progressive_close(c);
         return commit_scene(c);
     }
+    // "deform_light_space": the pairs' tables, off `f` as the full commit left it - before anything in it changes
+    const bool keep_ls = c->opt.deform_light_space != 0 && c->graph.light_space_shadows != 0;
+    ft_context::LightSpace& T = c->lightspace;
+    if (keep_ls && !T.ready) derive_light_space_tables(f, T);
     std::vector<double> bounds = f.mesh_bounds;
     for (const DeformedMesh& e : edits) for (int k = 0; k < 6; ++k) bounds[6 * (size_t)e.mesh + k] = e.scan.bounds[k];
     int32_t rc = c->graph.reflatten_deformed(f, bounds, c->err);   // the cull records, by the flattener's own walk
     if (rc != FT_OK) { if (rc == FT_ERR_UNSUPPORTED) c->committed = true; return rc; }
-    // The light-space structures are built from the vertices and are not refit: the directional shadow rays of an edited mesh walk its
-    // BVH (the same bits, include/functracer_hip.h "light_space_shadows") until the next full commit brings them back.
-    std::vector<bool> edited(f.meshes.size(), false);
-    for (const DeformedMesh& e : edits) edited[e.mesh] = true;
-    for (ftd::Leaf& L : f.leaves) if (L.kind == ftd::LK_MESH && L.mesh < edited.size() && edited[L.mesh]) L.ls_pairs = ~0u;
+    // The light-space structures are built from the vertices.  By default they are not refit: the directional shadow rays of an edited
+    // mesh walk its BVH (the same bits, include/functracer_hip.h "light_space_shadows") until the next full commit brings them back.
+    // Under "deform_light_space" a leaf keeps its pairs where every one of them that had a tree can be refit.
+    std::vector<const DeformedMesh*> edited(f.meshes.size(), nullptr);
+    for (const DeformedMesh& e : edits) edited[e.mesh] = &e;
+    std::vector<uint8_t> kept(f.leaves.size(), keep_ls ? 1 : 0);
+    if (keep_ls) for (const ft_context::LightSpace::Pair& P : T.pairs) if (P.ls_first == ~0u) kept[P.leaf] = 0;
+    for (size_t k = 0; k < f.leaves.size(); ++k) {
+        ftd::Leaf& L = f.leaves[k];
+        if (L.kind == ftd::LK_MESH && L.mesh < edited.size() && edited[L.mesh] && !kept[k]) L.ls_pairs = ~0u;
+    }
+    // Every pair of an edited mesh: the centre of the new bounds, R over the new records.  With it, as in ft_scene_commit_lights, every
+    // pair that is not the full commit's any more: the region behind that commit's arrays is laid out anew and holds all their grids.
+    std::vector<LightJob> jobs;
+    size_t n_regrid = 0;
+    bool touched = false;
+    const bool grids = c->graph.light_space_shadows == 2;
+    if (keep_ls) {
+        for (ft_context::LightSpace::Pair& P : T.pairs) {
+            if (f.leaves[P.leaf].ls_pairs == ~0u || P.mesh >= edited.size() || !edited[P.mesh]) continue;   // (stripped before: stays stripped)
+            const DeformedMesh& e = *edited[P.mesh];
+            for (int q = 0; q < 3; ++q) P.c[q] = 0.5 * (e.scan.bounds[q] + e.scan.bounds[3 + q]);
+            const std::vector<double>& v = c->graph.nodes[(size_t)e.node].tris;
+            P.R = fth::ls_pair_extent(v.data(), v.size() / 9, true, P.c);
+            P.deformed = true;
+            touched = true;
+        }
+        for (const ft_context::LightSpace::Pair& P : T.pairs) {
+            if (!touched || f.leaves[P.leaf].ls_pairs == ~0u) continue;
+            const bool now = P.mesh < edited.size() && edited[P.mesh];
+            if (now || P.deformed || std::memcmp(f.lights[P.light].v, P.v0, sizeof P.v0) != 0) moved_pair_job(f, P, f.lights[P.light], now, now, grids, jobs, n_regrid);
+        }
+    }
     progressive_close(c);
     const double tallest = c->commit_ms[3];
     for (double& v : c->commit_ms) v = 0.0;
@@ -1108,7 +1194,10 @@ int32_t ft_scene_commit_deformed(ft_context* c) {
     RebuildPlan plan;
     for (ft_context* d : devices(c)) {                              // every device refits its own copy
         if ((rc = refit_device(d, f, c->graph, edits, ms, d == c, plan)) != FT_OK) { if (d != c) c->err = d->err; break; }
+        // behind the refit, which has written the list-order records the gather and the grid passes read
+        if (!jobs.empty() && (rc = rebuild_light_space(d, f, T, jobs, grids, d == c, ms, "ft_scene_commit_deformed")) != FT_OK) { if (d != c) c->err = d->err; break; }
     }
+    if (!jobs.empty()) for (ft_context* p : c->peers) p->flat.ls_pairs = f.ls_pairs;
     if (rc == FT_OK && plan.tallest > 0) {                          // rebuilt trees: the height figure, and room in the stacks for a taller one
         c->commit_ms[3] = std::max(c->commit_ms[3], (double)plan.tallest);
         for (ft_context* d : devices(c)) {
@@ -1156,27 +1245,15 @@ int32_t ft_scene_commit_lights(ft_context* c) {
     for (const ft_context::LightSpace::Pair& P : T.pairs) {
         if (!turned || f.leaves[P.leaf].ls_pairs == ~0u) continue;  // (stripped by ft_scene_commit_deformed: stays stripped)
         const bool refit = !same_dir(lights[P.light].v, f.lights[P.light].v);
+        if (P.deformed || !same_dir(lights[P.light].v, P.v0)) { moved_pair_job(f, P, lights[P.light], refit, false, grids, jobs, n_regrid); continue; }
+        // the full commit's direction (again) over that commit's vertices: its record, and with it its grid, which still lies where that
+        // commit put it.  (Not for a deformed pair: rec0 and that grid describe vertices that are gone.)
         double* rec = &f.ls_pairs[(size_t)ftd::kLsPairDoubles * P.rec];
+        std::memcpy(rec, P.rec0, sizeof P.rec0);
+        if (!refit) continue;
         LightJob j{&P, {}, refit, false};
-        if (same_dir(lights[P.light].v, P.v0)) {
-            // the full commit's direction (again): its record, and with it its grid, which still lies where that commit put it
-            std::memcpy(rec, P.rec0, sizeof P.rec0);
-            if (!refit) continue;
-            for (int q = 0; q < 3; ++q) { j.frame.U[q] = rec[q]; j.frame.V[q] = rec[3 + q]; j.frame.D[q] = rec[6 + q]; j.frame.c[q] = rec[9 + q]; }
-        } else {
-            for (int k = 0; k < ftd::kLsPairDoubles; ++k) rec[k] = 0.0;
-            fth::LsPairFrame fr;
-            // (every projected coordinate is at most R in size: the builder's finiteness test, five of them below 1e30, holds with R < 2e29)
-            const bool usable = fth::ls_pair_frame(f.leaves[P.leaf], lights[P.light], fr) && P.R < 2e29;
-            const int32_t root = usable ? P.root : INT32_MIN;       // none: the tree's nodes and records stay where they are for the direction's return
-            std::memcpy(&rec[14], &root, 4);
-            if (!usable) continue;
-            for (int q = 0; q < 3; ++q) { rec[q] = j.frame.U[q] = fr.U[q]; rec[3 + q] = j.frame.V[q] = fr.V[q]; rec[6 + q] = j.frame.D[q] = fr.D[q]; rec[9 + q] = j.frame.c[q] = P.c[q]; }
-            rec[12] = fr.k_rel; rec[13] = (fr.k_rel + 1e-6) * P.R + 1e-20;
-            j.regrid = grids;
-        }
+        for (int q = 0; q < 3; ++q) { j.frame.U[q] = rec[q]; j.frame.V[q] = rec[3 + q]; j.frame.D[q] = rec[6 + q]; j.frame.c[q] = rec[9 + q]; }
         j.frame.pad = 1e-7 * P.R + 1e-30;
-        if (j.regrid) j.slot = n_regrid++;
         jobs.push_back(j);
     }
     f.lights = lights;

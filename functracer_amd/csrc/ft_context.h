@@ -97,6 +97,7 @@ struct Options {
     int64_t csg_auto_grow = 1;      // ft_render: double csg_mesh_capacity and render again when a hit list overflows (read on device 0)
     int64_t primary_block_lists = 1;   // k_block_lists: the primaries of a classified frame over ONE bare mesh test their block's candidate list; 0: the tree walk everywhere
     int64_t refit_rebuild_percent = 0;   // ft_scene_commit_deformed rebuilds a device-built tree in place once cost now x 100 > this x cost as built; 0: never (not a commit-time option)
+    int64_t deform_light_space = 0;     // ft_scene_commit_deformed refits the light-space trees and builds the grids of the meshes it edits again instead of stripping them (not a commit-time option)
     int64_t temporal_follow_deformed = 0;   // ft_scene_commit_deformed keeps a mesh's records as the history saw them and ft_temporal_accumulate follows them
     int64_t primary_mesh_kernel = 1;   // k_primary_mesh for the frames that qualify (ft_context::mesh_kernel_scene, queue_chunks); 0: k_primary everywhere (A/B)
     int64_t edge_cull = 1;          // candidate-list and shadow-grid entries are also tested against their triangle's projected edges (ft_edges.h); 0: the rectangles alone (A/B)
@@ -272,26 +273,32 @@ struct ft_context {
     // built since lie behind them.  On every device: `order` in HBM (d_order, uploaded by the device's first refit), the sizes of its
     // ls_nodes and ls_tris now, whether they have been rewritten since the upload (ft_debug_light_space then answers from HBM) and the
     // grid builder's scratch, kept from call to call.
+    // ft_scene_commit_deformed under "deform_light_space"  derives the same tables and adds to a pair: its mesh, the first
+    // of the n_tris contiguous records of ls_tris that are its tree's leaves (ls_first), where in `src` the triangles those records copy are
+    // named (src_at; `src` is that part of fth::FlatScene::ls_src, in HBM as d_src from the device's first such call), and `deformed`: the
+    // mesh has been refit since the full commit, so c and R are the new vertices' and rec0 and the grid in that commit's arrays describe
+    // vertices that are gone - such a pair never takes ft_scene_commit_lights' way back to rec0.
     struct LightSpace {
         struct Pair {
             uint32_t rec, leaf, light; int32_t root; double c[3], R; uint32_t first_tri, n_tris; double v0[3], rec0[ftd::kLsPairDoubles];
             std::vector<std::pair<uint32_t, uint32_t>> levels;
+            uint32_t mesh, ls_first, src_at; bool deformed;
         };
         std::vector<Pair> pairs;
-        std::vector<uint32_t> order;
+        std::vector<uint32_t> order, src;
         size_t base_node_words = 0, base_tri_doubles = 0;
         bool ready = false;
-        DeviceBuf d_order, d_first, d_cursor, d_idx, d_small, d_scan;
+        DeviceBuf d_order, d_src, d_first, d_cursor, d_idx, d_small, d_scan;
         // Option "edge_cull": the edge records of the grids' entries (ft_edges.h), one per record of ls_tris as it lies in HBM now, written
         // by k_ls_edges after every upload of the light-space arrays and at the end of every ft_scene_commit_lights; empty where the scene
         // has no grid or the records would pass kLsEdgeMaxBytes (the shadow queries then go by the rectangles alone).
         DeviceBuf d_edges;
         std::vector<DeviceBuf> d_ebox, d_counts;   // per pair whose grid a call builds: its entry boxes and cell counts, from the pass that decides the grid to the one that writes it
         size_t node_words = 0, tri_doubles = 0;
-        bool order_uploaded = false, rewritten = false;
-        void reset() { pairs.clear(); order.clear(); ready = order_uploaded = rewritten = false; node_words = tri_doubles = base_node_words = base_tri_doubles = 0; }
+        bool order_uploaded = false, src_uploaded = false, rewritten = false;
+        void reset() { pairs.clear(); order.clear(); src.clear(); ready = order_uploaded = src_uploaded = rewritten = false; node_words = tri_doubles = base_node_words = base_tri_doubles = 0; }
         void release() {
-            for (DeviceBuf* b : {&d_order, &d_first, &d_cursor, &d_idx, &d_small, &d_scan, &d_edges}) b->release();
+            for (DeviceBuf* b : {&d_order, &d_src, &d_first, &d_cursor, &d_idx, &d_small, &d_scan, &d_edges}) b->release();
             for (DeviceBuf& b : d_ebox) b.release();
             for (DeviceBuf& b : d_counts) b.release();
             d_ebox.clear(); d_counts.clear(); reset();

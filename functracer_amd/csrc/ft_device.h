@@ -257,6 +257,10 @@ void refit_cost(hipStream_t stream, const RefitArrays& A, const RefitMesh& m, do
 // leaf children from their records in ls_tris, node children from the boxes the call before wrote.
 struct LsFrame { double U[3], V[3], D[3], c[3], pad; };
 void ls_refit_level(hipStream_t stream, uint32_t* ls_nodes, uint32_t n_nodes, const double* ls_tris, uint32_t n_tris, const uint32_t* order, uint32_t count, const LsFrame& F);
+// The leaf records of a tree whose mesh was refit (k_ls_gather): ls_tris[ls_first + i] = tris[src[i]] bitwise, i < count, for every src[i]
+// inside the mesh's list-order records [mesh_first, mesh_first + mesh_n); n_tris, n_ls: the sizes of tris and ls_tris in records.
+void ls_gather(hipStream_t stream, const double* tris, uint32_t n_tris, uint32_t mesh_first, uint32_t mesh_n, const uint32_t* src, uint32_t count, double* ls_tris, uint32_t n_ls,
+               uint32_t ls_first);
 // The grid of such a pair built again (ft_scene.cpp, build_grid, its host loops as passes; tris: the mesh's n list-order records in HBM):
 //   ls_grid_entries     ebox[5 k ..] = triangle k's entry box; ruv (zeroed by the caller, or null): the bits of Ru and Rv
 //   ls_grid_count       sums[a] (zeroed by the caller) += the cells every entry covers under candidate a of build_grid's attempt loop

@@ -9,6 +9,10 @@
 // builder's own unfused arithmetic, and rounds outward to float through the device twins of f_down / f_up; a node child takes the union of
 // that node's four child boxes, which the level before wrote (a union of floats is exact, and f_down / f_up are monotone, so the result is
 // what the host's widen computes from the union in double).  Empty slots keep their NaN boxes.
+//
+// The same passes serve a mesh whose vertices changed (ft_scene_commit_deformed under "deform_light_space"): there the
+// frame stays and the centre, the pad and the leaf records change, so k_ls_gather first copies the refit list-order records into the
+// tree's leaves, and k_ls_refit and the grid passes then run as for a turned light.
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_scan.hpp>
 
@@ -75,6 +79,22 @@ __global__ __launch_bounds__(256) void k_ls_refit(uint32_t* __restrict__ nodes, 
         }
         for (int k = 0; k < 5; ++k) N[5 * c + k] = __float_as_uint(box[k]);
     }
+}
+
+// ---- the leaf records of a pair's tree after its mesh was refit (ft_scene_commit_deformed under "deform_light_space") ----
+// One lane per leaf record of the tree: ls_tris[ls_first + i] becomes the bitwise copy of tris[src[i]] again, the list-order record
+// k_refit_records has just written for the triangle that record copied at the full commit (fth::FlatScene::ls_src).  An index outside the
+// mesh's list-order range [mesh_first, mesh_first + mesh_n), outside tris (n_tris records) or outside ls_tris (n_ls records) writes nothing.
+__global__ __launch_bounds__(256) void k_ls_gather(const double* __restrict__ tris, uint32_t n_tris, uint32_t mesh_first, uint32_t mesh_n, const uint32_t* __restrict__ src,
+                                                   uint32_t count, double* __restrict__ ls_tris, uint32_t n_ls, uint32_t ls_first) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= count) return;
+    const uint32_t s = src[i];
+    const uint64_t d = (uint64_t)ls_first + i;
+    if (s < mesh_first || s - mesh_first >= mesh_n || s >= n_tris || d >= n_ls) return;
+    const double* T = tris + 9ull * s;
+    double* O = ls_tris + 9ull * d;
+    for (int q = 0; q < 9; ++q) O[q] = T[q];
 }
 
 // ---- the grid of a pair, built again (ft_scene.cpp, build_grid, with its host loops as passes) ----------------------------------------
@@ -227,6 +247,12 @@ void ls_grid_emit(hipStream_t stream, const float* ebox, const double* tris, uin
                   uint32_t* cursor, uint32_t* idx, uint32_t n_entries, uint32_t* ls_nodes, uint32_t at, double* ls_tris, uint32_t tri_at) {
     hipLaunchKernelGGL(k_ls_cells<true>, dim3((n + 255u) / 256u), dim3(256), 0, stream, ebox, n, s, nu, nv, cursor, first, idx, n_entries);
     hipLaunchKernelGGL(k_ls_emit, dim3((nu * nv + 3u) / 4u), dim3(256), 0, stream, ebox, tris, n, idx, counts, first, nu * nv, n_entries, ls_nodes, at, ls_tris, tri_at);
+}
+
+void ls_gather(hipStream_t stream, const double* tris, uint32_t n_tris, uint32_t mesh_first, uint32_t mesh_n, const uint32_t* src, uint32_t count, double* ls_tris, uint32_t n_ls,
+               uint32_t ls_first) {
+    if (count == 0u) return;
+    hipLaunchKernelGGL(k_ls_gather, dim3((count + 255u) / 256u), dim3(256), 0, stream, tris, n_tris, mesh_first, mesh_n, src, count, ls_tris, n_ls, ls_first);
 }
 
 void ls_refit_level(hipStream_t stream, uint32_t* nodes, uint32_t n_nodes, const double* tris, uint32_t n_tris, const uint32_t* order, uint32_t count, const LsFrame& F) {

@@ -931,7 +931,10 @@ struct LsBuilder {
         bn.push_back(BNode{r, -1, -1, 0, 0});
         if (hi - lo <= kLeafTris) {                                            // bitwise copies of the mesh's own records
             bn[(size_t)node].first = (uint32_t)(out.ls_tris.size() / 9); bn[(size_t)node].count = (uint32_t)(hi - lo);
-            for (size_t k = lo; k < hi; ++k) out.ls_tris.insert(out.ls_tris.end(), &out.tris[9 * (size_t)items[k].rec], &out.tris[9 * (size_t)items[k].rec] + 9);
+            for (size_t k = lo; k < hi; ++k) {
+                out.ls_tris.insert(out.ls_tris.end(), &out.tris[9 * (size_t)items[k].rec], &out.tris[9 * (size_t)items[k].rec] + 9);
+                out.ls_src.push_back(items[k].rec);
+            }
             return node;
         }
         int axis = cr.hi[1] - cr.lo[1] > cr.hi[0] - cr.lo[0] ? 1 : 0;
@@ -1082,6 +1085,7 @@ bool build_grid(FlatScene& out, const LsBuilder& B, uint64_t& bytes, double* rec
             std::memcpy(&out.ls_nodes[box], es[k].box, sizeof es[k].box);
             box += 5;
             out.ls_tris.insert(out.ls_tris.end(), &out.tris[9 * (size_t)es[k].rec], &out.tris[9 * (size_t)es[k].rec] + 9);
+            out.ls_src.push_back(es[k].rec);
         }
     }
     out.ls_nodes.resize((out.ls_nodes.size() + ftd::kLsNodeWords - 1) / ftd::kLsNodeWords * ftd::kLsNodeWords, 0u);
@@ -1123,9 +1127,25 @@ bool ls_pair_frame(const ftd::Leaf& L, const ftd::Light& light, LsPairFrame& out
     return true;
 }
 
+double ls_pair_extent(const double* tris, size_t n, bool vertices, const double c[3]) {
+    double R = 0.0;
+    for (size_t k = 0; k < n; ++k) {
+        const double* T = tris + 9 * k;
+        for (int v = 0; v < 3; ++v) {
+            double p[3];
+            for (int q = 0; q < 3; ++q) {
+                const double e = v == 0 ? 0.0 : vertices ? T[3 * v + q] - T[q] : T[3 * v + q];
+                p[q] = (T[q] - c[q]) + e;
+            }
+            R = std::max(R, std::fabs(p[0]) + std::fabs(p[1]) + std::fabs(p[2]));
+        }
+    }
+    return R;
+}
+
 void build_light_space(FlatScene& out, bool grids) {
     for (auto& L : out.leaves) L.ls_pairs = ~0u;
-    out.ls_pairs.clear(); out.ls_nodes.clear(); out.ls_tris.clear();
+    out.ls_pairs.clear(); out.ls_nodes.clear(); out.ls_tris.clear(); out.ls_src.clear();
     std::vector<uint32_t> dirs;
     for (uint32_t l = 0; l < (uint32_t)out.lights.size(); ++l) if (out.lights[l].kind == ftd::LT_DIRECTIONAL) dirs.push_back(l);
     if (dirs.empty()) return;

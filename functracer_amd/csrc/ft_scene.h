@@ -65,6 +65,9 @@ struct FlatScene {
     std::vector<double> ls_pairs;
     std::vector<uint32_t> ls_nodes;
     std::vector<double> ls_tris;
+    // Per record the builders appended to ls_tris, the record of `tris` it is a bitwise copy of.  Host only: no commit uploads it; the first
+    // ft_scene_commit_deformed under "deform_light_space" uploads the trees' part (ft_lightspace.hip, k_ls_gather).
+    std::vector<uint32_t> ls_src;
     // Meshes whose exact BVH is built on the device after the upload (ft_bvh.hip): the flattener only reserves their ranges.
     struct BvhJob { uint32_t mesh, first_global, n, node_base, leaf_base, tri_base, wide_base, coarse_first, coarse_count; };
     std::vector<BvhJob> bvh_jobs;
@@ -124,6 +127,9 @@ void build_light_space(FlatScene& out, bool grids);
 // What build_light_space derives from a leaf's w2m and a light's direction alone, for ft_scene_commit_lights to derive again.
 struct LsPairFrame { double U[3], V[3], D[3], k_rel; };
 bool ls_pair_frame(const ftd::Leaf& L, const ftd::Light& light, LsPairFrame& out);
+// R of a pair as build_light_space sums it - the largest L1 distance of a vertex from c, (T[q] - c[q]) + e - over n triangles given as
+// records (v0, e1, e2) or, `vertices`, as corners (a, b, c), of which the records are formed as the flattener forms them.
+double ls_pair_extent(const double* tris, size_t n, bool vertices, const double c[3]);
 
 // Triangle.slice (Triangle.fs:24-41) exposed for the known-answer tests of the product's own builder.
 int32_t slice_triangle(const double p0[3], const double n[3], const double tri[9],

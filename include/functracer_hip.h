@@ -185,6 +185,10 @@ const char* ft_last_error(const ft_context* ctx);
  * "refit_rebuild_percent" (0 = default: never; 100 .. 1000000: ft_scene_commit_deformed builds the tree of an edited, device-built mesh again in place once
  * its measured cost x 100 exceeds this x its cost as built - "deforming meshes" below; any other value is refused.  It is read by ft_scene_commit_deformed
  * alone and needs no new ft_scene_commit),
+ * "deform_light_space" (0 = default; any other value means 1: ft_scene_commit_deformed refits the light-space shadow trees of the meshes it edits and builds their
+ * grids again on the device instead of stripping them - "deforming meshes" below.  It is read by ft_scene_commit_deformed alone and needs no new
+ * ft_scene_commit; a host-only context accepts it without effect, because its deformed commit is the full host commit, which builds the structures anyway; with 0
+ * every call launches the kernels and gives the bits it gave before the option existed),
  * "temporal_follow_deformed" (0 = default; any other value means 1: ft_scene_commit_deformed keeps the triangle records of the meshes it refits as the open
  * temporal accumulation last saw them, and the next ft_temporal_accumulate takes every pixel on a changed triangle back to where that point of the triangle was -
  * "history on deforming meshes" below.  It needs no new ft_scene_commit; a host-only or multi-device context accepts it without effect, because the accumulation
@@ -660,6 +664,31 @@ int32_t ft_scene_commit_moved(ft_context* ctx);
  * "light_space_shadows" 1 / 2: the light-space trees and grids are built on the host from the vertices and are NOT refit.  Every leaf of
  * an edited mesh loses its pair records (ft_debug_light_space: 0xFFFFFFFF), so its directional shadow rays walk the refit BVH as option 0
  * does - the same bits - until the next full ft_scene_commit brings the structures back.
+ * With ft_set_option("deform_light_space", 1) they are refit instead.  After a successful call every pair of an edited mesh that had a
+ * tree at the last full commit, and whose leaf no earlier call stripped, still has one, and under option 2 a grid wherever the full
+ * commit's rules give one:
+ *  - the pair record's doubles [0..13] are what a fresh full commit of the new vertices writes, bit for bit: the frame and k_rel stay, c
+ *    is the centre of the new mesh bounds, R the largest L1 distance of a new vertex from c in the full commit's arithmetic,
+ *    s_abs = (k_rel + 1e-6) * R + 1e-20.  With R from 2e29 on the pair gets root INT32_MIN and no grid (the rule of
+ *    ft_scene_commit_lights; its rays walk the BVH - the same bits) until a later deformation brings R back;
+ *  - the tree keeps the full commit's topology; every leaf record becomes the new record of the triangle it copied (k_ls_gather, by a table
+ *    the flattener keeps: duplicates that deform apart stay apart) and every box is written again about the new c with pad 1e-7 * R + 1e-30;
+ *  - the grid is built again from the refit list-order records by the passes of ft_scene_commit_lights, so its resolution, cells, entry
+ *    boxes, records and their order are a fresh commit's; the edge records follow.
+ * Every later call gives a fresh context's bits, frames and counters, as above; the temporal accumulation stays open, the pose counter
+ * stays, and "refit_rebuild_percent" and "temporal_follow_deformed" compose (neither touches list-order records after the refit).  A leaf
+ * stripped by an earlier call with the option at 0 stays stripped until the next full commit.  A deformed pair's grid lies with the
+ * moving lights' grids behind the full commit's arrays (ft_scene_commit_lights below): a call that edits a mesh with pairs lays that
+ * region out anew and builds every grid in it again, the ones of other meshes whose lights have turned included, and from then on
+ * ft_scene_commit_lights never gives such a pair the full commit's record or grid back, not even at that commit's direction - both
+ * describe vertices that are gone.  The full commit's own grids of deformed pairs stay in that commit's arrays, unused, and count against
+ * the 256 MiB cap until the next full commit.  On a multi-device context the first device takes the decisions that need a readback and
+ * every device carries them out.  ft_get_commit_times: [1] includes the gather, tree and grid kernels with their readbacks, [2] the uploads.
+ * What it is worth (MI355X, the 69.6 K-face mesh under one directional light, 1920 x 1080 x 16, tools/deform_shadow_rate.py, DESIGN.md
+ * 16.3): after 1, 4 and 16 steps of a twist of 0.05 rad per step k_primary takes 1.05, 1.09 and 2.68 times a fresh commit's time and 0.79,
+ * 0.83 and 2.22 times what it takes with the option at 0.  The grid is a fresh commit's, but the tree that wide waves fall back to keeps
+ * the rest pose's topology and decays: at 6 steps (0.3 rad) the option makes no difference, from 8 steps (0.4 rad) on it costs.  The call
+ * itself takes 2.7 ms instead of 0.95 ms; a full commit takes 86 ms.  The library does not decide when to fall back: the default is 0.
  * Tree quality: the refit tree is the OLD vertices' tree around the new ones, so its boxes overlap more the further the mesh moves from
  * the pose it was built in, and the walk slows down while the results stay exact.  The library measures how far that has gone:
  * ft_scene_tree_quality(mesh_node, out) gives the surface-area cost of the mesh's binary tree as it lies in device memory,
@@ -725,7 +754,7 @@ int32_t ft_scene_tree_quality(ft_context* ctx, ft_node mesh_node, double out[4])
  * other kinds of light are an upload alone.  A direction that is zero, not finite or ill-conditioned in the leaf's model space gets root
  * INT32_MIN and no grid (its rays walk the BVH) until a later call gives it a usable direction again; a pair that had no tree at the last
  * full commit, and the pairs ft_scene_commit_deformed stripped, stay without one until the next full commit; a light back at the direction
- * of the last full commit gets that commit's record and grid back.  The grids built since the full commit lie behind that commit's
+ * of the last full commit gets that commit's record and grid back (unless its mesh has been deformed under "deform_light_space" since).  The grids built since the full commit lie behind that commit's
  * arrays in freshly sized arrays that every call which turns a light lays out anew, so repeated calls do not grow memory; the bytes the
  * cap (256 MiB) counts include the full commit's arrays whole.  Once a call has rewritten anything ft_debug_light_space answers from device
  * memory.
