@@ -15,7 +15,7 @@ from . import _capi
 from ._capi import (CIRCLE, CONE, CUBE, CYLINDER, EXCLUDE, INTERSECT, PLANE, SOLID_CYLINDER, SPHERE, SQUARE, SUBTRACT, UNION,
                     FtError, SceneBuilder, make_camera)
 
-__all__ = ["Context", "PinnedArray", "ParsedScene", "parse_scene", "parse_scene_file", "jitter_pattern", "quantise_rgba8", "write_png",
+__all__ = ["Context", "ls_topology", "PinnedArray", "ParsedScene", "parse_scene", "parse_scene_file", "jitter_pattern", "quantise_rgba8", "write_png",
            "parse_colour", "parse_ply", "FtError", "make_camera", "HIP_LIB", "HOST_LIB", "DEFAULT_SEED"]
 
 HIP_LIB = os.environ.get("FT_HIP_LIB") or os.path.join(_capi.LIB_DIR, "libfunctracer_hip.so")   # FT_HIP_LIB: experimental builds
@@ -737,6 +737,23 @@ class Context(SceneBuilder):
         self._check(fn(self._ctx, sizes, grid.ctypes.data, lists.ctypes.data))
         return {"grid": grid[:sizes[0]], "lists": lists[:sizes[1]]}
 
+    def ls_retree(self):
+        """ft_debug_ls_retree: the pairs ft_scene_commit_lights / ft_scene_commit_deformed keep track of since the last full commit (option
+        "light_space_retree") - a list of dicts, one per pair: `rec` (its pair record), `leaf`, `light`, `n_tris`, `ls_first` (the first of
+        its tree's leaf records, -1: none), `R`, `retreed`, `block` (the first node of its block, -1: none) and `block_nodes` (N)."""
+        fn = self._lib.ft_debug_ls_retree
+        fn.restype, fn.argtypes = C.c_int32, [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p]
+        n = C.c_int64()
+        self._check(fn(self._ctx, C.byref(n), None, None))
+        rows, R = np.zeros((n.value, 8), dtype=np.int64), np.zeros(n.value)
+        self._check(fn(self._ctx, C.byref(n), rows.ctypes.data, R.ctypes.data))
+        out = []
+        for row, r in zip(rows[:n.value], R):
+            d = dict(zip(_capi.LS_RETREE_FIELDS, (int(v) for v in row)))
+            d["retreed"], d["R"] = bool(d["retreed"]), float(r)
+            out.append(d)
+        return out
+
     def classify_reuse(self):
         """ft_debug_classify_reuse: what the frames queued since the context was created did with their classifications (option
         "classify_reuse"), summed over its devices - a dict of `classified` (k_classify launched), `reused` (a slot's kept classification
@@ -767,6 +784,23 @@ def rays_handled_by(kernel, st):
         return generated + st["rays_shadow_primary"]
     # k_bounce ("shade"): the reflection rays of every level >= 1 and the shadow rays of their hits
     return st["rays_reflect"] + st["rays_shadow"] - st["rays_shadow_primary"]
+
+
+def ls_topology(n, ls_first, first_node):
+    """ft_debug_ls_topology: the tree option "light_space_retree" gives n sorted leaf records from ls_first on in a block of nodes from
+    first_node on, as the host generates it - (child words N x 4 int32, order N uint32, levels k x 2 uint32: offset into order and count,
+    deepest level first)."""
+    fn = hip_lib().ft_debug_ls_topology
+    fn.restype, fn.argtypes = C.c_int32, [C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_void_p]
+    sizes = (C.c_int64 * 2)()
+    rc = fn(n, ls_first, first_node, sizes, None, None, None)
+    if rc < 0:
+        raise FtError(rc, "ls_topology")
+    child, order, levels = np.zeros((sizes[0], 4), dtype=np.int32), np.zeros(sizes[0], dtype=np.uint32), np.zeros((sizes[1], 2), dtype=np.uint32)
+    rc = fn(n, ls_first, first_node, sizes, child.ctypes.data, order.ctypes.data, levels.ctypes.data)
+    if rc < 0:
+        raise FtError(rc, "ls_topology")
+    return child, order, levels
 
 
 def debug_slice(p0, n, tri):

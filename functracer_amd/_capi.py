@@ -187,6 +187,8 @@ LIST_ENTRY_DTYPE = np.dtype([("tri", np.uint32), ("orig", np.uint32), ("x0", np.
 LIST_NONE = 0xFFFFFFFF
 # ft_debug_edge_records: a record is three lines (a, b, c) as floats (ft_device.h, kEdgeFloats)
 EDGE_RECORD_SHAPE = (3, 3)
+# ft_debug_ls_retree: the eight values of a pair's row, in order ("light_space_retree")
+LS_RETREE_FIELDS = ("rec", "leaf", "light", "n_tris", "ls_first", "retreed", "block", "block_nodes")
 
 
 class fth_options(C.Structure):

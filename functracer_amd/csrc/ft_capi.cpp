@@ -3,6 +3,7 @@
 // the features over it ft_progressive.cpp and ft_passes.cpp, the test entry points ft_debug.cpp.
 // Reference citations are relative to FuncTracer/ of the reference (antonburger/FuncTracer).
 #include "ft_context.h"
+#include "ft_ls_topology.h"
 #include "ft_refit_cost.h"
 
 namespace ftc {
@@ -200,6 +201,8 @@ const OptionSpec kOptions[] = {
     {"refit_rebuild_percent", 100, 1000000, &Options::refit_rebuild_percent, nullptr, kOrZero},
     // read by ft_scene_commit_deformed alone, as the one above (any value other than 0 means 1)
     {"deform_light_space", 0, 1, &Options::deform_light_space, nullptr, kFlag},
+    // read by ft_scene_commit_lights and ft_scene_commit_deformed alone, as the ones above (any value other than 0 means 1)
+    {"light_space_retree", 0, 1, &Options::light_space_retree, nullptr, kFlag},
     {"csg_mesh_capacity", 1, 255, nullptr, [](fth::SceneGraph& g, int64_t v) { g.csg_mesh_capacity = (int32_t)v; }, kCommit},
     // directional shadow rays of coherent waves: 0 the BVH; 1 light-space trees; 2 (default) light-space grids, the trees for wide waves.
     // It was a flag before the grids: it still takes any value, and any other than 0 / 1 means 2.
@@ -854,9 +857,11 @@ static void derive_light_space_tables(const fth::FlatScene& f, ft_context::Light
 // gather: its mesh was refit in this call (ft_scene_commit_deformed, "deform_light_space"), so the tree's leaf records are copied again
 // from the mesh's list-order records before anything reads them - also where the record is unusable and nothing else is done, so that the
 // tree is current whenever a later call refits its boxes.
+// retree ("light_space_retree"): the tree that is refit is the one in the pair's block, over leaf records sorted again
+// along the Morton curve of the current projection before they are copied.
 struct LightJob {
     const ft_context::LightSpace::Pair* pair; ftk::LsFrame frame; bool refit, regrid;
-    bool gather = false;
+    bool gather = false, retree = false;
     bool grid = false; float s = 0.0f; uint32_t nu = 0, nv = 0, entries = 0, at = 0, tri_at = 0;
     size_t slot = 0;                                                // of the device's per-pair scratch (ft_context::LightSpace::d_ebox, d_counts)
 };
@@ -865,7 +870,9 @@ struct LightJob {
 // from the pair's current centre and R as build_light_space derives it, and the pair's job: its tree refit (`refit`: the direction or the
 // vertices changed in this call), its grid built again behind the full commit's arrays (`grids`: the scene has them).  No usable frame,
 // or R from 2e29 on: root INT32_MIN and no grid - its rays walk the BVH, and the tree's nodes and records stay where they are.
-static void moved_pair_job(fth::FlatScene& f, const ft_context::LightSpace::Pair& P, const ftd::Light& light, bool refit, bool gather, bool grids, std::vector<LightJob>& jobs, size_t& n_regrid) {
+// `retree`: the option is on - a pair that is refit here and has a block takes the block's tree from now on.
+static void moved_pair_job(fth::FlatScene& f, ft_context::LightSpace::Pair& P, const ftd::Light& light, bool refit, bool gather, bool grids, bool retree, std::vector<LightJob>& jobs,
+                           size_t& n_regrid) {
     double* rec = &f.ls_pairs[(size_t)ftd::kLsPairDoubles * P.rec];
     LightJob j{&P, {}, false, false};
     j.gather = gather;
@@ -873,6 +880,10 @@ static void moved_pair_job(fth::FlatScene& f, const ft_context::LightSpace::Pair
     fth::LsPairFrame fr;
     // (every projected coordinate is at most R in size: the builder's finiteness test, five of them below 1e30, holds with R < 2e29)
     const bool usable = fth::ls_pair_frame(f.leaves[P.leaf], light, fr) && P.R < 2e29;
+    if (usable && refit && retree && P.block != ~0u && P.ls_first != ~0u) {
+        j.retree = true;
+        if (!P.retreed) { P.retreed = true; P.root = (int32_t)P.block; P.levels = P.block_levels; }
+    }
     const int32_t root = usable ? P.root : INT32_MIN;               // none: the tree's nodes and records stay where they are for the direction's return
     std::memcpy(&rec[14], &root, 4);
     if (usable) {
@@ -883,6 +894,26 @@ static void moved_pair_job(fth::FlatScene& f, const ft_context::LightSpace::Pair
         if (j.regrid) j.slot = n_regrid++;
     }
     if (usable || gather) jobs.push_back(j);
+}
+
+// "light_space_retree", the first call under the option since the full commit: where every pair's block of nodes lies behind that commit's
+// nodes (ft_ls_topology.h), the blocks' child words, and their levels behind the trees' in `order`.
+static void lay_retree_blocks(ft_context::LightSpace& T) {
+    std::vector<uint32_t> n(T.pairs.size(), 0u), block;
+    for (size_t k = 0; k < T.pairs.size(); ++k) if (T.pairs[k].ls_first != ~0u && T.pairs[k].src_at + (size_t)T.pairs[k].n_tris <= T.src.size()) n[k] = T.pairs[k].n_tris;
+    const uint64_t nodes = fth::ls_retree_layout(n, T.base_node_words / ftd::kLsNodeWords, (uint64_t)T.base_node_words * 4 + (uint64_t)T.base_tri_doubles * 8, ftd::kLsMaxBytes, block);
+    T.block_init.assign((size_t)nodes * ftd::kLsNodeWords, fth::kLsTopoNaN);
+    fth::LsTopology topo;
+    for (size_t k = 0; k < T.pairs.size(); ++k) {
+        ft_context::LightSpace::Pair& P = T.pairs[k];
+        if (block[k] == ~0u || !fth::ls_retree_topology(P.n_tris, P.ls_first, block[k], topo)) continue;
+        P.block = block[k]; P.block_nodes = (uint32_t)(topo.nodes.size() / ftd::kLsNodeWords);
+        std::copy(topo.nodes.begin(), topo.nodes.end(), T.block_init.begin() + ((size_t)block[k] * ftd::kLsNodeWords - T.base_node_words));
+        for (const auto& lv : topo.levels) P.block_levels.push_back({(uint32_t)T.order.size() + lv.first, lv.second});
+        T.order.insert(T.order.end(), topo.order.begin(), topo.order.end());
+    }
+    T.block_words = T.block_init.size();
+    T.blocks_laid = true;
 }
 
 // build_grid's decisions for one pair (ft_scene.cpp), its host loops run as passes on the device: readback 1 Ru and Rv, readback 2 the
@@ -954,12 +985,12 @@ static int32_t rebuild_light_space(ft_context* c, fth::FlatScene& f, const ft_co
     DeviceBuf* B = c->d_scene;
     ft_context::LightSpace& L = c->lightspace;
     if (L.node_words == 0) { L.node_words = T.base_node_words; L.tri_doubles = T.base_tri_doubles; }   // the first call since the upload
-    if (!jobs.empty() && !L.order_uploaded) {
+    if (!jobs.empty() && (!L.order_uploaded || L.order_words != T.order.size())) {   // (the blocks' levels were appended since: "light_space_retree")
         if ((rc = upload(c, L.d_order, T.order)) != FT_OK) return rc;
-        L.order_uploaded = true;
+        L.order_uploaded = true; L.order_words = T.order.size();
     }
-    bool gathers = false;
-    for (const LightJob& j : jobs) gathers = gathers || j.gather;
+    bool gathers = false, retrees = false;
+    for (const LightJob& j : jobs) { gathers = gathers || j.gather || j.retree; retrees = retrees || j.retree; }
     if (gathers && !L.src_uploaded) {
         if ((rc = upload(c, L.d_src, T.src)) != FT_OK) return rc;
         L.src_uploaded = true;
@@ -967,14 +998,44 @@ static int32_t rebuild_light_space(ft_context* c, fth::FlatScene& f, const ft_co
     FT_HIP(c, hipStreamSynchronize(c->stream));
     ms[0] += since(t0);
     const auto t1 = clock::now();
-    if (B[kLsNodes].bytes < L.node_words * 4 || B[kLsTris].bytes < L.tri_doubles * 8 || L.node_words < T.base_node_words || L.tri_doubles < T.base_tri_doubles ||
+    if (B[kLsNodes].bytes < L.node_words * 4 || B[kLsTris].bytes < L.tri_doubles * 8 || L.node_words < T.base_node_words + L.block_words_here || L.tri_doubles < T.base_tri_doubles ||
         B[kTris].bytes < f.tris.size() * 8) { c->err = std::string(who) + ": a scene array in device memory is smaller than the flattened one"; return FT_ERR_STATE; }
-    const uint32_t n_nodes = (uint32_t)(T.base_node_words / ftd::kLsNodeWords), n_tris = (uint32_t)(T.base_tri_doubles / 9);   // the trees lie in the full commit's part
-    size_t slots = 0;
     bool regrid = relay;                                            // a light turned: the region behind the full commit's arrays is laid out anew, be it to nothing
+    if (retrees && L.block_words_here != T.block_words) {
+        // "light_space_retree", this device's first retree since the full commit: the blocks take their place behind that commit's nodes.
+        // What lay there - the grids of earlier calls - is laid out anew below, behind the blocks: every pair that has one there has a job.
+        const size_t front = T.base_node_words + T.block_words;
+        DeviceBuf nodes;
+        if ((rc = ensure(c, nodes, front * 4)) != FT_OK) { nodes.release(); return rc; }
+        if (hipMemcpyAsync(nodes.p, B[kLsNodes].p, T.base_node_words * 4, hipMemcpyDeviceToDevice, c->stream) != hipSuccess ||
+            hipMemcpyAsync(nodes.as<uint32_t>() + T.base_node_words, T.block_init.data(), T.block_words * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+            hipStreamSynchronize(c->stream) != hipSuccess) { nodes.release(); c->err = std::string(who) + ": laying out the retree blocks failed"; return FT_ERR_HIP; }
+        B[kLsNodes].release();
+        B[kLsNodes] = nodes;
+        c->dev_scene.ls_nodes = static_cast<std::remove_reference_t<decltype(c->dev_scene.ls_nodes)>>(nodes.p);
+        L.node_words = front; L.block_words_here = T.block_words;
+        L.rewritten = true; regrid = true;
+    }
+    const size_t front = T.base_node_words + L.block_words_here;    // the full commit's nodes and the blocks: what every call carries forward
+    const uint32_t n_nodes = (uint32_t)(front / ftd::kLsNodeWords), n_tris = (uint32_t)(T.base_tri_doubles / 9);   // the trees lie in that part
+    size_t slots = 0;
     for (const LightJob& j : jobs) {                                // (a pair's tree lies apart from every other's: one pass over the jobs keeps each tree's order)
         if (j.regrid) slots = std::max(slots, j.slot + 1);
-        if (j.gather && j.pair->src_at + (size_t)j.pair->n_tris <= T.src.size()) {
+        const bool sorts = j.retree && j.pair->src_at + (size_t)j.pair->n_tris <= T.src.size() && (size_t)j.pair->first_tri + j.pair->n_tris <= f.tris.size() / 9;
+        if (sorts) {
+            // the pair's part of d_src becomes its list-order triangles sorted by the Morton code of their centres in the job's frame
+            // (stable: equal codes keep the list order); the gather below and every later one copy the records in that order
+            const uint32_t n = j.pair->n_tris;
+            size_t sort_bytes = 0;
+            if (ftk::ls_sort_pairs(c->stream, nullptr, nullptr, nullptr, nullptr, n, nullptr, &sort_bytes) != hipSuccess) { c->err = std::string(who) + ": sizing the sort failed"; return FT_ERR_HIP; }
+            if ((rc = ensure(c, L.d_keys, (size_t)n * 12)) != FT_OK || (rc = ensure(c, L.d_sort, sort_bytes)) != FT_OK) return rc;
+            uint32_t* keys = L.d_keys.as<uint32_t>();               // n keys, n sorted keys, n values
+            ftk::ls_morton_keys(c->stream, B[kTris].as<double>(), (uint32_t)(f.tris.size() / 9), j.pair->first_tri, n, j.frame, j.pair->R, keys, keys + 2 * (size_t)n);
+            if (ftk::ls_sort_pairs(c->stream, keys, keys + n, keys + 2 * (size_t)n, L.d_src.as<uint32_t>() + j.pair->src_at, n, L.d_sort.p, &sort_bytes) != hipSuccess) {
+                c->err = std::string(who) + ": the sort failed"; return FT_ERR_HIP;
+            }
+        }
+        if ((j.gather || sorts) && j.pair->src_at + (size_t)j.pair->n_tris <= T.src.size()) {
             ftk::ls_gather(c->stream, B[kTris].as<double>(), (uint32_t)(f.tris.size() / 9), j.pair->first_tri, j.pair->n_tris, L.d_src.as<uint32_t>() + j.pair->src_at, j.pair->n_tris,
                            B[kLsTris].as<double>(), n_tris, j.pair->ls_first);
             L.rewritten = true;
@@ -985,13 +1046,13 @@ static int32_t rebuild_light_space(ft_context* c, fth::FlatScene& f, const ft_co
         L.rewritten = true;
     }
     FT_HIP(c, hipGetLastError());
-    size_t words = T.base_node_words, doubles = T.base_tri_doubles;   // the arrays' sizes: the full commit's part, the grids behind it
+    size_t words = front, doubles = T.base_tri_doubles;             // the arrays' sizes: the full commit's part and the blocks, the grids behind them
     if (regrid) {
         if (L.d_ebox.size() < slots) { L.d_ebox.resize(slots); L.d_counts.resize(slots); }
         if ((rc = ensure(c, L.d_small, 128)) != FT_OK) return rc;
         if (lead) {                                                 // the decisions that need a readback, and with them the layout
-            uint64_t bytes = (uint64_t)T.base_node_words * 4 + (uint64_t)T.base_tri_doubles * 8;
-            size_t at = T.base_node_words, recs = T.base_tri_doubles / 9;
+            uint64_t bytes = (uint64_t)front * 4 + (uint64_t)T.base_tri_doubles * 8;
+            size_t at = front, recs = T.base_tri_doubles / 9;
             for (LightJob& j : jobs) {
                 if (!j.regrid) continue;
                 if ((rc = plan_grid(c, j, bytes)) != FT_OK) return rc;
@@ -1011,16 +1072,16 @@ static int32_t rebuild_light_space(ft_context* c, fth::FlatScene& f, const ft_co
             words = std::max(words, (size_t)j.at + (own + ftd::kLsNodeWords - 1) / ftd::kLsNodeWords * ftd::kLsNodeWords);
             doubles = std::max(doubles, 9 * ((size_t)j.tri_at + j.entries));
         }
-        if (words == T.base_node_words && doubles == T.base_tri_doubles && words == L.node_words && doubles == L.tri_doubles) regrid = false;   // no grid before, none now
+        if (words == front && doubles == T.base_tri_doubles && words == L.node_words && doubles == L.tri_doubles) regrid = false;   // no grid before, none now
     }
     if (regrid) {
         // Fresh arrays of exactly that size: the full commit's part as it lies in HBM now (the refit trees in it), the grids behind it.
         DeviceBuf nodes, tris;
         if ((rc = ensure(c, nodes, words * 4)) != FT_OK || (rc = ensure(c, tris, doubles * 8)) != FT_OK) { nodes.release(); tris.release(); return rc; }
         const auto fail = [&](int32_t code) { nodes.release(); tris.release(); return code; };
-        if (hipMemcpyAsync(nodes.p, B[kLsNodes].p, T.base_node_words * 4, hipMemcpyDeviceToDevice, c->stream) != hipSuccess ||
+        if (hipMemcpyAsync(nodes.p, B[kLsNodes].p, front * 4, hipMemcpyDeviceToDevice, c->stream) != hipSuccess ||
             hipMemcpyAsync(tris.p, B[kLsTris].p, T.base_tri_doubles * 8, hipMemcpyDeviceToDevice, c->stream) != hipSuccess ||
-            (words > T.base_node_words && hipMemsetAsync(nodes.as<uint32_t>() + T.base_node_words, 0, (words - T.base_node_words) * 4, c->stream) != hipSuccess) ||
+            (words > front && hipMemsetAsync(nodes.as<uint32_t>() + front, 0, (words - front) * 4, c->stream) != hipSuccess) ||
             (doubles > T.base_tri_doubles && hipMemsetAsync(tris.as<double>() + T.base_tri_doubles, 0, (doubles - T.base_tri_doubles) * 8, c->stream) != hipSuccess)) {
             c->err = std::string(who) + ": copying the light-space arrays failed"; return fail(FT_ERR_HIP);
         }
@@ -1148,6 +1209,8 @@ int32_t ft_scene_commit_deformed(ft_context* c) {
     const bool keep_ls = c->opt.deform_light_space != 0 && c->graph.light_space_shadows != 0;
     ft_context::LightSpace& T = c->lightspace;
     if (keep_ls && !T.ready) derive_light_space_tables(f, T);
+    const bool retree = keep_ls && c->opt.light_space_retree != 0;
+    if (retree && !T.blocks_laid) lay_retree_blocks(T);
     std::vector<double> bounds = f.mesh_bounds;
     for (const DeformedMesh& e : edits) for (int k = 0; k < 6; ++k) bounds[6 * (size_t)e.mesh + k] = e.scan.bounds[k];
     int32_t rc = c->graph.reflatten_deformed(f, bounds, c->err);   // the cull records, by the flattener's own walk
@@ -1179,10 +1242,10 @@ int32_t ft_scene_commit_deformed(ft_context* c) {
             P.deformed = true;
             touched = true;
         }
-        for (const ft_context::LightSpace::Pair& P : T.pairs) {
+        for (ft_context::LightSpace::Pair& P : T.pairs) {
             if (!touched || f.leaves[P.leaf].ls_pairs == ~0u) continue;
             const bool now = P.mesh < edited.size() && edited[P.mesh];
-            if (now || P.deformed || std::memcmp(f.lights[P.light].v, P.v0, sizeof P.v0) != 0) moved_pair_job(f, P, f.lights[P.light], now, now, grids, jobs, n_regrid);
+            if (now || P.deformed || P.retreed || std::memcmp(f.lights[P.light].v, P.v0, sizeof P.v0) != 0) moved_pair_job(f, P, f.lights[P.light], now, now, grids, retree, jobs, n_regrid);
         }
     }
     progressive_close(c);
@@ -1233,6 +1296,8 @@ int32_t ft_scene_commit_lights(ft_context* c) {
     if (c->graph.lights.size() != f.lights.size()) { c->err = "ft_scene_commit_lights: the number of lights changed since the commit (ft_scene_commit)"; return FT_ERR_STATE; }
     ft_context::LightSpace& T = c->lightspace;
     if (!T.ready) derive_light_space_tables(f, T);                  // off the records as the full commit left them
+    const bool retree = c->opt.light_space_retree != 0 && c->graph.light_space_shadows != 0;
+    if (retree && !T.blocks_laid) lay_retree_blocks(T);
     std::vector<ftd::Light> lights = c->graph.lights;
     for (ftd::Light& l : lights) if (l.kind == ftd::LT_SOFT) l.tan_half_scatter = std::tan(l.scatter / 2.0);   // (as the flattener)
     const auto same_dir = [](const double a[3], const double b[3]) { return std::memcmp(a, b, 3 * sizeof(double)) == 0; };
@@ -1242,12 +1307,13 @@ int32_t ft_scene_commit_lights(ft_context* c) {
     const bool grids = c->graph.light_space_shadows == 2;
     std::vector<LightJob> jobs;
     size_t n_regrid = 0;
-    for (const ft_context::LightSpace::Pair& P : T.pairs) {
+    for (ft_context::LightSpace::Pair& P : T.pairs) {
         if (!turned || f.leaves[P.leaf].ls_pairs == ~0u) continue;  // (stripped by ft_scene_commit_deformed: stays stripped)
         const bool refit = !same_dir(lights[P.light].v, f.lights[P.light].v);
-        if (P.deformed || !same_dir(lights[P.light].v, P.v0)) { moved_pair_job(f, P, lights[P.light], refit, false, grids, jobs, n_regrid); continue; }
+        if (P.deformed || P.retreed || (retree && refit && P.block != ~0u) || !same_dir(lights[P.light].v, P.v0)) { moved_pair_job(f, P, lights[P.light], refit, false, grids, retree, jobs, n_regrid); continue; }
         // the full commit's direction (again) over that commit's vertices: its record, and with it its grid, which still lies where that
-        // commit put it.  (Not for a deformed pair: rec0 and that grid describe vertices that are gone.)
+        // commit put it.  (Not for a deformed pair: rec0 and that grid describe vertices that are gone.  Not for a retreed one: that
+        // commit's tree leads to leaf records that have been sorted anew since.)
         double* rec = &f.ls_pairs[(size_t)ftd::kLsPairDoubles * P.rec];
         std::memcpy(rec, P.rec0, sizeof P.rec0);
         if (!refit) continue;

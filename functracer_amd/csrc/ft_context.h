@@ -97,6 +97,7 @@ struct Options {
     int64_t csg_auto_grow = 1;      // ft_render: double csg_mesh_capacity and render again when a hit list overflows (read on device 0)
     int64_t primary_block_lists = 1;   // k_block_lists: the primaries of a classified frame over ONE bare mesh test their block's candidate list; 0: the tree walk everywhere
     int64_t refit_rebuild_percent = 0;   // ft_scene_commit_deformed rebuilds a device-built tree in place once cost now x 100 > this x cost as built; 0: never (not a commit-time option)
+    int64_t light_space_retree = 0;     // ft_scene_commit_lights and ft_scene_commit_deformed build the topology of the light-space trees they would refit again on the device (not a commit-time option)
     int64_t deform_light_space = 0;     // ft_scene_commit_deformed refits the light-space trees and builds the grids of the meshes it edits again instead of stripping them (not a commit-time option)
     int64_t temporal_follow_deformed = 0;   // ft_scene_commit_deformed keeps a mesh's records as the history saw them and ft_temporal_accumulate follows them
     int64_t primary_mesh_kernel = 1;   // k_primary_mesh for the frames that qualify (ft_context::mesh_kernel_scene, queue_chunks); 0: k_primary everywhere (A/B)
@@ -278,17 +279,30 @@ struct ft_context {
     // named (src_at; `src` is that part of fth::FlatScene::ls_src, in HBM as d_src from the device's first such call), and `deformed`: the
     // mesh has been refit since the full commit, so c and R are the new vertices' and rec0 and the grid in that commit's arrays describe
     // vertices that are gone - such a pair never takes ft_scene_commit_lights' way back to rec0.
+    // Option "light_space_retree" (DESIGN.md 17.1).  The first call that retrees a pair lays one block of N(n_tris) nodes per pair out
+    // behind the full commit's nodes, in table order, while kLsMaxBytes allows (ft_ls_topology.h; block_words in all, Pair::block the
+    // block's first node or ~0u, Pair::block_levels its levels in `order`, appended then); the grids lie behind the blocks from then on.
+    // block_init: the blocks as a device's first such call uploads them - the child words, every box NaN.  Pair::retreed: the pair's
+    // tree is the block's (root and levels are), its leaf records lie in the order the device sorted them into - d_src holds it, the
+    // host's `src` is stale for that pair - and, as with `deformed`, there is no way back to rec0: the full commit's tree leads to
+    // records that have been permuted.  On every device: block_words_here, what of the blocks its ls_nodes holds; order_words, how much
+    // of `order` d_order holds; the sort's scratch.
     struct LightSpace {
         struct Pair {
             uint32_t rec, leaf, light; int32_t root; double c[3], R; uint32_t first_tri, n_tris; double v0[3], rec0[ftd::kLsPairDoubles];
             std::vector<std::pair<uint32_t, uint32_t>> levels;
             uint32_t mesh, ls_first, src_at; bool deformed;
+            uint32_t block = ~0u, block_nodes = 0; bool retreed = false;
+            std::vector<std::pair<uint32_t, uint32_t>> block_levels;
         };
         std::vector<Pair> pairs;
         std::vector<uint32_t> order, src;
         size_t base_node_words = 0, base_tri_doubles = 0;
         bool ready = false;
-        DeviceBuf d_order, d_src, d_first, d_cursor, d_idx, d_small, d_scan;
+        DeviceBuf d_order, d_src, d_first, d_cursor, d_idx, d_small, d_scan, d_keys, d_sort;
+        std::vector<uint32_t> block_init;
+        size_t block_words = 0, block_words_here = 0, order_words = 0;
+        bool blocks_laid = false;
         // Option "edge_cull": the edge records of the grids' entries (ft_edges.h), one per record of ls_tris as it lies in HBM now, written
         // by k_ls_edges after every upload of the light-space arrays and at the end of every ft_scene_commit_lights; empty where the scene
         // has no grid or the records would pass kLsEdgeMaxBytes (the shadow queries then go by the rectangles alone).
@@ -296,9 +310,9 @@ struct ft_context {
         std::vector<DeviceBuf> d_ebox, d_counts;   // per pair whose grid a call builds: its entry boxes and cell counts, from the pass that decides the grid to the one that writes it
         size_t node_words = 0, tri_doubles = 0;
         bool order_uploaded = false, src_uploaded = false, rewritten = false;
-        void reset() { pairs.clear(); order.clear(); src.clear(); ready = order_uploaded = src_uploaded = rewritten = false; node_words = tri_doubles = base_node_words = base_tri_doubles = 0; }
+        void reset() { pairs.clear(); order.clear(); src.clear(); block_init.clear(); ready = order_uploaded = src_uploaded = rewritten = blocks_laid = false; node_words = tri_doubles = base_node_words = base_tri_doubles = block_words = block_words_here = order_words = 0; }
         void release() {
-            for (DeviceBuf* b : {&d_order, &d_src, &d_first, &d_cursor, &d_idx, &d_small, &d_scan, &d_edges}) b->release();
+            for (DeviceBuf* b : {&d_order, &d_src, &d_first, &d_cursor, &d_idx, &d_small, &d_scan, &d_keys, &d_sort, &d_edges}) b->release();
             for (DeviceBuf& b : d_ebox) b.release();
             for (DeviceBuf& b : d_counts) b.release();
             d_ebox.clear(); d_counts.clear(); reset();

@@ -1,5 +1,6 @@
 // ft_debug.cpp — ft_debug_*: explicit ray queries through the device paths and views of the committed scene, for the tests.
 #include "ft_context.h"
+#include "ft_ls_topology.h"
 using namespace ftc;
 
 extern "C" {
@@ -182,6 +183,37 @@ int32_t ft_debug_light_space(ft_context* c, int64_t sizes[4], double* pairs, uin
         if (tris) std::memcpy(tris, f.ls_tris.data(), f.ls_tris.size() * sizeof(double));
     }
     if (leaf_pairs) for (size_t k = 0; k < f.leaves.size(); ++k) leaf_pairs[k] = f.leaves[k].ls_pairs;
+    return FT_OK;
+}
+
+// "light_space_retree": the pairs' table as the last ft_scene_commit_lights / ft_scene_commit_deformed left it.
+int32_t ft_debug_ls_retree(ft_context* c, int64_t* n_pairs, int64_t* rows, double* R) {
+    if (!c || !n_pairs) return FT_ERR_INVALID;
+    if (c->host_only) return FT_ERR_NO_DEVICE;
+    const ft_context::LightSpace& T = c->lightspace;
+    *n_pairs = T.ready ? (int64_t)T.pairs.size() : 0;
+    for (int64_t k = 0; k < *n_pairs; ++k) {
+        const ft_context::LightSpace::Pair& P = T.pairs[(size_t)k];
+        if (rows) {
+            int64_t* r = rows + 8 * k;
+            r[0] = P.rec; r[1] = P.leaf; r[2] = P.light; r[3] = P.n_tris; r[4] = P.ls_first == ~0u ? -1 : (int64_t)P.ls_first;
+            r[5] = P.retreed ? 1 : 0; r[6] = P.block == ~0u ? -1 : (int64_t)P.block; r[7] = P.block_nodes;
+        }
+        if (R) R[k] = P.R;
+    }
+    return FT_OK;
+}
+
+// The host half of "light_space_retree" (ft_ls_topology.h), context-free.
+int32_t ft_debug_ls_topology(int64_t n, int64_t ls_first, int64_t first_node, int64_t sizes[2], uint32_t* child, uint32_t* order, uint32_t* levels) {
+    if (!sizes || n < 0 || ls_first < 0 || first_node < 0 || n > 0xFFFFFFFFll || ls_first > 0xFFFFFFFFll || first_node > 0xFFFFFFFFll) return FT_ERR_INVALID;
+    fth::LsTopology topo;
+    if (!fth::ls_retree_topology((uint32_t)n, (uint32_t)ls_first, (uint32_t)first_node, topo)) return FT_ERR_INVALID;
+    const size_t N = topo.nodes.size() / fth::kLsTopoNodeWords;
+    sizes[0] = (int64_t)N; sizes[1] = (int64_t)topo.levels.size();
+    if (child) for (size_t k = 0; k < N; ++k) std::memcpy(child + 4 * k, &topo.nodes[k * fth::kLsTopoNodeWords + 20], 16);
+    if (order) std::memcpy(order, topo.order.data(), N * 4);
+    if (levels) for (size_t k = 0; k < topo.levels.size(); ++k) { levels[2 * k] = topo.levels[k].first; levels[2 * k + 1] = topo.levels[k].second; }
     return FT_OK;
 }
 

@@ -261,6 +261,12 @@ void ls_refit_level(hipStream_t stream, uint32_t* ls_nodes, uint32_t n_nodes, co
 // inside the mesh's list-order records [mesh_first, mesh_first + mesh_n); n_tris, n_ls: the sizes of tris and ls_tris in records.
 void ls_gather(hipStream_t stream, const double* tris, uint32_t n_tris, uint32_t mesh_first, uint32_t mesh_n, const uint32_t* src, uint32_t count, double* ls_tris, uint32_t n_ls,
                uint32_t ls_first);
+// The order of a pair's leaf records under "light_space_retree" (DESIGN.md 17.1).  ls_morton_keys (k_ls_keys): for the pair's n list-order
+// triangles, records first_tri .. first_tri + n of tris (n_tris records in all), keys[k] = the 32-bit Morton code of the centre of
+// triangle k's (u, v) rectangle in frame F - 16 bits per axis over [-R, R], u in the even bits - and vals[k] = first_tri + k.
+// ls_sort_pairs: rocprim's stable radix sort of (keys, vals) ascending by key (tmp = null: *tmp_bytes receives the scratch size needed).
+void ls_morton_keys(hipStream_t stream, const double* tris, uint32_t n_tris, uint32_t first_tri, uint32_t n, const LsFrame& F, double R, uint32_t* keys, uint32_t* vals);
+hipError_t ls_sort_pairs(hipStream_t stream, const uint32_t* keys_in, uint32_t* keys_out, const uint32_t* vals_in, uint32_t* vals_out, uint32_t n, void* tmp, size_t* tmp_bytes);
 // The grid of such a pair built again (ft_scene.cpp, build_grid, its host loops as passes; tris: the mesh's n list-order records in HBM):
 //   ls_grid_entries     ebox[5 k ..] = triangle k's entry box; ruv (zeroed by the caller, or null): the bits of Ru and Rv
 //   ls_grid_count       sums[a] (zeroed by the caller) += the cells every entry covers under candidate a of build_grid's attempt loop

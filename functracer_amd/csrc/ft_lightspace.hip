@@ -13,7 +13,12 @@
 // The same passes serve a mesh whose vertices changed (ft_scene_commit_deformed under "deform_light_space"): there the
 // frame stays and the centre, the pad and the leaf records change, so k_ls_gather first copies the refit list-order records into the
 // tree's leaves, and k_ls_refit and the grid passes then run as for a turned light.
+//
+// Under "light_space_retree"  the topology is built again as well: k_ls_keys gives every list-order triangle of the pair
+// the Morton code of its projected centre, a radix sort orders the triangles by it, k_ls_gather copies the records in that order, and
+// k_ls_refit boxes the tree the host generated over the sorted positions (ft_ls_topology.h) - a function of the triangle count alone.
 #include <hip/hip_runtime.h>
+#include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
 #include <math.h>
@@ -95,6 +100,33 @@ __global__ __launch_bounds__(256) void k_ls_gather(const double* __restrict__ tr
     const double* T = tris + 9ull * s;
     double* O = ls_tris + 9ull * d;
     for (int q = 0; q < 9; ++q) O[q] = T[q];
+}
+
+// ---- the order of a pair's leaf records under "light_space_retree"  ------------------------------------------------------
+// x in the even bits, y in the odd bits
+__device__ __forceinline__ uint32_t spread16(uint32_t v) {
+    v &= 0xFFFFu;
+    v = (v | v << 8) & 0x00FF00FFu; v = (v | v << 4) & 0x0F0F0F0Fu; v = (v | v << 2) & 0x33333333u; v = (v | v << 1) & 0x55555555u;
+    return v;
+}
+// A centre coordinate in [-R, R] on 65536 steps, clamped; a NaN gives 0 (fmax and fmin return their other operand).
+__device__ __forceinline__ uint32_t morton_axis(double c, double R, double g) { return (uint32_t)fmin(65535.0, fmax(0.0, floor(__dmul_rn(__dadd_rn(c, R), g)))); }
+
+// One lane per list-order triangle k of the pair (record first_tri + k of tris, n_tris records in all): the (u, v) rectangle exactly as
+// grow_by_tri computes it, its centre, and the Morton code of the centre as the key; the record's index as the value.  g = 32768 / R.
+__global__ __launch_bounds__(256) void k_ls_keys(const double* __restrict__ tris, uint32_t n_tris, uint32_t first_tri, uint32_t n, LsFrame F, double R, double g,
+                                                 uint32_t* __restrict__ keys, uint32_t* __restrict__ vals) {
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    if (k >= n) return;
+    const uint64_t t = (uint64_t)first_tri + k;
+    uint32_t key = 0u;
+    if (t < n_tris) {
+        double lo[2] = {INFINITY, INFINITY}, hi[2] = {-INFINITY, -INFINITY}, wmax = -INFINITY;
+        grow_by_tri(tris + 9ull * t, F, lo, hi, wmax);
+        const double cu = __dmul_rn(0.5, __dadd_rn(lo[0], hi[0])), cv = __dmul_rn(0.5, __dadd_rn(lo[1], hi[1]));
+        key = spread16(morton_axis(cu, R, g)) | spread16(morton_axis(cv, R, g)) << 1;
+    }
+    keys[k] = key; vals[k] = (uint32_t)t;                           // (an index outside tris: k_ls_gather writes nothing for it)
 }
 
 // ---- the grid of a pair, built again (ft_scene.cpp, build_grid, with its host loops as passes) ----------------------------------------
@@ -247,6 +279,14 @@ void ls_grid_emit(hipStream_t stream, const float* ebox, const double* tris, uin
                   uint32_t* cursor, uint32_t* idx, uint32_t n_entries, uint32_t* ls_nodes, uint32_t at, double* ls_tris, uint32_t tri_at) {
     hipLaunchKernelGGL(k_ls_cells<true>, dim3((n + 255u) / 256u), dim3(256), 0, stream, ebox, n, s, nu, nv, cursor, first, idx, n_entries);
     hipLaunchKernelGGL(k_ls_emit, dim3((nu * nv + 3u) / 4u), dim3(256), 0, stream, ebox, tris, n, idx, counts, first, nu * nv, n_entries, ls_nodes, at, ls_tris, tri_at);
+}
+
+void ls_morton_keys(hipStream_t stream, const double* tris, uint32_t n_tris, uint32_t first_tri, uint32_t n, const LsFrame& F, double R, uint32_t* keys, uint32_t* vals) {
+    if (n == 0u) return;
+    hipLaunchKernelGGL(k_ls_keys, dim3((n + 255u) / 256u), dim3(256), 0, stream, tris, n_tris, first_tri, n, F, R, 32768.0 / R, keys, vals);
+}
+hipError_t ls_sort_pairs(hipStream_t stream, const uint32_t* keys_in, uint32_t* keys_out, const uint32_t* vals_in, uint32_t* vals_out, uint32_t n, void* tmp, size_t* tmp_bytes) {
+    return rocprim::radix_sort_pairs(tmp, *tmp_bytes, keys_in, keys_out, vals_in, vals_out, (size_t)n, 0u, 32u, stream);
 }
 
 void ls_gather(hipStream_t stream, const double* tris, uint32_t n_tris, uint32_t mesh_first, uint32_t mesh_n, const uint32_t* src, uint32_t count, double* ls_tris, uint32_t n_ls,

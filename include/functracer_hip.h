@@ -189,6 +189,10 @@ const char* ft_last_error(const ft_context* ctx);
  * grids again on the device instead of stripping them - "deforming meshes" below.  It is read by ft_scene_commit_deformed alone and needs no new
  * ft_scene_commit; a host-only context accepts it without effect, because its deformed commit is the full host commit, which builds the structures anyway; with 0
  * every call launches the kernels and gives the bits it gave before the option existed),
+ * "light_space_retree" (0 = default; any other value means 1: ft_scene_commit_lights and ft_scene_commit_deformed build the topology of every light-space shadow
+ * tree they would refit again on the device from the current projection, instead of keeping the one the last full commit built - "moving lights" below.  It is
+ * read by those two calls alone and needs no new ft_scene_commit; a host-only context accepts it without effect, because both calls are the full host commit
+ * there; with 0 both calls launch the kernels and write the bytes they wrote before the option existed),
  * "temporal_follow_deformed" (0 = default; any other value means 1: ft_scene_commit_deformed keeps the triangle records of the meshes it refits as the open
  * temporal accumulation last saw them, and the next ft_temporal_accumulate takes every pixel on a changed triangle back to where that point of the triangle was -
  * "history on deforming meshes" below.  It needs no new ft_scene_commit; a host-only or multi-device context accepts it without effect, because the accumulation
@@ -776,7 +780,30 @@ int32_t ft_scene_tree_quality(ft_context* ctx, ft_node mesh_node, double out[4])
  * A host that never calls these functions gets bit-identical results from everything else.
  * Device memory: 4 bytes per 4-wide node of the trees that can be refit, the grids built since the full commit, and while a call runs
  * 20 bytes per triangle and 4 per cell of every pair whose grid is built (kept from call to call) and 8 per cell and 4 per entry of the
- * largest grid. */
+ * largest grid.
+ * "light_space_retree" 1: the cure for that decay short of a full commit.  Every pair whose tree a call would refit - it has a usable
+ * frame and R < 2e29, and its direction changed in this call, or (ft_scene_commit_deformed under "deform_light_space") its mesh was edited
+ * in this call - gets a NEW topology instead, built on the device from the current projection, and that tree is then boxed by the same
+ * refit pass.  The rule: the pair's n triangles are keyed by the Morton code of the centre of their (u, v) rectangle (16 bits per axis over
+ * [-R, R], u in the even bits), sorted by it (stable, so equal codes keep the list order), and the leaf records are copied in that order
+ * into the run of n records the pair's tree has always had; over the sorted positions stands a tree that depends on n alone - a binary
+ * tree cut at the middle position down to leaves of 2 .. 4, two binary levels per 4-wide node as the host builder collapses them, at most
+ * 9 wide levels for the 2^20 triangles a pair may have, so the walk holds at most 27 of its 64 pending entries.  The nodes live in a block of
+ * N(n) nodes per pair that the first such call lays out behind the full commit's nodes, in pair order, while the 256 MiB cap allows (a
+ * pair whose block does not fit is refit as before, for good); the grids lie behind the blocks from then on, and ft_debug_light_space
+ * follows the new sizes.  Everything else in the call is unchanged: pair records, grids, edge records, what the call ends and leaves open,
+ * and frames and counters are a fresh context's, bit for bit.  A retreed pair stays retreed until the next full commit: turning the option
+ * off later refits it over the new topology, and - as for a pair deformed under "deform_light_space" - a light back at the direction of
+ * the last full commit does NOT get that commit's record and grid back, because that commit's tree leads to leaf records that have been
+ * sorted anew; it gets a derived record and a rebuilt grid.  A pair that is unusable in a call is not retreed in it.  On a multi-device
+ * context every device runs the same deterministic passes.  Device memory: 96 bytes per node of the blocks, about 0.3 n nodes for a pair of
+ * n triangles, and 12 bytes per triangle of the largest pair plus the sort's scratch while a call runs (kept from call to call).  Measured
+ * on the 69.6 K-face mesh above: the call costs what it costs without the option (1.4 ms against 1.4; 2.4 against 2.1 for a deformed
+ * commit), and k_primary stays 1.04 - 1.13 x a fresh full commit's at every turn from 1 to 180 degrees and along 16 steps of a twist, where the refit
+ * reaches 7.3 x at 45 degrees, 15 x at 90 and 2.6 x after 16 twist steps.  It pays over the refit from about 10 degrees of turn or 4 twist steps on; at
+ * 1 degree it is 4 - 5 % slower than the refit, because a median tree over a Morton order is not as good as the full commit's surface-area tree - by
+ * the same 4 - 13 % it stays behind a fresh commit, and at 45 degrees it is 8 % slower than "light_space_shadows" 0 on this mesh, which a fresh
+ * commit's tree is not.  Hence the default 0: set it where lights swing far or meshes bend far between full commits. */
 int32_t ft_scene_set_directional(ft_context* ctx, int32_t light, const double dir[3], const double colour[3]);
 int32_t ft_scene_set_soft_directional(ft_context* ctx, int32_t light, const double dir[3], double scatter_rad, const double colour[3]);
 int32_t ft_scene_set_positional(ft_context* ctx, int32_t light, const double pos[3], const double falloff[3], const double colour[3]);
@@ -844,6 +871,18 @@ int32_t ft_debug_slice(const double p0[3], const double n[3], const double tri[9
  * sizes = pair records, nodes, triangle records, leaves; each non-null array receives 16 doubles per record, 24 words per node,
  * 9 doubles per triangle and, per leaf, the index of its first pair record (0xFFFFFFFF = none).  Host-only contexts too. */
 int32_t ft_debug_light_space(ft_context* ctx, int64_t sizes[4], double* pairs, uint32_t* nodes, double* tris, uint32_t* leaf_pairs);
+/* "light_space_retree" at work, for tests: the pairs of the table ft_scene_commit_lights / ft_scene_commit_deformed keep since the last full
+ * commit (*n_pairs; 0 before the first such call).  Each non-null array receives per pair: rows = 8 values - pair record, leaf, light,
+ * n_tris, the first of the tree's leaf records in ls_tris (-1: none), 1 if the pair has been retreed, the first node of its block (-1: no
+ * block, also before the option's first call) and the block's node count N; R = the pair's extent about its centre as the last call left it.
+ * FT_ERR_NO_DEVICE on a host-only context. */
+int32_t ft_debug_ls_retree(ft_context* ctx, int64_t* n_pairs, int64_t* rows, double* R);
+/* The topology "light_space_retree" gives a pair of n triangles whose leaf records start at ls_first and whose block starts at node
+ * first_node, as the host generates it (no context, no device): sizes = nodes N, levels.  Each non-null array receives: child = 4 words per
+ * node, numbered from first_node breadth first (>= 0 a node, INT32_MIN empty, otherwise ~(first record << 3 | count)); order = the N nodes
+ * by level, deepest level first; levels = per level, deepest first, its offset into order and its count.  FT_ERR_INVALID where n < 5 or an
+ * index would not fit its word. */
+int32_t ft_debug_ls_topology(int64_t n, int64_t ls_first, int64_t first_node, int64_t sizes[2], uint32_t* child, uint32_t* order, uint32_t* levels);
 /* The mesh trees of the committed scene as the kernels walk them (layouts in ft_flat.h), for tests.  A device context copies the arrays
  * back from device memory, so the trees ft_bvh.hip built after the upload are seen; a host-only context hands out the flattened arrays.
  * sizes = BspNode records, BspLeaf records, triangle records, tri_orig entries, tri_src entries, 4-wide nodes, coarse boxes, meshes,
