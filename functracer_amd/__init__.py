@@ -71,6 +71,9 @@ def hip_lib():
         for name, res, args in _capi.PROGRESSIVE_SIGNATURES + _capi.TEMPORAL_SIGNATURES + _capi.TEMPORAL_QUEUE_SIGNATURES + _capi.MOTION_SIGNATURES + _capi.DEFORM_SIGNATURES + _capi.LIGHT_SIGNATURES:
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
+        if hasattr(lib, _capi.MOVED_COMMITS_SIGNATURE[0]):          # (FT_HIP_LIB may name an older build, as above)
+            fn = getattr(lib, _capi.MOVED_COMMITS_SIGNATURE[0])
+            fn.restype, fn.argtypes = _capi.MOVED_COMMITS_SIGNATURE[1:]
         _hip = lib
     return _hip
 
@@ -579,9 +582,21 @@ class Context(SceneBuilder):
 
     def commit_moved(self):
         """ft_scene_commit_moved: commit a graph whose transforms alone changed since the last commit.  A temporal accumulation stays open
-        and its history follows the moved leaves; a progressive accumulation ends."""
+        and its history follows the moved leaves; a progressive accumulation ends.  Under set_option("moved_in_place", 1) a device context
+        uploads the new poses over the old ones and refits the light-space shadow structures of the leaves that turned, instead of
+        committing the whole scene again, whenever nothing but poses changed; every later call gives the same bits either way
+        (moved_commits tells which way a call went)."""
         self._check(self._lib.ft_scene_commit_moved(self._ctx))
         self._progressive = None
+
+    def moved_commits(self):
+        """ft_debug_moved_commits: a dict of `in_place` and `full` (commit_moved calls done in place / by the full commit since the context
+        was created), `full_reason` (of the last call: 0 it was done in place, 1 option "moved_in_place" off or a host-only context, 2 a
+        light setter, new mesh vertices or a commit-time option pending, 3 the re-flatten differs in more than poses) and `pairs_refit`
+        (light-space pairs the last in-place call refit or retreed)."""
+        out = (C.c_int64 * 4)()
+        self._check(self._lib.ft_debug_moved_commits(self._ctx, out))
+        return dict(zip(_capi.MOVED_COMMITS_FIELDS, (int(v) for v in out)))
 
     # deforming meshes: a refit instead of a rebuild (include/functracer_hip.h) ------------------------
     def set_mesh_triangles(self, node, tris):

@@ -125,6 +125,10 @@ MOTION_SIGNATURES = [
     ("ft_scene_commit_moved", C.c_int32, [C.c_void_p]),
     ("ft_debug_leaf_matrices", C.c_int32, [C.c_void_p, C.POINTER(C.c_int64), c_double_p, c_double_p]),
 ]
+# ft_debug_moved_commits (option "moved_in_place"): its four values, in order, and what `full_reason` says
+MOVED_COMMITS_SIGNATURE = ("ft_debug_moved_commits", C.c_int32, [C.c_void_p, C.POINTER(C.c_int64)])
+MOVED_COMMITS_FIELDS = ("in_place", "full", "full_reason", "pairs_refit")
+MOVED_NOT_FULL, MOVED_OPTION_OFF, MOVED_PENDING, MOVED_DIFFERS = 0, 1, 2, 3
 
 
 # Deforming meshes (include/functracer_hip.h): new vertices for an existing bspMesh node, committed by a refit of its tree on the device.

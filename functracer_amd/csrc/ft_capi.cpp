@@ -203,6 +203,8 @@ const OptionSpec kOptions[] = {
     {"deform_light_space", 0, 1, &Options::deform_light_space, nullptr, kFlag},
     // read by ft_scene_commit_lights and ft_scene_commit_deformed alone, as the ones above (any value other than 0 means 1)
     {"light_space_retree", 0, 1, &Options::light_space_retree, nullptr, kFlag},
+    // read by ft_scene_commit_moved alone, as the ones above (any value other than 0 means 1)
+    {"moved_in_place", 0, 1, &Options::moved_in_place, nullptr, kFlag},
     {"csg_mesh_capacity", 1, 255, nullptr, [](fth::SceneGraph& g, int64_t v) { g.csg_mesh_capacity = (int32_t)v; }, kCommit},
     // directional shadow rays of coherent waves: 0 the BVH; 1 light-space trees; 2 (default) light-space grids, the trees for wide waves.
     // It was a flag before the grids: it still takes any value, and any other than 0 / 1 means 2.
@@ -819,6 +821,7 @@ static void derive_light_space_tables(const fth::FlatScene& f, ft_context::Light
             P.rec = (uint32_t)rec; P.leaf = leaf; P.light = l; P.root = root; P.R = R; P.first_tri = src.first_tri; P.n_tris = src.n_tris;
             P.mesh = L.mesh; P.ls_first = ~0u; P.src_at = (uint32_t)T.src.size(); P.deformed = false;
             for (int q = 0; q < 3; ++q) { P.c[q] = c[q]; P.v0[q] = f.lights[l].v[q]; }
+            std::memcpy(P.w2m0, L.w2m, sizeof P.w2m0); P.flags0 = L.flags;
             std::memcpy(P.rec0, &f.ls_pairs[ftd::kLsPairDoubles * rec], sizeof P.rec0);
             // breadth first: `level` holds one level of the tree; the levels are then laid out deepest first
             std::vector<std::vector<uint32_t>> by_level;
@@ -849,6 +852,14 @@ static void derive_light_space_tables(const fth::FlatScene& f, ft_context::Light
         }
     }
     T.ready = true;
+}
+
+// Is the pair still the full commit's - may it have that commit's record (rec0) and, with it, the grid that lies where that commit put it?
+// Only with the light at that commit's direction (`v`: the light's direction now) over the leaf in that commit's pose, its mesh not
+// deformed and its tree not retreed since.  ft_scene_commit_lights, ft_scene_commit_deformed and ft_scene_commit_moved all ask here.
+static bool full_commits_pair(const fth::FlatScene& f, const ft_context::LightSpace::Pair& P, const double v[3]) {
+    const ftd::Leaf& L = f.leaves[P.leaf];
+    return !P.deformed && !P.retreed && std::memcmp(v, P.v0, sizeof P.v0) == 0 && std::memcmp(L.w2m, P.w2m0, sizeof P.w2m0) == 0 && ((L.flags ^ P.flags0) & ftd::LF_XFORM) == 0u;
 }
 
 // One pair's share of an ft_scene_commit_lights: its frame; whether its tree is refit (its direction changed in this call); whether its
@@ -1148,6 +1159,116 @@ static int32_t relight_device(ft_context* c, fth::FlatScene& f, const ft_context
     return FT_OK;
 }
 
+// The new poses on one device of the context ("moved_in_place"): `f` is the held scene with the new leaves, m2w, cull
+// records and face directions already in it, every array as long as it was.  They are uploaded over the old ones, then the light-space
+// structures follow where a pair's frame changed (rebuild_light_space; `turned`: some pair's did - otherwise no kernel is launched).
+static int32_t move_device(ft_context* c, fth::FlatScene& f, const ft_context::LightSpace& T, std::vector<LightJob>& jobs, bool turned, bool relay, bool lead, double ms[2]) {
+    using clock = std::chrono::steady_clock;
+    int32_t rc;
+    FT_HIP(c, hipSetDevice(c->device));
+    const auto t0 = clock::now();
+    // frames still queued trace the scene these uploads rewrite (as upload_scene): they show the old poses
+    if (any_queued(c)) { if ((rc = retire_queued(c)) != FT_OK) return rc; c->accum_open = false; }
+    if ((rc = drain_frame_streams(c)) != FT_OK) return rc;
+    if (c->side) FT_HIP(c, hipStreamSynchronize(c->side));
+    DeviceBuf* B = c->d_scene;
+    cull_items_image(f, c->cull_items_and_rows);
+    if (B[kLeaves].bytes < f.leaves.size() * sizeof(ftd::Leaf) || B[kM2w].bytes < f.m2w.size() * 8 || B[kCulls].bytes < f.culls.size() * sizeof(ftd::CullRecord) ||
+        B[kCullItems].bytes < c->cull_items_and_rows.size() * 4 || B[kCullRows].bytes < f.cull_rows.size() * 8) {
+        c->err = "ft_scene_commit_moved: a scene array in device memory is smaller than the flattened one"; return FT_ERR_STATE;
+    }
+    if ((rc = upload(c, B[kLeaves], f.leaves)) != FT_OK || (rc = upload(c, B[kM2w], f.m2w)) != FT_OK || (rc = upload(c, B[kCulls], f.culls)) != FT_OK ||
+        (rc = upload(c, B[kCullItems], c->cull_items_and_rows)) != FT_OK || (rc = upload(c, B[kCullRows], f.cull_rows)) != FT_OK) return rc;
+    FT_HIP(c, hipStreamSynchronize(c->stream));
+    ms[0] += std::chrono::duration<double, std::milli>(clock::now() - t0).count();
+    // (a pair that lost its usable frame has a new record and no job)
+    if (turned && (rc = rebuild_light_space(c, f, T, jobs, relay, lead, ms, "ft_scene_commit_moved")) != FT_OK) return rc;
+    c->zero_signature[0] = c->zero_signature[1] = 0;                // (as every commit)
+    c->committed = true;
+    ++c->commit_serial; c->staged_hint = -1;
+    return FT_OK;
+}
+
+// ft_scene_commit_moved under "moved_in_place".  FT_OK with *in_place false: the re-flatten differs in more than poses and nothing was
+// changed - the caller takes the full commit.
+static int32_t move_in_place(ft_context* c, bool* in_place) {
+    using clock = std::chrono::steady_clock;
+    const auto t0 = clock::now();
+    *in_place = false;
+    fth::FlatScene& f = c->flat;
+    // the pairs' tables, off `f` as the full commit left it: the poses in it are still that commit's, or an earlier call here derived them
+    ft_context::LightSpace& T = c->lightspace;
+    const bool ls = c->graph.light_space_shadows != 0;
+    if (ls && !T.ready) derive_light_space_tables(f, T);
+    const bool retree = ls && c->opt.light_space_retree != 0;
+    if (retree && !T.blocks_laid) lay_retree_blocks(T);
+    std::string why;
+    if (c->graph.reflatten_moved(f, why) != FT_OK) return FT_OK;
+    *in_place = true;
+    // A pair's frame follows from its leaf's w2m and its light's direction alone (fth::ls_pair_frame); c and R are model-space and stay.
+    // A pair whose frame is what its record holds is not touched: a translation changes no frame.
+    const bool grids = c->graph.light_space_shadows == 2;
+    std::vector<uint8_t> changed(T.pairs.size(), 0);
+    bool turned = false;
+    for (size_t k = 0; ls && k < T.pairs.size(); ++k) {
+        const ft_context::LightSpace::Pair& P = T.pairs[k];
+        if (f.leaves[P.leaf].ls_pairs == ~0u) continue;            // (stripped by ft_scene_commit_deformed: stays stripped)
+        const double* rec = &f.ls_pairs[(size_t)ftd::kLsPairDoubles * P.rec];
+        int32_t root;
+        std::memcpy(&root, &rec[14], 4);
+        fth::LsPairFrame fr;
+        const bool usable = fth::ls_pair_frame(f.leaves[P.leaf], f.lights[P.light], fr) && P.R < 2e29;
+        const bool same = usable ? root != INT32_MIN && std::memcmp(&rec[0], fr.U, 24) == 0 && std::memcmp(&rec[3], fr.V, 24) == 0 && std::memcmp(&rec[6], fr.D, 24) == 0 &&
+                                       std::memcmp(&rec[12], &fr.k_rel, 8) == 0
+                                 : root == INT32_MIN;
+        changed[k] = same ? 0 : 1;
+        turned = turned || !same;
+    }
+    std::vector<LightJob> jobs;
+    size_t n_regrid = 0;
+    int64_t n_refit = 0;
+    for (size_t k = 0; turned && k < T.pairs.size(); ++k) {
+        ft_context::LightSpace::Pair& P = T.pairs[k];
+        if (f.leaves[P.leaf].ls_pairs == ~0u) continue;
+        const bool refit = changed[k] != 0;
+        // as in ft_scene_commit_lights: every pair that is not the full commit's has a job, since the region behind that commit's arrays
+        // is laid out anew; a pair back at that commit's pose under that commit's direction takes its record, and with it its grid
+        if ((retree && refit && P.block != ~0u) || !full_commits_pair(f, P, f.lights[P.light].v)) {
+            const size_t before = jobs.size();
+            moved_pair_job(f, P, f.lights[P.light], refit, false, grids, retree, jobs, n_regrid);
+            if (refit && jobs.size() > before) ++n_refit;
+            continue;
+        }
+        double* rec = &f.ls_pairs[(size_t)ftd::kLsPairDoubles * P.rec];
+        std::memcpy(rec, P.rec0, sizeof P.rec0);
+        if (!refit) continue;
+        LightJob j{&P, {}, refit, false};
+        for (int q = 0; q < 3; ++q) { j.frame.U[q] = rec[q]; j.frame.V[q] = rec[3 + q]; j.frame.D[q] = rec[6 + q]; j.frame.c[q] = rec[9 + q]; }
+        j.frame.pad = 1e-7 * P.R + 1e-30;
+        jobs.push_back(j);
+        ++n_refit;
+    }
+    progressive_close(c);
+    const double tallest = c->commit_ms[3];
+    for (double& v : c->commit_ms) v = 0.0;
+    c->commit_ms[3] = tallest;
+    c->commit_ms[0] = std::chrono::duration<double, std::milli>(clock::now() - t0).count();
+    double ms[2] = {0.0, 0.0};
+    int32_t rc = FT_OK;
+    for (ft_context* d : devices(c)) {                              // every device rewrites its own copy; the first decides the grids
+        if ((rc = move_device(d, f, T, jobs, turned, turned && grids, d == c, ms)) != FT_OK) { if (d != c) c->err = d->err; break; }
+    }
+    for (ft_context* p : c->peers) {
+        p->flat.leaves = f.leaves; p->flat.m2w = f.m2w; p->flat.culls = f.culls; p->flat.cull_items = f.cull_items; p->flat.cull_rows = f.cull_rows;
+        if (turned) p->flat.ls_pairs = f.ls_pairs;
+    }
+    c->commit_ms[1] = ms[1]; c->commit_ms[2] = ms[0];
+    if (rc != FT_OK) { for (ft_context* d : devices(c)) d->committed = false; c->holds_commit = false; return rc; }   // HBM holds neither scene whole: ft_scene_commit
+    c->moved_pending = false;
+    c->moved_counts[3] = n_refit;
+    return FT_OK;
+}
+
 } // namespace ftc
 
 extern "C" {
@@ -1167,10 +1288,32 @@ int32_t ft_scene_commit_moved(ft_context* c) {
     if (!c) return FT_ERR_INVALID;
     if (!c->holds_commit) { c->err = "ft_scene_commit_moved: no committed scene to move (ft_scene_commit)"; return FT_ERR_STATE; }
     if (c->restructured) { c->err = "ft_scene_commit_moved: the graph, the root or the lights changed since the commit (ft_scene_commit)"; return FT_ERR_STATE; }
+    // Option "moved_in_place" (DESIGN.md 14.1): the new poses go over the old ones and the light-space pairs follow on the device.  What
+    // a full commit has always absorbed - a pending light setter, new vertices, a commit-time option - is still the full commit's.
+    int64_t why = 0;
+    if (c->host_only || !c->opt.moved_in_place) why = 1;
+    else if (c->lights_pending || c->options_pending) why = 2;
+    else for (const fth::GraphNode& n : c->graph.nodes) if (n.deformed) why = 2;
+    if (why == 0) {
+        bool in_place = false;
+        const int32_t rc = move_in_place(c, &in_place);
+        if (in_place) {
+            if (rc == FT_OK) { ++c->pose_serial; ++c->moved_counts[0]; c->moved_counts[2] = 0; }
+            return rc;
+        }
+        if (rc != FT_OK) return rc;
+        why = 3;
+    }
     progressive_close(c);
     const int32_t rc = commit_scene(c);
-    if (rc == FT_OK) ++c->pose_serial;
+    if (rc == FT_OK) { ++c->pose_serial; ++c->moved_counts[1]; c->moved_counts[2] = why; c->moved_counts[3] = 0; }
     return rc;
+}
+
+int32_t ft_debug_moved_commits(ft_context* c, int64_t out[4]) {
+    if (!c || !out) return FT_ERR_INVALID;
+    for (int k = 0; k < 4; ++k) out[k] = c->moved_counts[k];
+    return FT_OK;
 }
 
 // The commit of a graph whose mesh vertices alone changed (ft_sg_set_mesh_triangles): the trees keep their topology and are refit on the
@@ -1245,7 +1388,7 @@ int32_t ft_scene_commit_deformed(ft_context* c) {
         for (ft_context::LightSpace::Pair& P : T.pairs) {
             if (!touched || f.leaves[P.leaf].ls_pairs == ~0u) continue;
             const bool now = P.mesh < edited.size() && edited[P.mesh];
-            if (now || P.deformed || P.retreed || std::memcmp(f.lights[P.light].v, P.v0, sizeof P.v0) != 0) moved_pair_job(f, P, f.lights[P.light], now, now, grids, retree, jobs, n_regrid);
+            if (now || !full_commits_pair(f, P, f.lights[P.light].v)) moved_pair_job(f, P, f.lights[P.light], now, now, grids, retree, jobs, n_regrid);
         }
     }
     progressive_close(c);
@@ -1310,9 +1453,9 @@ int32_t ft_scene_commit_lights(ft_context* c) {
     for (ft_context::LightSpace::Pair& P : T.pairs) {
         if (!turned || f.leaves[P.leaf].ls_pairs == ~0u) continue;  // (stripped by ft_scene_commit_deformed: stays stripped)
         const bool refit = !same_dir(lights[P.light].v, f.lights[P.light].v);
-        if (P.deformed || P.retreed || (retree && refit && P.block != ~0u) || !same_dir(lights[P.light].v, P.v0)) { moved_pair_job(f, P, lights[P.light], refit, false, grids, retree, jobs, n_regrid); continue; }
-        // the full commit's direction (again) over that commit's vertices: its record, and with it its grid, which still lies where that
-        // commit put it.  (Not for a deformed pair: rec0 and that grid describe vertices that are gone.  Not for a retreed one: that
+        if ((retree && refit && P.block != ~0u) || !full_commits_pair(f, P, lights[P.light].v)) { moved_pair_job(f, P, lights[P.light], refit, false, grids, retree, jobs, n_regrid); continue; }
+        // the full commit's direction (again) over that commit's vertices in that commit's pose: its record, and with it its grid, which
+        // still lies where that commit put it.  (Not for a deformed pair: rec0 and that grid describe vertices that are gone.  Not for a retreed one: that
         // commit's tree leads to leaf records that have been sorted anew since.)
         double* rec = &f.ls_pairs[(size_t)ftd::kLsPairDoubles * P.rec];
         std::memcpy(rec, P.rec0, sizeof P.rec0);

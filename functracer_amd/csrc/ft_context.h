@@ -98,6 +98,7 @@ struct Options {
     int64_t primary_block_lists = 1;   // k_block_lists: the primaries of a classified frame over ONE bare mesh test their block's candidate list; 0: the tree walk everywhere
     int64_t refit_rebuild_percent = 0;   // ft_scene_commit_deformed rebuilds a device-built tree in place once cost now x 100 > this x cost as built; 0: never (not a commit-time option)
     int64_t light_space_retree = 0;     // ft_scene_commit_lights and ft_scene_commit_deformed build the topology of the light-space trees they would refit again on the device (not a commit-time option)
+    int64_t moved_in_place = 0;         // ft_scene_commit_moved uploads the new poses and refits the light-space pairs instead of committing the scene again (not a commit-time option)
     int64_t deform_light_space = 0;     // ft_scene_commit_deformed refits the light-space trees and builds the grids of the meshes it edits again instead of stripping them (not a commit-time option)
     int64_t temporal_follow_deformed = 0;   // ft_scene_commit_deformed keeps a mesh's records as the history saw them and ft_temporal_accumulate follows them
     int64_t primary_mesh_kernel = 1;   // k_primary_mesh for the frames that qualify (ft_context::mesh_kernel_scene, queue_chunks); 0: k_primary everywhere (A/B)
@@ -185,6 +186,10 @@ struct ft_context {
     // (both cleared by every successful full commit).
     bool moved_pending = false, options_pending = false;
     bool lights_pending = false;    // an ft_scene_set_* light setter since the last successful commit (ft_scene_commit_deformed waits for ft_scene_commit_lights)
+    // ft_scene_commit_moved since ft_create: done in place ("moved_in_place"), taken by the full commit, why the last one was (0: it was
+    // not; 1: option off or host-only; 2: a light setter, new vertices or a commit-time option pending; 3: the re-flatten differs in more
+    // than poses), pairs the last in-place call refit or retreed (ft_debug_moved_commits)
+    int64_t moved_counts[4] = {0, 0, 0, 0};
     uint64_t pose_serial = 0;      // advanced by ft_scene_commit_moved only (commit_serial also by the hit lists' re-commit, which moves nothing)
     double commit_ms[4] = {0, 0, 0, 0};   // last ft_scene_commit: flatten on the host, device BVH builds, uploads + the rest, BVH height (not a time)
 
@@ -287,12 +292,16 @@ struct ft_context {
     // host's `src` is stale for that pair - and, as with `deformed`, there is no way back to rec0: the full commit's tree leads to
     // records that have been permuted.  On every device: block_words_here, what of the blocks its ls_nodes holds; order_words, how much
     // of `order` d_order holds; the sort's scratch.
+    // ft_scene_commit_moved under "moved_in_place"  derives the same tables before it changes a pose, and treats a pair whose
+    // leaf turned as the lights' call treats one whose light turned.  Pair::w2m0, flags0: the leaf's pose at the full commit - rec0 and that
+    // commit's grid belong to it, so the way back to them needs the pose as well as the direction (ftc full_commits_pair, ft_capi.cpp).
     struct LightSpace {
         struct Pair {
             uint32_t rec, leaf, light; int32_t root; double c[3], R; uint32_t first_tri, n_tris; double v0[3], rec0[ftd::kLsPairDoubles];
             std::vector<std::pair<uint32_t, uint32_t>> levels;
             uint32_t mesh, ls_first, src_at; bool deformed;
             uint32_t block = ~0u, block_nodes = 0; bool retreed = false;
+            double w2m0[12]; uint32_t flags0;   // the leaf's pose at the full commit (ft_scene_commit_moved under "moved_in_place" changes the leaf's: rec0 and that commit's grid belong to this one)
             std::vector<std::pair<uint32_t, uint32_t>> block_levels;
         };
         std::vector<Pair> pairs;

@@ -485,6 +485,47 @@ int32_t SceneGraph::reflatten_deformed(FlatScene& held, const std::vector<double
     return FT_OK;
 }
 
+int32_t SceneGraph::reflatten_moved(FlatScene& held, std::string& err) const {
+    if (!valid(root) || held.mesh_node.size() != held.meshes.size() || held.mesh_bounds.size() != 6 * held.meshes.size()) { err = "no held scene to move"; return FT_ERR_STATE; }
+    FlatScene out;
+    out.mesh_coarse = held.mesh_coarse;                             // end_item reads a bare mesh's coarse range
+    Flattener f(*this, out, err);
+    f.held = &held; f.held_bounds = &held.mesh_bounds;
+    WalkCtx c;
+    f.walk(root, c, false);
+    if (f.status != FT_OK) return f.status;                         // (FT_ERR_UNSUPPORTED: the graph no longer flattens to the held meshes)
+    out.item_pc.push_back((uint32_t)out.program.size());
+    out.program.push_back(ftd::make_op(ftd::OP_END, 0));
+    if (out.textures.empty()) out.textures.push_back(ftd::Texture{});   // as flatten pads them
+    if (out.culls.empty()) out.culls.push_back(ftd::CullRecord{});
+    if (out.run_nodes.empty()) out.run_nodes.assign(1, -1);
+    const auto bytes_equal = [](const auto& a, const auto& b) {
+        return a.size() == b.size() && (a.empty() || std::memcmp(a.data(), b.data(), a.size() * sizeof(a[0])) == 0);
+    };
+    // Everything but the poses must be what it was.  The face-direction table decides launch arguments and the size of what HBM holds of
+    // cull_items: a scene-wide table of another length, a table that overflows (cull_bundle) and an item that gains or
+    // loses its bounds (unbounded) are the full commit's.
+    bool same = out.meshes.size() == held.meshes.size() && out.leaves.size() == held.leaves.size() && bytes_equal(out.materials, held.materials) &&
+                bytes_equal(out.textures, held.textures) && out.tex_pixels.size() == held.tex_pixels.size() && out.program == held.program && out.item_pc == held.item_pc &&
+                out.run_nodes == held.run_nodes && out.culls.size() == held.culls.size() && out.cull_items.size() == held.cull_items.size() &&
+                out.cull_rows.size() == held.cull_rows.size() && out.cull_bundle == held.cull_bundle && out.unbounded == held.unbounded &&
+                out.any_reflective == held.any_reflective && out.any_texture == held.any_texture && out.mesh_under_csg == held.mesh_under_csg && f.max_list == held.csg_capacity &&
+                f.max_csg_depth <= 8 && out.m2w.size() == held.m2w.size();
+    for (size_t k = 0; same && k < out.leaves.size(); ++k) {
+        ftd::Leaf a = out.leaves[k], b = held.leaves[k];            // everything but w2m, flags and ls_pairs
+        std::memset(a.w2m, 0, sizeof a.w2m); std::memset(b.w2m, 0, sizeof b.w2m);
+        a.flags = b.flags = 0u; a.ls_pairs = b.ls_pairs = 0u;
+        same = std::memcmp(&a, &b, sizeof a) == 0 && ((out.leaves[k].flags ^ held.leaves[k].flags) & ~(uint32_t)ftd::LF_XFORM) == 0u;
+    }
+    if (!same) { err = "the moved graph differs from the held scene in more than poses: ft_scene_commit rebuilds the scene"; return FT_ERR_UNSUPPORTED; }
+    for (size_t k = 0; k < out.leaves.size(); ++k) {
+        std::memcpy(held.leaves[k].w2m, out.leaves[k].w2m, sizeof out.leaves[k].w2m);
+        held.leaves[k].flags = out.leaves[k].flags;
+    }
+    held.m2w.swap(out.m2w); held.culls.swap(out.culls); held.cull_items.swap(out.cull_items); held.cull_rows.swap(out.cull_rows);
+    return FT_OK;
+}
+
 int32_t SceneGraph::flatten(FlatScene& out, std::string& err) const {
     out = FlatScene();
     if (!valid(root)) { err = "scene has no objects (ft_scene_set_objects)"; return FT_ERR_STATE; }

@@ -115,6 +115,13 @@ struct SceneGraph {
     // held.mesh_bounds, culls and cull_items are the fresh flatten's; FT_ERR_UNSUPPORTED, with held untouched, when the new bounds change
     // anything else (an item that gains or loses its bounds).
     int32_t reflatten_deformed(FlatScene& held, const std::vector<double>& bounds, std::string& err) const;
+    // The poses of a graph that differs from the one `held` was flattened from in transform lists only (ft_scene_commit_moved under
+    // "moved_in_place"): the flattener's walk again, with held's meshes and bounds taken as they are.  On FT_OK every leaf's w2m and flags,
+    // m2w, culls, cull_items and cull_rows of held are the fresh flatten's; Leaf::ls_pairs, every mesh array and every ls_* array stay -
+    // the caller brings the pair records up to the new poses.  FT_ERR_UNSUPPORTED, with held untouched, when anything else differs: an
+    // item that crosses six face directions (its OP_CULL pair appears in or leaves the program), an item that gains or loses its bounds,
+    // a face-direction table of another length.
+    int32_t reflatten_moved(FlatScene& held, std::string& err) const;
 };
 
 // BspMesh.compile (BspMesh.fs:51-65) on the host: appends nodes / leaves / clipped triangles to
