@@ -1882,8 +1882,9 @@ FT_DEV void shade_lights(const Scene& S, const Surface& sf, const MaterialV& mat
             if (!VOTED || !voted) reflected_and_view();
             // intensity = (view . -reflected) ** shineyness.  With shineyness <= 0 the shader is black whatever the power is, so
             // the power is only evaluated when some lane needs it; integral exponents up to 64 (the usual case, ft_flat.h) go through
-            // square-and-multiply, everything else through pow.
-            const bool wants = active && mat.shineyness > 0.0;
+            // square-and-multiply, everything else through pow.  A NaN shineyness is not <= 0: its power is NaN and so is the colour
+            // (x ** nan, Shading.fs:85-87).  Only the FANCY variants can meet one (ft_capi.cpp routes it there), and only they carry pow.
+            const bool wants = active && (FANCY ? !(mat.shineyness <= 0.0) : mat.shineyness > 0.0);
             double si = 0.0;
             if (__any(wants)) {                                   // each lane takes its own route: a ray's result must not depend on its wave
                 if (VOTED && voted) reflected_and_view();
@@ -2067,11 +2068,15 @@ __global__ __launch_bounds__(kBlock, BLOCKS) void k_primary(PrimaryArgs) {
             // - and only when a lane of the wave reads it: the specular power's base, Oren-Nayar, a reflection ray.  A lane that reads it makes
             // the vote true itself, so no lane's ray depends on its neighbours.
             const FT_CONST PrimaryArgs* K2 = fresh(K);
-            const bool spawn = lit && mat.reflectance > 0.0 && 0 < K2->max_depth;
+            const bool spawn = lit && mat.reflectance > 0.0 && 0 < K2->max_depth && n_lights > 0;   // (no light, no fragment: nothing reflects, Shading.fs:119-127)
             const bool reads_view = spawn || (lit && (mat.shineyness > 0.0 || (FANCY && mat.roughness != 0.0)));
             Ray rv{0, 0, 0, 0, 0, 0};
             if (!uniform || __any(reads_view)) { if (hit) rv = primary_ray_from(&K2->gen, at_of(bi).s, pid); }
             shade_lights<FANCY, SOFT, !FANCY>(S, sf, mat, rv, hit, lit, vis_lo, vis_hi, cr, cg, cb, uniform);
+            if (!(0 < K2->max_depth)) {                             // at the recursion limit every fragment still adds reflectance x black (Shading.fs:96, 133): NaN for an infinite reflectance
+                const double z = (lit && mat.reflectance > 0.0 && n_lights > 0) ? (mat.reflectance * uniform_f64((double)n_lights)) * 0.0 : 0.0;
+                cr += z; cg += z; cb += z;
+            }
             // reflectionShader (Shading.fs:89-98), see k_bounce: one ray of weight L * reflectance stands for the L identical sub-traces
             const unsigned long long m = __ballot(spawn);
             const uint32_t cnt = (uint32_t)__popcll(m);
@@ -2305,7 +2310,13 @@ __global__ __launch_bounds__(kBlock, FANCY ? 2 : 4) void k_bounce(BounceArgs) {
             n_ovf_wave += (unsigned long long)__popcll(__ballot(overflow && alive));
             const bool hit = alive && q.id0 != ID_MISS;
             const unsigned long long hit_mask = __ballot(hit);
-            if (hit_mask == 0ull) break;                            // a ray that hits nothing adds Colour.Zero
+            // a ray that hits nothing adds Colour.Zero - times its weight (Shading.fs:96): NaN under a weight that is infinite or NaN
+            const bool lost = alive && !hit && !(fabs(w) <= 1.7976931348623157e308);
+            if (__any(lost)) {
+                if (lost) { double* acc = fresh(K)->acc; const uint32_t acc_stride = fresh(K)->acc_stride; const double z = w * 0.0;
+                            acc[slot] += z; acc[(size_t)acc_stride + slot] += z; acc[2 * (size_t)acc_stride + slot] += z; }
+            }
+            if (hit_mask == 0ull) break;
             // ---- shade
             Surface sf{{0, 0, 0}, {0, 1, 0}, 0, 0.0, 0.0};
             bool lit = false;
@@ -2326,13 +2337,17 @@ __global__ __launch_bounds__(kBlock, FANCY ? 2 : 4) void k_bounce(BounceArgs) {
             double cr, cg, cb;
             shade_lights<FANCY, SOFT>(S, sf, mat, r, hit, lit, vis_lo, vis_hi, cr, cg, cb);
             const FT_CONST BounceArgs* K2 = fresh(K);
+            if (!(depth < K2->max_depth)) {                         // at the recursion limit: reflectance x black per fragment (see k_primary)
+                const double z = (lit && mat.reflectance > 0.0 && n_lights > 0) ? (mat.reflectance * lights_f) * 0.0 : 0.0;
+                cr += z; cg += z; cb += z;
+            }
             if (hit) {                                              // one ray per sample per level: no write conflicts, fixed order
                 double* acc = K2->acc; const uint32_t acc_stride = K2->acc_stride;
                 acc[slot] += w * cr; acc[(size_t)acc_stride + slot] += w * cg; acc[2 * (size_t)acc_stride + slot] += w * cb;
             }
             // reflectionShader (Shading.fs:89-98): every one of the L fragments adds reflectance * colour(reflected ray); those L sub-traces
             // are identical (deterministic lights, or streams keyed without the parent light), so one ray carries weight L * reflectance.
-            const bool spawn = lit && mat.reflectance > 0.0 && depth < K2->max_depth;
+            const bool spawn = lit && mat.reflectance > 0.0 && depth < K2->max_depth && n_lights > 0;
             const unsigned long long m = __ballot(spawn);
             const uint32_t cnt = (uint32_t)__popcll(m);
             n_refl_wave += cnt;
