@@ -74,6 +74,10 @@ def hip_lib():
         if hasattr(lib, _capi.MOVED_COMMITS_SIGNATURE[0]):          # (FT_HIP_LIB may name an older build, as above)
             fn = getattr(lib, _capi.MOVED_COMMITS_SIGNATURE[0])
             fn.restype, fn.argtypes = _capi.MOVED_COMMITS_SIGNATURE[1:]
+        for name, res, args in _capi.POSE_QUEUE_SIGNATURES:
+            if hasattr(lib, name):                                  # (FT_HIP_LIB may name an older build, as above)
+                fn = getattr(lib, name)
+                fn.restype, fn.argtypes = res, args
         _hip = lib
     return _hip
 
@@ -630,6 +634,29 @@ class Context(SceneBuilder):
         progressive accumulation ends."""
         self._check(self._lib.ft_scene_commit_lights(self._ctx))
         self._progressive = None
+
+    # queued pose and light commits (include/functracer_hip.h) ------------------------------------------
+    def commit_moved_enqueue(self):
+        """ft_scene_commit_moved_enqueue: commit_moved as under "moved_in_place" 1, but nothing queued is retired and no stream is drained:
+        frames and temporal calls queued before the call show the old poses, everything queued or run after it the new ones.  Takes the
+        blocking path, with its bits, when it cannot queue (pose_queue tells why)."""
+        self._check(self._lib.ft_scene_commit_moved_enqueue(self._ctx))
+        self._progressive = None
+
+    def commit_lights_enqueue(self):
+        """ft_scene_commit_lights_enqueue: commit_lights without retiring what is queued, unless a directional light over a mesh with
+        light-space shadow structures turns (pose_queue tells)."""
+        self._check(self._lib.ft_scene_commit_lights_enqueue(self._ctx))
+        self._progressive = None
+
+    def pose_queue(self):
+        """ft_debug_pose_queue: a dict of `moved_queued`, `moved_blocking`, `moved_reason` (of the last commit_moved_enqueue: 0 queued, 1 host-only
+        context, 2 a light setter, new vertices or a commit-time option pending, 3 the re-flatten differs in more than poses, 4 a
+        light-space pair's frame changed), the same three for commit_lights_enqueue, `sets` (pose sets on the first device) and `pending`
+        (frames + temporal calls the host still had pending on the first device when the last of the two calls returned)."""
+        out = (C.c_int64 * 8)()
+        self._check(self._lib.ft_debug_pose_queue(self._ctx, out))
+        return dict(zip(_capi.POSE_QUEUE_FIELDS, (int(v) for v in out)))
 
     def tree_quality(self, node):
         """ft_scene_tree_quality: the measured surface-area cost of the tree of the `bsp_mesh(0, tris)` node as it lies in device memory.

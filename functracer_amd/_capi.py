@@ -129,6 +129,16 @@ MOTION_SIGNATURES = [
 MOVED_COMMITS_SIGNATURE = ("ft_debug_moved_commits", C.c_int32, [C.c_void_p, C.POINTER(C.c_int64)])
 MOVED_COMMITS_FIELDS = ("in_place", "full", "full_reason", "pairs_refit")
 MOVED_NOT_FULL, MOVED_OPTION_OFF, MOVED_PENDING, MOVED_DIFFERS = 0, 1, 2, 3
+# ft_scene_commit_moved_enqueue / ft_scene_commit_lights_enqueue / ft_debug_pose_queue (include/functracer_hip.h, "queued pose and light
+# commits"): the hook's eight values, in order, and the reasons a call took the blocking path
+POSE_QUEUE_SIGNATURES = [
+    ("ft_scene_commit_moved_enqueue", C.c_int32, [C.c_void_p]),
+    ("ft_scene_commit_lights_enqueue", C.c_int32, [C.c_void_p]),
+    ("ft_debug_pose_queue", C.c_int32, [C.c_void_p, C.POINTER(C.c_int64)]),
+]
+POSE_QUEUE_FIELDS = ("moved_queued", "moved_blocking", "moved_reason", "lights_queued", "lights_blocking", "lights_reason", "sets", "pending")
+POSE_QUEUED, POSE_HOST_ONLY, POSE_PENDING, POSE_DIFFERS, POSE_PAIR_CHANGED = 0, 1, 2, 3, 4
+POSE_SETS_MAX = 9       # frame slots + FT_TEMPORAL_QUEUE_DEPTH + 1
 
 
 # Deforming meshes (include/functracer_hip.h): new vertices for an existing bspMesh node, committed by a refit of its tree on the device.

@@ -145,6 +145,8 @@ void ft_destroy(ft_context* c) {
         (void)hipSetDevice(c->device);
         (void)drain_frame_streams(c);
         if (c->side) (void)hipStreamSynchronize(c->side);
+        if (c->pose.copies) (void)hipStreamSynchronize(c->pose.copies);
+        c->pose.release();
         for (DeviceBuf& b : c->d_scene) b.release();
         for (DeviceBuf& b : c->d_rays) b.release();
         for (DeviceBuf& b : c->d_acc) b.release();
@@ -509,6 +511,10 @@ static int32_t upload_scene(ft_context* c) {
     if (any_queued(c)) { if ((rc = retire_queued(c)) != FT_OK) return rc; c->accum_open = false; }
     const fth::FlatScene& f = c->flat;
     if ((rc = lds_fits(c)) != FT_OK) return rc;
+    // back to pose set 0, the arrays uploaded below; the other sets have the previous commit's sizes and go (nothing reads them: every
+    // frame and temporal call has been retired, and an upload nobody has read yet ends here)
+    if (c->pose.copies) FT_HIP(c, hipStreamSynchronize(c->pose.copies));
+    c->pose.free_spares();
     c->refit.ready = false;                                         // the trees these uploads bring are not the ones its tables describe
     c->lightspace.reset();                                          // nor the light-space trees ft_scene_commit_lights' tables describe
     ftk::DevScene& S = c->dev_scene;
@@ -722,7 +728,6 @@ static int32_t refit_device(ft_context* c, const fth::FlatScene& f, const fth::S
     if ((rc = drain_frame_streams(c)) != FT_OK) return rc;
     if (c->side) FT_HIP(c, hipStreamSynchronize(c->side));
     ft_context::Refit& R = c->refit;
-    DeviceBuf* B = c->d_scene;
     const bool first = !R.ready;
     if (first) {
         if ((rc = ensure(c, R.d_parent_node, f.nodes.size() * 4)) != FT_OK || (rc = ensure(c, R.d_arrived, f.nodes.size() * 4)) != FT_OK ||
@@ -744,9 +749,10 @@ static int32_t refit_device(ft_context* c, const fth::FlatScene& f, const fth::S
     // "temporal_follow_deformed": what the open accumulation's history saw of each edited mesh, before the first refit since the last
     // accumulate overwrites it (later ones keep it, so several deformations between two accumulates compose)
     if (c->opt.temporal_follow_deformed && c->temporal.open && c->temporal.calls > 0 && (rc = snapshot_records(c, f, edits)) != FT_OK) return rc;
-    if ((rc = upload(c, B[kLeaves], f.leaves)) != FT_OK || (rc = upload(c, B[kCulls], f.culls)) != FT_OK) return rc;
+    // (into the live pose set, which dev_scene points into: d_scene's own arrays unless a queued commit has moved on)
+    if ((rc = upload(c, pose_array(c, kLeaves), f.leaves)) != FT_OK || (rc = upload(c, pose_array(c, kCulls), f.culls)) != FT_OK) return rc;
     cull_items_image(f, c->cull_items_and_rows);
-    if ((rc = upload(c, B[kCullItems], c->cull_items_and_rows)) != FT_OK) return rc;
+    if ((rc = upload(c, pose_array(c, kCullItems), c->cull_items_and_rows)) != FT_OK) return rc;
     FT_HIP(c, hipStreamSynchronize(c->stream));
     ms[0] += since(t0);
     const auto t1 = clock::now();
@@ -1150,12 +1156,22 @@ static int32_t relight_device(ft_context* c, fth::FlatScene& f, const ft_context
     if (any_queued(c)) { if ((rc = retire_queued(c)) != FT_OK) return rc; c->accum_open = false; }
     if ((rc = drain_frame_streams(c)) != FT_OK) return rc;
     if (c->side) FT_HIP(c, hipStreamSynchronize(c->side));
-    if ((rc = upload(c, c->d_scene[kLights], f.lights)) != FT_OK) return rc;
+    if ((rc = upload(c, pose_array(c, kLights), f.lights)) != FT_OK) return rc;   // (the live pose set's: what dev_scene points into)
     ms[0] += std::chrono::duration<double, std::milli>(clock::now() - t0).count();
     if ((rc = rebuild_light_space(c, f, T, jobs, relay, lead, ms, "ft_scene_commit_lights")) != FT_OK) return rc;
     c->zero_signature[0] = c->zero_signature[1] = 0;                // (as every commit)
     c->committed = true;
     ++c->commit_serial; c->staged_hint = -1;
+    return FT_OK;
+}
+
+// Every array of a pose set as `f` and the device's cull image hold it now fits the one in HBM (all sets have set 0's sizes).
+static int32_t pose_arrays_fit(ft_context* c, const fth::FlatScene& f, const char* who) {
+    const DeviceBuf* B = c->d_scene;
+    if (B[kLeaves].bytes < f.leaves.size() * sizeof(ftd::Leaf) || B[kM2w].bytes < f.m2w.size() * 8 || B[kCulls].bytes < f.culls.size() * sizeof(ftd::CullRecord) ||
+        B[kCullItems].bytes < c->cull_items_and_rows.size() * 4 || B[kCullRows].bytes < f.cull_rows.size() * 8 || B[kLights].bytes < f.lights.size() * sizeof(ftd::Light)) {
+        c->err = std::string(who) + ": a scene array in device memory is smaller than the flattened one"; return FT_ERR_STATE;
+    }
     return FT_OK;
 }
 
@@ -1171,14 +1187,11 @@ static int32_t move_device(ft_context* c, fth::FlatScene& f, const ft_context::L
     if (any_queued(c)) { if ((rc = retire_queued(c)) != FT_OK) return rc; c->accum_open = false; }
     if ((rc = drain_frame_streams(c)) != FT_OK) return rc;
     if (c->side) FT_HIP(c, hipStreamSynchronize(c->side));
-    DeviceBuf* B = c->d_scene;
     cull_items_image(f, c->cull_items_and_rows);
-    if (B[kLeaves].bytes < f.leaves.size() * sizeof(ftd::Leaf) || B[kM2w].bytes < f.m2w.size() * 8 || B[kCulls].bytes < f.culls.size() * sizeof(ftd::CullRecord) ||
-        B[kCullItems].bytes < c->cull_items_and_rows.size() * 4 || B[kCullRows].bytes < f.cull_rows.size() * 8) {
-        c->err = "ft_scene_commit_moved: a scene array in device memory is smaller than the flattened one"; return FT_ERR_STATE;
-    }
-    if ((rc = upload(c, B[kLeaves], f.leaves)) != FT_OK || (rc = upload(c, B[kM2w], f.m2w)) != FT_OK || (rc = upload(c, B[kCulls], f.culls)) != FT_OK ||
-        (rc = upload(c, B[kCullItems], c->cull_items_and_rows)) != FT_OK || (rc = upload(c, B[kCullRows], f.cull_rows)) != FT_OK) return rc;
+    if ((rc = pose_arrays_fit(c, f, "ft_scene_commit_moved")) != FT_OK) return rc;
+    // into the live pose set, which dev_scene points into: d_scene's own arrays unless a queued commit has moved on
+    if ((rc = upload(c, pose_array(c, kLeaves), f.leaves)) != FT_OK || (rc = upload(c, pose_array(c, kM2w), f.m2w)) != FT_OK || (rc = upload(c, pose_array(c, kCulls), f.culls)) != FT_OK ||
+        (rc = upload(c, pose_array(c, kCullItems), c->cull_items_and_rows)) != FT_OK || (rc = upload(c, pose_array(c, kCullRows), f.cull_rows)) != FT_OK) return rc;
     FT_HIP(c, hipStreamSynchronize(c->stream));
     ms[0] += std::chrono::duration<double, std::milli>(clock::now() - t0).count();
     // (a pair that lost its usable frame has a new record and no job)
@@ -1189,9 +1202,110 @@ static int32_t move_device(ft_context* c, fth::FlatScene& f, const ft_context::L
     return FT_OK;
 }
 
+// Does a pending frame or a queued temporal call hold pose set k?  (From the host's view: what it has not retired yet.)
+static bool pose_set_held(const ft_context* c, int k) {
+    for (const ft_context::FrameSlot& F : c->slots) if (F.pending && F.pose_set == k) return true;
+    const ft_context::Temporal& T = c->temporal;
+    for (int q = 1; q <= T.q_pending; ++q) if (T.queue[(T.q_turn + ft_context::Temporal::kQueue - q) % ft_context::Temporal::kQueue].pose_set == k) return true;
+    return false;
+}
+
+// A further pose set with set 0's sizes; the first call also makes the entry that stands for set 0 and the uploads' stream.
+static int32_t add_pose_set(ft_context* c) {
+    ft_context::PoseSets& P = c->pose;
+    if (!P.copies) FT_HIP(c, hipStreamCreateWithFlags(&P.copies, hipStreamNonBlocking));
+    const bool first = P.sets.empty();
+    P.sets.emplace_back();
+    ft_context::PoseSets::Set& S = P.sets.back();
+    int32_t rc;
+    size_t at = 0;
+    for (int a = 0; a < ft_context::kPoseArrayCount; ++a) {
+        const size_t bytes = c->d_scene[kPoseArrays[a]].bytes;
+        S.at[a] = at;
+        at += (bytes + 255) / 256 * 256;
+        if (!first && (rc = ensure(c, S.buf[a], bytes)) != FT_OK) { S.release(); P.sets.pop_back(); return rc; }
+    }
+    S.at[ft_context::kPoseArrayCount] = at;
+    if (hipHostMalloc(reinterpret_cast<void**>(&S.staging), at, hipHostMallocDefault) != hipSuccess || hipEventCreateWithFlags(&S.ready, hipEventDisableTiming) != hipSuccess) {
+        S.release(); P.sets.pop_back();
+        c->err = "a pose set's staging memory or event could not be made"; return FT_ERR_HIP;
+    }
+    return FT_OK;
+}
+
+// A queued pose or light commit on one device of the context (ft_scene_commit_moved_enqueue / ft_scene_commit_lights_enqueue, DESIGN.md
+// 14.2): `f` is the held scene with the new poses or lights already in it, every array as long as it was.  Nothing is retired and no
+// stream is drained: the arrays go into a pose set no pending frame or temporal call was given, on a stream of their own, dev_scene is
+// pointed at that set, and every stream that launches scene-reading kernels waits for the upload before its next launch.  `moved`: the
+// poses changed (the cull image is made again).  ms[0] += the host time to queue the uploads.
+static int32_t pose_enqueue_device(ft_context* c, const fth::FlatScene& f, bool moved, double ms[2], const char* who) {
+    using clock = std::chrono::steady_clock;
+    int32_t rc;
+    FT_HIP(c, hipSetDevice(c->device));
+    const auto t0 = clock::now();
+    ft_context::PoseSets& P = c->pose;
+    if (moved) cull_items_image(f, c->cull_items_and_rows);
+    if ((rc = pose_arrays_fit(c, f, who)) != FT_OK) return rc;
+    if (P.sets.empty() && (rc = add_pose_set(c)) != FT_OK) return rc;   // set 0's entry: its staging memory and event
+    // The set: the live one when nothing pending was given it (nothing on the device reads it any more: blocking calls end before they
+    // return), else any other that is free, else a new one; with every set held and none left to make, the oldest pending frame or
+    // temporal call is retired, as queuing a fifth frame retires the first.
+    int pick = -1;
+    for (;;) {
+        if (!pose_set_held(c, P.live)) pick = P.live;
+        for (int k = 0; pick < 0 && k < (int)P.sets.size(); ++k) if (!pose_set_held(c, k)) pick = k;
+        if (pick >= 0) break;
+        if ((int)P.sets.size() < P.max_sets) { if ((rc = add_pose_set(c)) != FT_OK) return rc; pick = (int)P.sets.size() - 1; break; }
+        ++P.retired_for_set;
+        if ((rc = any_pending(c) ? retire_oldest_frame(c) : retire_oldest_temporal(c)) != FT_OK) return rc;
+    }
+    ft_context::PoseSets::Set& S = P.sets[(size_t)pick];
+    // The staging copy is the source of the set's previous upload, which waits for nothing on the device: it has ended, or ends now.
+    // (The host's own vectors are pageable and rewritten by the next call: they are never the source of an asynchronous copy.)
+    if (S.uploaded) FT_HIP(c, hipEventSynchronize(S.ready));
+    const void* src[ft_context::kPoseArrayCount] = {f.leaves.data(), f.m2w.data(), f.culls.data(), c->cull_items_and_rows.data(), f.cull_rows.data(), f.lights.data()};
+    const size_t bytes[ft_context::kPoseArrayCount] = {f.leaves.size() * sizeof(ftd::Leaf), f.m2w.size() * 8, f.culls.size() * sizeof(ftd::CullRecord),
+                                                       c->cull_items_and_rows.size() * 4, f.cull_rows.size() * 8, f.lights.size() * sizeof(ftd::Light)};
+    ftk::DevScene& D = c->dev_scene;
+    for (int a = 0; a < ft_context::kPoseArrayCount; ++a) {
+        void* dst = pick == 0 ? c->d_scene[kPoseArrays[a]].p : S.buf[a].p;
+        if (bytes[a]) {
+            std::memcpy(S.staging + S.at[a], src[a], bytes[a]);
+            FT_HIP(c, hipMemcpyAsync(dst, S.staging + S.at[a], bytes[a], hipMemcpyHostToDevice, P.copies));
+        }
+    }
+    FT_HIP(c, hipEventRecord(S.ready, P.copies));
+    S.uploaded = true;
+    const auto point = [&](auto*& ptr, int a) { ptr = static_cast<std::remove_reference_t<decltype(ptr)>>(pick == 0 ? c->d_scene[kPoseArrays[a]].p : S.buf[a].p); };
+    point(D.leaves, 0); point(D.m2w, 1); point(D.culls, 2); point(D.cull_items, 3); point(D.cull_rows, 4); point(D.lights, 5);
+    P.live = pick;
+    // every stream that launches kernels that read the scene: the main streams and `side`, where k_classify runs ahead (`tail` runs
+    // k_resolve, which reads no scene array)
+    FT_HIP(c, hipStreamWaitEvent(c->stream, S.ready, 0));
+    for (hipStream_t m : c->more_mains) if (m) FT_HIP(c, hipStreamWaitEvent(m, S.ready, 0));
+    if (c->side) FT_HIP(c, hipStreamWaitEvent(c->side, S.ready, 0));
+    ms[0] += std::chrono::duration<double, std::milli>(clock::now() - t0).count();
+    c->zero_signature[0] = c->zero_signature[1] = 0;                // (as every commit)
+    c->committed = true;
+    ++c->commit_serial; c->staged_hint = -1;
+    return FT_OK;
+}
+
+// What ft_debug_pose_queue reports of one _enqueue call (`lights`: of the lights call): why it took the blocking path, or 0, and what the
+// host still had pending on the first device when it returned.
+static void note_pose_call(ft_context* c, bool lights, int64_t why) {
+    int64_t* n = c->pose.counts + (lights ? 3 : 0);
+    ++n[why == 0 ? 0 : 1]; n[2] = why;
+    int64_t pending = c->temporal.q_pending;
+    for (const ft_context::FrameSlot& F : c->slots) pending += F.pending ? 1 : 0;
+    c->pose.counts[7] = pending;
+}
+
 // ft_scene_commit_moved under "moved_in_place".  FT_OK with *in_place false: the re-flatten differs in more than poses and nothing was
 // changed - the caller takes the full commit.
-static int32_t move_in_place(ft_context* c, bool* in_place) {
+// `queue` (ft_scene_commit_moved_enqueue): when no light-space pair's frame changed the poses are queued instead (pose_enqueue_device) and
+// *queued says so; with a changed pair the call goes on as the blocking one.
+static int32_t move_in_place(ft_context* c, bool* in_place, bool queue = false, bool* queued = nullptr) {
     using clock = std::chrono::steady_clock;
     const auto t0 = clock::now();
     *in_place = false;
@@ -1255,8 +1369,11 @@ static int32_t move_in_place(ft_context* c, bool* in_place) {
     c->commit_ms[0] = std::chrono::duration<double, std::milli>(clock::now() - t0).count();
     double ms[2] = {0.0, 0.0};
     int32_t rc = FT_OK;
+    const bool queues = queue && !turned;                           // (a changed pair means refit and grid kernels that write what frames in flight read)
+    if (queued) *queued = queues;
     for (ft_context* d : devices(c)) {                              // every device rewrites its own copy; the first decides the grids
-        if ((rc = move_device(d, f, T, jobs, turned, turned && grids, d == c, ms)) != FT_OK) { if (d != c) c->err = d->err; break; }
+        rc = queues ? pose_enqueue_device(d, f, true, ms, "ft_scene_commit_moved_enqueue") : move_device(d, f, T, jobs, turned, turned && grids, d == c, ms);
+        if (rc != FT_OK) { if (d != c) c->err = d->err; break; }
     }
     for (ft_context* p : c->peers) {
         p->flat.leaves = f.leaves; p->flat.m2w = f.m2w; p->flat.culls = f.culls; p->flat.cull_items = f.cull_items; p->flat.cull_rows = f.cull_rows;
@@ -1284,21 +1401,22 @@ int32_t ft_scene_commit(ft_context* c) {
 // The commit of a graph whose transforms alone changed (ft_sg_set_transform): ft_scene_commit's, but the temporal accumulation stays
 // open - the leaves are the same in the same order, and the next ft_temporal_accumulate takes each moved leaf's surfaces back to the
 // pose its history was written in (ft_passes.cpp).  A progressive accumulation's sums belong to the old scene: it ends.
-int32_t ft_scene_commit_moved(ft_context* c) {
+// `queue`: ft_scene_commit_moved_enqueue - the call as under "moved_in_place" = 1 whatever the option says, queued when it can be.
+static int32_t commit_moved(ft_context* c, bool queue) {
     if (!c) return FT_ERR_INVALID;
     if (!c->holds_commit) { c->err = "ft_scene_commit_moved: no committed scene to move (ft_scene_commit)"; return FT_ERR_STATE; }
     if (c->restructured) { c->err = "ft_scene_commit_moved: the graph, the root or the lights changed since the commit (ft_scene_commit)"; return FT_ERR_STATE; }
     // Option "moved_in_place" (DESIGN.md 14.1): the new poses go over the old ones and the light-space pairs follow on the device.  What
     // a full commit has always absorbed - a pending light setter, new vertices, a commit-time option - is still the full commit's.
     int64_t why = 0;
-    if (c->host_only || !c->opt.moved_in_place) why = 1;
+    if (c->host_only || !(c->opt.moved_in_place || queue)) why = 1;
     else if (c->lights_pending || c->options_pending) why = 2;
     else for (const fth::GraphNode& n : c->graph.nodes) if (n.deformed) why = 2;
     if (why == 0) {
-        bool in_place = false;
-        const int32_t rc = move_in_place(c, &in_place);
+        bool in_place = false, queued = false;
+        const int32_t rc = move_in_place(c, &in_place, queue, &queued);
         if (in_place) {
-            if (rc == FT_OK) { ++c->pose_serial; ++c->moved_counts[0]; c->moved_counts[2] = 0; }
+            if (rc == FT_OK) { ++c->pose_serial; ++c->moved_counts[0]; c->moved_counts[2] = 0; if (queue) note_pose_call(c, false, queued ? 0 : 4); }
             return rc;
         }
         if (rc != FT_OK) return rc;
@@ -1306,9 +1424,11 @@ int32_t ft_scene_commit_moved(ft_context* c) {
     }
     progressive_close(c);
     const int32_t rc = commit_scene(c);
-    if (rc == FT_OK) { ++c->pose_serial; ++c->moved_counts[1]; c->moved_counts[2] = why; c->moved_counts[3] = 0; }
+    if (rc == FT_OK) { ++c->pose_serial; ++c->moved_counts[1]; c->moved_counts[2] = why; c->moved_counts[3] = 0; if (queue) note_pose_call(c, false, why); }
     return rc;
 }
+int32_t ft_scene_commit_moved(ft_context* c) { return commit_moved(c, false); }
+int32_t ft_scene_commit_moved_enqueue(ft_context* c) { return commit_moved(c, true); }
 
 int32_t ft_debug_moved_commits(ft_context* c, int64_t out[4]) {
     if (!c || !out) return FT_ERR_INVALID;
@@ -1422,7 +1542,8 @@ int32_t ft_scene_commit_deformed(ft_context* c) {
 // work.  The lights are uploaded again; every light-space pair whose direction changed gets its record derived again on the host, as
 // build_light_space derives it, its tree refit and its grid built again on the device (ft_lightspace.hip).  The temporal accumulation
 // stays open and the pose counter stays; a progressive accumulation ends.
-int32_t ft_scene_commit_lights(ft_context* c) {
+// `queue`: ft_scene_commit_lights_enqueue - queued when no light that has a light-space pair turns.
+static int32_t commit_lights(ft_context* c, bool queue) {
     if (!c) return FT_ERR_INVALID;
     if (!c->holds_commit) { c->err = "ft_scene_commit_lights: no committed scene to relight (ft_scene_commit)"; return FT_ERR_STATE; }
     if (c->restructured) { c->err = "ft_scene_commit_lights: the graph, the root or the number or kinds of the lights changed since the commit (ft_scene_commit)"; return FT_ERR_STATE; }
@@ -1431,7 +1552,9 @@ int32_t ft_scene_commit_lights(ft_context* c) {
     if (c->options_pending) { c->err = "ft_scene_commit_lights: a commit-time option changed since the commit (ft_scene_commit)"; return FT_ERR_STATE; }
     if (c->host_only) {                                             // the same rules; the commit itself is the full one
         progressive_close(c);
-        return commit_scene(c);
+        const int32_t rc = commit_scene(c);
+        if (rc == FT_OK && queue) note_pose_call(c, true, 1);
+        return rc;
     }
     using clock = std::chrono::steady_clock;
     const auto t0 = clock::now();
@@ -1473,15 +1596,21 @@ int32_t ft_scene_commit_lights(ft_context* c) {
     c->commit_ms[0] = std::chrono::duration<double, std::milli>(clock::now() - t0).count();
     double ms[2] = {0.0, 0.0};
     int32_t rc = FT_OK;
+    const bool queues = queue && !turned;                           // (a light with pairs that turns means refit and grid kernels that write what frames in flight read)
     for (ft_context* d : devices(c)) {                              // every device rewrites its own copy; the first decides the grids
-        if ((rc = relight_device(d, f, T, jobs, turned && grids, d == c, ms)) != FT_OK) { if (d != c) c->err = d->err; break; }
+        rc = queues ? pose_enqueue_device(d, f, false, ms, "ft_scene_commit_lights_enqueue") : relight_device(d, f, T, jobs, turned && grids, d == c, ms);
+        if (rc != FT_OK) { if (d != c) c->err = d->err; break; }
     }
     for (ft_context* p : c->peers) { p->flat.lights = f.lights; p->flat.ls_pairs = f.ls_pairs; }
     c->commit_ms[1] = ms[1]; c->commit_ms[2] = ms[0];
     if (rc != FT_OK) { for (ft_context* d : devices(c)) d->committed = false; c->holds_commit = false; return rc; }   // HBM holds neither scene whole: ft_scene_commit
     c->lights_pending = false;
+    if (queue) note_pose_call(c, true, queues ? 0 : 4);
     return FT_OK;
 }
+int32_t ft_scene_commit_lights(ft_context* c) { return commit_lights(c, false); }
+int32_t ft_scene_commit_lights_enqueue(ft_context* c) { return commit_lights(c, true); }
+
 
 // The measured quality of one mesh's tree: what a host sets "refit_rebuild_percent" by.
 int32_t ft_scene_tree_quality(ft_context* c, ft_node mesh_node, double out[4]) {

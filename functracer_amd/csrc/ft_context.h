@@ -253,6 +253,7 @@ struct ft_context {
         ftk::FrameReport* d_report = nullptr;   // written by the frame's last kernel through this device-side address of the same memory
         uint64_t signature = 0;                 // what the frame rendered (scene, size, samples, depth, threshold): keys the staged-launch hint
         bool pending = false;
+        int pose_set = 0;                       // the pose set its launches were given (PoseSets): held until the frame retires
         uint64_t rays_primary = 0; int64_t n_pix_total = 0; int32_t spp = 0, n_launches = 0, n_chunks = 0, format = 0; bool classify = false;   // (n_launches, n_chunks: as planned from the request, FramePlan::n_planned)
         std::chrono::steady_clock::time_point wall0;
         void release() {
@@ -263,6 +264,40 @@ struct ft_context {
         }
     };
     FrameSlot slots[kSlots];
+    // ft_scene_commit_moved_enqueue / ft_scene_commit_lights_enqueue.  A pose set is one copy in HBM of what depends on a
+    // pose or a light value - kPoseArrays - with a page-locked staging copy of the same size (`staging`, the arrays one behind the other at
+    // `at`) and the event behind its last upload.  Set 0 IS d_scene[kPoseArrays] (its `buf` stay empty); the others are allocated on first
+    // need with set 0's sizes, kMaxSets at most in all: one per frame slot, one per queued temporal call and the one being written.
+    // `live`: the set dev_scene points into - every launch from now on reads it, and every blocking commit uploads into it (pose_array).
+    // A frame slot or temporal queue slot names the set its launches were given; a set nothing pending names has no reader on the device.
+    // Freed by every full commit (upload_scene), which goes back to the scene's own arrays: the sizes may be stale.
+    static constexpr int kPoseArrayCount = 6;
+    struct PoseSets {
+        static constexpr int kMaxSets = kSlots + FT_TEMPORAL_QUEUE_DEPTH + 1;
+        struct Set {
+            DeviceBuf buf[kPoseArrayCount];
+            char* staging = nullptr; size_t at[kPoseArrayCount + 1] = {};
+            hipEvent_t ready = nullptr; bool uploaded = false;   // uploaded: `ready` has been recorded (the staging copy may still be the source of a copy)
+            void release() {
+                for (DeviceBuf& b : buf) b.release();
+                if (staging) (void)hipHostFree(staging);
+                if (ready) (void)hipEventDestroy(ready);
+                staging = nullptr; ready = nullptr; uploaded = false;
+            }
+        };
+        std::vector<Set> sets;          // empty until the first queued call; sets[0] then stands for d_scene's own arrays
+        int live = 0;
+        hipStream_t copies = nullptr;   // the uploads' own stream
+        int max_sets = kMaxSets;        // (lowered only by a scratch build that tests the retirement branch)
+        // ft_debug_pose_queue, on the context's first device: [0] moved calls queued, [1] moved calls that took the blocking path, [2] why the
+        // last one did, [3 .. 5] the same for the lights calls, [7] frames + temporal calls pending when the last _enqueue call returned
+        // ([6] is sets.size(), at least 1); retired_for_set: frames or temporal calls retired because every set was held
+        int64_t counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        int64_t retired_for_set = 0;
+        // back to the scene's own arrays alone (the entry that stands for them goes too: its staging copy has the old scene's sizes)
+        void free_spares() { for (Set& s : sets) s.release(); sets.clear(); live = 0; }
+        void release() { for (Set& s : sets) s.release(); sets.clear(); live = 0; if (copies) (void)hipStreamDestroy(copies); copies = nullptr; }
+    } pose;
     // ft_scene_commit_deformed's own tables in HBM (ftk::RefitArrays), made by the first refit after a full commit and kept until the next
     // one (`ready`); d_verts: the new vertices of the meshes being refit.
     struct Refit {
@@ -425,6 +460,7 @@ struct ft_context {
             std::vector<double> motion, jitter;
             std::vector<ftk::TemporalDeformLeaf> deform;
             int64_t n_pix = 0; int32_t n_launches = 0;
+            int pose_set = 0;                   // the pose set its guide passes were given (PoseSets): held until the call retires
             std::chrono::steady_clock::time_point wall0;
             void release() {
                 for (DeviceBuf* b : {&d_motion, &d_deform, &d_snap}) b->release();
@@ -501,6 +537,15 @@ struct RenderRequest {
 constexpr double kNoJitter[2] = {0.0, 0.0};
 inline bool any_pending(const ft_context* c, bool on_second_main = false) { for (const auto& f : c->slots) if (f.pending && (!on_second_main || f.main_ix != 0)) return true; return false; }
 
+// The arrays of a pose set, in its order, and the buffer of the LIVE set that holds array k (one of kPoseArrays): where every blocking
+// commit uploads poses and lights, so that they land in what dev_scene points into.  Without a queued call that is d_scene[k].
+constexpr SceneArray kPoseArrays[ft_context::kPoseArrayCount] = {kLeaves, kM2w, kCulls, kCullItems, kCullRows, kLights};
+inline DeviceBuf& pose_array(ft_context* c, SceneArray k) {
+    if (c->pose.live == 0) return c->d_scene[k];
+    for (int a = 0; a < ft_context::kPoseArrayCount; ++a) if (kPoseArrays[a] == k) return c->pose.sets[(size_t)c->pose.live].buf[a];
+    return c->d_scene[k];
+}
+
 // ft_capi.cpp
 bool need_device(ft_context* c);
 bool need_committed(ft_context* c);
@@ -516,6 +561,7 @@ int32_t fetch_single(ft_context* c, void* out, int format);
 ftk::RayBuf ray_view(const DeviceBuf& b, int64_t cap);
 int32_t ensure_frame_buffers(ft_context* c, int64_t cap, bool reflective);
 int32_t retire_pending(ft_context* c, ft_stats* stats);
+int32_t retire_oldest_frame(ft_context* c);                         // the oldest pending frame alone, as queuing a fifth frame retires it
 std::vector<std::vector<ft_rect>> band_shares(const RenderRequest& q, size_t n_devs);
 int32_t check_request(ft_context* c, const RenderRequest& q);
 std::vector<ft_rect> clip_rects(const RenderRequest& q);
@@ -533,6 +579,7 @@ void temporal_drop_snapshots(ft_context* c);
 // ft_temporal_clamp_status from the newest and `stats`, when given, with that call's.  Returns the first error among them; a hit-list
 // overflow ends the accumulation.  Nothing queued: FT_OK, stats untouched.
 int32_t retire_temporal(ft_context* c, ft_stats* stats);
+int32_t retire_oldest_temporal(ft_context* c);                      // the oldest queued temporal call alone
 // Everything queued on this device, as the blocking calls and the commits retire it: the frames, then the temporal calls that read them.
 inline bool any_queued(const ft_context* c) { return any_pending(c) || c->temporal.q_pending > 0; }
 inline int32_t retire_queued(ft_context* c) {

@@ -325,6 +325,14 @@ int32_t ft_debug_classify_reuse(ft_context* c, int64_t out[4]) {
     return FT_OK;
 }
 
+// What the queued pose and light commits did since ft_create (ft_context::PoseSets::counts), and the pose sets the first device holds.
+int32_t ft_debug_pose_queue(ft_context* c, int64_t out[8]) {
+    if (!c || !out) return FT_ERR_INVALID;
+    for (int k = 0; k < 8; ++k) out[k] = c->pose.counts[k];
+    out[6] = c->host_only ? 0 : std::max<int64_t>(1, (int64_t)c->pose.sets.size());
+    return FT_OK;
+}
+
 // Which kernel the bounce-0 launches of the frames queued since ft_create went to: k_primary, k_primary_mesh.
 int32_t ft_debug_primary_kernels(ft_context* c, int64_t out[2]) {
     if (!c || !out) return FT_ERR_INVALID;

@@ -131,6 +131,14 @@ int32_t retire_pending(ft_context* c, ft_stats* stats) {
     return rc;
 }
 
+int32_t retire_oldest_frame(ft_context* c) {
+    for (int k = 0; k < ft_context::kSlots; ++k) {
+        ft_context::FrameSlot& f = c->slots[(c->slot_turn + k) % ft_context::kSlots];
+        if (f.pending) return retire_frame(c, f, nullptr);
+    }
+    return FT_OK;
+}
+
 // What a frame is, decided on the host from the request and the context's cached state before anything is queued (plan_pixels,
 // plan_chunks); queue_frame then puts it on the device.
 struct FramePlan {
@@ -565,6 +573,7 @@ static int32_t queue_frame(ft_context* c, const RenderRequest& q, const FramePla
     FT_HIP(c, hipGetLastError());
     F.signature = p.signature; F.simple = p.simple; F.main_ix = main_ix;
     F.pending = true; F.wall0 = wall0;
+    F.pose_set = c->pose.live;                                     // every launch above was given dev_scene as it points now
     F.rays_primary = 0;
     if (p.corner) for (auto& j : p.jobs) F.rays_primary += (uint64_t)j.n_ids * (uint64_t)p.spp;
     else F.rays_primary = (uint64_t)p.n_pix_total * (uint64_t)p.spp;   // the windows of a pixel list cover it, launched or not

@@ -764,6 +764,16 @@ int32_t retire_temporal(ft_context* c, ft_stats* stats) {
     if (rc != FT_OK) c->err = why;
     return rc;
 }
+int32_t retire_oldest_temporal(ft_context* c) {
+    ft_context::Temporal& T = c->temporal;
+    if (T.q_pending == 0) return FT_OK;
+    FT_HIP(c, hipSetDevice(c->device));
+    const int32_t rc = retire_temporal_slot(c, T.queue[(T.q_turn + ft_context::Temporal::kQueue - T.q_pending) % ft_context::Temporal::kQueue], nullptr);
+    --T.q_pending;
+    if (T.q_pending == 0) T.fork_owed = false;
+    if (rc == FT_ERR_OVERFLOW) { const std::string why = c->err; (void)retire_temporal(c, nullptr); T.release(); c->err = why; }   // as retire_temporal ends it
+    return rc;
+}
 } // namespace ftc
 
 static int32_t temporal_enqueue_single(ft_context* c, const RenderRequest& q, int32_t sample, const ft_temporal_params& P, const ft_temporal_filter_params* F, bool rgba8, void* host_out) {
@@ -893,6 +903,7 @@ static int32_t temporal_enqueue_single(ft_context* c, const RenderRequest& q, in
     if (following) { S.d_snap = T.d_snap; T.d_snap = DeviceBuf{}; }
     temporal_advance(c, cam, moving);
     S.n_pix = n_pix; S.n_launches = n_launches; S.wall0 = wall0;
+    S.pose_set = c->pose.live;                                      // the guide passes above were given dev_scene as it points now
     T.q_turn = (T.q_turn + 1) % Temporal::kQueue; ++T.q_pending;
     return FT_OK;
 }
