@@ -52,6 +52,7 @@ namespace {
 #define FT_DEV __device__ __forceinline__
 
 constexpr double kEps = 0.0000001;
+constexpr double kSignFloor = 0x1p-900;                              // tri_hit: |sh / a| above this cannot underflow in u = (1 / a) sh; |a| >= kEps keeps |a| 2^-900 normal
 constexpr int kDone = INT32_MIN;
 
 // Scene data is immutable for the lifetime of a launch.  Reading it through constant-address-space
@@ -326,12 +327,13 @@ FT_DEV bool tri_hit(cdp T, const Ray& r, double& t_out) {
     if (a > -kEps && a < kEps) return false;
     const double sx = r.ox - v0x, sy = r.oy - v0y, sz = r.oz - v0z;
     const double sh = sx * hx + sy * hy + sz * hz;
-    const double abs_a = fabs(a);
-    // u = (1/a)*sh: u < 0 iff sh and a have strictly opposite signs; |sh| > |a|(1+4e-15) implies fl(u) > 1.
-    if ((sh < 0.0 && a > 0.0) || (sh > 0.0 && a < 0.0) || fabs(sh) > abs_a * 1.000000000000004) return false;
+    const double abs_a = fabs(a), tiny = abs_a * kSignFloor;
+    // u = (1/a)*sh: opposite signs and |sh| > |a| 2^-900 imply fl(u) < 0 (below that fl(u) can underflow to -0, which is not < 0: the
+    // division decides); |sh| > |a|(1+4e-15) implies fl(u) > 1.
+    if ((sh < -tiny && a > 0.0) || (sh > tiny && a < 0.0) || fabs(sh) > abs_a * 1.000000000000004) return false;
     const double qx = sy * e1z - sz * e1y, qy = e1x * sz - e1z * sx, qz = sx * e1y - sy * e1x;               // s .** edge1
     const double dq = r.dx * qx + r.dy * qy + r.dz * qz;
-    if ((dq < 0.0 && a > 0.0) || (dq > 0.0 && a < 0.0) || fabs(dq) > abs_a * 1.000000000000004) return false;
+    if ((dq < -tiny && a > 0.0) || (dq > tiny && a < 0.0) || fabs(dq) > abs_a * 1.000000000000004) return false;
     const double f = 1.0 / a;
     const double u = f * sh;
     if (u < 0.0 || u > 1.0) return false;
@@ -352,14 +354,14 @@ FT_DEV bool tri_hit_wave(cdp T, const Ray& r, bool live, double& t_out) {
     const double a = e1x * hx + e1y * hy + e1z * hz;
     const double sx = r.ox - v0x, sy = r.oy - v0y, sz = r.oz - v0z;
     const double sh = sx * hx + sy * hy + sz * hz;
-    const double abs_a = fabs(a), lim = abs_a * 1.000000000000004;
+    const double abs_a = fabs(a), lim = abs_a * 1.000000000000004, tiny = abs_a * kSignFloor;
     const bool pos = a > 0.0, neg = a < 0.0;
     bool ok = live & !((a > -kEps) & (a < kEps));
-    ok = ok & !(((sh < 0.0) & pos) | ((sh > 0.0) & neg) | (fabs(sh) > lim));
+    ok = ok & !(((sh < -tiny) & pos) | ((sh > tiny) & neg) | (fabs(sh) > lim));
     if (!__any(ok)) return false;                                   // the usual end in a dense mesh: the triangle lies beside the whole bundle
     const double qx = sy * e1z - sz * e1y, qy = e1x * sz - e1z * sx, qz = sx * e1y - sy * e1x;
     const double dq = r.dx * qx + r.dy * qy + r.dz * qz;
-    ok = ok & !(((dq < 0.0) & pos) | ((dq > 0.0) & neg) | (fabs(dq) > lim));
+    ok = ok & !(((dq < -tiny) & pos) | ((dq > tiny) & neg) | (fabs(dq) > lim));
     if (!__any(ok)) return false;
     const double f = 1.0 / a;
     const double u = f * sh;
@@ -667,7 +669,11 @@ FT_DEV void mesh_bsp_query(const Scene& S, int32_t root, const Ray& r, Query<ANY
 }
 
 // The same walk for a coherent wave that mesh_bsp_packet turned away: the wave walks the tree one node at a time together (a
-// WaveStack, scalar loads), entering a node if any live lane's test passes.
+// WaveStack, scalar loads), entering a node if any live lane's test passes.  A lane whose own test of an entered node fails sits that
+// node's subtree out (`out_at`: the stack height at which it left; it is back once a pop goes below that - the node's pending left child
+// lies AT that height): the reference's box test turns a ray away that runs in a face of the box with a zero direction component
+// (0 * inf = NaN falls through BoundingBox.fs:41-56) although it meets the triangles inside, so "another lane's box can only offer
+// triangles this lane misses" does not hold here, and these are the waves that come here.
 template <bool ANY>
 FT_DEV void mesh_bsp_narrow(const Scene& S, int32_t root, const Ray& r, Query<ANY>& q, uint32_t leaf, bool lit) {
     bool alive = q.active && !(ANY && q.blocked);
@@ -677,16 +683,18 @@ FT_DEV void mesh_bsp_narrow(const Scene& S, int32_t root, const Ray& r, Query<AN
     uint32_t best_tri = 0u;
     bool found = false;
     WaveStack st;
-    int cur = root;
+    int cur = root, out_at = -1;                                    // out_at < 0: the lane is inside every box on the way to `cur`
     for (;;) {
         cur = __builtin_amdgcn_readfirstlane(cur);
         if (cur >= 0) {
             cdp nd = S.nodes + 8ull * (uint32_t)cur;
             double entry = 0.0, exit = 0.0;
-            const bool enter = alive && aabb_hit(nd, r, ivx, ivy, ivz, &entry, &exit) && !(entry > bound * (1.0 + 1e-12) + 1e-12) && !(exit < 0.0);
+            const bool in = alive && out_at < 0;
+            const bool enter = in && aabb_hit(nd, r, ivx, ivy, ivz, &entry, &exit) && !(entry > bound * (1.0 + 1e-12) + 1e-12) && !(exit < 0.0);
             if (__any(enter)) {
                 cip ch = reinterpret_cast<cip>(nd + 6);
                 const int left = ch[0];
+                out_at = (in && !enter) ? st.sp : out_at;
                 st.lanes = ((int)lane_id() == st.sp) ? left : st.lanes;
                 ++st.sp; cur = ch[1];
                 continue;
@@ -695,7 +703,7 @@ FT_DEV void mesh_bsp_narrow(const Scene& S, int32_t root, const Ray& r, Query<AN
             const uint32_t first = S.bsp_leaves[2 * (~cur)], count = S.bsp_leaves[2 * (~cur) + 1];
             for (uint32_t k = 0; k < count; ++k) {
                 double t;
-                if (alive && tri_hit(S.tris + 9ull * (first + k), r, t)) {
+                if (alive && out_at < 0 && tri_hit(S.tris + 9ull * (first + k), r, t)) {
                     if (ANY) { if (t < bound) { q.blocked = true; alive = false; } }
                     else if (t < bound) { bound = t; best_tri = first + k; found = true; }
                 }
@@ -703,6 +711,7 @@ FT_DEV void mesh_bsp_narrow(const Scene& S, int32_t root, const Ray& r, Query<AN
             if (ANY) { if (!__any(alive)) break; }
         }
         if (!st.pop(cur)) break;
+        out_at = st.sp < out_at ? -1 : out_at;
     }
     if (!ANY && found) q.hit(bound, leaf, best_tri, lit);
 }
