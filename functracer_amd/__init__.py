@@ -15,7 +15,7 @@ from . import _capi
 from ._capi import (CIRCLE, CONE, CUBE, CYLINDER, EXCLUDE, INTERSECT, PLANE, SOLID_CYLINDER, SPHERE, SQUARE, SUBTRACT, UNION,
                     FtError, SceneBuilder, make_camera)
 
-__all__ = ["Context", "ls_topology", "PinnedArray", "ParsedScene", "parse_scene", "parse_scene_file", "jitter_pattern", "quantise_rgba8", "write_png",
+__all__ = ["Context", "ls_topology", "PinnedArray", "ParsedScene", "parse_scene", "parse_scene_file", "jitter_pattern", "morph_blend", "quantise_rgba8", "write_png",
            "parse_colour", "parse_ply", "FtError", "make_camera", "HIP_LIB", "HOST_LIB", "DEFAULT_SEED"]
 
 HIP_LIB = os.environ.get("FT_HIP_LIB") or os.path.join(_capi.LIB_DIR, "libfunctracer_hip.so")   # FT_HIP_LIB: experimental builds
@@ -74,7 +74,7 @@ def hip_lib():
         if hasattr(lib, _capi.MOVED_COMMITS_SIGNATURE[0]):          # (FT_HIP_LIB may name an older build, as above)
             fn = getattr(lib, _capi.MOVED_COMMITS_SIGNATURE[0])
             fn.restype, fn.argtypes = _capi.MOVED_COMMITS_SIGNATURE[1:]
-        for name, res, args in _capi.POSE_QUEUE_SIGNATURES:
+        for name, res, args in _capi.POSE_QUEUE_SIGNATURES + _capi.MORPH_SIGNATURES:
             if hasattr(lib, name):                                  # (FT_HIP_LIB may name an older build, as above)
                 fn = getattr(lib, name)
                 fn.restype, fn.argtypes = res, args
@@ -164,6 +164,23 @@ def parse_ply(text):
     out = np.zeros((n, 9))
     host_lib().fth_parse_ply(text.encode(), _capi.dptr(out), n, err, len(err))
     return out
+
+
+def morph_blend(base, targets, w):
+    """The vertices ft_sg_set_mesh_weights declares (include/functracer_hip.h, "morph targets"), evaluated in numpy with one elementwise
+    IEEE double operation per step: D_k = T_k - B, then acc = B; p = w_k * D_k; acc = acc + p for k = 0 .. K-1 in order, every term
+    evaluated.  base [n, 9], targets [K, n, 9] (absolute positions), w [K]; returns [n, 9].  What the library promises bit for bit."""
+    base = np.ascontiguousarray(base, dtype=np.float64).reshape(-1, 9)
+    targets = np.ascontiguousarray(targets, dtype=np.float64).reshape(-1, base.shape[0], 9)
+    w = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
+    if w.shape[0] != targets.shape[0]:
+        raise ValueError("morph_blend: one weight per target")
+    acc = base.copy()
+    for k in range(targets.shape[0]):
+        d = targets[k] - base
+        p = w[k] * d
+        acc = acc + p
+    return acc
 
 
 def jitter_pattern(n, seed=DEFAULT_SEED):
@@ -614,6 +631,35 @@ class Context(SceneBuilder):
         edited meshes' records are kept as the accumulation last saw them (72 bytes per triangle, until the next temporal_accumulate)."""
         self._check(self._lib.ft_scene_commit_deformed(self._ctx))
         self._progressive = None
+
+    # morph targets: vertices blended on the device before the refit (include/functracer_hip.h) --------
+    def set_mesh_targets(self, node, targets):
+        """ft_sg_set_mesh_targets: the key shapes of the `bsp_mesh` node, [K, n, 9] absolute positions (K = 0 .. 16; an empty array removes
+        them).  The node's vertices as they stand become the base; the library keeps the targets as deltas from it."""
+        t = _capi.as_f64(targets)
+        if t.ndim == 4:                                             # [K, n, 3, 3]
+            t = t.reshape(t.shape[0], t.shape[1], -1)
+        if t.ndim != 3 or t.shape[2] != 9:
+            raise ValueError("set_mesh_targets: targets are [K, n, 9]")
+        self._check(self._lib.ft_sg_set_mesh_targets(self._ctx, int(node), _capi.dptr(t) if t.shape[0] else None, t.shape[0], t.shape[1]))
+
+    def set_mesh_weights(self, node, w):
+        """ft_sg_set_mesh_weights: the node's vertices are morph_blend(base, targets, w) from the next commit on; commit_deformed makes
+        them on the device (option "morph_on_device", default 1)."""
+        w = _capi.as_f64(w).reshape(-1)
+        self._check(self._lib.ft_sg_set_mesh_weights(self._ctx, int(node), _capi.dptr(w) if w.size else None, w.shape[0]))
+
+    def morph(self, node):
+        """ft_debug_morph: a dict of `device_commits` (commit_deformed calls since the context was created that blended a mesh on the
+        device), `device_meshes` / `host_meshes` (meshes the last commit_deformed blended on the device / on the host), `resident_bytes`
+        (base and deltas of `node` per device), `scan` (8 doubles: the bounds lo, hi and the extent that call used for `node`) and
+        `from_device` (whether they were reduced on the device)."""
+        counts = (C.c_int64 * 4)()
+        scan = np.zeros(8)
+        self._check(self._lib.ft_debug_morph(self._ctx, int(node), counts, _capi.dptr(scan)))
+        out = dict(zip(_capi.MORPH_FIELDS, (int(v) for v in counts)))
+        out["scan"], out["from_device"] = scan, bool(scan[7] == 1.0)
+        return out
 
     # moving lights (include/functracer_hip.h) ---------------------------------------------------------
     def set_directional(self, light, direction, colour):

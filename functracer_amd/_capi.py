@@ -148,6 +148,15 @@ DEFORM_SIGNATURES = [
     ("ft_scene_tree_quality", C.c_int32, [C.c_void_p, C.c_int32, c_double_p]),
 ]
 
+# Morph targets (include/functracer_hip.h): key shapes resident in device memory, weights per frame; ft_debug_morph's counts, in order
+MAX_MORPH_TARGETS = 16
+MORPH_SIGNATURES = [
+    ("ft_sg_set_mesh_targets", C.c_int32, [C.c_void_p, C.c_int32, c_double_p, C.c_int32, C.c_int64]),
+    ("ft_sg_set_mesh_weights", C.c_int32, [C.c_void_p, C.c_int32, c_double_p, C.c_int32]),
+    ("ft_debug_morph", C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), c_double_p]),
+]
+MORPH_FIELDS = ("device_commits", "device_meshes", "host_meshes", "resident_bytes")
+
 
 # Moving lights (include/functracer_hip.h): new values for an existing light, committed without a flatten or a BVH build.
 LIGHT_SIGNATURES = [

@@ -2,6 +2,8 @@
 // builder, options, commit and HBM residency of the flattened scene, and the frame's way out of HBM.  The frame driver is ft_frame.cpp,
 // the features over it ft_progressive.cpp and ft_passes.cpp, the test entry points ft_debug.cpp.
 // Reference citations are relative to FuncTracer/ of the reference (antonburger/FuncTracer).
+#include <map>
+
 #include "ft_context.h"
 #include "ft_ls_topology.h"
 #include "ft_refit_cost.h"
@@ -152,7 +154,7 @@ void ft_destroy(ft_context* c) {
         for (DeviceBuf& b : c->d_acc) b.release();
         for (DeviceBuf* b : {&c->d_out, &c->d_out8, &c->d_out_index, &c->d_pixels, &c->d_jitter, &c->d_wave_counts, &c->d_dbg_in, &c->d_dbg_out}) b->release();
         for (auto& f : c->slots) f.release();
-        c->prog.release(); c->aov.release(); c->denoise.release(); c->temporal.release(); c->refit.release(); c->lightspace.release();   // what the features own
+        c->prog.release(); c->aov.release(); c->denoise.release(); c->temporal.release(); c->refit.release(); c->morph.release(); c->lightspace.release();   // what the features own
         if (c->classified) (void)hipEventDestroy(c->classified);
         for (hipEvent_t& e : c->acc_free) if (e) { (void)hipEventDestroy(e); e = nullptr; }
         if (c->side) (void)hipStreamDestroy(c->side);
@@ -169,7 +171,7 @@ const char* ft_last_error(const ft_context* c) { return c ? c->err.c_str() : "nu
 // kPowerOfTwo says so).  It goes into an Options member of every device of the context, or into device 0's scene graph: the peers
 // receive the scene flattened on device 0.  kCommit / kLevelHint / kZeroFill: a change invalidates the committed scene, the staged
 // level hint, the zero-fill signatures.  kOrZero: 0 is valid beside [lo, hi].  kClassified: setting it drops what the frame slots keep of their last classification.
-enum { kFlag = 1, kPowerOfTwo = 2, kCommit = 4, kLevelHint = 8, kZeroFill = 16, kOrZero = 32, kClassified = 64 };
+enum { kFlag = 1, kPowerOfTwo = 2, kCommit = 4, kLevelHint = 8, kZeroFill = 16, kOrZero = 32, kClassified = 64, kOneElseZero = 128 };   // kOneElseZero: 1 is 1, any other value 0
 struct OptionSpec {
     const char* key;
     int64_t lo, hi;
@@ -205,6 +207,8 @@ const OptionSpec kOptions[] = {
     {"deform_light_space", 0, 1, &Options::deform_light_space, nullptr, kFlag},
     // read by ft_scene_commit_lights and ft_scene_commit_deformed alone, as the ones above (any value other than 0 means 1)
     {"light_space_retree", 0, 1, &Options::light_space_retree, nullptr, kFlag},
+    // read by ft_scene_commit_deformed alone, as the ones above (the default is 1, and any other value means 0)
+    {"morph_on_device", 0, 1, &Options::morph_on_device, nullptr, kOneElseZero},
     // read by ft_scene_commit_moved alone, as the ones above (any value other than 0 means 1)
     {"moved_in_place", 0, 1, &Options::moved_in_place, nullptr, kFlag},
     {"csg_mesh_capacity", 1, 255, nullptr, [](fth::SceneGraph& g, int64_t v) { g.csg_mesh_capacity = (int32_t)v; }, kCommit},
@@ -220,6 +224,7 @@ int32_t ft_set_option(ft_context* c, const char* key, int64_t value) {
     for (const OptionSpec& o : kOptions) {
         if (std::strcmp(key, o.key)) continue;
         if (o.rules & kFlag) value = value != 0;
+        else if (o.rules & kOneElseZero) value = value == 1;
         else if (!((o.rules & kOrZero) && value == 0) && (value < o.lo || value > o.hi || ((o.rules & kPowerOfTwo) && (value & (value - 1))))) return FT_ERR_INVALID;
         if (o.to_graph) { o.to_graph(c->graph, value); c->committed = false; c->options_pending = true; return FT_OK; }
         for (ft_context* d : devices(c)) {
@@ -282,8 +287,74 @@ int32_t ft_sg_set_mesh_triangles(ft_context* c, ft_node node, const double* tris
     fth::GraphNode& n = c->graph.nodes[node];
     if (n_tris < 0 || (uint64_t)n_tris != n.tris.size() / 9) { c->err = "ft_sg_set_mesh_triangles: the triangle count differs from the node's"; return FT_ERR_INVALID; }
     n.tris.assign(tris, tris + 9 * n_tris);
+    n.by_weights = false; n.tris_stale = false;                     // explicit vertices; base and deltas stay for a later ft_sg_set_mesh_weights
     n.deformed = true;
     c->committed = false;
+    return FT_OK;
+}
+// Morph targets: the base is the node's vertices as they stand, the targets are kept as deltas from it.  Not a structural
+// change and no edit: the vertices stay what they are.
+static_assert(ftk::kMaxMorphTargets == FT_MAX_MORPH_TARGETS, "ftk::MorphBlend carries FT_MAX_MORPH_TARGETS weights");
+static void drop_resident_targets(ft_context* c, ft_node node) {
+    if (c->host_only) return;
+    for (ft_context* d : devices(c)) {
+        auto& held = d->morph.meshes;
+        for (size_t k = 0; k < held.size(); ++k) {
+            if (held[k].node != node) continue;
+            (void)hipSetDevice(d->device);
+            held[k].d.release();
+            held.erase(held.begin() + (long)k);
+            break;
+        }
+    }
+    (void)hipSetDevice(c->device);
+}
+int32_t ft_sg_set_mesh_targets(ft_context* c, ft_node node, const double* targets, int32_t n_targets, int64_t n_tris) {
+    if (!c) return FT_ERR_INVALID;
+    if (!c->graph.valid(node) || c->graph.nodes[node].kind != fth::GraphNode::Mesh) { c->err = "ft_sg_set_mesh_targets: not a bspMesh node"; return FT_ERR_INVALID; }
+    fth::GraphNode& n = c->graph.nodes[node];
+    if (n_tris < 0 || (uint64_t)n_tris != n.tris.size() / 9) { c->err = "ft_sg_set_mesh_targets: the triangle count differs from the node's"; return FT_ERR_INVALID; }
+    if (n_targets < 0 || n_targets > FT_MAX_MORPH_TARGETS) { c->err = "ft_sg_set_mesh_targets: the target count is outside 0 .. FT_MAX_MORPH_TARGETS"; return FT_ERR_INVALID; }
+    if (n_targets > 0 && !targets) { c->err = "ft_sg_set_mesh_targets: no targets"; return FT_ERR_INVALID; }
+    const std::vector<double>& B = n.vertices();                    // (blended first where weights describe them: they are explicit from here on)
+    n.by_weights = false; n.tris_stale = false;
+    n.weights.clear();
+    n.n_targets = n_targets;
+    n.targets_serial = ++c->morph.serials;
+    if (n_targets == 0) {
+        std::vector<double>().swap(n.base); std::vector<double>().swap(n.deltas);
+        drop_resident_targets(c, node);
+        return FT_OK;
+    }
+    const size_t count = B.size();
+    n.base = B;
+    n.deltas.resize((size_t)n_targets * count);
+    for (int32_t k = 0; k < n_targets; ++k) for (size_t i = 0; i < count; ++i) n.deltas[(size_t)k * count + i] = targets[(size_t)k * count + i] - B[i];
+    return FT_OK;
+}
+int32_t ft_sg_set_mesh_weights(ft_context* c, ft_node node, const double* weights, int32_t n_weights) {
+    if (!c) return FT_ERR_INVALID;
+    if (!c->graph.valid(node) || c->graph.nodes[node].kind != fth::GraphNode::Mesh) { c->err = "ft_sg_set_mesh_weights: not a bspMesh node"; return FT_ERR_INVALID; }
+    fth::GraphNode& n = c->graph.nodes[node];
+    if (n.n_targets == 0) { c->err = "ft_sg_set_mesh_weights: the node has no targets (ft_sg_set_mesh_targets)"; return FT_ERR_INVALID; }
+    if (n_weights != n.n_targets) { c->err = "ft_sg_set_mesh_weights: the weight count differs from the node's target count"; return FT_ERR_INVALID; }
+    if (!weights) { c->err = "ft_sg_set_mesh_weights: no weights"; return FT_ERR_INVALID; }
+    for (int32_t k = 0; k < n_weights; ++k) if (!std::isfinite(weights[k])) { c->err = "ft_sg_set_mesh_weights: a weight is not finite"; return FT_ERR_INVALID; }
+    n.weights.assign(weights, weights + n_weights);
+    n.by_weights = true; n.tris_stale = true;
+    n.deformed = true;
+    c->committed = false;
+    return FT_OK;
+}
+int32_t ft_debug_morph(ft_context* c, ft_node node, int64_t counts[4], double scan[8]) {
+    if (!c || !counts || !scan) return FT_ERR_INVALID;
+    if (!c->graph.valid(node) || c->graph.nodes[node].kind != fth::GraphNode::Mesh) { c->err = "ft_debug_morph: not a bspMesh node"; return FT_ERR_INVALID; }
+    const ft_context::Morph& M = c->morph;
+    for (int k = 0; k < 3; ++k) counts[k] = M.counts[k];
+    counts[3] = 0;
+    for (const ft_context::Morph::Resident& r : M.meshes) if (r.node == node) counts[3] = (int64_t)r.used;
+    for (int k = 0; k < 8; ++k) scan[k] = 0.0;
+    for (const ft_context::Morph::Used& u : M.last) if (u.node == node) for (int k = 0; k < 8; ++k) scan[k] = u.scan[k];
     return FT_OK;
 }
 ft_node ft_sg_material(ft_context* c, const ft_material* m, ft_node child) {
@@ -329,6 +400,16 @@ int32_t ft_scene_clear(ft_context* c) {
     progressive_close(c);
     temporal_close(c);
     c->graph.nodes.clear(); c->graph.lights.clear(); c->graph.root = -1; c->committed = false; c->restructured = true;
+    if (!c->host_only) {                                            // the morph targets of nodes that are gone (no frame reads them)
+        for (ft_context* d : devices(c)) {
+            if (d->morph.meshes.empty()) continue;
+            (void)hipSetDevice(d->device);
+            for (ft_context::Morph::Resident& r : d->morph.meshes) r.d.release();
+            d->morph.meshes.clear();
+        }
+        (void)hipSetDevice(c->device);
+    }
+    c->morph.last.clear();
     return FT_OK;
 }
 int32_t ft_scene_set_objects(ft_context* c, ft_node root) {
@@ -609,7 +690,14 @@ int32_t commit_scene(ft_context* c) {
 
 // ------------------------------------------------------------------------------------------ refit (ft_scene_commit_deformed)
 // One edited mesh of the held scene: its index, its builder node and what one pass over the new vertices gave.
-struct DeformedMesh { uint32_t mesh; int32_t node; fth::MeshScan scan; };
+// at: where its new vertices lie in ft_context::Refit::d_verts (doubles; even, so that every mesh starts on 16 bytes); on_device: weights
+// describe them and k_morph_blend writes them there on every device - the host holds no copy of them.
+struct DeformedMesh { uint32_t mesh; int32_t node; fth::MeshScan scan; size_t at = 0; bool on_device = false; };
+static size_t verts_doubles(const fth::SceneGraph& g, const std::vector<DeformedMesh>& edits) {
+    size_t n = 0;
+    for (const DeformedMesh& e : edits) n = std::max(n, e.at + g.nodes[(size_t)e.node].tris.size());
+    return n;
+}
 
 using ftk::refit::refit_ranges;                                    // one mesh's ranges as the refit kernels take them (ft_refit_cost.h)
 
@@ -710,6 +798,93 @@ static int32_t snapshot_records(ft_context* c, const fth::FlatScene& f, const st
     return FT_OK;
 }
 
+// Morph targets on one device of the context: the vertices of every `on_device` edit blended into d_verts at the edit's
+// place, from base and deltas resident in this device's HBM - uploaded here when the device holds none of the node's current
+// ft_sg_set_mesh_targets call (ms[0] += that upload).  Only d_verts is written, which no frame reads, so queued frames go on.  lead:
+// the context's first device, which also scans every blended mesh, bit for bit fth::scan_mesh, into the edit (ms[1] += blend, scan
+// and readback).  The others' blends are left queued on their streams: their refit_device follows on the same stream.
+static int32_t morph_device(ft_context* c, const fth::SceneGraph& g, std::vector<DeformedMesh>& edits, double ms[2], bool lead) {
+    using clock = std::chrono::steady_clock;
+    auto since = [](clock::time_point t0) { return std::chrono::duration<double, std::milli>(clock::now() - t0).count(); };
+    int32_t rc;
+    FT_HIP(c, hipSetDevice(c->device));
+    ft_context::Morph& M = c->morph;
+    const auto t0 = clock::now();
+    if ((rc = ensure(c, c->refit.d_verts, verts_doubles(g, edits) * 8)) != FT_OK) return rc;
+    bool uploaded = false;
+    size_t blocks = 1, n_scans = 0;
+    for (const DeformedMesh& e : edits) {
+        if (!e.on_device) continue;
+        const fth::GraphNode& n = g.nodes[(size_t)e.node];
+        ft_context::Morph::Resident* r = nullptr;
+        for (ft_context::Morph::Resident& h : M.meshes) if (h.node == e.node) r = &h;
+        if (!r) { M.meshes.push_back({e.node, 0, 0, 0, DeviceBuf{}}); r = &M.meshes.back(); }
+        if (r->serial != n.targets_serial) {
+            const size_t count = n.base.size(), stride = count + (count & 1);
+            if ((rc = ensure(c, r->d, (size_t)(n.n_targets + 1) * stride * 8)) != FT_OK) return rc;
+            if (count) {
+                FT_HIP(c, hipMemcpyAsync(r->d.p, n.base.data(), count * 8, hipMemcpyHostToDevice, c->stream));
+                for (int32_t k = 0; k < n.n_targets; ++k)
+                    FT_HIP(c, hipMemcpyAsync(r->d.as<double>() + (size_t)(k + 1) * stride, n.deltas.data() + (size_t)k * count, count * 8, hipMemcpyHostToDevice, c->stream));
+            }
+            r->serial = n.targets_serial; r->stride = stride; r->used = (size_t)(n.n_targets + 1) * count * 8;
+            uploaded = true;
+        }
+        blocks = std::max(blocks, (size_t)ftk::morph_blocks((uint32_t)(n.tris.size() / 9)));
+        ++n_scans;
+    }
+    if (uploaded) FT_HIP(c, hipStreamSynchronize(c->stream));
+    ms[0] += since(t0);
+    const auto t1 = clock::now();
+    if (lead && ((rc = ensure(c, M.d_partials, blocks * sizeof(ftk::MorphPartial))) != FT_OK || (rc = ensure(c, M.d_out, n_scans * sizeof(ftk::MorphScanOut))) != FT_OK)) return rc;
+    std::vector<ftk::MorphScanOut> out(n_scans);
+    size_t k_scan = 0;
+    for (const DeformedMesh& e : edits) {
+        if (!e.on_device) continue;
+        const fth::GraphNode& n = g.nodes[(size_t)e.node];
+        const ft_context::Morph::Resident* r = nullptr;
+        for (const ft_context::Morph::Resident& h : M.meshes) if (h.node == e.node) r = &h;
+        ftk::MorphBlend a{};
+        a.resident = r->d.as<double>(); a.out = c->refit.d_verts.as<double>() + e.at; a.count = n.tris.size(); a.stride = r->stride; a.n_targets = n.n_targets;
+        for (int32_t k = 0; k < n.n_targets; ++k) a.w[k] = n.weights[(size_t)k];
+        ftk::morph_blend(c->stream, a);
+        // (one scan after the other on the stream: they share the partials)
+        if (lead) ftk::morph_scan(c->stream, a.out, (uint32_t)(a.count / 9), M.d_partials.as<ftk::MorphPartial>(), M.d_out.as<ftk::MorphScanOut>() + k_scan++);
+    }
+    FT_HIP(c, hipGetLastError());
+    if (lead && n_scans) {
+        FT_HIP(c, hipMemcpyAsync(out.data(), M.d_out.p, n_scans * sizeof(ftk::MorphScanOut), hipMemcpyDeviceToHost, c->stream));
+        FT_HIP(c, hipStreamSynchronize(c->stream));
+        k_scan = 0;
+        for (DeformedMesh& e : edits) {
+            if (!e.on_device) continue;
+            const ftk::MorphScanOut& o = out[k_scan++];
+            for (int k = 0; k < 6; ++k) e.scan.bounds[k] = o.bounds[k];
+            e.scan.extent = o.extent; e.scan.finite = o.finite != 0.0;
+        }
+        ms[1] += since(t1);
+    }
+    return FT_OK;
+}
+// fth::ls_pair_extent(vertices = true) of a blended mesh about `centre`, reduced on the context's first device from the vertices
+// morph_device left in d_verts: a maximum of non-negative finite values, so the order cannot show.  ms[1] += kernels and readback.
+static int32_t morph_pair_extent(ft_context* c, const fth::SceneGraph& g, const DeformedMesh& e, const double centre[3], double* R, double ms[2]) {
+    const auto t0 = std::chrono::steady_clock::now();
+    int32_t rc;
+    FT_HIP(c, hipSetDevice(c->device));
+    ft_context::Morph& M = c->morph;
+    const uint32_t n = (uint32_t)(g.nodes[(size_t)e.node].tris.size() / 9);
+    if ((rc = ensure(c, M.d_partials, (size_t)ftk::morph_blocks(n) * 8)) != FT_OK) return rc;   // (the scan's partials hold more: nothing is allocated here)
+    double* partials = M.d_partials.as<double>();
+    double* out = M.d_out.as<double>();
+    ftk::morph_extent(c->stream, c->refit.d_verts.as<double>() + e.at, n, centre, partials, out);
+    FT_HIP(c, hipGetLastError());
+    FT_HIP(c, hipMemcpyAsync(R, out, 8, hipMemcpyDeviceToHost, c->stream));
+    FT_HIP(c, hipStreamSynchronize(c->stream));
+    ms[1] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return FT_OK;
+}
+
 // What the context's first device decides for the others ("refit_rebuild_percent"): per edit whether its tree is rebuilt in place, and the
 // tallest tree the rebuilds made.
 struct RebuildPlan { std::vector<uint8_t> rebuild; uint32_t tallest = 0; };
@@ -737,14 +912,11 @@ static int32_t refit_device(ft_context* c, const fth::FlatScene& f, const fth::S
         FT_HIP(c, hipMemsetAsync(R.d_parent_leaf.p, 0xFF, R.d_parent_leaf.bytes, c->stream));
     }
     const ftk::RefitArrays A = refit_arrays(c);
-    size_t n_verts = 0;
-    for (const DeformedMesh& e : edits) n_verts += g.nodes[(size_t)e.node].tris.size();
-    if ((rc = ensure(c, R.d_verts, n_verts * 8)) != FT_OK) return rc;
-    size_t at = 0;
+    if ((rc = ensure(c, R.d_verts, verts_doubles(g, edits) * 8)) != FT_OK) return rc;   // (no larger than what a blend has already written into)
     for (const DeformedMesh& e : edits) {
-        const std::vector<double>& v = g.nodes[(size_t)e.node].tris;
-        if (!v.empty()) FT_HIP(c, hipMemcpyAsync(R.d_verts.as<double>() + at, v.data(), v.size() * 8, hipMemcpyHostToDevice, c->stream));
-        at += v.size();
+        if (e.on_device) continue;                                  // k_morph_blend has filled them
+        const std::vector<double>& v = g.nodes[(size_t)e.node].vertices();
+        if (!v.empty()) FT_HIP(c, hipMemcpyAsync(R.d_verts.as<double>() + e.at, v.data(), v.size() * 8, hipMemcpyHostToDevice, c->stream));
     }
     // "temporal_follow_deformed": what the open accumulation's history saw of each edited mesh, before the first refit since the last
     // accumulate overwrites it (later ones keep it, so several deformations between two accumulates compose)
@@ -761,12 +933,10 @@ static int32_t refit_device(ft_context* c, const fth::FlatScene& f, const fth::S
         for (uint32_t k = 0; k < (uint32_t)f.meshes.size(); ++k) if (refittable(f, k)) ftk::refit_parents(c->stream, A, refit_ranges(f, k, 0.0));
         R.ready = true;
     }
-    at = 0;
     for (const DeformedMesh& e : edits) {
         const ftk::RefitMesh m = refit_ranges(f, e.mesh, 1e-7 * e.scan.extent + 1e-300);
         if (m.node_count) FT_HIP(c, hipMemsetAsync(R.d_arrived.as<uint32_t>() + m.node_first, 0, (size_t)m.node_count * 4, c->stream));
-        ftk::refit_mesh(c->stream, A, m, R.d_verts.as<double>() + at);
-        at += 9 * (size_t)m.n;
+        ftk::refit_mesh(c->stream, A, m, R.d_verts.as<double>() + e.at);
     }
     FT_HIP(c, hipGetLastError());
     FT_HIP(c, hipStreamSynchronize(c->stream));
@@ -1450,20 +1620,53 @@ int32_t ft_scene_commit_deformed(ft_context* c) {
     fth::FlatScene& f = c->flat;
     // Host: one pass over every edited mesh - bounds, extent, finiteness - before anything is changed or uploaded.
     std::vector<DeformedMesh> edits;
+    size_t verts_at = 0, n_on_device = 0;
+    // ft_debug_morph counts[2]: the meshes this call - whichever way it ends - has the host blend (GraphNode::vertices)
+    struct HostBlends {
+        ft_context* c; uint64_t before;
+        static uint64_t total(const ft_context* c) { uint64_t n = 0; for (const fth::GraphNode& g : c->graph.nodes) n += g.host_blends; return n; }
+        explicit HostBlends(ft_context* ctx) : c(ctx), before(total(ctx)) {}
+        ~HostBlends() { c->morph.counts[2] = (int64_t)(total(c) - before); }
+    } host_blends(c);
+    auto refuse = [c](bool depth) {
+        c->err = depth ? "ft_scene_commit_deformed: an edited mesh has depth above 0 - its clipped BSP depends on the positions (ft_scene_commit)"
+                       : "ft_scene_commit_deformed: an edited mesh holds a non-finite coordinate (ft_scene_commit)";
+        c->committed = true;                                         // the old commit stays in HBM and stays renderable
+        return (int32_t)FT_ERR_UNSUPPORTED;
+    };
     for (uint32_t m = 0; m < (uint32_t)f.meshes.size(); ++m) {
         const int32_t id = f.mesh_node[m];
         if (id < 0 || !c->graph.valid(id) || !c->graph.nodes[(size_t)id].deformed) continue;
         const fth::GraphNode& n = c->graph.nodes[(size_t)id];
         const bool refuse_depth = n.depth > 0 && !c->graph.mesh_unclipped_bvh;
-        const fth::MeshScan scan = refuse_depth ? fth::MeshScan{} : fth::scan_mesh(n.tris.data(), (int64_t)(n.tris.size() / 9));
-        if (refuse_depth || !scan.finite || f.meshes[m].root >= 0) {
-            c->err = refuse_depth || f.meshes[m].root >= 0 ? "ft_scene_commit_deformed: an edited mesh has depth above 0 - its clipped BSP depends on the positions (ft_scene_commit)"
-                                                            : "ft_scene_commit_deformed: an edited mesh holds a non-finite coordinate (ft_scene_commit)";
-            c->committed = true;                                     // the old commit stays in HBM and stays renderable
-            return FT_ERR_UNSUPPORTED;
-        }
-        edits.push_back(DeformedMesh{m, id, scan});
+        // "morph_on_device" (DESIGN.md 16.4): weights describe the vertices - the device blends and scans them, below, once every
+        // refusal that needs no vertices has been looked at (the positions 3 x triangle + corner are 32 bits wide there)
+        const bool on_device = n.by_weights && !c->host_only && c->opt.morph_on_device == 1 && n.tris.size() / 9 <= 0x55555555u;
+        const fth::MeshScan scan = refuse_depth || on_device ? fth::MeshScan{{0, 0, 0, 0, 0, 0}, 0.0, true} : fth::scan_mesh(n.vertices().data(), (int64_t)(n.tris.size() / 9));
+        if (refuse_depth || !scan.finite || f.meshes[m].root >= 0) return refuse(refuse_depth || f.meshes[m].root >= 0);
+        DeformedMesh e{m, id, scan};
+        e.at = verts_at; e.on_device = on_device;
+        verts_at += n.tris.size() + (n.tris.size() & 1);
+        n_on_device += on_device ? 1 : 0;
+        edits.push_back(e);
     }
+    double morph_ms[2] = {0.0, 0.0};                                // uploads, kernels with their readbacks
+    ft_context::Morph& M = c->morph;
+    M.counts[1] = (int64_t)n_on_device;
+    if (n_on_device) {
+        ++M.counts[0];
+        for (ft_context* d : devices(c)) {
+            const int32_t mrc = morph_device(d, c->graph, edits, morph_ms, d == c);
+            if (mrc != FT_OK) { if (d != c) c->err = d->err; return mrc; }   // (only d_verts has been written: the old commit stands)
+        }
+    }
+    M.last.clear();
+    for (const DeformedMesh& e : edits) {
+        ft_context::Morph::Used u{e.node, {0, 0, 0, 0, 0, 0, e.scan.extent, e.on_device ? 1.0 : 0.0}};
+        for (int k = 0; k < 6; ++k) u.scan[k] = e.scan.bounds[k];
+        M.last.push_back(u);
+    }
+    for (const DeformedMesh& e : edits) if (e.on_device && !e.scan.finite) return refuse(false);
     if (c->host_only) {                                             // the same rules; the commit itself is the full one
         progressive_close(c);
         return commit_scene(c);
@@ -1495,13 +1698,27 @@ int32_t ft_scene_commit_deformed(ft_context* c) {
     size_t n_regrid = 0;
     bool touched = false;
     const bool grids = c->graph.light_space_shadows == 2;
+    std::map<uint32_t, double> extent_of;
     if (keep_ls) {
         for (ft_context::LightSpace::Pair& P : T.pairs) {
             if (f.leaves[P.leaf].ls_pairs == ~0u || P.mesh >= edited.size() || !edited[P.mesh]) continue;   // (stripped before: stays stripped)
             const DeformedMesh& e = *edited[P.mesh];
             for (int q = 0; q < 3; ++q) P.c[q] = 0.5 * (e.scan.bounds[q] + e.scan.bounds[3 + q]);
-            const std::vector<double>& v = c->graph.nodes[(size_t)e.node].tris;
-            P.R = fth::ls_pair_extent(v.data(), v.size() / 9, true, P.c);
+            if (e.on_device) {                                      // the vertices are in HBM alone: reduced there (once per mesh - every pair of it has this centre)
+                if (!(extent_of.count(e.mesh))) {
+                    double R = 0.0;
+                    if ((rc = morph_pair_extent(c, c->graph, e, P.c, &R, morph_ms)) != FT_OK) {   // (a HIP error; the held scene is half rewritten: ft_scene_commit)
+                        for (ft_context* d : devices(c)) d->committed = false;
+                        c->holds_commit = false;
+                        return rc;
+                    }
+                    extent_of[e.mesh] = R;
+                }
+                P.R = extent_of[e.mesh];
+            } else {
+                const std::vector<double>& v = c->graph.nodes[(size_t)e.node].vertices();
+                P.R = fth::ls_pair_extent(v.data(), v.size() / 9, true, P.c);
+            }
             P.deformed = true;
             touched = true;
         }
@@ -1515,8 +1732,8 @@ int32_t ft_scene_commit_deformed(ft_context* c) {
     const double tallest = c->commit_ms[3];
     for (double& v : c->commit_ms) v = 0.0;
     c->commit_ms[3] = tallest;
-    c->commit_ms[0] = std::chrono::duration<double, std::milli>(clock::now() - t0).count();
-    double ms[2] = {0.0, 0.0};
+    c->commit_ms[0] = std::chrono::duration<double, std::milli>(clock::now() - t0).count() - morph_ms[0] - morph_ms[1];
+    double ms[2] = {morph_ms[0], morph_ms[1]};
     RebuildPlan plan;
     for (ft_context* d : devices(c)) {                              // every device refits its own copy
         if ((rc = refit_device(d, f, c->graph, edits, ms, d == c, plan)) != FT_OK) { if (d != c) c->err = d->err; break; }

@@ -100,6 +100,7 @@ struct Options {
     int64_t light_space_retree = 0;     // ft_scene_commit_lights and ft_scene_commit_deformed build the topology of the light-space trees they would refit again on the device (not a commit-time option)
     int64_t moved_in_place = 0;         // ft_scene_commit_moved uploads the new poses and refits the light-space pairs instead of committing the scene again (not a commit-time option)
     int64_t deform_light_space = 0;     // ft_scene_commit_deformed refits the light-space trees and builds the grids of the meshes it edits again instead of stripping them (not a commit-time option)
+    int64_t morph_on_device = 1;        // ft_scene_commit_deformed blends and scans weight-driven meshes on the device (not a commit-time option; any value but 1 means 0)
     int64_t temporal_follow_deformed = 0;   // ft_scene_commit_deformed keeps a mesh's records as the history saw them and ft_temporal_accumulate follows them
     int64_t primary_mesh_kernel = 1;   // k_primary_mesh for the frames that qualify (ft_context::mesh_kernel_scene, queue_chunks); 0: k_primary everywhere (A/B)
     int64_t edge_cull = 1;          // candidate-list and shadow-grid entries are also tested against their triangle's projected edges (ft_edges.h); 0: the rectangles alone (A/B)
@@ -306,6 +307,19 @@ struct ft_context {
         bool ready = false;
         void release() { for (DeviceBuf* b : {&d_verts, &d_parent_node, &d_parent_leaf, &d_arrived, &d_leaf_boxes, &d_wide_node, &d_cost}) b->release(); ready = false; }
     } refit;
+    // Morph targets.  On every device: per mesh node the base and deltas in HBM as ftk::MorphBlend reads them (`stride`
+    // doubles apart), of the ft_sg_set_mesh_targets call `serial` names; the scan's partials and result.  On the context's first device:
+    // ft_debug_morph's counters, and what the last ft_scene_commit_deformed used as every edited mesh's scan (scan[7]: from the device).
+    struct Morph {
+        struct Resident { int32_t node; uint64_t serial; uint64_t stride; size_t used; DeviceBuf d; };
+        std::vector<Resident> meshes;
+        DeviceBuf d_partials, d_out;
+        int64_t counts[3] = {0, 0, 0};
+        struct Used { int32_t node; double scan[8]; };
+        std::vector<Used> last;
+        uint64_t serials = 0;       // the last value a GraphNode::targets_serial was given
+        void release() { for (Resident& r : meshes) r.d.release(); meshes.clear(); d_partials.release(); d_out.release(); }
+    } morph;
     // ft_scene_commit_lights.  On the context's first device, derived from `flat` by the first call after a full commit
     // (`ready`) and kept until the next one: per (leaf, directional light) pair that had a tree then its record as that commit wrote it
     // (rec0) and the light's direction then (v0), the tree's root, what of the record does not depend on the direction (centre, R; the

@@ -251,6 +251,23 @@ void refit_mesh(hipStream_t stream, const RefitArrays& A, const RefitMesh& m, co
 inline uint32_t refit_cost_blocks(const RefitMesh& m) { return (m.node_count + 255u) / 256u; }
 void refit_cost(hipStream_t stream, const RefitArrays& A, const RefitMesh& m, double* partials, double* cost);
 
+// Morph targets (ft_morph.hip, ft_sg_set_mesh_weights + ft_scene_commit_deformed).  MorphBlend: resident = the mesh's
+// base, then its n_targets deltas, `stride` doubles apart (count = 9 x triangles of them used; stride even and resident and out 16-byte
+// aligned); out[i] = blend(base, deltas, w)[i] in fth::morph_blend's arithmetic - what refit_mesh then reads as `verts`.
+constexpr int kMaxMorphTargets = 16;                               // FT_MAX_MORPH_TARGETS (ft_capi.cpp asserts it)
+struct MorphBlend { const double* resident; double* out; uint64_t count, stride; int32_t n_targets; double w[kMaxMorphTargets]; };
+void morph_blend(hipStream_t stream, const MorphBlend& a);
+// fth::scan_mesh over n triangles in HBM, bit for bit (a zero bound has the sign of the first zero in list order): out->bounds, extent,
+// finite (1.0 / 0.0).  partials: morph_blocks(n) records of scratch, one per block of 256 triangles in a fixed slot, folded by a second launch.
+struct MorphPartial { double b[6]; double extent; uint32_t at[6]; uint32_t finite, pad; };
+struct MorphScanOut { double bounds[6]; double extent; double finite; };
+struct MorphCentre { double c[3]; };
+inline uint32_t morph_blocks(uint32_t n) { return n / 256u + (n % 256u ? 1u : 0u); }
+void morph_scan(hipStream_t stream, const double* verts, uint32_t n, MorphPartial* partials, MorphScanOut* out);
+// fth::ls_pair_extent(verts, n, true, c) over vertices in HBM: *out (in HBM) = the largest L1 distance of a vertex from c, in that
+// function's arithmetic; partials: morph_blocks(n) doubles of scratch.
+void morph_extent(hipStream_t stream, const double* verts, uint32_t n, const double c[3], double* partials, double* out);
+
 // Refit of a light-space shadow tree whose light turned (ft_lightspace.hip, ft_scene_commit_lights).  LsFrame: the pair's new frame and
 // centre as its record holds them (ft_flat.h, kLsPairDoubles) and the builder's inflation, 1e-7 * R + 1e-30.  One call per level of the
 // tree, deepest first: order[0 .. count) are that level's 4-wide nodes (indices into ls_nodes), whose child boxes are written again -

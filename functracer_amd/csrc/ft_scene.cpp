@@ -365,7 +365,8 @@ struct Flattener {
                 break;
             }
             case GraphNode::Mesh: {
-                uint32_t mesh = mesh_for(id, n.tris.data(), (int64_t)(n.tris.size() / 9), g.mesh_unclipped_bvh ? 0 : n.depth);
+                // (with a held scene the meshes are taken as they are: no vertex is read, and none is blended for it)
+                uint32_t mesh = mesh_for(id, held ? nullptr : n.vertices().data(), (int64_t)(n.tris.size() / 9), g.mesh_unclipped_bvh ? 0 : n.depth);
                 ItemMark im = begin_item(in_csg);
                 if (status == FT_OK) {
                     if (in_csg) out.mesh_under_csg = true;
@@ -447,6 +448,22 @@ struct Flattener {
 };
 
 } // namespace
+
+void morph_blend(const double* base, const double* deltas, const double* w, int32_t n_targets, size_t count, double* out) {
+    for (size_t i = 0; i < count; ++i) {
+        double acc = base[i];
+        for (int32_t k = 0; k < n_targets; ++k) { const double p = w[k] * deltas[(size_t)k * count + i]; acc = acc + p; }
+        out[i] = acc;
+    }
+}
+const std::vector<double>& GraphNode::vertices() const {
+    if (by_weights && tris_stale) {
+        morph_blend(base.data(), deltas.data(), weights.data(), n_targets, tris.size(), tris.data());
+        tris_stale = false;
+        ++host_blends;
+    }
+    return tris;
+}
 
 MeshScan scan_mesh(const double* tris, int64_t n) {
     const double inf = std::numeric_limits<double>::infinity();

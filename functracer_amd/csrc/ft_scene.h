@@ -16,8 +16,20 @@ struct GraphNode {
     int32_t prim = 0;                 // ft_primitive_kind
     double tri[9] = {0};              // TriangleP
     int32_t depth = 0;                // Mesh: BspMesh.bspMesh depth
-    std::vector<double> tris;         // Mesh: n x 9 (a,b,c)
-    bool deformed = false;            // Mesh: the vertices were replaced (ft_sg_set_mesh_triangles) since the last successful commit
+    // Mesh: n x 9 (a,b,c).  Stale (the right size, old contents) while `tris_stale`: every reader of a mesh's vertices asks vertices().
+    mutable std::vector<double> tris;
+    bool deformed = false;            // Mesh: the vertices were replaced (ft_sg_set_mesh_triangles / ft_sg_set_mesh_weights) since the last successful commit
+    // Mesh: morph targets (ft_sg_set_mesh_targets).  base: B, n x 9; deltas: K x n x 9, D_k = T_k - B; weights: K once
+    // ft_sg_set_mesh_weights was called; targets_serial: another value after every ft_sg_set_mesh_targets (what a device holds of base
+    // and deltas is that call's).  by_weights: the vertices are blend(B, D, w) and not what ft_sg_set_mesh_triangles gave.
+    std::vector<double> base, deltas, weights;
+    int32_t n_targets = 0;
+    uint64_t targets_serial = 0;
+    bool by_weights = false;
+    mutable bool tris_stale = false;  // by_weights and `tris` has not been blended from the weights as they stand
+    mutable uint64_t host_blends = 0; // times vertices() has blended them on the host (ft_debug_morph counts[2])
+    // The vertices as they stand: `tris`, blended first where the weights describe them (morph_blend's arithmetic).
+    const std::vector<double>& vertices() const;
     std::vector<ft_transform> xf;     // Transform: one basic transform or a Composed list
     ft_material mat{};                // MaterialF
     int32_t op = 0;                   // Csg
@@ -89,6 +101,9 @@ struct FlatScene {
 // coordinate passes the builders' own test, |v| < 1e300.
 struct MeshScan { double bounds[6]; double extent; bool finite; };
 MeshScan scan_mesh(const double* tris_abc, int64_t n_tris);
+// Morph targets: out[i] = blend(base, deltas, w)[i], i < count - acc = base[i]; for k = 0 .. K-1 in order: p = w[k] * deltas[k * count + i],
+// acc = acc + p; every term evaluated, product and sum each rounded once (this unit is built with -ffp-contract=off).
+void morph_blend(const double* base, const double* deltas, const double* w, int32_t n_targets, size_t count, double* out);
 
 struct SceneGraph {
     std::vector<GraphNode> nodes;

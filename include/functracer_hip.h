@@ -200,7 +200,11 @@ const char* ft_last_error(const ft_context* ctx);
  * "temporal_follow_deformed" (0 = default; any other value means 1: ft_scene_commit_deformed keeps the triangle records of the meshes it refits as the open
  * temporal accumulation last saw them, and the next ft_temporal_accumulate takes every pixel on a changed triangle back to where that point of the triangle was -
  * "history on deforming meshes" below.  It needs no new ft_scene_commit; a host-only or multi-device context accepts it without effect, because the accumulation
- * lives on a single device; with 0 every call launches the kernels and gives the bits it gave before the option existed).  Every option reaches every device of a context.  Scene-affecting
+ * lives on a single device; with 0 every call launches the kernels and gives the bits it gave before the option existed),
+ * "morph_on_device" (1 = default; any other value means 0: ft_scene_commit_deformed blends the vertices of
+ * the meshes that ft_sg_set_mesh_weights describes on the device, from a base and deltas resident in HBM, and scans them there - "morph targets" below; with 0
+ * the host blends them and the call is the ft_sg_set_mesh_triangles path, the same bits.  It is read by ft_scene_commit_deformed alone and needs no new
+ * ft_scene_commit; a host-only context accepts it without effect).  Every option reaches every device of a context.  Scene-affecting
  * options need a new ft_scene_commit.  Any other key is refused (FT_ERR_INVALID, "unknown option"). */
 int32_t ft_set_option(ft_context* ctx, const char* key, int64_t value);
 
@@ -751,6 +755,51 @@ int32_t ft_scene_commit_moved(ft_context* ctx);
 int32_t ft_sg_set_mesh_triangles(ft_context* ctx, ft_node node, const double* tris, int64_t n_tris);
 int32_t ft_scene_commit_deformed(ft_context* ctx);
 int32_t ft_scene_tree_quality(ft_context* ctx, ft_node mesh_node, double out[4]);
+/* ---- morph targets: vertices blended on the device before the refit --------------------------- */
+/* A mesh whose poses are blends of a few key shapes needs no vertices from the host: the key shapes stay in device memory, a frame sets
+ * K weights, and ft_scene_commit_deformed makes the vertices where the refit reads them.
+ * ft_sg_set_mesh_targets(mesh, targets, n_targets, n_tris): targets = n_targets x n_tris x 9 doubles, each target laid out as
+ * ft_sg_bsp_mesh's tris (absolute positions), copied.  The base B is the node's triangles as they stand at the call (from ft_sg_bsp_mesh,
+ * the last ft_sg_set_mesh_triangles or the last ft_sg_set_mesh_weights); the library keeps B and per target the deltas D_k = T_k - B, one
+ * rounded subtraction per coordinate.  n_targets = 0 removes the targets (targets may then be null).  Not a structural change, and nothing
+ * is marked deformed: the vertices stay what they were.  FT_ERR_INVALID, with nothing changed, for a null context, an invalid handle, a
+ * node that is not a bspMesh node, an n_tris that differs from the node's count, n_targets outside 0 .. FT_MAX_MORPH_TARGETS, or null
+ * targets with n_targets > 0.
+ * ft_sg_set_mesh_weights(mesh, weights, n_weights) declares the node's vertices to be V = blend(B, D, w), per coordinate in IEEE double:
+ *     acc = B;  for k = 0 .. K-1 in order:  p = w_k * D_k (one rounded product);  acc = acc + p (one rounded sum, never fused);  V = acc
+ * with every term evaluated, zero weights included.  It marks the node as ft_sg_set_mesh_triangles does, leaves the scene uncommitted and
+ * is not structural.  FT_ERR_INVALID, with nothing changed, for a null context, an invalid handle, a node that is not a bspMesh node or
+ * has no targets, an n_weights that differs from the node's target count, null weights or a weight that is not finite.
+ * ft_sg_set_mesh_triangles on a node with targets sets explicit vertices for the next commit; base and deltas stay for a later
+ * ft_sg_set_mesh_weights.
+ * The promise: ft_sg_set_mesh_weights(node, w) followed by any commit gives every bit that ft_sg_set_mesh_triangles(node, V) followed by
+ * the same commit gives - frames, ft_stats (times aside), ft_render_aov, the ft_debug_* ray queries, ft_debug_mesh_trees - so everything
+ * said under "deforming meshes" above holds unchanged: the refusals, the open temporal accumulation, "temporal_follow_deformed",
+ * "refit_rebuild_percent", "deform_light_space", "light_space_retree", several devices.
+ * ft_scene_commit_deformed, for every edited mesh that weights describe, on a device context with "morph_on_device" = 1 (the default):
+ * uploads base and deltas to every device on first use or after a new ft_sg_set_mesh_targets ((K + 1) x n_tris x 72 bytes per device, kept
+ * until the targets change, ft_scene_clear or ft_destroy; inside ft_get_commit_times [2]); blends the vertices on every device into the buffer the
+ * refit reads; reduces bounds, extent and finiteness on the context's first device, bit for bit what the host's pass gives (a zero bound
+ * has the sign of the first zero in list order) and reads them back, one small copy; under "deform_light_space" reduces each pair's R
+ * there as well; then goes on as for ft_sg_set_mesh_triangles, uploading only the vertices of the meshes edited that way in the same call.
+ * The blend writes only that buffer, which no frame reads: a refusal (a non-finite result, bounds that change which items have bounds,
+ * depth above 0 - the last before any kernel runs) leaves the old commit renderable, as there.  With the option at 0, on a host-only
+ * context, and in every other commit (ft_scene_commit, ft_scene_commit_moved with vertices pending) the host blends V by the formula when
+ * the vertices are needed.  ft_get_commit_times: [0] host, [1] blend, scan, R and refit kernels with their readbacks, [2] uploads.
+ * ft_debug_morph(mesh, counts, scan), for tests and tools: counts[0] = ft_scene_commit_deformed calls since ft_create that blended at
+ * least one mesh on the device, counts[1] = meshes blended on the device in the last ft_scene_commit_deformed, counts[2] = meshes whose
+ * blend the host made in it, counts[3] = bytes of base and deltas resident per device for `mesh`; scan[0..5] = the bounds that call used
+ * for `mesh`, scan[6] the extent, scan[7] = 1.0 where they came from the device, else 0.0 (all 0 when the call did not edit `mesh`).
+ * FT_ERR_INVALID for a null context or pointer, an invalid handle or a node that is not a bspMesh node.
+ * What it is worth (MI355X, the 69.6 K-face mesh, nothing in flight, tools/morph_rate.py): a pose by weights
+ * takes 0.31 / 0.32 / 0.34 ms at K = 1 / 4 / 16 for the whole step (set the weights, ft_scene_commit_deformed), against 1.43 / 2.08 / 4.82 ms for a host that
+ * blends the pose in numpy and hands it to ft_sg_set_mesh_triangles; of the commit, [0] goes from 0.54 ms to under 0.01 ms, [2] from 0.14 to 0.03 ms and
+ * [1] from 0.23 to 0.29 ms (blend, scan and readback), whatever K.  With "morph_on_device" 0 the library's host blend makes [0] 0.95 / 1.35 / 5.59 ms.
+ * The first pose after ft_sg_set_mesh_targets uploads base and deltas: 0.66 / 0.86 / 4.09 ms in [2]. */
+#define FT_MAX_MORPH_TARGETS 16
+int32_t ft_sg_set_mesh_targets(ft_context* ctx, ft_node mesh, const double* targets, int32_t n_targets, int64_t n_tris);
+int32_t ft_sg_set_mesh_weights(ft_context* ctx, ft_node mesh, const double* weights, int32_t n_weights);
+int32_t ft_debug_morph(ft_context* ctx, ft_node mesh, int64_t counts[4], double scan[8]);
 /* ---- moving lights ----------------------------------------------------------------------------- */
 /* ft_scene_set_directional / _soft_directional / _positional + ft_scene_commit_lights change the lights of a committed scene without a
  * flatten, without a BVH build and without ending ft_temporal_*.
