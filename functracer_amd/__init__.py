@@ -15,7 +15,7 @@ from . import _capi
 from ._capi import (CIRCLE, CONE, CUBE, CYLINDER, EXCLUDE, INTERSECT, PLANE, SOLID_CYLINDER, SPHERE, SQUARE, SUBTRACT, UNION,
                     FtError, SceneBuilder, make_camera)
 
-__all__ = ["Context", "ls_topology", "PinnedArray", "ParsedScene", "parse_scene", "parse_scene_file", "jitter_pattern", "morph_blend", "quantise_rgba8", "write_png",
+__all__ = ["Context", "ls_topology", "PinnedArray", "ParsedScene", "parse_scene", "parse_scene_file", "jitter_pattern", "morph_blend", "skin_blend", "quantise_rgba8", "write_png",
            "parse_colour", "parse_ply", "FtError", "make_camera", "HIP_LIB", "HOST_LIB", "DEFAULT_SEED"]
 
 HIP_LIB = os.environ.get("FT_HIP_LIB") or os.path.join(_capi.LIB_DIR, "libfunctracer_hip.so")   # FT_HIP_LIB: experimental builds
@@ -74,7 +74,7 @@ def hip_lib():
         if hasattr(lib, _capi.MOVED_COMMITS_SIGNATURE[0]):          # (FT_HIP_LIB may name an older build, as above)
             fn = getattr(lib, _capi.MOVED_COMMITS_SIGNATURE[0])
             fn.restype, fn.argtypes = _capi.MOVED_COMMITS_SIGNATURE[1:]
-        for name, res, args in _capi.POSE_QUEUE_SIGNATURES + _capi.MORPH_SIGNATURES:
+        for name, res, args in _capi.POSE_QUEUE_SIGNATURES + _capi.MORPH_SIGNATURES + _capi.SKIN_SIGNATURES:
             if hasattr(lib, name):                                  # (FT_HIP_LIB may name an older build, as above)
                 fn = getattr(lib, name)
                 fn.restype, fn.argtypes = res, args
@@ -181,6 +181,32 @@ def morph_blend(base, targets, w):
         p = w[k] * d
         acc = acc + p
     return acc
+
+
+def skin_blend(shape, index, weight, bones):
+    """The vertices ft_sg_set_mesh_bones declares (include/functracer_hip.h, "skinning"), evaluated in numpy with one elementwise IEEE
+    double operation per step: per corner and influence j in order t_i = ((M[i][0] * x + M[i][1] * y) + M[i][2] * z) + M[i][3],
+    q_i = w_j * t_i, acc_i = q_i (j = 0) or acc_i + q_i, every influence evaluated.  shape [n, 9] (or [n, 3, 3]), index and weight
+    [n, 3, J] (or [3n, J]), bones [n_bones, 12] (or [n_bones, 3, 4]); returns [n, 9].  What the library promises bit for bit."""
+    shape = np.ascontiguousarray(shape, dtype=np.float64).reshape(-1, 3)
+    index = np.asarray(index, dtype=np.int64).reshape(shape.shape[0], -1)
+    weight = np.ascontiguousarray(weight, dtype=np.float64).reshape(shape.shape[0], -1)
+    bones = np.ascontiguousarray(bones, dtype=np.float64).reshape(-1, 3, 4)
+    if index.shape != weight.shape or index.shape[1] < 1:
+        raise ValueError("skin_blend: one weight per index, at least one influence per corner")
+    x, y, z = shape[:, 0:1], shape[:, 1:2], shape[:, 2:3]
+    acc = None
+    for j in range(index.shape[1]):
+        m = bones[index[:, j]]                                      # [corners, 3, 4]
+        px = m[:, :, 0] * x
+        py = m[:, :, 1] * y
+        pz = m[:, :, 2] * z
+        t = px + py
+        t = t + pz
+        t = t + m[:, :, 3]
+        q = weight[:, j:j + 1] * t
+        acc = q if j == 0 else acc + q
+    return np.ascontiguousarray(acc).reshape(-1, 9)
 
 
 def jitter_pattern(n, seed=DEFAULT_SEED):
@@ -660,6 +686,32 @@ class Context(SceneBuilder):
         out = dict(zip(_capi.MORPH_FIELDS, (int(v) for v in counts)))
         out["scan"], out["from_device"] = scan, bool(scan[7] == 1.0)
         return out
+
+    # skinning: vertices posed from a bone palette on the device before the refit (include/functracer_hip.h) --------
+    def set_mesh_skin(self, node, index, weight):
+        """ft_sg_set_mesh_skin: bone indices and weights of the `bsp_mesh` node's corners, [n, 3, J] each (J = 1 .. 4), corner-major.  It
+        removes any palette; J = 0 (arrays of shape [n, 3, 0]) removes the skin as well."""
+        idx = np.ascontiguousarray(index, dtype=np.int32)
+        w = _capi.as_f64(weight)
+        if idx.ndim != 3 or idx.shape[1] != 3 or w.shape != idx.shape:
+            raise ValueError("set_mesh_skin: index and weight are [n, 3, J]")
+        j = idx.shape[2]
+        self._check(self._lib.ft_sg_set_mesh_skin(self._ctx, int(node), idx.ctypes.data_as(C.POINTER(C.c_int32)) if j else None, _capi.dptr(w) if j else None, j, idx.shape[0]))
+
+    def set_mesh_bones(self, node, matrices):
+        """ft_sg_set_mesh_bones: the node's vertices are skin_blend(shape, index, weight, matrices) from the next commit on, matrices
+        [n_bones, 12] or [n_bones, 3, 4] (an empty array removes the palette); commit_deformed makes them on the device (option
+        "skin_on_device", default 1)."""
+        m = _capi.as_f64(matrices).reshape(-1, 12)
+        self._check(self._lib.ft_sg_set_mesh_bones(self._ctx, int(node), _capi.dptr(m) if m.shape[0] else None, m.shape[0]))
+
+    def skin(self, node):
+        """ft_debug_skin: a dict of `device_commits` (commit_deformed calls since the context was created that skinned a mesh on the device),
+        `device_meshes` / `host_meshes` (meshes the last commit_deformed skinned on the device / on the host) and `resident_bytes` (rest
+        shape, indices, weights and palette of `node` per device)."""
+        counts = (C.c_int64 * 4)()
+        self._check(self._lib.ft_debug_skin(self._ctx, int(node), counts))
+        return dict(zip(_capi.MORPH_FIELDS, (int(v) for v in counts)))
 
     # moving lights (include/functracer_hip.h) ---------------------------------------------------------
     def set_directional(self, light, direction, colour):

@@ -157,6 +157,15 @@ MORPH_SIGNATURES = [
 ]
 MORPH_FIELDS = ("device_commits", "device_meshes", "host_meshes", "resident_bytes")
 
+# Skinning (include/functracer_hip.h): indices and weights per corner, a palette of 3x4 bone matrices per pose; ft_debug_skin's counts are MORPH_FIELDS
+MAX_SKIN_BONES = 256
+MAX_SKIN_INFLUENCES = 4
+SKIN_SIGNATURES = [
+    ("ft_sg_set_mesh_skin", C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), c_double_p, C.c_int32, C.c_int64]),
+    ("ft_sg_set_mesh_bones", C.c_int32, [C.c_void_p, C.c_int32, c_double_p, C.c_int32]),
+    ("ft_debug_skin", C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]),
+]
+
 
 # Moving lights (include/functracer_hip.h): new values for an existing light, committed without a flatten or a BVH build.
 LIGHT_SIGNATURES = [

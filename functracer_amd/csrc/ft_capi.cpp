@@ -154,7 +154,7 @@ void ft_destroy(ft_context* c) {
         for (DeviceBuf& b : c->d_acc) b.release();
         for (DeviceBuf* b : {&c->d_out, &c->d_out8, &c->d_out_index, &c->d_pixels, &c->d_jitter, &c->d_wave_counts, &c->d_dbg_in, &c->d_dbg_out}) b->release();
         for (auto& f : c->slots) f.release();
-        c->prog.release(); c->aov.release(); c->denoise.release(); c->temporal.release(); c->refit.release(); c->morph.release(); c->lightspace.release();   // what the features own
+        c->prog.release(); c->aov.release(); c->denoise.release(); c->temporal.release(); c->refit.release(); c->morph.release(); c->skin.release(); c->lightspace.release();   // what the features own
         if (c->classified) (void)hipEventDestroy(c->classified);
         for (hipEvent_t& e : c->acc_free) if (e) { (void)hipEventDestroy(e); e = nullptr; }
         if (c->side) (void)hipStreamDestroy(c->side);
@@ -209,6 +209,7 @@ const OptionSpec kOptions[] = {
     {"light_space_retree", 0, 1, &Options::light_space_retree, nullptr, kFlag},
     // read by ft_scene_commit_deformed alone, as the ones above (the default is 1, and any other value means 0)
     {"morph_on_device", 0, 1, &Options::morph_on_device, nullptr, kOneElseZero},
+    {"skin_on_device", 0, 1, &Options::skin_on_device, nullptr, kOneElseZero},
     // read by ft_scene_commit_moved alone, as the ones above (any value other than 0 means 1)
     {"moved_in_place", 0, 1, &Options::moved_in_place, nullptr, kFlag},
     {"csg_mesh_capacity", 1, 255, nullptr, [](fth::SceneGraph& g, int64_t v) { g.csg_mesh_capacity = (int32_t)v; }, kCommit},
@@ -288,6 +289,7 @@ int32_t ft_sg_set_mesh_triangles(ft_context* c, ft_node node, const double* tris
     if (n_tris < 0 || (uint64_t)n_tris != n.tris.size() / 9) { c->err = "ft_sg_set_mesh_triangles: the triangle count differs from the node's"; return FT_ERR_INVALID; }
     n.tris.assign(tris, tris + 9 * n_tris);
     n.by_weights = false; n.tris_stale = false;                     // explicit vertices; base and deltas stay for a later ft_sg_set_mesh_weights
+    n.shape_serial = ++c->skin.serials; n.posed_stale = true;       // (under a palette they are the shape U: the palette stays in force)
     n.deformed = true;
     c->committed = false;
     return FT_OK;
@@ -316,7 +318,8 @@ int32_t ft_sg_set_mesh_targets(ft_context* c, ft_node node, const double* target
     if (n_tris < 0 || (uint64_t)n_tris != n.tris.size() / 9) { c->err = "ft_sg_set_mesh_targets: the triangle count differs from the node's"; return FT_ERR_INVALID; }
     if (n_targets < 0 || n_targets > FT_MAX_MORPH_TARGETS) { c->err = "ft_sg_set_mesh_targets: the target count is outside 0 .. FT_MAX_MORPH_TARGETS"; return FT_ERR_INVALID; }
     if (n_targets > 0 && !targets) { c->err = "ft_sg_set_mesh_targets: no targets"; return FT_ERR_INVALID; }
-    const std::vector<double>& B = n.vertices();                    // (blended first where weights describe them: they are explicit from here on)
+    const std::vector<double>& B = n.shape();                       // (blended first where weights describe them: they are explicit from here on; under a palette the shape U, not the skinned V)
+    if (n.by_weights) n.shape_serial = ++c->skin.serials;           // (what a device holds as the rest shape is not this)
     n.by_weights = false; n.tris_stale = false;
     n.weights.clear();
     n.n_targets = n_targets;
@@ -341,7 +344,7 @@ int32_t ft_sg_set_mesh_weights(ft_context* c, ft_node node, const double* weight
     if (!weights) { c->err = "ft_sg_set_mesh_weights: no weights"; return FT_ERR_INVALID; }
     for (int32_t k = 0; k < n_weights; ++k) if (!std::isfinite(weights[k])) { c->err = "ft_sg_set_mesh_weights: a weight is not finite"; return FT_ERR_INVALID; }
     n.weights.assign(weights, weights + n_weights);
-    n.by_weights = true; n.tris_stale = true;
+    n.by_weights = true; n.tris_stale = true; n.posed_stale = true;
     n.deformed = true;
     c->committed = false;
     return FT_OK;
@@ -355,6 +358,77 @@ int32_t ft_debug_morph(ft_context* c, ft_node node, int64_t counts[4], double sc
     for (const ft_context::Morph::Resident& r : M.meshes) if (r.node == node) counts[3] = (int64_t)r.used;
     for (int k = 0; k < 8; ++k) scan[k] = 0.0;
     for (const ft_context::Morph::Used& u : M.last) if (u.node == node) for (int k = 0; k < 8; ++k) scan[k] = u.scan[k];
+    return FT_OK;
+}
+// Skinning: a skin is indices and weights per corner, a palette the bone matrices of one pose; V = skin(U, palette).
+static_assert(ftk::kMaxSkinBones == FT_MAX_SKIN_BONES && ftk::kMaxSkinInfluences == FT_MAX_SKIN_INFLUENCES, "k_skin reads a byte per index and a word per corner");
+static void drop_resident_skin(ft_context* c, ft_node node) {
+    if (c->host_only) return;
+    for (ft_context* d : devices(c)) {
+        auto& held = d->skin.meshes;
+        for (size_t k = 0; k < held.size(); ++k) {
+            if (held[k].node != node) continue;
+            (void)hipSetDevice(d->device);
+            ft_context::Skin::drop(held[k]);
+            held.erase(held.begin() + (long)k);
+            break;
+        }
+    }
+    (void)hipSetDevice(c->device);
+}
+int32_t ft_sg_set_mesh_skin(ft_context* c, ft_node node, const int32_t* bone_index, const double* bone_weight, int32_t influences, int64_t n_tris) {
+    if (!c) return FT_ERR_INVALID;
+    if (!c->graph.valid(node) || c->graph.nodes[node].kind != fth::GraphNode::Mesh) { c->err = "ft_sg_set_mesh_skin: not a bspMesh node"; return FT_ERR_INVALID; }
+    fth::GraphNode& n = c->graph.nodes[node];
+    if (n_tris < 0 || (uint64_t)n_tris != n.tris.size() / 9) { c->err = "ft_sg_set_mesh_skin: the triangle count differs from the node's"; return FT_ERR_INVALID; }
+    if (influences < 0 || influences > FT_MAX_SKIN_INFLUENCES) { c->err = "ft_sg_set_mesh_skin: influences outside 0 .. FT_MAX_SKIN_INFLUENCES"; return FT_ERR_INVALID; }
+    if (influences > 0 && (!bone_index || !bone_weight)) { c->err = "ft_sg_set_mesh_skin: no indices or no weights"; return FT_ERR_INVALID; }
+    const size_t corners = 3 * (size_t)n_tris, J = (size_t)influences;
+    int32_t largest = 0;
+    for (size_t k = 0; k < corners * J; ++k) {
+        if (bone_index[k] < 0 || bone_index[k] >= FT_MAX_SKIN_BONES) { c->err = "ft_sg_set_mesh_skin: a bone index is outside 0 .. FT_MAX_SKIN_BONES - 1"; return FT_ERR_INVALID; }
+        if (!std::isfinite(bone_weight[k])) { c->err = "ft_sg_set_mesh_skin: a weight is not finite"; return FT_ERR_INVALID; }
+        largest = std::max(largest, bone_index[k]);
+    }
+    if (n.n_bones > 0) { n.deformed = true; c->committed = false; }  // a palette was in force: the vertices are the shape again
+    n.n_bones = 0;
+    std::vector<double>().swap(n.palette); std::vector<double>().swap(n.posed);
+    n.posed_stale = false;
+    n.skin_influences = influences; n.skin_max_index = largest;
+    n.skin_serial = ++c->skin.serials;
+    if (influences == 0) {
+        std::vector<uint32_t>().swap(n.skin_index); std::vector<double>().swap(n.skin_weight);
+        drop_resident_skin(c, node);
+        return FT_OK;
+    }
+    n.skin_index.assign(corners, 0u);
+    for (size_t k = 0; k < corners; ++k) for (size_t j = 0; j < J; ++j) n.skin_index[k] |= (uint32_t)bone_index[k * J + j] << (8 * j);
+    n.skin_weight.assign(bone_weight, bone_weight + corners * J);
+    return FT_OK;
+}
+int32_t ft_sg_set_mesh_bones(ft_context* c, ft_node node, const double* matrices, int32_t n_bones) {
+    if (!c) return FT_ERR_INVALID;
+    if (!c->graph.valid(node) || c->graph.nodes[node].kind != fth::GraphNode::Mesh) { c->err = "ft_sg_set_mesh_bones: not a bspMesh node"; return FT_ERR_INVALID; }
+    fth::GraphNode& n = c->graph.nodes[node];
+    if (n.skin_influences == 0) { c->err = "ft_sg_set_mesh_bones: the node has no skin (ft_sg_set_mesh_skin)"; return FT_ERR_INVALID; }
+    if (n_bones < 0 || n_bones > FT_MAX_SKIN_BONES) { c->err = "ft_sg_set_mesh_bones: the bone count is outside 0 .. FT_MAX_SKIN_BONES"; return FT_ERR_INVALID; }
+    if (n_bones > 0 && n_bones <= n.skin_max_index) { c->err = "ft_sg_set_mesh_bones: the skin uses a bone index the palette does not have"; return FT_ERR_INVALID; }
+    if (n_bones > 0 && !matrices) { c->err = "ft_sg_set_mesh_bones: no matrices"; return FT_ERR_INVALID; }
+    for (size_t k = 0; k < 12 * (size_t)n_bones; ++k) if (!std::isfinite(matrices[k])) { c->err = "ft_sg_set_mesh_bones: a matrix entry is not finite"; return FT_ERR_INVALID; }
+    n.n_bones = n_bones;
+    if (n_bones > 0) n.palette.assign(matrices, matrices + 12 * (size_t)n_bones);
+    else { std::vector<double>().swap(n.palette); std::vector<double>().swap(n.posed); }
+    n.posed_stale = n_bones > 0;
+    n.deformed = true;
+    c->committed = false;
+    return FT_OK;
+}
+int32_t ft_debug_skin(ft_context* c, ft_node node, int64_t counts[4]) {
+    if (!c || !counts) return FT_ERR_INVALID;
+    if (!c->graph.valid(node) || c->graph.nodes[node].kind != fth::GraphNode::Mesh) { c->err = "ft_debug_skin: not a bspMesh node"; return FT_ERR_INVALID; }
+    for (int k = 0; k < 3; ++k) counts[k] = c->skin.counts[k];
+    counts[3] = 0;
+    for (const ft_context::Skin::Resident& r : c->skin.meshes) if (r.node == node) counts[3] = (int64_t)(r.used_rest + r.used_skin + r.used_palette);
     return FT_OK;
 }
 ft_node ft_sg_material(ft_context* c, const ft_material* m, ft_node child) {
@@ -406,6 +480,11 @@ int32_t ft_scene_clear(ft_context* c) {
             (void)hipSetDevice(d->device);
             for (ft_context::Morph::Resident& r : d->morph.meshes) r.d.release();
             d->morph.meshes.clear();
+        }
+        for (ft_context* d : devices(c)) {                          // and their skins
+            if (d->skin.meshes.empty()) continue;
+            (void)hipSetDevice(d->device);
+            d->skin.release();
         }
         (void)hipSetDevice(c->device);
     }
@@ -692,7 +771,9 @@ int32_t commit_scene(ft_context* c) {
 // One edited mesh of the held scene: its index, its builder node and what one pass over the new vertices gave.
 // at: where its new vertices lie in ft_context::Refit::d_verts (doubles; even, so that every mesh starts on 16 bytes); on_device: weights
 // describe them and k_morph_blend writes them there on every device - the host holds no copy of them.
-struct DeformedMesh { uint32_t mesh; int32_t node; fth::MeshScan scan; size_t at = 0; bool on_device = false; };
+// blended / skinned: which of k_morph_blend and k_skin make them (the blend writes the shape there, the skin poses it in
+// place; without a blend the skin reads the rest shape resident beside its indices and weights).
+struct DeformedMesh { uint32_t mesh; int32_t node; fth::MeshScan scan; size_t at = 0; bool on_device = false, blended = false, skinned = false; };
 static size_t verts_doubles(const fth::SceneGraph& g, const std::vector<DeformedMesh>& edits) {
     size_t n = 0;
     for (const DeformedMesh& e : edits) n = std::max(n, e.at + g.nodes[(size_t)e.node].tris.size());
@@ -798,7 +879,11 @@ static int32_t snapshot_records(ft_context* c, const fth::FlatScene& f, const st
     return FT_OK;
 }
 
-// Morph targets on one device of the context: the vertices of every `on_device` edit blended into d_verts at the edit's
+// Morph targets and skinning on one device of the context: the vertices of every `on_device` edit made in d_verts at
+// the edit's place - `blended`: k_morph_blend from base and deltas; `skinned`: k_skin behind it, in place, or from the rest shape resident
+// beside the skin's index words and slot-major weights (uploaded when the device holds another ft_sg_set_mesh_skin call's / another
+// shape's), with this pose's palette (ms[0] += those uploads).
+// The blend: the vertices of every `blended` edit blended into d_verts at the edit's
 // place, from base and deltas resident in this device's HBM - uploaded here when the device holds none of the node's current
 // ft_sg_set_mesh_targets call (ms[0] += that upload).  Only d_verts is written, which no frame reads, so queued frames go on.  lead:
 // the context's first device, which also scans every blended mesh, bit for bit fth::scan_mesh, into the edit (ms[1] += blend, scan
@@ -813,9 +898,42 @@ static int32_t morph_device(ft_context* c, const fth::SceneGraph& g, std::vector
     if ((rc = ensure(c, c->refit.d_verts, verts_doubles(g, edits) * 8)) != FT_OK) return rc;
     bool uploaded = false;
     size_t blocks = 1, n_scans = 0;
+    std::vector<std::vector<double>> staged;                        // slot-major weights, until the stream has taken them
     for (const DeformedMesh& e : edits) {
         if (!e.on_device) continue;
         const fth::GraphNode& n = g.nodes[(size_t)e.node];
+        blocks = std::max(blocks, (size_t)ftk::morph_blocks((uint32_t)(n.tris.size() / 9)));
+        ++n_scans;
+        if (e.skinned) {                                            // indices and weights of the skin, the rest shape where no blend makes the shape, this pose's palette
+            ft_context::Skin& S = c->skin;
+            ft_context::Skin::Resident* s = nullptr;
+            for (ft_context::Skin::Resident& h : S.meshes) if (h.node == e.node) s = &h;
+            if (!s) { S.meshes.emplace_back(); s = &S.meshes.back(); s->node = e.node; s->skin_serial = s->rest_serial = ~0ull; s->wstride = 0; s->used_skin = s->used_rest = s->used_palette = 0; }
+            const size_t corners = n.tris.size() / 3, J = (size_t)n.skin_influences;
+            if (s->skin_serial != n.skin_serial) {
+                if ((rc = ensure(c, s->d_index, corners * 4)) != FT_OK || (rc = ensure(c, s->d_weight, J * corners * 8)) != FT_OK) return rc;
+                staged.emplace_back(J * corners);
+                std::vector<double>& w = staged.back();
+                for (size_t k = 0; k < corners; ++k) for (size_t j = 0; j < J; ++j) w[j * corners + k] = n.skin_weight[k * J + j];
+                if (corners) {
+                    FT_HIP(c, hipMemcpyAsync(s->d_index.p, n.skin_index.data(), corners * 4, hipMemcpyHostToDevice, c->stream));
+                    FT_HIP(c, hipMemcpyAsync(s->d_weight.p, w.data(), J * corners * 8, hipMemcpyHostToDevice, c->stream));
+                }
+                s->skin_serial = n.skin_serial; s->wstride = corners; s->used_skin = corners * 4 + J * corners * 8;
+                uploaded = true;
+            }
+            if (!e.blended && s->rest_serial != n.shape_serial) {
+                if ((rc = ensure(c, s->d_rest, n.tris.size() * 8)) != FT_OK) return rc;
+                if (!n.tris.empty()) FT_HIP(c, hipMemcpyAsync(s->d_rest.p, n.tris.data(), n.tris.size() * 8, hipMemcpyHostToDevice, c->stream));
+                s->rest_serial = n.shape_serial; s->used_rest = n.tris.size() * 8;
+                uploaded = true;
+            }
+            if ((rc = ensure(c, s->d_palette, n.palette.size() * 8)) != FT_OK) return rc;
+            FT_HIP(c, hipMemcpyAsync(s->d_palette.p, n.palette.data(), n.palette.size() * 8, hipMemcpyHostToDevice, c->stream));
+            s->used_palette = n.palette.size() * 8;
+            uploaded = true;
+        }
+        if (!e.blended) continue;
         ft_context::Morph::Resident* r = nullptr;
         for (ft_context::Morph::Resident& h : M.meshes) if (h.node == e.node) r = &h;
         if (!r) { M.meshes.push_back({e.node, 0, 0, 0, DeviceBuf{}}); r = &M.meshes.back(); }
@@ -830,8 +948,6 @@ static int32_t morph_device(ft_context* c, const fth::SceneGraph& g, std::vector
             r->serial = n.targets_serial; r->stride = stride; r->used = (size_t)(n.n_targets + 1) * count * 8;
             uploaded = true;
         }
-        blocks = std::max(blocks, (size_t)ftk::morph_blocks((uint32_t)(n.tris.size() / 9)));
-        ++n_scans;
     }
     if (uploaded) FT_HIP(c, hipStreamSynchronize(c->stream));
     ms[0] += since(t0);
@@ -842,14 +958,25 @@ static int32_t morph_device(ft_context* c, const fth::SceneGraph& g, std::vector
     for (const DeformedMesh& e : edits) {
         if (!e.on_device) continue;
         const fth::GraphNode& n = g.nodes[(size_t)e.node];
-        const ft_context::Morph::Resident* r = nullptr;
-        for (const ft_context::Morph::Resident& h : M.meshes) if (h.node == e.node) r = &h;
-        ftk::MorphBlend a{};
-        a.resident = r->d.as<double>(); a.out = c->refit.d_verts.as<double>() + e.at; a.count = n.tris.size(); a.stride = r->stride; a.n_targets = n.n_targets;
-        for (int32_t k = 0; k < n.n_targets; ++k) a.w[k] = n.weights[(size_t)k];
-        ftk::morph_blend(c->stream, a);
+        double* out = c->refit.d_verts.as<double>() + e.at;
+        if (e.blended) {
+            const ft_context::Morph::Resident* r = nullptr;
+            for (const ft_context::Morph::Resident& h : M.meshes) if (h.node == e.node) r = &h;
+            ftk::MorphBlend a{};
+            a.resident = r->d.as<double>(); a.out = out; a.count = n.tris.size(); a.stride = r->stride; a.n_targets = n.n_targets;
+            for (int32_t k = 0; k < n.n_targets; ++k) a.w[k] = n.weights[(size_t)k];
+            ftk::morph_blend(c->stream, a);
+        }
+        if (e.skinned) {                                            // behind the blend on the stream, in place; else from the rest shape
+            const ft_context::Skin::Resident* s = nullptr;
+            for (const ft_context::Skin::Resident& h : c->skin.meshes) if (h.node == e.node) s = &h;
+            ftk::SkinPose a{};
+            a.src = e.blended ? out : s->d_rest.as<double>(); a.out = out; a.index = s->d_index.as<uint32_t>(); a.weight = s->d_weight.as<double>();
+            a.palette = s->d_palette.as<double>(); a.corners = n.tris.size() / 3; a.wstride = s->wstride; a.influences = n.skin_influences; a.n_bones = n.n_bones;
+            ftk::skin(c->stream, a);
+        }
         // (one scan after the other on the stream: they share the partials)
-        if (lead) ftk::morph_scan(c->stream, a.out, (uint32_t)(a.count / 9), M.d_partials.as<ftk::MorphPartial>(), M.d_out.as<ftk::MorphScanOut>() + k_scan++);
+        if (lead) ftk::morph_scan(c->stream, out, (uint32_t)(n.tris.size() / 9), M.d_partials.as<ftk::MorphPartial>(), M.d_out.as<ftk::MorphScanOut>() + k_scan++);
     }
     FT_HIP(c, hipGetLastError());
     if (lead && n_scans) {
@@ -1620,7 +1747,7 @@ int32_t ft_scene_commit_deformed(ft_context* c) {
     fth::FlatScene& f = c->flat;
     // Host: one pass over every edited mesh - bounds, extent, finiteness - before anything is changed or uploaded.
     std::vector<DeformedMesh> edits;
-    size_t verts_at = 0, n_on_device = 0;
+    size_t verts_at = 0, n_on_device = 0, n_blended = 0, n_skinned = 0;
     // ft_debug_morph counts[2]: the meshes this call - whichever way it ends - has the host blend (GraphNode::vertices)
     struct HostBlends {
         ft_context* c; uint64_t before;
@@ -1628,6 +1755,12 @@ int32_t ft_scene_commit_deformed(ft_context* c) {
         explicit HostBlends(ft_context* ctx) : c(ctx), before(total(ctx)) {}
         ~HostBlends() { c->morph.counts[2] = (int64_t)(total(c) - before); }
     } host_blends(c);
+    struct HostSkins {                                              // ft_debug_skin counts[2], the same way
+        ft_context* c; uint64_t before;
+        static uint64_t total(const ft_context* c) { uint64_t n = 0; for (const fth::GraphNode& g : c->graph.nodes) n += g.host_skins; return n; }
+        explicit HostSkins(ft_context* ctx) : c(ctx), before(total(ctx)) {}
+        ~HostSkins() { c->skin.counts[2] = (int64_t)(total(c) - before); }
+    } host_skins(c);
     auto refuse = [c](bool depth) {
         c->err = depth ? "ft_scene_commit_deformed: an edited mesh has depth above 0 - its clipped BSP depends on the positions (ft_scene_commit)"
                        : "ft_scene_commit_deformed: an edited mesh holds a non-finite coordinate (ft_scene_commit)";
@@ -1641,20 +1774,28 @@ int32_t ft_scene_commit_deformed(ft_context* c) {
         const bool refuse_depth = n.depth > 0 && !c->graph.mesh_unclipped_bvh;
         // "morph_on_device" (DESIGN.md 16.4): weights describe the vertices - the device blends and scans them, below, once every
         // refusal that needs no vertices has been looked at (the positions 3 x triangle + corner are 32 bits wide there)
-        const bool on_device = n.by_weights && !c->host_only && c->opt.morph_on_device == 1 && n.tris.size() / 9 <= 0x55555555u;
+        const bool fits = !c->host_only && n.tris.size() / 9 <= 0x55555555u;
+        const bool morph_device_ok = n.by_weights && fits && c->opt.morph_on_device == 1;
+        // "skin_on_device" (DESIGN.md 16.5): a palette poses the shape - k_skin does, where the shape is explicit or blended on the device in
+        // this same call; in every other case the host makes V (GraphNode::vertices) and the mesh goes the ft_sg_set_mesh_triangles way
+        const bool skinned = n.n_bones > 0 && fits && c->opt.skin_on_device == 1 && (!n.by_weights || morph_device_ok);
+        const bool blended = morph_device_ok && (n.n_bones == 0 || skinned);
+        const bool on_device = blended || skinned;
         const fth::MeshScan scan = refuse_depth || on_device ? fth::MeshScan{{0, 0, 0, 0, 0, 0}, 0.0, true} : fth::scan_mesh(n.vertices().data(), (int64_t)(n.tris.size() / 9));
         if (refuse_depth || !scan.finite || f.meshes[m].root >= 0) return refuse(refuse_depth || f.meshes[m].root >= 0);
         DeformedMesh e{m, id, scan};
-        e.at = verts_at; e.on_device = on_device;
+        e.at = verts_at; e.on_device = on_device; e.blended = blended; e.skinned = skinned;
         verts_at += n.tris.size() + (n.tris.size() & 1);
-        n_on_device += on_device ? 1 : 0;
+        n_on_device += on_device ? 1 : 0; n_blended += blended ? 1 : 0; n_skinned += skinned ? 1 : 0;
         edits.push_back(e);
     }
     double morph_ms[2] = {0.0, 0.0};                                // uploads, kernels with their readbacks
     ft_context::Morph& M = c->morph;
-    M.counts[1] = (int64_t)n_on_device;
+    M.counts[1] = (int64_t)n_blended;
+    c->skin.counts[1] = (int64_t)n_skinned;
     if (n_on_device) {
-        ++M.counts[0];
+        if (n_blended) ++M.counts[0];
+        if (n_skinned) ++c->skin.counts[0];
         for (ft_context* d : devices(c)) {
             const int32_t mrc = morph_device(d, c->graph, edits, morph_ms, d == c);
             if (mrc != FT_OK) { if (d != c) c->err = d->err; return mrc; }   // (only d_verts has been written: the old commit stands)

@@ -101,6 +101,7 @@ struct Options {
     int64_t moved_in_place = 0;         // ft_scene_commit_moved uploads the new poses and refits the light-space pairs instead of committing the scene again (not a commit-time option)
     int64_t deform_light_space = 0;     // ft_scene_commit_deformed refits the light-space trees and builds the grids of the meshes it edits again instead of stripping them (not a commit-time option)
     int64_t morph_on_device = 1;        // ft_scene_commit_deformed blends and scans weight-driven meshes on the device (not a commit-time option; any value but 1 means 0)
+    int64_t skin_on_device = 1;         // ft_scene_commit_deformed skins meshes with a bone palette on the device (not a commit-time option; any value but 1 means 0)
     int64_t temporal_follow_deformed = 0;   // ft_scene_commit_deformed keeps a mesh's records as the history saw them and ft_temporal_accumulate follows them
     int64_t primary_mesh_kernel = 1;   // k_primary_mesh for the frames that qualify (ft_context::mesh_kernel_scene, queue_chunks); 0: k_primary everywhere (A/B)
     int64_t edge_cull = 1;          // candidate-list and shadow-grid entries are also tested against their triangle's projected edges (ft_edges.h); 0: the rectangles alone (A/B)
@@ -320,6 +321,17 @@ struct ft_context {
         uint64_t serials = 0;       // the last value a GraphNode::targets_serial was given
         void release() { for (Resident& r : meshes) r.d.release(); meshes.clear(); d_partials.release(); d_out.release(); }
     } morph;
+    // Skinning.  On every device: per skinned mesh node the index words and slot-major weights of the ft_sg_set_mesh_skin
+    // call `skin_serial` names (wstride doubles from slot to slot), the rest shape of the explicit vertices `rest_serial` names (empty
+    // until a pose needs it) and the palette of the last pose.  On the context's first device: ft_debug_skin's counters.
+    struct Skin {
+        struct Resident { int32_t node; uint64_t skin_serial, rest_serial, wstride; size_t used_skin, used_rest, used_palette; DeviceBuf d_index, d_weight, d_rest, d_palette; };
+        std::vector<Resident> meshes;
+        int64_t counts[3] = {0, 0, 0};
+        uint64_t serials = 0;       // the last value a GraphNode::skin_serial or shape_serial was given
+        static void drop(Resident& r) { for (DeviceBuf* b : {&r.d_index, &r.d_weight, &r.d_rest, &r.d_palette}) b->release(); }
+        void release() { for (Resident& r : meshes) drop(r); meshes.clear(); }
+    } skin;
     // ft_scene_commit_lights.  On the context's first device, derived from `flat` by the first call after a full commit
     // (`ready`) and kept until the next one: per (leaf, directional light) pair that had a tree then its record as that commit wrote it
     // (rec0) and the light's direction then (v0), the tree's root, what of the record does not depend on the direction (centre, R; the

@@ -268,6 +268,14 @@ void morph_scan(hipStream_t stream, const double* verts, uint32_t n, MorphPartia
 // function's arithmetic; partials: morph_blocks(n) doubles of scratch.
 void morph_extent(hipStream_t stream, const double* verts, uint32_t n, const double c[3], double* partials, double* out);
 
+// Skinning (ft_skin.hip, ft_sg_set_mesh_bones + ft_scene_commit_deformed).  SkinPose: out[3c .. 3c+2] = the corner
+// src[3c .. 3c+2] posed by fth::skin_blend's arithmetic, c < corners.  index: one word per corner, bone j in byte j (every byte below
+// n_bones); weight: slot-major, weight[j * wstride + c]; palette: n_bones x 12 doubles, 16-byte aligned.  src == out is allowed (a lane
+// reads its own corner before it writes it); corners <= 0xFFFFFFFF.
+constexpr int kMaxSkinBones = 256, kMaxSkinInfluences = 4;        // FT_MAX_SKIN_BONES, FT_MAX_SKIN_INFLUENCES (ft_capi.cpp asserts them)
+struct SkinPose { const double* src; double* out; const uint32_t* index; const double* weight; const double* palette; uint64_t corners, wstride; int32_t influences, n_bones; };
+void skin(hipStream_t stream, const SkinPose& a);
+
 // Refit of a light-space shadow tree whose light turned (ft_lightspace.hip, ft_scene_commit_lights).  LsFrame: the pair's new frame and
 // centre as its record holds them (ft_flat.h, kLsPairDoubles) and the builder's inflation, 1e-7 * R + 1e-30.  One call per level of the
 // tree, deepest first: order[0 .. count) are that level's 4-wide nodes (indices into ls_nodes), whose child boxes are written again -

@@ -456,13 +456,46 @@ void morph_blend(const double* base, const double* deltas, const double* w, int3
         out[i] = acc;
     }
 }
-const std::vector<double>& GraphNode::vertices() const {
+const std::vector<double>& GraphNode::shape() const {
     if (by_weights && tris_stale) {
         morph_blend(base.data(), deltas.data(), weights.data(), n_targets, tris.size(), tris.data());
         tris_stale = false;
         ++host_blends;
     }
     return tris;
+}
+void skin_blend(const double* shape, const uint32_t* index, const double* weight, int32_t influences, const double* palette, size_t corners, double* out) {
+    for (size_t c = 0; c < corners; ++c) {
+        const double x = shape[3 * c], y = shape[3 * c + 1], z = shape[3 * c + 2];
+        double acc[3] = {0.0, 0.0, 0.0};
+        for (int32_t j = 0; j < influences; ++j) {
+            const double* M = palette + 12 * (size_t)((index[c] >> (8 * j)) & 255u);
+            const double w = weight[c * (size_t)influences + (size_t)j];
+            for (int i = 0; i < 3; ++i) {
+                const double* R = M + 4 * i;
+                const double px = R[0] * x;
+                const double py = R[1] * y;
+                const double pz = R[2] * z;
+                double t = px + py;
+                t = t + pz;
+                t = t + R[3];
+                const double q = w * t;
+                acc[i] = j == 0 ? q : acc[i] + q;
+            }
+        }
+        out[3 * c] = acc[0]; out[3 * c + 1] = acc[1]; out[3 * c + 2] = acc[2];
+    }
+}
+const std::vector<double>& GraphNode::vertices() const {
+    if (n_bones == 0) return shape();
+    if (posed_stale || (by_weights && tris_stale) || posed.size() != tris.size()) {
+        const std::vector<double>& U = shape();
+        posed.resize(U.size());
+        skin_blend(U.data(), skin_index.data(), skin_weight.data(), skin_influences, palette.data(), U.size() / 3, posed.data());
+        posed_stale = false;
+        ++host_skins;
+    }
+    return posed;
 }
 
 MeshScan scan_mesh(const double* tris, int64_t n) {

@@ -28,7 +28,21 @@ struct GraphNode {
     bool by_weights = false;
     mutable bool tris_stale = false;  // by_weights and `tris` has not been blended from the weights as they stand
     mutable uint64_t host_blends = 0; // times vertices() has blended them on the host (ft_debug_morph counts[2])
-    // The vertices as they stand: `tris`, blended first where the weights describe them (morph_blend's arithmetic).
+    // Mesh: skinning (ft_sg_set_mesh_skin / ft_sg_set_mesh_bones).  skin_index: per corner (3 x triangle + corner) one word
+    // of four bone indices, slot j in byte j, unused slots 0 - as the device reads them; skin_weight: per corner J weights, corner-major as
+    // given; palette: n_bones x 12, the rows of a 3x4 matrix per bone (n_bones 0: no palette in force).  skin_serial: another value after
+    // every ft_sg_set_mesh_skin, shape_serial: after every call that makes the shape explicit vertices of other contents
+    // (ft_sg_set_mesh_triangles, ft_sg_set_mesh_targets) - what a device holds of indices and weights / of the rest shape is that call's.
+    std::vector<uint32_t> skin_index;
+    std::vector<double> skin_weight, palette;
+    int32_t skin_influences = 0, skin_max_index = 0, n_bones = 0;
+    uint64_t skin_serial = 0, shape_serial = 0;
+    mutable std::vector<double> posed;   // skin(shape(), palette) while a palette is in force and not `posed_stale`
+    mutable bool posed_stale = false;
+    mutable uint64_t host_skins = 0;  // times vertices() has skinned them on the host (ft_debug_skin counts[2])
+    // The shape U as it stands: `tris`, blended first where the weights describe them (morph_blend's arithmetic).
+    const std::vector<double>& shape() const;
+    // The vertices V as they stand: the shape, skinned first where a palette is in force (skin_blend's arithmetic).
     const std::vector<double>& vertices() const;
     std::vector<ft_transform> xf;     // Transform: one basic transform or a Composed list
     ft_material mat{};                // MaterialF
@@ -104,6 +118,11 @@ MeshScan scan_mesh(const double* tris_abc, int64_t n_tris);
 // Morph targets: out[i] = blend(base, deltas, w)[i], i < count - acc = base[i]; for k = 0 .. K-1 in order: p = w[k] * deltas[k * count + i],
 // acc = acc + p; every term evaluated, product and sum each rounded once (this unit is built with -ffp-contract=off).
 void morph_blend(const double* base, const double* deltas, const double* w, int32_t n_targets, size_t count, double* out);
+// Skinning: out = skin(shape, palette) over `corners` corners of three doubles.  Per corner (x, y, z), for j = 0 .. J-1 in order with
+// b = byte j of index[corner], M = palette + 12 * b, wj = weight[corner * J + j]: t_i = ((M[4i] * x + M[4i+1] * y) + M[4i+2] * z) + M[4i+3],
+// q_i = wj * t_i, acc_i = j == 0 ? q_i : acc_i + q_i; every influence evaluated, every product and sum rounded once (-ffp-contract=off).
+// out may not alias shape.
+void skin_blend(const double* shape, const uint32_t* index, const double* weight, int32_t influences, const double* palette, size_t corners, double* out);
 
 struct SceneGraph {
     std::vector<GraphNode> nodes;

@@ -204,7 +204,11 @@ const char* ft_last_error(const ft_context* ctx);
  * "morph_on_device" (1 = default; any other value means 0: ft_scene_commit_deformed blends the vertices of
  * the meshes that ft_sg_set_mesh_weights describes on the device, from a base and deltas resident in HBM, and scans them there - "morph targets" below; with 0
  * the host blends them and the call is the ft_sg_set_mesh_triangles path, the same bits.  It is read by ft_scene_commit_deformed alone and needs no new
- * ft_scene_commit; a host-only context accepts it without effect).  Every option reaches every device of a context.  Scene-affecting
+ * ft_scene_commit; a host-only context accepts it without effect),
+ * "skin_on_device" (1 = default; any other value means 0: ft_scene_commit_deformed poses the meshes that carry a bone palette on the
+ * device, from indices, weights and a rest shape resident in HBM - "skinning" below; with 0 the host skins them and the call is the
+ * ft_sg_set_mesh_triangles path, the same bits.  It is read by ft_scene_commit_deformed alone and needs no new ft_scene_commit; a
+ * host-only context accepts it without effect).  Every option reaches every device of a context.  Scene-affecting
  * options need a new ft_scene_commit.  Any other key is refused (FT_ERR_INVALID, "unknown option"). */
 int32_t ft_set_option(ft_context* ctx, const char* key, int64_t value);
 
@@ -800,6 +804,65 @@ int32_t ft_scene_tree_quality(ft_context* ctx, ft_node mesh_node, double out[4])
 int32_t ft_sg_set_mesh_targets(ft_context* ctx, ft_node mesh, const double* targets, int32_t n_targets, int64_t n_tris);
 int32_t ft_sg_set_mesh_weights(ft_context* ctx, ft_node mesh, const double* weights, int32_t n_weights);
 int32_t ft_debug_morph(ft_context* ctx, ft_node mesh, int64_t counts[4], double scan[8]);
+/* ---- skinning: vertices posed from a bone palette on the device before the refit ------------- */
+/* A bspMesh node has a shape U: its explicit vertices (ft_sg_bsp_mesh, ft_sg_set_mesh_triangles) or blend(B, D, w) once
+ * ft_sg_set_mesh_weights has been called.  A node may also carry a skin and a palette; its vertices are then V = skin(U, palette), and
+ * ft_scene_commit_deformed makes them where the refit reads them.
+ * ft_sg_set_mesh_skin(mesh, bone_index, bone_weight, influences, n_tris): bone_index and bone_weight are n_tris x 3 x influences values,
+ * corner-major (triangle, corner a / b / c, slot), copied; influences = J in 1 .. FT_MAX_SKIN_INFLUENCES.  The call attaches the skin and
+ * removes any palette.  Not a structural change and no edit: the vertices stay U and nothing is marked deformed - unless a palette was in
+ * force, which the call removes: the node is then marked deformed.  influences = 0 removes skin and palette (the pointers may be null).
+ * FT_ERR_INVALID, with nothing changed, for a null context, an invalid handle, a node that is not a bspMesh node, an n_tris that differs
+ * from the node's count, influences outside 0 .. 4, null arrays with influences > 0, an index outside 0 .. FT_MAX_SKIN_BONES - 1 or a
+ * weight that is not finite.  Weights are used as given: the library does not normalise them.
+ * ft_sg_set_mesh_bones(mesh, matrices, n_bones): matrices = n_bones x 12 doubles, the rows of a 3x4 affine matrix per bone, copied.  The
+ * call declares V = skin(U, palette), marks the node as ft_sg_set_mesh_triangles does, leaves the scene uncommitted and is not structural.
+ * n_bones = 0 removes the palette (matrices may be null): V is U again and the node is marked deformed.  FT_ERR_INVALID, with nothing
+ * changed, for the node checks above, a node without a skin, n_bones outside 0 .. FT_MAX_SKIN_BONES, 0 < n_bones <= the largest index the
+ * skin uses, null matrices with n_bones > 0 or an entry that is not finite.
+ * The formula, per corner with shape position (x, y, z), in IEEE double, every product and every sum rounded once and never fused:
+ *     for j = 0 .. J-1 in order, b = index[corner][j], M = palette[b], wj = weight[corner][j]:
+ *         t_i = ((M[i][0]*x + M[i][1]*y) + M[i][2]*z) + M[i][3]     (i = 0, 1, 2; left to right)
+ *         q_i = wj * t_i
+ *         acc_i = (j == 0) ? q_i : acc_i + q_i
+ *     V = acc
+ * Every influence is evaluated, zero weights included.  Two corners with bitwise equal shape positions, indices and weights therefore come
+ * out bitwise equal: a mesh that is welded in its rest pose stays welded in every pose.
+ * The other setters: ft_sg_set_mesh_triangles and ft_sg_set_mesh_weights on a node with a palette change U and the palette stays in force;
+ * ft_sg_set_mesh_targets on such a node takes U as its base, not the skinned V (blend the shape, then skin it).  Nodes without a skin
+ * behave exactly as before.
+ * The promise: ft_sg_set_mesh_bones(node, P) followed by any commit gives every bit that ft_sg_set_mesh_triangles(node, V) gives on a twin
+ * node without a skin, followed by the same commit - frames, ft_stats (times aside), ft_render_aov, the ft_debug_* ray queries,
+ * ft_debug_mesh_trees - so everything said under "deforming meshes" above holds unchanged: the refusals (depth above 0, a non-finite V,
+ * bounds that change which items have bounds), the open temporal accumulation, "temporal_follow_deformed", "refit_rebuild_percent",
+ * "deform_light_space", "light_space_retree", several devices.
+ * ft_scene_commit_deformed, for every edited mesh with a palette, on a device context with "skin_on_device" = 1 (the default), where U is
+ * explicit or blended on the device in the same call ("morph_on_device" 1): keeps per device the index words (4 bytes per corner), the
+ * weights (J x 8 bytes per corner) and, where U is explicit, the rest shape (72 bytes per triangle; uploaded on first use and after an
+ * ft_sg_set_mesh_triangles), until the skin is removed, ft_scene_clear or ft_destroy; uploads the palette (n_bones x 96 bytes, at most 24 KiB)
+ * per pose, inside ft_get_commit_times [2]; runs k_skin (ft_skin.hip) on every device, in place behind the blend or from the rest shape;
+ * reduces bounds, extent, finiteness and, under "deform_light_space", each pair's R on the context's first device with the morph
+ * kernels, and goes on as for morph targets: a refused call has written only that buffer and leaves the old commit renderable.  With the
+ * option at 0, on a host-only context, with a weight-driven U under "morph_on_device" 0, and in every other commit the host makes V by
+ * the formula when the vertices are needed.
+ * ft_debug_skin(mesh, counts), for tests and tools: counts[0] = ft_scene_commit_deformed calls since ft_create that skinned at least one
+ * mesh on the device, counts[1] = meshes skinned on the device in the last ft_scene_commit_deformed, counts[2] = meshes whose skin the
+ * host made in it, counts[3] = bytes resident per device for `mesh` (rest shape, indices, weights, palette).  ft_debug_morph's scan[] keeps
+ * reporting the bounds the call used, scan[7] = 1 when they came from the device, skinned or not; its counters count morph blends only.
+ * FT_ERR_INVALID for a null context or pointer, an invalid handle or a node that is not a bspMesh node.
+ * What it is worth (MI355X, the 69.6 K-face mesh, nothing in flight, tools/skin_rate.py): the commit of a pose set by bones takes
+ * 0.33 ms ([0] 0.004, [1] 0.28, [2] 0.05 ms) whatever J and the bone count, against 0.98 ms ([0] 0.55, [1] 0.25, [2] 0.18 ms) for the same
+ * vertices handed to ft_sg_set_mesh_triangles; k_skin itself runs 7 - 10 microseconds.  The whole step (make the palette, set it, commit) takes
+ * 0.35 / 0.56 / 1.22 ms at J = 4 with 4 / 64 / 256 bones - the difference is the tool's own palette loop - against 31.5 / 32.6 / 32.3 ms for a host
+ * that skins in numpy and 2.06 / 2.26 / 2.93 ms with "skin_on_device" 0 (the library's host skin in [0]: 0.93 ms at J = 1, 1.6 ms at J = 4).
+ * The device route's whole step lies below the numpy host's by more than both spreads at every row measured (J = 1 and 4; 4, 64 and 256
+ * bones; under "deform_light_space"; over morph targets), so the default is 1.  The first pose after ft_sg_set_mesh_skin uploads the
+ * resident arrays: 0.6 - 2.3 ms in [2]. */
+#define FT_MAX_SKIN_BONES 256
+#define FT_MAX_SKIN_INFLUENCES 4
+int32_t ft_sg_set_mesh_skin(ft_context* ctx, ft_node mesh, const int32_t* bone_index, const double* bone_weight, int32_t influences, int64_t n_tris);
+int32_t ft_sg_set_mesh_bones(ft_context* ctx, ft_node mesh, const double* matrices, int32_t n_bones);
+int32_t ft_debug_skin(ft_context* ctx, ft_node mesh, int64_t counts[4]);
 /* ---- moving lights ----------------------------------------------------------------------------- */
 /* ft_scene_set_directional / _soft_directional / _positional + ft_scene_commit_lights change the lights of a committed scene without a
  * flatten, without a BVH build and without ending ft_temporal_*.
