@@ -15,7 +15,7 @@ from . import _capi
 from ._capi import (CIRCLE, CONE, CUBE, CYLINDER, EXCLUDE, INTERSECT, PLANE, SOLID_CYLINDER, SPHERE, SQUARE, SUBTRACT, UNION,
                     FtError, SceneBuilder, make_camera)
 
-__all__ = ["Context", "ls_topology", "PinnedArray", "ParsedScene", "parse_scene", "parse_scene_file", "jitter_pattern", "morph_blend", "skin_blend", "quantise_rgba8", "write_png",
+__all__ = ["Context", "ls_topology", "PinnedArray", "ParsedScene", "parse_scene", "parse_scene_file", "jitter_pattern", "morph_blend", "skin_blend", "skin_blend_dq", "dual_quaternions", "quantise_rgba8", "write_png",
            "parse_colour", "parse_ply", "FtError", "make_camera", "HIP_LIB", "HOST_LIB", "DEFAULT_SEED"]
 
 HIP_LIB = os.environ.get("FT_HIP_LIB") or os.path.join(_capi.LIB_DIR, "libfunctracer_hip.so")   # FT_HIP_LIB: experimental builds
@@ -74,7 +74,7 @@ def hip_lib():
         if hasattr(lib, _capi.MOVED_COMMITS_SIGNATURE[0]):          # (FT_HIP_LIB may name an older build, as above)
             fn = getattr(lib, _capi.MOVED_COMMITS_SIGNATURE[0])
             fn.restype, fn.argtypes = _capi.MOVED_COMMITS_SIGNATURE[1:]
-        for name, res, args in _capi.POSE_QUEUE_SIGNATURES + _capi.MORPH_SIGNATURES + _capi.SKIN_SIGNATURES:
+        for name, res, args in _capi.POSE_QUEUE_SIGNATURES + _capi.MORPH_SIGNATURES + _capi.SKIN_SIGNATURES + _capi.SKIN_DQ_SIGNATURES:
             if hasattr(lib, name):                                  # (FT_HIP_LIB may name an older build, as above)
                 fn = getattr(lib, name)
                 fn.restype, fn.argtypes = res, args
@@ -207,6 +207,81 @@ def skin_blend(shape, index, weight, bones):
         q = weight[:, j:j + 1] * t
         acc = q if j == 0 else acc + q
     return np.ascontiguousarray(acc).reshape(-1, 9)
+
+
+def _cross(a, b):
+    """cross(a, b) of [n, 3] arrays: per component two products and one difference, one elementwise operation per step."""
+    out = []
+    for i in range(3):
+        i1, i2 = (i + 1) % 3, (i + 2) % 3
+        left = a[:, i1] * b[:, i2]
+        right = a[:, i2] * b[:, i1]
+        out.append(left - right)
+    return np.stack(out, axis=1)
+
+
+def skin_blend_dq(shape, index, weight, dq):
+    """The vertices ft_sg_set_mesh_bones_dq declares (include/functracer_hip.h, "dual-quaternion skinning"), evaluated in numpy with one
+    elementwise IEEE double operation per step: per corner the weighted sum of the bones' dual quaternions in slot order, a bone whose
+    real part lies opposite slot 0's entering with its weight negated, normalised by the length of the real part, applied to the shape
+    position.  shape [n, 9] (or [n, 3, 3]), index and weight [n, 3, J] (or [3n, J]), dq [n_bones, 8] (real w, x, y, z, then dual); returns
+    [n, 9].  What the library promises bit for bit."""
+    p = np.ascontiguousarray(shape, dtype=np.float64).reshape(-1, 3)
+    index = np.asarray(index, dtype=np.int64).reshape(p.shape[0], -1)
+    weight = np.ascontiguousarray(weight, dtype=np.float64).reshape(p.shape[0], -1)
+    dq = np.ascontiguousarray(dq, dtype=np.float64).reshape(-1, 8)
+    if index.shape != weight.shape or index.shape[1] < 1:
+        raise ValueError("skin_blend_dq: one weight per index, at least one influence per corner")
+    with np.errstate(all="ignore"):
+        r0 = dq[index[:, 0], :4]
+        acc = None
+        for j in range(index.shape[1]):
+            d = dq[index[:, j]]                                     # [corners, 8]
+            ws = weight[:, j]
+            if j > 0:
+                g0 = d[:, 0] * r0[:, 0]
+                g1 = d[:, 1] * r0[:, 1]
+                g2 = d[:, 2] * r0[:, 2]
+                g3 = d[:, 3] * r0[:, 3]
+                g = g0 + g1
+                g = g + g2
+                g = g + g3
+                ws = np.where(g < 0.0, -ws, ws)                     # (a NaN g does not negate)
+            q = ws[:, None] * d
+            acc = q if j == 0 else acc + q
+        sq = acc[:, :4] * acc[:, :4]
+        n2 = sq[:, 0] + sq[:, 1]
+        n2 = n2 + sq[:, 2]
+        n2 = n2 + sq[:, 3]
+        n = np.sqrt(n2)
+        s = 1.0 / n
+        u = acc * s[:, None]
+        w, v, e, f = u[:, 0:1], u[:, 1:4], u[:, 4:5], u[:, 5:8]
+        wp = w * p
+        c = _cross(v, p) + wp
+        h = _cross(v, c)
+        wf = w * f
+        ev = e * v
+        m = wf - ev
+        m = m + _cross(v, f)
+        h2 = 2.0 * h
+        m2 = 2.0 * m
+        out = p + h2
+        out = out + m2
+    return np.ascontiguousarray(out).reshape(-1, 9)
+
+
+def dual_quaternions(rotations, translations):
+    """Palettes [n, 8] for ft_sg_set_mesh_bones_dq from unit quaternions [n, 4] (w, x, y, z) and translations [n, 3]: "rotate by r, then
+    translate by t" has real part r and dual part 0.5 * (0, t) (x) r.  A convenience, not part of the bit promise."""
+    r = np.ascontiguousarray(rotations, dtype=np.float64).reshape(-1, 4)
+    t = np.ascontiguousarray(translations, dtype=np.float64).reshape(-1, 3)
+    if r.shape[0] != t.shape[0]:
+        raise ValueError("dual_quaternions: one translation per rotation")
+    rw, rv = r[:, 0:1], r[:, 1:4]
+    dw = -0.5 * np.sum(t * rv, axis=1, keepdims=True)
+    dv = 0.5 * (rw * t + np.cross(t, rv))
+    return np.ascontiguousarray(np.concatenate([r, dw, dv], axis=1))
 
 
 def jitter_pattern(n, seed=DEFAULT_SEED):
@@ -712,6 +787,21 @@ class Context(SceneBuilder):
         counts = (C.c_int64 * 4)()
         self._check(self._lib.ft_debug_skin(self._ctx, int(node), counts))
         return dict(zip(_capi.MORPH_FIELDS, (int(v) for v in counts)))
+
+    def set_mesh_bones_dq(self, node, dq):
+        """ft_sg_set_mesh_bones_dq: the node's vertices are skin_blend_dq(shape, index, weight, dq) from the next commit on, dq [n_bones, 8]
+        (real part w, x, y, z, then the dual part; an empty array removes whichever palette is in force); it replaces a matrix palette,
+        and commit_deformed makes the vertices on the device as for set_mesh_bones (option "skin_on_device", default 1)."""
+        d = _capi.as_f64(dq).reshape(-1, 8)
+        self._check(self._lib.ft_sg_set_mesh_bones_dq(self._ctx, int(node), _capi.dptr(d) if d.shape[0] else None, d.shape[0]))
+
+    def skin_dq(self, node):
+        """ft_debug_skin_dq: a dict of `device_commits` (commit_deformed calls since the context was created that posed a mesh with k_skin_dq
+        on the device), `device_meshes` / `host_meshes` (meshes whose dual-quaternion skin the last commit_deformed made on the device / on
+        the host) and `palette_kind` (0 none, 1 matrices, 2 dual quaternions in force for `node`)."""
+        counts = (C.c_int64 * 4)()
+        self._check(self._lib.ft_debug_skin_dq(self._ctx, int(node), counts))
+        return dict(zip(_capi.SKIN_DQ_FIELDS, (int(v) for v in counts)))
 
     # moving lights (include/functracer_hip.h) ---------------------------------------------------------
     def set_directional(self, light, direction, colour):

@@ -165,6 +165,12 @@ SKIN_SIGNATURES = [
     ("ft_sg_set_mesh_bones", C.c_int32, [C.c_void_p, C.c_int32, c_double_p, C.c_int32]),
     ("ft_debug_skin", C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]),
 ]
+# Dual-quaternion palettes (include/functracer_hip.h, "dual-quaternion skinning"): 8 doubles per bone; ft_debug_skin_dq's counts are SKIN_DQ_FIELDS
+SKIN_DQ_SIGNATURES = [
+    ("ft_sg_set_mesh_bones_dq", C.c_int32, [C.c_void_p, C.c_int32, c_double_p, C.c_int32]),
+    ("ft_debug_skin_dq", C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]),
+]
+SKIN_DQ_FIELDS = ("device_commits", "device_meshes", "host_meshes", "palette_kind")
 
 
 # Moving lights (include/functracer_hip.h): new values for an existing light, committed without a flatten or a BVH build.

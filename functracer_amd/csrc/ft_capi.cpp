@@ -391,7 +391,7 @@ int32_t ft_sg_set_mesh_skin(ft_context* c, ft_node node, const int32_t* bone_ind
         largest = std::max(largest, bone_index[k]);
     }
     if (n.n_bones > 0) { n.deformed = true; c->committed = false; }  // a palette was in force: the vertices are the shape again
-    n.n_bones = 0;
+    n.n_bones = 0; n.palette_kind = fth::GraphNode::NoPalette;
     std::vector<double>().swap(n.palette); std::vector<double>().swap(n.posed);
     n.posed_stale = false;
     n.skin_influences = influences; n.skin_max_index = largest;
@@ -406,22 +406,32 @@ int32_t ft_sg_set_mesh_skin(ft_context* c, ft_node node, const int32_t* bone_ind
     n.skin_weight.assign(bone_weight, bone_weight + corners * J);
     return FT_OK;
 }
-int32_t ft_sg_set_mesh_bones(ft_context* c, ft_node node, const double* matrices, int32_t n_bones) {
+// One pose's palette of either kind (a node holds at most one): per_bone doubles per bone, `what` names the entries in the messages.
+static int32_t set_palette(ft_context* c, ft_node node, const double* data, int32_t n_bones, int32_t kind, size_t per_bone, const char* call, const char* what, const char* entry) {
     if (!c) return FT_ERR_INVALID;
-    if (!c->graph.valid(node) || c->graph.nodes[node].kind != fth::GraphNode::Mesh) { c->err = "ft_sg_set_mesh_bones: not a bspMesh node"; return FT_ERR_INVALID; }
+    const std::string name(call);
+    if (!c->graph.valid(node) || c->graph.nodes[node].kind != fth::GraphNode::Mesh) { c->err = name + ": not a bspMesh node"; return FT_ERR_INVALID; }
     fth::GraphNode& n = c->graph.nodes[node];
-    if (n.skin_influences == 0) { c->err = "ft_sg_set_mesh_bones: the node has no skin (ft_sg_set_mesh_skin)"; return FT_ERR_INVALID; }
-    if (n_bones < 0 || n_bones > FT_MAX_SKIN_BONES) { c->err = "ft_sg_set_mesh_bones: the bone count is outside 0 .. FT_MAX_SKIN_BONES"; return FT_ERR_INVALID; }
-    if (n_bones > 0 && n_bones <= n.skin_max_index) { c->err = "ft_sg_set_mesh_bones: the skin uses a bone index the palette does not have"; return FT_ERR_INVALID; }
-    if (n_bones > 0 && !matrices) { c->err = "ft_sg_set_mesh_bones: no matrices"; return FT_ERR_INVALID; }
-    for (size_t k = 0; k < 12 * (size_t)n_bones; ++k) if (!std::isfinite(matrices[k])) { c->err = "ft_sg_set_mesh_bones: a matrix entry is not finite"; return FT_ERR_INVALID; }
+    if (n.skin_influences == 0) { c->err = name + ": the node has no skin (ft_sg_set_mesh_skin)"; return FT_ERR_INVALID; }
+    if (n_bones < 0 || n_bones > FT_MAX_SKIN_BONES) { c->err = name + ": the bone count is outside 0 .. FT_MAX_SKIN_BONES"; return FT_ERR_INVALID; }
+    if (n_bones > 0 && n_bones <= n.skin_max_index) { c->err = name + ": the skin uses a bone index the palette does not have"; return FT_ERR_INVALID; }
+    if (n_bones > 0 && !data) { c->err = name + ": no " + what; return FT_ERR_INVALID; }
+    for (size_t k = 0; k < per_bone * (size_t)n_bones; ++k) if (!std::isfinite(data[k])) { c->err = name + ": " + entry + " is not finite"; return FT_ERR_INVALID; }
     n.n_bones = n_bones;
-    if (n_bones > 0) n.palette.assign(matrices, matrices + 12 * (size_t)n_bones);
+    n.palette_kind = n_bones > 0 ? kind : (int32_t)fth::GraphNode::NoPalette;
+    if (n_bones > 0) n.palette.assign(data, data + per_bone * (size_t)n_bones);
     else { std::vector<double>().swap(n.palette); std::vector<double>().swap(n.posed); }
     n.posed_stale = n_bones > 0;
     n.deformed = true;
     c->committed = false;
     return FT_OK;
+}
+int32_t ft_sg_set_mesh_bones(ft_context* c, ft_node node, const double* matrices, int32_t n_bones) {
+    return set_palette(c, node, matrices, n_bones, fth::GraphNode::Matrices, 12, "ft_sg_set_mesh_bones", "matrices", "a matrix entry");
+}
+// Dual-quaternion palettes: 8 doubles per bone, used as given - neither normalised nor checked for unit length.
+int32_t ft_sg_set_mesh_bones_dq(ft_context* c, ft_node node, const double* dual_quaternions, int32_t n_bones) {
+    return set_palette(c, node, dual_quaternions, n_bones, fth::GraphNode::DualQuaternions, 8, "ft_sg_set_mesh_bones_dq", "dual quaternions", "a dual-quaternion entry");
 }
 int32_t ft_debug_skin(ft_context* c, ft_node node, int64_t counts[4]) {
     if (!c || !counts) return FT_ERR_INVALID;
@@ -429,6 +439,13 @@ int32_t ft_debug_skin(ft_context* c, ft_node node, int64_t counts[4]) {
     for (int k = 0; k < 3; ++k) counts[k] = c->skin.counts[k];
     counts[3] = 0;
     for (const ft_context::Skin::Resident& r : c->skin.meshes) if (r.node == node) counts[3] = (int64_t)(r.used_rest + r.used_skin + r.used_palette);
+    return FT_OK;
+}
+int32_t ft_debug_skin_dq(ft_context* c, ft_node node, int64_t counts[4]) {
+    if (!c || !counts) return FT_ERR_INVALID;
+    if (!c->graph.valid(node) || c->graph.nodes[node].kind != fth::GraphNode::Mesh) { c->err = "ft_debug_skin_dq: not a bspMesh node"; return FT_ERR_INVALID; }
+    for (int k = 0; k < 3; ++k) counts[k] = c->skin.counts_dq[k];
+    counts[3] = c->graph.nodes[node].palette_kind;
     return FT_OK;
 }
 ft_node ft_sg_material(ft_context* c, const ft_material* m, ft_node child) {
@@ -973,7 +990,8 @@ static int32_t morph_device(ft_context* c, const fth::SceneGraph& g, std::vector
             ftk::SkinPose a{};
             a.src = e.blended ? out : s->d_rest.as<double>(); a.out = out; a.index = s->d_index.as<uint32_t>(); a.weight = s->d_weight.as<double>();
             a.palette = s->d_palette.as<double>(); a.corners = n.tris.size() / 3; a.wstride = s->wstride; a.influences = n.skin_influences; a.n_bones = n.n_bones;
-            ftk::skin(c->stream, a);
+            if (n.palette_kind == fth::GraphNode::DualQuaternions) ftk::skin_dq(c->stream, a);   // (the palette holds 8 doubles per bone: DESIGN.md 16.6)
+            else ftk::skin(c->stream, a);
         }
         // (one scan after the other on the stream: they share the partials)
         if (lead) ftk::morph_scan(c->stream, out, (uint32_t)(n.tris.size() / 9), M.d_partials.as<ftk::MorphPartial>(), M.d_out.as<ftk::MorphScanOut>() + k_scan++);
@@ -1747,7 +1765,7 @@ int32_t ft_scene_commit_deformed(ft_context* c) {
     fth::FlatScene& f = c->flat;
     // Host: one pass over every edited mesh - bounds, extent, finiteness - before anything is changed or uploaded.
     std::vector<DeformedMesh> edits;
-    size_t verts_at = 0, n_on_device = 0, n_blended = 0, n_skinned = 0;
+    size_t verts_at = 0, n_on_device = 0, n_blended = 0, n_skinned = 0, n_skinned_dq = 0;
     // ft_debug_morph counts[2]: the meshes this call - whichever way it ends - has the host blend (GraphNode::vertices)
     struct HostBlends {
         ft_context* c; uint64_t before;
@@ -1761,6 +1779,12 @@ int32_t ft_scene_commit_deformed(ft_context* c) {
         explicit HostSkins(ft_context* ctx) : c(ctx), before(total(ctx)) {}
         ~HostSkins() { c->skin.counts[2] = (int64_t)(total(c) - before); }
     } host_skins(c);
+    struct HostSkinsDq {                                            // ft_debug_skin_dq counts[2], the same way
+        ft_context* c; uint64_t before;
+        static uint64_t total(const ft_context* c) { uint64_t n = 0; for (const fth::GraphNode& g : c->graph.nodes) n += g.host_skins_dq; return n; }
+        explicit HostSkinsDq(ft_context* ctx) : c(ctx), before(total(ctx)) {}
+        ~HostSkinsDq() { c->skin.counts_dq[2] = (int64_t)(total(c) - before); }
+    } host_skins_dq(c);
     auto refuse = [c](bool depth) {
         c->err = depth ? "ft_scene_commit_deformed: an edited mesh has depth above 0 - its clipped BSP depends on the positions (ft_scene_commit)"
                        : "ft_scene_commit_deformed: an edited mesh holds a non-finite coordinate (ft_scene_commit)";
@@ -1786,16 +1810,20 @@ int32_t ft_scene_commit_deformed(ft_context* c) {
         DeformedMesh e{m, id, scan};
         e.at = verts_at; e.on_device = on_device; e.blended = blended; e.skinned = skinned;
         verts_at += n.tris.size() + (n.tris.size() & 1);
-        n_on_device += on_device ? 1 : 0; n_blended += blended ? 1 : 0; n_skinned += skinned ? 1 : 0;
+        n_on_device += on_device ? 1 : 0; n_blended += blended ? 1 : 0;
+        const bool dq = n.palette_kind == fth::GraphNode::DualQuaternions;   // (the same route, k_skin_dq, counters of its own)
+        n_skinned += skinned && !dq ? 1 : 0; n_skinned_dq += skinned && dq ? 1 : 0;
         edits.push_back(e);
     }
     double morph_ms[2] = {0.0, 0.0};                                // uploads, kernels with their readbacks
     ft_context::Morph& M = c->morph;
     M.counts[1] = (int64_t)n_blended;
     c->skin.counts[1] = (int64_t)n_skinned;
+    c->skin.counts_dq[1] = (int64_t)n_skinned_dq;
     if (n_on_device) {
         if (n_blended) ++M.counts[0];
         if (n_skinned) ++c->skin.counts[0];
+        if (n_skinned_dq) ++c->skin.counts_dq[0];
         for (ft_context* d : devices(c)) {
             const int32_t mrc = morph_device(d, c->graph, edits, morph_ms, d == c);
             if (mrc != FT_OK) { if (d != c) c->err = d->err; return mrc; }   // (only d_verts has been written: the old commit stands)

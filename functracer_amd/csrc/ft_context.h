@@ -328,6 +328,7 @@ struct ft_context {
         struct Resident { int32_t node; uint64_t skin_serial, rest_serial, wstride; size_t used_skin, used_rest, used_palette; DeviceBuf d_index, d_weight, d_rest, d_palette; };
         std::vector<Resident> meshes;
         int64_t counts[3] = {0, 0, 0};
+        int64_t counts_dq[3] = {0, 0, 0};   // ft_debug_skin_dq's: the same three for dual-quaternion palettes (k_skin_dq)
         uint64_t serials = 0;       // the last value a GraphNode::skin_serial or shape_serial was given
         static void drop(Resident& r) { for (DeviceBuf* b : {&r.d_index, &r.d_weight, &r.d_rest, &r.d_palette}) b->release(); }
         void release() { for (Resident& r : meshes) drop(r); meshes.clear(); }

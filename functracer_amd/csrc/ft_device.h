@@ -275,6 +275,9 @@ void morph_extent(hipStream_t stream, const double* verts, uint32_t n, const dou
 constexpr int kMaxSkinBones = 256, kMaxSkinInfluences = 4;        // FT_MAX_SKIN_BONES, FT_MAX_SKIN_INFLUENCES (ft_capi.cpp asserts them)
 struct SkinPose { const double* src; double* out; const uint32_t* index; const double* weight; const double* palette; uint64_t corners, wstride; int32_t influences, n_bones; };
 void skin(hipStream_t stream, const SkinPose& a);
+// Dual-quaternion skinning (k_skin_dq, ft_sg_set_mesh_bones_dq): the same arguments, posed by fth::skin_blend_dq's
+// arithmetic; palette: n_bones x 8 doubles (real part, then dual part), 16-byte aligned.
+void skin_dq(hipStream_t stream, const SkinPose& a);
 
 // Refit of a light-space shadow tree whose light turned (ft_lightspace.hip, ft_scene_commit_lights).  LsFrame: the pair's new frame and
 // centre as its record holds them (ft_flat.h, kLsPairDoubles) and the builder's inflation, 1e-7 * R + 1e-30.  One call per level of the

@@ -486,14 +486,87 @@ void skin_blend(const double* shape, const uint32_t* index, const double* weight
         out[3 * c] = acc[0]; out[3 * c + 1] = acc[1]; out[3 * c + 2] = acc[2];
     }
 }
+// cross(a, b): two products and one difference per component, each rounded once.
+static inline void cross3(const double a[3], const double b[3], double out[3]) {
+    for (int i = 0; i < 3; ++i) {
+        const int i1 = (i + 1) % 3, i2 = (i + 2) % 3;
+        const double l = a[i1] * b[i2];
+        const double r = a[i2] * b[i1];
+        out[i] = l - r;
+    }
+}
+void skin_blend_dq(const double* shape, const uint32_t* index, const double* weight, int32_t influences, const double* palette, size_t corners, double* out) {
+    for (size_t c = 0; c < corners; ++c) {
+        const double p[3] = {shape[3 * c], shape[3 * c + 1], shape[3 * c + 2]};
+        const double* R0 = palette + 8 * (size_t)(index[c] & 255u);
+        double a[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        for (int32_t j = 0; j < influences; ++j) {
+            const double* D = palette + 8 * (size_t)((index[c] >> (8 * j)) & 255u);
+            const double wj = weight[c * (size_t)influences + (size_t)j];
+            double ws = wj;
+            if (j > 0) {                                            // antipodality: D and -D are the same motion; a NaN g does not negate
+                const double g0 = D[0] * R0[0];
+                const double g1 = D[1] * R0[1];
+                const double g2 = D[2] * R0[2];
+                const double g3 = D[3] * R0[3];
+                double g = g0 + g1;
+                g = g + g2;
+                g = g + g3;
+                ws = g < 0.0 ? -wj : wj;
+            }
+            for (int k = 0; k < 8; ++k) {
+                const double q = ws * D[k];
+                a[k] = j == 0 ? q : a[k] + q;
+            }
+        }
+        const double s0 = a[0] * a[0];
+        const double s1 = a[1] * a[1];
+        const double s2 = a[2] * a[2];
+        const double s3 = a[3] * a[3];
+        double n2 = s0 + s1;
+        n2 = n2 + s2;
+        n2 = n2 + s3;
+        const double n = std::sqrt(n2);
+        const double s = 1.0 / n;
+        double u[8];
+        for (int k = 0; k < 8; ++k) u[k] = a[k] * s;
+        const double w = u[0], e = u[4];
+        const double* v = u + 1;
+        const double* f = u + 5;
+        double vp[3], cc[3], h[3], vf[3];
+        cross3(v, p, vp);
+        for (int i = 0; i < 3; ++i) {
+            const double wp = w * p[i];
+            cc[i] = vp[i] + wp;
+        }
+        cross3(v, cc, h);
+        cross3(v, f, vf);
+        for (int i = 0; i < 3; ++i) {
+            const double wf = w * f[i];
+            const double ev = e * v[i];
+            double m = wf - ev;
+            m = m + vf[i];
+            const double h2 = 2.0 * h[i];
+            const double m2 = 2.0 * m;
+            double t = p[i] + h2;
+            t = t + m2;
+            out[3 * c + i] = t;
+        }
+    }
+}
 const std::vector<double>& GraphNode::vertices() const {
     if (n_bones == 0) return shape();
     if (posed_stale || (by_weights && tris_stale) || posed.size() != tris.size()) {
         const std::vector<double>& U = shape();
         posed.resize(U.size());
-        skin_blend(U.data(), skin_index.data(), skin_weight.data(), skin_influences, palette.data(), U.size() / 3, posed.data());
+        if (palette_kind == DualQuaternions) {
+            skin_blend_dq(U.data(), skin_index.data(), skin_weight.data(), skin_influences, palette.data(), U.size() / 3, posed.data());
+            ++host_skins_dq;
+        } else {
+            skin_blend(U.data(), skin_index.data(), skin_weight.data(), skin_influences, palette.data(), U.size() / 3, posed.data());
+            ++host_skins;
+        }
         posed_stale = false;
-        ++host_skins;
     }
     return posed;
 }

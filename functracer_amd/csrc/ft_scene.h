@@ -36,13 +36,18 @@ struct GraphNode {
     std::vector<uint32_t> skin_index;
     std::vector<double> skin_weight, palette;
     int32_t skin_influences = 0, skin_max_index = 0, n_bones = 0;
+    // palette_kind: what `palette` holds while n_bones > 0 - Matrices as above, or DualQuaternions (ft_sg_set_mesh_bones_dq):
+    // n_bones x 8, real part (w, x, y, z) then dual part per bone.  A node holds at most one palette.
+    enum PaletteKind : int32_t { NoPalette = 0, Matrices = 1, DualQuaternions = 2 };
+    int32_t palette_kind = NoPalette;
     uint64_t skin_serial = 0, shape_serial = 0;
     mutable std::vector<double> posed;   // skin(shape(), palette) while a palette is in force and not `posed_stale`
     mutable bool posed_stale = false;
     mutable uint64_t host_skins = 0;  // times vertices() has skinned them on the host (ft_debug_skin counts[2])
+    mutable uint64_t host_skins_dq = 0;   // the same for a dual-quaternion palette (ft_debug_skin_dq counts[2])
     // The shape U as it stands: `tris`, blended first where the weights describe them (morph_blend's arithmetic).
     const std::vector<double>& shape() const;
-    // The vertices V as they stand: the shape, skinned first where a palette is in force (skin_blend's arithmetic).
+    // The vertices V as they stand: the shape, skinned first where a palette is in force (skin_blend's / skin_blend_dq's arithmetic).
     const std::vector<double>& vertices() const;
     std::vector<ft_transform> xf;     // Transform: one basic transform or a Composed list
     ft_material mat{};                // MaterialF
@@ -123,6 +128,12 @@ void morph_blend(const double* base, const double* deltas, const double* w, int3
 // q_i = wj * t_i, acc_i = j == 0 ? q_i : acc_i + q_i; every influence evaluated, every product and sum rounded once (-ffp-contract=off).
 // out may not alias shape.
 void skin_blend(const double* shape, const uint32_t* index, const double* weight, int32_t influences, const double* palette, size_t corners, double* out);
+// Dual-quaternion skinning: the same arguments, palette = n_bones x 8 (real part w, x, y, z, then the dual part).  Per corner p, with R0 the
+// real part of slot 0's bone: for j in order D = palette + 8 * b, g = ((D0*R0_0 + D1*R0_1) + D2*R0_2) + D3*R0_3 (j > 0), ws = g < 0 ? -wj : wj
+// (slot 0: wj), a_k = j == 0 ? ws * D_k : a_k + ws * D_k; n = sqrt(((a0*a0 + a1*a1) + a2*a2) + a3*a3), s = 1 / n, u = a * s; with w = u0,
+// v = u1..3, e = u4, f = u5..7: c = cross(v, p) + w*p, h = cross(v, c), m = (w*f - e*v) + cross(v, f), V = (p + 2h) + 2m - the header's
+// formula ("dual-quaternion skinning"), every product, sum, difference, square root and division rounded once (-ffp-contract=off).
+void skin_blend_dq(const double* shape, const uint32_t* index, const double* weight, int32_t influences, const double* palette, size_t corners, double* out);
 
 struct SceneGraph {
     std::vector<GraphNode> nodes;

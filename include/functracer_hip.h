@@ -863,6 +863,67 @@ int32_t ft_debug_morph(ft_context* ctx, ft_node mesh, int64_t counts[4], double 
 int32_t ft_sg_set_mesh_skin(ft_context* ctx, ft_node mesh, const int32_t* bone_index, const double* bone_weight, int32_t influences, int64_t n_tris);
 int32_t ft_sg_set_mesh_bones(ft_context* ctx, ft_node mesh, const double* matrices, int32_t n_bones);
 int32_t ft_debug_skin(ft_context* ctx, ft_node mesh, int64_t counts[4]);
+/* ---- dual-quaternion skinning: a second kind of palette for the same skin ---------------------- */
+/* Linear-blend skinning collapses the surface between two bones that twist against each other (the blended matrix is no rotation).  A
+ * node that carries a skin (ft_sg_set_mesh_skin, unchanged) may instead be posed by a palette of unit dual quaternions (Kavan et al.
+ * 2008), whose normalised blend is always a rigid motion.
+ * ft_sg_set_mesh_bones_dq(mesh, dual_quaternions, n_bones): dual_quaternions = n_bones x 8 doubles, copied; per bone the real part
+ * (rw, rx, ry, rz), then the dual part (dw, dx, dy, dz).  The rigid motion "rotate by the unit quaternion r, then translate by t" has
+ * real part r and dual part 0.5 * (0, t) (x) r (quaternion product).  Scale and shear cannot be expressed.  The call declares
+ * V = skin_dq(U, palette), marks the node as ft_sg_set_mesh_triangles does, leaves the scene uncommitted and is not structural.
+ * A node holds at most one palette: ft_sg_set_mesh_bones_dq replaces a matrix palette, ft_sg_set_mesh_bones replaces a dual-quaternion
+ * one, n_bones = 0 through either call removes whichever palette is in force (the pointer may be null; V is U again and the node is
+ * marked deformed), and ft_sg_set_mesh_skin removes either kind.  Nodes that never see this call behave exactly as before.
+ * FT_ERR_INVALID, with nothing changed, for the cases of ft_sg_set_mesh_bones: a null context, an invalid handle, a node that is not a
+ * bspMesh node, a node without a skin, n_bones outside 0 .. FT_MAX_SKIN_BONES, 0 < n_bones <= the largest index the skin uses, null
+ * data with n_bones > 0 or an entry that is not finite.  The library does not normalise the input and does not check unit length; the
+ * blend is normalised, as the formula says.
+ * The formula, per corner with shape position p = (x, y, z), in IEEE double; every product, sum, difference, square root and division is
+ * rounded once and never fused, sums run left to right as written, negation and multiplication by 2 are exact:
+ *     R0 = real part of palette[index[corner][0]]
+ *     for j = 0 .. J-1 in order, D = palette[index[corner][j]] (8 values), wj = weight[corner][j]:
+ *         if j == 0:  ws = wj
+ *         else:       g = ((D.rw*R0.rw + D.rx*R0.rx) + D.ry*R0.ry) + D.rz*R0.rz
+ *                     ws = (g < 0) ? -wj : wj          (antipodality: D and -D are the same motion; a NaN g does not negate)
+ *         q_k = ws * D_k                                (k = 0 .. 7)
+ *         a_k = (j == 0) ? q_k : a_k + q_k
+ *     n2 = ((a_0*a_0 + a_1*a_1) + a_2*a_2) + a_3*a_3;   n = sqrt(n2);   s = 1.0 / n;   u_k = a_k * s   (k = 0 .. 7)
+ *     w = u_0, v = (u_1, u_2, u_3), e = u_4, f = (u_5, u_6, u_7)
+ *     cross(a, b)_x = a_y*b_z - a_z*b_y   (two products, one difference; y and z cyclic)
+ *     c_i = cross(v, p)_i + w*p_i
+ *     h   = cross(v, c)
+ *     m_i = (w*f_i - e*v_i) + cross(v, f)_i
+ *     V_i = (p_i + 2*h_i) + 2*m_i
+ * Every influence is evaluated, zero weights included.  Two corners with bitwise equal shape positions, indices and weights come out
+ * bitwise equal: a mesh that is welded in its rest pose stays welded in every pose.  A blend whose real part is zero gives s = inf and a
+ * NaN V: ft_scene_commit_deformed then refuses the call ("an edited mesh holds a non-finite coordinate") and leaves the old commit
+ * renderable, as for any non-finite vertex.
+ * Everything else is as said under "skinning" for matrices, with V = skin_dq(U, palette): the other setters (ft_sg_set_mesh_triangles and
+ * ft_sg_set_mesh_weights change U and the palette stays in force; ft_sg_set_mesh_targets takes U as its base - blend the shape, then skin
+ * it), the promise (ft_sg_set_mesh_bones_dq(node, P) followed by any commit gives every bit that ft_sg_set_mesh_triangles(node, V) gives
+ * on a twin node without a skin followed by the same commit - frames, ft_stats (times aside), ft_render_aov, the ft_debug_* ray queries,
+ * ft_debug_mesh_trees - hence the refusals, the open temporal accumulation, "temporal_follow_deformed", "refit_rebuild_percent",
+ * "deform_light_space", "light_space_retree", morph targets under the skin, several devices), and the device route of
+ * ft_scene_commit_deformed under exactly the same conditions ("skin_on_device" 1, a device context, U explicit or blended on the device in
+ * the same call): the index words, the weights and the rest shape stay resident as they are - switching the palette kind uploads none of
+ * them again - the palette (n_bones x 64 bytes, at most 16 KiB) is uploaded per pose inside ft_get_commit_times [2], and k_skin_dq
+ * (ft_skin.hip) runs where k_skin runs for matrices.  With the option at 0, on a host-only context and in every other commit the host
+ * makes V by the formula when the vertices are needed.
+ * ft_debug_skin_dq(mesh, counts), for tests and tools: counts[0] = ft_scene_commit_deformed calls since ft_create that posed at least one
+ * mesh with k_skin_dq on the device, counts[1] = meshes posed that way in the last ft_scene_commit_deformed, counts[2] = meshes whose
+ * dual-quaternion skin the host made in it, counts[3] = the palette kind in force for `mesh` (0 none, 1 matrices, 2 dual quaternions).
+ * ft_debug_skin keeps its meaning for matrix palettes - its first three counters count matrix skins alone - and its counts[3] counts
+ * n_bones x 64 bytes for a dual-quaternion palette where it counts n_bones x 96 for matrices.  FT_ERR_INVALID for a null context or
+ * pointer, an invalid handle or a node that is not a bspMesh node.
+ * What it is worth (MI355X, the 69.6 K-face mesh, nothing in flight, tools/skin_rate.py --dq): the commit of a pose set by
+ * dual quaternions takes 0.33 ms ([0] 0.004, [1] 0.28, [2] 0.05 ms) whatever J and the bone count, as for matrices; k_skin_dq itself runs
+ * 6.5 - 8.8 microseconds, no slower than k_skin (it is bound by memory, and its palette is a third smaller).  The whole step (make the
+ * palette, set it, commit) takes 0.40 / 0.45 / 0.56 ms at J = 4 with 4 / 64 / 256 bones, against 32.3 / 32.4 / 32.3 ms for a host that
+ * skins in numpy and 5.09 / 5.13 / 5.23 ms with "skin_on_device" 0 (the library's host skin in [0]: 2.4 ms at J = 1, 4.6 ms at J = 4).
+ * The device route's whole step lies below the numpy host's by more than both spreads at every row measured (J = 1 and 4; 4, 64 and 256
+ * bones), so the default stays 1. */
+int32_t ft_sg_set_mesh_bones_dq(ft_context* ctx, ft_node mesh, const double* dual_quaternions, int32_t n_bones);
+int32_t ft_debug_skin_dq(ft_context* ctx, ft_node mesh, int64_t counts[4]);
 /* ---- moving lights ----------------------------------------------------------------------------- */
 /* ft_scene_set_directional / _soft_directional / _positional + ft_scene_commit_lights change the lights of a committed scene without a
  * flatten, without a BVH build and without ending ft_temporal_*.

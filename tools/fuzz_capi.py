@@ -34,7 +34,7 @@ stats = {"graphs": 0, "committed": 0, "refused": 0}
 t_end = time.time() + budget
 while time.time() < t_end:
     ctx.clear()
-    nodes = []
+    nodes, meshes = [], {}
 
     def pick():
         if not nodes: nodes.append(ctx.primitive(ft.SPHERE))
@@ -43,10 +43,13 @@ while time.time() < t_end:
 
     try:
         for _ in range(rng.randint(1, 25)):
-            k = rng.randrange(12)
+            k = rng.randrange(13)
             if k == 0: n = ctx.primitive(rng.choice([ft.SPHERE, ft.PLANE, ft.CUBE, ft.CONE, ft.CYLINDER, 0, 99, -3]))
             elif k == 1: n = ctx.triangle(vec(), vec(), vec())
-            elif k == 2: n = ctx.bsp_mesh(rng.choice([0, 1, 3, 6, -1, 40]), tris(rng.choice([0, 1, 2, 7, 40])))
+            elif k == 2:
+                count = rng.choice([0, 1, 2, 7, 40])
+                n = ctx.bsp_mesh(rng.choice([0, 1, 3, 6, -1, 40]), tris(count))
+                meshes[n] = count
             elif k == 3: n = ctx.translate(vec(), pick())
             elif k == 4: n = ctx.scale(rng.choice([num(), vec()]), pick())
             elif k == 5: n = ctx.rotate(vec(), num(), pick())
@@ -55,6 +58,21 @@ while time.time() < t_end:
             elif k == 8: n = ctx.csg(rng.choice([0, 1, 2, 3, 4, -1, 17]), pick(), pick())
             elif k == 9: n = ctx.texture_grid(vec(), vec(), [(rng.randrange(-1, 4), num(), num()) for _ in range(rng.randint(0, 7))], pick())
             elif k == 10: n = ctx.hue_shift(num(), pick())
+            elif k == 12:                                            # a skin and a dual-quaternion palette on a mesh (or on what is none)
+                n = rng.choice(list(meshes)) if meshes and rng.random() < 0.9 else pick()
+                count, J, bones = meshes.get(n, rng.choice([0, 3])), rng.choice([0, 1, 2, 4, 4, 5]), rng.choice([0, 1, 2, 5, 256, 257])
+                try:
+                    index = nrng.integers(-1 if rng.random() < 0.1 else 0, max(bones, 1) + (rng.random() < 0.1), size=(count + (rng.random() < 0.05), 3, J))
+                    ctx.set_mesh_skin(n, index, nrng.normal(size=index.shape) * rng.choice([1.0, 1.0, 0.0, 1e300]))
+                    d = nrng.normal(size=(bones, 8))
+                    if bones and rng.random() < 0.2: d[rng.randrange(bones), rng.randrange(8)] = rng.choice(odd)
+                    if bones and rng.random() < 0.2: d[rng.randrange(bones), :4] = 0.0   # a zero real part: NaN vertices, refused at the commit
+                    ctx.set_mesh_bones_dq(n, d)
+                    if rng.random() < 0.3: ctx.set_mesh_bones(n, nrng.normal(size=(bones, 12)))
+                    if rng.random() < 0.3: ctx.skin_dq(n)
+                except (ft.FtError, ValueError):
+                    pass
+                continue
             else: n = ctx.texture_image(nrng.integers(0, 256, size=(rng.randint(1, 4), rng.randint(1, 4), 3), dtype=np.uint8), [], pick())
             nodes.append(n)
         ctx.set_objects(pick())

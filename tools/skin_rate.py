@@ -13,6 +13,9 @@ Rows: J = 1 and 4 with 4, 64 and 256 bones; J = 4, 64 bones under "deform_light_
 Per way and row: median (min - max) of ft_get_commit_times [0] host / [1] kernels / [2] uploads of the commits, and of the wall time of
 the whole step { make the pose, hand it over, commit_deformed }.  The first pose of (c) uploads the resident arrays and is reported apart.
 --device-only: route (c) alone on three rows, for a kernel trace of k_skin.
+--dq: the six J x bones rows for dual-quaternion palettes: the same bones and poses as unit dual quaternions, (a) skins
+with functracer_amd.skin_blend_dq, (b) and (c) call set_mesh_bones_dq.  With --device-only: route (c) of both palette kinds on the three
+rows, for one kernel trace of k_skin_dq beside k_skin.
 Prints one JSON line; run on the GPU box."""
 import json, os, statistics, sys, time
 import numpy as np
@@ -58,7 +61,15 @@ def palette(c, n_bones, pose):
     return out.reshape(n_bones, 12)
 
 
-def run(tris, influences, n_bones, light_space, k_targets, ways):
+def palette_dq(c, n_bones, pose):
+    """The same motions as unit dual quaternions: a turn about y through c is the rotation and the translation c - A c."""
+    ang = np.array([0.6 * np.sin(0.4 * pose) * (b + 1) / n_bones for b in range(n_bones)])
+    r = np.stack([np.cos(0.5 * ang), np.zeros(n_bones), np.sin(0.5 * ang), np.zeros(n_bones)], axis=1)
+    t = np.stack([c[0] - (np.cos(ang) * c[0] + np.sin(ang) * c[2]), np.zeros(n_bones), c[2] - (-np.sin(ang) * c[0] + np.cos(ang) * c[2])], axis=1)
+    return ft.dual_quaternions(r, t)
+
+
+def run(tris, influences, n_bones, light_space, k_targets, ways, dq=False):
     index, weight = skin_of(tris, influences, n_bones)
     targets = np.stack([twisted(tris, 2 * (k + 1)) for k in range(k_targets)]) if k_targets else None
     deltas = targets - tris if k_targets else None
@@ -82,18 +93,18 @@ def run(tris, influences, n_bones, light_space, k_targets, ways):
         for way in ways:
             ctx = ctxs[way]
             t0 = time.perf_counter()
-            bones = palette(centre, n_bones, pose)                   # (every way makes its own palette: part of the step)
+            bones = (palette_dq if dq else palette)(centre, n_bones, pose)   # (every way makes its own palette: part of the step)
             if way == "a":
                 shape = tris
                 if k_targets:
                     shape = tris.copy()
                     for k in range(k_targets):
                         shape = shape + w[k] * deltas[k]
-                ctx.set_mesh_triangles(mesh[way], ft.skin_blend(shape, index, weight, bones))
+                ctx.set_mesh_triangles(mesh[way], (ft.skin_blend_dq if dq else ft.skin_blend)(shape, index, weight, bones))
             else:
                 if k_targets:
                     ctx.set_mesh_weights(mesh[way], w)
-                ctx.set_mesh_bones(mesh[way], bones)
+                (ctx.set_mesh_bones_dq if dq else ctx.set_mesh_bones)(mesh[way], bones)
             ctx.commit_deformed()
             wall = (time.perf_counter() - t0) * 1e3
             t = ctx.commit_times()
@@ -109,6 +120,8 @@ def run(tris, influences, n_bones, light_space, k_targets, ways):
         ta, tc = ctxs["a"].mesh_trees(), ctxs["c"].mesh_trees()
         same = all(np.array_equal(ta[k].view(np.uint8), tc[k].view(np.uint8)) for k in ("tris", "wide", "coarse_boxes"))
     skin = ctxs["c"].skin(mesh["c"]) if "c" in ways else None
+    if skin and dq:
+        skin["device_commits"] = ctxs["c"].skin_dq(mesh["c"])["device_commits"]
     for c in ctxs.values():
         c.close()
     out = {way: {key: stats(v) for key, v in r.items()} for way, r in rows.items()}
@@ -129,9 +142,19 @@ def main():
     out = {"faces": int(tris.shape[0]), "poses": POSES, "library": os.path.basename(ft.HIP_LIB),
            "ways": {"a": "numpy skin + set_mesh_triangles", "b": "bones, skin_on_device 0", "c": "bones, skin_on_device 1"},
            "columns": {"flatten_ms": "[0] host", "device_bvh_ms": "[1] kernels and readbacks", "upload_ms": "[2] uploads"}, "rows": {}}
+    dq = "--dq" in sys.argv
+    if dq:
+        out["palette"] = "dual quaternions"
+        out["ways"] = {"a": "numpy skin_blend_dq + set_mesh_triangles", "b": "bones_dq, skin_on_device 0", "c": "bones_dq, skin_on_device 1"}
     if "--device-only" in sys.argv:
         for influences, n_bones in ((1, 4), (4, 64), (4, 256)):
             out["rows"][f"J{influences}_bones{n_bones}"] = run(tris, influences, n_bones, 0, 0, ("c",))
+            if dq:
+                out["rows"][f"J{influences}_bones{n_bones}_dq"] = run(tris, influences, n_bones, 0, 0, ("c",), dq=True)
+    elif dq:
+        for influences in (1, 4):
+            for n_bones in (4, 64, 256):
+                out["rows"][f"J{influences}_bones{n_bones}"] = run(tris, influences, n_bones, 0, 0, ("a", "b", "c"), dq=True)
     else:
         for influences in (1, 4):
             for n_bones in (4, 64, 256):
