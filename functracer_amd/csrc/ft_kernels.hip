@@ -2876,7 +2876,7 @@ FT_DEV void resolve_grouped(const ResolveArgs& a, uint32_t n_pix, double* T, Sta
                 for (uint32_t k = 0; k < G; ++k) T[k * row + lane] = v[p][k];
                 wave_sync();
 #pragma unroll
-                for (uint32_t ds = 0; ds < G; ++ds) { const double x = T[mine + (ds << pw)]; sum[p] += x; if (SQ) sq[p] += x * x; }
+                for (uint32_t ds = 0; ds < G; ++ds) { const double x = T[mine + (ds << pw)]; sum[p] += x; if (SQ) { const double xx = x * x; sq[p] += xx; } }   // the square rounded on its own (no fma)
                 wave_sync();
             }
         }
@@ -2899,7 +2899,7 @@ FT_DEV void resolve_body(const ResolveArgs& a, Start&& start, Emit&& emit, Untra
             for (int k = 0; k < a.spp; ++k) {
                 const size_t i = (size_t)k * n_pix + q;
 #pragma unroll
-                for (int c = 0; c < 3; ++c) { const double x = a.acc[(size_t)c * a.acc_stride + i]; s[c] += x; if (SQ) sq[c] += x * x; }
+                for (int c = 0; c < 3; ++c) { const double x = a.acc[(size_t)c * a.acc_stride + i]; s[c] += x; if (SQ) { const double xx = x * x; sq[c] += xx; } }   // the square rounded on its own (no fma)
             }
             emit(q, s, sq);
         }
@@ -2954,7 +2954,9 @@ FT_DEV void progressive_out(const ResolveArgs& a, const ProgressiveArgs& pa, uin
         bool within = (word & ~kRetired) >= pa.min_samples;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            const double m = s[c] / dn, v0 = sq[c] / dn - m * m, v = (v0 < 0.0 ? 0.0 : v0) * dn / (dn - 1.0);
+            const double m = s[c] / dn;
+            const double mm = m * m;                                // a statement of its own, as in k_denoise_scatter: nothing for -ffp-contract=on to fuse
+            const double v0 = sq[c] / dn - mm, v = (v0 < 0.0 ? 0.0 : v0) * dn / (dn - 1.0);
             within = within && sqrt(v / dn) <= pa.tolerance;
         }
         if (__ballot(!within) == 0ull) word |= kRetired;

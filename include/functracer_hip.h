@@ -317,6 +317,8 @@ int32_t ft_render_wait(ft_context* ctx, ft_stats* stats);
  *  - Retirement (tolerance > 0): after each pass, per pixel and channel var = max(0, Q/n - (S/n)^2) * n / (n - 1) and se = sqrt(var / n),
  *    with Q the running sum of squares.  A 64-pixel block (an 8x8 tile of the list) retires when n >= min_samples and the largest se of
  *    its 64 pixels and 3 channels is <= tolerance.  Retirement is final: a retired block is never traced again and its S, Q, n stay.
+ *    Q adds each sample's square rounded on its own, and every operation of var and se is rounded on its own (nothing is fused): the
+ *    device judges a block by exactly the se ft_progressive_fetch reports for it.
  *  - Lifetime: one accumulation per context; a caller's ft_scene_commit or ft_scene_clear ends it (the next pass returns FT_ERR_STATE, as a
  *    pass without a begin does).  The re-commit by which a blocking call grows the CSG hit lists does not: the pass that overflowed leaves no
  *    trace and runs again.  ft_render calls between passes are allowed and change nothing accumulated.  A pass retires queued frames first,
