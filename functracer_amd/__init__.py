@@ -74,7 +74,7 @@ def hip_lib():
         if hasattr(lib, _capi.MOVED_COMMITS_SIGNATURE[0]):          # (FT_HIP_LIB may name an older build, as above)
             fn = getattr(lib, _capi.MOVED_COMMITS_SIGNATURE[0])
             fn.restype, fn.argtypes = _capi.MOVED_COMMITS_SIGNATURE[1:]
-        for name, res, args in _capi.POSE_QUEUE_SIGNATURES + _capi.MORPH_SIGNATURES + _capi.SKIN_SIGNATURES + _capi.SKIN_DQ_SIGNATURES:
+        for name, res, args in _capi.POSE_QUEUE_SIGNATURES + _capi.DEFORM_QUEUE_SIGNATURES + _capi.MORPH_SIGNATURES + _capi.SKIN_SIGNATURES + _capi.SKIN_DQ_SIGNATURES:
             if hasattr(lib, name):                                  # (FT_HIP_LIB may name an older build, as above)
                 fn = getattr(lib, name)
                 fn.restype, fn.argtypes = res, args
@@ -845,6 +845,27 @@ class Context(SceneBuilder):
         out = (C.c_int64 * 8)()
         self._check(self._lib.ft_debug_pose_queue(self._ctx, out))
         return dict(zip(_capi.POSE_QUEUE_FIELDS, (int(v) for v in out)))
+
+    # queued deform commits (include/functracer_hip.h) --------------------------------------------------
+    def commit_deformed_enqueue(self):
+        """ft_scene_commit_deformed_enqueue: commit_deformed, but nothing queued is retired and no stream a frame runs on is waited for: the
+        refit goes into a copy of the mesh trees that no frame in flight reads.  Frames and temporal calls queued before the call show the
+        old vertices, everything queued or run after it the new ones, bit for bit a fresh context's.  Every kind of edit can be queued -
+        set_mesh_triangles, weights, matrix or dual-quaternion palettes, their host twins.  Takes the blocking path, with its bits and
+        its draining, when it cannot queue (deform_queue tells why)."""
+        self._check(self._lib.ft_scene_commit_deformed_enqueue(self._ctx))
+        self._progressive = None
+
+    def deform_queue(self):
+        """ft_debug_deform_queue: a dict of `queued`, `blocking`, `reason` (of the last commit_deformed_enqueue: 0 queued, 1 host-only
+        context, 2 several devices, 3 the first refit since a full commit, 4 "refit_rebuild_percent" above 0, 5 "deform_light_space" gives
+        an edited mesh a light-space job, 6 "temporal_follow_deformed" with an accumulation that has accumulated), `sets` (geometry sets on
+        the first device), `pending` (frames + temporal calls the host still had pending there when the last call returned),
+        `retired_for_set` (frames or temporal calls retired because every set was held) and `carried` (mesh ranges copied between sets
+        by the last call)."""
+        out = (C.c_int64 * 8)()
+        self._check(self._lib.ft_debug_deform_queue(self._ctx, out))
+        return dict(zip(_capi.DEFORM_QUEUE_FIELDS, (int(v) for v in out)))
 
     def tree_quality(self, node):
         """ft_scene_tree_quality: the measured surface-area cost of the tree of the `bsp_mesh(0, tris)` node as it lies in device memory.

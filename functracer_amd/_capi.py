@@ -139,6 +139,15 @@ POSE_QUEUE_SIGNATURES = [
 POSE_QUEUE_FIELDS = ("moved_queued", "moved_blocking", "moved_reason", "lights_queued", "lights_blocking", "lights_reason", "sets", "pending")
 POSE_QUEUED, POSE_HOST_ONLY, POSE_PENDING, POSE_DIFFERS, POSE_PAIR_CHANGED = 0, 1, 2, 3, 4
 POSE_SETS_MAX = 9       # frame slots + FT_TEMPORAL_QUEUE_DEPTH + 1
+# ft_scene_commit_deformed_enqueue / ft_debug_deform_queue (include/functracer_hip.h, "queued deform commits"): the hook's eight values,
+# in order, and the reasons a call took the blocking path
+DEFORM_QUEUE_SIGNATURES = [
+    ("ft_scene_commit_deformed_enqueue", C.c_int32, [C.c_void_p]),
+    ("ft_debug_deform_queue", C.c_int32, [C.c_void_p, C.POINTER(C.c_int64)]),
+]
+DEFORM_QUEUE_FIELDS = ("queued", "blocking", "reason", "sets", "pending", "retired_for_set", "carried", "reserved")
+(DEFORM_QUEUED, DEFORM_HOST_ONLY, DEFORM_MULTI_DEVICE, DEFORM_FIRST_REFIT, DEFORM_REBUILD, DEFORM_LIGHT_SPACE, DEFORM_TEMPORAL_FOLLOW) = range(7)
+GEO_SETS_MAX = 9        # frame slots + FT_TEMPORAL_QUEUE_DEPTH + 1
 
 
 # Deforming meshes (include/functracer_hip.h): new vertices for an existing bspMesh node, committed by a refit of its tree on the device.

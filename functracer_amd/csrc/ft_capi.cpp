@@ -75,6 +75,7 @@ int32_t drain_frame_streams(ft_context* c) {
     FT_HIP(c, hipStreamSynchronize(c->stream));
     for (hipStream_t m : c->more_mains) if (m) FT_HIP(c, hipStreamSynchronize(m));
     FT_HIP(c, hipStreamSynchronize(c->tail));
+    if (c->geo.deform) FT_HIP(c, hipStreamSynchronize(c->geo.deform));   // a queued refit may still write the live geometry set
     return FT_OK;
 }
 size_t lds_bytes_for(const fth::FlatScene& f) { return lds_bytes_at(f, std::max(1, lane_fold_for(f))); }
@@ -149,6 +150,7 @@ void ft_destroy(ft_context* c) {
         if (c->side) (void)hipStreamSynchronize(c->side);
         if (c->pose.copies) (void)hipStreamSynchronize(c->pose.copies);
         c->pose.release();
+        c->geo.release();
         for (DeviceBuf& b : c->d_scene) b.release();
         for (DeviceBuf& b : c->d_rays) b.release();
         for (DeviceBuf& b : c->d_acc) b.release();
@@ -592,8 +594,8 @@ static void cull_items_image(const fth::FlatScene& f, std::vector<float>& v) {
 // The ranges of a device job in the context's scene arrays, as ft_bvh.hip takes them.
 static ftk::LbvhTarget lbvh_target(ft_context* c, const fth::FlatScene::BvhJob& j) {
     const DeviceBuf* B = c->d_scene;
-    return ftk::LbvhTarget{B[kTris].as<double>(), j.first_global, j.n, B[kNodes].as<ftd::BspNode>(), j.node_base, B[kBspLeaves].as<ftd::BspLeaf>(), j.leaf_base,
-                           B[kTriOrig].as<uint32_t>(), j.tri_base, B[kWide].as<double>(), j.wide_base, B[kCoarse].as<float>() + 6 * (size_t)j.coarse_first, j.coarse_count,
+    return ftk::LbvhTarget{geo_array(c, kTris).as<double>(), j.first_global, j.n, geo_array(c, kNodes).as<ftd::BspNode>(), j.node_base, B[kBspLeaves].as<ftd::BspLeaf>(), j.leaf_base,
+                           B[kTriOrig].as<uint32_t>(), j.tri_base, geo_array(c, kWide).as<double>(), j.wide_base, geo_array(c, kCoarse).as<float>() + 6 * (size_t)j.coarse_first, j.coarse_count,
                            B[kTriSrc].as<uint32_t>()};
 }
 
@@ -692,6 +694,9 @@ static int32_t upload_scene(ft_context* c) {
     // frame and temporal call has been retired, and an upload nobody has read yet ends here)
     if (c->pose.copies) FT_HIP(c, hipStreamSynchronize(c->pose.copies));
     c->pose.free_spares();
+    // and to geometry set 0, the same way (a queued refit nobody has read yet ends here)
+    if (c->geo.deform) FT_HIP(c, hipStreamSynchronize(c->geo.deform));
+    c->geo.free_spares();
     c->refit.ready = false;                                         // the trees these uploads bring are not the ones its tables describe
     c->lightspace.reset();                                          // nor the light-space trees ft_scene_commit_lights' tables describe
     ftk::DevScene& S = c->dev_scene;
@@ -804,12 +809,13 @@ static const fth::FlatScene::BvhJob* job_of(const fth::FlatScene& f, uint32_t me
     for (const fth::FlatScene::BvhJob& j : f.bvh_jobs) if (j.mesh == mesh) return &j;
     return nullptr;
 }
-// The scene's arrays in HBM and, once a refit has made them, the refit's own tables.
+// The scene's arrays in HBM - of what a refit rewrites, the live geometry set's (geo_array) - and, once a refit has made them, the
+// refit's own tables.
 static ftk::RefitArrays refit_arrays(ft_context* c) {
     DeviceBuf* B = c->d_scene;
     ft_context::Refit& R = c->refit;
-    return ftk::RefitArrays{B[kTris].as<double>(), B[kNodes].as<ftd::BspNode>(), B[kBspLeaves].as<ftd::BspLeaf>(), B[kTriOrig].as<uint32_t>(), B[kWide].as<double>(),
-                            B[kCoarse].as<float>(), R.d_wide_node.as<int32_t>(), R.d_parent_node.as<int32_t>(), R.d_parent_leaf.as<int32_t>(), R.d_arrived.as<uint32_t>(),
+    return ftk::RefitArrays{geo_array(c, kTris).as<double>(), geo_array(c, kNodes).as<ftd::BspNode>(), B[kBspLeaves].as<ftd::BspLeaf>(), B[kTriOrig].as<uint32_t>(), geo_array(c, kWide).as<double>(),
+                            geo_array(c, kCoarse).as<float>(), R.d_wide_node.as<int32_t>(), R.d_parent_node.as<int32_t>(), R.d_parent_leaf.as<int32_t>(), R.d_arrived.as<uint32_t>(),
                             R.d_leaf_boxes.as<double>()};
 }
 
@@ -848,9 +854,9 @@ static int32_t rebuild_in_place(ft_context* c, const fth::FlatScene& f, const ft
     DeviceBuf* B = c->d_scene;
     ft_context::Refit& R = c->refit;
     const fth::FlatScene::JobSpans sp = fth::FlatScene::reserved_spans(j);
-    FT_HIP(c, hipMemsetAsync(B[kNodes].as<ftd::BspNode>() + sp.node_first, 0, sp.node_count * sizeof(ftd::BspNode), c->stream));
+    FT_HIP(c, hipMemsetAsync(geo_array(c, kNodes).as<ftd::BspNode>() + sp.node_first, 0, sp.node_count * sizeof(ftd::BspNode), c->stream));
     FT_HIP(c, hipMemsetAsync(B[kBspLeaves].as<ftd::BspLeaf>() + sp.leaf_first, 0, sp.leaf_count * sizeof(ftd::BspLeaf), c->stream));
-    FT_HIP(c, hipMemsetAsync(B[kWide].as<double>() + ftd::kWideNodeDoubles * sp.wide_first, 0, sp.wide_count * ftd::kWideNodeDoubles * 8, c->stream));
+    FT_HIP(c, hipMemsetAsync(geo_array(c, kWide).as<double>() + ftd::kWideNodeDoubles * sp.wide_first, 0, sp.wide_count * ftd::kWideNodeDoubles * 8, c->stream));
     FT_HIP(c, ftk::build_lbvh(c->stream, lbvh_target(c, j), height, c->opt.bvh_builder == 1 ? 0 : 1));
     if (*height == 0 || *height > 40) { c->err = "ft_scene_commit_deformed: the rebuild in place was refused (a tree deeper than 40 levels): ft_scene_commit"; return FT_ERR_BUILD; }
     FT_HIP(c, hipMemsetAsync(R.d_parent_node.as<int32_t>() + sp.node_first, 0xFF, sp.node_count * 4, c->stream));
@@ -886,7 +892,7 @@ static int32_t snapshot_records(ft_context* c, const fth::FlatScene& f, const st
         T.d_snap.release();
         T.d_snap = grown;
     }
-    const double* tris = c->d_scene[kTris].as<double>();
+    const double* tris = geo_array(c, kTris).as<double>();
     for (const ft_context::Temporal::Snapshot& s : fresh) {
         const ftk::RefitMesh m = refit_ranges(f, s.mesh, 0.0);
         FT_HIP(c, hipMemcpyAsync(T.d_snap.as<double>() + 9 * (size_t)s.first, tris + 9 * (size_t)m.first_global, (size_t)s.n * 72, hipMemcpyDeviceToDevice, c->stream));
@@ -894,6 +900,24 @@ static int32_t snapshot_records(ft_context* c, const fth::FlatScene& f, const st
     }
     T.snap_used = need;
     return FT_OK;
+}
+
+// The page-locked block of a queued call (ft_context::GeoSets::staging): what the call's asynchronous copies take from the host passes
+// through it, one piece behind the other on 16 bytes.  The caller has sized it (stage_begin).
+struct Stager {
+    char* base = nullptr; size_t used = 0, cap = 0;
+    const void* put(const void* src, size_t bytes) {
+        if (bytes > cap - used) return src;                         // (never: stage_begin counted the same pieces)
+        char* at = base + used;
+        std::memcpy(at, src, bytes);
+        used += (bytes + 15) / 16 * 16;
+        return at;
+    }
+};
+// Refit::d_verts of at least `bytes`.  queued: the last queued refit may still read it on `deform`, which is waited for before it grows.
+static int32_t ensure_verts(ft_context* c, size_t bytes, bool queued) {
+    if (queued && c->refit.d_verts.bytes < std::max<size_t>(bytes, 16) && c->geo.deform) FT_HIP(c, hipStreamSynchronize(c->geo.deform));
+    return ensure(c, c->refit.d_verts, bytes);
 }
 
 // Morph targets and skinning on one device of the context: the vertices of every `on_device` edit made in d_verts at
@@ -905,14 +929,15 @@ static int32_t snapshot_records(ft_context* c, const fth::FlatScene& f, const st
 // ft_sg_set_mesh_targets call (ms[0] += that upload).  Only d_verts is written, which no frame reads, so queued frames go on.  lead:
 // the context's first device, which also scans every blended mesh, bit for bit fth::scan_mesh, into the edit (ms[1] += blend, scan
 // and readback).  The others' blends are left queued on their streams: their refit_device follows on the same stream.
-static int32_t morph_device(ft_context* c, const fth::SceneGraph& g, std::vector<DeformedMesh>& edits, double ms[2], bool lead) {
+static int32_t morph_device(ft_context* c, const fth::SceneGraph& g, std::vector<DeformedMesh>& edits, double ms[2], bool lead, Stager* stage = nullptr) {
     using clock = std::chrono::steady_clock;
     auto since = [](clock::time_point t0) { return std::chrono::duration<double, std::milli>(clock::now() - t0).count(); };
     int32_t rc;
     FT_HIP(c, hipSetDevice(c->device));
     ft_context::Morph& M = c->morph;
     const auto t0 = clock::now();
-    if ((rc = ensure(c, c->refit.d_verts, verts_doubles(g, edits) * 8)) != FT_OK) return rc;
+    const hipStream_t on = stage ? c->geo.deform : c->stream;
+    if ((rc = ensure_verts(c, verts_doubles(g, edits) * 8, stage != nullptr)) != FT_OK) return rc;
     bool uploaded = false;
     size_t blocks = 1, n_scans = 0;
     std::vector<std::vector<double>> staged;                        // slot-major weights, until the stream has taken them
@@ -933,22 +958,22 @@ static int32_t morph_device(ft_context* c, const fth::SceneGraph& g, std::vector
                 std::vector<double>& w = staged.back();
                 for (size_t k = 0; k < corners; ++k) for (size_t j = 0; j < J; ++j) w[j * corners + k] = n.skin_weight[k * J + j];
                 if (corners) {
-                    FT_HIP(c, hipMemcpyAsync(s->d_index.p, n.skin_index.data(), corners * 4, hipMemcpyHostToDevice, c->stream));
-                    FT_HIP(c, hipMemcpyAsync(s->d_weight.p, w.data(), J * corners * 8, hipMemcpyHostToDevice, c->stream));
+                    FT_HIP(c, hipMemcpyAsync(s->d_index.p, n.skin_index.data(), corners * 4, hipMemcpyHostToDevice, on));
+                    FT_HIP(c, hipMemcpyAsync(s->d_weight.p, w.data(), J * corners * 8, hipMemcpyHostToDevice, on));
                 }
                 s->skin_serial = n.skin_serial; s->wstride = corners; s->used_skin = corners * 4 + J * corners * 8;
                 uploaded = true;
             }
             if (!e.blended && s->rest_serial != n.shape_serial) {
                 if ((rc = ensure(c, s->d_rest, n.tris.size() * 8)) != FT_OK) return rc;
-                if (!n.tris.empty()) FT_HIP(c, hipMemcpyAsync(s->d_rest.p, n.tris.data(), n.tris.size() * 8, hipMemcpyHostToDevice, c->stream));
+                if (!n.tris.empty()) FT_HIP(c, hipMemcpyAsync(s->d_rest.p, n.tris.data(), n.tris.size() * 8, hipMemcpyHostToDevice, on));
                 s->rest_serial = n.shape_serial; s->used_rest = n.tris.size() * 8;
                 uploaded = true;
             }
             if ((rc = ensure(c, s->d_palette, n.palette.size() * 8)) != FT_OK) return rc;
-            FT_HIP(c, hipMemcpyAsync(s->d_palette.p, n.palette.data(), n.palette.size() * 8, hipMemcpyHostToDevice, c->stream));
+            FT_HIP(c, hipMemcpyAsync(s->d_palette.p, stage ? stage->put(n.palette.data(), n.palette.size() * 8) : n.palette.data(), n.palette.size() * 8, hipMemcpyHostToDevice, on));
             s->used_palette = n.palette.size() * 8;
-            uploaded = true;
+            if (!stage) uploaded = true;                            // (a queued call's palette left page-locked memory: the stream orders it, nothing is waited for)
         }
         if (!e.blended) continue;
         ft_context::Morph::Resident* r = nullptr;
@@ -958,15 +983,15 @@ static int32_t morph_device(ft_context* c, const fth::SceneGraph& g, std::vector
             const size_t count = n.base.size(), stride = count + (count & 1);
             if ((rc = ensure(c, r->d, (size_t)(n.n_targets + 1) * stride * 8)) != FT_OK) return rc;
             if (count) {
-                FT_HIP(c, hipMemcpyAsync(r->d.p, n.base.data(), count * 8, hipMemcpyHostToDevice, c->stream));
+                FT_HIP(c, hipMemcpyAsync(r->d.p, n.base.data(), count * 8, hipMemcpyHostToDevice, on));
                 for (int32_t k = 0; k < n.n_targets; ++k)
-                    FT_HIP(c, hipMemcpyAsync(r->d.as<double>() + (size_t)(k + 1) * stride, n.deltas.data() + (size_t)k * count, count * 8, hipMemcpyHostToDevice, c->stream));
+                    FT_HIP(c, hipMemcpyAsync(r->d.as<double>() + (size_t)(k + 1) * stride, n.deltas.data() + (size_t)k * count, count * 8, hipMemcpyHostToDevice, on));
             }
             r->serial = n.targets_serial; r->stride = stride; r->used = (size_t)(n.n_targets + 1) * count * 8;
             uploaded = true;
         }
     }
-    if (uploaded) FT_HIP(c, hipStreamSynchronize(c->stream));
+    if (uploaded) FT_HIP(c, hipStreamSynchronize(on));
     ms[0] += since(t0);
     const auto t1 = clock::now();
     if (lead && ((rc = ensure(c, M.d_partials, blocks * sizeof(ftk::MorphPartial))) != FT_OK || (rc = ensure(c, M.d_out, n_scans * sizeof(ftk::MorphScanOut))) != FT_OK)) return rc;
@@ -982,7 +1007,7 @@ static int32_t morph_device(ft_context* c, const fth::SceneGraph& g, std::vector
             ftk::MorphBlend a{};
             a.resident = r->d.as<double>(); a.out = out; a.count = n.tris.size(); a.stride = r->stride; a.n_targets = n.n_targets;
             for (int32_t k = 0; k < n.n_targets; ++k) a.w[k] = n.weights[(size_t)k];
-            ftk::morph_blend(c->stream, a);
+            ftk::morph_blend(on, a);
         }
         if (e.skinned) {                                            // behind the blend on the stream, in place; else from the rest shape
             const ft_context::Skin::Resident* s = nullptr;
@@ -990,16 +1015,16 @@ static int32_t morph_device(ft_context* c, const fth::SceneGraph& g, std::vector
             ftk::SkinPose a{};
             a.src = e.blended ? out : s->d_rest.as<double>(); a.out = out; a.index = s->d_index.as<uint32_t>(); a.weight = s->d_weight.as<double>();
             a.palette = s->d_palette.as<double>(); a.corners = n.tris.size() / 3; a.wstride = s->wstride; a.influences = n.skin_influences; a.n_bones = n.n_bones;
-            if (n.palette_kind == fth::GraphNode::DualQuaternions) ftk::skin_dq(c->stream, a);   // (the palette holds 8 doubles per bone: DESIGN.md 16.6)
-            else ftk::skin(c->stream, a);
+            if (n.palette_kind == fth::GraphNode::DualQuaternions) ftk::skin_dq(on, a);   // (the palette holds 8 doubles per bone: DESIGN.md 16.6)
+            else ftk::skin(on, a);
         }
         // (one scan after the other on the stream: they share the partials)
-        if (lead) ftk::morph_scan(c->stream, out, (uint32_t)(n.tris.size() / 9), M.d_partials.as<ftk::MorphPartial>(), M.d_out.as<ftk::MorphScanOut>() + k_scan++);
+        if (lead) ftk::morph_scan(on, out, (uint32_t)(n.tris.size() / 9), M.d_partials.as<ftk::MorphPartial>(), M.d_out.as<ftk::MorphScanOut>() + k_scan++);
     }
     FT_HIP(c, hipGetLastError());
     if (lead && n_scans) {
-        FT_HIP(c, hipMemcpyAsync(out.data(), M.d_out.p, n_scans * sizeof(ftk::MorphScanOut), hipMemcpyDeviceToHost, c->stream));
-        FT_HIP(c, hipStreamSynchronize(c->stream));
+        FT_HIP(c, hipMemcpyAsync(out.data(), M.d_out.p, n_scans * sizeof(ftk::MorphScanOut), hipMemcpyDeviceToHost, on));
+        FT_HIP(c, hipStreamSynchronize(on));
         k_scan = 0;
         for (DeformedMesh& e : edits) {
             if (!e.on_device) continue;
@@ -1082,6 +1107,8 @@ static int32_t refit_device(ft_context* c, const fth::FlatScene& f, const fth::S
         const ftk::RefitMesh m = refit_ranges(f, e.mesh, 1e-7 * e.scan.extent + 1e-300);
         if (m.node_count) FT_HIP(c, hipMemsetAsync(R.d_arrived.as<uint32_t>() + m.node_first, 0, (size_t)m.node_count * 4, c->stream));
         ftk::refit_mesh(c->stream, A, m, R.d_verts.as<double>() + e.at);
+        // (the live geometry set now holds this call's refit of the mesh: the other sets are behind it)
+        if (!c->geo.sets.empty() && e.mesh < c->geo.sets[(size_t)c->geo.live].wrote.size()) c->geo.sets[(size_t)c->geo.live].wrote[e.mesh] = ++c->geo.serial;
     }
     FT_HIP(c, hipGetLastError());
     FT_HIP(c, hipStreamSynchronize(c->stream));
@@ -1100,6 +1127,8 @@ static int32_t refit_device(ft_context* c, const fth::FlatScene& f, const fth::S
         if (!plan.rebuild[k]) continue;
         uint32_t height = 0;
         if ((rc = rebuild_in_place(c, f, *j, &height)) != FT_OK) return rc;
+        // (every other geometry set holds the old tree's child words: the next queued call that picks one carries the mesh over whole)
+        for (size_t k2 = 0; k2 < c->geo.sets.size(); ++k2) if ((int)k2 != c->geo.live && mesh < c->geo.sets[k2].wrote.size()) c->geo.sets[k2].wrote[mesh] = ~0ull;
         plan.tallest = std::max(plan.tallest, height);
         if (lead) {
             ft_context::TreeQuality& q = c->tree_quality[mesh];
@@ -1258,7 +1287,7 @@ static int32_t plan_grid(ft_context* c, LightJob& j, uint64_t& bytes) {
     const uint32_t n = j.pair->n_tris;
     int32_t rc;
     if ((rc = ensure(c, ebox, (size_t)n * 20)) != FT_OK) return rc;
-    const double* tris = c->d_scene[kTris].as<double>() + 9 * (size_t)j.pair->first_tri;
+    const double* tris = geo_array(c, kTris).as<double>() + 9 * (size_t)j.pair->first_tri;
     uint32_t* small = L.d_small.as<uint32_t>();                     // [0] Ru, [1] Rv, [2] the fullest cell, [4 ..] eight 64-bit sums
     unsigned long long* sums = reinterpret_cast<unsigned long long*>(small + 4);
     FT_HIP(c, hipMemsetAsync(small, 0, 128, c->stream));
@@ -1331,7 +1360,7 @@ static int32_t rebuild_light_space(ft_context* c, fth::FlatScene& f, const ft_co
     ms[0] += since(t0);
     const auto t1 = clock::now();
     if (B[kLsNodes].bytes < L.node_words * 4 || B[kLsTris].bytes < L.tri_doubles * 8 || L.node_words < T.base_node_words + L.block_words_here || L.tri_doubles < T.base_tri_doubles ||
-        B[kTris].bytes < f.tris.size() * 8) { c->err = std::string(who) + ": a scene array in device memory is smaller than the flattened one"; return FT_ERR_STATE; }
+        geo_array(c, kTris).bytes < f.tris.size() * 8) { c->err = std::string(who) + ": a scene array in device memory is smaller than the flattened one"; return FT_ERR_STATE; }
     bool regrid = relay;                                            // a light turned: the region behind the full commit's arrays is laid out anew, be it to nothing
     if (retrees && L.block_words_here != T.block_words) {
         // "light_space_retree", this device's first retree since the full commit: the blocks take their place behind that commit's nodes.
@@ -1362,13 +1391,13 @@ static int32_t rebuild_light_space(ft_context* c, fth::FlatScene& f, const ft_co
             if (ftk::ls_sort_pairs(c->stream, nullptr, nullptr, nullptr, nullptr, n, nullptr, &sort_bytes) != hipSuccess) { c->err = std::string(who) + ": sizing the sort failed"; return FT_ERR_HIP; }
             if ((rc = ensure(c, L.d_keys, (size_t)n * 12)) != FT_OK || (rc = ensure(c, L.d_sort, sort_bytes)) != FT_OK) return rc;
             uint32_t* keys = L.d_keys.as<uint32_t>();               // n keys, n sorted keys, n values
-            ftk::ls_morton_keys(c->stream, B[kTris].as<double>(), (uint32_t)(f.tris.size() / 9), j.pair->first_tri, n, j.frame, j.pair->R, keys, keys + 2 * (size_t)n);
+            ftk::ls_morton_keys(c->stream, geo_array(c, kTris).as<double>(), (uint32_t)(f.tris.size() / 9), j.pair->first_tri, n, j.frame, j.pair->R, keys, keys + 2 * (size_t)n);
             if (ftk::ls_sort_pairs(c->stream, keys, keys + n, keys + 2 * (size_t)n, L.d_src.as<uint32_t>() + j.pair->src_at, n, L.d_sort.p, &sort_bytes) != hipSuccess) {
                 c->err = std::string(who) + ": the sort failed"; return FT_ERR_HIP;
             }
         }
         if ((j.gather || sorts) && j.pair->src_at + (size_t)j.pair->n_tris <= T.src.size()) {
-            ftk::ls_gather(c->stream, B[kTris].as<double>(), (uint32_t)(f.tris.size() / 9), j.pair->first_tri, j.pair->n_tris, L.d_src.as<uint32_t>() + j.pair->src_at, j.pair->n_tris,
+            ftk::ls_gather(c->stream, geo_array(c, kTris).as<double>(), (uint32_t)(f.tris.size() / 9), j.pair->first_tri, j.pair->n_tris, L.d_src.as<uint32_t>() + j.pair->src_at, j.pair->n_tris,
                            B[kLsTris].as<double>(), n_tris, j.pair->ls_first);
             L.rewritten = true;
         }
@@ -1420,7 +1449,7 @@ static int32_t rebuild_light_space(ft_context* c, fth::FlatScene& f, const ft_co
         for (const LightJob& j : jobs) {
             if (!j.grid) continue;
             const uint32_t n = j.pair->n_tris, cells = j.nu * j.nv;
-            const double* mesh = B[kTris].as<double>() + 9 * (size_t)j.pair->first_tri;
+            const double* mesh = geo_array(c, kTris).as<double>() + 9 * (size_t)j.pair->first_tri;
             size_t scan_bytes = 0;
             if (ftk::ls_grid_scan(c->stream, nullptr, nullptr, cells, nullptr, &scan_bytes) != hipSuccess) { c->err = std::string(who) + ": sizing the scan failed"; return fail(FT_ERR_HIP); }
             DeviceBuf& ebox = L.d_ebox[j.slot];
@@ -1616,6 +1645,171 @@ static void note_pose_call(ft_context* c, bool lights, int64_t why) {
     c->pose.counts[7] = pending;
 }
 
+// ------------------------------------------------------------------------------------------ queued deforms (ft_scene_commit_deformed_enqueue)
+// Does a pending frame or a queued temporal call hold geometry set k?  (From the host's view, as pose_set_held.)
+static bool geo_set_held(const ft_context* c, int k) {
+    for (const ft_context::FrameSlot& F : c->slots) if (F.pending && F.geo_set == k) return true;
+    const ft_context::Temporal& T = c->temporal;
+    for (int q = 1; q <= T.q_pending; ++q) if (T.queue[(T.q_turn + ft_context::Temporal::kQueue - q) % ft_context::Temporal::kQueue].geo_set == k) return true;
+    return false;
+}
+
+// A further geometry set with set 0's sizes, filled on `deform` by one device-to-device copy of the live set: the topology, and every
+// mesh as the live set holds it.  The first call makes the entry that stands for set 0 instead.
+static int32_t add_geo_set(ft_context* c, size_t n_meshes) {
+    ft_context::GeoSets& G = c->geo;
+    const bool first = G.sets.empty();
+    G.sets.emplace_back();
+    ft_context::GeoSets::Set& S = G.sets.back();
+    const auto fail = [&](int32_t rc) { S.release(); G.sets.pop_back(); return rc; };
+    if (hipEventCreateWithFlags(&S.ready, hipEventDisableTiming) != hipSuccess) { c->err = "a geometry set's event could not be made"; return fail(FT_ERR_HIP); }
+    if (first) { S.wrote.assign(n_meshes, 0); return FT_OK; }
+    int32_t rc;
+    for (int a = 0; a < ft_context::kGeoArrayCount; ++a) {
+        const DeviceBuf& from = geo_array(c, kGeoArrays[a]);
+        if ((rc = ensure(c, S.buf[a], c->d_scene[kGeoArrays[a]].bytes)) != FT_OK) return fail(rc);
+        if (from.bytes != S.buf[a].bytes || hipMemcpyAsync(S.buf[a].p, from.p, from.bytes, hipMemcpyDeviceToDevice, G.deform) != hipSuccess) {
+            c->err = "a geometry set could not be filled from the live one"; return fail(FT_ERR_HIP);
+        }
+    }
+    S.wrote = G.sets[(size_t)G.live].wrote;
+    return FT_OK;
+}
+
+// What a queued call needs before its first launch: the stream, the staging block's event, and the page-locked block itself with room
+// for `bytes` - grown only once `deform` has been waited for, written again only behind the event of the copies that last read it.
+static int32_t stage_begin(ft_context* c, size_t bytes, Stager& st) {
+    ft_context::GeoSets& G = c->geo;
+    FT_HIP(c, hipSetDevice(c->device));
+    if (!G.deform) FT_HIP(c, hipStreamCreateWithFlags(&G.deform, hipStreamNonBlocking));
+    if (!G.staged) FT_HIP(c, hipEventCreateWithFlags(&G.staged, hipEventDisableTiming));
+    if (G.staging_bytes < bytes) {
+        FT_HIP(c, hipStreamSynchronize(G.deform));
+        if (G.staging) FT_HIP(c, hipHostFree(G.staging));
+        G.staging = nullptr; G.staging_bytes = 0; G.staged_used = false;
+        FT_HIP(c, hipHostMalloc(reinterpret_cast<void**>(&G.staging), bytes, hipHostMallocDefault));
+        G.staging_bytes = bytes;
+    }
+    if (G.staged_used) FT_HIP(c, hipEventSynchronize(G.staged));
+    st.base = G.staging; st.used = 0; st.cap = G.staging_bytes;
+    return FT_OK;
+}
+// The bytes a queued call passes through the staging block: the palettes of the meshes skinned on the device, the vertices the host made.
+static size_t stage_bytes(const fth::SceneGraph& g, const std::vector<DeformedMesh>& edits) {
+    size_t n = 0;
+    for (const DeformedMesh& e : edits) {
+        const fth::GraphNode& node = g.nodes[(size_t)e.node];
+        if (e.skinned) n += (node.palette.size() * 8 + 15) / 16 * 16;
+        if (!e.on_device) n += (node.tris.size() * 8 + 15) / 16 * 16;
+    }
+    return n;
+}
+
+// A queued deform on the context's one device: `f` is the held scene with the new cull records and leaves already in it, `g` the graph
+// with the new vertices; morph_device has made those of the `on_device` edits in d_verts, on `deform`.  Nothing is retired and no stream
+// a frame runs on is waited for.  The refit goes into a geometry set no pending frame or temporal call was given - the live one when
+// nothing holds it, else a free one, else a new one - after the ranges of the meshes it does not edit, where that set is behind the live
+// one, have been carried over (k_refit_carry); the new leaves and cull records go out as a queued pose commit's do; dev_scene is pointed at
+// the set, and every stream that launches scene-reading kernels waits for the refit before its next launch.  ms[0] += the host time.
+static int32_t deform_enqueue_device(ft_context* c, const fth::FlatScene& f, const fth::SceneGraph& g, const std::vector<DeformedMesh>& edits, Stager& st, double ms[2]) {
+    using clock = std::chrono::steady_clock;
+    int32_t rc;
+    FT_HIP(c, hipSetDevice(c->device));
+    const auto t0 = clock::now();
+    ft_context::GeoSets& G = c->geo;
+    ft_context::Refit& R = c->refit;
+    const DeviceBuf* B = c->d_scene;
+    static_assert(sizeof(ftd::BspNode) % 8 == 0 && (ftd::kWideNodeDoubles * 8) % 8 == 0, "k_refit_carry copies 8-byte elements at the least");
+    if (B[kNodes].bytes < f.nodes.size() * sizeof(ftd::BspNode) || B[kTris].bytes < f.tris.size() * 8 || B[kWide].bytes < f.wide.size() * 8 ||
+        B[kCoarse].bytes < f.coarse_boxes.size() * 4 || R.d_arrived.bytes < f.nodes.size() * 4) {
+        c->err = "ft_scene_commit_deformed_enqueue: a scene array in device memory is smaller than the flattened one"; return FT_ERR_STATE;
+    }
+    if (G.sets.empty() && (rc = add_geo_set(c, f.meshes.size())) != FT_OK) return rc;   // set 0's entry
+    for (ft_context::GeoSets::Set& S : G.sets) if (S.wrote.size() != f.meshes.size()) { c->err = "ft_scene_commit_deformed_enqueue: the geometry sets are another scene's"; return FT_ERR_STATE; }
+    // 1. The set, by the rule of the pose sets (pose_enqueue_device).
+    int pick = -1;
+    for (;;) {
+        if (!geo_set_held(c, G.live)) pick = G.live;
+        for (int k = 0; pick < 0 && k < (int)G.sets.size(); ++k) if (!geo_set_held(c, k)) pick = k;
+        if (pick >= 0) break;
+        if ((int)G.sets.size() < G.max_sets) { if ((rc = add_geo_set(c, f.meshes.size())) != FT_OK) return rc; pick = (int)G.sets.size() - 1; break; }
+        ++G.counts[5];
+        if ((rc = any_pending(c) ? retire_oldest_frame(c) : retire_oldest_temporal(c)) != FT_OK) return rc;
+    }
+    ft_context::GeoSets::Set& S = G.sets[(size_t)pick];
+    const ft_context::GeoSets::Set& L = G.sets[(size_t)G.live];
+    const auto buf_of = [&](int set, int a) -> const DeviceBuf& { return set == 0 ? c->d_scene[kGeoArrays[a]] : G.sets[(size_t)set].buf[a]; };
+    // 2. The stale meshes: live -> picked, every range a refit writes (a mesh this call edits has them all written below - unless the
+    // live set's tree is another one, rebuilt in place since: then its topology comes over first).
+    std::vector<uint8_t> edited(f.meshes.size(), 0);
+    for (const DeformedMesh& e : edits) edited[e.mesh] = 1;
+    ftk::CarryTable table{};
+    const auto flush = [&] { if (table.n) ftk::refit_carry(G.deform, table); table.n = 0; };
+    int64_t carried = 0;
+    for (uint32_t m = 0; pick != G.live && m < (uint32_t)f.meshes.size(); ++m) {
+        if (S.wrote[m] == L.wrote[m] || (edited[m] && S.wrote[m] != ~0ull) || f.meshes[m].root >= 0) continue;
+        const ftk::RefitMesh r = refit_ranges(f, m, 0.0);
+        // array of kGeoArrays, first byte, bytes: nodes, list-order records, sorted copies, 4-wide nodes, coarse boxes
+        const uint64_t spans[5][3] = {{0, (uint64_t)r.node_first * sizeof(ftd::BspNode), (uint64_t)r.node_count * sizeof(ftd::BspNode)},
+                                      {1, (uint64_t)r.first_global * 72, (uint64_t)r.n * 72}, {1, (uint64_t)r.tri_first * 72, (uint64_t)r.tri_count * 72},
+                                      {2, (uint64_t)r.wide_first * ftd::kWideNodeDoubles * 8, (uint64_t)r.wide_count * ftd::kWideNodeDoubles * 8},
+                                      {3, (uint64_t)r.coarse_first * 24, (uint64_t)r.coarse_count * 24}};
+        if (table.n + 5 > (uint32_t)ftk::kCarryRanges) flush();
+        for (const auto& sp : spans) {
+            if (sp[2] == 0) continue;
+            const DeviceBuf& from = buf_of(G.live, (int)sp[0]);
+            const DeviceBuf& to = buf_of(pick, (int)sp[0]);
+            if (sp[1] + sp[2] > from.bytes || sp[1] + sp[2] > to.bytes) { c->err = "ft_scene_commit_deformed_enqueue: a mesh's range lies outside its array"; return FT_ERR_STATE; }
+            table.r[table.n++] = ftk::CarryRange{static_cast<const char*>(from.p) + sp[1], static_cast<char*>(to.p) + sp[1], sp[2]};
+            ++carried;
+        }
+        S.wrote[m] = L.wrote[m];
+    }
+    flush();
+    G.counts[6] = carried;
+    // 3. The vertices the host made, through the staging block, beside the ones morph_device left in d_verts.
+    if ((rc = ensure_verts(c, verts_doubles(g, edits) * 8, true)) != FT_OK) return rc;   // (no larger than what a blend has already written into)
+    for (const DeformedMesh& e : edits) {
+        if (e.on_device) continue;
+        const std::vector<double>& v = g.nodes[(size_t)e.node].vertices();
+        if (!v.empty()) FT_HIP(c, hipMemcpyAsync(R.d_verts.as<double>() + e.at, st.put(v.data(), v.size() * 8), v.size() * 8, hipMemcpyHostToDevice, G.deform));
+    }
+    if (st.used) { FT_HIP(c, hipEventRecord(G.staged, G.deform)); G.staged_used = true; }
+    // 4. The new leaves, cull records and cull image: a queued pose commit's steps (the serial, the signatures and the level hint with them).
+    double pose_ms[2] = {0.0, 0.0};                                 // (its host time is part of this call's, taken below)
+    if ((rc = pose_enqueue_device(c, f, true, pose_ms, "ft_scene_commit_deformed_enqueue")) != FT_OK) return rc;
+    // 5. The refit, with the four arrays it rewrites taken from the picked set; `arrived` and `leaf_boxes` are scratch the stream orders.
+    ftk::RefitArrays A = refit_arrays(c);
+    A.nodes = buf_of(pick, 0).as<ftd::BspNode>(); A.tris = buf_of(pick, 1).as<double>(); A.wide = buf_of(pick, 2).as<double>(); A.coarse = buf_of(pick, 3).as<float>();
+    for (const DeformedMesh& e : edits) {
+        const ftk::RefitMesh m = refit_ranges(f, e.mesh, 1e-7 * e.scan.extent + 1e-300);
+        if (m.node_count) FT_HIP(c, hipMemsetAsync(R.d_arrived.as<uint32_t>() + m.node_first, 0, (size_t)m.node_count * 4, G.deform));
+        ftk::refit_mesh(G.deform, A, m, R.d_verts.as<double>() + e.at);
+        S.wrote[e.mesh] = ++G.serial;
+    }
+    FT_HIP(c, hipGetLastError());
+    FT_HIP(c, hipEventRecord(S.ready, G.deform));
+    // 6. Live: dev_scene's four pointers, and every stream that launches kernels that read the scene behind the refit (`tail` reads no scene array).
+    ftk::DevScene& D = c->dev_scene;
+    D.nodes = A.nodes; D.tris = A.tris; D.wide = A.wide; D.coarse_boxes = A.coarse;
+    G.live = pick;
+    FT_HIP(c, hipStreamWaitEvent(c->stream, S.ready, 0));
+    for (hipStream_t m : c->more_mains) if (m) FT_HIP(c, hipStreamWaitEvent(m, S.ready, 0));
+    if (c->side) FT_HIP(c, hipStreamWaitEvent(c->side, S.ready, 0));
+    ms[0] += std::chrono::duration<double, std::milli>(clock::now() - t0).count();
+    return FT_OK;
+}
+
+// What ft_debug_deform_queue reports of one call: why it took the blocking path, or 0, and what the host still had pending on the first
+// device when it returned.
+static void note_deform_call(ft_context* c, int64_t why) {
+    int64_t* n = c->geo.counts;
+    ++n[why == 0 ? 0 : 1]; n[2] = why;
+    int64_t pending = c->temporal.q_pending;
+    for (const ft_context::FrameSlot& F : c->slots) pending += F.pending ? 1 : 0;
+    n[4] = pending;
+}
+
 // ft_scene_commit_moved under "moved_in_place".  FT_OK with *in_place false: the re-flatten differs in more than poses and nothing was
 // changed - the caller takes the full commit.
 // `queue` (ft_scene_commit_moved_enqueue): when no light-space pair's frame changed the poses are queued instead (pose_enqueue_device) and
@@ -1753,7 +1947,10 @@ int32_t ft_debug_moved_commits(ft_context* c, int64_t out[4]) {
 
 // The commit of a graph whose mesh vertices alone changed (ft_sg_set_mesh_triangles): the trees keep their topology and are refit on the
 // device (ft_refit.hip); the temporal accumulation stays open and the pose counter stays, a progressive accumulation ends.
-int32_t ft_scene_commit_deformed(ft_context* c) {
+// `queue`: ft_scene_commit_deformed_enqueue - the same call, rule for rule, but nothing is retired and no stream a frame
+// runs on is waited for: the refit goes into a geometry set no frame in flight reads (deform_enqueue_device).  A call that cannot be
+// queued goes on as the blocking one; ft_debug_deform_queue says why.
+static int32_t commit_deformed(ft_context* c, bool queue) {
     if (!c) return FT_ERR_INVALID;
     if (!c->holds_commit) { c->err = "ft_scene_commit_deformed: no committed scene to deform (ft_scene_commit)"; return FT_ERR_STATE; }
     if (c->restructured) { c->err = "ft_scene_commit_deformed: the graph, the root or the lights changed since the commit (ft_scene_commit)"; return FT_ERR_STATE; }
@@ -1815,6 +2012,31 @@ int32_t ft_scene_commit_deformed(ft_context* c) {
         n_skinned += skinned && !dq ? 1 : 0; n_skinned_dq += skinned && dq ? 1 : 0;
         edits.push_back(e);
     }
+    // Why a queued call takes the blocking path (include/functracer_hip.h): decided before anything is changed or launched.
+    int64_t why = 0;
+    if (queue) {
+        const bool ls_kept = c->opt.deform_light_space != 0 && c->graph.light_space_shadows != 0;
+        if (c->host_only) why = 1;
+        else if (!c->peers.empty()) why = 2;
+        else if (!c->refit.ready) why = 3;
+        else if (c->opt.refit_rebuild_percent > 0) why = 4;
+        else if (ls_kept) {                                         // an edited mesh with a pair that still has its tree gets a light-space job, below
+            if (!c->lightspace.ready) derive_light_space_tables(f, c->lightspace);
+            std::vector<uint8_t> is_edited(f.meshes.size(), 0);
+            for (const DeformedMesh& e : edits) is_edited[e.mesh] = 1;
+            std::vector<uint8_t> keeps(f.leaves.size(), 1);       // (a leaf with a pair that cannot be refit is stripped instead: no job)
+            for (const ft_context::LightSpace::Pair& P : c->lightspace.pairs) if (P.ls_first == ~0u) keeps[P.leaf] = 0;
+            for (const ft_context::LightSpace::Pair& P : c->lightspace.pairs)
+                if (f.leaves[P.leaf].ls_pairs != ~0u && keeps[P.leaf] && P.mesh < is_edited.size() && is_edited[P.mesh]) why = 5;
+        }
+        if (why == 0 && c->opt.temporal_follow_deformed && c->temporal.open && c->temporal.calls > 0) why = 6;
+    }
+    const bool queues = queue && why == 0;
+    Stager stager;
+    if (queues) { const int32_t src = stage_begin(c, stage_bytes(c->graph, edits), stager); if (src != FT_OK) return src; }
+    // (the blocking call's blend and refit share d_verts and the scan's scratch with the queued calls' stream)
+    else if (!c->host_only && c->geo.deform) { FT_HIP(c, hipSetDevice(c->device)); FT_HIP(c, hipStreamSynchronize(c->geo.deform)); }
+    c->geo.counts[6] = 0;
     double morph_ms[2] = {0.0, 0.0};                                // uploads, kernels with their readbacks
     ft_context::Morph& M = c->morph;
     M.counts[1] = (int64_t)n_blended;
@@ -1825,7 +2047,7 @@ int32_t ft_scene_commit_deformed(ft_context* c) {
         if (n_skinned) ++c->skin.counts[0];
         if (n_skinned_dq) ++c->skin.counts_dq[0];
         for (ft_context* d : devices(c)) {
-            const int32_t mrc = morph_device(d, c->graph, edits, morph_ms, d == c);
+            const int32_t mrc = morph_device(d, c->graph, edits, morph_ms, d == c, queues ? &stager : nullptr);
             if (mrc != FT_OK) { if (d != c) c->err = d->err; return mrc; }   // (only d_verts has been written: the old commit stands)
         }
     }
@@ -1838,7 +2060,9 @@ int32_t ft_scene_commit_deformed(ft_context* c) {
     for (const DeformedMesh& e : edits) if (e.on_device && !e.scan.finite) return refuse(false);
     if (c->host_only) {                                             // the same rules; the commit itself is the full one
         progressive_close(c);
-        return commit_scene(c);
+        const int32_t hrc = commit_scene(c);
+        if (hrc == FT_OK && queue) note_deform_call(c, why);
+        return hrc;
     }
     // "deform_light_space": the pairs' tables, off `f` as the full commit left it - before anything in it changes
     const bool keep_ls = c->opt.deform_light_space != 0 && c->graph.light_space_shadows != 0;
@@ -1904,7 +2128,8 @@ int32_t ft_scene_commit_deformed(ft_context* c) {
     c->commit_ms[0] = std::chrono::duration<double, std::milli>(clock::now() - t0).count() - morph_ms[0] - morph_ms[1];
     double ms[2] = {morph_ms[0], morph_ms[1]};
     RebuildPlan plan;
-    for (ft_context* d : devices(c)) {                              // every device refits its own copy
+    if (queues) rc = deform_enqueue_device(c, f, c->graph, edits, stager, ms);   // (one device, no light-space job, no rebuild: the reasons above)
+    else for (ft_context* d : devices(c)) {                         // every device refits its own copy
         if ((rc = refit_device(d, f, c->graph, edits, ms, d == c, plan)) != FT_OK) { if (d != c) c->err = d->err; break; }
         // behind the refit, which has written the list-order records the gather and the grid passes read
         if (!jobs.empty() && (rc = rebuild_light_space(d, f, T, jobs, grids, d == c, ms, "ft_scene_commit_deformed")) != FT_OK) { if (d != c) c->err = d->err; break; }
@@ -1921,8 +2146,11 @@ int32_t ft_scene_commit_deformed(ft_context* c) {
     c->commit_ms[1] = ms[1]; c->commit_ms[2] = ms[0];
     if (rc != FT_OK) { for (ft_context* d : devices(c)) d->committed = false; c->holds_commit = false; return rc; }   // HBM holds neither scene whole: ft_scene_commit
     for (fth::GraphNode& n : c->graph.nodes) n.deformed = false;
+    if (queue) note_deform_call(c, why);
     return FT_OK;
 }
+int32_t ft_scene_commit_deformed(ft_context* c) { return commit_deformed(c, false); }
+int32_t ft_scene_commit_deformed_enqueue(ft_context* c) { return commit_deformed(c, true); }
 
 // The commit of a graph whose lights alone changed (ft_scene_set_directional / _soft_directional / _positional): no flatten and no BVH
 // work.  The lights are uploaded again; every light-space pair whose direction changed gets its record derived again on the host, as

@@ -256,6 +256,7 @@ struct ft_context {
         uint64_t signature = 0;                 // what the frame rendered (scene, size, samples, depth, threshold): keys the staged-launch hint
         bool pending = false;
         int pose_set = 0;                       // the pose set its launches were given (PoseSets): held until the frame retires
+        int geo_set = 0;                        // the geometry set its launches were given (GeoSets): held until the frame retires
         uint64_t rays_primary = 0; int64_t n_pix_total = 0; int32_t spp = 0, n_launches = 0, n_chunks = 0, format = 0; bool classify = false;   // (n_launches, n_chunks: as planned from the request, FramePlan::n_planned)
         std::chrono::steady_clock::time_point wall0;
         void release() {
@@ -300,6 +301,49 @@ struct ft_context {
         void free_spares() { for (Set& s : sets) s.release(); sets.clear(); live = 0; }
         void release() { for (Set& s : sets) s.release(); sets.clear(); live = 0; if (copies) (void)hipStreamDestroy(copies); copies = nullptr; }
     } pose;
+    // ft_scene_commit_deformed_enqueue.  A geometry set is one copy in HBM of the arrays a refit rewrites - kGeoArrays: the
+    // nodes, the triangle records and their sorted copies, the 4-wide nodes, the coarse boxes - whole arrays, since DevScene has one pointer
+    // per array, and the event behind the last refit into it.  Set 0 IS d_scene[kGeoArrays] (its `buf` stay empty); the others are
+    // allocated on first need with set 0's sizes and filled by one device-to-device copy of the live set, kMaxSets at most in all.  Kept
+    // apart from the pose sets, each kind with its own `live`: a queued pose or light commit does not change which geometry is live, nor
+    // the reverse.  `live`: the set dev_scene points into - every launch from now on reads it, and every blocking call that reads or
+    // writes these arrays outside a launch goes through geo_array.  A frame slot or temporal queue slot names the set its launches were
+    // given; a set nothing pending names has no reader on the device.  wrote[m]: the serial of the queued or blocking call whose refit of
+    // mesh m the set holds (0: the full commit's tree) - a set that is behind the live one for a mesh the call does not edit has the
+    // mesh's ranges carried over first (k_refit_carry).  Freed by every full commit (upload_scene).
+    // `deform`: the queued calls' own stream - blend, skin, scan, carry, refit - which waits for nothing a frame does.  staging: the
+    // page-locked block palettes and host-made vertices pass through (the host's vectors are pageable and rewritten by the next call);
+    // `staged` lies behind its last copy, and it is written again only behind that event.
+    static constexpr int kGeoArrayCount = 4;
+    struct GeoSets {
+        static constexpr int kMaxSets = kSlots + FT_TEMPORAL_QUEUE_DEPTH + 1;
+        struct Set {
+            DeviceBuf buf[kGeoArrayCount];
+            hipEvent_t ready = nullptr;
+            std::vector<uint64_t> wrote;
+            void release() { for (DeviceBuf& b : buf) b.release(); if (ready) (void)hipEventDestroy(ready); ready = nullptr; wrote.clear(); }
+        };
+        std::vector<Set> sets;          // empty until the first queued call; sets[0] then stands for d_scene's own arrays
+        int live = 0;
+        hipStream_t deform = nullptr;
+        int max_sets = kMaxSets;        // (lowered only by a scratch build that tests the retirement branch)
+        char* staging = nullptr; size_t staging_bytes = 0;
+        hipEvent_t staged = nullptr; bool staged_used = false;
+        uint64_t serial = 0;            // the last value a Set::wrote entry was given
+        // ft_debug_deform_queue, on the context's first device: [0] calls queued, [1] calls that took the blocking path, [2] why the last
+        // one did, [4] frames + temporal calls pending when the last call returned, [5] frames or temporal calls retired because every
+        // set was held, [6] mesh ranges carried between sets in the last call ([3] is sets.size(), at least 1)
+        int64_t counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        // back to the scene's own arrays alone (nothing on the device reads or writes a spare: the caller has waited for `deform`)
+        void free_spares() { for (Set& s : sets) s.release(); sets.clear(); live = 0; }
+        void release() {
+            free_spares();
+            if (staging) (void)hipHostFree(staging);
+            if (staged) (void)hipEventDestroy(staged);
+            if (deform) (void)hipStreamDestroy(deform);
+            staging = nullptr; staging_bytes = 0; staged = nullptr; staged_used = false; deform = nullptr;
+        }
+    } geo;
     // ft_scene_commit_deformed's own tables in HBM (ftk::RefitArrays), made by the first refit after a full commit and kept until the next
     // one (`ready`); d_verts: the new vertices of the meshes being refit.
     struct Refit {
@@ -488,6 +532,7 @@ struct ft_context {
             std::vector<ftk::TemporalDeformLeaf> deform;
             int64_t n_pix = 0; int32_t n_launches = 0;
             int pose_set = 0;                   // the pose set its guide passes were given (PoseSets): held until the call retires
+            int geo_set = 0;                    // the geometry set they were given (GeoSets), held as long
             std::chrono::steady_clock::time_point wall0;
             void release() {
                 for (DeviceBuf* b : {&d_motion, &d_deform, &d_snap}) b->release();
@@ -570,6 +615,15 @@ constexpr SceneArray kPoseArrays[ft_context::kPoseArrayCount] = {kLeaves, kM2w, 
 inline DeviceBuf& pose_array(ft_context* c, SceneArray k) {
     if (c->pose.live == 0) return c->d_scene[k];
     for (int a = 0; a < ft_context::kPoseArrayCount; ++a) if (kPoseArrays[a] == k) return c->pose.sets[(size_t)c->pose.live].buf[a];
+    return c->d_scene[k];
+}
+
+// The arrays of a geometry set, in its order, and the buffer of the LIVE set that holds array k (one of kGeoArrays): what everything that
+// reads or writes them outside a launch takes, so that it meets what dev_scene points into.  Without a queued deform that is d_scene[k].
+constexpr SceneArray kGeoArrays[ft_context::kGeoArrayCount] = {kNodes, kTris, kWide, kCoarse};
+inline DeviceBuf& geo_array(ft_context* c, SceneArray k) {
+    if (c->geo.live == 0) return c->d_scene[k];
+    for (int a = 0; a < ft_context::kGeoArrayCount; ++a) if (kGeoArrays[a] == k) return c->geo.sets[(size_t)c->geo.live].buf[a];
     return c->d_scene[k];
 }
 

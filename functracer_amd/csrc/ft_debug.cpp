@@ -236,8 +236,9 @@ int32_t ft_debug_mesh_trees(ft_context* c, int64_t sizes[12], void* nodes, uint3
     auto get = [&](void* dst, SceneArray k, const void* host, size_t bytes) -> int32_t {
         if (!dst || bytes == 0) return FT_OK;
         if (c->host_only) { std::memcpy(dst, host, bytes); return FT_OK; }
-        if (c->d_scene[k].bytes < bytes) { c->err = "ft_debug_mesh_trees: a scene array in device memory is smaller than the flattened one"; return FT_ERR_STATE; }
-        FT_HIP(c, hipMemcpy(dst, c->d_scene[k].p, bytes, hipMemcpyDeviceToHost));
+        const DeviceBuf& b = geo_array(c, k);                       // (the live geometry set's where a refit rewrites the array)
+        if (b.bytes < bytes) { c->err = "ft_debug_mesh_trees: a scene array in device memory is smaller than the flattened one"; return FT_ERR_STATE; }
+        FT_HIP(c, hipMemcpy(dst, b.p, bytes, hipMemcpyDeviceToHost));
         return FT_OK;
     };
     int32_t rc;
@@ -330,6 +331,15 @@ int32_t ft_debug_pose_queue(ft_context* c, int64_t out[8]) {
     if (!c || !out) return FT_ERR_INVALID;
     for (int k = 0; k < 8; ++k) out[k] = c->pose.counts[k];
     out[6] = c->host_only ? 0 : std::max<int64_t>(1, (int64_t)c->pose.sets.size());
+    return FT_OK;
+}
+
+// What the queued deform commits did since ft_create (ft_context::GeoSets::counts), and the geometry sets the first device holds.
+int32_t ft_debug_deform_queue(ft_context* c, int64_t out[8]) {
+    if (!c || !out) return FT_ERR_INVALID;
+    for (int k = 0; k < 8; ++k) out[k] = c->geo.counts[k];
+    out[3] = c->host_only ? 0 : std::max<int64_t>(1, (int64_t)c->geo.sets.size());
+    out[7] = 0;
     return FT_OK;
 }
 

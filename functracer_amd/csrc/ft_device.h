@@ -243,6 +243,14 @@ struct RefitMesh {
 void refit_parents(hipStream_t stream, const RefitArrays& A, const RefitMesh& m);
 // verts: the mesh's new vertices in HBM, n x 9 doubles (a, b, c).  Records and sorted copies, boxes leaves to root, 4-wide slots, coarse boxes.
 void refit_mesh(hipStream_t stream, const RefitArrays& A, const RefitMesh& m, const double* verts);
+// Ranges of bytes copied from one geometry set to another (k_refit_carry, ft_scene_commit_deformed_enqueue): the ranges
+// of the meshes a queued refit does not edit, where the set it writes is behind the live one.  One launch copies every range of the
+// table, in 16-byte lanes with an 8-byte element at an unaligned end; src, dst and bytes are multiples of 8, src and dst congruent
+// modulo 16 (the same offset into two hipMalloc'ed arrays), and no two ranges of a table overlap.
+constexpr int kCarryRanges = 60;                                   // per launch: twelve meshes' five ranges
+struct CarryRange { const char* src; char* dst; uint64_t bytes; };
+struct CarryTable { uint32_t n, pad; CarryRange r[kCarryRanges]; };
+void refit_carry(hipStream_t stream, const CarryTable& t);
 // The surface-area cost of the mesh's binary tree as it lies in HBM (k_refit_cost), with A(box) = dx dy + dy dz + dz dx:
 //   ( sum over the real inner nodes of A(stored box) + sum over the leaves of n_tris x A(exact bound of the leaf's sorted records) ) / A(root's stored box),
 // 0 when the root's area is 0 or not finite.  Reads A.tris, A.nodes and A.leaves only (the refit's own tables may be null).  partials:

@@ -574,6 +574,7 @@ static int32_t queue_frame(ft_context* c, const RenderRequest& q, const FramePla
     F.signature = p.signature; F.simple = p.simple; F.main_ix = main_ix;
     F.pending = true; F.wall0 = wall0;
     F.pose_set = c->pose.live;                                     // every launch above was given dev_scene as it points now
+    F.geo_set = c->geo.live;
     F.rays_primary = 0;
     if (p.corner) for (auto& j : p.jobs) F.rays_primary += (uint64_t)j.n_ids * (uint64_t)p.spp;
     else F.rays_primary = (uint64_t)p.n_pix_total * (uint64_t)p.spp;   // the windows of a pixel list cover it, launched or not

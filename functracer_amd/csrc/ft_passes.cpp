@@ -470,7 +470,7 @@ static ftk::TemporalArgs temporal_args(ft_context* c, const ftk::GuideWindow& wi
     a.out_rgb = want_rgb ? T.d_rgb.as<double>() : nullptr; a.out8 = want_rgba8 ? T.d_rgba8.as<uint8_t>() : nullptr;
     a.counters = T.d_ctr.as<unsigned long long>();
     a.motion = rec.motion; a.n_leaves = (uint32_t)c->flat.leaves.size();
-    if (rec.deform) { a.deform = rec.deform; a.tris = c->d_scene[kTris].as<double>(); a.snap = rec.snap; }
+    if (rec.deform) { a.deform = rec.deform; a.tris = geo_array(c, kTris).as<double>(); a.snap = rec.snap; }
     a.box = box; a.clamped_history = (double)T.clamp.clamped_history;
     return a;
 }
@@ -904,6 +904,7 @@ static int32_t temporal_enqueue_single(ft_context* c, const RenderRequest& q, in
     temporal_advance(c, cam, moving);
     S.n_pix = n_pix; S.n_launches = n_launches; S.wall0 = wall0;
     S.pose_set = c->pose.live;                                      // the guide passes above were given dev_scene as it points now
+    S.geo_set = c->geo.live;
     T.q_turn = (T.q_turn + 1) % Temporal::kQueue; ++T.q_pending;
     return FT_OK;
 }

@@ -13,6 +13,8 @@
 //                    monotone in x), so a node's stored box is the exact bound of its triangles, inflated: what every builder stores
 //   k_refit_wide     per 4-wide node the inflated boxes of what its slots point to; empty slots stay all-NaN
 //   k_refit_coarse   one thread: the level of the tree with at most 64 nodes (the rule both builders use), as float boxes rounded outward
+// k_refit_carry copies ranges of these arrays from one geometry set to another (ft_scene_commit_deformed_enqueue): what
+// a queued refit does not write of a set that is behind the live one.
 // Beside them k_refit_cost / k_refit_cost_sum measure the surface-area cost of a tree as it lies in HBM (ft_scene_tree_quality, the
 // "refit_rebuild_percent" decision): one thread per node slot, a sum of fixed shape, no floating-point atomics.
 #include <hip/hip_runtime.h>
@@ -170,7 +172,35 @@ __global__ void k_refit_cost_sum(RefitArrays A, RefitMesh m, const double* __res
     *cost = cost_of_sum(A, m, sum);
 }
 
+// Range blockIdx.y of the table, the launch's blocks along x striding over its 16-byte lanes; the first thread also copies the 8-byte
+// element in front of the first whole lane and the one behind the last, where the range starts or ends between two lanes.
+__global__ __launch_bounds__(256) void k_refit_carry(CarryTable t) {
+    if (blockIdx.y >= t.n) return;
+    const CarryRange r = t.r[blockIdx.y];
+    const unsigned long long head = (16ull - ((unsigned long long)(uintptr_t)r.src & 15ull)) & 15ull;   // 0 or 8
+    if (r.bytes < head + 16ull) {                                   // no whole lane: at most two elements
+        if (blockIdx.x == 0u && threadIdx.x < r.bytes / 8ull) reinterpret_cast<double*>(r.dst)[threadIdx.x] = reinterpret_cast<const double*>(r.src)[threadIdx.x];
+        return;
+    }
+    const unsigned long long lanes = (r.bytes - head) / 16ull, tail = head + 16ull * lanes;
+    const double2* __restrict__ src = reinterpret_cast<const double2*>(r.src + head);
+    double2* __restrict__ dst = reinterpret_cast<double2*>(r.dst + head);
+    for (unsigned long long i = blockIdx.x * 256ull + threadIdx.x; i < lanes; i += gridDim.x * 256ull) dst[i] = src[i];
+    if (blockIdx.x == 0u && threadIdx.x == 0u) {
+        if (head) *reinterpret_cast<double*>(r.dst) = *reinterpret_cast<const double*>(r.src);
+        if (tail < r.bytes) *reinterpret_cast<double*>(r.dst + tail) = *reinterpret_cast<const double*>(r.src + tail);
+    }
+}
+
 } // namespace
+
+void refit_carry(hipStream_t stream, const CarryTable& t) {
+    if (t.n == 0u) return;
+    uint64_t most = 0;
+    for (uint32_t k = 0; k < t.n; ++k) most = most > t.r[k].bytes ? most : t.r[k].bytes;
+    const uint64_t blocks = (most / 16u + 255u) / 256u;             // the longest range's lanes, 256 blocks per range at most: the rest is strided
+    hipLaunchKernelGGL(k_refit_carry, dim3((uint32_t)(blocks < 1u ? 1u : (blocks > 256u ? 256u : blocks)), t.n), dim3(256), 0, stream, t);
+}
 
 void refit_cost(hipStream_t stream, const RefitArrays& A, const RefitMesh& m, double* partials, double* cost) {
     const uint32_t blocks = refit_cost_blocks(m);

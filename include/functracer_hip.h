@@ -1044,6 +1044,46 @@ int32_t ft_scene_commit_lights(ft_context* ctx);
  * 3.49 against 4.21 on hollow-sphere (3.48 with no commit). */
 int32_t ft_scene_commit_moved_enqueue(ft_context* ctx);
 int32_t ft_scene_commit_lights_enqueue(ft_context* ctx);
+/* ---- queued deform commits ---------------------------------------------------------------------- */
+/* ft_scene_commit_deformed_enqueue: ft_scene_commit_deformed without the drain, so that a host that poses a mesh every frame - set bones
+ * or weights, commit, ft_render_enqueue_into - keeps its frames in flight.
+ * The call is ft_scene_commit_deformed in every respect - the FT_ERR_STATE rules in their order; the FT_ERR_UNSUPPORTED refusals (depth
+ * above 0, a non-finite vertex, bounds that change which items have bounds), after each of which the old commit stays renderable; the
+ * progressive accumulation ended, the temporal one left open, the pose counter left; no kept classification matched afterwards; the
+ * ft_debug_morph / ft_debug_skin / ft_debug_skin_dq counters - with two differences:
+ *  1. Nothing queued is retired and no stream that frames run on is waited for.  Frames and temporal calls queued BEFORE the call show the
+ *     old vertices, the copies of ft_render_enqueue_into and the host_out of ft_temporal_enqueue included; everything queued or run AFTER
+ *     it is bit for bit what a fresh context built with the new vertices and committed with ft_scene_commit gives: frames, ft_stats
+ *     counters (times and the hint-dependent n_launches aside), ft_render_aov planes, the ft_debug_* ray queries, ft_debug_mesh_trees.
+ *     The host may wait for the call's own small stream - the readback of the bounds of vertices made on the device, a first-use upload
+ *     of a mesh's targets or skin - never for a frame.
+ *  2. A call that cannot be queued takes the blocking call's path, bits and draining; ft_debug_deform_queue's out[2] says why:
+ *       1  a host-only context;
+ *       2  a context over several devices;
+ *       3  the first refit since a full commit, which derives the refit's tables, records the trees' costs as built and strips the
+ *          light-space pairs: it stays blocking, once;
+ *       4  "refit_rebuild_percent" above 0: a rebuild rewrites topology behind a cost readback;
+ *       5  "deform_light_space" would give an edited mesh a light-space job, whose arrays are rewritten with readbacks;
+ *       6  "temporal_follow_deformed" with an open accumulation that has accumulated: its snapshot reads the records about to be replaced.
+ * Every kind of edit is queued: ft_sg_set_mesh_triangles, weights, matrix or dual-quaternion palettes alone or over weights, and their
+ * host twins under "morph_on_device" 0 / "skin_on_device" 0.
+ * Geometry sets.  What a refit rewrites - the scene's tree nodes (64 bytes each), its triangle records and their sorted copies (72 bytes
+ * each), its 4-wide nodes (224 bytes each) and the coarse boxes (24 bytes each), whole arrays - exists in up to 9 copies on the device
+ * (frame slots 4 + FT_TEMPORAL_QUEUE_DEPTH + 1), each made on first need by one device-to-device copy: for the 69.6 K-face mesh
+ * 10 MB of records per copy, and its nodes.  They are kept apart from the pose sets of the queued pose and light commits: neither kind of call changes which
+ * copy of the other kind is live.  A queued call refits into a copy that no pending frame or temporal call was given (the live one
+ * when nothing holds it), on a stream of its own that waits for nothing a frame does, after k_refit_carry has brought over the ranges
+ * of the meshes the call does not edit where that copy is behind the live one; the streams that launch scene-reading kernels wait
+ * for the refit before their next launch.  With every copy held and none left to make, the oldest pending frame or temporal call is
+ * retired.  The new leaves and cull records travel as a queued pose commit's do.  Every full commit frees all copies but the first.  A
+ * host that never calls this function has one copy, the scene's own arrays, and gets the launches and bytes it got before.
+ * ft_get_commit_times after a queued call: [0] the host's work, [1] the blend, skin and scan kernels with the host's wait for their
+ * readback (exactly 0 when every edit's vertices came from the host), [2] the host time to queue copies, carry and refit, [3] unchanged.
+ * A HIP failure once the refit is being queued leaves the context as a failed ft_scene_commit_deformed does: uncommitted until ft_scene_commit.
+ * Measured (MI355X, 1920 x 1080 x 16, a 64-bone palette, a commit and a queued RGBA8 frame per step): 0.87 ms per step
+ * against 1.08 with the blocking call on the 69.6 K-face mesh (0.34 with no commit at all: the host still waits for the readback of the
+ * new bounds, and a new pose needs its classification), 4.93 against 5.65 on hollow-sphere with a skinned tube. */
+int32_t ft_scene_commit_deformed_enqueue(ft_context* ctx);
 /* ---- history on deforming meshes ("temporal_follow_deformed") ----------------------------------- */
 /* Without the option the history of a deformed mesh survives only where its surface stayed within clause 2's position tolerance.  With
  * ft_set_option("temporal_follow_deformed", 1) the history follows the triangles, as it follows moved leaves:
@@ -1156,6 +1196,12 @@ int32_t ft_debug_moved_commits(ft_context* ctx, int64_t out[4]);
  * plus temporal calls the host still had pending on the first device when the last of the two calls returned.  FT_ERR_INVALID for null arguments;
  * works on a host-only context, where the queued counts stay 0. */
 int32_t ft_debug_pose_queue(ft_context* ctx, int64_t out[8]);
+/* The queued deform commits at work, for tests: since ft_create, out[0] = ft_scene_commit_deformed_enqueue calls queued without retiring
+ * anything, out[1] = calls that took the blocking path, out[2] = why the last call did (0: it was queued; the reasons are listed with the
+ * function), out[3] = geometry sets the first device holds (1: the scene's own arrays alone; 0 on a host-only context), out[4] = frames +
+ * temporal calls the host still had pending on the first device when the last call returned, out[5] = frames or temporal calls retired
+ * because every set was held, out[6] = mesh ranges k_refit_carry copied between sets in the last call, out[7] = 0. */
+int32_t ft_debug_deform_queue(ft_context* ctx, int64_t out[8]);
 /* "primary_mesh_kernel" at work, for tests: bounce-0 launches since ft_create, summed over the context's devices - out[0] of k_primary, out[1] of
  * k_primary_mesh.  FT_ERR_NO_DEVICE on a host-only context. */
 int32_t ft_debug_primary_kernels(ft_context* ctx, int64_t out[2]);
